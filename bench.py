@@ -48,11 +48,12 @@ def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=1,
                     help="the timed region (exactly --steps steps between barrier + synchronize) is run this many times; "
                          "value / ms_per_step are the MEDIAN repeat, every repeat is listed in repeats_ms")
-    ap.add_argument("--min-timed-seconds", type=float, default=2.0,
-                    help="repeat the timed region until the timed GPU work adds up to at least this (see --repeats)")
+    ap.add_argument("--min-timed-seconds", type=float, default=0.0,
+                    help="> 0: an untimed pilot region sizes the repeat count so that the timed GPU work adds up to at least "
+                         "this (see --repeats); the number of steps before --dump-outputs then depends on the timing")
     ap.add_argument("--max-repeats", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
@@ -84,6 +85,8 @@ def parse():
     ap.add_argument("--cpu-sample-steps", type=int, default=60)
     ap.add_argument("--cpu-eager-seconds", type=float, default=10.0,
                     help="wall-clock budget of the like-for-like eager CPU baseline (BASELINE.md B1); 0 = skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
     return ap.parse_args()
 
 
@@ -270,6 +273,8 @@ def main():
 
         prefetch(0)
 
+    last = [None]                                         # the (u, i, j) of the latest step, for --dump-outputs
+
     def one_step(s):
         if pipe:
             slot = state["n"] & 1
@@ -279,6 +284,7 @@ def main():
             u, i, j = bufs2[slot]
         else:
             u, i, j = sampler.sample(B, out=bufs) if batches is None else batches[s % nb]
+        last[0] = (u, i, j)
         if sharded is None:
             eng.step(u, i, j, want_loss=False)
         else:
@@ -299,27 +305,30 @@ def main():
     with torch.cuda.stream(run_stream):
         for s in range(W):
             one_step(s)
-        # Every timed region is EXACTLY K steps between barrier + synchronize.  A region of the driver's K = 20 is ~5 ms of
-        # GPU work, invisible to an outside utilisation sampler, so the region is repeated until the timed GPU work adds up to
-        # --min-timed-seconds (default 2 s): an untimed pilot region sizes the repeat count (the same on every rank: MAX over
-        # ranks), the median region is the one reported, every region is listed in repeats_ms.
-        barrier()
-        t0 = time.perf_counter()
-        for s in range(K):
-            one_step(W + s)
-        barrier()
-        pilot = time.perf_counter() - t0
-        if world > 1:
-            pt = torch.tensor([pilot], device="cpu" if rehearse else device, dtype=torch.float64)
-            dist.all_reduce(pt, op=dist.ReduceOp.MAX)
-            pilot = float(pt.item())
-        n_rep = max(1, args.repeats, int(np.ceil(args.min_timed_seconds / max(pilot, 1e-6))))
+        # Every timed region is EXACTLY K steps between barrier + synchronize; by default there is one, so --steps is the
+        # number of timed steps.  --repeats runs more regions (the median one is reported, every region is listed in
+        # repeats_ms); --min-timed-seconds > 0 adds an untimed pilot region that sizes the repeat count (the same on every
+        # rank: MAX over ranks) so that the timed GPU work adds up to at least that.
+        n_rep, first = max(1, args.repeats), W
+        if args.min_timed_seconds > 0:
+            barrier()
+            t0 = time.perf_counter()
+            for s in range(K):
+                one_step(W + s)
+            barrier()
+            pilot = time.perf_counter() - t0
+            if world > 1:
+                pt = torch.tensor([pilot], device="cpu" if rehearse else device, dtype=torch.float64)
+                dist.all_reduce(pt, op=dist.ReduceOp.MAX)
+                pilot = float(pt.item())
+            n_rep = max(n_rep, int(np.ceil(args.min_timed_seconds / max(pilot, 1e-6))))
+            first += K
         n_rep = min(n_rep, args.max_repeats)
         for rep in range(n_rep):
             barrier()
             t0 = time.perf_counter()
             for s in range(K):                                # EXACTLY K steps between barrier + synchronize
-                one_step(W + (rep + 1) * K + s)
+                one_step(first + rep * K + s)
             barrier()
             repeats.append(time.perf_counter() - t0)
     torch.cuda.current_stream().wait_stream(run_stream)
@@ -329,6 +338,8 @@ def main():
         repeats = [float(x) for x in tmax.tolist()]
     elapsed = float(np.median(repeats))                       # the median repeat is the reported one
     eng.sync_check()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, last[0], torch)
 
     # what this device's HBM delivers to a plain streaming-read kernel (bprx_probe_stream_read), on the launch stream
     measured_peak = measured_peak_nt = None
@@ -442,6 +453,38 @@ def main():
         print(json.dumps(out))
     if world > 1 or force_sharded:
         dist.destroy_process_group()
+
+
+DUMP_ROWS = 8192            # --dump-outputs: rows kept of a longer table
+DUMP_BATCH = 1 << 18        # --dump-outputs: entries kept of a longer index batch
+DUMP_BYTES = 64 << 20
+
+
+def _dump_rows(n, cap):
+    """A fixed, seeded, sorted sample of cap of range(n) (all of it when n <= cap): tables with the same row count (Gu and
+    Tu, Gi and Bi) keep the same rows."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.RandomState(0).choice(n, cap, replace=False))
+
+
+def dump_outputs(path, eng, batch, torch):
+    """What the timed path computed in its last step, as DIR/<name>.npy: the trained tables after that step (fp32; a
+    DUMP_ROWS-row sample of a longer table) and the step's index batch u, i, j as drawn by the sampler (float64, exact;
+    a DUMP_BATCH-entry sample of a longer batch).  This rank's tables only (its shard, N > 1)."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for n, t in eng.params().items():
+        rows = torch.as_tensor(_dump_rows(t.shape[0], DUMP_ROWS), device=t.device)
+        out[n] = t.index_select(0, rows).cpu().numpy().astype(np.float32)
+    for n, t in zip(("batch_user", "batch_pos", "batch_neg"), batch):
+        rows = torch.as_tensor(_dump_rows(t.numel(), DUMP_BATCH), device=t.device)
+        out[n] = t.reshape(-1).index_select(0, rows).cpu().numpy().astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_BYTES))
+    for n, a in out.items():
+        np.save(os.path.join(path, n + ".npy"), a)
 
 
 def hbm_stream_probe(torch, device, stream, nt=False):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One gpurun call: "name|ENV=1 ENV2=2|bench args" -> gpurun_out/bench_<name>.log and a one-line summary per spec.
 set -u
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 for spec in "$@"; do
   IFS='|' read -r name envs args <<< "$spec"

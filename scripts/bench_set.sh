@@ -1,7 +1,7 @@
 #!/bin/bash
 # scripts/bench_set.sh <outdir> : the default C2 line + one line per other workload into gpurun_out/<outdir>/ (one box)
 set -u
-cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
+R="$(cd "$(dirname "$0")/.." && pwd)"; cd /tmp && export TMPDIR=/tmp && cd "$R"
 O=gpurun_out/$1; mkdir -p $O
 t() { timeout -k 10 "$@"; local rc=$?; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "TIMEOUT: $*"; exit 1; fi; return 0; }
 summ() { python - "$1" <<'PY'

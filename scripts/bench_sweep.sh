@@ -1,7 +1,7 @@
 #!/bin/bash
 # One gpurun call: bench.py lines for a list of "name:args" workloads -> gpurun_out/bench_<name>.log (JSON line last).
 set -u
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 for spec in "$@"; do
   name=${spec%%:*}; args=${spec#*:}

@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU parity suite under the library's mode switches (one pytest process per setting, sequentially).
 set -u
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 SETTINGS=("BPRX_LIST_MODE=0" "BPRX_LIST_MODE=2" "BPRX_ITEM_MODE=0" "BPRX_ITEM_MODE=2" "BPRX_ADAM_LAZY=0" "BPRX_GRAPH=1" "BPRX_GRAPH=2" "BPRX_SIDE_STREAM=0" "BPRX_SIDE_STREAM=5")
 if [ -n "${MATRIX_ONLY:-}" ]; then SETTINGS=("BPRX_LIST_MODE=0" "BPRX_LIST_MODE=2" "BPRX_ITEM_MODE=0" "BPRX_ITEM_MODE=2" "BPRX_ADAM_LAZY=0" "BPRX_GRAPH=1" "BPRX_GRAPH=2" "BPRX_SIDE_STREAM=0" "BPRX_SIDE_STREAM=5")

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Runs on the GPU box via gpurun: parity tests, smoke, bench, rocprof.  Stops at the first TIMED-OUT GPU step.
 set -u
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 step() {  # name, timeout, cmd...

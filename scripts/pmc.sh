@@ -2,7 +2,7 @@
 # PMC passes (separate runs, counters only + kernel-trace) on the bench workload; summaries under gpurun_out/pmc*.
 # The program itself follows `--` (no env / shell hop): rocprofv3's preloaded library initialises the GPU first.
 set -u
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 ARGS="--steps 6 --warmup 2 --repeats 1 --no-cpu-baseline ${BENCH_ARGS:-}"

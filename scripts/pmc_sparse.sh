@@ -1,7 +1,7 @@
 #!/bin/bash
 # PMC passes for the sparse kernels (issue / wait breakdown): scripts/pmc_sparse.sh <name> <bench args...>
 set -u
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 name=$1; shift

@@ -1,7 +1,7 @@
 #!/bin/bash
 # rocprofv3 kernel stats of one bench.py invocation: scripts/prof_stats.sh <name> <bench args...>   (env passes through)
 set -u
-cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
+R="$(cd "$(dirname "$0")/.." && pwd)"; cd /tmp && export TMPDIR=/tmp && cd "$R"
 name=$1; shift
 mkdir -p gpurun_out
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$name -o $name -- python bench.py --no-cpu-baseline "$@" > gpurun_out/prof_$name.log 2>&1 || { echo "rocprof failed"; tail -5 gpurun_out/prof_$name.log; exit 1; }

@@ -3,7 +3,7 @@
 # --steps 20 --warmup 5), its rocprofv3 kernel stats, the PMC passes, the other workloads' bench lines, the forced-sharded
 # N=1 lines and the two-rank rehearsals.  The program itself follows `--` under rocprofv3 (no env / shell hop).
 set -u
-cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
+R="$(cd "$(dirname "$0")/.." && pwd)"; cd /tmp && export TMPDIR=/tmp && cd "$R"
 O=gpurun_out/r03; rm -rf $O; mkdir -p $O
 t() { timeout -k 10 "$@"; local rc=$?; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "TIMEOUT: $*"; exit 1; fi; return 0; }
 echo "== default bench (driver form)"; t 600 python bench.py --steps 20 --warmup 5 > $O/bench_c2.log 2>&1; grep '^{"metric"' $O/bench_c2.log | tail -1 > $O/bench_c2.json; cut -c1-300 $O/bench_c2.json

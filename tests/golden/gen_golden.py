@@ -2,16 +2,16 @@
 """One-off generator of the golden fixtures in tests/golden/ (run in the BUILD container only).
 
 It executes the two pieces of the reference hot path that run without TensorFlow,
-unmodified and read-only from /root/reference/src:
+unmodified and read-only from the reference checkout's src/ directory (the first argument):
   * DataLoader.all_triple_batches   (src/dataset/dataset.py:83-114)  -> index-stream fixtures
   * Evaluator.eval / store_recommendation (src/recommender/Evaluator.py:149-239) -> metric fixtures
 dataset.py line 3 does `import tensorflow as tf`; the sampled code never touches `tf`, so an EMPTY
 module object is registered under that name to let the import statement succeed (SURVEY 8(c) recipe).
 Nothing else of the reference is stubbed, and no reference source is copied: the outputs written here
-are data (inputs + expected outputs) only.  /root/reference does not exist on the GPU box; tests read
+are data (inputs + expected outputs) only.  The reference does not exist on the GPU box; tests read
 only the files this script wrote.
 
-    python tests/golden/gen_golden.py        # rewrites tests/golden/*.npz / *.json / *.tsv
+    python tests/golden/gen_golden.py <reference>/src     # rewrites tests/golden/*.npz / *.json / *.tsv
 """
 import hashlib
 import json
@@ -26,7 +26,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
-REF_SRC = "/root/reference/src"
+REF_SRC = None                                      # the reference's src/ directory (argv[1], set in __main__)
 sys.dont_write_bytecode = True
 sys.path.insert(0, REPO)
 
@@ -138,4 +138,7 @@ def main():
 
 
 if __name__ == "__main__":
+    if len(sys.argv) != 2 or not os.path.isdir(sys.argv[1]):
+        sys.exit("usage: python tests/golden/gen_golden.py <reference>/src")
+    REF_SRC = os.path.abspath(sys.argv[1])
     main()
