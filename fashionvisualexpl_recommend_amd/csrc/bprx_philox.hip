@@ -5,6 +5,8 @@
 //   positive p  = mulhi64(block(n,0).xy, N)  -> (pos_user[p], items_sorted[p])   uniform over training interactions
 //   negative j  = mulhi32(block(n,a).z, I), a = 0,1,.. until j is not a positive of the user (binary search in the
 //                 user's ascending item list; at most 1024 attempts)              uniform over non-positives
+//                 after 1024 positives in a row (a user holding nearly every item): the r-th non-positive of the user,
+//                 r = mulhi32(block(n,1024).z, M) over its M = I - #distinct(list) non-positives (an O(len) walk)
 // so any rank can regenerate any other rank's triplets, and the CPU twin (oracle/bpr_oracle.c orc_sample_philox)
 // is bit-exact.  One thread per triplet; 12 B written per triplet.
 #include <hip/hip_runtime.h>
@@ -24,6 +26,23 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
   }
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// The negative after 1024 rejections: the r-th (0-based) item that is not in the user's ascending list (which may repeat an
+// item), r = mulhi32(z, M) over the M = I - #distinct non-positives -- uniform over the non-positives like the rejection draw,
+// and never a positive.  Only users whose positives cover nearly every item get here.  M == 0 (every item a positive: the
+// samplers' constructors refuse such a user) keeps `last`.  CPU twin: nth_non_positive in oracle/bpr_oracle.c.
+__device__ __forceinline__ int32_t nth_non_positive(const int32_t *__restrict__ lst, long long len, uint32_t I, uint32_t z,
+                                                    int32_t last) {
+  long long distinct = 0;
+  for (long long q = 0; q < len; ++q) distinct += (q == 0 || lst[q] != lst[q - 1]);
+  if (distinct >= (long long)I) return last;
+  uint32_t x = __umulhi(z, I - (uint32_t)distinct);
+  for (long long q = 0; q < len; ++q) {
+    if (q && lst[q] == lst[q - 1]) continue;
+    if ((uint32_t)lst[q] <= x) ++x; else break;
+  }
+  return x < I ? (int32_t)x : last;                       // (ids outside [0, I) in the list)
 }
 
 // the owner plane (id >> sh: one byte) and the local plane (id & (2^sh - 1): a byte at sh == 8, else 16 bits) of a triplet's items
@@ -55,7 +74,8 @@ __global__ __launch_bounds__(256) void k_sample_philox(const int64_t *__restrict
   const long long lo0 = indptr[uu], len = indptr[uu + 1] - lo0;
   const int32_t *lst = items + lo0;
   int32_t jj = 0;
-  for (uint32_t a = 0; a < 1024u; ++a) {
+  bool hit = true;
+  for (uint32_t a = 0; a < 1024u && hit; ++a) {
     if (a) philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), a, 0u, k0, k1, r);
     jj = (int32_t)__umulhi(r[2], I);
     long long lo = 0, hi = len;
@@ -63,7 +83,11 @@ __global__ __launch_bounds__(256) void k_sample_philox(const int64_t *__restrict
       const long long mid = (lo + hi) >> 1;
       if (lst[mid] < jj) lo = mid + 1; else hi = mid;
     }
-    if (!(lo < len && lst[lo] == jj)) break;
+    hit = lo < len && lst[lo] == jj;
+  }
+  if (hit) {
+    philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), 1024u, 0u, k0, k1, r);
+    jj = nth_non_positive(lst, len, I, r[2], jj);
   }
   const int32_t ii = items[p];
   u[b] = uu; i[b] = ii; j[b] = jj;
@@ -97,7 +121,8 @@ __global__ __launch_bounds__(256) void k_sample_epoch(const int64_t *__restrict_
   const int32_t *lst = items + l0;
   uint32_t r[4];
   int32_t jj = 0;
-  for (uint32_t a = 0; a < 1024u; ++a) {
+  bool hit = true;
+  for (uint32_t a = 0; a < 1024u && hit; ++a) {
     philox4x32_10((uint32_t)n, (uint32_t)((unsigned long long)n >> 32), a, epoch, k0, k1, r);
     jj = (int32_t)__umulhi(r[2], I);
     long long l = 0, h = len;
@@ -105,7 +130,11 @@ __global__ __launch_bounds__(256) void k_sample_epoch(const int64_t *__restrict_
       const long long mid = (l + h) >> 1;
       if (lst[mid] < jj) l = mid + 1; else h = mid;
     }
-    if (!(l < len && lst[l] == jj)) break;
+    hit = l < len && lst[l] == jj;
+  }
+  if (hit) {
+    philox4x32_10((uint32_t)n, (uint32_t)((unsigned long long)n >> 32), 1024u, epoch, k0, k1, r);
+    jj = nth_non_positive(lst, len, I, r[2], jj);
   }
   const int32_t ii = lst[n - epoch_ptr[lo]];
   u[b] = uu; i[b] = ii; j[b] = jj;
@@ -118,7 +147,7 @@ __global__ __launch_bounds__(256) void k_sample_epoch(const int64_t *__restrict_
 // (a bijection of [0, 2^(2 half)) restricted to [0, U) by cycle-walking: a bijection of [0, U); < 4 walks on average).  No keys,
 // no sort: until the end of round 3 the order was the stable argsort of per-user Philox keys -- a device merge sort of 8 launches
 // and 60 us per epoch inside a preparation of 23 launches and 158 us (5 us per C2 step); this is one launch of a few us.  The third
-// counter word never collides with the negative draws (attempt numbers < 1024).  CPU twin: oracle orc_epoch_perm.
+// counter word never collides with the negative draws (attempt numbers <= 1024).  CPU twin: oracle orc_epoch_perm.
 __device__ __forceinline__ uint32_t epoch_perm_at(uint32_t a, uint32_t U, int half, uint32_t k0, uint32_t k1, uint32_t epoch) {
   const uint32_t mask = (1u << half) - 1u;
   uint32_t x = a;

@@ -350,6 +350,9 @@ class PhiloxSampler:
         self.num_pos, self.num_items, self.seed, self.next = int(indptr[-1]), int(num_items), int(seed), 0
         if self.num_pos == 0:
             raise ValueError("no training interactions")
+        full = [u for u, l in enumerate(train_lists) if len(l) >= num_items and len(set(l)) >= num_items]
+        if full:
+            raise ValueError("user %d holds every item as a positive: it has no negative to sample" % full[0])
         self.indptr, self.items, self.pos_user = (torch.as_tensor(a, device=self.device) for a in (indptr, items, pos_user))
 
     @classmethod
@@ -360,6 +363,15 @@ class PhiloxSampler:
         self.device = indptr.device
         self.indptr, self.items, self.pos_user = indptr.contiguous(), items_sorted.contiguous(), pos_user.contiguous()
         self.num_pos, self.num_items, self.seed, self.next = int(items_sorted.numel()), int(num_items), int(seed), 0
+        lens = self.indptr[1:] - self.indptr[:-1]
+        if self.num_pos and int(lens.max()) >= self.num_items:       # only then can a list hold every item: count distinct ids
+            it = self.items.long()
+            new = torch.ones_like(it, dtype=torch.int64)
+            new[1:] = (it[1:] != it[:-1]) | (self.pos_user[1:] != self.pos_user[:-1])
+            distinct = torch.zeros(lens.numel(), dtype=torch.int64, device=self.device).index_add_(0, self.pos_user.long(), new)
+            full = torch.nonzero(distinct >= self.num_items).flatten()
+            if full.numel():
+                raise ValueError("user %d holds every item as a positive: it has no negative to sample" % int(full[0]))
         return self
 
     def feeds(self, engine):

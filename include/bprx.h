@@ -335,7 +335,11 @@ BPRX_API int64_t bprx_sampler_ref_stream(bprx_sampler *s, int32_t batch_size, in
 /* ---- throughput sampler (DEVICE side; not in the reference: its sampler tops out at ~4e5 triplets/s) ---------
    Stateless counter-based Philox4x32-10: triplet n = first + b of stream `seed` depends on (seed, n) only.
    Positive: uniform over the num_pos training interactions (pos_user[p], items_sorted[p]); negative: uniform over the
-   items that are not positives of that user (rejection with binary search, <= 1024 attempts).  Replaces the role of
+   items that are not positives of that user (rejection with binary search, <= 1024 attempts; after 1024 positives in a
+   row -- a user holding nearly every item -- the r-th non-positive of the user, r = mulhi32(block(n, 1024).z, M) over its
+   M = num_items - #distinct(list) non-positives: the negative is NEVER a positive, lists may repeat an item.  A user whose
+   list holds every item has no negative: the Python sampler constructors raise ValueError for it; passed here, that
+   user's negative is an unspecified item in range).  Replaces the role of
    dataset.py:83-122 for throughput runs; its distribution differs from the reference's epoch-permutation walk.
    All pointers are DEVICE pointers: indptr int64 [U+1], items_sorted int32 [num_pos] (ascending inside each user),
    pos_user int32 [num_pos]. */

@@ -552,6 +552,8 @@ void orc_set_threads(int n) {
 /*   positive p  = mulhi64(block(n,0).xy, N)          -> (user_of[p], item_of[p]) */
 /*   negative j  = mulhi32(block(n,a).z, I), a = 0,1,.. until j not in train(u) */
 /*   (train lists sorted ascending per user; at most 1024 attempts).             */
+/*   after 1024 positives in a row: the r-th non-positive of the user,          */
+/*   r = mulhi32(block(n,1024).z, I - #distinct(list)) (nth_non_positive).      */
 /* ------------------------------------------------------------------------- */
 static void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
   for (int r = 0; r < 10; r++) {
@@ -562,6 +564,20 @@ static void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, ui
     k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
   }
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+/* the negative after 1024 rejections (twin of nth_non_positive in bprx_philox.hip): the r-th (0-based) item outside the
+   ascending, possibly repeating list, r = mulhi32(z, I - #distinct); `last` when the list holds every item */
+static int32_t nth_non_positive(const int32_t *lst, int64_t len, uint32_t I, uint32_t z, int32_t last) {
+  int64_t distinct = 0;
+  for (int64_t q = 0; q < len; q++) distinct += (q == 0 || lst[q] != lst[q - 1]);
+  if (distinct >= (int64_t)I) return last;
+  uint32_t x = (uint32_t)(((uint64_t)z * (uint64_t)(I - (uint32_t)distinct)) >> 32);
+  for (int64_t q = 0; q < len; q++) {
+    if (q && lst[q] == lst[q - 1]) continue;
+    if ((uint32_t)lst[q] <= x) x++; else break;
+  }
+  return x < I ? (int32_t)x : last;
 }
 
 /* the user order of an epoch (twin of k_epoch_prepare / epoch_perm_at in bprx_philox.hip): a 4-round Feistel network over
@@ -600,12 +616,17 @@ void orc_sample_philox(const int64_t *indptr, const int32_t *items_sorted, const
     const int32_t *lst = items_sorted + indptr[uu];
     int64_t len = indptr[uu + 1] - indptr[uu];
     int32_t jj = 0;
-    for (uint32_t a = 0; a < 1024; a++) {
+    int hit = 1;
+    for (uint32_t a = 0; a < 1024 && hit; a++) {
       if (a) philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), a, 0, (uint32_t)seed, (uint32_t)(seed >> 32), r);
       jj = (int32_t)(((uint64_t)r[2] * (uint64_t)(uint32_t)I) >> 32);
       int64_t lo = 0, hi = len;                     /* binary search in the sorted positives */
       while (lo < hi) { int64_t mid = (lo + hi) >> 1; if (lst[mid] < jj) lo = mid + 1; else hi = mid; }
-      if (!(lo < len && lst[lo] == jj)) break;
+      hit = lo < len && lst[lo] == jj;
+    }
+    if (hit) {
+      philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), 1024u, 0, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+      jj = nth_non_positive(lst, len, (uint32_t)I, r[2], jj);
     }
     u[b] = uu; i[b] = items_sorted[p]; j[b] = jj;
   }
@@ -626,12 +647,17 @@ void orc_sample_epoch(const int64_t *indptr, const int32_t *items_sorted, const 
     int64_t len = indptr[uu + 1] - indptr[uu];
     uint32_t r[4];
     int32_t jj = 0;
-    for (uint32_t a = 0; a < 1024; a++) {
+    int hit = 1;
+    for (uint32_t a = 0; a < 1024 && hit; a++) {
       philox4x32_10((uint32_t)n, (uint32_t)((uint64_t)n >> 32), a, epoch, (uint32_t)seed, (uint32_t)(seed >> 32), r);
       jj = (int32_t)(((uint64_t)r[2] * (uint64_t)(uint32_t)I) >> 32);
       int64_t l = 0, h = len;
       while (l < h) { int64_t mid = (l + h) >> 1; if (lst[mid] < jj) l = mid + 1; else h = mid; }
-      if (!(l < len && lst[l] == jj)) break;
+      hit = l < len && lst[l] == jj;
+    }
+    if (hit) {
+      philox4x32_10((uint32_t)n, (uint32_t)((uint64_t)n >> 32), 1024u, epoch, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+      jj = nth_non_positive(lst, len, (uint32_t)I, r[2], jj);
     }
     u[b] = uu; i[b] = lst[n - epoch_ptr[lo]]; j[b] = jj;
   }

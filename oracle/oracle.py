@@ -105,7 +105,12 @@ def interactions_csr(train_lists):
 
 
 def sample_philox(train_lists, num_items, seed, first, B):
-    indptr, items, pos_user = interactions_csr(train_lists)
+    return sample_philox_csr(*interactions_csr(train_lists), num_items, seed, first, B)
+
+
+def sample_philox_csr(indptr, items, pos_user, num_items, seed, first, B):
+    """Twin of PhiloxSampler on CSR arrays (indptr int64 [U+1], items int32 sorted per user, pos_user int32)."""
+    indptr, items, pos_user = (np.ascontiguousarray(a, dt) for a, dt in ((indptr, np.int64), (items, np.int32), (pos_user, np.int32)))
     u = np.empty(B, np.int32); i = np.empty(B, np.int32); j = np.empty(B, np.int32)
     lib().orc_sample_philox(_p(indptr), _p(items), _p(pos_user), len(items), num_items, seed, first, B, _p(u), _p(i), _p(j))
     return u, i, j
@@ -121,7 +126,13 @@ def epoch_perm(seed, epoch, U):
 def sample_epoch(train_lists, num_items, seed, epoch, first, B):
     """Twin of EpochWalkSampler for one epoch: the user order is the keyed Feistel permutation of bprx_epoch_prepare, same prefix sums."""
     indptr, items, _ = interactions_csr(train_lists)
-    U = len(train_lists)
+    return sample_epoch_csr(indptr, items, num_items, seed, epoch, first, B)
+
+
+def sample_epoch_csr(indptr, items, num_items, seed, epoch, first, B):
+    """sample_epoch on CSR arrays (indptr int64 [U+1], items int32 sorted per user): for millions of users."""
+    indptr, items = np.ascontiguousarray(indptr, np.int64), np.ascontiguousarray(items, np.int32)
+    U = len(indptr) - 1
     perm = epoch_perm(seed, epoch, U)
     eptr = np.zeros(U + 1, np.int64)
     eptr[1:] = np.cumsum(np.diff(indptr)[perm])

@@ -209,3 +209,112 @@ def test_adam_policy_picks_sweeps_for_small_batches_and_lazy_for_large_ones(monk
         e.close()
     for n in res[0]:
         assert np.array_equal(res[0][n].view(np.uint32), res[1][n].view(np.uint32)), n
+
+
+def _c2_tables(dev, seed):
+    import bench
+    w = dict(bench.WORKLOADS["c2"])
+    t = bench.make_state(w, dev, seed, torch)
+    g = torch.Generator(device=dev); g.manual_seed(seed)
+    t["Bi"] = torch.randn(w["I"], generator=g, device=dev) * 0.01
+    return w, t
+
+
+def _run_three_forms(monkeypatch, w, t, B, batches, mid_step, extra_env):
+    """The same run on three engines: lazy replay with the catch-up on the side stream (the default with VBPR + adam_tf23,
+    want_loss=False), BPRX_SIDE_STREAM=0 and BPRX_ADAM_LAZY=0 (want_loss=True).  Each engine binds its own clones.  The
+    tables are only read at the end (e.t syncs every pending row); one score_block + score_pairs mid-run on purpose: the
+    step after it finds the projection valid and runs the catch-up on the caller's stream.  Losses go to a device vector."""
+    from fashionvisualexpl_recommend_amd.engine import Engine
+    forms = [("side", {"BPRX_ADAM_LAZY": "1"}, False), ("no_side", {"BPRX_ADAM_LAZY": "1", "BPRX_SIDE_STREAM": "0"}, True),
+             ("sweeps", {"BPRX_ADAM_LAZY": "0"}, True)]
+    names = ["Gu", "Tu", "Gi", "Bi", "E", "Bp"]
+    names += ["m_" + n for n in names] + ["v_" + n for n in names]
+    res = {}
+    for form, env, want_loss in forms:
+        monkeypatch.delenv("BPRX_SIDE_STREAM", raising=False)
+        for kv in list(extra_env.items()) + list(env.items()):
+            monkeypatch.setenv(*kv)
+        e = Engine(model="vbpr", num_users=w["U"], num_items=w["I"], embed_k=w["k"], embed_d=w["d"], feat_dim=w["D"],
+                   feat_dtype=w["dtype"], optimizer="adam_tf23", lr=1e-3, reg=1e-4, max_batch=B).bind(
+                       **{n: v.clone() for n, v in t.items()})
+        assert e.adam_is_lazy() == (form != "sweeps")
+        losses = torch.zeros(len(batches), dtype=torch.float32, device=e.device)
+        mid = None
+        for s, (u, i, j) in enumerate(batches):
+            if want_loss:
+                e.step(u, i, j, loss_out=losses, loss_index=s)
+            else:
+                e.step(u, i, j, want_loss=False)
+            if s == mid_step:
+                mid = (e.score_block(0, 64).clone(), e.score_pairs(u, i).clone())
+        res[form] = (losses.cpu().numpy(), [m.cpu().numpy() for m in mid],
+                     {n: e.t[n].cpu().numpy().copy() for n in names})
+        e.sync_check()
+        e.close()
+    return res
+
+
+@pytest.mark.parametrize("item_mode", ["0", "2"])
+def test_side_stream_catchup_is_bit_identical_in_dense_mode_at_c2_size(monkeypatch, item_mode):
+    """c2 tables (VBPR k = d = 64, bf16 100K x 50K), B = 16 384 in dense mode (BPRX_LIST_MODE=0; by default 2B < I would
+    select list mode, where the catch-up never leaves the caller's stream): the lazy-Adam catch-up runs on the side stream
+    beside a forward projection over every item, long enough to overlap.  14 batches without a repeated row (the gradients
+    carry no atomic-order noise) -> the three forms must agree bit for bit, and skipping the loss must change no table."""
+    dev = torch.device("cuda", 0)
+    w, t = _c2_tables(dev, 31)
+    U, I, B = w["U"], w["I"], 16384
+    rs = np.random.RandomState(17)
+    batches = []
+    for s in range(14):
+        hotU, hotI = (U // 4, max(I // 4, 2 * B)) if s % 3 else (U, I)     # rows recur after varying gaps
+        u = rs.choice(hotU, B, replace=False)
+        it = rs.choice(hotI, 2 * B, replace=False)
+        batches.append(tuple(_dev(a.astype(np.int32)) for a in (u, it[:B], it[B:])))
+    res = _run_three_forms(monkeypatch, w, t, B, batches, 6, {"BPRX_LIST_MODE": "0", "BPRX_ITEM_MODE": item_mode})
+    np.testing.assert_array_equal(res["no_side"][0], res["sweeps"][0])              # identical losses, step by step
+    assert np.isfinite(res["sweeps"][0]).all()
+    for form in ("no_side", "sweeps"):
+        for a, b in zip(res["side"][1], res[form][1]):
+            assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), form
+        for n, a in res["side"][2].items():
+            b = res[form][2][n]
+            assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), "%s vs side, %s: %d of %d words differ" % (
+                form, n, int((a.view(np.uint32) != b.view(np.uint32)).sum()), a.size)
+
+
+def test_lazy_adam_matches_the_sweeps_at_the_bench_shape(monkeypatch):
+    """c2 at the bench's batch (B = 65 536) on the bench's epoch-walk stream (12 steps, item rows repeat inside a batch): the
+    three forms agree up to fp32 atomic-order noise of the duplicate-row sums, which Adam turns into moves of up to a few lr
+    where a gradient is within noise of cancelling.  Stated tolerance: at most 1e-3 of a row table's elements differ by more
+    than 2e-3 lr, none by more than 2 lr per step; E and Bp (moved every step by F^T W, whose bf16 W rounding the noise can
+    flip) by at most 0.05 lr, every element; the m / v slots as the row tables, relative to their own scale; the mid-run
+    scores (sums of 64 + 64 products of those tables) by at most 2 lr."""
+    from fashionvisualexpl_recommend_amd.engine import EpochWalkSampler
+    dev = torch.device("cuda", 0)
+    w, t = _c2_tables(dev, 32)
+    U, I, B, lr, steps = w["U"], w["I"], w["B"], 1e-3, 12
+    g = torch.Generator(device=dev); g.manual_seed(3)
+    items = torch.randint(I, (U, 20), generator=g, device=dev, dtype=torch.int32).sort(dim=1).values
+    indptr = torch.arange(U + 1, device=dev, dtype=torch.int64) * 20
+    pos_user = torch.arange(U, device=dev, dtype=torch.int32).repeat_interleave(20)
+    smp = EpochWalkSampler.from_csr(indptr, items.reshape(-1), pos_user, I, seed=2024)
+    batches = [tuple(x.clone() for x in smp.sample(B)) for _ in range(steps)]
+    res = _run_three_forms(monkeypatch, w, t, B, batches, 5, {})
+    np.testing.assert_allclose(res["no_side"][0], res["sweeps"][0], rtol=1e-5)
+    stats = {}
+    for form in ("no_side", "sweeps"):
+        for n, a in list(zip(("score_block", "score_pairs"), res["side"][1])) + list(res["side"][2].items()):
+            b = res[form][1][0 if n == "score_block" else 1] if n.startswith("score") else res[form][2][n]
+            diff = np.abs(a - b)
+            scale = lr if not n[:2] in ("m_", "v_") else float(np.abs(b).max()) + 1e-30
+            stats[form, n] = (float(diff.max() / scale), float((diff > 2e-3 * scale).mean()))
+    for kv in sorted(stats.items()):
+        print(kv)
+    for (form, n), (mx, frac) in stats.items():
+        if n.startswith("score"):
+            assert mx <= 2, (form, n, mx)
+        elif n in ("E", "Bp"):
+            assert mx <= 0.05, (form, n, mx)
+        else:
+            assert mx <= 2 * steps and frac <= 1e-3, (form, n, mx, frac)
