@@ -24,27 +24,66 @@ def shard_size(total, world):
     return (total + world - 1) // world
 
 
+# ---- collectives: RCCL on device tensors; gloo (the CPU tests, two ranks rehearsed on one GPU) moves host tensors only, so a
+#      device tensor goes through a host copy there.  async_op returns the RCCL work handle (wait() before the result is
+#      used); a staged or synchronous collective returns None.  Without a process group (a world of one) a gather copies and
+#      a reduction does nothing.
+def _host_staged(t, group):
+    return t.is_cuda and dist.get_backend(group) != "nccl"
+
+
+def all_reduce(t, group=None, async_op=False):
+    """t = the sum of every rank's t."""
+    if not dist.is_initialized():
+        return None
+    if _host_staged(t, group):
+        h = t.cpu()
+        dist.all_reduce(h, group=group)
+        t.copy_(h)
+        return None
+    return dist.all_reduce(t, group=group, async_op=async_op)
+
+
+def all_gather_into(out, inp, group=None, async_op=False):
+    """out = every rank's inp, concatenated along dim 0 in rank order."""
+    if not dist.is_initialized():
+        out.copy_(inp)
+        return None
+    if _host_staged(inp, group):
+        h = inp.cpu()
+        parts = [torch.empty_like(h) for _ in range(dist.get_world_size(group))]
+        dist.all_gather(parts, h, group=group)
+        out.copy_(torch.cat(parts))
+        return None
+    return dist.all_gather_into_tensor(out, inp, group=group, async_op=async_op)
+
+
+def all_to_all(out, inp, out_splits=None, in_splits=None, group=None, async_op=False):
+    """all_to_all_single: split lists of rows, or equal splits when none are given."""
+    if _host_staged(inp, group):
+        o = out.cpu()
+        dist.all_to_all_single(o, inp.cpu(), out_splits, in_splits, group=group)
+        out.copy_(o)
+        return None
+    return dist.all_to_all_single(out, inp.contiguous(), out_splits, in_splits, group=group, async_op=async_op)
+
+
 class UserRowExchange:
     """Routing of table rows (user rows for item-sharded VBPR, item rows for user-sharded BPRMF) between the ranks that
-    use them and the ranks that own them.  Pure tensor + collective logic (no kernels): works on CPU tensors with gloo
-    (tests) and on device tensors with nccl."""
+    use them and the ranks that own them.  Two forms: exact splits (plan / fetch / give_back: pure tensor + collective
+    logic, CPU tensors with gloo in the tests, device tensors with nccl) and fixed-capacity splits (plan_native /
+    fetch_native / give_back_native: routing in HIP kernels, device tensors)."""
 
     def __init__(self, rank, world, users_total, group=None):
         self.rank, self.world, self.group = rank, world, group
         self.ush = shard_size(users_total, world)
-        # gloo has no all_to_all for device tensors: stage through the host in that case (test mode only)
-        self.host_staged = dist.get_backend(group) != "nccl"
 
-    def _a2a(self, inp, in_splits, out_splits, async_op=False):
-        """all_to_all_single with split lists.  async_op: returns (out, work); the collective then runs on the
-        communicator's stream beside whatever the caller enqueues next, until work.wait() (nccl only)."""
-        out = inp.new_empty((sum(out_splits),) + tuple(inp.shape[1:]))
-        if self.host_staged and inp.is_cuda:
-            o, i = out.cpu(), inp.cpu()
-            dist.all_to_all_single(o, i, out_splits, in_splits, group=self.group)
-            out.copy_(o)
-            return (out, None) if async_op else out
-        work = dist.all_to_all_single(out, inp.contiguous(), out_splits, in_splits, group=self.group, async_op=async_op)
+    def _a2a(self, inp, in_splits=None, out_splits=None, async_op=False):
+        """all_to_all into a new tensor (equal splits when no split lists are given).  async_op: returns (out, work); the
+        collective then runs on the communicator's stream beside whatever the caller enqueues next, until work.wait()
+        (nccl only; work is None otherwise)."""
+        out = torch.empty_like(inp) if out_splits is None else inp.new_empty((sum(out_splits),) + tuple(inp.shape[1:]))
+        work = all_to_all(out, inp, out_splits, in_splits, group=self.group, async_op=async_op)
         return (out, work) if async_op else out
 
     def plan(self, u_global):
@@ -54,15 +93,8 @@ class UserRowExchange:
         owner = torch.div(u_global, self.ush, rounding_mode="floor").to(torch.int64)
         order = torch.argsort(owner, stable=True)
         counts = torch.bincount(owner, minlength=self.world)
-        if self.host_staged or not counts.is_cuda:
-            send = counts.cpu()
-            recv = torch.empty_like(send)
-            dist.all_to_all_single(recv, send, group=self.group)
-        else:                                            # nccl moves device tensors only
-            recv_dev = torch.empty_like(counts)
-            dist.all_to_all_single(recv_dev, counts, group=self.group)
-            send, recv = counts.cpu(), recv_dev.cpu()
-        send_counts, recv_counts = send.tolist(), recv.tolist()
+        recv = self._a2a(counts)
+        send_counts, recv_counts = counts.cpu().tolist(), recv.cpu().tolist()    # the step's one read back to the host
         local = (u_global[order] - owner[order] * self.ush).to(torch.int32)
         recv_local_idx = self._a2a(local, send_counts, recv_counts)
         return order, send_counts, recv_counts, recv_local_idx
@@ -80,44 +112,19 @@ class UserRowExchange:
         parts = list(torch.split(out, widths, dim=1))
         return (parts, work) if async_op else parts
 
+    def give_back(self, grad_rows, send_counts, recv_counts):
+        """Send per-row gradients (batch-sorted order, concatenated column-wise: ONE collective) to the owners; returns
+        the rows each owner received, aligned with the recv_local_idx of plan()."""
+        widths = [g.shape[1] for g in grad_rows]
+        packed = torch.cat(list(grad_rows), dim=1) if len(grad_rows) > 1 else grad_rows[0]
+        return list(torch.split(self._a2a(packed, send_counts, recv_counts), widths, dim=1))
+
     # ---- fixed-capacity form: no data-dependent split sizes, hence NO host synchronisation ---------------------------
     # Every rank sends exactly `cap` slots to every rank (a slot = one requested row id, -1 = empty), so the collectives
-    # take equal splits and nothing has to be read back to size them.  cap = slack x ceil(B / world) (default slack 2: the
-    # batch's users spread evenly over the owners up to sampling noise); a bucket that overflows is reported by
-    # overflowed() -- a device flag, read when the caller next synchronises anyway -- and its surplus rows take part with
-    # zero rows / dropped gradients in that step.
-    def _a2a_equal(self, inp):
-        out = torch.empty_like(inp)
-        if self.host_staged and inp.is_cuda:
-            o, i = out.cpu(), inp.cpu()
-            dist.all_to_all_single(o, i, group=self.group)
-            out.copy_(o)
-            return out
-        dist.all_to_all_single(out, inp.contiguous(), group=self.group)
-        return out
-
-    def plan_fixed(self, u_global, cap):
-        """Returns (order, slot, valid, recv_idx): request r sits in send slot slot[r] (owner * cap + its position among the
-        requests to that owner, in batch order) when valid[r]; recv_idx [world*cap] are the shard-local row ids the other
-        ranks ask this rank for (-1 = empty slot).  `order` is the identity (kept for the callers' signature: rows come back
-        in BATCH order).  No sort and nothing that reads a size back to the host: positions are a running count per owner
-        (one-hot cumsum over the <= 8 owners), invalid requests are written to a dump slot instead of being masked out
-        (boolean-mask indexing, bincount and nonzero all synchronise)."""
-        dev = u_global.device
-        n, W = u_global.numel(), self.world
-        owner = torch.div(u_global, self.ush, rounding_mode="floor").to(torch.int64)
-        run = (owner[:, None] == torch.arange(W, device=dev)[None, :]).to(torch.int32).cumsum(0)     # [n, W]
-        pos = run.gather(1, owner[:, None]).squeeze(1).to(torch.int64) - 1
-        valid = pos < cap
-        slot = owner * cap + pos
-        local = (u_global.to(torch.int64) - owner * self.ush).to(torch.int32)
-        send = torch.full((W * cap + 1,), -1, dtype=torch.int32, device=dev)
-        send.scatter_(0, torch.where(valid, slot, torch.full_like(slot, W * cap)), local)             # dump slot: W * cap
-        flag = (run[-1] > cap).any()
-        self._overflow = flag if getattr(self, "_overflow", None) is None else (self._overflow | flag)
-        order = torch.arange(n, device=dev)
-        return order, slot, valid, self._a2a_equal(send[:W * cap].contiguous())
-
+    # take equal splits and nothing has to be read back to size them.  cap = slack x ceil(n / world) + 8, at most n, for n
+    # requests per step (default slack 2: the requests spread evenly over the owners up to sampling noise); a bucket that
+    # overflows is reported by overflowed() -- a device flag, read when the caller next synchronises anyway -- and its
+    # surplus rows take part with zero rows / dropped gradients in that step.
     def overflowed(self):
         """True if any bucket of any plan_fixed() / plan_native() since the last call overflowed (synchronises)."""
         f = bool(self._overflow.item()) if getattr(self, "_overflow", None) is not None else False
@@ -127,17 +134,18 @@ class UserRowExchange:
             self._nat["overflow"].zero_()
         return f
 
-    # ---- the same fixed-capacity exchange with the routing in HIP kernels (include/bprx.h: bprx_route_*) ---------------
-    # plan: one kernel (requests counted per owner in LDS, one cursor atomic per workgroup and owner); owners gather the
-    # requested rows straight into the send buffer; the requester unpacks straight into the engine's staging tables; the
-    # gradient rows are packed into the send buffer (and zeroed) by one kernel and added at the owners by one kernel.
-    # Device tensors only (the torch forms above remain for CPU tensors: the gloo routing tests).
-    def native_setup(self, device, cap, n_max, width):
+    # The routing runs in HIP kernels (include/bprx.h: bprx_route_*).  plan: one kernel (requests counted per owner in LDS, one
+    # cursor atomic per workgroup and owner); owners gather the requested rows straight into the send buffer; the requester
+    # unpacks straight into the engine's staging tables; the gradient rows are packed into the send buffer (and zeroed) by
+    # one kernel and added at the owners by one kernel.  Device tensors only.
+    def native_setup(self, device, n_max, width, slack=2.0):
+        """n_max: requests per step at most; width: floats per routed row."""
         from . import _ffi
         W = self.world
+        cap = int(min(n_max, -(-n_max // W) * slack + 8))
         i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=device)
         ps = (int(width) + 3) & ~3                                # routed rows are padded to whole 16-byte pieces
-        self._nat = dict(lib=_ffi.lib(), cap=int(cap), width=int(width), send_idx=i32(W * cap), cursor=i32(W), overflow=i32(1),
+        self._nat = dict(lib=_ffi.lib(), cap=cap, width=int(width), send_idx=i32(W * cap), cursor=i32(W), overflow=i32(1),
                          slot=i32(n_max), rows_out=torch.zeros((W * cap, ps), dtype=torch.float32, device=device),
                          grad_out=torch.zeros((W * cap, ps), dtype=torch.float32, device=device),
                          # row multiplicities (own requests / the other ranks' requests): a row that occurs once is added
@@ -173,7 +181,7 @@ class UserRowExchange:
                                             self.rank, self._p(nat["slot"]), self._p(nat["send_idx"]), self._p(nat["cursor"]),
                                             self._p(nat["overflow"]), self._p(nat["own_cnt"]), self._s()), "route_plan")
         nat["n"] = n + nb
-        return self._a2a_equal(nat["send_idx"]) if W > 1 else nat["send_idx"]
+        return self._a2a(nat["send_idx"]) if W > 1 else nat["send_idx"]
 
     def fetch_native(self, t0, t1, recv_idx, dst0, dst1):
         """Owners gather [t0 | t1] rows (t1 may be None) into the send buffer; after the all-to-all the requester's rows land
@@ -184,7 +192,7 @@ class UserRowExchange:
         if self.world > 1:
             self._rc(nat["lib"].bprx_route_gather(self._p(t0), w0, self._p(t1), w1, t0.shape[0], self._p(recv_idx), recv_idx.numel(),
                                                   self._p(nat["rows_out"]), self._p(nat["cnt"]), self._s()), "route_gather")
-            got = self._a2a_equal(nat["rows_out"])
+            got = self._a2a(nat["rows_out"])
         self._rc(nat["lib"].bprx_route_unpack(self._p(got), self._p(nat["slot"]), nat["n"], self._p(dst0), w0, self._p(dst1), w1,
                                               self._p(t0), self._p(t1), t0.shape[0], self._s()), "route_unpack")
 
@@ -198,10 +206,34 @@ class UserRowExchange:
                                             self._p(t0), self._p(t1), t0.shape[0], float(scale), self._p(nat["own_cnt"]),
                                             self._p(nat["send_idx"]), W * nat["cap"], self._p(nat["cursor"]), W, self._s()), "route_pack")
         if W > 1:
-            back = self._a2a_equal(nat["grad_out"])
+            back = self._a2a(nat["grad_out"])
             self._rc(nat["lib"].bprx_route_scatter_add(self._p(t0), w0, self._p(t1), w1, t0.shape[0], self._p(recv_idx), self._p(back),
                                                        recv_idx.numel(), float(scale), self._p(nat["cnt"]), self._s()), "route_scatter_add")
 
+    # ---- the same fixed-capacity exchange in torch ops, for CPU tensors.  No driver calls it: tests/test_dist_cpu.py uses
+    # it as the only CPU coverage of the fixed-capacity semantics (equal splits, empty slots, the overflow flag) that the
+    # HIP routing above implements.
+    def plan_fixed(self, u_global, cap):
+        """Returns (order, slot, valid, recv_idx): request r sits in send slot slot[r] (owner * cap + its position among the
+        requests to that owner, in batch order) when valid[r]; recv_idx [world*cap] are the shard-local row ids the other
+        ranks ask this rank for (-1 = empty slot).  `order` is the identity (kept for the callers' signature: rows come back
+        in BATCH order).  No sort and nothing that reads a size back to the host: positions are a running count per owner
+        (one-hot cumsum over the <= 8 owners), invalid requests are written to a dump slot instead of being masked out
+        (boolean-mask indexing, bincount and nonzero all synchronise)."""
+        dev = u_global.device
+        n, W = u_global.numel(), self.world
+        owner = torch.div(u_global, self.ush, rounding_mode="floor").to(torch.int64)
+        run = (owner[:, None] == torch.arange(W, device=dev)[None, :]).to(torch.int32).cumsum(0)     # [n, W]
+        pos = run.gather(1, owner[:, None]).squeeze(1).to(torch.int64) - 1
+        valid = pos < cap
+        slot = owner * cap + pos
+        local = (u_global.to(torch.int64) - owner * self.ush).to(torch.int32)
+        send = torch.full((W * cap + 1,), -1, dtype=torch.int32, device=dev)
+        send.scatter_(0, torch.where(valid, slot, torch.full_like(slot, W * cap)), local)             # dump slot: W * cap
+        flag = (run[-1] > cap).any()
+        self._overflow = flag if getattr(self, "_overflow", None) is None else (self._overflow | flag)
+        order = torch.arange(n, device=dev)
+        return order, slot, valid, self._a2a(send[:W * cap].contiguous())
 
     def fetch_fixed(self, shard_tables, recv_idx, slot, valid):
         """Owners gather the requested rows (empty slots: zero rows) and send them back; returns the rows in batch-sorted
@@ -210,7 +242,7 @@ class UserRowExchange:
         idx = recv_idx.clamp(min=0).long()
         widths = [t.shape[1] for t in shard_tables]
         packed = torch.cat([t.index_select(0, idx) for t in shard_tables], dim=1) * ok[:, None].to(shard_tables[0].dtype)
-        got = self._a2a_equal(packed)
+        got = self._a2a(packed)
         rows = got.index_select(0, slot.clamp(max=got.shape[0] - 1)) * valid[:, None].to(got.dtype)
         return list(torch.split(rows, widths, dim=1))
 
@@ -221,14 +253,39 @@ class UserRowExchange:
         packed = torch.cat(list(grad_rows), dim=1) if len(grad_rows) > 1 else grad_rows[0]
         send = torch.zeros((self.world * cap + 1, packed.shape[1]), dtype=packed.dtype, device=packed.device)
         send.index_copy_(0, torch.where(valid, slot, torch.full_like(slot, self.world * cap)), packed)   # (dump row: W * cap)
-        return list(torch.split(self._a2a_equal(send[:self.world * cap]), widths, dim=1))
+        return list(torch.split(self._a2a(send[:self.world * cap]), widths, dim=1))
 
-    def give_back(self, grad_rows, send_counts, recv_counts):
-        """Send per-row gradients (batch-sorted order, concatenated column-wise: ONE collective) to the owners; returns
-        the rows each owner received, aligned with the recv_local_idx of plan()."""
-        widths = [g.shape[1] for g in grad_rows]
-        packed = torch.cat(list(grad_rows), dim=1) if len(grad_rows) > 1 else grad_rows[0]
-        return list(torch.split(self._a2a(packed, send_counts, recv_counts), widths, dim=1))
+
+class ShardOwners:
+    """The owners' side of the fixed-capacity exchange (give_back_native) in the all-to-all drivers.  'sgd': the owners add
+    -lr x the returned gradient rows into their shard tables.  'adam_tf23': they sum them into a gradient table per shard
+    table and take the Adam step of the WHOLE shard (bprx_adam_rows: TF-2.3's Adam moves every row every step) with the
+    engine's lr_t; the engine takes the Adam steps of the rows it keeps."""
+
+    def __init__(self, optimizer, fixed_cap, lr):
+        from .engine import adam_rows
+        self._adam_rows, self.lr = adam_rows, lr
+        self.adam = optimizer == "adam_tf23"
+        if optimizer not in ("sgd", "adam_tf23"):
+            raise ValueError("optimizer: 'sgd' | 'adam_tf23'")
+        if self.adam and not fixed_cap:
+            raise NotImplementedError("adam_tf23 in the all-to-all mode: the native fixed-capacity exchange only")
+
+    def own(self, tables):
+        """The shard tables, and under adam their state: moments + the summed gradients of a step."""
+        self.tables = tables
+        if self.adam:
+            self.adam_state = [tuple(torch.zeros_like(t) for _ in range(3)) for t in tables]
+
+    def give_back(self, x, eng, g0, g1, recv_idx):
+        """The staging gradient rows g0 | g1 (returned to zero) to their owners, who update their shard."""
+        if not self.adam:
+            x.give_back_native(g0, g1, recv_idx, *self.tables, -self.lr)
+            return
+        x.give_back_native(g0, g1, recv_idx, *(g for _, _, g in self.adam_state), 1.0)
+        lr_t = eng.step_lr()
+        for t, (m, v, g) in zip(self.tables, self.adam_state):
+            self._adam_rows(t, m, v, g, lr_t)
 
 
 class ItemShardedVBPR:
@@ -236,22 +293,17 @@ class ItemShardedVBPR:
 
     def __init__(self, rank, world, users_total, Gu_shard, Tu_shard, Gi_shard, Bi_shard, F_shard, E, Bp, lr, reg,
                  max_batch, feat_dtype="bf16", group=None, device=None, fixed_cap=True, slack=2.0, optimizer="sgd"):
-        """fixed_cap (default): the row exchange uses equal, fixed-capacity splits (UserRowExchange.plan_fixed): no host
-        synchronisation inside the step; False: exact data-dependent splits (one `.cpu()` of the split sizes per step).
-        optimizer: 'sgd' | 'adam_tf23' (native fixed-capacity path): the engine takes the Adam steps of its item rows and of
-        E|Bp; the returned user-row gradients are summed into a gradient table of the owner's shard, and the owner takes the
-        Adam step of its WHOLE shard (bprx_adam_rows: TF-2.3's Adam moves every row every step)."""
-        from .engine import Engine, scatter_add, adam_rows
-        self._scatter_add, self._adam_rows = scatter_add, adam_rows
+        """fixed_cap (default): the row exchange uses equal, fixed-capacity splits with the routing in HIP kernels
+        (UserRowExchange.plan_native / fetch_native / give_back_native): no host synchronisation inside the step; False:
+        exact data-dependent splits (plan / fetch / give_back: the split sizes are read back to the host every step).
+        optimizer: 'sgd' | 'adam_tf23' (fixed_cap only): the engine takes the Adam steps of its item rows and of E|Bp, the
+        owners those of their user shards (ShardOwners)."""
+        from .engine import Engine, scatter_add
+        self._scatter_add = scatter_add
         self.rank, self.world, self.group = rank, world, group
         self.lr = lr
         self.fixed_cap = fixed_cap
-        self.adam = optimizer == "adam_tf23"
-        if optimizer not in ("sgd", "adam_tf23"):
-            raise ValueError("optimizer: 'sgd' | 'adam_tf23'")
-        if self.adam and not fixed_cap:
-            raise NotImplementedError("adam_tf23 in the all-to-all mode: the native fixed-capacity exchange only")
-        self.cap = int(min(max_batch, -(-max_batch // world) * slack + 8))
+        self.owners = ShardOwners(optimizer, fixed_cap, lr)
         self.x = UserRowExchange(rank, world, users_total, group)
         k, d = Gu_shard.shape[1], Tu_shard.shape[1]
         self.eng = Engine(model="vbpr", num_users=max_batch, num_items=Gi_shard.shape[0], embed_k=k, embed_d=d,
@@ -260,24 +312,24 @@ class ItemShardedVBPR:
         dev = self.eng.device
         self.Gu_shard = Gu_shard.to(dev).contiguous()
         self.Tu_shard = Tu_shard.to(dev).contiguous()
-        if self.adam:                                            # the owner's Adam state: moments + the summed gradients of a step
-            self.adam_state = {n: tuple(torch.zeros_like(t) for _ in range(3)) for n, t in (("Gu", self.Gu_shard), ("Tu", self.Tu_shard))}
+        self.owners.own([self.Gu_shard, self.Tu_shard])
         self.stage_Gu = torch.zeros((max_batch, k), dtype=torch.float32, device=dev)
         self.stage_Tu = torch.zeros((max_batch, d), dtype=torch.float32, device=dev)
         self.eng.bind(Gu=self.stage_Gu, Gi=Gi_shard, Bi=Bi_shard, Tu=self.stage_Tu, F=F_shard, E=E, Bp=Bp)
         self.iota = torch.arange(max_batch, dtype=torch.int32, device=dev)
         self.dense = self.eng.dense_grad()
-        self.native = bool(fixed_cap)                            # routing in HIP kernels (bprx_route_*)
-        if self.native:
-            self.x.native_setup(dev, self.cap, max_batch, k + d)
+        if fixed_cap:
+            self.x.native_setup(dev, max_batch, k + d, slack)
+
+    def _dense_allreduce(self):
+        if self.world > 1:
+            all_reduce(self.dense, self.group)                    # RCCL, 4*(D*d + D) bytes
 
     def step(self, u_global, i_local, j_local, want_loss=False):
         """One global batch-synchronous step; every rank calls it with its own local batch (int32 device tensors)."""
-        B = u_global.numel()
-        if self.fixed_cap and self.native:
-            return self._step_native(u_global, i_local, j_local, want_loss)
         if self.fixed_cap:
-            return self._step_fixed(u_global, i_local, j_local, want_loss)
+            return self._step_native(u_global, i_local, j_local, want_loss)
+        B = u_global.numel()
         order, sc, rc, ridx = self.x.plan(u_global)
         (gu, tu), work = self.x.fetch([self.Gu_shard, self.Tu_shard], ridx, sc, rc, async_op=True)
         self.eng.step_project()                                   # P = F.[E|Bp] runs beside the row fetch (xGMI)
@@ -287,13 +339,7 @@ class ItemShardedVBPR:
         self.stage_Tu[:B].copy_(tu)
         i_s, j_s = i_local[order].contiguous(), j_local[order].contiguous()
         self.eng.step_begin(self.iota[:B], i_s, j_s)
-        if self.world > 1:
-            if self.x.host_staged:
-                h = self.dense.cpu()
-                dist.all_reduce(h, group=self.group)
-                self.dense.copy_(h)
-            else:
-                dist.all_reduce(self.dense, group=self.group)     # RCCL, 4*(D*d + D) bytes
+        self._dense_allreduce()
         loss = self.eng.step_end(want_loss=want_loss)
         dG, dT = self.eng.user_grad()
         g_back, t_back = self.x.give_back([dG[:B], dT[:B]], sc, rc)
@@ -301,16 +347,6 @@ class ItemShardedVBPR:
         self._scatter_add(self.Gu_shard, ridx, g_back.contiguous(), -self.lr)
         self._scatter_add(self.Tu_shard, ridx, t_back.contiguous(), -self.lr)
         return loss
-
-
-    def _dense_allreduce(self):
-        if self.world > 1:
-            if self.x.host_staged:
-                h = self.dense.cpu()
-                dist.all_reduce(h, group=self.group)
-                self.dense.copy_(h)
-            else:
-                dist.all_reduce(self.dense, group=self.group)     # RCCL, 4*(D*d + D) bytes
 
     def _step_native(self, u_global, i_local, j_local, want_loss):
         """Fixed-capacity exchange with the routing in HIP kernels: plan, gather, unpack, pack, scatter-add are one launch each
@@ -323,40 +359,8 @@ class ItemShardedVBPR:
         self._dense_allreduce()
         loss = self.eng.step_end(want_loss=want_loss)
         dG, dT = self.eng.user_grad()
-        if self.adam:
-            (mG, vG, gG), (mT, vT, gT) = self.adam_state["Gu"], self.adam_state["Tu"]
-            self.x.give_back_native(dG, dT, ridx, gG, gT, 1.0)                               # summed gradients of my users' rows
-            lr_t = self.eng.step_lr()
-            self._adam_rows(self.Gu_shard, mG, vG, gG, lr_t)
-            self._adam_rows(self.Tu_shard, mT, vT, gT, lr_t)
-        else:
-            self.x.give_back_native(dG, dT, ridx, self.Gu_shard, self.Tu_shard, -self.lr)  # (also re-zeroes the gradient rows)
+        self.owners.give_back(self.x, self.eng, dG, dT, ridx)    # (also re-zeroes the gradient rows)
         self.eng.clear_user_marks(B)
-        return loss
-
-    def _step_fixed(self, u_global, i_local, j_local, want_loss):
-        """The same global step with fixed-capacity exchanges: every tensor op and collective is enqueued without reading
-        anything back to the host."""
-        B = u_global.numel()
-        order, slot, valid, ridx = self.x.plan_fixed(u_global, self.cap)
-        self.eng.step_project()                                   # P = F.[E|Bp]: no user rows needed
-        gu, tu = self.x.fetch_fixed([self.Gu_shard, self.Tu_shard], ridx, slot, valid)
-        self.stage_Gu[:B].copy_(gu)
-        self.stage_Tu[:B].copy_(tu)
-        self.eng.step_begin(self.iota[:B], i_local, j_local)     # (rows arrive in batch order: nothing to permute)
-        if self.world > 1:
-            if self.x.host_staged:
-                h = self.dense.cpu()
-                dist.all_reduce(h, group=self.group)
-                self.dense.copy_(h)
-            else:
-                dist.all_reduce(self.dense, group=self.group)     # RCCL, 4*(D*d + D) bytes
-        loss = self.eng.step_end(want_loss=want_loss)
-        dG, dT = self.eng.user_grad()
-        g_back, t_back = self.x.give_back_fixed([dG[:B], dT[:B]], slot, valid, self.cap)
-        self.eng.clear_user_grad(B)
-        self._scatter_add(self.Gu_shard, ridx, g_back.contiguous(), -self.lr)
-        self._scatter_add(self.Tu_shard, ridx, t_back.contiguous(), -self.lr)
         return loss
 
 
@@ -404,8 +408,6 @@ class ReplicatedUserVBPR:
         self.msgs = torch.zeros(world * n, dtype=torch.float32, device=dev)
         self.dparts = (torch.zeros(world * self.dense.numel(), dtype=torch.float32, device=dev)
                        if separate_dense and dense_reduce == "gather" else None)
-        self.live = dist.is_initialized()
-        self.host_staged = self.live and dist.get_backend(group) != "nccl"     # gloo: test mode
 
     @property
     def Gu(self):
@@ -414,30 +416,6 @@ class ReplicatedUserVBPR:
     @property
     def Tu(self):
         return self.eng.t["Tu"]
-
-    # -- collectives: RCCL (asynchronous: the returned work is waited for where the result is needed), or staged through
-    #    the host for the gloo test mode, or a plain copy without a process group
-    def _all_gather(self, out, inp):
-        if not self.live:
-            out.copy_(inp)
-            return None
-        if self.host_staged:
-            h = inp.cpu()
-            parts = [torch.empty_like(h) for _ in range(self.world)]
-            dist.all_gather(parts, h, group=self.group)
-            out.copy_(torch.cat(parts))
-            return None
-        return dist.all_gather_into_tensor(out, inp, group=self.group, async_op=True)
-
-    def _all_reduce(self, t):
-        if not self.live:
-            return None
-        if self.host_staged:
-            h = t.cpu()
-            dist.all_reduce(h, group=self.group)
-            t.copy_(h)
-            return None
-        return dist.all_reduce(t, group=self.group, async_op=True)
 
     def step(self, u_global, i_local, j_local, want_loss=False, loss_out=None, loss_index=0):
         """One global step.  A rank whose item shard holds no positive of this batch passes EMPTY index tensors: it sends a
@@ -448,8 +426,8 @@ class ReplicatedUserVBPR:
         if not self.overlap:
             eng.step_begin(u_global, i_local, j_local)
             eng.pack_user_msg(u_global, self.cap, self.msg)
-            wd = self._all_reduce(self.dense) if self.dense is not None and self.world > 1 else None
-            wm = self._all_gather(self.msgs, self.msg)
+            wd = all_reduce(self.dense, self.group, async_op=True) if self.dense is not None and self.world > 1 else None
+            wm = all_gather_into(self.msgs, self.msg, self.group, async_op=True)
             for w in (wd, wm):
                 if w is not None:
                     w.wait()
@@ -457,12 +435,12 @@ class ReplicatedUserVBPR:
             return end()
         eng.step_begin_sparse(u_global, i_local, j_local)          # ... per-triplet gradients: user rows are final
         eng.pack_user_msg(u_global, self.cap, self.msg)
-        wm = self._all_gather(self.msgs, self.msg)                  # in flight beside:
+        wm = all_gather_into(self.msgs, self.msg, self.group, async_op=True)     # in flight beside:
         eng.step_begin_dense()                                      # item rows, W, dE|dBp = F^T W
         if self.dense_reduce == "allreduce":
-            wd = self._all_reduce(self.dense) if self.world > 1 else None
+            wd = all_reduce(self.dense, self.group, async_op=True) if self.world > 1 else None
         else:
-            wd = self._all_gather(self.dparts, self.dense)
+            wd = all_gather_into(self.dparts, self.dense, self.group, async_op=True)
         if wm is not None:
             wm.wait()
         eng.apply_user_msgs(self.msgs, self.world, self.cap, -self.lr)
@@ -486,22 +464,17 @@ class UserShardedBPRMF:
 
     def __init__(self, rank, world, items_total, Gu_shard, Gi_shard, Bi_shard, lr, reg, max_batch, group=None, device=None,
                  fixed_cap=True, slack=2.0, optimizer="sgd"):
-        """fixed_cap (default): the row exchange uses equal, fixed-capacity splits (RowExchange.plan_fixed: 2B requested rows
-        spread over `world` owners, `slack` x the even share per owner): no host synchronisation inside the step, an
-        overflowing bucket raises a device flag (x.overflowed()); False: exact data-dependent splits (one `.cpu()` of the
-        split sizes per step)."""
-        from .engine import Engine, scatter_add, adam_rows
-        self._scatter_add, self._adam_rows = scatter_add, adam_rows
+        """fixed_cap (default): the row exchange uses equal, fixed-capacity splits with the routing in HIP kernels
+        (RowExchange.plan_native: 2B requested rows spread over `world` owners, `slack` x the even share per owner): no host
+        synchronisation inside the step, an overflowing bucket raises a device flag (x.overflowed()); False: exact
+        data-dependent splits (plan / fetch / give_back: the split sizes are read back to the host every step).
+        optimizer: 'sgd' | 'adam_tf23' (fixed_cap only): the engine (lazy form) steps the user rows, the item owners their
+        whole Gi / Bi shard, every global step (ShardOwners)."""
+        from .engine import Engine, scatter_add
+        self._scatter_add = scatter_add
         self.rank, self.world, self.group, self.lr = rank, world, group, lr
         self.fixed_cap = fixed_cap
-        # adam_tf23 (native fixed-capacity path): the engine (lazy form) steps the user rows; the item owners sum the returned
-        # gradients into a gradient table of their shard and step the WHOLE shard (bprx_adam_rows), every global step
-        self.adam = optimizer == "adam_tf23"
-        if optimizer not in ("sgd", "adam_tf23"):
-            raise ValueError("optimizer: 'sgd' | 'adam_tf23'")
-        if self.adam and not fixed_cap:
-            raise NotImplementedError("adam_tf23 in the all-to-all mode: the native fixed-capacity exchange only")
-        self.cap = int(min(2 * max_batch, -(-2 * max_batch // world) * slack + 8))
+        self.owners = ShardOwners(optimizer, fixed_cap, lr)
         self.x = RowExchange(rank, world, items_total, group)
         k = Gu_shard.shape[1]
         self.eng = Engine(model="bprmf", num_users=Gu_shard.shape[0], num_items=2 * max_batch, embed_k=k, optimizer=optimizer,
@@ -509,61 +482,38 @@ class UserShardedBPRMF:
         dev = self.eng.device
         self.Gi_shard = Gi_shard.to(dev).float().contiguous()                  # [Ish, k]
         self.Bi_col = Bi_shard.to(dev).float().reshape(-1, 1).contiguous()      # [Ish, 1]
-        if self.adam:
-            self.adam_state = {n: tuple(torch.zeros_like(t) for _ in range(3)) for n, t in (("Gi", self.Gi_shard), ("Bi", self.Bi_col))}
+        self.owners.own([self.Gi_shard, self.Bi_col])
         self.stage_Gi = torch.zeros((2 * max_batch, k), dtype=torch.float32, device=dev)
         self.stage_Bi = torch.zeros(2 * max_batch, dtype=torch.float32, device=dev)
         self.eng.bind(Gu=Gu_shard, Gi=self.stage_Gi, Bi=self.stage_Bi)
         self.iota = torch.arange(2 * max_batch, dtype=torch.int32, device=dev)
-        self.k = k
-        self.native = bool(fixed_cap)                            # routing in HIP kernels (bprx_route_*)
-        if self.native:
-            self.x.native_setup(dev, self.cap, 2 * max_batch, k + 1)
+        if fixed_cap:
+            self.x.native_setup(dev, 2 * max_batch, k + 1, slack)
 
     @property
     def Bi_shard(self):
         return self.Bi_col[:, 0]
 
     def step(self, u_local, i_global, j_global, want_loss=False, loss_out=None, loss_index=0):
-        """loss_out / loss_index: see Engine.step.  An EMPTY batch (a rank whose users have no positives) still takes part in
-        the three all-to-alls (native path)."""
-        B, k = u_local.numel(), self.k
-        if self.fixed_cap and self.native:
+        """loss_out / loss_index: see Engine.step (fixed_cap).  An EMPTY batch (a rank whose users have no positives) still
+        takes part in the three all-to-alls (fixed_cap)."""
+        B = u_local.numel()
+        if self.fixed_cap:
             # a routed row is [Gi row | Bi] (k + 1 floats, padded to k + 4): the gather / unpack / pack / scatter-add kernels
             # take the two tables as they are (w0 = k, w1 = 1)
             ridx = self.x.plan_native(i_global, j_global)        # (requests 0..B-1: the positives, B..2B-1: the negatives)
             self.x.fetch_native(self.Gi_shard, self.Bi_col, ridx, self.stage_Gi, self.stage_Bi)
             loss = None
-            if B or self.adam:                                   # (adam: an empty batch is still a step -- every row moves)
+            if B or self.owners.adam:                            # (adam: an empty batch is still a step -- every row moves)
                 loss = self.eng.step(u_local, self.iota[:B], self.iota[B:2 * B], want_loss=want_loss, loss_out=loss_out,
                                      loss_index=loss_index)
             dG, dB = self.eng.item_grad()
-            if self.adam:
-                (mG, vG, gG), (mB, vB, gB) = self.adam_state["Gi"], self.adam_state["Bi"]
-                self.x.give_back_native(dG, dB.view(-1, 1), ridx, gG, gB, 1.0)                       # summed gradients of my items' rows
-                lr_t = self.eng.step_lr()
-                self._adam_rows(self.Gi_shard, mG, vG, gG, lr_t)
-                self._adam_rows(self.Bi_col, mB, vB, gB, lr_t)
-            else:
-                self.x.give_back_native(dG, dB.view(-1, 1), ridx, self.Gi_shard, self.Bi_col, -self.lr)   # (re-zeroes dG / dB rows)
+            self.owners.give_back(self.x, self.eng, dG, dB.view(-1, 1), ridx)   # (re-zeroes dG / dB rows)
             self.eng.clear_item_marks(2 * B)
             return loss
         items = torch.cat([i_global, j_global])                                   # 2B requested rows
-        tabs = [self.Gi_shard, self.Bi_col]
-        if self.fixed_cap:
-            order, slot, valid, ridx = self.x.plan_fixed(items, self.cap)
-            gi, bi = self.x.fetch_fixed(tabs, ridx, slot, valid)                  # [2B, k], [2B, 1] in batch order
-            self.stage_Gi[:2 * B].copy_(gi)
-            self.stage_Bi[:2 * B].copy_(bi[:, 0])
-            loss = self.eng.step(u_local, self.iota[:B], self.iota[B:2 * B], want_loss=want_loss)
-            dG, dB = self.eng.item_grad()
-            g_back, b_back = self.x.give_back_fixed([dG[:2 * B], dB[:2 * B].reshape(-1, 1)], slot, valid, self.cap)
-            self.eng.clear_item_grad(2 * B)
-            self._scatter_add(self.Gi_shard, ridx, g_back.contiguous(), -self.lr)  # (index -1 = empty slot: skipped)
-            self._scatter_add(self.Bi_col, ridx, b_back.contiguous(), -self.lr)
-            return loss
         order, sc, rc, ridx = self.x.plan(items)
-        gi, bi = self.x.fetch(tabs, ridx, sc, rc)                                 # owner-sorted order
+        gi, bi = self.x.fetch([self.Gi_shard, self.Bi_col], ridx, sc, rc)       # owner-sorted order
         inv = torch.empty_like(order)
         inv[order] = torch.arange(order.numel(), device=order.device)             # back to batch order
         self.stage_Gi[:2 * B].copy_(gi.index_select(0, inv))

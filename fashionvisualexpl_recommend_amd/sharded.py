@@ -28,6 +28,7 @@ import torch
 import torch.distributed as dist
 
 from . import configs
+from .dist import all_gather_into, all_reduce
 from .synth import glorot_uniform
 
 
@@ -59,12 +60,115 @@ def local_positive_lists(training_list, num_users, lo, hi):
     return out
 
 
-class ShardedVBPR:
+class _ShardedModel:
+    """The epoch's step count, the rank's sampler, the collectives and the training loop of both sharded models.  A subclass
+    sets rank, world, group, params, batch, engine, m (the per-rank driver), evaluator and directory_parameters, and brings
+    metrics, local_state / load_local_state / full_state and store_recommendation."""
+    default_rec = None                                          # the --rec name the output directories take by default
+
+    def _epoch_walk(self, lists, num_items):
+        """steps_per_epoch, and this rank's sampler over its positive lists (None if it holds no positive)."""
+        from .engine import EpochWalkSampler
+        self.local_pos = sum(len(l) for l in lists)
+        n = torch.tensor([self.local_pos], dtype=torch.int64)
+        dist.all_reduce(n, op=dist.ReduceOp.MAX, group=self.group)
+        self.steps_per_epoch = max(1, int(n.item()) // self.batch)     # every rank steps as often as the fullest shard
+        # a rank whose shard holds no positive still takes every step (with an empty batch)
+        self.sampler = EpochWalkSampler(lists, num_items, device=self.engine.device,
+                                        seed=getattr(self.params, "init_seed", 0) + 7919 * self.rank) if self.local_pos else None
+
+    def _all_reduce_sum(self, t):
+        if self.world > 1:
+            all_reduce(t, self.group)
+        return t
+
+    def _gather_to_root(self, loc, sh, total, dim=0):
+        """Rank 0: every rank's host tensor loc, zero-padded to sh along dim, concatenated in rank order and cut to total
+        (None on the other ranks)."""
+        n = min(sh, loc.shape[dim])
+        pad = loc.new_zeros(loc.shape[:dim] + (sh,) + loc.shape[dim + 1:])
+        pad.narrow(dim, 0, n).copy_(loc.narrow(dim, 0, n))
+        parts = [torch.empty_like(pad) for _ in range(self.world)] if self.rank == 0 else None
+        dist.gather(pad, parts, dst=0, group=self.group)
+        return torch.cat(parts, dim=dim).narrow(dim, 0, total) if self.rank == 0 else None
+
+    @staticmethod
+    def _means(r, suf):
+        """The five means of Evaluator.py:189-193 over one held-out list's per-user metric rows (-1: no held-out item)."""
+        if (r[:, 0] == -2).any():
+            raise NotImplementedError("more than 32 held-out items per user: not supported by the sharded evaluator")
+        r = r[r[:, 0] >= 0]
+        return dict(zip([n + suf for n in ("hr", "p", "r", "auc", "ndcg")], r.mean(axis=0).tolist()))
+
+    # ---- BPRMF.py:127-192 with one step = one global batch of world x batch_size triplets ---------------------------
+    def train(self):
+        params, dev = self.params, self.engine.device
+        max_metrics = {'hr': 0, 'p': 0, 'r': 0, 'auc': 0, 'ndcg': 0}
+        best_state, best_epoch, best_epoch_print = None, getattr(params, "restore_epochs", 1), 'No best epoch found!'
+        results = {}
+        rec = getattr(params, "rec", self.default_rec)
+        wdir = os.path.join(configs.weight_dir(), params.dataset, rec)
+        rdir = os.path.join(configs.results_dir(), params.dataset, rec)
+        if self.rank == 0:
+            os.makedirs(wdir, exist_ok=True)
+            os.makedirs(rdir, exist_ok=True)
+            print('Start training...')
+        empty = torch.zeros(0, dtype=torch.int32, device=dev)
+        loss_buf = torch.zeros(self.steps_per_epoch, dtype=torch.float32, device=dev)      # read once per epoch: no per-step sync
+        verbose, best_metric = getattr(params, "verbose", -1), getattr(params, "best_metric", "ndcg")
+        for it in range(1, params.epochs + 1):
+            start = time()
+            loss_buf.zero_()                                   # (an empty sgd batch of BPRMF writes no loss)
+            for s in range(self.steps_per_epoch):
+                u, i, j = self.sampler.sample(self.batch) if self.sampler is not None else (empty, empty, empty)
+                self.m.step(u, i, j, loss_out=loss_buf, loss_index=s)
+            loss = float(loss_buf.double().sum().item())
+            epoch_text = 'Epoch {0}/{1} \tLoss (rank 0 shard): {2:.3f}'.format(it, params.epochs, loss / self.steps_per_epoch)
+            epoch_print = self.evaluator.eval(it, results, epoch_text, start)               # identical on every rank
+            for metric in max_metrics.keys():                                               # BPRMF.py:152-156
+                if max_metrics[metric] <= results[it][metric + '_v']:
+                    max_metrics[metric] = results[it][metric + '_v']
+                    if metric == best_metric:
+                        best_epoch, best_state, best_epoch_print = it, self.local_state(), epoch_print
+            if (it % verbose == 0 or it == 1) and verbose != -1:
+                full = self.full_state()
+                if self.rank == 0:
+                    torch.save(full, os.path.join(wdir, f'weights-{it}-{self.directory_parameters}.pt'))
+        self.engine.sync_check()
+        x = getattr(self.m, "x", None)                         # the all-to-all row exchange (ShardedBPRMF)
+        if x is not None and x.overflowed():
+            raise RuntimeError("a row-routing bucket overflowed (dist.UserShardedBPRMF: raise `slack`)")
+        last = params.epochs
+        if self.rank == 0:
+            print('Training end...')
+        self.store_recommendation(os.path.join(rdir, f'recs-{last}-{self.directory_parameters}.tsv'))
+        if self.rank == 0:
+            with open(os.path.join(rdir, f'results-metrics-{self.directory_parameters}') + '.pkl', 'wb') as f:
+                pickle.dump(results, f)                                                     # utils/write.py:14-22
+            print("Store Best Model at Epoch {0}".format(best_epoch))
+            print(best_epoch_print)
+        last_state = self.local_state()
+        if best_state is not None:
+            full = self.full_state(best_state)
+            if self.rank == 0:
+                torch.save(full, os.path.join(wdir, f'best-weights-{best_epoch}-{self.directory_parameters}.pt'))
+            self.load_local_state(best_state)
+        self.store_recommendation(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
+        self.load_local_state(last_state)
+        if self.rank == 0:
+            print('End Store Best Model!')
+            print('Best Values for Each Metric:\nHR\tPrec\tRec\tAUC\tnDCG\n{}\t{}\t{}\t{}\t{}\n'.format(
+                max_metrics['hr'], max_metrics['p'], max_metrics['r'], max_metrics['auc'], max_metrics['ndcg']))
+        self.results = results
+        return results
+
+
+class ShardedVBPR(_ShardedModel):
     """Item-sharded VBPR behind the reference's model surface (train(), predict_block(), evaluator)."""
+    default_rec = "vbpr"
 
     def __init__(self, data, params, features=None, group=None):
         from .dist import ReplicatedUserVBPR
-        from .engine import EpochWalkSampler
         from .evaluator import Evaluator
         self.data, self.params, self.group = data, params, group
         self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
@@ -89,15 +193,7 @@ class ShardedVBPR:
                                     optimizer=getattr(params, "optimizer", "adam_tf23"),
                                     dense_reduce=getattr(params, "dense_reduce", "gather"))
         self.engine = self.m.eng
-        self.host_staged = dist.get_backend(group) != "nccl"              # gloo (tests, one-GPU rehearsals): collectives on host copies
-        lists = local_positive_lists(data.training_list, self.num_users, self.lo, self.hi)
-        self.local_pos = sum(len(l) for l in lists)
-        n = torch.tensor([self.local_pos], dtype=torch.int64)
-        dist.all_reduce(n, op=dist.ReduceOp.MAX, group=group)
-        self.steps_per_epoch = max(1, int(n.item()) // self.batch)     # every rank steps as often as the fullest shard
-        # a rank whose shard holds no positive still takes every step (with an empty batch: dist.ReplicatedUserVBPR.step)
-        self.sampler = EpochWalkSampler(lists, self.hi - self.lo, device=self.engine.device,
-                                        seed=getattr(params, "init_seed", 0) + 7919 * self.rank) if self.local_pos else None
+        self._epoch_walk(local_positive_lists(data.training_list, self.num_users, self.lo, self.hi), self.hi - self.lo)
         if self.sampler is not None:
             self.sampler.feeds(self.engine)                # (the step hands the sampler's index arrays to the engine unchanged)
         self.directory_parameters = f'batch_{params.batch_size}-D_{d}-K_{k}-lr_{params.lr}-reg_{params.reg}-W_{self.world}'
@@ -107,29 +203,11 @@ class ShardedVBPR:
         self._csr = ev._csr
         self.evaluator = _ShardedEvaluator(self, data, params.top_k)
 
-    # ---- collectives on device tensors (RCCL), or through host copies under gloo ----------------------------------
-    def _all_reduce_sum(self, t):
-        if self.world == 1:
-            return t
-        if self.host_staged:
-            h = t.cpu()
-            dist.all_reduce(h, group=self.group)
-            t.copy_(h)
-        else:
-            dist.all_reduce(t, group=self.group)
-        return t
-
     # ---- scores: every rank's item columns, gathered on rank 0 (output files only: never inside the training loop) ------
     def predict_block(self, u0, u1):
         loc = self.engine.score_block(u0, u1).cpu()                    # [nb, I_shard]
-        sh = (self.num_items + self.world - 1) // self.world
-        pad = torch.zeros((u1 - u0, sh), dtype=torch.float32)
-        pad[:, :loc.shape[1]] = loc
-        parts = [torch.empty_like(pad) for _ in range(self.world)] if self.rank == 0 else None
-        dist.gather(pad, parts, dst=0, group=self.group)
-        if self.rank != 0:
-            return None
-        return torch.cat(parts, dim=1)[:, :self.num_items].numpy()
+        sc = self._gather_to_root(loc, (self.num_items + self.world - 1) // self.world, self.num_items, dim=1)
+        return None if sc is None else sc.numpy()
 
     def metrics(self, K, user_block=4096):
         """The ten means of Evaluator.py:189-193 on the devices; every rank returns the same dict."""
@@ -148,12 +226,7 @@ class ShardedVBPR:
         for key, suf in (("test", "_t"), ("val", "_v")):
             if not rows[key]:
                 continue
-            r = torch.cat(rows[key]).cpu().numpy()
-            if (r[:, 0] == -2).any():
-                raise NotImplementedError("more than 32 held-out items per user: not supported by the sharded evaluator")
-            r = r[r[:, 0] >= 0]
-            hr, p, rr, auc, ndcg = r.mean(axis=0).tolist()
-            out.update({"hr" + suf: hr, "p" + suf: p, "r" + suf: rr, "auc" + suf: auc, "ndcg" + suf: ndcg})
+            out.update(self._means(torch.cat(rows[key]).cpu().numpy(), suf))
         return out
 
     # ---- snapshots: the reference deep-copies / checkpoints the whole model (BPRMF.py:156-160,177-179) ---------------
@@ -180,13 +253,7 @@ class ShardedVBPR:
             if n == "adam_step" or not (n.endswith("Gi") or n.endswith("Bi")):
                 out[n] = v if n == "adam_step" else v.cpu()
                 continue
-            loc = v.cpu()
-            pad = torch.zeros((sh,) + tuple(loc.shape[1:]), dtype=loc.dtype)
-            pad[:loc.shape[0]] = loc
-            parts = [torch.empty_like(pad) for _ in range(self.world)] if self.rank == 0 else None
-            dist.gather(pad, parts, dst=0, group=self.group)
-            if self.rank == 0:
-                out[n] = torch.cat(parts, dim=0)[:self.num_items]
+            out[n] = self._gather_to_root(v.cpu(), sh, self.num_items)
         return out if self.rank == 0 else None
 
     def store_recommendation(self, path):
@@ -209,68 +276,8 @@ class ShardedVBPR:
             if out is not None:
                 out.close()
 
-    # ---- BPRMF.py:127-192 with one step = one global batch of world x batch_size triplets ---------------------------
-    def train(self):
-        params, dev = self.params, self.engine.device
-        max_metrics = {'hr': 0, 'p': 0, 'r': 0, 'auc': 0, 'ndcg': 0}
-        best_state, best_epoch, best_epoch_print = None, getattr(params, "restore_epochs", 1), 'No best epoch found!'
-        results = {}
-        rec = getattr(params, "rec", "vbpr")
-        wdir = os.path.join(configs.weight_dir(), params.dataset, rec)
-        rdir = os.path.join(configs.results_dir(), params.dataset, rec)
-        if self.rank == 0:
-            os.makedirs(wdir, exist_ok=True)
-            os.makedirs(rdir, exist_ok=True)
-        empty = torch.zeros(0, dtype=torch.int32, device=dev)
-        loss_buf = torch.zeros(self.steps_per_epoch, dtype=torch.float32, device=dev)      # read once per epoch: no per-step sync
-        verbose = getattr(params, "verbose", -1)
-        best_metric = getattr(params, "best_metric", "ndcg")
-        if self.rank == 0:
-            print('Start training...')
-        for it in range(1, params.epochs + 1):
-            start = time()
-            for s in range(self.steps_per_epoch):
-                u, i, j = self.sampler.sample(self.batch) if self.sampler is not None else (empty, empty, empty)
-                self.m.step(u, i, j, loss_out=loss_buf, loss_index=s)
-            loss = float(loss_buf.double().sum().item())
-            epoch_text = 'Epoch {0}/{1} \tLoss (rank 0 shard): {2:.3f}'.format(it, params.epochs, loss / self.steps_per_epoch)
-            epoch_print = self.evaluator.eval(it, results, epoch_text, start)               # identical on every rank
-            for metric in max_metrics.keys():                                               # BPRMF.py:152-156
-                if max_metrics[metric] <= results[it][metric + '_v']:
-                    max_metrics[metric] = results[it][metric + '_v']
-                    if metric == best_metric:
-                        best_epoch, best_state, best_epoch_print = it, self.local_state(), epoch_print
-            if (it % verbose == 0 or it == 1) and verbose != -1:
-                full = self.full_state()
-                if self.rank == 0:
-                    torch.save(full, os.path.join(wdir, f'weights-{it}-{self.directory_parameters}.pt'))
-        self.engine.sync_check()
-        last = params.epochs
-        if self.rank == 0:
-            print('Training end...')
-        self.store_recommendation(os.path.join(rdir, f'recs-{last}-{self.directory_parameters}.tsv'))
-        if self.rank == 0:
-            with open(os.path.join(rdir, f'results-metrics-{self.directory_parameters}') + '.pkl', 'wb') as f:
-                pickle.dump(results, f)                                                     # utils/write.py:14-22
-            print("Store Best Model at Epoch {0}".format(best_epoch))
-            print(best_epoch_print)
-        last_state = self.local_state()
-        if best_state is not None:
-            full = self.full_state(best_state)
-            if self.rank == 0:
-                torch.save(full, os.path.join(wdir, f'best-weights-{best_epoch}-{self.directory_parameters}.pt'))
-            self.load_local_state(best_state)
-        self.store_recommendation(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
-        self.load_local_state(last_state)
-        if self.rank == 0:
-            print('End Store Best Model!')
-            print('Best Values for Each Metric:\nHR\tPrec\tRec\tAUC\tnDCG\n{}\t{}\t{}\t{}\t{}\n'.format(
-                max_metrics['hr'], max_metrics['p'], max_metrics['r'], max_metrics['auc'], max_metrics['ndcg']))
-        self.results = results
-        return results
 
-
-class ShardedBPRMF:
+class ShardedBPRMF(_ShardedModel):
     """User-sharded BPRMF behind the reference's model surface (BASELINE.json configs[2]; train_rec --world_size N --shard user
     --rec bprmf).  Rank r owns the users [r*ush, (r+1)*ush) -- their Gu rows, their training positives, their
     evaluation -- and the item rows [r*ish, (r+1)*ish) of Gi / Bi.  A step fetches the rows of the batch's positive and negative
@@ -281,10 +288,11 @@ class ShardedBPRMF:
     evaluator's.  Rank 0 writes the reference's outputs (BPRMF.py:152-183).  --optimizer sgd: the owners add the routed gradient
     rows into their shard; adam_tf23 (the reference's optimizer): they sum them into a gradient table and take the Adam step of
     the whole shard (dist.UserShardedBPRMF)."""
+    default_rec = "bprmf"
 
     def __init__(self, data, params, group=None):
         from .dist import UserShardedBPRMF, shard_size
-        from .engine import Engine, EpochWalkSampler
+        from .engine import Engine
         from .evaluator import Evaluator
         self.data, self.params, self.group = data, params, group
         self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
@@ -305,14 +313,8 @@ class ShardedBPRMF:
                                   max_batch=self.batch, group=group, optimizer=getattr(params, "optimizer", "sgd"))
         self.engine = self.m.eng
         dev = self.engine.device
-        self.host_staged = dist.get_backend(group) != "nccl"
-        lists = [sorted(l) for l in (list(data.training_list[u]) if u < len(data.training_list) else [] for u in range(self.u0, self.u1))]
-        self.local_pos = sum(len(l) for l in lists)
-        n = torch.tensor([self.local_pos], dtype=torch.int64)
-        dist.all_reduce(n, op=dist.ReduceOp.MAX, group=group)
-        self.steps_per_epoch = max(1, int(n.item()) // self.batch)
-        self.sampler = EpochWalkSampler(lists, self.num_items, device=dev,
-                                        seed=getattr(params, "init_seed", 0) + 7919 * self.rank) if self.local_pos else None
+        self._epoch_walk([sorted(l) for l in (list(data.training_list[u]) if u < len(data.training_list) else []
+                                              for u in range(self.u0, self.u1))], self.num_items)
         self.directory_parameters = f'batch_{params.batch_size}-K_{k}-lr_{params.lr}-reg_{params.reg}-W_{self.world}'
         # evaluation engine: this rank's users x ALL items (the gathered item shards are copied into its tables once per epoch)
         self.Gi_full = torch.zeros((self.num_items, k), dtype=torch.float32, device=dev)
@@ -328,9 +330,9 @@ class ShardedBPRMF:
     def _gather_items(self):
         """Item shards of every rank -> this rank's full Gi / Bi (evaluation, snapshots)."""
         for shard, full in ((self.m.Gi_shard, self.Gi_full), (self.m.Bi_col, self.Bi_full.view(-1, 1))):
-            parts = [torch.empty_like(shard.cpu() if self.host_staged else shard) for _ in range(self.world)]
-            dist.all_gather(parts, shard.cpu() if self.host_staged else shard, group=self.group)
-            full.copy_(torch.cat(parts, dim=0)[:self.num_items].to(full.device))
+            parts = shard.new_empty((self.world * shard.shape[0],) + tuple(shard.shape[1:]))
+            all_gather_into(parts, shard, self.group)
+            full.copy_(parts[:self.num_items])
         self.ev_eng.t["Gu"].copy_(self.engine.t["Gu"]) if self.ev_eng.t["Gu"].data_ptr() != self.engine.t["Gu"].data_ptr() else None
         self.ev_eng.tables_dirty()
 
@@ -357,12 +359,7 @@ class ShardedBPRMF:
                 continue
             parts = [None] * self.world
             dist.all_gather_object(parts, mine[key].numpy(), group=self.group)       # (U x 5 doubles in all: small)
-            r = np.concatenate(parts, axis=0)
-            if (r[:, 0] == -2).any():
-                raise NotImplementedError("more than 32 held-out items per user: not supported by the sharded evaluator")
-            r = r[r[:, 0] >= 0]
-            hr, p, rr, auc, ndcg = r.mean(axis=0).tolist()
-            out.update({"hr" + suf: hr, "p" + suf: p, "r" + suf: rr, "auc" + suf: auc, "ndcg" + suf: ndcg})
+            out.update(self._means(np.concatenate(parts, axis=0), suf))
         return out
 
     def local_state(self):
@@ -378,14 +375,7 @@ class ShardedBPRMF:
         sd = self.local_state() if sd is None else sd
         out = {}
         for n, total in (("Gu", self.num_users), ("Gi", self.num_items), ("Bi", self.num_items)):
-            loc = sd[n].cpu()
-            sh = self.ush if n == "Gu" else self.ish
-            pad = torch.zeros((sh,) + tuple(loc.shape[1:]), dtype=loc.dtype)
-            pad[:min(sh, loc.shape[0])] = loc[:sh]
-            parts = [torch.empty_like(pad) for _ in range(self.world)] if self.rank == 0 else None
-            dist.gather(pad, parts, dst=0, group=self.group)
-            if self.rank == 0:
-                out[n] = torch.cat(parts, dim=0)[:total]
+            out[n] = self._gather_to_root(sd[n].cpu(), self.ush if n == "Gu" else self.ish, total)
         if self.rank == 0:
             out["Bi"] = out["Bi"].reshape(-1)
         return out if self.rank == 0 else None
@@ -415,66 +405,6 @@ class ShardedBPRMF:
         if self.rank == 0:
             with open(path, 'w') as f:
                 f.write("".join(parts))
-
-    def train(self):
-        params, dev = self.params, self.engine.device
-        max_metrics = {'hr': 0, 'p': 0, 'r': 0, 'auc': 0, 'ndcg': 0}
-        best_state, best_epoch, best_epoch_print = None, getattr(params, "restore_epochs", 1), 'No best epoch found!'
-        results = {}
-        rec = getattr(params, "rec", "bprmf")
-        wdir = os.path.join(configs.weight_dir(), params.dataset, rec)
-        rdir = os.path.join(configs.results_dir(), params.dataset, rec)
-        if self.rank == 0:
-            os.makedirs(wdir, exist_ok=True)
-            os.makedirs(rdir, exist_ok=True)
-            print('Start training...')
-        empty = torch.zeros(0, dtype=torch.int32, device=dev)
-        loss_buf = torch.zeros(self.steps_per_epoch, dtype=torch.float32, device=dev)
-        verbose, best_metric = getattr(params, "verbose", -1), getattr(params, "best_metric", "ndcg")
-        for it in range(1, params.epochs + 1):
-            start = time()
-            loss_buf.zero_()
-            for s in range(self.steps_per_epoch):
-                u, i, j = self.sampler.sample(self.batch) if self.sampler is not None else (empty, empty, empty)
-                self.m.step(u, i, j, loss_out=loss_buf, loss_index=s)
-            loss = float(loss_buf.double().sum().item())
-            epoch_text = 'Epoch {0}/{1} \tLoss (rank 0 shard): {2:.3f}'.format(it, params.epochs, loss / self.steps_per_epoch)
-            epoch_print = self.evaluator.eval(it, results, epoch_text, start)
-            for metric in max_metrics.keys():
-                if max_metrics[metric] <= results[it][metric + '_v']:
-                    max_metrics[metric] = results[it][metric + '_v']
-                    if metric == best_metric:
-                        best_epoch, best_state, best_epoch_print = it, self.local_state(), epoch_print
-            if (it % verbose == 0 or it == 1) and verbose != -1:
-                full = self.full_state()
-                if self.rank == 0:
-                    torch.save(full, os.path.join(wdir, f'weights-{it}-{self.directory_parameters}.pt'))
-        self.engine.sync_check()
-        if self.m.x.overflowed():
-            raise RuntimeError("a row-routing bucket overflowed (dist.UserShardedBPRMF: raise `slack`)")
-        last = params.epochs
-        if self.rank == 0:
-            print('Training end...')
-        self.store_recommendation(os.path.join(rdir, f'recs-{last}-{self.directory_parameters}.tsv'))
-        if self.rank == 0:
-            with open(os.path.join(rdir, f'results-metrics-{self.directory_parameters}') + '.pkl', 'wb') as f:
-                pickle.dump(results, f)
-            print("Store Best Model at Epoch {0}".format(best_epoch))
-            print(best_epoch_print)
-        last_state = self.local_state()
-        if best_state is not None:
-            full = self.full_state(best_state)
-            if self.rank == 0:
-                torch.save(full, os.path.join(wdir, f'best-weights-{best_epoch}-{self.directory_parameters}.pt'))
-            self.load_local_state(best_state)
-        self.store_recommendation(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
-        self.load_local_state(last_state)
-        if self.rank == 0:
-            print('End Store Best Model!')
-            print('Best Values for Each Metric:\nHR\tPrec\tRec\tAUC\tnDCG\n{}\t{}\t{}\t{}\t{}\n'.format(
-                max_metrics['hr'], max_metrics['p'], max_metrics['r'], max_metrics['auc'], max_metrics['ndcg']))
-        self.results = results
-        return results
 
 
 from .evaluator import Evaluator as _Evaluator                                              # noqa: E402
