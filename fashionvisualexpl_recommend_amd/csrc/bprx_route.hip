@@ -10,8 +10,11 @@
 //                           Positions are taken per workgroup: requests counted per owner in LDS, one cursor atomic per
 //                           (workgroup, owner).  The caller pre-fills send_idx with -1 and zeroes the cursors
 //                           (bprx_route_reset).
-//   bprx_route_gather       owner side: out[q] = [t0[idx[q]] | t1[idx[q]]] for the requested rows (idx < 0: slot unused, skipped)
-//   bprx_route_unpack       requester side: dst0[r] | dst1[r] = got[slot[r]]  (slot < 0: zero row)
+//   bprx_route_gather       owner side: out[q] = [t0[idx[q]] | t1[idx[q]]] for the requested rows (idx < 0: slot unused, skipped;
+//                           idx past the shard's num_rows -- an id in [total, nranks * rows_per_rank) of a short last shard,
+//                           which plan routes because it sees rows_per_rank only: zero row, and *err = 1 in the _checked form)
+//   bprx_route_unpack       requester side: dst0[r] | dst1[r] = got[slot[r]]  (slot < 0: zero row; an own row past own_rows:
+//                           zero row, and *err = 1 in the _checked form)
 //   bprx_route_pack         requester side, gradients: send[slot[r]] = [src0[r] | src1[r]], and src rows back to zero
 //   bprx_route_scatter_add  owner side: t0[idx[q]] += scale * rows[q][0:w0], t1[idx[q]] += scale * rows[q][w0:w0+w1]
 // A routed row is [w0 floats | w1 floats | pad to a multiple of 4 floats]; a part moves 16 B per lane where its width and
@@ -131,21 +134,29 @@ __device__ __forceinline__ void row_add(float *__restrict__ t0, int w0, float *_
 
 __global__ __launch_bounds__(256) void k_route_gather(const float *__restrict__ t0, int w0, const float *__restrict__ t1, int w1,
                                                       int rows0, const int32_t *__restrict__ idx, int64_t n,
-                                                      float *__restrict__ out, int v0, int v1, int32_t *__restrict__ cnt) {
+                                                      float *__restrict__ out, int v0, int v1, int32_t *__restrict__ cnt,
+                                                      int32_t *__restrict__ err) {
   const int64_t q = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
   const int lane = threadIdx.x & 15;
   if (q >= n) return;
   const int i = idx[q];
-  if ((unsigned)i >= (unsigned)rows0) return;             // unused slot (or a bad id): the requester never reads it
-  if (cnt && lane == 0) atomicAdd(cnt + i, 1);            // its gradient will come back to this row (k_route_scatter_add)
+  if (i < 0) return;                                      // unused slot: the requester never reads it
   float *o = out + (size_t)q * route_ps(w0, w1);
+  if (i >= rows0) {                                       // a row past this shard's end (ids in [total, nranks * rows_per_rank)
+    row_zero(o, w0, lane, v0);                            // of a short last shard): the requester reads a zero row, its
+    if (w1) row_zero(o + w0, w1, lane, v1);               // gradient is dropped (scatter_add skips the slot), and it is reported
+    if (err && lane == 0) *err = 1;
+    return;
+  }
+  if (cnt && lane == 0) atomicAdd(cnt + i, 1);            // its gradient will come back to this row (k_route_scatter_add)
   row_copy(o, t0 + (size_t)i * w0, w0, lane, v0);
   if (w1) row_copy(o + w0, t1 + (size_t)i * w1, w1, lane, v1);
 }
 
 __global__ __launch_bounds__(256) void k_route_unpack(const float *__restrict__ got, const int32_t *__restrict__ slot, int64_t n,
                                                       float *__restrict__ d0, int w0, float *__restrict__ d1, int w1, int v0, int v1,
-                                                      const float *__restrict__ t0, const float *__restrict__ t1, int rows0) {
+                                                      const float *__restrict__ t0, const float *__restrict__ t1, int rows0,
+                                                      int32_t *__restrict__ err) {
   const int64_t r = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
   const int lane = threadIdx.x & 15;
   if (r >= n) return;
@@ -156,6 +167,7 @@ __global__ __launch_bounds__(256) void k_route_unpack(const float *__restrict__ 
     if (w1) row_copy(d1 + (size_t)r * w1, t1 + (size_t)i * w1, w1, lane, v1);
     return;
   }
+  if (s <= -2 && t0 && err && lane == 0) *err = 1;        // an own row past the end of a short last shard: zero row, reported
   if (s < 0) {
     row_zero(d0 + (size_t)r * w0, w0, lane, v0);
     if (w1) row_zero(d1 + (size_t)r * w1, w1, lane, v1);
@@ -185,6 +197,8 @@ __global__ __launch_bounds__(256) void k_route_pack(float *__restrict__ s0, int 
   float *a = s0 + (size_t)r * w0, *b = w1 ? s1 + (size_t)r * w1 : nullptr;
   if (s <= -2 && t0 && (unsigned)(-2 - s) < (unsigned)rows0) {      // own row: added here
     row_add(t0, w0, t1, w1, -2 - s, a, b, lane, vt0, vt1, scale, own_cnt);
+  } else if (s <= -2) {                                   // own row never added (past a short last shard, or no own tables):
+    if (own_cnt && lane == 0) own_cnt[-2 - s] = 0;        // plan counted it; its count returns to zero here
   } else if (s >= 0) {
     float *o = send + (size_t)s * route_ps(w0, w1);
     row_copy(o, a, w0, lane, v0);
@@ -236,23 +250,34 @@ extern "C" int bprx_route_plan(const int32_t *ids, int64_t n, const int32_t *ids
   return launched();
 }
 
-extern "C" int bprx_route_gather(const float *t0, int32_t w0, const float *t1, int32_t w1, int32_t num_rows, const int32_t *idx,
-                                 int64_t n, float *out, int32_t *cnt, void *stream) {
+extern "C" int bprx_route_gather_checked(const float *t0, int32_t w0, const float *t1, int32_t w1, int32_t num_rows,
+                                         const int32_t *idx, int64_t n, float *out, int32_t *cnt, int32_t *err, void *stream) {
   if (!t0 || !idx || !out || w0 <= 0 || w1 < 0 || (w1 && !t1) || num_rows <= 0 || n < 0) return BPRX_E_INVALID;
   if (n == 0) return BPRX_OK;
   hipLaunchKernelGGL(k_route_gather, dim3(rows_grid(n)), dim3(256), 0, (hipStream_t)stream, t0, w0, t1, w1, num_rows, idx, n, out,
-                     vec_ok(w0, t0, out), w0 % 4 == 0 ? vec_ok(w1, t1, out) : 0, cnt);
+                     vec_ok(w0, t0, out), w0 % 4 == 0 ? vec_ok(w1, t1, out) : 0, cnt, err);
   return launched();
 }
 
-extern "C" int bprx_route_unpack(const float *got, const int32_t *slot, int64_t n, float *dst0, int32_t w0, float *dst1, int32_t w1,
-                                 const float *own0, const float *own1, int32_t own_rows, void *stream) {
+extern "C" int bprx_route_unpack_checked(const float *got, const int32_t *slot, int64_t n, float *dst0, int32_t w0, float *dst1,
+                                         int32_t w1, const float *own0, const float *own1, int32_t own_rows, int32_t *err,
+                                         void *stream) {
   if (!got || !slot || !dst0 || w0 <= 0 || w1 < 0 || (w1 && !dst1) || n < 0 || (own0 && w1 && !own1)) return BPRX_E_INVALID;
   if (n == 0) return BPRX_OK;
   hipLaunchKernelGGL(k_route_unpack, dim3(rows_grid(n)), dim3(256), 0, (hipStream_t)stream, got, slot, n, dst0, w0, dst1, w1,
                      vec_ok(w0, dst0, got) & (own0 ? vec_ok(w0, own0, got) : 1),
-                     w0 % 4 == 0 ? (vec_ok(w1, dst1, got) & (own1 ? vec_ok(w1, own1, got) : 1)) : 0, own0, own1, own_rows);
+                     w0 % 4 == 0 ? (vec_ok(w1, dst1, got) & (own1 ? vec_ok(w1, own1, got) : 1)) : 0, own0, own1, own_rows, err);
   return launched();
+}
+
+extern "C" int bprx_route_gather(const float *t0, int32_t w0, const float *t1, int32_t w1, int32_t num_rows, const int32_t *idx,
+                                 int64_t n, float *out, int32_t *cnt, void *stream) {
+  return bprx_route_gather_checked(t0, w0, t1, w1, num_rows, idx, n, out, cnt, nullptr, stream);
+}
+
+extern "C" int bprx_route_unpack(const float *got, const int32_t *slot, int64_t n, float *dst0, int32_t w0, float *dst1, int32_t w1,
+                                 const float *own0, const float *own1, int32_t own_rows, void *stream) {
+  return bprx_route_unpack_checked(got, slot, n, dst0, w0, dst1, w1, own0, own1, own_rows, nullptr, stream);
 }
 
 extern "C" int bprx_route_pack(float *src0, int32_t w0, float *src1, int32_t w1, const int32_t *slot, int64_t n, float *send,

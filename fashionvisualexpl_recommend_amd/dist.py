@@ -126,7 +126,8 @@ class UserRowExchange:
     # overflows is reported by overflowed() -- a device flag, read when the caller next synchronises anyway -- and its
     # surplus rows take part with zero rows / dropped gradients in that step.
     def overflowed(self):
-        """True if any bucket of any plan_fixed() / plan_native() since the last call overflowed (synchronises)."""
+        """True if any bucket of any plan_fixed() / plan_native() since the last call overflowed, or fetch_native() met a row
+        id past the end of a short last shard (synchronises)."""
         f = bool(self._overflow.item()) if getattr(self, "_overflow", None) is not None else False
         self._overflow = None
         if getattr(self, "_nat", None) is not None:
@@ -190,11 +191,13 @@ class UserRowExchange:
         w0, w1 = t0.shape[1], (t1.shape[1] if t1 is not None else 0)
         got = nat["rows_out"]
         if self.world > 1:
-            self._rc(nat["lib"].bprx_route_gather(self._p(t0), w0, self._p(t1), w1, t0.shape[0], self._p(recv_idx), recv_idx.numel(),
-                                                  self._p(nat["rows_out"]), self._p(nat["cnt"]), self._s()), "route_gather")
+            self._rc(nat["lib"].bprx_route_gather_checked(self._p(t0), w0, self._p(t1), w1, t0.shape[0], self._p(recv_idx), recv_idx.numel(),
+                                                  self._p(nat["rows_out"]), self._p(nat["cnt"]), self._p(nat["overflow"]), self._s()),
+                     "route_gather")
             got = self._a2a(nat["rows_out"])
-        self._rc(nat["lib"].bprx_route_unpack(self._p(got), self._p(nat["slot"]), nat["n"], self._p(dst0), w0, self._p(dst1), w1,
-                                              self._p(t0), self._p(t1), t0.shape[0], self._s()), "route_unpack")
+        self._rc(nat["lib"].bprx_route_unpack_checked(self._p(got), self._p(nat["slot"]), nat["n"], self._p(dst0), w0, self._p(dst1), w1,
+                                              self._p(t0), self._p(t1), t0.shape[0], self._p(nat["overflow"]), self._s()),
+                 "route_unpack")
 
     def give_back_native(self, g0, g1, recv_idx, t0, t1, scale):
         """The staging gradient rows (g0 | g1, row r = request r; returned to zero) travel to the owners, who add scale * row into

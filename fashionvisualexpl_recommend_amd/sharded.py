@@ -31,6 +31,8 @@ from . import configs
 from .dist import all_gather_into, all_reduce
 from .synth import glorot_uniform
 
+EVAL_MAX = 32                       # held-out items per user that the device evaluation kernels take (EVMAX, bprx_eval.hip)
+
 
 def item_range(num_items, rank, world):
     """[lo, hi) of rank's item shard: equal shards of ceil(I / world), the last one shorter."""
@@ -94,11 +96,26 @@ class _ShardedModel:
 
     @staticmethod
     def _means(r, suf):
-        """The five means of Evaluator.py:189-193 over one held-out list's per-user metric rows (-1: no held-out item)."""
-        if (r[:, 0] == -2).any():
-            raise NotImplementedError("more than 32 held-out items per user: not supported by the sharded evaluator")
+        """The five means of Evaluator.py:189-193 over one held-out list's per-user metric rows (-1: no held-out item).  The
+        rows the device kernels mark -2 (more than EVAL_MAX held-out items) were recomputed by the caller (_host_rows)."""
+        assert not (r[:, 0] == -2).any(), "metric rows of users with more than %d held-out items left unresolved" % EVAL_MAX
         r = r[r[:, 0] >= 0]
         return dict(zip([n + suf for n in ("hr", "p", "r", "auc", "ndcg")], r.mean(axis=0).tolist()))
+
+    def _host_rows(self, out, full, users, lst, K):
+        """The metric rows of users with more than EVAL_MAX held-out items (the device kernels mark them -2), recomputed by
+        evaluator._eval_block, as the single-GPU Evaluator does.  out: the block's [nb, 5] device rows; users: [(row in the
+        block, global user id)]; full: their full-width score rows (host [len(users), I]); lst: the held-out lists."""
+        from .evaluator import _eval_block
+        train = self.data.training_list
+        rows = _eval_block(full, 0, [train[u] if u < len(train) else [] for _, u in users], [lst[u] for _, u in users], K)
+        idx = torch.as_tensor([b for b, _ in users], device=out.device)
+        out[idx] = torch.as_tensor(np.array(rows, dtype=np.float64), device=out.device)
+
+    @staticmethod
+    def _long_users(lst, u0, u1):
+        """[(row in the block, user)] of the users of [u0, u1) whose held-out list is too long for the device kernels."""
+        return [(u - u0, u) for u in range(u0, min(u1, len(lst))) if len(lst[u]) > EVAL_MAX]
 
     # ---- BPRMF.py:127-192 with one step = one global batch of world x batch_size triplets ---------------------------
     def train(self):
@@ -222,12 +239,28 @@ class ShardedVBPR(_ShardedModel):
                 sp = self._all_reduce_sum(eng.eval_pos(u0, u1, sc, self.lo, self.num_items, self._csr[key]))
                 cn = self._all_reduce_sum(eng.eval_counts(u0, u1, sc, self.lo, self.num_items, self._csr["train"],
                                                           self._csr[key], sp))
-                rows[key].append(eng.eval_finish(u0, u1, self.num_items, self._csr[key], sp, cn, K))
+                r = eng.eval_finish(u0, u1, self.num_items, self._csr[key], sp, cn, K)
+                lst = self.data.test_list if key == "test" else self.data.validation_list
+                long = self._long_users(lst, u0, u1)
+                if long:                                        # (the same users on every rank: the lists are global)
+                    self._host_rows(r, self._gather_rows(sc, [b for b, _ in long]), long, lst, K)
+                rows[key].append(r)
         for key, suf in (("test", "_t"), ("val", "_v")):
             if not rows[key]:
                 continue
             out.update(self._means(torch.cat(rows[key]).cpu().numpy(), suf))
         return out
+
+    def _gather_rows(self, sc, rows):
+        """Full-width score rows sc[rows] on EVERY rank (host [len(rows), I]): an all-gather of every rank's columns of those
+        rows only."""
+        sh = (self.num_items + self.world - 1) // self.world
+        loc = sc.index_select(0, torch.as_tensor(rows, device=sc.device))
+        pad = loc.new_zeros((len(rows), sh))
+        pad[:, :loc.shape[1]] = loc
+        parts = pad.new_empty((self.world * len(rows), sh))
+        all_gather_into(parts, pad, self.group)
+        return parts.view(self.world, len(rows), sh).permute(1, 0, 2).reshape(len(rows), -1)[:, :self.num_items].cpu().numpy()
 
     # ---- snapshots: the reference deep-copies / checkpoints the whole model (BPRMF.py:156-160,177-179) ---------------
     def local_state(self):
@@ -344,10 +377,16 @@ class ShardedBPRMF(_ShardedModel):
                 out[key] = torch.zeros((0, 5), dtype=torch.float64)
                 continue
             rows = []
+            lst = self.data.test_list if key == "test" else self.data.validation_list
             for b0 in range(0, nu, 4096):
                 b1 = min(nu, b0 + 4096)
                 sc = self.ev_eng.score_block(b0, b1)
-                rows.append(self.ev_eng.eval_users(b0, b1, sc, self._csr["train"], self._csr[key], K))
+                r = self.ev_eng.eval_users(b0, b1, sc, self._csr["train"], self._csr[key], K)
+                long = self._long_users(lst, self.u0 + b0, self.u0 + b1)
+                if long:                                        # this rank's full-width score rows of those users
+                    idx = torch.as_tensor([b for b, _ in long], device=sc.device)
+                    self._host_rows(r, sc.index_select(0, idx).cpu().numpy(), long, lst, K)
+                rows.append(r)
             out[key] = torch.cat(rows).cpu()
         return out
 

@@ -238,7 +238,11 @@ BPRX_API int bprx_scatter_add(float *table, int32_t num_rows, int32_t num_cols, 
    counts all-zero again by themselves (see bprx_route.hip).  Pass the same array to the pair (plan, pack) and another one to the
    pair (gather, scatter_add).
    bprx_route_pack with send_idx != NULL also returns send_idx (nslots entries) to -1 and the nranks cursors to 0 for the next
-   step's plan: bprx_route_reset is then needed once, before the first step. */
+   step's plan: bprx_route_reset is then needed once, before the first step.
+   A short last shard (num_rows < rows_per_rank): plan routes an id in [total, nranks * rows_per_rank) to the last rank, whose
+   gather writes a zero row for it; unpack does the same for such an id among the requester's own rows (own0 given).  The row's
+   gradient is dropped.  bprx_route_gather_checked / bprx_route_unpack_checked are the same calls with one more argument,
+   `err` (int32, optional): set to 1 when that happens. */
 BPRX_API int bprx_route_reset(int32_t *send_idx, int64_t nslots, int32_t *cursor, int32_t nranks, void *stream);
 BPRX_API int bprx_route_plan(const int32_t *ids, int64_t n, const int32_t *ids_b, int64_t n_b, int32_t rows_per_rank, int32_t nranks,
                              int32_t cap, int32_t my_rank, int32_t *slot, int32_t *send_idx, int32_t *cursor, int32_t *overflow,
@@ -247,6 +251,10 @@ BPRX_API int bprx_route_gather(const float *t0, int32_t w0, const float *t1, int
                                int64_t n, float *out, int32_t *cnt, void *stream);
 BPRX_API int bprx_route_unpack(const float *got, const int32_t *slot, int64_t n, float *dst0, int32_t w0, float *dst1, int32_t w1,
                                const float *own0, const float *own1, int32_t own_rows, void *stream);
+BPRX_API int bprx_route_gather_checked(const float *t0, int32_t w0, const float *t1, int32_t w1, int32_t num_rows,
+                                       const int32_t *idx, int64_t n, float *out, int32_t *cnt, int32_t *err, void *stream);
+BPRX_API int bprx_route_unpack_checked(const float *got, const int32_t *slot, int64_t n, float *dst0, int32_t w0, float *dst1,
+                                       int32_t w1, const float *own0, const float *own1, int32_t own_rows, int32_t *err, void *stream);
 BPRX_API int bprx_route_pack(float *src0, int32_t w0, float *src1, int32_t w1, const int32_t *slot, int64_t n, float *send,
                              float *own0, float *own1, int32_t own_rows, float scale, int32_t *own_cnt, int32_t *send_idx,
                              int64_t nslots, int32_t *cursor, int32_t nranks, void *stream);
