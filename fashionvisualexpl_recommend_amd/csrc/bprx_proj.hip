@@ -1238,11 +1238,14 @@ void launch_v10(bprx_handle *h, int64_t nrows, float *Pout, hipStream_t s, int n
 
 // P = F.[E|Bp] over the whole table.  BPRX_FWD_VARIANT=0: the plain kernel (k_proj_fwd_bf16: two barriers per chunk, nothing
 // overlapped) -- the reference every streaming kernel is tested against, and the fallback for odd widths.
-//   shape                                           kernel                              covered by
-//   <= 9 column tiles (d <= 143), bf16 or fp8       k_proj_fwd_bf16_v10                 test_gpu_variants::test_lds_staged_forward...
-//   >= 10 tiles, fp8 (configs[4]: d = 256)          k_proj_fwd_f8s (scaled fp8 MFMA)    test_gpu_variants::test_wide_projection...
-//   >= 10 tiles, bf16 (or BPRX_F8S=0)               v10 in right-aligned passes of 9    test_gpu_variants::test_wide_projection...
-//   feat_dim not a multiple of 256 (512 for fp8)    k_proj_fwd_bf16 (plain)             test_gpu_parity (D = 128 / 384 shapes)
+//   shape                                           kernel                              covered by (fp64 reference: test_gpu_projections)
+//   <= 9 column tiles (d <= 143), bf16 or fp8       k_proj_fwd_bf16_v10                 test_forward_whole_table[v10-*], ..._beyond_the_cache;
+//                                                                                       test_gpu_variants::test_lds_staged_forward...
+//   >= 10 tiles, fp8 (configs[4]: d = 256)          k_proj_fwd_f8s (scaled fp8 MFMA)    test_forward_whole_table[f8s-*]; test_wide_projection...
+//   >= 10 tiles, bf16 (or BPRX_F8S=0)               v10 in right-aligned passes of 9    test_forward_whole_table[passes-*, f8s_off-*]
+//   feat_dim not a multiple of 256 (512 for fp8)    k_proj_fwd_bf16 (plain)             test_forward_whole_table[oddD-*, plain-*]; test_gpu_parity
+//   row list (bprx_score_pairs, list mode)          launch_fwd_rows / f8s over the list test_forward_row_list[split / mt1 / mt2 / mt4 / f8s_rows-*]
+//   fp32 features                                   k_proj_fwd_f32_mfma, k_proj_fwd_f32 test_forward_whole_table[fp32-*], test_forward_row_list[fp32-*]
 template <int NT>
 int launch_fwd_nt(bprx_handle *h, const int32_t *rows, int64_t nrows, float *Pout, hipStream_t s) {
   constexpr int MTD = NT <= 9 ? 2 : 1;
@@ -1252,7 +1255,9 @@ int launch_fwd_nt(bprx_handle *h, const int32_t *rows, int64_t nrows, float *Pou
   const bool plain = h->fwd_variant == 0 || Deq % 256 != 0 || rows;
   if (!plain) {
     if constexpr (NT >= 10) {
-      static const int f8s_on = getenv("BPRX_F8S") ? atoi(getenv("BPRX_F8S")) : 1;   // 0: column-range passes (A/B, tests)
+      // 0: column-range passes (A/B, tests).  Read at every launch, as the row-list branch of bprx_launch_proj_fwd does (a
+      // function-static copy kept the value of the process's first launch of each NT: a later BPRX_F8S=0 was ignored)
+      const bool f8s_on = !(getenv("BPRX_F8S") && atoi(getenv("BPRX_F8S")) == 0);
       if (f8 && f8s_on && h->EtS && h->cfg.feat_dim % 256 == 0) {
         launch_f8s<NT>(h, nullptr, nrows, nullptr, 0, Pout, s, 1);
         return 0;
@@ -1310,6 +1315,8 @@ int launch_bwd_rows(bprx_handle *h, int64_t bound, hipStream_t s) {
 //   fp8, or > 9 column tiles                     8 waves, 2 tiles in flight, double-buffered LDS    MFMA-paced: one barrier per tile (c5, c2fp8);
 //                                                > 9 tiles: waves as a 4 x 2 grid (NS = 2)
 //   D % 256 != 0 (bf16)                          4 waves (128 columns), 2 tiles in flight           small / odd feature widths
+// covered against an fp64 reference by tests/test_gpu_projections.py: test_backward_whole_table[pd3-* (1 / 2 / 3 / 4 / 25 tiles per
+// split), db2-fp8-*, ns2-*, w4-*, grid-* (SK % 8 != 0: no XCD remap), fp32-*], test_backward_row_list (launch_bwd_rows, ROWS)
 template <int NT>
 int launch_bwd_nt(bprx_handle *h, hipStream_t s) {
   const int D = h->cfg.feat_dim, I = h->cfg.num_items;
