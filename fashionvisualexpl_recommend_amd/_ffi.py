@@ -36,6 +36,15 @@ class Config(C.Structure):
                 ("epsilon", C.c_float), ("flags", C.c_int32), ("feat_scale", C.c_float)]
 
 
+FACTORED_FIELDS = ["Ea", "Eb", "A", "Ap", "m_Ea", "v_Ea", "m_Eb", "v_Eb", "m_A", "v_A", "m_Ap", "v_Ap"]
+
+
+class Factored(C.Structure):
+    """bprx_factored: GradFashion's factor tables (include/bprx.h)."""
+    _fields_ = [("feat_dim_a", C.c_int32), ("feat_dim_b", C.c_int32), ("embed_a", C.c_int32), ("embed_b", C.c_int32),
+                ("neg_bias_reg", C.c_float)] + [(n, C.c_void_p) for n in FACTORED_FIELDS]
+
+
 TABLE_FIELDS = ["Gu", "Gi", "Bi", "Tu", "F", "E", "Bp", "m_Gu", "v_Gu", "m_Gi", "v_Gi", "m_Bi", "v_Bi",
                 "m_Tu", "v_Tu", "m_E", "v_E", "m_Bp", "v_Bp"]
 
@@ -67,6 +76,8 @@ def lib():
         "bprx_destroy": (C.c_int, [vp]),
         "bprx_last_error": (C.c_char_p, [vp]),
         "bprx_bind_tables": (C.c_int, [vp, C.POINTER(Tables)]),
+        "bprx_bind_factored": (C.c_int, [vp, C.POINTER(Tables), C.POINTER(Factored)]),
+        "bprx_explain_pairs": (C.c_int, [vp, vp, vp, i64, vp, vp]),
         "bprx_set_hyper": (C.c_int, [vp, f32, f32]),
         "bprx_tables_dirty": (C.c_int, [vp, vp]),
         "bprx_set_adam_step": (C.c_int, [vp, i64, vp]),
@@ -133,7 +144,7 @@ def lib():
     return L
 
 
-EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error", "bprx_bind_tables", "bprx_set_hyper", "bprx_tables_dirty",
+EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error", "bprx_bind_tables", "bprx_bind_factored", "bprx_explain_pairs", "bprx_set_hyper", "bprx_tables_dirty",
            "bprx_set_adam_step", "bprx_get_adam_step", "bprx_adam_is_lazy", "bprx_sync_adam", "bprx_score_pairs", "bprx_step", "bprx_step_begin",
            "bprx_step_begin_sparse", "bprx_step_begin_dense", "bprx_sum_dense_parts",
            "bprx_dense_grad", "bprx_step_end", "bprx_step_project", "bprx_user_grad", "bprx_clear_user_grad", "bprx_item_grad", "bprx_clear_item_grad",

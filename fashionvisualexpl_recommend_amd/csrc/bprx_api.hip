@@ -8,6 +8,8 @@
 
 static char g_create_err[512] = "";
 
+static int check_ready(bprx_handle *h, int64_t B);
+
 extern "C" int bprx_abi_version(void) { return BPRX_ABI_VERSION; }
 
 extern "C" const char *bprx_last_error(const bprx_handle *h) { return h ? h->err : g_create_err; }
@@ -44,7 +46,7 @@ static bool graph_sig_eq(const bprx_handle::GraphSig &a, const bprx_handle::Grap
 
 static void free_scratch(bprx_handle *h) {
   void *ptrs[] = {h->dGu, h->dGi, h->dBi, h->dTu, h->flagU, h->flagI, h->lossb, h->loss_acc, h->errflag,
-                  h->P,   h->W,   h->Wb, h->Ppair, h->Et, h->EtF, h->EtS, h->dEp, h->part, h->qs, h->Ft, h->seg_rank, h->seg_cnt, h->seg_ptr, h->seg_cursor, h->seg_lead, h->seg_ent, h->hot_done, h->uslot_of, h->ulist, h->uold, h->own8, h->loc8, h->cntU, h->cntI, h->ilist, h->ilist_n, h->lastU, h->lastI, h->lr_hist, h->slist, h->slist_n, h->msg_cursor, h->msg_next};
+                  h->P,   h->W,   h->Wb, h->Ppair, h->Et, h->EtF, h->EtS, h->dEp, h->part, h->qs, h->Ft, h->seg_rank, h->seg_cnt, h->seg_ptr, h->seg_cursor, h->seg_lead, h->seg_ent, h->hot_done, h->uslot_of, h->ulist, h->uold, h->own8, h->loc8, h->cntU, h->cntI, h->ilist, h->ilist_n, h->lastU, h->lastI, h->lr_hist, h->slist, h->slist_n, h->msg_cursor, h->msg_next, h->gF};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
 }
@@ -92,6 +94,7 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
   if (!h) CFAIL(BPRX_E_NOMEM, "out of host memory");
   memset(h, 0, sizeof(*h));
   h->cfg = *cfg;
+  h->neg_bias_reg = 0.1f;                                  // VBPR.py:125 (BPRMF.py:111); GradFashion: bprx_bind_factored
   if (!vb) { h->cfg.embed_d = 0; h->cfg.feat_dim = 0; }
   const size_t U = cfg->num_users, I = cfg->num_items, k = cfg->embed_k, d = h->cfg.embed_d, D = h->cfg.feat_dim;
   const size_t MB = cfg->max_batch;
@@ -320,7 +323,7 @@ extern "C" int bprx_profile_read(bprx_handle *h, double *ms, int64_t *launches) 
   return BPRX_OK;
 }
 
-extern "C" int bprx_bind_tables(bprx_handle *h, const bprx_tables *t) {
+static int bind_tables(bprx_handle *h, const bprx_tables *t, bool factored) {
   if (!h || !t) return BPRX_E_INVALID;
   if (!t->Gu || !t->Gi || !t->Bi) BPRX_FAIL(h, BPRX_E_INVALID, "bind_tables: Gu, Gi, Bi are required");
   const bool vb = h->cfg.model == BPRX_MODEL_VBPR;
@@ -328,12 +331,14 @@ extern "C" int bprx_bind_tables(bprx_handle *h, const bprx_tables *t) {
   if (h->cfg.optimizer == BPRX_OPT_ADAM_TF23) {
     if (!t->m_Gu || !t->v_Gu || !t->m_Gi || !t->v_Gi || !t->m_Bi || !t->v_Bi)
       BPRX_FAIL(h, BPRX_E_INVALID, "bind_tables: adam_tf23 needs m_/v_ slots for Gu, Gi, Bi");
-    if (vb && (!t->m_Tu || !t->v_Tu || !t->m_E || !t->v_E || !t->m_Bp || !t->v_Bp))
+    if (vb && (!t->m_Tu || !t->v_Tu || (!factored && (!t->m_E || !t->v_E || !t->m_Bp || !t->v_Bp))))
       BPRX_FAIL(h, BPRX_E_INVALID, "bind_tables: adam_tf23 needs m_/v_ slots for Tu, E, Bp");
   }
   if (((uintptr_t)t->Gu | (uintptr_t)t->Gi | (uintptr_t)t->Tu | (uintptr_t)t->F | (uintptr_t)t->E) & 15)
     BPRX_FAIL(h, BPRX_E_INVALID, "bind_tables: table base pointers must be 16-byte aligned");
   h->t = *t;
+  h->factored = factored;
+  if (!factored) h->neg_bias_reg = 0.1f;
   h->et_valid = h->p_valid = h->absmax_valid = false;
   graph_drop(h);                            // a captured step holds the old table pointers
   {
@@ -344,9 +349,61 @@ extern "C" int bprx_bind_tables(bprx_handle *h, const bprx_tables *t) {
   return bprx_launch_adam_reset(h, h->adam_t, 0);   // every bound row counts as current at optimizer.iterations
 }
 
+extern "C" int bprx_bind_tables(bprx_handle *h, const bprx_tables *t) { return bind_tables(h, t, false); }
+
+extern "C" int bprx_bind_factored(bprx_handle *h, const bprx_tables *t, const bprx_factored *f) {
+  if (!h || !t || !f) return BPRX_E_INVALID;
+  const bprx_config &c = h->cfg;
+  if (c.model != BPRX_MODEL_VBPR) BPRX_FAIL(h, BPRX_E_INVALID, "bind_factored: needs a VBPR handle");
+  if (c.feat_dtype == BPRX_F_FP8) BPRX_FAIL(h, BPRX_E_INVALID, "bind_factored: fp8 features are not supported (fp32 or bf16)");
+  if (c.flags & (BPRX_FLAG_EXPORT_USER_GRAD | BPRX_FLAG_EXPORT_ITEM_GRAD))
+    BPRX_FAIL(h, BPRX_E_INVALID, "bind_factored: exported gradients (multi-GPU) are not supported");
+  if (f->feat_dim_a <= 0 || f->feat_dim_b <= 0 || (int64_t)f->feat_dim_a + f->feat_dim_b > c.feat_dim)
+    BPRX_FAIL(h, BPRX_E_INVALID, "bind_factored: need Dc, De > 0 and Dc + De <= feat_dim (%d, %d, %d)", f->feat_dim_a,
+              f->feat_dim_b, c.feat_dim);
+  if (f->embed_a <= 0 || f->embed_b <= 0 || f->embed_a > 256 || f->embed_b > 256)
+    BPRX_FAIL(h, BPRX_E_INVALID, "bind_factored: embed_a, embed_b must lie in [1, 256] (%d, %d)", f->embed_a, f->embed_b);
+  if (!(f->neg_bias_reg >= 0.f)) BPRX_FAIL(h, BPRX_E_INVALID, "bind_factored: neg_bias_reg must be >= 0");
+  if (!f->Ea || !f->Eb || !f->A || !f->Ap) BPRX_FAIL(h, BPRX_E_INVALID, "bind_factored: Ea, Eb, A, Ap are required");
+  if (c.optimizer == BPRX_OPT_ADAM_TF23 &&
+      (!f->m_Ea || !f->v_Ea || !f->m_Eb || !f->v_Eb || !f->m_A || !f->v_A || !f->m_Ap || !f->v_Ap))
+    BPRX_FAIL(h, BPRX_E_INVALID, "bind_factored: adam_tf23 needs m_/v_ slots for Ea, Eb, A, Ap");
+  if (!h->gF) {
+    const size_t n = (size_t)f->feat_dim_a * f->embed_a + (size_t)f->feat_dim_b * f->embed_b +
+                     (size_t)(f->embed_a + f->embed_b) * (c.embed_d + 1);
+    BPRX_HIP(h, hipMalloc((void **)&h->gF, n * sizeof(float)));
+  } else if (f->feat_dim_a != h->fx.feat_dim_a || f->feat_dim_b != h->fx.feat_dim_b || f->embed_a != h->fx.embed_a ||
+             f->embed_b != h->fx.embed_b) {
+    BPRX_FAIL(h, BPRX_E_INVALID, "bind_factored: the factor shapes of a handle cannot change");
+  }
+  int rc = bind_tables(h, t, true);
+  if (rc) return rc;
+  h->fx = *f;
+  h->neg_bias_reg = f->neg_bias_reg;
+  if ((rc = bprx_launch_fact_compose(h, nullptr))) return rc;
+  BPRX_HIP(h, hipStreamSynchronize(nullptr));
+  return BPRX_OK;
+}
+
+extern "C" int bprx_explain_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t n, float *out, void *stream) {
+  int rc = check_ready(h, 0);
+  if (rc) return rc;
+  if (!h->factored) BPRX_FAIL(h, BPRX_E_STATE, "explain_pairs: the handle is not bound with bprx_bind_factored");
+  if (n < 0 || n > ((int64_t)1 << 32)) BPRX_FAIL(h, BPRX_E_INVALID, "explain_pairs: n = %lld out of range", (long long)n);
+  if (n == 0) return BPRX_OK;
+  if (!user || !item || !out) BPRX_FAIL(h, BPRX_E_INVALID, "explain_pairs: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: Tu rows must be current
+  return bprx_launch_explain(h, user, item, n, out, s);
+}
+
 extern "C" int bprx_tables_dirty(bprx_handle *h, void *stream) {
   if (!h) return BPRX_E_INVALID;
   h->et_valid = h->p_valid = h->absmax_valid = false;
+  if (h->bound && h->factored) {                           // the factors were written: E_eff / Bp_eff follow them
+    const int rc = bprx_launch_fact_compose(h, (hipStream_t)stream);
+    if (rc) return rc;
+  }
   // outside values are current by definition; the bookkeeping reset is ordered on the caller's stream, behind whatever
   // wrote the tables there (a NULL stream is synchronised instead)
   return h->bound ? bprx_launch_adam_reset(h, h->adam_t, (hipStream_t)stream) : BPRX_OK;
@@ -586,6 +643,7 @@ extern "C" int bprx_step_end(bprx_handle *h, float *loss_out, void *stream) {
     BPRX_HIP(h, hipStreamWaitEvent(s, h->ev_join, 0));
     h->side_pending = false;
   }
+  if (h->factored && (rc = bprx_launch_fact_update(h, lr_t, s))) return rc;   // the factors, then E_eff / Bp_eff
   if (h->cfg.model == BPRX_MODEL_VBPR && (rc = bprx_launch_dense_update(h, lr_t, s))) return rc;
   if (loss_out && (rc = bprx_launch_loss_reduce(h, B, loss_out, s))) return rc;
   return BPRX_OK;
@@ -593,7 +651,8 @@ extern "C" int bprx_step_end(bprx_handle *h, float *loss_out, void *stream) {
 
 static int step_plain(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B, float *loss_out,
                       void *stream) {
-  h->fused_reduce = true;          // no all-reduce in between: the dense update sums the split-K slabs itself
+  h->fused_reduce = !h->factored;  // no all-reduce in between: the dense update sums the split-K slabs itself (GradFashion's
+                                   // chain rule reads the summed gradient from dEp)
   int rc = bprx_step_begin(h, user, pos, neg, B, stream);
   if (!rc) rc = bprx_step_end(h, loss_out, stream);
   h->fused_reduce = false;
@@ -609,7 +668,7 @@ extern "C" int bprx_step(bprx_handle *h, const int32_t *user, const int32_t *pos
   // default stream (cannot be captured): those take the plain path.
   const bool can_graph = (h->graph_mode == 1 || (h->graph_mode == 2 && B <= 8192)) && h->cfg.optimizer == BPRX_OPT_SGD &&
                          !h->prof && stream != nullptr && !h->side_mode && h->bound && B > 0 && B <= h->cfg.max_batch && user && pos &&
-                         neg && !h->proj_fresh && !h->pending_stage;
+                         neg && !h->proj_fresh && !h->pending_stage && !h->factored;
   if (!can_graph) return step_plain(h, user, pos, neg, B, loss_out, stream);
   hipStream_t s = (hipStream_t)stream;
   const bool same = h->graph_key.u == user && h->graph_key.i == pos && h->graph_key.j == neg && h->graph_key.loss == loss_out &&

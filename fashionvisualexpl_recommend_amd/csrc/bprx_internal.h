@@ -112,6 +112,11 @@ struct bprx_handle {
   int pending_stage;              // 1 = bprx_step_begin_sparse done (user gradients final), 2 = whole _begin done
   const int32_t *pend_u, *pend_i, *pend_j;   // the pending step's index buffers (bprx_step_begin_dense)
   float pend_lr;
+  float neg_bias_reg;             // factor of reg on the negative item's bias: 0.1 (VBPR.py:125), 1.0 for GradFashion
+  // GradFashion (bprx_bind_factored, bprx_factored.hip): E / Bp of t are E_eff / Bp_eff, composed from the factors fx
+  bool factored;
+  bprx_factored fx;
+  float *gF;                      // [Dc*ec + De*ee + (ec+ee)*(d+1)] gradient of the factors (Ea | Eb | A | Ap), one step
   // replicated-user message exchange (bprx_pack_user_msg / bprx_apply_user_msgs)
   int32_t *msg_cursor;            // [2] next free slot of the message being packed, workgroups done (both zero between calls)
   int32_t *msg_next;              // [nranks*cap] chain links of the occurrences of one user across the ranks' messages
@@ -202,3 +207,7 @@ int bprx_launch_cast_Et(bprx_handle *h, hipStream_t s);
 int bprx_launch_proj_fwd(bprx_handle *h, const int32_t *rows, int64_t nrows, const int32_t *nrows_dev, int scatter, float *Pout,
                          hipStream_t s);
 int bprx_launch_proj_bwd(bprx_handle *h, int64_t B, hipStream_t s);
+// GradFashion factors (bprx_factored.hip)
+int bprx_launch_fact_compose(bprx_handle *h, hipStream_t s);                // E_eff | Bp_eff from the factors
+int bprx_launch_fact_update(bprx_handle *h, float lr_t, hipStream_t s);     // chain rule from dEp, optimizer, loss partials
+int bprx_launch_explain(bprx_handle *h, const int32_t *u, const int32_t *i, int64_t n, float *out, hipStream_t s);

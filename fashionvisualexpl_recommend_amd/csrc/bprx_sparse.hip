@@ -27,6 +27,7 @@ struct SparseArgs {
   int32_t *errflag;
   int U, I, k, d, PS;
   float reg;
+  float nb;         // factor of reg on the negative item's bias (VBPR.py:125: 0.1f; GradFashion.py:175-176: 1)
   // exclusive-row fast path (sgd): multiplicity of every row in the batch; rows used by exactly one triplet are
   // updated in place by that triplet's group (6 row transfers per triplet, no staging, no atomics, no apply pass)
   int32_t *cntU, *cntI;
@@ -288,21 +289,21 @@ __global__ __launch_bounds__(TripletGradThreads<G>::value) void k_triplet_grad(S
   const bool exU = a.fastU && mulU == 1;
   const bool exI = a.fastI && mulI == 1, exJ = a.fastI && mulJ == 1;               // i == j gives count 2: shared
   if (lane == 0) {
-    a.lossb[b] = sp + reg * (nrm + bi * bi + bj * bj * 0.1f);          // BPRMF.py:108-112 / VBPR.py:121-126
+    a.lossb[b] = sp + reg * (nrm + bi * bi + bj * bj * a.nb);           // BPRMF.py:108-112 / VBPR.py:121-126
     if (a.use_list) {
       // shared rows were listed for the apply pass by k_row_count (the occurrence that found the count at one); exclusive
       // rows (finished by this group alone) reset their multiplicity here -- nobody else looks at it
       if (exU) a.cntU[u] = 0;
       if (exI) { a.wBi[i] = bi - lr * (g + r2 * bi); a.cntI[i] = 0; }
       else atomicAdd(a.dBi + i, g + r2 * bi);
-      if (exJ) { a.wBi[j] = bj - lr * (-g + (r2 * 0.1f) * bj); a.cntI[j] = 0; }
-      else atomicAdd(a.dBi + j, -g + (r2 * 0.1f) * bj);
+      if (exJ) { a.wBi[j] = bj - lr * (-g + (r2 * a.nb) * bj); a.cntI[j] = 0; }
+      else atomicAdd(a.dBi + j, -g + (r2 * a.nb) * bj);
     } else {
       if (!exU) a.flagU[u] = 1u;
       if (exI) a.wBi[i] = bi - lr * (g + r2 * bi);
       else { atomicAdd(a.dBi + i, g + r2 * bi); a.flagI[i] = 1u; }
-      if (exJ) a.wBi[j] = bj - lr * (-g + (r2 * 0.1f) * bj);
-      else { atomicAdd(a.dBi + j, -g + (r2 * 0.1f) * bj); a.flagI[j] = 1u; }
+      if (exJ) a.wBi[j] = bj - lr * (-g + (r2 * a.nb) * bj);
+      else { atomicAdd(a.dBi + j, -g + (r2 * a.nb) * bj); a.flagI[j] = 1u; }
     }
   }
   // ---- backward: per-occurrence gradients from the same pre-update rows (L1/L2 hits) ----
@@ -869,7 +870,7 @@ __global__ __launch_bounds__(1024) void k_dense_update(float *__restrict__ E, fl
                                                       uint16_t *__restrict__ EtF, const int32_t *__restrict__ ilist,
                                                       const int32_t *__restrict__ ilist_n, int32_t *__restrict__ ilist_n_next,
                                                       int bound, float *__restrict__ W, int32_t *__restrict__ cnt_reset,
-                                                      uint32_t *__restrict__ absmax_out) {
+                                                      uint32_t *__restrict__ absmax_out, int upd) {
   __shared__ __attribute__((aligned(16))) uint16_t tile[DU_KB][288];   // PS <= 272
   const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
   if (ilist_n_next && blockIdx.x == 0 && threadIdx.x == 0) *ilist_n_next = 0;
@@ -896,7 +897,13 @@ __global__ __launch_bounds__(1024) void k_dense_update(float *__restrict__ E, fl
     for (int q = threadIdx.x; q < DU_KB * PQ; q += (int)blockDim.x) {
       const int kr = q / PQ, n4 = (q - kr * PQ) * 4, kk = k0 + kr;
       float nvv[4] = {0.f, 0.f, 0.f, 0.f};
-      if (kk < D && n4 <= d) {
+      if (!upd && kk < D && n4 <= d) {                   // housekeeping only (GradFashion: E / Bp were composed already)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int n = n4 + c;
+          if (n <= d) nvv[c] = n < d ? E[(size_t)kk * d + n] : Bp[kk];
+        }
+      } else if (kk < D && n4 <= d) {
         const size_t e = (size_t)kk * PS + n4;
         float gs[4] = {0.f, 0.f, 0.f, 0.f};
         if (part) {                                      // fused split-K reduction (single-GPU step), fixed slab order
@@ -987,7 +994,7 @@ __global__ __launch_bounds__(1024) void k_dense_update(float *__restrict__ E, fl
   for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
   __syncthreads();
-  if (threadIdx.x == 0) {
+  if (threadIdx.x == 0 && sqpart) {
     double t = 0.0;
     for (int q = 0; q < (int)(blockDim.x >> 6); ++q) t += red[q];
     sqpart[blockIdx.x] = t;
@@ -1393,7 +1400,7 @@ __global__ __launch_bounds__(TS_T) void k_triplet_seg(SparseArgs a, SegUser su, 
   const float g = inr ? -1.0f / (1.0f + expf(diff)) : 0.f;            // -sigmoid(-diff)
   const float reg = a.reg, r2 = 2.f * reg, lr = a.lr;
   if (lane == 0 && valid) {
-    a.lossb[b] = sp + reg * (nrm + bi * bi + bj * bj * 0.1f);          // BPRMF.py:108-112 / VBPR.py:121-126
+    a.lossb[b] = sp + reg * (nrm + bi * bi + bj * bj * a.nb);           // BPRMF.py:108-112 / VBPR.py:121-126
     const int key = su.mode == 0 ? slot : u;                           // where k_item_seg finds the pre-update user row
     if ((unsigned)spI < (unsigned)a.seg_ent_cap) a.seg_ent[spI] = make_int2(key, __float_as_int(g));
     if ((unsigned)spJ < (unsigned)a.seg_ent_cap) a.seg_ent[spJ] = make_int2((int)((unsigned)key | 0x80000000u), __float_as_int(g));
@@ -1582,7 +1589,7 @@ __global__ __launch_bounds__(IS_T) void k_item_seg(SparseArgs a, float *__restri
   const float fn = (float)ns, fj = (float)nj, fi = (float)(ns - nj);
   float4 gr = make_float4(0.f, 0.f, 0.f, 0.f);
   if (hk) gr = make_float4(ag.x + r2 * fn * q.x, ag.y + r2 * fn * q.y, ag.z + r2 * fn * q.z, ag.w + r2 * fn * q.w);
-  float gb = gsum + r2 * fi * pb + (r2 * 0.1f) * fj * pb;
+  float gb = gsum + r2 * fi * pb + (r2 * a.nb) * fj * pb;
   float wl = gsum;                                                    // column d of W: the Bp column of [theta_u | 1]
   if (n > SEG_CAP) {
     // ---- hot item: this group holds one chunk.  Partial sums meet in the staging rows (dGi, dBi, fp32 W); the group that
@@ -1702,6 +1709,7 @@ SparseArgs make_args(bprx_handle *h, const float *P) {
   a.P = P; a.W = h->W; a.lossb = h->lossb; a.errflag = h->errflag;
   a.U = h->cfg.num_users; a.I = h->cfg.num_items; a.k = h->cfg.embed_k; a.d = h->cfg.embed_d; a.PS = h->PS;
   a.reg = h->cfg.reg;
+  a.nb = h->neg_bias_reg;
   a.cntU = h->cntU; a.cntI = h->cntI;
   a.wGu = h->t.Gu; a.wGi = h->t.Gi; a.wBi = h->t.Bi; a.wTu = h->t.Tu;
   a.fast = h->fast_rows;
@@ -2357,10 +2365,14 @@ int bprx_launch_dense_update(bprx_handle *h, float lr_t, hipStream_t s) {
   const int D = h->cfg.feat_dim;
   unsigned blocks = (unsigned)((D + DU_KB - 1) / DU_KB);
   if (blocks > BPRX_DENSE_BLOCKS) blocks = BPRX_DENSE_BLOCKS;
-  h->dense_blocks = (int)blocks;
+  // GradFashion: bprx_launch_fact_update has moved the factors, composed E_eff / Bp_eff and left the loss partials; this
+  // launch only does the step's housekeeping below (nothing to do: no launch)
+  const bool upd = !h->factored;
+  if (upd) h->dense_blocks = (int)blocks;
+  else if (!h->list_mode && h->cfg.feat_dtype != BPRX_F_BF16) { h->et_valid = false; h->p_valid = false; return BPRX_OK; }
   BprxProfScope ps(h, BPRX_PHASE_DENSE, s);
   // fused_reduce: the split-K slabs are summed here (bprx_step); otherwise dEp holds the (all-reduced) gradient
-  const float *part = (h->fused_reduce && h->cfg.feat_dtype != BPRX_F_FP32) ? h->part : nullptr;
+  const float *part = (upd && h->fused_reduce && h->cfg.feat_dtype != BPRX_F_FP32) ? h->part : nullptr;
   // fp8 features: the slabs hold (F*feat_scale)^T W; an all-reduced dEp was already rescaled by k_reduce_parts
   const float gscale = (part && h->cfg.feat_dtype == BPRX_F_FP8) ? 1.0f / h->cfg.feat_scale : 1.0f;
   // bf16 features: this kernel writes the next step's [E|Bp]^T images (fp8 images need the global max first: k_cast_Et8)
@@ -2374,12 +2386,12 @@ int bprx_launch_dense_update(bprx_handle *h, float lr_t, hipStream_t s) {
   hipLaunchKernelGGL(k_dense_update, dim3(blocks), dim3((unsigned)threads), 0, s, h->t.E, h->t.Bp, h->t.m_E, h->t.v_E, h->t.m_Bp,
                      h->t.v_Bp, h->dEp, part, h->SK_step, D, h->cfg.embed_d, h->PS,
                      h->cfg.optimizer == BPRX_OPT_ADAM_TF23 ? 1 : 0, lr_t, h->cfg.reg, h->cfg.beta1, h->cfg.beta2,
-                     h->cfg.epsilon, h->loss_acc, gscale, images ? (uint16_t *)h->Et : (uint16_t *)nullptr, (uint16_t *)h->EtF,
+                     h->cfg.epsilon, upd ? h->loss_acc : (double *)nullptr, gscale, images ? (uint16_t *)h->Et : (uint16_t *)nullptr, (uint16_t *)h->EtF,
                      lm ? (const int32_t *)h->ilist : (const int32_t *)nullptr, (const int32_t *)h->list_cur,
                      lm ? h->ilist_n + (h->list_slot ^ 1) : (int32_t *)nullptr, (int)bound, h->W,
                      (lm && h->list_reset_cnt) ? h->cntI : (int32_t *)nullptr,
                      // fp8: the slot the next k_cast_Et8 reads (cleared by the last one)
-                     h->cfg.feat_dtype == BPRX_F_FP8 ? (uint32_t *)h->qs + 2 + h->qs_slot : (uint32_t *)nullptr);
+                     h->cfg.feat_dtype == BPRX_F_FP8 ? (uint32_t *)h->qs + 2 + h->qs_slot : (uint32_t *)nullptr, upd ? 1 : 0);
   BPRX_LAUNCH_CHECK(h, "k_dense_update");
   h->absmax_valid = h->cfg.feat_dtype == BPRX_F_FP8;
   if (lm) { h->list_slot ^= 1; h->list_mode = 0; }      // the step's list is consumed

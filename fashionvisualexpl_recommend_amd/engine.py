@@ -11,6 +11,7 @@ import torch
 from . import _ffi
 
 PARAM_NAMES = ("Gu", "Gi", "Bi", "Tu", "E", "Bp")
+FACTORED_PARAM_NAMES = ("Gu", "Gi", "Bi", "Tu", "Ec", "Ee", "E", "Bp")     # GradFashion.py:182-186 (bind_factored)
 
 
 def _ptr(t):
@@ -125,13 +126,57 @@ class Engine:
         self.t = t
         return self
 
+    def bind_factored(self, Gu, Gi, Bi, Tu, F, Ec, Ee, E, Bp, feat_dim_a, feat_dim_b, neg_bias_reg=1.0, slots=None):
+        """GradFashion (bprx_bind_factored): the handle trains the factor tables Ec [Dc,ec], Ee [De,ee], E [ec+ee,d],
+        Bp [ec+ee] (GradFashion.py:59-81); F = [Fc | Fe | zero padding] is [I, feat_dim].  The handle's own E / Bp are the
+        EFFECTIVE projection E_eff [D,d] / Bp_eff [D], library-written buffers kept here as t['E_eff'] / t['Bp_eff'].
+        fp32 or bf16 features.  Adam slots (m_ / v_ for Gu, Gi, Bi, Tu, Ec, Ee, E, Bp) are zeros unless given."""
+        if self.model != "vbpr":
+            raise ValueError("bind_factored needs an Engine(model='vbpr', ...)")
+        def prep(x, shape, dtype=torch.float32):
+            return torch.as_tensor(x).to(device=self.device, dtype=dtype).reshape(shape).contiguous()
+        Ec, Ee = torch.as_tensor(Ec), torch.as_tensor(Ee)
+        ea, eb = int(Ec.shape[1]), int(Ee.shape[1])
+        t = {"Gu": prep(Gu, (self.U, self.k)), "Gi": prep(Gi, (self.I, self.k)), "Bi": prep(Bi, (self.I,)),
+             "Tu": prep(Tu, (self.U, self.d)),
+             "F": prep(F, (self.I, self.D), torch.bfloat16 if self.feat_dtype == "bf16" else torch.float32),
+             "Ec": prep(Ec, (feat_dim_a, ea)), "Ee": prep(Ee, (feat_dim_b, eb)),
+             "E": prep(E, (ea + eb, self.d)), "Bp": prep(Bp, (ea + eb,)),
+             "E_eff": torch.zeros((self.D, self.d), dtype=torch.float32, device=self.device),
+             "Bp_eff": torch.zeros(self.D, dtype=torch.float32, device=self.device)}
+        if self.optimizer == "adam_tf23":
+            for n in FACTORED_PARAM_NAMES:
+                for s_ in ("m_", "v_"):
+                    given = None if slots is None else slots.get(s_ + n)
+                    t[s_ + n] = torch.zeros_like(t[n]) if given is None else prep(given, tuple(t[n].shape))
+        tb = _ffi.Tables()
+        for n in _ffi.TABLE_FIELDS:
+            v = {"E": t["E_eff"], "Bp": t["Bp_eff"]}.get(n) if n in ("E", "Bp", "m_E", "v_E", "m_Bp", "v_Bp") else t.get(n)
+            setattr(tb, n, None if v is None else v.data_ptr())
+        fx = _ffi.Factored(int(feat_dim_a), int(feat_dim_b), ea, eb, float(neg_bias_reg))
+        for n, name in zip(_ffi.FACTORED_FIELDS, ("Ec", "Ee", "E", "Bp", "m_Ec", "v_Ec", "m_Ee", "v_Ee", "m_E", "v_E", "m_Bp", "v_Bp")):
+            setattr(fx, n, None if t.get(name) is None else t[name].data_ptr())
+        torch.cuda.current_stream(self.device).synchronize()
+        _ffi.check(self.h, self.lib.bprx_bind_factored(self.h, C.byref(tb), C.byref(fx)))
+        self.factored = True
+        self.t = t
+        return self
+
+    def explain_pairs(self, user, item):
+        """GradFashion.predict_ui_grads for every pair (bprx_explain_pairs): fp32 device tensor [n, 2] = (colour, edges)."""
+        u, i = as_index(user, self.device), as_index(item, self.device)
+        out = torch.empty((u.numel(), 2), dtype=torch.float32, device=self.device)
+        _ffi.check(self.h, self.lib.bprx_explain_pairs(self.h, _ptr(u), _ptr(i), u.numel(), _ptr(out), _stream()))
+        return out
+
     def tables_dirty(self):
         """Call after writing any bound table from outside the library (bprx_tables_dirty): the handle reuses images
         derived from E/Bp (their bf16/fp8 copy, the item projections) until a step changes them."""
         _ffi.check(self.h, self.lib.bprx_tables_dirty(self.h, _stream()))
 
     def params(self):
-        return {n: self.t[n] for n in PARAM_NAMES if self.t.get(n) is not None}
+        names = FACTORED_PARAM_NAMES if getattr(self, "factored", False) else PARAM_NAMES
+        return {n: self.t[n] for n in names if self.t.get(n) is not None}
 
     def set_hyper(self, lr, reg):
         _ffi.check(self.h, self.lib.bprx_set_hyper(self.h, lr, reg))

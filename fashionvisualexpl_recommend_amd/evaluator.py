@@ -209,3 +209,23 @@ class Evaluator:
                     top_k_score = row[top_k_id]
                     for i, value in enumerate(top_k_id):
                         out.write(str(u) + '\t' + str(value) + '\t' + str(top_k_score[i]) + '\n')
+
+    def store_recommendation_grads(self, path=""):
+        """Evaluator.py:261-275 (GradFashion): for every user the items training_list[u] + validation_list[u] + test_list[u],
+        in that order, one row 'u\\ti\\tcolour\\tedges' each (get_explanations.py:19-21 reads USER_ID, ITEM_ID, COLOR, EDGES).
+        The attributions come from the device, one bprx_explain_pairs call per block of users."""
+        lists = (self.data.training_list, self.data.validation_list, self.data.test_list)
+        U = self.data.num_users
+        with open(path, 'w') as out:
+            for u0 in range(0, U, self.user_block):
+                u1 = min(U, u0 + self.user_block)
+                users, items = [], []
+                for u in range(u0, u1):
+                    pos_items_u = [i for l in lists for i in (l[u] if u < len(l) else [])]
+                    users += [u] * len(pos_items_u)
+                    items += pos_items_u
+                if not items:
+                    continue
+                g = self.model.engine.explain_pairs(users, items).cpu().numpy()
+                for r, (u, i) in enumerate(zip(users, items)):
+                    out.write(str(u) + '\t' + str(i) + '\t' + str(g[r, 0]) + '\t' + str(g[r, 1]) + '\n')

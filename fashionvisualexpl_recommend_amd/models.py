@@ -199,7 +199,7 @@ class BPRMF(RecommenderModel):
                 loss = 0
                 steps = 0
         print('Training end...')
-        self.evaluator.store_recommendation(path=os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
+        self._store_recs(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
         with open(os.path.join(rdir, f'results-metrics-{self.directory_parameters}') + '.pkl', 'wb') as f:
             pickle.dump(results, f)                                             # utils/write.py:14-22
         print("Store Best Model at Epoch {0}".format(best_epoch))
@@ -208,14 +208,17 @@ class BPRMF(RecommenderModel):
         if best_state is not None:
             torch.save(best_state, os.path.join(wdir, f'best-weights-{best_epoch}-{self.directory_parameters}.pt'))
             self.load_state_dict(best_state)
-        self.evaluator.store_recommendation(
-            path=os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
+        self._store_recs(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
         self.load_state_dict(last_state)
         print('End Store Best Model!')
         print('Best Values for Each Metric:\nHR\tPrec\tRec\tAUC\tnDCG\n{}\t{}\t{}\t{}\t{}\n'.format(
             max_metrics['hr'], max_metrics['p'], max_metrics['r'], max_metrics['auc'], max_metrics['ndcg']))
         self.results = results
         return results
+
+    def _store_recs(self, path):
+        """What train() leaves at the recs-* / best-recs-* paths: the top-K lists (BPRMF.py:167-187)."""
+        self.evaluator.store_recommendation(path=path)
 
 
 def _table_property(name):
@@ -272,3 +275,121 @@ class VBPR(BPRMF):
         return xui, self.Gu[u], self.Gi[i], self.F[i], self.Tu[u], self.Bi[i]
 
     __call__ = call
+
+
+class GradFashion(VBPR):
+    """GradFashion.py:23-320: VBPR whose projection is factored through a colour and an edge embedding,
+        vf_i = [Fc_i Ec | Fe_i Ee],   x_ui = Bi_i + Gu_u.Gi_i + Tu_u.(vf_i E) + vf_i.Bp,
+    trained on the VBPR hot path with the effective projection E_eff = [Ec E[:ec] ; Ee E[ec:]] (include/bprx.h,
+    bprx_bind_factored).  Same surface as the reference: color_weights {'Fc','Ec'}, edges_weights {'Fe','Ee'},
+    visual_profile {'Bp','E','Tu'}, embed_color, embed_edges, call, predict_all, train_step, predict_ui_grads,
+    get_grads_user, train.  F = [Fc | Fe] is padded with zero columns to the kernels' width granularity (16 fp32, 128 bf16).
+    `features`: optional (Fc, Fe) arrays used instead of the two .npy files (normalised here like the files)."""
+    model_kind = "grad_fashion"
+    GRANULE = {"fp32": 16, "bf16": 128}
+
+    def __init__(self, data, params, init=None, features=None):
+        self.embed_color = params.embed_color                                   # GradFashion.py:28-29
+        self.embed_edges = params.embed_edges
+        super().__init__(data, params, init, features)
+        self.directory_parameters = f'batch_{params.batch_size}-D_{params.embed_d}-K_{params.embed_k}' \
+                                    f'-lr_{params.lr}-reg_{params.reg}'      # GradFashion.py:48-52
+
+    # ---- visual_loader_mixin.py:51-54, 60-69: np.load, each table divided by its OWN global max-abs -------------------
+    def process_edge_visual_features(self):
+        f = self._features[1] if self._features is not None else np.load(configs.edge_features_path(
+            self.params.dataset, getattr(self.params, "cnn_model", "vgg19"), getattr(self.params, "output_layer", "fc2")))
+        f = np.asarray(f)
+        self.edge_features = f / np.max(np.abs(f))
+        self.dim_edge_features = self.edge_features.shape[1]
+
+    def process_color_visual_features(self):
+        f = self._features[0] if self._features is not None else np.load(configs.hist_color_features_path(self.params.dataset))
+        f = np.asarray(f)
+        self.color_features = f / np.max(np.abs(f))
+        self.dim_color_features = self.color_features.shape[1]
+
+    def padded_features(self):
+        """[I, D] float32: [Fc | Fe | zeros], D = Dc + De rounded up to the feature dtype's granule."""
+        Dc, De = self.dim_color_features, self.dim_edge_features
+        g = self.GRANULE[getattr(self.params, "dtype", "fp32")]
+        D = -(-(Dc + De) // g) * g
+        F = np.zeros((self.num_items, D), np.float32)
+        F[:, :Dc] = self.color_features
+        F[:, Dc:Dc + De] = self.edge_features
+        return F
+
+    def _init_tables(self, init):
+        t, rs = BPRMF._init_tables(self, init)                                  # Bi, Gu, Gi (BPRMF.py:48-50)
+        dtype = getattr(self.params, "dtype", "fp32")
+        if dtype not in self.GRANULE:
+            raise ValueError("GradFashion runs with --dtype fp32 or bf16 (got %s)" % dtype)
+        self.process_edge_visual_features()                                     # GradFashion.py:33-34
+        self.process_color_visual_features()
+        e, d = self.embed_color + self.embed_edges, self.embed_d
+        v = {"Bp": glorot_uniform(rs, e, 1).reshape(-1),                        # create_visual_profile, GradFashion.py:73-81
+             "E": glorot_uniform(rs, e, d),
+             "Tu": glorot_uniform(rs, self.num_users, d)}
+        v["Ec"] = glorot_uniform(rs, self.dim_color_features, self.embed_color)  # create_color_features, :59-65
+        v["Ee"] = glorot_uniform(rs, self.dim_edge_features, self.embed_edges)   # create_edges_features, :67-71
+        v["F"] = self.padded_features()
+        self.dim_cnn_features = v["F"].shape[1]
+        v.update({k: val for k, val in init.items() if k in v})
+        t.update(v)
+        return t, rs
+
+    def _build(self, init):
+        t, _ = self._init_tables(init)
+        self.engine = Engine(optimizer=self.optimizer_name, lr=self.learning_rate, reg=self.reg,
+                             max_batch=max(self.batch_size, 4096), adam_form=self._adam_form(), **self._engine_kwargs())
+        self.engine.bind_factored(t["Gu"], t["Gi"], t["Bi"], t["Tu"], t["F"], t["Ec"], t["Ee"], t["E"], t["Bp"],
+                                  self.dim_color_features, self.dim_edge_features, neg_bias_reg=1.0)
+
+    # ---- the reference's attribute surface ---------------------------------------------------------------------------
+    @property
+    def color_weights(self):
+        return {"Fc": self.F[:, :self.dim_color_features], "Ec": self.engine.t["Ec"]}
+
+    @property
+    def edges_weights(self):
+        Dc = self.dim_color_features
+        return {"Fe": self.F[:, Dc:Dc + self.dim_edge_features], "Ee": self.engine.t["Ee"]}
+
+    @property
+    def visual_profile(self):
+        t = self.engine.t
+        return {"Bp": t["Bp"][:, None], "E": t["E"], "Tu": t["Tu"]}
+
+    # ---- GradFashion.py:83-131 ---------------------------------------------------------------------------------------
+    def call(self, inputs, training=True, mask=None):
+        """xui from the engine (bprx_score_pairs); the other outputs are the reference's gathered rows (theta_i = F_i E_eff:
+        the projected rows, recomputed here for inspection only -- the training step never calls this)."""
+        user, item = inputs
+        u, i = as_index(user, self.engine.device).long(), as_index(item, self.engine.device).long()
+        xui = self.engine.score_pairs(u, i)
+        t = self.engine.t
+        Dc, De = self.dim_color_features, self.dim_edge_features
+        Fi = t["F"][i].float()
+        theta_i = Fi @ t["E_eff"]
+        return xui, t["Gu"][u], t["Gi"][i], Fi[:, :Dc], Fi[:, Dc:Dc + De], t["Tu"][u], theta_i, t["Bi"][i]
+
+    __call__ = call
+
+    # ---- GradFashion.py:269-303 ----------------------------------------------------------------------------------------
+    def predict_ui_grads(self, inputs):
+        """Gradient x input of x_ui with respect to Fc_i and Fe_i, summed per table: np.float32 [1, 2] (colour, edges)."""
+        u, i = inputs
+        return self.engine.explain_pairs([int(u)], [int(i)]).cpu().numpy()
+
+    def get_grads_user(self, u, top_k_items):
+        """[len(items), 2] for the user's items: one device call for the whole list (the reference maps predict_ui_grads over
+        a thread pool, one tape per pair)."""
+        items = list(top_k_items)
+        if not items:
+            return np.zeros((0, 2), np.float32)
+        return self.engine.explain_pairs([int(u)] * len(items), items).cpu().numpy()
+
+    def _store_recs(self, path):
+        """GradFashion.py:236-240, 252-258: the reference writes the top-K list to the recs path and then OVERWRITES the same
+        path with the explanation rows (get_explanations.py:19-21 reads them from there); only the final content is written."""
+        self.evaluator.store_recommendation_grads(path=path)

@@ -78,3 +78,13 @@ def make_interactions_clustered(num_users, num_items, per_user=22, clusters=20, 
         val.append([chosen[per_user - 2]])
         test.append([chosen[per_user - 1]])
     return train, val, test
+
+
+def write_grad_fashion_features(root, name, color, edges, cnn_model="vgg19", output_layer="fc2"):
+    """GradFashion's two feature files (visual_loader_mixin.py:51-54, 60-69): the colour histograms
+    original/features/histograms.npy [I, Dc] and the edge features original/edge_features_{model}_{layer}.npy [I, De]."""
+    d = os.path.join(root, name, "original")
+    os.makedirs(os.path.join(d, "features"), exist_ok=True)
+    np.save(os.path.join(d, "features", "histograms.npy"), np.asarray(color))
+    np.save(os.path.join(d, "edge_features_{0}_{1}.npy".format(cnn_model, output_layer)), np.asarray(edges))
+    return d

@@ -1,6 +1,8 @@
-"""CLI mirror of the reference's src/train_rec.py:17-93 for the two in-scope models.
+"""CLI mirror of the reference's src/train_rec.py:17-93 for the in-scope models (BPRMF, VBPR, GradFashion).
 
-Same flag names and defaults for every flag BPRMF/VBPR consume; new flags: --optimizer, --dtype, --init_seed.
+Same flag names and defaults for every flag BPRMF/VBPR consume; new flags: --optimizer, --dtype, --init_seed, and GradFashion's
+--embed_color / --embed_edges, which the reference reads (GradFashion.py:28-29) but never defines: they default to 20, the
+--embed_d default.
 Run as `python -m fashionvisualexpl_recommend_amd.train_rec --rec bprmf --dataset <name> ...`.
 """
 import argparse
@@ -17,7 +19,7 @@ def parse_args(argv=None):
                                                             'no counterpart: this engine is GPU-only)')
     parser.add_argument('--best_metric', type=str, default='ndcg')
     parser.add_argument('--dataset', nargs='?', default='amazon_baby', help='dataset name')
-    parser.add_argument('--rec', nargs='?', default="vbpr", help="bprmf | vbpr")
+    parser.add_argument('--rec', nargs='?', default="vbpr", help="bprmf | vbpr | grad_fashion")
     parser.add_argument('--batch_size', type=int, default=256, help='batch_size')
     parser.add_argument('--top_k', type=int, default=20, help='top-k of recommendation.')
     parser.add_argument('--epochs', type=int, default=200, help='Number of epochs.')
@@ -32,6 +34,9 @@ def parse_args(argv=None):
     parser.add_argument('--embed_k', type=int, default=128, help='Embedding size.')
     parser.add_argument('--embed_d', type=int, default=20, help='size of low dimensionality for visual features')
     parser.add_argument('--reg', type=float, default=0, help='regularization')
+    # read by GradFashion.py:28-29, defined nowhere in the reference: the --embed_d default
+    parser.add_argument('--embed_color', type=int, default=20, help='grad_fashion: size of the colour embedding (Ec columns)')
+    parser.add_argument('--embed_edges', type=int, default=20, help='grad_fashion: size of the edge embedding (Ee columns)')
     # not in the reference
     parser.add_argument('--optimizer', default='adam_tf23', choices=['adam_tf23', 'sgd'])
     parser.add_argument('--dtype', default='fp32', choices=['fp32', 'bf16', 'fp8'],
@@ -54,10 +59,12 @@ def parse_args(argv=None):
 
 def train(argv=None):
     args = parse_args(argv)
+    if args.rec == 'grad_fashion' and int(args.world_size) > 1:
+        raise NotImplementedError('--rec grad_fashion runs on one GPU (no multi-GPU form): use --world_size 1')
     configs.set_roots(args.data_root, args.results_root)
     import torch
     from .dataset import DataLoader
-    from .models import BPRMF, VBPR
+    from .models import BPRMF, VBPR, GradFashion
     os.makedirs(os.path.join(configs.results_dir(), args.dataset, args.rec), exist_ok=True)     # train_rec.py:52-55
     os.makedirs(os.path.join(configs.weight_dir(), args.dataset, args.rec), exist_ok=True)
     world = int(args.world_size)
@@ -93,6 +100,8 @@ def train(argv=None):
             model = BPRMF(data, args)
         elif args.rec == 'vbpr':
             model = VBPR(data, args)
+        elif args.rec == 'grad_fashion':
+            model = GradFashion(data, args)
         else:
             raise NotImplementedError('Not implemented or unknown Recommender Model.')        # train_rec.py:86
         out.append(model.train())

@@ -137,6 +137,35 @@ BPRX_API int64_t bprx_get_adam_step(const bprx_handle *h);
    bprx_create from the table sizes and max_batch (BPRX_ADAM_LAZY=0 / 1 forces it); the arithmetic is the same. */
 BPRX_API int bprx_adam_is_lazy(const bprx_handle *h);
 
+/* ---- GradFashion (GradFashion.py:57-193) on a VBPR handle ----------------------------------------------------------
+   The reference's score is linear in its factored projection:
+       vf_i = [Fc_i Ec | Fe_i Ee]            x_ui = Bi_i + Gu_u.Gi_i + Tu_u.(vf_i E) + vf_i.Bp       (GradFashion.py:98-131)
+   i.e. VBPR with F = [Fc | Fe | zero padding] and the EFFECTIVE projection
+       E_eff  = [Ec E[:ec] ; Ee E[ec:] ; 0]  [D, d]        Bp_eff = [Ec Bp[:ec] ; Ee Bp[ec:] ; 0]  [D].
+   bprx_bind_factored binds a VBPR handle (fp32 or bf16 features; fp8 is rejected with BPRX_E_INVALID) whose t->E / t->Bp are
+   caller-owned buffers of E_eff / Bp_eff that the LIBRARY writes (composed at bind, after every step and by bprx_tables_dirty);
+   t->m_E / v_E / m_Bp / v_Bp are unused.  The trainable dense tables are the four factors below; each step takes the chain rule
+   of the VBPR dense gradient G = dL/d[E_eff|Bp_eff] into them:
+       dEc = G_c [E|Bp][:ec]^T + 2 reg Ec       d[E|Bp][:ec] = Ec^T G_c + 2 reg [E|Bp][:ec]     (edges likewise, rows Dc..Dc+De)
+   with sgd or TF-2.3's dense ApplyAdam form (GradFashion.py:182-190), and the loss gains reg*(|Ec|^2+|Ee|^2+|E|^2+|Bp|^2)
+   (GradFashion.py:177-180).  The negative item's bias is regularised with factor neg_bias_reg (1.0 in GradFashion.py:175-176;
+   VBPR.py:125 / BPRMF have 0.1, the default of every handle).  Everything else (bprx_step, _begin / _end, score_pairs,
+   score_block, eval_*, topk, sync_adam) works unchanged; the caller's F must stay valid while bprx_explain_pairs is used
+   (it reads the caller's F).  Multi-GPU (exported gradients) and hipGraph capture are not supported: graphs fall back to
+   plain launches. */
+typedef struct {
+  int32_t feat_dim_a, feat_dim_b;   /* Dc, De: F = [Fc | Fe | zero padding] (visual_loader_mixin.py:51-54, 60-69); Dc + De <= feat_dim */
+  int32_t embed_a, embed_b;         /* --embed_color, --embed_edges (GradFashion.py:28-29); 1..256 each */
+  float neg_bias_reg;               /* 1.0 for GradFashion (GradFashion.py:175-176) */
+  float *Ea, *Eb, *A, *Ap;          /* Ec [Dc,ec], Ee [De,ee], E [ec+ee,d], Bp [ec+ee] (GradFashion.py:59-81) */
+  float *m_Ea, *v_Ea, *m_Eb, *v_Eb, *m_A, *v_A, *m_Ap, *v_Ap;   /* adam_tf23 slots (NULL with sgd) */
+} bprx_factored;
+BPRX_API int bprx_bind_factored(bprx_handle *h, const bprx_tables *t, const bprx_factored *f);
+/* GradFashion.predict_ui_grads (GradFashion.py:269-292): gradient x input of x_ui with respect to Fc_i and Fe_i, summed --
+   exact for the linear score:  out[p] = { (Fc_i Ec).(E[:ec] Tu_u + Bp[:ec]),  (Fe_i Ee).(E[ec:] Tu_u + Bp[ec:]) }, fp32 [n,2].
+   user / item: device int32 [n]; any n >= 0 (not bounded by max_batch). */
+BPRX_API int bprx_explain_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t n, float *out, void *stream);
+
 /* Model.call((user,item)) -> xui        BPRMF.py:55-76 / VBPR.py:59-86.   x: fp32 [B] */
 BPRX_API int bprx_score_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t B, float *x, void *stream);
 
