@@ -45,6 +45,18 @@ class Factored(C.Structure):
                 ("neg_bias_reg", C.c_float)] + [(n, C.c_void_p) for n in FACTORED_FIELDS]
 
 
+ACF_WEIGHTS = ["component.W_0_u", "component.W_0_i", "component.b_0", "component.W_1", "component.b_1",
+               "item.W_0_u", "item.W_0_iv", "item.W_0_ip", "item.W_0_ix", "item.b_0", "item.W_1", "item.b_1"]    # the order of bprx_acf.w (include/bprx.h, BPRX_ACF_*)
+
+
+class Acf(C.Structure):
+    """bprx_acf: ACF's feature maps, histories, Pi and attention tensors (include/bprx.h)."""
+    _fields_ = [("feat_m", C.c_int32), ("feat_c", C.c_int32), ("width_c", C.c_int32), ("width_i", C.c_int32),
+                ("feat_dtype", C.c_int32), ("F", C.c_void_p), ("train_ptr", C.c_void_p), ("train_items", C.c_void_p),
+                ("eval_ptr", C.c_void_p), ("eval_items", C.c_void_p), ("Pi", C.c_void_p), ("m_Pi", C.c_void_p),
+                ("v_Pi", C.c_void_p), ("w", C.c_void_p * 12), ("m_w", C.c_void_p * 12), ("v_w", C.c_void_p * 12)]
+
+
 TABLE_FIELDS = ["Gu", "Gi", "Bi", "Tu", "F", "E", "Bp", "m_Gu", "v_Gu", "m_Gi", "v_Gi", "m_Bi", "v_Bi",
                 "m_Tu", "v_Tu", "m_E", "v_E", "m_Bp", "v_Bp"]
 
@@ -78,6 +90,8 @@ def lib():
         "bprx_bind_tables": (C.c_int, [vp, C.POINTER(Tables)]),
         "bprx_bind_factored": (C.c_int, [vp, C.POINTER(Tables), C.POINTER(Factored)]),
         "bprx_explain_pairs": (C.c_int, [vp, vp, vp, i64, vp, vp]),
+        "bprx_bind_acf": (C.c_int, [vp, C.POINTER(Tables), C.POINTER(Acf)]),
+        "bprx_acf_profiles": (C.c_int, [vp, vp, i64, vp, vp, vp, vp]),
         "bprx_set_hyper": (C.c_int, [vp, f32, f32]),
         "bprx_tables_dirty": (C.c_int, [vp, vp]),
         "bprx_set_adam_step": (C.c_int, [vp, i64, vp]),
@@ -144,7 +158,7 @@ def lib():
     return L
 
 
-EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error", "bprx_bind_tables", "bprx_bind_factored", "bprx_explain_pairs", "bprx_set_hyper", "bprx_tables_dirty",
+EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error", "bprx_bind_tables", "bprx_bind_factored", "bprx_explain_pairs", "bprx_bind_acf", "bprx_acf_profiles", "bprx_set_hyper", "bprx_tables_dirty",
            "bprx_set_adam_step", "bprx_get_adam_step", "bprx_adam_is_lazy", "bprx_sync_adam", "bprx_score_pairs", "bprx_step", "bprx_step_begin",
            "bprx_step_begin_sparse", "bprx_step_begin_dense", "bprx_sum_dense_parts",
            "bprx_dense_grad", "bprx_step_end", "bprx_step_project", "bprx_user_grad", "bprx_clear_user_grad", "bprx_item_grad", "bprx_clear_item_grad",

@@ -1,5 +1,5 @@
 """On-disk contract of the hot path: the path templates of the reference's
-src/config/configs.py:2-33 (only the entries BPRMF, VBPR and GradFashion consume).
+src/config/configs.py:2-33 (only the entries BPRMF, VBPR, GradFashion and ACF consume).
 
 The reference's templates are cwd-relative ('../data/{0}/', so its scripts must run
 from src/).  The same relative defaults are kept; `set_roots()` lets a caller point
@@ -41,6 +41,10 @@ def dataset_info(dataset):                   # configs.py:14
 
 def cnn_features_path(dataset, cnn_model, output_layer):   # configs.py:12,17
     return data_path(dataset) + "original/" + "cnn_features_{0}_{1}.npy".format(cnn_model, output_layer)
+
+
+def cnn_features_path_split(dataset, cnn_model, output_layer):   # configs.py:18 (ACF: one {item}.npy per item)
+    return data_path(dataset) + "original/" + "features/" + "cnn_{0}_{1}/".format(cnn_model, output_layer)
 
 
 def edge_features_path(dataset, cnn_model, output_layer):  # configs.py:20 (GradFashion's edge features)

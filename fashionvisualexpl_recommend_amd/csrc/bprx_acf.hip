@@ -1,0 +1,837 @@
+// bprx_acf.hip -- ACF (ACF.py:20-270) on a BPRMF handle: bprx_bind_acf, bprx_acf_profiles, and what bprx_step /
+// bprx_score_pairs / bprx_score_block do on an ACF handle (include/bprx.h).
+//
+// Per call that needs user profiles g'_u:
+//   k_acf_wcat      [Wci | Wix | 0] as the projection operand (fp32 [Cp][NP]; bf16 features: hi + lo bf16 halves, transposed)
+//   k_acf_mark      the distinct items of the users' histories -> ilist (marks in imark, cleared by k_acf_unmark)
+//   k_acf_proj_*    Z_l = f_l [Wci | Wix]  [M, NP] per listed item: one MFMA GEMM over the rows (l, m), f32 32x32x2 for fp32
+//                   features, bf16 32x32x16 for bf16 features (W split into two bf16 halves: the features are the only operand
+//                   rounded)
+//   k_acf_itemvec   GP_l = Wiv^T Gi_l + Wip^T Pi_l per listed item
+//   k_acf_user      one workgroup per distinct user: component softmax over m for each history item, item-level softmax over
+//                   the history as an online (running max) softmax per wave, merged across the waves; g'_u = g_u + sum alpha Pi
+// A step then adds:
+//   k_acf_triplet   scores with g', loss terms, the detached gradients of Gi / Gu / Pi into the staging tables
+//   k_acf_dense     the twelve attention tensors (g = 2 reg w: sgd or the dense ApplyAdam rule) and the loss (one workgroup, fixed
+//                   summation order)
+//   k_acf_apply_sgd / k_acf_sweep   sgd on the touched rows / adam_tf23's sparse rule over the whole tables (adam_elem)
+//   k_acf_finish    clears the user slots and the sgd claim marks
+#include <climits>
+
+#include "bprx_internal.h"
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+#define ACF_MAX_M 2048
+#define ACF_MAX_NP 256
+#define ACF_MAX_K 512
+
+struct AcfState {
+  bprx_acf a;
+  int M, C, hc, ha, NP, k, fdt, Cp;   // NP = 32*ceil((h+a)/32); Cp = C rounded up to the K chunk (32)
+  int64_t nw[BPRX_ACF_NW];
+  float *Z;                           // [I][M][NP]  f_l [Wci | Wix | 0]
+  float *GP;                          // [I][a]      Wiv^T Gi_l + Wip^T Pi_l
+  float *Wc;                          // [Cp][NP]    fp32 projection operand
+  uint16_t *Wh, *Wl;                  // [NP][Cp]    bf16 hi / lo halves of the same, transposed (bf16 features)
+  float *gp;                          // [max_batch][k] g' of the batch positions (step: the user's first position)
+  float *Gup;                         // [U][k]      g' with the evaluation histories (bprx_score_block)
+  float *dPi;                         // [I][k]      staging gradient of Pi, all-zero between steps
+  int32_t *uslot;                     // [U]         first batch position of the user in the step; INT_MAX between steps
+  int32_t *imark;                     // [I]         item listed in this call; 0 between calls
+  int32_t *ilist, *nlist;             // [I], [1]
+  bool eval_valid;                    // Gup matches the bound tables
+};
+
+__device__ __forceinline__ int acf_clamp(int v, int n, int32_t *errflag, int code) {
+  if ((unsigned)v >= (unsigned)n) {
+    *errflag = code;
+    return v < 0 ? 0 : n - 1;
+  }
+  return v;
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// LDS written by some lanes of a wave and read by others of the same wave
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ uint16_t bf16_rne(float x) {
+  const uint32_t b = __float_as_uint(x);
+  return (uint16_t)((b + 0x7fffu + ((b >> 16) & 1u)) >> 16);
+}
+
+// ---- projection operand --------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_acf_wcat(const float *__restrict__ Wci, const float *__restrict__ Wix, int C, int Cp,
+                                                  int hc, int ha, int NP, float *__restrict__ Wc, uint16_t *__restrict__ Wh,
+                                                  uint16_t *__restrict__ Wl) {
+  const int64_t n = (int64_t)Cp * NP;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(e / NP), j = (int)(e % NP);
+    float v = 0.f;
+    if (c < C) v = j < hc ? Wci[(int64_t)c * hc + j] : (j < hc + ha ? Wix[(int64_t)c * ha + (j - hc)] : 0.f);
+    if (Wc) Wc[e] = v;
+    if (Wh) {
+      const uint16_t hi = bf16_rne(v);
+      const float rest = v - __uint_as_float((uint32_t)hi << 16);
+      Wh[(int64_t)j * Cp + c] = hi;
+      Wl[(int64_t)j * Cp + c] = bf16_rne(rest);
+    }
+  }
+}
+
+// ---- distinct items of the users' histories ------------------------------------------------------------------------
+// one wave per position b; users == nullptr: position b is user b; uslot: only the user's first position lists its history
+__global__ __launch_bounds__(256) void k_acf_mark(const int32_t *__restrict__ users, int64_t n, const int32_t *__restrict__ uslot,
+                                                  const int64_t *__restrict__ ptr, const int32_t *__restrict__ items, int U, int I,
+                                                  int32_t *__restrict__ imark, int32_t *__restrict__ ilist, int32_t *__restrict__ nlist,
+                                                  int32_t *errflag) {
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (b >= n) return;
+  const int u = users ? acf_clamp(users[b], U, errflag, 1) : (int)b;
+  if (uslot && uslot[u] != (int32_t)b) return;
+  const int64_t beg = ptr[u], end = ptr[u + 1];
+  for (int64_t p = beg + lane; p < end; p += 64) {
+    const int l = acf_clamp(items[p], I, errflag, 5);
+    if (atomicExch(imark + l, 1) == 0) ilist[atomicAdd(nlist, 1)] = l;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_acf_unmark(const int32_t *__restrict__ ilist, const int32_t *__restrict__ nlist,
+                                                    int32_t *__restrict__ imark) {
+  const int n = *nlist;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) imark[ilist[e]] = 0;
+}
+
+// ---- Z = f_l [Wci | Wix]: MFMA GEMM over the rows (l, m) of the listed items ----------------------------------------------
+// A workgroup computes 64 rows x NP columns; wave w takes row tile w & 1 and the column tiles ct == w >> 1 (mod 2).  K runs in
+// chunks of 32 staged in LDS.  Row r of the GEMM is component r % M of item list[r / M] (all items when list == nullptr).
+__device__ __forceinline__ void acf_store_tile(float *__restrict__ Z, const f32x16 &acc, const int32_t *list, int64_t r0, int64_t nrows,
+                                               int M, int NP, int rt, int ct, int lane) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    const int64_t gr = r0 + row;
+    if (gr >= nrows) continue;
+    const int64_t li = gr / M;
+    const int m = (int)(gr - li * M);
+    const int64_t item = list ? (int64_t)list[li] : li;
+    Z[(item * M + m) * NP + ct * 32 + (lane & 31)] = acc[r];
+  }
+}
+
+template <int NCT>
+__global__ __launch_bounds__(256) void k_acf_proj_f32(const float *__restrict__ F, const float *__restrict__ Wc, float *__restrict__ Z,
+                                                      const int32_t *__restrict__ list, const int32_t *__restrict__ nlist, int nall,
+                                                      int M, int C, int Cp) {
+  constexpr int NP = 32 * NCT, NJ = (NCT + 1) / 2;
+  __shared__ float As[64][33];
+  __shared__ __attribute__((aligned(16))) float Bs[32][NP];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, rt = w & 1, cq = w >> 1;
+  const int64_t nrows = (int64_t)(list ? *nlist : nall) * M;
+  const int64_t tiles = (nrows + 63) / 64;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t r0 = tile * 64;
+    const float *src[2];
+    int lrow[2], lc4[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int idx = tid + 256 * q;
+      lrow[q] = idx >> 3; lc4[q] = idx & 7;
+      const int64_t gr = r0 + lrow[q];
+      src[q] = nullptr;
+      if (gr < nrows) {
+        const int64_t li = gr / M;
+        const int64_t item = list ? (int64_t)list[li] : li;
+        src[q] = F + (item * M + (gr - li * M)) * (int64_t)C;
+      }
+    }
+    f32x16 acc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+      for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    for (int kc = 0; kc < Cp; kc += 32) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int col = kc + lc4[q] * 4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (src[q] && col < C) v = *(const float4 *)(src[q] + col);
+        float *d = &As[lrow[q]][lc4[q] * 4];
+        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+      }
+      for (int e = tid; e < 8 * NP; e += 256) {
+        const int r = e / (NP / 4), c4 = e % (NP / 4);
+        *(float4 *)&Bs[r][c4 * 4] = *(const float4 *)(Wc + (int64_t)(kc + r) * NP + c4 * 4);
+      }
+      __syncthreads();
+#pragma unroll
+      for (int kk = 0; kk < 32; kk += 2) {
+        const float a = As[rt * 32 + (lane & 31)][kk + (lane >> 5)];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          const int ct = cq + 2 * j;
+          if (ct < NCT) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, Bs[kk + (lane >> 5)][ct * 32 + (lane & 31)], acc[j], 0, 0, 0);
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int ct = cq + 2 * j;
+      if (ct < NCT) acf_store_tile(Z, acc[j], list, r0, nrows, M, NP, rt, ct, lane);
+    }
+  }
+}
+
+// bf16 features: A = the feature rows (bf16, exact), B = W as hi + lo bf16 halves (two MFMAs), fp32 accumulation
+template <int NCT>
+__global__ __launch_bounds__(256) void k_acf_proj_bf16(const uint16_t *__restrict__ F, const uint16_t *__restrict__ Wh,
+                                                       const uint16_t *__restrict__ Wl, float *__restrict__ Z,
+                                                       const int32_t *__restrict__ list, const int32_t *__restrict__ nlist, int nall,
+                                                       int M, int C, int Cp) {
+  constexpr int NP = 32 * NCT, NJ = (NCT + 1) / 2;
+  __shared__ __attribute__((aligned(16))) uint16_t As[64][40];
+  __shared__ __attribute__((aligned(16))) uint16_t Bh[NP][40];
+  __shared__ __attribute__((aligned(16))) uint16_t Bl[NP][40];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, rt = w & 1, cq = w >> 1;
+  const int64_t nrows = (int64_t)(list ? *nlist : nall) * M;
+  const int64_t tiles = (nrows + 63) / 64;
+  const int lrow = tid >> 2, lc8 = tid & 3;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t r0 = tile * 64;
+    const uint16_t *src = nullptr;
+    {
+      const int64_t gr = r0 + lrow;
+      if (gr < nrows) {
+        const int64_t li = gr / M;
+        const int64_t item = list ? (int64_t)list[li] : li;
+        src = F + (item * M + (gr - li * M)) * (int64_t)C;
+      }
+    }
+    f32x16 acc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+      for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    for (int kc = 0; kc < Cp; kc += 32) {
+      {
+        const int col = kc + lc8 * 8;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (src && col < C) v = *(const uint4 *)(src + col);
+        *(uint4 *)&As[lrow][lc8 * 8] = v;
+      }
+      for (int e = tid; e < NP * 4; e += 256) {
+        const int r = e >> 2, c8 = e & 3;
+        *(uint4 *)&Bh[r][c8 * 8] = *(const uint4 *)(Wh + (int64_t)r * Cp + kc + c8 * 8);
+        *(uint4 *)&Bl[r][c8 * 8] = *(const uint4 *)(Wl + (int64_t)r * Cp + kc + c8 * 8);
+      }
+      __syncthreads();
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const bf16x8 a = *(const bf16x8 *)&As[rt * 32 + (lane & 31)][ks * 16 + 8 * (lane >> 5)];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          const int ct = cq + 2 * j;
+          if (ct < NCT) {
+            const bf16x8 bh = *(const bf16x8 *)&Bh[ct * 32 + (lane & 31)][ks * 16 + 8 * (lane >> 5)];
+            const bf16x8 bl = *(const bf16x8 *)&Bl[ct * 32 + (lane & 31)][ks * 16 + 8 * (lane >> 5)];
+            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bh, acc[j], 0, 0, 0);
+            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bl, acc[j], 0, 0, 0);
+          }
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int ct = cq + 2 * j;
+      if (ct < NCT) acf_store_tile(Z, acc[j], list, r0, nrows, M, NP, rt, ct, lane);
+    }
+  }
+}
+
+// ---- GP_l = Wiv^T Gi_l + Wip^T Pi_l (ACF.py:167-170), one wave per listed item ---------------------------------------
+__global__ __launch_bounds__(256) void k_acf_itemvec(const float *__restrict__ Gi, const float *__restrict__ Pi,
+                                                     const float *__restrict__ Wiv, const float *__restrict__ Wip,
+                                                     const int32_t *__restrict__ list, const int32_t *__restrict__ nlist, int nall,
+                                                     int k, int ha, float *__restrict__ GP) {
+  const int n = list ? *nlist : nall;
+  const int lane = threadIdx.x & 63;
+  for (int t = blockIdx.x * 4 + (threadIdx.x >> 6); t < n; t += gridDim.x * 4) {
+    const int64_t l = list ? list[t] : t;
+    const float *g = Gi + l * k, *p = Pi + l * k;
+    for (int j = lane; j < ha; j += 64) {
+      float sv = 0.f, sp = 0.f;
+      for (int c = 0; c < k; ++c) {
+        sv = fmaf(g[c], Wiv[(int64_t)c * ha + j], sv);
+        sp = fmaf(p[c], Wip[(int64_t)c * ha + j], sp);
+      }
+      GP[l * ha + j] = sv + sp;
+    }
+  }
+}
+
+// ---- user profiles (calculate_beta_alpha, ACF.py:135-181) --------------------------------------------------------------
+struct AcfUserArgs {
+  const float *Gu, *Pi, *Z, *GP;
+  const float *wcu, *bc0, *w1c, *bc1, *wiu, *bi0, *w1i, *bi1;
+  const int64_t *ptr;
+  const int32_t *items;
+  int32_t *errflag;
+  int U, I, k, M, hc, ha, NP;
+};
+
+// One workgroup (4 waves) per position b.  Wave w walks history entries w, w+4, ...; for each item l:
+//   s_m = w1c.relu(uc + Z_lm[:h]) + bc1 (lane per m), beta = softmax_m(s), xz = sum_m beta_m Z_lm[h:] (lane per column),
+//   t = w1i.relu(ui + GP_l + xz) + bi1; the wave keeps a running max / denominator / sum of e^(t - max) Pi_l.
+// LDS: gu[k] uc[h] ui[a] w1c[h] w1i[a] | per wave: beta[M], acc[k] | wmx[4] wden[4]
+__global__ __launch_bounds__(256) void k_acf_user(AcfUserArgs A, const int32_t *__restrict__ users, int64_t n,
+                                                  const int32_t *__restrict__ uslot, float *__restrict__ out) {
+  extern __shared__ float sm[];
+  const int64_t b = blockIdx.x;
+  if (b >= n) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int u = users ? acf_clamp(users[b], A.U, A.errflag, 1) : (int)b;
+  if (uslot && uslot[u] != (int32_t)b) return;
+  const int k = A.k, M = A.M, hc = A.hc, ha = A.ha, NP = A.NP;
+  float *gu = sm, *uc = gu + k, *ui = uc + hc, *w1c = ui + ha, *w1i = w1c + hc;
+  float *wbase = w1i + ha;
+  float *beta = wbase + (size_t)w * (M + k), *acc = beta + M;
+  float *wmx = wbase + 4 * (size_t)(M + k), *wden = wmx + 4;
+  for (int c = tid; c < k; c += 256) gu[c] = A.Gu[(int64_t)u * k + c];
+  for (int j = tid; j < hc; j += 256) w1c[j] = A.w1c[j];
+  for (int j = tid; j < ha; j += 256) w1i[j] = A.w1i[j];
+  __syncthreads();
+  for (int j = tid; j < hc + ha; j += 256) {                 // W_0_u^T g_u + b_0 of both levels
+    float s = 0.f;
+    if (j < hc) {
+      for (int c = 0; c < k; ++c) s = fmaf(gu[c], A.wcu[(int64_t)c * hc + j], s);
+      uc[j] = s + A.bc0[j];
+    } else {
+      const int jj = j - hc;
+      for (int c = 0; c < k; ++c) s = fmaf(gu[c], A.wiu[(int64_t)c * ha + jj], s);
+      ui[jj] = s + A.bi0[jj];
+    }
+  }
+  for (int c = lane; c < k; c += 64) acc[c] = 0.f;
+  __syncthreads();
+  const float bc1 = A.bc1[0], bi1 = A.bi1[0];
+  const int64_t beg = A.ptr[u], end = A.ptr[u + 1];
+  float mx = -INFINITY, den = 0.f;
+  for (int64_t p = beg + w; p < end; p += 4) {
+    const int l = acf_clamp(A.items[p], A.I, A.errflag, 5);
+    const float *Zl = A.Z + (int64_t)l * M * NP;
+    float lmax = -INFINITY;
+    for (int m = lane; m < M; m += 64) {
+      const float *z = Zl + (int64_t)m * NP;
+      float s = 0.f;
+      for (int j = 0; j < hc; ++j) s = fmaf(w1c[j], fmaxf(uc[j] + z[j], 0.f), s);
+      s += bc1;
+      beta[m] = s;
+      lmax = fmaxf(lmax, s);
+    }
+    lmax = wave_max(lmax);
+    wave_sync();
+    float lsum = 0.f;
+    for (int m = lane; m < M; m += 64) {
+      const float e = expf(beta[m] - lmax);
+      beta[m] = e;
+      lsum += e;
+    }
+    lsum = wave_sum(lsum);
+    wave_sync();
+    const float inv = 1.0f / lsum;
+    float tp = 0.f;
+    for (int j = lane; j < ha; j += 64) {
+      float xz = 0.f;
+      for (int m = 0; m < M; ++m) xz = fmaf(beta[m], Zl[(int64_t)m * NP + hc + j], xz);
+      tp = fmaf(w1i[j], fmaxf(ui[j] + A.GP[(int64_t)l * ha + j] + xz * inv, 0.f), tp);
+    }
+    const float t = wave_sum(tp) + bi1;
+    const float nmx = fmaxf(mx, t);
+    const float sc = expf(mx - nmx), e = expf(t - nmx);        // (mx = -inf at the first item: sc = 0)
+    den = den * sc + e;
+    const float *pl = A.Pi + (int64_t)l * k;
+    for (int c = lane; c < k; c += 64) acc[c] = acc[c] * sc + e * pl[c];
+    mx = nmx;
+    wave_sync();                                               // beta is rewritten by the next item
+  }
+  if (lane == 0) { wmx[w] = mx; wden[w] = den; }
+  __syncthreads();
+  float gm = -INFINITY;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) gm = fmaxf(gm, wmx[q]);
+  float f[4], D = 0.f;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    f[q] = wden[q] > 0.f ? expf(wmx[q] - gm) : 0.f;
+    D += wden[q] * f[q];
+  }
+  for (int c = tid; c < k; c += 256) {
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (f[q] != 0.f) s += wbase[(size_t)q * (M + k) + M + c] * f[q];
+    out[b * k + c] = D > 0.f ? gu[c] + s / D : gu[c];
+  }
+}
+
+// ---- step ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_acf_claim(const int32_t *__restrict__ user, int64_t B, int U, int32_t *__restrict__ uslot,
+                                                   int32_t *errflag) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) atomicMin(uslot + acf_clamp(user[b], U, errflag, 1), (int32_t)b);
+}
+
+struct AcfStepArgs {
+  const float *Gu, *Gi, *Pi, *gp;
+  float *dGu, *dGi, *dPi, *lossb;
+  const int32_t *uslot;
+  int32_t *errflag;
+  int U, I, k;
+  float reg;
+};
+
+// one wave per triplet (ACF.py:239-270 with the detached g'_u)
+__global__ __launch_bounds__(256) void k_acf_triplet(AcfStepArgs A, const int32_t *__restrict__ user, const int32_t *__restrict__ pos,
+                                                     const int32_t *__restrict__ neg, int64_t B) {
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (b >= B) return;
+  const int u = acf_clamp(user[b], A.U, A.errflag, 1), i = acf_clamp(pos[b], A.I, A.errflag, 2),
+            j = acf_clamp(neg[b], A.I, A.errflag, 2);
+  const int k = A.k;
+  const float *g = A.gp + (int64_t)A.uslot[u] * k;
+  const float *gu = A.Gu + (int64_t)u * k, *gi = A.Gi + (int64_t)i * k, *gj = A.Gi + (int64_t)j * k;
+  const float *pi = A.Pi + (int64_t)i * k, *pj = A.Pi + (int64_t)j * k;
+  float xp = 0.f, xn = 0.f, nrm = 0.f;
+  for (int c = lane; c < k; c += 64) {
+    xp = fmaf(g[c], gi[c], xp);
+    xn = fmaf(g[c], gj[c], xn);
+    nrm += gu[c] * gu[c] + gi[c] * gi[c] + gj[c] * gj[c] + pi[c] * pi[c] + pj[c] * pj[c];
+  }
+  xp = wave_sum(xp); xn = wave_sum(xn); nrm = wave_sum(nrm);
+  const float diff = xp - xn;
+  const bool inr = (diff >= -80.0f) && (diff <= 1e8f);                 // tf.clip_by_value gradient mask
+  const float cl = fminf(fmaxf(diff, -80.0f), 1e8f);
+  const float z = -cl;                                                 // softplus(z), stable form
+  const float sp = z > 0.f ? z + log1pf(expf(-z)) : log1pf(expf(z));
+  const float gd = inr ? -1.0f / (1.0f + expf(diff)) : 0.f;           // -sigmoid(-diff)
+  const float r2 = 2.f * A.reg;
+  if (lane == 0) A.lossb[b] = sp + A.reg * nrm;
+  float *dgu = A.dGu + (int64_t)u * k, *dgi = A.dGi + (int64_t)i * k, *dgj = A.dGi + (int64_t)j * k;
+  float *dpi = A.dPi + (int64_t)i * k, *dpj = A.dPi + (int64_t)j * k;
+  for (int c = lane; c < k; c += 64) {
+    atomicAdd(dgi + c, gd * g[c] + r2 * gi[c]);
+    atomicAdd(dgj + c, -gd * g[c] + r2 * gj[c]);
+    if (r2 != 0.f) {
+      atomicAdd(dgu + c, r2 * gu[c]);
+      atomicAdd(dpi + c, r2 * pi[c]);
+      atomicAdd(dpj + c, r2 * pj[c]);
+    }
+  }
+}
+
+// The attention tensors (gradient 2 reg w only) and the step's loss, in ONE workgroup: fixed summation order.
+struct AcfDenseArgs {
+  float *w[BPRX_ACF_NW], *m[BPRX_ACF_NW], *v[BPRX_ACF_NW];
+  int64_t n[BPRX_ACF_NW];
+};
+__global__ __launch_bounds__(1024) void k_acf_dense(AcfDenseArgs T, int adam, float lr_t, float reg, float b1, float b2, float eps,
+                                                    const float *__restrict__ lossb, int64_t B, float *__restrict__ loss_out) {
+  __shared__ double red[1024];
+  const float omb1 = 1.0f - b1, omb2 = 1.0f - b2, r2 = 2.f * reg;
+  double sq = 0.0, ls = 0.0;
+  for (int q = 0; q < BPRX_ACF_NW; ++q) {
+    float *p = T.w[q];
+    for (int64_t e = threadIdx.x; e < T.n[q]; e += 1024) {
+      const float pv = p[e], g = r2 * pv;
+      sq += (double)pv * (double)pv;
+      if (adam) {                                            // TF-2.3 dense ApplyAdam (as k_dense_update / k_fact_update)
+        const float mo = T.m[q][e], vo = T.v[q][e];
+        const float mt = mo + (g - mo) * omb1;
+        const float vt = vo + (g * g - vo) * omb2;
+        T.m[q][e] = mt; T.v[q][e] = vt;
+        p[e] = pv - lr_t * mt / (sqrtf(vt) + eps);
+      } else {
+        p[e] = pv - lr_t * g;
+      }
+    }
+  }
+  for (int64_t b = threadIdx.x; b < B; b += 1024) ls += (double)lossb[b];
+  red[threadIdx.x] = ls + (double)reg * sq;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && loss_out) *loss_out = (float)red[0];
+}
+
+// sgd on the touched rows: one wave per (triplet, role); the first claimant of a row applies and clears its gradient
+__global__ __launch_bounds__(256) void k_acf_apply_sgd(float *Gu, float *Gi, float *Pi, float *dGu, float *dGi, float *dPi,
+                                                       uint32_t *flagU, uint32_t *flagI, const int32_t *__restrict__ user,
+                                                       const int32_t *__restrict__ pos, const int32_t *__restrict__ neg, int64_t B,
+                                                       int U, int I, int k, float lr) {
+  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (t >= 3 * B) return;
+  const int role = (int)(t / B);
+  const int64_t b = t - (int64_t)role * B;
+  int r;
+  if (role == 0) {
+    r = user[b]; r = r < 0 ? 0 : (r >= U ? U - 1 : r);
+  } else {
+    r = role == 1 ? pos[b] : neg[b]; r = r < 0 ? 0 : (r >= I ? I - 1 : r);
+  }
+  int claim = 0;
+  if (lane == 0) claim = atomicExch(role == 0 ? flagU + r : flagI + r, 1u) == 0u;
+  claim = __shfl(claim, 0, 64);
+  if (!claim) return;
+  const int64_t o = (int64_t)r * k;
+  for (int c = lane; c < k; c += 64) {
+    if (role == 0) {
+      Gu[o + c] -= lr * dGu[o + c]; dGu[o + c] = 0.f;
+    } else {
+      Gi[o + c] -= lr * dGi[o + c]; dGi[o + c] = 0.f;
+      Pi[o + c] -= lr * dPi[o + c]; dPi[o + c] = 0.f;
+    }
+  }
+}
+
+// adam_tf23 (sparse rule, not lazy): every row of Gu, Gi, Pi moves every step (ACF.py:266-268)
+struct AcfSweep { float *p[3], *m[3], *v[3], *g[3]; size_t n[3]; };
+__global__ __launch_bounds__(256) void k_acf_sweep(AcfSweep S, float b1, float b2, float lr_t, float eps) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x, first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+#pragma unroll
+  for (int q = 0; q < 3; ++q)
+    for (size_t e = first; e < S.n[q]; e += stride) {
+      float pp = S.p[q][e], mm = S.m[q][e], vv = S.v[q][e];
+      adam_elem(pp, mm, vv, S.g[q][e], b1, b2, lr_t, eps);
+      S.p[q][e] = pp; S.m[q][e] = mm; S.v[q][e] = vv;
+      S.g[q][e] = 0.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_acf_finish(const int32_t *__restrict__ user, const int32_t *__restrict__ pos,
+                                                    const int32_t *__restrict__ neg, int64_t B, int U, int I, int32_t *uslot,
+                                                    uint32_t *flagU, uint32_t *flagI) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  int u = user[b], i = pos[b], j = neg[b];
+  u = u < 0 ? 0 : (u >= U ? U - 1 : u);
+  i = i < 0 ? 0 : (i >= I ? I - 1 : i);
+  j = j < 0 ? 0 : (j >= I ? I - 1 : j);
+  uslot[u] = INT_MAX;
+  flagU[u] = 0u; flagI[i] = 0u; flagI[j] = 0u;
+}
+
+// score_pairs: x_b = g'_b . Gi_item (ACF.py:210)
+__global__ __launch_bounds__(256) void k_acf_score(const float *__restrict__ gp, const float *__restrict__ Gi,
+                                                   const int32_t *__restrict__ item, int64_t n, int I, int k, float *__restrict__ x,
+                                                   int32_t *errflag) {
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (b >= n) return;
+  const int i = acf_clamp(item[b], I, errflag, 2);
+  float s = 0.f;
+  for (int c = lane; c < k; c += 64) s = fmaf(gp[b * k + c], Gi[(int64_t)i * k + c], s);
+  s = wave_sum(s);
+  if (lane == 0) x[b] = s;
+}
+
+__global__ void k_acf_fill(int32_t *p, size_t n, int32_t v) {
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) p[e] = v;
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------
+static unsigned acf_grid(int64_t work, int64_t per_block, int64_t cap) {
+  int64_t g = (work + per_block - 1) / per_block;
+  if (g > cap) g = cap;
+  return (unsigned)(g < 1 ? 1 : g);
+}
+
+static int acf_wcat(bprx_handle *h, hipStream_t s) {
+  AcfState *S = h->acf;
+  const bool bf = S->fdt == BPRX_F_BF16;
+  hipLaunchKernelGGL(k_acf_wcat, dim3(acf_grid((int64_t)S->Cp * S->NP, 256, 2048)), dim3(256), 0, s, S->a.w[BPRX_ACF_C_WI],
+                     S->a.w[BPRX_ACF_I_WX], S->C, S->Cp, S->hc, S->ha, S->NP, bf ? (float *)nullptr : S->Wc,
+                     bf ? S->Wh : (uint16_t *)nullptr, bf ? S->Wl : (uint16_t *)nullptr);
+  BPRX_LAUNCH_CHECK(h, "k_acf_wcat");
+  return BPRX_OK;
+}
+
+// Z and GP of the listed items (list == nullptr: every item)
+static int acf_project(bprx_handle *h, const int32_t *list, const int32_t *nlist, hipStream_t s) {
+  AcfState *S = h->acf;
+  const int I = h->cfg.num_items, NCT = S->NP / 32;
+  const unsigned pg = acf_grid((int64_t)I * S->M, 64, (int64_t)h->num_cu * 4);
+  {
+    BprxProfScope ps(h, BPRX_PHASE_PROJ_FWD, s);
+#define ACF_PROJ(N)                                                                                                           \
+  case N:                                                                                                                     \
+    if (S->fdt == BPRX_F_BF16)                                                                                                \
+      hipLaunchKernelGGL(k_acf_proj_bf16<N>, dim3(pg), dim3(256), 0, s, (const uint16_t *)S->a.F, S->Wh, S->Wl, S->Z, list,    \
+                         nlist, I, S->M, S->C, S->Cp);                                                                        \
+    else                                                                                                                      \
+      hipLaunchKernelGGL(k_acf_proj_f32<N>, dim3(pg), dim3(256), 0, s, (const float *)S->a.F, S->Wc, S->Z, list, nlist, I,     \
+                         S->M, S->C, S->Cp);                                                                                  \
+    break;
+    switch (NCT) {
+      ACF_PROJ(1) ACF_PROJ(2) ACF_PROJ(3) ACF_PROJ(4) ACF_PROJ(5) ACF_PROJ(6) ACF_PROJ(7) ACF_PROJ(8)
+      default: BPRX_FAIL(h, BPRX_E_INVALID, "acf: h + a > %d", ACF_MAX_NP);
+    }
+#undef ACF_PROJ
+    BPRX_LAUNCH_CHECK(h, "k_acf_proj");
+  }
+  hipLaunchKernelGGL(k_acf_itemvec, dim3(acf_grid(I, 4, 4096)), dim3(256), 0, s, h->t.Gi, S->a.Pi, S->a.w[BPRX_ACF_I_WV],
+                     S->a.w[BPRX_ACF_I_WP], list, nlist, I, S->k, S->ha, S->GP);
+  BPRX_LAUNCH_CHECK(h, "k_acf_itemvec");
+  return BPRX_OK;
+}
+
+// Z / GP for the distinct items of the histories of users[0..n) (uslot: first positions only)
+static int acf_prepare(bprx_handle *h, const int32_t *users, int64_t n, const int32_t *uslot, const int64_t *ptr,
+                       const int32_t *items, hipStream_t s) {
+  AcfState *S = h->acf;
+  int rc;
+  if ((rc = acf_wcat(h, s))) return rc;
+  BPRX_HIP(h, hipMemsetAsync(S->nlist, 0, sizeof(int32_t), s));
+  {
+    BprxProfScope ps(h, BPRX_PHASE_ROW_COUNT, s);
+    hipLaunchKernelGGL(k_acf_mark, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, users, n, uslot, ptr, items, h->cfg.num_users,
+                       h->cfg.num_items, S->imark, S->ilist, S->nlist, h->errflag);
+    BPRX_LAUNCH_CHECK(h, "k_acf_mark");
+  }
+  if ((rc = acf_project(h, S->ilist, S->nlist, s))) return rc;
+  hipLaunchKernelGGL(k_acf_unmark, dim3(256), dim3(256), 0, s, S->ilist, S->nlist, S->imark);
+  BPRX_LAUNCH_CHECK(h, "k_acf_unmark");
+  return BPRX_OK;
+}
+
+static size_t acf_user_lds(const AcfState *S) {
+  return sizeof(float) * ((size_t)S->k + 2 * (S->hc + S->ha) + 4 * (size_t)(S->M + S->k) + 8);
+}
+
+static int acf_users(bprx_handle *h, const int32_t *users, int64_t n, const int32_t *uslot, const int64_t *ptr,
+                     const int32_t *items, float *out, hipStream_t s) {
+  AcfState *S = h->acf;
+  AcfUserArgs A;
+  A.Gu = h->t.Gu; A.Pi = S->a.Pi; A.Z = S->Z; A.GP = S->GP;
+  A.wcu = S->a.w[BPRX_ACF_C_WU]; A.bc0 = S->a.w[BPRX_ACF_C_B0]; A.w1c = S->a.w[BPRX_ACF_C_W1]; A.bc1 = S->a.w[BPRX_ACF_C_B1];
+  A.wiu = S->a.w[BPRX_ACF_I_WU]; A.bi0 = S->a.w[BPRX_ACF_I_B0]; A.w1i = S->a.w[BPRX_ACF_I_W1]; A.bi1 = S->a.w[BPRX_ACF_I_B1];
+  A.ptr = ptr; A.items = items; A.errflag = h->errflag;
+  A.U = h->cfg.num_users; A.I = h->cfg.num_items; A.k = S->k; A.M = S->M; A.hc = S->hc; A.ha = S->ha; A.NP = S->NP;
+  BprxProfScope ps(h, BPRX_PHASE_TRIPLET, s);
+  hipLaunchKernelGGL(k_acf_user, dim3((unsigned)n), dim3(256), acf_user_lds(S), s, A, users, n, uslot, out);
+  BPRX_LAUNCH_CHECK(h, "k_acf_user");
+  return BPRX_OK;
+}
+
+int bprx_acf_step(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B, float *loss_out,
+                  hipStream_t s) {
+  AcfState *S = h->acf;
+  if (B <= 0) BPRX_FAIL(h, BPRX_E_INVALID, "step: empty batch");
+  if (!user || !pos || !neg) BPRX_FAIL(h, BPRX_E_INVALID, "step: null index pointer");
+  const int U = h->cfg.num_users, I = h->cfg.num_items, k = S->k;
+  const bool adam = h->cfg.optimizer == BPRX_OPT_ADAM_TF23;
+  float lr_t = h->cfg.lr;
+  if (adam) {
+    h->adam_t += 1;
+    const float t = (float)h->adam_t;
+    lr_t = h->cfg.lr * sqrtf(1.0f - powf(h->cfg.beta2, t)) / (1.0f - powf(h->cfg.beta1, t));
+  }
+  h->pend_lr = lr_t;
+  int rc;
+  hipLaunchKernelGGL(k_acf_claim, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, user, B, U, S->uslot, h->errflag);
+  BPRX_LAUNCH_CHECK(h, "k_acf_claim");
+  if ((rc = acf_prepare(h, user, B, S->uslot, S->a.train_ptr, S->a.train_items, s))) return rc;
+  if ((rc = acf_users(h, user, B, S->uslot, S->a.train_ptr, S->a.train_items, S->gp, s))) return rc;
+  AcfStepArgs A;
+  A.Gu = h->t.Gu; A.Gi = h->t.Gi; A.Pi = S->a.Pi; A.gp = S->gp;
+  A.dGu = h->dGu; A.dGi = h->dGi; A.dPi = S->dPi; A.lossb = h->lossb;
+  A.uslot = S->uslot; A.errflag = h->errflag; A.U = U; A.I = I; A.k = k; A.reg = h->cfg.reg;
+  {
+    BprxProfScope ps(h, BPRX_PHASE_ITEM_SEG, s);
+    hipLaunchKernelGGL(k_acf_triplet, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, A, user, pos, neg, B);
+    BPRX_LAUNCH_CHECK(h, "k_acf_triplet");
+  }
+  {
+    BprxProfScope ps(h, BPRX_PHASE_DENSE, s);
+    AcfDenseArgs T;
+    for (int q = 0; q < BPRX_ACF_NW; ++q) { T.w[q] = S->a.w[q]; T.m[q] = S->a.m_w[q]; T.v[q] = S->a.v_w[q]; T.n[q] = S->nw[q]; }
+    hipLaunchKernelGGL(k_acf_dense, dim3(1), dim3(1024), 0, s, T, adam ? 1 : 0, lr_t, h->cfg.reg, h->cfg.beta1, h->cfg.beta2,
+                       h->cfg.epsilon, h->lossb, B, loss_out);
+    BPRX_LAUNCH_CHECK(h, "k_acf_dense");
+  }
+  {
+    BprxProfScope ps(h, BPRX_PHASE_APPLY, s);
+    if (adam) {
+      AcfSweep W;
+      W.p[0] = h->t.Gu; W.m[0] = h->t.m_Gu; W.v[0] = h->t.v_Gu; W.g[0] = h->dGu; W.n[0] = (size_t)U * k;
+      W.p[1] = h->t.Gi; W.m[1] = h->t.m_Gi; W.v[1] = h->t.v_Gi; W.g[1] = h->dGi; W.n[1] = (size_t)I * k;
+      W.p[2] = S->a.Pi; W.m[2] = S->a.m_Pi; W.v[2] = S->a.v_Pi; W.g[2] = S->dPi; W.n[2] = (size_t)I * k;
+      const size_t most = (size_t)(U > I ? U : I) * k;
+      hipLaunchKernelGGL(k_acf_sweep, dim3(acf_grid((int64_t)most, 256, 4096)), dim3(256), 0, s, W, h->cfg.beta1, h->cfg.beta2,
+                         lr_t, h->cfg.epsilon);
+      BPRX_LAUNCH_CHECK(h, "k_acf_sweep");
+    } else {
+      hipLaunchKernelGGL(k_acf_apply_sgd, dim3((unsigned)((3 * B + 3) / 4)), dim3(256), 0, s, h->t.Gu, h->t.Gi, S->a.Pi, h->dGu,
+                         h->dGi, S->dPi, h->flagU, h->flagI, user, pos, neg, B, U, I, k, lr_t);
+      BPRX_LAUNCH_CHECK(h, "k_acf_apply_sgd");
+    }
+  }
+  hipLaunchKernelGGL(k_acf_finish, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, user, pos, neg, B, U, I, S->uslot, h->flagU,
+                     h->flagI);
+  BPRX_LAUNCH_CHECK(h, "k_acf_finish");
+  S->eval_valid = false;
+  return BPRX_OK;
+}
+
+int bprx_acf_score_pairs(bprx_handle *h, const int32_t *u, const int32_t *i, int64_t B, float *x, hipStream_t s) {
+  AcfState *S = h->acf;
+  int rc;
+  if ((rc = acf_prepare(h, u, B, nullptr, S->a.train_ptr, S->a.train_items, s))) return rc;
+  if ((rc = acf_users(h, u, B, nullptr, S->a.train_ptr, S->a.train_items, S->gp, s))) return rc;
+  hipLaunchKernelGGL(k_acf_score, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, S->gp, h->t.Gi, i, B, h->cfg.num_items, S->k, x,
+                     h->errflag);
+  BPRX_LAUNCH_CHECK(h, "k_acf_score");
+  return BPRX_OK;
+}
+
+int bprx_acf_eval_profiles(bprx_handle *h, hipStream_t s) {
+  AcfState *S = h->acf;
+  if (S->eval_valid) return BPRX_OK;
+  int rc;
+  if ((rc = acf_wcat(h, s))) return rc;
+  if ((rc = acf_project(h, nullptr, nullptr, s))) return rc;
+  const int64_t *ptr = S->a.eval_ptr ? S->a.eval_ptr : S->a.train_ptr;
+  const int32_t *items = S->a.eval_ptr ? S->a.eval_items : S->a.train_items;
+  if ((rc = acf_users(h, nullptr, h->cfg.num_users, nullptr, ptr, items, S->Gup, s))) return rc;
+  S->eval_valid = true;
+  return BPRX_OK;
+}
+
+float *bprx_acf_eval_gu(bprx_handle *h) { return h->acf->Gup; }
+
+void bprx_acf_invalidate(bprx_handle *h) {
+  if (h->acf) h->acf->eval_valid = false;
+}
+
+void bprx_acf_free(bprx_handle *h) {
+  AcfState *S = h->acf;
+  if (!S) return;
+  void *ptrs[] = {S->Z, S->GP, S->Wc, S->Wh, S->Wl, S->gp, S->Gup, S->dPi, S->uslot, S->imark, S->ilist, S->nlist};
+  for (void *p : ptrs)
+    if (p) (void)hipFree(p);
+  delete S;
+  h->acf = nullptr;
+}
+
+int bprx_bind_tables_internal(bprx_handle *h, const bprx_tables *t);
+
+extern "C" int bprx_bind_acf(bprx_handle *h, const bprx_tables *t, const bprx_acf *a) {
+  if (!h || !t || !a) return BPRX_E_INVALID;
+  const bprx_config &c = h->cfg;
+  if (c.model != BPRX_MODEL_BPRMF) BPRX_FAIL(h, BPRX_E_INVALID, "bind_acf: needs a BPRMF handle");
+  if (c.flags & (BPRX_FLAG_EXPORT_USER_GRAD | BPRX_FLAG_EXPORT_ITEM_GRAD))
+    BPRX_FAIL(h, BPRX_E_INVALID, "bind_acf: exported gradients (multi-GPU) are not supported");
+  if (a->feat_dtype != BPRX_F_FP32 && a->feat_dtype != BPRX_F_BF16)
+    BPRX_FAIL(h, BPRX_E_INVALID, "bind_acf: features must be fp32 or bf16 (feat_dtype %d)", a->feat_dtype);
+  if (a->feat_m <= 0 || a->feat_m > ACF_MAX_M) BPRX_FAIL(h, BPRX_E_INVALID, "bind_acf: M = %d outside [1, %d]", a->feat_m, ACF_MAX_M);
+  if (a->feat_c <= 0 || a->feat_c % (a->feat_dtype == BPRX_F_BF16 ? 8 : 4))
+    BPRX_FAIL(h, BPRX_E_INVALID, "bind_acf: C = %d must be a positive multiple of %d", a->feat_c, a->feat_dtype == BPRX_F_BF16 ? 8 : 4);
+  if (a->width_c <= 0 || a->width_i <= 0 || a->width_c + a->width_i > ACF_MAX_NP)
+    BPRX_FAIL(h, BPRX_E_INVALID, "bind_acf: need h, a > 0 and h + a <= %d (%d, %d)", ACF_MAX_NP, a->width_c, a->width_i);
+  if (c.embed_k > ACF_MAX_K) BPRX_FAIL(h, BPRX_E_INVALID, "bind_acf: embed_k %d > %d", c.embed_k, ACF_MAX_K);
+  if (!a->F || !a->train_ptr || !a->train_items || !a->Pi) BPRX_FAIL(h, BPRX_E_INVALID, "bind_acf: F, train CSR and Pi are required");
+  if ((uintptr_t)a->F & 15) BPRX_FAIL(h, BPRX_E_INVALID, "bind_acf: F must be 16-byte aligned");
+  if (!a->eval_ptr != !a->eval_items) BPRX_FAIL(h, BPRX_E_INVALID, "bind_acf: eval_ptr and eval_items go together");
+  const bool adam = c.optimizer == BPRX_OPT_ADAM_TF23;
+  for (int q = 0; q < BPRX_ACF_NW; ++q) {
+    if (!a->w[q]) BPRX_FAIL(h, BPRX_E_INVALID, "bind_acf: attention tensor %d is missing", q);
+    if (adam && (!a->m_w[q] || !a->v_w[q])) BPRX_FAIL(h, BPRX_E_INVALID, "bind_acf: adam_tf23 needs m_/v_ slots of tensor %d", q);
+  }
+  if (adam && (!a->m_Pi || !a->v_Pi)) BPRX_FAIL(h, BPRX_E_INVALID, "bind_acf: adam_tf23 needs m_/v_ slots for Pi");
+  AcfState *S = h->acf;
+  const int NP = 32 * ((a->width_c + a->width_i + 31) / 32);
+  if (S && (S->M != a->feat_m || S->C != a->feat_c || S->hc != a->width_c || S->ha != a->width_i || S->fdt != a->feat_dtype))
+    bprx_acf_free(h), S = nullptr;
+  int rc = bprx_bind_tables_internal(h, t);
+  if (rc) return rc;
+  // TF-2.3's Adam moves every row every step: an ACF handle takes the whole-table sweeps (bring lazily held rows up to date first)
+  if (h->adam_lazy) {
+    if ((rc = bprx_launch_adam_sync(h, h->adam_t, nullptr))) return rc;
+    BPRX_HIP(h, hipStreamSynchronize(nullptr));
+    h->adam_lazy = false;
+  }
+  const size_t U = c.num_users, I = c.num_items, k = c.embed_k, MB = c.max_batch;
+  if (!S) {
+    S = new (std::nothrow) AcfState();
+    if (!S) BPRX_FAIL(h, BPRX_E_NOMEM, "bind_acf: out of host memory");
+    memset(S, 0, sizeof(*S));
+    h->acf = S;
+    S->M = a->feat_m; S->C = a->feat_c; S->hc = a->width_c; S->ha = a->width_i; S->NP = NP; S->k = (int)k; S->fdt = a->feat_dtype;
+    S->Cp = (S->C + 31) / 32 * 32;
+    bool ok = true;
+    auto al = [&](void **p, size_t bytes) { ok = ok && hipMalloc(p, bytes) == hipSuccess && hipMemset(*p, 0, bytes) == hipSuccess; };
+    al((void **)&S->Z, I * S->M * NP * sizeof(float));
+    al((void **)&S->GP, I * S->ha * sizeof(float));
+    if (S->fdt == BPRX_F_BF16) {
+      al((void **)&S->Wh, (size_t)S->Cp * NP * sizeof(uint16_t));
+      al((void **)&S->Wl, (size_t)S->Cp * NP * sizeof(uint16_t));
+    } else {
+      al((void **)&S->Wc, (size_t)S->Cp * NP * sizeof(float));
+    }
+    al((void **)&S->gp, MB * k * sizeof(float));
+    al((void **)&S->Gup, U * k * sizeof(float));
+    al((void **)&S->dPi, I * k * sizeof(float));
+    al((void **)&S->uslot, U * sizeof(int32_t));
+    al((void **)&S->imark, I * sizeof(int32_t));
+    al((void **)&S->ilist, I * sizeof(int32_t));
+    al((void **)&S->nlist, sizeof(int32_t));
+    if (!ok) {
+      bprx_acf_free(h);
+      BPRX_FAIL(h, BPRX_E_NOMEM, "bind_acf: scratch allocation failed (Z: %zu MB)", (I * a->feat_m * NP * 4) >> 20);
+    }
+    hipLaunchKernelGGL(k_acf_fill, dim3(512), dim3(256), 0, nullptr, S->uslot, U, (int32_t)INT_MAX);
+    BPRX_LAUNCH_CHECK(h, "k_acf_fill");
+    if (acf_user_lds(S) > 65536) {
+      bprx_acf_free(h);
+      BPRX_FAIL(h, BPRX_E_INVALID, "bind_acf: M = %d with embed_k = %d needs more LDS than a workgroup has", a->feat_m, (int)k);
+    }
+  }
+  S->a = *a;
+  const int64_t hc = S->hc, ha = S->ha, C = S->C;
+  const int64_t nw[BPRX_ACF_NW] = {(int64_t)k * hc, C * hc, hc, hc, 1, (int64_t)k * ha, (int64_t)k * ha, (int64_t)k * ha, C * ha, ha, ha, 1};
+  for (int q = 0; q < BPRX_ACF_NW; ++q) S->nw[q] = nw[q];
+  S->eval_valid = false;
+  BPRX_HIP(h, hipStreamSynchronize(nullptr));
+  return BPRX_OK;
+}
+
+extern "C" int bprx_acf_profiles(bprx_handle *h, const int32_t *users, int64_t n, const int64_t *hist_ptr, const int32_t *hist_items,
+                                 float *out, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (!h->bound || !h->acf) BPRX_FAIL(h, BPRX_E_STATE, "acf_profiles: the handle is not bound with bprx_bind_acf");
+  if (n < 0 || n > ((int64_t)1 << 31) - 1) BPRX_FAIL(h, BPRX_E_INVALID, "acf_profiles: n = %lld out of range", (long long)n);
+  if (n == 0) return BPRX_OK;
+  if (!users || !hist_ptr || !hist_items || !out) BPRX_FAIL(h, BPRX_E_INVALID, "acf_profiles: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = acf_prepare(h, users, n, nullptr, hist_ptr, hist_items, s))) return rc;
+  return acf_users(h, users, n, nullptr, hist_ptr, hist_items, out, s);
+}

@@ -292,6 +292,7 @@ extern "C" int bprx_destroy(bprx_handle *h) {
   (void)hipSetDevice(h->cfg.device);
   if (h->side) (void)hipStreamSynchronize(h->side);
   free_scratch(h);
+  bprx_acf_free(h);
   graph_drop(h);
   if (h->side) (void)hipStreamDestroy(h->side);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -349,7 +350,13 @@ static int bind_tables(bprx_handle *h, const bprx_tables *t, bool factored) {
   return bprx_launch_adam_reset(h, h->adam_t, 0);   // every bound row counts as current at optimizer.iterations
 }
 
-extern "C" int bprx_bind_tables(bprx_handle *h, const bprx_tables *t) { return bind_tables(h, t, false); }
+extern "C" int bprx_bind_tables(bprx_handle *h, const bprx_tables *t) {
+  if (h && h->acf) bprx_acf_free(h);                        // a plain bind makes the handle a BPRMF / VBPR handle again
+  return bind_tables(h, t, false);
+}
+
+// bprx_bind_acf (bprx_acf.hip) binds the BPRMF tables through here
+int bprx_bind_tables_internal(bprx_handle *h, const bprx_tables *t) { return bind_tables(h, t, false); }
 
 extern "C" int bprx_bind_factored(bprx_handle *h, const bprx_tables *t, const bprx_factored *f) {
   if (!h || !t || !f) return BPRX_E_INVALID;
@@ -400,6 +407,7 @@ extern "C" int bprx_explain_pairs(bprx_handle *h, const int32_t *user, const int
 extern "C" int bprx_tables_dirty(bprx_handle *h, void *stream) {
   if (!h) return BPRX_E_INVALID;
   h->et_valid = h->p_valid = h->absmax_valid = false;
+  if (h->acf) bprx_acf_invalidate(h);                      // ACF: the evaluation profiles follow the tables
   if (h->bound && h->factored) {                           // the factors were written: E_eff / Bp_eff follow them
     const int rc = bprx_launch_fact_compose(h, (hipStream_t)stream);
     if (rc) return rc;
@@ -444,6 +452,7 @@ extern "C" int bprx_score_pairs(bprx_handle *h, const int32_t *user, const int32
   if (B == 0) return BPRX_OK;
   if (!user || !item || !x) BPRX_FAIL(h, BPRX_E_INVALID, "score_pairs: null pointer");
   hipStream_t s = (hipStream_t)stream;
+  if (h->acf) return bprx_acf_score_pairs(h, user, item, B, x, s);
   if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: the rows must be current
   if (h->cfg.model == BPRX_MODEL_VBPR) {
     if (h->p_valid) return bprx_launch_score(h, user, item, B, nullptr, 0, x, s);      // every item's projection is at hand
@@ -461,6 +470,7 @@ extern "C" int bprx_step_begin_sparse(bprx_handle *h, const int32_t *user, const
   int rc = check_ready(h, B);
   if (rc) return rc;
   if (h->pending_stage) BPRX_FAIL(h, BPRX_E_STATE, "step_begin called twice without step_end");
+  if (h->acf) BPRX_FAIL(h, BPRX_E_STATE, "step_begin: an ACF handle takes whole steps only (bprx_step)");
   hipStream_t s = (hipStream_t)stream;
   const bool vb = h->cfg.model == BPRX_MODEL_VBPR;
   if (B == 0) {
@@ -662,6 +672,10 @@ static int step_plain(bprx_handle *h, const int32_t *user, const int32_t *pos, c
 extern "C" int bprx_step(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B,
                          float *loss_out, void *stream) {
   if (!h) return BPRX_E_INVALID;
+  if (h->acf) {                                              // ACF: its own launch sequence, never captured
+    const int rc = check_ready(h, B);
+    return rc ? rc : bprx_acf_step(h, user, pos, neg, B, loss_out, (hipStream_t)stream);
+  }
   // The sgd step is a fixed sequence of launches whose arguments repeat from call to call (index buffers, loss scalar,
   // stream): captured into a hipGraph and replayed, it is ONE launch per step (see graph_mode in bprx_internal.h for
   // when that pays).  Not for adam (lr_t changes every step), not while per-kernel profiling is on, not on the legacy
@@ -721,6 +735,16 @@ extern "C" int bprx_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *o
   if (u0 == u1) return BPRX_OK;
   hipStream_t s = (hipStream_t)stream;
   if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: predict_all reads every row
+  if (h->acf) {
+    // ACF.py:216-227: Gu' (evaluation histories) once per parameter state, then the BPRMF scoring kernels with Gu' in place of
+    // Gu (Bi is zero: Bi + Gu'.Gi is the reference's Gu' Gi^T exactly)
+    if ((rc = bprx_acf_eval_profiles(h, s))) return rc;
+    float *gu = h->t.Gu;
+    h->t.Gu = bprx_acf_eval_gu(h);
+    rc = h->cfg.embed_k % 2 == 0 ? bprx_launch_score_gemm(h, u0, u1, out, s) : bprx_launch_score_block(h, u0, u1, out, s);
+    h->t.Gu = gu;
+    return rc;
+  }
   if (h->cfg.model == BPRX_MODEL_VBPR && !h->p_valid) {   // P = F.[E|Bp] once per parameter state, not once per user block
     if ((rc = bprx_launch_cast_Et(h, s))) return rc;
     if ((rc = bprx_launch_proj_fwd(h, nullptr, h->cfg.num_items, nullptr, 0, h->P, s))) return rc;

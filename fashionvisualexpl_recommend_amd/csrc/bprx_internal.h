@@ -11,6 +11,8 @@
 
 #define BPRX_DENSE_BLOCKS 2048
 
+struct AcfState;   // bprx_acf.hip
+
 struct bprx_handle {
   bprx_config cfg;
   bprx_tables t;
@@ -117,6 +119,8 @@ struct bprx_handle {
   bool factored;
   bprx_factored fx;
   float *gF;                      // [Dc*ec + De*ee + (ec+ee)*(d+1)] gradient of the factors (Ea | Eb | A | Ap), one step
+  // ACF (bprx_bind_acf, bprx_acf.hip): bound model state and scratch; nullptr unless the handle is bound ACF
+  struct AcfState *acf;
   // replicated-user message exchange (bprx_pack_user_msg / bprx_apply_user_msgs)
   int32_t *msg_cursor;            // [2] next free slot of the message being packed, workgroups done (both zero between calls)
   int32_t *msg_next;              // [nranks*cap] chain links of the occurrences of one user across the ranks' messages
@@ -211,3 +215,23 @@ int bprx_launch_proj_bwd(bprx_handle *h, int64_t B, hipStream_t s);
 int bprx_launch_fact_compose(bprx_handle *h, hipStream_t s);                // E_eff | Bp_eff from the factors
 int bprx_launch_fact_update(bprx_handle *h, float lr_t, hipStream_t s);     // chain rule from dEp, optimizer, loss partials
 int bprx_launch_explain(bprx_handle *h, const int32_t *u, const int32_t *i, int64_t n, float *out, hipStream_t s);
+// ACF (bprx_acf.hip): what bprx_step / bprx_score_pairs / bprx_score_block do on a handle bound with bprx_bind_acf
+int bprx_acf_step(bprx_handle *h, const int32_t *u, const int32_t *i, const int32_t *j, int64_t B, float *loss_out, hipStream_t s);
+int bprx_acf_score_pairs(bprx_handle *h, const int32_t *u, const int32_t *i, int64_t B, float *x, hipStream_t s);
+int bprx_acf_eval_profiles(bprx_handle *h, hipStream_t s);   // g'_u of every user (evaluation histories) into acf_eval_gu()
+float *bprx_acf_eval_gu(bprx_handle *h);
+void bprx_acf_invalidate(bprx_handle *h);                    // bound tables written from outside
+void bprx_acf_free(bprx_handle *h);
+
+// adam_tf23, sparse-variable rule (TF-2.3 Keras Adam is NOT lazy: every row of the table decays and moves every step):
+//   m = m*b1 + g*(1-b1); v = v*b2 + g*g*(1-b2); var -= lr_t*m/(sqrt(v)+eps)     (g == 0 on untouched rows)
+// One element, one step.  The whole-table sweeps (bprx_sparse.hip, bprx_acf.hip) and the lazy catch-up replay share this
+// function, so that a replayed step performs bit for bit the arithmetic the sweep would have performed.
+__device__ __forceinline__ void adam_elem(float &p, float &m, float &v, float g, float b1, float b2, float lr_t, float eps) {
+#pragma clang fp contract(off)   // no fused multiply-adds: the same roundings wherever this is inlined (scalar sweep, float4 replay)
+  const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
+  const float mt = m * b1 + g * omb1;
+  const float vt = v * b2 + (g * g) * omb2;
+  m = mt; v = vt;
+  p = p - lr_t * mt / (sqrtf(vt) + eps);
+}

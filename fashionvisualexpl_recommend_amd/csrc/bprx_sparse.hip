@@ -578,18 +578,7 @@ __global__ __launch_bounds__(256) void k_apply_sgd_list(float *Gu, float *Gi, fl
   }
 }
 
-// adam_tf23, sparse-variable rule (TF-2.3 Keras Adam is NOT lazy: every row of the table decays and moves every step):
-//   m = m*b1 + g*(1-b1); v = v*b2 + g*g*(1-b2); var -= lr_t*m/(sqrt(v)+eps)     (g == 0 on untouched rows)
-// One element, one step.  The whole-table sweep and the lazy catch-up replay share this function, so that a replayed
-// step performs bit for bit the arithmetic the sweep would have performed.
-__device__ __forceinline__ void adam_elem(float &p, float &m, float &v, float g, float b1, float b2, float lr_t, float eps) {
-#pragma clang fp contract(off)   // no fused multiply-adds: the same roundings wherever this is inlined (scalar sweep, float4 replay)
-  const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
-  const float mt = m * b1 + g * omb1;
-  const float vt = v * b2 + (g * g) * omb2;
-  m = mt; v = vt;
-  p = p - lr_t * mt / (sqrtf(vt) + eps);
-}
+// adam_elem (bprx_internal.h): TF-2.3's sparse-variable Adam rule for one element and one step.
 
 __global__ __launch_bounds__(256) void k_adam_sparse(float *__restrict__ p, float *__restrict__ m, float *__restrict__ v,
                                                      float *__restrict__ g, size_t n, float b1, float b2, float lr_t, float eps) {

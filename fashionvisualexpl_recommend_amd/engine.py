@@ -162,6 +162,76 @@ class Engine:
         self.t = t
         return self
 
+    def csr(self, lists):
+        """Python lists of item ids per user -> (int64 indptr [n+1], int32 items) device tensors."""
+        lens = np.fromiter((len(l) for l in lists), dtype=np.int64, count=len(lists))
+        ptr = np.zeros(len(lists) + 1, np.int64)
+        np.cumsum(lens, out=ptr[1:])
+        items = np.fromiter((int(i) for l in lists for i in l), dtype=np.int64, count=int(ptr[-1])).astype(np.int32)
+        return (torch.as_tensor(ptr, device=self.device), torch.as_tensor(items, device=self.device))
+
+    def bind_acf(self, Gu, Gi, Bi, F, Pi, weights, train_lists, eval_lists=None, slots=None):
+        """ACF (bprx_bind_acf) on a BPRMF engine: F [I, M, C] feature maps (fp32, or bf16 with feat_dtype='bf16'), Pi [I, k],
+        weights = the twelve attention tensors as {'component.W_0_u': array, ..., 'item.b_1': array} (_ffi.ACF_WEIGHTS, shapes of
+        include/bprx.h),
+        train_lists / eval_lists = the histories P(u) of steps / score_pairs and of score_block (None: the training lists).
+        Adam slots (m_ / v_ for Gu, Gi, Bi, Pi and every weight, keyed 'm_Pi', 'm_item.W_1', ...) are zeros unless given."""
+        if self.model != "bprmf":
+            raise ValueError("bind_acf needs an Engine(model='bprmf', ...)")
+        if self.feat_dtype not in ("fp32", "bf16"):
+            raise ValueError("ACF features are fp32 or bf16 (got %s)" % self.feat_dtype)
+        def prep(x, shape=None, dtype=torch.float32):
+            x = torch.as_tensor(x).to(device=self.device, dtype=dtype)
+            return (x.reshape(shape) if shape is not None else x).contiguous()
+        Ft = prep(F, None, torch.bfloat16 if self.feat_dtype == "bf16" else torch.float32)
+        if Ft.dim() != 3 or Ft.shape[0] != self.I:
+            raise ValueError("F must be [num_items, M, C], got %s" % (tuple(Ft.shape),))
+        M, Cf = int(Ft.shape[1]), int(Ft.shape[2])
+        t = {"Gu": prep(Gu, (self.U, self.k)), "Gi": prep(Gi, (self.I, self.k)), "Bi": prep(Bi, (self.I,)),
+             "Pi": prep(Pi, (self.I, self.k))}
+        for key in _ffi.ACF_WEIGHTS:
+            t[key] = prep(weights[key])
+        hc, ha = int(t["component.W_0_u"].shape[1]), int(t["item.W_0_u"].shape[1])
+        if self.optimizer == "adam_tf23":
+            for n in ["Gu", "Gi", "Bi", "Pi"] + list(_ffi.ACF_WEIGHTS):
+                for s_ in ("m_", "v_"):
+                    key = s_ + n
+                    given = None if slots is None else slots.get(key)
+                    t[key] = torch.zeros_like(t[n]) if given is None else prep(given, tuple(t[n].shape))
+        self.acf_train = self.csr(train_lists)
+        self.acf_eval = self.csr(eval_lists) if eval_lists is not None else None
+        self.acf_F = Ft
+        tb = _ffi.Tables()
+        for n in _ffi.TABLE_FIELDS:
+            setattr(tb, n, None if t.get(n) is None else t[n].data_ptr())
+        ac = _ffi.Acf(M, Cf, hc, ha, _ffi.FEAT_DTYPE[self.feat_dtype], Ft.data_ptr(), self.acf_train[0].data_ptr(),
+                      self.acf_train[1].data_ptr() if self.acf_train[1].numel() else self.acf_train[0].data_ptr(),
+                      None if self.acf_eval is None else self.acf_eval[0].data_ptr(),
+                      None if self.acf_eval is None else (self.acf_eval[1].data_ptr() if self.acf_eval[1].numel()
+                                                          else self.acf_eval[0].data_ptr()),
+                      t["Pi"].data_ptr(), None if t.get("m_Pi") is None else t["m_Pi"].data_ptr(),
+                      None if t.get("v_Pi") is None else t["v_Pi"].data_ptr())
+        for q, key in enumerate(_ffi.ACF_WEIGHTS):
+            ac.w[q] = t[key].data_ptr()
+            if self.optimizer == "adam_tf23":
+                ac.m_w[q], ac.v_w[q] = t["m_" + key].data_ptr(), t["v_" + key].data_ptr()
+        torch.cuda.current_stream(self.device).synchronize()
+        _ffi.check(self.h, self.lib.bprx_bind_acf(self.h, C.byref(tb), C.byref(ac)))
+        self.acf = True
+        self.t = t
+        return self
+
+    def acf_profiles(self, users, lists=None, csr=None):
+        """calculate_beta_alpha (bprx_acf_profiles): g'_u [n, k] for `users` with the histories `lists` (per user id, or a
+        prebuilt `csr`; default: the bound training histories)."""
+        u = as_index(users, self.device)
+        ptr, items = csr if csr is not None else (self.csr(lists) if lists is not None else self.acf_train)
+        if items.numel() == 0:
+            items = torch.zeros(1, dtype=torch.int32, device=self.device)
+        out = torch.empty((u.numel(), self.k), dtype=torch.float32, device=self.device)
+        _ffi.check(self.h, self.lib.bprx_acf_profiles(self.h, _ptr(u), u.numel(), _ptr(ptr), _ptr(items), _ptr(out), _stream()))
+        return out
+
     def explain_pairs(self, user, item):
         """GradFashion.predict_ui_grads for every pair (bprx_explain_pairs): fp32 device tensor [n, 2] = (colour, edges)."""
         u, i = as_index(user, self.device), as_index(item, self.device)

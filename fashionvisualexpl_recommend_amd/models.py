@@ -393,3 +393,154 @@ class GradFashion(VBPR):
         """GradFashion.py:236-240, 252-258: the reference writes the top-K list to the recs path and then OVERWRITES the same
         path with the explanation rows (get_explanations.py:19-21 reads them from there); only the final content is written."""
         self.evaluator.store_recommendation_grads(path=path)
+
+
+def _glorot_1d(rs, n):
+    """tf.initializers.GlorotUniform of a 1-D shape [n]: fan_in = fan_out = n."""
+    lim = np.sqrt(6.0 / (n + n))
+    return rs.uniform(-lim, lim, size=n).astype(np.float32)
+
+
+def load_acf_features(path, num_items, dtype="fp32", chunk=1024):
+    """The per-item feature maps of ACF.py:140-148: `{path}{i}.npy` of shape (1, H, W, C) for every item, NOT normalised,
+    as one [I, H*W, C] CPU tensor (float32, or bfloat16 converted chunk by chunk: peak host memory stays near one copy of
+    the table).  A missing file or any other shape raises ValueError naming the path and the shape."""
+    first = os.path.join(path, "0.npy")
+    if not os.path.exists(first):
+        raise ValueError("ACF feature map %s is missing" % first)
+    shape = np.load(first, mmap_mode="r").shape
+    if len(shape) != 4 or shape[0] != 1:
+        raise ValueError("ACF feature map %s has shape %s, expected (1, H, W, C)" % (first, shape))
+    M, C = shape[1] * shape[2], shape[3]
+    out = torch.empty((num_items, M, C), dtype=torch.bfloat16 if dtype == "bf16" else torch.float32)
+    buf = np.empty((min(chunk, num_items), M, C), np.float32)
+    for s0 in range(0, num_items, chunk):
+        n = min(chunk, num_items - s0)
+        for q in range(n):
+            f = os.path.join(path, "%d.npy" % (s0 + q))
+            if not os.path.exists(f):
+                raise ValueError("ACF feature map %s is missing" % f)
+            a = np.load(f)
+            if a.shape != shape:
+                raise ValueError("ACF feature map %s has shape %s, expected %s (the shape of 0.npy)" % (f, a.shape, shape))
+            buf[q] = a.reshape(M, C)
+        out[s0:s0 + n] = torch.from_numpy(buf[:n])
+    return out, shape
+
+
+class ACF(BPRMF):
+    """ACF.py:20-270, Attentive Collaborative Filtering: the user profile g'_u = g_u + sum_l alpha_l Pi_l with a component-level
+    attention over each history item's feature map and an item-level attention over the history; x_ui = g'_u . Gi_i.  Trained on
+    the engine's ACF path (include/bprx.h, bprx_bind_acf) with the reference's DETACHED gradient (g'_u is rebuilt as a new leaf,
+    ACF.py:208).  Same surface as the reference: Pi, component_weights, item_weights, layers_component, layers_item, call,
+    predict_all, train_step, train.  `features`: optional [I, M, C] (or [I, H, W, C]) array used instead of the per-item .npy
+    files (not normalised, like the files)."""
+    model_kind = "acf"
+
+    def __init__(self, data, params, init=None, features=None):
+        self.layers_component = [int(x) for x in getattr(params, "layers_component", [64, 1])]
+        self.layers_item = [int(x) for x in getattr(params, "layers_item", [64, 1])]
+        for name, l in (("layers_component", self.layers_component), ("layers_item", self.layers_item)):
+            if len(l) != 2 or l[1] != 1 or l[0] <= 0:
+                raise ValueError("ACF: --%s must be two ints 'h 1' with h > 0 (got %s)" % (name, l))
+        self._features = features
+        super().__init__(data, params, init)
+        self.directory_parameters = f'batch_{params.batch_size}' \
+                                    f'-K_{params.embed_k}' \
+                                    f'-lr_{params.lr}' \
+                                    f'-reg_{params.reg}' \
+                                    f'-comp_{list(self.layers_component)}' \
+                                    f'-item_{list(self.layers_item)}'          # ACF.py:46-51
+
+    def process_cnn_feature_maps(self):
+        dtype = getattr(self.params, "dtype", "fp32")
+        if dtype not in ("fp32", "bf16"):
+            raise ValueError("ACF runs with --dtype fp32 or bf16 (got %s)" % dtype)
+        f = self._features
+        if f is None:
+            path = configs.cnn_features_path_split(self.params.dataset, getattr(self.params, "cnn_model", "vgg19"),
+                                                   getattr(self.params, "output_layer", "fc2"))
+            self.acf_features, self.feature_shape = load_acf_features(path, self.num_items, dtype)
+        else:
+            t = torch.as_tensor(np.asarray(f) if not isinstance(f, torch.Tensor) else f)
+            if t.dim() == 4:
+                self.feature_shape = (1,) + tuple(t.shape[1:])
+                t = t.reshape(t.shape[0], t.shape[1] * t.shape[2], t.shape[3])
+            elif t.dim() == 3:
+                self.feature_shape = (1, int(t.shape[1]), 1, int(t.shape[2]))
+            else:
+                raise ValueError("ACF features must be [I, M, C] or [I, H, W, C], got shape %s" % (tuple(t.shape),))
+            if t.shape[0] != self.num_items:
+                raise ValueError("ACF features have %d rows for %d items" % (t.shape[0], self.num_items))
+            self.acf_features = t.to(torch.bfloat16 if dtype == "bf16" else torch.float32)
+
+    def _init_tables(self, init):
+        t, rs = super()._init_tables(init)                                     # Bi, Gu, Gi (BPRMF.py:48-50)
+        self.process_cnn_feature_maps()
+        C, k, h, a = int(self.acf_features.shape[2]), self.embed_k, self.layers_component[0], self.layers_item[0]
+        v = {"Pi": rs.normal(0.0, 0.01, size=(self.num_items, k)).astype(np.float32)}    # ACF.py:35,54
+        v["component.W_0_u"] = glorot_uniform(rs, k, h)                         # build_attention_weights, ACF.py:62-132
+        v["component.W_0_i"] = glorot_uniform(rs, C, h)
+        v["component.b_0"] = _glorot_1d(rs, h)
+        v["component.W_1"] = glorot_uniform(rs, 1, h)
+        v["component.b_1"] = _glorot_1d(rs, 1)
+        v["item.W_0_u"] = glorot_uniform(rs, k, a)
+        v["item.W_0_iv"] = glorot_uniform(rs, k, a)
+        v["item.W_0_ip"] = glorot_uniform(rs, k, a)
+        v["item.W_0_ix"] = glorot_uniform(rs, C, a)
+        v["item.b_0"] = _glorot_1d(rs, a)
+        v["item.W_1"] = glorot_uniform(rs, 1, a)
+        v["item.b_1"] = _glorot_1d(rs, 1)
+        v.update({n: val for n, val in init.items() if n in v})
+        t.update(v)
+        return t, rs
+
+    def eval_lists(self):
+        """P(u) of predict_all: training_list[u] + validation_list[u] (ACF.py:220); the training lists without validation."""
+        tr, va = self.data.training_list, self.data.validation_list
+        if not va:
+            return [list(l) for l in tr]
+        return [list(l) + list(va[u]) for u, l in enumerate(tr)]
+
+    def _engine_kwargs(self):
+        return dict(model="bprmf", num_users=self.num_users, num_items=self.num_items, embed_k=self.embed_k,
+                    feat_dtype=getattr(self.params, "dtype", "fp32"))
+
+    def _adam_form(self):
+        return "sweep" if self.optimizer_name == "adam_tf23" else None      # an ACF handle always sweeps (include/bprx.h)
+
+    def _build(self, init):
+        t, _ = self._init_tables(init)
+        self.engine = Engine(optimizer=self.optimizer_name, lr=self.learning_rate, reg=self.reg,
+                             max_batch=max(self.batch_size, 4096), adam_form=self._adam_form(), **self._engine_kwargs())
+        self.engine.bind_acf(t["Gu"], t["Gi"], t["Bi"], self.acf_features, t["Pi"], {n: t[n] for n in _ACF_W},
+                             self.data.training_list, self.eval_lists())
+
+    # ---- the reference's attribute surface ---------------------------------------------------------------------------
+    @property
+    def Pi(self):
+        return self.engine.t["Pi"]
+
+    @property
+    def component_weights(self):
+        return {n.split(".", 1)[1]: self.engine.t[n] for n in _ACF_W if n.startswith("component.")}
+
+    @property
+    def item_weights(self):
+        return {n.split(".", 1)[1]: self.engine.t[n] for n in _ACF_W if n.startswith("item.")}
+
+    def calculate_beta_alpha(self, users, lists=None):
+        """g'_u of ACF.py:135-181 for several users at once ([n, k] device tensor; default histories: the training lists)."""
+        return self.engine.acf_profiles(users, lists)
+
+    # ---- ACF.py:183-212 ----------------------------------------------------------------------------------------------------
+    def call(self, inputs, training=None, mask=None):
+        user, item = inputs
+        u, i = as_index(user, self.engine.device).long(), as_index(item, self.engine.device).long()
+        xui = self.engine.score_pairs(u, i)
+        return xui, self.Gu[u], self.Gi[i], self.Pi[i]
+
+    __call__ = call
+
+
+from ._ffi import ACF_WEIGHTS as _ACF_W     # noqa: E402

@@ -1,8 +1,9 @@
-"""CLI mirror of the reference's src/train_rec.py:17-93 for the in-scope models (BPRMF, VBPR, GradFashion).
+"""CLI mirror of the reference's src/train_rec.py:17-93 for the in-scope models (BPRMF, VBPR, GradFashion, ACF).
 
 Same flag names and defaults for every flag BPRMF/VBPR consume; new flags: --optimizer, --dtype, --init_seed, and GradFashion's
 --embed_color / --embed_edges, which the reference reads (GradFashion.py:28-29) but never defines: they default to 20, the
---embed_d default.
+--embed_d default.  ACF's --layers_component / --layers_item are `type=list` in the reference (only the default [64, 1] is
+reachable there); here they take two ints `h 1`.
 Run as `python -m fashionvisualexpl_recommend_amd.train_rec --rec bprmf --dataset <name> ...`.
 """
 import argparse
@@ -19,7 +20,7 @@ def parse_args(argv=None):
                                                             'no counterpart: this engine is GPU-only)')
     parser.add_argument('--best_metric', type=str, default='ndcg')
     parser.add_argument('--dataset', nargs='?', default='amazon_baby', help='dataset name')
-    parser.add_argument('--rec', nargs='?', default="vbpr", help="bprmf | vbpr | grad_fashion")
+    parser.add_argument('--rec', nargs='?', default="vbpr", help="bprmf | vbpr | grad_fashion | acf")
     parser.add_argument('--batch_size', type=int, default=256, help='batch_size')
     parser.add_argument('--top_k', type=int, default=20, help='top-k of recommendation.')
     parser.add_argument('--epochs', type=int, default=200, help='Number of epochs.')
@@ -37,6 +38,10 @@ def parse_args(argv=None):
     # read by GradFashion.py:28-29, defined nowhere in the reference: the --embed_d default
     parser.add_argument('--embed_color', type=int, default=20, help='grad_fashion: size of the colour embedding (Ec columns)')
     parser.add_argument('--embed_edges', type=int, default=20, help='grad_fashion: size of the edge embedding (Ee columns)')
+    parser.add_argument('--layers_component', nargs='+', type=int, default=[64, 1],
+                        help='acf: component-level attention layers, two ints "h 1" (ACF.py:40)')
+    parser.add_argument('--layers_item', nargs='+', type=int, default=[64, 1],
+                        help='acf: item-level attention layers, two ints "a 1" (ACF.py:41)')
     # not in the reference
     parser.add_argument('--optimizer', default='adam_tf23', choices=['adam_tf23', 'sgd'])
     parser.add_argument('--dtype', default='fp32', choices=['fp32', 'bf16', 'fp8'],
@@ -54,17 +59,26 @@ def parse_args(argv=None):
     parser.add_argument('--dist_backend', default='nccl', choices=['nccl', 'gloo'], help='nccl == RCCL on ROCm')
     parser.add_argument('--data_root', default=None, help="overrides the reference's '../data'")
     parser.add_argument('--results_root', default=None, help="overrides the reference's '../results'")
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    for name in ("layers_component", "layers_item"):
+        v = getattr(args, name)
+        if len(v) != 2 or v[1] != 1 or v[0] <= 0:
+            parser.error("--%s takes two ints 'h 1' with h > 0 (got %s)" % (name, " ".join(str(x) for x in v)))
+    return args
 
 
 def train(argv=None):
     args = parse_args(argv)
     if args.rec == 'grad_fashion' and int(args.world_size) > 1:
         raise NotImplementedError('--rec grad_fashion runs on one GPU (no multi-GPU form): use --world_size 1')
+    if args.rec == 'acf' and int(args.world_size) > 1:
+        raise NotImplementedError('--rec acf runs on one GPU (no multi-GPU form): use --world_size 1')
+    if args.rec == 'acf' and args.dtype not in ('fp32', 'bf16'):
+        raise ValueError('--rec acf runs with --dtype fp32 or bf16 (got %s)' % args.dtype)
     configs.set_roots(args.data_root, args.results_root)
     import torch
     from .dataset import DataLoader
-    from .models import BPRMF, VBPR, GradFashion
+    from .models import ACF, BPRMF, VBPR, GradFashion
     os.makedirs(os.path.join(configs.results_dir(), args.dataset, args.rec), exist_ok=True)     # train_rec.py:52-55
     os.makedirs(os.path.join(configs.weight_dir(), args.dataset, args.rec), exist_ok=True)
     world = int(args.world_size)
@@ -102,6 +116,8 @@ def train(argv=None):
             model = VBPR(data, args)
         elif args.rec == 'grad_fashion':
             model = GradFashion(data, args)
+        elif args.rec == 'acf':
+            model = ACF(data, args)
         else:
             raise NotImplementedError('Not implemented or unknown Recommender Model.')        # train_rec.py:86
         out.append(model.train())

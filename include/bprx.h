@@ -166,6 +166,50 @@ BPRX_API int bprx_bind_factored(bprx_handle *h, const bprx_tables *t, const bprx
    user / item: device int32 [n]; any n >= 0 (not bounded by max_batch). */
 BPRX_API int bprx_explain_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t n, float *out, void *stream);
 
+/* ---- ACF (ACF.py:20-270) on a BPRMF handle ------------------------------------------------------------------------------
+   Attentive Collaborative Filtering over per-item feature maps f_l [M, C] (M = H*W spatial components).  For user u with
+   history P(u) (ACF.py:135-181):
+       s_lm = W1c.relu(Wcu^T g_u + Wci^T f_lm + bc0) + bc1        beta_l = softmax_m(s_l)        x_l = sum_m beta_lm f_lm
+       t_l  = W1i.relu(Wiu^T g_u + Wiv^T Gi_l + Wip^T Pi_l + Wix^T x_l + bi0) + bi1               alpha = softmax_l(t)
+       g'_u = g_u + sum_l alpha_l Pi_l        (g'_u = g_u for an empty history)        x_ui = g'_u . Gi_i   (no bias)
+   The library never forms x_l: Z_l = f_l [Wci | Wix] ([M, h+a], one MFMA GEMM per distinct item) gives both the component
+   term and sum_m beta_lm Z_lm[h:] = Wix^T x_l.  bprx_bind_acf binds a BPRMF handle (t: Gu, Gi, Bi and their slots; Bi stays
+   zero and is neither read nor trained); afterwards
+     bprx_step         the reference's step with its DETACHED gradient (g'_u is rebuilt as a new leaf, ACF.py:208): Gi gets
+                       -+sigmoid(-d) g'_u + 2 reg Gi, Gu only 2 reg g_u, Pi only 2 reg Pi on the pos / neg rows, every attention
+                       tensor only 2 reg w; loss = sum softplus(-clip(d)) + reg (|g_u|^2 + |Gi_i|^2 + |Gi_j|^2 + |Pi_i|^2 +
+                       |Pi_j|^2 per triplet + sum |w|^2).  sgd, or adam_tf23 (sparse rule on Gu / Gi / Pi, dense rule on the
+                       weights) by whole-table sweeps: an ACF handle never runs the lazy form.
+     bprx_score_pairs  scores with the training histories (train_ptr / train_items)
+     bprx_score_block  scores with the evaluation histories (eval_ptr / eval_items: training + validation, ACF.py:220), so
+                       eval_* and topk work unchanged.
+   bprx_step_begin / _end and the multi-GPU entry points are rejected (BPRX_E_STATE); hipGraph capture falls back to plain
+   launches.  History and batch indices out of range are clamped and reported by bprx_sync_check (BPRX_E_RANGE).
+   Limits: M <= 2048, C % 4 == 0 (fp32) or C % 8 == 0 (bf16), h + a <= 256, embed_k <= 512. */
+enum {
+  BPRX_ACF_C_WU = 0, BPRX_ACF_C_WI = 1, BPRX_ACF_C_B0 = 2, BPRX_ACF_C_W1 = 3, BPRX_ACF_C_B1 = 4,      /* component_weights */
+  BPRX_ACF_I_WU = 5, BPRX_ACF_I_WV = 6, BPRX_ACF_I_WP = 7, BPRX_ACF_I_WX = 8, BPRX_ACF_I_B0 = 9,      /* item_weights */
+  BPRX_ACF_I_W1 = 10, BPRX_ACF_I_B1 = 11, BPRX_ACF_NW = 12
+};
+typedef struct {
+  int32_t feat_m, feat_c;           /* M = H*W, C: the feature maps (ACF.py:140-148) */
+  int32_t width_c, width_i;         /* h = layers_component[0], a = layers_item[0] */
+  int32_t feat_dtype;               /* BPRX_F_FP32 or BPRX_F_BF16 */
+  const void *F;                    /* [I, M, C], frozen; read in place (must stay valid while bound) */
+  const int64_t *train_ptr;         /* CSR [U+1] / items: training_list (steps, score_pairs) */
+  const int32_t *train_items;
+  const int64_t *eval_ptr;          /* CSR [U+1] / items: training + validation lists (score_block); NULL = the training lists */
+  const int32_t *eval_items;
+  float *Pi, *m_Pi, *v_Pi;          /* [I, k] (ACF.py:54) and its adam_tf23 slots */
+  float *w[BPRX_ACF_NW];            /* shapes: [k,h] [C,h] [h] [1,h] [1]  [k,a] [k,a] [k,a] [C,a] [a] [1,a] [1] */
+  float *m_w[BPRX_ACF_NW], *v_w[BPRX_ACF_NW];
+} bprx_acf;
+BPRX_API int bprx_bind_acf(bprx_handle *h, const bprx_tables *t, const bprx_acf *a);
+/* calculate_beta_alpha for n users (duplicates allowed, any n >= 0) with the histories of the given CSR (indexed by user id):
+   out fp32 [n, k] = g'_u. */
+BPRX_API int bprx_acf_profiles(bprx_handle *h, const int32_t *users, int64_t n, const int64_t *hist_ptr,
+                               const int32_t *hist_items, float *out, void *stream);
+
 /* Model.call((user,item)) -> xui        BPRMF.py:55-76 / VBPR.py:59-86.   x: fp32 [B] */
 BPRX_API int bprx_score_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t B, float *x, void *stream);
 
