@@ -1,6 +1,7 @@
 // bprx_api.hip -- host side of the C ABI (include/bprx.h): handle, scratch, step orchestration.
 #include <math.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <new>
 
 #include "bprx_internal.h"
@@ -23,25 +24,10 @@ static hipError_t dalloc_zero(T **p, size_t n) {
   return hipMemset(*p, 0, n * sizeof(T));
 }
 
-static void graph_drop(bprx_handle *h) {
-  for (int q = 0; q < h->graph_n; ++q)
-    if (h->graph_ents[q].exec) (void)hipGraphExecDestroy(h->graph_ents[q].exec);
-  h->graph_n = 0;
-}
-
-static bprx_handle::GraphSig graph_sig(const bprx_handle *h) {
-  return {h->list_slot, h->slist_slot, h->qs_slot, h->seg_slot, h->et_valid, h->p_valid, h->absmax_valid, h->W_dirty,
-          h->idx8_ready((const int32_t *)h->graph_key.i, (const int32_t *)h->graph_key.j, h->graph_key.B)};
-}
-static void graph_sig_apply(bprx_handle *h, const bprx_handle::GraphSig &g) {
-  h->list_slot = g.list_slot; h->slist_slot = g.slist_slot; h->qs_slot = g.qs_slot; h->seg_slot = g.seg_slot;
-  h->et_valid = g.et_valid; h->p_valid = g.p_valid; h->absmax_valid = g.absmax_valid; h->W_dirty = g.W_dirty;
-}
-static bool graph_sig_eq(const bprx_handle::GraphSig &a, const bprx_handle::GraphSig &b) {
-  return a.list_slot == b.list_slot && a.slist_slot == b.slist_slot && a.qs_slot == b.qs_slot && a.seg_slot == b.seg_slot &&
-         a.idx8 == b.idx8 &&
-         a.et_valid == b.et_valid &&
-         a.p_valid == b.p_valid && a.absmax_valid == b.absmax_valid && a.W_dirty == b.W_dirty;
+// The library's environment switches (README "Environment switches"), all read here, once, by bprx_create.
+static int env_int(const char *name, int fallback) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : fallback;
 }
 
 static void free_scratch(bprx_handle *h) {
@@ -78,12 +64,29 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
       CFAIL(BPRX_E_INVALID, "fp8 features need feat_dim %% 256 == 0 (got %d)", cfg->feat_dim);
     if (cfg->feat_dtype == BPRX_F_FP8 && !(cfg->feat_scale > 0.f)) CFAIL(BPRX_E_INVALID, "fp8 features need feat_scale > 0");
   }
+  const bool exported = cfg->flags & (BPRX_FLAG_EXPORT_USER_GRAD | BPRX_FLAG_EXPORT_ITEM_GRAD);
+  // adam_tf23: lazily exact (per-row replay on touch) or by whole-table sweeps -- the same arithmetic either way.  A row's replay
+  // is a serial recurrence over the steps since its last touch: with ~20 positives per user that is 20 U / B steps of ~0.45 us
+  // each, against a sweep that moves every row's (p, m, v) once per step.  Large batches (C2: 30 steps, 14 us, against a 96-us
+  // sweep) want the replay; the reference's own defaults (batch 256: 1 562 steps = 700 us, against a 25-us sweep of its small
+  // tables) want the sweeps: measured on the CLI, 20 000 x 10 000, an epoch of 1 562 steps takes 0.76 s lazily and 0.22 s with
+  // sweeps (BPRMF 0.46 / 0.10).  BPRX_ADAM_LAZY=0 / 1 forces either; exported user gradients (multi-GPU) need the lazy form.
+  bool adam_lazy = false;
+  if (cfg->optimizer == BPRX_OPT_ADAM_TF23) {
+    // (0.45 us per replayed step: k_adam_catchup on C2's tables takes 86 / 235 / 702 us at replay depths 122 / 488 / 1953 =
+    //  batches of 16 384 / 4 096 / 1 024, where the sweeps take 81-88 us: measured crossover between 16 384 and 4 096)
+    const double chain_us = 20.0 * (double)cfg->num_users / (double)cfg->max_batch * 0.45;
+    const double sweep_us =
+        ((double)cfg->num_users * (cfg->embed_k + (vb ? cfg->embed_d : 0)) + (double)cfg->num_items * (cfg->embed_k + 1)) * 24.0 / 4e6;
+    adam_lazy = exported ? true : chain_us < sweep_us;
+    if (cfg->flags & BPRX_FLAG_ADAM_SWEEP) adam_lazy = false;
+    if (cfg->flags & BPRX_FLAG_ADAM_LAZY) adam_lazy = true;
+    adam_lazy = env_int("BPRX_ADAM_LAZY", adam_lazy) != 0;
+  }
   // exported gradients + adam_tf23: the handle takes the Adam steps of the rows it keeps; the exported side's owner applies its
   // rows' steps (bprx_apply_user_msgs, or bprx_adam_rows over its shard).  A rank may see an empty batch and must still move
   // every row it owns: the lazy form only (a sweep per step would have to run on ranks that launch nothing else).
-  if ((cfg->flags & (BPRX_FLAG_EXPORT_USER_GRAD | BPRX_FLAG_EXPORT_ITEM_GRAD)) && cfg->optimizer != BPRX_OPT_SGD &&
-      ((getenv("BPRX_ADAM_LAZY") && atoi(getenv("BPRX_ADAM_LAZY")) == 0) ||
-       (!getenv("BPRX_ADAM_LAZY") && (cfg->flags & BPRX_FLAG_ADAM_SWEEP) && !(cfg->flags & BPRX_FLAG_ADAM_LAZY))))
+  if (exported && cfg->optimizer != BPRX_OPT_SGD && !adam_lazy)
     CFAIL(BPRX_E_INVALID, "BPRX_FLAG_EXPORT_*_GRAD with adam_tf23 needs the lazy form (BPRX_ADAM_LAZY != 0)");
   if ((cfg->flags & BPRX_FLAG_EXPORT_ITEM_GRAD) && cfg->model != BPRX_MODEL_BPRMF)
     CFAIL(BPRX_E_INVALID, "BPRX_FLAG_EXPORT_ITEM_GRAD is for BPRMF (VBPR keeps its items and features local)");
@@ -93,7 +96,14 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
   bprx_handle *h = new (std::nothrow) bprx_handle();
   if (!h) CFAIL(BPRX_E_NOMEM, "out of host memory");
   memset(h, 0, sizeof(*h));
+// the one failure exit once the handle exists: bprx_destroy frees whatever has been made so far
+#define HFAIL(code, ...)         \
+  do {                           \
+    bprx_destroy(h);             \
+    CFAIL(code, __VA_ARGS__);    \
+  } while (0)
   h->cfg = *cfg;
+  h->adam_lazy = adam_lazy;
   h->neg_bias_reg = 0.1f;                                  // VBPR.py:125 (BPRMF.py:111); GradFashion: bprx_bind_factored
   if (!vb) { h->cfg.embed_d = 0; h->cfg.feat_dim = 0; }
   const size_t U = cfg->num_users, I = cfg->num_items, k = cfg->embed_k, d = h->cfg.embed_d, D = h->cfg.feat_dim;
@@ -130,11 +140,9 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
     }
     if (h->SK > 64) h->SK = 64;
     if (h->SK < 1) h->SK = 1;
-    if (h->SK > 256) h->SK = 256;
     // BPRX_FWD_VARIANT=0: the plain forward kernel (the reference the streaming kernels are tested against); anything else:
     // the per-shape policy of bprx_proj.hip (launch_fwd_nt / launch_bwd_nt)
-    h->fwd_variant = 4;
-    if (const char *e = getenv("BPRX_FWD_VARIANT")) h->fwd_variant = atoi(e);
+    h->fwd_variant = env_int("BPRX_FWD_VARIANT", 4);
     A(dalloc_zero(&h->dTu, U * d));
     A(dalloc_zero(&h->P, I * PS));
     A(dalloc_zero(&h->W, I * PS));
@@ -150,12 +158,7 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
       A(dalloc_zero((uint8_t **)&h->Ft, (size_t)((I + 31) / 32 * 32) * D * (cfg->feat_dtype == BPRX_F_FP8 ? 1 : 2)));
   }
 #undef A
-  if (!ok) {
-    snprintf(g_create_err, sizeof(g_create_err), "scratch allocation failed: %s", hipGetErrorString(e));
-    free_scratch(h);
-    delete h;
-    return BPRX_E_NOMEM;
-  }
+  if (!ok) HFAIL(BPRX_E_NOMEM, "scratch allocation failed: %s", hipGetErrorString(e));
   {
     // Item-side gradients through per-item occurrence segments (k_item_seg) instead of global float atomics: the
     // default whenever the row widths fit the 16-B-per-lane layout and the item rows are not staging rows of a sharded
@@ -163,16 +166,14 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
     const bool fits = k % 4 == 0 && d % 4 == 0 && k <= 256 && d <= 256;
     // seg_policy: 0 never, 1 per step (segments when the batch revisits items: 2B >= I; sparse batches keep the atomic
     // staging path with its in-place update of exclusive rows -- C3 shard: 0.104 vs 0.121 ms/step), 2 always
-    h->seg_policy = (fits && !(cfg->flags & BPRX_FLAG_EXPORT_ITEM_GRAD)) ? 1 : 0;
-    if (const char *e = getenv("BPRX_ITEM_MODE")) { const int v = atoi(e); h->seg_policy = h->seg_policy ? (v < 0 ? 0 : (v > 2 ? 2 : v)) : 0; }
+    h->seg_policy = (fits && !(cfg->flags & BPRX_FLAG_EXPORT_ITEM_GRAD)) ? std::min(std::max(env_int("BPRX_ITEM_MODE", 1), 0), 2) : 0;
     h->item_mode = 0;
     if (h->seg_policy) {
       // chunk list: the owners' regions (one slot per item + 4 per owner, <= 1024 owners; a last partial range) + the overflow list
       h->seg_lead_cap = (int64_t)(I + 8192 + 4 * 1024 + 2 * MB / 64 + 64 + 64);
       h->seg_ent_cap = (int64_t)(6 * MB + 64 * 1024 + 2048);
-    // byte planes for the index pass (bprx_sample_*_h): at most 256 owners of 2^shift items; BPRX_IDX8=0: none (A/B)
-    h->idx8_shift = 0;
-    if (!(getenv("BPRX_IDX8") && atoi(getenv("BPRX_IDX8")) == 0))
+      // byte planes for the index pass (bprx_sample_*_h): at most 256 owners of 2^shift items
+      h->idx8_shift = 0;
       for (int sh = 8; sh <= 13 && !h->idx8_shift; ++sh)
         if ((((int64_t)I - 1) >> sh) <= 255) h->idx8_shift = sh;
       bool ok2 = dalloc_zero(&h->seg_rank, (size_t)2 * MB) == hipSuccess && dalloc_zero(&h->seg_cnt, I) == hipSuccess &&
@@ -183,12 +184,7 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
                  dalloc_zero(&h->uold, MB * (k + d)) == hipSuccess &&
                  (!h->idx8_shift ||
                   (dalloc_zero(&h->own8, (size_t)2 * MB) == hipSuccess && dalloc_zero(&h->loc8, (size_t)2 * MB * (h->idx8_shift > 8 ? 2 : 1)) == hipSuccess));
-      if (!ok2) {
-        snprintf(g_create_err, sizeof(g_create_err), "segment scratch allocation failed");
-        free_scratch(h);
-        delete h;
-        return BPRX_E_NOMEM;
-      }
+      if (!ok2) HFAIL(BPRX_E_NOMEM, "segment scratch allocation failed");
     }
   }
   // Touched-item list (sparse batches): when the batch touches few of the items, both projections run over the batch's
@@ -196,94 +192,42 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
   // train_rec.py:23) instead of streaming all of F twice.  Per step: list mode iff 2B < I, i.e. whenever the batch cannot touch every item (measured on C2's tables: B = 16 384 / 24 576:
   // 0.182 / 0.223 ms with the list, 0.231 / 0.239 ms streaming; B = 32 768 = 2B >= I: 0.287 vs 0.240 ms with occurrence segments);
   // BPRX_LIST_MODE = 0 never / 1 per step / 2 always.
-  h->list_policy = vb ? 1 : 0;
-  if (const char *e = getenv("BPRX_LIST_MODE")) { const int v = atoi(e); h->list_policy = vb ? (v < 0 ? 0 : (v > 2 ? 2 : v)) : 0; }
+  h->list_policy = vb ? std::min(std::max(env_int("BPRX_LIST_MODE", 1), 0), 2) : 0;
   if (h->list_policy) {
     const size_t cap = 2 * MB < I ? 2 * MB : I;
-    if (dalloc_zero(&h->ilist, cap) != hipSuccess || dalloc_zero(&h->ilist_n, (size_t)2) != hipSuccess) {
-      snprintf(g_create_err, sizeof(g_create_err), "item list allocation failed");
-      free_scratch(h);
-      delete h;
-      return BPRX_E_NOMEM;
-    }
+    if (dalloc_zero(&h->ilist, cap) != hipSuccess || dalloc_zero(&h->ilist_n, (size_t)2) != hipSuccess)
+      HFAIL(BPRX_E_NOMEM, "item list allocation failed");
   }
   h->SK_step = h->SK;
-  // adam_tf23: lazy-exact form by default (rows are replayed when read; BPRX_ADAM_LAZY=0 = the whole-table sweeps)
-  // adam_tf23: lazily exact (per-row replay on touch) or by whole-table sweeps -- the same arithmetic either way.  A row's replay
-  // is a serial recurrence over the steps since its last touch: with ~20 positives per user that is 20 U / B steps of ~0.45 us
-  // each, against a sweep that moves every row's (p, m, v) once per step.  Large batches (C2: 30 steps, 14 us, against a 96-us
-  // sweep) want the replay; the reference's own defaults (batch 256: 1 562 steps = 700 us, against a 25-us sweep of its small
-  // tables) want the sweeps: measured on the CLI, 20 000 x 10 000, an epoch of 1 562 steps takes 0.76 s lazily and 0.22 s with
-  // sweeps (BPRMF 0.46 / 0.10).  BPRX_ADAM_LAZY=0 / 1 forces either; exported user gradients (multi-GPU) need the lazy form.
-  h->adam_lazy = false;
-  if (cfg->optimizer == BPRX_OPT_ADAM_TF23) {
-    // (0.45 us per replayed step: k_adam_catchup on C2's tables takes 86 / 235 / 702 us at replay depths 122 / 488 / 1953 =
-    //  batches of 16 384 / 4 096 / 1 024, where the sweeps take 81-88 us: measured crossover between 16 384 and 4 096)
-    const double chain_us = 20.0 * (double)cfg->num_users / (double)cfg->max_batch * 0.45;
-    const double sweep_us = ((double)cfg->num_users * (cfg->embed_k + h->cfg.embed_d) + (double)cfg->num_items * (cfg->embed_k + 1)) * 24.0 / 4e6;
-    h->adam_lazy = (cfg->flags & (BPRX_FLAG_EXPORT_USER_GRAD | BPRX_FLAG_EXPORT_ITEM_GRAD)) ? true : chain_us < sweep_us;
-    if (cfg->flags & BPRX_FLAG_ADAM_SWEEP) h->adam_lazy = false;
-    if (cfg->flags & BPRX_FLAG_ADAM_LAZY) h->adam_lazy = true;
-    if (const char *e = getenv("BPRX_ADAM_LAZY")) h->adam_lazy = atoi(e) != 0;
-  }
   if (h->adam_lazy) {
     if (dalloc_zero(&h->lastU, U) != hipSuccess || dalloc_zero(&h->lastI, I) != hipSuccess ||
-        dalloc_zero(&h->lr_hist, (size_t)bprx_adam_hist()) != hipSuccess) {
-      snprintf(g_create_err, sizeof(g_create_err), "adam bookkeeping allocation failed");
-      free_scratch(h);
-      delete h;
-      return BPRX_E_NOMEM;
-    }
+        dalloc_zero(&h->lr_hist, (size_t)bprx_adam_hist()) != hipSuccess)
+      HFAIL(BPRX_E_NOMEM, "adam bookkeeping allocation failed");
   }
   // exclusive-row fast path: sgd only (adam sweeps every row anyway); not with exported user gradients
   h->fast_rows = (cfg->optimizer == BPRX_OPT_SGD && !(cfg->flags & BPRX_FLAG_EXPORT_USER_GRAD)) ? 1 : 0;   // per side: make_args
-  if (h->fast_rows && !(cfg->flags & (BPRX_FLAG_EXPORT_USER_GRAD | BPRX_FLAG_EXPORT_ITEM_GRAD))) {
-    if (dalloc_zero(&h->slist, (size_t)3 * MB) != hipSuccess || dalloc_zero(&h->slist_n, (size_t)2) != hipSuccess) {
-      snprintf(g_create_err, sizeof(g_create_err), "shared-row list allocation failed");
-      free_scratch(h);
-      delete h;
-      return BPRX_E_NOMEM;
-    }
+  if (h->fast_rows && !exported) {
+    if (dalloc_zero(&h->slist, (size_t)3 * MB) != hipSuccess || dalloc_zero(&h->slist_n, (size_t)2) != hipSuccess)
+      HFAIL(BPRX_E_NOMEM, "shared-row list allocation failed");
   }
-  if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess) {
-    snprintf(g_create_err, sizeof(g_create_err), "side stream / event creation failed");
-    free_scratch(h);
-    delete h;
-    return BPRX_E_HIP;
-  }
-  // BPRX_SIDE_STREAM (bit mask).  Measured on C2:
-  //   1  the sparse optimizer pass beside the backward projection: SLOWER (0.385 vs 0.363 ms/step; both are
-  //      bandwidth-bound and interfere: proj_bwd 93 -> 144 us, apply 35 -> 64 us)
-  //   (2, removed: the segment-mode index pass beside the forward projection.  Round 2's pass, 130 K memory-side count atomics:
-  //      0.2599 vs 0.2600 ms, both kernels stretched; round 3's k_index_seg, LDS counting: 0.238 vs 0.229 ms on a plain side
-  //      stream -- its workgroups share every CU's memory pipeline with the projection's streaming loads and take 84 us instead
-  //      of 19 -- and 0.250 / 0.246 vs 0.224 ms on a stream whose CU mask confines it to 16 / 32 CUs: with few owner workgroups
-  //      each of them matches 16x / 8x more of the scanned values and the rare-match path of the scan becomes its bulk)
-  //   4  lazy Adam's catch-up (ALU-bound: correctly rounded sqrt / divide per replayed element and step) beside the
-  //      HBM-bound forward projection of a streaming step: adam_tf23 0.330 -> 0.317 ms/step.  The default with adam_tf23.
-  {
-    const char *e = getenv("BPRX_SIDE_STREAM");
-    h->side_mode = e ? atoi(e) : ((vb && cfg->optimizer == BPRX_OPT_ADAM_TF23 && h->adam_lazy) ? 4 : 0);
-    if (!h->side_mode) { (void)hipStreamDestroy(h->side); h->side = nullptr; }
-  }
+  // Side stream: lazy Adam's catch-up (ALU-bound: correctly rounded sqrt / divide per replayed element and step) runs beside the
+  // HBM-bound forward projection of a streaming step: adam_tf23 0.330 -> 0.317 ms/step on C2.  BPRX_SIDE_STREAM=0: on the
+  // step's own stream.  (Measured and removed, DESIGN §5.1: the sparse optimizer pass beside the backward projection, and the
+  // segment-mode index pass beside the forward projection.)
+  if (vb && cfg->optimizer == BPRX_OPT_ADAM_TF23 && h->adam_lazy && env_int("BPRX_SIDE_STREAM", 1) != 0 &&
+      (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess ||
+       hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
+       hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess))
+    HFAIL(BPRX_E_HIP, "side stream / event creation failed");
   {
     hipDeviceProp_t prop;
     h->num_cu = hipGetDeviceProperties(&prop, cfg->device) == hipSuccess ? prop.multiProcessorCount : 256;
   }
-  // Measured (ROCm 7.0, bench.py on a non-default stream): replaying the step as a hipGraph is SLOWER than the plain
-  // launches it replaces, for large batches (C2, B = 65 536: 0.2828 vs 0.2747 ms/step) and for small ones alike (C2 tables,
-  // B = 256: 0.0576 vs 0.0529; B = 4096: 0.0944 vs 0.0906; BPRMF B = 256: 0.0256 vs 0.0261 ms/step) -- the host is not the
-  // limiter: a small step is six dependent kernels of 5-10 us each (chains of 3-5 memory round trips), and a graph
-  // launch costs more than the dispatch gaps it removes.  Off by default.  BPRX_GRAPH=1: always; 2: steps of B <= 8192.
-  h->graph_mode = 0;
-  if (const char *e = getenv("BPRX_GRAPH")) h->graph_mode = atoi(e);
-  if (h->graph_mode < 0 || h->graph_mode > 2) h->graph_mode = 0;
   h->prof_pending = new std::vector<bprx_handle::ProfRec>();
   h->prof_free = new std::vector<hipEvent_t>();
   *out = h;
   return BPRX_OK;
+#undef HFAIL
 #undef CFAIL
 }
 
@@ -293,7 +237,6 @@ extern "C" int bprx_destroy(bprx_handle *h) {
   if (h->side) (void)hipStreamSynchronize(h->side);
   free_scratch(h);
   bprx_acf_free(h);
-  graph_drop(h);
   if (h->side) (void)hipStreamDestroy(h->side);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
@@ -341,7 +284,6 @@ static int bind_tables(bprx_handle *h, const bprx_tables *t, bool factored) {
   h->factored = factored;
   if (!factored) h->neg_bias_reg = 0.1f;
   h->et_valid = h->p_valid = h->absmax_valid = false;
-  graph_drop(h);                            // a captured step holds the old table pointers
   {
     const int rc = bprx_launch_tile_F(h);   // the projections read a tiled copy of the frozen F (made here, once)
     if (rc) return rc;
@@ -502,7 +444,7 @@ extern "C" int bprx_step_begin_sparse(bprx_handle *h, const int32_t *user, const
   h->idx8_use = h->idx8_ready(pos, neg, B);
   h->idx8_n = 0;
   float lr_t = h->cfg.lr;
-  bool catchup_aside = false;     // BPRX_SIDE_STREAM & 4: the (ALU-bound) lazy-Adam catch-up runs beside the (HBM-bound) projection
+  bool catchup_aside = false;     // the (ALU-bound) lazy-Adam catch-up runs on the side stream beside the (HBM-bound) projection
   if (h->cfg.optimizer == BPRX_OPT_ADAM_TF23) {
     h->adam_t += 1;
     float t = (float)h->adam_t;
@@ -511,7 +453,7 @@ extern "C" int bprx_step_begin_sparse(bprx_handle *h, const int32_t *user, const
       // the ring holds lr_s of the last ADAM_HIST steps: before it would wrap, everything is caught up (amortised: one
       // sweep per ~8000 steps); then the rows of THIS batch are brought to step t-1 for the forward pass
       if (h->adam_t - h->adam_synced >= bprx_adam_hist() - 2 && (rc = bprx_launch_adam_sync(h, h->adam_t - 1, s))) return rc;
-      catchup_aside = vb && !h->proj_fresh && !h->list_mode && !h->p_valid && h->side && (h->side_mode & 4);
+      catchup_aside = h->side && !h->proj_fresh && !h->list_mode && !h->p_valid;
       if (!catchup_aside && (rc = bprx_launch_adam_catchup(h, user, pos, neg, B, lr_t, s))) return rc;
     }
   }
@@ -557,19 +499,8 @@ extern "C" int bprx_step_begin_dense(bprx_handle *h, void *stream) {
   const float lr_t = h->pend_lr;
   int rc;
   if ((rc = bprx_launch_item_seg(h, pos, neg, B, lr_t, s))) return rc;                  // item rows + W, no float atomics
-  // sparse tables are final now: their optimizer pass does not depend on the dense all-reduce, nor on the backward
-  // projection -- with VBPR it runs on the side stream beside it
-  if (vb && h->side && (h->side_mode & 1)) {
-    BPRX_HIP(h, hipEventRecord(h->ev_fork, s));
-    BPRX_HIP(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
-    if ((rc = bprx_launch_apply(h, user, pos, neg, B, lr_t, h->side))) return rc;
-    BPRX_HIP(h, hipEventRecord(h->ev_join, h->side));
-    h->side_pending = true;
-    if ((rc = bprx_launch_proj_bwd(h, B, s))) return rc;                                // dE|dBp = F^T W
-  } else {
-    if (vb && (rc = bprx_launch_proj_bwd(h, B, s))) return rc;
-    if ((rc = bprx_launch_apply(h, user, pos, neg, B, lr_t, s))) return rc;
-  }
+  if (vb && (rc = bprx_launch_proj_bwd(h, B, s))) return rc;                           // dE|dBp = F^T W
+  if ((rc = bprx_launch_apply(h, user, pos, neg, B, lr_t, s))) return rc;
   h->pending_stage = 2;
   return BPRX_OK;
 }
@@ -649,83 +580,25 @@ extern "C" int bprx_step_end(bprx_handle *h, float *loss_out, void *stream) {
   int64_t B = h->pending_B;
   h->pending_B = 0;
   h->pending_stage = 0;
-  if (h->side_pending) {                                  // join the side stream (sparse optimizer pass)
-    BPRX_HIP(h, hipStreamWaitEvent(s, h->ev_join, 0));
-    h->side_pending = false;
-  }
   if (h->factored && (rc = bprx_launch_fact_update(h, lr_t, s))) return rc;   // the factors, then E_eff / Bp_eff
   if (h->cfg.model == BPRX_MODEL_VBPR && (rc = bprx_launch_dense_update(h, lr_t, s))) return rc;
   if (loss_out && (rc = bprx_launch_loss_reduce(h, B, loss_out, s))) return rc;
   return BPRX_OK;
 }
 
-static int step_plain(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B, float *loss_out,
-                      void *stream) {
+extern "C" int bprx_step(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B,
+                         float *loss_out, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (h->acf) {                                              // ACF: its own launch sequence
+    const int rc = check_ready(h, B);
+    return rc ? rc : bprx_acf_step(h, user, pos, neg, B, loss_out, (hipStream_t)stream);
+  }
   h->fused_reduce = !h->factored;  // no all-reduce in between: the dense update sums the split-K slabs itself (GradFashion's
                                    // chain rule reads the summed gradient from dEp)
   int rc = bprx_step_begin(h, user, pos, neg, B, stream);
   if (!rc) rc = bprx_step_end(h, loss_out, stream);
   h->fused_reduce = false;
   return rc;
-}
-
-extern "C" int bprx_step(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B,
-                         float *loss_out, void *stream) {
-  if (!h) return BPRX_E_INVALID;
-  if (h->acf) {                                              // ACF: its own launch sequence, never captured
-    const int rc = check_ready(h, B);
-    return rc ? rc : bprx_acf_step(h, user, pos, neg, B, loss_out, (hipStream_t)stream);
-  }
-  // The sgd step is a fixed sequence of launches whose arguments repeat from call to call (index buffers, loss scalar,
-  // stream): captured into a hipGraph and replayed, it is ONE launch per step (see graph_mode in bprx_internal.h for
-  // when that pays).  Not for adam (lr_t changes every step), not while per-kernel profiling is on, not on the legacy
-  // default stream (cannot be captured): those take the plain path.
-  const bool can_graph = (h->graph_mode == 1 || (h->graph_mode == 2 && B <= 8192)) && h->cfg.optimizer == BPRX_OPT_SGD &&
-                         !h->prof && stream != nullptr && !h->side_mode && h->bound && B > 0 && B <= h->cfg.max_batch && user && pos &&
-                         neg && !h->proj_fresh && !h->pending_stage && !h->factored;
-  if (!can_graph) return step_plain(h, user, pos, neg, B, loss_out, stream);
-  hipStream_t s = (hipStream_t)stream;
-  const bool same = h->graph_key.u == user && h->graph_key.i == pos && h->graph_key.j == neg && h->graph_key.loss == loss_out &&
-                    h->graph_key.B == B && h->graph_key.stream == stream && h->graph_key.lr == h->cfg.lr &&
-                    h->graph_key.reg == h->cfg.reg;
-  if (!same) {
-    // capture only when a call repeats the previous call's arguments (a caller that walks through a pre-generated
-    // stream passes new pointers every step and must not pay for a capture each time)
-    graph_drop(h);
-    h->graph_key.u = user; h->graph_key.i = pos; h->graph_key.j = neg; h->graph_key.loss = loss_out; h->graph_key.B = B;
-    h->graph_key.stream = stream; h->graph_key.lr = h->cfg.lr; h->graph_key.reg = h->cfg.reg;
-    return step_plain(h, user, pos, neg, B, loss_out, stream);
-  }
-  const bprx_handle::GraphSig in = graph_sig(h);
-  for (int q = 0; q < h->graph_n; ++q)
-    if (graph_sig_eq(h->graph_ents[q].in, in)) {
-      BPRX_HIP(h, hipGraphLaunch(h->graph_ents[q].exec, s));
-      h->idx8_n = 0;                                         // (byte planes of this batch, if any: consumed)
-      graph_sig_apply(h, h->graph_ents[q].out);              // what the launches of the captured step left on the host
-      return BPRX_OK;
-    }
-  if (h->graph_n == 4) graph_drop(h);                        // the host state wandered (outside reads between steps): start over
-  if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-    (void)hipGetLastError();
-    h->graph_mode = 0;                                       // this stream cannot be captured: plain launches from now on
-    return step_plain(h, user, pos, neg, B, loss_out, stream);
-  }
-  const int rc = step_plain(h, user, pos, neg, B, loss_out, stream);
-  hipGraph_t g = nullptr;
-  const hipError_t e = hipStreamEndCapture(s, &g);
-  hipGraphExec_t exec = nullptr;
-  const bool ok = !rc && e == hipSuccess && g && hipGraphInstantiate(&exec, g, nullptr, nullptr, 0) == hipSuccess && exec;
-  if (g) (void)hipGraphDestroy(g);
-  if (!ok) {
-    (void)hipGetLastError();
-    h->graph_mode = 0;
-    h->pending_B = 0; h->pending_stage = 0;
-    graph_sig_apply(h, in);                                  // nothing ran: back to the state before the capture
-    return rc ? rc : step_plain(h, user, pos, neg, B, loss_out, stream);
-  }
-  h->graph_ents[h->graph_n++] = {exec, in, graph_sig(h)};
-  BPRX_HIP(h, hipGraphLaunch(exec, s));
-  return BPRX_OK;
 }
 
 extern "C" int bprx_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, void *stream) {

@@ -125,23 +125,10 @@ struct bprx_handle {
   int32_t *msg_cursor;            // [2] next free slot of the message being packed, workgroups done (both zero between calls)
   int32_t *msg_next;              // [nranks*cap] chain links of the occurrences of one user across the ranks' messages
   size_t msg_next_n;
-  // side stream: the sparse optimizer pass (k_apply_sgd / adam sweeps: factor tables only) runs beside the backward
-  // projection (F, W, slabs only); forked after k_triplet_grad, joined in bprx_step_end
+  // side stream (lazy adam_tf23 with VBPR, unless BPRX_SIDE_STREAM=0; else nullptr): the lazy-Adam catch-up runs on it beside
+  // the forward projection; forked and joined by the two events within bprx_step_begin_sparse
   hipStream_t side;
   hipEvent_t ev_fork, ev_join;
-  bool side_pending;
-  int side_mode;                  // BPRX_SIDE_STREAM bit mask: 1 = sparse optimizer pass beside proj_bwd, 4 = lazy-Adam catch-up beside proj_fwd
-  // hipGraph of the whole sgd step (bprx_step): captured on first use, replayed while the call's arguments repeat
-  // hipGraphs of the whole sgd step (bprx_step): captured when a call repeats the previous call's arguments, replayed while
-  // they keep repeating.  A captured launch sequence depends on the host-side state below (cursor slots that alternate from
-  // step to step, validity of the derived images), so an exec is stored with the state it was captured in and the state
-  // it leaves, and is replayed only from the same state; a steady training loop alternates between two execs.
-  int graph_mode;                 // env BPRX_GRAPH: 0 (default) = never, 1 = always, 2 = small steps only (B <= 8192)
-  struct GraphSig { int list_slot, slist_slot, qs_slot, seg_slot; bool et_valid, p_valid, absmax_valid, W_dirty, idx8; };
-  struct GraphEnt { hipGraphExec_t exec; GraphSig in, out; };
-  GraphEnt graph_ents[4];
-  int graph_n;
-  struct { const void *u, *i, *j, *loss; int64_t B; void *stream; float lr, reg; } graph_key;
   // per-kernel HIP-event timing (bprx_profile_*)
   bool prof;
   struct ProfRec { int phase; hipEvent_t a, b; };

@@ -1242,7 +1242,7 @@ void launch_v10(bprx_handle *h, int64_t nrows, float *Pout, hipStream_t s, int n
 //   <= 9 column tiles (d <= 143), bf16 or fp8       k_proj_fwd_bf16_v10                 test_forward_whole_table[v10-*], ..._beyond_the_cache;
 //                                                                                       test_gpu_variants::test_lds_staged_forward...
 //   >= 10 tiles, fp8 (configs[4]: d = 256)          k_proj_fwd_f8s (scaled fp8 MFMA)    test_forward_whole_table[f8s-*]; test_wide_projection...
-//   >= 10 tiles, bf16 (or BPRX_F8S=0)               v10 in right-aligned passes of 9    test_forward_whole_table[passes-*, f8s_off-*]
+//   >= 10 tiles, bf16                               v10 in right-aligned passes of 9    test_forward_whole_table[passes-*]
 //   feat_dim not a multiple of 256 (512 for fp8)    k_proj_fwd_bf16 (plain)             test_forward_whole_table[oddD-*, plain-*]; test_gpu_parity
 //   row list (bprx_score_pairs, list mode)          launch_fwd_rows / f8s over the list test_forward_row_list[split / mt1 / mt2 / mt4 / f8s_rows-*]
 //   fp32 features                                   k_proj_fwd_f32_mfma, k_proj_fwd_f32 test_forward_whole_table[fp32-*], test_forward_row_list[fp32-*]
@@ -1255,14 +1255,11 @@ int launch_fwd_nt(bprx_handle *h, const int32_t *rows, int64_t nrows, float *Pou
   const bool plain = h->fwd_variant == 0 || Deq % 256 != 0 || rows;
   if (!plain) {
     if constexpr (NT >= 10) {
-      // 0: column-range passes (A/B, tests).  Read at every launch, as the row-list branch of bprx_launch_proj_fwd does (a
-      // function-static copy kept the value of the process's first launch of each NT: a later BPRX_F8S=0 was ignored)
-      const bool f8s_on = !(getenv("BPRX_F8S") && atoi(getenv("BPRX_F8S")) == 0);
-      if (f8 && f8s_on && h->EtS && h->cfg.feat_dim % 256 == 0) {
+      if (f8 && h->EtS && h->cfg.feat_dim % 256 == 0) {
         launch_f8s<NT>(h, nullptr, nrows, nullptr, 0, Pout, s, 1);
         return 0;
       }
-      // column ranges of nine tiles, the last one right-aligned: ranges may overlap by some tiles, which are then computed and
+      // bf16: column ranges of nine tiles, the last one right-aligned: ranges may overlap by some tiles, which are then computed and
       // stored twice, identically (F is read once per pass: two passes at d = 256)
       for (int c0 = 0; c0 < NT; c0 += 9) launch_v10<9>(h, nrows, Pout, s, (c0 + 9 <= NT ? c0 : NT - 9) * 16);
       return 0;
@@ -1410,8 +1407,7 @@ int bprx_launch_proj_fwd(bprx_handle *h, const int32_t *rows, int64_t nrows, con
   BprxProfScope ps(h, BPRX_PHASE_PROJ_FWD, s);
   if (h->cfg.feat_dtype != BPRX_F_FP32) {
     const int NT = h->PS / 16;
-    if (rows && NT >= 10 && h->cfg.feat_dtype == BPRX_F_FP8 && h->EtS && h->cfg.feat_dim % 256 == 0 && nrows >= 4096 &&
-        !(getenv("BPRX_F8S") && atoi(getenv("BPRX_F8S")) == 0)) {
+    if (rows && NT >= 10 && h->cfg.feat_dtype == BPRX_F_FP8 && h->EtS && h->cfg.feat_dim % 256 == 0 && nrows >= 4096) {
       // a LARGE row list of a wide fp8 projection (list mode at configs[4] scale: ~123 K distinct items per batch of 65 536):
       // the one-pass streaming kernel gathers the listed rows (k_proj_fwd_rows is built for lists of a few hundred rows)
       switch (NT) {

@@ -151,8 +151,7 @@ BPRX_API int bprx_adam_is_lazy(const bprx_handle *h);
    (GradFashion.py:177-180).  The negative item's bias is regularised with factor neg_bias_reg (1.0 in GradFashion.py:175-176;
    VBPR.py:125 / BPRMF have 0.1, the default of every handle).  Everything else (bprx_step, _begin / _end, score_pairs,
    score_block, eval_*, topk, sync_adam) works unchanged; the caller's F must stay valid while bprx_explain_pairs is used
-   (it reads the caller's F).  Multi-GPU (exported gradients) and hipGraph capture are not supported: graphs fall back to
-   plain launches. */
+   (it reads the caller's F).  Multi-GPU (exported gradients) is not supported. */
 typedef struct {
   int32_t feat_dim_a, feat_dim_b;   /* Dc, De: F = [Fc | Fe | zero padding] (visual_loader_mixin.py:51-54, 60-69); Dc + De <= feat_dim */
   int32_t embed_a, embed_b;         /* --embed_color, --embed_edges (GradFashion.py:28-29); 1..256 each */
@@ -183,8 +182,8 @@ BPRX_API int bprx_explain_pairs(bprx_handle *h, const int32_t *user, const int32
      bprx_score_pairs  scores with the training histories (train_ptr / train_items)
      bprx_score_block  scores with the evaluation histories (eval_ptr / eval_items: training + validation, ACF.py:220), so
                        eval_* and topk work unchanged.
-   bprx_step_begin / _end and the multi-GPU entry points are rejected (BPRX_E_STATE); hipGraph capture falls back to plain
-   launches.  History and batch indices out of range are clamped and reported by bprx_sync_check (BPRX_E_RANGE).
+   bprx_step_begin / _end and the multi-GPU entry points are rejected (BPRX_E_STATE).  History and batch indices out of range
+   are clamped and reported by bprx_sync_check (BPRX_E_RANGE).
    Limits: M <= 2048, C % 4 == 0 (fp32) or C % 8 == 0 (bf16), h + a <= 256, embed_k <= 512. */
 enum {
   BPRX_ACF_C_WU = 0, BPRX_ACF_C_WI = 1, BPRX_ACF_C_B0 = 2, BPRX_ACF_C_W1 = 3, BPRX_ACF_C_B1 = 4,      /* component_weights */

@@ -10,7 +10,6 @@ fwd_table::v10 bf16 D 256 / fp8 D 512, NT 1-9  launch_fwd_nt -> launch_v10<NT> -
 fwd_table::plain (BPRX_FWD_VARIANT=0)          launch_fwd_nt -> k_proj_fwd_bf16<NT, MTD = NT <= 9 ? 2 : 1, F8>
 fwd_table::odd D (bf16 384, fp8 768)           the same plain kernel, chosen by Deq % 256 != 0
 fwd_table::f8s fp8 D 512, NT 10/11/13/16/17    launch_f8s<NT> -> k_proj_fwd_f8s<NT, false>
-fwd_table::f8s_off (BPRX_F8S=0)                launch_v10<9> in right-aligned column-range passes (fp8)
 fwd_table::passes bf16 NT 10 / 17              launch_v10<9> passes: columns 0-8 + 1-9 (overlap 8), 0-8 + 8-16
 test_forward_streaming_loads_beyond_the_cache  300 000 x 1 024 fp8 (> 256 MiB): k_proj_fwd_bf16_v10<4, true, NTL=true>
 fwd_rows::split                                launch_fwd_rows: tiles*NT <= 2N -> k_proj_fwd_rows<1, 1, 16, F8> (K split)
@@ -155,10 +154,8 @@ def _check_scores(got, pu, au, pd, ad, fp32, what):
                                 float(want.flatten()[k])))
 
 
-def _forward_table(monkeypatch, I, D, d, dtype, variant=4, f8s=None, seed=0):
+def _forward_table(monkeypatch, I, D, d, dtype, variant=4, seed=0):
     monkeypatch.setenv("BPRX_FWD_VARIANT", str(variant))
-    if f8s is not None:
-        monkeypatch.setenv("BPRX_F8S", str(f8s))
     tables, P, A = _forward_setup(I, D, d, dtype, seed)
     e = _engine(I, D, d, dtype, d + 1, tables)
     got = e.score_block(0, d + 1)
@@ -173,33 +170,32 @@ def _nt_cases():
     c = []
     for dt, D in (("bf16", 256), ("fp8", 512)):
         for nt in range(1, 10):
-            c.append(pytest.param(dt, D, nt, 40_003, 4, None, id="v10-%s-nt%d-I40003" % (dt, nt)))
+            c.append(pytest.param(dt, D, nt, 40_003, 4, id="v10-%s-nt%d-I40003" % (dt, nt)))
         for nt in (1, 5, 9):
             for I in (7, 3_001):
-                c.append(pytest.param(dt, D, nt, I, 4, None, id="v10-%s-nt%d-I%d" % (dt, nt, I)))
+                c.append(pytest.param(dt, D, nt, I, 4, id="v10-%s-nt%d-I%d" % (dt, nt, I)))
     for nt in (1, 4, 9, 10, 17):
-        c.append(pytest.param("bf16", 256, nt, 3_001, 0, None, id="plain-bf16-nt%d" % nt))
+        c.append(pytest.param("bf16", 256, nt, 3_001, 0, id="plain-bf16-nt%d" % nt))
     for nt in (3, 12):
-        c.append(pytest.param("fp8", 512, nt, 3_001, 0, None, id="plain-fp8-nt%d" % nt))
+        c.append(pytest.param("fp8", 512, nt, 3_001, 0, id="plain-fp8-nt%d" % nt))
     for nt in (2, 9, 17):
-        c.append(pytest.param("bf16", 384, nt, 3_001, 4, None, id="oddD-bf16-D384-nt%d" % nt))
+        c.append(pytest.param("bf16", 384, nt, 3_001, 4, id="oddD-bf16-D384-nt%d" % nt))
     for nt in (4, 10):
-        c.append(pytest.param("fp8", 768, nt, 3_001, 4, None, id="oddD-fp8-D768-nt%d" % nt))
+        c.append(pytest.param("fp8", 768, nt, 3_001, 4, id="oddD-fp8-D768-nt%d" % nt))
     for nt in (10, 11, 13, 16, 17):
-        c.append(pytest.param("fp8", 512, nt, 40_003, 4, 1, id="f8s-nt%d" % nt))
-        c.append(pytest.param("fp8", 512, nt, 40_003, 4, 0, id="f8s_off-nt%d" % nt))
+        c.append(pytest.param("fp8", 512, nt, 40_003, 4, id="f8s-nt%d" % nt))
     for nt in (10, 17):
-        c.append(pytest.param("bf16", 256, nt, 40_003, 4, None, id="passes-bf16-nt%d" % nt))
+        c.append(pytest.param("bf16", 256, nt, 40_003, 4, id="passes-bf16-nt%d" % nt))
     for D in (128, 100):
         for d in (20, 40):
-            c.append(pytest.param("fp32", D, d, 1_001, 4, None, id="fp32-D%d-d%d" % (D, d)))
+            c.append(pytest.param("fp32", D, d, 1_001, 4, id="fp32-D%d-d%d" % (D, d)))
     return c
 
 
-@pytest.mark.parametrize("dtype,D,nt,I,variant,f8s", _nt_cases())
-def test_forward_whole_table(monkeypatch, dtype, D, nt, I, variant, f8s):
+@pytest.mark.parametrize("dtype,D,nt,I,variant", _nt_cases())
+def test_forward_whole_table(monkeypatch, dtype, D, nt, I, variant):
     d = nt if dtype == "fp32" else 16 * nt - 1              # PS = 16 * nt: exactly this instantiation
-    _forward_table(monkeypatch, I, D, d, dtype, variant, f8s, seed=nt + I % 101)
+    _forward_table(monkeypatch, I, D, d, dtype, variant, seed=nt + I % 101)
 
 
 def test_forward_streaming_loads_beyond_the_cache(monkeypatch):
@@ -237,7 +233,6 @@ def test_forward_row_list(monkeypatch, dtype, D, nt, nrows):
         tiles = a * _ncu() // b + k
         nrows = 16 * tiles - (tiles * 7) % 16
     monkeypatch.delenv("BPRX_FWD_VARIANT", raising=False)
-    monkeypatch.delenv("BPRX_F8S", raising=False)
     I = 3_001
     d = nt if dtype == "fp32" else 16 * nt - 1
     tables, P, A = _forward_setup(I, D, d, dtype, seed=nt)

@@ -75,7 +75,7 @@ def test_wide_projection_passes_match_the_plain_kernel(monkeypatch, d, fp8):
     """d > 143 (more than nine column tiles; BASELINE.json configs[4]: d = 256).  bf16: right-aligned, possibly overlapping
     column-range passes of v10<9> -- bit-identical to the plain kernel.  fp8: ONE pass of k_proj_fwd_f8s on the block-scaled
     MFMA (K = 128 per instruction, unit scales): same products, another fp32 summation order inside the instruction ->
-    tolerance; with BPRX_F8S=0 the fp8 table takes the column-range passes too and is bit-exact again."""
+    tolerance."""
     I = 50_000
     t = _state(I, d, fp8, seed=d)
     plain = _scores(monkeypatch, 0, I, d, fp8, t)
