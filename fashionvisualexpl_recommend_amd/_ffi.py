@@ -57,6 +57,17 @@ class Acf(C.Structure):
                 ("v_Pi", C.c_void_p), ("w", C.c_void_p * 12), ("m_w", C.c_void_p * 12), ("v_w", C.c_void_p * 12)]
 
 
+AF_WEIGHTS = ["color.W1", "color.b1", "color.W2", "edges.conv", "edges.conv_b", "edges.W2", "class.W1", "class.b1", "class.W2",
+              "attention.W_1", "attention.b_1", "attention.W_2", "attention.b_2"]    # the order of bprx_attentive.w (BPRX_AF_*)
+
+
+class Attentive(C.Structure):
+    """bprx_attentive: AttentiveFashion's item inputs, encoder and attention tensors (include/bprx.h)."""
+    _fields_ = [("dim_color", C.c_int32), ("dim_class", C.c_int32), ("width", C.c_int32), ("dropout", C.c_float),
+                ("seed", C.c_uint64), ("edges", C.c_void_p), ("color", C.c_void_p), ("cls", C.c_void_p),
+                ("w", C.c_void_p * 13), ("m_w", C.c_void_p * 13), ("v_w", C.c_void_p * 13)]
+
+
 TABLE_FIELDS = ["Gu", "Gi", "Bi", "Tu", "F", "E", "Bp", "m_Gu", "v_Gu", "m_Gi", "v_Gi", "m_Bi", "v_Bi",
                 "m_Tu", "v_Tu", "m_E", "v_E", "m_Bp", "v_Bp"]
 
@@ -92,6 +103,13 @@ def lib():
         "bprx_explain_pairs": (C.c_int, [vp, vp, vp, i64, vp, vp]),
         "bprx_bind_acf": (C.c_int, [vp, C.POINTER(Tables), C.POINTER(Acf)]),
         "bprx_acf_profiles": (C.c_int, [vp, vp, i64, vp, vp, vp, vp]),
+        "bprx_bind_attentive": (C.c_int, [vp, C.POINTER(Tables), C.POINTER(Attentive)]),
+        "bprx_af_encode": (C.c_int, [vp, vp, i64, vp, vp]),
+        "bprx_af_attention_pairs": (C.c_int, [vp, vp, vp, i64, vp, vp, vp]),
+        "bprx_af_score_block": (C.c_int, [vp, C.c_int32, C.c_int32, vp, vp, vp]),
+        "bprx_af_dropout_mask": (C.c_int, [vp, i64, i64, vp, vp]),
+        "bprx_af_get_step": (i64, [vp]),
+        "bprx_af_set_step": (C.c_int, [vp, i64]),
         "bprx_set_hyper": (C.c_int, [vp, f32, f32]),
         "bprx_tables_dirty": (C.c_int, [vp, vp]),
         "bprx_set_adam_step": (C.c_int, [vp, i64, vp]),
@@ -158,7 +176,8 @@ def lib():
     return L
 
 
-EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error", "bprx_bind_tables", "bprx_bind_factored", "bprx_explain_pairs", "bprx_bind_acf", "bprx_acf_profiles", "bprx_set_hyper", "bprx_tables_dirty",
+EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error", "bprx_bind_tables", "bprx_bind_factored", "bprx_explain_pairs", "bprx_bind_acf", "bprx_acf_profiles", "bprx_bind_attentive", "bprx_af_encode", "bprx_af_attention_pairs",
+           "bprx_af_score_block", "bprx_af_dropout_mask", "bprx_af_get_step", "bprx_af_set_step", "bprx_set_hyper", "bprx_tables_dirty",
            "bprx_set_adam_step", "bprx_get_adam_step", "bprx_adam_is_lazy", "bprx_sync_adam", "bprx_score_pairs", "bprx_step", "bprx_step_begin",
            "bprx_step_begin_sparse", "bprx_step_begin_dense", "bprx_sum_dense_parts",
            "bprx_dense_grad", "bprx_step_end", "bprx_step_project", "bprx_user_grad", "bprx_clear_user_grad", "bprx_item_grad", "bprx_clear_item_grad",

@@ -1,5 +1,5 @@
 """On-disk contract of the hot path: the path templates of the reference's
-src/config/configs.py:2-33 (only the entries BPRMF, VBPR, GradFashion and ACF consume).
+src/config/configs.py:2-33 (only the entries BPRMF, VBPR, GradFashion, ACF and AttentiveFashion consume).
 
 The reference's templates are cwd-relative ('../data/{0}/', so its scripts must run
 from src/).  The same relative defaults are kept; `set_roots()` lets a caller point
@@ -53,6 +53,18 @@ def edge_features_path(dataset, cnn_model, output_layer):  # configs.py:20 (Grad
 
 def hist_color_features_path(dataset):       # configs.py:23-24 (GradFashion's colour histograms)
     return data_path(dataset) + "original/" + "features/" + "histograms.npy"
+
+
+def edges_path(dataset):                     # configs.py:29 (AttentiveFashion: one {item}.tiff per item)
+    return data_path(dataset) + "original/" + "features/" + "edges/"
+
+
+def hist_color_features_path_dir(dataset):   # configs.py:25 (AttentiveFashion: one {item}.npy per item)
+    return data_path(dataset) + "original/" + "features/" + "color_histograms/"
+
+
+def class_features_path_dir(dataset):        # configs.py:27 (AttentiveFashion: one {item}.npy per item)
+    return data_path(dataset) + "original/" + "features/" + "one_hot_encodings/"
 
 
 def weight_dir():                            # configs.py:32

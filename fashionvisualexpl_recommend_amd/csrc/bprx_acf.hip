@@ -770,6 +770,7 @@ extern "C" int bprx_bind_acf(bprx_handle *h, const bprx_tables *t, const bprx_ac
   const int NP = 32 * ((a->width_c + a->width_i + 31) / 32);
   if (S && (S->M != a->feat_m || S->C != a->feat_c || S->hc != a->width_c || S->ha != a->width_i || S->fdt != a->feat_dtype))
     bprx_acf_free(h), S = nullptr;
+  if (h->af) bprx_af_free(h);                               // the handle stops being an AttentiveFashion handle
   int rc = bprx_bind_tables_internal(h, t);
   if (rc) return rc;
   // TF-2.3's Adam moves every row every step: an ACF handle takes the whole-table sweeps (bring lazily held rows up to date first)

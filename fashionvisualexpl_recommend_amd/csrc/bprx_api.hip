@@ -237,6 +237,7 @@ extern "C" int bprx_destroy(bprx_handle *h) {
   if (h->side) (void)hipStreamSynchronize(h->side);
   free_scratch(h);
   bprx_acf_free(h);
+  bprx_af_free(h);
   if (h->side) (void)hipStreamDestroy(h->side);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
@@ -294,6 +295,7 @@ static int bind_tables(bprx_handle *h, const bprx_tables *t, bool factored) {
 
 extern "C" int bprx_bind_tables(bprx_handle *h, const bprx_tables *t) {
   if (h && h->acf) bprx_acf_free(h);                        // a plain bind makes the handle a BPRMF / VBPR handle again
+  if (h && h->af) bprx_af_free(h);
   return bind_tables(h, t, false);
 }
 
@@ -350,6 +352,7 @@ extern "C" int bprx_tables_dirty(bprx_handle *h, void *stream) {
   if (!h) return BPRX_E_INVALID;
   h->et_valid = h->p_valid = h->absmax_valid = false;
   if (h->acf) bprx_acf_invalidate(h);                      // ACF: the evaluation profiles follow the tables
+  if (h->af) bprx_af_invalidate(h);                        // AttentiveFashion: so do the item encodings
   if (h->bound && h->factored) {                           // the factors were written: E_eff / Bp_eff follow them
     const int rc = bprx_launch_fact_compose(h, (hipStream_t)stream);
     if (rc) return rc;
@@ -395,6 +398,7 @@ extern "C" int bprx_score_pairs(bprx_handle *h, const int32_t *user, const int32
   if (!user || !item || !x) BPRX_FAIL(h, BPRX_E_INVALID, "score_pairs: null pointer");
   hipStream_t s = (hipStream_t)stream;
   if (h->acf) return bprx_acf_score_pairs(h, user, item, B, x, s);
+  if (h->af) return bprx_af_pairs(h, user, item, B, x, nullptr, s);
   if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: the rows must be current
   if (h->cfg.model == BPRX_MODEL_VBPR) {
     if (h->p_valid) return bprx_launch_score(h, user, item, B, nullptr, 0, x, s);      // every item's projection is at hand
@@ -413,6 +417,7 @@ extern "C" int bprx_step_begin_sparse(bprx_handle *h, const int32_t *user, const
   if (rc) return rc;
   if (h->pending_stage) BPRX_FAIL(h, BPRX_E_STATE, "step_begin called twice without step_end");
   if (h->acf) BPRX_FAIL(h, BPRX_E_STATE, "step_begin: an ACF handle takes whole steps only (bprx_step)");
+  if (h->af) BPRX_FAIL(h, BPRX_E_STATE, "step_begin: an AttentiveFashion handle takes whole steps only (bprx_step)");
   hipStream_t s = (hipStream_t)stream;
   const bool vb = h->cfg.model == BPRX_MODEL_VBPR;
   if (B == 0) {
@@ -593,6 +598,10 @@ extern "C" int bprx_step(bprx_handle *h, const int32_t *user, const int32_t *pos
     const int rc = check_ready(h, B);
     return rc ? rc : bprx_acf_step(h, user, pos, neg, B, loss_out, (hipStream_t)stream);
   }
+  if (h->af) {                                               // AttentiveFashion likewise
+    const int rc = check_ready(h, B);
+    return rc ? rc : bprx_af_step(h, user, pos, neg, B, loss_out, (hipStream_t)stream);
+  }
   h->fused_reduce = !h->factored;  // no all-reduce in between: the dense update sums the split-K slabs itself (GradFashion's
                                    // chain rule reads the summed gradient from dEp)
   int rc = bprx_step_begin(h, user, pos, neg, B, stream);
@@ -608,6 +617,7 @@ extern "C" int bprx_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *o
   if (u0 == u1) return BPRX_OK;
   hipStream_t s = (hipStream_t)stream;
   if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: predict_all reads every row
+  if (h->af) return bprx_af_block(h, u0, u1, out, nullptr, s);
   if (h->acf) {
     // ACF.py:216-227: Gu' (evaluation histories) once per parameter state, then the BPRMF scoring kernels with Gu' in place of
     // Gu (Bi is zero: Bi + Gu'.Gi is the reference's Gu' Gi^T exactly)

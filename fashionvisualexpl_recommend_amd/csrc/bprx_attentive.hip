@@ -1,0 +1,1167 @@
+// bprx_attentive.hip -- AttentiveFashion (AttentiveFashion.py:20-371) on a BPRMF handle: bprx_bind_attentive, bprx_af_*, and what
+// bprx_step / bprx_score_pairs / bprx_score_block do on such a handle (include/bprx.h).
+//
+// Sample rows: a step of B triplets has 2B rows, row r < B = (user r, positive r), row B + r = (user r, negative r).  An item that
+// occurs in several rows is OWNED by its first row (islot[item], k_af_claim); a user by its first triplet (uslot[user]).
+//   k_af_conv<false>  edge encoder forward, one workgroup per owner row: the 228 x 232 zero-padded uint8 image in LDS, im2col
+//                     fragments of 2 x 8 pixel tiles read from it, v_mfma_f32_16x16x32_bf16 with the conv weights split into
+//                     three bf16 terms (pixels 0..255 are exact in bf16, 1/255 is applied to the sum), bias + relu + 2x2 max in
+//                     the accumulator registers (a lane holds the four positions of a window), global mean -> pool [row, 64]
+//   k_af_conv<true>   edge encoder backward: recomputes each tile exactly as the forward, turns the (argmax, > 0) decisions into
+//                     0/1 bf16 B operands and counts  cnt[tap, c] = sum_windows pixel(argmax + tap) * [c active]  with a second
+//                     MFMA -- integer sums below 2^24, exact in any order; dW = cnt * g_c / (12544 * 255), db = #active * g_c / 12544
+//   k_af_gemm         the one small fp32 GEMM of the dense encoders, forward and backward (plain HIP, 64 x 64 tiles)
+//   k_af_triplet      attention forward + backward, one wave per triplet (both sides)
+//   k_af_rowsum       sums the per-row gradients of equal items / users in ascending row order (no float atomics)
+//   k_af_colsum       fixed-order column sums (biases, conv partials)
+//   k_af_update       sgd / dense ApplyAdam on the thirteen encoder and attention tensors
+//   k_af_block        pairwise attention of a user block against every item: f32 MFMA (32x32x2) of the item encodings with the
+//                     user's diag(g_u) W_1 staged in LDS, relu . W_2, 3-way softmax and the score in the epilogue
+#include <climits>
+
+#include "bprx_internal.h"
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+
+#define AF_IMG BPRX_AF_IMG
+#define AF_HID BPRX_AF_HID
+#define AF_CH BPRX_AF_CH
+#define AF_LP 232                 // bytes per padded image row in LDS: 4 left (2 used), 224, 4 right (2 used)
+#define AF_LROWS 228
+#define AF_WIN 12544              // 112 x 112 pooling windows
+#define AF_CPART (26 * AF_CH)     // conv gradient partial of a row: 25 taps x 64 + 64 bias
+#define AF_MAX_H 128
+#define AF_MAX_K 512
+
+struct AfState {
+  bprx_attentive a;
+  int k, h, Dc, Dk;
+  int64_t R;                      // sample rows of scratch: 2 * max_batch
+  int64_t nw[BPRX_AF_NW];
+  int64_t step;                   // dropout step index of the next bprx_step
+  int32_t *islot, *uslot;         // [I], [U] owner row / triplet; INT_MAX between calls
+  int32_t *rowitem, *rowuser;     // [R], [R/2] clamped ids of the rows
+  float *pool, *PD;               // [R, 64] pooled conv output of the owner rows; after gather + dropout
+  float *Hc, *Hk;                 // [R, 256] hidden units after relu and dropout
+  float *C, *dC;                  // [3, R, k] encodings (colour, edges, class) and their gradients
+  float *A6, *Hid, *dHid, *da;    // [3R, k] g_u * c_l; [3R, h] hidden, its gradient; [3R] gradient of a_l
+  float *dGuS, *dGiS;             // [R/2, k], [R, k] per-triplet / per-row gradients
+  float *dH, *dPD, *gsum;         // [R, 256], [R, 64], [R, 64]
+  float *cpart, *cred;            // [R, AF_CPART] conv gradient partials; [64, AF_CPART] column-sum stage
+  float *g[BPRX_AF_NW];           // gradients of the tensors
+  float *Call;                    // [3, I, k] encodings of every item (evaluation)
+  bool eval_valid;
+};
+
+__device__ __forceinline__ int af_clamp(int v, int n, int32_t *errflag, int code) {
+  if ((unsigned)v >= (unsigned)n) {
+    *errflag = code;
+    return v < 0 ? 0 : n - 1;
+  }
+  return v;
+}
+__device__ __forceinline__ float af_wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ void af_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ uint32_t af_bf16_rne(float x) {
+  const uint32_t b = __float_as_uint(x);
+  return (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
+}
+
+// ---- dropout stream ----------------------------------------------------------------------------------------------------
+struct AfDrop { uint32_t k0, k1, step, thr; float scale; int on; };   // thr = rate * 2^32; on == 0: no mask, no scaling
+
+// keep bits of units 4q .. 4q+3 of (encoder enc, sample row): bit j set = unit 4q + j kept
+__device__ __forceinline__ uint32_t af_keep4(const AfDrop &d, int enc, uint32_t row, uint32_t q) {
+  uint32_t o[4];
+  philox4x32_10(q, row, (uint32_t)enc, d.step, d.k0, d.k1, o);
+  return (o[0] >= d.thr ? 1u : 0u) | (o[1] >= d.thr ? 2u : 0u) | (o[2] >= d.thr ? 4u : 0u) | (o[3] >= d.thr ? 8u : 0u);
+}
+
+__global__ __launch_bounds__(256) void k_af_mask(AfDrop d, int64_t n_rows, uint8_t *__restrict__ out) {
+  const int64_t per = (int64_t)(AF_HID + AF_CH + AF_HID) / 4 * n_rows;        // groups of four units
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < per; e += (int64_t)gridDim.x * blockDim.x) {
+    int enc; int64_t rem = e;
+    if (rem < n_rows * (AF_HID / 4)) enc = 0;
+    else if ((rem -= n_rows * (AF_HID / 4)) < n_rows * (AF_CH / 4)) enc = 1;
+    else { rem -= n_rows * (AF_CH / 4); enc = 2; }
+    const int w4 = enc == 1 ? AF_CH / 4 : AF_HID / 4;
+    const uint32_t row = (uint32_t)(rem / w4), q = (uint32_t)(rem % w4);
+    const uint32_t kb = d.on ? af_keep4(d, enc, row, q) : 15u;
+    const int64_t base = (enc == 0 ? 0 : enc == 1 ? n_rows * AF_HID : n_rows * (AF_HID + AF_CH)) + (int64_t)row * (w4 * 4) + q * 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out[base + j] = (uint8_t)((kb >> j) & 1u);
+  }
+}
+
+// ---- rows and owners -----------------------------------------------------------------------------------------------------
+// row r of n: item = r < nsplit ? ia[r] : ib[r - nsplit]; islot (optional): atomicMin claims the item for its first row.
+// users (optional, [nu]): the same for the users' first triplet.
+__global__ __launch_bounds__(256) void k_af_claim(const int32_t *__restrict__ ia, const int32_t *__restrict__ ib, int64_t nsplit,
+                                                  int64_t n, const int32_t *__restrict__ users, int64_t nu, int I, int U,
+                                                  int32_t *__restrict__ rowitem, int32_t *__restrict__ rowuser,
+                                                  int32_t *__restrict__ islot, int32_t *__restrict__ uslot, int32_t *errflag) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < n) {
+    const int it = af_clamp(r < nsplit ? ia[r] : ib[r - nsplit], I, errflag, 2);
+    rowitem[r] = it;
+    if (islot) atomicMin(islot + it, (int32_t)r);
+  }
+  if (users && r < nu) {
+    const int u = af_clamp(users[r], U, errflag, 1);
+    rowuser[r] = u;
+    if (uslot) atomicMin(uslot + u, (int32_t)r);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_af_iota(int32_t *__restrict__ rowitem, int64_t n, int32_t first) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < n) rowitem[r] = first + (int32_t)r;
+}
+
+__global__ __launch_bounds__(256) void k_af_release(const int32_t *__restrict__ rowitem, int64_t n, const int32_t *__restrict__ rowuser,
+                                                    int64_t nu, int32_t *__restrict__ islot, int32_t *__restrict__ uslot) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < n) islot[rowitem[r]] = INT_MAX;
+  if (r < nu) uslot[rowuser[r]] = INT_MAX;
+}
+
+__global__ void k_af_fill(int32_t *p, size_t n, int32_t v) {
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) p[e] = v;
+}
+
+// ---- edge encoder: conv5x5 + bias + relu + maxpool2x2 + global mean, forward and (BWD) weight gradient --------------------
+// K slot 8g + j of the MFMA (g = lane >> 4) is tap (ky, kx) = (g, j) for j < 5; the fifth kernel row rides in the spare slots:
+// slots 5, 6, 7 = taps (4,0) (4,1) (4,2), slots 13, 14 = taps (4,3) (4,4); every other slot is zero.
+__device__ __forceinline__ int af_slot_tap(int g, int j) {
+  if (j < 5) return 5 * g + j;
+  if (g == 0) return 20 + (j - 5);
+  if (g == 1 && j < 7) return 23 + (j - 5);
+  return -1;
+}
+__device__ __forceinline__ uint32_t af_pk(uint32_t p0, uint32_t p1) {        // two pixels -> two bf16 (exact)
+  return (__float_as_uint((float)p0) >> 16) | (__float_as_uint((float)p1) & 0xffff0000u);
+}
+// im2col fragment of MFMA row m = lane & 15 of the tile at window row wy, first window wx0: row m = 4 w + q is position q (row-major
+// in its 2x2 window) of window wx0 + w
+__device__ __forceinline__ bf16x8 af_patch_frag(const uint8_t *__restrict__ img, int wy, int wx0, int lane) {
+  const int m = lane & 15, g = lane >> 4, q = m & 3;
+  const int py = 2 * wy + (q >> 1), px = 2 * (wx0 + (m >> 2)) + (q & 1);
+  const uint8_t *a = img + (py + g) * AF_LP + px + 2;
+  const uint8_t *b = img + (py + 4) * AF_LP + px + 2 + (g == 0 ? 0 : 3);
+  const uint32_t p5 = g < 2 ? b[0] : 0u, p6 = g < 2 ? b[1] : 0u, p7 = g == 0 ? b[2] : 0u;
+  u32x4 v;
+  v[0] = af_pk(a[0], a[1]); v[1] = af_pk(a[2], a[3]); v[2] = af_pk(a[4], p5); v[3] = af_pk(p6, p7);
+  return __builtin_bit_cast(bf16x8, v);
+}
+
+template <bool BWD>
+__global__ __launch_bounds__(256) void k_af_conv(const uint8_t *__restrict__ edges, const float *__restrict__ cw,
+                                                 const float *__restrict__ cb, const int32_t *__restrict__ rowitem,
+                                                 const int32_t *__restrict__ islot, int64_t n, float *__restrict__ pool,
+                                                 const float *__restrict__ gsum, float *__restrict__ cpart) {
+  __shared__ __attribute__((aligned(16))) uint8_t smem[AF_LROWS * AF_LP];     // the image; afterwards the reduction stage
+  const int64_t r = blockIdx.x;
+  if (r >= n) return;
+  const int item = rowitem[r];
+  if (islot && islot[item] != (int32_t)r) return;                             // another row owns this item
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, cl = lane & 15;
+  uint32_t *sm32 = (uint32_t *)smem;
+  for (int e = tid; e < AF_LROWS * AF_LP / 4; e += 256) sm32[e] = 0u;
+  __syncthreads();
+  const uint4 *src = (const uint4 *)(edges + (int64_t)item * (AF_IMG * AF_IMG));
+  for (int e = tid; e < AF_IMG * AF_IMG / 16; e += 256) {
+    const uint4 v = src[e];
+    const int row = e / 14, c16 = e % 14;
+    uint32_t *d = sm32 + ((row + 2) * AF_LP + 4 + c16 * 16) / 4;
+    d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+  }
+  // the conv weights as B operands: channel tile ct, three bf16 terms (hi, mid, lo) of w[tap][16 ct + cl]
+  bf16x8 wf[4][3];
+  float bias[4];
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) {
+    const int c = 16 * ct + cl;
+    bias[ct] = cb[c];
+    uint32_t t3[3][8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int tap = af_slot_tap(g, j);
+      const float x = tap >= 0 ? cw[tap * AF_CH + c] : 0.f;
+      const uint32_t hi = af_bf16_rne(x);
+      const float r1 = x - __uint_as_float(hi << 16);
+      const uint32_t mid = af_bf16_rne(r1);
+      const float r2 = r1 - __uint_as_float(mid << 16);
+      t3[0][j] = hi; t3[1][j] = mid; t3[2][j] = af_bf16_rne(r2);
+    }
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+      u32x4 v;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) v[p] = t3[t][2 * p] | (t3[t][2 * p + 1] << 16);
+      wf[ct][t] = __builtin_bit_cast(bf16x8, v);
+    }
+  }
+  __syncthreads();
+  const float inv255 = 1.0f / 255.0f;
+  float psum[4] = {0.f, 0.f, 0.f, 0.f};        // forward: sum of the pooled relu; backward: number of active windows
+  f32x4 cnt[2][4];
+  if (BWD) {
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+      for (int ct = 0; ct < 4; ++ct) cnt[mt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  // tiles of 4 windows: 28 per window row, 3136 per image; wave w takes the pairs (2p, 2p + 1), p = w, w + 4, ...
+  for (int pr = w; pr < 1568; pr += 4) {
+    uint32_t ind[4][4];                         // backward: [ct][2 T + (q >> 1)] two 0/1 bf16 of tile T
+#pragma unroll
+    for (int T = 0; T < 2; ++T) {
+      const int tile = 2 * pr + T, wy = tile / 28, wx0 = (tile % 28) * 4;
+      const bf16x8 a = af_patch_frag(smem, wy, wx0, lane);
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, wf[ct][2], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, wf[ct][1], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, wf[ct][0], acc, 0, 0, 0);
+        // this lane: channel 16 ct + cl, window wx0 + g, its four positions in row-major order
+        float mx = fmaf(acc[0], inv255, bias[ct]);
+        int am = 0;
+#pragma unroll
+        for (int q = 1; q < 4; ++q) {
+          const float v = fmaf(acc[q], inv255, bias[ct]);
+          if (v > mx) { mx = v; am = q; }       // the first maximum wins a tie
+        }
+        if (!BWD) {
+          psum[ct] += fmaxf(mx, 0.f);
+        } else {
+          const bool act = mx > 0.f;            // relu'(0) = 0
+          psum[ct] += act ? 1.f : 0.f;
+          const uint32_t one = 0x3F80u;
+          ind[ct][2 * T] = act ? (am == 0 ? one : am == 1 ? one << 16 : 0u) : 0u;
+          ind[ct][2 * T + 1] = act ? (am == 2 ? one : am == 3 ? one << 16 : 0u) : 0u;
+        }
+      }
+    }
+    if (BWD) {
+      // cnt[tap, c] += sum over the 32 positions of the pair: K slot 8g + s is position 4g + (s & 3) of tile s >> 2 -- the
+      // positions whose decisions this lane already holds
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt) {
+        const int tap = 16 * mt + cl;
+        const int ky = tap / 5, kx = tap - 5 * ky;
+        u32x4 av = {0u, 0u, 0u, 0u};
+        if (tap < 25) {
+#pragma unroll
+          for (int T = 0; T < 2; ++T) {
+            const int tile = 2 * pr + T, wy = tile / 28, wx0 = (tile % 28) * 4;
+            const uint8_t *p0 = smem + (2 * wy + ky) * AF_LP + 2 * (wx0 + g) + kx + 2;
+            av[2 * T] = af_pk(p0[0], p0[1]);
+            av[2 * T + 1] = af_pk(p0[AF_LP], p0[AF_LP + 1]);
+          }
+        }
+        const bf16x8 a2 = __builtin_bit_cast(bf16x8, av);
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) {
+          u32x4 bv;
+          bv[0] = ind[ct][0]; bv[1] = ind[ct][1]; bv[2] = ind[ct][2]; bv[3] = ind[ct][3];
+          cnt[mt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, __builtin_bit_cast(bf16x8, bv), cnt[mt][ct], 0, 0, 0);
+        }
+      }
+    }
+  }
+  __syncthreads();                               // the image is no longer read: its LDS becomes the reduction stage
+  float *red = (float *)smem;                    // [4 waves][4 g][64] sums, then (backward) [4 waves][32 taps][64] counts
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) red[(w * 4 + g) * AF_CH + 16 * ct + cl] = psum[ct];
+  if (BWD) {
+    float *cs = red + 16 * AF_CH;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+      for (int ct = 0; ct < 4; ++ct)
+        for (int q = 0; q < 4; ++q) cs[(w * 32 + 16 * mt + 4 * g + q) * AF_CH + 16 * ct + cl] = cnt[mt][ct][q];
+  }
+  __syncthreads();
+  if (!BWD) {
+    if (tid < AF_CH) {
+      float s = 0.f;
+      for (int q = 0; q < 16; ++q) s += red[q * AF_CH + tid];
+      pool[r * AF_CH + tid] = s * (1.0f / AF_WIN);
+    }
+  } else {
+    const float *cs = red + 16 * AF_CH;
+    for (int e = tid; e < AF_CPART; e += 256) {
+      const int t = e / AF_CH, c = e % AF_CH;
+      const float gc = gsum[r * AF_CH + c] * (1.0f / AF_WIN);
+      float s = 0.f;
+      if (t < 25) {
+        for (int q = 0; q < 4; ++q) s += cs[(q * 32 + t) * AF_CH + c];
+        cpart[r * AF_CPART + e] = s * (gc * inv255);
+      } else {
+        for (int q = 0; q < 16; ++q) s += red[q * AF_CH + c];
+        cpart[r * AF_CPART + e] = s * gc;
+      }
+    }
+  }
+}
+
+// PD[r] = pool[owner row of r's item] with the edge encoder's dropout (encoder 1)
+__global__ __launch_bounds__(256) void k_af_pooldrop(const float *__restrict__ pool, const int32_t *__restrict__ rowitem,
+                                                     const int32_t *__restrict__ islot, int64_t n, AfDrop d, float *__restrict__ PD) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;            // one thread per four channels
+  if (e >= n * (AF_CH / 4)) return;
+  const int64_t r = e / (AF_CH / 4);
+  const uint32_t q = (uint32_t)(e % (AF_CH / 4));
+  const int64_t srow = islot ? islot[rowitem[r]] : r;
+  const uint32_t kb = d.on ? af_keep4(d, 1, (uint32_t)r, q) : 15u;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float v = pool[srow * AF_CH + q * 4 + j];
+    PD[r * AF_CH + q * 4 + j] = d.on ? ((kb >> j) & 1u ? v * d.scale : 0.f) : v;
+  }
+}
+
+// ---- the small GEMM of the dense encoders ------------------------------------------------------------------------------------
+// C [M, N] = opA [M, K] . opB [K, N];  opA(m, kk) = TA ? A[arow(kk) * lda + m] : A[arow(m) * lda + kk] with arow = rows ? rows[.] : .
+// opB(kk, n) = TB ? B[n * ldb + kk] : B[kk * ldb + n].  Epilogue: 0 none; 1: relu(acc + bias[n]), then dropout (encoder enc, row m);
+// 2: acc * (gate[m, n] > 0 ? gscale : 0)  (backward through dropout and relu: the stored activation is zero where either cut).
+struct AfGemm {
+  const float *A, *B, *bias, *gate;
+  const int32_t *rows;
+  float *C;
+  int M, N, K, lda, ldb, ldc, epi, enc;
+  float gscale;
+  AfDrop d;
+};
+template <bool TA, bool TB>
+__global__ __launch_bounds__(256) void k_af_gemm(AfGemm G) {
+  __shared__ float As[16][68], Bs[16][68];
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+  float acc[4][4] = {};
+  for (int k0 = 0; k0 < G.K; k0 += 16) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int e = tid + 256 * q;
+      {
+        const int mm = TA ? (e & 63) : (e >> 4), kk = TA ? (e >> 6) : (e & 15);
+        float v = 0.f;
+        if (m0 + mm < G.M && k0 + kk < G.K) {
+          const int64_t ri = TA ? (k0 + kk) : (m0 + mm);
+          const int64_t row = G.rows ? G.rows[ri] : ri;
+          v = G.A[row * G.lda + (TA ? (m0 + mm) : (k0 + kk))];
+        }
+        As[kk][mm] = v;
+      }
+      {
+        const int nn = TB ? (e >> 4) : (e & 63), kk = TB ? (e & 15) : (e >> 6);
+        float v = 0.f;
+        if (n0 + nn < G.N && k0 + kk < G.K) v = TB ? G.B[(int64_t)(n0 + nn) * G.ldb + k0 + kk] : G.B[(int64_t)(k0 + kk) * G.ldb + n0 + nn];
+        Bs[kk][nn] = v;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) {
+      float a[4], b[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { a[i] = As[kk][ty * 4 + i]; b[i] = Bs[kk][tx * 4 + i]; }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int m = m0 + ty * 4 + i;
+    if (m >= G.M) continue;
+    uint32_t kb = 15u;
+    if (G.epi == 1 && G.d.on) kb = af_keep4(G.d, G.enc, (uint32_t)m, (uint32_t)((n0 + tx * 4) >> 2));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int n = n0 + tx * 4 + j;
+      if (n >= G.N) continue;
+      float v = acc[i][j];
+      if (G.epi == 1) {
+        v = fmaxf(v + G.bias[n], 0.f);
+        if (G.d.on) v = (kb >> j) & 1u ? v * G.d.scale : 0.f;
+      } else if (G.epi == 2) {
+        v = G.gate[(int64_t)m * G.ldc + n] > 0.f ? v * G.gscale : 0.f;
+      }
+      G.C[(int64_t)m * G.ldc + n] = v;
+    }
+  }
+}
+
+// ---- attention: forward of one (user, item) side --------------------------------------------------------------------------------
+struct AfAtt {
+  const float *Gu, *Gi, *W1, *b1, *W2, *b2;
+  const float *C;                 // [3, ldr, k]
+  int64_t ldr;                    // rows of C per component
+  int k, h;
+};
+// The calling wave has gu[k] and cs[3][k] (this side's encodings) in LDS.  Returns a[3]; hid (optional, global [3, ldh, h] at row)
+__device__ __forceinline__ void af_att_fwd(const AfAtt &A, const float *gu, const float *cs, int lane, float (&a)[3], float *hid,
+                                           int64_t ldh, int64_t row) {
+  const int k = A.k, h = A.h;
+  float part[3] = {0.f, 0.f, 0.f};
+  for (int j = lane; j < h; j += 64) {
+    float s[3] = {0.f, 0.f, 0.f};
+    for (int c = 0; c < k; ++c) {
+      const float w = A.W1[(int64_t)c * h + j], g = gu[c];
+#pragma unroll
+      for (int l = 0; l < 3; ++l) s[l] = fmaf(g * cs[l * k + c], w, s[l]);
+    }
+    const float b = A.b1[j], w2 = A.W2[j];
+#pragma unroll
+    for (int l = 0; l < 3; ++l) {
+      const float hv = fmaxf(s[l] + b, 0.f);
+      if (hid) hid[((int64_t)l * ldh + row) * h + j] = hv;
+      part[l] = fmaf(hv, w2, part[l]);
+    }
+  }
+  const float b2 = A.b2[0];
+#pragma unroll
+  for (int l = 0; l < 3; ++l) a[l] = af_wave_sum(part[l]) + b2;
+}
+__device__ __forceinline__ void af_softmax3(const float (&a)[3], float (&al)[3]) {
+  const float m = fmaxf(a[0], fmaxf(a[1], a[2]));
+  const float e0 = expf(a[0] - m), e1 = expf(a[1] - m), e2 = expf(a[2] - m);
+  const float inv = 1.0f / (e0 + e1 + e2);
+  al[0] = e0 * inv; al[1] = e1 * inv; al[2] = e2 * inv;
+}
+
+// scores (and attentions) of n pairs whose encodings are rows 0..n of A.C: one wave per pair.  LDS: 4 waves x 4k floats
+__global__ __launch_bounds__(256) void k_af_pairs(AfAtt A, const int32_t *__restrict__ rowuser, const int32_t *__restrict__ rowitem,
+                                                  int64_t n, float *__restrict__ x, float *__restrict__ alpha) {
+  extern __shared__ float sm[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, k = A.k;
+  const int64_t r = (int64_t)blockIdx.x * 4 + w;
+  if (r >= n) return;
+  float *gu = sm + (size_t)w * 4 * k, *cs = gu + k;
+  const int u = rowuser[r], it = rowitem[r];
+  for (int c = lane; c < k; c += 64) {
+    gu[c] = A.Gu[(int64_t)u * k + c];
+#pragma unroll
+    for (int l = 0; l < 3; ++l) cs[l * k + c] = A.C[((int64_t)l * A.ldr + r) * k + c];
+  }
+  af_wave_sync();
+  float a[3], al[3];
+  af_att_fwd(A, gu, cs, lane, a, nullptr, 0, 0);
+  af_softmax3(a, al);
+  float s = 0.f;
+  for (int c = lane; c < k; c += 64) {
+    const float wf = al[0] * cs[c] + al[1] * cs[k + c] + al[2] * cs[2 * k + c];
+    s = fmaf(gu[c] * wf, A.Gi[(int64_t)it * k + c], s);
+  }
+  s = af_wave_sum(s);
+  if (lane == 0) {
+    x[r] = s;
+    if (alpha) { alpha[r * 3] = al[0]; alpha[r * 3 + 1] = al[1]; alpha[r * 3 + 2] = al[2]; }
+  }
+}
+
+// ---- attention forward + backward of a step: one wave per triplet -------------------------------------------------------------
+// LDS per wave: gu[k] cs[2][3][k] dh[6][h]
+struct AfTrip {
+  AfAtt A;
+  float *dC, *A6, *Hid, *dHid, *da, *dGuS, *dGiS, *lossb;
+  const int32_t *rowuser, *rowitem;
+  int64_t B;
+  float reg;
+};
+__global__ __launch_bounds__(256) void k_af_triplet(AfTrip T) {
+  extern __shared__ float sm[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const AfAtt &A = T.A;
+  const int k = A.k, h = A.h;
+  const int64_t b = (int64_t)blockIdx.x * 4 + w, B = T.B, R = 2 * B;
+  if (b >= B) return;
+  float *gu = sm + (size_t)w * (7 * k + 6 * h), *cs = gu + k, *dh = cs + 6 * k;
+  const int u = T.rowuser[b];
+  const int it[2] = {T.rowitem[b], T.rowitem[B + b]};
+  for (int c = lane; c < k; c += 64) {
+    gu[c] = A.Gu[(int64_t)u * k + c];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      for (int l = 0; l < 3; ++l) cs[(s * 3 + l) * k + c] = A.C[((int64_t)l * A.ldr + s * B + b) * k + c];
+  }
+  af_wave_sync();
+  float a[2][3], al[2][3], x[2] = {0.f, 0.f}, nrm = 0.f;
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    af_att_fwd(A, gu, cs + s * 3 * k, lane, a[s], T.Hid, R, s * B + b);
+    af_softmax3(a[s], al[s]);
+  }
+  for (int c = lane; c < k; c += 64) {
+    const float g = gu[c];
+    nrm += g * g;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const float *c3 = cs + s * 3 * k;
+      const float gi = A.Gi[(int64_t)it[s] * k + c];
+      const float wf = al[s][0] * c3[c] + al[s][1] * c3[k + c] + al[s][2] * c3[2 * k + c];
+      x[s] = fmaf(g * wf, gi, x[s]);
+      nrm += gi * gi + c3[c] * c3[c] + c3[k + c] * c3[k + c] + c3[2 * k + c] * c3[2 * k + c];
+    }
+  }
+  x[0] = af_wave_sum(x[0]); x[1] = af_wave_sum(x[1]); nrm = af_wave_sum(nrm);
+  const float diff = x[0] - x[1];
+  const bool inr = (diff >= -80.0f) && (diff <= 1e8f);                 // tf.clip_by_value gradient mask
+  const float z = -fminf(fmaxf(diff, -80.0f), 1e8f);
+  const float sp = z > 0.f ? z + log1pf(expf(-z)) : log1pf(expf(z));
+  const float gd = inr ? -1.0f / (1.0f + expf(diff)) : 0.f;           // d loss / d x_pos = -sigmoid(-diff)
+  if (lane == 0) T.lossb[b] = sp + T.reg * nrm;
+  const float dx[2] = {gd, -gd}, r2 = 2.f * T.reg;
+  // d alpha, then d a through the softmax
+  float dav[2][3];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    float dal[3] = {0.f, 0.f, 0.f};
+    for (int c = lane; c < k; c += 64) {
+      const float t = dx[s] * gu[c] * A.Gi[(int64_t)it[s] * k + c];
+#pragma unroll
+      for (int l = 0; l < 3; ++l) dal[l] = fmaf(t, cs[(s * 3 + l) * k + c], dal[l]);
+    }
+#pragma unroll
+    for (int l = 0; l < 3; ++l) dal[l] = af_wave_sum(dal[l]);
+    const float dot = al[s][0] * dal[0] + al[s][1] * dal[1] + al[s][2] * dal[2];
+#pragma unroll
+    for (int l = 0; l < 3; ++l) {
+      dav[s][l] = al[s][l] * (dal[l] - dot);
+      if (lane == 0) T.da[(int64_t)l * R + s * B + b] = dav[s][l];
+    }
+  }
+  for (int j = lane; j < h; j += 64) {
+    const float w2 = A.W2[j];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      for (int l = 0; l < 3; ++l) {
+        const int64_t o = ((int64_t)l * R + s * B + b) * h + j;
+        const float v = T.Hid[o] > 0.f ? dav[s][l] * w2 : 0.f;
+        T.dHid[o] = v;
+        dh[(s * 3 + l) * h + j] = v;
+      }
+  }
+  af_wave_sync();
+  for (int c = lane; c < k; c += 64) {
+    float dp[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const float *wr = A.W1 + (int64_t)c * h;
+    for (int j = 0; j < h; ++j) {
+      const float wv = wr[j];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) dp[q] = fmaf(wv, dh[q * h + j], dp[q]);
+    }
+    const float g = gu[c];
+    float dgu = r2 * g;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const float *c3 = cs + s * 3 * k;
+      const float gi = A.Gi[(int64_t)it[s] * k + c];
+      const float wf = al[s][0] * c3[c] + al[s][1] * c3[k + c] + al[s][2] * c3[2 * k + c];
+      dgu = fmaf(dx[s] * gi, wf, dgu);
+      T.dGiS[(s * B + b) * k + c] = dx[s] * g * wf + r2 * gi;
+#pragma unroll
+      for (int l = 0; l < 3; ++l) {
+        const float cv = c3[l * k + c], d = dp[s * 3 + l];
+        const int64_t row = (int64_t)l * R + s * B + b;
+        T.dC[((int64_t)l * A.ldr + s * B + b) * k + c] = al[s][l] * (dx[s] * g * gi) + g * d + r2 * cv;
+        dgu = fmaf(cv, d, dgu);
+        T.A6[row * k + c] = g * cv;
+      }
+    }
+    T.dGuS[b * k + c] = dgu;
+  }
+}
+
+// dst[key] (by_row: dst[r]) [w] = sum over the rows s (ascending) with ids[s] == ids[r] of src[s], for the owner rows r
+__global__ __launch_bounds__(256) void k_af_rowsum(const int32_t *__restrict__ ids, const int32_t *__restrict__ slot, int64_t n,
+                                                   const float *__restrict__ src, int wdt, float *__restrict__ dst, int by_row) {
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (r >= n) return;
+  const int id = ids[r];
+  if (slot[id] != (int32_t)r) return;
+  float *o = dst + (by_row ? r : (int64_t)id) * wdt;
+  for (int c0 = 0; c0 < wdt; c0 += 64) {
+    const int c = c0 + lane;
+    float s = 0.f;
+    for (int64_t base = r; base < n; base += 64) {             // the owner is the first row: earlier rows cannot match
+      const int64_t q = base + lane;
+      unsigned long long mk = __ballot(q < n && ids[q] == id);
+      while (mk) {
+        const int t = __ffsll((long long)mk) - 1;
+        mk &= mk - 1;
+        if (c < wdt) s += src[(base + t) * wdt + c];
+      }
+    }
+    if (c < wdt) o[c] = s;
+  }
+}
+
+// out[grp][c] = sum of src[r][c] over the rows r of group grp (gsz rows each, ascending); owner rows only when slot is given
+__global__ __launch_bounds__(256) void k_af_colsum(const float *__restrict__ src, int64_t n, int ncols, int64_t gsz,
+                                                   const int32_t *__restrict__ ids, const int32_t *__restrict__ slot,
+                                                   float *__restrict__ out) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t grp = blockIdx.y, r0 = grp * gsz, r1 = r0 + gsz < n ? r0 + gsz : n;
+  if (c >= ncols) return;
+  float s = 0.f;
+  for (int64_t r = r0; r < r1; ++r)
+    if (!slot || slot[ids[r]] == (int32_t)r) s += src[r * ncols + c];
+  out[grp * ncols + c] = s;
+}
+
+// sgd on the owner rows of a table (stage: all-zero between steps)
+__global__ __launch_bounds__(256) void k_af_apply_sgd(float *__restrict__ tab, float *__restrict__ stage, const int32_t *__restrict__ ids,
+                                                      const int32_t *__restrict__ slot, int64_t n, int k, float lr) {
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (r >= n) return;
+  const int id = ids[r];
+  if (slot[id] != (int32_t)r) return;
+  for (int c = lane; c < k; c += 64) {
+    const int64_t o = (int64_t)id * k + c;
+    tab[o] -= lr * stage[o];
+    stage[o] = 0.f;
+  }
+}
+
+// adam_tf23, sparse rule (not lazy): every row of Gu and Gi moves every step
+struct AfSweep { float *p[2], *m[2], *v[2], *g[2]; size_t n[2]; };
+__global__ __launch_bounds__(256) void k_af_sweep(AfSweep S, float b1, float b2, float lr_t, float eps) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x, first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+#pragma unroll
+  for (int q = 0; q < 2; ++q)
+    for (size_t e = first; e < S.n[q]; e += stride) {
+      float pp = S.p[q][e], mm = S.m[q][e], vv = S.v[q][e];
+      adam_elem(pp, mm, vv, S.g[q][e], b1, b2, lr_t, eps);
+      S.p[q][e] = pp; S.m[q][e] = mm; S.v[q][e] = vv;
+      S.g[q][e] = 0.f;
+    }
+}
+
+// the step's loss: per-triplet terms + reg * |attention tensors|^2, one workgroup, fixed order
+struct AfDense { float *w[BPRX_AF_NW], *m[BPRX_AF_NW], *v[BPRX_AF_NW], *g[BPRX_AF_NW]; int64_t n[BPRX_AF_NW]; };
+__global__ __launch_bounds__(1024) void k_af_loss(AfDense T, float reg, const float *__restrict__ lossb, int64_t B,
+                                                  float *__restrict__ loss_out) {
+  __shared__ double red[1024];
+  double sq = 0.0, ls = 0.0;
+  for (int q = BPRX_AF_ATT_W1; q < BPRX_AF_NW; ++q)
+    for (int64_t e = threadIdx.x; e < T.n[q]; e += 1024) sq += (double)T.w[q][e] * (double)T.w[q][e];
+  for (int64_t b = threadIdx.x; b < B; b += 1024) ls += (double)lossb[b];
+  red[threadIdx.x] = ls + (double)reg * sq;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && loss_out) *loss_out = (float)red[0];
+}
+
+// sgd or TF-2.3 dense ApplyAdam (as k_dense_update / k_acf_dense) on every tensor; the attention tensors carry 2 reg w
+__global__ __launch_bounds__(256) void k_af_update(AfDense T, int adam, float lr_t, float reg, float b1, float b2, float eps) {
+  const float omb1 = 1.0f - b1, omb2 = 1.0f - b2, r2 = 2.f * reg;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x, first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (int q = 0; q < BPRX_AF_NW; ++q) {
+    float *p = T.w[q];
+    for (int64_t e = first; e < T.n[q]; e += stride) {
+      const float pv = p[e];
+      const float g = q >= BPRX_AF_ATT_W1 ? T.g[q][e] + r2 * pv : T.g[q][e];
+      if (adam) {
+        const float mo = T.m[q][e], vo = T.v[q][e];
+        const float mt = mo + (g - mo) * omb1;
+        const float vt = vo + (g * g - vo) * omb2;
+        T.m[q][e] = mt; T.v[q][e] = vt;
+        p[e] = pv - lr_t * mt / (sqrtf(vt) + eps);
+      } else {
+        p[e] = pv - lr_t * g;
+      }
+    }
+  }
+}
+
+// ---- pairwise attention of a user block against every item ----------------------------------------------------------------------
+// Workgroup (4 waves): user u0 + blockIdx.y, item tiles blockIdx.x, + gridDim.x, ... of 128 items (32 per wave).
+// LDS: Ws[KP][HP] = g_u[c] W_1[c][j] (zero padded), b1s[HP], w2s[HP], gus[KP].  The MFMA runs transposed,
+// hidden^T [HP, 32 items] = Ws^T . C_l^T, so that a lane holds 16 hidden units per tile of ONE item (column = lane & 31): the
+// relu . W_2 sum stays in the lane, one exchange between the lane halves finishes it.  Lane half hb takes k in [hb KP/2, (hb+1) KP/2).
+template <int NJ>
+__global__ __launch_bounds__(256) void k_af_block(AfAtt A, const float *__restrict__ Call, int I, int u0, int KP,
+                                                  float *__restrict__ out, float *__restrict__ alpha) {
+  constexpr int HP = 32 * NJ;
+  extern __shared__ float sm[];
+  float *Ws = sm, *b1s = Ws + (size_t)KP * HP, *w2s = b1s + HP, *gus = w2s + HP;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, it = lane & 31, hb = lane >> 5;
+  const int k = A.k, h = A.h, KH = KP / 2;
+  const int64_t ub = blockIdx.y, u = u0 + ub;
+  for (int e = tid; e < KP * HP; e += 256) {
+    const int c = e / HP, j = e % HP;
+    Ws[e] = (c < k && j < h) ? A.Gu[u * k + c] * A.W1[(int64_t)c * h + j] : 0.f;
+  }
+  for (int j = tid; j < HP; j += 256) { b1s[j] = j < h ? A.b1[j] : 0.f; w2s[j] = j < h ? A.W2[j] : 0.f; }
+  for (int c = tid; c < KP; c += 256) gus[c] = c < k ? A.Gu[u * k + c] : 0.f;
+  __syncthreads();
+  const float b2 = A.b2[0];
+  const bool vec = (k % 8) == 0;                 // KP == k: float4 rows
+  const int64_t tiles = ((int64_t)I + 127) / 128;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t item = tile * 128 + w * 32 + it;
+    const bool ok = item < I;
+    const int64_t irow = ok ? item : 0;
+    const float *gi = A.Gi + irow * k + hb * KH;
+    float a[3], t[3];
+#pragma unroll
+    for (int l = 0; l < 3; ++l) {
+      const float *cl = Call + ((int64_t)l * I + irow) * k + hb * KH;
+      f32x16 acc[NJ];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+      float tl = 0.f;
+      for (int s4 = 0; s4 < KH; s4 += 4) {
+        float cv[4], gv[4];
+        if (vec) {
+          const float4 c4 = *(const float4 *)(cl + s4), g4 = *(const float4 *)(gi + s4);
+          cv[0] = c4.x; cv[1] = c4.y; cv[2] = c4.z; cv[3] = c4.w;
+          gv[0] = g4.x; gv[1] = g4.y; gv[2] = g4.z; gv[3] = g4.w;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const bool in = hb * KH + s4 + e < k;
+            cv[e] = in ? cl[s4 + e] : 0.f;
+            gv[e] = in ? gi[s4 + e] : 0.f;
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int kk = hb * KH + s4 + e;
+          tl = fmaf(cv[e], gus[kk] * gv[e], tl);
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ws[kk * HP + 32 * j + it], cv[e], acc[j], 0, 0, 0);
+        }
+      }
+      float part = 0.f;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        for (int r = 0; r < 16; ++r) {
+          const int hj = 32 * j + (r & 3) + 8 * (r >> 2) + 4 * hb;
+          part = fmaf(fmaxf(acc[j][r] + b1s[hj], 0.f), w2s[hj], part);
+        }
+      a[l] = part + __shfl_xor(part, 32, 64) + b2;
+      t[l] = tl + __shfl_xor(tl, 32, 64);
+    }
+    float al[3];
+    af_softmax3(a, al);
+    if (ok && hb == 0) {
+      const int64_t o = ub * I + item;
+      out[o] = al[0] * t[0] + al[1] * t[1] + al[2] * t[2];
+      if (alpha) { alpha[o * 3] = al[0]; alpha[o * 3 + 1] = al[1]; alpha[o * 3 + 2] = al[2]; }
+    }
+  }
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------
+static unsigned af_blocks(int64_t work, int64_t per) { return (unsigned)((work + per - 1) / per < 1 ? 1 : (work + per - 1) / per); }
+
+static AfDrop af_drop(const AfState *S, int64_t step, bool training) {
+  AfDrop d;
+  d.k0 = (uint32_t)S->a.seed; d.k1 = (uint32_t)(S->a.seed >> 32); d.step = (uint32_t)step;
+  const double rate = S->a.dropout;
+  d.on = training && rate > 0.0 ? 1 : 0;
+  d.thr = (uint32_t)(rate * 4294967296.0);
+  d.scale = (float)(1.0 / (1.0 - rate));
+  return d;
+}
+
+static int af_gemm(bprx_handle *h, hipStream_t s, bool ta, bool tb, const float *A, int lda, const int32_t *rows, const float *B,
+                   int ldb, float *C, int ldc, int M, int N, int K, int epi = 0, const float *bias = nullptr, int enc = 0,
+                   const AfDrop *d = nullptr, const float *gate = nullptr, float gscale = 1.f) {
+  AfGemm G;
+  G.A = A; G.B = B; G.bias = bias; G.gate = gate; G.rows = rows; G.C = C;
+  G.M = M; G.N = N; G.K = K; G.lda = lda; G.ldb = ldb; G.ldc = ldc; G.epi = epi; G.enc = enc; G.gscale = gscale;
+  if (d) G.d = *d; else memset(&G.d, 0, sizeof(G.d));
+  const dim3 grid((N + 63) / 64, (M + 63) / 64);
+  if (!ta && !tb) hipLaunchKernelGGL((k_af_gemm<false, false>), grid, dim3(256), 0, s, G);
+  else if (ta && !tb) hipLaunchKernelGGL((k_af_gemm<true, false>), grid, dim3(256), 0, s, G);
+  else if (!ta && tb) hipLaunchKernelGGL((k_af_gemm<false, true>), grid, dim3(256), 0, s, G);
+  else BPRX_FAIL(h, BPRX_E_INVALID, "af_gemm: unsupported form");
+  BPRX_LAUNCH_CHECK(h, "k_af_gemm");
+  return BPRX_OK;
+}
+
+// The three encodings of rows 0..n (items S->rowitem[r]) into Cout [3, ldr, k].  dedupe: conv only on the owner rows (islot)
+static int af_encode_rows(bprx_handle *h, int64_t n, bool dedupe, const AfDrop &d, float *Cout, int64_t ldr, hipStream_t s) {
+  AfState *S = h->af;
+  const int k = S->k;
+  const int32_t *islot = dedupe ? S->islot : nullptr;
+  int rc;
+  {
+    BprxProfScope ps(h, BPRX_PHASE_PROJ_FWD, s);
+    hipLaunchKernelGGL(k_af_conv<false>, dim3((unsigned)n), dim3(256), 0, s, S->a.edges, S->a.w[BPRX_AF_EDG_CW], S->a.w[BPRX_AF_EDG_CB],
+                       S->rowitem, islot, n, S->pool, (const float *)nullptr, (float *)nullptr);
+    BPRX_LAUNCH_CHECK(h, "k_af_conv<fwd>");
+  }
+  hipLaunchKernelGGL(k_af_pooldrop, dim3(af_blocks(n * (AF_CH / 4), 256)), dim3(256), 0, s, S->pool, S->rowitem, islot, n, d, S->PD);
+  BPRX_LAUNCH_CHECK(h, "k_af_pooldrop");
+  if ((rc = af_gemm(h, s, false, false, S->a.color, S->Dc, S->rowitem, S->a.w[BPRX_AF_COL_W1], AF_HID, S->Hc, AF_HID, (int)n, AF_HID,
+                    S->Dc, 1, S->a.w[BPRX_AF_COL_B1], 0, &d))) return rc;
+  if ((rc = af_gemm(h, s, false, false, S->Hc, AF_HID, nullptr, S->a.w[BPRX_AF_COL_W2], k, Cout, k, (int)n, k, AF_HID))) return rc;
+  if ((rc = af_gemm(h, s, false, false, S->PD, AF_CH, nullptr, S->a.w[BPRX_AF_EDG_W2], k, Cout + ldr * k, k, (int)n, k, AF_CH))) return rc;
+  if ((rc = af_gemm(h, s, false, false, S->a.cls, S->Dk, S->rowitem, S->a.w[BPRX_AF_CLS_W1], AF_HID, S->Hk, AF_HID, (int)n, AF_HID,
+                    S->Dk, 1, S->a.w[BPRX_AF_CLS_B1], 2, &d))) return rc;
+  return af_gemm(h, s, false, false, S->Hk, AF_HID, nullptr, S->a.w[BPRX_AF_CLS_W2], k, Cout + 2 * ldr * k, k, (int)n, k, AF_HID);
+}
+
+static AfAtt af_att(bprx_handle *h, const float *C, int64_t ldr) {
+  AfState *S = h->af;
+  AfAtt A;
+  A.Gu = h->t.Gu; A.Gi = h->t.Gi; A.W1 = S->a.w[BPRX_AF_ATT_W1]; A.b1 = S->a.w[BPRX_AF_ATT_B1]; A.W2 = S->a.w[BPRX_AF_ATT_W2];
+  A.b2 = S->a.w[BPRX_AF_ATT_B2]; A.C = C; A.ldr = ldr; A.k = S->k; A.h = S->h;
+  return A;
+}
+
+// fixed-order column sums of src [n, ncols] into out [ncols] (two levels of at most 64 groups)
+static int af_colsum(bprx_handle *h, hipStream_t s, const float *src, int64_t n, int ncols, const int32_t *ids, const int32_t *slot,
+                     float *out) {
+  AfState *S = h->af;
+  const int64_t gsz = (n + 63) / 64, ng = (n + gsz - 1) / gsz;
+  hipLaunchKernelGGL(k_af_colsum, dim3((ncols + 255) / 256, (unsigned)ng), dim3(256), 0, s, src, n, ncols, gsz, ids, slot, S->cred);
+  hipLaunchKernelGGL(k_af_colsum, dim3((ncols + 255) / 256, 1), dim3(256), 0, s, (const float *)S->cred, ng, ncols, ng,
+                     (const int32_t *)nullptr, (const int32_t *)nullptr, out);
+  BPRX_LAUNCH_CHECK(h, "k_af_colsum");
+  return BPRX_OK;
+}
+
+static int af_step_body(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B, float *loss_out, hipStream_t s) {
+  AfState *S = h->af;
+  if (B <= 0) BPRX_FAIL(h, BPRX_E_INVALID, "step: empty batch");
+  if (!user || !pos || !neg) BPRX_FAIL(h, BPRX_E_INVALID, "step: null index pointer");
+  const int U = h->cfg.num_users, I = h->cfg.num_items, k = S->k, hh = S->h;
+  const int64_t R = 2 * B;
+  const bool adam = h->cfg.optimizer == BPRX_OPT_ADAM_TF23;
+  float lr_t = h->cfg.lr;
+  if (adam) {
+    h->adam_t += 1;
+    const float t = (float)h->adam_t;
+    lr_t = h->cfg.lr * sqrtf(1.0f - powf(h->cfg.beta2, t)) / (1.0f - powf(h->cfg.beta1, t));
+  }
+  h->pend_lr = lr_t;
+  const AfDrop d = af_drop(S, S->step, true);
+  S->step += 1;
+  int rc;
+  hipLaunchKernelGGL(k_af_claim, dim3(af_blocks(R, 256)), dim3(256), 0, s, pos, neg, B, R, user, B, I, U, S->rowitem, S->rowuser,
+                     S->islot, S->uslot, h->errflag);
+  BPRX_LAUNCH_CHECK(h, "k_af_claim");
+  if ((rc = af_encode_rows(h, R, true, d, S->C, S->R, s))) return rc;
+  {
+    BprxProfScope ps(h, BPRX_PHASE_TRIPLET, s);
+    AfTrip T;
+    T.A = af_att(h, S->C, S->R);
+    T.dC = S->dC; T.A6 = S->A6; T.Hid = S->Hid; T.dHid = S->dHid; T.da = S->da; T.dGuS = S->dGuS; T.dGiS = S->dGiS; T.lossb = h->lossb;
+    T.rowuser = S->rowuser; T.rowitem = S->rowitem; T.B = B; T.reg = h->cfg.reg;
+    hipLaunchKernelGGL(k_af_triplet, dim3(af_blocks(B, 4)), dim3(256), 4 * sizeof(float) * (7 * (size_t)k + 6 * (size_t)hh), s, T);
+    BPRX_LAUNCH_CHECK(h, "k_af_triplet");
+  }
+  AfDense D;
+  for (int q = 0; q < BPRX_AF_NW; ++q) { D.w[q] = S->a.w[q]; D.m[q] = S->a.m_w[q]; D.v[q] = S->a.v_w[q]; D.g[q] = S->g[q]; D.n[q] = S->nw[q]; }
+  hipLaunchKernelGGL(k_af_loss, dim3(1), dim3(1024), 0, s, D, h->cfg.reg, h->lossb, B, loss_out);
+  BPRX_LAUNCH_CHECK(h, "k_af_loss");
+  // attention tensors: dW_1 = A6^T dHid, db_1 = colsum dHid, dW_2 = Hid^T da, db_2 = sum da
+  if ((rc = af_gemm(h, s, true, false, S->A6, k, nullptr, S->dHid, hh, S->g[BPRX_AF_ATT_W1], hh, k, hh, (int)(3 * R)))) return rc;
+  if ((rc = af_colsum(h, s, S->dHid, 3 * R, hh, nullptr, nullptr, S->g[BPRX_AF_ATT_B1]))) return rc;
+  if ((rc = af_gemm(h, s, true, false, S->Hid, hh, nullptr, S->da, 1, S->g[BPRX_AF_ATT_W2], 1, hh, 1, (int)(3 * R)))) return rc;
+  if ((rc = af_colsum(h, s, S->da, 3 * R, 1, nullptr, nullptr, S->g[BPRX_AF_ATT_B2]))) return rc;
+  // dense encoders (colour l = 0, class l = 2): dW2 = H^T dC, dH = (dC W2^T) gated, dW1 = X^T dH, db1 = colsum dH
+  for (int l = 0; l < 3; l += 2) {
+    const int w1 = l == 0 ? BPRX_AF_COL_W1 : BPRX_AF_CLS_W1, D_in = l == 0 ? S->Dc : S->Dk;
+    const float *X = l == 0 ? S->a.color : S->a.cls, *H = l == 0 ? S->Hc : S->Hk, *dC = S->dC + (int64_t)l * S->R * k;
+    if ((rc = af_gemm(h, s, true, false, H, AF_HID, nullptr, dC, k, S->g[w1 + 2], k, AF_HID, k, (int)R))) return rc;
+    if ((rc = af_gemm(h, s, false, true, dC, k, nullptr, S->a.w[w1 + 2], k, S->dH, AF_HID, (int)R, AF_HID, k, 2, nullptr, 0, nullptr, H,
+                      d.on ? d.scale : 1.f))) return rc;
+    if ((rc = af_gemm(h, s, true, false, X, D_in, S->rowitem, S->dH, AF_HID, S->g[w1], AF_HID, D_in, AF_HID, (int)R))) return rc;
+    if ((rc = af_colsum(h, s, S->dH, R, AF_HID, nullptr, nullptr, S->g[w1 + 1]))) return rc;
+  }
+  // edge encoder: dW2 = PD^T dC, dPD = (dC W2^T) gated, summed per item, then the conv weight gradient by recomputation
+  {
+    const float *dC = S->dC + S->R * k;
+    if ((rc = af_gemm(h, s, true, false, S->PD, AF_CH, nullptr, dC, k, S->g[BPRX_AF_EDG_W2], k, AF_CH, k, (int)R))) return rc;
+    if ((rc = af_gemm(h, s, false, true, dC, k, nullptr, S->a.w[BPRX_AF_EDG_W2], k, S->dPD, AF_CH, (int)R, AF_CH, k, 2, nullptr, 0,
+                      nullptr, S->PD, d.on ? d.scale : 1.f))) return rc;
+    hipLaunchKernelGGL(k_af_rowsum, dim3(af_blocks(R, 4)), dim3(256), 0, s, S->rowitem, S->islot, R, S->dPD, AF_CH, S->gsum, 1);
+    BPRX_LAUNCH_CHECK(h, "k_af_rowsum");
+    {
+      BprxProfScope ps(h, BPRX_PHASE_PROJ_BWD, s);
+      hipLaunchKernelGGL(k_af_conv<true>, dim3((unsigned)R), dim3(256), 0, s, S->a.edges, S->a.w[BPRX_AF_EDG_CW], S->a.w[BPRX_AF_EDG_CB],
+                         S->rowitem, S->islot, R, (float *)nullptr, S->gsum, S->cpart);
+      BPRX_LAUNCH_CHECK(h, "k_af_conv<bwd>");
+    }
+    // g[EDG_CW] [25 * 64] and g[EDG_CB] [64] are one allocation of AF_CPART floats
+    if ((rc = af_colsum(h, s, S->cpart, R, AF_CPART, S->rowitem, S->islot, S->g[BPRX_AF_EDG_CW]))) return rc;
+  }
+  // Gu / Gi: per-row gradients summed per distinct row in ascending row order into the staging tables
+  hipLaunchKernelGGL(k_af_rowsum, dim3(af_blocks(R, 4)), dim3(256), 0, s, S->rowitem, S->islot, R, S->dGiS, k, h->dGi, 0);
+  hipLaunchKernelGGL(k_af_rowsum, dim3(af_blocks(B, 4)), dim3(256), 0, s, S->rowuser, S->uslot, B, S->dGuS, k, h->dGu, 0);
+  BPRX_LAUNCH_CHECK(h, "k_af_rowsum");
+  {
+    BprxProfScope ps(h, BPRX_PHASE_DENSE, s);
+    hipLaunchKernelGGL(k_af_update, dim3(256), dim3(256), 0, s, D, adam ? 1 : 0, lr_t, h->cfg.reg, h->cfg.beta1, h->cfg.beta2,
+                       h->cfg.epsilon);
+    BPRX_LAUNCH_CHECK(h, "k_af_update");
+  }
+  {
+    BprxProfScope ps(h, BPRX_PHASE_APPLY, s);
+    if (adam) {
+      AfSweep W;
+      W.p[0] = h->t.Gu; W.m[0] = h->t.m_Gu; W.v[0] = h->t.v_Gu; W.g[0] = h->dGu; W.n[0] = (size_t)U * k;
+      W.p[1] = h->t.Gi; W.m[1] = h->t.m_Gi; W.v[1] = h->t.v_Gi; W.g[1] = h->dGi; W.n[1] = (size_t)I * k;
+      const size_t most = (size_t)(U > I ? U : I) * k;
+      const unsigned gb = af_blocks((int64_t)most, 256);
+      hipLaunchKernelGGL(k_af_sweep, dim3(gb > 4096 ? 4096 : gb), dim3(256), 0, s, W, h->cfg.beta1, h->cfg.beta2, lr_t, h->cfg.epsilon);
+      BPRX_LAUNCH_CHECK(h, "k_af_sweep");
+    } else {
+      hipLaunchKernelGGL(k_af_apply_sgd, dim3(af_blocks(R, 4)), dim3(256), 0, s, h->t.Gi, h->dGi, S->rowitem, S->islot, R, k, lr_t);
+      hipLaunchKernelGGL(k_af_apply_sgd, dim3(af_blocks(B, 4)), dim3(256), 0, s, h->t.Gu, h->dGu, S->rowuser, S->uslot, B, k, lr_t);
+      BPRX_LAUNCH_CHECK(h, "k_af_apply_sgd");
+    }
+  }
+  return BPRX_OK;
+}
+
+// The owner slots are released on every path: a step that failed half way must not leave items and users claimed.
+int bprx_af_step(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B, float *loss_out, hipStream_t s) {
+  AfState *S = h->af;
+  const int rc = af_step_body(h, user, pos, neg, B, loss_out, s);
+  S->eval_valid = false;
+  if (B > 0 && user && pos && neg) {                         // the claim kernel ran (or was at least tried): rowitem / rowuser name the rows
+    hipLaunchKernelGGL(k_af_release, dim3(af_blocks(2 * B, 256)), dim3(256), 0, s, S->rowitem, 2 * B, S->rowuser, B, S->islot, S->uslot);
+    if (!rc) BPRX_LAUNCH_CHECK(h, "k_af_release");
+  }
+  return rc;
+}
+
+int bprx_af_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t n, float *x, float *alpha, hipStream_t s) {
+  AfState *S = h->af;
+  if (n > S->R) BPRX_FAIL(h, BPRX_E_INVALID, "attentive pairs: n = %lld > 2 * max_batch", (long long)n);
+  int rc;
+  hipLaunchKernelGGL(k_af_claim, dim3(af_blocks(n, 256)), dim3(256), 0, s, item, item, n, n, user, n, h->cfg.num_items, h->cfg.num_users,
+                     S->rowitem, S->rowuser, (int32_t *)nullptr, (int32_t *)nullptr, h->errflag);
+  BPRX_LAUNCH_CHECK(h, "k_af_claim");
+  const AfDrop d = af_drop(S, 0, false);
+  if ((rc = af_encode_rows(h, n, false, d, S->C, S->R, s))) return rc;
+  hipLaunchKernelGGL(k_af_pairs, dim3(af_blocks(n, 4)), dim3(256), 16 * sizeof(float) * (size_t)S->k, s, af_att(h, S->C, S->R), S->rowuser,
+                     S->rowitem, n, x, alpha);
+  BPRX_LAUNCH_CHECK(h, "k_af_pairs");
+  return BPRX_OK;
+}
+
+// encodings of items first .. first + n (consecutive) or of a list, in chunks of R rows, into out [3, ld, k] at row offset
+static int af_encode_many(bprx_handle *h, const int32_t *items, int64_t n, float *out, int64_t ld, hipStream_t s) {
+  AfState *S = h->af;
+  const AfDrop d = af_drop(S, 0, false);
+  const size_t kb = (size_t)S->k * sizeof(float);
+  for (int64_t r0 = 0; r0 < n; r0 += S->R) {
+    const int64_t m = n - r0 < S->R ? n - r0 : S->R;
+    if (items)
+      hipLaunchKernelGGL(k_af_claim, dim3(af_blocks(m, 256)), dim3(256), 0, s, items + r0, items + r0, m, m, (const int32_t *)nullptr,
+                         (int64_t)0, h->cfg.num_items, h->cfg.num_users, S->rowitem, S->rowuser, (int32_t *)nullptr, (int32_t *)nullptr,
+                         h->errflag);
+    else
+      hipLaunchKernelGGL(k_af_iota, dim3(af_blocks(m, 256)), dim3(256), 0, s, S->rowitem, m, (int32_t)r0);
+    BPRX_LAUNCH_CHECK(h, "k_af_claim");
+    int rc;
+    if ((rc = af_encode_rows(h, m, false, d, S->C, S->R, s))) return rc;
+    for (int l = 0; l < 3; ++l)
+      BPRX_HIP(h, hipMemcpyAsync(out + ((int64_t)l * ld + r0) * S->k, S->C + (int64_t)l * S->R * S->k, m * kb, hipMemcpyDeviceToDevice, s));
+  }
+  return BPRX_OK;
+}
+
+int bprx_af_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, float *alpha, hipStream_t s) {
+  AfState *S = h->af;
+  const int I = h->cfg.num_items;
+  int rc;
+  if (!S->eval_valid) {
+    if ((rc = af_encode_many(h, nullptr, I, S->Call, I, s))) return rc;
+    S->eval_valid = true;
+  }
+  const int KP = (S->k + 7) / 8 * 8, NJ = (S->h + 31) / 32;
+  const size_t lds = sizeof(float) * ((size_t)KP * 32 * NJ + 64 * NJ + KP);
+  const int64_t tiles = ((int64_t)I + 127) / 128;
+  const AfAtt A = af_att(h, S->Call, I);
+  for (int32_t c0 = u0; c0 < u1; c0 += 32768) {              // gridDim.y holds the users: at most 65 535 per launch
+    const int32_t c1 = u1 - c0 < 32768 ? u1 : c0 + 32768;
+    const dim3 grid((unsigned)(tiles < 16 ? tiles : 16), (unsigned)(c1 - c0));
+    float *o = out + (int64_t)(c0 - u0) * I, *al = alpha ? alpha + (int64_t)(c0 - u0) * I * 3 : nullptr;
+    switch (NJ) {
+      case 1: hipLaunchKernelGGL(k_af_block<1>, grid, dim3(256), lds, s, A, S->Call, I, c0, KP, o, al); break;
+      case 2: hipLaunchKernelGGL(k_af_block<2>, grid, dim3(256), lds, s, A, S->Call, I, c0, KP, o, al); break;
+      case 3: hipLaunchKernelGGL(k_af_block<3>, grid, dim3(256), lds, s, A, S->Call, I, c0, KP, o, al); break;
+      default: hipLaunchKernelGGL(k_af_block<4>, grid, dim3(256), lds, s, A, S->Call, I, c0, KP, o, al); break;
+    }
+    BPRX_LAUNCH_CHECK(h, "k_af_block");
+  }
+  return BPRX_OK;
+}
+
+void bprx_af_invalidate(bprx_handle *h) {
+  if (h->af) h->af->eval_valid = false;
+}
+
+void bprx_af_free(bprx_handle *h) {
+  AfState *S = h->af;
+  if (!S) return;
+  void *ptrs[] = {S->islot, S->uslot, S->rowitem, S->rowuser, S->pool, S->PD, S->Hc, S->Hk, S->C, S->dC, S->A6, S->Hid, S->dHid, S->da,
+                  S->dGuS, S->dGiS, S->dH, S->dPD, S->gsum, S->cpart, S->cred, S->Call};
+  for (void *p : ptrs)
+    if (p) (void)hipFree(p);
+  for (int q = 0; q < BPRX_AF_NW; ++q)
+    if (S->g[q] && q != BPRX_AF_EDG_CB) (void)hipFree(S->g[q]);                // g[EDG_CB] lives inside g[EDG_CW]
+  delete S;
+  h->af = nullptr;
+}
+
+int bprx_bind_tables_internal(bprx_handle *h, const bprx_tables *t);
+
+extern "C" int bprx_bind_attentive(bprx_handle *h, const bprx_tables *t, const bprx_attentive *a) {
+  if (!h || !t || !a) return BPRX_E_INVALID;
+  const bprx_config &c = h->cfg;
+  if (c.model != BPRX_MODEL_BPRMF) BPRX_FAIL(h, BPRX_E_INVALID, "bind_attentive: needs a BPRMF handle");
+  if (c.flags & (BPRX_FLAG_EXPORT_USER_GRAD | BPRX_FLAG_EXPORT_ITEM_GRAD))
+    BPRX_FAIL(h, BPRX_E_INVALID, "bind_attentive: exported gradients (multi-GPU) are not supported");
+  if (a->dim_color <= 0 || a->dim_class <= 0) BPRX_FAIL(h, BPRX_E_INVALID, "bind_attentive: Dc = %d, Dk = %d must be positive", a->dim_color, a->dim_class);
+  if (a->width <= 0 || a->width > AF_MAX_H) BPRX_FAIL(h, BPRX_E_INVALID, "bind_attentive: width = %d outside [1, %d]", a->width, AF_MAX_H);
+  if (c.embed_k > AF_MAX_K) BPRX_FAIL(h, BPRX_E_INVALID, "bind_attentive: embed_k %d > %d", c.embed_k, AF_MAX_K);
+  if (!(a->dropout >= 0.f && a->dropout < 1.f)) BPRX_FAIL(h, BPRX_E_INVALID, "bind_attentive: dropout = %g outside [0, 1)", (double)a->dropout);
+  if (!a->edges || !a->color || !a->cls) BPRX_FAIL(h, BPRX_E_INVALID, "bind_attentive: edges, color and cls are required");
+  if ((uintptr_t)a->edges & 15) BPRX_FAIL(h, BPRX_E_INVALID, "bind_attentive: edges must be 16-byte aligned");
+  const int KP = (c.embed_k + 7) / 8 * 8, HP = (a->width + 31) / 32 * 32;
+  if (KP * HP > 15360) BPRX_FAIL(h, BPRX_E_INVALID, "bind_attentive: embed_k %d x width %d needs more LDS than a workgroup has", c.embed_k, a->width);
+  if (4 * (7 * (size_t)c.embed_k + 6 * (size_t)a->width) * sizeof(float) > 65536)
+    BPRX_FAIL(h, BPRX_E_INVALID, "bind_attentive: embed_k %d x width %d needs more LDS than a workgroup has", c.embed_k, a->width);
+  const bool adam = c.optimizer == BPRX_OPT_ADAM_TF23;
+  for (int q = 0; q < BPRX_AF_NW; ++q) {
+    if (!a->w[q]) BPRX_FAIL(h, BPRX_E_INVALID, "bind_attentive: tensor %d is missing", q);
+    if (adam && (!a->m_w[q] || !a->v_w[q])) BPRX_FAIL(h, BPRX_E_INVALID, "bind_attentive: adam_tf23 needs m_/v_ slots of tensor %d", q);
+  }
+  AfState *S = h->af;
+  const int64_t keep_step = S ? S->step : 0;
+  if (S) bprx_af_free(h), S = nullptr;
+  if (h->acf) bprx_acf_free(h);
+  int rc = bprx_bind_tables_internal(h, t);
+  if (rc) return rc;
+  // TF-2.3's Adam moves every row every step: the handle takes the whole-table sweeps (bring lazily held rows up to date first)
+  if (h->adam_lazy) {
+    if ((rc = bprx_launch_adam_sync(h, h->adam_t, nullptr))) return rc;
+    BPRX_HIP(h, hipStreamSynchronize(nullptr));
+    h->adam_lazy = false;
+  }
+  const size_t U = c.num_users, I = c.num_items, k = c.embed_k, R = 2 * (size_t)c.max_batch, hh = a->width;
+  S = new (std::nothrow) AfState();
+  if (!S) BPRX_FAIL(h, BPRX_E_NOMEM, "bind_attentive: out of host memory");
+  memset(S, 0, sizeof(*S));
+  h->af = S;
+  S->a = *a; S->k = (int)k; S->h = (int)hh; S->Dc = a->dim_color; S->Dk = a->dim_class; S->R = (int64_t)R; S->step = keep_step;
+  const int64_t Dc = S->Dc, Dk = S->Dk;
+  const int64_t nw[BPRX_AF_NW] = {Dc * AF_HID, AF_HID, AF_HID * (int64_t)k, 25 * AF_CH, AF_CH, AF_CH * (int64_t)k, Dk * AF_HID, AF_HID,
+                                  AF_HID * (int64_t)k, (int64_t)(k * hh), (int64_t)hh, (int64_t)hh, 1};
+  bool ok = true;
+  auto al = [&](void **p, size_t bytes) { ok = ok && hipMalloc(p, bytes) == hipSuccess && hipMemset(*p, 0, bytes) == hipSuccess; };
+  for (int q = 0; q < BPRX_AF_NW; ++q) {
+    S->nw[q] = nw[q];
+    if (q == BPRX_AF_EDG_CW) al((void **)&S->g[q], AF_CPART * sizeof(float));
+    else if (q == BPRX_AF_EDG_CB) S->g[q] = S->g[BPRX_AF_EDG_CW] ? S->g[BPRX_AF_EDG_CW] + 25 * AF_CH : nullptr;
+    else al((void **)&S->g[q], nw[q] * sizeof(float));
+  }
+  al((void **)&S->islot, I * sizeof(int32_t));
+  al((void **)&S->uslot, U * sizeof(int32_t));
+  al((void **)&S->rowitem, R * sizeof(int32_t));
+  al((void **)&S->rowuser, R * sizeof(int32_t));
+  al((void **)&S->pool, R * AF_CH * sizeof(float));
+  al((void **)&S->PD, R * AF_CH * sizeof(float));
+  al((void **)&S->Hc, R * AF_HID * sizeof(float));
+  al((void **)&S->Hk, R * AF_HID * sizeof(float));
+  al((void **)&S->C, 3 * R * k * sizeof(float));
+  al((void **)&S->dC, 3 * R * k * sizeof(float));
+  al((void **)&S->A6, 3 * R * k * sizeof(float));
+  al((void **)&S->Hid, 3 * R * hh * sizeof(float));
+  al((void **)&S->dHid, 3 * R * hh * sizeof(float));
+  al((void **)&S->da, 3 * R * sizeof(float));
+  al((void **)&S->dGuS, R / 2 * k * sizeof(float));
+  al((void **)&S->dGiS, R * k * sizeof(float));
+  al((void **)&S->dH, R * AF_HID * sizeof(float));
+  al((void **)&S->dPD, R * AF_CH * sizeof(float));
+  al((void **)&S->gsum, R * AF_CH * sizeof(float));
+  al((void **)&S->cpart, R * AF_CPART * sizeof(float));
+  al((void **)&S->cred, 64 * (size_t)AF_CPART * sizeof(float));
+  al((void **)&S->Call, 3 * I * k * sizeof(float));
+  if (!ok) {
+    bprx_af_free(h);
+    BPRX_FAIL(h, BPRX_E_NOMEM, "bind_attentive: scratch allocation failed");
+  }
+  hipLaunchKernelGGL(k_af_fill, dim3(512), dim3(256), 0, nullptr, S->islot, I, (int32_t)INT_MAX);
+  hipLaunchKernelGGL(k_af_fill, dim3(512), dim3(256), 0, nullptr, S->uslot, U, (int32_t)INT_MAX);
+  BPRX_LAUNCH_CHECK(h, "k_af_fill");
+  S->eval_valid = false;
+  BPRX_HIP(h, hipStreamSynchronize(nullptr));
+  return BPRX_OK;
+}
+
+#define AF_CHECK(name)                                                                                              \
+  if (!h) return BPRX_E_INVALID;                                                                                    \
+  if (!h->bound || !h->af) BPRX_FAIL(h, BPRX_E_STATE, name ": the handle is not bound with bprx_bind_attentive");
+
+extern "C" int bprx_af_encode(bprx_handle *h, const int32_t *items, int64_t n, float *out, void *stream) {
+  AF_CHECK("af_encode")
+  if (n < 0 || n > ((int64_t)1 << 31) - 1) BPRX_FAIL(h, BPRX_E_INVALID, "af_encode: n = %lld out of range", (long long)n);
+  if (n == 0) return BPRX_OK;
+  if (!items || !out) BPRX_FAIL(h, BPRX_E_INVALID, "af_encode: null pointer");
+  return af_encode_many(h, items, n, out, n, (hipStream_t)stream);
+}
+
+extern "C" int bprx_af_attention_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t n, float *x, float *alpha,
+                                       void *stream) {
+  AF_CHECK("af_attention_pairs")
+  if (n < 0 || n > h->cfg.max_batch) BPRX_FAIL(h, BPRX_E_INVALID, "af_attention_pairs: n = %lld outside [0, max_batch]", (long long)n);
+  if (n == 0) return BPRX_OK;
+  if (!user || !item || !x) BPRX_FAIL(h, BPRX_E_INVALID, "af_attention_pairs: null pointer");
+  return bprx_af_pairs(h, user, item, n, x, alpha, (hipStream_t)stream);
+}
+
+extern "C" int bprx_af_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *scores, float *alpha, void *stream) {
+  AF_CHECK("af_score_block")
+  if (u0 < 0 || u1 > h->cfg.num_users || u0 > u1 || !scores) BPRX_FAIL(h, BPRX_E_INVALID, "af_score_block: bad user range [%d,%d)", u0, u1);
+  if (u0 == u1) return BPRX_OK;
+  return bprx_af_block(h, u0, u1, scores, alpha, (hipStream_t)stream);
+}
+
+extern "C" int bprx_af_dropout_mask(bprx_handle *h, int64_t step, int64_t n_rows, uint8_t *out, void *stream) {
+  AF_CHECK("af_dropout_mask")
+  if (n_rows < 0 || n_rows > h->af->R || step < 0) BPRX_FAIL(h, BPRX_E_INVALID, "af_dropout_mask: bad step / n_rows");
+  if (n_rows == 0) return BPRX_OK;
+  if (!out) BPRX_FAIL(h, BPRX_E_INVALID, "af_dropout_mask: null pointer");
+  const AfDrop d = af_drop(h->af, step, true);
+  hipLaunchKernelGGL(k_af_mask, dim3(af_blocks(n_rows * 144, 256)), dim3(256), 0, (hipStream_t)stream, d, n_rows, out);
+  BPRX_LAUNCH_CHECK(h, "k_af_mask");
+  return BPRX_OK;
+}
+
+extern "C" int64_t bprx_af_get_step(const bprx_handle *h) { return h && h->af ? h->af->step : -1; }
+
+extern "C" int bprx_af_set_step(bprx_handle *h, int64_t step) {
+  AF_CHECK("af_set_step")
+  if (step < 0) BPRX_FAIL(h, BPRX_E_INVALID, "af_set_step: step < 0");
+  h->af->step = step;
+  return BPRX_OK;
+}

@@ -12,6 +12,7 @@
 #define BPRX_DENSE_BLOCKS 2048
 
 struct AcfState;   // bprx_acf.hip
+struct AfState;    // bprx_attentive.hip
 
 struct bprx_handle {
   bprx_config cfg;
@@ -121,6 +122,8 @@ struct bprx_handle {
   float *gF;                      // [Dc*ec + De*ee + (ec+ee)*(d+1)] gradient of the factors (Ea | Eb | A | Ap), one step
   // ACF (bprx_bind_acf, bprx_acf.hip): bound model state and scratch; nullptr unless the handle is bound ACF
   struct AcfState *acf;
+  // AttentiveFashion (bprx_bind_attentive, bprx_attentive.hip): nullptr unless the handle is bound for it
+  struct AfState *af;
   // replicated-user message exchange (bprx_pack_user_msg / bprx_apply_user_msgs)
   int32_t *msg_cursor;            // [2] next free slot of the message being packed, workgroups done (both zero between calls)
   int32_t *msg_next;              // [nranks*cap] chain links of the occurrences of one user across the ranks' messages
@@ -209,6 +212,27 @@ int bprx_acf_eval_profiles(bprx_handle *h, hipStream_t s);   // g'_u of every us
 float *bprx_acf_eval_gu(bprx_handle *h);
 void bprx_acf_invalidate(bprx_handle *h);                    // bound tables written from outside
 void bprx_acf_free(bprx_handle *h);
+// AttentiveFashion (bprx_attentive.hip): what bprx_step / bprx_score_pairs / bprx_score_block do on a handle bound with bprx_bind_attentive
+int bprx_af_step(bprx_handle *h, const int32_t *u, const int32_t *i, const int32_t *j, int64_t B, float *loss_out, hipStream_t s);
+int bprx_af_pairs(bprx_handle *h, const int32_t *u, const int32_t *i, int64_t n, float *x, float *alpha, hipStream_t s);
+int bprx_af_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, float *alpha, hipStream_t s);
+void bprx_af_invalidate(bprx_handle *h);
+void bprx_af_free(bprx_handle *h);
+
+// Philox4x32-10 (Salmon et al. 2011): the generator of the device samplers (bprx_philox.hip) and of the dropout stream
+// (bprx_attentive.hip)
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t (&out)[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
+    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
 
 // adam_tf23, sparse-variable rule (TF-2.3 Keras Adam is NOT lazy: every row of the table decays and moves every step):
 //   m = m*b1 + g*(1-b1); v = v*b2 + g*g*(1-b2); var -= lr_t*m/(sqrt(v)+eps)     (g == 0 on untouched rows)

@@ -232,6 +232,85 @@ class Engine:
         _ffi.check(self.h, self.lib.bprx_acf_profiles(self.h, _ptr(u), u.numel(), _ptr(ptr), _ptr(items), _ptr(out), _stream()))
         return out
 
+    def bind_attentive(self, Gu, Gi, Bi, edges, color, cls, weights, dropout=0.5, seed=0, slots=None):
+        """AttentiveFashion (bprx_bind_attentive) on a BPRMF engine: edges uint8 [I, 224, 224], color fp32 [I, Dc] (each row already
+        divided by its own max-abs), cls fp32 [I, Dk], weights = the thirteen tensors keyed by _ffi.AF_WEIGHTS (shapes of
+        include/bprx.h).  Adam slots (m_ / v_ for Gu, Gi, Bi and every weight) are zeros unless given."""
+        if self.model != "bprmf":
+            raise ValueError("bind_attentive needs an Engine(model='bprmf', ...)")
+        def prep(x, shape=None, dtype=torch.float32):
+            x = torch.as_tensor(x).to(device=self.device, dtype=dtype)
+            return (x.reshape(shape) if shape is not None else x).contiguous()
+        Ed = prep(edges, (self.I, 224, 224), torch.uint8)
+        Xc, Xk = prep(color), prep(cls)
+        if Xc.dim() != 2 or Xk.dim() != 2 or Xc.shape[0] != self.I or Xk.shape[0] != self.I:
+            raise ValueError("color / cls must be [num_items, D], got %s and %s" % (tuple(Xc.shape), tuple(Xk.shape)))
+        Dc, Dk, k = int(Xc.shape[1]), int(Xk.shape[1]), self.k
+        hh = int(torch.as_tensor(weights["attention.W_1"]).shape[1])
+        shapes = {"color.W1": (Dc, 256), "color.b1": (256,), "color.W2": (256, k), "edges.conv": (25, 64), "edges.conv_b": (64,),
+                  "edges.W2": (64, k), "class.W1": (Dk, 256), "class.b1": (256,), "class.W2": (256, k),
+                  "attention.W_1": (k, hh), "attention.b_1": (hh,), "attention.W_2": (hh, 1), "attention.b_2": (1,)}
+        t = {"Gu": prep(Gu, (self.U, self.k)), "Gi": prep(Gi, (self.I, self.k)), "Bi": prep(Bi, (self.I,))}
+        for key in _ffi.AF_WEIGHTS:
+            t[key] = prep(weights[key], shapes[key])
+        if self.optimizer == "adam_tf23":
+            for n in ["Gu", "Gi", "Bi"] + list(_ffi.AF_WEIGHTS):
+                for s_ in ("m_", "v_"):
+                    given = None if slots is None else slots.get(s_ + n)
+                    t[s_ + n] = torch.zeros_like(t[n]) if given is None else prep(given, tuple(t[n].shape))
+        self.af_inputs = (Ed, Xc, Xk)
+        tb = _ffi.Tables()
+        for n in _ffi.TABLE_FIELDS:
+            setattr(tb, n, None if t.get(n) is None else t[n].data_ptr())
+        af = _ffi.Attentive(Dc, Dk, hh, float(dropout), int(seed) & (2 ** 64 - 1), Ed.data_ptr(), Xc.data_ptr(), Xk.data_ptr())
+        for q, key in enumerate(_ffi.AF_WEIGHTS):
+            af.w[q] = t[key].data_ptr()
+            if self.optimizer == "adam_tf23":
+                af.m_w[q], af.v_w[q] = t["m_" + key].data_ptr(), t["v_" + key].data_ptr()
+        torch.cuda.current_stream(self.device).synchronize()
+        _ffi.check(self.h, self.lib.bprx_bind_attentive(self.h, C.byref(tb), C.byref(af)))
+        self.attentive = True
+        self.t = t
+        return self
+
+    def af_encode(self, items):
+        """The three encodings of the listed items, dropout off (bprx_af_encode): fp32 device tensor [3, n, k]."""
+        i = as_index(items, self.device)
+        out = torch.empty((3, i.numel(), self.k), dtype=torch.float32, device=self.device)
+        _ffi.check(self.h, self.lib.bprx_af_encode(self.h, _ptr(i), i.numel(), _ptr(out), _stream()))
+        return out
+
+    def af_attention_pairs(self, user, item):
+        """Scores [n] and attentions [n, 3] (colour, edges, class) of the pairs, dropout off (bprx_af_attention_pairs)."""
+        u, i = as_index(user, self.device), as_index(item, self.device)
+        x = torch.empty(u.numel(), dtype=torch.float32, device=self.device)
+        al = torch.empty((u.numel(), 3), dtype=torch.float32, device=self.device)
+        _ffi.check(self.h, self.lib.bprx_af_attention_pairs(self.h, _ptr(u), _ptr(i), u.numel(), _ptr(x), _ptr(al), _stream()))
+        return x, al
+
+    def af_score_block(self, u0, u1):
+        """Scores [u1-u0, I] and attentions [u1-u0, I, 3] of a user block (bprx_af_score_block)."""
+        x = torch.empty((u1 - u0, self.I), dtype=torch.float32, device=self.device)
+        al = torch.empty((u1 - u0, self.I, 3), dtype=torch.float32, device=self.device)
+        _ffi.check(self.h, self.lib.bprx_af_score_block(self.h, int(u0), int(u1), _ptr(x), _ptr(al), _stream()))
+        return x, al
+
+    def af_dropout_mask(self, step, n_rows):
+        """The keep masks of step index `step` for n_rows = 2B sample rows (bprx_af_dropout_mask): three uint8 device tensors
+        [n_rows, 256], [n_rows, 64], [n_rows, 256] (colour hidden units, pooled edge channels, class hidden units)."""
+        out = torch.empty(int(n_rows) * 576, dtype=torch.uint8, device=self.device)
+        _ffi.check(self.h, self.lib.bprx_af_dropout_mask(self.h, int(step), int(n_rows), _ptr(out), _stream()))
+        n = int(n_rows)
+        return out[:n * 256].view(n, 256), out[n * 256:n * 320].view(n, 64), out[n * 320:].view(n, 256)
+
+    @property
+    def af_step(self):
+        return int(self.lib.bprx_af_get_step(self.h))
+
+    @af_step.setter
+    def af_step(self, v):
+        _ffi.check(self.h, self.lib.bprx_af_set_step(self.h, int(v)))
+
     def explain_pairs(self, user, item):
         """GradFashion.predict_ui_grads for every pair (bprx_explain_pairs): fp32 device tensor [n, 2] = (colour, edges)."""
         u, i = as_index(user, self.device), as_index(item, self.device)

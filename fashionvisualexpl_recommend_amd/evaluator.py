@@ -229,3 +229,35 @@ class Evaluator:
                 g = self.model.engine.explain_pairs(users, items).cpu().numpy()
                 for r, (u, i) in enumerate(zip(users, items)):
                     out.write(str(u) + '\t' + str(i) + '\t' + str(g[r, 0]) + '\t' + str(g[r, 1]) + '\n')
+
+    def store_recommendation_attention(self, path=""):
+        """Evaluator.py:241-259 (AttentiveFashion): the top-k rows 'u\\titem\\tscore\\talpha_colour\\talpha_edges\\talpha_class'.
+        Scores and attentions come from one bprx_af_score_block call per user block; the top-k and the gather of its
+        attentions run on the device, rows whose order depends on equal scores are redone on the host as in
+        store_recommendation."""
+        import torch
+        eng = self.model.engine
+        self._metrics_device_csr()
+        U, I = self.model.data.num_users, self.model.data.num_items
+        blk = max(1, min(self.user_block, (1 << 27) // max(1, I)))
+        with open(path, 'w') as out:
+            for u0 in range(0, U, blk):
+                u1 = min(U, u0 + blk)
+                sc, al = eng.af_score_block(u0, u1)
+                idx, val, flag = eng.topk(u0, u1, sc, self._csr["train"], self.k)
+                kk = min(self.k, idx.shape[1], I)
+                pick = idx[:, :kk].long().clamp_(0, I - 1).unsqueeze(-1).expand(-1, -1, 3)
+                att = torch.gather(al, 1, pick).cpu().numpy()
+                idx, val, flag = idx.cpu().numpy(), val.cpu().numpy(), flag.cpu().numpy()
+                for r in range(u1 - u0):
+                    u = u0 + r
+                    if flag[r]:
+                        row = sc[r].cpu().numpy()
+                        top_k_id = row.argsort()[-self.k:][::-1]
+                        top_k_score = row[top_k_id]
+                        a = al[r].cpu().numpy()[top_k_id]
+                    else:
+                        top_k_id, top_k_score, a = idx[r, :kk], val[r, :kk], att[r]
+                    for i, value in enumerate(top_k_id):
+                        out.write(str(u) + '\t' + str(value) + '\t' + str(top_k_score[i]) + '\t' + str(a[i, 0]) + '\t' +
+                                  str(a[i, 1]) + '\t' + str(a[i, 2]) + '\n')

@@ -543,4 +543,138 @@ class ACF(BPRMF):
     __call__ = call
 
 
+def load_attentive_inputs(dataset, num_items):
+    """AttentiveFashion's three per-item inputs (dataset.py:158-208) as CPU tensors: edges uint8 [I, 224, 224] (PIL convert('L'),
+    resize((224, 224)); the reference's `/ np.float32(255)` of a uint8 image is applied by the kernels, exactly), colour fp32 [I, Dc]
+    with every histogram divided by its OWN max-abs, classes fp32 [I, Dk] as they are.  A missing file raises ValueError naming it; an
+    all-zero histogram (a division by zero in the reference) is rejected."""
+    from PIL import Image
+    ed, cd, kd = configs.edges_path(dataset), configs.hist_color_features_path_dir(dataset), configs.class_features_path_dir(dataset)
+    edges = torch.empty((num_items, 224, 224), dtype=torch.uint8)
+    color, classes = None, None
+    for i in range(num_items):
+        for f in (ed + "%d.tiff" % i, cd + "%d.npy" % i, kd + "%d.npy" % i):
+            if not os.path.exists(f):
+                raise ValueError("AttentiveFashion input %s is missing" % f)
+        with Image.open(ed + "%d.tiff" % i) as im:
+            edges[i] = torch.from_numpy(np.array(im.convert('L').resize((224, 224)), dtype=np.uint8))
+        col = np.asarray(np.load(cd + "%d.npy" % i)).reshape(-1)
+        cl = np.asarray(np.load(kd + "%d.npy" % i)).reshape(-1)
+        if color is None:
+            color = np.empty((num_items, col.size), np.float32)
+            classes = np.empty((num_items, cl.size), np.float32)
+        if col.size != color.shape[1] or cl.size != classes.shape[1]:
+            raise ValueError("AttentiveFashion inputs of item %d have sizes %d / %d, expected %d / %d (the sizes of item 0)"
+                             % (i, col.size, cl.size, color.shape[1], classes.shape[1]))
+        mx = np.max(np.abs(col))
+        if not mx > 0:
+            raise ValueError("colour histogram %s is all zero: its max-abs normalisation divides by zero" % (cd + "%d.npy" % i))
+        color[i] = col / mx
+        classes[i] = cl
+    return edges, torch.from_numpy(color), torch.from_numpy(classes)
+
+
+class AttentiveFashion(BPRMF):
+    """AttentiveFashion.py:20-371: x_ui = sum_k g_u * (sum_l alpha_l c_l) * g_i with the encodings c_l of the item's colour
+    histogram, edge image and class vector and a three-way attention over them, trained on the engine's AttentiveFashion path
+    (include/bprx.h, bprx_bind_attentive) with the reference's full gradient and active dropout.  Same surface as the reference:
+    color_encoder / edges_encoder / class_encoder / attention_network (dicts of the bound tensors), attention_layers, call, train_step,
+    train, predict_all_batch.  `inputs`: optional (edges uint8 [I, 224, 224], colour [I, Dc] already normalised, classes [I, Dk]) used
+    instead of the per-item files."""
+    model_kind = "attentive_fashion"
+
+    def __init__(self, data, params, init=None, inputs=None):
+        self.attention_layers = [int(x) for x in getattr(params, "attention_layers", [64, 1])]
+        l = self.attention_layers
+        if len(l) != 2 or l[1] != 1 or l[0] <= 0:
+            raise ValueError("AttentiveFashion: --attention_layers must be two ints 'h 1' with h > 0 (got %s)" % (l,))
+        if getattr(params, "dtype", "fp32") != "fp32":
+            raise ValueError("AttentiveFashion runs with --dtype fp32 (got %s)" % params.dtype)
+        self.dropout = float(getattr(params, "dropout", 0.5))
+        self._inputs = inputs
+        super().__init__(data, params, init)
+        self.directory_parameters = f'batch_{params.batch_size}' \
+                                    f'-K_{params.embed_k}' \
+                                    f'-lr_{params.lr}' \
+                                    f'-reg_{params.reg}' \
+                                    f'-attlayers_{list(self.attention_layers)}'       # AttentiveFashion.py:275-279
+
+    def _init_tables(self, init):
+        # BPRMF.py:48-50 creates Bi, Gu, Gi with ITS initialiser (Glorot uniform): AttentiveFashion.py:24 assigns RandomNormal(0.01)
+        # only afterwards, and nothing reads it.  Then the Keras layers in creation order (Glorot-uniform kernels, zero biases),
+        # then the attention tensors (Glorot uniform, biases included: AttentiveFashion.py:118-144).
+        t, rs = super()._init_tables(init)
+        if self._inputs is None:
+            self._inputs = load_attentive_inputs(self.params.dataset, self.num_items)
+        self.edges, self.color, self.classes = (torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x)
+                                                for x in self._inputs)
+        Dc, Dk, k, h = int(self.color.shape[1]), int(self.classes.shape[1]), self.embed_k, self.attention_layers[0]
+        lim = np.sqrt(6.0 / (25 * 1 + 25 * 64))                                  # Conv2D fans: 5*5*in, 5*5*out
+        v = {"color.W1": glorot_uniform(rs, Dc, 256), "color.b1": np.zeros(256, np.float32), "color.W2": glorot_uniform(rs, 256, k),
+             "edges.conv": rs.uniform(-lim, lim, size=(25, 64)).astype(np.float32), "edges.conv_b": np.zeros(64, np.float32),
+             "edges.W2": glorot_uniform(rs, 64, k),
+             "class.W1": glorot_uniform(rs, Dk, 256), "class.b1": np.zeros(256, np.float32), "class.W2": glorot_uniform(rs, 256, k),
+             "attention.W_1": glorot_uniform(rs, k, h), "attention.b_1": _glorot_1d(rs, h),
+             "attention.W_2": glorot_uniform(rs, h, 1), "attention.b_2": _glorot_1d(rs, 1)}
+        v.update({n: val for n, val in init.items() if n in v})
+        t.update(v)
+        return t, rs
+
+    def _adam_form(self):
+        return "sweep" if self.optimizer_name == "adam_tf23" else None      # the handle always sweeps (include/bprx.h)
+
+    def _build(self, init):
+        t, _ = self._init_tables(init)
+        self.engine = Engine(optimizer=self.optimizer_name, lr=self.learning_rate, reg=self.reg,
+                             max_batch=max(self.batch_size, 1024), adam_form=self._adam_form(), **self._engine_kwargs())
+        self.engine.bind_attentive(t["Gu"], t["Gi"], t["Bi"], self.edges, self.color, self.classes, {n: t[n] for n in _AF_W},
+                                   dropout=self.dropout, seed=getattr(self.params, "init_seed", 0))
+
+    # ---- the reference's attribute surface ---------------------------------------------------------------------------
+    def _group(self, prefix):
+        return {n.split(".", 1)[1]: self.engine.t[n] for n in _AF_W if n.startswith(prefix + ".")}
+
+    color_encoder = property(lambda self: self._group("color"))
+    edges_encoder = property(lambda self: self._group("edges"))
+    class_encoder = property(lambda self: self._group("class"))
+    attention_network = property(lambda self: self._group("attention"))
+
+    # ---- AttentiveFashion.py:168-209 (dropout off, as a call outside train_step) -------------------------------------------------
+    def call(self, inputs, training=None, mask=None):
+        user, item = inputs[0], inputs[1]
+        u, i = as_index(user, self.engine.device).long(), as_index(item, self.engine.device).long()
+        xui, alpha = self.engine.af_attention_pairs(u, i)
+        c = self.engine.af_encode(i)
+        return xui, self.Gu[u], self.Gi[i], c[0], c[1], c[2], alpha
+
+    __call__ = call
+
+    # ---- AttentiveFashion.py:325-371 ------------------------------------------------------------------------------------------------
+    def predict_all_batch(self, step=None, next_image=None, user_block=256):
+        """Scores [U, I] and attentions [U, I, 3] as numpy arrays, user block by user block.  Every item is encoded once per call
+        (the reference re-encodes every item for every user, and fails when num_items % batch_eval == 0); `step` / `next_image` are
+        accepted for the reference's signature and ignored."""
+        xs, als = [], []
+        for u0 in range(0, self.num_users, user_block):
+            x, al = self.engine.af_score_block(u0, min(self.num_users, u0 + user_block))
+            xs.append(x.cpu().numpy()); als.append(al.cpu().numpy())
+        return np.concatenate(xs), np.concatenate(als)
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["dropout_step"] = self.engine.af_step
+        return sd
+
+    def load_state_dict(self, sd):
+        sd = dict(sd)
+        step = sd.pop("dropout_step", None)
+        super().load_state_dict(sd)
+        if step is not None:
+            self.engine.af_step = step
+
+    def _store_recs(self, path):
+        self.evaluator.store_recommendation_attention(path=path)
+
+
 from ._ffi import ACF_WEIGHTS as _ACF_W     # noqa: E402
+from ._ffi import AF_WEIGHTS as _AF_W       # noqa: E402

@@ -88,3 +88,40 @@ def write_grad_fashion_features(root, name, color, edges, cnn_model="vgg19", out
     np.save(os.path.join(d, "features", "histograms.npy"), np.asarray(color))
     np.save(os.path.join(d, "edge_features_{0}_{1}.npy".format(cnn_model, output_layer)), np.asarray(edges))
     return d
+
+
+def make_edge_images(num_items, size=48, seed=2024):
+    """Sparse edge-like greyscale images, uint8 [I, size, size]: a few random strokes on black (most pixels are zero, as in
+    an edge map), plus a blank image for item 0 when there are at least two items."""
+    rs = np.random.RandomState(seed + 2)
+    out = np.zeros((num_items, size, size), np.uint8)
+    for i in range(num_items):
+        if i == 0 and num_items > 1:
+            continue
+        for _ in range(rs.randint(3, 9)):
+            r, c = rs.randint(size), rs.randint(size)
+            if rs.randint(2):
+                out[i, r, c:c + rs.randint(4, size)] = rs.randint(64, 256)
+            else:
+                out[i, r:r + rs.randint(4, size), c] = rs.randint(64, 256)
+    return out
+
+
+def write_attentive_features(root, name, num_items, dim_color=24, dim_class=10, image_size=48, seed=2024):
+    """AttentiveFashion's three per-item inputs in the reference's layout (dataset.py:158-208): original/features/edges/{i}.tiff
+    (greyscale, image_size x image_size: NOT 224, so that loading exercises the resize), color_histograms/{i}.npy [dim_color]
+    (non-negative counts, not normalised) and one_hot_encodings/{i}.npy [dim_class].  Returns (edges, color, cls) as written."""
+    from PIL import Image
+    rs = np.random.RandomState(seed + 3)
+    d = os.path.join(root, name, "original", "features")
+    for sub in ("edges", "color_histograms", "one_hot_encodings"):
+        os.makedirs(os.path.join(d, sub), exist_ok=True)
+    edges = make_edge_images(num_items, image_size, seed)
+    color = (rs.random_sample((num_items, dim_color)) * 100.0 + 1.0).astype(np.float32)
+    cls = np.zeros((num_items, dim_class), np.float32)
+    cls[np.arange(num_items), rs.randint(dim_class, size=num_items)] = 1.0
+    for i in range(num_items):
+        Image.fromarray(edges[i], mode="L").save(os.path.join(d, "edges", "%d.tiff" % i))
+        np.save(os.path.join(d, "color_histograms", "%d.npy" % i), color[i])
+        np.save(os.path.join(d, "one_hot_encodings", "%d.npy" % i), cls[i])
+    return edges, color, cls

@@ -209,6 +209,64 @@ BPRX_API int bprx_bind_acf(bprx_handle *h, const bprx_tables *t, const bprx_acf 
 BPRX_API int bprx_acf_profiles(bprx_handle *h, const int32_t *users, int64_t n, const int64_t *hist_ptr,
                                const int32_t *hist_items, float *out, void *stream);
 
+/* ---- AttentiveFashion (AttentiveFashion.py:20-371) on a BPRMF handle ----------------------------------------------------
+   Per item i three inputs: an edge image (uint8 [224, 224]; the model sees pixel / 255), a colour histogram [Dc] and a class
+   vector [Dk].  Three encoders into k = embed_k columns:
+       colour, class   c = dropout(relu(x W1 + b1)) W2                        (W1 [D, 256], b1 [256], W2 [256, k])
+       edges           c = dropout(mean(maxpool2x2(relu(conv5x5_same(img) + cb)))) W2    (conv [5, 5, 1, 64], cb [64], W2 [64, k])
+   and a three-way attention over c_l, l = (colour, edges, class) in that order:
+       a_l = relu((g_u * c_l) W_1 + b_1) W_2 + b_2      alpha = softmax_l(a)      x_ui = sum_k g_u * (sum_l alpha_l c_l) * g_i
+   There is no item bias (Bi is bound but neither scored nor trained).  After bprx_bind_attentive
+     bprx_step         the reference's step (AttentiveFashion.py:211-258): BPR loss + reg * (|g_u|^2 + |g_i|^2 + |g_j|^2 + the six
+                       encoder OUTPUTS + the four attention tensors), the full gradient (nothing detached) into Gu, Gi, every
+                       encoder weight and the attention tensors.  Dropout is active (rate, seed below; the stream is the
+                       library's own: Philox4x32-10 keyed by seed, counter (unit / 4, sample row, encoder 0/1/2, step index),
+                       word unit % 4 >= rate * 2^32 keeps the unit, kept units are scaled by 1 / (1 - rate); sample rows are
+                       the B positives, then the B negatives).  sgd, or adam_tf23: the sparse-variable rule on Gu / Gi by
+                       whole-table sweeps (the handle never runs the lazy form), the dense ApplyAdam rule on the rest.
+                       Every sum of a step runs in a fixed order: a step is bit-reproducible.
+     bprx_score_pairs  scores with dropout off
+     bprx_score_block  every item is encoded once per parameter state, then one pairwise MFMA attention kernel per user block;
+                       eval_* and topk work unchanged on the scores.
+   bprx_step_begin / _end and the multi-GPU entry points are rejected (BPRX_E_STATE).  Indices out of range are clamped and
+   reported by bprx_sync_check (BPRX_E_RANGE).
+   Limits: width <= 128, embed_k <= 512, (embed_k rounded up to 8) * (width rounded up to 32) <= 15 360. */
+enum {
+  BPRX_AF_COL_W1 = 0, BPRX_AF_COL_B1 = 1, BPRX_AF_COL_W2 = 2,      /* color_encoder.trainable_weights */
+  BPRX_AF_EDG_CW = 3, BPRX_AF_EDG_CB = 4, BPRX_AF_EDG_W2 = 5,      /* edges_encoder: conv kernel [25, 64] (tap-major), bias, dense */
+  BPRX_AF_CLS_W1 = 6, BPRX_AF_CLS_B1 = 7, BPRX_AF_CLS_W2 = 8,      /* class_encoder */
+  BPRX_AF_ATT_W1 = 9, BPRX_AF_ATT_B1 = 10, BPRX_AF_ATT_W2 = 11, BPRX_AF_ATT_B2 = 12,   /* attention_network [k,h] [h] [h,1] [1] */
+  BPRX_AF_NW = 13
+};
+#define BPRX_AF_IMG 224       /* edge images are [224, 224] */
+#define BPRX_AF_HID 256       /* hidden units of the colour / class encoders */
+#define BPRX_AF_CH 64         /* conv filters */
+typedef struct {
+  int32_t dim_color, dim_class;     /* Dc, Dk */
+  int32_t width;                    /* h = attention_layers[0] */
+  float dropout;                    /* rate in [0, 1); 0: no mask and no scaling */
+  uint64_t seed;                    /* key of the dropout stream */
+  const uint8_t *edges;             /* [I, 224, 224], frozen; read in place (must stay valid while bound) */
+  const float *color;               /* [I, Dc], each row already divided by its own max-abs */
+  const float *cls;                 /* [I, Dk] */
+  float *w[BPRX_AF_NW];
+  float *m_w[BPRX_AF_NW], *v_w[BPRX_AF_NW];   /* adam_tf23 slots */
+} bprx_attentive;
+BPRX_API int bprx_bind_attentive(bprx_handle *h, const bprx_tables *t, const bprx_attentive *a);
+/* The three encodings of n listed items with dropout off: out fp32 [3, n, k] (colour, edges, class).  Any n >= 0. */
+BPRX_API int bprx_af_encode(bprx_handle *h, const int32_t *items, int64_t n, float *out, void *stream);
+/* Scores and attentions of n <= max_batch pairs, dropout off: x fp32 [n], alpha fp32 [n, 3] (colour, edges, class). */
+BPRX_API int bprx_af_attention_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t n, float *x, float *alpha,
+                                     void *stream);
+/* bprx_score_block with the attentions next to the scores: scores fp32 [u1-u0, I], alpha fp32 [u1-u0, I, 3] (NULL: scores only). */
+BPRX_API int bprx_af_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *scores, float *alpha, void *stream);
+/* The keep-mask bytes (1 = kept) of step index `step` for a batch of n_rows / 2 triplets: out uint8
+   [n_rows * 256 | n_rows * 64 | n_rows * 256] (colour hidden units, pooled edge channels, class hidden units). */
+BPRX_API int bprx_af_dropout_mask(bprx_handle *h, int64_t step, int64_t n_rows, uint8_t *out, void *stream);
+/* The step index the next bprx_step uses (starts at 0 at the first bind; part of a snapshot). */
+BPRX_API int64_t bprx_af_get_step(const bprx_handle *h);
+BPRX_API int bprx_af_set_step(bprx_handle *h, int64_t step);
+
 /* Model.call((user,item)) -> xui        BPRMF.py:55-76 / VBPR.py:59-86.   x: fp32 [B] */
 BPRX_API int bprx_score_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t B, float *x, void *stream);
 

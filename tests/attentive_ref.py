@@ -1,0 +1,147 @@
+"""Restatement of the reference's AttentiveFashion.py (20-371) in torch on the CPU, float64 by default, in its literal order:
+three encoders (colour / class: Dense(256, relu) -> Dropout -> Dense(k, no bias); edges: Conv2D(64, 5x5, same, relu) -> MaxPool 2x2
+-> GlobalAveragePooling -> Dropout -> Dense(k, no bias)), the three-way attention over (colour, edges, class), the BPR loss with the
+regulariser on g_u, g_i, g_j, the six encoder OUTPUTS and the four attention tensors, the full gradient (autograd, nothing detached),
+sgd or TF-2.3 Adam (sparse-variable rule on Gu / Gi, dense ApplyAdam on the rest, as tests/torch_ref.py states them).
+The dropout keep masks are an ARGUMENT (the library owns the stream; TF's cannot be reproduced): masks = (colour [2B, 256],
+edges [2B, 64], class [2B, 256]) of 0/1, rows = the B positives then the B negatives, kept units scaled by 1 / (1 - rate).
+`dtype=torch.float32` runs the same statement in float32 (the yardstick of the conv-gradient tolerance)."""
+import numpy as np
+import torch
+import torch.nn.functional as Fn
+
+AF_WEIGHTS = ["color.W1", "color.b1", "color.W2", "edges.conv", "edges.conv_b", "edges.W2", "class.W1", "class.b1", "class.W2",
+              "attention.W_1", "attention.b_1", "attention.W_2", "attention.b_2"]
+SPARSE = ("Gu", "Gi")
+B1, B2, EPS = 0.9, 0.999, 1e-7
+
+
+class AttentiveRef:
+    def __init__(self, tables, edges, color, cls, reg=0.0, rate=0.5, dtype=torch.float64):
+        """tables: Gu, Gi and the thirteen AF_WEIGHTS (edges.conv as [25, 64] = the [5, 5, 1, 64] kernel, tap-major);
+        edges uint8 [I, 224, 224]; color [I, Dc] (already divided by each row's max-abs); cls [I, Dk]."""
+        self.dt = dtype
+        self.p = {n: torch.as_tensor(np.asarray(tables[n])).to(dtype).clone() for n in ("Gu", "Gi") + tuple(AF_WEIGHTS)}
+        self.edges = torch.as_tensor(np.asarray(edges))
+        self.color = torch.as_tensor(np.asarray(color)).to(dtype)
+        self.cls = torch.as_tensor(np.asarray(cls)).to(dtype)
+        self.reg, self.rate = reg, rate
+        self.slots, self.t = {}, 0
+
+    # ---- encoders (AttentiveFashion.py:50-72) -------------------------------------------------------------------------
+    def pooled(self, p, items):
+        x = (self.edges[items].to(self.dt) / 255.0).unsqueeze(1)                     # dataset.py:172 (/ np.float32(255))
+        w = p["edges.conv"].reshape(5, 5, 64).permute(2, 0, 1).unsqueeze(1)          # [64, 1, 5, 5]
+        y = torch.relu(Fn.conv2d(x, w, p["edges.conv_b"], padding=2))
+        return Fn.max_pool2d(y, 2).mean((2, 3))
+
+    def encode(self, p, items, masks=None):
+        items = torch.as_tensor(np.asarray(items)).long()
+        sc = 1.0 / (1.0 - self.rate) if masks is not None else 1.0
+        drop = (lambda x, m: x * m.to(self.dt) * sc) if masks is not None else (lambda x, m: x)
+        mc, me, mk = masks if masks is not None else (None, None, None)
+        col = drop(torch.relu(self.color[items] @ p["color.W1"] + p["color.b1"]), mc) @ p["color.W2"]
+        edg = drop(self.pooled(p, items), me) @ p["edges.W2"]
+        cla = drop(torch.relu(self.cls[items] @ p["class.W1"] + p["class.b1"]), mk) @ p["class.W2"]
+        return col, edg, cla
+
+    # ---- propagate_attention + call (AttentiveFashion.py:146-209) -------------------------------------------------------
+    def score(self, p, gu, gi, enc):
+        c = torch.stack(enc, 1)                                                      # [n, 3, k]: colour, edges, class
+        a = torch.relu((gu.unsqueeze(1) * c) @ p["attention.W_1"] + p["attention.b_1"]) @ p["attention.W_2"].reshape(-1, 1) \
+            + p["attention.b_2"]
+        alpha = torch.softmax(a, 1)                                                  # [n, 3, 1]
+        x = (gu * (alpha * c).sum(1) * gi).sum(1)
+        return x, alpha[:, :, 0]
+
+    def call(self, users, items, masks=None, p=None):
+        p = self.p if p is None else p
+        u, i = torch.as_tensor(np.asarray(users)).long(), torch.as_tensor(np.asarray(items)).long()
+        enc = self.encode(p, i, masks)
+        x, alpha = self.score(p, p["Gu"][u], p["Gi"][i], enc)
+        return x, alpha, enc
+
+    def predict_all(self):
+        """predict_all_batch (AttentiveFashion.py:325-371): scores [U, I] and attentions [U, I, 3], every item encoded once."""
+        with torch.no_grad():
+            I = self.p["Gi"].shape[0]
+            enc = self.encode(self.p, np.arange(I))
+            xs, als = [], []
+            for u in range(self.p["Gu"].shape[0]):
+                x, al = self.score(self.p, self.p["Gu"][u].unsqueeze(0).expand(I, -1), self.p["Gi"], enc)
+                xs.append(x); als.append(al)
+            return torch.stack(xs), torch.stack(als)
+
+    # ---- train_step (AttentiveFashion.py:211-258) ---------------------------------------------------------------------------
+    def grads(self, batch, masks):
+        u, i, j = (torch.as_tensor(np.asarray(b)).long() for b in batch)
+        B = u.numel()
+        leaves = {n: v.clone().requires_grad_(True) for n, v in self.p.items()}
+        mp = None if masks is None else tuple(m[:B] for m in masks)
+        mn = None if masks is None else tuple(m[B:] for m in masks)
+        xp, _, ep = self.call(u, i, mp, leaves)
+        xn, _, en = self.call(u, j, mn, leaves)
+        res = torch.clamp(xp - xn, -80.0, 1e8)
+        loss = Fn.softplus(-res).sum()
+        reg = (leaves["Gu"][u] ** 2).sum() + (leaves["Gi"][i] ** 2).sum() + (leaves["Gi"][j] ** 2).sum()
+        reg = reg + sum((e ** 2).sum() for e in ep + en)
+        reg = reg + sum((leaves[n] ** 2).sum() for n in AF_WEIGHTS[9:])
+        loss = loss + self.reg * reg                                                 # reg * sum(l2_loss) * 2
+        g = torch.autograd.grad(loss, list(leaves.values()), allow_unused=True)
+        return loss.item(), {n: (torch.zeros_like(self.p[n]) if gr is None else gr) for n, gr in zip(leaves, g)}
+
+    def step(self, batch, masks, optimizer="sgd", lr=0.01):
+        loss, g = self.grads(batch, masks)
+        self.t += 1
+        if optimizer == "sgd":
+            for n in self.p:
+                self.p[n] = self.p[n] - lr * g[n]
+            return loss
+        lr_t = lr * np.sqrt(1.0 - B2 ** self.t) / (1.0 - B1 ** self.t)
+        for n in self.p:
+            m, v = self.slots.get("m_" + n, torch.zeros_like(self.p[n])), self.slots.get("v_" + n, torch.zeros_like(self.p[n]))
+            if n in SPARSE:
+                m = m * B1 + g[n] * (1 - B1)
+                v = v * B2 + g[n] * g[n] * (1 - B2)
+            else:
+                m = m + (g[n] - m) * (1 - B1)
+                v = v + (g[n] * g[n] - v) * (1 - B2)
+            self.slots["m_" + n], self.slots["v_" + n] = m, v
+            self.p[n] = self.p[n] - lr_t * m / (torch.sqrt(v) + EPS)
+        return loss
+
+
+def random_tables(rs, U, I, k, Dc, Dk, h, bias=True):
+    """Tables with the reference's initialiser magnitudes (Glorot-uniform encoders and attention; Gu / Gi Glorot-sized so that scores
+    are not vanishing); `bias`: random non-zero Keras biases instead of the zero initialiser."""
+    from fashionvisualexpl_recommend_amd.synth import glorot_uniform
+    g1 = lambda n: rs.uniform(-np.sqrt(3.0 / n), np.sqrt(3.0 / n), size=n).astype(np.float32)
+    kb = (lambda n: rs.uniform(-0.05, 0.05, size=n).astype(np.float32)) if bias else (lambda n: np.zeros(n, np.float32))
+    lim = np.sqrt(6.0 / (25 + 25 * 64))
+    return {"Gu": glorot_uniform(rs, U, k), "Gi": glorot_uniform(rs, I, k), "Bi": np.zeros(I, np.float32),
+            "color.W1": glorot_uniform(rs, Dc, 256), "color.b1": kb(256), "color.W2": glorot_uniform(rs, 256, k),
+            "edges.conv": rs.uniform(-lim, lim, size=(25, 64)).astype(np.float32), "edges.conv_b": kb(64),
+            "edges.W2": glorot_uniform(rs, 64, k),
+            "class.W1": glorot_uniform(rs, Dk, 256), "class.b1": kb(256), "class.W2": glorot_uniform(rs, 256, k),
+            "attention.W_1": glorot_uniform(rs, k, h), "attention.b_1": g1(h), "attention.W_2": glorot_uniform(rs, h, 1),
+            "attention.b_2": g1(1)}
+
+
+def random_inputs(rs, I, Dc, Dk):
+    """edges uint8 [I, 224, 224]: item 0 blank, item 1 dense noise, the rest sparse random strokes upsampled to grey levels;
+    colour histograms divided by their own max-abs; one-hot classes."""
+    edges = np.zeros((I, 224, 224), np.uint8)
+    for i in range(I):
+        if i == 0:
+            continue
+        if i == 1:
+            edges[i] = rs.randint(0, 256, size=(224, 224))
+            continue
+        a = (rs.random_sample((28, 28)) < 0.15).astype(np.float32)
+        t = Fn.interpolate(torch.tensor(a)[None, None], size=224, mode="bicubic").clamp(0, 1)
+        edges[i] = (t[0, 0] * 255).round().numpy().astype(np.uint8)
+    color = (rs.random_sample((I, Dc)) * 50).astype(np.float32)
+    color = color / np.abs(color).max(1, keepdims=True)
+    cls = np.zeros((I, Dk), np.float32)
+    cls[np.arange(I), rs.randint(Dk, size=I)] = 1.0
+    return edges, color, cls
