@@ -18,6 +18,7 @@ FLAG_ADAM_SWEEP, FLAG_ADAM_LAZY = 8, 16
 MODEL = {"bprmf": 0, "vbpr": 1}
 OPTIMIZER = {"sgd": 0, "adam_tf23": 1}
 FEAT_DTYPE = {"fp32": 0, "bf16": 1, "fp8": 2}
+E_INVALID, E_STATE = -1, -2
 E_RANGE = -4
 PHASES = ["cast_Et", "proj_fwd", "triplet_grad", "proj_bwd", "reduce_parts", "apply", "dense_update", "loss_reduce", "item_seg", "seg_alloc", "row_count", "adam_catchup"]
 
@@ -47,6 +48,9 @@ class Factored(C.Structure):
 
 ACF_WEIGHTS = ["component.W_0_u", "component.W_0_i", "component.b_0", "component.W_1", "component.b_1",
                "item.W_0_u", "item.W_0_iv", "item.W_0_ip", "item.W_0_ix", "item.b_0", "item.W_1", "item.b_1"]    # the order of bprx_acf.w (include/bprx.h, BPRX_ACF_*)
+
+
+ACF_GRADIENT = {"detached": 0, "full": 1}    # BPRX_ACF_GRAD_* (include/bprx.h)
 
 
 class Acf(C.Structure):
@@ -103,6 +107,8 @@ def lib():
         "bprx_explain_pairs": (C.c_int, [vp, vp, vp, i64, vp, vp]),
         "bprx_bind_acf": (C.c_int, [vp, C.POINTER(Tables), C.POINTER(Acf)]),
         "bprx_acf_profiles": (C.c_int, [vp, vp, i64, vp, vp, vp, vp]),
+        "bprx_acf_set_gradient": (C.c_int, [vp, C.c_int]),
+        "bprx_acf_get_gradient": (C.c_int, [vp]),
         "bprx_bind_attentive": (C.c_int, [vp, C.POINTER(Tables), C.POINTER(Attentive)]),
         "bprx_af_encode": (C.c_int, [vp, vp, i64, vp, vp]),
         "bprx_af_attention_pairs": (C.c_int, [vp, vp, vp, i64, vp, vp, vp]),
@@ -176,7 +182,7 @@ def lib():
     return L
 
 
-EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error", "bprx_bind_tables", "bprx_bind_factored", "bprx_explain_pairs", "bprx_bind_acf", "bprx_acf_profiles", "bprx_bind_attentive", "bprx_af_encode", "bprx_af_attention_pairs",
+EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error", "bprx_bind_tables", "bprx_bind_factored", "bprx_explain_pairs", "bprx_bind_acf", "bprx_acf_profiles", "bprx_acf_set_gradient", "bprx_acf_get_gradient", "bprx_bind_attentive", "bprx_af_encode", "bprx_af_attention_pairs",
            "bprx_af_score_block", "bprx_af_dropout_mask", "bprx_af_get_step", "bprx_af_set_step", "bprx_set_hyper", "bprx_tables_dirty",
            "bprx_set_adam_step", "bprx_get_adam_step", "bprx_adam_is_lazy", "bprx_sync_adam", "bprx_score_pairs", "bprx_step", "bprx_step_begin",
            "bprx_step_begin_sparse", "bprx_step_begin_dense", "bprx_sum_dense_parts",

@@ -16,6 +16,16 @@
 //                   summation order)
 //   k_acf_apply_sgd / k_acf_sweep   sgd on the touched rows / adam_tf23's sparse rule over the whole tables (adam_elem)
 //   k_acf_finish    clears the user slots and the sgd claim marks
+// With bprx_acf_set_gradient(h, BPRX_ACF_GRAD_FULL) a step also differentiates through g'_u (include/bprx.h), between
+// k_acf_triplet and k_acf_dense:
+//   k_acf_q         q_u = dL/dg'_u per distinct user (row = the user's first batch position)
+//   k_acf_user_bwd  one workgroup per distinct user: recomputes both attention levels per history item and adds dZ, dGP, dPi rows
+//                   (float atomics), writes dGu_u and the user's [duc | dui | dW1c | dW1i] row
+//   k_acf_item_bwd  dGi_l += Wiv dGP_l, dPi_l += Wip dGP_l per listed item
+//   k_acf_outer     sum_r R[r] (x) V[r] in split-K partials (dWcu | dWiu over the users, dWiv / dWip over the listed items);
+//   k_acf_colsum    column sums of the user rows (dbc0, dbi0, dW1c, dW1i); k_acf_reduce sums partials in ascending order
+//   k_acf_proj_bwd_*  [dWci | dWix] = F^T dZ over the rows (l, m) of the listed items: MFMA GEMM, K split over the workgroups
+//   k_acf_clear     dZ / dGP rows of the listed items back to zero
 #include <climits>
 
 #include "bprx_internal.h"
@@ -42,6 +52,18 @@ struct AcfState {
   int32_t *imark;                     // [I]         item listed in this call; 0 between calls
   int32_t *ilist, *nlist;             // [I], [1]
   bool eval_valid;                    // Gup matches the bound tables
+  // full-gradient mode (bprx_acf_set_gradient), allocated at the first switch to BPRX_ACF_GRAD_FULL
+  int grad_mode;
+  float *dZ;                          // [I][M][NP]  gradient of Z, all-zero between steps
+  float *dGP;                         // [I][a]      gradient of GP, all-zero between steps
+  float *q;                           // [max_batch][k]        dL/dg'_u at the user's first position
+  float *aux;                         // [max_batch][k+2]      k_acf_user: sum_l alpha_l Pi_l, the item softmax's max and denominator
+  float *UV;                          // [max_batch][2(h+a)]   per user [duc | dui | dW1c | dW1i]
+  float *part;                        // split-K partials (part_floats)
+  float *gw[BPRX_ACF_NW];             // gradients of the attention tensors (b_1 of both levels: nullptr, identically zero)
+  float *gwbuf;
+  size_t part_floats;
+  int nsplit_proj;
 };
 
 __device__ __forceinline__ int acf_clamp(int v, int n, int32_t *errflag, int code) {
@@ -298,8 +320,11 @@ struct AcfUserArgs {
 //   s_m = w1c.relu(uc + Z_lm[:h]) + bc1 (lane per m), beta = softmax_m(s), xz = sum_m beta_m Z_lm[h:] (lane per column),
 //   t = w1i.relu(ui + GP_l + xz) + bi1; the wave keeps a running max / denominator / sum of e^(t - max) Pi_l.
 // LDS: gu[k] uc[h] ui[a] w1c[h] w1i[a] | per wave: beta[M], acc[k] | wmx[4] wden[4]
+// AUX (full-gradient mode): also store what k_acf_user_bwd needs of the forward; <false> is the detached step's kernel unchanged
+template <bool AUX>
 __global__ __launch_bounds__(256) void k_acf_user(AcfUserArgs A, const int32_t *__restrict__ users, int64_t n,
-                                                  const int32_t *__restrict__ uslot, float *__restrict__ out) {
+                                                  const int32_t *__restrict__ uslot, float *__restrict__ out,
+                                                  float *__restrict__ aux) {
   extern __shared__ float sm[];
   const int64_t b = blockIdx.x;
   if (b >= n) return;
@@ -386,6 +411,11 @@ __global__ __launch_bounds__(256) void k_acf_user(AcfUserArgs A, const int32_t *
     for (int q = 0; q < 4; ++q)
       if (f[q] != 0.f) s += wbase[(size_t)q * (M + k) + M + c] * f[q];
     out[b * k + c] = D > 0.f ? gu[c] + s / D : gu[c];
+    if (AUX) aux[b * (k + 2) + c] = D > 0.f ? s / D : 0.f;   // sum_l alpha_l Pi_l
+  }
+  if (AUX && tid == 0) {                                     // the item softmax's max and denominator
+    aux[b * (k + 2) + k] = gm;
+    aux[b * (k + 2) + k + 1] = D;
   }
 }
 
@@ -445,9 +475,11 @@ __global__ __launch_bounds__(256) void k_acf_triplet(AcfStepArgs A, const int32_
   }
 }
 
-// The attention tensors (gradient 2 reg w only) and the step's loss, in ONE workgroup: fixed summation order.
+// The attention tensors (gradient 2 reg w, plus T.g in full-gradient mode) and the step's loss, in ONE workgroup: fixed
+// summation order.
 struct AcfDenseArgs {
   float *w[BPRX_ACF_NW], *m[BPRX_ACF_NW], *v[BPRX_ACF_NW];
+  const float *g[BPRX_ACF_NW];                                // full-gradient mode; nullptr: the gradient is 2 reg w alone
   int64_t n[BPRX_ACF_NW];
 };
 __global__ __launch_bounds__(1024) void k_acf_dense(AcfDenseArgs T, int adam, float lr_t, float reg, float b1, float b2, float eps,
@@ -457,8 +489,11 @@ __global__ __launch_bounds__(1024) void k_acf_dense(AcfDenseArgs T, int adam, fl
   double sq = 0.0, ls = 0.0;
   for (int q = 0; q < BPRX_ACF_NW; ++q) {
     float *p = T.w[q];
+    const float *gq = T.g[q];
     for (int64_t e = threadIdx.x; e < T.n[q]; e += 1024) {
-      const float pv = p[e], g = r2 * pv;
+      const float pv = p[e];
+      float g = r2 * pv;
+      if (gq) g += gq[e];
       sq += (double)pv * (double)pv;
       if (adam) {                                            // TF-2.3 dense ApplyAdam (as k_dense_update / k_fact_update)
         const float mo = T.m[q][e], vo = T.v[q][e];
@@ -557,6 +592,521 @@ __global__ void k_acf_fill(int32_t *p, size_t n, int32_t v) {
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) p[e] = v;
 }
 
+// ---- full-gradient mode: the backward through g'_u ------------------------------------------------------------------
+// q_u = sum_{b: user_b = u} c_b (Gi_i - Gi_j), c_b = -sigmoid(-d_b) inside the clip range: one wave per triplet, the row of the
+// user's first position
+__global__ __launch_bounds__(256) void k_acf_q(AcfStepArgs A, const int32_t *__restrict__ user, const int32_t *__restrict__ pos,
+                                               const int32_t *__restrict__ neg, int64_t B, float *__restrict__ q) {
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (b >= B) return;
+  const int u = acf_clamp(user[b], A.U, A.errflag, 1), i = acf_clamp(pos[b], A.I, A.errflag, 2),
+            j = acf_clamp(neg[b], A.I, A.errflag, 2);
+  const int k = A.k;
+  const int64_t row = A.uslot[u];
+  const float *g = A.gp + row * k, *gi = A.Gi + (int64_t)i * k, *gj = A.Gi + (int64_t)j * k;
+  float xp = 0.f, xn = 0.f;
+  for (int c = lane; c < k; c += 64) {
+    xp = fmaf(g[c], gi[c], xp);
+    xn = fmaf(g[c], gj[c], xn);
+  }
+  xp = wave_sum(xp); xn = wave_sum(xn);
+  const float diff = xp - xn;
+  const bool inr = (diff >= -80.0f) && (diff <= 1e8f);
+  if (!inr) return;
+  const float gd = -1.0f / (1.0f + expf(diff));
+  for (int c = lane; c < k; c += 64) atomicAdd(q + row * k + c, gd * (gi[c] - gj[c]));
+}
+
+struct AcfBwdArgs {
+  const float *q, *aux;               // [B][k], [B][k+2]
+  float *dZ, *dGP, *dPi, *dGu, *UV;
+};
+
+#define ACF_JR 4                      // column slots per lane: h, a <= ACF_MAX_NP = 4 * 64
+
+// One workgroup (4 waves) per distinct user, at the user's first position b.  Wave w walks history entries w, w+4, ... and
+// recomputes beta_l, pre_l and t_l as k_acf_user does; alpha_l = e^(t_l - max) / den comes from the forward's aux row, and
+// sum_l alpha_l Pi_l . q from its stored attention part.  Per entry: dt, dpre (dGP_l, dPi_l by atomics), dbeta, ds, then a pass
+// over the M rows with a lane per column adds dZ_lm.  The per-lane column sums (duc, dui, dW1c, dW1i) are merged over the waves
+// in a fixed order into the user's UV row; dGu_u += q + Wcu duc + Wiu dui.
+// LDS: gu[k] q[k] uc[h] ui[a] w1c[h] w1i[a] | per wave: beta[M] dbeta[M] dpre[a] | red[4][2(h+a)] fin[2(h+a)] rb[4]
+__global__ __launch_bounds__(256) void k_acf_user_bwd(AcfUserArgs A, AcfBwdArgs G, const int32_t *__restrict__ users, int64_t n,
+                                                      const int32_t *__restrict__ uslot) {
+  extern __shared__ float sm[];
+  const int64_t b = blockIdx.x;
+  if (b >= n) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int u = acf_clamp(users[b], A.U, A.errflag, 1);
+  if (uslot[u] != (int32_t)b) return;
+  const int k = A.k, M = A.M, hc = A.hc, ha = A.ha, NP = A.NP, W2 = 2 * (hc + ha);
+  float *gu = sm, *qs = gu + k, *uc = qs + k, *ui = uc + hc, *w1c = ui + ha, *w1i = w1c + hc;
+  float *wbase = w1i + ha;
+  const size_t wstride = 2 * (size_t)M + ha;
+  float *beta = wbase + (size_t)w * wstride, *dbeta = beta + M, *dpre = dbeta + M;
+  float *red = wbase + 4 * wstride, *fin = red + 4 * (size_t)W2, *rb = fin + W2;
+  const float *aux = G.aux + b * (k + 2);
+  for (int c = tid; c < k; c += 256) {
+    gu[c] = A.Gu[(int64_t)u * k + c];
+    qs[c] = G.q[b * k + c];
+  }
+  for (int j = tid; j < hc; j += 256) w1c[j] = A.w1c[j];
+  for (int j = tid; j < ha; j += 256) w1i[j] = A.w1i[j];
+  __syncthreads();
+  for (int j = tid; j < hc + ha; j += 256) {                 // as k_acf_user
+    float s = 0.f;
+    if (j < hc) {
+      for (int c = 0; c < k; ++c) s = fmaf(gu[c], A.wcu[(int64_t)c * hc + j], s);
+      uc[j] = s + A.bc0[j];
+    } else {
+      const int jj = j - hc;
+      for (int c = 0; c < k; ++c) s = fmaf(gu[c], A.wiu[(int64_t)c * ha + jj], s);
+      ui[jj] = s + A.bi0[jj];
+    }
+  }
+  {
+    float pr = 0.f;
+    for (int c = tid; c < k; c += 256) pr = fmaf(aux[c], qs[c], pr);
+    pr = wave_sum(pr);
+    if (lane == 0) rb[w] = pr;
+  }
+  __syncthreads();
+  const float rbar = (rb[0] + rb[1]) + (rb[2] + rb[3]);      // sum_l alpha_l Pi_l . q
+  const float gm = aux[k], D = aux[k + 1];
+  const float bc1 = A.bc1[0], bi1 = A.bi1[0];
+  float duc_r[ACF_JR], dw1c_r[ACF_JR], dui_r[ACF_JR], dw1i_r[ACF_JR];
+#pragma unroll
+  for (int i = 0; i < ACF_JR; ++i) duc_r[i] = dw1c_r[i] = dui_r[i] = dw1i_r[i] = 0.f;
+  const int64_t beg = A.ptr[u], end = A.ptr[u + 1];
+  if (D > 0.f) {
+    int run_l = -1;
+    float run_a = 0.f;
+    for (int64_t p = beg + w; p < end; p += 4) {
+      const int l = acf_clamp(A.items[p], A.I, A.errflag, 5);
+      const float *Zl = A.Z + (int64_t)l * M * NP;
+      float lmax = -INFINITY;
+      for (int m = lane; m < M; m += 64) {                   // component scores, as k_acf_user
+        const float *z = Zl + (int64_t)m * NP;
+        float s = 0.f;
+        for (int j = 0; j < hc; ++j) s = fmaf(w1c[j], fmaxf(uc[j] + z[j], 0.f), s);
+        s += bc1;
+        beta[m] = s;
+        lmax = fmaxf(lmax, s);
+      }
+      lmax = wave_max(lmax);
+      wave_sync();
+      float lsum = 0.f;
+      for (int m = lane; m < M; m += 64) {
+        const float e = expf(beta[m] - lmax);
+        beta[m] = e;
+        lsum += e;
+      }
+      lsum = wave_sum(lsum);
+      wave_sync();
+      const float inv = 1.0f / lsum;
+      float prej[ACF_JR], tp = 0.f;
+#pragma unroll
+      for (int i = 0; i < ACF_JR; ++i) {
+        const int j = lane + 64 * i;
+        prej[i] = 0.f;
+        if (j < ha) {
+          float xz = 0.f;
+          for (int m = 0; m < M; ++m) xz = fmaf(beta[m], Zl[(int64_t)m * NP + hc + j], xz);
+          prej[i] = ui[j] + A.GP[(int64_t)l * ha + j] + xz * inv;
+          tp = fmaf(w1i[j], fmaxf(prej[i], 0.f), tp);
+        }
+      }
+      const float t = wave_sum(tp) + bi1;
+      const float alpha = expf(t - gm) / D;
+      const float *pl = A.Pi + (int64_t)l * k;
+      float r = 0.f;
+      for (int c = lane; c < k; c += 64) r = fmaf(pl[c], qs[c], r);
+      r = wave_sum(r);
+      const float dt = alpha * (r - rbar);
+      // dPi_l += alpha_l q: entries of one item that follow each other in this wave's walk (sorted histories with repeats)
+      // are summed first -- hundreds of small adds onto a row that already holds a large term would each round at that
+      // term's ulp, all in the same direction
+      if (l != run_l) {
+        if (run_l >= 0)
+          for (int c = lane; c < k; c += 64) atomicAdd(G.dPi + (int64_t)run_l * k + c, run_a * qs[c]);
+        run_l = l;
+        run_a = 0.f;
+      }
+      run_a += alpha;
+#pragma unroll
+      for (int i = 0; i < ACF_JR; ++i) {
+        const int j = lane + 64 * i;
+        if (j < ha) {
+          const float dp = prej[i] > 0.f ? dt * w1i[j] : 0.f;
+          dpre[j] = dp;
+          dui_r[i] += dp;
+          dw1i_r[i] = fmaf(dt, fmaxf(prej[i], 0.f), dw1i_r[i]);
+          if (dp != 0.f) atomicAdd(G.dGP + (int64_t)l * ha + j, dp);
+        }
+      }
+      wave_sync();
+      float bsum = 0.f;
+      for (int m = lane; m < M; m += 64) {                   // dbeta_lm = Z_lm[h:] . dpre_l
+        const float *z = Zl + (int64_t)m * NP + hc;
+        float d = 0.f;
+        for (int j = 0; j < ha; ++j) d = fmaf(z[j], dpre[j], d);
+        const float bn = beta[m] * inv;
+        beta[m] = bn;
+        bsum = fmaf(bn, d, bsum);
+        dbeta[m] = d;
+      }
+      bsum = wave_sum(bsum);
+      for (int m = lane; m < M; m += 64) dbeta[m] = beta[m] * (dbeta[m] - bsum);      // ds_lm (the lane's own entries)
+      wave_sync();
+      float *dZl = G.dZ + (int64_t)l * M * NP;
+      for (int m = 0; m < M; ++m) {                           // a lane per column
+        const float ds = dbeta[m], bn = beta[m];
+        const float *z = Zl + (int64_t)m * NP;
+        float *dz = dZl + (int64_t)m * NP;
+#pragma unroll
+        for (int i = 0; i < ACF_JR; ++i) {
+          const int j = lane + 64 * i;
+          if (j < hc) {
+            const float a = uc[j] + z[j];
+            if (a > 0.f) {
+              const float da = ds * w1c[j];
+              atomicAdd(dz + j, da);
+              duc_r[i] += da;
+              dw1c_r[i] = fmaf(ds, a, dw1c_r[i]);
+            }
+          }
+          if (j < ha) {
+            const float v = bn * dpre[j];
+            if (v != 0.f) atomicAdd(dz + hc + j, v);
+          }
+        }
+      }
+      wave_sync();                                             // beta / dbeta / dpre are rewritten by the next entry
+    }
+    if (run_l >= 0)
+      for (int c = lane; c < k; c += 64) atomicAdd(G.dPi + (int64_t)run_l * k + c, run_a * qs[c]);
+  }
+#pragma unroll
+  for (int i = 0; i < ACF_JR; ++i) {
+    const int j = lane + 64 * i;
+    if (j < hc) {
+      red[(size_t)w * W2 + j] = duc_r[i];
+      red[(size_t)w * W2 + hc + ha + j] = dw1c_r[i];
+    }
+    if (j < ha) {
+      red[(size_t)w * W2 + hc + j] = dui_r[i];
+      red[(size_t)w * W2 + 2 * hc + ha + j] = dw1i_r[i];
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < W2; e += 256) {
+    const float v = (red[e] + red[(size_t)W2 + e]) + (red[2 * (size_t)W2 + e] + red[3 * (size_t)W2 + e]);
+    fin[e] = v;
+    G.UV[b * W2 + e] = v;
+  }
+  __syncthreads();
+  for (int c = tid; c < k; c += 256) {
+    float s = qs[c];
+    for (int j = 0; j < hc; ++j) s = fmaf(A.wcu[(int64_t)c * hc + j], fin[j], s);
+    for (int j = 0; j < ha; ++j) s = fmaf(A.wiu[(int64_t)c * ha + j], fin[hc + j], s);
+    G.dGu[(int64_t)u * k + c] += s;
+  }
+}
+
+// dGi_l += Wiv dGP_l, dPi_l += Wip dGP_l: one wave per listed item (the row belongs to that wave alone in this kernel)
+__global__ __launch_bounds__(256) void k_acf_item_bwd(const float *__restrict__ Wiv, const float *__restrict__ Wip,
+                                                      const float *__restrict__ dGP, const int32_t *__restrict__ list,
+                                                      const int32_t *__restrict__ nlist, int k, int ha, float *dGi, float *dPi) {
+  __shared__ float dv[4][ACF_MAX_NP];
+  const int n = *nlist, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int t = blockIdx.x * 4 + w; t < n; t += gridDim.x * 4) {
+    const int64_t l = list[t];
+    for (int j = lane; j < ha; j += 64) dv[w][j] = dGP[l * ha + j];
+    wave_sync();
+    for (int c = lane; c < k; c += 64) {
+      float sv = 0.f, sp = 0.f;
+      for (int j = 0; j < ha; ++j) {
+        sv = fmaf(Wiv[(int64_t)c * ha + j], dv[w][j], sv);
+        sp = fmaf(Wip[(int64_t)c * ha + j], dv[w][j], sp);
+      }
+      dGi[l * k + c] += sv;
+      dPi[l * k + c] += sp;
+    }
+    wave_sync();
+  }
+}
+
+// part[split][k][W] = sum over this split's rows r of R[ridx_r][:] (x) V[vidx_r][:].  Rows: the listed items (ridx = vidx = the
+// item) or, with list == nullptr, the batch positions that own their user (ridx = user, vidx = position).  64 x 64 output tile
+// per workgroup, 4 x 4 per thread, 16 rows per LDS stage.
+struct AcfOuter {
+  const float *R, *V;
+  int ldv, W, k, U;
+  int64_t B;
+  const int32_t *user, *uslot, *list, *nlist;
+};
+__global__ __launch_bounds__(256) void k_acf_outer(AcfOuter O, float *__restrict__ part) {
+  __shared__ float Rs[16][64], Vs[16][64];
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int tilesj = (O.W + 63) / 64, tj = blockIdx.x % tilesj, tc = blockIdx.x / tilesj;
+  const int64_t n = O.list ? (int64_t)*O.nlist : O.B;
+  float acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+  for (int64_t r0 = (int64_t)blockIdx.y * 16; r0 < n; r0 += (int64_t)gridDim.y * 16) {
+    for (int e = tid; e < 1024; e += 256) {
+      const int rr = e >> 6, cc = e & 63;
+      const int64_t r = r0 + rr;
+      int64_t ridx = -1, vidx = -1;
+      if (r < n) {
+        if (O.list) {
+          ridx = vidx = O.list[r];
+        } else {
+          int u = O.user[r];
+          u = u < 0 ? 0 : (u >= O.U ? O.U - 1 : u);
+          if (O.uslot[u] == (int32_t)r) { ridx = u; vidx = r; }
+        }
+      }
+      const int c = tc * 64 + cc, j = tj * 64 + cc;
+      Rs[rr][cc] = (ridx >= 0 && c < O.k) ? O.R[ridx * O.k + c] : 0.f;
+      Vs[rr][cc] = (ridx >= 0 && j < O.W) ? O.V[vidx * O.ldv + j] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int rr = 0; rr < 16; ++rr) {
+      float a[4], v[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { a[i] = Rs[rr][ty * 4 + i]; v[i] = Vs[rr][tx * 4 + i]; }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], v[j], acc[i][j]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int c = tc * 64 + ty * 4 + i;
+    for (int j = 0; j < 4; ++j) {
+      const int col = tj * 64 + tx * 4 + j;
+      if (c < O.k && col < O.W) part[((int64_t)blockIdx.y * O.k + c) * O.W + col] = acc[i][j];
+    }
+  }
+}
+
+// part[split][W2] = column sums of the UV rows of this split's owner positions
+__global__ __launch_bounds__(256) void k_acf_colsum(const float *__restrict__ UV, int W2, const int32_t *__restrict__ user,
+                                                    const int32_t *__restrict__ uslot, int U, int64_t B, float *__restrict__ part) {
+  for (int e = threadIdx.x; e < W2; e += 256) {
+    float s = 0.f;
+    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+      int u = user[b];
+      u = u < 0 ? 0 : (u >= U ? U - 1 : u);
+      if (uslot[u] == (int32_t)b) s += UV[b * W2 + e];
+    }
+    part[(int64_t)blockIdx.x * W2 + e] = s;
+  }
+}
+
+// out = sum_s part[s] in ascending s; element (c, j) of the [rows][ld] partial goes to out0[c][j] (j < w0) or out1[c][j - w0]
+__global__ __launch_bounds__(256) void k_acf_reduce(const float *__restrict__ part, int nsplit, int64_t sstride, int rows, int ld,
+                                                    float *__restrict__ out0, int w0, float *__restrict__ out1, int w1) {
+  const int64_t n = (int64_t)rows * ld;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t c = e / ld;
+    const int j = (int)(e - c * ld);
+    if (j >= w0 + w1) continue;
+    float s = 0.f;
+    for (int q = 0; q < nsplit; ++q) s += part[(int64_t)q * sstride + e];
+    if (j < w0) out0[c * w0 + j] = s;
+    else out1[c * w1 + (j - w0)] = s;
+  }
+}
+
+// ---- [dWci | dWix] = F^T dZ over the rows (l, m) of the listed items ---------------------------------------------------
+// Workgroup (x, y, z): feature columns [128 x, 128 x + 128), K split y of gridDim.y (row chunks of 32: y, y + gridDim.y, ...),
+// output column tiles [NB z, NB z + NB).  Wave w owns the 32 feature columns 128 x + 32 w.  part[y][Crows][NP].
+__device__ __forceinline__ void acf_bwd_store(float *__restrict__ part, const f32x16 &acc, int64_t base, int NP, int col, int lane) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    part[(base + row) * NP + col + (lane & 31)] = acc[r];
+  }
+}
+
+template <int NB>
+__global__ __launch_bounds__(256) void k_acf_proj_bwd_f32(const float *__restrict__ F, const float *__restrict__ dZ,
+                                                          float *__restrict__ part, const int32_t *__restrict__ list,
+                                                          const int32_t *__restrict__ nlist, int M, int C, int NP, int Crows) {
+  constexpr int LDA = 128 + 32, LDB = NB * 32 + 32;           // rows k and k + 1 of an operand pair fall into disjoint banks
+  __shared__ __attribute__((aligned(16))) float As[32][LDA];
+  __shared__ __attribute__((aligned(16))) float Bs[32][LDB];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int c0 = blockIdx.x * 128, col0 = blockIdx.z * NB * 32;
+  const int nb = min(NB, NP / 32 - (int)blockIdx.z * NB);
+  const int64_t nrows = (int64_t)*nlist * M, nchunks = (nrows + 31) / 32;
+  f32x16 acc[NB];
+#pragma unroll
+  for (int j = 0; j < NB; ++j)
+    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+  for (int64_t chunk = blockIdx.y; chunk < nchunks; chunk += gridDim.y) {
+    const int64_t r0 = chunk * 32;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int idx = tid + 256 * q, row = idx >> 5, c4 = idx & 31;
+      const int64_t gr = r0 + row;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      const int col = c0 + c4 * 4;
+      if (gr < nrows && col < C) {
+        const int64_t li = gr / M;
+        v = *(const float4 *)(F + ((int64_t)list[li] * M + (gr - li * M)) * C + col);
+      }
+      *(float4 *)&As[row][c4 * 4] = v;
+    }
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+      const int idx = tid + 256 * q, row = idx / (NB * 8), c4 = idx % (NB * 8);
+      const int64_t gr = r0 + row;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      const int col = col0 + c4 * 4;
+      if (gr < nrows && col < NP) {
+        const int64_t li = gr / M;
+        v = *(const float4 *)(dZ + ((int64_t)list[li] * M + (gr - li * M)) * NP + col);
+      }
+      *(float4 *)&Bs[row][c4 * 4] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < 32; kk += 2) {
+      const float a = As[kk + (lane >> 5)][w * 32 + (lane & 31)];
+#pragma unroll
+      for (int j = 0; j < NB; ++j)
+        if (j < nb) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, Bs[kk + (lane >> 5)][j * 32 + (lane & 31)], acc[j], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int j = 0; j < NB; ++j)
+    if (j < nb) acf_bwd_store(part, acc[j], (int64_t)blockIdx.y * Crows + c0 + w * 32, NP, col0 + j * 32, lane);
+}
+
+// bf16 features: A = F^T (bf16, exact), B = dZ as three bf16 terms (24 bits: only the features are rounded), fp32 accumulation.
+// Both operands are staged transposed ([column][row]) so that a lane reads its 8 consecutive K entries as one 16-byte word.
+template <int NB>
+__global__ __launch_bounds__(256) void k_acf_proj_bwd_bf16(const uint16_t *__restrict__ F, const float *__restrict__ dZ,
+                                                           float *__restrict__ part, const int32_t *__restrict__ list,
+                                                           const int32_t *__restrict__ nlist, int M, int C, int NP, int Crows) {
+  __shared__ __attribute__((aligned(16))) uint16_t At[128][40];
+  __shared__ __attribute__((aligned(16))) uint16_t Bh[NB * 32][40];
+  __shared__ __attribute__((aligned(16))) uint16_t Bm[NB * 32][40];
+  __shared__ __attribute__((aligned(16))) uint16_t Bl[NB * 32][40];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int c0 = blockIdx.x * 128, col0 = blockIdx.z * NB * 32;
+  const int nb = min(NB, NP / 32 - (int)blockIdx.z * NB);
+  const int64_t nrows = (int64_t)*nlist * M, nchunks = (nrows + 31) / 32;
+  f32x16 acc[NB];
+#pragma unroll
+  for (int j = 0; j < NB; ++j)
+    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+  for (int64_t chunk = blockIdx.y; chunk < nchunks; chunk += gridDim.y) {
+    const int64_t r0 = chunk * 32;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int idx = tid + 256 * q, row = idx >> 4, c8 = idx & 15;
+      const int64_t gr = r0 + row;
+      uint4 v = make_uint4(0u, 0u, 0u, 0u);
+      const int col = c0 + c8 * 8;
+      if (gr < nrows && col < C) {
+        const int64_t li = gr / M;
+        v = *(const uint4 *)(F + ((int64_t)list[li] * M + (gr - li * M)) * C + col);
+      }
+      const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        At[c8 * 8 + 2 * i][row] = (uint16_t)(wd[i] & 0xffffu);
+        At[c8 * 8 + 2 * i + 1][row] = (uint16_t)(wd[i] >> 16);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+      const int idx = tid + 256 * q, row = idx / (NB * 8), c4 = idx % (NB * 8);
+      const int64_t gr = r0 + row;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      const int col = col0 + c4 * 4;
+      if (gr < nrows && col < NP) {
+        const int64_t li = gr / M;
+        v = *(const float4 *)(dZ + ((int64_t)list[li] * M + (gr - li * M)) * NP + col);
+      }
+      const float x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const uint16_t hi = bf16_rne(x[i]);
+        const float r1 = x[i] - __uint_as_float((uint32_t)hi << 16);
+        const uint16_t mi = bf16_rne(r1);
+        const float r2 = r1 - __uint_as_float((uint32_t)mi << 16);
+        Bh[c4 * 4 + i][row] = hi;
+        Bm[c4 * 4 + i][row] = mi;
+        Bl[c4 * 4 + i][row] = bf16_rne(r2);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int ko = ks * 16 + 8 * (lane >> 5);
+      const bf16x8 a = *(const bf16x8 *)&At[w * 32 + (lane & 31)][ko];
+#pragma unroll
+      for (int j = 0; j < NB; ++j)
+        if (j < nb) {
+          const bf16x8 bh = *(const bf16x8 *)&Bh[j * 32 + (lane & 31)][ko];
+          const bf16x8 bm = *(const bf16x8 *)&Bm[j * 32 + (lane & 31)][ko];
+          const bf16x8 bl = *(const bf16x8 *)&Bl[j * 32 + (lane & 31)][ko];
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bl, acc[j], 0, 0, 0);
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bm, acc[j], 0, 0, 0);
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bh, acc[j], 0, 0, 0);
+        }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int j = 0; j < NB; ++j)
+    if (j < nb) acf_bwd_store(part, acc[j], (int64_t)blockIdx.y * Crows + c0 + w * 32, NP, col0 + j * 32, lane);
+}
+
+// dZ and dGP rows of the listed items back to zero (both are all-zero between steps)
+__global__ __launch_bounds__(256) void k_acf_clear(float *__restrict__ dZ, float *__restrict__ dGP, const int32_t *__restrict__ list,
+                                                   const int32_t *__restrict__ nlist, int64_t zrow, int ha) {
+  const int n = *nlist;
+  for (int t = blockIdx.x; t < n; t += gridDim.x) {
+    const int64_t l = list[t];
+    float4 *z = (float4 *)(dZ + l * zrow);                     // zrow = M * NP, NP % 32 == 0
+    for (int64_t e = threadIdx.x; e < zrow / 4; e += 256) z[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int j = threadIdx.x; j < ha; j += 256) dGP[l * ha + j] = 0.f;
+  }
+}
+
+// sgd, full mode: the Gi / Pi rows of the listed history items move too (one wave per listed item, same claim marks)
+__global__ __launch_bounds__(256) void k_acf_apply_sgd_list(float *Gi, float *Pi, float *dGi, float *dPi, uint32_t *flagI,
+                                                            const int32_t *__restrict__ list, const int32_t *__restrict__ nlist,
+                                                            int k, float lr) {
+  const int n = *nlist, lane = threadIdx.x & 63;
+  for (int t = blockIdx.x * 4 + (threadIdx.x >> 6); t < n; t += gridDim.x * 4) {
+    const int64_t l = list[t];
+    int claim = 0;
+    if (lane == 0) claim = atomicExch(flagI + l, 1u) == 0u;
+    claim = __shfl(claim, 0, 64);
+    if (!claim) continue;
+    for (int c = lane; c < k; c += 64) {
+      Gi[l * k + c] -= lr * dGi[l * k + c]; dGi[l * k + c] = 0.f;
+      Pi[l * k + c] -= lr * dPi[l * k + c]; dPi[l * k + c] = 0.f;
+    }
+  }
+}
+__global__ __launch_bounds__(256) void k_acf_finish_list(const int32_t *__restrict__ list, const int32_t *__restrict__ nlist,
+                                                         uint32_t *flagI) {
+  const int n = *nlist;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) flagI[list[e]] = 0u;
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------
 static unsigned acf_grid(int64_t work, int64_t per_block, int64_t cap) {
   int64_t g = (work + per_block - 1) / per_block;
@@ -627,7 +1177,7 @@ static size_t acf_user_lds(const AcfState *S) {
 }
 
 static int acf_users(bprx_handle *h, const int32_t *users, int64_t n, const int32_t *uslot, const int64_t *ptr,
-                     const int32_t *items, float *out, hipStream_t s) {
+                     const int32_t *items, float *out, hipStream_t s, float *aux = nullptr) {
   AcfState *S = h->acf;
   AcfUserArgs A;
   A.Gu = h->t.Gu; A.Pi = S->a.Pi; A.Z = S->Z; A.GP = S->GP;
@@ -636,8 +1186,104 @@ static int acf_users(bprx_handle *h, const int32_t *users, int64_t n, const int3
   A.ptr = ptr; A.items = items; A.errflag = h->errflag;
   A.U = h->cfg.num_users; A.I = h->cfg.num_items; A.k = S->k; A.M = S->M; A.hc = S->hc; A.ha = S->ha; A.NP = S->NP;
   BprxProfScope ps(h, BPRX_PHASE_TRIPLET, s);
-  hipLaunchKernelGGL(k_acf_user, dim3((unsigned)n), dim3(256), acf_user_lds(S), s, A, users, n, uslot, out);
+  if (aux)
+    hipLaunchKernelGGL(k_acf_user<true>, dim3((unsigned)n), dim3(256), acf_user_lds(S), s, A, users, n, uslot, out, aux);
+  else
+    hipLaunchKernelGGL(k_acf_user<false>, dim3((unsigned)n), dim3(256), acf_user_lds(S), s, A, users, n, uslot, out, aux);
   BPRX_LAUNCH_CHECK(h, "k_acf_user");
+  return BPRX_OK;
+}
+
+
+static size_t acf_user_bwd_lds(const AcfState *S) {
+  const size_t hw = (size_t)S->hc + S->ha;
+  return sizeof(float) * (2 * (size_t)S->k + 2 * hw + 4 * (2 * (size_t)S->M + S->ha) + 5 * 2 * hw + 4);
+}
+
+static int acf_reduce(bprx_handle *h, int nsplit, int64_t sstride, int rows, int ld, float *out0, int w0, float *out1, int w1,
+                      hipStream_t s) {
+  hipLaunchKernelGGL(k_acf_reduce, dim3(acf_grid((int64_t)rows * ld, 256, 1024)), dim3(256), 0, s, h->acf->part, nsplit, sstride,
+                     rows, ld, out0, w0, out1, w1);
+  BPRX_LAUNCH_CHECK(h, "k_acf_reduce");
+  return BPRX_OK;
+}
+
+#define ACF_SPLIT 64                                         // K splits of k_acf_outer / k_acf_colsum
+
+// The gradient through g'_u (include/bprx.h, BPRX_ACF_GRAD_FULL): after k_acf_triplet, before k_acf_dense
+static int acf_backward(bprx_handle *h, const AcfStepArgs &A, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B,
+                        hipStream_t s) {
+  AcfState *S = h->acf;
+  const int U = h->cfg.num_users, I = h->cfg.num_items, k = S->k, hc = S->hc, ha = S->ha, W = hc + ha, W2 = 2 * W;
+  int rc;
+  BPRX_HIP(h, hipMemsetAsync(S->q, 0, (size_t)B * k * sizeof(float), s));
+  {
+    BprxProfScope ps(h, BPRX_PHASE_REDUCE, s);
+    hipLaunchKernelGGL(k_acf_q, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, A, user, pos, neg, B, S->q);
+    BPRX_LAUNCH_CHECK(h, "k_acf_q");
+    AcfUserArgs UA;
+    UA.Gu = h->t.Gu; UA.Pi = S->a.Pi; UA.Z = S->Z; UA.GP = S->GP;
+    UA.wcu = S->a.w[BPRX_ACF_C_WU]; UA.bc0 = S->a.w[BPRX_ACF_C_B0]; UA.w1c = S->a.w[BPRX_ACF_C_W1]; UA.bc1 = S->a.w[BPRX_ACF_C_B1];
+    UA.wiu = S->a.w[BPRX_ACF_I_WU]; UA.bi0 = S->a.w[BPRX_ACF_I_B0]; UA.w1i = S->a.w[BPRX_ACF_I_W1]; UA.bi1 = S->a.w[BPRX_ACF_I_B1];
+    UA.ptr = S->a.train_ptr; UA.items = S->a.train_items; UA.errflag = h->errflag;
+    UA.U = U; UA.I = I; UA.k = k; UA.M = S->M; UA.hc = hc; UA.ha = ha; UA.NP = S->NP;
+    AcfBwdArgs G;
+    G.q = S->q; G.aux = S->aux; G.dZ = S->dZ; G.dGP = S->dGP; G.dPi = S->dPi; G.dGu = h->dGu; G.UV = S->UV;
+    hipLaunchKernelGGL(k_acf_user_bwd, dim3((unsigned)B), dim3(256), acf_user_bwd_lds(S), s, UA, G, user, B, S->uslot);
+    BPRX_LAUNCH_CHECK(h, "k_acf_user_bwd");
+  }
+  {
+    BprxProfScope ps(h, BPRX_PHASE_LOSS, s);
+    hipLaunchKernelGGL(k_acf_item_bwd, dim3(acf_grid(I, 4, 4096)), dim3(256), 0, s, S->a.w[BPRX_ACF_I_WV], S->a.w[BPRX_ACF_I_WP],
+                       S->dGP, S->ilist, S->nlist, k, ha, h->dGi, S->dPi);
+    BPRX_LAUNCH_CHECK(h, "k_acf_item_bwd");
+    // dWiv = sum_l Gi_l (x) dGP_l, dWip = sum_l Pi_l (x) dGP_l over the listed items
+    AcfOuter O;
+    O.V = S->dGP; O.ldv = ha; O.W = ha; O.k = k; O.U = U; O.B = B; O.user = user; O.uslot = S->uslot; O.list = S->ilist;
+    O.nlist = S->nlist;
+    const int isplit = (int)acf_grid(I, 16, ACF_SPLIT);
+    const dim3 gi((unsigned)(((k + 63) / 64) * ((ha + 63) / 64)), (unsigned)isplit);
+    const float *R[2] = {h->t.Gi, S->a.Pi};
+    float *out[2] = {S->gw[BPRX_ACF_I_WV], S->gw[BPRX_ACF_I_WP]};
+    for (int t = 0; t < 2; ++t) {
+      O.R = R[t];
+      hipLaunchKernelGGL(k_acf_outer, gi, dim3(256), 0, s, O, S->part);
+      BPRX_LAUNCH_CHECK(h, "k_acf_outer");
+      if ((rc = acf_reduce(h, isplit, (int64_t)k * ha, k, ha, out[t], ha, nullptr, 0, s))) return rc;
+    }
+    // [dWcu | dWiu] = sum_u g_u (x) [duc_u | dui_u] over the distinct users
+    O.R = h->t.Gu; O.V = S->UV; O.ldv = W2; O.W = W; O.list = nullptr; O.nlist = nullptr;
+    const int usplit = (int)acf_grid(B, 16, ACF_SPLIT);
+    hipLaunchKernelGGL(k_acf_outer, dim3((unsigned)(((k + 63) / 64) * ((W + 63) / 64)), (unsigned)usplit), dim3(256), 0, s, O, S->part);
+    BPRX_LAUNCH_CHECK(h, "k_acf_outer");
+    if ((rc = acf_reduce(h, usplit, (int64_t)k * W, k, W, S->gw[BPRX_ACF_C_WU], hc, S->gw[BPRX_ACF_I_WU], ha, s))) return rc;
+    // [dbc0 | dbi0 | dW1c | dW1i] = column sums of the users' rows (gw[C_B0] is the head of that block)
+    hipLaunchKernelGGL(k_acf_colsum, dim3((unsigned)usplit), dim3(256), 0, s, S->UV, W2, user, S->uslot, U, B, S->part);
+    BPRX_LAUNCH_CHECK(h, "k_acf_colsum");
+    if ((rc = acf_reduce(h, usplit, W2, 1, W2, S->gw[BPRX_ACF_C_B0], W2, nullptr, 0, s))) return rc;
+  }
+  {
+    BprxProfScope ps(h, BPRX_PHASE_PROJ_BWD, s);
+    const int NCT = S->NP / 32, nb = NCT < 4 ? NCT : 4, ctiles = (S->C + 127) / 128, Crows = ctiles * 128;
+    const dim3 g((unsigned)ctiles, (unsigned)S->nsplit_proj, (unsigned)((NCT + nb - 1) / nb));
+#define ACF_PROJ_BWD(N)                                                                                                       \
+  case N:                                                                                                                     \
+    if (S->fdt == BPRX_F_BF16)                                                                                                \
+      hipLaunchKernelGGL(k_acf_proj_bwd_bf16<N>, g, dim3(256), 0, s, (const uint16_t *)S->a.F, S->dZ, S->part, S->ilist,       \
+                         S->nlist, S->M, S->C, S->NP, Crows);                                                                 \
+    else                                                                                                                      \
+      hipLaunchKernelGGL(k_acf_proj_bwd_f32<N>, g, dim3(256), 0, s, (const float *)S->a.F, S->dZ, S->part, S->ilist, S->nlist, \
+                         S->M, S->C, S->NP, Crows);                                                                           \
+    break;
+    switch (nb) { ACF_PROJ_BWD(1) ACF_PROJ_BWD(2) ACF_PROJ_BWD(3) ACF_PROJ_BWD(4) }
+#undef ACF_PROJ_BWD
+    BPRX_LAUNCH_CHECK(h, "k_acf_proj_bwd");
+    if ((rc = acf_reduce(h, S->nsplit_proj, (int64_t)Crows * S->NP, S->C, S->NP, S->gw[BPRX_ACF_C_WI], hc, S->gw[BPRX_ACF_I_WX], ha, s)))
+      return rc;
+    hipLaunchKernelGGL(k_acf_clear, dim3(acf_grid(I, 1, 8192)), dim3(256), 0, s, S->dZ, S->dGP, S->ilist, S->nlist,
+                       (int64_t)S->M * S->NP, ha);
+    BPRX_LAUNCH_CHECK(h, "k_acf_clear");
+  }
   return BPRX_OK;
 }
 
@@ -659,7 +1305,8 @@ int bprx_acf_step(bprx_handle *h, const int32_t *user, const int32_t *pos, const
   hipLaunchKernelGGL(k_acf_claim, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, user, B, U, S->uslot, h->errflag);
   BPRX_LAUNCH_CHECK(h, "k_acf_claim");
   if ((rc = acf_prepare(h, user, B, S->uslot, S->a.train_ptr, S->a.train_items, s))) return rc;
-  if ((rc = acf_users(h, user, B, S->uslot, S->a.train_ptr, S->a.train_items, S->gp, s))) return rc;
+  const bool full = S->grad_mode == BPRX_ACF_GRAD_FULL;
+  if ((rc = acf_users(h, user, B, S->uslot, S->a.train_ptr, S->a.train_items, S->gp, s, full ? S->aux : nullptr))) return rc;
   AcfStepArgs A;
   A.Gu = h->t.Gu; A.Gi = h->t.Gi; A.Pi = S->a.Pi; A.gp = S->gp;
   A.dGu = h->dGu; A.dGi = h->dGi; A.dPi = S->dPi; A.lossb = h->lossb;
@@ -669,10 +1316,14 @@ int bprx_acf_step(bprx_handle *h, const int32_t *user, const int32_t *pos, const
     hipLaunchKernelGGL(k_acf_triplet, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, A, user, pos, neg, B);
     BPRX_LAUNCH_CHECK(h, "k_acf_triplet");
   }
+  if (full && (rc = acf_backward(h, A, user, pos, neg, B, s))) return rc;
   {
     BprxProfScope ps(h, BPRX_PHASE_DENSE, s);
     AcfDenseArgs T;
-    for (int q = 0; q < BPRX_ACF_NW; ++q) { T.w[q] = S->a.w[q]; T.m[q] = S->a.m_w[q]; T.v[q] = S->a.v_w[q]; T.n[q] = S->nw[q]; }
+    for (int q = 0; q < BPRX_ACF_NW; ++q) {
+      T.w[q] = S->a.w[q]; T.m[q] = S->a.m_w[q]; T.v[q] = S->a.v_w[q]; T.n[q] = S->nw[q];
+      T.g[q] = full ? S->gw[q] : nullptr;
+    }
     hipLaunchKernelGGL(k_acf_dense, dim3(1), dim3(1024), 0, s, T, adam ? 1 : 0, lr_t, h->cfg.reg, h->cfg.beta1, h->cfg.beta2,
                        h->cfg.epsilon, h->lossb, B, loss_out);
     BPRX_LAUNCH_CHECK(h, "k_acf_dense");
@@ -692,7 +1343,16 @@ int bprx_acf_step(bprx_handle *h, const int32_t *user, const int32_t *pos, const
       hipLaunchKernelGGL(k_acf_apply_sgd, dim3((unsigned)((3 * B + 3) / 4)), dim3(256), 0, s, h->t.Gu, h->t.Gi, S->a.Pi, h->dGu,
                          h->dGi, S->dPi, h->flagU, h->flagI, user, pos, neg, B, U, I, k, lr_t);
       BPRX_LAUNCH_CHECK(h, "k_acf_apply_sgd");
+      if (full) {
+        hipLaunchKernelGGL(k_acf_apply_sgd_list, dim3(acf_grid(I, 4, 4096)), dim3(256), 0, s, h->t.Gi, S->a.Pi, h->dGi, S->dPi,
+                           h->flagI, S->ilist, S->nlist, k, lr_t);
+        BPRX_LAUNCH_CHECK(h, "k_acf_apply_sgd_list");
+      }
     }
+  }
+  if (full && !adam) {
+    hipLaunchKernelGGL(k_acf_finish_list, dim3(acf_grid(I, 256, 1024)), dim3(256), 0, s, S->ilist, S->nlist, h->flagI);
+    BPRX_LAUNCH_CHECK(h, "k_acf_finish_list");
   }
   hipLaunchKernelGGL(k_acf_finish, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, user, pos, neg, B, U, I, S->uslot, h->flagU,
                      h->flagI);
@@ -734,7 +1394,8 @@ void bprx_acf_invalidate(bprx_handle *h) {
 void bprx_acf_free(bprx_handle *h) {
   AcfState *S = h->acf;
   if (!S) return;
-  void *ptrs[] = {S->Z, S->GP, S->Wc, S->Wh, S->Wl, S->gp, S->Gup, S->dPi, S->uslot, S->imark, S->ilist, S->nlist};
+  void *ptrs[] = {S->Z, S->GP, S->Wc, S->Wh, S->Wl, S->gp, S->Gup, S->dPi, S->uslot, S->imark, S->ilist, S->nlist,
+                  S->dZ, S->dGP, S->q, S->aux, S->UV, S->part, S->gwbuf};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   delete S;
@@ -816,6 +1477,7 @@ extern "C" int bprx_bind_acf(bprx_handle *h, const bprx_tables *t, const bprx_ac
     }
   }
   S->a = *a;
+  S->grad_mode = BPRX_ACF_GRAD_DETACHED;                     // every bind starts with the reference's step
   const int64_t hc = S->hc, ha = S->ha, C = S->C;
   const int64_t nw[BPRX_ACF_NW] = {(int64_t)k * hc, C * hc, hc, hc, 1, (int64_t)k * ha, (int64_t)k * ha, (int64_t)k * ha, C * ha, ha, ha, 1};
   for (int q = 0; q < BPRX_ACF_NW; ++q) S->nw[q] = nw[q];
@@ -835,4 +1497,72 @@ extern "C" int bprx_acf_profiles(bprx_handle *h, const int32_t *users, int64_t n
   int rc;
   if ((rc = acf_prepare(h, users, n, nullptr, hist_ptr, hist_items, s))) return rc;
   return acf_users(h, users, n, nullptr, hist_ptr, hist_items, out, s);
+}
+
+// Workspace of the full-gradient mode, allocated at the first switch to it (a detached handle never pays for it)
+static int acf_full_alloc(bprx_handle *h) {
+  AcfState *S = h->acf;
+  if (S->dZ) return BPRX_OK;
+  if (acf_user_bwd_lds(S) > 65536)
+    BPRX_FAIL(h, BPRX_E_INVALID, "acf_set_gradient: M = %d with embed_k = %d needs more LDS than a workgroup has in the backward",
+              S->M, S->k);
+  const size_t I = h->cfg.num_items, MB = h->cfg.max_batch, k = S->k, hc = S->hc, ha = S->ha, W = hc + ha, C = S->C;
+  const int NCT = S->NP / 32, nb = NCT < 4 ? NCT : 4, ctiles = (S->C + 127) / 128, zt = (NCT + nb - 1) / nb;
+  int ns = 4 * h->num_cu / (ctiles * zt);
+  S->nsplit_proj = ns < 1 ? 1 : (ns > 128 ? 128 : ns);
+  size_t pf = (size_t)S->nsplit_proj * ctiles * 128 * S->NP;
+  if (pf < ACF_SPLIT * k * W) pf = ACF_SPLIT * k * W;
+  S->part_floats = pf;
+  const size_t gwn = k * hc + C * hc + 3 * k * ha + C * ha + 2 * W;
+  bool ok = true;
+  auto al = [&](void **p, size_t bytes) { ok = ok && hipMalloc(p, bytes) == hipSuccess && hipMemset(*p, 0, bytes) == hipSuccess; };
+  al((void **)&S->dGP, I * ha * sizeof(float));
+  al((void **)&S->q, MB * k * sizeof(float));
+  al((void **)&S->aux, MB * (k + 2) * sizeof(float));
+  al((void **)&S->UV, MB * 2 * W * sizeof(float));
+  al((void **)&S->part, pf * sizeof(float));
+  al((void **)&S->gwbuf, gwn * sizeof(float));
+  al((void **)&S->dZ, I * S->M * S->NP * sizeof(float));
+  if (!ok) {
+    void *ptrs[] = {S->dZ, S->dGP, S->q, S->aux, S->UV, S->part, S->gwbuf};
+    for (void *p : ptrs)
+      if (p) (void)hipFree(p);
+    S->dZ = S->dGP = S->q = S->aux = S->UV = S->part = S->gwbuf = nullptr;
+    BPRX_FAIL(h, BPRX_E_NOMEM, "acf_set_gradient: workspace allocation failed (dZ: %zu MB)", (I * S->M * S->NP * 4) >> 20);
+  }
+  float *g = S->gwbuf;
+  for (int q = 0; q < BPRX_ACF_NW; ++q) S->gw[q] = nullptr;
+  S->gw[BPRX_ACF_C_WU] = g; g += k * hc;
+  S->gw[BPRX_ACF_C_WI] = g; g += C * hc;
+  S->gw[BPRX_ACF_I_WU] = g; g += k * ha;
+  S->gw[BPRX_ACF_I_WV] = g; g += k * ha;
+  S->gw[BPRX_ACF_I_WP] = g; g += k * ha;
+  S->gw[BPRX_ACF_I_WX] = g; g += C * ha;
+  S->gw[BPRX_ACF_C_B0] = g;                                 // [dbc0 | dbi0 | dW1c | dW1i]: one block, k_acf_colsum's column order
+  S->gw[BPRX_ACF_I_B0] = g + hc;
+  S->gw[BPRX_ACF_C_W1] = g + W;
+  S->gw[BPRX_ACF_I_W1] = g + W + hc;
+  // b_1 of both levels: no gradient tensor.  Both softmaxes are shift-invariant, so the derivative is identically zero; the
+  // library writes exactly 2 reg b_1 instead of rounding noise (which Adam would divide by its own magnitude).
+  BPRX_HIP(h, hipDeviceSynchronize());
+  return BPRX_OK;
+}
+
+extern "C" int bprx_acf_set_gradient(bprx_handle *h, int mode) {
+  if (!h) return BPRX_E_INVALID;
+  if (!h->bound || !h->acf) BPRX_FAIL(h, BPRX_E_STATE, "acf_set_gradient: the handle is not bound with bprx_bind_acf");
+  if (mode != BPRX_ACF_GRAD_DETACHED && mode != BPRX_ACF_GRAD_FULL)
+    BPRX_FAIL(h, BPRX_E_INVALID, "acf_set_gradient: mode %d is neither BPRX_ACF_GRAD_DETACHED nor BPRX_ACF_GRAD_FULL", mode);
+  if (mode == BPRX_ACF_GRAD_FULL) {
+    const int rc = acf_full_alloc(h);
+    if (rc) return rc;
+  }
+  h->acf->grad_mode = mode;
+  return BPRX_OK;
+}
+
+extern "C" int bprx_acf_get_gradient(bprx_handle *h) {
+  if (!h) return BPRX_E_INVALID;
+  if (!h->bound || !h->acf) BPRX_FAIL(h, BPRX_E_STATE, "acf_get_gradient: the handle is not bound with bprx_bind_acf");
+  return h->acf->grad_mode;
 }

@@ -170,14 +170,18 @@ class Engine:
         items = np.fromiter((int(i) for l in lists for i in l), dtype=np.int64, count=int(ptr[-1])).astype(np.int32)
         return (torch.as_tensor(ptr, device=self.device), torch.as_tensor(items, device=self.device))
 
-    def bind_acf(self, Gu, Gi, Bi, F, Pi, weights, train_lists, eval_lists=None, slots=None):
+    def bind_acf(self, Gu, Gi, Bi, F, Pi, weights, train_lists, eval_lists=None, slots=None, gradient="detached"):
         """ACF (bprx_bind_acf) on a BPRMF engine: F [I, M, C] feature maps (fp32, or bf16 with feat_dtype='bf16'), Pi [I, k],
         weights = the twelve attention tensors as {'component.W_0_u': array, ..., 'item.b_1': array} (_ffi.ACF_WEIGHTS, shapes of
         include/bprx.h),
         train_lists / eval_lists = the histories P(u) of steps / score_pairs and of score_block (None: the training lists).
-        Adam slots (m_ / v_ for Gu, Gi, Bi, Pi and every weight, keyed 'm_Pi', 'm_item.W_1', ...) are zeros unless given."""
+        Adam slots (m_ / v_ for Gu, Gi, Bi, Pi and every weight, keyed 'm_Pi', 'm_item.W_1', ...) are zeros unless given.
+        gradient: 'detached' (the reference's step: g'_u is a constant of the tape) or 'full' (the same loss differentiated through
+        both attention levels, bprx_acf_set_gradient)."""
         if self.model != "bprmf":
             raise ValueError("bind_acf needs an Engine(model='bprmf', ...)")
+        if gradient not in _ffi.ACF_GRADIENT:
+            raise ValueError("ACF gradient is 'detached' or 'full' (got %r)" % (gradient,))
         if self.feat_dtype not in ("fp32", "bf16"):
             raise ValueError("ACF features are fp32 or bf16 (got %s)" % self.feat_dtype)
         def prep(x, shape=None, dtype=torch.float32):
@@ -219,7 +223,19 @@ class Engine:
         _ffi.check(self.h, self.lib.bprx_bind_acf(self.h, C.byref(tb), C.byref(ac)))
         self.acf = True
         self.t = t
+        if gradient != "detached":
+            self.acf_set_gradient(gradient)
         return self
+
+    def acf_set_gradient(self, gradient):
+        """bprx_acf_set_gradient: 'detached' or 'full' for the following steps of an ACF-bound engine."""
+        if gradient not in _ffi.ACF_GRADIENT:
+            raise ValueError("ACF gradient is 'detached' or 'full' (got %r)" % (gradient,))
+        _ffi.check(self.h, self.lib.bprx_acf_set_gradient(self.h, _ffi.ACF_GRADIENT[gradient]))
+
+    def acf_gradient(self):
+        mode = _ffi.check(self.h, self.lib.bprx_acf_get_gradient(self.h))
+        return {v: n for n, v in _ffi.ACF_GRADIENT.items()}[mode]
 
     def acf_profiles(self, users, lists=None, csr=None):
         """calculate_beta_alpha (bprx_acf_profiles): g'_u [n, k] for `users` with the histories `lists` (per user id, or a

@@ -432,7 +432,8 @@ class ACF(BPRMF):
     """ACF.py:20-270, Attentive Collaborative Filtering: the user profile g'_u = g_u + sum_l alpha_l Pi_l with a component-level
     attention over each history item's feature map and an item-level attention over the history; x_ui = g'_u . Gi_i.  Trained on
     the engine's ACF path (include/bprx.h, bprx_bind_acf) with the reference's DETACHED gradient (g'_u is rebuilt as a new leaf,
-    ACF.py:208).  Same surface as the reference: Pi, component_weights, item_weights, layers_component, layers_item, call,
+    ACF.py:208) unless `params.acf_gradient == "full"`: then the same loss is differentiated through both attention levels
+    (bprx_acf_set_gradient; directory_parameters ends in -grad_full and the snapshot records the mode).  Same surface as the reference: Pi, component_weights, item_weights, layers_component, layers_item, call,
     predict_all, train_step, train.  `features`: optional [I, M, C] (or [I, H, W, C]) array used instead of the per-item .npy
     files (not normalised, like the files)."""
     model_kind = "acf"
@@ -444,6 +445,9 @@ class ACF(BPRMF):
             if len(l) != 2 or l[1] != 1 or l[0] <= 0:
                 raise ValueError("ACF: --%s must be two ints 'h 1' with h > 0 (got %s)" % (name, l))
         self._features = features
+        self.acf_gradient = getattr(params, "acf_gradient", None) or "detached"
+        if self.acf_gradient not in ("detached", "full"):
+            raise ValueError("ACF: acf_gradient is 'detached' or 'full' (got %r)" % (self.acf_gradient,))
         super().__init__(data, params, init)
         self.directory_parameters = f'batch_{params.batch_size}' \
                                     f'-K_{params.embed_k}' \
@@ -451,6 +455,8 @@ class ACF(BPRMF):
                                     f'-reg_{params.reg}' \
                                     f'-comp_{list(self.layers_component)}' \
                                     f'-item_{list(self.layers_item)}'          # ACF.py:46-51
+        if self.acf_gradient == "full":                                        # detached runs keep the reference's file names
+            self.directory_parameters += '-grad_full'
 
     def process_cnn_feature_maps(self):
         dtype = getattr(self.params, "dtype", "fp32")
@@ -513,8 +519,22 @@ class ACF(BPRMF):
         t, _ = self._init_tables(init)
         self.engine = Engine(optimizer=self.optimizer_name, lr=self.learning_rate, reg=self.reg,
                              max_batch=max(self.batch_size, 4096), adam_form=self._adam_form(), **self._engine_kwargs())
+        kw = {"gradient": "full"} if self.acf_gradient == "full" else {}
         self.engine.bind_acf(t["Gu"], t["Gi"], t["Bi"], self.acf_features, t["Pi"], {n: t[n] for n in _ACF_W},
-                             self.data.training_list, self.eval_lists())
+                             self.data.training_list, self.eval_lists(), **kw)
+
+    # ---- snapshots: the gradient mode is part of a full-mode snapshot; one without the key is detached --------------------
+    def state_dict(self):
+        sd = super().state_dict()
+        if self.acf_gradient == "full":
+            sd["acf_gradient"] = "full"
+        return sd
+
+    def load_state_dict(self, sd):
+        mode = sd.get("acf_gradient", "detached")
+        if mode != self.acf_gradient:
+            raise ValueError("ACF: the snapshot was taken with acf_gradient=%s, this model runs %s" % (mode, self.acf_gradient))
+        super().load_state_dict({n: v for n, v in sd.items() if n != "acf_gradient"})
 
     # ---- the reference's attribute surface ---------------------------------------------------------------------------
     @property

@@ -43,6 +43,9 @@ def parse_args(argv=None):
                         help='acf: component-level attention layers, two ints "h 1" (ACF.py:40)')
     parser.add_argument('--layers_item', nargs='+', type=int, default=[64, 1],
                         help='acf: item-level attention layers, two ints "a 1" (ACF.py:41)')
+    parser.add_argument('--acf_gradient', default='detached', choices=['detached', 'full'],
+                        help="acf: 'detached' = the reference's step (g'_u is a constant of the tape, ACF.py:203-208); 'full' = the "
+                             "same loss differentiated through both attention levels")
     parser.add_argument('--attention_layers', nargs='+', type=int, default=[64, 1],
                         help='attentive_fashion: attention layers, two ints "h 1" (train_rec.py:38)')
     # not in the reference
@@ -69,6 +72,8 @@ def parse_args(argv=None):
         v = getattr(args, name)
         if len(v) != 2 or v[1] != 1 or v[0] <= 0:
             parser.error("--%s takes two ints 'h 1' with h > 0 (got %s)" % (name, " ".join(str(x) for x in v)))
+    if args.acf_gradient != 'detached' and args.rec != 'acf':
+        parser.error("--acf_gradient %s needs --rec acf (got --rec %s)" % (args.acf_gradient, args.rec))
     if not 0.0 <= args.dropout < 1.0:
         parser.error("--dropout takes a rate in [0, 1) (got %s)" % args.dropout)
     return args

@@ -184,7 +184,28 @@ BPRX_API int bprx_explain_pairs(bprx_handle *h, const int32_t *user, const int32
                        eval_* and topk work unchanged.
    bprx_step_begin / _end and the multi-GPU entry points are rejected (BPRX_E_STATE).  History and batch indices out of range
    are clamped and reported by bprx_sync_check (BPRX_E_RANGE).
-   Limits: M <= 2048, C % 4 == 0 (fp32) or C % 8 == 0 (bf16), h + a <= 256, embed_k <= 512. */
+   Limits: M <= 2048, C % 4 == 0 (fp32) or C % 8 == 0 (bf16), h + a <= 256, embed_k <= 512.
+
+   bprx_acf_set_gradient(h, BPRX_ACF_GRAD_FULL) makes bprx_step differentiate the SAME loss with nothing detached (the paper's
+   end-to-end training; not what the reference's tape computes).  With d_b = g'_u.(Gi_i - Gi_j), c_b = -sigmoid(-d_b) inside
+   the clip range (0 outside) and q_u = sum_{b: user_b = u} c_b (Gi_i - Gi_j) = dL/dg'_u, per distinct user u of the batch and
+   history item l (pre_l = the item level's relu input, a_lm = the component level's):
+       dGu_u += q_u                dPi_l += alpha_l q_u            dt_l = alpha_l (Pi_l.q_u - sum_l' alpha_l' Pi_l'.q_u)
+       dpre_l = dt_l W1i * [pre_l > 0]      dW1i += dt_l relu(pre_l)      dbi0 += dpre_l
+       dWiu += g_u (x) dpre_l   dGu_u += Wiu dpre_l     dWiv += Gi_l (x) dpre_l   dGi_l += Wiv dpre_l
+       dWip += Pi_l (x) dpre_l  dPi_l += Wip dpre_l     dZ_lm[h:] += beta_lm dpre_l   dbeta_lm = Z_lm[h:].dpre_l
+       ds_lm = beta_lm (dbeta_lm - sum_m' beta_lm' dbeta_lm')      da_lm = ds_lm W1c * [a_lm > 0]      dW1c += ds_lm relu(a_lm)
+       dZ_lm[:h] += da_lm      dbc0 += da_lm      dWcu += g_u (x) da_lm      dGu_u += Wcu da_lm      [dWci | dWix] = sum F_lm^T dZ_lm
+   on top of everything the detached step adds (same loss value, same clip mask, same 2 reg terms, same range-error
+   behaviour).  b_1 of both levels: each softmax is invariant under a shift of its inputs, so these two derivatives are
+   identically zero and the library writes EXACTLY 2 reg b_1 for them, not rounding noise.  sgd then also moves the Gi / Pi
+   rows of the history items of the batch's users; adam_tf23 sweeps as before.  dZ, the per-item gradients and the row tables
+   accumulate with float atomics (as the detached step's dGi does), so a full step is not bit-reproducible; the gradients of
+   the attention tensors are split-K partials summed in a fixed order.  The mode costs a second buffer the size of Z and a
+   few small ones, allocated at the first switch to FULL; in the backward M is limited by 4 (2 M + a) + 2 k + 12 (h + a) + 4
+   floats of LDS <= 64 KB (BPRX_E_INVALID otherwise).  The default is BPRX_ACF_GRAD_DETACHED, bit for bit the step above; every
+   bprx_bind_acf starts detached again.
+   BPRX_E_STATE on a handle that is not ACF-bound, BPRX_E_INVALID for another mode; _get_ returns the mode. */
 enum {
   BPRX_ACF_C_WU = 0, BPRX_ACF_C_WI = 1, BPRX_ACF_C_B0 = 2, BPRX_ACF_C_W1 = 3, BPRX_ACF_C_B1 = 4,      /* component_weights */
   BPRX_ACF_I_WU = 5, BPRX_ACF_I_WV = 6, BPRX_ACF_I_WP = 7, BPRX_ACF_I_WX = 8, BPRX_ACF_I_B0 = 9,      /* item_weights */
@@ -208,6 +229,9 @@ BPRX_API int bprx_bind_acf(bprx_handle *h, const bprx_tables *t, const bprx_acf 
    out fp32 [n, k] = g'_u. */
 BPRX_API int bprx_acf_profiles(bprx_handle *h, const int32_t *users, int64_t n, const int64_t *hist_ptr,
                                const int32_t *hist_items, float *out, void *stream);
+enum { BPRX_ACF_GRAD_DETACHED = 0, BPRX_ACF_GRAD_FULL = 1 };
+BPRX_API int bprx_acf_set_gradient(bprx_handle *h, int mode);
+BPRX_API int bprx_acf_get_gradient(bprx_handle *h);
 
 /* ---- AttentiveFashion (AttentiveFashion.py:20-371) on a BPRMF handle ----------------------------------------------------
    Per item i three inputs: an edge image (uint8 [224, 224]; the model sees pixel / 255), a colour histogram [Dc] and a class

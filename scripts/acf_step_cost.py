@@ -4,7 +4,11 @@ training items per user, feature maps M = 49 x C = 512, k = 128, h = a = 64, reg
 events (phase proj_fwd) and reported against its roofline (f32 MFMA 157 TF for fp32 features, 8 TB/s of feature bytes for bf16).
 An ACF step reports its kernels under the library's phase names: proj_fwd = k_acf_proj_*, triplet_grad = k_acf_user,
 item_seg = k_acf_triplet, dense_update = k_acf_dense, apply = k_acf_sweep / k_acf_apply_sgd, row_count = k_acf_mark.
-Prints one JSON line per case.  Usage: python scripts/acf_step_cost.py [--steps 50] [--warmup 5]"""
+--gradient full measures the full-gradient mode (bprx_acf_set_gradient); its extra kernels report as reduce_parts = k_acf_q +
+k_acf_user_bwd, loss_reduce = k_acf_item_bwd + k_acf_outer + k_acf_colsum + their k_acf_reduce, proj_bwd = k_acf_proj_bwd_* + its
+k_acf_reduce + k_acf_clear (per-kernel times: rocprofv3 --kernel-trace --stats, profiles/acf_full_kernel_stats.txt).
+ms_per_step is the median of five timed windows of --steps steps, with (min, max).
+Prints one JSON line per case.  Usage: python scripts/acf_step_cost.py [--steps 50] [--warmup 5] [--gradient full] [--no-eval]"""
 import argparse
 import json
 import os
@@ -34,10 +38,11 @@ def tables(rs):
     return t
 
 
-def case(dtype, B, steps, warmup, train, t, F):
+def case(dtype, B, steps, warmup, train, t, F, gradient="detached"):
     e = Engine(model="bprmf", num_users=U, num_items=I, embed_k=K, feat_dtype=dtype, optimizer="adam_tf23", lr=1e-3, reg=1e-4,
                max_batch=B)
-    e.bind_acf(t["Gu"], t["Gi"], t["Bi"], F, t["Pi"], {n: t[n] for n in _ffi.ACF_WEIGHTS}, train)
+    e.bind_acf(t["Gu"], t["Gi"], t["Bi"], F, t["Pi"], {n: t[n] for n in _ffi.ACF_WEIGHTS}, train,
+               **({"gradient": "full"} if gradient == "full" else {}))
     rs = np.random.RandomState(1)
     host = [tuple(rs.randint(0, n, B).astype(np.int32) for n in (U, I, I)) for _ in range(4)]
     batches = [tuple(torch.as_tensor(x, device="cuda") for x in b) for b in host]
@@ -45,13 +50,16 @@ def case(dtype, B, steps, warmup, train, t, F):
     for s in range(warmup):
         e.step(*batches[s % 4], want_loss=False)
     torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for s in range(steps):
-        e.step(*batches[s % 4], want_loss=False)
-    b.record()
-    b.synchronize()
-    ms = a.elapsed_time(b) / steps
+    windows = []
+    for _ in range(5):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for s in range(steps):
+            e.step(*batches[s % 4], want_loss=False)
+        b.record()
+        b.synchronize()
+        windows.append(a.elapsed_time(b) / steps)
+    ms = float(np.median(windows))
     e.profile(True)
     for s in range(steps):
         e.step(*batches[s % 4], want_loss=False)
@@ -63,10 +71,16 @@ def case(dtype, B, steps, warmup, train, t, F):
     flop = 2.0 * nd * M * C * 128                                   # h + a = 128 columns
     byts = nd * M * C * (4 if dtype == "fp32" else 2)
     roof = 157e12 if dtype == "fp32" else None
-    out = {"case": "step", "dtype": dtype, "B": B, "ms_per_step": round(ms, 4), "distinct_items": round(nd, 1),
+    out = {"case": "step", "gradient": gradient, "dtype": dtype, "B": B, "ms_per_step": round(ms, 4),
+           "ms_min_max": [round(min(windows), 4), round(max(windows), 4)], "distinct_items": round(nd, 1),
            "proj_ms": round(proj_ms, 4), "proj_tflops": round(flop / proj_ms / 1e9, 1), "proj_tbps": round(byts / proj_ms / 1e9, 2),
            "phases_ms": {k_: round(v[0] / max(1, v[1]), 4) for k_, v in prof.items() if v[1]}}
     out["proj_roofline_frac"] = round((flop / proj_ms * 1e3) / roof, 3) if roof else round((byts / proj_ms * 1e3) / 8e12, 3)
+    if gradient == "full" and "proj_bwd" in out["phases_ms"]:       # F^T dZ: the same flops and feature bytes as the forward
+        pb = out["phases_ms"]["proj_bwd"]
+        out["proj_bwd_tflops"] = round(flop / pb / 1e9, 1)
+        out["proj_bwd_tbps"] = round(byts / pb / 1e9, 2)
+        out["proj_bwd_roofline_frac"] = round((flop / pb * 1e3) / roof, 3) if roof else round((byts / pb * 1e3) / 8e12, 3)
     print(json.dumps(out), flush=True)
     return e
 
@@ -86,6 +100,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--gradient", default="detached", choices=["detached", "full"])
+    ap.add_argument("--no-eval", action="store_true", help="skip the evaluation pass")
+    ap.add_argument("--dtypes", nargs="+", default=["fp32", "bf16"])
+    ap.add_argument("--batches", nargs="+", type=int, default=[256, 65_536])
     a = ap.parse_args()
     torch.cuda.set_device(0)
     train, _, _ = synth.make_interactions(U, I, per_user=22, seed=2024)
@@ -93,11 +111,11 @@ def main():
     t = tables(rs)
     g = torch.Generator().manual_seed(0)
     F32 = torch.randn((I, M, C), generator=g).abs_()
-    for dtype in ("fp32", "bf16"):
+    for dtype in a.dtypes:
         F = F32 if dtype == "fp32" else F32.to(torch.bfloat16)
-        for B in (256, 65_536):
-            e = case(dtype, B, a.steps, a.warmup, train, t, F)
-            if B == 65_536:
+        for B in a.batches:
+            e = case(dtype, B, a.steps, a.warmup, train, t, F, a.gradient)
+            if B == 65_536 and not a.no_eval:
                 evaluation(e, dtype)
             e.close()
             torch.cuda.empty_cache()
