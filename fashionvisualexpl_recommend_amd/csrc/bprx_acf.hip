@@ -64,6 +64,10 @@ struct AcfState {
   float *gwbuf;
   size_t part_floats;
   int nsplit_proj;
+  // bprx_acf_explain, allocated at its first call
+  float *xt;                          // [xt_cap] item-level logits t_l by CSR position of the call's histories
+  float *xu;                          // int64 xt_cap, then [U][2 + h]: the item softmax's max and denominator, uc
+  int64_t xt_cap;
 };
 
 __device__ __forceinline__ int acf_clamp(int v, int n, int32_t *errflag, int code) {
@@ -320,11 +324,17 @@ struct AcfUserArgs {
 //   s_m = w1c.relu(uc + Z_lm[:h]) + bc1 (lane per m), beta = softmax_m(s), xz = sum_m beta_m Z_lm[h:] (lane per column),
 //   t = w1i.relu(ui + GP_l + xz) + bi1; the wave keeps a running max / denominator / sum of e^(t - max) Pi_l.
 // LDS: gu[k] uc[h] ui[a] w1c[h] w1i[a] | per wave: beta[M], acc[k] | wmx[4] wden[4]
-// AUX (full-gradient mode): also store what k_acf_user_bwd needs of the forward; <false> is the detached step's kernel unchanged
-template <bool AUX>
+// MODE (compile time, so that ACF_USER_PLAIN stays the detached step's kernel unchanged):
+//   ACF_USER_AUX      full-gradient mode: also store what k_acf_user_bwd needs of the forward
+//   ACF_USER_EXPLAIN  bprx_acf_explain's attention pass: the same walk, but instead of g' it keeps what makes alpha_l recoverable
+//                     per entry: `out` = the item-level logits t_l by CSR position, `aux` = int64 size of `out`, then per USER a
+//                     row [softmax max, denominator, uc[h]]; the sum of e^(t - max) Pi_l is not formed
+enum { ACF_USER_PLAIN = 0, ACF_USER_AUX = 1, ACF_USER_EXPLAIN = 2 };
+template <int MODE>
 __global__ __launch_bounds__(256) void k_acf_user(AcfUserArgs A, const int32_t *__restrict__ users, int64_t n,
                                                   const int32_t *__restrict__ uslot, float *__restrict__ out,
                                                   float *__restrict__ aux) {
+  constexpr bool AUX = MODE == ACF_USER_AUX, EXPL = MODE == ACF_USER_EXPLAIN;
   extern __shared__ float sm[];
   const int64_t b = blockIdx.x;
   if (b >= n) return;
@@ -351,10 +361,12 @@ __global__ __launch_bounds__(256) void k_acf_user(AcfUserArgs A, const int32_t *
       ui[jj] = s + A.bi0[jj];
     }
   }
-  for (int c = lane; c < k; c += 64) acc[c] = 0.f;
+  if (!EXPL)
+    for (int c = lane; c < k; c += 64) acc[c] = 0.f;
   __syncthreads();
   const float bc1 = A.bc1[0], bi1 = A.bi1[0];
   const int64_t beg = A.ptr[u], end = A.ptr[u + 1];
+  const int64_t ncap = EXPL ? *(const int64_t *)aux : 0;      // EXPL: entries `out` has room for
   float mx = -INFINITY, den = 0.f;
   for (int64_t p = beg + w; p < end; p += 4) {
     const int l = acf_clamp(A.items[p], A.I, A.errflag, 5);
@@ -389,8 +401,12 @@ __global__ __launch_bounds__(256) void k_acf_user(AcfUserArgs A, const int32_t *
     const float nmx = fmaxf(mx, t);
     const float sc = expf(mx - nmx), e = expf(t - nmx);        // (mx = -inf at the first item: sc = 0)
     den = den * sc + e;
-    const float *pl = A.Pi + (int64_t)l * k;
-    for (int c = lane; c < k; c += 64) acc[c] = acc[c] * sc + e * pl[c];
+    if (EXPL) {
+      if (lane == 0 && p >= 0 && p < ncap) out[p] = t;
+    } else {
+      const float *pl = A.Pi + (int64_t)l * k;
+      for (int c = lane; c < k; c += 64) acc[c] = acc[c] * sc + e * pl[c];
+    }
     mx = nmx;
     wave_sync();                                               // beta is rewritten by the next item
   }
@@ -404,6 +420,12 @@ __global__ __launch_bounds__(256) void k_acf_user(AcfUserArgs A, const int32_t *
   for (int q = 0; q < 4; ++q) {
     f[q] = wden[q] > 0.f ? expf(wmx[q] - gm) : 0.f;
     D += wden[q] * f[q];
+  }
+  if (EXPL) {
+    float *st = aux + 2 + (int64_t)u * (2 + hc);
+    if (tid == 0) { st[0] = gm; st[1] = D; }
+    for (int j = tid; j < hc; j += 256) st[2 + j] = uc[j];
+    return;
   }
   for (int c = tid; c < k; c += 256) {
     float s = 0.f;
@@ -590,6 +612,175 @@ __global__ __launch_bounds__(256) void k_acf_score(const float *__restrict__ gp,
 
 __global__ void k_acf_fill(int32_t *p, size_t n, int32_t v) {
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) p[e] = v;
+}
+
+// ---- bprx_acf_explain: the pair pass ----------------------------------------------------------------------------------
+// x_ui = g_u.Gi_i + sum_l alpha_l (Pi_l.Gi_i): one WAVE per pair (u, i), four pairs per workgroup.  alpha_l = e^(t_l - max) / D from
+// the attention pass's logits and per-user row; Pi_l.Gi_i is a lane-strided dot (Gi_i in registers) with a butterfly reduction, so
+// every lane holds the same c_l and sum_l c_l is a compensated sum in history order (base is added last).  The `top` largest c_l live one per lane in lanes
+// 0..top-1, sorted: an entry that beats the last slot is ranked by a ballot (slots >= it stay in front: equal values keep
+// ascending positions) and the tail shifts one lane up.  No history-sized buffer.  beta_l is then recomputed from the Z rows for the
+// selected entries only (a lane per component m, as k_acf_user).
+// LDS: w1c[h] | per wave: uc[h] e[M]
+struct AcfExplainArgs {
+  const float *Gu, *Gi, *Pi, *Z, *w1c, *bc1;
+  const float *tl, *ustat;            // attention pass: logits by CSR position; per user [max, D, uc[h]]
+  const int64_t *ptr;
+  const int32_t *items;
+  int32_t *errflag;
+  int64_t ncap;                       // entries of tl
+  int U, I, k, M, hc, NP, top;
+  float *score, *base;
+  int32_t *pos, *hist_item;
+  float *alpha, *contrib;
+  int32_t *peak;
+  float *beta_peak, *beta;
+};
+
+__global__ __launch_bounds__(256) void k_acf_explain(AcfExplainArgs A, const int32_t *__restrict__ user,
+                                                     const int32_t *__restrict__ item, int64_t n) {
+  extern __shared__ float sm[];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int k = A.k, M = A.M, hc = A.hc, NP = A.NP, top = A.top;
+  float *w1c = sm, *uc = w1c + hc + (size_t)w * (hc + M), *eb = uc + hc;
+  for (int j = tid; j < hc; j += 256) w1c[j] = A.w1c[j];
+  __syncthreads();
+  const int64_t b = (int64_t)blockIdx.x * 4 + w;
+  if (b >= n) return;
+  const int u = acf_clamp(user[b], A.U, A.errflag, 1), i = acf_clamp(item[b], A.I, A.errflag, 2);
+  const float *st = A.ustat + (int64_t)u * (2 + hc);
+  const float gm = st[0], D = st[1];
+  for (int j = lane; j < hc; j += 64) uc[j] = st[2 + j];
+  wave_sync();
+  const float *gu = A.Gu + (int64_t)u * k, *gi = A.Gi + (int64_t)i * k;
+  float gir[ACF_MAX_K / 64], bs = 0.f;
+#pragma unroll
+  for (int q = 0; q < ACF_MAX_K / 64; ++q) {
+    const int c = lane + 64 * q;
+    gir[q] = c < k ? gi[c] : 0.f;
+    if (c < k) bs = fmaf(gu[c], gir[q], bs);
+  }
+  bs = wave_sum(bs);
+  int64_t beg = A.ptr[u], end = A.ptr[u + 1];
+  if (beg < 0) beg = 0;
+  if (end > A.ncap) end = A.ncap;                             // (a CSR that is not monotone: stay inside the workspace)
+  float sc = 0.f, comp = 0.f;                                 // sum_l c_l in history order, compensated (Kahan): thousands of
+                                                              // small terms must not each round at the ulp of the running sum
+  float tv = 0.f, thr = 0.f;                                  // this lane's slot (lane < top); thr = the last slot once all are taken
+  int tp = -1, cnt = 0;
+  for (int64_t p0 = beg; p0 < end; p0 += 64) {
+    const int64_t p = p0 + lane;
+    int l = 0;
+    float a = 0.f;
+    if (p < end) {
+      l = acf_clamp(A.items[p], A.I, A.errflag, 5);
+      a = expf(A.tl[p] - gm) / D;
+    }
+    const int m = (int)(end - p0 < 64 ? end - p0 : 64);
+    for (int e = 0; e < m; ++e) {
+      const int le = __shfl(l, e, 64);
+      const float ae = __shfl(a, e, 64);
+      const float *pl = A.Pi + (int64_t)le * k;
+      float d = 0.f;
+#pragma unroll
+      for (int q = 0; q < ACF_MAX_K / 64; ++q) {
+        const int c = lane + 64 * q;
+        if (c < k) d = fmaf(pl[c], gir[q], d);
+      }
+      d = wave_sum(d);
+      const float c = ae * d;
+      {
+        const float y = c - comp, ns = sc + y;
+        comp = (ns - sc) - y;
+        sc = ns;
+      }
+      if (cnt < top || c > thr) {
+        const int rank = __popcll(__ballot(lane < cnt && tv >= c));
+        if (rank < top) {
+          const float uv = __shfl_up(tv, 1, 64);
+          const int up = __shfl_up(tp, 1, 64);
+          if (lane == rank) {
+            tv = c;
+            tp = (int)(p0 - beg) + e;
+          } else if (lane > rank && lane < top) {
+            tv = uv;
+            tp = up;
+          }
+          if (cnt < top) ++cnt;
+          if (cnt == top) thr = __shfl(tv, top - 1, 64);
+        }
+      }
+    }
+  }
+  if (lane == 0) {
+    A.score[b] = bs + sc;
+    A.base[b] = bs;
+  }
+  const float bc1 = A.bc1[0];
+  for (int s = 0; s < top; ++s) {
+    const int64_t o = b * top + s;
+    if (s >= cnt) {                                            // beyond the history
+      if (lane == 0) {
+        A.pos[o] = -1; A.hist_item[o] = -1; A.peak[o] = -1;
+        A.alpha[o] = 0.f; A.contrib[o] = 0.f; A.beta_peak[o] = 0.f;
+      }
+      if (A.beta)
+        for (int m = lane; m < M; m += 64) A.beta[o * M + m] = 0.f;
+      continue;
+    }
+    const int ps = __shfl(tp, s, 64);
+    const float cs = __shfl(tv, s, 64);
+    const int64_t p = beg + ps;
+    const int l = acf_clamp(A.items[p], A.I, A.errflag, 5);
+    const float al = expf(A.tl[p] - gm) / D;
+    const float *Zl = A.Z + (int64_t)l * M * NP;
+    float lmax = -INFINITY;
+    for (int m = lane; m < M; m += 64) {                       // component scores, as k_acf_user (rows read four columns at a time)
+      const float *z = Zl + (int64_t)m * NP;
+      float sv = 0.f;
+      for (int j = 0; j < hc; j += 4) {
+        const float4 v = *(const float4 *)(z + j);             // NP % 32 == 0: the row holds ceil4(h) columns
+        sv = fmaf(w1c[j], fmaxf(uc[j] + v.x, 0.f), sv);
+        if (j + 1 < hc) sv = fmaf(w1c[j + 1], fmaxf(uc[j + 1] + v.y, 0.f), sv);
+        if (j + 2 < hc) sv = fmaf(w1c[j + 2], fmaxf(uc[j + 2] + v.z, 0.f), sv);
+        if (j + 3 < hc) sv = fmaf(w1c[j + 3], fmaxf(uc[j + 3] + v.w, 0.f), sv);
+      }
+      sv += bc1;
+      eb[m] = sv;
+      lmax = fmaxf(lmax, sv);
+    }
+    lmax = wave_max(lmax);
+    float lsum = 0.f, bv = -INFINITY;
+    int bi = INT_MAX;
+    for (int m = lane; m < M; m += 64) {                       // (each lane rereads only what it wrote)
+      const float e = expf(eb[m] - lmax);
+      eb[m] = e;
+      lsum += e;
+      if (e > bv) { bv = e; bi = m; }
+    }
+    lsum = wave_sum(lsum);
+    const float inv = 1.0f / lsum;
+#pragma unroll
+    for (int x = 32; x > 0; x >>= 1) {                         // arg-max, the lowest m among equal values
+      const float ov = __shfl_xor(bv, x, 64);
+      const int oi = __shfl_xor(bi, x, 64);
+      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) {
+      A.pos[o] = ps; A.hist_item[o] = l; A.peak[o] = bi;
+      A.alpha[o] = al; A.contrib[o] = cs; A.beta_peak[o] = bv * inv;
+    }
+    if (A.beta)
+      for (int m = lane; m < M; m += 64) A.beta[o * M + m] = eb[m] * inv;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_acf_unclaim(const int32_t *__restrict__ user, int64_t n, int U, int32_t *__restrict__ uslot) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n) return;
+  int u = user[b];
+  u = u < 0 ? 0 : (u >= U ? U - 1 : u);
+  uslot[u] = INT_MAX;
 }
 
 // ---- full-gradient mode: the backward through g'_u ------------------------------------------------------------------
@@ -1187,9 +1378,9 @@ static int acf_users(bprx_handle *h, const int32_t *users, int64_t n, const int3
   A.U = h->cfg.num_users; A.I = h->cfg.num_items; A.k = S->k; A.M = S->M; A.hc = S->hc; A.ha = S->ha; A.NP = S->NP;
   BprxProfScope ps(h, BPRX_PHASE_TRIPLET, s);
   if (aux)
-    hipLaunchKernelGGL(k_acf_user<true>, dim3((unsigned)n), dim3(256), acf_user_lds(S), s, A, users, n, uslot, out, aux);
+    hipLaunchKernelGGL(k_acf_user<ACF_USER_AUX>, dim3((unsigned)n), dim3(256), acf_user_lds(S), s, A, users, n, uslot, out, aux);
   else
-    hipLaunchKernelGGL(k_acf_user<false>, dim3((unsigned)n), dim3(256), acf_user_lds(S), s, A, users, n, uslot, out, aux);
+    hipLaunchKernelGGL(k_acf_user<ACF_USER_PLAIN>, dim3((unsigned)n), dim3(256), acf_user_lds(S), s, A, users, n, uslot, out, aux);
   BPRX_LAUNCH_CHECK(h, "k_acf_user");
   return BPRX_OK;
 }
@@ -1395,7 +1586,7 @@ void bprx_acf_free(bprx_handle *h) {
   AcfState *S = h->acf;
   if (!S) return;
   void *ptrs[] = {S->Z, S->GP, S->Wc, S->Wh, S->Wl, S->gp, S->Gup, S->dPi, S->uslot, S->imark, S->ilist, S->nlist,
-                  S->dZ, S->dGP, S->q, S->aux, S->UV, S->part, S->gwbuf};
+                  S->dZ, S->dGP, S->q, S->aux, S->UV, S->part, S->gwbuf, S->xt, S->xu};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   delete S;
@@ -1565,4 +1756,81 @@ extern "C" int bprx_acf_get_gradient(bprx_handle *h) {
   if (!h) return BPRX_E_INVALID;
   if (!h->bound || !h->acf) BPRX_FAIL(h, BPRX_E_STATE, "acf_get_gradient: the handle is not bound with bprx_bind_acf");
   return h->acf->grad_mode;
+}
+
+// Workspace of bprx_acf_explain, allocated at its first call and regrown when a call's histories are longer
+static int acf_explain_alloc(bprx_handle *h, int64_t nnz) {
+  AcfState *S = h->acf;
+  if (!S->xu) {
+    const size_t bytes = (2 + (size_t)h->cfg.num_users * (2 + S->hc)) * sizeof(float);
+    if (hipMalloc((void **)&S->xu, bytes) != hipSuccess || hipMemset(S->xu, 0, bytes) != hipSuccess) {
+      if (S->xu) (void)hipFree(S->xu);
+      S->xu = nullptr;
+      BPRX_FAIL(h, BPRX_E_NOMEM, "acf_explain: workspace allocation failed (%zu MB)", bytes >> 20);
+    }
+  }
+  if (nnz > S->xt_cap || !S->xt) {
+    BPRX_HIP(h, hipDeviceSynchronize());
+    if (S->xt) (void)hipFree(S->xt);
+    S->xt = nullptr;
+    S->xt_cap = 0;
+    const int64_t cap = nnz < 1 ? 1 : nnz;
+    if (hipMalloc((void **)&S->xt, (size_t)cap * sizeof(float)) != hipSuccess) {
+      S->xt = nullptr;
+      BPRX_FAIL(h, BPRX_E_NOMEM, "acf_explain: workspace allocation failed (%zu MB)", ((size_t)cap * 4) >> 20);
+    }
+    S->xt_cap = cap;
+    BPRX_HIP(h, hipMemcpy(S->xu, &cap, sizeof(int64_t), hipMemcpyHostToDevice));   // where the attention pass reads it
+  }
+  return BPRX_OK;
+}
+
+extern "C" int bprx_acf_explain(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t n, const int64_t *hist_ptr,
+                                const int32_t *hist_items, int32_t top, float *score, float *base, int32_t *pos, int32_t *hist_item,
+                                float *alpha, float *contrib, int32_t *peak, float *beta_peak, float *beta, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (!h->bound || !h->acf) BPRX_FAIL(h, BPRX_E_STATE, "acf_explain: the handle is not bound with bprx_bind_acf");
+  if (top < 1 || top > 32) BPRX_FAIL(h, BPRX_E_INVALID, "acf_explain: top = %d outside [1, 32]", (int)top);
+  if (n < 0 || n > ((int64_t)1 << 31) - 1) BPRX_FAIL(h, BPRX_E_INVALID, "acf_explain: n = %lld out of range", (long long)n);
+  if (n == 0) return BPRX_OK;
+  if (!user || !item || !hist_ptr || !hist_items || !score || !base || !pos || !hist_item || !alpha || !contrib || !peak || !beta_peak)
+    BPRX_FAIL(h, BPRX_E_INVALID, "acf_explain: null pointer");
+  AcfState *S = h->acf;
+  hipStream_t s = (hipStream_t)stream;
+  const int U = h->cfg.num_users;
+  int64_t nnz = 0;                                             // the one host read: the size of the per-entry workspace
+  BPRX_HIP(h, hipMemcpyAsync(&nnz, hist_ptr + U, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  BPRX_HIP(h, hipStreamSynchronize(s));
+  if (nnz < 0) BPRX_FAIL(h, BPRX_E_INVALID, "acf_explain: hist_ptr[U] = %lld", (long long)nnz);
+  int rc;
+  if ((rc = acf_explain_alloc(h, nnz))) return rc;
+  hipLaunchKernelGGL(k_acf_claim, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, user, n, U, S->uslot, h->errflag);
+  BPRX_LAUNCH_CHECK(h, "k_acf_claim");
+  if ((rc = acf_prepare(h, user, n, S->uslot, hist_ptr, hist_items, s))) {
+    // the next step's claim is an atomicMin against uslot: leave no claim of this call behind
+    hipLaunchKernelGGL(k_acf_unclaim, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, user, n, U, S->uslot);
+    (void)hipGetLastError();
+    return rc;
+  }
+  AcfUserArgs UA;
+  UA.Gu = h->t.Gu; UA.Pi = S->a.Pi; UA.Z = S->Z; UA.GP = S->GP;
+  UA.wcu = S->a.w[BPRX_ACF_C_WU]; UA.bc0 = S->a.w[BPRX_ACF_C_B0]; UA.w1c = S->a.w[BPRX_ACF_C_W1]; UA.bc1 = S->a.w[BPRX_ACF_C_B1];
+  UA.wiu = S->a.w[BPRX_ACF_I_WU]; UA.bi0 = S->a.w[BPRX_ACF_I_B0]; UA.w1i = S->a.w[BPRX_ACF_I_W1]; UA.bi1 = S->a.w[BPRX_ACF_I_B1];
+  UA.ptr = hist_ptr; UA.items = hist_items; UA.errflag = h->errflag;
+  UA.U = U; UA.I = h->cfg.num_items; UA.k = S->k; UA.M = S->M; UA.hc = S->hc; UA.ha = S->ha; UA.NP = S->NP;
+  hipLaunchKernelGGL(k_acf_user<ACF_USER_EXPLAIN>, dim3((unsigned)n), dim3(256), acf_user_lds(S), s, UA, user, n, S->uslot, S->xt,
+                     S->xu);
+  BPRX_LAUNCH_CHECK(h, "k_acf_user<explain>");
+  AcfExplainArgs A;
+  A.Gu = h->t.Gu; A.Gi = h->t.Gi; A.Pi = S->a.Pi; A.Z = S->Z; A.w1c = S->a.w[BPRX_ACF_C_W1]; A.bc1 = S->a.w[BPRX_ACF_C_B1];
+  A.tl = S->xt; A.ustat = S->xu + 2; A.ptr = hist_ptr; A.items = hist_items; A.errflag = h->errflag; A.ncap = S->xt_cap;
+  A.U = U; A.I = h->cfg.num_items; A.k = S->k; A.M = S->M; A.hc = S->hc; A.NP = S->NP; A.top = top;
+  A.score = score; A.base = base; A.pos = pos; A.hist_item = hist_item; A.alpha = alpha; A.contrib = contrib; A.peak = peak;
+  A.beta_peak = beta_peak; A.beta = beta;
+  const size_t lds = sizeof(float) * ((size_t)S->hc + 4 * (size_t)(S->hc + S->M));
+  hipLaunchKernelGGL(k_acf_explain, dim3((unsigned)((n + 3) / 4)), dim3(256), lds, s, A, user, item, n);
+  BPRX_LAUNCH_CHECK(h, "k_acf_explain");
+  hipLaunchKernelGGL(k_acf_unclaim, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, user, n, U, S->uslot);
+  BPRX_LAUNCH_CHECK(h, "k_acf_unclaim");
+  return BPRX_OK;
 }

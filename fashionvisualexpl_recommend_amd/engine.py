@@ -248,6 +248,34 @@ class Engine:
         _ffi.check(self.h, self.lib.bprx_acf_profiles(self.h, _ptr(u), u.numel(), _ptr(ptr), _ptr(items), _ptr(out), _stream()))
         return out
 
+    def acf_explain(self, users, items, top=5, lists=None, csr=None, maps=False):
+        """bprx_acf_explain: why the pairs (users[p], items[p]) score what they score.  x_ui = base + sum_l c_l over the user's
+        history (`lists` per user id, or a prebuilt `csr`; default: the bound training histories), c_l = alpha_l (Pi_l . Gi_i).
+        Returns a dict of device tensors: score, base [n]; pos, hist_item, alpha, contrib, peak, beta_peak [n, top] for the `top`
+        entries with the largest c_l (non-increasing; slots beyond the history: -1 in the int fields, 0 in the float ones); with
+        maps=True also beta [n, top, M], the component attention of every returned entry."""
+        u, i = as_index(users, self.device), as_index(items, self.device)
+        if u.numel() != i.numel():
+            raise ValueError("acf_explain: %d users for %d items" % (u.numel(), i.numel()))
+        ptr, hist = csr if csr is not None else (self.csr(lists) if lists is not None else getattr(self, "acf_train", None)
+                                                 or self.csr([[]] * self.U))
+        if hist.numel() == 0:
+            hist = torch.zeros(1, dtype=torch.int32, device=self.device)
+        n, top = u.numel(), int(top)
+        shape = (n, max(top, 0))
+        f = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)
+        g = lambda *s: torch.empty(s, dtype=torch.int32, device=self.device)
+        out = {"score": f(n), "base": f(n), "pos": g(*shape), "hist_item": g(*shape), "alpha": f(*shape), "contrib": f(*shape),
+               "peak": g(*shape), "beta_peak": f(*shape)}
+        if maps:
+            out["beta"] = f(n, max(top, 0), int(self.acf_F.shape[1]) if getattr(self, "acf", False) else 1)
+        p = lambda t: C.c_void_p(t.data_ptr())      # (an empty tensor still has to reach the library's argument checks)
+        _ffi.check(self.h, self.lib.bprx_acf_explain(self.h, p(u), p(i), n, p(ptr), p(hist), top, p(out["score"]), p(out["base"]),
+                                                     p(out["pos"]), p(out["hist_item"]), p(out["alpha"]), p(out["contrib"]),
+                                                     p(out["peak"]), p(out["beta_peak"]), p(out["beta"]) if maps else None,
+                                                     _stream()))
+        return out
+
     def bind_attentive(self, Gu, Gi, Bi, edges, color, cls, weights, dropout=0.5, seed=0, slots=None):
         """AttentiveFashion (bprx_bind_attentive) on a BPRMF engine: edges uint8 [I, 224, 224], color fp32 [I, Dc] (each row already
         divided by its own max-abs), cls fp32 [I, Dk], weights = the thirteen tensors keyed by _ffi.AF_WEIGHTS (shapes of

@@ -157,10 +157,11 @@ class Evaluator:
         }                                   # 'auc_t': auc_v is the reference's own aliasing (Evaluator.py:220)
         return print_results
 
-    def _store_recommendation_device(self, out):
+    def _store_recommendation_device(self, out, block_hook=None):
         """bprx_score_block + bprx_topk per user block; only rows whose list depends on the order of EQUAL scores (flagged
         by the kernel: the reference's order there is numpy's unstable argsort) are redone on the host, from the row the
-        kernel has already masked."""
+        kernel has already masked.  block_hook(users, items): called once per user block with the (u, item) of the rows just
+        written, in their order."""
         eng = self.model.engine
         self._metrics_device_csr()
         U = self.model.data.num_users
@@ -171,6 +172,7 @@ class Evaluator:
             idx, val, flag = idx.cpu().numpy(), val.cpu().numpy(), flag.cpu().numpy()
             redo = np.nonzero(flag)[0]
             rows = {int(r): sc[int(r)].cpu().numpy() for r in redo}          # few: ties are rare in real-valued scores
+            written = ([], [])
             for r in range(u1 - u0):
                 u = u0 + r
                 if r in rows:
@@ -182,6 +184,11 @@ class Evaluator:
                     top_k_id, top_k_score = idx[r, :kk], val[r, :kk]
                 for i, value in enumerate(top_k_id):
                     out.write(str(u) + '\t' + str(value) + '\t' + str(top_k_score[i]) + '\n')
+                if block_hook is not None:
+                    written[0].extend([u] * len(top_k_id))
+                    written[1].extend(int(v) for v in top_k_id)
+            if block_hook is not None and written[0]:
+                block_hook(*written)
 
     def _metrics_device_csr(self):
         if getattr(self, "_csr", None) is None:
@@ -195,20 +202,30 @@ class Evaluator:
 
     def store_recommendation(self, path=""):
         """Evaluator.py:225-239: per user mask train items, top-k by argsort, 'u\\titem\\tscore' rows."""
-        if getattr(self.model, "engine", None) is not None and not getattr(self, "force_host", False) and self.k <= 1024:
-            with open(path, 'w') as out:
-                self._store_recommendation_device(out)
-            return
         with open(path, 'w') as out:
-            for u0, sc in self._score_blocks():
-                for r in range(sc.shape[0]):
-                    u = u0 + r
-                    row = sc[r]
-                    row[self.data.training_list[u]] = -np.inf
-                    top_k_id = row.argsort()[-self.k:][::-1]
-                    top_k_score = row[top_k_id]
-                    for i, value in enumerate(top_k_id):
-                        out.write(str(u) + '\t' + str(value) + '\t' + str(top_k_score[i]) + '\n')
+            self._store_recommendation_rows(out)
+
+    def _store_recommendation_rows(self, out, block_hook=None):
+        """The rows of store_recommendation: on the device where the model has an engine and top_k fits bprx_topk, else (or with
+        force_host) on the host.  block_hook as in _store_recommendation_device."""
+        if getattr(self.model, "engine", None) is not None and not getattr(self, "force_host", False) and self.k <= 1024:
+            self._store_recommendation_device(out, block_hook)
+            return
+        for u0, sc in self._score_blocks():
+            written = ([], [])
+            for r in range(sc.shape[0]):
+                u = u0 + r
+                row = sc[r]
+                row[self.data.training_list[u]] = -np.inf
+                top_k_id = row.argsort()[-self.k:][::-1]
+                top_k_score = row[top_k_id]
+                for i, value in enumerate(top_k_id):
+                    out.write(str(u) + '\t' + str(value) + '\t' + str(top_k_score[i]) + '\n')
+                if block_hook is not None:
+                    written[0].extend([u] * len(top_k_id))
+                    written[1].extend(int(v) for v in top_k_id)
+            if block_hook is not None and written[0]:
+                block_hook(*written)
 
     def store_recommendation_grads(self, path=""):
         """Evaluator.py:261-275 (GradFashion): for every user the items training_list[u] + validation_list[u] + test_list[u],
@@ -261,3 +278,26 @@ class Evaluator:
                     for i, value in enumerate(top_k_id):
                         out.write(str(u) + '\t' + str(value) + '\t' + str(top_k_score[i]) + '\t' + str(a[i, 0]) + '\t' +
                                   str(a[i, 1]) + '\t' + str(a[i, 2]) + '\n')
+
+    def store_recommendation_acf(self, path_recs="", path_expl="", top=5):
+        """ACF: `path_recs` exactly as store_recommendation writes it (the same device or host path), and for every row written there the rows
+        'u\\ti\\tscore\\tbase\\trank\\thist_item\\talpha\\tcontribution\\tpeak_m\\tbeta_peak' in `path_expl`: the `top` entries of the
+        user's history that contribute most to x_ui = base + sum_l alpha_l (Pi_l . Gi_i), rank 0 first (bprx_acf_explain, one call
+        per user block, with the evaluation histories the scores were made with: training + validation, ACF.py:220).  A user
+        with an empty history gets one row with rank = hist_item = peak_m = -1 and zeros, so that base is still recorded."""
+        eng = self.model.engine
+        csr = eng.acf_eval if eng.acf_eval is not None else eng.acf_train
+        with open(path_recs, 'w') as out, open(path_expl, 'w') as ex:
+            def block(users, items):
+                e = {n: v.cpu().numpy() for n, v in eng.acf_explain(users, items, top, csr=csr).items()}
+                for r, (u, i) in enumerate(zip(users, items)):
+                    head = str(u) + '\t' + str(i) + '\t' + str(e["score"][r]) + '\t' + str(e["base"][r]) + '\t'
+                    if e["pos"][r, 0] < 0:
+                        ex.write(head + '-1\t-1\t0.0\t0.0\t-1\t0.0\n')
+                        continue
+                    for s in range(e["pos"].shape[1]):
+                        if e["pos"][r, s] < 0:
+                            break
+                        ex.write(head + str(s) + '\t' + str(e["hist_item"][r, s]) + '\t' + str(e["alpha"][r, s]) + '\t' +
+                                 str(e["contrib"][r, s]) + '\t' + str(e["peak"][r, s]) + '\t' + str(e["beta_peak"][r, s]) + '\n')
+            self._store_recommendation_rows(out, block)

@@ -448,6 +448,9 @@ class ACF(BPRMF):
         self.acf_gradient = getattr(params, "acf_gradient", None) or "detached"
         if self.acf_gradient not in ("detached", "full"):
             raise ValueError("ACF: acf_gradient is 'detached' or 'full' (got %r)" % (self.acf_gradient,))
+        self.acf_explain = int(getattr(params, "acf_explain", 0) or 0)            # rows per recommendation in expl-*; 0: none
+        if not 0 <= self.acf_explain <= 32:
+            raise ValueError("ACF: acf_explain is 0 (off) .. 32 (got %r)" % (self.acf_explain,))
         super().__init__(data, params, init)
         self.directory_parameters = f'batch_{params.batch_size}' \
                                     f'-K_{params.embed_k}' \
@@ -561,6 +564,27 @@ class ACF(BPRMF):
         return xui, self.Gu[u], self.Gi[i], self.Pi[i]
 
     __call__ = call
+
+    # ---- explanations: x_ui = g_u.Gi_i + sum_l alpha_l (Pi_l.Gi_i), both attention levels read out ----------------------------
+    def explain(self, users, items, top=5, lists=None, maps=False):
+        """The `top` history entries that contribute most to each pair's score (Engine.acf_explain) as numpy arrays: score, base
+        [n]; pos, hist_item, alpha, contrib, peak, beta_peak [n, top]; beta [n, top, M] with maps=True (reshape a row to
+        feature_shape[:2] for the H x W map).  Default histories: the training lists."""
+        return {n: v.cpu().numpy() for n, v in self.engine.acf_explain(users, items, top, lists, maps=maps).items()}
+
+    def explain_ui(self, u, items, top=5, lists=None, maps=False):
+        """explain() for one user and several items."""
+        items = [int(i) for i in np.asarray(items).reshape(-1)]
+        return self.explain([int(u)] * len(items), items, top, lists, maps)
+
+    def _store_recs(self, path):
+        """recs-* / best-recs-* as every model writes them; with params.acf_explain = L > 0 also expl-* / best-expl-* next to them."""
+        if self.acf_explain <= 0:
+            return super()._store_recs(path)
+        d, f = os.path.split(path)
+        if not (f.startswith("recs-") or f.startswith("best-recs-")):
+            raise ValueError("ACF: %s is neither a recs-* nor a best-recs-* path" % path)
+        self.evaluator.store_recommendation_acf(path, os.path.join(d, f.replace("recs-", "expl-", 1)), self.acf_explain)
 
 
 def load_attentive_inputs(dataset, num_items):

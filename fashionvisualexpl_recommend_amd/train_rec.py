@@ -46,6 +46,9 @@ def parse_args(argv=None):
     parser.add_argument('--acf_gradient', default='detached', choices=['detached', 'full'],
                         help="acf: 'detached' = the reference's step (g'_u is a constant of the tape, ACF.py:203-208); 'full' = the "
                              "same loss differentiated through both attention levels")
+    parser.add_argument('--acf_explain', type=int, default=0,
+                        help="acf: also write expl-* / best-expl-* files with the L (1..32) history entries that contribute most to "
+                             "every recommended (u, i): alpha, contribution and the peak of the component attention; 0 = off")
     parser.add_argument('--attention_layers', nargs='+', type=int, default=[64, 1],
                         help='attentive_fashion: attention layers, two ints "h 1" (train_rec.py:38)')
     # not in the reference
@@ -74,6 +77,10 @@ def parse_args(argv=None):
             parser.error("--%s takes two ints 'h 1' with h > 0 (got %s)" % (name, " ".join(str(x) for x in v)))
     if args.acf_gradient != 'detached' and args.rec != 'acf':
         parser.error("--acf_gradient %s needs --rec acf (got --rec %s)" % (args.acf_gradient, args.rec))
+    if not 0 <= args.acf_explain <= 32:
+        parser.error("--acf_explain takes 0 (off) .. 32 (got %s)" % args.acf_explain)
+    if args.acf_explain != 0 and args.rec != 'acf':
+        parser.error("--acf_explain %s needs --rec acf (got --rec %s)" % (args.acf_explain, args.rec))
     if not 0.0 <= args.dropout < 1.0:
         parser.error("--dropout takes a rate in [0, 1) (got %s)" % args.dropout)
     return args

@@ -229,6 +229,27 @@ BPRX_API int bprx_bind_acf(bprx_handle *h, const bprx_tables *t, const bprx_acf 
    out fp32 [n, k] = g'_u. */
 BPRX_API int bprx_acf_profiles(bprx_handle *h, const int32_t *users, int64_t n, const int64_t *hist_ptr,
                                const int32_t *hist_items, float *out, void *stream);
+/* Why pair p = (user[p], item[p]) scores what it scores, with the histories of the given CSR (indexed by user id, as for
+   bprx_acf_profiles).  The score decomposes exactly over the history:
+       x_ui = g_u.Gi_i + sum_{l in P(u)} alpha_l (Pi_l.Gi_i) = base + sum_l c_l
+   Outputs (device, fp32 / int32): score[n] (the quantity bprx_score_pairs returns with that history), base[n], and per pair the
+   `top` history ENTRIES with the largest c_l in non-increasing order of c_l, bit-equal c_l by ascending position (every CSR
+   position is an entry: a repeated item is several entries, as it is in the softmax), each [n, top]:
+       pos        position in the user's list, 0-based          hist_item  the item id there
+       alpha      alpha_l                                       contrib    c_l
+       peak       argmax_m beta_lm (the lowest m among equals)  beta_peak  beta_l at the peak (== beta[.., peak] bit for bit)
+       beta       [n, top, M], the whole row beta_l; NULL: not written
+   Slots beyond the history length (all of them for an empty history): pos = hist_item = peak = -1 and 0.0f in every float field.
+   Any n >= 0 (not bounded by max_batch), duplicate pairs and users allowed; 1 <= top <= 32 (BPRX_E_INVALID otherwise);
+   BPRX_E_STATE on a handle that is not ACF-bound; indices out of range are clamped and reported by bprx_sync_check.  The call
+   reads the tables and writes its outputs and library workspace only (Z / GP scratch, a logit per history entry and h + 2 floats
+   per user, allocated at the first call): step index, Adam slots and gradient workspaces are untouched.  It reads hist_ptr[U]
+   on the host to size that workspace, so it waits once for the work queued on `stream`.  No float atomics: the outputs are
+   reproducible run to run. */
+BPRX_API int bprx_acf_explain(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t n, const int64_t *hist_ptr,
+                              const int32_t *hist_items, int32_t top, float *score, float *base, int32_t *pos,
+                              int32_t *hist_item, float *alpha, float *contrib, int32_t *peak, float *beta_peak, float *beta,
+                              void *stream);
 enum { BPRX_ACF_GRAD_DETACHED = 0, BPRX_ACF_GRAD_FULL = 1 };
 BPRX_API int bprx_acf_set_gradient(bprx_handle *h, int mode);
 BPRX_API int bprx_acf_get_gradient(bprx_handle *h);
