@@ -3,13 +3,15 @@
 //
 // Sample rows: a step of B triplets has 2B rows, row r < B = (user r, positive r), row B + r = (user r, negative r).  An item that
 // occurs in several rows is OWNED by its first row (islot[item], k_af_claim); a user by its first triplet (uslot[user]).
-//   k_af_conv<false>  edge encoder forward, one workgroup per owner row: the 228 x 232 zero-padded uint8 image in LDS, im2col
+//   k_af_conv<FWD>    edge encoder forward, one workgroup per owner row: the 228 x 232 zero-padded uint8 image in LDS, im2col
 //                     fragments of 2 x 8 pixel tiles read from it, v_mfma_f32_16x16x32_bf16 with the conv weights split into
 //                     three bf16 terms (pixels 0..255 are exact in bf16, 1/255 is applied to the sum), bias + relu + 2x2 max in
 //                     the accumulator registers (a lane holds the four positions of a window), global mean -> pool [row, 64]
-//   k_af_conv<true>   edge encoder backward: recomputes each tile exactly as the forward, turns the (argmax, > 0) decisions into
+//   k_af_conv<BWD>    edge encoder backward: recomputes each tile exactly as the forward, turns the (argmax, > 0) decisions into
 //                     0/1 bf16 B operands and counts  cnt[tap, c] = sum_windows pixel(argmax + tap) * [c active]  with a second
 //                     MFMA -- integer sums below 2^24, exact in any order; dW = cnt * g_c / (12544 * 255), db = #active * g_c / 12544
+//   k_af_conv<CELL>   bprx_af_explain: the forward's tiles, summed per cell of a G x G grid instead of over the image
+//   k_af_rank, k_af_explain   bprx_af_explain: slots of the distinct items; one wave per pair: v, the three parts, the cells, the peak
 //   k_af_gemm         the one small fp32 GEMM of the dense encoders, forward and backward (plain HIP, 64 x 64 tiles)
 //   k_af_triplet      attention forward + backward, one wave per triplet (both sides)
 //   k_af_rowsum       sums the per-row gradients of equal items / users in ascending row order (no float atomics)
@@ -53,6 +55,9 @@ struct AfState {
   float *cpart, *cred;            // [R, AF_CPART] conv gradient partials; [64, AF_CPART] column-sum stage
   float *g[BPRX_AF_NW];           // gradients of the tensors
   float *Call;                    // [3, I, k] encodings of every item (evaluation)
+  float *E;                       // bprx_af_explain: [E_items, G * G, 64] cell sums of a chunk of distinct items (first use)
+  size_t E_bytes;
+  int32_t *erank;                 // bprx_af_explain: [R] number of owner rows before a row = the slot of its item
   bool eval_valid;
 };
 
@@ -165,16 +170,36 @@ __device__ __forceinline__ bf16x8 af_patch_frag(const uint8_t *__restrict__ img,
   return __builtin_bit_cast(bf16x8, v);
 }
 
-template <bool BWD>
+// MODE: AF_CONV_FWD, AF_CONV_BWD (above), or AF_CONV_CELL: keeps A per region instead of averaging it away,
+//   E[e][cell][c] = sum over the windows p of the cell of A_c(p),  cell = (wy / cs) * G + wx / cs,  cs = 112 / G,
+// for the owner row's slot e = erank[r] - e0 of the chunk [e0, e0 + ecap).  A window row is computed by the four waves into an LDS
+// stage [112 windows][64] (the tiles of four windows may straddle cells: nothing is summed in the MFMA layout), then thread
+// (b, c) = (wave + 4 i, lane) adds the cs windows of cell column b (four interleaved partial sums, ascending wx) to its running,
+// compensated sum, window rows ascending, and stores the cell after its last row: one fixed order per cell, whichever wave
+// produced the window, and no atomics.
+enum { AF_CONV_FWD = 0, AF_CONV_BWD = 1, AF_CONV_CELL = 2 };
+#define AF_WROW 112               // pooling windows per row / column
+struct AfCells { float *E; const int32_t *erank; int G, e0, ecap; };
+template <int MODE> struct AfConvOut { typedef float *__restrict__ T; };      // forward: unused; backward: cpart
+template <> struct AfConvOut<AF_CONV_CELL> { typedef AfCells T; };
+
+template <int MODE>
 __global__ __launch_bounds__(256) void k_af_conv(const uint8_t *__restrict__ edges, const float *__restrict__ cw,
                                                  const float *__restrict__ cb, const int32_t *__restrict__ rowitem,
                                                  const int32_t *__restrict__ islot, int64_t n, float *__restrict__ pool,
-                                                 const float *__restrict__ gsum, float *__restrict__ cpart) {
-  __shared__ __attribute__((aligned(16))) uint8_t smem[AF_LROWS * AF_LP];     // the image; afterwards the reduction stage
+                                                 const float *__restrict__ gsum, typename AfConvOut<MODE>::T cpart) {
+  constexpr bool BWD = MODE == AF_CONV_BWD, CELL = MODE == AF_CONV_CELL;
+  // the image; afterwards the reduction stage.  CELL: followed by the stage of one window row
+  __shared__ __attribute__((aligned(16))) uint8_t smem[AF_LROWS * AF_LP + (CELL ? AF_WROW * AF_CH * 4 : 0)];
   const int64_t r = blockIdx.x;
   if (r >= n) return;
   const int item = rowitem[r];
   if (islot && islot[item] != (int32_t)r) return;                             // another row owns this item
+  int eslot = 0;
+  if constexpr (CELL) {
+    eslot = cpart.erank[r] - cpart.e0;
+    if ((unsigned)eslot >= (unsigned)cpart.ecap) return;                      // another chunk of the call holds this item
+  }
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, cl = lane & 15;
   uint32_t *sm32 = (uint32_t *)smem;
   for (int e = tid; e < AF_LROWS * AF_LP / 4; e += 256) sm32[e] = 0u;
@@ -222,7 +247,13 @@ __global__ __launch_bounds__(256) void k_af_conv(const uint8_t *__restrict__ edg
       for (int ct = 0; ct < 4; ++ct) cnt[mt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   // tiles of 4 windows: 28 per window row, 3136 per image; wave w takes the pairs (2p, 2p + 1), p = w, w + 4, ...
-  for (int pr = w; pr < 1568; pr += 4) {
+  // (CELL: of one window row at a time, 14 pairs, then the row is added to the cells)
+  constexpr int NROUND = CELL ? AF_WROW : 1, NPR = CELL ? 14 : 1568;
+  float *stage = (float *)(smem + AF_LROWS * AF_LP);
+  float cacc[CELL ? AF_WROW / 4 : 1], ccmp[4];   // CELL: running cell sums and their compensations
+  for (int wr = 0; wr < NROUND; ++wr) {
+  for (int pq = w; pq < NPR; pq += 4) {
+    const int pr = CELL ? 14 * wr + pq : pq;
     uint32_t ind[4][4];                         // backward: [ct][2 T + (q >> 1)] two 0/1 bf16 of tile T
 #pragma unroll
     for (int T = 0; T < 2; ++T) {
@@ -242,7 +273,9 @@ __global__ __launch_bounds__(256) void k_af_conv(const uint8_t *__restrict__ edg
           const float v = fmaf(acc[q], inv255, bias[ct]);
           if (v > mx) { mx = v; am = q; }       // the first maximum wins a tie
         }
-        if (!BWD) {
+        if (CELL) {
+          stage[(wx0 + g) * AF_CH + 16 * ct + cl] = fmaxf(mx, 0.f);
+        } else if (!BWD) {
           psum[ct] += fmaxf(mx, 0.f);
         } else {
           const bool act = mx > 0.f;            // relu'(0) = 0
@@ -280,6 +313,35 @@ __global__ __launch_bounds__(256) void k_af_conv(const uint8_t *__restrict__ edg
       }
     }
   }
+  if constexpr (CELL) {
+    __syncthreads();
+    const int G = cpart.G, cs = AF_WROW / G, ca = wr / cs, rin = wr - ca * cs;
+    float *Eo = cpart.E + ((size_t)eslot * G * G + (size_t)ca * G) * AF_CH + lane;
+#pragma unroll
+    for (int i = 0; i < AF_WROW / 4; ++i) {
+      const int b = w + 4 * i;                   // cell column of this thread; its channel is the lane
+      if (b < G) {
+        const float *sp = stage + b * cs * AF_CH + lane;
+        // the row's share in four interleaved partial sums, then a compensated (Kahan) add over the rows: a plain running sum
+        // over the 12 544 windows of a G = 1 cell rounds every add at the ulp of the whole cell
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+        int q = 0;
+        for (; q + 3 < cs; q += 4) {
+          a0 += sp[q * AF_CH]; a1 += sp[(q + 1) * AF_CH]; a2 += sp[(q + 2) * AF_CH]; a3 += sp[(q + 3) * AF_CH];
+        }
+        for (; q < cs; ++q) a0 += sp[q * AF_CH];
+        // (compensated for cell columns below 16 only: a finer grid, G >= 28, sums at most four rows per cell)
+        const float s0 = rin == 0 ? 0.f : cacc[i], c0 = (i < 4 && rin != 0) ? ccmp[i < 4 ? i : 0] : 0.f;
+        const float y = ((a0 + a1) + (a2 + a3)) - c0, t = s0 + y;
+        if (i < 4) ccmp[i] = (t - s0) - y;
+        cacc[i] = t;
+        if (rin == cs - 1) Eo[b * AF_CH] = t;
+      }
+    }
+    __syncthreads();
+  }
+  }
+  if constexpr (CELL) return;
   __syncthreads();                               // the image is no longer read: its LDS becomes the reduction stage
   float *red = (float *)smem;                    // [4 waves][4 g][64] sums, then (backward) [4 waves][32 taps][64] counts
 #pragma unroll
@@ -292,13 +354,13 @@ __global__ __launch_bounds__(256) void k_af_conv(const uint8_t *__restrict__ edg
         for (int q = 0; q < 4; ++q) cs[(w * 32 + 16 * mt + 4 * g + q) * AF_CH + 16 * ct + cl] = cnt[mt][ct][q];
   }
   __syncthreads();
-  if (!BWD) {
+  if constexpr (MODE == AF_CONV_FWD) {
     if (tid < AF_CH) {
       float s = 0.f;
       for (int q = 0; q < 16; ++q) s += red[q * AF_CH + tid];
       pool[r * AF_CH + tid] = s * (1.0f / AF_WIN);
     }
-  } else {
+  } else if constexpr (BWD) {
     const float *cs = red + 16 * AF_CH;
     for (int e = tid; e < AF_CPART; e += 256) {
       const int t = e / AF_CH, c = e % AF_CH;
@@ -469,6 +531,97 @@ __global__ __launch_bounds__(256) void k_af_pairs(AfAtt A, const int32_t *__rest
   if (lane == 0) {
     x[r] = s;
     if (alpha) { alpha[r * 3] = al[0]; alpha[r * 3 + 1] = al[1]; alpha[r * 3 + 2] = al[2]; }
+  }
+}
+
+// ---- explanations (bprx_af_explain) ------------------------------------------------------------------------------------------------
+// erank[r] = number of owner rows before row r (one workgroup, ascending rows): the slot of an owner row's item among the distinct items
+__global__ __launch_bounds__(256) void k_af_rank(const int32_t *__restrict__ rowitem, const int32_t *__restrict__ islot, int64_t n,
+                                                 int32_t *__restrict__ erank) {
+  __shared__ int wsum[4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int base = 0;
+  for (int64_t r0 = 0; r0 < n; r0 += 256) {
+    const int64_t r = r0 + tid;
+    const bool own = r < n && islot[rowitem[r]] == (int32_t)r;
+    const unsigned long long mk = __ballot(own);
+    if (lane == 0) wsum[w] = __popcll(mk);
+    __syncthreads();
+    int off = base;
+    for (int q = 0; q < w; ++q) off += wsum[q];
+    if (r < n) erank[r] = off + __popcll(mk & ((1ull << lane) - 1ull));
+    base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    __syncthreads();
+  }
+}
+
+// One wave per pair r whose item's cell sums are in this chunk of E.  alpha is what k_af_pairs wrote for the pair (held fixed).
+//   t_l = sum_k g_uk c_lk g_ik, parts = alpha_l t_l;   v_c = sum_k W2e[c, k] g_uk g_ik  (lane = channel);
+//   cell j = (alpha_e / 12544) sum_c E[j, c] v_c  (lane-strided over the cells, c ascending);  peak = the largest cell, lowest j among equals
+// LDS per wave: p[k] = g_u * g_i, v[64]
+struct AfExpl {
+  AfAtt A;
+  const float *W2e, *E, *alpha;
+  const int32_t *rowuser, *rowitem, *islot, *erank;
+  int64_t n;
+  int G, e0, ecap;
+  float *parts, *map, *peak_val;
+  int32_t *peak_cell;
+};
+__global__ __launch_bounds__(256) void k_af_explain(AfExpl X) {
+  extern __shared__ float sm[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, k = X.A.k;
+  const int64_t r = (int64_t)blockIdx.x * 4 + w;
+  if (r >= X.n) return;
+  const int it = X.rowitem[r], u = X.rowuser[r];
+  const int e = X.erank[X.islot[it]] - X.e0;
+  if ((unsigned)e >= (unsigned)X.ecap) return;
+  float *p = sm + (size_t)w * (k + AF_CH), *vs = p + k;
+  float t[3] = {0.f, 0.f, 0.f};
+  for (int c = lane; c < k; c += 64) {
+    const float pg = X.A.Gu[(int64_t)u * k + c] * X.A.Gi[(int64_t)it * k + c];
+    p[c] = pg;
+#pragma unroll
+    for (int l = 0; l < 3; ++l) t[l] = fmaf(pg, X.A.C[((int64_t)l * X.A.ldr + r) * k + c], t[l]);
+  }
+#pragma unroll
+  for (int l = 0; l < 3; ++l) t[l] = af_wave_sum(t[l]);
+  af_wave_sync();
+  {
+    const float *wr = X.W2e + (int64_t)lane * k;
+    float v = 0.f;
+    for (int c = 0; c < k; ++c) v = fmaf(wr[c], p[c], v);
+    vs[lane] = v;
+  }
+  af_wave_sync();
+  const float al[3] = {X.alpha[r * 3], X.alpha[r * 3 + 1], X.alpha[r * 3 + 2]};
+  if (lane < 3) X.parts[r * 3 + lane] = lane == 0 ? al[0] * t[0] : lane == 1 ? al[1] * t[1] : al[2] * t[2];
+  const float scale = al[1] * (1.0f / AF_WIN);
+  const int G2 = X.G * X.G;
+  const float *Er = X.E + (size_t)e * G2 * AF_CH;
+  float bv = -INFINITY;
+  int bi = INT_MAX;
+  for (int j = lane; j < G2; j += 64) {
+    const float4 *row = (const float4 *)(Er + (size_t)j * AF_CH);
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < AF_CH / 4; ++q) {
+      const float4 a = row[q];
+      s = fmaf(a.x, vs[4 * q], s); s = fmaf(a.y, vs[4 * q + 1], s); s = fmaf(a.z, vs[4 * q + 2], s); s = fmaf(a.w, vs[4 * q + 3], s);
+    }
+    s *= scale;
+    if (X.map) X.map[r * G2 + j] = s;
+    if (s > bv) { bv = s; bi = j; }               // ascending j: the first of equal cells stays
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+  }
+  if (lane == 0) {
+    X.peak_cell[r] = bi == INT_MAX ? 0 : bi;
+    X.peak_val[r] = bv;
   }
 }
 
@@ -809,7 +962,7 @@ static int af_encode_rows(bprx_handle *h, int64_t n, bool dedupe, const AfDrop &
   int rc;
   {
     BprxProfScope ps(h, BPRX_PHASE_PROJ_FWD, s);
-    hipLaunchKernelGGL(k_af_conv<false>, dim3((unsigned)n), dim3(256), 0, s, S->a.edges, S->a.w[BPRX_AF_EDG_CW], S->a.w[BPRX_AF_EDG_CB],
+    hipLaunchKernelGGL(k_af_conv<AF_CONV_FWD>, dim3((unsigned)n), dim3(256), 0, s, S->a.edges, S->a.w[BPRX_AF_EDG_CW], S->a.w[BPRX_AF_EDG_CB],
                        S->rowitem, islot, n, S->pool, (const float *)nullptr, (float *)nullptr);
     BPRX_LAUNCH_CHECK(h, "k_af_conv<fwd>");
   }
@@ -903,7 +1056,7 @@ static int af_step_body(bprx_handle *h, const int32_t *user, const int32_t *pos,
     BPRX_LAUNCH_CHECK(h, "k_af_rowsum");
     {
       BprxProfScope ps(h, BPRX_PHASE_PROJ_BWD, s);
-      hipLaunchKernelGGL(k_af_conv<true>, dim3((unsigned)R), dim3(256), 0, s, S->a.edges, S->a.w[BPRX_AF_EDG_CW], S->a.w[BPRX_AF_EDG_CB],
+      hipLaunchKernelGGL(k_af_conv<AF_CONV_BWD>, dim3((unsigned)R), dim3(256), 0, s, S->a.edges, S->a.w[BPRX_AF_EDG_CW], S->a.w[BPRX_AF_EDG_CB],
                          S->rowitem, S->islot, R, (float *)nullptr, S->gsum, S->cpart);
       BPRX_LAUNCH_CHECK(h, "k_af_conv<bwd>");
     }
@@ -966,6 +1119,44 @@ int bprx_af_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int6
   return BPRX_OK;
 }
 
+// bprx_af_explain after its argument checks and with the workspace in place.  Items are claimed (islot); the caller releases them.
+static int af_explain_body(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t n, int G, float *x, float *alpha,
+                           float *parts, float *map, int32_t *peak_cell, float *peak_val, int64_t ecap, hipStream_t s) {
+  AfState *S = h->af;
+  int rc;
+  hipLaunchKernelGGL(k_af_claim, dim3(af_blocks(n, 256)), dim3(256), 0, s, item, item, n, n, user, n, h->cfg.num_items, h->cfg.num_users,
+                     S->rowitem, S->rowuser, S->islot, (int32_t *)nullptr, h->errflag);
+  BPRX_LAUNCH_CHECK(h, "k_af_claim");
+  // x and alpha: the kernels of bprx_af_attention_pairs; the conv runs on the owner rows only and gives the same bits per item
+  const AfDrop d = af_drop(S, 0, false);
+  if ((rc = af_encode_rows(h, n, true, d, S->C, S->R, s))) return rc;
+  hipLaunchKernelGGL(k_af_pairs, dim3(af_blocks(n, 4)), dim3(256), 16 * sizeof(float) * (size_t)S->k, s, af_att(h, S->C, S->R), S->rowuser,
+                     S->rowitem, n, x, alpha);
+  BPRX_LAUNCH_CHECK(h, "k_af_pairs");
+  hipLaunchKernelGGL(k_af_rank, dim3(1), dim3(256), 0, s, S->rowitem, S->islot, n, S->erank);
+  BPRX_LAUNCH_CHECK(h, "k_af_rank");
+  // the distinct items in chunks of ecap slots (their number is not read back: at most n, the later chunks may be empty)
+  for (int64_t e0 = 0; e0 < n; e0 += ecap) {
+    AfCells Cc;
+    Cc.E = S->E; Cc.erank = S->erank; Cc.G = G; Cc.e0 = (int)e0; Cc.ecap = (int)ecap;
+    {
+      BprxProfScope ps(h, BPRX_PHASE_PROJ_FWD, s);
+      hipLaunchKernelGGL(k_af_conv<AF_CONV_CELL>, dim3((unsigned)n), dim3(256), 0, s, S->a.edges, S->a.w[BPRX_AF_EDG_CW],
+                         S->a.w[BPRX_AF_EDG_CB], S->rowitem, S->islot, n, (float *)nullptr, (const float *)nullptr, Cc);
+      BPRX_LAUNCH_CHECK(h, "k_af_conv<cell>");
+    }
+    AfExpl X;
+    X.A = af_att(h, S->C, S->R);
+    X.W2e = S->a.w[BPRX_AF_EDG_W2]; X.E = S->E; X.alpha = alpha;
+    X.rowuser = S->rowuser; X.rowitem = S->rowitem; X.islot = S->islot; X.erank = S->erank;
+    X.n = n; X.G = G; X.e0 = (int)e0; X.ecap = (int)ecap;
+    X.parts = parts; X.map = map; X.peak_val = peak_val; X.peak_cell = peak_cell;
+    hipLaunchKernelGGL(k_af_explain, dim3(af_blocks(n, 4)), dim3(256), 4 * sizeof(float) * ((size_t)S->k + AF_CH), s, X);
+    BPRX_LAUNCH_CHECK(h, "k_af_explain");
+  }
+  return BPRX_OK;
+}
+
 // encodings of items first .. first + n (consecutive) or of a list, in chunks of R rows, into out [3, ld, k] at row offset
 static int af_encode_many(bprx_handle *h, const int32_t *items, int64_t n, float *out, int64_t ld, hipStream_t s) {
   AfState *S = h->af;
@@ -1023,7 +1214,7 @@ void bprx_af_free(bprx_handle *h) {
   AfState *S = h->af;
   if (!S) return;
   void *ptrs[] = {S->islot, S->uslot, S->rowitem, S->rowuser, S->pool, S->PD, S->Hc, S->Hk, S->C, S->dC, S->A6, S->Hid, S->dHid, S->da,
-                  S->dGuS, S->dGiS, S->dH, S->dPD, S->gsum, S->cpart, S->cred, S->Call};
+                  S->dGuS, S->dGiS, S->dH, S->dPD, S->gsum, S->cpart, S->cred, S->Call, S->E, S->erank};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (int q = 0; q < BPRX_AF_NW; ++q)
@@ -1137,6 +1328,42 @@ extern "C" int bprx_af_attention_pairs(bprx_handle *h, const int32_t *user, cons
   if (n == 0) return BPRX_OK;
   if (!user || !item || !x) BPRX_FAIL(h, BPRX_E_INVALID, "af_attention_pairs: null pointer");
   return bprx_af_pairs(h, user, item, n, x, alpha, (hipStream_t)stream);
+}
+
+extern "C" int bprx_af_explain(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t n, int32_t grid, float *x, float *alpha,
+                               float *parts, float *map, int32_t *peak_cell, float *peak_val, void *stream) {
+  AF_CHECK("af_explain")
+  if (n < 0 || n > h->cfg.max_batch) BPRX_FAIL(h, BPRX_E_INVALID, "af_explain: n = %lld outside [0, max_batch]", (long long)n);
+  if (grid < 1 || grid > AF_WROW || AF_WROW % grid != 0)
+    BPRX_FAIL(h, BPRX_E_INVALID, "af_explain: grid = %d is not a divisor of %d", grid, AF_WROW);
+  if (n == 0) return BPRX_OK;
+  if (!user || !item || !x || !alpha || !parts || !peak_cell || !peak_val) BPRX_FAIL(h, BPRX_E_INVALID, "af_explain: null pointer");
+  AfState *S = h->af;
+  // E: the cell sums of at most ecap distinct items at a time, at most 1 GiB
+  const size_t per = (size_t)grid * grid * AF_CH * sizeof(float);
+  int64_t ecap = (int64_t)(((size_t)1 << 30) / per);
+  if (ecap > n) ecap = n;
+  if (!S->erank && hipMalloc((void **)&S->erank, (size_t)S->R * sizeof(int32_t)) != hipSuccess) {
+    S->erank = nullptr;
+    BPRX_FAIL(h, BPRX_E_NOMEM, "af_explain: workspace allocation failed");
+  }
+  if ((size_t)ecap * per > S->E_bytes) {
+    BPRX_HIP(h, hipDeviceSynchronize());                      // earlier calls may still read the old one
+    if (S->E) (void)hipFree(S->E);
+    S->E = nullptr;
+    S->E_bytes = 0;
+    if (hipMalloc((void **)&S->E, (size_t)ecap * per) != hipSuccess) {
+      S->E = nullptr;
+      BPRX_FAIL(h, BPRX_E_NOMEM, "af_explain: workspace allocation failed (%zu MB)", ((size_t)ecap * per) >> 20);
+    }
+    S->E_bytes = (size_t)ecap * per;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = af_explain_body(h, user, item, n, grid, x, alpha, parts, map, peak_cell, peak_val, ecap, s);
+  // the claims are released on every path (the claim kernel ran, or was at least tried: rowitem names the rows)
+  hipLaunchKernelGGL(k_af_release, dim3(af_blocks(n, 256)), dim3(256), 0, s, S->rowitem, n, S->rowuser, (int64_t)0, S->islot, S->uslot);
+  if (!rc) BPRX_LAUNCH_CHECK(h, "k_af_release");
+  return rc;
 }
 
 extern "C" int bprx_af_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *scores, float *alpha, void *stream) {

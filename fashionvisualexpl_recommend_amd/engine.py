@@ -332,6 +332,30 @@ class Engine:
         _ffi.check(self.h, self.lib.bprx_af_attention_pairs(self.h, _ptr(u), _ptr(i), u.numel(), _ptr(x), _ptr(al), _stream()))
         return x, al
 
+    def af_explain(self, user, item, grid=14, maps=True):
+        """bprx_af_explain: the exact split of every pair's score over the three modalities, and of its edges share over a
+        grid x grid partition of the 112 x 112 pooling windows (alpha held fixed at the value the model reports).  Returns a dict of
+        device tensors: score [n], alpha [n, 3], parts [n, 3] (colour, edges, class; they sum to score), peak_cell int32 [n] (row-major
+        index of the largest cell, the lowest among equals), peak_val [n], and with maps=True map [n, grid * grid] (its cells sum to
+        parts[:, 1]).  Any n: the pairs go to the library in chunks of max_batch."""
+        u, i = as_index(user, self.device), as_index(item, self.device)
+        if u.numel() != i.numel():
+            raise ValueError("af_explain: %d users for %d items" % (u.numel(), i.numel()))
+        n, G = u.numel(), int(grid)
+        G2 = G * G if 0 < G <= 112 else 0
+        f = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)
+        out = {"score": f(n), "alpha": f(n, 3), "parts": f(n, 3), "peak_cell": torch.empty(n, dtype=torch.int32, device=self.device),
+               "peak_val": f(n)}
+        if maps:
+            out["map"] = f(n, G2)
+        p = lambda t, r0: C.c_void_p(t.data_ptr() + r0 * t.stride(0) * t.element_size() if t.numel() else t.data_ptr())
+        for r0 in range(0, max(n, 1), self.max_batch):          # (an empty call still reaches the library's argument checks)
+            m = min(self.max_batch, n - r0)
+            _ffi.check(self.h, self.lib.bprx_af_explain(self.h, p(u, r0), p(i, r0), m, G, p(out["score"], r0), p(out["alpha"], r0),
+                                                        p(out["parts"], r0), p(out["map"], r0) if maps else None,
+                                                        p(out["peak_cell"], r0), p(out["peak_val"], r0), _stream()))
+        return out
+
     def af_score_block(self, u0, u1):
         """Scores [u1-u0, I] and attentions [u1-u0, I, 3] of a user block (bprx_af_score_block)."""
         x = torch.empty((u1 - u0, self.I), dtype=torch.float32, device=self.device)

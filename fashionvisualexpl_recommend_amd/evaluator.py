@@ -252,32 +252,58 @@ class Evaluator:
         Scores and attentions come from one bprx_af_score_block call per user block; the top-k and the gather of its
         attentions run on the device, rows whose order depends on equal scores are redone on the host as in
         store_recommendation."""
+        with open(path, 'w') as out:
+            self._store_attention_rows(out)
+
+    def _store_attention_rows(self, out, block_hook=None):
+        """The rows of store_recommendation_attention; block_hook(users, items) is called once per user block with the rows
+        just written, in their order."""
         import torch
         eng = self.model.engine
         self._metrics_device_csr()
         U, I = self.model.data.num_users, self.model.data.num_items
         blk = max(1, min(self.user_block, (1 << 27) // max(1, I)))
-        with open(path, 'w') as out:
-            for u0 in range(0, U, blk):
-                u1 = min(U, u0 + blk)
-                sc, al = eng.af_score_block(u0, u1)
-                idx, val, flag = eng.topk(u0, u1, sc, self._csr["train"], self.k)
-                kk = min(self.k, idx.shape[1], I)
-                pick = idx[:, :kk].long().clamp_(0, I - 1).unsqueeze(-1).expand(-1, -1, 3)
-                att = torch.gather(al, 1, pick).cpu().numpy()
-                idx, val, flag = idx.cpu().numpy(), val.cpu().numpy(), flag.cpu().numpy()
-                for r in range(u1 - u0):
-                    u = u0 + r
-                    if flag[r]:
-                        row = sc[r].cpu().numpy()
-                        top_k_id = row.argsort()[-self.k:][::-1]
-                        top_k_score = row[top_k_id]
-                        a = al[r].cpu().numpy()[top_k_id]
-                    else:
-                        top_k_id, top_k_score, a = idx[r, :kk], val[r, :kk], att[r]
-                    for i, value in enumerate(top_k_id):
-                        out.write(str(u) + '\t' + str(value) + '\t' + str(top_k_score[i]) + '\t' + str(a[i, 0]) + '\t' +
-                                  str(a[i, 1]) + '\t' + str(a[i, 2]) + '\n')
+        for u0 in range(0, U, blk):
+            written = ([], [])
+            u1 = min(U, u0 + blk)
+            sc, al = eng.af_score_block(u0, u1)
+            idx, val, flag = eng.topk(u0, u1, sc, self._csr["train"], self.k)
+            kk = min(self.k, idx.shape[1], I)
+            pick = idx[:, :kk].long().clamp_(0, I - 1).unsqueeze(-1).expand(-1, -1, 3)
+            att = torch.gather(al, 1, pick).cpu().numpy()
+            idx, val, flag = idx.cpu().numpy(), val.cpu().numpy(), flag.cpu().numpy()
+            for r in range(u1 - u0):
+                u = u0 + r
+                if flag[r]:
+                    row = sc[r].cpu().numpy()
+                    top_k_id = row.argsort()[-self.k:][::-1]
+                    top_k_score = row[top_k_id]
+                    a = al[r].cpu().numpy()[top_k_id]
+                else:
+                    top_k_id, top_k_score, a = idx[r, :kk], val[r, :kk], att[r]
+                for i, value in enumerate(top_k_id):
+                    out.write(str(u) + '\t' + str(value) + '\t' + str(top_k_score[i]) + '\t' + str(a[i, 0]) + '\t' +
+                              str(a[i, 1]) + '\t' + str(a[i, 2]) + '\n')
+                if block_hook is not None:
+                    written[0].extend([u] * len(top_k_id))
+                    written[1].extend(int(v) for v in top_k_id)
+            if block_hook is not None and written[0]:
+                block_hook(*written)
+
+    def store_recommendation_attention_explain(self, path_recs="", path_expl="", grid=14):
+        """AttentiveFashion: `path_recs` exactly as store_recommendation_attention writes it, and for every row written there one row
+        'u\\ti\\tscore\\ts_colour\\ts_edges\\ts_class\\tpeak_row\\tpeak_col\\tpeak_value\\tcell_0 ... cell_{G*G-1}' in `path_expl`
+        (bprx_af_explain, one call per block of rows): score = s_colour + s_edges + s_class exactly as the model weighs the three
+        modalities, and the cells (row-major, G x G over the 112 x 112 pooled edge image) sum to s_edges, alpha held fixed."""
+        eng, G = self.model.engine, int(grid)
+        with open(path_recs, 'w') as out, open(path_expl, 'w') as ex:
+            def block(users, items):
+                e = {n: v.cpu().numpy() for n, v in eng.af_explain(users, items, G, maps=True).items()}
+                for r, (u, i) in enumerate(zip(users, items)):
+                    pc = int(e["peak_cell"][r])
+                    ex.write('\t'.join([str(u), str(i), str(e["score"][r])] + [str(v) for v in e["parts"][r]] +
+                                       [str(pc // G), str(pc % G), str(e["peak_val"][r])] + [str(v) for v in e["map"][r]]) + '\n')
+            self._store_attention_rows(out, block)
 
     def store_recommendation_acf(self, path_recs="", path_expl="", top=5):
         """ACF: `path_recs` exactly as store_recommendation writes it (the same device or host path), and for every row written there the rows

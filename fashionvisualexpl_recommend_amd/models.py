@@ -587,6 +587,9 @@ class ACF(BPRMF):
         self.evaluator.store_recommendation_acf(path, os.path.join(d, f.replace("recs-", "expl-", 1)), self.acf_explain)
 
 
+AF_EXPLAIN_GRIDS = (0, 1, 2, 4, 7, 8, 14, 16)      # --af_explain: the divisors of 112 whose expl-* rows stay readable
+
+
 def load_attentive_inputs(dataset, num_items):
     """AttentiveFashion's three per-item inputs (dataset.py:158-208) as CPU tensors: edges uint8 [I, 224, 224] (PIL convert('L'),
     resize((224, 224)); the reference's `/ np.float32(255)` of a uint8 image is applied by the kernels, exactly), colour fp32 [I, Dc]
@@ -635,6 +638,10 @@ class AttentiveFashion(BPRMF):
         if getattr(params, "dtype", "fp32") != "fp32":
             raise ValueError("AttentiveFashion runs with --dtype fp32 (got %s)" % params.dtype)
         self.dropout = float(getattr(params, "dropout", 0.5))
+        self.af_explain = int(getattr(params, "af_explain", 0) or 0)              # grid of the edge maps in expl-*; 0: none
+        if self.af_explain not in AF_EXPLAIN_GRIDS:
+            raise ValueError("AttentiveFashion: af_explain is 0 (off) or one of %s (got %r)"
+                             % (", ".join(str(g) for g in AF_EXPLAIN_GRIDS[1:]), self.af_explain))
         self._inputs = inputs
         super().__init__(data, params, init)
         self.directory_parameters = f'batch_{params.batch_size}' \
@@ -716,8 +723,26 @@ class AttentiveFashion(BPRMF):
         if step is not None:
             self.engine.af_step = step
 
+    # ---- explanations: x_ui = sum_l alpha_l t_l, and the edges share over a grid of the pooled edge image ----------------------
+    def explain(self, users, items, grid=14, maps=True):
+        """The exact split of each pair's score (Engine.af_explain) as numpy arrays: score [n], alpha [n, 3], parts [n, 3] (colour,
+        edges, class: alpha_l * t_l, they sum to score), peak_cell, peak_val [n] and with maps=True map [n, grid * grid] (reshape a
+        row to (grid, grid) for the image; the cells sum to parts[:, 1]).  alpha is held fixed at the value the model reports."""
+        return {n: v.cpu().numpy() for n, v in self.engine.af_explain(users, items, grid, maps=maps).items()}
+
+    def explain_ui(self, u, items, grid=14, maps=True):
+        """explain() for one user and several items."""
+        items = [int(i) for i in np.asarray(items).reshape(-1)]
+        return self.explain([int(u)] * len(items), items, grid, maps)
+
     def _store_recs(self, path):
-        self.evaluator.store_recommendation_attention(path=path)
+        """recs-* / best-recs-* with the attentions; with params.af_explain = G > 0 also expl-* / best-expl-* next to them."""
+        if self.af_explain <= 0:
+            return self.evaluator.store_recommendation_attention(path=path)
+        d, f = os.path.split(path)
+        if not (f.startswith("recs-") or f.startswith("best-recs-")):
+            raise ValueError("AttentiveFashion: %s is neither a recs-* nor a best-recs-* path" % path)
+        self.evaluator.store_recommendation_attention_explain(path, os.path.join(d, f.replace("recs-", "expl-", 1)), self.af_explain)
 
 
 from ._ffi import ACF_WEIGHTS as _ACF_W     # noqa: E402

@@ -51,6 +51,10 @@ def parse_args(argv=None):
                              "every recommended (u, i): alpha, contribution and the peak of the component attention; 0 = off")
     parser.add_argument('--attention_layers', nargs='+', type=int, default=[64, 1],
                         help='attentive_fashion: attention layers, two ints "h 1" (train_rec.py:38)')
+    parser.add_argument('--af_explain', type=int, default=0,
+                        help="attentive_fashion: also write expl-* / best-expl-* files with the exact split of every recommended "
+                             "(u, i) score over colour, edges and class and the edges share over a G x G grid of the edge image "
+                             "(G = 1, 2, 4, 7, 8, 14 or 16); 0 = off")
     # not in the reference
     parser.add_argument('--dropout', type=float, default=0.5,
                         help="attentive_fashion: rate of the encoders' Dropout layers (AttentiveFashion.py:53,62,70: 0.5)")
@@ -81,6 +85,10 @@ def parse_args(argv=None):
         parser.error("--acf_explain takes 0 (off) .. 32 (got %s)" % args.acf_explain)
     if args.acf_explain != 0 and args.rec != 'acf':
         parser.error("--acf_explain %s needs --rec acf (got --rec %s)" % (args.acf_explain, args.rec))
+    if args.af_explain not in (0, 1, 2, 4, 7, 8, 14, 16):
+        parser.error("--af_explain takes 0 (off), 1, 2, 4, 7, 8, 14 or 16 (got %s)" % args.af_explain)
+    if args.af_explain != 0 and args.rec != 'attentive_fashion':
+        parser.error("--af_explain %s needs --rec attentive_fashion (got --rec %s)" % (args.af_explain, args.rec))
     if not 0.0 <= args.dropout < 1.0:
         parser.error("--dropout takes a rate in [0, 1) (got %s)" % args.dropout)
     return args

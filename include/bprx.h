@@ -303,6 +303,29 @@ BPRX_API int bprx_af_encode(bprx_handle *h, const int32_t *items, int64_t n, flo
 /* Scores and attentions of n <= max_batch pairs, dropout off: x fp32 [n], alpha fp32 [n, 3] (colour, edges, class). */
 BPRX_API int bprx_af_attention_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t n, float *x, float *alpha,
                                      void *stream);
+/* Why pair p = (user[p], item[p]) scores what it scores (dropout off, n <= max_batch as for bprx_af_attention_pairs).  The score
+   is a sum over the three modalities (AttentiveFashion.py:168-209, call), an algebraic identity:
+       x_ui    = sum_l s_l,        s_l = alpha_l * sum_k g_uk c_lk g_ik           l = colour, edges, class
+   and the edge encoder (AttentiveFashion.py:56-63: Conv2D 5x5 same + relu, MaxPooling2D 2x2, GlobalAveragePooling2D, Dropout,
+   Dense(k, no bias)) is the class-activation-map architecture, so the edges share splits over the 112 x 112 pooling windows:
+       s_edges = sum_p S(p),       S(p) = (alpha_e / 12544) * sum_c v_c A_c(p)
+       v_c     = sum_k W2e[c, k] g_uk g_ik
+       A_c(p)  = max over the 2x2 window p of relu(conv_c + b_c)
+   alpha is the value the model reports, HELD FIXED: the map decomposes s_edges given alpha_e; it is not a derivative through
+   the softmax.  `grid` = G divides 112 (1, 2, 4, 7, 8, 14, 16, 28, 56, 112; BPRX_E_INVALID otherwise).  Outputs (device):
+       x fp32 [n], alpha fp32 [n, 3]   exactly the bits bprx_af_attention_pairs returns for the same pairs
+       parts fp32 [n, 3]               s_colour, s_edges, s_class
+       map fp32 [n, G * G]             cell (a, b), stored at a * G + b, = sum of S(p) over the window rows [a 112/G, (a+1) 112/G)
+                                       and columns [b 112/G, (b+1) 112/G); NULL: not written
+       peak_cell int32 [n]             index of the largest cell, the lowest index among equal cells; peak_val fp32 [n] its value
+   Indices out of range are clamped and reported by bprx_sync_check, as for bprx_af_attention_pairs; the handle stays usable and
+   the item claims of the call are released on every exit path.  The conv runs once per DISTINCT item of the call, into a
+   workspace of cell sums fp32 [items, G * G, 64] that is allocated at the first use for min(n, 1 GiB / (G * G * 256 B)) items
+   (grown when a later call needs more, freed with the handle); a call with more distinct items than that runs in chunks.  The
+   call reads the tables and writes its outputs and that workspace only: dropout step index, tables and Adam slots are untouched.
+   No float atomics and one summation order per cell: two calls with the same arguments return the same bits. */
+BPRX_API int bprx_af_explain(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t n, int32_t grid, float *x,
+                             float *alpha, float *parts, float *map, int32_t *peak_cell, float *peak_val, void *stream);
 /* bprx_score_block with the attentions next to the scores: scores fp32 [u1-u0, I], alpha fp32 [u1-u0, I, 3] (NULL: scores only). */
 BPRX_API int bprx_af_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *scores, float *alpha, void *stream);
 /* The keep-mask bytes (1 = kept) of step index `step` for a batch of n_rows / 2 triplets: out uint8
