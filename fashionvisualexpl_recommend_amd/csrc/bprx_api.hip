@@ -143,6 +143,12 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
     // BPRX_FWD_VARIANT=0: the plain forward kernel (the reference the streaming kernels are tested against); anything else:
     // the per-shape policy of bprx_proj.hip (launch_fwd_nt / launch_bwd_nt)
     h->fwd_variant = env_int("BPRX_FWD_VARIANT", 4);
+    // BPRX_PROJ_MASK: the rows of items the batch does not touch are left out of both projections of a segment-mode step
+    // (bprx_step_begin_sparse).  0 never (the form the masked passes are tested against); 1 (default) where it was measured to
+    // pay: bf16 features, up to nine column tiles (C2 0.2091 -> 0.2064 ms/step, --zipf 1.0 0.2386 -> 0.2250; fp8 tables lose:
+    // the masked backward pass is slower where the MFMAs pace it, c2fp8 49.3 -> 53.0 us, c5 944 -> 1 139 us, and a table that
+    // sits in the Infinity Cache has no HBM bytes to save); 2 wherever a masked form exists
+    h->proj_mask = std::min(std::max(env_int("BPRX_PROJ_MASK", 1), 0), 2);
     A(dalloc_zero(&h->dTu, U * d));
     A(dalloc_zero(&h->P, I * PS));
     A(dalloc_zero(&h->W, I * PS));
@@ -425,7 +431,7 @@ extern "C" int bprx_step_begin_sparse(bprx_handle *h, const int32_t *user, const
     // empty message and a zero dense gradient, but takes part in every collective and takes the same optimizer step as the
     // other replicas (bprx_pack_user_msg -> count 0, bprx_step_begin_dense -> dE|dBp = 0, bprx_apply_user_msgs, bprx_step_end).
     if (!(h->cfg.flags & (BPRX_FLAG_EXPORT_USER_GRAD | BPRX_FLAG_EXPORT_ITEM_GRAD))) BPRX_FAIL(h, BPRX_E_INVALID, "step: empty batch");
-    h->list_mode = 0; h->item_mode = 0;
+    h->list_mode = 0; h->item_mode = 0; h->step_masked = false; h->mask_kind = 0;
     if (h->cfg.optimizer == BPRX_OPT_ADAM_TF23) {
       h->adam_t += 1;
       const float t = (float)h->adam_t;
@@ -444,6 +450,7 @@ extern "C" int bprx_step_begin_sparse(bprx_handle *h, const int32_t *user, const
   // list mode: both projections over the batch's distinct items only (needs the index pass BEFORE the forward projection)
   h->list_mode = vb && !h->proj_fresh && (h->list_policy == 2 || (h->list_policy == 1 && 2 * B < (int64_t)h->cfg.num_items));
   h->item_mode = !h->list_mode && (h->seg_policy == 2 || (h->seg_policy == 1 && 2 * B >= (int64_t)h->cfg.num_items));
+  h->step_masked = false;
   h->list_reset_cnt = !(h->fast_rows && !(h->cfg.flags & BPRX_FLAG_EXPORT_ITEM_GRAD));
   // byte planes of this very batch, left by bprx_sample_*_h (consumed here, whatever this step does with them)
   h->idx8_use = h->idx8_ready(pos, neg, B);
@@ -476,12 +483,24 @@ extern "C" int bprx_step_begin_sparse(bprx_handle *h, const int32_t *user, const
     if (!h->p_valid &&                                                                   // P rows of the listed items only
         (rc = bprx_launch_proj_fwd(h, h->ilist, h->list_bound, h->list_cur, 1, h->P, s))) return rc;
   } else if (vb && !h->proj_fresh) {
+    // Segment mode: k_index_seg depends on the index arrays only, so it runs BEFORE the forward projection and both projections
+    // skip the feature rows of the items this batch does not touch (seg_cnt[item] == 0: nobody reads that row of P in this step
+    // and p_valid stays false; its W row is all zeros).  Everything the index pass writes -- the Wb rows it zeroes, cntU / ulist /
+    // uslot_of, seg_rank / seg_cnt / seg_ptr, the chunk list and both cursor triples -- was last read by the previous step's
+    // kernels (k_triplet_seg, k_item_seg, the backward projection) on this same stream: stream order is the only ordering there
+    // is today and it still holds.  The side stream's catch-up touches none of these buffers (rows, slots, lastU / lastI, lr_hist).
+    h->step_masked = h->item_mode && !h->p_valid &&
+                     (h->proj_mask == 2 ? h->cfg.feat_dtype != BPRX_F_FP32
+                                        : (h->proj_mask == 1 && h->cfg.feat_dtype == BPRX_F_BF16 && h->PS / 16 <= 9));
+    if (h->step_masked && (rc = bprx_launch_index_pass(h, user, pos, neg, B, s))) return rc;
     if ((rc = bprx_launch_cast_Et(h, s))) return rc;
-    if (!h->p_valid && (rc = bprx_launch_proj_fwd(h, nullptr, h->cfg.num_items, nullptr, 0, h->P, s))) return rc;  // every item
+    if (!h->p_valid && (rc = bprx_launch_proj_fwd(h, nullptr, h->cfg.num_items, nullptr, 0, h->P, s,
+                                                  h->step_masked ? h->seg_cnt : nullptr))) return rc;   // every (touched) item
   }
+  h->mask_kind = h->step_masked && h->fwd_masked ? 2 : 0;   // (bprx_step_begin_dense adds the backward pass)
   h->proj_fresh = false;
   if (catchup_aside) BPRX_HIP(h, hipStreamWaitEvent(s, h->ev_join, 0));
-  if (!h->list_mode && (rc = bprx_launch_index_pass(h, user, pos, neg, B, s))) return rc;
+  if (!h->list_mode && !h->step_masked && (rc = bprx_launch_index_pass(h, user, pos, neg, B, s))) return rc;
   if ((rc = bprx_launch_triplet_grad(h, user, pos, neg, B, s))) return rc;
   h->pending_B = B;
   h->pending_stage = 1;
@@ -504,7 +523,8 @@ extern "C" int bprx_step_begin_dense(bprx_handle *h, void *stream) {
   const float lr_t = h->pend_lr;
   int rc;
   if ((rc = bprx_launch_item_seg(h, pos, neg, B, lr_t, s))) return rc;                  // item rows + W, no float atomics
-  if (vb && (rc = bprx_launch_proj_bwd(h, B, s))) return rc;                           // dE|dBp = F^T W
+  if (vb && (rc = bprx_launch_proj_bwd(h, B, s, h->step_masked ? h->seg_cnt : nullptr))) return rc;   // dE|dBp = F^T W
+  if (vb) h->mask_kind = h->mask_kind == 2 ? (h->bwd_masked ? 1 : 2) : (h->bwd_masked ? 3 : 0);
   if ((rc = bprx_launch_apply(h, user, pos, neg, B, lr_t, s))) return rc;
   h->pending_stage = 2;
   return BPRX_OK;
@@ -645,6 +665,7 @@ extern "C" int bprx_step_lr(const bprx_handle *h, float *lr_t) {
 }
 
 extern "C" int bprx_index_pass_kind(const bprx_handle *h) { return h ? h->idx_kind : 0; }
+extern "C" int bprx_proj_mask_kind(const bprx_handle *h) { return h ? h->mask_kind : 0; }
 
 extern "C" int bprx_sync_check(bprx_handle *h, void *stream) {
   if (!h) return BPRX_E_INVALID;

@@ -89,6 +89,12 @@ struct bprx_handle {
   int64_t idx8_B, idx8_n;
   bool idx8_use;                  // this step's index pass scans the byte planes
   int idx_kind;                   // bprx_index_pass_kind
+  // Untouched items' feature rows out of both streaming projections (segment-mode steps): the index pass runs BEFORE
+  // the forward projection and both projections read seg_cnt as the per-item "occurs in this batch" mask.
+  int proj_mask;                  // env BPRX_PROJ_MASK, read at create: 0 never, 1 (default) bf16 features up to nine column tiles, 2 every masked form
+  bool step_masked;               // this step: the index pass has already run and the projections take the mask
+  bool fwd_masked, bwd_masked;    // the last launch of bprx_launch_proj_fwd / _bwd took it (set by the launchers)
+  int mask_kind;                  // bprx_proj_mask_kind
   bool idx8_ready(const int32_t *pos, const int32_t *neg, int64_t B) const {
     return item_mode && own8 && B > 0 && idx8_n == B && idx8_B == B && idx8_pos == pos && idx8_neg == neg && B % 16 == 0;
   }
@@ -198,9 +204,12 @@ int bprx_launch_tile_F(bprx_handle *h);
 int bprx_launch_cast_Et(bprx_handle *h, hipStream_t s);
 // rows == nullptr: items 0..nrows; else the listed items.  nrows_dev (device, optional): the actual row count (<= nrows, the
 // host-side bound the grid is sized for).  scatter: row t of the result goes to Pout[rows[t]] instead of Pout[t].
+// occ (device, optional; whole-table form only): occ[t] == 0 marks an item whose row this step does not need -- the forward
+// projection then writes P[t] = 0 without reading its features, the backward one leaves it out of the sums (its W row must be
+// all zeros).  nullptr: every row.
 int bprx_launch_proj_fwd(bprx_handle *h, const int32_t *rows, int64_t nrows, const int32_t *nrows_dev, int scatter, float *Pout,
-                         hipStream_t s);
-int bprx_launch_proj_bwd(bprx_handle *h, int64_t B, hipStream_t s);
+                         hipStream_t s, const int32_t *occ = nullptr);
+int bprx_launch_proj_bwd(bprx_handle *h, int64_t B, hipStream_t s, const int32_t *occ = nullptr);
 // GradFashion factors (bprx_factored.hip)
 int bprx_launch_fact_compose(bprx_handle *h, hipStream_t s);                // E_eff | Bp_eff from the factors
 int bprx_launch_fact_update(bprx_handle *h, float lr_t, hipStream_t s);     // chain rule from dEp, optimizer, loss partials

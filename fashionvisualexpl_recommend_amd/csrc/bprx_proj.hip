@@ -47,6 +47,25 @@ __device__ __forceinline__ i32x4_t ld_stream16(const void *p) {
   if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const i32x4_t *>(p));
   else return *reinterpret_cast<const i32x4_t *>(p);
 }
+// The MASKED forms of the two streaming projections (items the batch does not touch are left out) load the feature
+// pieces through a buffer resource over the wave's / the split's part of the tiled F: a lane whose row is left out carries
+// a byte offset past the resource's end, for which the hardware returns zeros WITHOUT a memory request -- no branch, no exec
+// juggling, zero-filled destinations, the same straight-line loop as the unmasked form.  (Tried first and dropped: the loads
+// under a per-lane `if`: hipcc gave every load a block of its own with an s_cbranch_execz, waited for some of them on the
+// spot and cut the chunk loop's vmcnt depth from 19 to 3.)
+constexpr uint32_t BUF_OOB = 0x80000000u;                // byte offset of a masked lane: past every resource's end
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t ft_rsrc(const void *base, uint32_t bytes) {
+  // (base and size are wave-uniform; said so explicitly, or hipcc wraps the loads in a loop over the distinct values)
+  const uintptr_t b = (uintptr_t)base;
+  const uintptr_t u = (uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b) |
+                      ((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32)) << 32);
+  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(u), 0, __builtin_amdgcn_readfirstlane((int)bytes),
+                                           0x00020000);                                             // raw buffer, 32-bit data
+}
+template <bool NT>
+__device__ __forceinline__ i32x4_t ld_buf16(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff) {
+  return __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, __builtin_amdgcn_readfirstlane((int)soff), NT ? 2 : 0);   // aux bit 1: nt
+}
 // one 16-byte operand fragment per lane: 8 bf16 (one 16x16x32 MFMA) or 16 fp8 (two 16x16x32 fp8 MFMAs over the low and
 // the high 8 bytes; A and B fragments are cut the same way, so every k is paired with itself exactly once)
 template <bool F8>
@@ -441,13 +460,17 @@ __device__ __forceinline__ void fp8x4_to_bf16x4(uint32_t w, uint32_t &o0, uint32
 // of the projection's column tiles.  Per 32 items a wave reads (2*NS + NT/NS) KB of fragments from LDS for 2*NT MFMAs; NS = 1
 // at NT = 17 is 19 KB for 34 -- the transpose reads, 64 B/clk per CU, take 2.2x the MFMAs' time and pace the kernel (c5: 1 024 us
 // measured, 990 us by that count); NS = 2 is 13 KB for 36.
-template <int NT, int BTV, int NW, int PD, bool F8, bool ROWS = false, int DB = 1, int NS = 1>
+// MASK (whole-table form): occ[t] == 0 says that item t does not occur in this batch -- its W row is all zeros (k_index_seg), so
+// its feature row adds exactly nothing to the sums: its pieces are not fetched (ld_buf16 above) and zeros go to LDS in their
+// place.  One bit per row of the split, 32 per tile, built once behind the LDS images: a tile's word is wave-uniform.
+template <int NT, int BTV, int NW, int PD, bool F8, bool ROWS = false, int DB = 1, int NS = 1, bool MASK = false>
 __global__ __launch_bounds__(NW * 64) void k_proj_bwd_bf16_v3(const uint16_t *__restrict__ F, int nrows, int D,
                                                           const uint16_t *__restrict__ Wb, int PS, float *__restrict__ part,
                                                           int rows_per_split, int descend, int xcd_map,
                                                           const int32_t *__restrict__ rows = nullptr,
                                                           const int32_t *__restrict__ nrows_dev = nullptr,
-                                                          const float *__restrict__ Wf = nullptr) {
+                                                          const float *__restrict__ Wf = nullptr,
+                                                          const int32_t *__restrict__ occ = nullptr) {
   constexpr int NTH = NW * 64, MC = NW * 32;         // threads, feature columns per workgroup
   constexpr int ESZ = F8 ? 1 : 2;                    // bytes per feature element in HBM
   constexpr int FCH = MC * ESZ / 16;                 // 16-B pieces per F tile row (HBM side)
@@ -495,6 +518,11 @@ __global__ __launch_bounds__(NW * 64) void k_proj_bwd_bf16_v3(const uint16_t *__
   // global loads, so bytes in flight per CU set the delivered bandwidth
   uint4 freg[PD][FPT], wreg[PD][WPT];
   uint4 wreg2[ROWS ? PD : 1][WPT];                   // ROWS: a 16-B bf16 piece of W is 32 B of the fp32 row
+  static_assert(!(MASK && ROWS), "the row-list form has no untouched rows");
+  uint32_t *const tmask = reinterpret_cast<uint32_t *>(lds_bwd3 + DB * IMG);      // MASK: the split's row bits
+  // MASK: the split's block rows of the tiled F as one buffer (the launcher keeps it below 2 GB); tile offsets are scalar
+  const __amdgpu_buffer_rsrc_t frs = ft_rsrc(F + (size_t)(tbeg >> 5) * (Deq >> 7) * 4096,
+                                             MASK ? (uint32_t)(ntiles * (BTV / 32)) * (uint32_t)(Deq >> 7) * 8192u : 0u);
   // Loads are unconditional (rows / tiles past the end are clamped to the last valid one and zeroed at commit):
   // with a load inside a divergent branch the compiler waits for vmcnt(0) at every commit and the pipeline collapses.
 #define BWD3_ISSUE(ST, TILE)                                                                                             \
@@ -513,8 +541,16 @@ __global__ __launch_bounds__(NW * 64) void k_proj_bwd_bf16_v3(const uint16_t *__
                                                        (size_t)(pp & 15) * 8);                                           \
       } else {                                                                                                           \
         const size_t bidx = (size_t)((t0 >> 5) + blk / CBK) * (Deq >> 7) + (m0q >> 7) + blk % CBK;                       \
-        { const i32x4_t v_ = ld_stream16<!F8>(F + bidx * 4096 + (size_t)(pp & 511) * 8);                                 \
-          freg[ST][x] = make_uint4((unsigned)v_.x, (unsigned)v_.y, (unsigned)v_.z, (unsigned)v_.w); }                      \
+        i32x4_t v_;                                                                                                      \
+        if constexpr (MASK) {                                                                                            \
+          const uint32_t br_ = (uint32_t)(((t0 - tbeg) >> 5) + blk / CBK);            /* block row within the split */   \
+          const uint32_t on_ = (tmask[br_] >> ((pp & 511) >> 4)) & 1u;                                                   \
+          v_ = ld_buf16<!F8>(frs, on_ ? (uint32_t)((m0q >> 7) + blk % CBK) * 8192u + (uint32_t)(pp & 511) * 16u : BUF_OOB, \
+                             br_ * (uint32_t)(Deq >> 7) * 8192u);                                                        \
+        } else {                                                                                                         \
+          v_ = ld_stream16<!F8>(F + bidx * 4096 + (size_t)(pp & 511) * 8);                                               \
+        }                                                                                                                \
+        freg[ST][x] = make_uint4((unsigned)v_.x, (unsigned)v_.y, (unsigned)v_.z, (unsigned)v_.w);                        \
       }                                                                                                                  \
     }                                                                                                                    \
     _Pragma("unroll") for (int x = 0; x < WPT; ++x) {                                                                    \
@@ -577,6 +613,16 @@ __global__ __launch_bounds__(NW * 64) void k_proj_bwd_bf16_v3(const uint16_t *__
     float *slab0 = part + ((size_t)by * D + m0) * PS;
     for (int e = threadIdx.x; e < MC * PS; e += NTH) slab0[e] = 0.f;
     return;
+  }
+  if constexpr (MASK) {
+    {                                                 // a wave takes 64 rows = two tiles' words per trip
+      for (int r0 = w * 64; r0 < ntiles * BTV; r0 += NTH) {
+        const int t = tbeg + r0 + lane;
+        const unsigned long long b = __ballot(t < tend && occ[t] != 0);
+        if (lane == 0) { tmask[r0 >> 5] = (uint32_t)b; tmask[(r0 >> 5) + 1] = (uint32_t)(b >> 32); }
+      }
+      __syncthreads();
+    }
   }
 #pragma unroll
   for (int st = 0; st < PD; ++st) BWD3_ISSUE(st, st)
@@ -641,8 +687,9 @@ __global__ __launch_bounds__(NW * 64) void k_proj_bwd_bf16_v3(const uint16_t *__
 // detour costs no barrier (v9 tried this load shape with a workgroup-shared image and two barriers per chunk and lost).
 // Plain C++ with scheduling fences; B as in v8 (chunk through a double-buffered shared LDS image, one barrier per chunk).
 // ------------------------------------------------------------------------------------------------------------
-template <int NT, int MT, bool F8, bool NTL>
-__device__ __forceinline__ void v10_body(const uint16_t *const (&asrc)[2], const uint16_t *__restrict__ Et, unsigned char *lds,
+template <int NT, int MT, bool F8, bool NTL, bool MASK>
+__device__ __forceinline__ void v10_body(const uint16_t *const (&asrc)[2], const uint32_t (&voff)[2][4],
+                                         const uint16_t *__restrict__ Et, unsigned char *lds,
                                          unsigned char *myA, f32x4 (&acc)[2][NT], int D, int cshift, int lane, int et_chunk) {
   constexpr int BSB = (KC + 16) * 2;                    // B row stride in bytes (288)
   constexpr int BBUF = NT * 16 * BSB;                   // one B buffer
@@ -654,12 +701,18 @@ __device__ __forceinline__ void v10_body(const uint16_t *const (&asrc)[2], const
   i32x4_t aX[MT][4], aY[MT][4];
   constexpr int NBR = (NPIECE + 319) / 320;             // B pieces per thread for the smallest workgroup (5 waves)
   i32x4_t bst[NBR];
+  // MASK: a tile's chunks (16 rows x 256 B at every 8 KB) as one buffer per tile; chunk offsets are scalar
+  __amdgpu_buffer_rsrc_t ars[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) ars[mt] = ft_rsrc(asrc[mt], MASK ? (uint32_t)nch * 8192u : 0u);
 #define V10_ISSUE(c_, AR)                                                                                             \
   {                                                                                                                   \
     int ce_ = (c_) + cshift;                                                                                          \
     if (ce_ >= nch) ce_ -= nch;                                                                                       \
-    _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) _Pragma("unroll") for (int x = 0; x < 4; ++x)                   \
-        AR[mt][x] = ld_stream16<NTL>(asrc[mt] + ((size_t)ce_ << 12) + x * 512 + lane * 8);                          \
+    _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) _Pragma("unroll") for (int x = 0; x < 4; ++x) {                 \
+      if constexpr (MASK) AR[mt][x] = ld_buf16<NTL>(ars[mt], voff[mt][x], (uint32_t)ce_ << 13);  /* loop-invariant offsets */ \
+      else AR[mt][x] = ld_stream16<NTL>(asrc[mt] + ((size_t)ce_ << 12) + x * 512 + lane * 8);                        \
+    }                                                                                                                 \
     const uint16_t *bc_ = Et + (size_t)ce_ * et_chunk;                                                                \
     _Pragma("unroll") for (int x = 0; x < NBR; ++x) {                                                                 \
       int pc = tid + x * bdim;                                                                                        \
@@ -718,11 +771,14 @@ __device__ __forceinline__ void v10_body(const uint16_t *const (&asrc)[2], const
 
 // NTL: the feature loads carry `nt` (tables that cannot stay in the Infinity Cache between the two passes of a step);
 // n0: first column of this launch's column range (NT tiles from there; 0 unless a wide projection is covered in passes).
-template <int NT, bool F8, bool NTL>
+// MASK: occ[t] == 0 says that item t does not occur in this batch -- nobody reads its row of P, so the lanes that would move
+// its 256-B pieces (lane l: row 4x + l/16 of the tile in load x, for the whole chunk loop) fetch nothing and contribute zeros:
+// P[t] = 0.  A row's 128-B lines are its own in the tiled copy: masked lanes are bytes not fetched.
+template <int NT, bool F8, bool NTL, bool MASK>
 __global__ __launch_bounds__(512) void k_proj_fwd_bf16_v10(const uint16_t *__restrict__ F, int nrows, int D,
                                                            const uint16_t *__restrict__ Et, float *__restrict__ P, int PS,
                                                            const float *__restrict__ pscale, int stagger, int tiles_per_wave,
-                                                           int n0) {
+                                                           int n0, const int32_t *__restrict__ occ) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_v10[];   // Bs[2] | As[waves][2 tiles][16 rows][288 B]
   constexpr int BSB = (KC + 16) * 2;
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -732,12 +788,18 @@ __global__ __launch_bounds__(512) void k_proj_fwd_bf16_v10(const uint16_t *__res
   const int first = t0 + w * tiles_per_wave;
   const int nlive = (first < t1 ? 1 : 0) + ((tiles_per_wave == 2 && first + 1 < t1) ? 1 : 0);   // wave-uniform
   const uint16_t *asrc[2];
+  uint32_t voff[2][4];                                   // MASK: this lane's byte offset inside a tile chunk, or past the end
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt) {
     int tile = first + mt;
     if (tile >= t1) tile = t1 > t0 ? t1 - 1 : 0;         // only read by a wave without work
     asrc[mt] = F + ft_row(tile * 16, D);                 // the tile's 16 rows x 128 columns: 4 KB contiguous (rows past the
-  }                                                      // end of the table are zero rows of the tiled copy)
+#pragma unroll                                           // end of the table are zero rows of the tiled copy)
+    for (int x = 0; x < 4; ++x) {
+      const int t = tile * 16 + x * 4 + q;
+      voff[mt][x] = (MASK && t < nrows && occ[t] != 0) ? (uint32_t)(x * 1024 + lane * 16) : BUF_OOB;
+    }
+  }
   f32x4 acc[2][NT];
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt)
@@ -747,8 +809,8 @@ __global__ __launch_bounds__(512) void k_proj_fwd_bf16_v10(const uint16_t *__res
   const int cshift = (stagger & 1) ? (int)(blockIdx.x % (unsigned)nch) : 0;
   unsigned char *myA = lds_v10 + 2 * NT * 16 * BSB + w * (2 * 16 * BSB);
   // (chunk-major image: chunk c holds rows [0, PS) x 128 k; this launch's columns start at row n0 of every chunk)
-  if (nlive == 2) v10_body<NT, 2, F8, NTL>(asrc, Et + (size_t)n0 * 128, lds_v10, myA, acc, D, cshift, lane, PS * 128);
-  else v10_body<NT, 1, F8, NTL>(asrc, Et + (size_t)n0 * 128, lds_v10, myA, acc, D, cshift, lane, PS * 128);
+  if (nlive == 2) v10_body<NT, 2, F8, NTL, MASK>(asrc, voff, Et + (size_t)n0 * 128, lds_v10, myA, acc, D, cshift, lane, PS * 128);
+  else v10_body<NT, 1, F8, NTL, MASK>(asrc, voff, Et + (size_t)n0 * 128, lds_v10, myA, acc, D, cshift, lane, PS * 128);
   const float ps = F8 ? *pscale : 1.0f;
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt) {
@@ -1208,7 +1270,7 @@ void launch_f8s(bprx_handle *h, const int32_t *rows, int64_t nrows, const int32_
 
 // v10 over the whole table, NT (<= 9) column tiles from column n0
 template <int NT>
-void launch_v10(bprx_handle *h, int64_t nrows, float *Pout, hipStream_t s, int n0) {
+void launch_v10(bprx_handle *h, int64_t nrows, float *Pout, hipStream_t s, int n0, const int32_t *occ) {
   constexpr int NWMAX = 8, NWMIN = 5;
   const bool f8 = h->cfg.feat_dtype == BPRX_F_FP8;
   const int Deq = f8 ? h->cfg.feat_dim / 2 : h->cfg.feat_dim;
@@ -1224,15 +1286,20 @@ void launch_v10(bprx_handle *h, int64_t nrows, float *Pout, hipStream_t s, int n
   if (nw < NWMIN) nw = NWMIN;
   const size_t lds = (size_t)2 * NT * 16 * 288 + (size_t)nw * 2 * 16 * 288;
   const bool ntl = fwd_nt_loads(h);
-#define V10_LAUNCH(F8_, NTL_)                                                                                             \
+#define V10_LAUNCH(F8_, NTL_, MASK_)                                                                                      \
   do {                                                                                                                    \
-    auto kfn = k_proj_fwd_bf16_v10<NT, F8_, NTL_>;                                                                        \
+    auto kfn = k_proj_fwd_bf16_v10<NT, F8_, NTL_, MASK_>;                                                                 \
     (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                   \
     hipLaunchKernelGGL(kfn, dim3((unsigned)G), dim3(nw * 64), lds, s, (const uint16_t *)h->Ft, (int)nrows, Deq,            \
-                       (const uint16_t *)h->Et, Pout, h->PS, pscale, 0, per_wave, n0);                                     \
+                       (const uint16_t *)h->Et, Pout, h->PS, pscale, 0, per_wave, n0, occ);                                \
   } while (0)
-  if (f8) { if (ntl) V10_LAUNCH(true, true); else V10_LAUNCH(true, false); }
-  else { if (ntl) V10_LAUNCH(false, true); else V10_LAUNCH(false, false); }
+  if (occ) {
+    if (f8) { if (ntl) V10_LAUNCH(true, true, true); else V10_LAUNCH(true, false, true); }
+    else { if (ntl) V10_LAUNCH(false, true, true); else V10_LAUNCH(false, false, true); }
+  } else {
+    if (f8) { if (ntl) V10_LAUNCH(true, true, false); else V10_LAUNCH(true, false, false); }
+    else { if (ntl) V10_LAUNCH(false, true, false); else V10_LAUNCH(false, false, false); }
+  }
 #undef V10_LAUNCH
 }
 
@@ -1247,12 +1314,13 @@ void launch_v10(bprx_handle *h, int64_t nrows, float *Pout, hipStream_t s, int n
 //   row list (bprx_score_pairs, list mode)          launch_fwd_rows / f8s over the list test_forward_row_list[split / mt1 / mt2 / mt4 / f8s_rows-*]
 //   fp32 features                                   k_proj_fwd_f32_mfma, k_proj_fwd_f32 test_forward_whole_table[fp32-*], test_forward_row_list[fp32-*]
 template <int NT>
-int launch_fwd_nt(bprx_handle *h, const int32_t *rows, int64_t nrows, float *Pout, hipStream_t s) {
+int launch_fwd_nt(bprx_handle *h, const int32_t *rows, int64_t nrows, float *Pout, hipStream_t s, const int32_t *occ) {
   constexpr int MTD = NT <= 9 ? 2 : 1;
   const bool f8 = h->cfg.feat_dtype == BPRX_F_FP8;
   const int Deq = f8 ? h->cfg.feat_dim / 2 : h->cfg.feat_dim;
   const float *pscale = h->qs + 1;
   const bool plain = h->fwd_variant == 0 || Deq % 256 != 0 || rows;
+  h->fwd_masked = false;                                // only v10 takes the mask: the other forms project every row
   if (!plain) {
     if constexpr (NT >= 10) {
       if (f8 && h->EtS && h->cfg.feat_dim % 256 == 0) {
@@ -1261,10 +1329,12 @@ int launch_fwd_nt(bprx_handle *h, const int32_t *rows, int64_t nrows, float *Pou
       }
       // bf16: column ranges of nine tiles, the last one right-aligned: ranges may overlap by some tiles, which are then computed and
       // stored twice, identically (F is read once per pass: two passes at d = 256)
-      for (int c0 = 0; c0 < NT; c0 += 9) launch_v10<9>(h, nrows, Pout, s, (c0 + 9 <= NT ? c0 : NT - 9) * 16);
+      for (int c0 = 0; c0 < NT; c0 += 9) launch_v10<9>(h, nrows, Pout, s, (c0 + 9 <= NT ? c0 : NT - 9) * 16, occ);
+      h->fwd_masked = occ != nullptr;
       return 0;
     } else {
-      launch_v10<NT>(h, nrows, Pout, s, 0);
+      launch_v10<NT>(h, nrows, Pout, s, 0, occ);
+      h->fwd_masked = occ != nullptr;
       return 0;
     }
   }
@@ -1275,16 +1345,17 @@ int launch_fwd_nt(bprx_handle *h, const int32_t *rows, int64_t nrows, float *Pou
 }
 
 // one launch of k_proj_bwd_bf16_v3 with its dynamic LDS size (DB images of F tile + W tile)
-template <int NT, int BTV, int NW, int PD, bool F8, bool ROWS, int DB, int NS = 1>
+template <int NT, int BTV, int NW, int PD, bool F8, bool ROWS, int DB, int NS = 1, bool MASK = false>
 void launch_bwd3(dim3 grid, hipStream_t s, const uint16_t *Ft, int nrows, int D, const uint16_t *Wb, int PS, float *part, int rps,
-                 int desc, int xmap, const int32_t *rows, const int32_t *nrows_dev, const float *Wf) {
-  constexpr size_t lds = (size_t)DB * (BTV * (NW * 32 * 2 + 32) + BTV * WsStride3<NT>::bytes);
-  auto kfn = k_proj_bwd_bf16_v3<NT, BTV, NW, PD, F8, ROWS, DB, NS>;
+                 int desc, int xmap, const int32_t *rows, const int32_t *nrows_dev, const float *Wf, const int32_t *occ = nullptr) {
+  // occ: + one bit per row of a split behind the images (whole 64-row trips: two words of slack)
+  const size_t lds = (size_t)DB * (BTV * (NW * 32 * 2 + 32) + BTV * WsStride3<NT>::bytes) + (MASK ? ((size_t)rps / 32 + 2) * 4 : 0);
+  auto kfn = k_proj_bwd_bf16_v3<NT, BTV, NW, PD, F8, ROWS, DB, NS, MASK>;
   if (lds > 48 * 1024) {
-    static bool attr_set = false;                        // per instantiation
-    if (!attr_set) { (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; }
+    static size_t attr_lds = 0;                          // per instantiation
+    if (lds > attr_lds) { (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_lds = lds; }
   }
-  hipLaunchKernelGGL(kfn, grid, dim3(NW * 64), lds, s, Ft, nrows, D, Wb, PS, part, rps, desc, xmap, rows, nrows_dev, Wf);
+  hipLaunchKernelGGL(kfn, grid, dim3(NW * 64), lds, s, Ft, nrows, D, Wb, PS, part, rps, desc, xmap, rows, nrows_dev, Wf, occ);
 }
 
 // backward over the touched-item list (list mode): v3 kernel in ROWS form, 2 tiles in flight; `bound` = host-side bound of
@@ -1315,7 +1386,7 @@ int launch_bwd_rows(bprx_handle *h, int64_t bound, hipStream_t s) {
 // covered against an fp64 reference by tests/test_gpu_projections.py: test_backward_whole_table[pd3-* (1 / 2 / 3 / 4 / 25 tiles per
 // split), db2-fp8-*, ns2-*, w4-*, grid-* (SK % 8 != 0: no XCD remap), fp32-*], test_backward_row_list (launch_bwd_rows, ROWS)
 template <int NT>
-int launch_bwd_nt(bprx_handle *h, hipStream_t s) {
+int launch_bwd_nt(bprx_handle *h, hipStream_t s, const int32_t *occ) {
   const int D = h->cfg.feat_dim, I = h->cfg.num_items;
   int rps3 = (I + h->SK - 1) / h->SK;
   rps3 = (rps3 + 31) / 32 * 32;
@@ -1325,19 +1396,29 @@ int launch_bwd_nt(bprx_handle *h, hipStream_t s) {
   const bool f8 = h->cfg.feat_dtype == BPRX_F_FP8;
   const bool w8 = D % 256 == 0 || f8;                   // fp8: a 256-column tile row is one 256-B block row
   dim3 g3(D / (w8 ? 256 : 128), h->SK);
+  // masked form: a split's rows are one buffer resource (32-bit byte offsets: below 2 GB) and its row bits sit in LDS (at
+  // most 16 KB); splits beyond either bound (tables of tens of GB) sum every row
+  if (rps3 / 32 > 4096 || (size_t)rps3 * D * (h->cfg.feat_dtype == BPRX_F_FP8 ? 1 : 2) >= ((size_t)1 << 31)) occ = nullptr;
+  h->bwd_masked = occ != nullptr;
 #define BWD3_ARGS (const uint16_t *)h->Ft, I, D, (const uint16_t *)h->Wb, h->PS, h->part, rps3, 0, 1, (const int32_t *)nullptr, \
-                  (const int32_t *)nullptr, (const float *)nullptr
+                  (const int32_t *)nullptr, (const float *)nullptr, occ
+#define BWD3_GO(...)                                                                  \
+  do {                                                                                \
+    if (occ) launch_bwd3<__VA_ARGS__, true>(g3, s, BWD3_ARGS);                        \
+    else launch_bwd3<__VA_ARGS__, false>(g3, s, BWD3_ARGS);                           \
+    return 0;                                                                         \
+  } while (0)
   if constexpr (NT > 9) {        // wide projections: 4 x 2 wave grid (2 % on c5 / c5small / c5bf16; the kernel stays paced by
-    if (f8) { launch_bwd3<NT, 32, 8, 2, true, false, 2, 2>(g3, s, BWD3_ARGS); return 0; }          // issue, not by LDS volume)
-    if (w8) { launch_bwd3<NT, 32, 8, 2, false, false, 2, 2>(g3, s, BWD3_ARGS); return 0; }
+    if (f8) BWD3_GO(NT, 32, 8, 2, true, false, 2, 2);                                              // issue, not by LDS volume)
+    if (w8) BWD3_GO(NT, 32, 8, 2, false, false, 2, 2);
   }
   if constexpr (NT <= 9) {
-    if (f8) { launch_bwd3<NT, 32, 8, 2, true, false, 2>(g3, s, BWD3_ARGS); return 0; }
-    if (w8) { launch_bwd3<NT, 32, 8, 3, false, false, 1>(g3, s, BWD3_ARGS); return 0; }
+    if (f8) BWD3_GO(NT, 32, 8, 2, true, false, 2, 1);
+    if (w8) BWD3_GO(NT, 32, 8, 3, false, false, 1, 1);
   }
-  launch_bwd3<NT, 32, 4, 2, false, false, 1>(g3, s, BWD3_ARGS);
+  BWD3_GO(NT, 32, 4, 2, false, false, 1, 1);
+#undef BWD3_GO
 #undef BWD3_ARGS
-  return 0;
 }
 
 #define NT_SWITCH(NT, CALL)            \
@@ -1402,7 +1483,8 @@ int bprx_launch_cast_Et(bprx_handle *h, hipStream_t s) {
 }
 
 int bprx_launch_proj_fwd(bprx_handle *h, const int32_t *rows, int64_t nrows, const int32_t *nrows_dev, int scatter, float *Pout,
-                         hipStream_t s) {
+                         hipStream_t s, const int32_t *occ) {
+  h->fwd_masked = false;
   if (nrows <= 0) return BPRX_OK;
   BprxProfScope ps(h, BPRX_PHASE_PROJ_FWD, s);
   if (h->cfg.feat_dtype != BPRX_F_FP32) {
@@ -1430,7 +1512,7 @@ int bprx_launch_proj_fwd(bprx_handle *h, const int32_t *rows, int64_t nrows, con
       BPRX_LAUNCH_CHECK(h, "k_proj_fwd_rows");
       return BPRX_OK;
     }
-#define CALL(N) launch_fwd_nt<N>(h, rows, nrows, Pout, s)
+#define CALL(N) launch_fwd_nt<N>(h, rows, nrows, Pout, s, occ)
     NT_SWITCH(NT, CALL)
 #undef CALL
     BPRX_LAUNCH_CHECK(h, "k_proj_fwd_bf16");
@@ -1452,7 +1534,8 @@ int bprx_launch_proj_fwd(bprx_handle *h, const int32_t *rows, int64_t nrows, con
 }
 
 // B: batch size of the step (bounds the touched-item list in list mode)
-int bprx_launch_proj_bwd(bprx_handle *h, int64_t B, hipStream_t s) {
+int bprx_launch_proj_bwd(bprx_handle *h, int64_t B, hipStream_t s, const int32_t *occ) {
+  h->bwd_masked = false;
   const int D = h->cfg.feat_dim, d = h->cfg.embed_d, I = h->cfg.num_items;
   const int64_t bound = 2 * B < (int64_t)I ? 2 * B : (int64_t)I;     // list mode: at most 2B distinct items
   h->SK_step = h->SK;
@@ -1471,7 +1554,7 @@ int bprx_launch_proj_bwd(bprx_handle *h, int64_t B, hipStream_t s) {
       BPRX_LAUNCH_CHECK(h, "k_proj_bwd_bf16_v3<rows>");
     } else {
       BprxProfScope ps(h, BPRX_PHASE_PROJ_BWD, s);
-#define CALL(N) launch_bwd_nt<N>(h, s)
+#define CALL(N) launch_bwd_nt<N>(h, s, occ)
       NT_SWITCH(NT, CALL)
 #undef CALL
       BPRX_LAUNCH_CHECK(h, "k_proj_bwd_bf16");

@@ -594,6 +594,12 @@ BPRX_API int bprx_sample_epoch_h(bprx_handle *h, const int64_t *indptr, const in
 /* What the index pass of the handle's last step read: 0 = no segment-mode step yet, 1 = the int32 index arrays,
    2 = the sampler's byte planes.  (Introspection for tests and benchmarks.) */
 BPRX_API int bprx_index_pass_kind(const bprx_handle *h);
+/* Whether the projections of the handle's last step left out the feature rows of the items its batch did not touch:
+   0 = both streamed every row (list mode, a step after bprx_step_project or bprx_score_block, fp32 features, fp8 features or
+   more than nine column tiles unless BPRX_PROJ_MASK=2, BPRX_PROJ_MASK=0, no step yet), 1 = both passes masked, 2 = the forward pass alone (a split of the backward pass too long for its row bits),
+   3 = the backward pass alone (forward kernel forms without the mask: feat_dim not a multiple of 256 / 512, wide fp8
+   projections).  Results are the same either way.  (Introspection for tests and benchmarks.) */
+BPRX_API int bprx_proj_mask_kind(const bprx_handle *h);
 
 #ifdef __cplusplus
 }
