@@ -277,11 +277,14 @@ __global__ __launch_bounds__(256) void k_eval_finish(int u0, int nb, int Itot, c
 // The reference orders equal scores by numpy's unstable argsort (implementation- and CPU-dependent); rows whose output
 // depends on such a tie -- equal scores among the K selected, or at the selection boundary, or fewer than K unmasked
 // items -- are FLAGGED (flag[row] = 1) so that the caller can redo exactly those rows with numpy on the (masked) row.
+// "Equal" is float equality, as numpy compares: +0.0 and -0.0 are one score (f2key gives them one key) although their
+// bits differ; val_out is read from the row, so the sign of a zero is kept.  NaN scores are outside the contract.
 // ------------------------------------------------------------------------------------------------------------
 constexpr int TOPK_MAX = 1024;
 
 __device__ __forceinline__ uint32_t f2key(float x) {       // larger float <-> larger key; -inf is the smallest finite-order key
-  const uint32_t u = __float_as_uint(x);
+  uint32_t u = __float_as_uint(x);
+  if (u == 0x80000000u) u = 0u;                            // -0.0 == +0.0: one key, so a +-0 pair meets the tie checks below
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 

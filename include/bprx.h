@@ -506,8 +506,9 @@ BPRX_API int bprx_eval_finish(bprx_handle *h, int32_t u0, int32_t u1, int32_t it
    score matrix, :233) and the K (<= 1024) largest remaining scores are returned best first: idx int32 [(u1-u0), K] (-1 past
    min(K, I)), val fp32 same shape.  flag int32 [(u1-u0)]: 1 = the row's list depends on how EQUAL scores are ordered (ties
    inside the list or at its boundary, or fewer than K unmasked items) -- the reference's order there is numpy's unstable
-   argsort; the caller redoes flagged rows with numpy on the (already masked) row.  Unflagged rows equal the reference's
-   output exactly.  CSR as in bprx_eval_users. */
+   argsort; the caller redoes flagged rows with numpy on the (already masked) row.  Equality is float equality: +0.0 and
+   -0.0 are equal scores (val keeps the sign of the zero it read).  Unflagged rows equal the reference's output exactly.
+   CSR as in bprx_eval_users. */
 BPRX_API int bprx_topk(bprx_handle *h, int32_t u0, int32_t u1, float *scores, const int64_t *train_ptr,
                        const int32_t *train_items, int32_t K, int32_t *idx, float *val, int32_t *flag, void *stream);
 
