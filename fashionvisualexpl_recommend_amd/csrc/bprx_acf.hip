@@ -14,7 +14,7 @@
 //   k_acf_triplet   scores with g', loss terms, the detached gradients of Gi / Gu / Pi into the staging tables
 //   k_acf_dense     the twelve attention tensors (g = 2 reg w: sgd or the dense ApplyAdam rule) and the loss (one workgroup, fixed
 //                   summation order)
-//   k_acf_apply_sgd / k_acf_sweep   sgd on the touched rows / adam_tf23's sparse rule over the whole tables (adam_elem)
+//   k_acf_apply_sgd / k_adam_sweep  sgd on the touched rows / adam_tf23's sparse rule over the whole tables (bprx_sparse.hip)
 //   k_acf_finish    clears the user slots and the sgd claim marks
 // With bprx_acf_set_gradient(h, BPRX_ACF_GRAD_FULL) a step also differentiates through g'_u (include/bprx.h), between
 // k_acf_triplet and k_acf_dense:
@@ -70,36 +70,6 @@ struct AcfState {
   int64_t xt_cap;
 };
 
-__device__ __forceinline__ int acf_clamp(int v, int n, int32_t *errflag, int code) {
-  if ((unsigned)v >= (unsigned)n) {
-    *errflag = code;
-    return v < 0 ? 0 : n - 1;
-  }
-  return v;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-// LDS written by some lanes of a wave and read by others of the same wave
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ uint16_t bf16_rne(float x) {
-  const uint32_t b = __float_as_uint(x);
-  return (uint16_t)((b + 0x7fffu + ((b >> 16) & 1u)) >> 16);
-}
-
 // ---- projection operand --------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_acf_wcat(const float *__restrict__ Wci, const float *__restrict__ Wix, int C, int Cp,
                                                   int hc, int ha, int NP, float *__restrict__ Wc, uint16_t *__restrict__ Wh,
@@ -111,10 +81,10 @@ __global__ __launch_bounds__(256) void k_acf_wcat(const float *__restrict__ Wci,
     if (c < C) v = j < hc ? Wci[(int64_t)c * hc + j] : (j < hc + ha ? Wix[(int64_t)c * ha + (j - hc)] : 0.f);
     if (Wc) Wc[e] = v;
     if (Wh) {
-      const uint16_t hi = bf16_rne(v);
+      const uint16_t hi = (uint16_t)bf16_rne(v);
       const float rest = v - __uint_as_float((uint32_t)hi << 16);
       Wh[(int64_t)j * Cp + c] = hi;
-      Wl[(int64_t)j * Cp + c] = bf16_rne(rest);
+      Wl[(int64_t)j * Cp + c] = (uint16_t)bf16_rne(rest);
     }
   }
 }
@@ -128,11 +98,11 @@ __global__ __launch_bounds__(256) void k_acf_mark(const int32_t *__restrict__ us
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (b >= n) return;
-  const int u = users ? acf_clamp(users[b], U, errflag, 1) : (int)b;
+  const int u = users ? clamp_index(users[b], U, errflag, 1) : (int)b;
   if (uslot && uslot[u] != (int32_t)b) return;
   const int64_t beg = ptr[u], end = ptr[u + 1];
   for (int64_t p = beg + lane; p < end; p += 64) {
-    const int l = acf_clamp(items[p], I, errflag, 5);
+    const int l = clamp_index(items[p], I, errflag, 5);
     if (atomicExch(imark + l, 1) == 0) ilist[atomicAdd(nlist, 1)] = l;
   }
 }
@@ -339,7 +309,7 @@ __global__ __launch_bounds__(256) void k_acf_user(AcfUserArgs A, const int32_t *
   const int64_t b = blockIdx.x;
   if (b >= n) return;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int u = users ? acf_clamp(users[b], A.U, A.errflag, 1) : (int)b;
+  const int u = users ? clamp_index(users[b], A.U, A.errflag, 1) : (int)b;
   if (uslot && uslot[u] != (int32_t)b) return;
   const int k = A.k, M = A.M, hc = A.hc, ha = A.ha, NP = A.NP;
   float *gu = sm, *uc = gu + k, *ui = uc + hc, *w1c = ui + ha, *w1i = w1c + hc;
@@ -369,7 +339,7 @@ __global__ __launch_bounds__(256) void k_acf_user(AcfUserArgs A, const int32_t *
   const int64_t ncap = EXPL ? *(const int64_t *)aux : 0;      // EXPL: entries `out` has room for
   float mx = -INFINITY, den = 0.f;
   for (int64_t p = beg + w; p < end; p += 4) {
-    const int l = acf_clamp(A.items[p], A.I, A.errflag, 5);
+    const int l = clamp_index(A.items[p], A.I, A.errflag, 5);
     const float *Zl = A.Z + (int64_t)l * M * NP;
     float lmax = -INFINITY;
     for (int m = lane; m < M; m += 64) {
@@ -445,7 +415,7 @@ __global__ __launch_bounds__(256) void k_acf_user(AcfUserArgs A, const int32_t *
 __global__ __launch_bounds__(256) void k_acf_claim(const int32_t *__restrict__ user, int64_t B, int U, int32_t *__restrict__ uslot,
                                                    int32_t *errflag) {
   const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) atomicMin(uslot + acf_clamp(user[b], U, errflag, 1), (int32_t)b);
+  if (b < B) atomicMin(uslot + clamp_index(user[b], U, errflag, 1), (int32_t)b);
 }
 
 struct AcfStepArgs {
@@ -463,8 +433,8 @@ __global__ __launch_bounds__(256) void k_acf_triplet(AcfStepArgs A, const int32_
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (b >= B) return;
-  const int u = acf_clamp(user[b], A.U, A.errflag, 1), i = acf_clamp(pos[b], A.I, A.errflag, 2),
-            j = acf_clamp(neg[b], A.I, A.errflag, 2);
+  const int u = clamp_index(user[b], A.U, A.errflag, 1), i = clamp_index(pos[b], A.I, A.errflag, 2),
+            j = clamp_index(neg[b], A.I, A.errflag, 2);
   const int k = A.k;
   const float *g = A.gp + (int64_t)A.uslot[u] * k;
   const float *gu = A.Gu + (int64_t)u * k, *gi = A.Gi + (int64_t)i * k, *gj = A.Gi + (int64_t)j * k;
@@ -506,8 +476,7 @@ struct AcfDenseArgs {
 };
 __global__ __launch_bounds__(1024) void k_acf_dense(AcfDenseArgs T, int adam, float lr_t, float reg, float b1, float b2, float eps,
                                                     const float *__restrict__ lossb, int64_t B, float *__restrict__ loss_out) {
-  __shared__ double red[1024];
-  const float omb1 = 1.0f - b1, omb2 = 1.0f - b2, r2 = 2.f * reg;
+  const float r2 = 2.f * reg;
   double sq = 0.0, ls = 0.0;
   for (int q = 0; q < BPRX_ACF_NW; ++q) {
     float *p = T.w[q];
@@ -517,25 +486,12 @@ __global__ __launch_bounds__(1024) void k_acf_dense(AcfDenseArgs T, int adam, fl
       float g = r2 * pv;
       if (gq) g += gq[e];
       sq += (double)pv * (double)pv;
-      if (adam) {                                            // TF-2.3 dense ApplyAdam (as k_dense_update / k_fact_update)
-        const float mo = T.m[q][e], vo = T.v[q][e];
-        const float mt = mo + (g - mo) * omb1;
-        const float vt = vo + (g * g - vo) * omb2;
-        T.m[q][e] = mt; T.v[q][e] = vt;
-        p[e] = pv - lr_t * mt / (sqrtf(vt) + eps);
-      } else {
-        p[e] = pv - lr_t * g;
-      }
+      p[e] = dense_adam_elem(pv, T.m[q] + e, T.v[q] + e, g, adam, lr_t, b1, b2, eps);
     }
   }
   for (int64_t b = threadIdx.x; b < B; b += 1024) ls += (double)lossb[b];
-  red[threadIdx.x] = ls + (double)reg * sq;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && loss_out) *loss_out = (float)red[0];
+  const double loss = block_sum_1024(ls + (double)reg * sq);
+  if (threadIdx.x == 0 && loss_out) *loss_out = (float)loss;
 }
 
 // sgd on the touched rows: one wave per (triplet, role); the first claimant of a row applies and clears its gradient
@@ -548,12 +504,7 @@ __global__ __launch_bounds__(256) void k_acf_apply_sgd(float *Gu, float *Gi, flo
   if (t >= 3 * B) return;
   const int role = (int)(t / B);
   const int64_t b = t - (int64_t)role * B;
-  int r;
-  if (role == 0) {
-    r = user[b]; r = r < 0 ? 0 : (r >= U ? U - 1 : r);
-  } else {
-    r = role == 1 ? pos[b] : neg[b]; r = r < 0 ? 0 : (r >= I ? I - 1 : r);
-  }
+  const int r = role == 0 ? clamp_quiet(user[b], U) : clamp_quiet(role == 1 ? pos[b] : neg[b], I);
   int claim = 0;
   if (lane == 0) claim = atomicExch(role == 0 ? flagU + r : flagI + r, 1u) == 0u;
   claim = __shfl(claim, 0, 64);
@@ -569,29 +520,12 @@ __global__ __launch_bounds__(256) void k_acf_apply_sgd(float *Gu, float *Gi, flo
   }
 }
 
-// adam_tf23 (sparse rule, not lazy): every row of Gu, Gi, Pi moves every step (ACF.py:266-268)
-struct AcfSweep { float *p[3], *m[3], *v[3], *g[3]; size_t n[3]; };
-__global__ __launch_bounds__(256) void k_acf_sweep(AcfSweep S, float b1, float b2, float lr_t, float eps) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x, first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < 3; ++q)
-    for (size_t e = first; e < S.n[q]; e += stride) {
-      float pp = S.p[q][e], mm = S.m[q][e], vv = S.v[q][e];
-      adam_elem(pp, mm, vv, S.g[q][e], b1, b2, lr_t, eps);
-      S.p[q][e] = pp; S.m[q][e] = mm; S.v[q][e] = vv;
-      S.g[q][e] = 0.f;
-    }
-}
-
 __global__ __launch_bounds__(256) void k_acf_finish(const int32_t *__restrict__ user, const int32_t *__restrict__ pos,
                                                     const int32_t *__restrict__ neg, int64_t B, int U, int I, int32_t *uslot,
                                                     uint32_t *flagU, uint32_t *flagI) {
   const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  int u = user[b], i = pos[b], j = neg[b];
-  u = u < 0 ? 0 : (u >= U ? U - 1 : u);
-  i = i < 0 ? 0 : (i >= I ? I - 1 : i);
-  j = j < 0 ? 0 : (j >= I ? I - 1 : j);
+  const int u = clamp_quiet(user[b], U), i = clamp_quiet(pos[b], I), j = clamp_quiet(neg[b], I);
   uslot[u] = INT_MAX;
   flagU[u] = 0u; flagI[i] = 0u; flagI[j] = 0u;
 }
@@ -603,15 +537,11 @@ __global__ __launch_bounds__(256) void k_acf_score(const float *__restrict__ gp,
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (b >= n) return;
-  const int i = acf_clamp(item[b], I, errflag, 2);
+  const int i = clamp_index(item[b], I, errflag, 2);
   float s = 0.f;
   for (int c = lane; c < k; c += 64) s = fmaf(gp[b * k + c], Gi[(int64_t)i * k + c], s);
   s = wave_sum(s);
   if (lane == 0) x[b] = s;
-}
-
-__global__ void k_acf_fill(int32_t *p, size_t n, int32_t v) {
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) p[e] = v;
 }
 
 // ---- bprx_acf_explain: the pair pass ----------------------------------------------------------------------------------
@@ -647,7 +577,7 @@ __global__ __launch_bounds__(256) void k_acf_explain(AcfExplainArgs A, const int
   __syncthreads();
   const int64_t b = (int64_t)blockIdx.x * 4 + w;
   if (b >= n) return;
-  const int u = acf_clamp(user[b], A.U, A.errflag, 1), i = acf_clamp(item[b], A.I, A.errflag, 2);
+  const int u = clamp_index(user[b], A.U, A.errflag, 1), i = clamp_index(item[b], A.I, A.errflag, 2);
   const float *st = A.ustat + (int64_t)u * (2 + hc);
   const float gm = st[0], D = st[1];
   for (int j = lane; j < hc; j += 64) uc[j] = st[2 + j];
@@ -673,7 +603,7 @@ __global__ __launch_bounds__(256) void k_acf_explain(AcfExplainArgs A, const int
     int l = 0;
     float a = 0.f;
     if (p < end) {
-      l = acf_clamp(A.items[p], A.I, A.errflag, 5);
+      l = clamp_index(A.items[p], A.I, A.errflag, 5);
       a = expf(A.tl[p] - gm) / D;
     }
     const int m = (int)(end - p0 < 64 ? end - p0 : 64);
@@ -731,7 +661,7 @@ __global__ __launch_bounds__(256) void k_acf_explain(AcfExplainArgs A, const int
     const int ps = __shfl(tp, s, 64);
     const float cs = __shfl(tv, s, 64);
     const int64_t p = beg + ps;
-    const int l = acf_clamp(A.items[p], A.I, A.errflag, 5);
+    const int l = clamp_index(A.items[p], A.I, A.errflag, 5);
     const float al = expf(A.tl[p] - gm) / D;
     const float *Zl = A.Z + (int64_t)l * M * NP;
     float lmax = -INFINITY;
@@ -791,8 +721,8 @@ __global__ __launch_bounds__(256) void k_acf_q(AcfStepArgs A, const int32_t *__r
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (b >= B) return;
-  const int u = acf_clamp(user[b], A.U, A.errflag, 1), i = acf_clamp(pos[b], A.I, A.errflag, 2),
-            j = acf_clamp(neg[b], A.I, A.errflag, 2);
+  const int u = clamp_index(user[b], A.U, A.errflag, 1), i = clamp_index(pos[b], A.I, A.errflag, 2),
+            j = clamp_index(neg[b], A.I, A.errflag, 2);
   const int k = A.k;
   const int64_t row = A.uslot[u];
   const float *g = A.gp + row * k, *gi = A.Gi + (int64_t)i * k, *gj = A.Gi + (int64_t)j * k;
@@ -828,7 +758,7 @@ __global__ __launch_bounds__(256) void k_acf_user_bwd(AcfUserArgs A, AcfBwdArgs 
   const int64_t b = blockIdx.x;
   if (b >= n) return;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int u = acf_clamp(users[b], A.U, A.errflag, 1);
+  const int u = clamp_index(users[b], A.U, A.errflag, 1);
   if (uslot[u] != (int32_t)b) return;
   const int k = A.k, M = A.M, hc = A.hc, ha = A.ha, NP = A.NP, W2 = 2 * (hc + ha);
   float *gu = sm, *qs = gu + k, *uc = qs + k, *ui = uc + hc, *w1c = ui + ha, *w1i = w1c + hc;
@@ -873,7 +803,7 @@ __global__ __launch_bounds__(256) void k_acf_user_bwd(AcfUserArgs A, AcfBwdArgs 
     int run_l = -1;
     float run_a = 0.f;
     for (int64_t p = beg + w; p < end; p += 4) {
-      const int l = acf_clamp(A.items[p], A.I, A.errflag, 5);
+      const int l = clamp_index(A.items[p], A.I, A.errflag, 5);
       const float *Zl = A.Z + (int64_t)l * M * NP;
       float lmax = -INFINITY;
       for (int m = lane; m < M; m += 64) {                   // component scores, as k_acf_user
@@ -1231,13 +1161,13 @@ __global__ __launch_bounds__(256) void k_acf_proj_bwd_bf16(const uint16_t *__res
       const float x[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const uint16_t hi = bf16_rne(x[i]);
+        const uint16_t hi = (uint16_t)bf16_rne(x[i]);
         const float r1 = x[i] - __uint_as_float((uint32_t)hi << 16);
-        const uint16_t mi = bf16_rne(r1);
+        const uint16_t mi = (uint16_t)bf16_rne(r1);
         const float r2 = r1 - __uint_as_float((uint32_t)mi << 16);
         Bh[c4 * 4 + i][row] = hi;
         Bm[c4 * 4 + i][row] = mi;
-        Bl[c4 * 4 + i][row] = bf16_rne(r2);
+        Bl[c4 * 4 + i][row] = (uint16_t)bf16_rne(r2);
       }
     }
     __syncthreads();
@@ -1299,16 +1229,10 @@ __global__ __launch_bounds__(256) void k_acf_finish_list(const int32_t *__restri
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
-static unsigned acf_grid(int64_t work, int64_t per_block, int64_t cap) {
-  int64_t g = (work + per_block - 1) / per_block;
-  if (g > cap) g = cap;
-  return (unsigned)(g < 1 ? 1 : g);
-}
-
 static int acf_wcat(bprx_handle *h, hipStream_t s) {
   AcfState *S = h->acf;
   const bool bf = S->fdt == BPRX_F_BF16;
-  hipLaunchKernelGGL(k_acf_wcat, dim3(acf_grid((int64_t)S->Cp * S->NP, 256, 2048)), dim3(256), 0, s, S->a.w[BPRX_ACF_C_WI],
+  hipLaunchKernelGGL(k_acf_wcat, dim3(bprx_blocks((int64_t)S->Cp * S->NP, 256, 2048)), dim3(256), 0, s, S->a.w[BPRX_ACF_C_WI],
                      S->a.w[BPRX_ACF_I_WX], S->C, S->Cp, S->hc, S->ha, S->NP, bf ? (float *)nullptr : S->Wc,
                      bf ? S->Wh : (uint16_t *)nullptr, bf ? S->Wl : (uint16_t *)nullptr);
   BPRX_LAUNCH_CHECK(h, "k_acf_wcat");
@@ -1319,7 +1243,7 @@ static int acf_wcat(bprx_handle *h, hipStream_t s) {
 static int acf_project(bprx_handle *h, const int32_t *list, const int32_t *nlist, hipStream_t s) {
   AcfState *S = h->acf;
   const int I = h->cfg.num_items, NCT = S->NP / 32;
-  const unsigned pg = acf_grid((int64_t)I * S->M, 64, (int64_t)h->num_cu * 4);
+  const unsigned pg = bprx_blocks((int64_t)I * S->M, 64, (int64_t)h->num_cu * 4);
   {
     BprxProfScope ps(h, BPRX_PHASE_PROJ_FWD, s);
 #define ACF_PROJ(N)                                                                                                           \
@@ -1338,7 +1262,7 @@ static int acf_project(bprx_handle *h, const int32_t *list, const int32_t *nlist
 #undef ACF_PROJ
     BPRX_LAUNCH_CHECK(h, "k_acf_proj");
   }
-  hipLaunchKernelGGL(k_acf_itemvec, dim3(acf_grid(I, 4, 4096)), dim3(256), 0, s, h->t.Gi, S->a.Pi, S->a.w[BPRX_ACF_I_WV],
+  hipLaunchKernelGGL(k_acf_itemvec, dim3(bprx_blocks(I, 4, 4096)), dim3(256), 0, s, h->t.Gi, S->a.Pi, S->a.w[BPRX_ACF_I_WV],
                      S->a.w[BPRX_ACF_I_WP], list, nlist, I, S->k, S->ha, S->GP);
   BPRX_LAUNCH_CHECK(h, "k_acf_itemvec");
   return BPRX_OK;
@@ -1393,7 +1317,7 @@ static size_t acf_user_bwd_lds(const AcfState *S) {
 
 static int acf_reduce(bprx_handle *h, int nsplit, int64_t sstride, int rows, int ld, float *out0, int w0, float *out1, int w1,
                       hipStream_t s) {
-  hipLaunchKernelGGL(k_acf_reduce, dim3(acf_grid((int64_t)rows * ld, 256, 1024)), dim3(256), 0, s, h->acf->part, nsplit, sstride,
+  hipLaunchKernelGGL(k_acf_reduce, dim3(bprx_blocks((int64_t)rows * ld, 256, 1024)), dim3(256), 0, s, h->acf->part, nsplit, sstride,
                      rows, ld, out0, w0, out1, w1);
   BPRX_LAUNCH_CHECK(h, "k_acf_reduce");
   return BPRX_OK;
@@ -1425,14 +1349,14 @@ static int acf_backward(bprx_handle *h, const AcfStepArgs &A, const int32_t *use
   }
   {
     BprxProfScope ps(h, BPRX_PHASE_LOSS, s);
-    hipLaunchKernelGGL(k_acf_item_bwd, dim3(acf_grid(I, 4, 4096)), dim3(256), 0, s, S->a.w[BPRX_ACF_I_WV], S->a.w[BPRX_ACF_I_WP],
+    hipLaunchKernelGGL(k_acf_item_bwd, dim3(bprx_blocks(I, 4, 4096)), dim3(256), 0, s, S->a.w[BPRX_ACF_I_WV], S->a.w[BPRX_ACF_I_WP],
                        S->dGP, S->ilist, S->nlist, k, ha, h->dGi, S->dPi);
     BPRX_LAUNCH_CHECK(h, "k_acf_item_bwd");
     // dWiv = sum_l Gi_l (x) dGP_l, dWip = sum_l Pi_l (x) dGP_l over the listed items
     AcfOuter O;
     O.V = S->dGP; O.ldv = ha; O.W = ha; O.k = k; O.U = U; O.B = B; O.user = user; O.uslot = S->uslot; O.list = S->ilist;
     O.nlist = S->nlist;
-    const int isplit = (int)acf_grid(I, 16, ACF_SPLIT);
+    const int isplit = (int)bprx_blocks(I, 16, ACF_SPLIT);
     const dim3 gi((unsigned)(((k + 63) / 64) * ((ha + 63) / 64)), (unsigned)isplit);
     const float *R[2] = {h->t.Gi, S->a.Pi};
     float *out[2] = {S->gw[BPRX_ACF_I_WV], S->gw[BPRX_ACF_I_WP]};
@@ -1444,7 +1368,7 @@ static int acf_backward(bprx_handle *h, const AcfStepArgs &A, const int32_t *use
     }
     // [dWcu | dWiu] = sum_u g_u (x) [duc_u | dui_u] over the distinct users
     O.R = h->t.Gu; O.V = S->UV; O.ldv = W2; O.W = W; O.list = nullptr; O.nlist = nullptr;
-    const int usplit = (int)acf_grid(B, 16, ACF_SPLIT);
+    const int usplit = (int)bprx_blocks(B, 16, ACF_SPLIT);
     hipLaunchKernelGGL(k_acf_outer, dim3((unsigned)(((k + 63) / 64) * ((W + 63) / 64)), (unsigned)usplit), dim3(256), 0, s, O, S->part);
     BPRX_LAUNCH_CHECK(h, "k_acf_outer");
     if ((rc = acf_reduce(h, usplit, (int64_t)k * W, k, W, S->gw[BPRX_ACF_C_WU], hc, S->gw[BPRX_ACF_I_WU], ha, s))) return rc;
@@ -1471,7 +1395,7 @@ static int acf_backward(bprx_handle *h, const AcfStepArgs &A, const int32_t *use
     BPRX_LAUNCH_CHECK(h, "k_acf_proj_bwd");
     if ((rc = acf_reduce(h, S->nsplit_proj, (int64_t)Crows * S->NP, S->C, S->NP, S->gw[BPRX_ACF_C_WI], hc, S->gw[BPRX_ACF_I_WX], ha, s)))
       return rc;
-    hipLaunchKernelGGL(k_acf_clear, dim3(acf_grid(I, 1, 8192)), dim3(256), 0, s, S->dZ, S->dGP, S->ilist, S->nlist,
+    hipLaunchKernelGGL(k_acf_clear, dim3(bprx_blocks(I, 1, 8192)), dim3(256), 0, s, S->dZ, S->dGP, S->ilist, S->nlist,
                        (int64_t)S->M * S->NP, ha);
     BPRX_LAUNCH_CHECK(h, "k_acf_clear");
   }
@@ -1488,8 +1412,7 @@ int bprx_acf_step(bprx_handle *h, const int32_t *user, const int32_t *pos, const
   float lr_t = h->cfg.lr;
   if (adam) {
     h->adam_t += 1;
-    const float t = (float)h->adam_t;
-    lr_t = h->cfg.lr * sqrtf(1.0f - powf(h->cfg.beta2, t)) / (1.0f - powf(h->cfg.beta1, t));
+    lr_t = bprx_adam_lr_t(h);
   }
   h->pend_lr = lr_t;
   int rc;
@@ -1522,27 +1445,25 @@ int bprx_acf_step(bprx_handle *h, const int32_t *user, const int32_t *pos, const
   {
     BprxProfScope ps(h, BPRX_PHASE_APPLY, s);
     if (adam) {
-      AcfSweep W;
-      W.p[0] = h->t.Gu; W.m[0] = h->t.m_Gu; W.v[0] = h->t.v_Gu; W.g[0] = h->dGu; W.n[0] = (size_t)U * k;
-      W.p[1] = h->t.Gi; W.m[1] = h->t.m_Gi; W.v[1] = h->t.v_Gi; W.g[1] = h->dGi; W.n[1] = (size_t)I * k;
-      W.p[2] = S->a.Pi; W.m[2] = S->a.m_Pi; W.v[2] = S->a.v_Pi; W.g[2] = S->dPi; W.n[2] = (size_t)I * k;
-      const size_t most = (size_t)(U > I ? U : I) * k;
-      hipLaunchKernelGGL(k_acf_sweep, dim3(acf_grid((int64_t)most, 256, 4096)), dim3(256), 0, s, W, h->cfg.beta1, h->cfg.beta2,
-                         lr_t, h->cfg.epsilon);
-      BPRX_LAUNCH_CHECK(h, "k_acf_sweep");
+      // every row of Gu, Gi, Pi moves every step (ACF.py:266-268)
+      AdamSweepAll W = {};
+      W.seg[0] = {h->t.Gu, h->t.m_Gu, h->t.v_Gu, h->dGu, (size_t)U * k};
+      W.seg[1] = {h->t.Gi, h->t.m_Gi, h->t.v_Gi, h->dGi, (size_t)I * k};
+      W.seg[2] = {S->a.Pi, S->a.m_Pi, S->a.v_Pi, S->dPi, (size_t)I * k};
+      if ((rc = bprx_launch_adam_sweep(h, W, lr_t, s))) return rc;
     } else {
       hipLaunchKernelGGL(k_acf_apply_sgd, dim3((unsigned)((3 * B + 3) / 4)), dim3(256), 0, s, h->t.Gu, h->t.Gi, S->a.Pi, h->dGu,
                          h->dGi, S->dPi, h->flagU, h->flagI, user, pos, neg, B, U, I, k, lr_t);
       BPRX_LAUNCH_CHECK(h, "k_acf_apply_sgd");
       if (full) {
-        hipLaunchKernelGGL(k_acf_apply_sgd_list, dim3(acf_grid(I, 4, 4096)), dim3(256), 0, s, h->t.Gi, S->a.Pi, h->dGi, S->dPi,
+        hipLaunchKernelGGL(k_acf_apply_sgd_list, dim3(bprx_blocks(I, 4, 4096)), dim3(256), 0, s, h->t.Gi, S->a.Pi, h->dGi, S->dPi,
                            h->flagI, S->ilist, S->nlist, k, lr_t);
         BPRX_LAUNCH_CHECK(h, "k_acf_apply_sgd_list");
       }
     }
   }
   if (full && !adam) {
-    hipLaunchKernelGGL(k_acf_finish_list, dim3(acf_grid(I, 256, 1024)), dim3(256), 0, s, S->ilist, S->nlist, h->flagI);
+    hipLaunchKernelGGL(k_acf_finish_list, dim3(bprx_blocks(I, 256, 1024)), dim3(256), 0, s, S->ilist, S->nlist, h->flagI);
     BPRX_LAUNCH_CHECK(h, "k_acf_finish_list");
   }
   hipLaunchKernelGGL(k_acf_finish, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, user, pos, neg, B, U, I, S->uslot, h->flagU,
@@ -1660,8 +1581,7 @@ extern "C" int bprx_bind_acf(bprx_handle *h, const bprx_tables *t, const bprx_ac
       bprx_acf_free(h);
       BPRX_FAIL(h, BPRX_E_NOMEM, "bind_acf: scratch allocation failed (Z: %zu MB)", (I * a->feat_m * NP * 4) >> 20);
     }
-    hipLaunchKernelGGL(k_acf_fill, dim3(512), dim3(256), 0, nullptr, S->uslot, U, (int32_t)INT_MAX);
-    BPRX_LAUNCH_CHECK(h, "k_acf_fill");
+    if ((rc = bprx_launch_fill_i32(h, S->uslot, U, (int32_t)INT_MAX, nullptr))) return rc;
     if (acf_user_lds(S) > 65536) {
       bprx_acf_free(h);
       BPRX_FAIL(h, BPRX_E_INVALID, "bind_acf: M = %d with embed_k = %d needs more LDS than a workgroup has", a->feat_m, (int)k);

@@ -434,8 +434,7 @@ extern "C" int bprx_step_begin_sparse(bprx_handle *h, const int32_t *user, const
     h->list_mode = 0; h->item_mode = 0; h->step_masked = false; h->mask_kind = 0;
     if (h->cfg.optimizer == BPRX_OPT_ADAM_TF23) {
       h->adam_t += 1;
-      const float t = (float)h->adam_t;
-      const float lr_t = h->cfg.lr * sqrtf(1.0f - powf(h->cfg.beta2, t)) / (1.0f - powf(h->cfg.beta1, t));
+      const float lr_t = bprx_adam_lr_t(h);
       if (h->adam_lazy) {
         if (h->adam_t - h->adam_synced >= bprx_adam_hist() - 2 && (rc = bprx_launch_adam_sync(h, h->adam_t - 1, s))) return rc;
         if ((rc = bprx_launch_adam_catchup(h, nullptr, nullptr, nullptr, 0, lr_t, s))) return rc;   // records lr_t of this step
@@ -459,8 +458,7 @@ extern "C" int bprx_step_begin_sparse(bprx_handle *h, const int32_t *user, const
   bool catchup_aside = false;     // the (ALU-bound) lazy-Adam catch-up runs on the side stream beside the (HBM-bound) projection
   if (h->cfg.optimizer == BPRX_OPT_ADAM_TF23) {
     h->adam_t += 1;
-    float t = (float)h->adam_t;
-    lr_t = h->cfg.lr * sqrtf(1.0f - powf(h->cfg.beta2, t)) / (1.0f - powf(h->cfg.beta1, t));
+    lr_t = bprx_adam_lr_t(h);
     if (h->adam_lazy) {
       // the ring holds lr_s of the last ADAM_HIST steps: before it would wrap, everything is caught up (amortised: one
       // sweep per ~8000 steps); then the rows of THIS batch are brought to step t-1 for the forward pass
@@ -599,8 +597,7 @@ extern "C" int bprx_step_end(bprx_handle *h, float *loss_out, void *stream) {
   int rc;
   float lr_t = h->cfg.lr;
   if (h->cfg.optimizer == BPRX_OPT_ADAM_TF23) {
-    float t = (float)h->adam_t;
-    lr_t = h->cfg.lr * sqrtf(1.0f - powf(h->cfg.beta2, t)) / (1.0f - powf(h->cfg.beta1, t));
+    lr_t = bprx_adam_lr_t(h);
   }
   int64_t B = h->pending_B;
   h->pending_B = 0;

@@ -61,28 +61,6 @@ struct AfState {
   bool eval_valid;
 };
 
-__device__ __forceinline__ int af_clamp(int v, int n, int32_t *errflag, int code) {
-  if ((unsigned)v >= (unsigned)n) {
-    *errflag = code;
-    return v < 0 ? 0 : n - 1;
-  }
-  return v;
-}
-__device__ __forceinline__ float af_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ void af_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ uint32_t af_bf16_rne(float x) {
-  const uint32_t b = __float_as_uint(x);
-  return (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
-}
-
 // ---- dropout stream ----------------------------------------------------------------------------------------------------
 struct AfDrop { uint32_t k0, k1, step, thr; float scale; int on; };   // thr = rate * 2^32; on == 0: no mask, no scaling
 
@@ -118,12 +96,12 @@ __global__ __launch_bounds__(256) void k_af_claim(const int32_t *__restrict__ ia
                                                   int32_t *__restrict__ islot, int32_t *__restrict__ uslot, int32_t *errflag) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r < n) {
-    const int it = af_clamp(r < nsplit ? ia[r] : ib[r - nsplit], I, errflag, 2);
+    const int it = clamp_index(r < nsplit ? ia[r] : ib[r - nsplit], I, errflag, 2);
     rowitem[r] = it;
     if (islot) atomicMin(islot + it, (int32_t)r);
   }
   if (users && r < nu) {
-    const int u = af_clamp(users[r], U, errflag, 1);
+    const int u = clamp_index(users[r], U, errflag, 1);
     rowuser[r] = u;
     if (uslot) atomicMin(uslot + u, (int32_t)r);
   }
@@ -139,10 +117,6 @@ __global__ __launch_bounds__(256) void k_af_release(const int32_t *__restrict__ 
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r < n) islot[rowitem[r]] = INT_MAX;
   if (r < nu) uslot[rowuser[r]] = INT_MAX;
-}
-
-__global__ void k_af_fill(int32_t *p, size_t n, int32_t v) {
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) p[e] = v;
 }
 
 // ---- edge encoder: conv5x5 + bias + relu + maxpool2x2 + global mean, forward and (BWD) weight gradient --------------------
@@ -223,11 +197,11 @@ __global__ __launch_bounds__(256) void k_af_conv(const uint8_t *__restrict__ edg
     for (int j = 0; j < 8; ++j) {
       const int tap = af_slot_tap(g, j);
       const float x = tap >= 0 ? cw[tap * AF_CH + c] : 0.f;
-      const uint32_t hi = af_bf16_rne(x);
+      const uint32_t hi = bf16_rne(x);
       const float r1 = x - __uint_as_float(hi << 16);
-      const uint32_t mid = af_bf16_rne(r1);
+      const uint32_t mid = bf16_rne(r1);
       const float r2 = r1 - __uint_as_float(mid << 16);
-      t3[0][j] = hi; t3[1][j] = mid; t3[2][j] = af_bf16_rne(r2);
+      t3[0][j] = hi; t3[1][j] = mid; t3[2][j] = bf16_rne(r2);
     }
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
@@ -495,7 +469,7 @@ __device__ __forceinline__ void af_att_fwd(const AfAtt &A, const float *gu, cons
   }
   const float b2 = A.b2[0];
 #pragma unroll
-  for (int l = 0; l < 3; ++l) a[l] = af_wave_sum(part[l]) + b2;
+  for (int l = 0; l < 3; ++l) a[l] = wave_sum(part[l]) + b2;
 }
 __device__ __forceinline__ void af_softmax3(const float (&a)[3], float (&al)[3]) {
   const float m = fmaxf(a[0], fmaxf(a[1], a[2]));
@@ -518,7 +492,7 @@ __global__ __launch_bounds__(256) void k_af_pairs(AfAtt A, const int32_t *__rest
 #pragma unroll
     for (int l = 0; l < 3; ++l) cs[l * k + c] = A.C[((int64_t)l * A.ldr + r) * k + c];
   }
-  af_wave_sync();
+  wave_sync();
   float a[3], al[3];
   af_att_fwd(A, gu, cs, lane, a, nullptr, 0, 0);
   af_softmax3(a, al);
@@ -527,7 +501,7 @@ __global__ __launch_bounds__(256) void k_af_pairs(AfAtt A, const int32_t *__rest
     const float wf = al[0] * cs[c] + al[1] * cs[k + c] + al[2] * cs[2 * k + c];
     s = fmaf(gu[c] * wf, A.Gi[(int64_t)it * k + c], s);
   }
-  s = af_wave_sum(s);
+  s = wave_sum(s);
   if (lane == 0) {
     x[r] = s;
     if (alpha) { alpha[r * 3] = al[0]; alpha[r * 3 + 1] = al[1]; alpha[r * 3 + 2] = al[2]; }
@@ -585,15 +559,15 @@ __global__ __launch_bounds__(256) void k_af_explain(AfExpl X) {
     for (int l = 0; l < 3; ++l) t[l] = fmaf(pg, X.A.C[((int64_t)l * X.A.ldr + r) * k + c], t[l]);
   }
 #pragma unroll
-  for (int l = 0; l < 3; ++l) t[l] = af_wave_sum(t[l]);
-  af_wave_sync();
+  for (int l = 0; l < 3; ++l) t[l] = wave_sum(t[l]);
+  wave_sync();
   {
     const float *wr = X.W2e + (int64_t)lane * k;
     float v = 0.f;
     for (int c = 0; c < k; ++c) v = fmaf(wr[c], p[c], v);
     vs[lane] = v;
   }
-  af_wave_sync();
+  wave_sync();
   const float al[3] = {X.alpha[r * 3], X.alpha[r * 3 + 1], X.alpha[r * 3 + 2]};
   if (lane < 3) X.parts[r * 3 + lane] = lane == 0 ? al[0] * t[0] : lane == 1 ? al[1] * t[1] : al[2] * t[2];
   const float scale = al[1] * (1.0f / AF_WIN);
@@ -650,7 +624,7 @@ __global__ __launch_bounds__(256) void k_af_triplet(AfTrip T) {
     for (int s = 0; s < 2; ++s)
       for (int l = 0; l < 3; ++l) cs[(s * 3 + l) * k + c] = A.C[((int64_t)l * A.ldr + s * B + b) * k + c];
   }
-  af_wave_sync();
+  wave_sync();
   float a[2][3], al[2][3], x[2] = {0.f, 0.f}, nrm = 0.f;
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
@@ -669,7 +643,7 @@ __global__ __launch_bounds__(256) void k_af_triplet(AfTrip T) {
       nrm += gi * gi + c3[c] * c3[c] + c3[k + c] * c3[k + c] + c3[2 * k + c] * c3[2 * k + c];
     }
   }
-  x[0] = af_wave_sum(x[0]); x[1] = af_wave_sum(x[1]); nrm = af_wave_sum(nrm);
+  x[0] = wave_sum(x[0]); x[1] = wave_sum(x[1]); nrm = wave_sum(nrm);
   const float diff = x[0] - x[1];
   const bool inr = (diff >= -80.0f) && (diff <= 1e8f);                 // tf.clip_by_value gradient mask
   const float z = -fminf(fmaxf(diff, -80.0f), 1e8f);
@@ -688,7 +662,7 @@ __global__ __launch_bounds__(256) void k_af_triplet(AfTrip T) {
       for (int l = 0; l < 3; ++l) dal[l] = fmaf(t, cs[(s * 3 + l) * k + c], dal[l]);
     }
 #pragma unroll
-    for (int l = 0; l < 3; ++l) dal[l] = af_wave_sum(dal[l]);
+    for (int l = 0; l < 3; ++l) dal[l] = wave_sum(dal[l]);
     const float dot = al[s][0] * dal[0] + al[s][1] * dal[1] + al[s][2] * dal[2];
 #pragma unroll
     for (int l = 0; l < 3; ++l) {
@@ -707,7 +681,7 @@ __global__ __launch_bounds__(256) void k_af_triplet(AfTrip T) {
         dh[(s * 3 + l) * h + j] = v;
       }
   }
-  af_wave_sync();
+  wave_sync();
   for (int c = lane; c < k; c += 64) {
     float dp[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const float *wr = A.W1 + (int64_t)c * h;
@@ -791,56 +765,28 @@ __global__ __launch_bounds__(256) void k_af_apply_sgd(float *__restrict__ tab, f
   }
 }
 
-// adam_tf23, sparse rule (not lazy): every row of Gu and Gi moves every step
-struct AfSweep { float *p[2], *m[2], *v[2], *g[2]; size_t n[2]; };
-__global__ __launch_bounds__(256) void k_af_sweep(AfSweep S, float b1, float b2, float lr_t, float eps) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x, first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-    for (size_t e = first; e < S.n[q]; e += stride) {
-      float pp = S.p[q][e], mm = S.m[q][e], vv = S.v[q][e];
-      adam_elem(pp, mm, vv, S.g[q][e], b1, b2, lr_t, eps);
-      S.p[q][e] = pp; S.m[q][e] = mm; S.v[q][e] = vv;
-      S.g[q][e] = 0.f;
-    }
-}
-
 // the step's loss: per-triplet terms + reg * |attention tensors|^2, one workgroup, fixed order
 struct AfDense { float *w[BPRX_AF_NW], *m[BPRX_AF_NW], *v[BPRX_AF_NW], *g[BPRX_AF_NW]; int64_t n[BPRX_AF_NW]; };
 __global__ __launch_bounds__(1024) void k_af_loss(AfDense T, float reg, const float *__restrict__ lossb, int64_t B,
                                                   float *__restrict__ loss_out) {
-  __shared__ double red[1024];
   double sq = 0.0, ls = 0.0;
   for (int q = BPRX_AF_ATT_W1; q < BPRX_AF_NW; ++q)
     for (int64_t e = threadIdx.x; e < T.n[q]; e += 1024) sq += (double)T.w[q][e] * (double)T.w[q][e];
   for (int64_t b = threadIdx.x; b < B; b += 1024) ls += (double)lossb[b];
-  red[threadIdx.x] = ls + (double)reg * sq;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && loss_out) *loss_out = (float)red[0];
+  const double loss = block_sum_1024(ls + (double)reg * sq);
+  if (threadIdx.x == 0 && loss_out) *loss_out = (float)loss;
 }
 
-// sgd or TF-2.3 dense ApplyAdam (as k_dense_update / k_acf_dense) on every tensor; the attention tensors carry 2 reg w
+// sgd or TF-2.3 dense ApplyAdam (dense_adam_elem) on every tensor; the attention tensors carry 2 reg w
 __global__ __launch_bounds__(256) void k_af_update(AfDense T, int adam, float lr_t, float reg, float b1, float b2, float eps) {
-  const float omb1 = 1.0f - b1, omb2 = 1.0f - b2, r2 = 2.f * reg;
+  const float r2 = 2.f * reg;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x, first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (int q = 0; q < BPRX_AF_NW; ++q) {
     float *p = T.w[q];
     for (int64_t e = first; e < T.n[q]; e += stride) {
       const float pv = p[e];
       const float g = q >= BPRX_AF_ATT_W1 ? T.g[q][e] + r2 * pv : T.g[q][e];
-      if (adam) {
-        const float mo = T.m[q][e], vo = T.v[q][e];
-        const float mt = mo + (g - mo) * omb1;
-        const float vt = vo + (g * g - vo) * omb2;
-        T.m[q][e] = mt; T.v[q][e] = vt;
-        p[e] = pv - lr_t * mt / (sqrtf(vt) + eps);
-      } else {
-        p[e] = pv - lr_t * g;
-      }
+      p[e] = dense_adam_elem(pv, T.m[q] + e, T.v[q] + e, g, adam, lr_t, b1, b2, eps);
     }
   }
 }
@@ -926,8 +872,6 @@ __global__ __launch_bounds__(256) void k_af_block(AfAtt A, const float *__restri
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-static unsigned af_blocks(int64_t work, int64_t per) { return (unsigned)((work + per - 1) / per < 1 ? 1 : (work + per - 1) / per); }
-
 static AfDrop af_drop(const AfState *S, int64_t step, bool training) {
   AfDrop d;
   d.k0 = (uint32_t)S->a.seed; d.k1 = (uint32_t)(S->a.seed >> 32); d.step = (uint32_t)step;
@@ -966,7 +910,7 @@ static int af_encode_rows(bprx_handle *h, int64_t n, bool dedupe, const AfDrop &
                        S->rowitem, islot, n, S->pool, (const float *)nullptr, (float *)nullptr);
     BPRX_LAUNCH_CHECK(h, "k_af_conv<fwd>");
   }
-  hipLaunchKernelGGL(k_af_pooldrop, dim3(af_blocks(n * (AF_CH / 4), 256)), dim3(256), 0, s, S->pool, S->rowitem, islot, n, d, S->PD);
+  hipLaunchKernelGGL(k_af_pooldrop, dim3(bprx_blocks(n * (AF_CH / 4), 256)), dim3(256), 0, s, S->pool, S->rowitem, islot, n, d, S->PD);
   BPRX_LAUNCH_CHECK(h, "k_af_pooldrop");
   if ((rc = af_gemm(h, s, false, false, S->a.color, S->Dc, S->rowitem, S->a.w[BPRX_AF_COL_W1], AF_HID, S->Hc, AF_HID, (int)n, AF_HID,
                     S->Dc, 1, S->a.w[BPRX_AF_COL_B1], 0, &d))) return rc;
@@ -1007,14 +951,13 @@ static int af_step_body(bprx_handle *h, const int32_t *user, const int32_t *pos,
   float lr_t = h->cfg.lr;
   if (adam) {
     h->adam_t += 1;
-    const float t = (float)h->adam_t;
-    lr_t = h->cfg.lr * sqrtf(1.0f - powf(h->cfg.beta2, t)) / (1.0f - powf(h->cfg.beta1, t));
+    lr_t = bprx_adam_lr_t(h);
   }
   h->pend_lr = lr_t;
   const AfDrop d = af_drop(S, S->step, true);
   S->step += 1;
   int rc;
-  hipLaunchKernelGGL(k_af_claim, dim3(af_blocks(R, 256)), dim3(256), 0, s, pos, neg, B, R, user, B, I, U, S->rowitem, S->rowuser,
+  hipLaunchKernelGGL(k_af_claim, dim3(bprx_blocks(R, 256)), dim3(256), 0, s, pos, neg, B, R, user, B, I, U, S->rowitem, S->rowuser,
                      S->islot, S->uslot, h->errflag);
   BPRX_LAUNCH_CHECK(h, "k_af_claim");
   if ((rc = af_encode_rows(h, R, true, d, S->C, S->R, s))) return rc;
@@ -1024,7 +967,7 @@ static int af_step_body(bprx_handle *h, const int32_t *user, const int32_t *pos,
     T.A = af_att(h, S->C, S->R);
     T.dC = S->dC; T.A6 = S->A6; T.Hid = S->Hid; T.dHid = S->dHid; T.da = S->da; T.dGuS = S->dGuS; T.dGiS = S->dGiS; T.lossb = h->lossb;
     T.rowuser = S->rowuser; T.rowitem = S->rowitem; T.B = B; T.reg = h->cfg.reg;
-    hipLaunchKernelGGL(k_af_triplet, dim3(af_blocks(B, 4)), dim3(256), 4 * sizeof(float) * (7 * (size_t)k + 6 * (size_t)hh), s, T);
+    hipLaunchKernelGGL(k_af_triplet, dim3(bprx_blocks(B, 4)), dim3(256), 4 * sizeof(float) * (7 * (size_t)k + 6 * (size_t)hh), s, T);
     BPRX_LAUNCH_CHECK(h, "k_af_triplet");
   }
   AfDense D;
@@ -1052,7 +995,7 @@ static int af_step_body(bprx_handle *h, const int32_t *user, const int32_t *pos,
     if ((rc = af_gemm(h, s, true, false, S->PD, AF_CH, nullptr, dC, k, S->g[BPRX_AF_EDG_W2], k, AF_CH, k, (int)R))) return rc;
     if ((rc = af_gemm(h, s, false, true, dC, k, nullptr, S->a.w[BPRX_AF_EDG_W2], k, S->dPD, AF_CH, (int)R, AF_CH, k, 2, nullptr, 0,
                       nullptr, S->PD, d.on ? d.scale : 1.f))) return rc;
-    hipLaunchKernelGGL(k_af_rowsum, dim3(af_blocks(R, 4)), dim3(256), 0, s, S->rowitem, S->islot, R, S->dPD, AF_CH, S->gsum, 1);
+    hipLaunchKernelGGL(k_af_rowsum, dim3(bprx_blocks(R, 4)), dim3(256), 0, s, S->rowitem, S->islot, R, S->dPD, AF_CH, S->gsum, 1);
     BPRX_LAUNCH_CHECK(h, "k_af_rowsum");
     {
       BprxProfScope ps(h, BPRX_PHASE_PROJ_BWD, s);
@@ -1064,8 +1007,8 @@ static int af_step_body(bprx_handle *h, const int32_t *user, const int32_t *pos,
     if ((rc = af_colsum(h, s, S->cpart, R, AF_CPART, S->rowitem, S->islot, S->g[BPRX_AF_EDG_CW]))) return rc;
   }
   // Gu / Gi: per-row gradients summed per distinct row in ascending row order into the staging tables
-  hipLaunchKernelGGL(k_af_rowsum, dim3(af_blocks(R, 4)), dim3(256), 0, s, S->rowitem, S->islot, R, S->dGiS, k, h->dGi, 0);
-  hipLaunchKernelGGL(k_af_rowsum, dim3(af_blocks(B, 4)), dim3(256), 0, s, S->rowuser, S->uslot, B, S->dGuS, k, h->dGu, 0);
+  hipLaunchKernelGGL(k_af_rowsum, dim3(bprx_blocks(R, 4)), dim3(256), 0, s, S->rowitem, S->islot, R, S->dGiS, k, h->dGi, 0);
+  hipLaunchKernelGGL(k_af_rowsum, dim3(bprx_blocks(B, 4)), dim3(256), 0, s, S->rowuser, S->uslot, B, S->dGuS, k, h->dGu, 0);
   BPRX_LAUNCH_CHECK(h, "k_af_rowsum");
   {
     BprxProfScope ps(h, BPRX_PHASE_DENSE, s);
@@ -1076,16 +1019,13 @@ static int af_step_body(bprx_handle *h, const int32_t *user, const int32_t *pos,
   {
     BprxProfScope ps(h, BPRX_PHASE_APPLY, s);
     if (adam) {
-      AfSweep W;
-      W.p[0] = h->t.Gu; W.m[0] = h->t.m_Gu; W.v[0] = h->t.v_Gu; W.g[0] = h->dGu; W.n[0] = (size_t)U * k;
-      W.p[1] = h->t.Gi; W.m[1] = h->t.m_Gi; W.v[1] = h->t.v_Gi; W.g[1] = h->dGi; W.n[1] = (size_t)I * k;
-      const size_t most = (size_t)(U > I ? U : I) * k;
-      const unsigned gb = af_blocks((int64_t)most, 256);
-      hipLaunchKernelGGL(k_af_sweep, dim3(gb > 4096 ? 4096 : gb), dim3(256), 0, s, W, h->cfg.beta1, h->cfg.beta2, lr_t, h->cfg.epsilon);
-      BPRX_LAUNCH_CHECK(h, "k_af_sweep");
+      AdamSweepAll W = {};                                   // every row of Gu and Gi moves every step
+      W.seg[0] = {h->t.Gu, h->t.m_Gu, h->t.v_Gu, h->dGu, (size_t)U * k};
+      W.seg[1] = {h->t.Gi, h->t.m_Gi, h->t.v_Gi, h->dGi, (size_t)I * k};
+      if ((rc = bprx_launch_adam_sweep(h, W, lr_t, s))) return rc;
     } else {
-      hipLaunchKernelGGL(k_af_apply_sgd, dim3(af_blocks(R, 4)), dim3(256), 0, s, h->t.Gi, h->dGi, S->rowitem, S->islot, R, k, lr_t);
-      hipLaunchKernelGGL(k_af_apply_sgd, dim3(af_blocks(B, 4)), dim3(256), 0, s, h->t.Gu, h->dGu, S->rowuser, S->uslot, B, k, lr_t);
+      hipLaunchKernelGGL(k_af_apply_sgd, dim3(bprx_blocks(R, 4)), dim3(256), 0, s, h->t.Gi, h->dGi, S->rowitem, S->islot, R, k, lr_t);
+      hipLaunchKernelGGL(k_af_apply_sgd, dim3(bprx_blocks(B, 4)), dim3(256), 0, s, h->t.Gu, h->dGu, S->rowuser, S->uslot, B, k, lr_t);
       BPRX_LAUNCH_CHECK(h, "k_af_apply_sgd");
     }
   }
@@ -1098,7 +1038,7 @@ int bprx_af_step(bprx_handle *h, const int32_t *user, const int32_t *pos, const 
   const int rc = af_step_body(h, user, pos, neg, B, loss_out, s);
   S->eval_valid = false;
   if (B > 0 && user && pos && neg) {                         // the claim kernel ran (or was at least tried): rowitem / rowuser name the rows
-    hipLaunchKernelGGL(k_af_release, dim3(af_blocks(2 * B, 256)), dim3(256), 0, s, S->rowitem, 2 * B, S->rowuser, B, S->islot, S->uslot);
+    hipLaunchKernelGGL(k_af_release, dim3(bprx_blocks(2 * B, 256)), dim3(256), 0, s, S->rowitem, 2 * B, S->rowuser, B, S->islot, S->uslot);
     if (!rc) BPRX_LAUNCH_CHECK(h, "k_af_release");
   }
   return rc;
@@ -1108,12 +1048,12 @@ int bprx_af_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int6
   AfState *S = h->af;
   if (n > S->R) BPRX_FAIL(h, BPRX_E_INVALID, "attentive pairs: n = %lld > 2 * max_batch", (long long)n);
   int rc;
-  hipLaunchKernelGGL(k_af_claim, dim3(af_blocks(n, 256)), dim3(256), 0, s, item, item, n, n, user, n, h->cfg.num_items, h->cfg.num_users,
+  hipLaunchKernelGGL(k_af_claim, dim3(bprx_blocks(n, 256)), dim3(256), 0, s, item, item, n, n, user, n, h->cfg.num_items, h->cfg.num_users,
                      S->rowitem, S->rowuser, (int32_t *)nullptr, (int32_t *)nullptr, h->errflag);
   BPRX_LAUNCH_CHECK(h, "k_af_claim");
   const AfDrop d = af_drop(S, 0, false);
   if ((rc = af_encode_rows(h, n, false, d, S->C, S->R, s))) return rc;
-  hipLaunchKernelGGL(k_af_pairs, dim3(af_blocks(n, 4)), dim3(256), 16 * sizeof(float) * (size_t)S->k, s, af_att(h, S->C, S->R), S->rowuser,
+  hipLaunchKernelGGL(k_af_pairs, dim3(bprx_blocks(n, 4)), dim3(256), 16 * sizeof(float) * (size_t)S->k, s, af_att(h, S->C, S->R), S->rowuser,
                      S->rowitem, n, x, alpha);
   BPRX_LAUNCH_CHECK(h, "k_af_pairs");
   return BPRX_OK;
@@ -1124,13 +1064,13 @@ static int af_explain_body(bprx_handle *h, const int32_t *user, const int32_t *i
                            float *parts, float *map, int32_t *peak_cell, float *peak_val, int64_t ecap, hipStream_t s) {
   AfState *S = h->af;
   int rc;
-  hipLaunchKernelGGL(k_af_claim, dim3(af_blocks(n, 256)), dim3(256), 0, s, item, item, n, n, user, n, h->cfg.num_items, h->cfg.num_users,
+  hipLaunchKernelGGL(k_af_claim, dim3(bprx_blocks(n, 256)), dim3(256), 0, s, item, item, n, n, user, n, h->cfg.num_items, h->cfg.num_users,
                      S->rowitem, S->rowuser, S->islot, (int32_t *)nullptr, h->errflag);
   BPRX_LAUNCH_CHECK(h, "k_af_claim");
   // x and alpha: the kernels of bprx_af_attention_pairs; the conv runs on the owner rows only and gives the same bits per item
   const AfDrop d = af_drop(S, 0, false);
   if ((rc = af_encode_rows(h, n, true, d, S->C, S->R, s))) return rc;
-  hipLaunchKernelGGL(k_af_pairs, dim3(af_blocks(n, 4)), dim3(256), 16 * sizeof(float) * (size_t)S->k, s, af_att(h, S->C, S->R), S->rowuser,
+  hipLaunchKernelGGL(k_af_pairs, dim3(bprx_blocks(n, 4)), dim3(256), 16 * sizeof(float) * (size_t)S->k, s, af_att(h, S->C, S->R), S->rowuser,
                      S->rowitem, n, x, alpha);
   BPRX_LAUNCH_CHECK(h, "k_af_pairs");
   hipLaunchKernelGGL(k_af_rank, dim3(1), dim3(256), 0, s, S->rowitem, S->islot, n, S->erank);
@@ -1151,7 +1091,7 @@ static int af_explain_body(bprx_handle *h, const int32_t *user, const int32_t *i
     X.rowuser = S->rowuser; X.rowitem = S->rowitem; X.islot = S->islot; X.erank = S->erank;
     X.n = n; X.G = G; X.e0 = (int)e0; X.ecap = (int)ecap;
     X.parts = parts; X.map = map; X.peak_val = peak_val; X.peak_cell = peak_cell;
-    hipLaunchKernelGGL(k_af_explain, dim3(af_blocks(n, 4)), dim3(256), 4 * sizeof(float) * ((size_t)S->k + AF_CH), s, X);
+    hipLaunchKernelGGL(k_af_explain, dim3(bprx_blocks(n, 4)), dim3(256), 4 * sizeof(float) * ((size_t)S->k + AF_CH), s, X);
     BPRX_LAUNCH_CHECK(h, "k_af_explain");
   }
   return BPRX_OK;
@@ -1165,11 +1105,11 @@ static int af_encode_many(bprx_handle *h, const int32_t *items, int64_t n, float
   for (int64_t r0 = 0; r0 < n; r0 += S->R) {
     const int64_t m = n - r0 < S->R ? n - r0 : S->R;
     if (items)
-      hipLaunchKernelGGL(k_af_claim, dim3(af_blocks(m, 256)), dim3(256), 0, s, items + r0, items + r0, m, m, (const int32_t *)nullptr,
+      hipLaunchKernelGGL(k_af_claim, dim3(bprx_blocks(m, 256)), dim3(256), 0, s, items + r0, items + r0, m, m, (const int32_t *)nullptr,
                          (int64_t)0, h->cfg.num_items, h->cfg.num_users, S->rowitem, S->rowuser, (int32_t *)nullptr, (int32_t *)nullptr,
                          h->errflag);
     else
-      hipLaunchKernelGGL(k_af_iota, dim3(af_blocks(m, 256)), dim3(256), 0, s, S->rowitem, m, (int32_t)r0);
+      hipLaunchKernelGGL(k_af_iota, dim3(bprx_blocks(m, 256)), dim3(256), 0, s, S->rowitem, m, (int32_t)r0);
     BPRX_LAUNCH_CHECK(h, "k_af_claim");
     int rc;
     if ((rc = af_encode_rows(h, m, false, d, S->C, S->R, s))) return rc;
@@ -1301,9 +1241,8 @@ extern "C" int bprx_bind_attentive(bprx_handle *h, const bprx_tables *t, const b
     bprx_af_free(h);
     BPRX_FAIL(h, BPRX_E_NOMEM, "bind_attentive: scratch allocation failed");
   }
-  hipLaunchKernelGGL(k_af_fill, dim3(512), dim3(256), 0, nullptr, S->islot, I, (int32_t)INT_MAX);
-  hipLaunchKernelGGL(k_af_fill, dim3(512), dim3(256), 0, nullptr, S->uslot, U, (int32_t)INT_MAX);
-  BPRX_LAUNCH_CHECK(h, "k_af_fill");
+  if ((rc = bprx_launch_fill_i32(h, S->islot, I, (int32_t)INT_MAX, nullptr))) return rc;
+  if ((rc = bprx_launch_fill_i32(h, S->uslot, U, (int32_t)INT_MAX, nullptr))) return rc;
   S->eval_valid = false;
   BPRX_HIP(h, hipStreamSynchronize(nullptr));
   return BPRX_OK;
@@ -1361,7 +1300,7 @@ extern "C" int bprx_af_explain(bprx_handle *h, const int32_t *user, const int32_
   hipStream_t s = (hipStream_t)stream;
   const int rc = af_explain_body(h, user, item, n, grid, x, alpha, parts, map, peak_cell, peak_val, ecap, s);
   // the claims are released on every path (the claim kernel ran, or was at least tried: rowitem names the rows)
-  hipLaunchKernelGGL(k_af_release, dim3(af_blocks(n, 256)), dim3(256), 0, s, S->rowitem, n, S->rowuser, (int64_t)0, S->islot, S->uslot);
+  hipLaunchKernelGGL(k_af_release, dim3(bprx_blocks(n, 256)), dim3(256), 0, s, S->rowitem, n, S->rowuser, (int64_t)0, S->islot, S->uslot);
   if (!rc) BPRX_LAUNCH_CHECK(h, "k_af_release");
   return rc;
 }
@@ -1379,7 +1318,7 @@ extern "C" int bprx_af_dropout_mask(bprx_handle *h, int64_t step, int64_t n_rows
   if (n_rows == 0) return BPRX_OK;
   if (!out) BPRX_FAIL(h, BPRX_E_INVALID, "af_dropout_mask: null pointer");
   const AfDrop d = af_drop(h->af, step, true);
-  hipLaunchKernelGGL(k_af_mask, dim3(af_blocks(n_rows * 144, 256)), dim3(256), 0, (hipStream_t)stream, d, n_rows, out);
+  hipLaunchKernelGGL(k_af_mask, dim3(bprx_blocks(n_rows * 144, 256)), dim3(256), 0, (hipStream_t)stream, d, n_rows, out);
   BPRX_LAUNCH_CHECK(h, "k_af_mask");
   return BPRX_OK;
 }

@@ -95,12 +95,10 @@ struct FactTables {
   int64_t end[4];     // exclusive end offsets of the four tables in the flat gF order
 };
 
-// sgd or the dense ApplyAdam rule of k_dense_update (VBPR.py:142 / GradFashion.py:190):
-//   m += (g-m)(1-b1); v += (g*g-v)(1-b2); p -= lr_t*m/(sqrt(v)+eps)
+// sgd or the dense ApplyAdam rule (dense_adam_elem; VBPR.py:142 / GradFashion.py:190).
 // |p|^2 before the update leaves as one double per block in sqpart[] (k_loss_reduce sums them in block order).
 __global__ __launch_bounds__(256) void k_fact_update(FactTables T, const float *__restrict__ gF, int adam, float lr_t, float b1,
                                                      float b2, float eps, double *__restrict__ sqpart) {
-  const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
   double sq = 0.0;
   const int64_t total = T.end[3];
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
@@ -108,21 +106,10 @@ __global__ __launch_bounds__(256) void k_fact_update(FactTables T, const float *
     const int64_t o = e - (q ? T.end[q - 1] : 0);
     const float p = T.p[q][o], g = gF[e];
     sq += (double)p * (double)p;
-    float nv;
-    if (adam) {
-      const float mo = T.m[q][o], vo = T.v[q][o];
-      const float mt = mo + (g - mo) * omb1;
-      const float vt = vo + (g * g - vo) * omb2;
-      T.m[q][o] = mt; T.v[q][o] = vt;
-      nv = p - lr_t * mt / (sqrtf(vt) + eps);
-    } else {
-      nv = p - lr_t * g;
-    }
-    T.p[q][o] = nv;
+    T.p[q][o] = dense_adam_elem(p, T.m[q] + o, T.v[q] + o, g, adam, lr_t, b1, b2, eps);
   }
   __shared__ double red[4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
+  sq = wave_sum(sq);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
   __syncthreads();
   if (threadIdx.x == 0) sqpart[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
@@ -159,9 +146,7 @@ __global__ __launch_bounds__(256) void k_fact_explain(FactArgs f, const FT *__re
       for (int x = 0; x < d; ++x) w += a[x] * tu[x];
       acc += vf * w;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    res[part] = acc;
+    res[part] = wave_sum(acc);
   }
   if (lane == 0) { out[2 * p] = res[0]; out[2 * p + 1] = res[1]; }
 }

@@ -1,6 +1,7 @@
 // bprx_internal.h -- private state of libbprx.so (C ABI: include/bprx.h).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "bprx.h"
+#include "bprx_device.h"
 
 #define BPRX_DENSE_BLOCKS 2048
 
@@ -191,6 +193,13 @@ int bprx_launch_item_seg(bprx_handle *h, const int32_t *i, const int32_t *j, int
 int bprx_launch_apply(bprx_handle *h, const int32_t *u, const int32_t *i, const int32_t *j, int64_t B,
                       float lr_t, hipStream_t s);
 int bprx_launch_dense_update(bprx_handle *h, float lr_t, hipStream_t s);
+// One adam_tf23 step (sparse rule, adam_elem) of up to four whole tables from their staging gradients, which return to zero,
+// and the clearing of up to two claim-mark arrays, in ONE launch of k_adam_sweep: the sweep of every model and of
+// bprx_adam_rows.  A segment with n == 0 (a flag array with nflag == 0) costs nothing.
+struct AdamSweepSeg { float *p, *m, *v, *g; size_t n; };
+struct AdamSweepAll { AdamSweepSeg seg[4]; uint32_t *flag[2]; size_t nflag[2]; };
+int bprx_launch_adam_sweep(bprx_handle *h, const AdamSweepAll &sw, float lr_t, hipStream_t s);
+int bprx_launch_fill_i32(bprx_handle *h, int32_t *p, size_t n, int32_t v, hipStream_t s);
 int bprx_launch_adam_catchup(bprx_handle *h, const int32_t *u, const int32_t *i, const int32_t *j, int64_t B, float lr_t,
                              hipStream_t s);
 int bprx_launch_adam_sync(bprx_handle *h, int64_t t, hipStream_t s);
@@ -228,30 +237,15 @@ int bprx_af_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, float *alp
 void bprx_af_invalidate(bprx_handle *h);
 void bprx_af_free(bprx_handle *h);
 
-// Philox4x32-10 (Salmon et al. 2011): the generator of the device samplers (bprx_philox.hip) and of the dropout stream
-// (bprx_attentive.hip)
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t (&out)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+// ---- host helpers ----
+// Adam's bias-corrected step size at optimizer.iterations = h->adam_t (the caller decides when adam_t advances)
+static inline float bprx_adam_lr_t(const bprx_handle *h) {
+  const float t = (float)h->adam_t;
+  return h->cfg.lr * sqrtf(1.0f - powf(h->cfg.beta2, t)) / (1.0f - powf(h->cfg.beta1, t));
 }
-
-// adam_tf23, sparse-variable rule (TF-2.3 Keras Adam is NOT lazy: every row of the table decays and moves every step):
-//   m = m*b1 + g*(1-b1); v = v*b2 + g*g*(1-b2); var -= lr_t*m/(sqrt(v)+eps)     (g == 0 on untouched rows)
-// One element, one step.  The whole-table sweeps (bprx_sparse.hip, bprx_acf.hip) and the lazy catch-up replay share this
-// function, so that a replayed step performs bit for bit the arithmetic the sweep would have performed.
-__device__ __forceinline__ void adam_elem(float &p, float &m, float &v, float g, float b1, float b2, float lr_t, float eps) {
-#pragma clang fp contract(off)   // no fused multiply-adds: the same roundings wherever this is inlined (scalar sweep, float4 replay)
-  const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
-  const float mt = m * b1 + g * omb1;
-  const float vt = v * b2 + (g * g) * omb2;
-  m = mt; v = vt;
-  p = p - lr_t * mt / (sqrtf(vt) + eps);
+// workgroups for `work` items at `per_block` each: at least one, at most `cap`
+static inline unsigned bprx_blocks(int64_t work, int64_t per_block, int64_t cap = INT32_MAX) {
+  int64_t g = (work + per_block - 1) / per_block;
+  if (g > cap) g = cap;
+  return (unsigned)(g < 1 ? 1 : g);
 }

@@ -15,12 +15,6 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-__device__ __forceinline__ uint16_t f2bf(float x) {   // round-to-nearest-even; inputs are finite
-  uint32_t u = __float_as_uint(x);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
 // OCP e4m3fn code of x: round-to-nearest-even, saturating at +-448 (written out instead of v_cvt_pk_fp8_f32 so that
 // the CPU oracle's restatement is the same arithmetic bit for bit).  x is finite.
 __device__ __forceinline__ uint32_t f2e4m3(float x) {
@@ -181,7 +175,7 @@ __global__ __launch_bounds__(256) void k_cast_Et(const float *__restrict__ E, co
   for (int idx = threadIdx.x; idx < 64 * 16; idx += 256) {
     const int nc = idx >> 6, kr = idx & 63, kk = k0 + kr, n = n0 + nc;
     if (n < PS && kk < D) {
-      const uint16_t v = f2bf(tile[kr][nc]);
+      const uint16_t v = (uint16_t)bf16_rne(tile[kr][nc]);
       Et[et_idx(n, kk, PS)] = v;
       const int e = kk & 127;
       EtF[(((((size_t)(kk >> 7) * 4 + (e >> 5)) * (PS >> 4) + (n >> 4)) * 64) + ((e >> 3) & 3) * 16 + (n & 15)) * 8 + (e & 7)] = v;
@@ -416,8 +410,8 @@ __global__ __launch_bounds__(256) void k_cast_W(float *__restrict__ W, uint16_t 
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n4; e += (size_t)gridDim.x * 256) {
     float4 v = reinterpret_cast<float4 *>(W)[e];
     uint2 pk;
-    pk.x = (uint32_t)f2bf(v.x) | ((uint32_t)f2bf(v.y) << 16);
-    pk.y = (uint32_t)f2bf(v.z) | ((uint32_t)f2bf(v.w) << 16);
+    pk.x = bf16_rne(v.x) | (bf16_rne(v.y) << 16);
+    pk.y = bf16_rne(v.z) | (bf16_rne(v.w) << 16);
     reinterpret_cast<uint2 *>(Wb)[e] = pk;
     reinterpret_cast<float4 *>(W)[e] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
@@ -597,10 +591,10 @@ __global__ __launch_bounds__(NW * 64) void k_proj_bwd_bf16_v3(const uint16_t *__
       uint4 v = wreg[ST][x];                                                                                             \
       if constexpr (ROWS) {                                                                                              \
         const uint4 u = wreg2[ST][x];                                                                                    \
-        v.x = (uint32_t)f2bf(__uint_as_float(v.x)) | ((uint32_t)f2bf(__uint_as_float(v.y)) << 16);                       \
-        v.y = (uint32_t)f2bf(__uint_as_float(v.z)) | ((uint32_t)f2bf(__uint_as_float(v.w)) << 16);                       \
-        v.z = (uint32_t)f2bf(__uint_as_float(u.x)) | ((uint32_t)f2bf(__uint_as_float(u.y)) << 16);                       \
-        v.w = (uint32_t)f2bf(__uint_as_float(u.z)) | ((uint32_t)f2bf(__uint_as_float(u.w)) << 16);                       \
+        v.x = bf16_rne(__uint_as_float(v.x)) | (bf16_rne(__uint_as_float(v.y)) << 16);                       \
+        v.y = bf16_rne(__uint_as_float(v.z)) | (bf16_rne(__uint_as_float(v.w)) << 16);                       \
+        v.z = bf16_rne(__uint_as_float(u.x)) | (bf16_rne(__uint_as_float(u.y)) << 16);                       \
+        v.w = bf16_rne(__uint_as_float(u.z)) | (bf16_rne(__uint_as_float(u.w)) << 16);                       \
       }                                                                                                                  \
       if (part_) {                                                                                                       \
         const uint32_t mk = (t0 + tr < tend) ? 0xffffffffu : 0u;                                                         \

@@ -1,7 +1,7 @@
 // bprx_sparse.hip -- gfx950 kernels for the factor-table half of the BPR step:
 //   k_score         Model.call                         BPRMF.py:55-76 / VBPR.py:59-86
 //   k_triplet_grad  forward + analytic gradients       BPRMF.py:87-122 / VBPR.py:99-141 (GradientTape restated)
-//   k_apply_sgd / k_adam_sparse / k_dense_update       optimizer.apply_gradients  BPRMF.py:123 / VBPR.py:142
+//   k_apply_sgd / k_adam_sweep / k_dense_update        optimizer.apply_gradients  BPRMF.py:123 / VBPR.py:142
 //   k_score_block   predict_all                        BPRMF.py:78-85 / VBPR.py:88-97
 //
 // Layout: a group of G lanes (G = 8..64, a power of two, G*4 >= row length where possible) owns one
@@ -71,21 +71,7 @@ __device__ __forceinline__ float group_sum(float v) {
   return v;
 }
 
-__device__ __forceinline__ int clamp_idx(int v, int n, int32_t *errflag, int code) {
-  if ((unsigned)v >= (unsigned)n) {
-    *errflag = code;
-    return v < 0 ? 0 : n - 1;
-  }
-  return v;
-}
-
 __device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-
-__device__ __forceinline__ uint16_t f2bf_s(float x) {   // round-to-nearest-even; inputs are finite
-  uint32_t u = __float_as_uint(x);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
 
 // x_ui = Bi[i] + <Gu[u],Gi[i]> (+ <Tu[u],P[0:d]> + P[d])
 template <int G, bool VEC>
@@ -95,7 +81,7 @@ __global__ __launch_bounds__(256) void k_score(SparseArgs a, const int32_t *__re
   const int64_t b = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
   const int lane = threadIdx.x % G;
   if (b >= B) return;
-  const int u = clamp_idx(user[b], a.U, a.errflag, 1), i = clamp_idx(item[b], a.I, a.errflag, 2);
+  const int u = clamp_index(user[b], a.U, a.errflag, 1), i = clamp_index(item[b], a.I, a.errflag, 2);
   const float *gu = a.Gu + (size_t)u * a.k, *gi = a.Gi + (size_t)i * a.k;
   float s = 0.f;
   if (VEC) {
@@ -130,7 +116,6 @@ __device__ __forceinline__ void atomic_add4(float *p, float4 v) {
   atomicAdd(p + 0, v.x); atomicAdd(p + 1, v.y); atomicAdd(p + 2, v.z); atomicAdd(p + 3, v.w);
 }
 
-__device__ __forceinline__ int clamp_quiet(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }   // as clamp_idx()
 
 // Multiplicity of every user / item row in the batch (an item counts in both roles), for the atomic-staging paths (sparse
 // batches: exclusive-row fast path, touched-item list).  One thread per triplet, three int atomics.  The counters are reset
@@ -221,11 +206,11 @@ __global__ __launch_bounds__(TripletGradThreads<G>::value) void k_triplet_grad(S
   constexpr int TG_T = TripletGradThreads<G>::value;
   const bool full = ((int64_t)(blockIdx.x + 1) * TG_T) / G <= B;
   if (b >= B) return;
-  // (the three index loads are issued before the first is looked at: clamp_idx's error store would otherwise order them
+  // (the three index loads are issued before the first is looked at: clamp_index's error store would otherwise order them
   //  one behind the other -- three memory round trips instead of one at the head of every wave)
   const int u_raw = user[b], i_raw = pos[b], j_raw = neg[b];
-  const int u = clamp_idx(u_raw, a.U, a.errflag, 1);
-  const int i = clamp_idx(i_raw, a.I, a.errflag, 2), j = clamp_idx(j_raw, a.I, a.errflag, 3);
+  const int u = clamp_index(u_raw, a.U, a.errflag, 1);
+  const int i = clamp_index(i_raw, a.I, a.errflag, 2), j = clamp_index(j_raw, a.I, a.errflag, 3);
   const int k = a.k, d = a.d;
   // ... and everything that depends on the indices alone is requested together with the rows, not after them
   const float bi = a.Bi[i], bj = a.Bi[j];
@@ -489,8 +474,8 @@ __global__ __launch_bounds__(256) void k_apply_sgd(float *Gu, float *Gi, float *
   if (kind == 0) {
     const int ur = user[b], up = b > 0 ? user[b - 1] : -1;
     head = b == 0 || up != ur;
-    row = clamp_idx(ur, a.U, a.errflag, 1); flag = a.flagU + row; cntp = a.cntU + row;
-  } else { row = clamp_idx(kind == 1 ? pos[b] : neg[b], a.I, a.errflag, 2); flag = a.flagI + row; cntp = a.cntI + row; }
+    row = clamp_index(ur, a.U, a.errflag, 1); flag = a.flagU + row; cntp = a.cntU + row;
+  } else { row = clamp_index(kind == 1 ? pos[b] : neg[b], a.I, a.errflag, 2); flag = a.flagI + row; cntp = a.cntI + row; }
   if (kind == 0 ? a.fastU : a.fastI) {                 // rows with multiplicity 1 were finished by k_triplet_grad
     const int c1 = *cntp;
     if (lane == 0 && c1) *cntp = 0;                    // reset for the next step (every job of the row may do it)
@@ -580,21 +565,9 @@ __global__ __launch_bounds__(256) void k_apply_sgd_list(float *Gu, float *Gi, fl
 
 // adam_elem (bprx_internal.h): TF-2.3's sparse-variable Adam rule for one element and one step.
 
-__global__ __launch_bounds__(256) void k_adam_sparse(float *__restrict__ p, float *__restrict__ m, float *__restrict__ v,
-                                                     float *__restrict__ g, size_t n, float b1, float b2, float lr_t, float eps) {
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
-    float pp = p[e], mm = m[e], vv = v[e];
-    adam_elem(pp, mm, vv, g[e], b1, b2, lr_t, eps);
-    p[e] = pp; m[e] = mm; v[e] = vv;
-    g[e] = 0.f;
-  }
-}
-
-// The four sparse-variable sweeps of a step and the clearing of the two claim-mark arrays in ONE launch (six launches of a
-// few microseconds each before: a third of a batch-256 step on the reference CLI's default shapes).  Same element function.
-struct AdamSweepSeg { float *p, *m, *v, *g; size_t n; };
-struct AdamSweepAll { AdamSweepSeg seg[4]; uint32_t *flag[2]; size_t nflag[2]; };
-__global__ __launch_bounds__(256) void k_adam_sparse_all(AdamSweepAll a, float b1, float b2, float lr_t, float eps) {
+// The sparse-variable sweeps of a step (up to four tables) and the clearing of the two claim-mark arrays in ONE launch (six
+// launches of a few microseconds each before: a third of a batch-256 step on the reference CLI's default shapes).
+__global__ __launch_bounds__(256) void k_adam_sweep(AdamSweepAll a, float b1, float b2, float lr_t, float eps) {
   const size_t stride = (size_t)gridDim.x * blockDim.x, first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -833,10 +806,6 @@ __global__ void k_fill_i32(int32_t *p, size_t n, int32_t v) {
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) p[e] = v;
 }
 
-__global__ void k_clear_flags(uint32_t *f, size_t n) {
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) f[e] = 0u;
-}
-
 // Dense shared parameters E [D,d] and Bp [D]: grad = (sum of the SK split-K slabs of the backward projection, or the
 // all-reduced dEp) + 2*reg*param, then sgd or the dense ApplyAdam rule
 //   m += (g-m)(1-b1); v += (g*g-v)(1-b2); var -= lr_t*m/(sqrt(v)+eps)                      (VBPR.py:142).
@@ -861,7 +830,6 @@ __global__ __launch_bounds__(1024) void k_dense_update(float *__restrict__ E, fl
                                                       int bound, float *__restrict__ W, int32_t *__restrict__ cnt_reset,
                                                       uint32_t *__restrict__ absmax_out, int upd) {
   __shared__ __attribute__((aligned(16))) uint16_t tile[DU_KB][288];   // PS <= 272
-  const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
   if (ilist_n_next && blockIdx.x == 0 && threadIdx.x == 0) *ilist_n_next = 0;
   if (ilist) {
     int n = *ilist_n;
@@ -942,13 +910,13 @@ __global__ __launch_bounds__(1024) void k_dense_update(float *__restrict__ E, fl
           sq += (double)pv[c] * (double)pv[c];
           const float gg = gs[c] + 2.f * reg * pv[c];
           float nv;
-          if (adam) {
-            const float mt = mo[c] + (gg - mo[c]) * omb1;
-            const float vt = vo[c] + (gg * gg - vo[c]) * omb2;
-            *pm[c] = mt; *pv_[c] = vt;
-            nv = pv[c] - lr_t * mt / (sqrtf(vt) + eps);
+          if (adam) {                                      // (branched here, with the slots' stores: left to the helper's own
+                                                           //  test the two rules are if-converted into one select, and sgd's
+                                                           //  p - lr_t*g is no longer the one fused multiply-add it was)
+            nv = dense_adam_elem(pv[c], &mo[c], &vo[c], gg, 1, lr_t, b1, b2, eps);
+            *pm[c] = mo[c]; *pv_[c] = vo[c];
           } else {
-            nv = pv[c] - lr_t * gg;
+            nv = dense_adam_elem(pv[c], nullptr, nullptr, gg, 0, lr_t, b1, b2, eps);
           }
           *pp[c] = nv;
           nvv[c] = nv;
@@ -958,7 +926,7 @@ __global__ __launch_bounds__(1024) void k_dense_update(float *__restrict__ E, fl
       }
       if (Et) {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) tile[kr][n4 + c] = f2bf_s(nvv[c]);
+        for (int c = 0; c < 4; ++c) tile[kr][n4 + c] = (uint16_t)bf16_rne(nvv[c]);
       }
     }
     if (Et) {                                            // D % 128 == 0 with bf16 features: whole tiles only
@@ -979,8 +947,7 @@ __global__ __launch_bounds__(1024) void k_dense_update(float *__restrict__ E, fl
   }
   // (blockDim.x is a multiple of 64, at most 1024: a wave-level tree, then the waves' sums in a fixed order)
   __shared__ double red[16];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
+  sq = wave_sum(sq);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
   __syncthreads();
   if (threadIdx.x == 0 && sqpart) {
@@ -1006,17 +973,11 @@ __global__ __launch_bounds__(1024) void k_dense_update(float *__restrict__ E, fl
 __global__ __launch_bounds__(1024) void k_loss_reduce(const float *__restrict__ lossb, int64_t B,
                                                       const double *__restrict__ sqpart, int nsq, float reg,
                                                       float *__restrict__ out) {
-  __shared__ double red[1024];
   double s = 0.0;
   for (int64_t b = threadIdx.x; b < B; b += 1024) s += (double)lossb[b];
   for (int q = threadIdx.x; q < nsq; q += 1024) s += (double)reg * sqpart[q];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out = (float)red[0];
+  s = block_sum_1024(s);
+  if (threadIdx.x == 0) *out = (float)s;
 }
 
 // predict_all rows [u0,u1): out[u-u0][i] = Bi[i] + <Gu[u],Gi[i]> (+ <Tu[u],P_i[0:d]> + P_i[d]).
@@ -1338,8 +1299,8 @@ __global__ __launch_bounds__(TS_T) void k_triplet_seg(SparseArgs a, SegUser su, 
   const bool valid = b0 < B;                                // (the surplus groups of the last workgroup run along: barriers)
   const int64_t b = valid ? b0 : B - 1;
   const int u_raw = user[b], i_raw = pos[b], j_raw = neg[b];
-  const int u = clamp_idx(u_raw, a.U, a.errflag, 1);
-  const int i = clamp_idx(i_raw, a.I, a.errflag, 2), j = clamp_idx(j_raw, a.I, a.errflag, 3);
+  const int u = clamp_index(u_raw, a.U, a.errflag, 1);
+  const int i = clamp_index(i_raw, a.I, a.errflag, 2), j = clamp_index(j_raw, a.I, a.errflag, 3);
   const int k = a.k, d = a.d, kd = k + d;
   // everything that depends on the indices alone is requested together with the rows
   const float bi = a.Bi[i], bj = a.Bi[j];
@@ -1673,11 +1634,11 @@ __global__ __launch_bounds__(IS_T) void k_item_seg(SparseArgs a, float *__restri
     if (Wb) {
       if (hd) {
         uint2 pk;
-        pk.x = (uint32_t)f2bf_s(at.x) | ((uint32_t)f2bf_s(at.y) << 16);
-        pk.y = (uint32_t)f2bf_s(at.z) | ((uint32_t)f2bf_s(at.w) << 16);
+        pk.x = bf16_rne(at.x) | (bf16_rne(at.y) << 16);
+        pk.y = bf16_rne(at.z) | (bf16_rne(at.w) << 16);
         *reinterpret_cast<uint2 *>(Wb + ow + c4) = pk;
       }
-      if (lane == 0) Wb[ow + d] = f2bf_s(wl);
+      if (lane == 0) Wb[ow + d] = (uint16_t)bf16_rne(wl);
     } else if (n <= SEG_CAP) {                                        // fp32 features: W itself is the output (hot items:
       if (hd) *reinterpret_cast<float4 *>(Wf + ow + c4) = at;        // already accumulated in place)
       if (lane == 0) Wf[ow + d] = wl;
@@ -1776,6 +1737,15 @@ inline dim3 grid_for(int64_t groups, int G) {
   return dim3((unsigned)((threads + 255) / 256));
 }
 
+// The one launch of k_adam_sweep: one thread per element of the longest array, at most 4096 workgroups (shorter arrays and
+// the strides beyond ride along).  Without a handle, for bprx_adam_rows.
+hipError_t adam_sweep(const AdamSweepAll &sw, float b1, float b2, float lr_t, float eps, hipStream_t s) {
+  size_t most = sw.nflag[0] > sw.nflag[1] ? sw.nflag[0] : sw.nflag[1];
+  for (const AdamSweepSeg &sg : sw.seg) most = sg.n > most ? sg.n : most;
+  hipLaunchKernelGGL(k_adam_sweep, dim3(bprx_blocks((int64_t)most, 256, 4096)), dim3(256), 0, s, sw, b1, b2, lr_t, eps);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 // table[idx[r], :] += scale * rows[r, :]   (owner-side application of routed gradient rows; lane = element, so each
@@ -1810,11 +1780,9 @@ extern "C" int bprx_adam_rows(float *p, float *m, float *v, float *g, int64_t n,
                               void *stream) {
   if (!p || !m || !v || !g || n < 0) return BPRX_E_INVALID;
   if (n == 0) return BPRX_OK;
-  int64_t blocks = (n + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(k_adam_sparse, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, m, v, g, (size_t)n, beta1, beta2,
-                     lr_t, eps);
-  return hipGetLastError() == hipSuccess ? BPRX_OK : BPRX_E_HIP;
+  AdamSweepAll sw = {};
+  sw.seg[0] = {p, m, v, g, (size_t)n};
+  return adam_sweep(sw, beta1, beta2, lr_t, eps, (hipStream_t)stream) == hipSuccess ? BPRX_OK : BPRX_E_HIP;
 }
 
 // ---- replicated-user multi-GPU step: message packing / application (include/bprx.h) ----
@@ -2075,8 +2043,7 @@ extern "C" int bprx_apply_user_msgs(bprx_handle *h, const float *msgs, int32_t n
                      h->cfg.num_users, h->flagU, h->msg_next);
   if (h->cfg.optimizer == BPRX_OPT_ADAM_TF23) {
     // per touched user: the ranks' rows summed in rank order, then one lazy-exact Adam step (`scale` is sgd's -lr)
-    const float tt = (float)h->adam_t;
-    const float lr_t = h->cfg.lr * sqrtf(1.0f - powf(h->cfg.beta2, tt)) / (1.0f - powf(h->cfg.beta1, tt));
+    const float lr_t = bprx_adam_lr_t(h);
     const int G = pick_group(k, d, vec);
     const AdamTables T = make_adam_tables(h);
     const AdamLazy al = {h->cfg.beta1, h->cfg.beta2, h->cfg.epsilon, h->lr_hist};
@@ -2276,7 +2243,6 @@ int bprx_launch_apply(bprx_handle *h, const int32_t *u, const int32_t *i, const 
     BPRX_LAUNCH_CHECK(h, "k_apply_sgd");
     return BPRX_OK;
   }
-  const float b1 = h->cfg.beta1, b2 = h->cfg.beta2, eps = h->cfg.epsilon;
   if (h->adam_lazy) {                                    // touched rows only (claim per occurrence); everything else is replayed later
     const bool vec = vec_ok(h);
     const int G = pick_group(a.k, a.d, vec);
@@ -2284,7 +2250,7 @@ int bprx_launch_apply(bprx_handle *h, const int32_t *u, const int32_t *i, const 
     const int ek = (h->item_mode || (h->cfg.flags & BPRX_FLAG_EXPORT_ITEM_GRAD)) ? 1 : 3;   // segments: k_item_seg took the items' steps;
                                                                              // exported item gradients: their owner does
     const AdamTables T = make_adam_tables(h);
-    const AdamLazy al = {b1, b2, eps, h->lr_hist};
+    const AdamLazy al = {h->cfg.beta1, h->cfg.beta2, h->cfg.epsilon, h->lr_hist};
     if (ek > fk)
       DISPATCH_G(G, vec, k_adam_apply_lazy, grid_for((int64_t)(ek - fk) * B, G), s, T, al, h->dGu, h->dTu, h->dGi, h->dBi, h->flagU,
                  h->flagI, u, i, j, B, (int)h->adam_t, lr_t, fk, ek);
@@ -2299,12 +2265,18 @@ int bprx_launch_apply(bprx_handle *h, const int32_t *u, const int32_t *i, const 
   sw.seg[2] = {h->t.Gi, h->t.m_Gi, h->t.v_Gi, h->dGi, I * k};
   sw.seg[3] = {h->t.Tu, h->t.m_Tu, h->t.v_Tu, h->dTu, d ? U * d : (size_t)0};
   sw.flag[0] = h->flagU; sw.nflag[0] = U; sw.flag[1] = h->flagI; sw.nflag[1] = I;
-  const size_t most = U * (k > d ? k : d) > I * k ? U * (k > d ? k : d) : I * k;
-  unsigned blocks = (unsigned)((most + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_adam_sparse_all, dim3(blocks), dim3(256), 0, s, sw, b1, b2, lr_t, eps);
-  BPRX_LAUNCH_CHECK(h, "k_adam_sparse");
+  return bprx_launch_adam_sweep(h, sw, lr_t, s);
+}
+
+int bprx_launch_adam_sweep(bprx_handle *h, const AdamSweepAll &sw, float lr_t, hipStream_t s) {
+  const hipError_t e = adam_sweep(sw, h->cfg.beta1, h->cfg.beta2, lr_t, h->cfg.epsilon, s);
+  if (e != hipSuccess) BPRX_FAIL(h, BPRX_E_HIP, "launch k_adam_sweep: %s", hipGetErrorString(e));
+  return BPRX_OK;
+}
+
+int bprx_launch_fill_i32(bprx_handle *h, int32_t *p, size_t n, int32_t v, hipStream_t s) {
+  hipLaunchKernelGGL(k_fill_i32, dim3(512), dim3(256), 0, s, p, n, v);
+  BPRX_LAUNCH_CHECK(h, "k_fill_i32");
   return BPRX_OK;
 }
 
@@ -2340,9 +2312,9 @@ int bprx_launch_adam_sync(bprx_handle *h, int64_t t, hipStream_t s) {
 // every row counts as current at step t (bind, resume, outside writes): nothing to replay
 int bprx_launch_adam_reset(bprx_handle *h, int64_t t, hipStream_t s) {
   if (!h->adam_lazy) return BPRX_OK;
-  hipLaunchKernelGGL(k_fill_i32, dim3(512), dim3(256), 0, s, h->lastU, (size_t)h->cfg.num_users, (int32_t)t);
-  hipLaunchKernelGGL(k_fill_i32, dim3(512), dim3(256), 0, s, h->lastI, (size_t)h->cfg.num_items, (int32_t)t);
-  BPRX_LAUNCH_CHECK(h, "k_fill_i32");
+  int rc;
+  if ((rc = bprx_launch_fill_i32(h, h->lastU, (size_t)h->cfg.num_users, (int32_t)t, s))) return rc;
+  if ((rc = bprx_launch_fill_i32(h, h->lastI, (size_t)h->cfg.num_items, (int32_t)t, s))) return rc;
   if (s == nullptr) BPRX_HIP(h, hipStreamSynchronize(nullptr));   // control-path callers (bind, resume, tables_dirty) pass no
   h->adam_synced = t;                                             // stream: complete before work on any other stream
   return BPRX_OK;

@@ -3,7 +3,7 @@ training items per user, feature maps M = 49 x C = 512, k = 128, h = a = 64, reg
 (the reference default) and B = 65 536.  The per-item projection Z_l = f_l [W_0_i | W_0_ix] is timed with the library's per-kernel
 events (phase proj_fwd) and reported against its roofline (f32 MFMA 157 TF for fp32 features, 8 TB/s of feature bytes for bf16).
 An ACF step reports its kernels under the library's phase names: proj_fwd = k_acf_proj_*, triplet_grad = k_acf_user,
-item_seg = k_acf_triplet, dense_update = k_acf_dense, apply = k_acf_sweep / k_acf_apply_sgd, row_count = k_acf_mark.
+item_seg = k_acf_triplet, dense_update = k_acf_dense, apply = k_adam_sweep / k_acf_apply_sgd, row_count = k_acf_mark.
 --gradient full measures the full-gradient mode (bprx_acf_set_gradient); its extra kernels report as reduce_parts = k_acf_q +
 k_acf_user_bwd, loss_reduce = k_acf_item_bwd + k_acf_outer + k_acf_colsum + their k_acf_reduce, proj_bwd = k_acf_proj_bwd_* + its
 k_acf_reduce + k_acf_clear (per-kernel times: rocprofv3 --kernel-trace --stats, profiles/acf_full_kernel_stats.txt).
