@@ -19,7 +19,7 @@ MODEL = {"bprmf": 0, "vbpr": 1}
 OPTIMIZER = {"sgd": 0, "adam_tf23": 1}
 FEAT_DTYPE = {"fp32": 0, "bf16": 1, "fp8": 2}
 E_INVALID, E_STATE = -1, -2
-E_RANGE = -4
+E_RANGE, E_NOMEM = -4, -5
 PHASES = ["cast_Et", "proj_fwd", "triplet_grad", "proj_bwd", "reduce_parts", "apply", "dense_update", "loss_reduce", "item_seg", "seg_alloc", "row_count", "adam_catchup"]
 
 
@@ -102,6 +102,7 @@ def lib():
         "bprx_create": (C.c_int, [C.POINTER(Config), C.POINTER(vp)]),
         "bprx_destroy": (C.c_int, [vp]),
         "bprx_last_error": (C.c_char_p, [vp]),
+        "bprx_live_device_allocs": (i64, []),
         "bprx_bind_tables": (C.c_int, [vp, C.POINTER(Tables)]),
         "bprx_bind_factored": (C.c_int, [vp, C.POINTER(Tables), C.POINTER(Factored)]),
         "bprx_explain_pairs": (C.c_int, [vp, vp, vp, i64, vp, vp]),
@@ -185,7 +186,7 @@ def lib():
     return L
 
 
-EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error", "bprx_bind_tables", "bprx_bind_factored", "bprx_explain_pairs", "bprx_bind_acf", "bprx_acf_profiles", "bprx_acf_explain", "bprx_acf_set_gradient", "bprx_acf_get_gradient", "bprx_bind_attentive", "bprx_af_encode", "bprx_af_attention_pairs", "bprx_af_explain",
+EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error", "bprx_live_device_allocs", "bprx_bind_tables", "bprx_bind_factored", "bprx_explain_pairs", "bprx_bind_acf", "bprx_acf_profiles", "bprx_acf_explain", "bprx_acf_set_gradient", "bprx_acf_get_gradient", "bprx_bind_attentive", "bprx_af_encode", "bprx_af_attention_pairs", "bprx_af_explain",
            "bprx_af_score_block", "bprx_af_dropout_mask", "bprx_af_get_step", "bprx_af_set_step", "bprx_set_hyper", "bprx_tables_dirty",
            "bprx_set_adam_step", "bprx_get_adam_step", "bprx_adam_is_lazy", "bprx_sync_adam", "bprx_score_pairs", "bprx_step", "bprx_step_begin",
            "bprx_step_begin_sparse", "bprx_step_begin_dense", "bprx_sum_dense_parts",

@@ -38,6 +38,7 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 #define ACF_MAX_K 512
 
 struct AcfState {
+  DevPool mem;                        // owns every device buffer below
   bprx_acf a;
   int M, C, hc, ha, NP, k, fdt, Cp;   // NP = 32*ceil((h+a)/32); Cp = C rounded up to the K chunk (32)
   int64_t nw[BPRX_ACF_NW];
@@ -1504,13 +1505,7 @@ void bprx_acf_invalidate(bprx_handle *h) {
 }
 
 void bprx_acf_free(bprx_handle *h) {
-  AcfState *S = h->acf;
-  if (!S) return;
-  void *ptrs[] = {S->Z, S->GP, S->Wc, S->Wh, S->Wl, S->gp, S->Gup, S->dPi, S->uslot, S->imark, S->ilist, S->nlist,
-                  S->dZ, S->dGP, S->q, S->aux, S->UV, S->part, S->gwbuf, S->xt, S->xu};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
-  delete S;
+  delete h->acf;
   h->acf = nullptr;
 }
 
@@ -1556,32 +1551,33 @@ extern "C" int bprx_bind_acf(bprx_handle *h, const bprx_tables *t, const bprx_ac
   if (!S) {
     S = new (std::nothrow) AcfState();
     if (!S) BPRX_FAIL(h, BPRX_E_NOMEM, "bind_acf: out of host memory");
-    memset(S, 0, sizeof(*S));
     h->acf = S;
     S->M = a->feat_m; S->C = a->feat_c; S->hc = a->width_c; S->ha = a->width_i; S->NP = NP; S->k = (int)k; S->fdt = a->feat_dtype;
     S->Cp = (S->C + 31) / 32 * 32;
-    bool ok = true;
-    auto al = [&](void **p, size_t bytes) { ok = ok && hipMalloc(p, bytes) == hipSuccess && hipMemset(*p, 0, bytes) == hipSuccess; };
-    al((void **)&S->Z, I * S->M * NP * sizeof(float));
-    al((void **)&S->GP, I * S->ha * sizeof(float));
+    DevPool &A = S->mem;
+    A.zeros(&S->Z, I * S->M * NP);
+    A.zeros(&S->GP, I * S->ha);
     if (S->fdt == BPRX_F_BF16) {
-      al((void **)&S->Wh, (size_t)S->Cp * NP * sizeof(uint16_t));
-      al((void **)&S->Wl, (size_t)S->Cp * NP * sizeof(uint16_t));
+      A.zeros(&S->Wh, (size_t)S->Cp * NP);
+      A.zeros(&S->Wl, (size_t)S->Cp * NP);
     } else {
-      al((void **)&S->Wc, (size_t)S->Cp * NP * sizeof(float));
+      A.zeros(&S->Wc, (size_t)S->Cp * NP);
     }
-    al((void **)&S->gp, MB * k * sizeof(float));
-    al((void **)&S->Gup, U * k * sizeof(float));
-    al((void **)&S->dPi, I * k * sizeof(float));
-    al((void **)&S->uslot, U * sizeof(int32_t));
-    al((void **)&S->imark, I * sizeof(int32_t));
-    al((void **)&S->ilist, I * sizeof(int32_t));
-    al((void **)&S->nlist, sizeof(int32_t));
-    if (!ok) {
+    A.zeros(&S->gp, MB * k);
+    A.zeros(&S->Gup, U * k);
+    A.zeros(&S->dPi, I * k);
+    A.zeros(&S->uslot, U);
+    A.zeros(&S->imark, I);
+    A.zeros(&S->ilist, I);
+    A.zeros(&S->nlist, (size_t)1);
+    if (!A.ok()) {
       bprx_acf_free(h);
       BPRX_FAIL(h, BPRX_E_NOMEM, "bind_acf: scratch allocation failed (Z: %zu MB)", (I * a->feat_m * NP * 4) >> 20);
     }
-    if ((rc = bprx_launch_fill_i32(h, S->uslot, U, (int32_t)INT_MAX, nullptr))) return rc;
+    if ((rc = bprx_launch_fill_i32(h, S->uslot, U, (int32_t)INT_MAX, nullptr))) {
+      bprx_acf_free(h);
+      return rc;
+    }
     if (acf_user_lds(S) > 65536) {
       bprx_acf_free(h);
       BPRX_FAIL(h, BPRX_E_INVALID, "bind_acf: M = %d with embed_k = %d needs more LDS than a workgroup has", a->feat_m, (int)k);
@@ -1593,8 +1589,10 @@ extern "C" int bprx_bind_acf(bprx_handle *h, const bprx_tables *t, const bprx_ac
   const int64_t nw[BPRX_ACF_NW] = {(int64_t)k * hc, C * hc, hc, hc, 1, (int64_t)k * ha, (int64_t)k * ha, (int64_t)k * ha, C * ha, ha, ha, 1};
   for (int q = 0; q < BPRX_ACF_NW; ++q) S->nw[q] = nw[q];
   S->eval_valid = false;
-  BPRX_HIP(h, hipStreamSynchronize(nullptr));
-  return BPRX_OK;
+  const hipError_t e = hipStreamSynchronize(nullptr);
+  if (e == hipSuccess) return BPRX_OK;
+  bprx_acf_free(h);                                          // no failure leaves a model state on the handle
+  BPRX_FAIL(h, BPRX_E_HIP, "bind_acf: hipStreamSynchronize(nullptr): %s", hipGetErrorString(e));
 }
 
 extern "C" int bprx_acf_profiles(bprx_handle *h, const int32_t *users, int64_t n, const int64_t *hist_ptr, const int32_t *hist_items,
@@ -1625,20 +1623,17 @@ static int acf_full_alloc(bprx_handle *h) {
   if (pf < ACF_SPLIT * k * W) pf = ACF_SPLIT * k * W;
   S->part_floats = pf;
   const size_t gwn = k * hc + C * hc + 3 * k * ha + C * ha + 2 * W;
-  bool ok = true;
-  auto al = [&](void **p, size_t bytes) { ok = ok && hipMalloc(p, bytes) == hipSuccess && hipMemset(*p, 0, bytes) == hipSuccess; };
-  al((void **)&S->dGP, I * ha * sizeof(float));
-  al((void **)&S->q, MB * k * sizeof(float));
-  al((void **)&S->aux, MB * (k + 2) * sizeof(float));
-  al((void **)&S->UV, MB * 2 * W * sizeof(float));
-  al((void **)&S->part, pf * sizeof(float));
-  al((void **)&S->gwbuf, gwn * sizeof(float));
-  al((void **)&S->dZ, I * S->M * S->NP * sizeof(float));
-  if (!ok) {
-    void *ptrs[] = {S->dZ, S->dGP, S->q, S->aux, S->UV, S->part, S->gwbuf};
-    for (void *p : ptrs)
-      if (p) (void)hipFree(p);
-    S->dZ = S->dGP = S->q = S->aux = S->UV = S->part = S->gwbuf = nullptr;
+  DevPool &A = S->mem;
+  const size_t mk = A.mark();
+  A.zeros(&S->dGP, I * ha);
+  A.zeros(&S->q, MB * k);
+  A.zeros(&S->aux, MB * (k + 2));
+  A.zeros(&S->UV, MB * 2 * W);
+  A.zeros(&S->part, pf);
+  A.zeros(&S->gwbuf, gwn);
+  A.zeros(&S->dZ, I * S->M * S->NP);
+  if (!A.ok()) {
+    (void)A.rollback(mk);
     BPRX_FAIL(h, BPRX_E_NOMEM, "acf_set_gradient: workspace allocation failed (dZ: %zu MB)", (I * S->M * S->NP * 4) >> 20);
   }
   float *g = S->gwbuf;
@@ -1681,24 +1676,15 @@ extern "C" int bprx_acf_get_gradient(bprx_handle *h) {
 // Workspace of bprx_acf_explain, allocated at its first call and regrown when a call's histories are longer
 static int acf_explain_alloc(bprx_handle *h, int64_t nnz) {
   AcfState *S = h->acf;
-  if (!S->xu) {
-    const size_t bytes = (2 + (size_t)h->cfg.num_users * (2 + S->hc)) * sizeof(float);
-    if (hipMalloc((void **)&S->xu, bytes) != hipSuccess || hipMemset(S->xu, 0, bytes) != hipSuccess) {
-      if (S->xu) (void)hipFree(S->xu);
-      S->xu = nullptr;
-      BPRX_FAIL(h, BPRX_E_NOMEM, "acf_explain: workspace allocation failed (%zu MB)", bytes >> 20);
-    }
-  }
+  const size_t nu = 2 + (size_t)h->cfg.num_users * (2 + S->hc);
+  if (!S->xu && S->mem.regrow(&S->xu, nu, true) != hipSuccess)
+    BPRX_FAIL(h, BPRX_E_NOMEM, "acf_explain: workspace allocation failed (%zu MB)", (nu * 4) >> 20);
   if (nnz > S->xt_cap || !S->xt) {
     BPRX_HIP(h, hipDeviceSynchronize());
-    if (S->xt) (void)hipFree(S->xt);
-    S->xt = nullptr;
     S->xt_cap = 0;
     const int64_t cap = nnz < 1 ? 1 : nnz;
-    if (hipMalloc((void **)&S->xt, (size_t)cap * sizeof(float)) != hipSuccess) {
-      S->xt = nullptr;
+    if (S->mem.regrow(&S->xt, (size_t)cap) != hipSuccess)
       BPRX_FAIL(h, BPRX_E_NOMEM, "acf_explain: workspace allocation failed (%zu MB)", ((size_t)cap * 4) >> 20);
-    }
     S->xt_cap = cap;
     BPRX_HIP(h, hipMemcpy(S->xu, &cap, sizeof(int64_t), hipMemcpyHostToDevice));   // where the attention pass reads it
   }

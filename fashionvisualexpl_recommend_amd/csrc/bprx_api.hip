@@ -5,7 +5,6 @@
 #include <new>
 
 #include "bprx_internal.h"
-#include <utility>
 
 static char g_create_err[512] = "";
 
@@ -15,26 +14,12 @@ extern "C" int bprx_abi_version(void) { return BPRX_ABI_VERSION; }
 
 extern "C" const char *bprx_last_error(const bprx_handle *h) { return h ? h->err : g_create_err; }
 
-template <typename T>
-static hipError_t dalloc_zero(T **p, size_t n) {
-  *p = nullptr;
-  if (n == 0) return hipSuccess;
-  hipError_t e = hipMalloc((void **)p, n * sizeof(T));
-  if (e != hipSuccess) return e;
-  return hipMemset(*p, 0, n * sizeof(T));
-}
+extern "C" int64_t bprx_live_device_allocs(void) { return bprx_live_allocs.load(); }
 
 // The library's environment switches (README "Environment switches"), all read here, once, by bprx_create.
 static int env_int(const char *name, int fallback) {
   const char *e = getenv(name);
   return e ? atoi(e) : fallback;
-}
-
-static void free_scratch(bprx_handle *h) {
-  void *ptrs[] = {h->dGu, h->dGi, h->dBi, h->dTu, h->flagU, h->flagI, h->lossb, h->loss_acc, h->errflag,
-                  h->P,   h->W,   h->Wb, h->Ppair, h->Et, h->EtF, h->EtS, h->dEp, h->part, h->qs, h->Ft, h->seg_rank, h->seg_cnt, h->seg_ptr, h->seg_cursor, h->seg_lead, h->seg_ent, h->hot_done, h->uslot_of, h->ulist, h->uold, h->own8, h->loc8, h->cntU, h->cntI, h->ilist, h->ilist_n, h->lastU, h->lastI, h->lr_hist, h->slist, h->slist_n, h->msg_cursor, h->msg_next, h->gF};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
 }
 
 extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
@@ -95,7 +80,6 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
 
   bprx_handle *h = new (std::nothrow) bprx_handle();
   if (!h) CFAIL(BPRX_E_NOMEM, "out of host memory");
-  memset(h, 0, sizeof(*h));
 // the one failure exit once the handle exists: bprx_destroy frees whatever has been made so far
 #define HFAIL(code, ...)         \
   do {                           \
@@ -108,36 +92,35 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
   if (!vb) { h->cfg.embed_d = 0; h->cfg.feat_dim = 0; }
   const size_t U = cfg->num_users, I = cfg->num_items, k = cfg->embed_k, d = h->cfg.embed_d, D = h->cfg.feat_dim;
   const size_t MB = cfg->max_batch;
-  bool ok = true;
-#define A(call) ok = ok && ((e = (call)) == hipSuccess)
-  A(dalloc_zero(&h->dGu, U * k));
-  A(dalloc_zero(&h->dGi, I * k));
-  A(dalloc_zero(&h->dBi, I));
-  A(dalloc_zero(&h->flagU, U));
-  A(dalloc_zero(&h->flagI, I));
-  A(dalloc_zero(&h->lossb, MB));
-  A(dalloc_zero(&h->loss_acc, (size_t)BPRX_DENSE_BLOCKS));
-  A(dalloc_zero(&h->errflag, (size_t)1));
-  if (cfg->flags & BPRX_FLAG_EXPORT_USER_GRAD) A(dalloc_zero(&h->msg_cursor, (size_t)2));
-  A(dalloc_zero(&h->cntU, U));
-  A(dalloc_zero(&h->cntI, I));
+  hipDeviceProp_t prop;
+  h->num_cu = hipGetDeviceProperties(&prop, cfg->device) == hipSuccess ? prop.multiProcessorCount : 256;
+  // The pool stops at the first failure and is tested once, after the last allocation: until then the calls after a failure do
+  // nothing, and nothing in between may use a buffer (sizes and policies only).
+  DevPool &A = h->mem;
+  A.zeros(&h->dGu, U * k);
+  A.zeros(&h->dGi, I * k);
+  A.zeros(&h->dBi, I);
+  A.zeros(&h->flagU, U);
+  A.zeros(&h->flagI, I);
+  A.zeros(&h->lossb, MB);
+  A.zeros(&h->loss_acc, (size_t)BPRX_DENSE_BLOCKS);
+  A.zeros(&h->errflag, (size_t)1);
+  if (cfg->flags & BPRX_FLAG_EXPORT_USER_GRAD) A.zeros(&h->msg_cursor, (size_t)2);
+  A.zeros(&h->cntU, U);
+  A.zeros(&h->cntI, I);
   if (vb) {
     h->PS = 16 * (int)((d + 1 + 15) / 16);
     const size_t PS = h->PS;
     // split-K of the backward projection: ONE 8-wave workgroup per CU over the D/256 column ranges (C2: 16 ranges x 16
     // item splits on 256 CUs).  More splits only add slab traffic (SK*D*PS*4 B written, then read by the dense update):
     // measured on C2 SK 16 / 32 with 3 / 2 tiles in flight: backward 73.8 / 77.0 us, dense update 9.7 / 12.1 us.
-    {
-      hipDeviceProp_t prop;
-      const int ncu = hipGetDeviceProperties(&prop, cfg->device) == hipSuccess ? prop.multiProcessorCount : 256;
-      const int mr = (int)((D + 255) / 256);
-      h->SK = (ncu + mr - 1) / mr;
-      // fp8 tiles are half the bytes, wide projections (more than 9 column tiles) have no registers for a third tile in
-      // flight: both keep two workgroups per CU with two tiles in flight (measured: c2fp8 53 vs 58 us, c5 124 vs 362 us)
-      // (wide projections, re-measured with the 8-wave kernel at two tiles in flight -- c5: SK 16 / 24 / 32 = 120 / 154 / 127 us
-      //  backward and 24 / 30 / 38 us dense update: one workgroup per CU there as well)
-      if (cfg->feat_dtype == BPRX_F_FP8 && PS / 16 <= 9) h->SK *= 2;
-    }
+    const int mr = (int)((D + 255) / 256);
+    h->SK = (h->num_cu + mr - 1) / mr;
+    // fp8 tiles are half the bytes, wide projections (more than 9 column tiles) have no registers for a third tile in
+    // flight: both keep two workgroups per CU with two tiles in flight (measured: c2fp8 53 vs 58 us, c5 124 vs 362 us)
+    // (wide projections, re-measured with the 8-wave kernel at two tiles in flight -- c5: SK 16 / 24 / 32 = 120 / 154 / 127 us
+    //  backward and 24 / 30 / 38 us dense update: one workgroup per CU there as well)
+    if (cfg->feat_dtype == BPRX_F_FP8 && PS / 16 <= 9) h->SK *= 2;
     if (h->SK > 64) h->SK = 64;
     if (h->SK < 1) h->SK = 1;
     // BPRX_FWD_VARIANT=0: the plain forward kernel (the reference the streaming kernels are tested against); anything else:
@@ -149,22 +132,20 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
     // the masked backward pass is slower where the MFMAs pace it, c2fp8 49.3 -> 53.0 us, c5 944 -> 1 139 us, and a table that
     // sits in the Infinity Cache has no HBM bytes to save); 2 wherever a masked form exists
     h->proj_mask = std::min(std::max(env_int("BPRX_PROJ_MASK", 1), 0), 2);
-    A(dalloc_zero(&h->dTu, U * d));
-    A(dalloc_zero(&h->P, I * PS));
-    A(dalloc_zero(&h->W, I * PS));
-    A(dalloc_zero((uint16_t **)&h->Wb, I * PS));
-    A(dalloc_zero(&h->Ppair, MB * PS));
-    A(dalloc_zero((uint16_t **)&h->Et, PS * D));
-    A(dalloc_zero((uint16_t **)&h->EtF, PS * D));
-    if (cfg->feat_dtype == BPRX_F_FP8 && PS / 16 >= 10) A(dalloc_zero((uint8_t **)&h->EtS, PS * D));
-    A(dalloc_zero(&h->dEp, D * d + D));
-    A(dalloc_zero(&h->part, (size_t)h->SK * D * PS));
-    A(dalloc_zero(&h->qs, (size_t)4));
+    A.zeros(&h->dTu, U * d);
+    A.zeros(&h->P, I * PS);
+    A.zeros(&h->W, I * PS);
+    A.zeros((uint16_t **)&h->Wb, I * PS);
+    A.zeros(&h->Ppair, MB * PS);
+    A.zeros((uint16_t **)&h->Et, PS * D);
+    A.zeros((uint16_t **)&h->EtF, PS * D);
+    if (cfg->feat_dtype == BPRX_F_FP8 && PS / 16 >= 10) A.zeros((uint8_t **)&h->EtS, PS * D);
+    A.zeros(&h->dEp, D * d + D);
+    A.zeros(&h->part, (size_t)h->SK * D * PS);
+    A.zeros(&h->qs, (size_t)4);
     if (cfg->feat_dtype != BPRX_F_FP32)   // tiled copy of F, item count padded to whole 32-item blocks
-      A(dalloc_zero((uint8_t **)&h->Ft, (size_t)((I + 31) / 32 * 32) * D * (cfg->feat_dtype == BPRX_F_FP8 ? 1 : 2)));
+      A.zeros((uint8_t **)&h->Ft, (size_t)((I + 31) / 32 * 32) * D * (cfg->feat_dtype == BPRX_F_FP8 ? 1 : 2));
   }
-#undef A
-  if (!ok) HFAIL(BPRX_E_NOMEM, "scratch allocation failed: %s", hipGetErrorString(e));
   {
     // Item-side gradients through per-item occurrence segments (k_item_seg) instead of global float atomics: the
     // default whenever the row widths fit the 16-B-per-lane layout and the item rows are not staging rows of a sharded
@@ -182,15 +163,15 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
       h->idx8_shift = 0;
       for (int sh = 8; sh <= 13 && !h->idx8_shift; ++sh)
         if ((((int64_t)I - 1) >> sh) <= 255) h->idx8_shift = sh;
-      bool ok2 = dalloc_zero(&h->seg_rank, (size_t)2 * MB) == hipSuccess && dalloc_zero(&h->seg_cnt, I) == hipSuccess &&
-                 dalloc_zero(&h->seg_ptr, I) == hipSuccess && dalloc_zero(&h->seg_cursor, (size_t)6) == hipSuccess &&
-                 dalloc_zero((int4 **)&h->seg_lead, (size_t)h->seg_lead_cap) == hipSuccess &&
-                 dalloc_zero(&h->hot_done, I) == hipSuccess && dalloc_zero((int2 **)&h->seg_ent, (size_t)h->seg_ent_cap) == hipSuccess &&
-                 dalloc_zero(&h->uslot_of, U) == hipSuccess && dalloc_zero(&h->ulist, MB) == hipSuccess &&
-                 dalloc_zero(&h->uold, MB * (k + d)) == hipSuccess &&
-                 (!h->idx8_shift ||
-                  (dalloc_zero(&h->own8, (size_t)2 * MB) == hipSuccess && dalloc_zero(&h->loc8, (size_t)2 * MB * (h->idx8_shift > 8 ? 2 : 1)) == hipSuccess));
-      if (!ok2) HFAIL(BPRX_E_NOMEM, "segment scratch allocation failed");
+      A.zeros(&h->seg_rank, (size_t)2 * MB);
+      A.zeros(&h->seg_cnt, I); A.zeros(&h->seg_ptr, I);
+      A.zeros(&h->seg_cursor, (size_t)6);
+      A.zeros((int4 **)&h->seg_lead, (size_t)h->seg_lead_cap);
+      A.zeros(&h->hot_done, I);
+      A.zeros((int2 **)&h->seg_ent, (size_t)h->seg_ent_cap);
+      A.zeros(&h->uslot_of, U); A.zeros(&h->ulist, MB);
+      A.zeros(&h->uold, MB * (k + d));
+      if (h->idx8_shift) { A.zeros(&h->own8, (size_t)2 * MB); A.zeros(&h->loc8, (size_t)2 * MB * (h->idx8_shift > 8 ? 2 : 1)); }
     }
   }
   // Touched-item list (sparse batches): when the batch touches few of the items, both projections run over the batch's
@@ -201,21 +182,19 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
   h->list_policy = vb ? std::min(std::max(env_int("BPRX_LIST_MODE", 1), 0), 2) : 0;
   if (h->list_policy) {
     const size_t cap = 2 * MB < I ? 2 * MB : I;
-    if (dalloc_zero(&h->ilist, cap) != hipSuccess || dalloc_zero(&h->ilist_n, (size_t)2) != hipSuccess)
-      HFAIL(BPRX_E_NOMEM, "item list allocation failed");
+    A.zeros(&h->ilist, cap); A.zeros(&h->ilist_n, (size_t)2);
   }
   h->SK_step = h->SK;
   if (h->adam_lazy) {
-    if (dalloc_zero(&h->lastU, U) != hipSuccess || dalloc_zero(&h->lastI, I) != hipSuccess ||
-        dalloc_zero(&h->lr_hist, (size_t)bprx_adam_hist()) != hipSuccess)
-      HFAIL(BPRX_E_NOMEM, "adam bookkeeping allocation failed");
+    A.zeros(&h->lastU, U); A.zeros(&h->lastI, I);
+    A.zeros(&h->lr_hist, (size_t)bprx_adam_hist());
   }
   // exclusive-row fast path: sgd only (adam sweeps every row anyway); not with exported user gradients
   h->fast_rows = (cfg->optimizer == BPRX_OPT_SGD && !(cfg->flags & BPRX_FLAG_EXPORT_USER_GRAD)) ? 1 : 0;   // per side: make_args
   if (h->fast_rows && !exported) {
-    if (dalloc_zero(&h->slist, (size_t)3 * MB) != hipSuccess || dalloc_zero(&h->slist_n, (size_t)2) != hipSuccess)
-      HFAIL(BPRX_E_NOMEM, "shared-row list allocation failed");
+    A.zeros(&h->slist, (size_t)3 * MB); A.zeros(&h->slist_n, (size_t)2);
   }
+  if ((e = A.err) != hipSuccess) HFAIL(BPRX_E_NOMEM, "scratch allocation failed: %s", hipGetErrorString(e));
   // Side stream: lazy Adam's catch-up (ALU-bound: correctly rounded sqrt / divide per replayed element and step) runs beside the
   // HBM-bound forward projection of a streaming step: adam_tf23 0.330 -> 0.317 ms/step on C2.  BPRX_SIDE_STREAM=0: on the
   // step's own stream.  (Measured and removed, DESIGN §5.1: the sparse optimizer pass beside the backward projection, and the
@@ -225,12 +204,6 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
        hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
        hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess))
     HFAIL(BPRX_E_HIP, "side stream / event creation failed");
-  {
-    hipDeviceProp_t prop;
-    h->num_cu = hipGetDeviceProperties(&prop, cfg->device) == hipSuccess ? prop.multiProcessorCount : 256;
-  }
-  h->prof_pending = new std::vector<bprx_handle::ProfRec>();
-  h->prof_free = new std::vector<hipEvent_t>();
   *out = h;
   return BPRX_OK;
 #undef HFAIL
@@ -241,14 +214,14 @@ extern "C" int bprx_destroy(bprx_handle *h) {
   if (!h) return BPRX_OK;
   (void)hipSetDevice(h->cfg.device);
   if (h->side) (void)hipStreamSynchronize(h->side);
-  free_scratch(h);
+  (void)h->mem.rollback(0);
   bprx_acf_free(h);
   bprx_af_free(h);
   if (h->side) (void)hipStreamDestroy(h->side);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-  if (h->prof_pending) { for (auto &r : *h->prof_pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); } delete h->prof_pending; }
-  if (h->prof_free) { for (auto e : *h->prof_free) (void)hipEventDestroy(e); delete h->prof_free; }
+  for (auto &r : h->prof_pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
+  for (auto e : h->prof_free) (void)hipEventDestroy(e);
   delete h;
   return BPRX_OK;
 }
@@ -261,16 +234,16 @@ extern "C" int bprx_profile_enable(bprx_handle *h, int on) {
 
 extern "C" int bprx_profile_read(bprx_handle *h, double *ms, int64_t *launches) {
   if (!h || !ms || !launches) return BPRX_E_INVALID;
-  for (auto &r : *h->prof_pending) {
+  for (auto &r : h->prof_pending) {
     BPRX_HIP(h, hipEventSynchronize(r.b));
     float t = 0.f;
     BPRX_HIP(h, hipEventElapsedTime(&t, r.a, r.b));
     ms[r.phase] += (double)t;
     launches[r.phase] += 1;
-    h->prof_free->push_back(r.a);
-    h->prof_free->push_back(r.b);
+    h->prof_free.push_back(r.a);
+    h->prof_free.push_back(r.b);
   }
-  h->prof_pending->clear();
+  h->prof_pending.clear();
   return BPRX_OK;
 }
 
@@ -328,7 +301,8 @@ extern "C" int bprx_bind_factored(bprx_handle *h, const bprx_tables *t, const bp
   if (!h->gF) {
     const size_t n = (size_t)f->feat_dim_a * f->embed_a + (size_t)f->feat_dim_b * f->embed_b +
                      (size_t)(f->embed_a + f->embed_b) * (c.embed_d + 1);
-    BPRX_HIP(h, hipMalloc((void **)&h->gF, n * sizeof(float)));
+    const hipError_t e = h->mem.regrow(&h->gF, n);
+    if (e != hipSuccess) BPRX_FAIL(h, BPRX_E_HIP, "bind_factored: factor gradient (%zu floats): %s", n, hipGetErrorString(e));
   } else if (f->feat_dim_a != h->fx.feat_dim_a || f->feat_dim_b != h->fx.feat_dim_b || f->embed_a != h->fx.embed_a ||
              f->embed_b != h->fx.embed_b) {
     BPRX_FAIL(h, BPRX_E_INVALID, "bind_factored: the factor shapes of a handle cannot change");

@@ -39,6 +39,7 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 #define AF_MAX_K 512
 
 struct AfState {
+  DevPool mem;                    // owns every device buffer below
   bprx_attentive a;
   int k, h, Dc, Dk;
   int64_t R;                      // sample rows of scratch: 2 * max_batch
@@ -1151,15 +1152,7 @@ void bprx_af_invalidate(bprx_handle *h) {
 }
 
 void bprx_af_free(bprx_handle *h) {
-  AfState *S = h->af;
-  if (!S) return;
-  void *ptrs[] = {S->islot, S->uslot, S->rowitem, S->rowuser, S->pool, S->PD, S->Hc, S->Hk, S->C, S->dC, S->A6, S->Hid, S->dHid, S->da,
-                  S->dGuS, S->dGiS, S->dH, S->dPD, S->gsum, S->cpart, S->cred, S->Call, S->E, S->erank};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
-  for (int q = 0; q < BPRX_AF_NW; ++q)
-    if (S->g[q] && q != BPRX_AF_EDG_CB) (void)hipFree(S->g[q]);                // g[EDG_CB] lives inside g[EDG_CW]
-  delete S;
+  delete h->af;
   h->af = nullptr;
 }
 
@@ -1201,51 +1194,54 @@ extern "C" int bprx_bind_attentive(bprx_handle *h, const bprx_tables *t, const b
   const size_t U = c.num_users, I = c.num_items, k = c.embed_k, R = 2 * (size_t)c.max_batch, hh = a->width;
   S = new (std::nothrow) AfState();
   if (!S) BPRX_FAIL(h, BPRX_E_NOMEM, "bind_attentive: out of host memory");
-  memset(S, 0, sizeof(*S));
   h->af = S;
   S->a = *a; S->k = (int)k; S->h = (int)hh; S->Dc = a->dim_color; S->Dk = a->dim_class; S->R = (int64_t)R; S->step = keep_step;
   const int64_t Dc = S->Dc, Dk = S->Dk;
   const int64_t nw[BPRX_AF_NW] = {Dc * AF_HID, AF_HID, AF_HID * (int64_t)k, 25 * AF_CH, AF_CH, AF_CH * (int64_t)k, Dk * AF_HID, AF_HID,
                                   AF_HID * (int64_t)k, (int64_t)(k * hh), (int64_t)hh, (int64_t)hh, 1};
-  bool ok = true;
-  auto al = [&](void **p, size_t bytes) { ok = ok && hipMalloc(p, bytes) == hipSuccess && hipMemset(*p, 0, bytes) == hipSuccess; };
+  DevPool &A = S->mem;
   for (int q = 0; q < BPRX_AF_NW; ++q) {
     S->nw[q] = nw[q];
-    if (q == BPRX_AF_EDG_CW) al((void **)&S->g[q], AF_CPART * sizeof(float));
-    else if (q == BPRX_AF_EDG_CB) S->g[q] = S->g[BPRX_AF_EDG_CW] ? S->g[BPRX_AF_EDG_CW] + 25 * AF_CH : nullptr;
-    else al((void **)&S->g[q], nw[q] * sizeof(float));
+    if (q == BPRX_AF_EDG_CW) A.zeros(&S->g[q], (size_t)AF_CPART);
+    else if (q == BPRX_AF_EDG_CB) S->g[q] = S->g[BPRX_AF_EDG_CW] ? S->g[BPRX_AF_EDG_CW] + 25 * AF_CH : nullptr;   // an alias, not owned
+    else A.zeros(&S->g[q], (size_t)nw[q]);
   }
-  al((void **)&S->islot, I * sizeof(int32_t));
-  al((void **)&S->uslot, U * sizeof(int32_t));
-  al((void **)&S->rowitem, R * sizeof(int32_t));
-  al((void **)&S->rowuser, R * sizeof(int32_t));
-  al((void **)&S->pool, R * AF_CH * sizeof(float));
-  al((void **)&S->PD, R * AF_CH * sizeof(float));
-  al((void **)&S->Hc, R * AF_HID * sizeof(float));
-  al((void **)&S->Hk, R * AF_HID * sizeof(float));
-  al((void **)&S->C, 3 * R * k * sizeof(float));
-  al((void **)&S->dC, 3 * R * k * sizeof(float));
-  al((void **)&S->A6, 3 * R * k * sizeof(float));
-  al((void **)&S->Hid, 3 * R * hh * sizeof(float));
-  al((void **)&S->dHid, 3 * R * hh * sizeof(float));
-  al((void **)&S->da, 3 * R * sizeof(float));
-  al((void **)&S->dGuS, R / 2 * k * sizeof(float));
-  al((void **)&S->dGiS, R * k * sizeof(float));
-  al((void **)&S->dH, R * AF_HID * sizeof(float));
-  al((void **)&S->dPD, R * AF_CH * sizeof(float));
-  al((void **)&S->gsum, R * AF_CH * sizeof(float));
-  al((void **)&S->cpart, R * AF_CPART * sizeof(float));
-  al((void **)&S->cred, 64 * (size_t)AF_CPART * sizeof(float));
-  al((void **)&S->Call, 3 * I * k * sizeof(float));
-  if (!ok) {
+  A.zeros(&S->islot, I);
+  A.zeros(&S->uslot, U);
+  A.zeros(&S->rowitem, R);
+  A.zeros(&S->rowuser, R);
+  A.zeros(&S->pool, R * AF_CH);
+  A.zeros(&S->PD, R * AF_CH);
+  A.zeros(&S->Hc, R * AF_HID);
+  A.zeros(&S->Hk, R * AF_HID);
+  A.zeros(&S->C, 3 * R * k);
+  A.zeros(&S->dC, 3 * R * k);
+  A.zeros(&S->A6, 3 * R * k);
+  A.zeros(&S->Hid, 3 * R * hh);
+  A.zeros(&S->dHid, 3 * R * hh);
+  A.zeros(&S->da, 3 * R);
+  A.zeros(&S->dGuS, R / 2 * k);
+  A.zeros(&S->dGiS, R * k);
+  A.zeros(&S->dH, R * AF_HID);
+  A.zeros(&S->dPD, R * AF_CH);
+  A.zeros(&S->gsum, R * AF_CH);
+  A.zeros(&S->cpart, R * AF_CPART);
+  A.zeros(&S->cred, 64 * (size_t)AF_CPART);
+  A.zeros(&S->Call, 3 * I * k);
+  if (!A.ok()) {
     bprx_af_free(h);
     BPRX_FAIL(h, BPRX_E_NOMEM, "bind_attentive: scratch allocation failed");
   }
-  if ((rc = bprx_launch_fill_i32(h, S->islot, I, (int32_t)INT_MAX, nullptr))) return rc;
-  if ((rc = bprx_launch_fill_i32(h, S->uslot, U, (int32_t)INT_MAX, nullptr))) return rc;
   S->eval_valid = false;
-  BPRX_HIP(h, hipStreamSynchronize(nullptr));
-  return BPRX_OK;
+  if ((rc = bprx_launch_fill_i32(h, S->islot, I, (int32_t)INT_MAX, nullptr)) ||
+      (rc = bprx_launch_fill_i32(h, S->uslot, U, (int32_t)INT_MAX, nullptr))) {
+    bprx_af_free(h);
+    return rc;
+  }
+  const hipError_t e = hipStreamSynchronize(nullptr);
+  if (e == hipSuccess) return BPRX_OK;
+  bprx_af_free(h);                                          // no failure leaves a model state on the handle
+  BPRX_FAIL(h, BPRX_E_HIP, "bind_attentive: hipStreamSynchronize(nullptr): %s", hipGetErrorString(e));
 }
 
 #define AF_CHECK(name)                                                                                              \
@@ -1282,19 +1278,13 @@ extern "C" int bprx_af_explain(bprx_handle *h, const int32_t *user, const int32_
   const size_t per = (size_t)grid * grid * AF_CH * sizeof(float);
   int64_t ecap = (int64_t)(((size_t)1 << 30) / per);
   if (ecap > n) ecap = n;
-  if (!S->erank && hipMalloc((void **)&S->erank, (size_t)S->R * sizeof(int32_t)) != hipSuccess) {
-    S->erank = nullptr;
+  if (!S->erank && S->mem.regrow(&S->erank, (size_t)S->R) != hipSuccess)
     BPRX_FAIL(h, BPRX_E_NOMEM, "af_explain: workspace allocation failed");
-  }
   if ((size_t)ecap * per > S->E_bytes) {
     BPRX_HIP(h, hipDeviceSynchronize());                      // earlier calls may still read the old one
-    if (S->E) (void)hipFree(S->E);
-    S->E = nullptr;
     S->E_bytes = 0;
-    if (hipMalloc((void **)&S->E, (size_t)ecap * per) != hipSuccess) {
-      S->E = nullptr;
+    if (S->mem.regrow(&S->E, (size_t)ecap * per / sizeof(float)) != hipSuccess)
       BPRX_FAIL(h, BPRX_E_NOMEM, "af_explain: workspace allocation failed (%zu MB)", ((size_t)ecap * per) >> 20);
-    }
     S->E_bytes = (size_t)ecap * per;
   }
   hipStream_t s = (hipStream_t)stream;

@@ -6,12 +6,63 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <atomic>
+#include <utility>
 #include <vector>
 
 #include "bprx.h"
 #include "bprx_device.h"
 
 #define BPRX_DENSE_BLOCKS 2048
+
+// Every device buffer of the library belongs to a DevPool, a member of the struct that holds the buffer's pointer (the handle,
+// AcfState, AfState).  The pool records each allocation with the address of that pointer and frees them all when it is cleared or
+// destroyed: there is no list of names to keep in step.  bprx_live_allocs (bprx_live_device_allocs) counts them process-wide.
+inline std::atomic<int64_t> bprx_live_allocs{0};
+
+struct DevPool {
+  struct Rec { void **slot; void *p; };
+  std::vector<Rec> recs;
+  hipError_t err = hipSuccess;    // the first failure: sticky, zeros() does nothing more until a rollback takes it
+
+  DevPool() = default;
+  DevPool(const DevPool &) = delete;
+  DevPool &operator=(const DevPool &) = delete;
+  ~DevPool() { (void)rollback(0); }
+
+  // *slot = n zero-filled elements (n == 0: nullptr, a success).  Allocate everything, then test ok() once.
+  template <typename T> void zeros(T **slot, size_t n) { get((void **)slot, n * sizeof(T), true); }
+  bool ok() const { return err == hipSuccess; }
+  size_t mark() const { return recs.size(); }
+  // Frees what was allocated after `mark`, nulls the owning pointers, and returns (and forgets) the failure, if any.  A mark
+  // holds within one function only: regrow() takes records out of the middle.
+  hipError_t rollback(size_t mark) {
+    for (; recs.size() > mark; recs.pop_back()) drop(recs.back());
+    return std::exchange(err, hipSuccess);
+  }
+  // One buffer on its own: what *slot owns (if anything) goes, n new elements (not zeroed unless asked) take its place.  A failure
+  // is returned, not kept, and leaves *slot null.  The caller has made sure that no enqueued work still reads the old buffer.
+  // Also the first allocation of a buffer made on demand (gF, xu, erank), whose failure must not stop later calls.
+  template <typename T> hipError_t regrow(T **slot, size_t n, bool zero = false) {
+    for (size_t i = 0; i < recs.size(); ++i)
+      if (recs[i].slot == (void **)slot) { drop(recs[i]); recs.erase(recs.begin() + i); break; }
+    const size_t mk = mark();
+    get((void **)slot, n * sizeof(T), zero);
+    return ok() ? hipSuccess : rollback(mk);
+  }
+
+ private:
+  void get(void **slot, size_t bytes, bool zero) {
+    if (!ok() || bytes == 0) return;
+    void *p = nullptr;
+    if ((err = hipMalloc(&p, bytes)) != hipSuccess) { (void)hipGetLastError(); return; }   // (or the next launch check reports it)
+    recs.push_back({slot, p});
+    *slot = p;
+    ++bprx_live_allocs;
+    if (zero) err = hipMemset(p, 0, bytes);
+  }
+  void drop(const Rec &r) { (void)hipFree(r.p); *r.slot = nullptr; --bprx_live_allocs; }
+};
 
 struct AcfState;   // bprx_acf.hip
 struct AfState;    // bprx_attentive.hip
@@ -28,7 +79,8 @@ struct bprx_handle {
   int64_t adam_synced;     // every row is current at least up to this step
   char err[512];
 
-  // ---- scratch owned by the handle (device) ----
+  // ---- scratch owned by the handle (device): every pointer below that the library allocates belongs to `mem` ----
+  DevPool mem;
   float *dGu, *dGi, *dBi, *dTu;   // dense fp32 gradient staging, same shapes as the tables; all-zero between steps
   uint32_t *flagU, *flagI;        // "row touched this step" marks (sgd claim)
   float *lossb;                   // [max_batch] per-triplet loss (data + per-occurrence regularisation)
@@ -143,8 +195,8 @@ struct bprx_handle {
   // per-kernel HIP-event timing (bprx_profile_*)
   bool prof;
   struct ProfRec { int phase; hipEvent_t a, b; };
-  std::vector<ProfRec> *prof_pending;
-  std::vector<hipEvent_t> *prof_free;
+  std::vector<ProfRec> prof_pending;
+  std::vector<hipEvent_t> prof_free;
 };
 
 // RAII: records an event pair around one kernel launch when profiling is on.
@@ -152,7 +204,7 @@ struct BprxProfScope {
   bprx_handle *h; hipStream_t s; hipEvent_t a, b; int phase; bool on;
   BprxProfScope(bprx_handle *h_, int phase_, hipStream_t s_) : h(h_), s(s_), phase(phase_), on(h_->prof) {
     if (!on) return;
-    auto get = [&]() { hipEvent_t e; if (!h->prof_free->empty()) { e = h->prof_free->back(); h->prof_free->pop_back(); }
+    auto get = [&]() { hipEvent_t e; if (!h->prof_free.empty()) { e = h->prof_free.back(); h->prof_free.pop_back(); }
                        else (void)hipEventCreate(&e); return e; };
     a = get(); b = get();
     (void)hipEventRecord(a, s);
@@ -160,7 +212,7 @@ struct BprxProfScope {
   ~BprxProfScope() {
     if (!on) return;
     (void)hipEventRecord(b, s);
-    h->prof_pending->push_back({phase, a, b});
+    h->prof_pending.push_back({phase, a, b});
   }
 };
 

@@ -2030,12 +2030,8 @@ extern "C" int bprx_apply_user_msgs(bprx_handle *h, const float *msgs, int32_t n
   const size_t jobs = (size_t)nranks * (size_t)cap;
   if (h->msg_next_n < jobs) {                                                  // first call (or a larger world / capacity)
     BPRX_HIP(h, hipStreamSynchronize(s));
-    if (h->msg_next) (void)hipFree(h->msg_next);
-    h->msg_next = nullptr; h->msg_next_n = 0;
-    if (hipMalloc((void **)&h->msg_next, jobs * sizeof(int32_t)) != hipSuccess) {
-      (void)hipGetLastError();
-      BPRX_FAIL(h, BPRX_E_NOMEM, "apply_user_msgs: chain links (%zu entries)", jobs);
-    }
+    h->msg_next_n = 0;
+    if (h->mem.regrow(&h->msg_next, jobs) != hipSuccess) BPRX_FAIL(h, BPRX_E_NOMEM, "apply_user_msgs: chain links (%zu entries)", jobs);
     h->msg_next_n = jobs;
   }
   const bool vec = vec_ok(h) && ((uintptr_t)msgs & 15) == 0;

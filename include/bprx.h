@@ -109,6 +109,7 @@ BPRX_API int bprx_abi_version(void);
 BPRX_API int bprx_create(const bprx_config *cfg, bprx_handle **out);
 BPRX_API int bprx_destroy(bprx_handle *h);
 BPRX_API const char *bprx_last_error(const bprx_handle *h); /* h == NULL: error of the last failed bprx_create */
+BPRX_API int64_t bprx_live_device_allocs(void); /* device buffers the library holds right now, all handles of the process */
 
 /* Binds caller-owned device tables (they stay owned by the caller and are updated in place by the steps).
    bf16 / fp8 features: F is frozen (visual_loader_mixin.py:22-31) -- this call copies it ONCE into a tiled layout the
