@@ -386,6 +386,28 @@ class Engine:
         _ffi.check(self.h, self.lib.bprx_explain_pairs(self.h, _ptr(u), _ptr(i), u.numel(), _ptr(out), _stream()))
         return out
 
+    def feat_explain(self, user, item, top=5, ncols=None, maps=False):
+        """bprx_feat_explain on a VBPR engine, plain or factored: x_ui = base + sum_c F_ic w_uc, w_uc = Bp[c] + E[c,:].Tu_u.  Returns
+        a dict of device tensors: score, base, visual [n]; col int32 and contrib [n, top]: the `top` feature columns with the largest
+        F_ic w_uc (rank 0 first, equal values in ascending column order; slots beyond ncols: -1 / 0); with maps=True also map
+        [n, ncols], every F_ic w_uc.  ncols (default feat_dim): the columns that exist, the rest being zero padding.  Any n."""
+        u, i = as_index(user, self.device), as_index(item, self.device)
+        if u.numel() != i.numel():
+            raise ValueError("feat_explain: %d users for %d items" % (u.numel(), i.numel()))
+        n, top = u.numel(), int(top)
+        ncols = self.D if ncols is None else int(ncols)
+        f = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)
+        out = {"score": f(n), "base": f(n), "visual": f(n),
+               "col": torch.empty((n, max(top, 0)), dtype=torch.int32, device=self.device), "contrib": f(n, max(top, 0))}
+        if maps:
+            out["map"] = f(n, max(ncols, 0))
+        F = self._t.get("F")
+        p = lambda t: C.c_void_p(t.data_ptr())      # (an empty tensor still has to reach the library's argument checks)
+        _ffi.check(self.h, self.lib.bprx_feat_explain(self.h, None if F is None else p(F), p(u), p(i), n, ncols, top, p(out["score"]),
+                                                      p(out["base"]), p(out["visual"]), p(out["col"]), p(out["contrib"]),
+                                                      p(out["map"]) if maps else None, _stream()))
+        return out
+
     def tables_dirty(self):
         """Call after writing any bound table from outside the library (bprx_tables_dirty): the handle reuses images
         derived from E/Bp (their bf16/fp8 copy, the item projections) until a step changes them."""

@@ -11,6 +11,7 @@ Metric definitions restated (Evaluator.py:82-128), for user u with train set T, 
   auc = 1 - position/(|neg| n); top-K = stable descending order of (negatives by ascending id, then e_1..e_n);
   hr = any e in top-K; prec = hits/min(K,|cand|); rec = hits/n; ndcg = ln2/ln(position+2) if position < K else 0.
 """
+import contextlib
 import datetime
 import math
 from time import time
@@ -227,13 +228,32 @@ class Evaluator:
             if block_hook is not None and written[0]:
                 block_hook(*written)
 
-    def store_recommendation_grads(self, path=""):
+    def _write_feature_rows(self, ex, users, items, top):
+        """The expl-* rows of VBPR and GradFashion for the pairs (users, items), one bprx_feat_explain call:
+        'u\\ti\\tscore\\tbase\\trank\\tcolumn\\tcontribution', rank 0 (the largest F_ic w_uc) first, one row per rank below
+        min(top, feature columns); score = base + the sum of all the pair's contributions."""
+        e = self.model.explain(users, items, top)
+        for r, (u, i) in enumerate(zip(users, items)):
+            head = str(u) + '\t' + str(i) + '\t' + str(e["score"][r]) + '\t' + str(e["base"][r]) + '\t'
+            for s in range(e["col"].shape[1]):
+                if e["col"][r, s] < 0:
+                    break
+                ex.write(head + str(s) + '\t' + str(e["col"][r, s]) + '\t' + str(e["contrib"][r, s]) + '\n')
+
+    def store_recommendation_features(self, path_recs="", path_expl="", top=5):
+        """VBPR: `path_recs` exactly as store_recommendation writes it (the same device or host path), and for every row written
+        there the rows of _write_feature_rows in `path_expl`, one call per user block."""
+        with open(path_recs, 'w') as out, open(path_expl, 'w') as ex:
+            self._store_recommendation_rows(out, lambda users, items: self._write_feature_rows(ex, users, items, top))
+
+    def store_recommendation_grads(self, path="", path_expl=None, top=5):
         """Evaluator.py:261-275 (GradFashion): for every user the items training_list[u] + validation_list[u] + test_list[u],
         in that order, one row 'u\\ti\\tcolour\\tedges' each (get_explanations.py:19-21 reads USER_ID, ITEM_ID, COLOR, EDGES).
-        The attributions come from the device, one bprx_explain_pairs call per block of users."""
+        The attributions come from the device, one bprx_explain_pairs call per block of users.  path_expl: also the rows of
+        _write_feature_rows for the same pairs in the same order, one bprx_feat_explain call per block."""
         lists = (self.data.training_list, self.data.validation_list, self.data.test_list)
         U = self.data.num_users
-        with open(path, 'w') as out:
+        with open(path, 'w') as out, (open(path_expl, 'w') if path_expl else contextlib.nullcontext()) as ex:
             for u0 in range(0, U, self.user_block):
                 u1 = min(U, u0 + self.user_block)
                 users, items = [], []
@@ -246,6 +266,8 @@ class Evaluator:
                 g = self.model.engine.explain_pairs(users, items).cpu().numpy()
                 for r, (u, i) in enumerate(zip(users, items)):
                     out.write(str(u) + '\t' + str(i) + '\t' + str(g[r, 0]) + '\t' + str(g[r, 1]) + '\n')
+                if ex is not None:
+                    self._write_feature_rows(ex, users, items, top)
 
     def store_recommendation_attention(self, path=""):
         """Evaluator.py:241-259 (AttentiveFashion): the top-k rows 'u\\titem\\tscore\\talpha_colour\\talpha_edges\\talpha_class'.

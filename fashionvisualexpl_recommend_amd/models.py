@@ -237,6 +237,9 @@ class VBPR(BPRMF):
         unless `normalize=True` is left to do it)."""
         self.embed_d = params.embed_d
         self._features = features
+        self.feat_explain = int(getattr(params, "feat_explain", 0) or 0)          # rows per pair in expl-*; 0: none
+        if not 0 <= self.feat_explain <= 32:
+            raise ValueError("%s: feat_explain is 0 (off) .. 32 (got %r)" % (type(self).__name__, self.feat_explain))
         super().__init__(data, params, init)
         self.directory_parameters = f'batch_{params.batch_size}-D_{params.embed_d}-K_{params.embed_k}' \
                                     f'-lr_{params.lr}-reg_{params.reg}'      # VBPR.py:35-39
@@ -275,6 +278,29 @@ class VBPR(BPRMF):
         return xui, self.Gu[u], self.Gi[i], self.F[i], self.Tu[u], self.Bi[i]
 
     __call__ = call
+
+    @property
+    def feat_cols(self):
+        """The feature columns that exist: the width of the feature files, before any zero padding of F."""
+        return self.dim_cnn_features
+
+    def explain(self, users, items, top=5, maps=False):
+        """The `top` feature columns that contribute most to each pair's score (Engine.feat_explain) as numpy arrays: score, base,
+        visual [n], col / contrib [n, top] (rank 0 first), with maps=True also map [n, feat_cols]: x_ui = base + sum_c map[c]."""
+        return {n: v.cpu().numpy() for n, v in self.engine.feat_explain(users, items, top, self.feat_cols, maps=maps).items()}
+
+    def explain_ui(self, u, items, top=5, maps=False):
+        """explain() for one user and several items."""
+        items = list(items)
+        return self.explain([int(u)] * len(items), items, top, maps)
+
+    def _store_recs(self, path):
+        """recs-* / best-recs-* as every model writes them; with params.feat_explain = L > 0 also expl-* / best-expl-* next to them."""
+        if self.feat_explain <= 0:
+            super()._store_recs(path)
+            return
+        d, f = os.path.split(path)
+        self.evaluator.store_recommendation_features(path, os.path.join(d, f.replace("recs-", "expl-", 1)), self.feat_explain)
 
 
 class GradFashion(VBPR):
@@ -347,6 +373,10 @@ class GradFashion(VBPR):
 
     # ---- the reference's attribute surface ---------------------------------------------------------------------------
     @property
+    def feat_cols(self):
+        return self.dim_color_features + self.dim_edge_features                 # colour [0, Dc), edges [Dc, Dc + De); F is padded
+
+    @property
     def color_weights(self):
         return {"Fc": self.F[:, :self.dim_color_features], "Ec": self.engine.t["Ec"]}
 
@@ -391,8 +421,11 @@ class GradFashion(VBPR):
 
     def _store_recs(self, path):
         """GradFashion.py:236-240, 252-258: the reference writes the top-K list to the recs path and then OVERWRITES the same
-        path with the explanation rows (get_explanations.py:19-21 reads them from there); only the final content is written."""
-        self.evaluator.store_recommendation_grads(path=path)
+        path with the explanation rows (get_explanations.py:19-21 reads them from there); only the final content is written.
+        With params.feat_explain = L > 0 also expl-* / best-expl-* next to it: the L strongest feature columns of the same pairs."""
+        d, f = os.path.split(path)
+        expl = os.path.join(d, f.replace("recs-", "expl-", 1)) if self.feat_explain > 0 else None
+        self.evaluator.store_recommendation_grads(path=path, path_expl=expl, top=self.feat_explain)
 
 
 def _glorot_1d(rs, n):

@@ -55,6 +55,9 @@ def parse_args(argv=None):
                         help="attentive_fashion: also write expl-* / best-expl-* files with the exact split of every recommended "
                              "(u, i) score over colour, edges and class and the edges share over a G x G grid of the edge image "
                              "(G = 1, 2, 4, 7, 8, 14 or 16); 0 = off")
+    parser.add_argument('--feat_explain', type=int, default=0,
+                        help="vbpr, grad_fashion: also write expl-* / best-expl-* files with the L (1..32) feature columns that "
+                             "contribute most to every written (u, i): column and contribution F_ic w_uc, rank 0 first; 0 = off")
     # not in the reference
     parser.add_argument('--dropout', type=float, default=0.5,
                         help="attentive_fashion: rate of the encoders' Dropout layers (AttentiveFashion.py:53,62,70: 0.5)")
@@ -89,6 +92,10 @@ def parse_args(argv=None):
         parser.error("--af_explain takes 0 (off), 1, 2, 4, 7, 8, 14 or 16 (got %s)" % args.af_explain)
     if args.af_explain != 0 and args.rec != 'attentive_fashion':
         parser.error("--af_explain %s needs --rec attentive_fashion (got --rec %s)" % (args.af_explain, args.rec))
+    if not 0 <= args.feat_explain <= 32:
+        parser.error("--feat_explain takes 0 (off) .. 32 (got %s)" % args.feat_explain)
+    if args.feat_explain != 0 and args.rec not in ('vbpr', 'grad_fashion'):
+        parser.error("--feat_explain %s needs --rec vbpr or grad_fashion (got --rec %s)" % (args.feat_explain, args.rec))
     if not 0.0 <= args.dropout < 1.0:
         parser.error("--dropout takes a rate in [0, 1) (got %s)" % args.dropout)
     return args
@@ -98,6 +105,8 @@ def train(argv=None):
     args = parse_args(argv)
     if args.rec == 'grad_fashion' and int(args.world_size) > 1:
         raise NotImplementedError('--rec grad_fashion runs on one GPU (no multi-GPU form): use --world_size 1')
+    if args.feat_explain != 0 and int(args.world_size) > 1:
+        raise NotImplementedError('--feat_explain runs on one GPU (the sharded drivers write no expl-* files): use --world_size 1')
     if args.rec == 'acf' and int(args.world_size) > 1:
         raise NotImplementedError('--rec acf runs on one GPU (no multi-GPU form): use --world_size 1')
     if args.rec == 'acf' and args.dtype not in ('fp32', 'bf16'):

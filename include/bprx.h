@@ -166,6 +166,35 @@ BPRX_API int bprx_bind_factored(bprx_handle *h, const bprx_tables *t, const bprx
    user / item: device int32 [n]; any n >= 0 (not bounded by max_batch). */
 BPRX_API int bprx_explain_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t n, float *out, void *stream);
 
+/* ---- VBPR and GradFashion: the score per feature column ------------------------------------------------------------------
+   The linear score of a bound VBPR handle, plain or factored, decomposes exactly:
+       x_ui = Bi_i + Gu_u.Gi_i + sum_c F_ic w_uc        w_uc = Bp[c] + sum_x E[c,x] Tu[u,x]
+              `---- base ----'   `--- visual ---'
+   F_ic w_uc is gradient x input of x_ui with respect to feature column c -- the quantity GradFashion.predict_ui_grads sums per
+   modality (a factored handle's E / Bp are E_eff / Bp_eff: columns [0, Dc) are the colour histogram, [Dc, Dc + De) the edges).
+   F: device pointer to the caller's ROW-MAJOR [num_items, feat_dim] table in the handle's feat_dtype (fp32, bf16, or e4m3fn codes
+   of f * feat_scale); it is passed here because bprx_bind_tables allows a bf16 / fp8 F to be released once the tiled copy is
+   made -- this call never reads the tiled copy.  Only columns [0, ncols) exist for the explanation (1 <= ncols <= feat_dim: the
+   rest is the models' zero padding); 1 <= top <= 32; 0 <= n < 2^31, not bounded by max_batch (n == 0: BPRX_OK, nothing is
+   touched); feat_dim <= 16384 (one user's fp32 w row lives in LDS).  BPRX_E_INVALID otherwise and for a NULL pointer other than
+   map; BPRX_E_STATE on a BPRMF, ACF or AttentiveFashion handle.  After any error the handle stays usable.
+   Outputs (device): score, base, visual fp32 [n]; col int32 [n, top] and contrib fp32 [n, top]: the `top` columns with the
+   largest F_ic w_uc, rank 0 first, non-increasing; values compare as floats (+0.0 == -0.0, as in bprx_topk) and equal values come
+   in ascending column order; slots r >= ncols hold col = -1, contrib = 0.  map fp32 [n, ncols] (row stride ncols; NULL: not
+   written): every F_ic w_uc.
+   Precision: E, Bp, Tu, Gu, Gi, Bi are read as the fp32 master tables, and the features are dequantised exactly (bf16 -> fp32;
+   an fp8 code's value / feat_scale).  With bf16 / fp8 features bprx_score_pairs goes through a ROUNDED image of [E|Bp]^T: `score`
+   here does not, and differs from bprx_score_pairs by that rounding.  w_uc is a function of (E[c,:], Bp[c], Tu_u) alone (one
+   fma chain in the order of x): columns with bit-equal E rows, Bp and features give bit-equal contributions.  score == base +
+   visual as one fp32 add; visual is the sum of the row's contributions in a fixed order; contrib[p, r] is bit-equal to
+   map[p, col[p, r]].  No float atomics: two calls return the same bits.
+   Indices out of range are clamped and reported by bprx_sync_check (BPRX_E_RANGE), as for bprx_explain_pairs.  Lazy adam_tf23
+   rows are brought up to date first (as bprx_score_pairs does); apart from that the call writes its outputs only: no table, Adam
+   slot, step counter or cached projection changes, and nothing is allocated. */
+BPRX_API int bprx_feat_explain(bprx_handle *h, const void *F, const int32_t *user, const int32_t *item, int64_t n, int32_t ncols,
+                               int32_t top, float *score, float *base, float *visual, int32_t *col, float *contrib, float *map,
+                               void *stream);
+
 /* ---- ACF (ACF.py:20-270) on a BPRMF handle ------------------------------------------------------------------------------
    Attentive Collaborative Filtering over per-item feature maps f_l [M, C] (M = H*W spatial components).  For user u with
    history P(u) (ACF.py:135-181):
