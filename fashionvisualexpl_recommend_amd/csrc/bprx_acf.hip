@@ -1415,7 +1415,7 @@ int bprx_acf_step(bprx_handle *h, const int32_t *user, const int32_t *pos, const
     h->adam_t += 1;
     lr_t = bprx_adam_lr_t(h);
   }
-  h->pend_lr = lr_t;
+  h->step.lr_t = lr_t;                                     // (bprx_step_lr)
   int rc;
   hipLaunchKernelGGL(k_acf_claim, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, user, B, U, S->uslot, h->errflag);
   BPRX_LAUNCH_CHECK(h, "k_acf_claim");

@@ -154,7 +154,6 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
     // seg_policy: 0 never, 1 per step (segments when the batch revisits items: 2B >= I; sparse batches keep the atomic
     // staging path with its in-place update of exclusive rows -- C3 shard: 0.104 vs 0.121 ms/step), 2 always
     h->seg_policy = (fits && !(cfg->flags & BPRX_FLAG_EXPORT_ITEM_GRAD)) ? std::min(std::max(env_int("BPRX_ITEM_MODE", 1), 0), 2) : 0;
-    h->item_mode = 0;
     if (h->seg_policy) {
       // chunk list: the owners' regions (one slot per item + 4 per owner, <= 1024 owners; a last partial range) + the overflow list
       h->seg_lead_cap = (int64_t)(I + 8192 + 4 * 1024 + 2 * MB / 64 + 64 + 64);
@@ -184,10 +183,10 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
     const size_t cap = 2 * MB < I ? 2 * MB : I;
     A.zeros(&h->ilist, cap); A.zeros(&h->ilist_n, (size_t)2);
   }
-  h->SK_step = h->SK;
+  h->step.SK_step = h->SK;
   if (h->adam_lazy) {
     A.zeros(&h->lastU, U); A.zeros(&h->lastI, I);
-    A.zeros(&h->lr_hist, (size_t)bprx_adam_hist());
+    A.zeros(&h->lr_hist, (size_t)ADAM_HIST);
   }
   // exclusive-row fast path: sgd only (adam sweeps every row anyway); not with exported user gradients
   h->fast_rows = (cfg->optimizer == BPRX_OPT_SGD && !(cfg->flags & BPRX_FLAG_EXPORT_USER_GRAD)) ? 1 : 0;   // per side: make_args
@@ -389,123 +388,93 @@ extern "C" int bprx_score_pairs(bprx_handle *h, const int32_t *user, const int32
   return bprx_launch_score(h, user, item, B, nullptr, 0, x, s);
 }
 
+// A planned step becomes the step in flight: the only place that moves the carried state at the start of a step.
+static void commit_plan(bprx_handle *h, const StepPlan &p) {
+  h->step = p;
+  h->step_stage = 1;
+  h->adam_t = p.adam_t;
+  if (p.B == 0) return;
+  h->idx8_n = 0;                                           // the byte planes are consumed, whatever this step does with them
+  h->proj_fresh = false;
+  h->W_dirty = p.leaves_w_dirty;
+  if (p.item_mode) h->seg_slot ^= 1;                       // (k_index_seg clears the other cursor triple for the next such step)
+  if (p.use_list) h->slist_slot ^= 1;                      // (k_apply_sgd_list likewise)
+}
+
+// the launches of bprx_step_begin_sparse, in order
+static int launch_sparse_half(bprx_handle *h, const StepPlan &p, hipStream_t s) {
+  int rc;
+  if (p.adam_sync_first && (rc = bprx_launch_adam_sync(h, p.adam_t - 1, s))) return rc;
+  if (p.catchup_aside) {                                 // work that does not depend on P, beside the projection
+    BPRX_HIP(h, hipEventRecord(h->ev_fork, s));
+    BPRX_HIP(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
+    if ((rc = bprx_launch_adam_catchup(h, p, h->side))) return rc;
+    BPRX_HIP(h, hipEventRecord(h->ev_join, h->side));
+  } else if (p.catchup && (rc = bprx_launch_adam_catchup(h, p, s))) return rc;
+  if (p.project && p.list_mode && (rc = bprx_launch_cast_Et(h, s))) return rc;
+  if (p.index_first && (rc = bprx_launch_index_pass(h, p, s))) return rc;      // list: counts + the distinct-item list
+  if (p.project && !p.list_mode && (rc = bprx_launch_cast_Et(h, s))) return rc;
+  if (p.fwd) {                                           // P rows of the listed items only / of every (touched) item
+    rc = p.list_mode ? bprx_launch_proj_fwd(h, h->ilist, p.list_bound, p.list_cur, 1, h->P, s)
+                     : bprx_launch_proj_fwd(h, nullptr, h->cfg.num_items, nullptr, 0, h->P, s, p.mask ? h->seg_cnt : nullptr);
+    if (rc) return rc;
+  }
+  if (p.catchup_aside) BPRX_HIP(h, hipStreamWaitEvent(s, h->ev_join, 0));
+  if (p.B == 0) return BPRX_OK;
+  if (!p.index_first && (rc = bprx_launch_index_pass(h, p, s))) return rc;
+  return bprx_launch_triplet_grad(h, p, s);
+}
+
 // First half of bprx_step_begin: index pass, item projections, per-triplet gradients.  Afterwards the USER-side gradients
 // of the batch are final (staging tables with BPRX_FLAG_EXPORT_USER_GRAD): a replicated-user step packs and all-gathers
 // them while bprx_step_begin_dense (item rows, W, dE|dBp = F^T W) is still running.
-extern "C" int bprx_step_begin_sparse(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B, void *stream) {
+static int step_begin_sparse(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B, bool fused_reduce,
+                             hipStream_t s) {
   int rc = check_ready(h, B);
   if (rc) return rc;
-  if (h->pending_stage) BPRX_FAIL(h, BPRX_E_STATE, "step_begin called twice without step_end");
+  if (h->step_stage) BPRX_FAIL(h, BPRX_E_STATE, "step_begin called twice without step_end");
   if (h->acf) BPRX_FAIL(h, BPRX_E_STATE, "step_begin: an ACF handle takes whole steps only (bprx_step)");
   if (h->af) BPRX_FAIL(h, BPRX_E_STATE, "step_begin: an AttentiveFashion handle takes whole steps only (bprx_step)");
-  hipStream_t s = (hipStream_t)stream;
-  const bool vb = h->cfg.model == BPRX_MODEL_VBPR;
-  if (B == 0) {
-    // A rank of a replicated-user multi-GPU step whose item shard holds no positive of this global batch: it contributes an
-    // empty message and a zero dense gradient, but takes part in every collective and takes the same optimizer step as the
-    // other replicas (bprx_pack_user_msg -> count 0, bprx_step_begin_dense -> dE|dBp = 0, bprx_apply_user_msgs, bprx_step_end).
-    if (!(h->cfg.flags & (BPRX_FLAG_EXPORT_USER_GRAD | BPRX_FLAG_EXPORT_ITEM_GRAD))) BPRX_FAIL(h, BPRX_E_INVALID, "step: empty batch");
-    h->list_mode = 0; h->item_mode = 0; h->step_masked = false; h->mask_kind = 0;
-    if (h->cfg.optimizer == BPRX_OPT_ADAM_TF23) {
-      h->adam_t += 1;
-      const float lr_t = bprx_adam_lr_t(h);
-      if (h->adam_lazy) {
-        if (h->adam_t - h->adam_synced >= bprx_adam_hist() - 2 && (rc = bprx_launch_adam_sync(h, h->adam_t - 1, s))) return rc;
-        if ((rc = bprx_launch_adam_catchup(h, nullptr, nullptr, nullptr, 0, lr_t, s))) return rc;   // records lr_t of this step
-      }
-      h->pend_lr = lr_t;
-    } else h->pend_lr = h->cfg.lr;
-    h->pending_B = 0; h->pending_stage = 1;
-    h->pend_u = h->pend_i = h->pend_j = nullptr;
-    return BPRX_OK;
-  }
-  if (!user || !pos || !neg) BPRX_FAIL(h, BPRX_E_INVALID, "step: null index pointer");
-  // list mode: both projections over the batch's distinct items only (needs the index pass BEFORE the forward projection)
-  h->list_mode = vb && !h->proj_fresh && (h->list_policy == 2 || (h->list_policy == 1 && 2 * B < (int64_t)h->cfg.num_items));
-  h->item_mode = !h->list_mode && (h->seg_policy == 2 || (h->seg_policy == 1 && 2 * B >= (int64_t)h->cfg.num_items));
-  h->step_masked = false;
-  h->list_reset_cnt = !(h->fast_rows && !(h->cfg.flags & BPRX_FLAG_EXPORT_ITEM_GRAD));
-  // byte planes of this very batch, left by bprx_sample_*_h (consumed here, whatever this step does with them)
-  h->idx8_use = h->idx8_ready(pos, neg, B);
-  h->idx8_n = 0;
-  float lr_t = h->cfg.lr;
-  bool catchup_aside = false;     // the (ALU-bound) lazy-Adam catch-up runs on the side stream beside the (HBM-bound) projection
-  if (h->cfg.optimizer == BPRX_OPT_ADAM_TF23) {
-    h->adam_t += 1;
-    lr_t = bprx_adam_lr_t(h);
-    if (h->adam_lazy) {
-      // the ring holds lr_s of the last ADAM_HIST steps: before it would wrap, everything is caught up (amortised: one
-      // sweep per ~8000 steps); then the rows of THIS batch are brought to step t-1 for the forward pass
-      if (h->adam_t - h->adam_synced >= bprx_adam_hist() - 2 && (rc = bprx_launch_adam_sync(h, h->adam_t - 1, s))) return rc;
-      catchup_aside = h->side && !h->proj_fresh && !h->list_mode && !h->p_valid;
-      if (!catchup_aside && (rc = bprx_launch_adam_catchup(h, user, pos, neg, B, lr_t, s))) return rc;
-    }
-  }
-  if (catchup_aside) {                                     // work that does not depend on P, beside the projection
-    BPRX_HIP(h, hipEventRecord(h->ev_fork, s));
-    BPRX_HIP(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
-    if ((rc = bprx_launch_adam_catchup(h, user, pos, neg, B, lr_t, h->side))) return rc;
-    BPRX_HIP(h, hipEventRecord(h->ev_join, h->side));
-  }
-  if (h->list_mode) {
-    h->list_cur = h->ilist_n + h->list_slot;
-    h->list_bound = 2 * B < (int64_t)h->cfg.num_items ? 2 * B : (int64_t)h->cfg.num_items;
-    if ((rc = bprx_launch_cast_Et(h, s))) return rc;
-    if ((rc = bprx_launch_index_pass(h, user, pos, neg, B, s))) return rc;              // counts + the distinct-item list
-    if (!h->p_valid &&                                                                   // P rows of the listed items only
-        (rc = bprx_launch_proj_fwd(h, h->ilist, h->list_bound, h->list_cur, 1, h->P, s))) return rc;
-  } else if (vb && !h->proj_fresh) {
-    // Segment mode: k_index_seg depends on the index arrays only, so it runs BEFORE the forward projection and both projections
-    // skip the feature rows of the items this batch does not touch (seg_cnt[item] == 0: nobody reads that row of P in this step
-    // and p_valid stays false; its W row is all zeros).  Everything the index pass writes -- the Wb rows it zeroes, cntU / ulist /
-    // uslot_of, seg_rank / seg_cnt / seg_ptr, the chunk list and both cursor triples -- was last read by the previous step's
-    // kernels (k_triplet_seg, k_item_seg, the backward projection) on this same stream: stream order is the only ordering there
-    // is today and it still holds.  The side stream's catch-up touches none of these buffers (rows, slots, lastU / lastI, lr_hist).
-    h->step_masked = h->item_mode && !h->p_valid &&
-                     (h->proj_mask == 2 ? h->cfg.feat_dtype != BPRX_F_FP32
-                                        : (h->proj_mask == 1 && h->cfg.feat_dtype == BPRX_F_BF16 && h->PS / 16 <= 9));
-    if (h->step_masked && (rc = bprx_launch_index_pass(h, user, pos, neg, B, s))) return rc;
-    if ((rc = bprx_launch_cast_Et(h, s))) return rc;
-    if (!h->p_valid && (rc = bprx_launch_proj_fwd(h, nullptr, h->cfg.num_items, nullptr, 0, h->P, s,
-                                                  h->step_masked ? h->seg_cnt : nullptr))) return rc;   // every (touched) item
-  }
-  h->mask_kind = h->step_masked && h->fwd_masked ? 2 : 0;   // (bprx_step_begin_dense adds the backward pass)
-  h->proj_fresh = false;
-  if (catchup_aside) BPRX_HIP(h, hipStreamWaitEvent(s, h->ev_join, 0));
-  if (!h->list_mode && !h->step_masked && (rc = bprx_launch_index_pass(h, user, pos, neg, B, s))) return rc;
-  if ((rc = bprx_launch_triplet_grad(h, user, pos, neg, B, s))) return rc;
-  h->pending_B = B;
-  h->pending_stage = 1;
-  h->pend_u = user; h->pend_i = pos; h->pend_j = neg; h->pend_lr = lr_t;
-  return BPRX_OK;
+  if (B && (!user || !pos || !neg)) BPRX_FAIL(h, BPRX_E_INVALID, "step: null index pointer");
+  const StepPlan plan = plan_step(*h, user, pos, neg, B, fused_reduce);
+  if (plan.error == PLAN_E_EMPTY) BPRX_FAIL(h, BPRX_E_INVALID, "step: empty batch");
+  commit_plan(h, plan);
+  rc = launch_sparse_half(h, h->step, s);
+  if (rc) h->step_stage = 0;                               // a failed _begin leaves no step pending
+  return rc;
+}
+
+extern "C" int bprx_step_begin_sparse(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B, void *stream) {
+  return step_begin_sparse(h, user, pos, neg, B, false, (hipStream_t)stream);
 }
 
 extern "C" int bprx_step_begin_dense(bprx_handle *h, void *stream) {
   if (!h) return BPRX_E_INVALID;
-  if (h->pending_stage != 1) BPRX_FAIL(h, BPRX_E_STATE, "step_begin_dense without step_begin_sparse");
+  if (h->step_stage != 1) BPRX_FAIL(h, BPRX_E_STATE, "step_begin_dense without step_begin_sparse");
   hipStream_t s = (hipStream_t)stream;
+  const StepPlan &p = h->step;
   const bool vb = h->cfg.model == BPRX_MODEL_VBPR;
-  if (h->pending_B == 0) {                                 // empty batch of a replicated-user rank: zero dense gradient
-    if (vb) BPRX_HIP(h, hipMemsetAsync(h->dEp, 0, ((size_t)h->cfg.feat_dim * (h->cfg.embed_d + 1)) * sizeof(float), s));
-    h->pending_stage = 2;
-    return BPRX_OK;
-  }
-  const int32_t *user = h->pend_u, *pos = h->pend_i, *neg = h->pend_j;
-  const int64_t B = h->pending_B;
-  const float lr_t = h->pend_lr;
   int rc;
-  if ((rc = bprx_launch_item_seg(h, pos, neg, B, lr_t, s))) return rc;                  // item rows + W, no float atomics
-  if (vb && (rc = bprx_launch_proj_bwd(h, B, s, h->step_masked ? h->seg_cnt : nullptr))) return rc;   // dE|dBp = F^T W
-  if (vb) h->mask_kind = h->mask_kind == 2 ? (h->bwd_masked ? 1 : 2) : (h->bwd_masked ? 3 : 0);
-  if ((rc = bprx_launch_apply(h, user, pos, neg, B, lr_t, s))) return rc;
-  h->pending_stage = 2;
+  if (p.B == 0) {                                          // empty batch of a replicated-user rank: zero dense gradient
+    if (vb) BPRX_HIP(h, hipMemsetAsync(h->dEp, 0, ((size_t)h->cfg.feat_dim * (h->cfg.embed_d + 1)) * sizeof(float), s));
+  } else {
+    if (p.item_mode && (rc = bprx_launch_item_seg(h, p, s))) return rc;                 // item rows + W, no float atomics
+    if (vb && (rc = bprx_launch_proj_bwd(h, p, s))) return rc;                           // dE|dBp = F^T W
+    if (p.apply != APPLY_NONE && (rc = bprx_launch_apply(h, p, s))) return rc;
+  }
+  h->step_stage = 2;
   return BPRX_OK;
 }
 
-extern "C" int bprx_step_begin(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B, void *stream) {
-  int rc = bprx_step_begin_sparse(h, user, pos, neg, B, stream);
-  if (!rc && (rc = bprx_step_begin_dense(h, stream))) { h->pending_B = 0; h->pending_stage = 0; }   // a failed _begin leaves no step pending
+static int step_begin(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B, bool fused_reduce,
+                      void *stream) {
+  int rc = step_begin_sparse(h, user, pos, neg, B, fused_reduce, (hipStream_t)stream);
+  if (!rc && (rc = bprx_step_begin_dense(h, stream))) h->step_stage = 0;   // a failed _begin leaves no step pending
   return rc;
+}
+
+extern "C" int bprx_step_begin(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B, void *stream) {
+  return step_begin(h, user, pos, neg, B, false, stream);
 }
 
 extern "C" int bprx_step_project(bprx_handle *h, void *stream) {
@@ -565,20 +534,21 @@ extern "C" int bprx_dense_grad(bprx_handle *h, float **ptr, int64_t *count) {
 
 extern "C" int bprx_step_end(bprx_handle *h, float *loss_out, void *stream) {
   if (!h) return BPRX_E_INVALID;
-  if (!h->pending_stage) BPRX_FAIL(h, BPRX_E_STATE, "step_end without step_begin");
-  if (h->pending_stage != 2) BPRX_FAIL(h, BPRX_E_STATE, "step_end before step_begin_dense");
+  if (!h->step_stage) BPRX_FAIL(h, BPRX_E_STATE, "step_end without step_begin");
+  if (h->step_stage != 2) BPRX_FAIL(h, BPRX_E_STATE, "step_end before step_begin_dense");
   hipStream_t s = (hipStream_t)stream;
+  const StepPlan &p = h->step;
   int rc;
-  float lr_t = h->cfg.lr;
-  if (h->cfg.optimizer == BPRX_OPT_ADAM_TF23) {
-    lr_t = bprx_adam_lr_t(h);
+  h->step_stage = 0;
+  if (h->factored && (rc = bprx_launch_fact_update(h, p.lr_t, s))) return rc;   // the factors, then E_eff / Bp_eff
+  if (p.dense_launch && (rc = bprx_launch_dense_update(h, p, s))) return rc;
+  if (h->cfg.model == BPRX_MODEL_VBPR) {                    // what the end of a step leaves for the next one
+    if (p.dense_launch) h->absmax_valid = h->cfg.feat_dtype == BPRX_F_FP8;   // k_dense_update left max|E,Bp| in qs[2 + qs_slot]
+    if (p.list_mode) h->list_slot ^= 1;                     // the step's list is consumed
+    h->et_valid = p.dense_launch && h->cfg.feat_dtype == BPRX_F_BF16;   // E / Bp moved: the images were refreshed, or are stale
+    h->p_valid = false;                                     //               the item projections are stale
   }
-  int64_t B = h->pending_B;
-  h->pending_B = 0;
-  h->pending_stage = 0;
-  if (h->factored && (rc = bprx_launch_fact_update(h, lr_t, s))) return rc;   // the factors, then E_eff / Bp_eff
-  if (h->cfg.model == BPRX_MODEL_VBPR && (rc = bprx_launch_dense_update(h, lr_t, s))) return rc;
-  if (loss_out && (rc = bprx_launch_loss_reduce(h, B, loss_out, s))) return rc;
+  if (loss_out && (rc = bprx_launch_loss_reduce(h, p.B, loss_out, s))) return rc;
   return BPRX_OK;
 }
 
@@ -593,11 +563,9 @@ extern "C" int bprx_step(bprx_handle *h, const int32_t *user, const int32_t *pos
     const int rc = check_ready(h, B);
     return rc ? rc : bprx_af_step(h, user, pos, neg, B, loss_out, (hipStream_t)stream);
   }
-  h->fused_reduce = !h->factored;  // no all-reduce in between: the dense update sums the split-K slabs itself (GradFashion's
-                                   // chain rule reads the summed gradient from dEp)
-  int rc = bprx_step_begin(h, user, pos, neg, B, stream);
+  // no all-reduce in between: the dense update may sum the split-K slabs itself (StepPlan::fused_reduce)
+  int rc = step_begin(h, user, pos, neg, B, true, stream);
   if (!rc) rc = bprx_step_end(h, loss_out, stream);
-  h->fused_reduce = false;
   return rc;
 }
 
@@ -631,12 +599,16 @@ extern "C" int bprx_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *o
 
 extern "C" int bprx_step_lr(const bprx_handle *h, float *lr_t) {
   if (!h || !lr_t) return BPRX_E_INVALID;
-  *lr_t = h->pend_lr;
+  *lr_t = h->step.lr_t;
   return BPRX_OK;
 }
 
-extern "C" int bprx_index_pass_kind(const bprx_handle *h) { return h ? h->idx_kind : 0; }
-extern "C" int bprx_proj_mask_kind(const bprx_handle *h) { return h ? h->mask_kind : 0; }
+extern "C" int bprx_index_pass_kind(const bprx_handle *h) { return h ? h->step.idx_kind : 0; }
+extern "C" int bprx_proj_mask_kind(const bprx_handle *h) {
+  if (!h || !h->step.mask) return 0;
+  const bool fwd = bprx_proj_fwd_takes_mask(*h), bwd = bprx_proj_bwd_takes_mask(*h);
+  return fwd ? (bwd ? 1 : 2) : (bwd ? 3 : 0);
+}
 
 extern "C" int bprx_sync_check(bprx_handle *h, void *stream) {
   if (!h) return BPRX_E_INVALID;

@@ -954,7 +954,7 @@ static int af_step_body(bprx_handle *h, const int32_t *user, const int32_t *pos,
     h->adam_t += 1;
     lr_t = bprx_adam_lr_t(h);
   }
-  h->pend_lr = lr_t;
+  h->step.lr_t = lr_t;                                     // (bprx_step_lr)
   const AfDrop d = af_drop(S, S->step, true);
   S->step += 1;
   int rc;

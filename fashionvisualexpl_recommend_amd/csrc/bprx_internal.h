@@ -67,16 +67,62 @@ struct DevPool {
 struct AcfState;   // bprx_acf.hip
 struct AfState;    // bprx_attentive.hip
 
+constexpr int ADAM_HIST = 8192;   // lazy adam_tf23: steps of lr_t the device ring lr_hist holds (a power of two)
+constexpr int IX_RMAX = 8192;     // k_index_seg: items an owner workgroup can own (LDS counters)
+constexpr int IX_LPAD = 4;        // chunk-list slots of an owner beyond one per item (hot items' extra chunks; more: overflow list)
+
+// What ONE BPRMF / VBPR training step does: every decision about its form, made once by plan_step (below the handle) from the
+// configuration, the create-time policies and the state carried from step to step.  bprx_step_begin_sparse commits it to
+// bprx_handle::step; bprx_step_begin_dense, bprx_step_end and every launcher read it and decide nothing themselves.
+struct StepPlan {
+  int error;                      // 0, or why there is no step: PLAN_E_EMPTY (nothing else is filled in)
+  int64_t B;                      // triplets (0: the empty batch of a replicated rank)
+  const int32_t *user, *pos, *neg;   // the step's index buffers (nullptr for the empty batch)
+  // optimizer
+  int64_t adam_t;                 // optimizer.iterations of this step (sgd: unchanged)
+  float lr_t;                     // sgd: lr; adam_tf23: the bias-corrected step size at adam_t (bprx_step_lr)
+  bool adam_sync_first;           // lazy Adam: the lr_t ring would wrap, every row is caught up to adam_t - 1 first
+  bool catchup, catchup_aside;    // lazy Adam: k_adam_catchup runs; on the side stream beside the forward projection
+  // form of the step
+  bool list_mode;                 // touched-item list: both projections over the batch's DISTINCT items only
+  bool item_mode;                 // item-side gradients by per-item occurrence segments (k_item_seg); false: global float
+                                  //    atomics into the staging tables + claim-apply
+  bool seg_users;                 // segment-mode step whose users are finished inside k_triplet_seg (sgd, gradients not
+                                  //    exported): no apply pass for them
+  bool mask;                      // segment mode: the projections leave out the rows of the items the batch does not touch
+                                  //    (where a masked kernel form exists: proj_fwd_takes_mask / proj_bwd_takes_mask)
+  bool index_first;               // the index pass runs before the forward projection (list, mask), otherwise after it
+  bool row_count;                 // atomic staging / list mode: the index pass is k_row_count (neither: no index pass)
+  bool idx8;                      // the index pass scans the sampler's byte planes of this very batch
+  int idx_kind;                   // bprx_index_pass_kind: of this step if it is a segment-mode step, else of the last one
+  bool project, fwd;              // VBPR, no bprx_step_project before: [E|Bp]^T images are made; P is projected (not current)
+  int fast, fastU, fastI;         // sgd: rows used by exactly one triplet are updated in place; per side (off for exported rows)
+  bool use_list;                  // both sides fast: the apply pass walks the list of the batch's SHARED rows
+  bool list_reset_cnt;            // list mode: k_cast_W_rows resets cntI (no exclusive-row fast path on the item side)
+  bool w_memset, leaves_w_dirty;  // fp32 W is cleared before the triplet kernel; this step leaves it not all-zero
+  int64_t list_bound;             // list mode: host-side bound of the list length, min(2B, I)
+  int32_t *list_cur, *list_next;  // list mode: ilist_n cursor of this step, and the one k_dense_update clears for the next
+  int seg_cur;                    // segment mode: cursor triple (seg_cursor + 3 * seg_cur) this step's kernels read
+  int ix_R, ix_nown;              // k_index_seg: items per owner workgroup, owner workgroups
+  int seg_lead_over;              // slots of the owners' regions in seg_lead (the overflow list follows)
+  int slist_cur;                  // slist_n cursor of this step
+  int SK_step;                    // split-K slabs written by this step's backward projection (<= SK)
+  bool fused_reduce;              // bprx_step: k_dense_update sums the split-K slabs itself (no k_reduce_parts)
+  int apply;                      // APPLY_*: what bprx_launch_apply does
+  int fk, ek;                     // row kinds [fk, ek) of the apply pass (0 users, 1 / 2 positive / negative items)
+  bool dense_launch;              // bprx_step_end: k_dense_update runs (GradFashion: only for its housekeeping)
+};
+enum { PLAN_E_EMPTY = 1 };           // an empty batch on a handle without exported gradients
+enum { APPLY_NONE = 0, APPLY_SGD_LIST, APPLY_SGD, APPLY_ADAM_LAZY, APPLY_ADAM_SWEEP };
+
 struct bprx_handle {
   bprx_config cfg;
   bprx_tables t;
   bool bound;
-  int64_t adam_t;          // optimizer.iterations
   // lazy-exact adam_tf23 (bprx_sparse.hip): rows are brought up to date when they are read
   bool adam_lazy;
   int32_t *lastU, *lastI;  // [U], [I] step up to which the row (Gu/Tu resp. Gi/Bi and their slots) is current
   float *lr_hist;          // ring of the last ADAM_HIST steps' lr_t
-  int64_t adam_synced;     // every row is current at least up to this step
   char err[512];
 
   // ---- scratch owned by the handle (device): every pointer below that the library allocates belongs to `mem` ----
@@ -86,10 +132,35 @@ struct bprx_handle {
   float *lossb;                   // [max_batch] per-triplet loss (data + per-occurrence regularisation)
   double *loss_acc;               // [BPRX_DENSE_BLOCKS] per-block partial sums of ||E||^2+||Bp||^2 (k_dense_update)
   int dense_blocks;               // blocks of the last k_dense_update launch
-  bool proj_fresh;                // bprx_step_project already ran for the coming step
-  bool et_valid;                  // the bf16/fp8 image Et matches the bound E/Bp (cleared by every dense update, bind, tables_dirty)
-  bool p_valid;                   // P holds the projections of ALL items for the bound E/Bp (bprx_score_block reuses it)
-  bool fused_reduce;              // bprx_step: k_dense_update sums the split-K slabs itself (no k_reduce_parts)
+
+  // ---- the step in flight ----
+  StepPlan step;                  // committed by bprx_step_begin_sparse; read-only until the next one (the launchers, bprx_step_lr,
+                                  //    bprx_index_pass_kind / bprx_proj_mask_kind; ACF / AttentiveFashion steps record lr_t only)
+  int step_stage;                 // 0 = none, 1 = bprx_step_begin_sparse done (user gradients final), 2 = whole _begin done
+
+  // ---- carried from step to step (each with its writers; DESIGN §4 "How a step is planned") ----
+  int64_t adam_t;                 // optimizer.iterations: commit_plan (+1 per adam_tf23 step), bprx_set_adam_step
+  int64_t adam_synced;            // lazy Adam: every row is current at least up to this step: bprx_launch_adam_sync / _reset
+  bool proj_fresh;                // bprx_step_project already ran for the coming step: set there, cleared by commit_plan
+  bool et_valid;                  // the bf16/fp8 image Et matches the bound E/Bp: set by bprx_launch_cast_Et, by bprx_step_end for
+                                  //    the images k_dense_update wrote; cleared by bprx_step_end, bind, tables_dirty
+  bool p_valid;                   // P holds the projections of ALL items for the bound E/Bp: set by bprx_step_project /
+                                  //    bprx_score_block, cleared by bprx_step_end, bind, tables_dirty
+  bool absmax_valid;              // fp8: qs[2 + qs_slot] already holds max|E,Bp| of the bound values: set by bprx_step_end (left
+                                  //    there by k_dense_update), consumed by bprx_launch_cast_Et
+  int qs_slot;                    // fp8: the max|E,Bp| slot of the next k_cast_Et8: flipped by bprx_launch_cast_Et (also run
+                                  //    outside steps: bprx_score_pairs / _block, bprx_step_project)
+  bool W_dirty;                   // the fp32 W table is not all-zero (left so by a dense fp32-feature step): commit_plan
+  int list_slot;                  // ilist_n cursor of the next list-mode step: flipped by bprx_step_end after a list-mode step
+  int seg_slot;                   // seg_cursor triple of the next segment-mode step: flipped by commit_plan
+  int slist_slot;                 // slist_n cursor of the next shared-row-list step: flipped by commit_plan
+  // byte planes of the item ids of the NEXT step's batch, written by the library's own device samplers (bprx_sample_*_h) when
+  // own8 = id >> idx8_shift (the owner workgroup of k_index_seg, 2^shift items each: at most 256 owners), loc8 = the rest; [2 * max_batch]
+  // each (positives, then negatives).  idx8_pos / idx8_neg / idx8_B: the buffers and batch size they belong to; idx8_n: triplets
+  // filled so far (-1: invalid): written by the samplers; consumed (idx8_n = 0) by commit_plan, whatever the step does with them.
+  const int32_t *idx8_pos, *idx8_neg;
+  int64_t idx8_B, idx8_n;
+
   int32_t *errflag;               // device-side deferred error (index out of range)
   // VBPR projection state
   int PS;                         // padded row stride of P/W/Et: 16*ceil((d+1)/16)
@@ -106,13 +177,9 @@ struct bprx_handle {
   int SK;
   float *qs;                      // fp8 features: [1] = 1/(feat_scale*sE) for P, [2], [3] = max|E,Bp| bits (uint32, atomicMax;
                                   //               two slots used alternately, the idle one is cleared by k_cast_Et8)
-  int qs_slot;
-  bool absmax_valid;              // fp8: qs[2 + qs_slot] already holds max|E,Bp| of the bound values (left by k_dense_update)
   int fast_rows;                  // sgd: rows used by exactly one triplet of the batch are updated in place
   int32_t *cntU, *cntI;           // [U], [I] row multiplicities of the current batch (all-zero between steps)
   int seg_policy;                 // 0 never, 1 per step (2B >= I), 2 always (env BPRX_ITEM_MODE)
-  int item_mode;                  // this step: 1: item-side gradients by per-item occurrence segments (k_item_seg), 0: global
-                                  //    float atomics into the staging tables + claim-apply
   // Occurrence segments (segment mode), built by ONE launch of k_index_seg (bprx_sparse.hip): workgroup w OWNS the item
   // range [w*R, (w+1)*R): it scans all 2B item occurrences, counts and ranks those of its items in LDS (no global atomics),
   // prefix-sums its counts, reserves the entries with one cursor atomic and lists its items' chunks for k_item_seg.
@@ -121,11 +188,8 @@ struct bprx_handle {
   int32_t *seg_ptr;               // [I] start of the item's segment in seg_ent
   int32_t *seg_cursor;            // [6] two (overflow entries, overflow chunks, listed users) cursor triples used by alternate
                                   //     steps: an index pass clears the triple of the NEXT step
-  int seg_slot;                   // cursor pair of the next segment-mode step
-  int seg_cur_slot;               // cursor pair of the step in flight
   void *seg_lead;                 // int4 [seg_lead_cap] {item, first entry, entries of the chunk, entries of the item}: k_item_seg's work list
   int64_t seg_lead_cap;
-  int seg_lead_over;              // this step: slots of the owners' regions (the overflow list follows)
   int64_t seg_ent_cap;            // entries allocated in seg_ent
   // user side of a segment-mode sgd step: k_triplet_seg sums the runs of equal users in LDS and adds the run sums to the staging
   // rows; finishing lane groups at the front of k_item_seg's grid apply the totals (no apply launch).  k_item_seg's item groups,
@@ -133,23 +197,12 @@ struct bprx_handle {
   int32_t *uslot_of;              // [U] batch position of the user's first run head = the user's slot (valid for users of the batch)
   int32_t *ulist;                 // [max_batch] the batch's users (first-run order): walked by k_item_seg's finishing groups
   float *uold;                    // [max_batch][k + d] pre-update [gamma_u | theta_u] of the slot's user
-  // byte planes of the item ids of the NEXT step's batch, written by the library's own device samplers (bprx_sample_*_h) when
-  // own8 = id >> idx8_shift (the owner workgroup of k_index_seg, 2^shift items each: at most 256 owners), loc8 = the rest; [2 * max_batch]
-  // each (positives, then negatives).  idx8_pos / idx8_neg / idx8_B: the buffers and batch size they belong to; idx8_n: triplets
-  // filled so far (-1: invalid); consumed (idx8_n = 0) by the step that uses them.
-  uint8_t *own8, *loc8;
+  uint8_t *own8, *loc8;           // the sampler's byte planes (idx8_* above)
   int idx8_shift;                 // own8 = id >> idx8_shift (8: loc8 holds bytes; 9..13, num_items up to 2 M: loc8 holds uint16 id & (2^shift - 1))
-  const int32_t *idx8_pos, *idx8_neg;
-  int64_t idx8_B, idx8_n;
-  bool idx8_use;                  // this step's index pass scans the byte planes
-  int idx_kind;                   // bprx_index_pass_kind
   // Untouched items' feature rows out of both streaming projections (segment-mode steps): the index pass runs BEFORE
   // the forward projection and both projections read seg_cnt as the per-item "occurs in this batch" mask.
   int proj_mask;                  // env BPRX_PROJ_MASK, read at create: 0 never, 1 (default) bf16 features up to nine column tiles, 2 every masked form
-  bool step_masked;               // this step: the index pass has already run and the projections take the mask
-  bool fwd_masked, bwd_masked;    // the last launch of bprx_launch_proj_fwd / _bwd took it (set by the launchers)
-  int mask_kind;                  // bprx_proj_mask_kind
-  bool idx8_ready(const int32_t *pos, const int32_t *neg, int64_t B) const {
+  bool idx8_ready(bool item_mode, const int32_t *pos, const int32_t *neg, int64_t B) const {
     return item_mode && own8 && B > 0 && idx8_n == B && idx8_B == B && idx8_pos == pos && idx8_neg == neg && B % 16 == 0;
   }
   int32_t *hot_done;              // [I] finished chunks of a hot item (k_item_seg), all-zero between steps
@@ -157,24 +210,12 @@ struct bprx_handle {
                                   //     the expected occupancy each) + 2 * max_batch for the owners that overflow theirs
   // touched-item list (sparse batches, 2B < I): both projections run over the batch's DISTINCT items only
   int list_policy;                // 0 never, 1 per step (2B < I), 2 always (env BPRX_LIST_MODE)
-  int list_mode;                  // this step
   int32_t *ilist;                 // [min(2*max_batch, I)] distinct items of the batch, in arrival order (k_row_count)
   int32_t *ilist_n;               // [2] their number, two cursors used by alternate list-mode steps: k_dense_update (the
                                   //     last kernel of a step) clears the cursor the NEXT list-mode step appends through
-  int list_slot;                  // cursor of the next list-mode step
-  int32_t *list_cur;              // ilist_n + slot of the step in flight
-  int64_t list_bound;             // host-side bound of the list length of the step in flight: min(2B, I)
-  bool list_reset_cnt;            // list mode: k_cast_W_rows resets cntI (no exclusive-row fast path on the item side)
-  bool W_dirty;                   // the fp32 W table is not all-zero (left so by a dense fp32-feature step)
   int32_t *slist, *slist_n;       // sgd fast path: list of the batch's SHARED rows (kind << 30 | row), two alternating cursors
-  int slist_slot;
-  int SK_step;                    // split-K slabs written by this step's backward projection (<= SK)
   int num_cu;                     // compute units of the device (balanced forward grid)
   int fwd_variant;                // 0: the plain forward kernel (env BPRX_FWD_VARIANT, read at create), else the per-shape policy
-  int64_t pending_B;              // B of the step between _begin and _end (0 = none)
-  int pending_stage;              // 1 = bprx_step_begin_sparse done (user gradients final), 2 = whole _begin done
-  const int32_t *pend_u, *pend_i, *pend_j;   // the pending step's index buffers (bprx_step_begin_dense)
-  float pend_lr;
   float neg_bias_reg;             // factor of reg on the negative item's bias: 0.1 (VBPR.py:125), 1.0 for GradFashion
   // GradFashion (bprx_bind_factored, bprx_factored.hip): E / Bp of t are E_eff / Bp_eff, composed from the factors fx
   bool factored;
@@ -238,13 +279,12 @@ struct BprxProfScope {
 // sparse part (bprx_sparse.hip)
 int bprx_launch_score(bprx_handle *h, const int32_t *u, const int32_t *i, int64_t B, const float *Prow,
                       int p_by_pair, float *x, hipStream_t s);
-int bprx_launch_index_pass(bprx_handle *h, const int32_t *u, const int32_t *i, const int32_t *j, int64_t B, hipStream_t s);
-int bprx_launch_triplet_grad(bprx_handle *h, const int32_t *u, const int32_t *i, const int32_t *j, int64_t B,
-                             hipStream_t s);
-int bprx_launch_item_seg(bprx_handle *h, const int32_t *i, const int32_t *j, int64_t B, float lr_t, hipStream_t s);
-int bprx_launch_apply(bprx_handle *h, const int32_t *u, const int32_t *i, const int32_t *j, int64_t B,
-                      float lr_t, hipStream_t s);
-int bprx_launch_dense_update(bprx_handle *h, float lr_t, hipStream_t s);
+// the step's launchers read the plan of the step in flight (h->step) and decide nothing themselves
+int bprx_launch_index_pass(bprx_handle *h, const StepPlan &p, hipStream_t s);
+int bprx_launch_triplet_grad(bprx_handle *h, const StepPlan &p, hipStream_t s);
+int bprx_launch_item_seg(bprx_handle *h, const StepPlan &p, hipStream_t s);
+int bprx_launch_apply(bprx_handle *h, const StepPlan &p, hipStream_t s);
+int bprx_launch_dense_update(bprx_handle *h, const StepPlan &p, hipStream_t s);
 // One adam_tf23 step (sparse rule, adam_elem) of up to four whole tables from their staging gradients, which return to zero,
 // and the clearing of up to two claim-mark arrays, in ONE launch of k_adam_sweep: the sweep of every model and of
 // bprx_adam_rows.  A segment with n == 0 (a flag array with nflag == 0) costs nothing.
@@ -252,11 +292,9 @@ struct AdamSweepSeg { float *p, *m, *v, *g; size_t n; };
 struct AdamSweepAll { AdamSweepSeg seg[4]; uint32_t *flag[2]; size_t nflag[2]; };
 int bprx_launch_adam_sweep(bprx_handle *h, const AdamSweepAll &sw, float lr_t, hipStream_t s);
 int bprx_launch_fill_i32(bprx_handle *h, int32_t *p, size_t n, int32_t v, hipStream_t s);
-int bprx_launch_adam_catchup(bprx_handle *h, const int32_t *u, const int32_t *i, const int32_t *j, int64_t B, float lr_t,
-                             hipStream_t s);
+int bprx_launch_adam_catchup(bprx_handle *h, const StepPlan &p, hipStream_t s);
 int bprx_launch_adam_sync(bprx_handle *h, int64_t t, hipStream_t s);
 int bprx_launch_adam_reset(bprx_handle *h, int64_t t, hipStream_t s);
-int bprx_adam_hist(void);
 int bprx_launch_loss_reduce(bprx_handle *h, int64_t B, float *loss_out, hipStream_t s);
 int bprx_launch_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s);
 int bprx_launch_score_gemm(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s);
@@ -270,7 +308,11 @@ int bprx_launch_cast_Et(bprx_handle *h, hipStream_t s);
 // all zeros).  nullptr: every row.
 int bprx_launch_proj_fwd(bprx_handle *h, const int32_t *rows, int64_t nrows, const int32_t *nrows_dev, int scatter, float *Pout,
                          hipStream_t s, const int32_t *occ = nullptr);
-int bprx_launch_proj_bwd(bprx_handle *h, int64_t B, hipStream_t s, const int32_t *occ = nullptr);
+int bprx_launch_proj_bwd(bprx_handle *h, const StepPlan &p, hipStream_t s);
+// whether the kernel form the whole-table forward / backward projection takes for this handle's shape has a masked variant
+// (bprx_proj.hip, next to the form tables): what the launchers do with `occ`, and what bprx_proj_mask_kind reports
+bool bprx_proj_fwd_takes_mask(const bprx_handle &h);
+bool bprx_proj_bwd_takes_mask(const bprx_handle &h);
 // GradFashion factors (bprx_factored.hip)
 int bprx_launch_fact_compose(bprx_handle *h, hipStream_t s);                // E_eff | Bp_eff from the factors
 int bprx_launch_fact_update(bprx_handle *h, float lr_t, hipStream_t s);     // chain rule from dEp, optimizer, loss partials
@@ -290,14 +332,121 @@ void bprx_af_invalidate(bprx_handle *h);
 void bprx_af_free(bprx_handle *h);
 
 // ---- host helpers ----
-// Adam's bias-corrected step size at optimizer.iterations = h->adam_t (the caller decides when adam_t advances)
-static inline float bprx_adam_lr_t(const bprx_handle *h) {
-  const float t = (float)h->adam_t;
-  return h->cfg.lr * sqrtf(1.0f - powf(h->cfg.beta2, t)) / (1.0f - powf(h->cfg.beta1, t));
+// Adam's bias-corrected step size at optimizer.iterations = it
+static inline float bprx_adam_lr_at(const bprx_config &c, int64_t it) {
+  const float t = (float)it;
+  return c.lr * sqrtf(1.0f - powf(c.beta2, t)) / (1.0f - powf(c.beta1, t));
 }
+// ... at h->adam_t (the caller decides when adam_t advances)
+static inline float bprx_adam_lr_t(const bprx_handle *h) { return bprx_adam_lr_at(h->cfg, h->adam_t); }
 // workgroups for `work` items at `per_block` each: at least one, at most `cap`
 static inline unsigned bprx_blocks(int64_t work, int64_t per_block, int64_t cap = INT32_MAX) {
   int64_t g = (work + per_block - 1) / per_block;
   if (g > cap) g = cap;
   return (unsigned)(g < 1 ? 1 : g);
+}
+
+// ---- how a step is planned ----
+// The one place that decides what a BPRMF / VBPR step launches.  Pure: reads the configuration, the create-time policies and the
+// carried state of `h`, makes no HIP call and writes nothing.  fused_reduce: the caller is bprx_step (no all-reduce between the
+// backward projection and the dense update).  The pointers are compared (byte planes) and kept, never followed.
+inline StepPlan plan_step(const bprx_handle &h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B,
+                          bool fused_reduce = false) {
+  StepPlan p = {};
+  const bprx_config &c = h.cfg;
+  const bool vb = c.model == BPRX_MODEL_VBPR, sgd = c.optimizer == BPRX_OPT_SGD, lazy = !sgd && h.adam_lazy;
+  const bool exU = c.flags & BPRX_FLAG_EXPORT_USER_GRAD, exI = c.flags & BPRX_FLAG_EXPORT_ITEM_GRAD;
+  const int64_t I = c.num_items;
+  const bool bf = c.feat_dtype != BPRX_F_FP32;            // bf16 W image (bf16 and fp8 features)
+  // A rank of a replicated-user multi-GPU step whose item shard holds no positive of this global batch: it contributes an
+  // empty message and a zero dense gradient, but takes part in every collective and takes the same optimizer step as the
+  // other replicas (bprx_pack_user_msg -> count 0, bprx_step_begin_dense -> dE|dBp = 0, bprx_apply_user_msgs, bprx_step_end).
+  if (B == 0 && !exU && !exI) { p.error = PLAN_E_EMPTY; return p; }
+  p.B = B;
+  if (B) { p.user = user; p.pos = pos; p.neg = neg; }
+  p.adam_t = h.adam_t;
+  p.lr_t = c.lr;
+  if (!sgd) {
+    p.adam_t = h.adam_t + 1;
+    p.lr_t = bprx_adam_lr_at(c, p.adam_t);
+    // the ring holds lr_s of the last ADAM_HIST steps: before it would wrap, everything is caught up (amortised: one
+    // sweep per ~8000 steps); then the rows of THIS batch are brought to step t-1 for the forward pass (the empty batch: a
+    // zero-row catch-up that records lr_t of this step)
+    p.adam_sync_first = lazy && p.adam_t - h.adam_synced >= ADAM_HIST - 2;
+    p.catchup = lazy;
+  }
+  p.fused_reduce = fused_reduce && !h.factored;          // (GradFashion's chain rule reads the summed gradient from dEp)
+  p.idx_kind = h.step.idx_kind;
+  p.seg_cur = h.step.seg_cur; p.seg_lead_over = h.step.seg_lead_over;   // (as the last segment-mode step left them)
+  p.slist_cur = h.slist_slot;
+  p.SK_step = B ? h.SK : h.step.SK_step;                 // (no backward projection: the slabs are the last step's)
+  p.leaves_w_dirty = h.W_dirty;
+  // GradFashion: bprx_launch_fact_update has moved the factors, composed E_eff / Bp_eff and left the loss partials;
+  // k_dense_update only does the step's housekeeping (nothing to do: no launch)
+  p.dense_launch = vb && (!h.factored || c.feat_dtype == BPRX_F_BF16);
+  if (B == 0) return p;                                  // no list, no segments, no mask; the dense half zeroes dEp
+
+  // list mode: both projections over the batch's distinct items only (needs the index pass BEFORE the forward projection)
+  p.list_mode = vb && !h.proj_fresh && (h.list_policy == 2 || (h.list_policy == 1 && 2 * B < I));
+  p.item_mode = !p.list_mode && (h.seg_policy == 2 || (h.seg_policy == 1 && 2 * B >= I));
+  p.seg_users = p.item_mode && sgd && !exU;
+  p.dense_launch = p.dense_launch || p.list_mode;
+  // every item row of a segment-mode step is finished by k_item_seg, which gathers PRE-update user rows after k_triplet_grad:
+  // the user side may therefore not be updated in place either (staging + k_apply_sgd)
+  p.fast = p.item_mode ? 0 : h.fast_rows;
+  p.fastU = p.fast && !exU;
+  p.fastI = p.fast && !exI;
+  // shared-row list: both sides on the exclusive-row fast path (sgd, atomic staging, no exported gradients)
+  p.use_list = h.slist && p.fastU && p.fastI;
+  p.row_count = !p.item_mode && (h.fast_rows || p.list_mode);
+  // byte planes of this very batch, left by bprx_sample_*_h
+  p.idx8 = h.idx8_ready(p.item_mode, pos, neg, B);
+  if (p.list_mode) {
+    p.list_bound = 2 * B < I ? 2 * B : I;
+    p.list_cur = h.ilist_n + h.list_slot; p.list_next = h.ilist_n + (h.list_slot ^ 1);
+    p.list_reset_cnt = !(h.fast_rows && !exI);
+    // few rows: fewer item splits (each split writes a D x PS fp32 slab that the dense update reads back)
+    if (bf) { const int sk = (int)((p.list_bound + 127) / 128); p.SK_step = sk < 1 ? 1 : (sk > h.SK ? h.SK : sk); }
+  }
+  // the (ALU-bound) lazy-Adam catch-up runs on the side stream beside the (HBM-bound) forward projection
+  p.catchup_aside = lazy && h.side && !h.proj_fresh && !p.list_mode && !h.p_valid;
+  p.project = vb && !h.proj_fresh;
+  p.fwd = p.project && !h.p_valid;
+  // Segment mode: k_index_seg depends on the index arrays only, so it runs BEFORE the forward projection and both projections
+  // skip the feature rows of the items this batch does not touch (seg_cnt[item] == 0: nobody reads that row of P in this step
+  // and p_valid stays false; its W row is all zeros).  Everything the index pass writes -- the Wb rows it zeroes, cntU / ulist /
+  // uslot_of, seg_rank / seg_cnt / seg_ptr, the chunk list and both cursor triples -- was last read by the previous step's
+  // kernels (k_triplet_seg, k_item_seg, the backward projection) on this same stream: stream order is the only ordering there
+  // is today and it still holds.  The side stream's catch-up touches none of these buffers (rows, slots, lastU / lastI, lr_hist).
+  p.mask = p.project && !p.list_mode && p.item_mode && !h.p_valid &&
+           (h.proj_mask == 2 ? bf : (h.proj_mask == 1 && c.feat_dtype == BPRX_F_BF16 && h.PS / 16 <= 9));
+  p.index_first = p.list_mode || p.mask;
+  if (p.item_mode) {
+    // k_index_seg: one owner workgroup per CU, more when a range would not fit LDS; the byte planes fix 2^shift items per owner
+    p.idx_kind = p.idx8 ? 2 : 1;
+    int64_t nown = h.num_cu > 0 ? h.num_cu : 256;
+    if (nown > 1024) nown = 1024;
+    if ((I + nown - 1) / nown > IX_RMAX) nown = (I + IX_RMAX - 1) / IX_RMAX;
+    if (nown > I) nown = I;
+    p.ix_R = p.idx8 ? 1 << h.idx8_shift : (int)((I + nown - 1) / nown);
+    p.ix_nown = (int)((I + p.ix_R - 1) / p.ix_R);
+    p.seg_lead_over = p.ix_nown * (p.ix_R + IX_LPAD);
+    p.seg_cur = h.seg_slot;
+  }
+  // W (fp32) must be all-zero before the triplet kernel.  bf16 features: k_cast_W re-zeroes it while converting and k_item_seg
+  // re-zeroes the rows it folds in.  Dense form with fp32 features: W is consumed in place and cleared at the next step; list
+  // mode returns its rows to zero itself (k_cast_W_rows) and only needs the memset after such a step
+  p.leaves_w_dirty = vb && !p.list_mode && !bf;
+  p.w_memset = p.leaves_w_dirty || (vb && h.W_dirty);
+  // apply pass, row kinds [fk, ek): fk = 1 skips the user rows (exported to the caller, or finished by k_triplet_seg); ek = 1
+  // skips the item rows (finished in place by k_item_seg, or exported: their owner takes their steps)
+  p.ek = (p.item_mode || exI) ? 1 : 3;
+  if (sgd) {
+    p.fk = (exU || p.item_mode) ? 1 : 0;
+    p.apply = p.seg_users ? APPLY_NONE : (p.use_list ? APPLY_SGD_LIST : APPLY_SGD);
+  } else {
+    p.fk = exU ? 1 : 0;                                  // replicated multi-GPU: users via bprx_apply_user_msgs
+    p.apply = lazy ? APPLY_ADAM_LAZY : APPLY_ADAM_SWEEP;  // lazy: touched rows only, everything else is replayed later
+  }
+  return p;
 }

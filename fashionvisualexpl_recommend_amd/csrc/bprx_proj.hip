@@ -1307,28 +1307,33 @@ void launch_v10(bprx_handle *h, int64_t nrows, float *Pout, hipStream_t s, int n
 //   feat_dim not a multiple of 256 (512 for fp8)    k_proj_fwd_bf16 (plain)             test_forward_whole_table[oddD-*, plain-*]; test_gpu_parity
 //   row list (bprx_score_pairs, list mode)          launch_fwd_rows / f8s over the list test_forward_row_list[split / mt1 / mt2 / mt4 / f8s_rows-*]
 //   fp32 features                                   k_proj_fwd_f32_mfma, k_proj_fwd_f32 test_forward_whole_table[fp32-*], test_forward_row_list[fp32-*]
+// the form of the whole-table forward pass (the table above): the plain kernel, the one-pass wide-fp8 kernel, or v10
+inline bool fwd_form_plain(const bprx_handle &h) {
+  const int Deq = h.cfg.feat_dtype == BPRX_F_FP8 ? h.cfg.feat_dim / 2 : h.cfg.feat_dim;
+  return h.fwd_variant == 0 || Deq % 256 != 0;
+}
+inline bool fwd_form_f8s(const bprx_handle &h) {
+  return h.PS / 16 >= 10 && h.cfg.feat_dtype == BPRX_F_FP8 && h.EtS && h.cfg.feat_dim % 256 == 0;
+}
+
 template <int NT>
 int launch_fwd_nt(bprx_handle *h, const int32_t *rows, int64_t nrows, float *Pout, hipStream_t s, const int32_t *occ) {
   constexpr int MTD = NT <= 9 ? 2 : 1;
   const bool f8 = h->cfg.feat_dtype == BPRX_F_FP8;
   const int Deq = f8 ? h->cfg.feat_dim / 2 : h->cfg.feat_dim;
   const float *pscale = h->qs + 1;
-  const bool plain = h->fwd_variant == 0 || Deq % 256 != 0 || rows;
-  h->fwd_masked = false;                                // only v10 takes the mask: the other forms project every row
-  if (!plain) {
+  if (!fwd_form_plain(*h) && !rows) {
     if constexpr (NT >= 10) {
-      if (f8 && h->EtS && h->cfg.feat_dim % 256 == 0) {
+      if (fwd_form_f8s(*h)) {
         launch_f8s<NT>(h, nullptr, nrows, nullptr, 0, Pout, s, 1);
         return 0;
       }
       // bf16: column ranges of nine tiles, the last one right-aligned: ranges may overlap by some tiles, which are then computed and
       // stored twice, identically (F is read once per pass: two passes at d = 256)
       for (int c0 = 0; c0 < NT; c0 += 9) launch_v10<9>(h, nrows, Pout, s, (c0 + 9 <= NT ? c0 : NT - 9) * 16, occ);
-      h->fwd_masked = occ != nullptr;
       return 0;
     } else {
       launch_v10<NT>(h, nrows, Pout, s, 0, occ);
-      h->fwd_masked = occ != nullptr;
       return 0;
     }
   }
@@ -1355,14 +1360,15 @@ void launch_bwd3(dim3 grid, hipStream_t s, const uint16_t *Ft, int nrows, int D,
 // backward over the touched-item list (list mode): v3 kernel in ROWS form, 2 tiles in flight; `bound` = host-side bound of
 // the list length
 template <int NT>
-int launch_bwd_rows(bprx_handle *h, int64_t bound, hipStream_t s) {
+int launch_bwd_rows(bprx_handle *h, const StepPlan &p, hipStream_t s) {
+  const int64_t bound = p.list_bound;
   const int D = h->cfg.feat_dim;
   const bool f8 = h->cfg.feat_dtype == BPRX_F_FP8;
   const bool w8 = D % 256 == 0 || f8;
-  dim3 g3(D / (w8 ? 256 : 128), h->SK_step);
+  dim3 g3(D / (w8 ? 256 : 128), p.SK_step);
 #define BWDR_LAUNCH(NW_, F8_)                                                                                            \
   launch_bwd3<NT, 32, NW_, 2, F8_, true, 1>(g3, s, (const uint16_t *)h->Ft, (int)bound, D, (const uint16_t *)h->Wb, h->PS,     \
-                                            h->part, 0, 0, 1, (const int32_t *)h->ilist, (const int32_t *)h->list_cur,        \
+                                            h->part, 0, 0, 1, (const int32_t *)h->ilist, (const int32_t *)p.list_cur,         \
                                             (const float *)h->W)
   if (f8) BWDR_LAUNCH(8, true);
   else if (w8) BWDR_LAUNCH(8, false);
@@ -1379,21 +1385,23 @@ int launch_bwd_rows(bprx_handle *h, int64_t bound, hipStream_t s) {
 //   D % 256 != 0 (bf16)                          4 waves (128 columns), 2 tiles in flight           small / odd feature widths
 // covered against an fp64 reference by tests/test_gpu_projections.py: test_backward_whole_table[pd3-* (1 / 2 / 3 / 4 / 25 tiles per
 // split), db2-fp8-*, ns2-*, w4-*, grid-* (SK % 8 != 0: no XCD remap), fp32-*], test_backward_row_list (launch_bwd_rows, ROWS)
+// rows of one of the SK item splits of the whole-table backward pass (whole 32-row tiles)
+inline int bwd_rows_per_split(const bprx_handle &h) {
+  const int rps = (h.cfg.num_items + h.SK - 1) / h.SK;
+  return (rps + 31) / 32 * 32;
+}
+
 template <int NT>
-int launch_bwd_nt(bprx_handle *h, hipStream_t s, const int32_t *occ) {
+int launch_bwd_nt(bprx_handle *h, const StepPlan &p, hipStream_t s) {
   const int D = h->cfg.feat_dim, I = h->cfg.num_items;
-  int rps3 = (I + h->SK - 1) / h->SK;
-  rps3 = (rps3 + 31) / 32 * 32;
+  const int rps3 = bwd_rows_per_split(*h);
   const size_t n4 = (size_t)I * h->PS / 4;
-  if (!h->item_mode)   // k_item_seg has already written Wb (bf16) itself
+  if (!p.item_mode)   // k_item_seg has already written Wb (bf16) itself
     hipLaunchKernelGGL(k_cast_W, dim3(1024), dim3(256), 0, s, h->W, (uint16_t *)h->Wb, n4);
   const bool f8 = h->cfg.feat_dtype == BPRX_F_FP8;
   const bool w8 = D % 256 == 0 || f8;                   // fp8: a 256-column tile row is one 256-B block row
   dim3 g3(D / (w8 ? 256 : 128), h->SK);
-  // masked form: a split's rows are one buffer resource (32-bit byte offsets: below 2 GB) and its row bits sit in LDS (at
-  // most 16 KB); splits beyond either bound (tables of tens of GB) sum every row
-  if (rps3 / 32 > 4096 || (size_t)rps3 * D * (h->cfg.feat_dtype == BPRX_F_FP8 ? 1 : 2) >= ((size_t)1 << 31)) occ = nullptr;
-  h->bwd_masked = occ != nullptr;
+  const int32_t *occ = p.mask && bprx_proj_bwd_takes_mask(*h) ? h->seg_cnt : nullptr;
 #define BWD3_ARGS (const uint16_t *)h->Ft, I, D, (const uint16_t *)h->Wb, h->PS, h->part, rps3, 0, 1, (const int32_t *)nullptr, \
                   (const int32_t *)nullptr, (const float *)nullptr, occ
 #define BWD3_GO(...)                                                                  \
@@ -1438,6 +1446,19 @@ int launch_bwd_nt(bprx_handle *h, hipStream_t s, const int32_t *occ) {
 
 }  // namespace
 
+// Which whole-table forms have a masked variant (`occ`): the launchers and bprx_proj_mask_kind both ask here.
+// Forward: only v10 takes the mask -- not the plain kernel, not the wide-fp8 one-pass kernel (a row list has no use for one).
+bool bprx_proj_fwd_takes_mask(const bprx_handle &h) {
+  return h.cfg.feat_dtype != BPRX_F_FP32 && !fwd_form_plain(h) && !fwd_form_f8s(h);
+}
+// Backward: a split's rows are one buffer resource (32-bit byte offsets: below 2 GB) and its row bits sit in LDS (at most
+// 16 KB); splits beyond either bound (tables of tens of GB) sum every row
+bool bprx_proj_bwd_takes_mask(const bprx_handle &h) {
+  const int rps = bwd_rows_per_split(h);
+  return h.cfg.feat_dtype != BPRX_F_FP32 &&
+         !(rps / 32 > 4096 || (size_t)rps * h.cfg.feat_dim * (h.cfg.feat_dtype == BPRX_F_FP8 ? 1 : 2) >= ((size_t)1 << 31));
+}
+
 // builds the tiled copy of F (see k_tile_F); called from bprx_bind_tables, synchronous
 int bprx_launch_tile_F(bprx_handle *h) {
   if (h->cfg.model != BPRX_MODEL_VBPR || h->cfg.feat_dtype == BPRX_F_FP32) return BPRX_OK;
@@ -1478,8 +1499,8 @@ int bprx_launch_cast_Et(bprx_handle *h, hipStream_t s) {
 
 int bprx_launch_proj_fwd(bprx_handle *h, const int32_t *rows, int64_t nrows, const int32_t *nrows_dev, int scatter, float *Pout,
                          hipStream_t s, const int32_t *occ) {
-  h->fwd_masked = false;
   if (nrows <= 0) return BPRX_OK;
+  if (rows || !bprx_proj_fwd_takes_mask(*h)) occ = nullptr;   // the other forms project every row
   BprxProfScope ps(h, BPRX_PHASE_PROJ_FWD, s);
   if (h->cfg.feat_dtype != BPRX_F_FP32) {
     const int NT = h->PS / 16;
@@ -1527,36 +1548,31 @@ int bprx_launch_proj_fwd(bprx_handle *h, const int32_t *rows, int64_t nrows, con
   return BPRX_OK;
 }
 
-// B: batch size of the step (bounds the touched-item list in list mode)
-int bprx_launch_proj_bwd(bprx_handle *h, int64_t B, hipStream_t s, const int32_t *occ) {
-  h->bwd_masked = false;
+// dE|dBp = F^T W of the step in flight: over its touched-item list (at most list_bound distinct items) or the whole table
+int bprx_launch_proj_bwd(bprx_handle *h, const StepPlan &p, hipStream_t s) {
   const int D = h->cfg.feat_dim, d = h->cfg.embed_d, I = h->cfg.num_items;
-  const int64_t bound = 2 * B < (int64_t)I ? 2 * B : (int64_t)I;     // list mode: at most 2B distinct items
-  h->SK_step = h->SK;
+  const int64_t bound = p.list_bound;
   if (h->cfg.feat_dtype != BPRX_F_FP32) {
     const int NT = h->PS / 16;
-    if (h->list_mode) {
-      // few rows: fewer item splits (each split writes a D x PS fp32 slab that the dense update reads back)
-      int sk = (int)((bound + 127) / 128);
-      h->SK_step = sk < 1 ? 1 : (sk > h->SK ? h->SK : sk);
+    if (p.list_mode) {
       {
         BprxProfScope ps(h, BPRX_PHASE_PROJ_BWD, s);
-#define CALL(N) launch_bwd_rows<N>(h, bound, s)
+#define CALL(N) launch_bwd_rows<N>(h, p, s)
         NT_SWITCH(NT, CALL)
 #undef CALL
       }
       BPRX_LAUNCH_CHECK(h, "k_proj_bwd_bf16_v3<rows>");
     } else {
       BprxProfScope ps(h, BPRX_PHASE_PROJ_BWD, s);
-#define CALL(N) launch_bwd_nt<N>(h, s, occ)
+#define CALL(N) launch_bwd_nt<N>(h, p, s)
       NT_SWITCH(NT, CALL)
 #undef CALL
       BPRX_LAUNCH_CHECK(h, "k_proj_bwd_bf16");
     }
-    if (h->fused_reduce) return BPRX_OK;              // k_dense_update sums the slabs (bprx_step, bf16 path)
+    if (p.fused_reduce) return BPRX_OK;               // k_dense_update sums the slabs (bprx_step, bf16 path)
     const size_t n = (size_t)D * h->PS;
     BprxProfScope ps(h, BPRX_PHASE_REDUCE, s);
-    hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->part, h->SK_step, D, d, h->PS, h->dEp,
+    hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->part, p.SK_step, D, d, h->PS, h->dEp,
                        h->cfg.feat_dtype == BPRX_F_FP8 ? 1.0f / h->cfg.feat_scale : 1.0f);
     BPRX_LAUNCH_CHECK(h, "k_reduce_parts");
   } else {
@@ -1564,13 +1580,13 @@ int bprx_launch_proj_bwd(bprx_handle *h, int64_t B, hipStream_t s, const int32_t
       BprxProfScope ps(h, BPRX_PHASE_PROJ_BWD, s);
       // a row LIST is split over the lane groups of a block (vector-ALU tiles; the fp64-matrix form of this sum was no faster:
       // 19 vs 17 us, removed); the whole-table sum keeps one block per k
-      if (h->list_mode && D % F32_KV == 0)
+      if (p.list_mode && D % F32_KV == 0)
         hipLaunchKernelGGL(k_proj_bwd_f32_tile, dim3(D / F32_KV, (unsigned)((d + 1 + 31) / 32)), dim3(F32_NRS * 32), 0, s, (const float *)h->t.F,
-                           (int)bound, D, h->W, d, h->PS, h->dEp, (const int32_t *)h->ilist, (const int32_t *)h->list_cur);
+                           (int)bound, D, h->W, d, h->PS, h->dEp, (const int32_t *)h->ilist, (const int32_t *)p.list_cur);
       else
-      hipLaunchKernelGGL(k_proj_bwd_f32, dim3(D), dim3(256), 0, s, (const float *)h->t.F, h->list_mode ? (int)bound : I, D, h->W, d,
-                         h->PS, h->dEp, h->list_mode ? (const int32_t *)h->ilist : (const int32_t *)nullptr,
-                         h->list_mode ? (const int32_t *)h->list_cur : (const int32_t *)nullptr);
+        hipLaunchKernelGGL(k_proj_bwd_f32, dim3(D), dim3(256), 0, s, (const float *)h->t.F, p.list_mode ? (int)bound : I, D, h->W, d,
+                           h->PS, h->dEp, p.list_mode ? (const int32_t *)h->ilist : (const int32_t *)nullptr,
+                           (const int32_t *)p.list_cur);
     }
     BPRX_LAUNCH_CHECK(h, "k_proj_bwd_f32");
   }

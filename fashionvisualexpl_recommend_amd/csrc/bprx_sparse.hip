@@ -13,6 +13,8 @@
 // gradients into zero-initialised dense staging tables (fp32 global atomics, one 16-B-per-lane row
 // segment per wave instruction); the optimizer kernels then apply each touched row exactly once and
 // re-zero the staging rows.
+#include <type_traits>
+
 #include "bprx_internal.h"
 
 namespace {
@@ -594,7 +596,6 @@ __global__ __launch_bounds__(256) void k_adam_sweep(AdamSweepAll a, float b1, fl
 // kernel); the host forces a full catch-up sweep before the ring would wrap.  Rows with m = v = 0 (never touched) are
 // fixed points of the recurrence and are skipped.
 // ------------------------------------------------------------------------------------------------------------
-constexpr int ADAM_HIST = 8192;
 
 struct AdamLazy {
   float b1, b2, eps;
@@ -1017,8 +1018,7 @@ __global__ __launch_bounds__(256) void k_score_block(SparseArgs a, int u0, int u
 // the user to the list of the batch's users, which the finishing lane groups of k_item_seg walk.
 // ------------------------------------------------------------------------------------------------------------
 constexpr int IX_T = 1024;        // threads of an index workgroup
-constexpr int IX_RMAX = 8192;     // items an owner workgroup can own (LDS counters)
-constexpr int IX_LPAD = 4;        // chunk-list slots of an owner beyond one per item (hot items' extra chunks; more: overflow list)
+// (IX_RMAX items an owner workgroup can own, IX_LPAD spare chunk-list slots per owner: bprx_internal.h, with the step planner)
 
 struct IndexSegArgs {
   const int32_t *user, *pos, *neg;
@@ -1646,12 +1646,8 @@ __global__ __launch_bounds__(IS_T) void k_item_seg(SparseArgs a, float *__restri
   }
 }
 
-// segment-mode step whose users are finished inside k_triplet_seg (sgd, gradients not exported): no apply pass for them
-inline bool seg_finishes_users(const bprx_handle *h) {
-  return h->item_mode && h->cfg.optimizer == BPRX_OPT_SGD && !(h->cfg.flags & BPRX_FLAG_EXPORT_USER_GRAD);
-}
-
-SparseArgs make_args(bprx_handle *h, const float *P) {
+// `p`: the plan of the step in flight; the score kernels (outside a step) read none of the fields it fills
+SparseArgs make_args(bprx_handle *h, const float *P, const StepPlan &p) {
   SparseArgs a;
   a.Gu = h->t.Gu; a.Gi = h->t.Gi; a.Bi = h->t.Bi; a.Tu = h->t.Tu;
   a.dGu = h->dGu; a.dGi = h->dGi; a.dBi = h->dBi; a.dTu = h->dTu;
@@ -1662,32 +1658,24 @@ SparseArgs make_args(bprx_handle *h, const float *P) {
   a.nb = h->neg_bias_reg;
   a.cntU = h->cntU; a.cntI = h->cntI;
   a.wGu = h->t.Gu; a.wGi = h->t.Gi; a.wBi = h->t.Bi; a.wTu = h->t.Tu;
-  a.fast = h->fast_rows;
-  a.fastU = h->fast_rows && !(h->cfg.flags & BPRX_FLAG_EXPORT_USER_GRAD);
-  a.fastI = h->fast_rows && !(h->cfg.flags & BPRX_FLAG_EXPORT_ITEM_GRAD);
+  a.fast = p.fast; a.fastU = p.fastU; a.fastI = p.fastI;
   a.lr = h->cfg.lr;
-  if (h->item_mode) {
-    // every item row is finished by k_item_seg, which gathers PRE-update user rows after k_triplet_grad: the user
-    // side may therefore not be updated in place either (staging + k_apply_sgd)
-    a.fastI = 0; a.fastU = 0; a.fast = 0;
-  }
   a.seg_rank = h->seg_rank; a.seg_ptr = h->seg_ptr; a.seg_ent = (int2 *)h->seg_ent; a.seg_ent_cap = (int)h->seg_ent_cap; a.hot_done = h->hot_done;
   a.seg_lead = (const int4 *)h->seg_lead; a.seg_lead_cap = (int)h->seg_lead_cap;
-  a.seg_nlead = h->seg_cursor ? h->seg_cursor + 3 * h->seg_cur_slot + 1 : nullptr;
-  a.ulist = h->ulist; a.ulist_n = h->seg_cursor ? h->seg_cursor + 3 * h->seg_cur_slot + 2 : nullptr;
+  a.seg_nlead = h->seg_cursor ? h->seg_cursor + 3 * p.seg_cur + 1 : nullptr;
+  a.ulist = h->ulist; a.ulist_n = h->seg_cursor ? h->seg_cursor + 3 * p.seg_cur + 2 : nullptr;
   a.nfin = 0;
-  a.seg_lead_over = h->seg_lead_over;
+  a.seg_lead_over = p.seg_lead_over;
   a.seg_cap = (int)h->seg_ent_cap;
   // where k_item_seg finds the pre-update user rows: a segment-mode sgd step finishes its users inside k_triplet_seg and
   // keeps their old rows in uold (entry key = user slot); otherwise the tables are untouched until the apply pass
-  if (seg_finishes_users(h)) { a.uG = h->uold; a.uT = h->uold + a.k; a.usG = a.usT = a.k + a.d; }
+  if (p.seg_users) { a.uG = h->uold; a.uT = h->uold + a.k; a.usG = a.usT = a.k + a.d; }
   else { a.uG = h->t.Gu; a.uT = h->t.Tu; a.usG = a.k; a.usT = a.d; }
-  // shared-row list: both sides on the exclusive-row fast path (sgd, atomic staging, no exported gradients)
-  a.use_list = (h->slist && a.fastU && a.fastI) ? 1 : 0;
+  a.use_list = p.use_list ? 1 : 0;
   a.reg_items = 1;
   a.wg_combine = 1;
   a.slist = h->slist;
-  a.slist_n = h->slist ? h->slist_n + h->slist_slot : nullptr;
+  a.slist_n = h->slist ? h->slist_n + p.slist_cur : nullptr;
   return a;
 }
 
@@ -1709,24 +1697,23 @@ int pick_group(int k, int d, bool vec) {
   return G;
 }
 
-#define DISPATCH_G(G, VEC, KERNEL, grid, s, ...)                                               \
-  do {                                                                                         \
-    if (VEC) {                                                                                 \
-      switch (G) {                                                                             \
-        case 8: hipLaunchKernelGGL((KERNEL<8, true>), grid, dim3(256), 0, s, __VA_ARGS__); break;   \
-        case 16: hipLaunchKernelGGL((KERNEL<16, true>), grid, dim3(256), 0, s, __VA_ARGS__); break; \
-        case 32: hipLaunchKernelGGL((KERNEL<32, true>), grid, dim3(256), 0, s, __VA_ARGS__); break; \
-        default: hipLaunchKernelGGL((KERNEL<64, true>), grid, dim3(256), 0, s, __VA_ARGS__); break; \
-      }                                                                                        \
-    } else {                                                                                   \
-      switch (G) {                                                                             \
-        case 8: hipLaunchKernelGGL((KERNEL<8, false>), grid, dim3(256), 0, s, __VA_ARGS__); break;   \
-        case 16: hipLaunchKernelGGL((KERNEL<16, false>), grid, dim3(256), 0, s, __VA_ARGS__); break; \
-        case 32: hipLaunchKernelGGL((KERNEL<32, false>), grid, dim3(256), 0, s, __VA_ARGS__); break; \
-        default: hipLaunchKernelGGL((KERNEL<64, false>), grid, dim3(256), 0, s, __VA_ARGS__); break; \
-      }                                                                                        \
-    }                                                                                          \
-  } while (0)
+// The one map from a group width to its instantiation: f(std::integral_constant<int, G>) for G = 8 / 16 / 32, else 64.
+template <typename F>
+void with_group(int G, F &&f) {
+  switch (G) {
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    default: f(std::integral_constant<int, 64>{}); break;
+  }
+}
+
+// KERNEL<G, VEC> in workgroups of 256 threads
+#define DISPATCH_G(G, VEC, KERNEL, grid, s, ...)                                                                 \
+  with_group(G, [&](auto g_) {                                                                                   \
+    if (VEC) hipLaunchKernelGGL((KERNEL<decltype(g_)::value, true>), grid, dim3(256), 0, s, __VA_ARGS__);        \
+    else hipLaunchKernelGGL((KERNEL<decltype(g_)::value, false>), grid, dim3(256), 0, s, __VA_ARGS__);           \
+  })
 
 inline bool vec_ok(const bprx_handle *h) {
   return h->cfg.embed_k % 4 == 0 && h->cfg.embed_d % 4 == 0;   // PS is always a multiple of 16
@@ -1998,8 +1985,8 @@ extern "C" int64_t bprx_user_msg_floats(const bprx_handle *h, int64_t cap) {
 extern "C" int bprx_pack_user_msg(bprx_handle *h, const int32_t *user, int64_t B, int64_t cap, float *msg, void *stream) {
   if (!h || !msg || B < 0 || cap <= 0 || (B > 0 && !user)) return BPRX_E_INVALID;
   if (!(h->cfg.flags & BPRX_FLAG_EXPORT_USER_GRAD)) BPRX_FAIL(h, BPRX_E_STATE, "pack_user_msg needs BPRX_FLAG_EXPORT_USER_GRAD");
-  if (!h->pending_stage) BPRX_FAIL(h, BPRX_E_STATE, "pack_user_msg outside a step (after bprx_step_begin[_sparse])");
-  if (B != h->pending_B) BPRX_FAIL(h, BPRX_E_INVALID, "pack_user_msg: B differs from the pending step's");
+  if (!h->step_stage) BPRX_FAIL(h, BPRX_E_STATE, "pack_user_msg outside a step (after bprx_step_begin[_sparse])");
+  if (B != h->step.B) BPRX_FAIL(h, BPRX_E_INVALID, "pack_user_msg: B differs from the pending step's");
   hipStream_t s = (hipStream_t)stream;
   const int k = h->cfg.embed_k, d = h->cfg.embed_d;
   const dim3 grid((unsigned)((B + 255) / 256));
@@ -2013,7 +2000,7 @@ extern "C" int bprx_pack_user_msg(bprx_handle *h, const int32_t *user, int64_t B
   BPRX_LAUNCH_CHECK(h, "k_pack_user_msg");
   const size_t nd = (h->cfg.flags & BPRX_FLAG_DENSE_ALLREDUCE) ? 0 : (size_t)h->cfg.feat_dim * (d + 1);
   if (nd) {
-    if (h->pending_stage < 2) BPRX_FAIL(h, BPRX_E_STATE, "the message carries dE|dBp: pack it after bprx_step_begin[_dense]");
+    if (h->step_stage < 2) BPRX_FAIL(h, BPRX_E_STATE, "the message carries dE|dBp: pack it after bprx_step_begin[_dense]");
     BPRX_HIP(h, hipMemcpyAsync(msg + msg_rows_end(h, cap), h->dEp, nd * sizeof(float), hipMemcpyDeviceToDevice, s));
   }
   return BPRX_OK;
@@ -2078,7 +2065,7 @@ extern "C" int bprx_sum_dense_parts(bprx_handle *h, const float *parts, int32_t 
 
 int bprx_launch_score(bprx_handle *h, const int32_t *u, const int32_t *i, int64_t B, const float *Prow, int p_by_pair,
                       float *x, hipStream_t s) {
-  SparseArgs a = make_args(h, h->cfg.embed_d ? (p_by_pair ? Prow : h->P) : nullptr);
+  SparseArgs a = make_args(h, h->cfg.embed_d ? (p_by_pair ? Prow : h->P) : nullptr, h->step);
   const bool vec = vec_ok(h);
   const int G = pick_group(a.k, a.d, vec);
   DISPATCH_G(G, vec, k_score, grid_for(B, G), s, a, u, i, B, p_by_pair, x);
@@ -2088,36 +2075,28 @@ int bprx_launch_score(bprx_handle *h, const int32_t *u, const int32_t *i, int64_
 
 // row multiplicities / ranks / segment offsets: needs only the index arrays (not P), so it may run beside the forward
 // projection (bprx_step_begin)
-int bprx_launch_index_pass(bprx_handle *h, const int32_t *u, const int32_t *i, const int32_t *j, int64_t B, hipStream_t s) {
-  SparseArgs a = make_args(h, h->P);
-  if (h->item_mode) {
+int bprx_launch_index_pass(bprx_handle *h, const StepPlan &p, hipStream_t s) {
+  SparseArgs a = make_args(h, h->P, p);
+  const int32_t *u = p.user, *i = p.pos, *j = p.neg;
+  const int64_t B = p.B;
+  if (p.item_mode) {
     // segment mode: ranks, counts, segment offsets, the chunk list of k_item_seg, the users' counts and slots -- one launch
     BprxProfScope pc(h, BPRX_PHASE_ROW_COUNT, s);
     IndexSegArgs x;
     x.user = u; x.pos = i; x.neg = j; x.B = B; x.U = a.U; x.I = a.I;
-    int nown = h->num_cu > 0 ? h->num_cu : 256;                                  // one owner workgroup per CU ...
-    if (nown > 1024) nown = 1024;
-    if ((a.I + nown - 1) / nown > IX_RMAX) nown = (a.I + IX_RMAX - 1) / IX_RMAX;   // ... more when a range would not fit LDS
-    if (nown > a.I) nown = a.I;
-    x.R = (a.I + nown - 1) / nown;
+    x.R = p.ix_R; x.nown = p.ix_nown;                                            // (one owner workgroup per CU: plan_step)
     x.own8 = x.loc8 = nullptr; x.wide = 0;
-    h->idx_kind = 1;
-    if (h->idx8_use && h->idx8_shift) {                                          // the sampler left byte planes of this batch
-      x.R = 1 << h->idx8_shift; x.own8 = h->own8; x.loc8 = h->loc8; x.wide = h->idx8_shift > 8; h->idx_kind = 2;
-    }    // the sampler left byte planes of this batch
-    x.nown = (a.I + x.R - 1) / x.R;
+    if (p.idx8) { x.own8 = h->own8; x.loc8 = h->loc8; x.wide = h->idx8_shift > 8; }   // the sampler left byte planes of this batch
     x.seg_rank = h->seg_rank; x.seg_cnt = h->seg_cnt; x.seg_ptr = h->seg_ptr;
     x.Ce = (int)(2 * ((2 * B + x.nown - 1) / x.nown) + 64);
     x.Lc = x.R + IX_LPAD;
-    x.ent_over = x.nown * x.Ce; x.lead_over = x.nown * x.Lc; x.lead_cap = (int)h->seg_lead_cap;
+    x.ent_over = x.nown * x.Ce; x.lead_over = p.seg_lead_over; x.lead_cap = (int)h->seg_lead_cap;
     if ((int64_t)x.ent_over + 2 * B > h->seg_ent_cap || (int64_t)x.lead_over + 2 * B / SEG_CAP + 64 > h->seg_lead_cap)
       BPRX_FAIL(h, BPRX_E_STATE, "index pass: segment buffers too small (I=%d, B=%lld)", a.I, (long long)B);
-    h->seg_lead_over = x.lead_over;
-    h->seg_cur_slot = h->seg_slot;                                               // the pair this step's kernels read
-    x.cur = h->seg_cursor + 3 * h->seg_slot; x.cur_next = h->seg_cursor + 3 * (h->seg_slot ^ 1);
-    h->seg_slot ^= 1;
+    // the triple this step's kernels read, and the one of the next segment-mode step, which this launch clears
+    x.cur = h->seg_cursor + 3 * p.seg_cur; x.cur_next = h->seg_cursor + 3 * (p.seg_cur ^ 1);
     x.lead = (int4 *)h->seg_lead;
-    const bool users = seg_finishes_users(h);
+    const bool users = p.seg_users;
     x.cntU = users ? h->cntU : nullptr; x.uslot_of = users ? h->uslot_of : nullptr; x.ulist = users ? h->ulist : nullptr;
     const bool zw = a.d && h->cfg.feat_dtype != BPRX_F_FP32;                      // bf16 W image: rows of untouched items
     x.Wb = zw ? (uint16_t *)h->Wb : nullptr; x.PS = a.PS;
@@ -2127,129 +2106,106 @@ int bprx_launch_index_pass(bprx_handle *h, const int32_t *u, const int32_t *i, c
     BPRX_LAUNCH_CHECK(h, "k_index_seg");
     return BPRX_OK;
   }
-  if (h->fast_rows || h->list_mode) {
+  if (p.row_count) {
     BprxProfScope pc(h, BPRX_PHASE_ROW_COUNT, s);
     const int64_t cap = 2 * B < (int64_t)a.I ? 2 * B : (int64_t)a.I;
     hipLaunchKernelGGL(k_row_count, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, u, i, j, B, a.U, a.I, h->cntU, h->cntI,
-                       a.fastU, (a.fastI || h->list_mode) ? 1 : 0,
-                       h->list_mode ? h->ilist : (int32_t *)nullptr, h->list_cur, (int)cap,
+                       a.fastU, (a.fastI || p.list_mode) ? 1 : 0,
+                       p.list_mode ? h->ilist : (int32_t *)nullptr, p.list_cur, (int)cap,
                        a.use_list ? a.slist : (int32_t *)nullptr, a.slist_n, (int)(3 * h->cfg.max_batch));
   }
   BPRX_LAUNCH_CHECK(h, "k_row_count");
   return BPRX_OK;
 }
 
-int bprx_launch_triplet_grad(bprx_handle *h, const int32_t *u, const int32_t *i, const int32_t *j, int64_t B, hipStream_t s) {
-  SparseArgs a = make_args(h, h->P);
+int bprx_launch_triplet_grad(bprx_handle *h, const StepPlan &p, hipStream_t s) {
+  SparseArgs a = make_args(h, h->P, p);
+  const int32_t *u = p.user, *i = p.pos, *j = p.neg;
+  const int64_t B = p.B;
   const bool vec = vec_ok(h);
   const int G = pick_group(a.k, a.d, vec);
   BprxProfScope ps(h, BPRX_PHASE_TRIPLET, s);
-  // W (fp32) must be all-zero here.  bf16 features: k_cast_W (backward variants >= 8) re-zeroes it while converting and
-  // k_item_seg re-zeroes the rows it folds in, so only the remaining combinations need the memset.
-  const bool bf = h->cfg.feat_dtype != BPRX_F_FP32;     // bf16 W image (bf16 and fp8 features)
-  // dense form with fp32 features (or the fp32-W backward variants): W is consumed in place and cleared here, at the
-  // next step; list mode returns its rows to zero itself (k_cast_W_rows) and only needs the memset after such a step
-  const bool leaves_dirty = a.d && !h->list_mode && !bf;
-  if (leaves_dirty || (a.d && h->W_dirty))
-    BPRX_HIP(h, hipMemsetAsync(h->W, 0, (size_t)a.I * a.PS * sizeof(float), s));
-  h->W_dirty = leaves_dirty;
-  if (h->item_mode) {                                   // (segment mode implies the 16-B-per-lane layout: k % 4 == d % 4 == 0)
-    const SegUser su = {seg_finishes_users(h) ? 0 : 1, h->uslot_of, h->uold};
+  // W (fp32) must be all-zero here (StepPlan::w_memset: only where no kernel re-zeroes it)
+  if (p.w_memset) BPRX_HIP(h, hipMemsetAsync(h->W, 0, (size_t)a.I * a.PS * sizeof(float), s));
+  if (p.item_mode) {                                    // (segment mode implies the 16-B-per-lane layout: k % 4 == d % 4 == 0)
+    const SegUser su = {p.seg_users ? 0 : 1, h->uslot_of, h->uold};
     const int Gs = pick_group(a.k, a.d, true);
     const dim3 grid((unsigned)((B * Gs + TS_T - 1) / TS_T));
-    switch (Gs) {
-      case 8: hipLaunchKernelGGL((k_triplet_seg<8>), grid, dim3(TS_T), 0, s, a, su, u, i, j, B); break;
-      case 16: hipLaunchKernelGGL((k_triplet_seg<16>), grid, dim3(TS_T), 0, s, a, su, u, i, j, B); break;
-      case 32: hipLaunchKernelGGL((k_triplet_seg<32>), grid, dim3(TS_T), 0, s, a, su, u, i, j, B); break;
-      default: hipLaunchKernelGGL((k_triplet_seg<64>), grid, dim3(TS_T), 0, s, a, su, u, i, j, B); break;
-    }
+    with_group(Gs, [&](auto g_) { hipLaunchKernelGGL((k_triplet_seg<decltype(g_)::value>), grid, dim3(TS_T), 0, s, a, su, u, i, j, B); });
   } else {
-#define TG_LAUNCH(GG, VV)                                                                                                \
-  hipLaunchKernelGGL((k_triplet_grad<GG, VV>), dim3((unsigned)((B * GG + TripletGradThreads<GG>::value - 1) / TripletGradThreads<GG>::value)), \
-                     dim3(TripletGradThreads<GG>::value), 0, s, a, u, i, j, B)
-    if (vec) { switch (G) { case 8: TG_LAUNCH(8, true); break; case 16: TG_LAUNCH(16, true); break; case 32: TG_LAUNCH(32, true); break; default: TG_LAUNCH(64, true); break; } }
-    else { switch (G) { case 8: TG_LAUNCH(8, false); break; case 16: TG_LAUNCH(16, false); break; case 32: TG_LAUNCH(32, false); break; default: TG_LAUNCH(64, false); break; } }
-#undef TG_LAUNCH
+    with_group(G, [&](auto g_) {
+      constexpr int GG = decltype(g_)::value, T = TripletGradThreads<GG>::value;   // threads per workgroup: by group width
+      const dim3 grid((unsigned)((B * GG + T - 1) / T));
+      if (vec) hipLaunchKernelGGL((k_triplet_grad<GG, true>), grid, dim3(T), 0, s, a, u, i, j, B);
+      else hipLaunchKernelGGL((k_triplet_grad<GG, false>), grid, dim3(T), 0, s, a, u, i, j, B);
+    });
   }
   BPRX_LAUNCH_CHECK(h, "k_triplet_grad");
   return BPRX_OK;
 }
 
-int bprx_launch_item_seg(bprx_handle *h, const int32_t *i, const int32_t *j, int64_t B, float lr_t, hipStream_t s) {
-  if (!h->item_mode) return BPRX_OK;
-  SparseArgs a = make_args(h, nullptr);
+int bprx_launch_item_seg(bprx_handle *h, const StepPlan &p, hipStream_t s) {
+  SparseArgs a = make_args(h, nullptr, p);
+  const int64_t B = p.B;
+  const float lr_t = p.lr_t;
   const int G = pick_group(a.k, a.d, true);
   const int adam = h->cfg.optimizer == BPRX_OPT_ADAM_TF23 ? (h->adam_lazy ? 2 : 1) : 0;
   const bool bf = h->cfg.feat_dtype != BPRX_F_FP32;     // bf16 W image (bf16 and fp8 features)
   float *Wf = a.d && !bf ? h->W : nullptr;
   uint16_t *Wb = a.d && bf ? (uint16_t *)h->Wb : nullptr;
-  const AdamFuse af = {h->t.m_Gi, h->t.v_Gi, h->t.m_Bi, h->t.v_Bi, h->lastI, h->cfg.beta1, h->cfg.beta2, h->cfg.epsilon, (int)h->adam_t};
+  const AdamFuse af = {h->t.m_Gi, h->t.v_Gi, h->t.m_Bi, h->t.v_Bi, h->lastI, h->cfg.beta1, h->cfg.beta2, h->cfg.epsilon, (int)p.adam_t};
   BprxProfScope ps(h, BPRX_PHASE_ITEM_SEG, s);
   // (k_index_seg zeroed the bf16 rows of this batch's untouched items)
   // one lane group per chunk-list slot: the owners' regions (~one slot per item) + the overflow list (hot items' extra chunks)
-  const int64_t bound = (int64_t)h->seg_lead_over + 2 * B / SEG_CAP + 64;
+  const int64_t bound = (int64_t)p.seg_lead_over + 2 * B / SEG_CAP + 64;
   // (the finishing workgroups stride over the batch's users -- a few thousand in the reference's visiting order, up to B for
   //  i.i.d. batches: sized for a quarter of B, the surplus ones leave after one load)
   int64_t nfin = B * G / IS_T / 4;
   nfin = nfin < 16 ? 16 : (nfin > 2048 ? 2048 : nfin);
-  a.nfin = seg_finishes_users(h) ? (int)nfin : 0;
+  a.nfin = p.seg_users ? (int)nfin : 0;
   const dim3 grid((unsigned)((bound * G + IS_T - 1) / IS_T + a.nfin));
-#define LAUNCH_SEG(GG)                                                                                                   \
-  do {                                                                                                                   \
-    if (adam == 2) hipLaunchKernelGGL((k_item_seg<GG, 2>), grid, dim3(IS_T), 0, s, a, h->t.Gi, h->t.Bi, Wf, Wb, lr_t, af); \
-    else if (adam) hipLaunchKernelGGL((k_item_seg<GG, 1>), grid, dim3(IS_T), 0, s, a, h->t.Gi, h->t.Bi, Wf, Wb, lr_t, af); \
-    else hipLaunchKernelGGL((k_item_seg<GG, 0>), grid, dim3(IS_T), 0, s, a, h->t.Gi, h->t.Bi, Wf, Wb, lr_t, af);          \
-  } while (0)
-  switch (G) {
-    case 8: LAUNCH_SEG(8); break;
-    case 16: LAUNCH_SEG(16); break;
-    case 32: LAUNCH_SEG(32); break;
-    default: LAUNCH_SEG(64); break;
-  }
-#undef LAUNCH_SEG
+  with_group(G, [&](auto g_) {
+    constexpr int GG = decltype(g_)::value;
+    if (adam == 2) hipLaunchKernelGGL((k_item_seg<GG, 2>), grid, dim3(IS_T), 0, s, a, h->t.Gi, h->t.Bi, Wf, Wb, lr_t, af);
+    else if (adam) hipLaunchKernelGGL((k_item_seg<GG, 1>), grid, dim3(IS_T), 0, s, a, h->t.Gi, h->t.Bi, Wf, Wb, lr_t, af);
+    else hipLaunchKernelGGL((k_item_seg<GG, 0>), grid, dim3(IS_T), 0, s, a, h->t.Gi, h->t.Bi, Wf, Wb, lr_t, af);
+  });
   BPRX_LAUNCH_CHECK(h, "k_item_seg");
   return BPRX_OK;
 }
 
-int bprx_launch_apply(bprx_handle *h, const int32_t *u, const int32_t *i, const int32_t *j, int64_t B, float lr_t, hipStream_t s) {
-  SparseArgs a = make_args(h, nullptr);
+// the optimizer pass over the staging rows (StepPlan::apply; not called for APPLY_NONE: k_item_seg finished the items and
+// k_triplet_seg the users); row kinds [fk, ek)
+int bprx_launch_apply(bprx_handle *h, const StepPlan &p, hipStream_t s) {
+  SparseArgs a = make_args(h, nullptr, p);
   const size_t U = a.U, I = a.I, k = a.k, d = a.d;
-  if (seg_finishes_users(h)) return BPRX_OK;             // k_item_seg finished the items, k_triplet_seg the users
+  const int32_t *u = p.user, *i = p.pos, *j = p.neg;
+  const int64_t B = p.B;
+  const float lr_t = p.lr_t;
+  const bool vec = vec_ok(h);
+  const int G = pick_group(a.k, a.d, vec);
   BprxProfScope ps(h, BPRX_PHASE_APPLY, s);
-  if (h->cfg.optimizer == BPRX_OPT_SGD) {
-    const bool vec = vec_ok(h);
-    const int G = pick_group(a.k, a.d, vec);
-    // first_kind = 1 skips the user rows (their gradients are exported to the caller: BPRX_FLAG_EXPORT_USER_GRAD)
-    // item rows are finished in place by k_item_seg when that mode is on: kinds [fk, ek)
-    if (a.use_list) {
-      int64_t blocks = (3 * B * G + 255) / 256;
-      if (blocks > 1024) blocks = 1024;
-      DISPATCH_G(G, vec, k_apply_sgd_list, dim3((unsigned)blocks), s, h->t.Gu, h->t.Gi, h->t.Bi, h->t.Tu, a, h->slist,
-                 h->slist_n + h->slist_slot, h->slist_n + (h->slist_slot ^ 1), (int)(3 * h->cfg.max_batch), lr_t);
-      h->slist_slot ^= 1;
-      BPRX_LAUNCH_CHECK(h, "k_apply_sgd_list");
-      return BPRX_OK;
-    }
-    // (segment mode: k_item_seg finished the items and k_triplet_seg the users: nothing is left to apply)
-    const int fk = ((h->cfg.flags & BPRX_FLAG_EXPORT_USER_GRAD) || h->item_mode) ? 1 : 0;
-    const int ek = (h->item_mode || (h->cfg.flags & BPRX_FLAG_EXPORT_ITEM_GRAD)) ? 1 : 3;
-    if (ek > fk)
-      DISPATCH_G(G, vec, k_apply_sgd, grid_for((int64_t)(ek - fk) * B, G), s, h->t.Gu, h->t.Gi, h->t.Bi, h->t.Tu, a, u, i, j, B,
-                 lr_t, fk, ek);
+  if (p.apply == APPLY_SGD_LIST) {
+    int64_t blocks = (3 * B * G + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    DISPATCH_G(G, vec, k_apply_sgd_list, dim3((unsigned)blocks), s, h->t.Gu, h->t.Gi, h->t.Bi, h->t.Tu, a, h->slist,
+               h->slist_n + p.slist_cur, h->slist_n + (p.slist_cur ^ 1), (int)(3 * h->cfg.max_batch), lr_t);
+    BPRX_LAUNCH_CHECK(h, "k_apply_sgd_list");
+    return BPRX_OK;
+  }
+  if (p.apply == APPLY_SGD) {
+    if (p.ek > p.fk)
+      DISPATCH_G(G, vec, k_apply_sgd, grid_for((int64_t)(p.ek - p.fk) * B, G), s, h->t.Gu, h->t.Gi, h->t.Bi, h->t.Tu, a, u, i, j, B,
+                 lr_t, p.fk, p.ek);
     BPRX_LAUNCH_CHECK(h, "k_apply_sgd");
     return BPRX_OK;
   }
-  if (h->adam_lazy) {                                    // touched rows only (claim per occurrence); everything else is replayed later
-    const bool vec = vec_ok(h);
-    const int G = pick_group(a.k, a.d, vec);
-    const int fk = (h->cfg.flags & BPRX_FLAG_EXPORT_USER_GRAD) ? 1 : 0;      // replicated multi-GPU: users via bprx_apply_user_msgs
-    const int ek = (h->item_mode || (h->cfg.flags & BPRX_FLAG_EXPORT_ITEM_GRAD)) ? 1 : 3;   // segments: k_item_seg took the items' steps;
-                                                                             // exported item gradients: their owner does
+  if (p.apply == APPLY_ADAM_LAZY) {                      // touched rows only (claim per occurrence); everything else is replayed later
     const AdamTables T = make_adam_tables(h);
     const AdamLazy al = {h->cfg.beta1, h->cfg.beta2, h->cfg.epsilon, h->lr_hist};
-    if (ek > fk)
-      DISPATCH_G(G, vec, k_adam_apply_lazy, grid_for((int64_t)(ek - fk) * B, G), s, T, al, h->dGu, h->dTu, h->dGi, h->dBi, h->flagU,
-                 h->flagI, u, i, j, B, (int)h->adam_t, lr_t, fk, ek);
+    if (p.ek > p.fk)
+      DISPATCH_G(G, vec, k_adam_apply_lazy, grid_for((int64_t)(p.ek - p.fk) * B, G), s, T, al, h->dGu, h->dTu, h->dGi, h->dBi, h->flagU,
+                 h->flagI, u, i, j, B, (int)p.adam_t, lr_t, p.fk, p.ek);
     BPRX_LAUNCH_CHECK(h, "k_adam_apply_lazy");
     return BPRX_OK;
   }
@@ -2277,14 +2233,14 @@ int bprx_launch_fill_i32(bprx_handle *h, int32_t *p, size_t n, int32_t v, hipStr
 }
 
 // ---- lazy-exact adam_tf23: catch-up before the forward pass, full catch-up on demand ----
-int bprx_launch_adam_catchup(bprx_handle *h, const int32_t *u, const int32_t *i, const int32_t *j, int64_t B, float lr_t,
-                             hipStream_t s) {
+int bprx_launch_adam_catchup(bprx_handle *h, const StepPlan &p, hipStream_t s) {
   const bool vec = vec_ok(h);
   const int G = pick_group(h->cfg.embed_k, h->cfg.embed_d, vec);
   const AdamTables T = make_adam_tables(h);
   const AdamLazy al = {h->cfg.beta1, h->cfg.beta2, h->cfg.epsilon, h->lr_hist};
   BprxProfScope ps(h, BPRX_PHASE_ADAM_CATCHUP, s);
-  DISPATCH_G(G, vec, k_adam_catchup, grid_for(B ? 3 * B : 1, G), s, T, al, u, i, j, B, (int)h->adam_t, lr_t, h->lr_hist);
+  DISPATCH_G(G, vec, k_adam_catchup, grid_for(p.B ? 3 * p.B : 1, G), s, T, al, p.user, p.pos, p.neg, p.B, (int)p.adam_t, p.lr_t,
+             h->lr_hist);
   BPRX_LAUNCH_CHECK(h, "k_adam_catchup");
   return BPRX_OK;
 }
@@ -2316,44 +2272,36 @@ int bprx_launch_adam_reset(bprx_handle *h, int64_t t, hipStream_t s) {
   return BPRX_OK;
 }
 
-int bprx_adam_hist(void) { return ADAM_HIST; }
-
-int bprx_launch_dense_update(bprx_handle *h, float lr_t, hipStream_t s) {
+// (bprx_step_end calls it when StepPlan::dense_launch; GradFashion: bprx_launch_fact_update has moved the factors, composed
+//  E_eff / Bp_eff and left the loss partials, and this launch only does the step's housekeeping)
+int bprx_launch_dense_update(bprx_handle *h, const StepPlan &p, hipStream_t s) {
   const int D = h->cfg.feat_dim;
   unsigned blocks = (unsigned)((D + DU_KB - 1) / DU_KB);
   if (blocks > BPRX_DENSE_BLOCKS) blocks = BPRX_DENSE_BLOCKS;
-  // GradFashion: bprx_launch_fact_update has moved the factors, composed E_eff / Bp_eff and left the loss partials; this
-  // launch only does the step's housekeeping below (nothing to do: no launch)
   const bool upd = !h->factored;
   if (upd) h->dense_blocks = (int)blocks;
-  else if (!h->list_mode && h->cfg.feat_dtype != BPRX_F_BF16) { h->et_valid = false; h->p_valid = false; return BPRX_OK; }
   BprxProfScope ps(h, BPRX_PHASE_DENSE, s);
   // fused_reduce: the split-K slabs are summed here (bprx_step); otherwise dEp holds the (all-reduced) gradient
-  const float *part = (upd && h->fused_reduce && h->cfg.feat_dtype != BPRX_F_FP32) ? h->part : nullptr;
+  const float *part = (p.fused_reduce && h->cfg.feat_dtype != BPRX_F_FP32) ? h->part : nullptr;
   // fp8 features: the slabs hold (F*feat_scale)^T W; an all-reduced dEp was already rescaled by k_reduce_parts
   const float gscale = (part && h->cfg.feat_dtype == BPRX_F_FP8) ? 1.0f / h->cfg.feat_scale : 1.0f;
   // bf16 features: this kernel writes the next step's [E|Bp]^T images (fp8 images need the global max first: k_cast_Et8)
   const bool images = h->cfg.feat_dtype == BPRX_F_BF16;
-  const bool lm = h->list_mode != 0;
-  const int64_t bound = lm ? h->list_bound : 0;
+  const bool lm = p.list_mode;
   // one round per tile: a tile is DU_KB rows x PS / 4 float4 columns -- 160 threads' worth at PS = 80, 544 at PS = 272 (a 256-thread
   // block took three dependent rounds of slab loads there: c5small 21.5 us)
   int threads = (DU_KB * (h->PS / 4) + 63) / 64 * 64;
   threads = threads < 256 ? 256 : (threads > 1024 ? 1024 : threads);
   hipLaunchKernelGGL(k_dense_update, dim3(blocks), dim3((unsigned)threads), 0, s, h->t.E, h->t.Bp, h->t.m_E, h->t.v_E, h->t.m_Bp,
-                     h->t.v_Bp, h->dEp, part, h->SK_step, D, h->cfg.embed_d, h->PS,
-                     h->cfg.optimizer == BPRX_OPT_ADAM_TF23 ? 1 : 0, lr_t, h->cfg.reg, h->cfg.beta1, h->cfg.beta2,
+                     h->t.v_Bp, h->dEp, part, p.SK_step, D, h->cfg.embed_d, h->PS,
+                     h->cfg.optimizer == BPRX_OPT_ADAM_TF23 ? 1 : 0, p.lr_t, h->cfg.reg, h->cfg.beta1, h->cfg.beta2,
                      h->cfg.epsilon, upd ? h->loss_acc : (double *)nullptr, gscale, images ? (uint16_t *)h->Et : (uint16_t *)nullptr, (uint16_t *)h->EtF,
-                     lm ? (const int32_t *)h->ilist : (const int32_t *)nullptr, (const int32_t *)h->list_cur,
-                     lm ? h->ilist_n + (h->list_slot ^ 1) : (int32_t *)nullptr, (int)bound, h->W,
-                     (lm && h->list_reset_cnt) ? h->cntI : (int32_t *)nullptr,
+                     lm ? (const int32_t *)h->ilist : (const int32_t *)nullptr, (const int32_t *)p.list_cur,
+                     p.list_next, (int)p.list_bound, h->W,
+                     (lm && p.list_reset_cnt) ? h->cntI : (int32_t *)nullptr,
                      // fp8: the slot the next k_cast_Et8 reads (cleared by the last one)
                      h->cfg.feat_dtype == BPRX_F_FP8 ? (uint32_t *)h->qs + 2 + h->qs_slot : (uint32_t *)nullptr, upd ? 1 : 0);
   BPRX_LAUNCH_CHECK(h, "k_dense_update");
-  h->absmax_valid = h->cfg.feat_dtype == BPRX_F_FP8;
-  if (lm) { h->list_slot ^= 1; h->list_mode = 0; }      // the step's list is consumed
-  h->et_valid = images;                                 // E / Bp moved: the images were refreshed here, or are stale
-  h->p_valid = false;                                   //               the item projections are stale
   return BPRX_OK;
 }
 
@@ -2366,7 +2314,7 @@ int bprx_launch_loss_reduce(bprx_handle *h, int64_t B, float *loss_out, hipStrea
 }
 
 int bprx_launch_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s) {
-  SparseArgs a = make_args(h, h->P);
+  SparseArgs a = make_args(h, h->P, h->step);
   dim3 grid((a.I + 63) / 64, (u1 - u0 + 3) / 4);
   hipLaunchKernelGGL(k_score_block, grid, dim3(256), 0, s, a, u0, u1, out);
   BPRX_LAUNCH_CHECK(h, "k_score_block");
