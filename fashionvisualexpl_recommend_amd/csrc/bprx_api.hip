@@ -597,6 +597,36 @@ extern "C" int bprx_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *o
   return bprx_launch_score_block(h, u0, u1, out, s);
 }
 
+// ---- items outside the catalogue (include/bprx.h): bprx_project_rows here, bprx_score_new_block / bprx_topk_rows in
+// bprx_eval.hip, bprx_feat_explain_new in bprx_explain.hip ----
+int bprx_new_items_check(bprx_handle *h, const char *what, int64_t n) {
+  if (!h) return BPRX_E_INVALID;
+  if (h->cfg.model != BPRX_MODEL_VBPR || h->acf || h->af)
+    BPRX_FAIL(h, BPRX_E_INVALID, "%s: needs a VBPR handle (bprx_bind_tables or bprx_bind_factored)", what);
+  if (h->cfg.feat_dtype == BPRX_F_FP8)
+    BPRX_FAIL(h, BPRX_E_INVALID, "%s: fp8 features are not supported for new items (a new row may exceed the max-abs the codes "
+              "were scaled for and would saturate): fp32 or bf16", what);
+  if (n < 0 || n >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "%s: n = %lld out of range", what, (long long)n);
+  if (!h->bound) BPRX_FAIL(h, BPRX_E_STATE, "tables not bound (call bprx_bind_tables first)");
+  return BPRX_OK;
+}
+
+extern "C" int32_t bprx_proj_stride(const bprx_handle *h) {
+  return h && h->cfg.model == BPRX_MODEL_VBPR ? h->PS : BPRX_E_INVALID;
+}
+
+extern "C" int bprx_project_rows(bprx_handle *h, const void *Fnew, int64_t n, float *P, void *stream) {
+  int rc = bprx_new_items_check(h, "project_rows", n);
+  if (rc) return rc;
+  if (n == 0) return BPRX_OK;
+  if (!Fnew || !P) BPRX_FAIL(h, BPRX_E_INVALID, "project_rows: null pointer");
+  if ((uintptr_t)Fnew & 15) BPRX_FAIL(h, BPRX_E_INVALID, "project_rows: the table must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: as every call that reads the tables
+  if ((rc = bprx_launch_cast_Et(h, s))) return rc;
+  return bprx_launch_proj_new(h, Fnew, n, P, s);
+}
+
 extern "C" int bprx_step_lr(const bprx_handle *h, float *lr_t) {
   if (!h || !lr_t) return BPRX_E_INVALID;
   *lr_t = h->step.lr_t;

@@ -81,6 +81,38 @@ __global__ __launch_bounds__(256) void k_score_gemm(GemmArgs g, int u0, int u1, 
   }
 }
 
+// bprx_score_new_block: out[u][j] = <Tu[u], P[j, 0:d]> + P[j, d] for the n rows of a caller's P (items outside the catalogue: no
+// Gi, no Bi).  The Tu x P phase of k_score_gemm on its own, same tiles, same C/D map; any d >= 1 (gemm_phase pads k with zeros).
+__global__ __launch_bounds__(256) void k_score_new_gemm(const float *__restrict__ Tu, const float *__restrict__ P, int n, int d,
+                                                        int PS, int u0, int u1, float *__restrict__ out) {
+  __shared__ float As[TM][GLD];
+  __shared__ float Bs[TN][GLD];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wr = w >> 1, wc = w & 1;
+  const int i0 = blockIdx.x * TN, ub = u0 + blockIdx.y * TM;
+  const int arows = min(TM, u1 - ub), brows = min(TN, n - i0);
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+  gemm_phase(Tu, d, ub, arows, P, PS, i0, brows, d, As, Bs, acc, wr, wc, lane);
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+    const int ic = i0 + wc * 64 + b * 32 + (lane & 31);
+    if (ic >= n) continue;
+    const float bias = P[(size_t)ic * PS + d];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int ur = ub + wr * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (ur < u1) out[(size_t)(ur - u0) * n + ic] = acc[a][b][r] + bias;
+      }
+  }
+}
+
 constexpr int EVMAX = 32;   // held-out items per user handled on the device (the reference's split holds out 1)
 
 // One workgroup per user.  out[5] = hr, prec, rec, auc, ndcg (double); out[0] = -1 marks "no held-out items"
@@ -298,8 +330,8 @@ __global__ __launch_bounds__(256) void k_topk(float *__restrict__ S, int u0, int
   __shared__ int cidx[TOPK_MAX];
   const int u = u0 + blockIdx.x, tid = threadIdx.x;
   float *s = S + (size_t)blockIdx.x * I;
-  const int64_t t0 = tr_ptr[u];
-  const int ntr = (int)(tr_ptr[u + 1] - t0);
+  const int64_t t0 = tr_ptr ? tr_ptr[u] : 0;               // (tr_ptr == nullptr, bprx_topk_rows: nothing is masked)
+  const int ntr = tr_ptr ? (int)(tr_ptr[u + 1] - t0) : 0;
   for (int q = tid; q < ntr; q += 256) {
     const int it = tr_items[t0 + q];
     if ((unsigned)it < (unsigned)I) s[it] = -INFINITY;
@@ -385,6 +417,35 @@ extern "C" int bprx_topk(bprx_handle *h, int32_t u0, int32_t u1, float *scores, 
   hipLaunchKernelGGL(k_topk, dim3(u1 - u0), dim3(256), 0, (hipStream_t)stream, scores, u0, h->cfg.num_items, train_ptr,
                      train_items, K, idx, val, flag);
   BPRX_LAUNCH_CHECK(h, "k_topk");
+  return BPRX_OK;
+}
+
+extern "C" int bprx_topk_rows(bprx_handle *h, int64_t nrows, int32_t width, float *scores, int32_t K, int32_t *idx, float *val,
+                              int32_t *flag, void *stream) {
+  const int rc = bprx_new_items_check(h, "topk_rows", nrows);
+  if (rc) return rc;
+  if (width < 1) BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows: width = %d < 1", width);
+  if (K <= 0 || K > TOPK_MAX) BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows: K=%d outside [1, %d]", K, TOPK_MAX);
+  if (nrows == 0) return BPRX_OK;
+  if (!scores || !idx || !val || !flag) BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows: null pointer");
+  hipLaunchKernelGGL(k_topk, dim3((unsigned)nrows), dim3(256), 0, (hipStream_t)stream, scores, 0, width, (const int64_t *)nullptr,
+                     (const int32_t *)nullptr, K, idx, val, flag);
+  BPRX_LAUNCH_CHECK(h, "k_topk<rows>");
+  return BPRX_OK;
+}
+
+extern "C" int bprx_score_new_block(bprx_handle *h, int32_t u0, int32_t u1, const float *P, int64_t n, float *out, void *stream) {
+  int rc = bprx_new_items_check(h, "score_new_block", n);
+  if (rc) return rc;
+  if (u0 < 0 || u1 > h->cfg.num_users || u0 > u1) BPRX_FAIL(h, BPRX_E_INVALID, "score_new_block: bad user range [%d,%d)", u0, u1);
+  if (n == 0 || u0 == u1) return BPRX_OK;
+  if (!P || !out) BPRX_FAIL(h, BPRX_E_INVALID, "score_new_block: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: the Tu rows must be current
+  if ((rc = bprx_launch_cast_Et(h, s))) return rc;                       // (the image P was made from stays the current one)
+  dim3 grid((unsigned)((n + TN - 1) / TN), (unsigned)((u1 - u0 + TM - 1) / TM));
+  hipLaunchKernelGGL(k_score_new_gemm, grid, dim3(256), 0, s, (const float *)h->t.Tu, P, (int)n, h->cfg.embed_d, h->PS, u0, u1, out);
+  BPRX_LAUNCH_CHECK(h, "k_score_new_gemm");
   return BPRX_OK;
 }
 

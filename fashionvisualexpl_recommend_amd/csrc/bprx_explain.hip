@@ -88,7 +88,10 @@ template <int V> __device__ __forceinline__ void load_feats(const uint8_t *row, 
 // (av, ac) ranks before (bv, bc): larger value first (floats: +0.0 == -0.0), the lower column among equal values
 __device__ __forceinline__ bool ranks_before(float av, int ac, float bv, int bc) { return av > bv || (av == bv && ac < bc); }
 
-template <typename FT, int V>
+// NEW (bprx_feat_explain_new): the pairs are (user, row of a table the model was not trained on): A.item indexes the A.I rows
+// of A.F, there is no Gu.Gi dot and no Bi -- score is the visual sum; base and visual are not written.  Everything else is the
+// same code.
+template <typename FT, int V, bool NEW>
 __global__ __launch_bounds__(256) void k_feat_explain(FeatExplainArgs A) {
 #pragma clang fp contract(off)   // c = f * w is rounded before it is added: visual is the sum of the stored contributions
   extern __shared__ float w[];                               // [D] w_u of the current run
@@ -140,11 +143,14 @@ __global__ __launch_bounds__(256) void k_feat_explain(FeatExplainArgs A) {
     for (int q = s + wave; q < e; q += 4) {
       const int64_t p = p0 + q;
       const int i = __builtin_amdgcn_readfirstlane(__shfl(pi, q, 64));
-      const float *gu = A.Gu + (size_t)u * k, *gi = A.Gi + (size_t)i * k;
-      float dot = 0.f;
-      for (int c = lane; c < k; c += 64) dot = fmaf(gu[c], gi[c], dot);
-      dot = wave_sum(dot);
-      const float base = A.Bi[i] + dot;
+      float base = 0.f;
+      if constexpr (!NEW) {
+        const float *gu = A.Gu + (size_t)u * k, *gi = A.Gi + (size_t)i * k;
+        float dot = 0.f;
+        for (int c = lane; c < k; c += 64) dot = fmaf(gu[c], gi[c], dot);
+        dot = wave_sum(dot);
+        base = A.Bi[i] + dot;
+      }
       const FT *row = F + (size_t)i * D;
       float *mrow = A.map ? A.map + p * ncols : nullptr;
       float acc = 0.f;                                       // this lane's share of visual
@@ -216,9 +222,13 @@ __global__ __launch_bounds__(256) void k_feat_explain(FeatExplainArgs A) {
       }
       const float visual = wave_sum(acc);
       if (lane == 0) {
-        A.base[p] = base;
-        A.visual[p] = visual;
-        A.score[p] = base + visual;
+        if constexpr (NEW) {
+          A.score[p] = visual;
+        } else {
+          A.base[p] = base;
+          A.visual[p] = visual;
+          A.score[p] = base + visual;
+        }
       }
       if (lane < top) {
         A.col[p * top + lane] = lane < cnt ? tp : -1;
@@ -230,11 +240,11 @@ __global__ __launch_bounds__(256) void k_feat_explain(FeatExplainArgs A) {
   }
 }
 
-template <typename FT>
+template <typename FT, bool NEW = false>
 void launch(const FeatExplainArgs &A, bool vec, unsigned blocks, size_t lds, hipStream_t s) {
   constexpr int V = 16 / (int)sizeof(FT);
-  if (vec) hipLaunchKernelGGL((k_feat_explain<FT, V>), dim3(blocks), dim3(256), lds, s, A);
-  else hipLaunchKernelGGL((k_feat_explain<FT, 1>), dim3(blocks), dim3(256), lds, s, A);
+  if (vec) hipLaunchKernelGGL((k_feat_explain<FT, V, NEW>), dim3(blocks), dim3(256), lds, s, A);
+  else hipLaunchKernelGGL((k_feat_explain<FT, 1, NEW>), dim3(blocks), dim3(256), lds, s, A);
 }
 
 }  // namespace
@@ -274,5 +284,41 @@ extern "C" int bprx_feat_explain(bprx_handle *h, const void *F, const int32_t *u
   else if (c.feat_dtype == BPRX_F_FP8) launch<uint8_t>(A, vec, blocks, lds, s);
   else launch<float>(A, vec, blocks, lds, s);
   BPRX_LAUNCH_CHECK(h, "k_feat_explain");
+  return BPRX_OK;
+}
+
+extern "C" int bprx_feat_explain_new(bprx_handle *h, const void *Fnew, int64_t n_new, const int32_t *user, const int32_t *row,
+                                     int64_t n, int32_t ncols, int32_t top, float *score, int32_t *col, float *contrib, float *map,
+                                     void *stream) {
+  int rc = bprx_new_items_check(h, "feat_explain_new", n);
+  if (rc) return rc;
+  const bprx_config &c = h->cfg;
+  if (n_new < 0 || n_new >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: n_new = %lld out of range", (long long)n_new);
+  if (ncols < 1 || ncols > c.feat_dim) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: ncols = %d outside [1, feat_dim = %d]", ncols, c.feat_dim);
+  if (top < 1 || top > 32) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: top = %d outside [1, 32]", top);
+  if (c.feat_dim > 16384)
+    BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: feat_dim = %d > 16384 (one user's fp32 w row must fit in 64 KB of LDS)", c.feat_dim);
+  if (n == 0) return BPRX_OK;
+  if (n_new == 0) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: %lld pairs of an empty table", (long long)n);
+  if (!Fnew || !user || !row || !score || !col || !contrib) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: the rows must be current
+  if ((rc = bprx_launch_cast_Et(h, s))) return rc;                       // (not read here: the image bprx_project_rows scores with)
+  FeatExplainArgs A;
+  A.Gu = nullptr; A.Gi = nullptr; A.Bi = nullptr; A.Tu = h->t.Tu; A.E = h->t.E; A.Bp = h->t.Bp;
+  A.F = Fnew; A.user = user; A.item = row; A.n = n;
+  A.U = c.num_users; A.I = (int)n_new; A.k = c.embed_k; A.d = c.embed_d; A.D = c.feat_dim; A.ncols = ncols; A.top = top;
+  A.e_vec = c.embed_d % 4 == 0;
+  A.map_vec = map && ncols % 4 == 0 && ((uintptr_t)map & 15) == 0;
+  A.feat_scale = 1.0f;
+  A.score = score; A.base = nullptr; A.visual = nullptr; A.col = col; A.contrib = contrib; A.map = map;
+  A.errflag = h->errflag;
+  const size_t esz = c.feat_dtype == BPRX_F_FP32 ? 4 : 2;
+  const bool vec = ((uintptr_t)Fnew & 15) == 0 && ((size_t)c.feat_dim * esz) % 16 == 0;
+  const unsigned blocks = (unsigned)((n + FX_TILE - 1) / FX_TILE);
+  const size_t lds = (size_t)c.feat_dim * sizeof(float);
+  if (c.feat_dtype == BPRX_F_BF16) launch<uint16_t, true>(A, vec, blocks, lds, s);
+  else launch<float, true>(A, vec, blocks, lds, s);
+  BPRX_LAUNCH_CHECK(h, "k_feat_explain<new>");
   return BPRX_OK;
 }

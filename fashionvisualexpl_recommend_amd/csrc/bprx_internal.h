@@ -309,6 +309,11 @@ int bprx_launch_cast_Et(bprx_handle *h, hipStream_t s);
 int bprx_launch_proj_fwd(bprx_handle *h, const int32_t *rows, int64_t nrows, const int32_t *nrows_dev, int scatter, float *Pout,
                          hipStream_t s, const int32_t *occ = nullptr);
 int bprx_launch_proj_bwd(bprx_handle *h, const StepPlan &p, hipStream_t s);
+// P = Fnew.[E|Bp] for the n rows of a caller's ROW-MAJOR table (bprx_project_rows): bf16 features from the image Et in one pass
+// over the table (k_proj_new_bf16), fp32 features with the kernels of the catalogue
+int bprx_launch_proj_new(bprx_handle *h, const void *Fnew, int64_t n, float *P, hipStream_t s);
+// what the new-item entry points share (bprx_api.hip): 0, or the error of a handle / row count they do not take
+int bprx_new_items_check(bprx_handle *h, const char *what, int64_t n);
 // whether the kernel form the whole-table forward / backward projection takes for this handle's shape has a masked variant
 // (bprx_proj.hip, next to the form tables): what the launchers do with `occ`, and what bprx_proj_mask_kind reports
 bool bprx_proj_fwd_takes_mask(const bprx_handle &h);

@@ -262,6 +262,87 @@ __global__ __launch_bounds__(256) void k_proj_fwd_bf16(const uint16_t *__restric
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// forward over a caller's ROW-MAJOR bf16 table (bprx_project_rows: items the model was not trained on).  The shape of
+// k_proj_fwd_bf16 -- 4 waves, MT tiles of 16 rows per wave, all NT column tiles in registers, the chunk of the chunk-major
+// image Et staged through LDS -- with the A operand read from rows 2*D bytes apart instead of the tiled copy: lane l takes
+// 16 B of row l & 15 at column k0 + ks + 8 * (l >> 4) (D % 128 == 0: every load is 16-byte aligned), with `nt` loads: the
+// table is read once and nothing of it is worth keeping.  The 4 * MT fragments of the NEXT chunk are requested before this
+// chunk's barriers and MFMAs (rows are 2*D bytes apart: their round trips have to overlap), so every feature byte is read
+// exactly once and 2 * 4 * MT loads per lane are in flight.  Rows past n: their lanes re-read row n - 1 and are never stored.
+// The chunk order is fixed (no rotation per workgroup): a row's sums run in the order of k whatever the row's position, the
+// tile it falls in or n -- the same feature row gives the same bits everywhere.
+// ------------------------------------------------------------------------------------------------------------
+template <int NT, int MT>
+__global__ __launch_bounds__(256) void k_proj_new_bf16(const uint16_t *__restrict__ F, int n, int D,
+                                                       const uint16_t *__restrict__ Et, float *__restrict__ P) {
+  __shared__ __attribute__((aligned(16))) uint16_t Bs[NT * 16 * BS_STRIDE];
+  constexpr int KS = KC / 32, PS = NT * 16;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  const int row0 = (blockIdx.x * 4 + w) * MT * 16;
+  const int nchunks = D / KC;
+  const uint16_t *arow[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    int t = row0 + mt * 16 + r;
+    if (t >= n) t = n - 1;                              // padding lanes re-read the last row; never stored
+    arow[mt] = F + (size_t)t * D + q * 8;
+  }
+  f32x4 acc[MT][NT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  i32x4_t a[KS][MT], an[KS][MT];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) a[ks][mt] = an[ks][mt] = ld_stream16<true>(arow[mt] + ks * 32);
+
+  for (int cc = 0; cc < nchunks; ++cc) {
+    const int k0 = cc * KC;
+    if (cc + 1 < nchunks) {                             // (uniform) the next chunk's feature fragments, before anything waits
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) an[ks][mt] = ld_stream16<true>(arow[mt] + k0 + KC + ks * 32);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < NT * 16 * (KC / 8); idx += 256) {
+      const int nn = idx / (KC / 8), kk = (idx % (KC / 8)) * 8;
+      *reinterpret_cast<uint4 *>(&Bs[nn * BS_STRIDE + kk]) = *reinterpret_cast<const uint4 *>(&Et[et_idx(nn, k0 + kk, PS)]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const bf16x8 b = *reinterpret_cast<const bf16x8 *>(&Bs[(nt * 16 + r) * BS_STRIDE + ks * 32 + q * 8]);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+          acc[mt][nt] = mfma_frag<false>(a[ks][mt], __builtin_bit_cast(i32x4_t, b), acc[mt][nt]);
+      }
+    }
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) a[ks][mt] = an[ks][mt];
+  }
+  // C/D layout of 16x16 MFMA: col = lane & 15, row = (lane >> 4)*4 + reg
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int t = row0 + mt * 16 + q * 4 + reg;
+      if (t < n) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) P[(size_t)t * PS + nt * 16 + r] = acc[mt][nt][reg];
+      }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // forward over a ROW LIST (sparse batches: the batch's distinct items; bprx_score_pairs: one row per pair).  Few rows,
 // so the parallelism has to come from K: one NW-wave workgroup per MT*16 listed rows and NTW column tiles, the waves
 // split the k-chunks round-robin (wave w: chunks w, w+NW, ...).  Every wave loads its A fragments (feature rows of the
@@ -1545,6 +1626,41 @@ int bprx_launch_proj_fwd(bprx_handle *h, const int32_t *rows, int64_t nrows, con
     }
     BPRX_LAUNCH_CHECK(h, "k_proj_fwd_f32");
   }
+  return BPRX_OK;
+}
+
+// P = Fnew.[E|Bp] for a caller's row-major table of n > 0 rows (bprx_project_rows).  bf16: k_proj_new_bf16, two row tiles per wave
+// up to nine column tiles (the register budget of k_proj_fwd_bf16); the image Et is current (bprx_launch_cast_Et).  fp32: the
+// kernels of the catalogue take a table pointer and a row count; they write columns [0, d] only, the padding is cleared first.
+namespace {
+template <int NT>
+void launch_proj_new(bprx_handle *h, const uint16_t *Fnew, int64_t n, float *P, hipStream_t s) {
+  constexpr int MT = NT <= 9 ? 2 : 1;
+  dim3 grid((unsigned)((n + 4 * MT * 16 - 1) / (4 * MT * 16)));
+  hipLaunchKernelGGL((k_proj_new_bf16<NT, MT>), grid, dim3(256), 0, s, Fnew, (int)n, h->cfg.feat_dim, (const uint16_t *)h->Et, P);
+}
+}  // namespace
+
+int bprx_launch_proj_new(bprx_handle *h, const void *Fnew, int64_t n, float *P, hipStream_t s) {
+  const int D = h->cfg.feat_dim, d = h->cfg.embed_d;
+  if (h->cfg.feat_dtype == BPRX_F_BF16) {
+#define CALL(N) launch_proj_new<N>(h, (const uint16_t *)Fnew, n, P, s)
+    NT_SWITCH(h->PS / 16, CALL)
+#undef CALL
+    BPRX_LAUNCH_CHECK(h, "k_proj_new_bf16");
+    return BPRX_OK;
+  }
+  if (h->PS > d + 1) BPRX_HIP(h, hipMemsetAsync(P, 0, (size_t)n * h->PS * sizeof(float), s));
+  if (D % 16 == 0) {
+    dim3 grid((unsigned)((n + 15) / 16), (unsigned)((d + 1 + 15) / 16));
+    hipLaunchKernelGGL(k_proj_fwd_f32_mfma, grid, dim3(1024), 0, s, (const float *)Fnew, (const int32_t *)nullptr, (int)n,
+                       (const int32_t *)nullptr, 0, (int)n, D, h->t.E, h->t.Bp, d, P, h->PS, h->errflag);
+  } else {
+    dim3 grid((unsigned)((n + 3) / 4));
+    hipLaunchKernelGGL(k_proj_fwd_f32, grid, dim3(256), 0, s, (const float *)Fnew, (const int32_t *)nullptr, (int)n,
+                       (const int32_t *)nullptr, 0, (int)n, D, h->t.E, h->t.Bp, d, P, h->PS, h->errflag);
+  }
+  BPRX_LAUNCH_CHECK(h, "k_proj_fwd_f32<new>");
   return BPRX_OK;
 }
 

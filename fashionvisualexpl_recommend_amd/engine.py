@@ -408,6 +408,69 @@ class Engine:
                                                       p(out["map"]) if maps else None, _stream()))
         return out
 
+    # ---- items outside the catalogue (include/bprx.h: x_uj = Tu_u.(f_j E) + f_j.Bp, no Gi / Bi term) --------------------------
+    def _new_table(self, F):
+        """A [n, feat_dim] table of new items as a contiguous device tensor of the engine's feature dtype, quantised as bind does
+        (an fp8 engine: left in fp32 -- the library rejects the call, BPRX_E_INVALID)."""
+        Ft = torch.as_tensor(F)
+        if self.model == "vbpr" and (Ft.dim() != 2 or Ft.shape[1] != self.D):
+            raise ValueError("new items: the table must be [n, %d], got %s" % (self.D, tuple(Ft.shape)))
+        return Ft.to(device=self.device, dtype=torch.bfloat16 if self.feat_dtype == "bf16" else torch.float32).contiguous()
+
+    def proj_stride(self):
+        return int(_ffi.check(self.h, self.lib.bprx_proj_stride(self.h)))
+
+    def project_rows(self, F):
+        """bprx_project_rows: P fp32 [n, proj_stride()] = F.[E|Bp|0] for the rows of a [n, feat_dim] table of items the model was
+        not trained on (normalised like the training table; quantised here as bind quantises)."""
+        Ft = self._new_table(F)
+        n = int(Ft.shape[0])
+        P = torch.empty((n, self.proj_stride()), dtype=torch.float32, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        _ffi.check(self.h, self.lib.bprx_project_rows(self.h, p(Ft), n, p(P), _stream()))
+        return P
+
+    def score_new_block(self, u0, u1, P, out=None):
+        """bprx_score_new_block: fp32 [u1-u0, n], out[u][j] = Tu_u.P[j, :d] + P[j, d] for P = project_rows(F)."""
+        n = int(P.shape[0])
+        if out is None:
+            out = torch.empty((u1 - u0, n), dtype=torch.float32, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        _ffi.check(self.h, self.lib.bprx_score_new_block(self.h, int(u0), int(u1), p(P), n, p(out), _stream()))
+        return out
+
+    def topk_rows(self, scores, K):
+        """bprx_topk_rows: bprx_topk's lists for the rows of a contiguous fp32 [nrows, width] device tensor, nothing masked:
+        (idx int32 [nrows, K], val fp32 [nrows, K], flag int32 [nrows])."""
+        nrows, width = (int(x) for x in scores.shape)
+        K = int(K)
+        idx = torch.empty((nrows, max(K, 0)), dtype=torch.int32, device=self.device)
+        val = torch.empty((nrows, max(K, 0)), dtype=torch.float32, device=self.device)
+        flag = torch.empty(nrows, dtype=torch.int32, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        _ffi.check(self.h, self.lib.bprx_topk_rows(self.h, nrows, width, p(scores), K, p(idx), p(val), p(flag), _stream()))
+        return idx, val, flag
+
+    def feat_explain_new(self, F, user, row, top=5, ncols=None, maps=False):
+        """bprx_feat_explain_new: feat_explain for the pairs (user[p], row[p] of the new-item table F).  There is no base: the dict
+        holds score (== visual, the same tensor) [n], col int32 and contrib [n, top], with maps=True also map [n, ncols]."""
+        Ft = self._new_table(F)
+        u, r = as_index(user, self.device), as_index(row, self.device)
+        if u.numel() != r.numel():
+            raise ValueError("feat_explain_new: %d users for %d rows" % (u.numel(), r.numel()))
+        n, top = u.numel(), int(top)
+        ncols = self.D if ncols is None else int(ncols)
+        f = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)
+        out = {"score": f(n), "col": torch.empty((n, max(top, 0)), dtype=torch.int32, device=self.device), "contrib": f(n, max(top, 0))}
+        out["visual"] = out["score"]
+        if maps:
+            out["map"] = f(n, max(ncols, 0))
+        p = lambda t: C.c_void_p(t.data_ptr())
+        _ffi.check(self.h, self.lib.bprx_feat_explain_new(self.h, p(Ft), int(Ft.shape[0]), p(u), p(r), n, ncols, top, p(out["score"]),
+                                                          p(out["col"]), p(out["contrib"]), p(out["map"]) if maps else None,
+                                                          _stream()))
+        return out
+
     def tables_dirty(self):
         """Call after writing any bound table from outside the library (bprx_tables_dirty): the handle reuses images
         derived from E/Bp (their bf16/fp8 copy, the item projections) until a step changes them."""

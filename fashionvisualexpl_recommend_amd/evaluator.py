@@ -246,6 +246,32 @@ class Evaluator:
         with open(path_recs, 'w') as out, open(path_expl, 'w') as ex:
             self._store_recommendation_rows(out, lambda users, items: self._write_feature_rows(ex, users, items, top))
 
+    def store_recommendation_new(self, path="", features=None, path_expl=None, top=0):
+        """VBPR / GradFashion: the top-k NEW items of every user (model.recommend_new: the visual score, nothing masked) as rows
+        'u\\tj\\tscore', j = the row of `features` (raw rows, as model.prepare_new_items takes them), best first, formatted as
+        store_recommendation formats them.  path_expl with top > 0: also 'u\\tj\\tscore\\trank\\tcolumn\\tcontribution' for
+        the same pairs in the same order, rank 0 first, one row per rank below min(top, feature columns); there is no base."""
+        m = self.model
+        F = m.prepare_new_items(features)
+        U = m.data.num_users
+        with open(path, 'w') as out, (open(path_expl, 'w') if path_expl and top > 0 else contextlib.nullcontext()) as ex:
+            for u0 in range(0, U, self.user_block):
+                u1 = min(U, u0 + self.user_block)
+                res = m.recommend_new(F, self.k, u0, u1, explain=top if ex is not None else 0)
+                idx, val = res[0], res[1]
+                for r in range(u1 - u0):
+                    for q in range(idx.shape[1]):
+                        out.write(str(u0 + r) + '\t' + str(idx[r, q]) + '\t' + str(val[r, q]) + '\n')
+                if ex is None or not idx.size:
+                    continue
+                e, kk = res[2], idx.shape[1]
+                for p in range(e["col"].shape[0]):
+                    head = str(u0 + p // kk) + '\t' + str(idx[p // kk, p % kk]) + '\t' + str(e["score"][p]) + '\t'
+                    for s in range(e["col"].shape[1]):
+                        if e["col"][p, s] < 0:
+                            break
+                        ex.write(head + str(s) + '\t' + str(e["col"][p, s]) + '\t' + str(e["contrib"][p, s]) + '\n')
+
     def store_recommendation_grads(self, path="", path_expl=None, top=5):
         """Evaluator.py:261-275 (GradFashion): for every user the items training_list[u] + validation_list[u] + test_list[u],
         in that order, one row 'u\\ti\\tcolour\\tedges' each (get_explanations.py:19-21 reads USER_ID, ITEM_ID, COLOR, EDGES).

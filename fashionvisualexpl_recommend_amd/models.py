@@ -251,7 +251,8 @@ class VBPR(BPRMF):
             f = np.load(configs.cnn_features_path(self.params.dataset, getattr(self.params, "cnn_model", "vgg19"),
                                                   getattr(self.params, "output_layer", "fc2")))
         f = np.asarray(f)
-        self.cnn_features = f / np.max(np.abs(f))
+        self.feat_norm = np.max(np.abs(f))                                      # kept: new items are divided by the same value
+        self.cnn_features = f / self.feat_norm
         self.dim_cnn_features = self.cnn_features.shape[1]
 
     def _init_tables(self, init):
@@ -295,12 +296,95 @@ class VBPR(BPRMF):
         return self.explain([int(u)] * len(items), items, top, maps)
 
     def _store_recs(self, path):
-        """recs-* / best-recs-* as every model writes them; with params.feat_explain = L > 0 also expl-* / best-expl-* next to them."""
+        """recs-* / best-recs-* as every model writes them; with params.feat_explain = L > 0 also expl-* / best-expl-* next to them;
+        with params.new_items also new-recs-* (and new-expl-*) for the items of those files."""
+        d, f = os.path.split(path)
         if self.feat_explain <= 0:
             super()._store_recs(path)
+        else:
+            self.evaluator.store_recommendation_features(path, os.path.join(d, f.replace("recs-", "expl-", 1)), self.feat_explain)
+        self._store_new_recs(path)
+
+    # ---- items the model was not trained on: x_uj = Tu_u.(f_j E) + f_j.Bp, no Gi_j / Bi_j term (include/bprx.h) ---------------
+    NORM_KEYS = ("feat_norm",)                                                  # the divisors of the training tables, in snapshots
+
+    def state_dict(self):
+        sd = super().state_dict()
+        for n in self.NORM_KEYS:
+            sd[n] = torch.as_tensor(np.asarray(getattr(self, n)))
+        return sd
+
+    def load_state_dict(self, sd):
+        sd = dict(sd)
+        for n in self.NORM_KEYS:                                                # (a snapshot from before the keys: the model's own)
+            v = sd.pop(n, None)
+            if v is not None:
+                setattr(self, n, torch.as_tensor(v).cpu().numpy()[()])
+        super().load_state_dict(sd)
+
+    def _new_item_table(self, features):
+        """[n, dim_cnn_features] float32: the raw rows divided by the training divisor (VBPR's table has no padding columns)."""
+        return normalize_new_rows(features, self.feat_norm, self.dim_cnn_features, "features")
+
+    def prepare_new_items(self, features):
+        """Raw feature rows of items outside the catalogue (as the training file holds them, before any normalisation) -> the device
+        table Engine.project_rows / feat_explain_new take: divided by the TRAINING divisor (a row may then exceed 1), float32, laid
+        out like the training table, in the engine's feature dtype.  A raw row equal to a training row gives a bit-equal table row."""
+        if getattr(self.params, "dtype", "fp32") == "fp8":
+            raise ValueError("%s: new items need --dtype fp32 or bf16 (an fp8 table is scaled for the training max-abs: a new row "
+                             "may saturate)" % type(self).__name__)
+        return self.engine._new_table(self._new_item_table(features))
+
+    def _as_new_table(self, features):
+        return features if isinstance(features, torch.Tensor) and features.is_cuda else self.prepare_new_items(features)
+
+    def score_new_items(self, features, u0=0, u1=None):
+        """Device fp32 [u1-u0, n]: the visual score of every user of [u0, u1) for the n new items (raw rows, or a table from
+        prepare_new_items)."""
+        u1 = self.num_users if u1 is None else u1
+        return self.engine.score_new_block(u0, u1, self.engine.project_rows(self._as_new_table(features)))
+
+    def recommend_new(self, features, k=None, u0=0, u1=None, explain=0):
+        """The k (default top_k) best new items of every user of [u0, u1): numpy idx int [nu, min(k, n)] (row of `features`) and val,
+        best first; explain = L > 0: also the Engine.feat_explain_new dict (numpy) of those pairs, user by user.  Rows whose list
+        depends on the order of equal scores are redone with numpy on the GPU's row, as Evaluator.store_recommendation does."""
+        eng = self.engine
+        F = self._as_new_table(features)
+        n = int(F.shape[0])
+        k = self.evaluator.k if k is None else int(k)
+        u1 = self.num_users if u1 is None else u1
+        P = eng.project_rows(F)
+        kk = min(k, n)
+        idx_all, val_all = np.zeros((u1 - u0, kk), np.int64), np.zeros((u1 - u0, kk), np.float32)
+        blk = max(1, min(self.evaluator.user_block, (1 << 27) // max(1, n)))
+        for b0 in range(u0, u1, blk):
+            b1 = min(u1, b0 + blk)
+            sc = eng.score_new_block(b0, b1, P)
+            idx, val, flag = (x.cpu().numpy() for x in eng.topk_rows(sc, k))
+            idx_all[b0 - u0:b1 - u0], val_all[b0 - u0:b1 - u0] = idx[:, :kk], val[:, :kk]
+            for r in np.nonzero(flag)[0]:
+                row = sc[int(r)].cpu().numpy()
+                top_k_id = row.argsort()[-k:][::-1]
+                idx_all[b0 - u0 + r], val_all[b0 - u0 + r] = top_k_id, row[top_k_id]
+        if explain <= 0:
+            return idx_all, val_all
+        users = np.repeat(np.arange(u0, u1), kk)
+        ex = eng.feat_explain_new(F, users, idx_all.reshape(-1), explain, self.feat_cols) if users.size else None
+        return idx_all, val_all, ({} if ex is None else {nm: v.cpu().numpy() for nm, v in ex.items() if nm != "visual"})
+
+    def _load_new_items(self):
+        paths = list(getattr(self.params, "new_items", None) or [])
+        return np.load(paths[0]) if paths else None
+
+    def _store_new_recs(self, path):
+        """params.new_items: new-recs-* (with feat_explain also new-expl-*) next to the recs-* file at `path`."""
+        feats = self._load_new_items()
+        if feats is None:
             return
         d, f = os.path.split(path)
-        self.evaluator.store_recommendation_features(path, os.path.join(d, f.replace("recs-", "expl-", 1)), self.feat_explain)
+        new = f.replace("recs-", "new-recs-", 1)
+        expl = os.path.join(d, new.replace("recs-", "expl-", 1)) if self.feat_explain > 0 else None
+        self.evaluator.store_recommendation_new(os.path.join(d, new), feats, expl, self.feat_explain)
 
 
 class GradFashion(VBPR):
@@ -326,13 +410,15 @@ class GradFashion(VBPR):
         f = self._features[1] if self._features is not None else np.load(configs.edge_features_path(
             self.params.dataset, getattr(self.params, "cnn_model", "vgg19"), getattr(self.params, "output_layer", "fc2")))
         f = np.asarray(f)
-        self.edge_features = f / np.max(np.abs(f))
+        self.edge_norm = np.max(np.abs(f))
+        self.edge_features = f / self.edge_norm
         self.dim_edge_features = self.edge_features.shape[1]
 
     def process_color_visual_features(self):
         f = self._features[0] if self._features is not None else np.load(configs.hist_color_features_path(self.params.dataset))
         f = np.asarray(f)
-        self.color_features = f / np.max(np.abs(f))
+        self.color_norm = np.max(np.abs(f))
+        self.color_features = f / self.color_norm
         self.dim_color_features = self.color_features.shape[1]
 
     def padded_features(self):
@@ -426,6 +512,36 @@ class GradFashion(VBPR):
         d, f = os.path.split(path)
         expl = os.path.join(d, f.replace("recs-", "expl-", 1)) if self.feat_explain > 0 else None
         self.evaluator.store_recommendation_grads(path=path, path_expl=expl, top=self.feat_explain)
+        self._store_new_recs(path)
+
+    NORM_KEYS = ("color_norm", "edge_norm")
+
+    def _new_item_table(self, features):
+        """(colour rows, edge rows) -> [n, dim_cnn_features] float32 [Fc | Fe | 0], each table divided by its own training divisor."""
+        if not isinstance(features, (tuple, list)) or len(features) != 2:
+            raise ValueError("GradFashion: new items are a pair (colour rows, edge rows)")
+        Dc, De = self.dim_color_features, self.dim_edge_features
+        Fc = normalize_new_rows(features[0], self.color_norm, Dc, "colour features")
+        Fe = normalize_new_rows(features[1], self.edge_norm, De, "edge features")
+        if Fc.shape[0] != Fe.shape[0]:
+            raise ValueError("GradFashion: %d colour rows for %d edge rows" % (Fc.shape[0], Fe.shape[0]))
+        F = np.zeros((Fc.shape[0], self.dim_cnn_features), np.float32)
+        F[:, :Dc], F[:, Dc:Dc + De] = Fc, Fe
+        return F
+
+    def _load_new_items(self):
+        paths = list(getattr(self.params, "new_items", None) or [])
+        return tuple(np.load(p) for p in paths) if paths else None
+
+
+def normalize_new_rows(raw, norm, width, what="features"):
+    """Raw feature rows of new items -> float32 [n, width]: np.asarray(raw) / norm, the arithmetic the training table
+    went through (visual_loader_mixin.py:22-31 with the TRAINING max-abs `norm`), then the cast the tables get.  Equal raw rows
+    give bit-equal rows.  ValueError unless raw is [n, width]."""
+    raw = np.asarray(raw)
+    if raw.ndim != 2 or raw.shape[1] != width:
+        raise ValueError("new items: %s must be [n, %d], got %s" % (what, width, raw.shape))
+    return (raw / norm).astype(np.float32)
 
 
 def _glorot_1d(rs, n):

@@ -58,6 +58,11 @@ def parse_args(argv=None):
     parser.add_argument('--feat_explain', type=int, default=0,
                         help="vbpr, grad_fashion: also write expl-* / best-expl-* files with the L (1..32) feature columns that "
                              "contribute most to every written (u, i): column and contribution F_ic w_uc, rank 0 first; 0 = off")
+    parser.add_argument('--new_items', nargs='+', default=None, metavar='PATH',
+                        help="vbpr: one .npy of raw feature rows [n, D]; grad_fashion: two, colour then edges.  Items the model was "
+                             "not trained on: also write new-recs-* / best-new-recs-* files with every user's top-k of them by the "
+                             "visual score Tu.(fE) + f.Bp (rows divided by the training max-abs), and with --feat_explain L also "
+                             "new-expl-* / best-new-expl-*")
     # not in the reference
     parser.add_argument('--dropout', type=float, default=0.5,
                         help="attentive_fashion: rate of the encoders' Dropout layers (AttentiveFashion.py:53,62,70: 0.5)")
@@ -96,6 +101,13 @@ def parse_args(argv=None):
         parser.error("--feat_explain takes 0 (off) .. 32 (got %s)" % args.feat_explain)
     if args.feat_explain != 0 and args.rec not in ('vbpr', 'grad_fashion'):
         parser.error("--feat_explain %s needs --rec vbpr or grad_fashion (got --rec %s)" % (args.feat_explain, args.rec))
+    if args.new_items is not None:
+        want = {'vbpr': 1, 'grad_fashion': 2}.get(args.rec)
+        if want is None:
+            parser.error("--new_items needs --rec vbpr or grad_fashion (got --rec %s)" % args.rec)
+        if len(args.new_items) != want:
+            parser.error("--new_items takes %d path%s with --rec %s (got %d)" % (want, "s" if want > 1 else "", args.rec,
+                                                                                 len(args.new_items)))
     if not 0.0 <= args.dropout < 1.0:
         parser.error("--dropout takes a rate in [0, 1) (got %s)" % args.dropout)
     return args
@@ -107,6 +119,11 @@ def train(argv=None):
         raise NotImplementedError('--rec grad_fashion runs on one GPU (no multi-GPU form): use --world_size 1')
     if args.feat_explain != 0 and int(args.world_size) > 1:
         raise NotImplementedError('--feat_explain runs on one GPU (the sharded drivers write no expl-* files): use --world_size 1')
+    if args.new_items is not None and int(args.world_size) > 1:
+        raise NotImplementedError('--new_items runs on one GPU (the sharded drivers write no new-recs-* files): use --world_size 1')
+    if args.new_items is not None and args.dtype == 'fp8':
+        raise ValueError('--new_items runs with --dtype fp32 or bf16 (an fp8 table is scaled for the training max-abs: a new row '
+                         'may saturate)')
     if args.rec == 'acf' and int(args.world_size) > 1:
         raise NotImplementedError('--rec acf runs on one GPU (no multi-GPU form): use --world_size 1')
     if args.rec == 'acf' and args.dtype not in ('fp32', 'bf16'):

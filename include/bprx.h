@@ -195,6 +195,45 @@ BPRX_API int bprx_feat_explain(bprx_handle *h, const void *F, const int32_t *use
                                int32_t top, float *score, float *base, float *visual, int32_t *col, float *contrib, float *map,
                                void *stream);
 
+/* ---- VBPR and GradFashion: items the model was not trained on ------------------------------------------------------------
+   An item that is not in the bound catalogue has no Gi_j and no Bi_j; what the trained weights say about it is the visual part
+   of the score (the cold-start score of the VBPR paper):
+       x_uj = Tu_u.(f_j E) + f_j.Bp
+   (a factored handle: E_eff / Bp_eff).  The five calls below score, rank and explain the n rows of a caller-owned ROW-MAJOR
+   device table Fnew [n, feat_dim] of the handle's feat_dtype, normalised by the caller as the training table was.
+   Handles: a bound VBPR handle, plain or factored, with fp32 or bf16 features.  BPRX_E_INVALID for a NULL handle, a BPRMF, ACF or
+   AttentiveFashion handle, an fp8 handle (a new row may exceed the max-abs the codes were scaled for and would saturate), a NULL
+   pointer, n < 0, n >= 2^31; BPRX_E_STATE for an unbound handle; n == 0 / u0 == u1: BPRX_OK, nothing is touched.  After any error
+   the handle stays usable.
+   State: bprx_project_rows, bprx_score_new_block and bprx_feat_explain_new bring lazy adam_tf23 rows up to date first (they read
+   Tu, E, Bp) and make the bf16 image of [E|Bp]^T current where the step has not left it so (the image every projection of the
+   handle reads); apart from that they write their outputs only.  No table, Adam slot, step counter or cached projection
+   changes, nothing is allocated: a training run with these calls between its steps ends bit-identical to one without them. */
+/* PS = 16 * ceil((embed_d + 1) / 16), the row stride of P below; negative (BPRX_E_INVALID) for a NULL or non-VBPR handle. */
+BPRX_API int32_t bprx_proj_stride(const bprx_handle *h);
+/* P[j, 0:d] = f_j.E, P[j, d] = f_j.Bp, P[j, d+1:PS] = 0 for the n rows of Fnew.  P: fp32 [n, PS], caller-owned.
+   bf16 features (k_proj_new_bf16): one pass over the table, every feature byte read once, against the SAME bf16-rounded
+   [E|Bp] that projects the catalogue (fp32 accumulation): new and old items sit on one scale.  fp32 features: the fp64-accumulating
+   kernels of the catalogue.  A row's result depends on its own bytes, E and Bp only: the same feature row gives the same bits
+   wherever it stands in the table and whatever n is. */
+BPRX_API int bprx_project_rows(bprx_handle *h, const void *Fnew, int64_t n, float *P, void *stream);
+/* out fp32 [(u1-u0), n]: out[u][j] = Tu_u.P[j, 0:d] + P[j, d] (P from bprx_project_rows): the fp32 MFMA GEMM of
+   bprx_score_block, exact fp32 products.  0 <= u0 <= u1 <= num_users. */
+BPRX_API int bprx_score_new_block(bprx_handle *h, int32_t u0, int32_t u1, const float *P, int64_t n, float *out, void *stream);
+/* bprx_topk on nrows rows of explicit `width` (row stride width), nothing masked: the K (1..1024) largest scores of each row
+   best first, idx int32 [nrows, K] (-1 past min(K, width)), val fp32 same shape, flag int32 [nrows] with the selection, order
+   and flag rules of bprx_topk.  1 <= width < 2^31. */
+BPRX_API int bprx_topk_rows(bprx_handle *h, int64_t nrows, int32_t width, float *scores, int32_t K, int32_t *idx, float *val,
+                            int32_t *flag, void *stream);
+/* bprx_feat_explain for the pairs (user[p], row[p] of Fnew [n_new, feat_dim]): contributions F_jc w_uc, w_uc = Bp[c] + E[c,:].Tu_u
+   from the fp32 master tables.  There is no base: score is the sum of the contributions (what bprx_feat_explain calls visual).
+   Outputs, order and tie rules, limits (ncols, top, feat_dim) and bit-level guarantees as for bprx_feat_explain: score fp32 [n],
+   col int32 / contrib fp32 [n, top], map fp32 [n, ncols] or NULL.  user >= num_users and row >= n_new are clamped and reported by
+   bprx_sync_check (BPRX_E_RANGE).  With bf16 features score differs from bprx_score_new_block by the rounding of [E|Bp] there. */
+BPRX_API int bprx_feat_explain_new(bprx_handle *h, const void *Fnew, int64_t n_new, const int32_t *user, const int32_t *row,
+                                   int64_t n, int32_t ncols, int32_t top, float *score, int32_t *col, float *contrib, float *map,
+                                   void *stream);
+
 /* ---- ACF (ACF.py:20-270) on a BPRMF handle ------------------------------------------------------------------------------
    Attentive Collaborative Filtering over per-item feature maps f_l [M, C] (M = H*W spatial components).  For user u with
    history P(u) (ACF.py:135-181):
