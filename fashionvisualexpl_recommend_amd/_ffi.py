@@ -80,6 +80,8 @@ class Tables(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in TABLE_FIELDS]
 
 
+DEFER_ENTRIES = ("bprx_settle", "bprx_dense_pending", "bprx_set_loss_lag")    # the deferred dense update (include/bprx.h)
+
 _lib = None
 
 
@@ -182,8 +184,13 @@ def lib():
         "bprx_sampler_destroy": (C.c_int, [vp]),
         "bprx_sampler_count": (i64, [vp, i32, i32]),
         "bprx_sampler_ref_stream": (i64, [vp, i32, i32, u32, u32, vp, vp, vp, i64]),
+        "bprx_settle": (C.c_int, [vp, vp]),
+        "bprx_dense_pending": (C.c_int, [vp]),
+        "bprx_set_loss_lag": (C.c_int, [vp, C.c_int]),
     }
     for name, (res, args) in sig.items():
+        if name in DEFER_ENTRIES and not hasattr(L, name):
+            continue                # an older build named by BPRX_LIB (A/B runs): it never defers, the engine skips these calls
         fn = getattr(L, name)       # AttributeError here == header/library mismatch: fail loudly
         fn.restype, fn.argtypes = res, args
     if L.bprx_abi_version() != ABI_VERSION:
@@ -202,7 +209,7 @@ EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error",
            "bprx_route_scatter_add", "bprx_score_block", "bprx_eval_users", "bprx_eval_pos", "bprx_eval_counts", "bprx_eval_finish", "bprx_topk", "bprx_sync_check", "bprx_probe_stream_read", "bprx_probe_stream_read_nt", "bprx_probe_row_gather", "bprx_profile_enable",
            "bprx_profile_read", "bprx_sample_philox", "bprx_epoch_prepare", "bprx_epoch_slots", "bprx_sample_epoch", "bprx_sample_philox_h", "bprx_sample_epoch_h", "bprx_index_pass_kind", "bprx_proj_mask_kind", "bprx_adam_rows", "bprx_step_lr", "bprx_user_msg_floats", "bprx_pack_user_msg",
            "bprx_apply_user_msgs", "bprx_sampler_create",
-           "bprx_sampler_destroy", "bprx_sampler_count", "bprx_sampler_ref_stream"]
+           "bprx_sampler_destroy", "bprx_sampler_count", "bprx_sampler_ref_stream", "bprx_settle", "bprx_dense_pending", "bprx_set_loss_lag"]
 
 
 def check(handle, rc):

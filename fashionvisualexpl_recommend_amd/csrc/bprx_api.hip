@@ -132,6 +132,9 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
     // the masked backward pass is slower where the MFMAs pace it, c2fp8 49.3 -> 53.0 us, c5 944 -> 1 139 us, and a table that
     // sits in the Infinity Cache has no HBM bytes to save); 2 wherever a masked form exists
     h->proj_mask = std::min(std::max(env_int("BPRX_PROJ_MASK", 1), 0), 2);
+    // BPRX_DENSE_DEFER: a bprx_step that is not asked for its loss leaves its dense E|Bp update to the next step's index pass
+    // (k_index_seg hosts it on the CUs its owners leave idle).  0: the stand-alone kernel at the end of every step.
+    h->dense_defer = env_int("BPRX_DENSE_DEFER", 1) != 0;
     A.zeros(&h->dTu, U * d);
     A.zeros(&h->P, I * PS);
     A.zeros(&h->W, I * PS);
@@ -212,6 +215,7 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
 extern "C" int bprx_destroy(bprx_handle *h) {
   if (!h) return BPRX_OK;
   (void)hipSetDevice(h->cfg.device);
+  h->pend.on = false;                                      // a pending dense update is dropped: its tables are the caller's
   if (h->side) (void)hipStreamSynchronize(h->side);
   (void)h->mem.rollback(0);
   bprx_acf_free(h);
@@ -259,6 +263,7 @@ static int bind_tables(bprx_handle *h, const bprx_tables *t, bool factored) {
   }
   if (((uintptr_t)t->Gu | (uintptr_t)t->Gi | (uintptr_t)t->Tu | (uintptr_t)t->F | (uintptr_t)t->E) & 15)
     BPRX_FAIL(h, BPRX_E_INVALID, "bind_tables: table base pointers must be 16-byte aligned");
+  { const int rc = bprx_settle_pending(h, nullptr); if (rc) return rc; }   // (on the tables bound so far; the null stream as below)
   h->t = *t;
   h->factored = factored;
   if (!factored) h->neg_bias_reg = 0.1f;
@@ -318,6 +323,7 @@ extern "C" int bprx_bind_factored(bprx_handle *h, const bprx_tables *t, const bp
 extern "C" int bprx_explain_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t n, float *out, void *stream) {
   int rc = check_ready(h, 0);
   if (rc) return rc;
+  if ((rc = bprx_settle_pending(h, (hipStream_t)stream))) return rc;
   if (!h->factored) BPRX_FAIL(h, BPRX_E_STATE, "explain_pairs: the handle is not bound with bprx_bind_factored");
   if (n < 0 || n > ((int64_t)1 << 32)) BPRX_FAIL(h, BPRX_E_INVALID, "explain_pairs: n = %lld out of range", (long long)n);
   if (n == 0) return BPRX_OK;
@@ -329,6 +335,7 @@ extern "C" int bprx_explain_pairs(bprx_handle *h, const int32_t *user, const int
 
 extern "C" int bprx_tables_dirty(bprx_handle *h, void *stream) {
   if (!h) return BPRX_E_INVALID;
+  { const int rc = bprx_settle_pending(h, (hipStream_t)stream); if (rc) return rc; }
   h->et_valid = h->p_valid = h->absmax_valid = false;
   if (h->acf) bprx_acf_invalidate(h);                      // ACF: the evaluation profiles follow the tables
   if (h->af) bprx_af_invalidate(h);                        // AttentiveFashion: so do the item encodings
@@ -350,6 +357,7 @@ extern "C" int bprx_set_hyper(bprx_handle *h, float lr, float reg) {
 
 extern "C" int bprx_set_adam_step(bprx_handle *h, int64_t it, void *stream) {
   if (!h || it < 0) return BPRX_E_INVALID;
+  { const int rc = bprx_settle_pending(h, (hipStream_t)stream); if (rc) return rc; }
   h->adam_t = it;
   return h->bound ? bprx_launch_adam_reset(h, it, (hipStream_t)stream) : BPRX_OK;
 }
@@ -364,9 +372,33 @@ static int check_ready(bprx_handle *h, int64_t B) {
   return BPRX_OK;
 }
 
+// A deferred dense update runs now, on the stream of the call that needs it, and its lagging loss behind it.
+int bprx_settle_pending(bprx_handle *h, hipStream_t s) {
+  if (!h || !h->pend.on) return BPRX_OK;
+  const DensePending q = h->pend;
+  h->pend.on = false;
+  int rc = bprx_launch_dense_args(h, q.a, s);
+  if (!rc && q.loss_out) rc = bprx_launch_loss_reduce_at(h, q.loss_B, q.loss_nsq, q.loss_reg, q.loss_out, s);
+  return rc;
+}
+
+extern "C" int bprx_settle(bprx_handle *h, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  return bprx_settle_pending(h, (hipStream_t)stream);
+}
+
+extern "C" int bprx_dense_pending(const bprx_handle *h) { return h ? (h->pend.on ? 1 : 0) : BPRX_E_INVALID; }
+
+extern "C" int bprx_set_loss_lag(bprx_handle *h, int on) {
+  if (!h) return BPRX_E_INVALID;
+  h->loss_lag = on != 0;
+  return BPRX_OK;
+}
+
 extern "C" int bprx_sync_adam(bprx_handle *h, void *stream) {
   int rc = check_ready(h, 0);
   if (rc) return rc;
+  if ((rc = bprx_settle_pending(h, (hipStream_t)stream))) return rc;
   return bprx_launch_adam_sync(h, h->adam_t, (hipStream_t)stream);
 }
 
@@ -376,6 +408,7 @@ extern "C" int bprx_score_pairs(bprx_handle *h, const int32_t *user, const int32
   if (B == 0) return BPRX_OK;
   if (!user || !item || !x) BPRX_FAIL(h, BPRX_E_INVALID, "score_pairs: null pointer");
   hipStream_t s = (hipStream_t)stream;
+  if ((rc = bprx_settle_pending(h, s))) return rc;
   if (h->acf) return bprx_acf_score_pairs(h, user, item, B, x, s);
   if (h->af) return bprx_af_pairs(h, user, item, B, x, nullptr, s);
   if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: the rows must be current
@@ -413,6 +446,11 @@ static int launch_sparse_half(bprx_handle *h, const StepPlan &p, hipStream_t s) 
   } else if (p.catchup && (rc = bprx_launch_adam_catchup(h, p, s))) return rc;
   if (p.project && p.list_mode && (rc = bprx_launch_cast_Et(h, s))) return rc;
   if (p.index_first && (rc = bprx_launch_index_pass(h, p, s))) return rc;      // list: counts + the distinct-item list
+  if (p.carry_dense) {                                   // the pending update ran in that launch; its lagging loss right behind it,
+    const DensePending q = h->pend;                      // before k_triplet_seg rewrites lossb
+    h->pend.on = false;
+    if (q.loss_out && (rc = bprx_launch_loss_reduce_at(h, q.loss_B, q.loss_nsq, q.loss_reg, q.loss_out, s))) return rc;
+  }
   if (p.project && !p.list_mode && (rc = bprx_launch_cast_Et(h, s))) return rc;
   if (p.fwd) {                                           // P rows of the listed items only / of every (touched) item
     rc = p.list_mode ? bprx_launch_proj_fwd(h, h->ilist, p.list_bound, p.list_cur, 1, h->P, s)
@@ -438,6 +476,7 @@ static int step_begin_sparse(bprx_handle *h, const int32_t *user, const int32_t 
   if (B && (!user || !pos || !neg)) BPRX_FAIL(h, BPRX_E_INVALID, "step: null index pointer");
   const StepPlan plan = plan_step(*h, user, pos, neg, B, fused_reduce);
   if (plan.error == PLAN_E_EMPTY) BPRX_FAIL(h, BPRX_E_INVALID, "step: empty batch");
+  if (plan.settle_first && (rc = bprx_settle_pending(h, s))) return rc;
   commit_plan(h, plan);
   rc = launch_sparse_half(h, h->step, s);
   if (rc) h->step_stage = 0;                               // a failed _begin leaves no step pending
@@ -445,7 +484,8 @@ static int step_begin_sparse(bprx_handle *h, const int32_t *user, const int32_t 
 }
 
 extern "C" int bprx_step_begin_sparse(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B, void *stream) {
-  return step_begin_sparse(h, user, pos, neg, B, false, (hipStream_t)stream);
+  const int rc = bprx_settle_pending(h, (hipStream_t)stream);          // the split-phase calls neither defer nor carry
+  return rc ? rc : step_begin_sparse(h, user, pos, neg, B, false, (hipStream_t)stream);
 }
 
 extern "C" int bprx_step_begin_dense(bprx_handle *h, void *stream) {
@@ -474,7 +514,8 @@ static int step_begin(bprx_handle *h, const int32_t *user, const int32_t *pos, c
 }
 
 extern "C" int bprx_step_begin(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B, void *stream) {
-  return step_begin(h, user, pos, neg, B, false, stream);
+  const int rc = bprx_settle_pending(h, (hipStream_t)stream);
+  return rc ? rc : step_begin(h, user, pos, neg, B, false, stream);
 }
 
 extern "C" int bprx_step_project(bprx_handle *h, void *stream) {
@@ -482,6 +523,7 @@ extern "C" int bprx_step_project(bprx_handle *h, void *stream) {
   if (rc) return rc;
   if (h->cfg.model != BPRX_MODEL_VBPR) return BPRX_OK;
   hipStream_t s = (hipStream_t)stream;
+  if ((rc = bprx_settle_pending(h, s))) return rc;
   if ((rc = bprx_launch_cast_Et(h, s))) return rc;
   if (!h->p_valid && (rc = bprx_launch_proj_fwd(h, nullptr, h->cfg.num_items, nullptr, 0, h->P, s))) return rc;
   h->p_valid = true;
@@ -499,6 +541,7 @@ extern "C" int bprx_user_grad(bprx_handle *h, float **dGu, float **dTu) {
 extern "C" int bprx_clear_user_grad(bprx_handle *h, int64_t n_rows, int32_t marks_only, void *stream) {
   if (!h || n_rows < 0 || n_rows > h->cfg.num_users) return BPRX_E_INVALID;
   hipStream_t s = (hipStream_t)stream;
+  { const int rc = bprx_settle_pending(h, s); if (rc) return rc; }
   if (!marks_only) {                                       // (bprx_route_pack has already returned the gradient rows to zero)
     BPRX_HIP(h, hipMemsetAsync(h->dGu, 0, (size_t)n_rows * h->cfg.embed_k * sizeof(float), s));
     if (h->cfg.embed_d) BPRX_HIP(h, hipMemsetAsync(h->dTu, 0, (size_t)n_rows * h->cfg.embed_d * sizeof(float), s));
@@ -517,6 +560,7 @@ extern "C" int bprx_item_grad(bprx_handle *h, float **dGi, float **dBi) {
 extern "C" int bprx_clear_item_grad(bprx_handle *h, int64_t n_rows, int32_t marks_only, void *stream) {
   if (!h || n_rows < 0 || n_rows > h->cfg.num_items) return BPRX_E_INVALID;
   hipStream_t s = (hipStream_t)stream;
+  { const int rc = bprx_settle_pending(h, s); if (rc) return rc; }
   if (!marks_only) {
     BPRX_HIP(h, hipMemsetAsync(h->dGi, 0, (size_t)n_rows * h->cfg.embed_k * sizeof(float), s));
     BPRX_HIP(h, hipMemsetAsync(h->dBi, 0, (size_t)n_rows * sizeof(float), s));
@@ -532,7 +576,8 @@ extern "C" int bprx_dense_grad(bprx_handle *h, float **ptr, int64_t *count) {
   return BPRX_OK;
 }
 
-extern "C" int bprx_step_end(bprx_handle *h, float *loss_out, void *stream) {
+// may_defer: the caller is bprx_step -- the dense update may be left to the next step's index pass (StepPlan::defer_ok)
+static int step_end(bprx_handle *h, float *loss_out, void *stream, bool may_defer) {
   if (!h) return BPRX_E_INVALID;
   if (!h->step_stage) BPRX_FAIL(h, BPRX_E_STATE, "step_end without step_begin");
   if (h->step_stage != 2) BPRX_FAIL(h, BPRX_E_STATE, "step_end before step_begin_dense");
@@ -541,16 +586,24 @@ extern "C" int bprx_step_end(bprx_handle *h, float *loss_out, void *stream) {
   int rc;
   h->step_stage = 0;
   if (h->factored && (rc = bprx_launch_fact_update(h, p.lr_t, s))) return rc;   // the factors, then E_eff / Bp_eff
-  if (p.dense_launch && (rc = bprx_launch_dense_update(h, p, s))) return rc;
+  // a step asked for its loss keeps today's sequence unless the caller allowed the loss to lag (bprx_set_loss_lag)
+  const bool defer = may_defer && p.dense_launch && p.defer_ok && (!loss_out || h->loss_lag);
+  if (defer) {                                             // recorded with what the launch would be given now; the carried flags
+    h->pend.a = bprx_dense_args(h, p);                     // below are set as if it had run
+    h->pend.loss_out = loss_out; h->pend.loss_B = p.B; h->pend.loss_nsq = h->dense_blocks; h->pend.loss_reg = h->cfg.reg;
+    h->pend.on = true;
+  } else if (p.dense_launch && (rc = bprx_launch_dense_update(h, p, s))) return rc;
   if (h->cfg.model == BPRX_MODEL_VBPR) {                    // what the end of a step leaves for the next one
     if (p.dense_launch) h->absmax_valid = h->cfg.feat_dtype == BPRX_F_FP8;   // k_dense_update left max|E,Bp| in qs[2 + qs_slot]
     if (p.list_mode) h->list_slot ^= 1;                     // the step's list is consumed
     h->et_valid = p.dense_launch && h->cfg.feat_dtype == BPRX_F_BF16;   // E / Bp moved: the images were refreshed, or are stale
     h->p_valid = false;                                     //               the item projections are stale
   }
-  if (loss_out && (rc = bprx_launch_loss_reduce(h, p.B, loss_out, s))) return rc;
+  if (loss_out && !defer && (rc = bprx_launch_loss_reduce(h, p.B, loss_out, s))) return rc;
   return BPRX_OK;
 }
+
+extern "C" int bprx_step_end(bprx_handle *h, float *loss_out, void *stream) { return step_end(h, loss_out, stream, false); }
 
 extern "C" int bprx_step(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B,
                          float *loss_out, void *stream) {
@@ -565,7 +618,7 @@ extern "C" int bprx_step(bprx_handle *h, const int32_t *user, const int32_t *pos
   }
   // no all-reduce in between: the dense update may sum the split-K slabs itself (StepPlan::fused_reduce)
   int rc = step_begin(h, user, pos, neg, B, true, stream);
-  if (!rc) rc = bprx_step_end(h, loss_out, stream);
+  if (!rc) rc = step_end(h, loss_out, stream, true);
   return rc;
 }
 
@@ -575,6 +628,7 @@ extern "C" int bprx_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *o
   if (u0 < 0 || u1 > h->cfg.num_users || u0 > u1 || !out) BPRX_FAIL(h, BPRX_E_INVALID, "score_block: bad user range [%d,%d)", u0, u1);
   if (u0 == u1) return BPRX_OK;
   hipStream_t s = (hipStream_t)stream;
+  if ((rc = bprx_settle_pending(h, s))) return rc;
   if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: predict_all reads every row
   if (h->af) return bprx_af_block(h, u0, u1, out, nullptr, s);
   if (h->acf) {
@@ -622,6 +676,7 @@ extern "C" int bprx_project_rows(bprx_handle *h, const void *Fnew, int64_t n, fl
   if (!Fnew || !P) BPRX_FAIL(h, BPRX_E_INVALID, "project_rows: null pointer");
   if ((uintptr_t)Fnew & 15) BPRX_FAIL(h, BPRX_E_INVALID, "project_rows: the table must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
+  if ((rc = bprx_settle_pending(h, s))) return rc;
   if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: as every call that reads the tables
   if ((rc = bprx_launch_cast_Et(h, s))) return rc;
   return bprx_launch_proj_new(h, Fnew, n, P, s);
@@ -643,6 +698,7 @@ extern "C" int bprx_proj_mask_kind(const bprx_handle *h) {
 extern "C" int bprx_sync_check(bprx_handle *h, void *stream) {
   if (!h) return BPRX_E_INVALID;
   hipStream_t s = (hipStream_t)stream;
+  { const int rc = bprx_settle_pending(h, s); if (rc) return rc; }
   int32_t flag = 0;
   BPRX_HIP(h, hipMemcpyAsync(&flag, h->errflag, sizeof(flag), hipMemcpyDeviceToHost, s));
   BPRX_HIP(h, hipStreamSynchronize(s));

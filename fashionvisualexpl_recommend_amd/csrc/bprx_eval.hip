@@ -410,6 +410,7 @@ __global__ __launch_bounds__(256) void k_topk(float *__restrict__ S, int u0, int
 extern "C" int bprx_topk(bprx_handle *h, int32_t u0, int32_t u1, float *scores, const int64_t *train_ptr,
                          const int32_t *train_items, int32_t K, int32_t *idx, float *val, int32_t *flag, void *stream) {
   if (!h) return BPRX_E_INVALID;
+  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (u0 < 0 || u1 > h->cfg.num_users || u0 > u1 || !scores || !train_ptr || !train_items || !idx || !val || !flag)
     BPRX_FAIL(h, BPRX_E_INVALID, "topk: bad argument");
   if (K <= 0 || K > TOPK_MAX) BPRX_FAIL(h, BPRX_E_INVALID, "topk: K=%d outside [1, %d]", K, TOPK_MAX);
@@ -424,6 +425,7 @@ extern "C" int bprx_topk_rows(bprx_handle *h, int64_t nrows, int32_t width, floa
                               int32_t *flag, void *stream) {
   const int rc = bprx_new_items_check(h, "topk_rows", nrows);
   if (rc) return rc;
+  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (width < 1) BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows: width = %d < 1", width);
   if (K <= 0 || K > TOPK_MAX) BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows: K=%d outside [1, %d]", K, TOPK_MAX);
   if (nrows == 0) return BPRX_OK;
@@ -437,6 +439,7 @@ extern "C" int bprx_topk_rows(bprx_handle *h, int64_t nrows, int32_t width, floa
 extern "C" int bprx_score_new_block(bprx_handle *h, int32_t u0, int32_t u1, const float *P, int64_t n, float *out, void *stream) {
   int rc = bprx_new_items_check(h, "score_new_block", n);
   if (rc) return rc;
+  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (u0 < 0 || u1 > h->cfg.num_users || u0 > u1) BPRX_FAIL(h, BPRX_E_INVALID, "score_new_block: bad user range [%d,%d)", u0, u1);
   if (n == 0 || u0 == u1) return BPRX_OK;
   if (!P || !out) BPRX_FAIL(h, BPRX_E_INVALID, "score_new_block: null pointer");
@@ -464,6 +467,7 @@ extern "C" int bprx_eval_users(bprx_handle *h, int32_t u0, int32_t u1, const flo
                                const int32_t *train_items, const int64_t *eval_ptr, const int32_t *eval_items, int32_t K,
                                double *out, void *stream) {
   if (!h) return BPRX_E_INVALID;
+  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (u0 < 0 || u1 > h->cfg.num_users || u0 > u1 || !scores || !train_ptr || !train_items || !eval_ptr || !eval_items ||
       !out || K <= 0)
     BPRX_FAIL(h, BPRX_E_INVALID, "eval_users: bad argument");
@@ -478,6 +482,7 @@ extern "C" int bprx_eval_users(bprx_handle *h, int32_t u0, int32_t u1, const flo
 extern "C" int bprx_eval_pos(bprx_handle *h, int32_t u0, int32_t u1, const float *scores, int32_t item_lo, int32_t items_total,
                              const int64_t *eval_ptr, const int32_t *eval_items, float *sp, void *stream) {
   if (!h) return BPRX_E_INVALID;
+  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (u0 < 0 || u0 > u1 || !scores || !eval_ptr || !eval_items || !sp || item_lo < 0 || items_total <= 0)
     BPRX_FAIL(h, BPRX_E_INVALID, "eval_pos: bad argument");
   if (u0 == u1) return BPRX_OK;
@@ -492,6 +497,7 @@ extern "C" int bprx_eval_counts(bprx_handle *h, int32_t u0, int32_t u1, const fl
                                 const int64_t *train_ptr, const int32_t *train_items, const int64_t *eval_ptr,
                                 const int32_t *eval_items, const float *sp, int32_t *counts, void *stream) {
   if (!h) return BPRX_E_INVALID;
+  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (u0 < 0 || u0 > u1 || !scores || !train_ptr || !train_items || !eval_ptr || !eval_items || !sp || !counts || item_lo < 0)
     BPRX_FAIL(h, BPRX_E_INVALID, "eval_counts: bad argument");
   if (u0 == u1) return BPRX_OK;
@@ -504,6 +510,7 @@ extern "C" int bprx_eval_counts(bprx_handle *h, int32_t u0, int32_t u1, const fl
 extern "C" int bprx_eval_finish(bprx_handle *h, int32_t u0, int32_t u1, int32_t items_total, const int64_t *eval_ptr,
                                 const float *sp, const int32_t *counts, int32_t K, double *out, void *stream) {
   if (!h) return BPRX_E_INVALID;
+  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (u0 < 0 || u0 > u1 || !eval_ptr || !sp || !counts || !out || K <= 0 || items_total <= 0)
     BPRX_FAIL(h, BPRX_E_INVALID, "eval_finish: bad argument");
   if (u0 == u1) return BPRX_OK;

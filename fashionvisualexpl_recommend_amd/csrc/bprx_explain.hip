@@ -253,6 +253,7 @@ extern "C" int bprx_feat_explain(bprx_handle *h, const void *F, const int32_t *u
                                  int32_t top, float *score, float *base, float *visual, int32_t *col, float *contrib, float *map,
                                  void *stream) {
   if (!h) return BPRX_E_INVALID;
+  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (!h->bound) BPRX_FAIL(h, BPRX_E_STATE, "tables not bound (call bprx_bind_tables first)");
   if (h->cfg.model != BPRX_MODEL_VBPR || h->acf || h->af)
     BPRX_FAIL(h, BPRX_E_STATE, "feat_explain: needs a VBPR handle (bprx_bind_tables or bprx_bind_factored)");
@@ -292,6 +293,7 @@ extern "C" int bprx_feat_explain_new(bprx_handle *h, const void *Fnew, int64_t n
                                      void *stream) {
   int rc = bprx_new_items_check(h, "feat_explain_new", n);
   if (rc) return rc;
+  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   const bprx_config &c = h->cfg;
   if (n_new < 0 || n_new >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: n_new = %lld out of range", (long long)n_new);
   if (ncols < 1 || ncols > c.feat_dim) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: ncols = %d outside [1, feat_dim = %d]", ncols, c.feat_dim);

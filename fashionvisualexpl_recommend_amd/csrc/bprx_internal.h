@@ -111,9 +111,45 @@ struct StepPlan {
   int apply;                      // APPLY_*: what bprx_launch_apply does
   int fk, ek;                     // row kinds [fk, ek) of the apply pass (0 users, 1 / 2 positive / negative items)
   bool dense_launch;              // bprx_step_end: k_dense_update runs (GradFashion: only for its housekeeping)
+  // the dense update across two steps (bprx_step only; DESIGN §4 "The deferred dense update")
+  bool defer_ok;                  // this step's update may wait for the next step's index pass (bprx_step decides with the loss pointer)
+  bool carry_dense;               // the LAST step's update is pending and rides in this step's k_index_seg launch
+  bool settle_first;              // ... is pending and this step has no such launch: k_dense_update runs before anything else
 };
 enum { PLAN_E_EMPTY = 1 };           // an empty batch on a handle without exported gradients
 enum { APPLY_NONE = 0, APPLY_SGD_LIST, APPLY_SGD, APPLY_ADAM_LAZY, APPLY_ADAM_SWEEP };
+
+// What one dense E|Bp update is given (k_dense_update, and the dense workgroups of k_index_seg: bprx_sparse.hip), every value
+// fixed when the step that owns the update ends: bprx_dense_args.
+struct DenseArgs {
+  float *E, *Bp, *mE, *vE, *mBp, *vBp;
+  const float *dEp, *part;        // the (all-reduced) gradient, or the split-K slabs to sum (part != nullptr)
+  int SK, D, d, PS, adam;
+  float lr_t, reg, b1, b2, eps;
+  double *sqpart;                 // [nvb] per-block sums of squares (the loss), or nullptr
+  float gscale;
+  uint16_t *Et, *EtF;             // bf16 features: the images to refresh
+  const int32_t *ilist, *ilist_n; // list mode: the rows of W to clear
+  int32_t *ilist_n_next;
+  int bound;
+  float *W;
+  int32_t *cnt_reset;
+  uint32_t *absmax_out;           // fp8 features: the max|E,Bp| slot
+  int upd;
+  int nvb, vT;                    // blocks of the update and threads of one (a multiple of 64, 256 .. 1024)
+};
+
+// A dense update that bprx_step did not launch: the next segment-mode bprx_step runs it inside its k_index_seg launch, every other
+// call settles it first with k_dense_update (bprx_settle_pending).  Carried flags (et_valid, absmax_valid, p_valid, dense_blocks)
+// are already as if it had run.
+struct DensePending {
+  bool on;
+  DenseArgs a;                    // with the hyper-parameters of ITS step (a later bprx_set_hyper does not reach it)
+  float *loss_out;                // loss lag: where that step's loss goes once the update has run (or nullptr)
+  int64_t loss_B;
+  int loss_nsq;
+  float loss_reg;
+};
 
 struct bprx_handle {
   bprx_config cfg;
@@ -132,6 +168,9 @@ struct bprx_handle {
   float *lossb;                   // [max_batch] per-triplet loss (data + per-occurrence regularisation)
   double *loss_acc;               // [BPRX_DENSE_BLOCKS] per-block partial sums of ||E||^2+||Bp||^2 (k_dense_update)
   int dense_blocks;               // blocks of the last k_dense_update launch
+  int dense_defer;                // env BPRX_DENSE_DEFER, read at create: 1 (default) bprx_step may defer its dense update, 0 never
+  int loss_lag;                   // bprx_set_loss_lag: a step with a loss pointer may defer too (its loss lands one launch later)
+  DensePending pend;              // the deferred update, if any: set by bprx_step, taken by the next index pass / bprx_settle_pending
 
   // ---- the step in flight ----
   StepPlan step;                  // committed by bprx_step_begin_sparse; read-only until the next one (the launchers, bprx_step_lr,
@@ -285,6 +324,12 @@ int bprx_launch_triplet_grad(bprx_handle *h, const StepPlan &p, hipStream_t s);
 int bprx_launch_item_seg(bprx_handle *h, const StepPlan &p, hipStream_t s);
 int bprx_launch_apply(bprx_handle *h, const StepPlan &p, hipStream_t s);
 int bprx_launch_dense_update(bprx_handle *h, const StepPlan &p, hipStream_t s);
+DenseArgs bprx_dense_args(bprx_handle *h, const StepPlan &p);               // what that launch is given (also sets dense_blocks)
+int bprx_launch_dense_args(bprx_handle *h, const DenseArgs &a, hipStream_t s);
+// Runs a pending dense update (and its lagging loss) with the stand-alone kernel on `s`; returns at once when nothing is pending
+// or h is null.  Every entry that takes a handle calls it first, except bprx_step (which may carry the update instead), the
+// samplers, the profile calls, bprx_last_error, bprx_set_hyper / bprx_set_loss_lag and the pure getters.  (bprx_api.hip)
+int bprx_settle_pending(bprx_handle *h, hipStream_t s);
 // One adam_tf23 step (sparse rule, adam_elem) of up to four whole tables from their staging gradients, which return to zero,
 // and the clearing of up to two claim-mark arrays, in ONE launch of k_adam_sweep: the sweep of every model and of
 // bprx_adam_rows.  A segment with n == 0 (a flag array with nflag == 0) costs nothing.
@@ -296,6 +341,7 @@ int bprx_launch_adam_catchup(bprx_handle *h, const StepPlan &p, hipStream_t s);
 int bprx_launch_adam_sync(bprx_handle *h, int64_t t, hipStream_t s);
 int bprx_launch_adam_reset(bprx_handle *h, int64_t t, hipStream_t s);
 int bprx_launch_loss_reduce(bprx_handle *h, int64_t B, float *loss_out, hipStream_t s);
+int bprx_launch_loss_reduce_at(bprx_handle *h, int64_t B, int nsq, float reg, float *loss_out, hipStream_t s);   // a lagging loss
 int bprx_launch_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s);
 int bprx_launch_score_gemm(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s);
 // projection part (bprx_proj.hip)
@@ -389,6 +435,7 @@ inline StepPlan plan_step(const bprx_handle &h, const int32_t *user, const int32
   // GradFashion: bprx_launch_fact_update has moved the factors, composed E_eff / Bp_eff and left the loss partials;
   // k_dense_update only does the step's housekeeping (nothing to do: no launch)
   p.dense_launch = vb && (!h.factored || c.feat_dtype == BPRX_F_BF16);
+  p.settle_first = h.pend.on;                            // (until a k_index_seg launch turns up below)
   if (B == 0) return p;                                  // no list, no segments, no mask; the dense half zeroes dEp
 
   // list mode: both projections over the batch's distinct items only (needs the index pass BEFORE the forward projection)
@@ -426,6 +473,14 @@ inline StepPlan plan_step(const bprx_handle &h, const int32_t *user, const int32
   p.mask = p.project && !p.list_mode && p.item_mode && !h.p_valid &&
            (h.proj_mask == 2 ? bf : (h.proj_mask == 1 && c.feat_dtype == BPRX_F_BF16 && h.PS / 16 <= 9));
   p.index_first = p.list_mode || p.mask;
+  // The dense update across two steps.  This step's own update may wait (bprx_step, which alone sums the slabs in the update:
+  // fused_reduce) unless it has list housekeeping to do or GradFashion composes E / Bp elsewhere.  A pending one rides in this
+  // step's k_index_seg launch, which then runs before k_cast_Et* and the forward projection whatever the mask says (they read
+  // what the update writes; the index pass itself reads none of it).  No such launch: the stand-alone kernel first.
+  p.defer_ok = h.dense_defer && p.dense_launch && p.fused_reduce && !p.list_mode && !h.factored;
+  p.carry_dense = h.pend.on && p.item_mode;
+  p.settle_first = h.pend.on && !p.carry_dense;
+  p.index_first = p.index_first || p.carry_dense;
   if (p.item_mode) {
     // k_index_seg: one owner workgroup per CU, more when a range would not fit LDS; the byte planes fix 2^shift items per owner
     p.idx_kind = p.idx8 ? 2 : 1;

@@ -821,38 +821,51 @@ __global__ void k_fill_i32(int32_t *p, size_t n, int32_t v) {
 //   * list mode: the fp32 W rows of the listed items return to zero, their multiplicities are reset when nobody else does
 //     it, and the OTHER list cursor (the one the next list-mode step appends through) is cleared.
 constexpr int DU_KB = 8;
-__global__ __launch_bounds__(1024) void k_dense_update(float *__restrict__ E, float *__restrict__ Bp, float *mE, float *vE,
-                                                      float *mBp, float *vBp, const float *__restrict__ dEp,
-                                                      const float *__restrict__ part, int SK, int D, int d, int PS, int adam,
-                                                      float lr_t, float reg, float b1, float b2, float eps,
-                                                      double *__restrict__ sqpart, float gscale, uint16_t *__restrict__ Et,
-                                                      uint16_t *__restrict__ EtF, const int32_t *__restrict__ ilist,
-                                                      const int32_t *__restrict__ ilist_n, int32_t *__restrict__ ilist_n_next,
-                                                      int bound, float *__restrict__ W, int32_t *__restrict__ cnt_reset,
-                                                      uint32_t *__restrict__ absmax_out, int upd) {
-  __shared__ __attribute__((aligned(16))) uint16_t tile[DU_KB][288];   // PS <= 272
-  if (ilist_n_next && blockIdx.x == 0 && threadIdx.x == 0) *ilist_n_next = 0;
-  if (ilist) {
-    int n = *ilist_n;
-    n = n < bound ? n : bound;
+// (DenseArgs: bprx_internal.h -- what one launch is given; a deferred update keeps a copy until the next index pass runs it)
+// LDS of ONE block of the update: the transpose tile and the two reduction arrays
+struct DenseLds {
+  __attribute__((aligned(16))) uint16_t tile[DU_KB][288];   // PS <= 272
+  double red[16];
+  uint32_t wm[16];
+};
+// One block of the dense update as thread `vt` of VIRTUAL block `vb`: a.nvb blocks of a.vT threads (a multiple of 64, so a wave
+// belongs to one block).  k_dense_update runs it with its own block and thread ids; k_index_seg's dense workgroups run several
+// virtual blocks side by side with sub-groups of their 1 024 threads (a deferred update, bprx_step).  The tile -> block mapping,
+// the slab order, the order of the waves' sums and the stores are those of the ids alone, so both forms leave the same bits.
+// Every thread of the workgroup passes the same __syncthreads() whatever its block does: `live` == false (a surplus sub-group,
+// the threads behind the last one) only keeps the barriers company, and the tile loop has one trip count for all blocks.
+__device__ __forceinline__ void dense_update_block(const DenseArgs &a, const int vb, const int vt, const bool live, DenseLds &L) {
+  float *__restrict__ const E = a.E; float *__restrict__ const Bp = a.Bp;
+  float *const mE = a.mE, *const vE = a.vE, *const mBp = a.mBp, *const vBp = a.vBp;
+  const float *__restrict__ const dEp = a.dEp; const float *__restrict__ const part = a.part;
+  uint16_t *__restrict__ const Et = a.Et; uint16_t *__restrict__ const EtF = a.EtF;
+  const int SK = a.SK, D = a.D, d = a.d, PS = a.PS, adam = a.adam, upd = a.upd, nvb = a.nvb, vT = a.vT;
+  const float lr_t = a.lr_t, reg = a.reg, b1 = a.b1, b2 = a.b2, eps = a.eps, gscale = a.gscale;
+  uint16_t (*const tile)[288] = L.tile;
+  if (a.ilist_n_next && live && vb == 0 && vt == 0) *a.ilist_n_next = 0;
+  if (a.ilist && live) {
+    int n = *a.ilist_n;
+    n = n < a.bound ? n : a.bound;
     const int per = PS / 4;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < (int64_t)n * per; e += (int64_t)gridDim.x * blockDim.x) {
+    for (int64_t e = (int64_t)vb * vT + vt; e < (int64_t)n * per; e += (int64_t)nvb * vT) {
       const int p = (int)(e / per), c4 = (int)(e % per);
-      const int item = ilist[p];
-      reinterpret_cast<float4 *>(W + (size_t)item * PS)[c4] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (cnt_reset && c4 == 0) cnt_reset[item] = 0;
+      const int item = a.ilist[p];
+      reinterpret_cast<float4 *>(a.W + (size_t)item * PS)[c4] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (a.cnt_reset && c4 == 0) a.cnt_reset[item] = 0;
     }
   }
   double sq = 0.0;
   uint32_t amax = 0;                                     // bit pattern of max|new value| (monotonic for non-negative floats)
   const size_t total = (size_t)D * PS;
   const int ntile = (D + DU_KB - 1) / DU_KB;
-  for (int tl = blockIdx.x; tl < ntile; tl += gridDim.x) {
+  for (int t0 = 0; t0 < ntile; t0 += nvb) {              // block vb: tiles vb, vb + nvb, ...
+    const int tl = t0 + vb;
+    const bool on = live && tl < ntile;
     const int k0 = tl * DU_KB;
     // one thread per 4 consecutive columns: the slab reads are 16-B loads, eight slabs in flight per thread (4-B loads left
     // a block with 8 KB in flight: five round trips per tile; C2 10.7 us for 23 MB)
     const int PQ = PS >> 2;                              // PS % 16 == 0
-    for (int q = threadIdx.x; q < DU_KB * PQ; q += (int)blockDim.x) {
+    for (int q = vt; on && q < DU_KB * PQ; q += vT) {
       const int kr = q / PQ, n4 = (q - kr * PQ) * 4, kk = k0 + kr;
       float nvv[4] = {0.f, 0.f, 0.f, 0.f};
       if (!upd && kk < D && n4 <= d) {                   // housekeeping only (GradFashion: E / Bp were composed already)
@@ -890,12 +903,12 @@ __global__ __launch_bounds__(1024) void k_dense_update(float *__restrict__ E, fl
         //  dependent round trips per thread otherwise)
         float *pp[4], *pm[4], *pv_[4];
         float pv[4], mo[4] = {0.f, 0.f, 0.f, 0.f}, vo[4] = {0.f, 0.f, 0.f, 0.f};
-        bool on[4];
+        bool on4[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           const int n = n4 + c;
-          on[c] = n <= d;
-          const int nn = on[c] ? n : d;                    // (a valid address for the masked lanes)
+          on4[c] = n <= d;
+          const int nn = on4[c] ? n : d;                   // (a valid address for the masked lanes)
           pp[c] = nn < d ? E + (size_t)kk * d + nn : Bp + kk;
           pm[c] = adam ? (nn < d ? mE + (size_t)kk * d + nn : mBp + kk) : nullptr;
           pv_[c] = adam ? (nn < d ? vE + (size_t)kk * d + nn : vBp + kk) : nullptr;
@@ -907,7 +920,7 @@ __global__ __launch_bounds__(1024) void k_dense_update(float *__restrict__ E, fl
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          if (!on[c]) continue;
+          if (!on4[c]) continue;
           sq += (double)pv[c] * (double)pv[c];
           const float gg = gs[c] + 2.f * reg * pv[c];
           float nv;
@@ -932,7 +945,7 @@ __global__ __launch_bounds__(1024) void k_dense_update(float *__restrict__ E, fl
     }
     if (Et) {                                            // D % 128 == 0 with bf16 features: whole tiles only
       __syncthreads();
-      for (int n = threadIdx.x; n < PS; n += (int)blockDim.x) {
+      for (int n = vt; on && n < PS; n += vT) {
         uint4 v;
         v.x = (uint32_t)tile[0][n] | ((uint32_t)tile[1][n] << 16);
         v.y = (uint32_t)tile[2][n] | ((uint32_t)tile[3][n] << 16);
@@ -946,28 +959,32 @@ __global__ __launch_bounds__(1024) void k_dense_update(float *__restrict__ E, fl
       __syncthreads();
     }
   }
-  // (blockDim.x is a multiple of 64, at most 1024: a wave-level tree, then the waves' sums in a fixed order)
-  __shared__ double red[16];
+  // (vT is a multiple of 64, at most 1024: a wave-level tree, then the block's waves' sums in a fixed order)
   sq = wave_sum(sq);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
+  if (live && (vt & 63) == 0) L.red[vt >> 6] = sq;
   __syncthreads();
-  if (threadIdx.x == 0 && sqpart) {
+  if (live && vt == 0 && a.sqpart) {
     double t = 0.0;
-    for (int q = 0; q < (int)(blockDim.x >> 6); ++q) t += red[q];
-    sqpart[blockIdx.x] = t;
+    for (int q = 0; q < (vT >> 6); ++q) t += L.red[q];
+    a.sqpart[vb] = t;
   }
-  if (absmax_out) {
-    __shared__ uint32_t wm[16];
+  if (a.absmax_out) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { const uint32_t v = __shfl_xor(amax, o, 64); amax = v > amax ? v : amax; }
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = amax;
+    if (live && (vt & 63) == 0) L.wm[vt >> 6] = amax;
     __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t b = wm[0];
-      for (int q = 1; q < (int)(blockDim.x >> 6); ++q) b = wm[q] > b ? wm[q] : b;
-      if (b) atomicMax(absmax_out, b);
+    if (live && vt == 0) {
+      uint32_t b = L.wm[0];
+      for (int q = 1; q < (vT >> 6); ++q) b = L.wm[q] > b ? L.wm[q] : b;
+      if (b) atomicMax(a.absmax_out, b);
     }
   }
+}
+
+// the stand-alone launch: a flush (bprx_settle), the split-phase calls, and every step that does not defer its update
+__global__ __launch_bounds__(1024) void k_dense_update(DenseArgs a) {
+  __shared__ DenseLds L;
+  dense_update_block(a, (int)blockIdx.x, (int)threadIdx.x, true, L);
 }
 
 // loss = sum_b lossb[b] + reg*(||E||^2+||Bp||^2); fixed summation order (one block), double accumulation.
@@ -1039,6 +1056,9 @@ struct IndexSegArgs {
   // R == 256 and B % 16 == 0: owner w scans own8 for bytes equal to w, sixteen values per 16-byte load.
   const uint8_t *own8, *loc8;
   int wide;                       // loc8 holds 16-bit locals (R = 2^shift > 256 items per owner: num_items > 65 536)
+  // the LAST step's dense update, deferred into this launch (StepPlan::carry_dense): ndense workgroups behind the owners
+  int ndense;
+  DenseArgs dn;
 };
 
 __global__ __launch_bounds__(IX_T) void k_index_seg(IndexSegArgs a) {
@@ -1076,6 +1096,19 @@ __global__ __launch_bounds__(IX_T) void k_index_seg(IndexSegArgs a) {
       a.uslot_of[u] = (int)b;
       a.ulist[u_base + u_wcnt[wv] + __popcll(fm & (lane ? (~0ull >> (64 - lane)) : 0ull))] = u;   // (at most B users: the list holds max_batch)
     }
+    return;
+  }
+  if ((int)blockIdx.x >= a.nuser + a.nown) {
+    // ---- the last step's dense E|Bp update (last in the grid: the owners, the long pole, take their CUs first) ----
+    // It reads the split-K slabs and moves E / Bp and their images; the index pass reads the index arrays and writes the
+    // segments: disjoint memory, nothing here waits for another workgroup.  IX_T / vT sub-groups run one virtual block each.
+    // (static LDS of the KERNEL: every user and owner workgroup reserves these 19 KB too.  Harmless: 117 VGPRs already hold the
+    //  kernel to one 1 024-thread workgroup per CU, and 19 KB + the owners' 4 * IX_RMAX = 32 KB stay below the 64-KB limit)
+    __shared__ DenseLds dl[IX_T / 256];                              // (vT >= 256)
+    const int S = IX_T / a.dn.vT, sub = tid / a.dn.vT;
+    const int vb = ((int)blockIdx.x - a.nuser - a.nown) * S + sub;
+    const bool live = sub < S && vb < a.dn.nvb;
+    dense_update_block(a.dn, vb, tid - sub * a.dn.vT, live, dl[live ? sub : 0]);
     return;
   }
   // ---- item side ----
@@ -1984,6 +2017,7 @@ extern "C" int64_t bprx_user_msg_floats(const bprx_handle *h, int64_t cap) {
 
 extern "C" int bprx_pack_user_msg(bprx_handle *h, const int32_t *user, int64_t B, int64_t cap, float *msg, void *stream) {
   if (!h || !msg || B < 0 || cap <= 0 || (B > 0 && !user)) return BPRX_E_INVALID;
+  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (!(h->cfg.flags & BPRX_FLAG_EXPORT_USER_GRAD)) BPRX_FAIL(h, BPRX_E_STATE, "pack_user_msg needs BPRX_FLAG_EXPORT_USER_GRAD");
   if (!h->step_stage) BPRX_FAIL(h, BPRX_E_STATE, "pack_user_msg outside a step (after bprx_step_begin[_sparse])");
   if (B != h->step.B) BPRX_FAIL(h, BPRX_E_INVALID, "pack_user_msg: B differs from the pending step's");
@@ -2008,6 +2042,7 @@ extern "C" int bprx_pack_user_msg(bprx_handle *h, const int32_t *user, int64_t B
 
 extern "C" int bprx_apply_user_msgs(bprx_handle *h, const float *msgs, int32_t nranks, int64_t cap, float scale, void *stream) {
   if (!h || !msgs || nranks <= 0 || cap <= 0) return BPRX_E_INVALID;
+  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (!h->bound) BPRX_FAIL(h, BPRX_E_STATE, "tables not bound");
   if (!(h->cfg.flags & BPRX_FLAG_EXPORT_USER_GRAD)) BPRX_FAIL(h, BPRX_E_STATE, "apply_user_msgs needs BPRX_FLAG_EXPORT_USER_GRAD");
   if ((int64_t)nranks * cap >= ((int64_t)1 << 31) - 1) BPRX_FAIL(h, BPRX_E_INVALID, "nranks * cap too large");
@@ -2054,6 +2089,7 @@ extern "C" int bprx_apply_user_msgs(bprx_handle *h, const float *msgs, int32_t n
 // an RCCL all-reduce
 extern "C" int bprx_sum_dense_parts(bprx_handle *h, const float *parts, int32_t nranks, void *stream) {
   if (!h || !parts || nranks <= 0) return BPRX_E_INVALID;
+  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (h->cfg.model != BPRX_MODEL_VBPR) BPRX_FAIL(h, BPRX_E_STATE, "sum_dense_parts: VBPR only");
   const size_t nd = (size_t)h->cfg.feat_dim * (h->cfg.embed_d + 1);
   unsigned blocks = (unsigned)((nd + 255) / 256);
@@ -2102,7 +2138,15 @@ int bprx_launch_index_pass(bprx_handle *h, const StepPlan &p, hipStream_t s) {
     x.Wb = zw ? (uint16_t *)h->Wb : nullptr; x.PS = a.PS;
     x.aligned = (((uintptr_t)i | (uintptr_t)j) & 15) == 0;
     x.nuser = users ? (int)((B + IX_T - 1) / IX_T) : 0;
-    hipLaunchKernelGGL(k_index_seg, dim3((unsigned)(x.nown + x.nuser)), dim3(IX_T), (size_t)x.R * sizeof(int), s, x);
+    x.ndense = 0; x.dn = DenseArgs{};
+    if (p.carry_dense) {                                  // the last step's deferred update rides along (bprx_step)
+      x.dn = h->pend.a;
+      // (measured and dropped: blocks of the three waves that hold an element at PS = 80, five per workgroup instead of four --
+      //  103 fatter workgroups instead of 128: k_index_seg 16.4 -> 17.4 us, C2 0.2005 -> 0.2021 ms/step)
+      const int S = IX_T / x.dn.vT;                       // virtual blocks per workgroup
+      x.ndense = (x.dn.nvb + S - 1) / S;
+    }
+    hipLaunchKernelGGL(k_index_seg, dim3((unsigned)(x.nown + x.nuser + x.ndense)), dim3(IX_T), (size_t)x.R * sizeof(int), s, x);
     BPRX_LAUNCH_CHECK(h, "k_index_seg");
     return BPRX_OK;
   }
@@ -2272,19 +2316,16 @@ int bprx_launch_adam_reset(bprx_handle *h, int64_t t, hipStream_t s) {
   return BPRX_OK;
 }
 
-// (bprx_step_end calls it when StepPlan::dense_launch; GradFashion: bprx_launch_fact_update has moved the factors, composed
-//  E_eff / Bp_eff and left the loss partials, and this launch only does the step's housekeeping)
-int bprx_launch_dense_update(bprx_handle *h, const StepPlan &p, hipStream_t s) {
+// what the update of the step planned as `p` is given, fixed now: its own lr_t / reg / Adam constants, SK_step, gscale and slot
+// choices -- a launch now, or a record (bprx_handle::pend) that the next step's index pass or bprx_settle runs later
+DenseArgs bprx_dense_args(bprx_handle *h, const StepPlan &p) {
   const int D = h->cfg.feat_dim;
   unsigned blocks = (unsigned)((D + DU_KB - 1) / DU_KB);
   if (blocks > BPRX_DENSE_BLOCKS) blocks = BPRX_DENSE_BLOCKS;
   const bool upd = !h->factored;
   if (upd) h->dense_blocks = (int)blocks;
-  BprxProfScope ps(h, BPRX_PHASE_DENSE, s);
   // fused_reduce: the split-K slabs are summed here (bprx_step); otherwise dEp holds the (all-reduced) gradient
   const float *part = (p.fused_reduce && h->cfg.feat_dtype != BPRX_F_FP32) ? h->part : nullptr;
-  // fp8 features: the slabs hold (F*feat_scale)^T W; an all-reduced dEp was already rescaled by k_reduce_parts
-  const float gscale = (part && h->cfg.feat_dtype == BPRX_F_FP8) ? 1.0f / h->cfg.feat_scale : 1.0f;
   // bf16 features: this kernel writes the next step's [E|Bp]^T images (fp8 images need the global max first: k_cast_Et8)
   const bool images = h->cfg.feat_dtype == BPRX_F_BF16;
   const bool lm = p.list_mode;
@@ -2292,25 +2333,46 @@ int bprx_launch_dense_update(bprx_handle *h, const StepPlan &p, hipStream_t s) {
   // block took three dependent rounds of slab loads there: c5small 21.5 us)
   int threads = (DU_KB * (h->PS / 4) + 63) / 64 * 64;
   threads = threads < 256 ? 256 : (threads > 1024 ? 1024 : threads);
-  hipLaunchKernelGGL(k_dense_update, dim3(blocks), dim3((unsigned)threads), 0, s, h->t.E, h->t.Bp, h->t.m_E, h->t.v_E, h->t.m_Bp,
-                     h->t.v_Bp, h->dEp, part, p.SK_step, D, h->cfg.embed_d, h->PS,
-                     h->cfg.optimizer == BPRX_OPT_ADAM_TF23 ? 1 : 0, p.lr_t, h->cfg.reg, h->cfg.beta1, h->cfg.beta2,
-                     h->cfg.epsilon, upd ? h->loss_acc : (double *)nullptr, gscale, images ? (uint16_t *)h->Et : (uint16_t *)nullptr, (uint16_t *)h->EtF,
-                     lm ? (const int32_t *)h->ilist : (const int32_t *)nullptr, (const int32_t *)p.list_cur,
-                     p.list_next, (int)p.list_bound, h->W,
-                     (lm && p.list_reset_cnt) ? h->cntI : (int32_t *)nullptr,
-                     // fp8: the slot the next k_cast_Et8 reads (cleared by the last one)
-                     h->cfg.feat_dtype == BPRX_F_FP8 ? (uint32_t *)h->qs + 2 + h->qs_slot : (uint32_t *)nullptr, upd ? 1 : 0);
+  DenseArgs a = {};
+  a.E = h->t.E; a.Bp = h->t.Bp; a.mE = h->t.m_E; a.vE = h->t.v_E; a.mBp = h->t.m_Bp; a.vBp = h->t.v_Bp;
+  a.dEp = h->dEp; a.part = part; a.SK = p.SK_step; a.D = D; a.d = h->cfg.embed_d; a.PS = h->PS;
+  a.adam = h->cfg.optimizer == BPRX_OPT_ADAM_TF23 ? 1 : 0;
+  a.lr_t = p.lr_t; a.reg = h->cfg.reg; a.b1 = h->cfg.beta1; a.b2 = h->cfg.beta2; a.eps = h->cfg.epsilon;
+  a.sqpart = upd ? h->loss_acc : nullptr;
+  // fp8 features: the slabs hold (F*feat_scale)^T W; an all-reduced dEp was already rescaled by k_reduce_parts
+  a.gscale = (part && h->cfg.feat_dtype == BPRX_F_FP8) ? 1.0f / h->cfg.feat_scale : 1.0f;
+  a.Et = images ? (uint16_t *)h->Et : nullptr; a.EtF = (uint16_t *)h->EtF;
+  a.ilist = lm ? h->ilist : nullptr; a.ilist_n = p.list_cur; a.ilist_n_next = p.list_next; a.bound = (int)p.list_bound;
+  a.W = h->W; a.cnt_reset = (lm && p.list_reset_cnt) ? h->cntI : nullptr;
+  // fp8: the slot the next k_cast_Et8 reads (cleared by the last one)
+  a.absmax_out = h->cfg.feat_dtype == BPRX_F_FP8 ? (uint32_t *)h->qs + 2 + h->qs_slot : nullptr;
+  a.upd = upd ? 1 : 0;
+  a.nvb = (int)blocks; a.vT = threads;
+  return a;
+}
+
+// (bprx_step_end calls it when StepPlan::dense_launch; GradFashion: bprx_launch_fact_update has moved the factors, composed
+//  E_eff / Bp_eff and left the loss partials, and this launch only does the step's housekeeping)
+int bprx_launch_dense_args(bprx_handle *h, const DenseArgs &a, hipStream_t s) {
+  BprxProfScope ps(h, BPRX_PHASE_DENSE, s);
+  hipLaunchKernelGGL(k_dense_update, dim3((unsigned)a.nvb), dim3((unsigned)a.vT), 0, s, a);
   BPRX_LAUNCH_CHECK(h, "k_dense_update");
   return BPRX_OK;
 }
 
-int bprx_launch_loss_reduce(bprx_handle *h, int64_t B, float *loss_out, hipStream_t s) {
+int bprx_launch_dense_update(bprx_handle *h, const StepPlan &p, hipStream_t s) {
+  return bprx_launch_dense_args(h, bprx_dense_args(h, p), s);
+}
+
+int bprx_launch_loss_reduce_at(bprx_handle *h, int64_t B, int nsq, float reg, float *loss_out, hipStream_t s) {
   BprxProfScope ps(h, BPRX_PHASE_LOSS, s);
-  hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(1024), 0, s, h->lossb, B, h->loss_acc,
-                     h->cfg.model == BPRX_MODEL_VBPR ? h->dense_blocks : 0, h->cfg.reg, loss_out);
+  hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(1024), 0, s, h->lossb, B, h->loss_acc, nsq, reg, loss_out);
   BPRX_LAUNCH_CHECK(h, "k_loss_reduce");
   return BPRX_OK;
+}
+
+int bprx_launch_loss_reduce(bprx_handle *h, int64_t B, float *loss_out, hipStream_t s) {
+  return bprx_launch_loss_reduce_at(h, B, h->cfg.model == BPRX_MODEL_VBPR ? h->dense_blocks : 0, h->cfg.reg, loss_out, s);
 }
 
 int bprx_launch_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s) {

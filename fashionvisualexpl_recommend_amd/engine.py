@@ -4,6 +4,7 @@ PyTorch is plumbing here (device memory, streams); every computation of the hot 
 libbprx.so through the C ABI (include/bprx.h).  A missing library or a missing GPU raises.
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch
@@ -30,6 +31,50 @@ def as_index(x, device):
             t = t.to(torch.int32)
         return t.to(device, non_blocking=True).contiguous()
     return torch.as_tensor(np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32), device=device)
+
+
+class _Bound(dict):
+    """The bound tensors by name.  A step may leave its dense E|Bp update to the next step (Engine.settle); every way of getting
+    at a tensor through this dict first settles it (a host call that returns at once when nothing is pending): d[name], get,
+    items, values, iteration, keys, copy and dict(d).  `name in d` and len(d) touch no tensor and do not.  The engine is held by
+    a weak reference: the dict keeps no engine alive, and after the engine is gone it is a plain dict."""
+
+    def __init__(self, engine, tensors):
+        super().__init__(tensors)
+        self._engine = weakref.ref(engine)
+
+    def _settle(self):
+        e = self._engine()
+        if e is not None:
+            e.settle()
+
+    def __getitem__(self, name):
+        self._settle()
+        return dict.__getitem__(self, name)
+
+    def get(self, name, default=None):
+        self._settle()
+        return dict.get(self, name, default)
+
+    def items(self):
+        self._settle()
+        return dict.items(self)
+
+    def values(self):
+        self._settle()
+        return dict.values(self)
+
+    def keys(self):
+        self._settle()
+        return dict.keys(self)
+
+    def __iter__(self):
+        self._settle()
+        return dict.__iter__(self)
+
+    def copy(self):
+        self._settle()
+        return dict(dict.items(self))
 
 
 class Engine:
@@ -64,19 +109,39 @@ class Engine:
     def t(self):
         """The bound tensors.  adam_tf23 is lazy-exact inside the library: reading the tensors from outside first brings
         every row up to date (bprx_sync_adam; a host call that returns at once when nothing is pending)."""
-        if self.optimizer == "adam_tf23" and getattr(self, "h", None) and self._t:
-            self.sync_adam()
-        return self._t
+        if getattr(self, "h", None) and self._t:
+            self.settle()
+            if self.optimizer == "adam_tf23":
+                self.sync_adam()
+        return self._t                                       # (a _Bound: a later look-up settles again)
 
     @t.setter
     def t(self, v):
-        self._t = v
+        self._t = _Bound(self, v)
 
     def adam_is_lazy(self):
         return bool(self.lib.bprx_adam_is_lazy(self.h))
 
     def sync_adam(self):
         _ffi.check(self.h, self.lib.bprx_sync_adam(self.h, _stream()))
+
+    def settle(self):
+        """bprx_settle: a step(want_loss=False) may leave its dense E|Bp update to the next step's index pass; before E / Bp are
+        read from outside the library it runs now (a host call that returns at once when nothing is pending)."""
+        if getattr(self, "h", None) and hasattr(self.lib, "bprx_settle"):
+            _ffi.check(self.h, self.lib.bprx_settle(self.h, _stream()))
+
+    def dense_pending(self):
+        return bool(self.lib.bprx_dense_pending(self.h)) if hasattr(self.lib, "bprx_dense_pending") else False
+
+    def set_loss_lag(self, on):
+        """bprx_set_loss_lag: steps given loss_out may defer their dense update too; a step's loss then lands in loss_out when the
+        NEXT step (or settle()) is enqueued -- for loops that read their loss buffer once per epoch, after settle().  The buffer
+        must outlive the lag: turn it off (which settles first) before the buffer goes, in a finally clause."""
+        if not on:
+            self.settle()                                    # a lagging loss lands now, while its buffer is still the caller's
+        if getattr(self, "h", None) and hasattr(self.lib, "bprx_set_loss_lag"):
+            _ffi.check(self.h, self.lib.bprx_set_loss_lag(self.h, 1 if on else 0))
 
     def close(self):
         if getattr(self, "h", None):

@@ -179,25 +179,34 @@ class BPRMF(RecommenderModel):
         # (the reference reads loss.numpy() after every step, BPRMF.py:125 -- a host synchronisation per step; here the
         #  step losses land in a device buffer and are read once per epoch, so the host runs ahead of the device)
         loss_buf = torch.zeros(max(1, steps_per_epoch), dtype=torch.float32, device=self.engine.device)
-        for batch in next_batch:
-            steps += 1
-            user, pos, neg = (as_index(b, self.engine.device) for b in batch)
-            self.engine.step(user, pos, neg, loss_out=loss_buf, loss_index=steps - 1)
-            if steps == steps_per_epoch:                                        # epoch is over
-                loss = float(loss_buf[:steps].double().sum().item())
-                epoch_text = 'Epoch {0}/{1} \tLoss: {2:.3f}'.format(it, self.params.epochs, loss / steps)
-                epoch_print = self.evaluator.eval(it, results, epoch_text, start_ep)
-                for metric in max_metrics.keys():
-                    if max_metrics[metric] <= results[it][metric + '_v']:
-                        max_metrics[metric] = results[it][metric + '_v']
-                        if metric == self.params.best_metric:
-                            best_epoch, best_state, best_epoch_print = it, self.state_dict(), epoch_print
-                if (it % self.verbose == 0 or it == 1) and self.verbose != -1:
-                    torch.save(self.state_dict(), os.path.join(wdir, f'weights-{it}-{self.directory_parameters}.pt'))
-                start_ep = time()
-                it += 1
-                loss = 0
-                steps = 0
+        # (loss_buf outlives every step of this loop, so a step's loss may land one launch later: its dense update then rides in
+        #  the next step's index pass; settle() before the buffer is read, and the lag ends with the loop)
+        self.engine.set_loss_lag(True)
+        try:
+            for batch in next_batch:
+                steps += 1
+                user, pos, neg = (as_index(b, self.engine.device) for b in batch)
+                self.engine.step(user, pos, neg, loss_out=loss_buf, loss_index=steps - 1)
+                if steps == steps_per_epoch:                                        # epoch is over
+                    self.engine.settle()
+                    loss = float(loss_buf[:steps].double().sum().item())
+                    epoch_text = 'Epoch {0}/{1} \tLoss: {2:.3f}'.format(it, self.params.epochs, loss / steps)
+                    epoch_print = self.evaluator.eval(it, results, epoch_text, start_ep)
+                    for metric in max_metrics.keys():
+                        if max_metrics[metric] <= results[it][metric + '_v']:
+                            max_metrics[metric] = results[it][metric + '_v']
+                            if metric == self.params.best_metric:
+                                best_epoch, best_state, best_epoch_print = it, self.state_dict(), epoch_print
+                    if (it % self.verbose == 0 or it == 1) and self.verbose != -1:
+                        torch.save(self.state_dict(), os.path.join(wdir, f'weights-{it}-{self.directory_parameters}.pt'))
+                    start_ep = time()
+                    it += 1
+                    loss = 0
+                    steps = 0
+        finally:
+            # however the loop ends (an exception in the evaluator, an interrupt): the last step's update and loss land while
+            # loss_buf is still alive, and steps asked for their loss afterwards (train_step) get it at once again
+            self.engine.set_loss_lag(False)
         print('Training end...')
         self._store_recs(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
         with open(os.path.join(rdir, f'results-metrics-{self.directory_parameters}') + '.pkl', 'wb') as f:

@@ -133,6 +133,19 @@ BPRX_API int bprx_set_adam_step(bprx_handle *h, int64_t iterations, void *stream
    directly (snapshot, inspection) calls bprx_sync_adam first: afterwards every row holds what TF's tables would hold after
    optimizer.iterations steps.  No-op for sgd, or when nothing is pending.  (BPRX_ADAM_LAZY=0: the sweeps, for A/B.) */
 BPRX_API int bprx_sync_adam(bprx_handle *h, void *stream);
+/* The deferred dense update.  A bprx_step of a plain VBPR handle that is not asked for its loss does not launch its dense E|Bp
+   update: the next segment-mode bprx_step runs it inside its index-pass launch (k_index_seg), on compute units that launch leaves
+   idle, with the hyper-parameters of the step it belongs to (a bprx_set_hyper in between does not reach it).  Every other entry
+   that takes a handle first runs a pending update with the stand-alone kernel on ITS stream, so the library itself never sees a
+   stale E / Bp; bprx_destroy drops it.  A caller that reads the bound E / Bp (or their Adam slots) directly calls bprx_settle
+   first, as it calls bprx_sync_adam: it returns at once when nothing is pending.  bprx_dense_pending: 1 while an update waits.
+   bprx_set_loss_lag(h, 1) lets a step WITH a loss pointer defer too: its loss is then written behind the launch that runs its
+   update (the next step, or a settling call), so the pointer must stay valid until then; the value has the same bits.  Before the
+   buffer goes: bprx_settle, then bprx_set_loss_lag(h, 0) -- on every way out of the loop that set it.
+   BPRX_DENSE_DEFER=0 (read by bprx_create): never defer.  The split-phase calls never defer. */
+BPRX_API int bprx_settle(bprx_handle *h, void *stream);
+BPRX_API int bprx_dense_pending(const bprx_handle *h);
+BPRX_API int bprx_set_loss_lag(bprx_handle *h, int on);
 BPRX_API int64_t bprx_get_adam_step(const bprx_handle *h);
 /* 1: adam_tf23 runs lazily-exact on this handle (per-row replay, bprx_sync_adam meaningful), 0: by whole-table sweeps.  Chosen at
    bprx_create from the table sizes and max_batch (BPRX_ADAM_LAZY=0 / 1 forces it); the arithmetic is the same. */
