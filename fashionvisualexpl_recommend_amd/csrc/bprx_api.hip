@@ -182,6 +182,9 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
   // 0.182 / 0.223 ms with the list, 0.231 / 0.239 ms streaming; B = 32 768 = 2B >= I: 0.287 vs 0.240 ms with occurrence segments);
   // BPRX_LIST_MODE = 0 never / 1 per step / 2 always.
   h->list_policy = vb ? std::min(std::max(env_int("BPRX_LIST_MODE", 1), 0), 2) : 0;
+  // BPRX_FOLD_CACHE: bprx_fold_in keeps a user's pair differences in LDS across its steps where they fit (bprx_foldin.hip).
+  // 0: every step gathers the item rows again (the form large users take anyway; the same bits).
+  h->fold_cache = env_int("BPRX_FOLD_CACHE", 1) != 0;
   if (h->list_policy) {
     const size_t cap = 2 * MB < I ? 2 * MB : I;
     A.zeros(&h->ilist, cap); A.zeros(&h->ilist_n, (size_t)2);
@@ -649,6 +652,34 @@ extern "C" int bprx_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *o
   if (h->cfg.embed_k % 2 == 0 && h->cfg.embed_d % 2 == 0)
     return bprx_launch_score_gemm(h, u0, u1, out, s);          // fp32 MFMA GEMM (K step 2)
   return bprx_launch_score_block(h, u0, u1, out, s);
+}
+
+// bprx_score_block for caller-owned user rows (users folded in by bprx_fold_in): the same kernels, their user tables pointed at
+// the caller's rows for the length of the launch.
+extern "C" int bprx_score_rows_block(bprx_handle *h, const float *Gu_rows, const float *Tu_rows, int64_t n_rows, int64_t r0, int64_t r1,
+                                     float *out, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (h->acf || h->af) BPRX_FAIL(h, BPRX_E_INVALID, "score_rows_block: needs a BPRMF or VBPR handle");
+  if (n_rows < 0 || n_rows >= ((int64_t)1 << 31) || r0 < 0 || r1 > n_rows || r0 > r1)
+    BPRX_FAIL(h, BPRX_E_INVALID, "score_rows_block: bad row range [%lld,%lld) of %lld", (long long)r0, (long long)r1, (long long)n_rows);
+  if (!h->bound) BPRX_FAIL(h, BPRX_E_STATE, "tables not bound (call bprx_bind_tables first)");
+  if (r0 == r1) return BPRX_OK;
+  if (!Gu_rows || !out || (h->cfg.embed_d > 0) != (Tu_rows != nullptr)) BPRX_FAIL(h, BPRX_E_INVALID, "score_rows_block: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = bprx_settle_pending(h, s))) return rc;
+  if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: every item row is read
+  if (h->cfg.model == BPRX_MODEL_VBPR && !h->p_valid) {
+    if ((rc = bprx_launch_cast_Et(h, s))) return rc;
+    if ((rc = bprx_launch_proj_fwd(h, nullptr, h->cfg.num_items, nullptr, 0, h->P, s))) return rc;
+    h->p_valid = true;
+  }
+  float *gu = h->t.Gu, *tu = h->t.Tu;
+  h->t.Gu = const_cast<float *>(Gu_rows); h->t.Tu = const_cast<float *>(Tu_rows);      // (read-only in both kernels)
+  rc = (h->cfg.embed_k % 2 == 0 && h->cfg.embed_d % 2 == 0) ? bprx_launch_score_gemm(h, (int32_t)r0, (int32_t)r1, out, s)
+                                                            : bprx_launch_score_block(h, (int32_t)r0, (int32_t)r1, out, s);
+  h->t.Gu = gu; h->t.Tu = tu;
+  return rc;
 }
 
 // ---- items outside the catalogue (include/bprx.h): bprx_project_rows here, bprx_score_new_block / bprx_topk_rows in

@@ -436,6 +436,21 @@ extern "C" int bprx_topk_rows(bprx_handle *h, int64_t nrows, int32_t width, floa
   return BPRX_OK;
 }
 
+// bprx_topk for rows that are not users of the handle: row r masks the items of its own list
+extern "C" int bprx_topk_lists(bprx_handle *h, int64_t nrows, float *scores, const int64_t *list_ptr, const int32_t *list_items,
+                               int32_t K, int32_t *idx, float *val, int32_t *flag, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
+  if (nrows < 0 || nrows >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "topk_lists: nrows = %lld out of range", (long long)nrows);
+  if (K <= 0 || K > TOPK_MAX) BPRX_FAIL(h, BPRX_E_INVALID, "topk_lists: K=%d outside [1, %d]", K, TOPK_MAX);
+  if (nrows == 0) return BPRX_OK;
+  if (!scores || !list_ptr || !list_items || !idx || !val || !flag) BPRX_FAIL(h, BPRX_E_INVALID, "topk_lists: null pointer");
+  hipLaunchKernelGGL(k_topk, dim3((unsigned)nrows), dim3(256), 0, (hipStream_t)stream, scores, 0, h->cfg.num_items, list_ptr,
+                     list_items, K, idx, val, flag);
+  BPRX_LAUNCH_CHECK(h, "k_topk<lists>");
+  return BPRX_OK;
+}
+
 extern "C" int bprx_score_new_block(bprx_handle *h, int32_t u0, int32_t u1, const float *P, int64_t n, float *out, void *stream) {
   int rc = bprx_new_items_check(h, "score_new_block", n);
   if (rc) return rc;

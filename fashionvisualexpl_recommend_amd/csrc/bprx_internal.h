@@ -255,6 +255,7 @@ struct bprx_handle {
   int32_t *slist, *slist_n;       // sgd fast path: list of the batch's SHARED rows (kind << 30 | row), two alternating cursors
   int num_cu;                     // compute units of the device (balanced forward grid)
   int fwd_variant;                // 0: the plain forward kernel (env BPRX_FWD_VARIANT, read at create), else the per-shape policy
+  int fold_cache;                 // env BPRX_FOLD_CACHE, read at create: 1 (default) bprx_fold_in runs its steps from LDS where a user's pairs fit
   float neg_bias_reg;             // factor of reg on the negative item's bias: 0.1 (VBPR.py:125), 1.0 for GradFashion
   // GradFashion (bprx_bind_factored, bprx_factored.hip): E / Bp of t are E_eff / Bp_eff, composed from the factors fx
   bool factored;

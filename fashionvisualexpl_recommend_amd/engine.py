@@ -92,6 +92,7 @@ class Engine:
         self.feat_dtype = feat_dtype
         self.feat_scale = float(feat_scale)
         self.max_batch = int(max_batch)
+        self._lr_reg = (float(lr), float(reg))               # what fold_in falls back on (set_hyper keeps it current)
         cfg = _ffi.Config(_ffi.ABI_VERSION, _ffi.MODEL[model], self.U, self.I, self.k, self.d, self.D,
                           _ffi.FEAT_DTYPE[feat_dtype], _ffi.OPTIMIZER[optimizer], self.device.index, self.max_batch,
                           lr, reg, beta1, beta2, epsilon,
@@ -536,6 +537,59 @@ class Engine:
                                                           _stream()))
         return out
 
+    # ---- users outside the training set (include/bprx.h: the reference's step on one user's pairs, the item side frozen) -------
+    def fold_in(self, pair_ptr, pos, neg, steps, Gu_rows, Tu_rows=None, lr=None, reg=None, optimizer=None, want_loss=True):
+        """bprx_fold_in: `steps` optimiser steps on each row of Gu_rows [n, k] / Tu_rows [n, d] (contiguous fp32 device tensors,
+        updated IN PLACE; Tu_rows is None iff d == 0) over the pairs (pos[p], neg[p]), p in [pair_ptr[r], pair_ptr[r + 1]), of row
+        r.  pair_ptr: int64 [n + 1].  lr / reg / optimizer default to the engine's.  Returns loss fp32 [n] (loss_steps, before the
+        last update) or None."""
+        ptr = torch.as_tensor(pair_ptr, dtype=torch.int64).to(self.device).contiguous()
+        n = int(ptr.numel()) - 1
+        p_, n_ = as_index(pos, self.device), as_index(neg, self.device)
+        if p_.numel() != n_.numel():
+            raise ValueError("fold_in: %d positives for %d negatives" % (p_.numel(), n_.numel()))
+        for name, t, w in (("Gu_rows", Gu_rows, self.k), ("Tu_rows", Tu_rows, self.d)):
+            if t is None:
+                continue
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n, w)):
+                raise ValueError("fold_in: %s must be a contiguous fp32 device tensor [%d, %d]" % (name, n, w))
+        lr = self._hyper()[0] if lr is None else float(lr)
+        reg = self._hyper()[1] if reg is None else float(reg)
+        opt = _ffi.OPTIMIZER[self.optimizer if optimizer is None else optimizer]
+        loss = torch.empty(max(n, 0), dtype=torch.float32, device=self.device) if want_loss else None
+        if p_.numel() == 0:                                  # (nobody has a pair: the library still wants the pointers)
+            p_ = n_ = torch.zeros(1, dtype=torch.int32, device=self.device)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _ffi.check(self.h, self.lib.bprx_fold_in(self.h, p(ptr), p(p_), p(n_), n,
+                                                 int(steps), lr, reg, opt, p(Gu_rows), p(Tu_rows), p(loss), _stream()))
+        return loss
+
+    def score_rows_block(self, Gu_rows, Tu_rows, r0, r1, out=None):
+        """bprx_score_rows_block: score_block for rows [r0, r1) of caller-owned user tables: fp32 [r1 - r0, I]."""
+        if out is None:
+            out = torch.empty((r1 - r0, self.I), dtype=torch.float32, device=self.device)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _ffi.check(self.h, self.lib.bprx_score_rows_block(self.h, p(Gu_rows), p(Tu_rows), int(Gu_rows.shape[0]), int(r0), int(r1),
+                                                          p(out), _stream()))
+        return out
+
+    def topk_lists(self, scores, lists_csr, K):
+        """bprx_topk_lists: bprx_topk for the rows of a contiguous fp32 [nrows, I] device tensor; row r masks (IN `scores`) the
+        items of list r of lists_csr = (int64 ptr [nrows + 1], int32 items): (idx int32 [nrows, K], val, flag int32 [nrows])."""
+        nrows, K = int(scores.shape[0]), int(K)
+        idx = torch.empty((nrows, max(K, 0)), dtype=torch.int32, device=self.device)
+        val = torch.empty((nrows, max(K, 0)), dtype=torch.float32, device=self.device)
+        flag = torch.empty(nrows, dtype=torch.int32, device=self.device)
+        ptr, items = lists_csr
+        if items.numel() == 0:                               # (every list empty: the library still wants a pointer)
+            items = torch.zeros(1, dtype=torch.int32, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        _ffi.check(self.h, self.lib.bprx_topk_lists(self.h, nrows, p(scores), p(ptr), p(items), K, p(idx), p(val), p(flag), _stream()))
+        return idx, val, flag
+
+    def _hyper(self):
+        return self._lr_reg
+
     def tables_dirty(self):
         """Call after writing any bound table from outside the library (bprx_tables_dirty): the handle reuses images
         derived from E/Bp (their bf16/fp8 copy, the item projections) until a step changes them."""
@@ -547,6 +601,7 @@ class Engine:
 
     def set_hyper(self, lr, reg):
         _ffi.check(self.h, self.lib.bprx_set_hyper(self.h, lr, reg))
+        self._lr_reg = (float(lr), float(reg))
 
     @property
     def adam_step(self):

@@ -33,6 +33,41 @@ class _Scores:
         return self.tensor.cpu().numpy()
 
 
+def draw_fold_pairs(histories, num_items, negatives, seed):
+    """The (positive, negative) pairs of users the model was not trained on, drawn on the host with
+    numpy.random.default_rng(seed): users in order, each user's positives in history order, and for each positive `negatives`
+    uniform draws over the items that are not in that user's history (by rejection), kept next to each other.  A history that
+    covers the catalogue (or is empty) gives no pairs.  Returns (pair_ptr int64 [n + 1], pos int32, neg int32); an id outside
+    [0, num_items) raises ValueError."""
+    I, negatives = int(num_items), int(negatives)
+    if negatives < 1:
+        raise ValueError("draw_fold_pairs: negatives = %d < 1" % negatives)
+    rng = np.random.default_rng(seed)
+    ptr = np.zeros(len(histories) + 1, np.int64)
+    pos, neg = [], []
+    mask = np.zeros(I, bool)
+    for r, hist in enumerate(histories):
+        h = np.asarray(list(hist), dtype=np.int64).reshape(-1)
+        if h.size and (h.min() < 0 or h.max() >= I):
+            raise ValueError("draw_fold_pairs: user %d has an item outside [0, %d)" % (r, I))
+        mask[h] = True
+        need = 0 if int(mask.sum()) >= I else h.size * negatives
+        out = np.empty(need, np.int64)
+        filled = 0
+        while filled < need:
+            c = rng.integers(0, I, size=need - filled)
+            c = c[~mask[c]]
+            out[filled:filled + c.size] = c
+            filled += c.size
+        mask[h] = False
+        if need:
+            pos.append(np.repeat(h, negatives))
+            neg.append(out)
+        ptr[r + 1] = ptr[r] + need
+    cat = lambda parts: (np.concatenate(parts) if parts else np.zeros(0, np.int64)).astype(np.int32)
+    return ptr, cat(pos), cat(neg)
+
+
 class RecommenderModel:
     def __init__(self, data, params):                       # RecommenderModel.py:16-25
         self.data = data
@@ -209,6 +244,7 @@ class BPRMF(RecommenderModel):
             self.engine.set_loss_lag(False)
         print('Training end...')
         self._store_recs(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
+        self._store_new_user_recs(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
         with open(os.path.join(rdir, f'results-metrics-{self.directory_parameters}') + '.pkl', 'wb') as f:
             pickle.dump(results, f)                                             # utils/write.py:14-22
         print("Store Best Model at Epoch {0}".format(best_epoch))
@@ -218,6 +254,7 @@ class BPRMF(RecommenderModel):
             torch.save(best_state, os.path.join(wdir, f'best-weights-{best_epoch}-{self.directory_parameters}.pt'))
             self.load_state_dict(best_state)
         self._store_recs(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
+        self._store_new_user_recs(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
         self.load_state_dict(last_state)
         print('End Store Best Model!')
         print('Best Values for Each Metric:\nHR\tPrec\tRec\tAUC\tnDCG\n{}\t{}\t{}\t{}\t{}\n'.format(
@@ -228,6 +265,66 @@ class BPRMF(RecommenderModel):
     def _store_recs(self, path):
         """What train() leaves at the recs-* / best-recs-* paths: the top-K lists (BPRMF.py:167-187)."""
         self.evaluator.store_recommendation(path=path)
+
+    # ---- users the model was not trained on: the reference's step on one user's pairs, the item side frozen (include/bprx.h) ----
+    def fold_in_users(self, histories, steps=30, negatives=4, lr=None, reg=None, optimizer=None, seed=0, init=None):
+        """Rows for users who arrive after training with a history of catalogue items each: (Gu_new [n, k], Tu_new [n, d]) device
+        tensors (Tu_new is None for BPRMF), fitted by Engine.fold_in over the pairs of draw_fold_pairs(histories, num_items,
+        negatives, seed).  lr / reg / optimizer: None = the run's.  init: None = zero rows, or (Gu rows, Tu rows) to start from."""
+        eng = self.engine
+        n = len(histories)
+        ptr, pos, neg = draw_fold_pairs(histories, self.num_items, negatives, seed)
+        def rows(x, w):
+            if w == 0:
+                return None
+            if x is None:
+                return torch.zeros((n, w), dtype=torch.float32, device=eng.device)
+            return torch.as_tensor(np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(n, w),
+                                   device=eng.device).contiguous().clone()
+        g0, t0 = (None, None) if init is None else init
+        Gu, Tu = rows(g0, eng.k), rows(t0, eng.d)
+        eng.fold_in(ptr, pos, neg, steps, Gu, Tu, lr=self.learning_rate if lr is None else lr, reg=self.reg if reg is None else reg,
+                    optimizer=self.optimizer_name if optimizer is None else optimizer, want_loss=False)
+        return Gu, Tu
+
+    def recommend_new_users(self, histories, k=None, **fold):
+        """The k (default top_k) best catalogue items of every new user, their own histories masked: numpy idx int [n, min(k, I)]
+        and val, best first.  The rows are fitted by fold_in_users(histories, **fold), scored in row blocks and ranked on the
+        device; rows whose list depends on the order of equal scores are redone with numpy on the GPU's (masked) row, as
+        Evaluator.store_recommendation does."""
+        eng = self.engine
+        n, I = len(histories), self.num_items
+        k = self.evaluator.k if k is None else int(k)
+        kk = min(k, I)
+        Gu, Tu = self.fold_in_users(histories, **fold)
+        idx_all, val_all = np.zeros((n, kk), np.int64), np.zeros((n, kk), np.float32)
+        blk = max(1, min(self.evaluator.user_block, (1 << 27) // max(1, I)))
+        for b0 in range(0, n, blk):
+            b1 = min(n, b0 + blk)
+            sc = eng.score_rows_block(Gu, Tu, b0, b1)
+            idx, val, flag = (x.cpu().numpy() for x in eng.topk_lists(sc, eng.csr(histories[b0:b1]), k))
+            idx_all[b0:b1], val_all[b0:b1] = idx[:, :kk], val[:, :kk]
+            for r in np.nonzero(flag)[0]:
+                row = sc[int(r)].cpu().numpy()
+                top_k_id = row.argsort()[-k:][::-1]
+                idx_all[b0 + r], val_all[b0 + r] = top_k_id, row[top_k_id]
+        return idx_all, val_all
+
+    def _store_new_user_recs(self, path):
+        """params.new_users: new-user-recs-* next to the recs-* file at `path`, rows 'label\ti\tscore', best first."""
+        src = getattr(self.params, "new_users", None)
+        if not src:
+            return
+        from .train_rec import read_new_users
+        labels, lists = read_new_users(src)
+        d, f = os.path.split(path)
+        idx, val = self.recommend_new_users(lists, steps=getattr(self.params, "fold_steps", 30),
+                                            negatives=getattr(self.params, "fold_negatives", 4),
+                                            seed=getattr(self.params, "init_seed", 0))
+        with open(os.path.join(d, f.replace("recs-", "new-user-recs-", 1)), 'w') as out:
+            for r, label in enumerate(labels):
+                for q in range(idx.shape[1]):
+                    out.write(label + '\t' + str(idx[r, q]) + '\t' + str(val[r, q]) + '\n')
 
 
 def _table_property(name):

@@ -63,6 +63,13 @@ def parse_args(argv=None):
                              "not trained on: also write new-recs-* / best-new-recs-* files with every user's top-k of them by the "
                              "visual score Tu.(fE) + f.Bp (rows divided by the training max-abs), and with --feat_explain L also "
                              "new-expl-* / best-new-expl-*")
+    parser.add_argument('--new_users', default=None, metavar='PATH',
+                        help="bprmf, vbpr, grad_fashion: a TSV of `label<TAB>item` rows, the histories of users the model was not "
+                             "trained on (labels are free text, kept in first-appearance order).  Their rows are fitted with the "
+                             "item side frozen and new-user-recs-* / best-new-user-recs-* files (label, item, score) are written "
+                             "next to recs-* / best-recs-*")
+    parser.add_argument('--fold_steps', type=int, default=30, help='--new_users: optimiser steps per new user')
+    parser.add_argument('--fold_negatives', type=int, default=4, help='--new_users: sampled negatives per history item')
     # not in the reference
     parser.add_argument('--dropout', type=float, default=0.5,
                         help="attentive_fashion: rate of the encoders' Dropout layers (AttentiveFashion.py:53,62,70: 0.5)")
@@ -108,9 +115,37 @@ def parse_args(argv=None):
         if len(args.new_items) != want:
             parser.error("--new_items takes %d path%s with --rec %s (got %d)" % (want, "s" if want > 1 else "", args.rec,
                                                                                  len(args.new_items)))
+    if args.new_users is not None and args.rec not in ('bprmf', 'vbpr', 'grad_fashion'):
+        parser.error("--new_users needs --rec bprmf, vbpr or grad_fashion (got --rec %s)" % args.rec)
+    if args.fold_steps < 1 or args.fold_negatives < 1:
+        parser.error("--fold_steps and --fold_negatives take values >= 1 (got %s, %s)" % (args.fold_steps, args.fold_negatives))
     if not 0.0 <= args.dropout < 1.0:
         parser.error("--dropout takes a rate in [0, 1) (got %s)" % args.dropout)
     return args
+
+
+def read_new_users(path):
+    """The --new_users file: rows `label<TAB>item` -> (labels in first-appearance order, one item list per label, in file order).
+    Empty lines are skipped; anything else that is not a label and an integer item raises ValueError with its line number."""
+    labels, index, lists = [], {}, []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip():
+                continue
+            parts = line.split("\t")
+            if len(parts) != 2 or parts[0] == "":
+                raise ValueError("%s:%d: expected `label<TAB>item`, got %r" % (path, ln, line))
+            try:
+                item = int(parts[1])
+            except ValueError:
+                raise ValueError("%s:%d: the item %r is not an integer" % (path, ln, parts[1])) from None
+            if parts[0] not in index:
+                index[parts[0]] = len(labels)
+                labels.append(parts[0])
+                lists.append([])
+            lists[index[parts[0]]].append(item)
+    return labels, lists
 
 
 def train(argv=None):
@@ -121,6 +156,8 @@ def train(argv=None):
         raise NotImplementedError('--feat_explain runs on one GPU (the sharded drivers write no expl-* files): use --world_size 1')
     if args.new_items is not None and int(args.world_size) > 1:
         raise NotImplementedError('--new_items runs on one GPU (the sharded drivers write no new-recs-* files): use --world_size 1')
+    if args.new_users is not None and int(args.world_size) > 1:
+        raise NotImplementedError('--new_users runs on one GPU (the sharded drivers write no new-user-recs-* files): use --world_size 1')
     if args.new_items is not None and args.dtype == 'fp8':
         raise ValueError('--new_items runs with --dtype fp32 or bf16 (an fp8 table is scaled for the training max-abs: a new row '
                          'may saturate)')

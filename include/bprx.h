@@ -247,6 +247,43 @@ BPRX_API int bprx_feat_explain_new(bprx_handle *h, const void *Fnew, int64_t n_n
                                    int64_t n, int32_t ncols, int32_t top, float *score, int32_t *col, float *contrib, float *map,
                                    void *stream);
 
+/* ---- BPRMF, VBPR and GradFashion: users the model was not trained on ------------------------------------------------------
+   A user who arrives after training with a short history of catalogue items has no row of Gu / Tu.  With every item-side
+   parameter frozen, the reference's loss for one user (VBPR.py:117-127 with Gi, Bi, E, Bp held fixed) is a convex problem in that
+   user's k + d numbers.  For new user r with pairs (i_p, j_p), p in [pair_ptr[r], pair_ptr[r+1]), n_r of them:
+       z_i = [Gi_i | P_i[0:d]]        c_i = Bi_i + P_i[d]          (P = F.[E|Bp], the cached projections; BPRMF: d = 0, c_i = Bi_i)
+       D_p = z_i - z_j                dc_p = c_i - c_j             (one fp32 subtraction per element, formed once)
+       w = [gamma | theta] starts at the caller's row; for t = 1 .. steps:
+         x_p = w.D_p + dc_p           s_p = sigmoid(-clip(x_p, -80, 1e8))      (inclusive bounds, no gradient outside)
+         g = sum_p (-s_p D_p) + 2 reg n_r w                                     (summed in pair order)
+         loss_t = sum_p softplus(-clip(x_p)) + reg n_r |w|^2
+         BPRX_OPT_SGD:        w <- w - lr g
+         BPRX_OPT_ADAM_TF23:  the sparse-variable rule of the Gu / Tu rows, slots starting at zero,
+                              lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t); beta1, beta2, epsilon are the handle's
+   i.e. one train_step of the reference on a batch made of this user's pairs with everything but the user's row frozen: for
+   steps = 1, started from a trained user's row, the row moves as bprx_step on the same batch moves it.
+   bprx_fold_in: pair_ptr int64 [n+1], pos / neg int32 (device); Gu_rows fp32 [n, k] and Tu_rows fp32 [n, d] in / out (Tu_rows NULL
+   iff d == 0); loss fp32 [n] or NULL: loss_steps, evaluated before the last update, as train_step returns it.  A user without
+   pairs keeps its row and has loss 0.  lr, reg, optimizer are the call's (the handle's own are not read).
+   Handles: a bound BPRMF or VBPR handle, plain or factored, any feature dtype (the call reads P, never F).  BPRX_E_INVALID for a
+   NULL handle, an ACF or AttentiveFashion handle, a NULL pointer, n < 0, steps < 1, an unknown optimizer, k + d > 1024;
+   BPRX_E_STATE for an unbound handle; n == 0: BPRX_OK.  Item ids out of range are clamped and reported by bprx_sync_check
+   (BPRX_E_RANGE).  Like bprx_score_block the call first settles a pending dense update, brings lazy adam_tf23 rows up to date and
+   makes P current; apart from that it writes its outputs only and allocates nothing.  No atomics: a user's result depends on its
+   own pairs, its start row and the tables only -- not on n, on its position, or on BPRX_FOLD_CACHE (0: every step gathers the
+   item rows again instead of keeping D_p in LDS where a user's pairs fit; read by bprx_create). */
+BPRX_API int bprx_fold_in(bprx_handle *h, const int64_t *pair_ptr, const int32_t *pos, const int32_t *neg, int64_t n, int32_t steps,
+                          float lr, float reg, int32_t optimizer, float *Gu_rows, float *Tu_rows, float *loss, void *stream);
+/* bprx_score_block for caller-owned user rows: out fp32 [(r1-r0), num_items] for rows [r0, r1) of Gu_rows [n_rows, k] /
+   Tu_rows [n_rows, d] (NULL iff d == 0).  The same kernels (the non-MFMA one for an odd k or d), P made current first: a slice of
+   the handle's own Gu / Tu gives the bits of bprx_score_block.  0 <= r0 <= r1 <= n_rows < 2^31; errors as for bprx_fold_in. */
+BPRX_API int bprx_score_rows_block(bprx_handle *h, const float *Gu_rows, const float *Tu_rows, int64_t n_rows, int64_t r0, int64_t r1,
+                                   float *out, void *stream);
+/* bprx_topk for nrows (not bounded by num_users) rows of catalogue width: row r masks the items list_items[list_ptr[r] ..
+   list_ptr[r+1]) IN `scores` (list_ptr int64 [nrows+1], device).  Selection, order and flag rules, K and outputs as bprx_topk. */
+BPRX_API int bprx_topk_lists(bprx_handle *h, int64_t nrows, float *scores, const int64_t *list_ptr, const int32_t *list_items,
+                             int32_t K, int32_t *idx, float *val, int32_t *flag, void *stream);
+
 /* ---- ACF (ACF.py:20-270) on a BPRMF handle ------------------------------------------------------------------------------
    Attentive Collaborative Filtering over per-item feature maps f_l [M, C] (M = H*W spatial components).  For user u with
    history P(u) (ACF.py:135-181):
