@@ -8,8 +8,6 @@
 
 static char g_create_err[512] = "";
 
-static int check_ready(bprx_handle *h, int64_t B);
-
 extern "C" int bprx_abi_version(void) { return BPRX_ABI_VERSION; }
 
 extern "C" const char *bprx_last_error(const bprx_handle *h) { return h ? h->err : g_create_err; }
@@ -266,7 +264,7 @@ static int bind_tables(bprx_handle *h, const bprx_tables *t, bool factored) {
   }
   if (((uintptr_t)t->Gu | (uintptr_t)t->Gi | (uintptr_t)t->Tu | (uintptr_t)t->F | (uintptr_t)t->E) & 15)
     BPRX_FAIL(h, BPRX_E_INVALID, "bind_tables: table base pointers must be 16-byte aligned");
-  { const int rc = bprx_settle_pending(h, nullptr); if (rc) return rc; }   // (on the tables bound so far; the null stream as below)
+  { const int rc = bprx_enter(h, "bind_tables", 0, KIND_ANY, nullptr); if (rc) return rc; }   // (the tables bound so far, the null stream)
   h->t = *t;
   h->factored = factored;
   if (!factored) h->neg_bias_reg = 0.1f;
@@ -324,21 +322,17 @@ extern "C" int bprx_bind_factored(bprx_handle *h, const bprx_tables *t, const bp
 }
 
 extern "C" int bprx_explain_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t n, float *out, void *stream) {
-  int rc = check_ready(h, 0);
-  if (rc) return rc;
-  if ((rc = bprx_settle_pending(h, (hipStream_t)stream))) return rc;
-  if (!h->factored) BPRX_FAIL(h, BPRX_E_STATE, "explain_pairs: the handle is not bound with bprx_bind_factored");
+  if (!h) return BPRX_E_INVALID;
   if (n < 0 || n > ((int64_t)1 << 32)) BPRX_FAIL(h, BPRX_E_INVALID, "explain_pairs: n = %lld out of range", (long long)n);
-  if (n == 0) return BPRX_OK;
-  if (!user || !item || !out) BPRX_FAIL(h, BPRX_E_INVALID, "explain_pairs: null pointer");
+  if (n && (!user || !item || !out)) BPRX_FAIL(h, BPRX_E_INVALID, "explain_pairs: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: Tu rows must be current
+  const int rc = bprx_enter(h, "explain_pairs", NEED_BOUND | NEED_ROWS, KIND_FACTORED, s);
+  if (rc || n == 0) return rc;
   return bprx_launch_explain(h, user, item, n, out, s);
 }
 
 extern "C" int bprx_tables_dirty(bprx_handle *h, void *stream) {
-  if (!h) return BPRX_E_INVALID;
-  { const int rc = bprx_settle_pending(h, (hipStream_t)stream); if (rc) return rc; }
+  { const int rc = bprx_enter(h, "tables_dirty", 0, KIND_ANY, (hipStream_t)stream); if (rc) return rc; }
   h->et_valid = h->p_valid = h->absmax_valid = false;
   if (h->acf) bprx_acf_invalidate(h);                      // ACF: the evaluation profiles follow the tables
   if (h->af) bprx_af_invalidate(h);                        // AttentiveFashion: so do the item encodings
@@ -359,8 +353,8 @@ extern "C" int bprx_set_hyper(bprx_handle *h, float lr, float reg) {
 }
 
 extern "C" int bprx_set_adam_step(bprx_handle *h, int64_t it, void *stream) {
-  if (!h || it < 0) return BPRX_E_INVALID;
-  { const int rc = bprx_settle_pending(h, (hipStream_t)stream); if (rc) return rc; }
+  if (it < 0) return BPRX_E_INVALID;
+  { const int rc = bprx_enter(h, "set_adam_step", 0, KIND_ANY, (hipStream_t)stream); if (rc) return rc; }
   h->adam_t = it;
   return h->bound ? bprx_launch_adam_reset(h, it, (hipStream_t)stream) : BPRX_OK;
 }
@@ -368,9 +362,10 @@ extern "C" int bprx_set_adam_step(bprx_handle *h, int64_t it, void *stream) {
 extern "C" int64_t bprx_get_adam_step(const bprx_handle *h) { return h ? h->adam_t : -1; }
 extern "C" int bprx_adam_is_lazy(const bprx_handle *h) { return h ? (h->adam_lazy ? 1 : 0) : BPRX_E_INVALID; }
 
-static int check_ready(bprx_handle *h, int64_t B) {
+// the preamble of a step, which stays outside the read gate: plan_step carries or settles a pending update
+static int check_step(bprx_handle *h, int64_t B) {
   if (!h) return BPRX_E_INVALID;
-  if (!h->bound) BPRX_FAIL(h, BPRX_E_STATE, "tables not bound (call bprx_bind_tables first)");
+  if (!h->bound) BPRX_FAIL(h, BPRX_E_STATE, BPRX_NOT_BOUND, "step");
   if (B < 0 || B > h->cfg.max_batch) BPRX_FAIL(h, BPRX_E_INVALID, "B=%lld outside [0, max_batch=%lld]", (long long)B, (long long)h->cfg.max_batch);
   return BPRX_OK;
 }
@@ -383,6 +378,25 @@ int bprx_settle_pending(bprx_handle *h, hipStream_t s) {
   int rc = bprx_launch_dense_args(h, q.a, s);
   if (!rc && q.loss_out) rc = bprx_launch_loss_reduce_at(h, q.loss_B, q.loss_nsq, q.loss_reg, q.loss_out, s);
   return rc;
+}
+
+// The gate of every entry point that takes a handle: what plan_read decides, run in its order on `s`.  An entry validates its
+// arguments, enters, returns if there is no work, then launches.  Outside the gate: bprx_step and the split-phase begin (check_step:
+// they may carry the update), the samplers, the profile calls, bprx_last_error, bprx_set_hyper / bprx_set_loss_lag, the pure
+// getters and bprx_settle / bprx_dense_pending.
+int bprx_enter(bprx_handle *h, const char *what, unsigned need, int kind, hipStream_t s) {
+  if (!h) return BPRX_E_INVALID;
+  const ReadPlan p = plan_read(*h, need, kind);
+  if (p.error) BPRX_FAIL(h, p.error, p.why, what);
+  int rc;
+  if (p.settle && (rc = bprx_settle_pending(h, s))) return rc;
+  if (p.sync && (rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;
+  if (p.cast_et && (rc = bprx_launch_cast_Et(h, s))) return rc;
+  if (p.project) {                                         // P = F.[E|Bp] once per parameter state
+    if ((rc = bprx_launch_proj_fwd(h, nullptr, h->cfg.num_items, nullptr, 0, h->P, s))) return rc;
+    h->p_valid = true;
+  }
+  return BPRX_OK;
 }
 
 extern "C" int bprx_settle(bprx_handle *h, void *stream) {
@@ -399,29 +413,23 @@ extern "C" int bprx_set_loss_lag(bprx_handle *h, int on) {
 }
 
 extern "C" int bprx_sync_adam(bprx_handle *h, void *stream) {
-  int rc = check_ready(h, 0);
-  if (rc) return rc;
-  if ((rc = bprx_settle_pending(h, (hipStream_t)stream))) return rc;
-  return bprx_launch_adam_sync(h, h->adam_t, (hipStream_t)stream);
+  return bprx_enter(h, "sync_adam", NEED_BOUND | NEED_ROWS, KIND_ANY, (hipStream_t)stream);
 }
 
 extern "C" int bprx_score_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int64_t B, float *x, void *stream) {
-  int rc = check_ready(h, B);
-  if (rc) return rc;
-  if (B == 0) return BPRX_OK;
-  if (!user || !item || !x) BPRX_FAIL(h, BPRX_E_INVALID, "score_pairs: null pointer");
+  if (!h) return BPRX_E_INVALID;
+  if (B < 0 || B > h->cfg.max_batch) BPRX_FAIL(h, BPRX_E_INVALID, "B=%lld outside [0, max_batch=%lld]", (long long)B, (long long)h->cfg.max_batch);
+  int rc;
+  if (B && (!user || !item || !x)) BPRX_FAIL(h, BPRX_E_INVALID, "score_pairs: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = bprx_settle_pending(h, s))) return rc;
+  // every item's projection is at hand (p_valid), or one projection row per pair is made from the image
+  rc = bprx_enter(h, "score_pairs", NEED_BOUND | NEED_ROWS | (h->p_valid ? 0 : NEED_ET), KIND_ANY, s);
+  if (rc || B == 0) return rc;
   if (h->acf) return bprx_acf_score_pairs(h, user, item, B, x, s);
   if (h->af) return bprx_af_pairs(h, user, item, B, x, nullptr, s);
-  if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: the rows must be current
-  if (h->cfg.model == BPRX_MODEL_VBPR) {
-    if (h->p_valid) return bprx_launch_score(h, user, item, B, nullptr, 0, x, s);      // every item's projection is at hand
-    if ((rc = bprx_launch_cast_Et(h, s))) return rc;
-    if ((rc = bprx_launch_proj_fwd(h, item, B, nullptr, 0, h->Ppair, s))) return rc;     // one projection row per pair
-    return bprx_launch_score(h, user, item, B, h->Ppair, 1, x, s);
-  }
-  return bprx_launch_score(h, user, item, B, nullptr, 0, x, s);
+  if (h->cfg.model != BPRX_MODEL_VBPR || h->p_valid) return bprx_launch_score(h, user, item, B, nullptr, 0, x, s);
+  if ((rc = bprx_launch_proj_fwd(h, item, B, nullptr, 0, h->Ppair, s))) return rc;
+  return bprx_launch_score(h, user, item, B, h->Ppair, 1, x, s);
 }
 
 // A planned step becomes the step in flight: the only place that moves the carried state at the start of a step.
@@ -471,7 +479,7 @@ static int launch_sparse_half(bprx_handle *h, const StepPlan &p, hipStream_t s) 
 // them while bprx_step_begin_dense (item rows, W, dE|dBp = F^T W) is still running.
 static int step_begin_sparse(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B, bool fused_reduce,
                              hipStream_t s) {
-  int rc = check_ready(h, B);
+  int rc = check_step(h, B);
   if (rc) return rc;
   if (h->step_stage) BPRX_FAIL(h, BPRX_E_STATE, "step_begin called twice without step_end");
   if (h->acf) BPRX_FAIL(h, BPRX_E_STATE, "step_begin: an ACF handle takes whole steps only (bprx_step)");
@@ -522,16 +530,9 @@ extern "C" int bprx_step_begin(bprx_handle *h, const int32_t *user, const int32_
 }
 
 extern "C" int bprx_step_project(bprx_handle *h, void *stream) {
-  int rc = check_ready(h, 0);
-  if (rc) return rc;
-  if (h->cfg.model != BPRX_MODEL_VBPR) return BPRX_OK;
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = bprx_settle_pending(h, s))) return rc;
-  if ((rc = bprx_launch_cast_Et(h, s))) return rc;
-  if (!h->p_valid && (rc = bprx_launch_proj_fwd(h, nullptr, h->cfg.num_items, nullptr, 0, h->P, s))) return rc;
-  h->p_valid = true;
-  h->proj_fresh = true;
-  return BPRX_OK;
+  const int rc = bprx_enter(h, "step_project", NEED_BOUND | NEED_ET | NEED_P_ALL, KIND_ANY, (hipStream_t)stream);
+  if (!rc && h->cfg.model == BPRX_MODEL_VBPR) h->proj_fresh = true;
+  return rc;
 }
 
 extern "C" int bprx_user_grad(bprx_handle *h, float **dGu, float **dTu) {
@@ -544,7 +545,7 @@ extern "C" int bprx_user_grad(bprx_handle *h, float **dGu, float **dTu) {
 extern "C" int bprx_clear_user_grad(bprx_handle *h, int64_t n_rows, int32_t marks_only, void *stream) {
   if (!h || n_rows < 0 || n_rows > h->cfg.num_users) return BPRX_E_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  { const int rc = bprx_settle_pending(h, s); if (rc) return rc; }
+  { const int rc = bprx_enter(h, "clear_user_grad", 0, KIND_ANY, s); if (rc) return rc; }
   if (!marks_only) {                                       // (bprx_route_pack has already returned the gradient rows to zero)
     BPRX_HIP(h, hipMemsetAsync(h->dGu, 0, (size_t)n_rows * h->cfg.embed_k * sizeof(float), s));
     if (h->cfg.embed_d) BPRX_HIP(h, hipMemsetAsync(h->dTu, 0, (size_t)n_rows * h->cfg.embed_d * sizeof(float), s));
@@ -563,7 +564,7 @@ extern "C" int bprx_item_grad(bprx_handle *h, float **dGi, float **dBi) {
 extern "C" int bprx_clear_item_grad(bprx_handle *h, int64_t n_rows, int32_t marks_only, void *stream) {
   if (!h || n_rows < 0 || n_rows > h->cfg.num_items) return BPRX_E_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  { const int rc = bprx_settle_pending(h, s); if (rc) return rc; }
+  { const int rc = bprx_enter(h, "clear_item_grad", 0, KIND_ANY, s); if (rc) return rc; }
   if (!marks_only) {
     BPRX_HIP(h, hipMemsetAsync(h->dGi, 0, (size_t)n_rows * h->cfg.embed_k * sizeof(float), s));
     BPRX_HIP(h, hipMemsetAsync(h->dBi, 0, (size_t)n_rows * sizeof(float), s));
@@ -611,13 +612,11 @@ extern "C" int bprx_step_end(bprx_handle *h, float *loss_out, void *stream) { re
 extern "C" int bprx_step(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B,
                          float *loss_out, void *stream) {
   if (!h) return BPRX_E_INVALID;
-  if (h->acf) {                                              // ACF: its own launch sequence
-    const int rc = check_ready(h, B);
-    return rc ? rc : bprx_acf_step(h, user, pos, neg, B, loss_out, (hipStream_t)stream);
-  }
-  if (h->af) {                                               // AttentiveFashion likewise
-    const int rc = check_ready(h, B);
-    return rc ? rc : bprx_af_step(h, user, pos, neg, B, loss_out, (hipStream_t)stream);
+  if (h->acf || h->af) {                                     // ACF, AttentiveFashion: their own launch sequences
+    const int rc = check_step(h, B);
+    if (rc) return rc;
+    return h->acf ? bprx_acf_step(h, user, pos, neg, B, loss_out, (hipStream_t)stream)
+                  : bprx_af_step(h, user, pos, neg, B, loss_out, (hipStream_t)stream);
   }
   // no all-reduce in between: the dense update may sum the split-K slabs itself (StepPlan::fused_reduce)
   int rc = step_begin(h, user, pos, neg, B, true, stream);
@@ -625,91 +624,56 @@ extern "C" int bprx_step(bprx_handle *h, const int32_t *user, const int32_t *pos
   return rc;
 }
 
+// rows [u0, u1) of the given user tables against every item: the fp32 MFMA GEMM (K step 2) where the widths allow it
+static int score_rows(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s, UserRows rows) {
+  return (h->cfg.embed_k % 2 == 0 && h->cfg.embed_d % 2 == 0) ? bprx_launch_score_gemm(h, u0, u1, out, s, rows)
+                                                            : bprx_launch_score_block(h, u0, u1, out, s, rows);
+}
+
 extern "C" int bprx_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, void *stream) {
-  int rc = check_ready(h, 0);
-  if (rc) return rc;
+  if (!h) return BPRX_E_INVALID;
   if (u0 < 0 || u1 > h->cfg.num_users || u0 > u1 || !out) BPRX_FAIL(h, BPRX_E_INVALID, "score_block: bad user range [%d,%d)", u0, u1);
-  if (u0 == u1) return BPRX_OK;
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = bprx_settle_pending(h, s))) return rc;
-  if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: predict_all reads every row
+  int rc = bprx_enter(h, "score_block", NEED_BOUND | NEED_ROWS | NEED_P_ALL, KIND_ANY, s);
+  if (rc || u0 == u1) return rc;
   if (h->af) return bprx_af_block(h, u0, u1, out, nullptr, s);
   if (h->acf) {
     // ACF.py:216-227: Gu' (evaluation histories) once per parameter state, then the BPRMF scoring kernels with Gu' in place of
     // Gu (Bi is zero: Bi + Gu'.Gi is the reference's Gu' Gi^T exactly)
     if ((rc = bprx_acf_eval_profiles(h, s))) return rc;
-    float *gu = h->t.Gu;
-    h->t.Gu = bprx_acf_eval_gu(h);
-    rc = h->cfg.embed_k % 2 == 0 ? bprx_launch_score_gemm(h, u0, u1, out, s) : bprx_launch_score_block(h, u0, u1, out, s);
-    h->t.Gu = gu;
-    return rc;
+    return score_rows(h, u0, u1, out, s, {bprx_acf_eval_gu(h), h->t.Tu});
   }
-  if (h->cfg.model == BPRX_MODEL_VBPR && !h->p_valid) {   // P = F.[E|Bp] once per parameter state, not once per user block
-    if ((rc = bprx_launch_cast_Et(h, s))) return rc;
-    if ((rc = bprx_launch_proj_fwd(h, nullptr, h->cfg.num_items, nullptr, 0, h->P, s))) return rc;
-    h->p_valid = true;
-  }
-  if (h->cfg.embed_k % 2 == 0 && h->cfg.embed_d % 2 == 0)
-    return bprx_launch_score_gemm(h, u0, u1, out, s);          // fp32 MFMA GEMM (K step 2)
-  return bprx_launch_score_block(h, u0, u1, out, s);
+  return score_rows(h, u0, u1, out, s, {h->t.Gu, h->t.Tu});
 }
 
-// bprx_score_block for caller-owned user rows (users folded in by bprx_fold_in): the same kernels, their user tables pointed at
-// the caller's rows for the length of the launch.
+// bprx_score_block for caller-owned user rows (users folded in by bprx_fold_in): the same kernels, given the caller's rows.
 extern "C" int bprx_score_rows_block(bprx_handle *h, const float *Gu_rows, const float *Tu_rows, int64_t n_rows, int64_t r0, int64_t r1,
                                      float *out, void *stream) {
   if (!h) return BPRX_E_INVALID;
-  if (h->acf || h->af) BPRX_FAIL(h, BPRX_E_INVALID, "score_rows_block: needs a BPRMF or VBPR handle");
   if (n_rows < 0 || n_rows >= ((int64_t)1 << 31) || r0 < 0 || r1 > n_rows || r0 > r1)
     BPRX_FAIL(h, BPRX_E_INVALID, "score_rows_block: bad row range [%lld,%lld) of %lld", (long long)r0, (long long)r1, (long long)n_rows);
-  if (!h->bound) BPRX_FAIL(h, BPRX_E_STATE, "tables not bound (call bprx_bind_tables first)");
-  if (r0 == r1) return BPRX_OK;
-  if (!Gu_rows || !out || (h->cfg.embed_d > 0) != (Tu_rows != nullptr)) BPRX_FAIL(h, BPRX_E_INVALID, "score_rows_block: null pointer");
+  if (r0 != r1 && (!Gu_rows || !out || (h->cfg.embed_d > 0) != (Tu_rows != nullptr)))
+    BPRX_FAIL(h, BPRX_E_INVALID, "score_rows_block: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if ((rc = bprx_settle_pending(h, s))) return rc;
-  if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: every item row is read
-  if (h->cfg.model == BPRX_MODEL_VBPR && !h->p_valid) {
-    if ((rc = bprx_launch_cast_Et(h, s))) return rc;
-    if ((rc = bprx_launch_proj_fwd(h, nullptr, h->cfg.num_items, nullptr, 0, h->P, s))) return rc;
-    h->p_valid = true;
-  }
-  float *gu = h->t.Gu, *tu = h->t.Tu;
-  h->t.Gu = const_cast<float *>(Gu_rows); h->t.Tu = const_cast<float *>(Tu_rows);      // (read-only in both kernels)
-  rc = (h->cfg.embed_k % 2 == 0 && h->cfg.embed_d % 2 == 0) ? bprx_launch_score_gemm(h, (int32_t)r0, (int32_t)r1, out, s)
-                                                            : bprx_launch_score_block(h, (int32_t)r0, (int32_t)r1, out, s);
-  h->t.Gu = gu; h->t.Tu = tu;
-  return rc;
+  const int rc = bprx_enter(h, "score_rows_block", NEED_BOUND | NEED_ROWS | NEED_P_ALL, KIND_PLAIN, s);
+  if (rc || r0 == r1) return rc;
+  return score_rows(h, (int32_t)r0, (int32_t)r1, out, s, {Gu_rows, Tu_rows});
 }
 
 // ---- items outside the catalogue (include/bprx.h): bprx_project_rows here, bprx_score_new_block / bprx_topk_rows in
 // bprx_eval.hip, bprx_feat_explain_new in bprx_explain.hip ----
-int bprx_new_items_check(bprx_handle *h, const char *what, int64_t n) {
-  if (!h) return BPRX_E_INVALID;
-  if (h->cfg.model != BPRX_MODEL_VBPR || h->acf || h->af)
-    BPRX_FAIL(h, BPRX_E_INVALID, "%s: needs a VBPR handle (bprx_bind_tables or bprx_bind_factored)", what);
-  if (h->cfg.feat_dtype == BPRX_F_FP8)
-    BPRX_FAIL(h, BPRX_E_INVALID, "%s: fp8 features are not supported for new items (a new row may exceed the max-abs the codes "
-              "were scaled for and would saturate): fp32 or bf16", what);
-  if (n < 0 || n >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "%s: n = %lld out of range", what, (long long)n);
-  if (!h->bound) BPRX_FAIL(h, BPRX_E_STATE, "tables not bound (call bprx_bind_tables first)");
-  return BPRX_OK;
-}
-
 extern "C" int32_t bprx_proj_stride(const bprx_handle *h) {
   return h && h->cfg.model == BPRX_MODEL_VBPR ? h->PS : BPRX_E_INVALID;
 }
 
 extern "C" int bprx_project_rows(bprx_handle *h, const void *Fnew, int64_t n, float *P, void *stream) {
-  int rc = bprx_new_items_check(h, "project_rows", n);
-  if (rc) return rc;
-  if (n == 0) return BPRX_OK;
-  if (!Fnew || !P) BPRX_FAIL(h, BPRX_E_INVALID, "project_rows: null pointer");
+  if (!h) return BPRX_E_INVALID;
+  if (n < 0 || n >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "project_rows: n = %lld out of range", (long long)n);
+  if (n && (!Fnew || !P)) BPRX_FAIL(h, BPRX_E_INVALID, "project_rows: null pointer");
   if ((uintptr_t)Fnew & 15) BPRX_FAIL(h, BPRX_E_INVALID, "project_rows: the table must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = bprx_settle_pending(h, s))) return rc;
-  if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: as every call that reads the tables
-  if ((rc = bprx_launch_cast_Et(h, s))) return rc;
+  const int rc = bprx_enter(h, "project_rows", NEED_BOUND | NEED_ROWS | NEED_ET, KIND_VBPR_NO_FP8, s);
+  if (rc || n == 0) return rc;
   return bprx_launch_proj_new(h, Fnew, n, P, s);
 }
 
@@ -727,9 +691,8 @@ extern "C" int bprx_proj_mask_kind(const bprx_handle *h) {
 }
 
 extern "C" int bprx_sync_check(bprx_handle *h, void *stream) {
-  if (!h) return BPRX_E_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  { const int rc = bprx_settle_pending(h, s); if (rc) return rc; }
+  { const int rc = bprx_enter(h, "sync_check", 0, KIND_ANY, s); if (rc) return rc; }
   int32_t flag = 0;
   BPRX_HIP(h, hipMemcpyAsync(&flag, h->errflag, sizeof(flag), hipMemcpyDeviceToHost, s));
   BPRX_HIP(h, hipStreamSynchronize(s));

@@ -410,11 +410,11 @@ __global__ __launch_bounds__(256) void k_topk(float *__restrict__ S, int u0, int
 extern "C" int bprx_topk(bprx_handle *h, int32_t u0, int32_t u1, float *scores, const int64_t *train_ptr,
                          const int32_t *train_items, int32_t K, int32_t *idx, float *val, int32_t *flag, void *stream) {
   if (!h) return BPRX_E_INVALID;
-  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (u0 < 0 || u1 > h->cfg.num_users || u0 > u1 || !scores || !train_ptr || !train_items || !idx || !val || !flag)
     BPRX_FAIL(h, BPRX_E_INVALID, "topk: bad argument");
   if (K <= 0 || K > TOPK_MAX) BPRX_FAIL(h, BPRX_E_INVALID, "topk: K=%d outside [1, %d]", K, TOPK_MAX);
-  if (u0 == u1) return BPRX_OK;
+  const int rc = bprx_enter(h, "topk", 0, KIND_ANY, (hipStream_t)stream);
+  if (rc || u0 == u1) return rc;
   hipLaunchKernelGGL(k_topk, dim3(u1 - u0), dim3(256), 0, (hipStream_t)stream, scores, u0, h->cfg.num_items, train_ptr,
                      train_items, K, idx, val, flag);
   BPRX_LAUNCH_CHECK(h, "k_topk");
@@ -423,13 +423,13 @@ extern "C" int bprx_topk(bprx_handle *h, int32_t u0, int32_t u1, float *scores, 
 
 extern "C" int bprx_topk_rows(bprx_handle *h, int64_t nrows, int32_t width, float *scores, int32_t K, int32_t *idx, float *val,
                               int32_t *flag, void *stream) {
-  const int rc = bprx_new_items_check(h, "topk_rows", nrows);
-  if (rc) return rc;
-  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
+  if (!h) return BPRX_E_INVALID;
+  if (nrows < 0 || nrows >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows: n = %lld out of range", (long long)nrows);
   if (width < 1) BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows: width = %d < 1", width);
   if (K <= 0 || K > TOPK_MAX) BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows: K=%d outside [1, %d]", K, TOPK_MAX);
-  if (nrows == 0) return BPRX_OK;
-  if (!scores || !idx || !val || !flag) BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows: null pointer");
+  if (nrows && (!scores || !idx || !val || !flag)) BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows: null pointer");
+  const int rc = bprx_enter(h, "topk_rows", NEED_BOUND, KIND_VBPR_NO_FP8, (hipStream_t)stream);
+  if (rc || nrows == 0) return rc;
   hipLaunchKernelGGL(k_topk, dim3((unsigned)nrows), dim3(256), 0, (hipStream_t)stream, scores, 0, width, (const int64_t *)nullptr,
                      (const int32_t *)nullptr, K, idx, val, flag);
   BPRX_LAUNCH_CHECK(h, "k_topk<rows>");
@@ -440,11 +440,11 @@ extern "C" int bprx_topk_rows(bprx_handle *h, int64_t nrows, int32_t width, floa
 extern "C" int bprx_topk_lists(bprx_handle *h, int64_t nrows, float *scores, const int64_t *list_ptr, const int32_t *list_items,
                                int32_t K, int32_t *idx, float *val, int32_t *flag, void *stream) {
   if (!h) return BPRX_E_INVALID;
-  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (nrows < 0 || nrows >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "topk_lists: nrows = %lld out of range", (long long)nrows);
   if (K <= 0 || K > TOPK_MAX) BPRX_FAIL(h, BPRX_E_INVALID, "topk_lists: K=%d outside [1, %d]", K, TOPK_MAX);
-  if (nrows == 0) return BPRX_OK;
-  if (!scores || !list_ptr || !list_items || !idx || !val || !flag) BPRX_FAIL(h, BPRX_E_INVALID, "topk_lists: null pointer");
+  if (nrows && (!scores || !list_ptr || !list_items || !idx || !val || !flag)) BPRX_FAIL(h, BPRX_E_INVALID, "topk_lists: null pointer");
+  const int rc = bprx_enter(h, "topk_lists", 0, KIND_ANY, (hipStream_t)stream);
+  if (rc || nrows == 0) return rc;
   hipLaunchKernelGGL(k_topk, dim3((unsigned)nrows), dim3(256), 0, (hipStream_t)stream, scores, 0, h->cfg.num_items, list_ptr,
                      list_items, K, idx, val, flag);
   BPRX_LAUNCH_CHECK(h, "k_topk<lists>");
@@ -452,15 +452,15 @@ extern "C" int bprx_topk_lists(bprx_handle *h, int64_t nrows, float *scores, con
 }
 
 extern "C" int bprx_score_new_block(bprx_handle *h, int32_t u0, int32_t u1, const float *P, int64_t n, float *out, void *stream) {
-  int rc = bprx_new_items_check(h, "score_new_block", n);
-  if (rc) return rc;
-  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
+  if (!h) return BPRX_E_INVALID;
+  if (n < 0 || n >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "score_new_block: n = %lld out of range", (long long)n);
   if (u0 < 0 || u1 > h->cfg.num_users || u0 > u1) BPRX_FAIL(h, BPRX_E_INVALID, "score_new_block: bad user range [%d,%d)", u0, u1);
-  if (n == 0 || u0 == u1) return BPRX_OK;
-  if (!P || !out) BPRX_FAIL(h, BPRX_E_INVALID, "score_new_block: null pointer");
+  const bool empty = n == 0 || u0 == u1;
+  if (!empty && (!P || !out)) BPRX_FAIL(h, BPRX_E_INVALID, "score_new_block: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: the Tu rows must be current
-  if ((rc = bprx_launch_cast_Et(h, s))) return rc;                       // (the image P was made from stays the current one)
+  // (NEED_ET: the image P was made from stays the current one)
+  const int rc = bprx_enter(h, "score_new_block", NEED_BOUND | NEED_ROWS | NEED_ET, KIND_VBPR_NO_FP8, s);
+  if (rc || empty) return rc;
   dim3 grid((unsigned)((n + TN - 1) / TN), (unsigned)((u1 - u0 + TM - 1) / TM));
   hipLaunchKernelGGL(k_score_new_gemm, grid, dim3(256), 0, s, (const float *)h->t.Tu, P, (int)n, h->cfg.embed_d, h->PS, u0, u1, out);
   BPRX_LAUNCH_CHECK(h, "k_score_new_gemm");
@@ -468,9 +468,9 @@ extern "C" int bprx_score_new_block(bprx_handle *h, int32_t u0, int32_t u1, cons
 }
 
 // used by bprx_score_block when the factor widths allow the MFMA path (K step of 2)
-int bprx_launch_score_gemm(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s) {
+int bprx_launch_score_gemm(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s, UserRows rows) {
   GemmArgs g;
-  g.Gu = h->t.Gu; g.Gi = h->t.Gi; g.Bi = h->t.Bi; g.Tu = h->t.Tu; g.P = h->P;
+  g.Gu = rows.Gu; g.Gi = h->t.Gi; g.Bi = h->t.Bi; g.Tu = rows.Tu; g.P = h->P;
   g.U = h->cfg.num_users; g.I = h->cfg.num_items; g.k = h->cfg.embed_k; g.d = h->cfg.embed_d; g.PS = h->PS;
   dim3 grid((g.I + TN - 1) / TN, (u1 - u0 + TM - 1) / TM);
   hipLaunchKernelGGL(k_score_gemm, grid, dim3(256), 0, s, g, u0, u1, out);
@@ -482,11 +482,11 @@ extern "C" int bprx_eval_users(bprx_handle *h, int32_t u0, int32_t u1, const flo
                                const int32_t *train_items, const int64_t *eval_ptr, const int32_t *eval_items, int32_t K,
                                double *out, void *stream) {
   if (!h) return BPRX_E_INVALID;
-  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (u0 < 0 || u1 > h->cfg.num_users || u0 > u1 || !scores || !train_ptr || !train_items || !eval_ptr || !eval_items ||
       !out || K <= 0)
     BPRX_FAIL(h, BPRX_E_INVALID, "eval_users: bad argument");
-  if (u0 == u1) return BPRX_OK;
+  const int rc = bprx_enter(h, "eval_users", 0, KIND_ANY, (hipStream_t)stream);
+  if (rc || u0 == u1) return rc;
   hipLaunchKernelGGL(k_eval_users, dim3(u1 - u0), dim3(256), 0, (hipStream_t)stream, scores, u0, h->cfg.num_items, train_ptr,
                      train_items, eval_ptr, eval_items, K, out, h->errflag);
   BPRX_LAUNCH_CHECK(h, "k_eval_users");
@@ -497,10 +497,10 @@ extern "C" int bprx_eval_users(bprx_handle *h, int32_t u0, int32_t u1, const flo
 extern "C" int bprx_eval_pos(bprx_handle *h, int32_t u0, int32_t u1, const float *scores, int32_t item_lo, int32_t items_total,
                              const int64_t *eval_ptr, const int32_t *eval_items, float *sp, void *stream) {
   if (!h) return BPRX_E_INVALID;
-  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (u0 < 0 || u0 > u1 || !scores || !eval_ptr || !eval_items || !sp || item_lo < 0 || items_total <= 0)
     BPRX_FAIL(h, BPRX_E_INVALID, "eval_pos: bad argument");
-  if (u0 == u1) return BPRX_OK;
+  const int rc = bprx_enter(h, "eval_pos", 0, KIND_ANY, (hipStream_t)stream);
+  if (rc || u0 == u1) return rc;
   const int nb = u1 - u0;
   hipLaunchKernelGGL(k_eval_pos, dim3((unsigned)(((int64_t)nb * EVMAX + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, u0,
                      nb, h->cfg.num_items, item_lo, items_total, eval_ptr, eval_items, sp, h->errflag);
@@ -512,10 +512,10 @@ extern "C" int bprx_eval_counts(bprx_handle *h, int32_t u0, int32_t u1, const fl
                                 const int64_t *train_ptr, const int32_t *train_items, const int64_t *eval_ptr,
                                 const int32_t *eval_items, const float *sp, int32_t *counts, void *stream) {
   if (!h) return BPRX_E_INVALID;
-  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (u0 < 0 || u0 > u1 || !scores || !train_ptr || !train_items || !eval_ptr || !eval_items || !sp || !counts || item_lo < 0)
     BPRX_FAIL(h, BPRX_E_INVALID, "eval_counts: bad argument");
-  if (u0 == u1) return BPRX_OK;
+  const int rc = bprx_enter(h, "eval_counts", 0, KIND_ANY, (hipStream_t)stream);
+  if (rc || u0 == u1) return rc;
   hipLaunchKernelGGL(k_eval_counts, dim3(u1 - u0), dim3(256), 0, (hipStream_t)stream, scores, u0, h->cfg.num_items, item_lo,
                      items_total, train_ptr, train_items, eval_ptr, eval_items, sp, counts);
   BPRX_LAUNCH_CHECK(h, "k_eval_counts");
@@ -525,10 +525,10 @@ extern "C" int bprx_eval_counts(bprx_handle *h, int32_t u0, int32_t u1, const fl
 extern "C" int bprx_eval_finish(bprx_handle *h, int32_t u0, int32_t u1, int32_t items_total, const int64_t *eval_ptr,
                                 const float *sp, const int32_t *counts, int32_t K, double *out, void *stream) {
   if (!h) return BPRX_E_INVALID;
-  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (u0 < 0 || u0 > u1 || !eval_ptr || !sp || !counts || !out || K <= 0 || items_total <= 0)
     BPRX_FAIL(h, BPRX_E_INVALID, "eval_finish: bad argument");
-  if (u0 == u1) return BPRX_OK;
+  const int rc = bprx_enter(h, "eval_finish", 0, KIND_ANY, (hipStream_t)stream);
+  if (rc || u0 == u1) return rc;
   const int nb = u1 - u0;
   hipLaunchKernelGGL(k_eval_finish, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, (hipStream_t)stream, u0, nb, items_total,
                      eval_ptr, sp, counts, K, out);

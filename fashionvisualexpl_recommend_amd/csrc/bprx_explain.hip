@@ -253,21 +253,17 @@ extern "C" int bprx_feat_explain(bprx_handle *h, const void *F, const int32_t *u
                                  int32_t top, float *score, float *base, float *visual, int32_t *col, float *contrib, float *map,
                                  void *stream) {
   if (!h) return BPRX_E_INVALID;
-  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
-  if (!h->bound) BPRX_FAIL(h, BPRX_E_STATE, "tables not bound (call bprx_bind_tables first)");
-  if (h->cfg.model != BPRX_MODEL_VBPR || h->acf || h->af)
-    BPRX_FAIL(h, BPRX_E_STATE, "feat_explain: needs a VBPR handle (bprx_bind_tables or bprx_bind_factored)");
   const bprx_config &c = h->cfg;
   if (n < 0 || n >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain: n = %lld out of range", (long long)n);
   if (ncols < 1 || ncols > c.feat_dim) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain: ncols = %d outside [1, feat_dim = %d]", ncols, c.feat_dim);
   if (top < 1 || top > 32) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain: top = %d outside [1, 32]", top);
   if (c.feat_dim > 16384)
     BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain: feat_dim = %d > 16384 (one user's fp32 w row must fit in 64 KB of LDS)", c.feat_dim);
-  if (n == 0) return BPRX_OK;
-  if (!F || !user || !item || !score || !base || !visual || !col || !contrib) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain: null pointer");
+  if (n && (!F || !user || !item || !score || !base || !visual || !col || !contrib))
+    BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  const int rc = bprx_launch_adam_sync(h, h->adam_t, s);               // lazy adam: the rows must be current
-  if (rc) return rc;
+  const int rc = bprx_enter(h, "feat_explain", NEED_BOUND | NEED_ROWS, KIND_VBPR, s);
+  if (rc || n == 0) return rc;
   FeatExplainArgs A;
   A.Gu = h->t.Gu; A.Gi = h->t.Gi; A.Bi = h->t.Bi; A.Tu = h->t.Tu; A.E = h->t.E; A.Bp = h->t.Bp;
   A.F = F; A.user = user; A.item = item; A.n = n;
@@ -291,21 +287,20 @@ extern "C" int bprx_feat_explain(bprx_handle *h, const void *F, const int32_t *u
 extern "C" int bprx_feat_explain_new(bprx_handle *h, const void *Fnew, int64_t n_new, const int32_t *user, const int32_t *row,
                                      int64_t n, int32_t ncols, int32_t top, float *score, int32_t *col, float *contrib, float *map,
                                      void *stream) {
-  int rc = bprx_new_items_check(h, "feat_explain_new", n);
-  if (rc) return rc;
-  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
+  if (!h) return BPRX_E_INVALID;
   const bprx_config &c = h->cfg;
+  if (n < 0 || n >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: n = %lld out of range", (long long)n);
   if (n_new < 0 || n_new >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: n_new = %lld out of range", (long long)n_new);
   if (ncols < 1 || ncols > c.feat_dim) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: ncols = %d outside [1, feat_dim = %d]", ncols, c.feat_dim);
   if (top < 1 || top > 32) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: top = %d outside [1, 32]", top);
   if (c.feat_dim > 16384)
     BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: feat_dim = %d > 16384 (one user's fp32 w row must fit in 64 KB of LDS)", c.feat_dim);
-  if (n == 0) return BPRX_OK;
-  if (n_new == 0) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: %lld pairs of an empty table", (long long)n);
-  if (!Fnew || !user || !row || !score || !col || !contrib) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: null pointer");
+  if (n && n_new == 0) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: %lld pairs of an empty table", (long long)n);
+  if (n && (!Fnew || !user || !row || !score || !col || !contrib)) BPRX_FAIL(h, BPRX_E_INVALID, "feat_explain_new: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: the rows must be current
-  if ((rc = bprx_launch_cast_Et(h, s))) return rc;                       // (not read here: the image bprx_project_rows scores with)
+  // (NEED_ET: not read here, it is the image bprx_project_rows scores with)
+  const int rc = bprx_enter(h, "feat_explain_new", NEED_BOUND | NEED_ROWS | NEED_ET, KIND_VBPR_NO_FP8, s);
+  if (rc || n == 0) return rc;
   FeatExplainArgs A;
   A.Gu = nullptr; A.Gi = nullptr; A.Bi = nullptr; A.Tu = h->t.Tu; A.E = h->t.E; A.Bp = h->t.Bp;
   A.F = Fnew; A.user = user; A.item = row; A.n = n;

@@ -226,24 +226,16 @@ extern "C" int bprx_fold_in(bprx_handle *h, const int64_t *pair_ptr, const int32
                             void *stream) {
   if (!h) return BPRX_E_INVALID;
   const bprx_config &c = h->cfg;
-  if (h->acf || h->af) BPRX_FAIL(h, BPRX_E_INVALID, "fold_in: needs a BPRMF or VBPR handle (ACF and AttentiveFashion build the user side from attention)");
   if (n < 0 || n >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "fold_in: n = %lld out of range", (long long)n);
   if (steps < 1) BPRX_FAIL(h, BPRX_E_INVALID, "fold_in: steps = %d < 1", steps);
   if (optimizer != BPRX_OPT_SGD && optimizer != BPRX_OPT_ADAM_TF23) BPRX_FAIL(h, BPRX_E_INVALID, "fold_in: optimizer %d", optimizer);
   if (c.embed_k + c.embed_d > 1024) BPRX_FAIL(h, BPRX_E_INVALID, "fold_in: k + d = %d > 1024", c.embed_k + c.embed_d);
   if (!pair_ptr || !Gu_rows || (c.embed_d > 0) != (Tu_rows != nullptr)) BPRX_FAIL(h, BPRX_E_INVALID, "fold_in: null pointer");
-  if (!h->bound) BPRX_FAIL(h, BPRX_E_STATE, "tables not bound (call bprx_bind_tables first)");
-  if (n == 0) return BPRX_OK;
-  if (!pos || !neg) BPRX_FAIL(h, BPRX_E_INVALID, "fold_in: null pointer");
+  if (n && (!pos || !neg)) BPRX_FAIL(h, BPRX_E_INVALID, "fold_in: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if ((rc = bprx_settle_pending(h, s))) return rc;
-  if ((rc = bprx_launch_adam_sync(h, h->adam_t, s))) return rc;          // lazy adam: the item rows must be current
-  if (c.model == BPRX_MODEL_VBPR && !h->p_valid) {                        // P = F.[E|Bp], as bprx_score_block makes it current
-    if ((rc = bprx_launch_cast_Et(h, s))) return rc;
-    if ((rc = bprx_launch_proj_fwd(h, nullptr, c.num_items, nullptr, 0, h->P, s))) return rc;
-    h->p_valid = true;
-  }
+  // (ACF and AttentiveFashion build the user side from attention: plain handles only)
+  const int rc = bprx_enter(h, "fold_in", NEED_BOUND | NEED_ROWS | NEED_P_ALL, KIND_PLAIN, s);
+  if (rc || n == 0) return rc;
   FoldArgs a;
   a.Gi = h->t.Gi; a.Bi = h->t.Bi; a.P = c.embed_d ? h->P : nullptr;
   a.I = c.num_items; a.k = c.embed_k; a.d = c.embed_d; a.PS = h->PS;

@@ -328,8 +328,7 @@ int bprx_launch_dense_update(bprx_handle *h, const StepPlan &p, hipStream_t s);
 DenseArgs bprx_dense_args(bprx_handle *h, const StepPlan &p);               // what that launch is given (also sets dense_blocks)
 int bprx_launch_dense_args(bprx_handle *h, const DenseArgs &a, hipStream_t s);
 // Runs a pending dense update (and its lagging loss) with the stand-alone kernel on `s`; returns at once when nothing is pending
-// or h is null.  Every entry that takes a handle calls it first, except bprx_step (which may carry the update instead), the
-// samplers, the profile calls, bprx_last_error, bprx_set_hyper / bprx_set_loss_lag and the pure getters.  (bprx_api.hip)
+// or h is null.  Called by bprx_enter, the step path and bprx_settle only (bprx_api.hip).
 int bprx_settle_pending(bprx_handle *h, hipStream_t s);
 // One adam_tf23 step (sparse rule, adam_elem) of up to four whole tables from their staging gradients, which return to zero,
 // and the clearing of up to two claim-mark arrays, in ONE launch of k_adam_sweep: the sweep of every model and of
@@ -343,8 +342,10 @@ int bprx_launch_adam_sync(bprx_handle *h, int64_t t, hipStream_t s);
 int bprx_launch_adam_reset(bprx_handle *h, int64_t t, hipStream_t s);
 int bprx_launch_loss_reduce(bprx_handle *h, int64_t B, float *loss_out, hipStream_t s);
 int bprx_launch_loss_reduce_at(bprx_handle *h, int64_t B, int nsq, float reg, float *loss_out, hipStream_t s);   // a lagging loss
-int bprx_launch_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s);
-int bprx_launch_score_gemm(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s);
+// the user side of a block score: rows [u0, u1) of these tables (the handle's own Gu / Tu, or a caller's)
+struct UserRows { const float *Gu, *Tu; };
+int bprx_launch_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s, UserRows rows);
+int bprx_launch_score_gemm(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s, UserRows rows);
 // projection part (bprx_proj.hip)
 int bprx_launch_tile_F(bprx_handle *h);
 int bprx_launch_cast_Et(bprx_handle *h, hipStream_t s);
@@ -359,8 +360,6 @@ int bprx_launch_proj_bwd(bprx_handle *h, const StepPlan &p, hipStream_t s);
 // P = Fnew.[E|Bp] for the n rows of a caller's ROW-MAJOR table (bprx_project_rows): bf16 features from the image Et in one pass
 // over the table (k_proj_new_bf16), fp32 features with the kernels of the catalogue
 int bprx_launch_proj_new(bprx_handle *h, const void *Fnew, int64_t n, float *P, hipStream_t s);
-// what the new-item entry points share (bprx_api.hip): 0, or the error of a handle / row count they do not take
-int bprx_new_items_check(bprx_handle *h, const char *what, int64_t n);
 // whether the kernel form the whole-table forward / backward projection takes for this handle's shape has a masked variant
 // (bprx_proj.hip, next to the form tables): what the launchers do with `occ`, and what bprx_proj_mask_kind reports
 bool bprx_proj_fwd_takes_mask(const bprx_handle &h);
@@ -511,3 +510,42 @@ inline StepPlan plan_step(const bprx_handle &h, const int32_t *user, const int32
   }
   return p;
 }
+
+// ---- how a read is planned ----
+// What an entry point needs from the handle before it may read the bound tables, and the handles it takes.
+enum : unsigned {
+  NEED_BOUND = 1,                 // tables are bound
+  NEED_ROWS = 2,                  // lazy Adam: every row is current at adam_t
+  NEED_ET = 4,                    // VBPR: the [E|Bp]^T image matches E / Bp
+  NEED_P_ALL = 8,                 // VBPR: P holds the projection of every item (makes the image current on the way)
+};
+constexpr const char *BPRX_NOT_BOUND = "%s: tables not bound (call bprx_bind_tables first)";   // (also the step path's message)
+enum { KIND_ANY = 0, KIND_PLAIN, KIND_VBPR, KIND_VBPR_NO_FP8, KIND_FACTORED };   // PLAIN: BPRMF / VBPR, not ACF / AttentiveFashion
+struct ReadPlan {
+  int error;                      // 0, or BPRX_E_STATE (not bound) / BPRX_E_INVALID (a handle of the wrong kind): nothing is launched
+  const char *why;                // ... and its message, a format with one %s for the name of the entry
+  bool settle, sync, cast_et;     // in launch order: bprx_settle_pending, bprx_launch_adam_sync to adam_t, bprx_launch_cast_Et,
+  bool project;                   //    the forward projection of all items, after which p_valid = true
+};
+// The one place that decides what a call does to the carried state before its own launches; bprx_enter (bprx_api.hip) runs it.
+// Pure, like plan_step.  ACF / AttentiveFashion handles are BPRMF handles without lazy Adam: beyond settle nothing applies to them.
+inline ReadPlan plan_read(const bprx_handle &h, unsigned need, int kind) {
+  ReadPlan p = {};
+  const bool vb = h.cfg.model == BPRX_MODEL_VBPR, plain = !h.acf && !h.af;
+  auto fail = [&p](int code, const char *why) { p.error = code; p.why = why; return p; };
+  if ((need & NEED_BOUND) && !h.bound) return fail(BPRX_E_STATE, BPRX_NOT_BOUND);
+  if (kind == KIND_PLAIN && !plain) return fail(BPRX_E_INVALID, "%s: needs a BPRMF or VBPR handle, not ACF or AttentiveFashion");
+  if ((kind == KIND_VBPR || kind == KIND_VBPR_NO_FP8) && !(vb && plain))
+    return fail(BPRX_E_INVALID, "%s: needs a VBPR handle (bprx_bind_tables or bprx_bind_factored)");
+  if (kind == KIND_VBPR_NO_FP8 && h.cfg.feat_dtype == BPRX_F_FP8)
+    return fail(BPRX_E_INVALID, "%s: fp8 features are not supported for new items (a new row may exceed the max-abs the codes "
+                                "were scaled for and would saturate): fp32 or bf16");
+  if (kind == KIND_FACTORED && !h.factored) return fail(BPRX_E_INVALID, "%s: the handle is not bound with bprx_bind_factored");
+  p.settle = h.pend.on;
+  p.sync = (need & NEED_ROWS) && plain && h.adam_lazy && h.adam_synced < h.adam_t;
+  p.project = (need & NEED_P_ALL) && plain && vb && !h.p_valid;
+  p.cast_et = plain && vb && ((need & NEED_ET) || p.project);     // (the launcher returns at once when the image is current)
+  return p;
+}
+// The executor of that plan and the gate of every entry point that takes a handle (bprx_api.hip).
+int bprx_enter(bprx_handle *h, const char *what, unsigned need, int kind, hipStream_t s);

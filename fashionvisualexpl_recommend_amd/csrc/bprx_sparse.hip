@@ -2017,10 +2017,10 @@ extern "C" int64_t bprx_user_msg_floats(const bprx_handle *h, int64_t cap) {
 
 extern "C" int bprx_pack_user_msg(bprx_handle *h, const int32_t *user, int64_t B, int64_t cap, float *msg, void *stream) {
   if (!h || !msg || B < 0 || cap <= 0 || (B > 0 && !user)) return BPRX_E_INVALID;
-  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
   if (!(h->cfg.flags & BPRX_FLAG_EXPORT_USER_GRAD)) BPRX_FAIL(h, BPRX_E_STATE, "pack_user_msg needs BPRX_FLAG_EXPORT_USER_GRAD");
   if (!h->step_stage) BPRX_FAIL(h, BPRX_E_STATE, "pack_user_msg outside a step (after bprx_step_begin[_sparse])");
   if (B != h->step.B) BPRX_FAIL(h, BPRX_E_INVALID, "pack_user_msg: B differs from the pending step's");
+  { const int rc = bprx_enter(h, "pack_user_msg", 0, KIND_ANY, (hipStream_t)stream); if (rc) return rc; }
   hipStream_t s = (hipStream_t)stream;
   const int k = h->cfg.embed_k, d = h->cfg.embed_d;
   const dim3 grid((unsigned)((B + 255) / 256));
@@ -2042,10 +2042,9 @@ extern "C" int bprx_pack_user_msg(bprx_handle *h, const int32_t *user, int64_t B
 
 extern "C" int bprx_apply_user_msgs(bprx_handle *h, const float *msgs, int32_t nranks, int64_t cap, float scale, void *stream) {
   if (!h || !msgs || nranks <= 0 || cap <= 0) return BPRX_E_INVALID;
-  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
-  if (!h->bound) BPRX_FAIL(h, BPRX_E_STATE, "tables not bound");
   if (!(h->cfg.flags & BPRX_FLAG_EXPORT_USER_GRAD)) BPRX_FAIL(h, BPRX_E_STATE, "apply_user_msgs needs BPRX_FLAG_EXPORT_USER_GRAD");
   if ((int64_t)nranks * cap >= ((int64_t)1 << 31) - 1) BPRX_FAIL(h, BPRX_E_INVALID, "nranks * cap too large");
+  { const int rc = bprx_enter(h, "apply_user_msgs", NEED_BOUND, KIND_ANY, (hipStream_t)stream); if (rc) return rc; }
   hipStream_t s = (hipStream_t)stream;
   const int k = h->cfg.embed_k, d = h->cfg.embed_d;
   const size_t stride = (size_t)bprx_user_msg_floats(h, cap);
@@ -2088,9 +2087,8 @@ extern "C" int bprx_apply_user_msgs(bprx_handle *h, const float *msgs, int32_t n
 // (an all-gather of bprx_dense_grad()), for handles created with BPRX_FLAG_DENSE_ALLREDUCE that prefer the ordered sum to
 // an RCCL all-reduce
 extern "C" int bprx_sum_dense_parts(bprx_handle *h, const float *parts, int32_t nranks, void *stream) {
-  if (!h || !parts || nranks <= 0) return BPRX_E_INVALID;
-  { const int rc_ = bprx_settle_pending(h, (hipStream_t)stream); if (rc_) return rc_; }   // a deferred dense update first
-  if (h->cfg.model != BPRX_MODEL_VBPR) BPRX_FAIL(h, BPRX_E_STATE, "sum_dense_parts: VBPR only");
+  if (!parts || nranks <= 0) return BPRX_E_INVALID;
+  { const int rc = bprx_enter(h, "sum_dense_parts", 0, KIND_VBPR, (hipStream_t)stream); if (rc) return rc; }
   const size_t nd = (size_t)h->cfg.feat_dim * (h->cfg.embed_d + 1);
   unsigned blocks = (unsigned)((nd + 255) / 256);
   if (blocks > 2048) blocks = 2048;
@@ -2375,8 +2373,9 @@ int bprx_launch_loss_reduce(bprx_handle *h, int64_t B, float *loss_out, hipStrea
   return bprx_launch_loss_reduce_at(h, B, h->cfg.model == BPRX_MODEL_VBPR ? h->dense_blocks : 0, h->cfg.reg, loss_out, s);
 }
 
-int bprx_launch_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s) {
+int bprx_launch_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s, UserRows rows) {
   SparseArgs a = make_args(h, h->P, h->step);
+  a.Gu = rows.Gu; a.Tu = rows.Tu;
   dim3 grid((a.I + 63) / 64, (u1 - u0 + 3) / 4);
   hipLaunchKernelGGL(k_score_block, grid, dim3(256), 0, s, a, u0, u1, out);
   BPRX_LAUNCH_CHECK(h, "k_score_block");

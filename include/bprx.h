@@ -142,7 +142,27 @@ BPRX_API int bprx_sync_adam(bprx_handle *h, void *stream);
    bprx_set_loss_lag(h, 1) lets a step WITH a loss pointer defer too: its loss is then written behind the launch that runs its
    update (the next step, or a settling call), so the pointer must stay valid until then; the value has the same bits.  Before the
    buffer goes: bprx_settle, then bprx_set_loss_lag(h, 0) -- on every way out of the loop that set it.
-   BPRX_DENSE_DEFER=0 (read by bprx_create): never defer.  The split-phase calls never defer. */
+   BPRX_DENSE_DEFER=0 (read by bprx_create): never defer.  The split-phase calls never defer.
+   Every entry checks its arguments, then passes one gate that brings the handle to the state the entry reads (pending update,
+   lazy-Adam rows, the [E|Bp]^T image, P), then returns if there is no work.  So a call rejected for its arguments (or for the
+   handle, BPRX_E_STATE not bound / BPRX_E_INVALID a handle of the wrong kind) launches nothing and leaves an update pending; a
+   valid call with no work (B == 0, n == 0, u0 == u1) settles like any other.
+     entries                                                          handle              tables bound  rows  image  P of all items
+     bprx_score_block                                                 any                 yes           yes   via P  yes (VBPR)
+     bprx_score_rows_block, bprx_fold_in                              BPRMF / VBPR        yes           yes   via P  yes
+     bprx_step_project                                                any                 yes           -     yes    yes
+     bprx_score_pairs                                                 any                 yes           yes   unless P is current  -
+     bprx_project_rows, bprx_score_new_block, bprx_feat_explain_new   VBPR, not fp8       yes           yes   yes    -
+     bprx_feat_explain                                                VBPR                yes           yes   -      -
+     bprx_explain_pairs                                               GradFashion         yes           yes   -      -
+     bprx_sync_adam                                                   any                 yes           yes   -      -
+     bprx_topk_rows                                                   VBPR, not fp8       yes           -     -      -
+     bprx_apply_user_msgs                                             any                 yes           -     -      -
+     bprx_sum_dense_parts                                             VBPR                -             -     -      -
+     bprx_topk, bprx_topk_lists, bprx_eval_*, bprx_tables_dirty, bprx_set_adam_step, bprx_clear_*_grad, bprx_sync_check,
+     bprx_pack_user_msg, the bind calls                               any                 -             -     -      -
+   Not behind the gate: bprx_step and bprx_step_begin[_sparse] (a step may carry the update), the samplers, the profile calls, bprx_last_error, bprx_set_hyper,
+   bprx_set_loss_lag, the getters, bprx_settle and bprx_dense_pending. */
 BPRX_API int bprx_settle(bprx_handle *h, void *stream);
 BPRX_API int bprx_dense_pending(const bprx_handle *h);
 BPRX_API int bprx_set_loss_lag(bprx_handle *h, int on);
@@ -188,9 +208,9 @@ BPRX_API int bprx_explain_pairs(bprx_handle *h, const int32_t *user, const int32
    F: device pointer to the caller's ROW-MAJOR [num_items, feat_dim] table in the handle's feat_dtype (fp32, bf16, or e4m3fn codes
    of f * feat_scale); it is passed here because bprx_bind_tables allows a bf16 / fp8 F to be released once the tiled copy is
    made -- this call never reads the tiled copy.  Only columns [0, ncols) exist for the explanation (1 <= ncols <= feat_dim: the
-   rest is the models' zero padding); 1 <= top <= 32; 0 <= n < 2^31, not bounded by max_batch (n == 0: BPRX_OK, nothing is
-   touched); feat_dim <= 16384 (one user's fp32 w row lives in LDS).  BPRX_E_INVALID otherwise and for a NULL pointer other than
-   map; BPRX_E_STATE on a BPRMF, ACF or AttentiveFashion handle.  After any error the handle stays usable.
+   rest is the models' zero padding); 1 <= top <= 32; 0 <= n < 2^31, not bounded by max_batch (n == 0: BPRX_OK, no output
+   is written); feat_dim <= 16384 (one user's fp32 w row lives in LDS).  BPRX_E_INVALID otherwise and for a NULL pointer other than
+   map, and on a BPRMF, ACF or AttentiveFashion handle; BPRX_E_STATE on an unbound one.  After any error the handle stays usable.
    Outputs (device): score, base, visual fp32 [n]; col int32 [n, top] and contrib fp32 [n, top]: the `top` columns with the
    largest F_ic w_uc, rank 0 first, non-increasing; values compare as floats (+0.0 == -0.0, as in bprx_topk) and equal values come
    in ascending column order; slots r >= ncols hold col = -1, contrib = 0.  map fp32 [n, ncols] (row stride ncols; NULL: not
@@ -216,7 +236,7 @@ BPRX_API int bprx_feat_explain(bprx_handle *h, const void *F, const int32_t *use
    device table Fnew [n, feat_dim] of the handle's feat_dtype, normalised by the caller as the training table was.
    Handles: a bound VBPR handle, plain or factored, with fp32 or bf16 features.  BPRX_E_INVALID for a NULL handle, a BPRMF, ACF or
    AttentiveFashion handle, an fp8 handle (a new row may exceed the max-abs the codes were scaled for and would saturate), a NULL
-   pointer, n < 0, n >= 2^31; BPRX_E_STATE for an unbound handle; n == 0 / u0 == u1: BPRX_OK, nothing is touched.  After any error
+   pointer, n < 0, n >= 2^31; BPRX_E_STATE for an unbound handle; n == 0 / u0 == u1: BPRX_OK, no output is written.  After any error
    the handle stays usable.
    State: bprx_project_rows, bprx_score_new_block and bprx_feat_explain_new bring lazy adam_tf23 rows up to date first (they read
    Tu, E, Bp) and make the bf16 image of [E|Bp]^T current where the step has not left it so (the image every projection of the

@@ -189,7 +189,38 @@ def _mid_calls():
         e.step_begin(*_batch(901))
         e.step_end(want_loss=False)
 
+    # the entries behind the read gate that the Engine exposes: inputs that are the same for both engines
+    g = torch.Generator().manual_seed(78)
+    rnd = lambda *shape: torch.rand(shape, generator=g).cuda()
+    rows = lm._dev(np.arange(64, dtype=np.int32) * 3 % 40)
+    Pnew, Snew, Gu8, Tu8, S8 = rnd(40, 32), rnd(8, 40), rnd(8, K) - 0.5, rnd(8, 20) - 0.5, rnd(8, I)
+    lists = _lists()
+    from fashionvisualexpl_recommend_amd.models import draw_fold_pairs
+    fold = draw_fold_pairs(lists[:8], I, 3, seed=1)
+
+    def fold_in(e):
+        Gu, Tu = torch.zeros((8, K), device="cuda"), torch.zeros((8, 20), device="cuda")
+        return e.fold_in(*fold, 4, Gu, Tu, lr=0.05, reg=1e-3), Gu, Tu
+
+    gated = {
+        "feat_explain": lambda e: e.feat_explain(*pairs, 5, 256, maps=True),
+        "feat_explain_new": lambda e: e.feat_explain_new(Fnew, pairs[0], rows, 5, 256),
+        "score_new_block": lambda e: e.score_new_block(3, 50, Pnew),
+        "score_rows_block": lambda e: e.score_rows_block(Gu8, Tu8, 0, 8),
+        "fold_in": fold_in,
+        "topk_rows": lambda e: e.topk_rows(Snew, 5),
+        "topk_lists": lambda e: e.topk_lists(S8.clone(), e.csr(lists[:8]), 5),
+        "eval_users": lambda e: e.eval_users(0, 8, S8.clone(), e.csr(lists), e.csr(lists[::-1]), 5),
+        "eval_pos": lambda e: e.eval_pos(0, 8, S8, 0, I, e.csr(lists[::-1])),
+        "sync_adam": lambda e: e.sync_adam(),
+        "tables_dirty": lambda e: e.tables_dirty(),
+        "set_adam_step": lambda e: setattr(e, "adam_step", e.adam_step),
+        "clear_item_grad": lambda e: e.clear_item_grad(I),   # (the staging tables are all-zero between steps anyway)
+        "clear_user_grad": lambda e: e.clear_user_grad(U),
+        "sync_check": lambda e: e.sync_check(),
+    }
     return {
+        **gated,
         "score_pairs": lambda e: e.score_pairs(*pairs),
         "score_block": lambda e: e.score_block(3, 50),
         "step_project": lambda e: e.step_project(),
@@ -203,11 +234,22 @@ def _mid_calls():
 
 
 MID_CALLS = ("bind", "list_step", "profile", "project_rows", "score_block", "score_pairs", "set_hyper", "split_step", "step_project")
+GATED_CALLS = ("clear_item_grad", "clear_user_grad", "eval_pos", "eval_users", "feat_explain", "feat_explain_new", "fold_in",
+               "score_new_block", "score_rows_block", "set_adam_step", "sync_adam", "sync_check", "tables_dirty", "topk_lists", "topk_rows")
 
 
-@pytest.mark.parametrize("call", MID_CALLS)
+def _tensors(r):
+    """the tensors of a call's result (a tensor, a dict or a tuple of them; anything else holds none), in a fixed order"""
+    if isinstance(r, torch.Tensor):
+        return [r]
+    if isinstance(r, dict):
+        return [r[n] for n in sorted(r)]
+    return [t for x in r for t in _tensors(x)] if isinstance(r, (tuple, list)) else []
+
+
+@pytest.mark.parametrize("call", MID_CALLS + GATED_CALLS)
 def test_a_call_between_two_deferred_steps(monkeypatch, call):
-    assert sorted(_mid_calls()) == sorted(MID_CALLS)
+    assert sorted(_mid_calls()) == sorted(MID_CALLS + GATED_CALLS)
     mid = _mid_calls()[call]
     ea, eb = _pair(monkeypatch, 256, 20, "bf16", "sgd")
     batches = [_batch(200 + s) for s in range(4)]
@@ -216,8 +258,9 @@ def test_a_call_between_two_deferred_steps(monkeypatch, call):
         if s == 2:
             assert ea.dense_pending() and not eb.dense_pending()
             ra, rb = mid(ea), mid(eb)
-            if isinstance(ra, torch.Tensor):
-                _same(ra, rb, call)
+            assert len(_tensors(ra)) == len(_tensors(rb))
+            for q, (xa, xb) in enumerate(zip(_tensors(ra), _tensors(rb))):
+                _same(xa, xb, "%s[%d]" % (call, q))
             # set_hyper and profile touch no table: the update stays pending and the next step carries it.  Every other call
             # settles first and leaves nothing pending (a list-mode step never defers its own update).
             assert ea.dense_pending() == (call in ("set_hyper", "profile")), call
@@ -228,6 +271,84 @@ def test_a_call_between_two_deferred_steps(monkeypatch, call):
         _same(first[0][n], first[1][n], "%s: first %s" % (call, n))
     _same(ea.score_block(0, 8), eb.score_block(0, 8), call + ": score_block")
     _close(ea, eb)
+
+
+def test_a_rejected_call_leaves_the_update_pending(monkeypatch):
+    """A call turned away for its arguments, or by the gate for the handle's kind, launches nothing: the update stays pending and
+    the next step carries it."""
+    ea, eb = _pair(monkeypatch, 256, 20, "bf16", "sgd")
+    u = lm._dev(np.arange(8, dtype=np.int32))
+    S = torch.zeros((8, I), device="cuda")
+    rejected = (lambda e: e.lib.bprx_score_block(e.h, 5, 3, S.data_ptr(), None), lambda e: e.topk(0, 8, S, e.csr(_lists()), 0),
+                lambda e: e.feat_explain_new(torch.zeros((8, 256)), u, u, top=0), lambda e: e.lib.bprx_project_rows(e.h, None, 1 << 31, None, None),
+                lambda e: e.explain_pairs(u, u))             # (the last: not a GradFashion handle)
+    for s, call in enumerate(rejected):
+        b = _batch(601 + s)
+        ea.step(*b, want_loss=False); eb.step(*b, want_loss=False)
+        assert ea.dense_pending() == 1
+        ea.profile(True)
+        for e in (ea, eb):
+            try:
+                rc = call(e)
+            except _ffi.BprxError as err:
+                rc = err.code
+            assert rc == _ffi.E_INVALID, (s, rc)
+        assert ea.dense_pending() == 1 and ea.profile_read() == {}, s
+        b = _batch(650 + s)
+        ea.step(*b, want_loss=False); eb.step(*b, want_loss=False)
+        prof = ea.profile_read()
+        assert "dense_update" not in prof and prof["row_count"][1] == 1, (s, prof)     # carried by the index pass
+        ea.profile(False)
+    _same_tables(ea, eb, "rejected calls")
+    _close(ea, eb)
+
+
+def test_an_empty_call_settles(monkeypatch):
+    """A valid call with no work passes the gate like any other: nothing is pending afterwards."""
+    ea, eb = _pair(monkeypatch, 256, 20, "bf16", "sgd")
+    one = torch.zeros(64, device="cuda")
+    p = one.data_ptr()
+    empty = (lambda e: e.lib.bprx_score_pairs(e.h, None, None, 0, None, None), lambda e: e.lib.bprx_score_block(e.h, 7, 7, p, None),
+             lambda e: e.lib.bprx_project_rows(e.h, None, 0, None, None),
+             lambda e: e.lib.bprx_topk_lists(e.h, 0, None, None, None, 5, None, None, None, None),
+             lambda e: e.lib.bprx_fold_in(e.h, p, None, None, 0, 1, 0.1, 0.0, 0, p, p, None, None))
+    for s, call in enumerate(empty):
+        b = _batch(700 + s)
+        ea.step(*b, want_loss=False); eb.step(*b, want_loss=False)
+        assert ea.dense_pending() == 1
+        assert call(ea) == 0 and call(eb) == 0, s
+        assert ea.dense_pending() == 0, s
+    _same_tables(ea, eb, "empty calls")
+    _close(ea, eb)
+
+
+def test_borrowed_user_rows_leave_the_bound_ones_in_place(monkeypatch):
+    """score_rows_block and ACF's score_block run the block-score kernels on other user rows than the bound Gu / Tu: what reads the
+    bound rows scores the same bits before and after."""
+    e = _engine(monkeypatch, True, 256, 20, "bf16", "sgd")
+    g = torch.Generator().manual_seed(79)
+    Gu8, Tu8 = (torch.rand((8, w), generator=g).cuda() - 0.5 for w in (K, 20))
+    u, i = lm._dev(np.arange(64, dtype=np.int32) % U), lm._dev(np.arange(64, dtype=np.int32) * 7 % I)
+    block, pairs = e.score_block(0, 8).clone(), e.score_pairs(u, i).clone()
+    own = e.score_rows_block(e.t["Gu"], e.t["Tu"], 0, 8).clone()
+    other = e.score_rows_block(Gu8, Tu8, 0, 8)
+    _same(own, block, "the handle's own rows")
+    assert not torch.equal(other, block)
+    _same(e.score_block(0, 8), block, "score_block afterwards")
+    _same(e.score_pairs(u, i), pairs, "score_pairs afterwards")
+    _close(e)
+    import test_gpu_acf as ta
+    rs = np.random.RandomState(5)
+    t = ta.random_tables(rs, 20, 50, 16, 64, 64, 64, scale=10.0)
+    train = ta._lists(rs, 20, 50, rs.randint(1, 12, 20))
+    a = ta._engine(t, ta._features(rs, 50, 9, 64, "fp32"), train, eval_lists=[x + [int(rs.randint(50))] for x in train])
+    u, i = rs.randint(0, 20, 100), rs.randint(0, 50, 100)
+    pairs, prof = a.score_pairs(u, i).clone(), a.acf_profiles(range(20)).clone()
+    block = a.score_block(0, 20).clone()                    # (the block-score kernels on Gu' of the evaluation histories)
+    _same(a.score_pairs(u, i), pairs, "ACF score_pairs afterwards")
+    _same(a.acf_profiles(range(20)), prof, "ACF profiles afterwards")
+    _same(a.score_block(0, 20), block, "ACF score_block again")
+    _close(a)
 
 
 def test_close_with_an_update_pending(monkeypatch):

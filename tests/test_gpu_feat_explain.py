@@ -371,7 +371,7 @@ def test_errors_leave_the_handle_usable_and_no_allocation_behind():
     usable()
     with pytest.raises(_ffi.BprxError) as err:
         m.feat_explain(u, i, 5, 40)
-    assert err.value.code == _ffi.E_STATE
+    assert err.value.code == _ffi.E_INVALID                        # (a handle of the wrong kind, as everywhere)
     assert m.score_pairs(u, i).shape == (40,)
     m.sync_check()
     for bad_u, bad_i in ((50, 3), (3, 80), (-1, 3)):                 # clamped, and reported by sync_check
