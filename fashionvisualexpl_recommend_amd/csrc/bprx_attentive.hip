@@ -19,6 +19,8 @@
 //   k_af_update       sgd / dense ApplyAdam on the thirteen encoder and attention tensors
 //   k_af_block        pairwise attention of a user block against every item: f32 MFMA (32x32x2) of the item encodings with the
 //                     user's diag(g_u) W_1 staged in LDS, relu . W_2, 3-way softmax and the score in the epilogue
+//   k_af_fold         bprx_af_fold_in: one workgroup per new user, one wave per pair: attention forward + backward for the user's
+//                     row only, the item side and the encodings frozen, the row's optimiser steps in registers
 #include <climits>
 
 #include "bprx_internal.h"
@@ -872,6 +874,190 @@ __global__ __launch_bounds__(256) void k_af_block(AfAtt A, const float *__restri
   }
 }
 
+// ---- users the model was not trained on (bprx_af_fold_in) ---------------------------------------------------------------------
+// One workgroup per user, resident across the steps; NW = blockDim.x / 64 waves, wave w takes the pairs w, w + NW, ... of a round.
+// A pair is 8k floats in LDS: the six encoding rows (positive: colour, edges, class; then the negative) and the two Gi rows.  The
+// first nc pairs are gathered once into the cache area and stay there; the others are gathered into the wave's stage every step.
+// Either way af_fold_pair is handed an LDS pointer to the same eight rows: one code path, the same bits.  A pair's gradient goes
+// to the wave's dg row; after the round's barrier thread c adds the round's rows to its acc in pair order (no atomics).
+// LDS (floats): gs[k] | ls[NW] | NW x (stage[8k] hd[6h] dg[k]) | cache[nc x 8k]
+struct AfFold {
+  AfAtt A;                        // C = Call [3, I, k]; Gu is not read (the rows are the caller's)
+  int I;
+  const int64_t *ptr;             // [n + 1] pairs of user r: [ptr[r], ptr[r + 1])
+  const int32_t *pos, *neg;
+  int steps, adam;
+  float lr, reg, b1, b2, eps;
+  float *Gu, *loss;               // [n, k] in / out; [n] or nullptr
+  int32_t *errflag;
+  int cache;                      // floats of LDS behind the waves' areas (0: every pair is gathered every step)
+};
+constexpr int AF_FOLD_EPT = AF_MAX_K / 64;    // elements of g per thread in the smallest workgroup (one wave)
+
+// Forward and backward of one pair for the row gs: returns softplus(-d) and leaves -s (dx(i)/dg - dx(j)/dg) in dg[k].
+// rows = cs[2][3][k] gi[2][k], hd[6h] (hidden units, then their gradients): LDS of the calling wave.
+__device__ __forceinline__ float af_fold_pair(const AfAtt &A, const float *gs, const float *rows, float *hd, float *dg, int lane) {
+  const int k = A.k, h = A.h;
+  const float *gi = rows + 6 * k;
+  float a[2][3], al[2][3], t[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}}, x[2];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    af_att_fwd(A, gs, rows + s * 3 * k, lane, a[s], hd + s * 3 * h, 1, 0);
+    af_softmax3(a[s], al[s]);
+  }
+  for (int c = lane; c < k; c += 64) {
+    const float g = gs[c];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const float pg = g * gi[s * k + c];
+#pragma unroll
+      for (int l = 0; l < 3; ++l) t[s][l] = fmaf(pg, rows[(s * 3 + l) * k + c], t[s][l]);
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+#pragma unroll
+    for (int l = 0; l < 3; ++l) t[s][l] = wave_sum(t[s][l]);
+    x[s] = al[s][0] * t[s][0] + al[s][1] * t[s][1] + al[s][2] * t[s][2];   // (the form of k_af_block's epilogue)
+  }
+  const float diff = x[0] - x[1];
+  const bool inr = (diff >= -80.0f) && (diff <= 1e8f);                 // tf.clip_by_value gradient mask
+  const float z = -fminf(fmaxf(diff, -80.0f), 1e8f);
+  const float sp = z > 0.f ? z + log1pf(expf(-z)) : log1pf(expf(z));
+  const float gd = inr ? -1.0f / (1.0f + expf(diff)) : 0.f;           // -s_p = -sigmoid(-diff)
+  const float dx[2] = {gd, -gd};
+  float dav[2][3];                                                     // d loss / d a_l through the softmax
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+    for (int l = 0; l < 3; ++l) dav[s][l] = dx[s] * al[s][l] * (t[s][l] - x[s]);
+  for (int j = lane; j < h; j += 64) {                                 // (a lane reads back the units it wrote itself)
+    const float w2 = A.W2[j];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      for (int l = 0; l < 3; ++l) {
+        const int o = (s * 3 + l) * h + j;
+        hd[o] = hd[o] > 0.f ? dav[s][l] * w2 : 0.f;
+      }
+  }
+  wave_sync();
+  for (int c = lane; c < k; c += 64) {
+    float dp[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const float *wr = A.W1 + (int64_t)c * h;
+    for (int j = 0; j < h; ++j) {
+      const float wv = wr[j];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) dp[q] = fmaf(wv, hd[q * h + j], dp[q]);
+    }
+    float d = 0.f;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const float *c3 = rows + s * 3 * k;
+      const float wf = al[s][0] * c3[c] + al[s][1] * c3[k + c] + al[s][2] * c3[2 * k + c];
+      d = fmaf(dx[s] * gi[s * k + c], wf, d);
+#pragma unroll
+      for (int l = 0; l < 3; ++l) d = fmaf(c3[l * k + c], dp[s * 3 + l], d);
+    }
+    dg[c] = d;
+  }
+  return sp;
+}
+
+__global__ __launch_bounds__(256) void k_af_fold(AfFold F) {
+  extern __shared__ float sm[];
+  const AfAtt &A = F.A;
+  const int k = A.k, h = A.h, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, NT = blockDim.x, NW = NT >> 6;
+  const int64_t r = blockIdx.x;
+  const int64_t p0 = F.ptr[r], np64 = F.ptr[r + 1] - p0;
+  if (np64 <= 0) {                                           // no pairs: the row stays, the loss is 0 (the whole workgroup leaves)
+    if (tid == 0 && F.loss) F.loss[r] = 0.f;
+    return;
+  }
+  const int np = np64 > INT32_MAX ? INT32_MAX : (int)np64;
+  const int PW = 8 * k, WS = PW + 6 * h + k;                 // floats of a pair; of a wave's area
+  float *gs = sm, *ls = gs + k, *areas = ls + NW, *cache = areas + (size_t)NW * WS;
+  float *stage = areas + (size_t)w * WS, *hd = stage + PW, *dg = hd + 6 * h;
+  const int fit = F.cache / PW, nc = np < fit ? np : fit;
+  const int32_t *pos = F.pos + p0, *neg = F.neg + p0;
+  float gw[AF_FOLD_EPT], m[AF_FOLD_EPT], v[AF_FOLD_EPT];
+#pragma unroll
+  for (int e = 0; e < AF_FOLD_EPT; ++e) {
+    const int c = tid + NT * e;
+    gw[e] = c < k ? F.Gu[r * k + c] : 0.f;
+    m[e] = 0.f; v[e] = 0.f;
+    if (c < k) gs[c] = gw[e];
+  }
+  __syncthreads();
+  const float r2n = 2.f * F.reg * (float)np, rn = F.reg * (float)np;
+  for (int t = 1; t <= F.steps; ++t) {
+    const bool last = t == F.steps && F.loss != nullptr;
+    float acc[AF_FOLD_EPT], cmp[AF_FOLD_EPT];                // the gradient sum and its (Kahan) compensation
+    double lsum = 0.0;                                       // thread 0: the data term of the loss, in pair order
+#pragma unroll
+    for (int e = 0; e < AF_FOLD_EPT; ++e) { acc[e] = 0.f; cmp[e] = 0.f; }
+    for (int base = 0; base < np; base += NW) {
+      const int p = base + w;
+      if (p < np) {                                          // (wave-uniform)
+        float *rows = p < nc ? cache + (size_t)p * PW : stage;
+        if (t == 1 || p >= nc) {
+          const int it[2] = {clamp_index(pos[p], F.I, F.errflag, 2), clamp_index(neg[p], F.I, F.errflag, 2)};
+          for (int c = lane; c < k; c += 64) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+#pragma unroll
+              for (int l = 0; l < 3; ++l) rows[(s * 3 + l) * k + c] = A.C[((int64_t)l * A.ldr + it[s]) * k + c];
+              rows[(6 + s) * k + c] = A.Gi[(int64_t)it[s] * k + c];
+            }
+          }
+        }
+        wave_sync();
+        const float lp = af_fold_pair(A, gs, rows, hd, dg, lane);
+        if (lane == 0) ls[w] = lp;
+      }
+      __syncthreads();
+      const int cnt = np - base < NW ? np - base : NW;
+#pragma unroll
+      for (int e = 0; e < AF_FOLD_EPT; ++e) {
+        const int c = tid + NT * e;
+        if (c < k)
+          for (int q = 0; q < cnt; ++q) {                    // compensated: thousands of pairs pushing one way must not round
+            const float y = areas[(size_t)q * WS + PW + 6 * h + c] - cmp[e];     // every add at the ulp of the whole sum
+            const float ts = acc[e] + y;
+            cmp[e] = (ts - acc[e]) - y;
+            acc[e] = ts;
+          }
+      }
+      if (last && tid == 0)
+        for (int q = 0; q < cnt; ++q) lsum += (double)ls[q];
+      __syncthreads();
+    }
+    if (last) {                                              // loss_T, before the last update, as train_step returns it
+      if (w == 0) {
+        float s = 0.f;
+        for (int c = lane; c < k; c += 64) s = fmaf(gs[c], gs[c], s);
+        s = wave_sum(s);
+        if (lane == 0) F.loss[r] = (float)(lsum + (double)(rn * s));
+      }
+      __syncthreads();
+    }
+    const float tt = (float)t;
+    const float lr_t = F.adam ? F.lr * sqrtf(1.0f - powf(F.b2, tt)) / (1.0f - powf(F.b1, tt)) : F.lr;
+#pragma unroll
+    for (int e = 0; e < AF_FOLD_EPT; ++e) {
+      const int c = tid + NT * e;
+      const float g = acc[e] + r2n * gw[e];
+      if (F.adam) adam_elem(gw[e], m[e], v[e], g, F.b1, F.b2, lr_t, F.eps);
+      else gw[e] = gw[e] - lr_t * g;
+      if (c < k) gs[c] = gw[e];
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int e = 0; e < AF_FOLD_EPT; ++e) {
+    const int c = tid + NT * e;
+    if (c < k) F.Gu[r * k + c] = gw[e];
+  }
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------
 static AfDrop af_drop(const AfState *S, int64_t step, bool training) {
   AfDrop d;
@@ -1120,18 +1306,26 @@ static int af_encode_many(bprx_handle *h, const int32_t *items, int64_t n, float
   return BPRX_OK;
 }
 
-int bprx_af_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, float *alpha, hipStream_t s) {
+// Call = the dropout-off encodings of every item for the bound parameter state (a bprx_step invalidates it)
+static int af_call_current(bprx_handle *h, hipStream_t s) {
+  AfState *S = h->af;
+  if (S->eval_valid) return BPRX_OK;
+  const int I = h->cfg.num_items;
+  const int rc = af_encode_many(h, nullptr, I, S->Call, I, s);
+  if (!rc) S->eval_valid = true;
+  return rc;
+}
+
+int bprx_af_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, float *alpha, hipStream_t s, const float *Gu_rows) {
   AfState *S = h->af;
   const int I = h->cfg.num_items;
   int rc;
-  if (!S->eval_valid) {
-    if ((rc = af_encode_many(h, nullptr, I, S->Call, I, s))) return rc;
-    S->eval_valid = true;
-  }
+  if ((rc = af_call_current(h, s))) return rc;
   const int KP = (S->k + 7) / 8 * 8, NJ = (S->h + 31) / 32;
   const size_t lds = sizeof(float) * ((size_t)KP * 32 * NJ + 64 * NJ + KP);
   const int64_t tiles = ((int64_t)I + 127) / 128;
-  const AfAtt A = af_att(h, S->Call, I);
+  AfAtt A = af_att(h, S->Call, I);
+  if (Gu_rows) A.Gu = Gu_rows;
   for (int32_t c0 = u0; c0 < u1; c0 += 32768) {              // gridDim.y holds the users: at most 65 535 per launch
     const int32_t c1 = u1 - c0 < 32768 ? u1 : c0 + 32768;
     const dim3 grid((unsigned)(tiles < 16 ? tiles : 16), (unsigned)(c1 - c0));
@@ -1300,6 +1494,57 @@ extern "C" int bprx_af_score_block(bprx_handle *h, int32_t u0, int32_t u1, float
   if (u0 < 0 || u1 > h->cfg.num_users || u0 > u1 || !scores) BPRX_FAIL(h, BPRX_E_INVALID, "af_score_block: bad user range [%d,%d)", u0, u1);
   if (u0 == u1) return BPRX_OK;
   return bprx_af_block(h, u0, u1, scores, alpha, (hipStream_t)stream);
+}
+
+// bprx_af_score_block for caller-owned rows (users folded in by bprx_af_fold_in): k_af_block, given the caller's rows
+extern "C" int bprx_af_score_rows_block(bprx_handle *h, const float *Gu_rows, int64_t n_rows, int64_t r0, int64_t r1, float *scores,
+                                        float *alpha, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (n_rows < 0 || n_rows >= ((int64_t)1 << 31) || r0 < 0 || r1 > n_rows || r0 > r1)
+    BPRX_FAIL(h, BPRX_E_INVALID, "af_score_rows_block: bad row range [%lld,%lld) of %lld", (long long)r0, (long long)r1, (long long)n_rows);
+  if (r0 != r1 && (!Gu_rows || !scores)) BPRX_FAIL(h, BPRX_E_INVALID, "af_score_rows_block: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = bprx_enter(h, "af_score_rows_block", NEED_BOUND, KIND_AF, s);
+  if (rc || r0 == r1) return rc;
+  return bprx_af_block(h, (int32_t)r0, (int32_t)r1, scores, alpha, s, Gu_rows);
+}
+
+// Total LDS of a k_af_fold workgroup where the waves' own areas leave room: four workgroups share a CU (160 KB), the occupancy
+// bprx_fold_in chose; what the areas do not take holds the cached pairs.  Wider models take what they need, up to 64 KB.
+constexpr size_t AF_FOLD_LDS = 40 * 1024;
+
+extern "C" int bprx_af_fold_in(bprx_handle *h, const int64_t *pair_ptr, const int32_t *pos, const int32_t *neg, int64_t n, int32_t steps,
+                               float lr, float reg, int32_t optimizer, float *Gu_rows, float *loss, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (n < 0 || n >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in: n = %lld out of range", (long long)n);
+  if (steps < 1) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in: steps = %d < 1", steps);
+  if (optimizer != BPRX_OPT_SGD && optimizer != BPRX_OPT_ADAM_TF23) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in: optimizer %d", optimizer);
+  if (!pair_ptr || !Gu_rows) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in: null pointer");
+  if (n && (!pos || !neg)) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  int rc = bprx_enter(h, "af_fold_in", NEED_BOUND, KIND_AF, s);
+  if (rc || n == 0) return rc;
+  if ((rc = af_call_current(h, s))) return rc;               // the encodings the scores are computed from
+  AfState *S = h->af;
+  const bprx_config &c = h->cfg;
+  AfFold F;
+  F.A = af_att(h, S->Call, c.num_items);
+  F.I = c.num_items;
+  F.ptr = pair_ptr; F.pos = pos; F.neg = neg;
+  F.steps = steps; F.adam = optimizer == BPRX_OPT_ADAM_TF23;
+  F.lr = lr; F.reg = reg; F.b1 = c.beta1; F.b2 = c.beta2; F.eps = c.epsilon;
+  F.Gu = Gu_rows; F.loss = loss; F.errflag = h->errflag;
+  // as many waves (pairs in flight) as fit a workgroup's 64 KB with their areas: four up to k = 384 at h = 32, one always fits
+  const size_t per = 9 * (size_t)S->k + 6 * (size_t)S->h;
+  int NW = 4;
+  auto fixed = [&](int nw) { return sizeof(float) * ((size_t)S->k + nw + nw * per); };
+  while (NW > 1 && fixed(NW) > 65536) --NW;
+  const size_t total = fixed(NW) > AF_FOLD_LDS ? fixed(NW) : AF_FOLD_LDS;
+  F.cache = h->fold_cache ? (int)((total - fixed(NW)) / sizeof(float)) : 0;
+  const size_t lds = fixed(NW) + (size_t)F.cache * sizeof(float);
+  hipLaunchKernelGGL(k_af_fold, dim3((unsigned)n), dim3(64 * NW), lds, s, F);
+  BPRX_LAUNCH_CHECK(h, "k_af_fold");
+  return BPRX_OK;
 }
 
 extern "C" int bprx_af_dropout_mask(bprx_handle *h, int64_t step, int64_t n_rows, uint8_t *out, void *stream) {

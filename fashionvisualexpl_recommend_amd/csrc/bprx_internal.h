@@ -255,7 +255,7 @@ struct bprx_handle {
   int32_t *slist, *slist_n;       // sgd fast path: list of the batch's SHARED rows (kind << 30 | row), two alternating cursors
   int num_cu;                     // compute units of the device (balanced forward grid)
   int fwd_variant;                // 0: the plain forward kernel (env BPRX_FWD_VARIANT, read at create), else the per-shape policy
-  int fold_cache;                 // env BPRX_FOLD_CACHE, read at create: 1 (default) bprx_fold_in runs its steps from LDS where a user's pairs fit
+  int fold_cache;                 // env BPRX_FOLD_CACHE, read at create: 1 (default) bprx_fold_in / bprx_af_fold_in run their steps from LDS where a user's pairs fit
   float neg_bias_reg;             // factor of reg on the negative item's bias: 0.1 (VBPR.py:125), 1.0 for GradFashion
   // GradFashion (bprx_bind_factored, bprx_factored.hip): E / Bp of t are E_eff / Bp_eff, composed from the factors fx
   bool factored;
@@ -378,7 +378,8 @@ void bprx_acf_free(bprx_handle *h);
 // AttentiveFashion (bprx_attentive.hip): what bprx_step / bprx_score_pairs / bprx_score_block do on a handle bound with bprx_bind_attentive
 int bprx_af_step(bprx_handle *h, const int32_t *u, const int32_t *i, const int32_t *j, int64_t B, float *loss_out, hipStream_t s);
 int bprx_af_pairs(bprx_handle *h, const int32_t *u, const int32_t *i, int64_t n, float *x, float *alpha, hipStream_t s);
-int bprx_af_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, float *alpha, hipStream_t s);
+// Gu_rows: the user rows the block is scored for (nullptr: the handle's own Gu); [u0, u1) are rows of that table
+int bprx_af_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, float *alpha, hipStream_t s, const float *Gu_rows = nullptr);
 void bprx_af_invalidate(bprx_handle *h);
 void bprx_af_free(bprx_handle *h);
 
@@ -520,7 +521,8 @@ enum : unsigned {
   NEED_P_ALL = 8,                 // VBPR: P holds the projection of every item (makes the image current on the way)
 };
 constexpr const char *BPRX_NOT_BOUND = "%s: tables not bound (call bprx_bind_tables first)";   // (also the step path's message)
-enum { KIND_ANY = 0, KIND_PLAIN, KIND_VBPR, KIND_VBPR_NO_FP8, KIND_FACTORED };   // PLAIN: BPRMF / VBPR, not ACF / AttentiveFashion
+enum { KIND_ANY = 0, KIND_PLAIN, KIND_VBPR, KIND_VBPR_NO_FP8, KIND_FACTORED, KIND_AF };   // PLAIN: BPRMF / VBPR, not ACF / AttentiveFashion;
+                                                                                            // AF: bound with bprx_bind_attentive
 struct ReadPlan {
   int error;                      // 0, or BPRX_E_STATE (not bound) / BPRX_E_INVALID (a handle of the wrong kind): nothing is launched
   const char *why;                // ... and its message, a format with one %s for the name of the entry
@@ -541,6 +543,7 @@ inline ReadPlan plan_read(const bprx_handle &h, unsigned need, int kind) {
     return fail(BPRX_E_INVALID, "%s: fp8 features are not supported for new items (a new row may exceed the max-abs the codes "
                                 "were scaled for and would saturate): fp32 or bf16");
   if (kind == KIND_FACTORED && !h.factored) return fail(BPRX_E_INVALID, "%s: the handle is not bound with bprx_bind_factored");
+  if (kind == KIND_AF && !h.af) return fail(BPRX_E_INVALID, "%s: the handle is not bound with bprx_bind_attentive");
   p.settle = h.pend.on;
   p.sync = (need & NEED_ROWS) && plain && h.adam_lazy && h.adam_synced < h.adam_t;
   p.project = (need & NEED_P_ALL) && plain && vb && !h.p_valid;

@@ -429,6 +429,39 @@ class Engine:
         _ffi.check(self.h, self.lib.bprx_af_score_block(self.h, int(u0), int(u1), _ptr(x), _ptr(al), _stream()))
         return x, al
 
+    def af_fold_in(self, pair_ptr, pos, neg, steps, Gu_rows, lr=None, reg=None, optimizer=None, want_loss=True):
+        """bprx_af_fold_in: `steps` optimiser steps on each row of Gu_rows [n, k] (a contiguous fp32 device tensor, updated IN
+        PLACE) over the pairs (pos[p], neg[p]), p in [pair_ptr[r], pair_ptr[r + 1]), of row r, the item side, the encoders and the
+        attention tensors frozen and dropout off.  pair_ptr: int64 [n + 1].  lr / reg / optimizer default to the engine's.
+        Returns loss fp32 [n] (loss_steps, before the last update) or None."""
+        ptr = torch.as_tensor(pair_ptr, dtype=torch.int64).to(self.device).contiguous()
+        n = int(ptr.numel()) - 1
+        p_, n_ = as_index(pos, self.device), as_index(neg, self.device)
+        if p_.numel() != n_.numel():
+            raise ValueError("af_fold_in: %d positives for %d negatives" % (p_.numel(), n_.numel()))
+        if not (Gu_rows.is_cuda and Gu_rows.dtype == torch.float32 and Gu_rows.is_contiguous() and tuple(Gu_rows.shape) == (n, self.k)):
+            raise ValueError("af_fold_in: Gu_rows must be a contiguous fp32 device tensor [%d, %d]" % (n, self.k))
+        lr = self._hyper()[0] if lr is None else float(lr)
+        reg = self._hyper()[1] if reg is None else float(reg)
+        opt = _ffi.OPTIMIZER[self.optimizer if optimizer is None else optimizer]
+        loss = torch.empty(max(n, 0), dtype=torch.float32, device=self.device) if want_loss else None
+        if p_.numel() == 0:                                  # (nobody has a pair: the library still wants the pointers)
+            p_ = n_ = torch.zeros(1, dtype=torch.int32, device=self.device)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _ffi.check(self.h, self.lib.bprx_af_fold_in(self.h, p(ptr), p(p_), p(n_), n, int(steps), lr, reg, opt, p(Gu_rows), p(loss),
+                                                    _stream()))
+        return loss
+
+    def af_score_rows_block(self, Gu_rows, r0, r1, want_alpha=True):
+        """bprx_af_score_rows_block: af_score_block for rows [r0, r1) of a caller-owned user table: scores [r1 - r0, I] and
+        attentions [r1 - r0, I, 3] (None with want_alpha=False)."""
+        x = torch.empty((r1 - r0, self.I), dtype=torch.float32, device=self.device)
+        al = torch.empty((r1 - r0, self.I, 3), dtype=torch.float32, device=self.device) if want_alpha else None
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _ffi.check(self.h, self.lib.bprx_af_score_rows_block(self.h, p(Gu_rows), int(Gu_rows.shape[0]), int(r0), int(r1), p(x), p(al),
+                                                             _stream()))
+        return x, al
+
     def af_dropout_mask(self, step, n_rows):
         """The keep masks of step index `step` for n_rows = 2B sample rows (bprx_af_dropout_mask): three uint8 device tensors
         [n_rows, 256], [n_rows, 64], [n_rows, 256] (colour hidden units, pooled edge channels, class hidden units)."""

@@ -990,6 +990,70 @@ class AttentiveFashion(BPRMF):
         items = [int(i) for i in np.asarray(items).reshape(-1)]
         return self.explain([int(u)] * len(items), items, grid, maps)
 
+    # ---- users the model was not trained on: the reference's step on one user's pairs, everything else frozen, dropout off -------
+    def fold_in_users(self, histories, steps=30, negatives=4, lr=None, reg=None, optimizer=None, seed=0, init=None):
+        """Rows for users who arrive after training with a history of catalogue items each: Gu_new [n, k] (device), fitted by
+        Engine.af_fold_in over the pairs of draw_fold_pairs(histories, num_items, negatives, seed).  lr / reg / optimizer: None =
+        the run's.  init: None = zero rows (at g = 0 the gradient is (sum_l alpha_l c_l) * Gi, not zero: a zero start is live), or
+        the rows to start from."""
+        eng = self.engine
+        n = len(histories)
+        ptr, pos, neg = draw_fold_pairs(histories, self.num_items, negatives, seed)
+        if init is None:
+            Gu = torch.zeros((n, eng.k), dtype=torch.float32, device=eng.device)
+        else:
+            Gu = torch.as_tensor(np.asarray(init.detach().cpu() if isinstance(init, torch.Tensor) else init, dtype=np.float32)
+                                 .reshape(n, eng.k), device=eng.device).contiguous().clone()
+        eng.af_fold_in(ptr, pos, neg, steps, Gu, lr=self.learning_rate if lr is None else lr, reg=self.reg if reg is None else reg,
+                       optimizer=self.optimizer_name if optimizer is None else optimizer, want_loss=False)
+        return Gu
+
+    def recommend_new_users(self, histories, k=None, **fold):
+        """The k (default top_k) best catalogue items of every new user, their own histories masked: numpy idx int [n, kk], val
+        [n, kk] and alpha [n, kk, 3] (colour, edges, class), kk = min(k, I), best first.  The rows are fitted by
+        fold_in_users(histories, **fold), scored in row blocks and ranked on the device; rows whose list depends on the order of
+        equal scores are redone with numpy on the GPU's (masked) row, as BPRMF.recommend_new_users does."""
+        eng = self.engine
+        n, I = len(histories), self.num_items
+        k = self.evaluator.k if k is None else int(k)
+        kk = min(k, I)
+        Gu = self.fold_in_users(histories, **fold)
+        idx_all, val_all = np.zeros((n, kk), np.int64), np.zeros((n, kk), np.float32)
+        al_all = np.zeros((n, kk, 3), np.float32)
+        blk = max(1, min(self.evaluator.user_block, (1 << 27) // max(1, I)))
+        for b0 in range(0, n, blk):
+            b1 = min(n, b0 + blk)
+            sc, al = eng.af_score_rows_block(Gu, b0, b1)
+            idx, val, flag = eng.topk_lists(sc, eng.csr(histories[b0:b1]), k)
+            pick = idx[:, :kk].long().clamp_(0, I - 1).unsqueeze(-1).expand(-1, -1, 3)
+            al_all[b0:b1] = torch.gather(al, 1, pick).cpu().numpy()
+            idx, val, flag = idx.cpu().numpy(), val.cpu().numpy(), flag.cpu().numpy()
+            idx_all[b0:b1], val_all[b0:b1] = idx[:, :kk], val[:, :kk]
+            for r in np.nonzero(flag)[0]:
+                row = sc[int(r)].cpu().numpy()
+                top_k_id = row.argsort()[-k:][::-1]
+                idx_all[b0 + r], val_all[b0 + r] = top_k_id, row[top_k_id]
+                al_all[b0 + r] = al[int(r)].cpu().numpy()[top_k_id]
+        return idx_all, val_all, al_all
+
+    def _store_new_user_recs(self, path):
+        """params.af_new_users: new-user-recs-* next to the recs-* file at `path`, rows
+        'label\ti\tscore\talpha_colour\talpha_edges\talpha_class', best first, one block per label in file order."""
+        src = getattr(self.params, "af_new_users", None)
+        if not src:
+            return
+        from .train_rec import read_new_users
+        labels, lists = read_new_users(src)
+        d, f = os.path.split(path)
+        idx, val, al = self.recommend_new_users(lists, steps=getattr(self.params, "fold_steps", 30),
+                                                negatives=getattr(self.params, "fold_negatives", 4),
+                                                seed=getattr(self.params, "init_seed", 0))
+        with open(os.path.join(d, f.replace("recs-", "new-user-recs-", 1)), 'w') as out:
+            for r, label in enumerate(labels):
+                for q in range(idx.shape[1]):
+                    out.write(label + '\t' + str(idx[r, q]) + '\t' + str(val[r, q]) + '\t' + str(al[r, q, 0]) + '\t' +
+                              str(al[r, q, 1]) + '\t' + str(al[r, q, 2]) + '\n')
+
     def _store_recs(self, path):
         """recs-* / best-recs-* with the attentions; with params.af_explain = G > 0 also expl-* / best-expl-* next to them."""
         if self.af_explain <= 0:

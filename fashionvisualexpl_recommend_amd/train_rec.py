@@ -5,6 +5,7 @@ Same flag names and defaults for every flag BPRMF/VBPR consume; new flags: --opt
 --embed_d default.  ACF's --layers_component / --layers_item are `type=list` in the reference (only the default [64, 1] is
 reachable there); here they take two ints `h 1`, and so does AttentiveFashion's --attention_layers.  --dropout is the rate of the
 three encoders' Dropout layers (the reference's constant 0.5).
+--af_new_users PATH (attentive_fashion only) fits rows for users the model was not trained on and writes new-user-recs-* files.
 Run as `python -m fashionvisualexpl_recommend_amd.train_rec --rec bprmf --dataset <name> ...`.
 """
 import argparse
@@ -68,8 +69,14 @@ def parse_args(argv=None):
                              "trained on (labels are free text, kept in first-appearance order).  Their rows are fitted with the "
                              "item side frozen and new-user-recs-* / best-new-user-recs-* files (label, item, score) are written "
                              "next to recs-* / best-recs-*")
-    parser.add_argument('--fold_steps', type=int, default=30, help='--new_users: optimiser steps per new user')
-    parser.add_argument('--fold_negatives', type=int, default=4, help='--new_users: sampled negatives per history item')
+    parser.add_argument('--af_new_users', default=None, metavar='PATH',
+                        help="attentive_fashion: a TSV in the format of --new_users.  Each new user's row of Gu is fitted with the "
+                             "item side, the encoders and the attention frozen and dropout off, and new-user-recs-* / "
+                             "best-new-user-recs-* files (label, item, score, alpha_colour, alpha_edges, alpha_class) are written "
+                             "next to recs-* / best-recs-*")
+    parser.add_argument('--fold_steps', type=int, default=30, help='--new_users / --af_new_users: optimiser steps per new user')
+    parser.add_argument('--fold_negatives', type=int, default=4,
+                        help='--new_users / --af_new_users: sampled negatives per history item')
     # not in the reference
     parser.add_argument('--dropout', type=float, default=0.5,
                         help="attentive_fashion: rate of the encoders' Dropout layers (AttentiveFashion.py:53,62,70: 0.5)")
@@ -117,6 +124,8 @@ def parse_args(argv=None):
                                                                                  len(args.new_items)))
     if args.new_users is not None and args.rec not in ('bprmf', 'vbpr', 'grad_fashion'):
         parser.error("--new_users needs --rec bprmf, vbpr or grad_fashion (got --rec %s)" % args.rec)
+    if args.af_new_users is not None and args.rec != 'attentive_fashion':
+        parser.error("--af_new_users needs --rec attentive_fashion (got --rec %s)" % args.rec)
     if args.fold_steps < 1 or args.fold_negatives < 1:
         parser.error("--fold_steps and --fold_negatives take values >= 1 (got %s, %s)" % (args.fold_steps, args.fold_negatives))
     if not 0.0 <= args.dropout < 1.0:
@@ -158,6 +167,8 @@ def train(argv=None):
         raise NotImplementedError('--new_items runs on one GPU (the sharded drivers write no new-recs-* files): use --world_size 1')
     if args.new_users is not None and int(args.world_size) > 1:
         raise NotImplementedError('--new_users runs on one GPU (the sharded drivers write no new-user-recs-* files): use --world_size 1')
+    if args.af_new_users is not None and int(args.world_size) > 1:
+        raise NotImplementedError('--af_new_users runs on one GPU (no multi-GPU form): use --world_size 1')
     if args.new_items is not None and args.dtype == 'fp8':
         raise ValueError('--new_items runs with --dtype fp32 or bf16 (an fp8 table is scaled for the training max-abs: a new row '
                          'may saturate)')

@@ -150,6 +150,7 @@ BPRX_API int bprx_sync_adam(bprx_handle *h, void *stream);
      entries                                                          handle              tables bound  rows  image  P of all items
      bprx_score_block                                                 any                 yes           yes   via P  yes (VBPR)
      bprx_score_rows_block, bprx_fold_in                              BPRMF / VBPR        yes           yes   via P  yes
+     bprx_af_fold_in, bprx_af_score_rows_block                        AttentiveFashion    yes           -     -      -
      bprx_step_project                                                any                 yes           -     yes    yes
      bprx_score_pairs                                                 any                 yes           yes   unless P is current  -
      bprx_project_rows, bprx_score_new_block, bprx_feat_explain_new   VBPR, not fp8       yes           yes   yes    -
@@ -467,6 +468,40 @@ BPRX_API int bprx_af_explain(bprx_handle *h, const int32_t *user, const int32_t 
                              float *alpha, float *parts, float *map, int32_t *peak_cell, float *peak_val, void *stream);
 /* bprx_score_block with the attentions next to the scores: scores fp32 [u1-u0, I], alpha fp32 [u1-u0, I, 3] (NULL: scores only). */
 BPRX_API int bprx_af_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *scores, float *alpha, void *stream);
+/* Users the model was not trained on.  For AttentiveFashion a user is the k numbers g = Gu_u, and the score is not linear in them
+   (alpha depends on g), so bprx_fold_in's pair differences do not apply: every step runs the attention forward and backward for
+   every pair.  DEFINITION: the reference's train step (AttentiveFashion.py:211-258) on a batch made of this user's pairs, with
+   everything but the user's row frozen and DROPOUT OFF -- the encoders do not move, so the fit uses the encodings c_l(item) that
+   bprx_af_encode returns and that the scores are computed from.  For new user r with pairs (i_p, j_p),
+   p in [pair_ptr[r], pair_ptr[r+1]), n_r of them, g starting at Gu_rows[r]; for t = 1 .. steps:
+       pre_l(item) = (g * c_l) W_1 + b_1      a_l = relu(pre_l).W_2 + b_2      alpha = softmax_l(a)
+       t_l = sum_k g_k c_lk Gi_k              x = sum_l alpha_l t_l
+       d_p = clip(x(i_p) - x(j_p), -80, 1e8)  s_p = sigmoid(-d_p) inside the clip range (inclusive bounds), 0 outside
+       loss_t = sum_p softplus(-d_p) + reg n_r |g|^2
+       grad   = sum_p -s_p (dx(i_p)/dg - dx(j_p)/dg) + 2 reg n_r g                                   (summed in pair order)
+       dx/dg_k = (sum_l alpha_l c_lk) Gi_k + sum_l alpha_l (t_l - x) c_lk sum_h W_1[k,h] [pre_lh > 0] W_2[h]
+       BPRX_OPT_SGD: g <- g - lr grad       BPRX_OPT_ADAM_TF23: the sparse-variable rule of the Gu rows, slots starting at zero,
+                                            lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t); beta1, beta2, epsilon are the handle's
+   The constant regularisers of the reference's loss (Gi, the encoder outputs, the attention tensors) do not move g and are left
+   out of `loss`.  For steps = 1 and sgd, started from a trained user's row on a handle bound with dropout = 0, the row moves as
+   bprx_step on the same batch moves it.
+   bprx_af_fold_in: pair_ptr int64 [n+1], pos / neg int32 (device); Gu_rows fp32 [n, k] in / out; loss fp32 [n] or NULL:
+   loss_steps, evaluated before the last update.  A user without pairs keeps its row and has loss 0.  lr, reg, optimizer are the
+   call's (the handle's own are not read).  Like bprx_score_block the call first makes the encodings of every item current (a
+   bprx_step invalidates them); apart from that it writes its outputs only and allocates nothing.  fp32 throughout, no float
+   atomics, every sum in one fixed order: two calls return the same bits, and a user's result depends on its own pairs, its start
+   row and the tables only -- not on n, on its position, or on BPRX_FOLD_CACHE (0: every step gathers every pair's encoding and Gi
+   rows again instead of keeping the first pairs of a user in LDS; read by bprx_create).  Any n_r, every shape
+   bprx_bind_attentive accepts.  Item ids out of range are clamped and reported by bprx_sync_check (BPRX_E_RANGE).
+   BPRX_E_INVALID for a NULL handle, a handle that is not bound with bprx_bind_attentive, a NULL pointer, n < 0, steps < 1, an
+   unknown optimizer; BPRX_E_STATE for an unbound handle; n == 0: BPRX_OK. */
+BPRX_API int bprx_af_fold_in(bprx_handle *h, const int64_t *pair_ptr, const int32_t *pos, const int32_t *neg, int64_t n, int32_t steps,
+                             float lr, float reg, int32_t optimizer, float *Gu_rows, float *loss, void *stream);
+/* bprx_af_score_block for caller-owned user rows: scores fp32 [(r1-r0), num_items] and alpha fp32 [(r1-r0), num_items, 3] (NULL:
+   scores only) for rows [r0, r1) of Gu_rows [n_rows, k].  The same kernel: a slice of the handle's own Gu gives the bits of
+   bprx_af_score_block.  0 <= r0 <= r1 <= n_rows < 2^31; errors as for bprx_af_fold_in. */
+BPRX_API int bprx_af_score_rows_block(bprx_handle *h, const float *Gu_rows, int64_t n_rows, int64_t r0, int64_t r1, float *scores,
+                                      float *alpha, void *stream);
 /* The keep-mask bytes (1 = kept) of step index `step` for a batch of n_rows / 2 triplets: out uint8
    [n_rows * 256 | n_rows * 64 | n_rows * 256] (colour hidden units, pooled edge channels, class hidden units). */
 BPRX_API int bprx_af_dropout_mask(bprx_handle *h, int64_t step, int64_t n_rows, uint8_t *out, void *stream);
