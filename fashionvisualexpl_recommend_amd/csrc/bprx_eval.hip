@@ -407,18 +407,29 @@ __global__ __launch_bounds__(256) void k_topk(float *__restrict__ S, int u0, int
 
 }  // namespace
 
+// The shared tail of the three top-K entries, after each one's own argument checks: the K range, then `null` (the entry found a
+// null pointer with rows to list: rejected only now, as each entry orders its checks), the gate, and one k_topk launch over
+// nrows rows of `width` scores, row r masking the items of list row0 + r (ptr == nullptr: nothing).
+static int topk_launch(bprx_handle *h, const char *what, const char *kernel, bool null, unsigned need, int kind, int64_t nrows,
+                       float *scores, int row0, int width, const int64_t *ptr, const int32_t *items, int32_t K, int32_t *idx,
+                       float *val, int32_t *flag, void *stream) {
+  if (K <= 0 || K > TOPK_MAX) BPRX_FAIL(h, BPRX_E_INVALID, "%s: K=%d outside [1, %d]", what, K, TOPK_MAX);
+  if (null) BPRX_FAIL(h, BPRX_E_INVALID, "%s: null pointer", what);
+  const int rc = bprx_enter(h, what, need, kind, (hipStream_t)stream);
+  if (rc || nrows == 0) return rc;
+  hipLaunchKernelGGL(k_topk, dim3((unsigned)nrows), dim3(256), 0, (hipStream_t)stream, scores, row0, width, ptr, items, K, idx, val,
+                     flag);
+  BPRX_LAUNCH_CHECK(h, kernel);
+  return BPRX_OK;
+}
+
 extern "C" int bprx_topk(bprx_handle *h, int32_t u0, int32_t u1, float *scores, const int64_t *train_ptr,
                          const int32_t *train_items, int32_t K, int32_t *idx, float *val, int32_t *flag, void *stream) {
   if (!h) return BPRX_E_INVALID;
   if (u0 < 0 || u1 > h->cfg.num_users || u0 > u1 || !scores || !train_ptr || !train_items || !idx || !val || !flag)
     BPRX_FAIL(h, BPRX_E_INVALID, "topk: bad argument");
-  if (K <= 0 || K > TOPK_MAX) BPRX_FAIL(h, BPRX_E_INVALID, "topk: K=%d outside [1, %d]", K, TOPK_MAX);
-  const int rc = bprx_enter(h, "topk", 0, KIND_ANY, (hipStream_t)stream);
-  if (rc || u0 == u1) return rc;
-  hipLaunchKernelGGL(k_topk, dim3(u1 - u0), dim3(256), 0, (hipStream_t)stream, scores, u0, h->cfg.num_items, train_ptr,
-                     train_items, K, idx, val, flag);
-  BPRX_LAUNCH_CHECK(h, "k_topk");
-  return BPRX_OK;
+  return topk_launch(h, "topk", "k_topk", false, 0, KIND_ANY, u1 - u0, scores, u0, h->cfg.num_items, train_ptr, train_items, K, idx,
+                     val, flag, stream);
 }
 
 extern "C" int bprx_topk_rows(bprx_handle *h, int64_t nrows, int32_t width, float *scores, int32_t K, int32_t *idx, float *val,
@@ -426,14 +437,8 @@ extern "C" int bprx_topk_rows(bprx_handle *h, int64_t nrows, int32_t width, floa
   if (!h) return BPRX_E_INVALID;
   if (nrows < 0 || nrows >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows: n = %lld out of range", (long long)nrows);
   if (width < 1) BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows: width = %d < 1", width);
-  if (K <= 0 || K > TOPK_MAX) BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows: K=%d outside [1, %d]", K, TOPK_MAX);
-  if (nrows && (!scores || !idx || !val || !flag)) BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows: null pointer");
-  const int rc = bprx_enter(h, "topk_rows", NEED_BOUND, KIND_VBPR_NO_FP8, (hipStream_t)stream);
-  if (rc || nrows == 0) return rc;
-  hipLaunchKernelGGL(k_topk, dim3((unsigned)nrows), dim3(256), 0, (hipStream_t)stream, scores, 0, width, (const int64_t *)nullptr,
-                     (const int32_t *)nullptr, K, idx, val, flag);
-  BPRX_LAUNCH_CHECK(h, "k_topk<rows>");
-  return BPRX_OK;
+  return topk_launch(h, "topk_rows", "k_topk<rows>", nrows && (!scores || !idx || !val || !flag), NEED_BOUND, KIND_VBPR_NO_FP8, nrows,
+                     scores, 0, width, nullptr, nullptr, K, idx, val, flag, stream);
 }
 
 // bprx_topk for rows that are not users of the handle: row r masks the items of its own list
@@ -441,14 +446,8 @@ extern "C" int bprx_topk_lists(bprx_handle *h, int64_t nrows, float *scores, con
                                int32_t K, int32_t *idx, float *val, int32_t *flag, void *stream) {
   if (!h) return BPRX_E_INVALID;
   if (nrows < 0 || nrows >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "topk_lists: nrows = %lld out of range", (long long)nrows);
-  if (K <= 0 || K > TOPK_MAX) BPRX_FAIL(h, BPRX_E_INVALID, "topk_lists: K=%d outside [1, %d]", K, TOPK_MAX);
-  if (nrows && (!scores || !list_ptr || !list_items || !idx || !val || !flag)) BPRX_FAIL(h, BPRX_E_INVALID, "topk_lists: null pointer");
-  const int rc = bprx_enter(h, "topk_lists", 0, KIND_ANY, (hipStream_t)stream);
-  if (rc || nrows == 0) return rc;
-  hipLaunchKernelGGL(k_topk, dim3((unsigned)nrows), dim3(256), 0, (hipStream_t)stream, scores, 0, h->cfg.num_items, list_ptr,
-                     list_items, K, idx, val, flag);
-  BPRX_LAUNCH_CHECK(h, "k_topk<lists>");
-  return BPRX_OK;
+  return topk_launch(h, "topk_lists", "k_topk<lists>", nrows && (!scores || !list_ptr || !list_items || !idx || !val || !flag), 0,
+                     KIND_ANY, nrows, scores, 0, h->cfg.num_items, list_ptr, list_items, K, idx, val, flag, stream);
 }
 
 extern "C" int bprx_score_new_block(bprx_handle *h, int32_t u0, int32_t u1, const float *P, int64_t n, float *out, void *stream) {

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _ffi
+from .ranking import lists_to_csr
 
 PARAM_NAMES = ("Gu", "Gi", "Bi", "Tu", "E", "Bp")
 FACTORED_PARAM_NAMES = ("Gu", "Gi", "Bi", "Tu", "Ec", "Ee", "E", "Bp")     # GradFashion.py:182-186 (bind_factored)
@@ -229,12 +230,9 @@ class Engine:
         return self
 
     def csr(self, lists):
-        """Python lists of item ids per user -> (int64 indptr [n+1], int32 items) device tensors."""
-        lens = np.fromiter((len(l) for l in lists), dtype=np.int64, count=len(lists))
-        ptr = np.zeros(len(lists) + 1, np.int64)
-        np.cumsum(lens, out=ptr[1:])
-        items = np.fromiter((int(i) for l in lists for i in l), dtype=np.int64, count=int(ptr[-1])).astype(np.int32)
-        return (torch.as_tensor(ptr, device=self.device), torch.as_tensor(items, device=self.device))
+        """Python lists of item ids per user -> (int64 indptr [n+1], int32 items) device tensors (ranking.lists_to_csr: items is
+        never empty)."""
+        return lists_to_csr(lists, self.device)
 
     def bind_acf(self, Gu, Gi, Bi, F, Pi, weights, train_lists, eval_lists=None, slots=None, gradient="detached"):
         """ACF (bprx_bind_acf) on a BPRMF engine: F [I, M, C] feature maps (fp32, or bf16 with feat_dtype='bf16'), Pi [I, k],
@@ -275,10 +273,9 @@ class Engine:
         for n in _ffi.TABLE_FIELDS:
             setattr(tb, n, None if t.get(n) is None else t[n].data_ptr())
         ac = _ffi.Acf(M, Cf, hc, ha, _ffi.FEAT_DTYPE[self.feat_dtype], Ft.data_ptr(), self.acf_train[0].data_ptr(),
-                      self.acf_train[1].data_ptr() if self.acf_train[1].numel() else self.acf_train[0].data_ptr(),
+                      self.acf_train[1].data_ptr(),
                       None if self.acf_eval is None else self.acf_eval[0].data_ptr(),
-                      None if self.acf_eval is None else (self.acf_eval[1].data_ptr() if self.acf_eval[1].numel()
-                                                          else self.acf_eval[0].data_ptr()),
+                      None if self.acf_eval is None else self.acf_eval[1].data_ptr(),
                       t["Pi"].data_ptr(), None if t.get("m_Pi") is None else t["m_Pi"].data_ptr(),
                       None if t.get("v_Pi") is None else t["v_Pi"].data_ptr())
         for q, key in enumerate(_ffi.ACF_WEIGHTS):
@@ -308,8 +305,6 @@ class Engine:
         prebuilt `csr`; default: the bound training histories)."""
         u = as_index(users, self.device)
         ptr, items = csr if csr is not None else (self.csr(lists) if lists is not None else self.acf_train)
-        if items.numel() == 0:
-            items = torch.zeros(1, dtype=torch.int32, device=self.device)
         out = torch.empty((u.numel(), self.k), dtype=torch.float32, device=self.device)
         _ffi.check(self.h, self.lib.bprx_acf_profiles(self.h, _ptr(u), u.numel(), _ptr(ptr), _ptr(items), _ptr(out), _stream()))
         return out
@@ -325,8 +320,6 @@ class Engine:
             raise ValueError("acf_explain: %d users for %d items" % (u.numel(), i.numel()))
         ptr, hist = csr if csr is not None else (self.csr(lists) if lists is not None else getattr(self, "acf_train", None)
                                                  or self.csr([[]] * self.U))
-        if hist.numel() == 0:
-            hist = torch.zeros(1, dtype=torch.int32, device=self.device)
         n, top = u.numel(), int(top)
         shape = (n, max(top, 0))
         f = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)
@@ -543,9 +536,7 @@ class Engine:
         (idx int32 [nrows, K], val fp32 [nrows, K], flag int32 [nrows])."""
         nrows, width = (int(x) for x in scores.shape)
         K = int(K)
-        idx = torch.empty((nrows, max(K, 0)), dtype=torch.int32, device=self.device)
-        val = torch.empty((nrows, max(K, 0)), dtype=torch.float32, device=self.device)
-        flag = torch.empty(nrows, dtype=torch.int32, device=self.device)
+        idx, val, flag = self._topk_out(nrows, K)
         p = lambda t: C.c_void_p(t.data_ptr())
         _ffi.check(self.h, self.lib.bprx_topk_rows(self.h, nrows, width, p(scores), K, p(idx), p(val), p(flag), _stream()))
         return idx, val, flag
@@ -610,12 +601,8 @@ class Engine:
         """bprx_topk_lists: bprx_topk for the rows of a contiguous fp32 [nrows, I] device tensor; row r masks (IN `scores`) the
         items of list r of lists_csr = (int64 ptr [nrows + 1], int32 items): (idx int32 [nrows, K], val, flag int32 [nrows])."""
         nrows, K = int(scores.shape[0]), int(K)
-        idx = torch.empty((nrows, max(K, 0)), dtype=torch.int32, device=self.device)
-        val = torch.empty((nrows, max(K, 0)), dtype=torch.float32, device=self.device)
-        flag = torch.empty(nrows, dtype=torch.int32, device=self.device)
+        idx, val, flag = self._topk_out(nrows, K)
         ptr, items = lists_csr
-        if items.numel() == 0:                               # (every list empty: the library still wants a pointer)
-            items = torch.zeros(1, dtype=torch.int32, device=self.device)
         p = lambda t: C.c_void_p(t.data_ptr())
         _ffi.check(self.h, self.lib.bprx_topk_lists(self.h, nrows, p(scores), p(ptr), p(items), K, p(idx), p(val), p(flag), _stream()))
         return idx, val, flag
@@ -784,12 +771,16 @@ class Engine:
                                                      int(K), _ptr(out), _stream()))
         return out
 
+    def _topk_out(self, n, K):
+        """The outputs of the three top-K entries: (idx int32 [n, K], val fp32 [n, K], flag int32 [n]); K <= 0 is left to the
+        library to reject."""
+        return (torch.empty((n, max(K, 0)), dtype=torch.int32, device=self.device),
+                torch.empty((n, max(K, 0)), dtype=torch.float32, device=self.device),
+                torch.empty(n, dtype=torch.int32, device=self.device))
+
     def topk(self, u0, u1, scores, train_csr, K):
         """bprx_topk: masks the train items IN `scores` and returns (idx int32 [n,K], val fp32 [n,K], flag int32 [n])."""
-        n = u1 - u0
-        idx = torch.empty((n, K), dtype=torch.int32, device=self.device)
-        val = torch.empty((n, K), dtype=torch.float32, device=self.device)
-        flag = torch.empty(n, dtype=torch.int32, device=self.device)
+        idx, val, flag = self._topk_out(u1 - u0, int(K))
         _ffi.check(self.h, self.lib.bprx_topk(self.h, u0, u1, _ptr(scores), _ptr(train_csr[0]), _ptr(train_csr[1]), int(K),
                                               _ptr(idx), _ptr(val), _ptr(flag), _stream()))
         return idx, val, flag

@@ -18,6 +18,8 @@ from time import time
 
 import numpy as np
 
+from .ranking import lists_to_csr, rank_rows, rank_rows_host, rows_per_block, write_ranked
+
 
 def _eval_block(scores, u0, train, evl, K):
     """Rows of one user block -> list of (hr, prec, rec, auc, ndcg) tuples (users with empty eval lists skipped)."""
@@ -81,16 +83,7 @@ class Evaluator:
 
     # ---- device path (libbprx bprx_score_block + bprx_eval_users): used whenever the model runs on the engine ----
     def _device_csr(self, lists, device, dedup=False):
-        import torch
-        if dedup:       # the reference masks with set(training_list[user]) (Evaluator.py:41): a repeated row counts once
-            lists = [list(dict.fromkeys(l)) for l in lists]
-        indptr = np.zeros(len(lists) + 1, dtype=np.int64)
-        for u, l in enumerate(lists):
-            indptr[u + 1] = indptr[u] + len(l)
-        items = np.fromiter((i for l in lists for i in l), dtype=np.int32, count=int(indptr[-1]))
-        if items.size == 0:
-            items = np.zeros(1, np.int32)
-        return torch.as_tensor(indptr, device=device), torch.as_tensor(items, device=device)
+        return lists_to_csr(lists, device, dedup)
 
     def _metrics_device(self):
         import torch
@@ -159,37 +152,26 @@ class Evaluator:
         return print_results
 
     def _store_recommendation_device(self, out, block_hook=None):
-        """bprx_score_block + bprx_topk per user block; only rows whose list depends on the order of EQUAL scores (flagged
-        by the kernel: the reference's order there is numpy's unstable argsort) are redone on the host, from the row the
-        kernel has already masked.  block_hook(users, items): called once per user block with the (u, item) of the rows just
-        written, in their order."""
+        """bprx_score_block + bprx_topk per user block, listed by ranking.rank_rows (rows whose list depends on the order of
+        EQUAL scores are redone there with numpy) and written by ranking.write_ranked.  block_hook(users, items): called once
+        per user block with the (u, item) of the rows just written, in their order."""
         eng = self.model.engine
         self._metrics_device_csr()
         U = self.model.data.num_users
         for u0 in range(0, U, self.user_block):
             u1 = min(U, u0 + self.user_block)
-            sc = eng.score_block(u0, u1)
-            idx, val, flag = eng.topk(u0, u1, sc, self._csr["train"], self.k)
-            idx, val, flag = idx.cpu().numpy(), val.cpu().numpy(), flag.cpu().numpy()
-            redo = np.nonzero(flag)[0]
-            rows = {int(r): sc[int(r)].cpu().numpy() for r in redo}          # few: ties are rare in real-valued scores
-            written = ([], [])
-            for r in range(u1 - u0):
-                u = u0 + r
-                if r in rows:
-                    row = rows[r]
-                    top_k_id = row.argsort()[-self.k:][::-1]
-                    top_k_score = row[top_k_id]
-                else:
-                    kk = min(self.k, idx.shape[1], sc.shape[1])
-                    top_k_id, top_k_score = idx[r, :kk], val[r, :kk]
-                for i, value in enumerate(top_k_id):
-                    out.write(str(u) + '\t' + str(value) + '\t' + str(top_k_score[i]) + '\n')
-                if block_hook is not None:
-                    written[0].extend([u] * len(top_k_id))
-                    written[1].extend(int(v) for v in top_k_id)
-            if block_hook is not None and written[0]:
-                block_hook(*written)
+            ids, vals, _ = rank_rows(self._topk(u0, u1), eng.score_block(u0, u1), self.k)
+            self._write_block(out, range(u0, u1), ids, vals, None, block_hook)
+
+    def _topk(self, u0, u1):
+        """bprx_topk over the users [u0, u1) with their train items masked, as ranking.rank_rows calls it."""
+        return lambda scores, k: self.model.engine.topk(u0, u1, scores, self._csr["train"], k)
+
+    @staticmethod
+    def _write_block(out, labels, ids, vals, side, block_hook):
+        written = write_ranked(out, labels, ids, vals, side)
+        if block_hook is not None and written[0]:
+            block_hook(*written)
 
     def _metrics_device_csr(self):
         if getattr(self, "_csr", None) is None:
@@ -213,20 +195,9 @@ class Evaluator:
             self._store_recommendation_device(out, block_hook)
             return
         for u0, sc in self._score_blocks():
-            written = ([], [])
-            for r in range(sc.shape[0]):
-                u = u0 + r
-                row = sc[r]
-                row[self.data.training_list[u]] = -np.inf
-                top_k_id = row.argsort()[-self.k:][::-1]
-                top_k_score = row[top_k_id]
-                for i, value in enumerate(top_k_id):
-                    out.write(str(u) + '\t' + str(value) + '\t' + str(top_k_score[i]) + '\n')
-                if block_hook is not None:
-                    written[0].extend([u] * len(top_k_id))
-                    written[1].extend(int(v) for v in top_k_id)
-            if block_hook is not None and written[0]:
-                block_hook(*written)
+            u1 = u0 + sc.shape[0]
+            ids, vals = rank_rows_host(sc, self.data.training_list[u0:u1], self.k)
+            self._write_block(out, range(u0, u1), ids, vals, None, block_hook)
 
     def _write_feature_rows(self, ex, users, items, top):
         """The expl-* rows of VBPR and GradFashion for the pairs (users, items), one bprx_feat_explain call:
@@ -259,9 +230,7 @@ class Evaluator:
                 u1 = min(U, u0 + self.user_block)
                 res = m.recommend_new(F, self.k, u0, u1, explain=top if ex is not None else 0)
                 idx, val = res[0], res[1]
-                for r in range(u1 - u0):
-                    for q in range(idx.shape[1]):
-                        out.write(str(u0 + r) + '\t' + str(idx[r, q]) + '\t' + str(val[r, q]) + '\n')
+                write_ranked(out, range(u0, u1), idx, val)
                 if ex is None or not idx.size:
                     continue
                 e, kk = res[2], idx.shape[1]
@@ -298,45 +267,23 @@ class Evaluator:
     def store_recommendation_attention(self, path=""):
         """Evaluator.py:241-259 (AttentiveFashion): the top-k rows 'u\\titem\\tscore\\talpha_colour\\talpha_edges\\talpha_class'.
         Scores and attentions come from one bprx_af_score_block call per user block; the top-k and the gather of its
-        attentions run on the device, rows whose order depends on equal scores are redone on the host as in
-        store_recommendation."""
+        attentions run on the device, rows whose order depends on equal scores are redone on the host
+        (ranking.rank_rows, the attentions as its `side`)."""
         with open(path, 'w') as out:
             self._store_attention_rows(out)
 
     def _store_attention_rows(self, out, block_hook=None):
         """The rows of store_recommendation_attention; block_hook(users, items) is called once per user block with the rows
         just written, in their order."""
-        import torch
         eng = self.model.engine
         self._metrics_device_csr()
         U, I = self.model.data.num_users, self.model.data.num_items
-        blk = max(1, min(self.user_block, (1 << 27) // max(1, I)))
+        blk = rows_per_block(self.user_block, I)
         for u0 in range(0, U, blk):
-            written = ([], [])
             u1 = min(U, u0 + blk)
             sc, al = eng.af_score_block(u0, u1)
-            idx, val, flag = eng.topk(u0, u1, sc, self._csr["train"], self.k)
-            kk = min(self.k, idx.shape[1], I)
-            pick = idx[:, :kk].long().clamp_(0, I - 1).unsqueeze(-1).expand(-1, -1, 3)
-            att = torch.gather(al, 1, pick).cpu().numpy()
-            idx, val, flag = idx.cpu().numpy(), val.cpu().numpy(), flag.cpu().numpy()
-            for r in range(u1 - u0):
-                u = u0 + r
-                if flag[r]:
-                    row = sc[r].cpu().numpy()
-                    top_k_id = row.argsort()[-self.k:][::-1]
-                    top_k_score = row[top_k_id]
-                    a = al[r].cpu().numpy()[top_k_id]
-                else:
-                    top_k_id, top_k_score, a = idx[r, :kk], val[r, :kk], att[r]
-                for i, value in enumerate(top_k_id):
-                    out.write(str(u) + '\t' + str(value) + '\t' + str(top_k_score[i]) + '\t' + str(a[i, 0]) + '\t' +
-                              str(a[i, 1]) + '\t' + str(a[i, 2]) + '\n')
-                if block_hook is not None:
-                    written[0].extend([u] * len(top_k_id))
-                    written[1].extend(int(v) for v in top_k_id)
-            if block_hook is not None and written[0]:
-                block_hook(*written)
+            ids, vals, att = rank_rows(self._topk(u0, u1), sc, self.k, side=al)
+            self._write_block(out, range(u0, u1), ids, vals, att, block_hook)
 
     def store_recommendation_attention_explain(self, path_recs="", path_expl="", grid=14):
         """AttentiveFashion: `path_recs` exactly as store_recommendation_attention writes it, and for every row written there one row

@@ -19,6 +19,7 @@ import torch
 from . import configs
 from .engine import Engine, as_index
 from .evaluator import Evaluator
+from .ranking import rank_rows, rows_per_block, write_ranked
 from .synth import glorot_uniform
 
 
@@ -66,6 +67,17 @@ def draw_fold_pairs(histories, num_items, negatives, seed):
         ptr[r + 1] = ptr[r] + need
     cat = lambda parts: (np.concatenate(parts) if parts else np.zeros(0, np.int64)).astype(np.int32)
     return ptr, cat(pos), cat(neg)
+
+
+def fold_start_rows(x, n, w, device):
+    """The rows a fold-in starts from: zeros [n, w] for x = None, else a contiguous fp32 device copy of x (tensor or array)
+    shaped [n, w]; None for a table the model does not have (w == 0)."""
+    if w == 0:
+        return None
+    if x is None:
+        return torch.zeros((n, w), dtype=torch.float32, device=device)
+    return torch.as_tensor(np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(n, w),
+                           device=device).contiguous().clone()
 
 
 class RecommenderModel:
@@ -274,57 +286,59 @@ class BPRMF(RecommenderModel):
         eng = self.engine
         n = len(histories)
         ptr, pos, neg = draw_fold_pairs(histories, self.num_items, negatives, seed)
-        def rows(x, w):
-            if w == 0:
-                return None
-            if x is None:
-                return torch.zeros((n, w), dtype=torch.float32, device=eng.device)
-            return torch.as_tensor(np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(n, w),
-                                   device=eng.device).contiguous().clone()
         g0, t0 = (None, None) if init is None else init
-        Gu, Tu = rows(g0, eng.k), rows(t0, eng.d)
+        Gu, Tu = fold_start_rows(g0, n, eng.k, eng.device), fold_start_rows(t0, n, eng.d, eng.device)
         eng.fold_in(ptr, pos, neg, steps, Gu, Tu, lr=self.learning_rate if lr is None else lr, reg=self.reg if reg is None else reg,
                     optimizer=self.optimizer_name if optimizer is None else optimizer, want_loss=False)
         return Gu, Tu
 
+    def _score_fold_rows(self, rows, r0, r1):
+        """(scores [r1 - r0, I], side [r1 - r0, I, c] or None) of rows [r0, r1) of what fold_in_users returned."""
+        return self.engine.score_rows_block(rows[0], rows[1], r0, r1), None
+
     def recommend_new_users(self, histories, k=None, **fold):
-        """The k (default top_k) best catalogue items of every new user, their own histories masked: numpy idx int [n, min(k, I)]
-        and val, best first.  The rows are fitted by fold_in_users(histories, **fold), scored in row blocks and ranked on the
-        device; rows whose list depends on the order of equal scores are redone with numpy on the GPU's (masked) row, as
-        Evaluator.store_recommendation does."""
+        """The k (default top_k) best catalogue items of every new user, their own histories masked: numpy idx int [n, kk] and
+        val [n, kk], kk = min(k, I), best first; a model whose scores come with attentions (AttentiveFashion) also returns alpha
+        [n, kk, 3] (colour, edges, class).  The rows are fitted by fold_in_users(histories, **fold), scored in row blocks and
+        listed by ranking.rank_rows: on the device, rows whose list depends on the order of equal scores redone with numpy on the
+        GPU's (masked) row."""
         eng = self.engine
         n, I = len(histories), self.num_items
         k = self.evaluator.k if k is None else int(k)
-        kk = min(k, I)
-        Gu, Tu = self.fold_in_users(histories, **fold)
-        idx_all, val_all = np.zeros((n, kk), np.int64), np.zeros((n, kk), np.float32)
-        blk = max(1, min(self.evaluator.user_block, (1 << 27) // max(1, I)))
+        rows = self.fold_in_users(histories, **fold)
+        blk = rows_per_block(self.evaluator.user_block, I)
+        parts = []
         for b0 in range(0, n, blk):
             b1 = min(n, b0 + blk)
-            sc = eng.score_rows_block(Gu, Tu, b0, b1)
-            idx, val, flag = (x.cpu().numpy() for x in eng.topk_lists(sc, eng.csr(histories[b0:b1]), k))
-            idx_all[b0:b1], val_all[b0:b1] = idx[:, :kk], val[:, :kk]
-            for r in np.nonzero(flag)[0]:
-                row = sc[int(r)].cpu().numpy()
-                top_k_id = row.argsort()[-k:][::-1]
-                idx_all[b0 + r], val_all[b0 + r] = top_k_id, row[top_k_id]
-        return idx_all, val_all
+            sc, side = self._score_fold_rows(rows, b0, b1)
+            parts.append(rank_rows(lambda s, kq: eng.topk_lists(s, eng.csr(histories[b0:b1]), kq), sc, k, side))
+        return _stack_blocks(parts, min(k, I), self.new_users_side)
+
+    new_users_param = "new_users"                                # the params entry that names the new users' file
+    new_users_side = 0                                           # columns of the side _score_fold_rows returns; 0: none
 
     def _store_new_user_recs(self, path):
-        """params.new_users: new-user-recs-* next to the recs-* file at `path`, rows 'label\ti\tscore', best first."""
-        src = getattr(self.params, "new_users", None)
+        """params.new_users (AttentiveFashion: params.af_new_users): new-user-recs-* next to the recs-* file at `path`, rows
+        'label\ti\tscore' (AttentiveFashion: + '\talpha_colour\talpha_edges\talpha_class'), best first, one block per label
+        in file order."""
+        src = getattr(self.params, self.new_users_param, None)
         if not src:
             return
         from .train_rec import read_new_users
         labels, lists = read_new_users(src)
         d, f = os.path.split(path)
-        idx, val = self.recommend_new_users(lists, steps=getattr(self.params, "fold_steps", 30),
-                                            negatives=getattr(self.params, "fold_negatives", 4),
-                                            seed=getattr(self.params, "init_seed", 0))
+        res = self.recommend_new_users(lists, steps=getattr(self.params, "fold_steps", 30),
+                                       negatives=getattr(self.params, "fold_negatives", 4),
+                                       seed=getattr(self.params, "init_seed", 0))
         with open(os.path.join(d, f.replace("recs-", "new-user-recs-", 1)), 'w') as out:
-            for r, label in enumerate(labels):
-                for q in range(idx.shape[1]):
-                    out.write(label + '\t' + str(idx[r, q]) + '\t' + str(val[r, q]) + '\n')
+            write_ranked(out, labels, *res)
+
+
+def _stack_blocks(parts, kk, c=0):
+    """The per-block (ids, vals, side) of ranking.rank_rows as whole arrays: (ids int64 [n, kk], vals fp32 [n, kk]) and, for
+    blocks with a side of c > 0 columns, side fp32 [n, kk, c]."""
+    parts = [(np.zeros((0, kk), np.int64), np.zeros((0, kk), np.float32), np.zeros((0, kk, c), np.float32))] + parts
+    return tuple(np.concatenate(p) for p in list(zip(*parts))[:3 if c else 2])
 
 
 def _table_property(name):
@@ -452,8 +466,8 @@ class VBPR(BPRMF):
 
     def recommend_new(self, features, k=None, u0=0, u1=None, explain=0):
         """The k (default top_k) best new items of every user of [u0, u1): numpy idx int [nu, min(k, n)] (row of `features`) and val,
-        best first; explain = L > 0: also the Engine.feat_explain_new dict (numpy) of those pairs, user by user.  Rows whose list
-        depends on the order of equal scores are redone with numpy on the GPU's row, as Evaluator.store_recommendation does."""
+        best first; explain = L > 0: also the Engine.feat_explain_new dict (numpy) of those pairs, user by user.  Listed block by
+        block by ranking.rank_rows (rows whose list depends on the order of equal scores: numpy on the GPU's row)."""
         eng = self.engine
         F = self._as_new_table(features)
         n = int(F.shape[0])
@@ -461,17 +475,9 @@ class VBPR(BPRMF):
         u1 = self.num_users if u1 is None else u1
         P = eng.project_rows(F)
         kk = min(k, n)
-        idx_all, val_all = np.zeros((u1 - u0, kk), np.int64), np.zeros((u1 - u0, kk), np.float32)
-        blk = max(1, min(self.evaluator.user_block, (1 << 27) // max(1, n)))
-        for b0 in range(u0, u1, blk):
-            b1 = min(u1, b0 + blk)
-            sc = eng.score_new_block(b0, b1, P)
-            idx, val, flag = (x.cpu().numpy() for x in eng.topk_rows(sc, k))
-            idx_all[b0 - u0:b1 - u0], val_all[b0 - u0:b1 - u0] = idx[:, :kk], val[:, :kk]
-            for r in np.nonzero(flag)[0]:
-                row = sc[int(r)].cpu().numpy()
-                top_k_id = row.argsort()[-k:][::-1]
-                idx_all[b0 - u0 + r], val_all[b0 - u0 + r] = top_k_id, row[top_k_id]
+        blk = rows_per_block(self.evaluator.user_block, n)
+        parts = [rank_rows(eng.topk_rows, eng.score_new_block(b0, min(u1, b0 + blk), P), k) for b0 in range(u0, u1, blk)]
+        idx_all, val_all = _stack_blocks(parts, kk)
         if explain <= 0:
             return idx_all, val_all
         users = np.repeat(np.arange(u0, u1), kk)
@@ -999,60 +1005,15 @@ class AttentiveFashion(BPRMF):
         eng = self.engine
         n = len(histories)
         ptr, pos, neg = draw_fold_pairs(histories, self.num_items, negatives, seed)
-        if init is None:
-            Gu = torch.zeros((n, eng.k), dtype=torch.float32, device=eng.device)
-        else:
-            Gu = torch.as_tensor(np.asarray(init.detach().cpu() if isinstance(init, torch.Tensor) else init, dtype=np.float32)
-                                 .reshape(n, eng.k), device=eng.device).contiguous().clone()
+        Gu = fold_start_rows(init, n, eng.k, eng.device)
         eng.af_fold_in(ptr, pos, neg, steps, Gu, lr=self.learning_rate if lr is None else lr, reg=self.reg if reg is None else reg,
                        optimizer=self.optimizer_name if optimizer is None else optimizer, want_loss=False)
         return Gu
 
-    def recommend_new_users(self, histories, k=None, **fold):
-        """The k (default top_k) best catalogue items of every new user, their own histories masked: numpy idx int [n, kk], val
-        [n, kk] and alpha [n, kk, 3] (colour, edges, class), kk = min(k, I), best first.  The rows are fitted by
-        fold_in_users(histories, **fold), scored in row blocks and ranked on the device; rows whose list depends on the order of
-        equal scores are redone with numpy on the GPU's (masked) row, as BPRMF.recommend_new_users does."""
-        eng = self.engine
-        n, I = len(histories), self.num_items
-        k = self.evaluator.k if k is None else int(k)
-        kk = min(k, I)
-        Gu = self.fold_in_users(histories, **fold)
-        idx_all, val_all = np.zeros((n, kk), np.int64), np.zeros((n, kk), np.float32)
-        al_all = np.zeros((n, kk, 3), np.float32)
-        blk = max(1, min(self.evaluator.user_block, (1 << 27) // max(1, I)))
-        for b0 in range(0, n, blk):
-            b1 = min(n, b0 + blk)
-            sc, al = eng.af_score_rows_block(Gu, b0, b1)
-            idx, val, flag = eng.topk_lists(sc, eng.csr(histories[b0:b1]), k)
-            pick = idx[:, :kk].long().clamp_(0, I - 1).unsqueeze(-1).expand(-1, -1, 3)
-            al_all[b0:b1] = torch.gather(al, 1, pick).cpu().numpy()
-            idx, val, flag = idx.cpu().numpy(), val.cpu().numpy(), flag.cpu().numpy()
-            idx_all[b0:b1], val_all[b0:b1] = idx[:, :kk], val[:, :kk]
-            for r in np.nonzero(flag)[0]:
-                row = sc[int(r)].cpu().numpy()
-                top_k_id = row.argsort()[-k:][::-1]
-                idx_all[b0 + r], val_all[b0 + r] = top_k_id, row[top_k_id]
-                al_all[b0 + r] = al[int(r)].cpu().numpy()[top_k_id]
-        return idx_all, val_all, al_all
+    def _score_fold_rows(self, rows, r0, r1):
+        return self.engine.af_score_rows_block(rows, r0, r1)
 
-    def _store_new_user_recs(self, path):
-        """params.af_new_users: new-user-recs-* next to the recs-* file at `path`, rows
-        'label\ti\tscore\talpha_colour\talpha_edges\talpha_class', best first, one block per label in file order."""
-        src = getattr(self.params, "af_new_users", None)
-        if not src:
-            return
-        from .train_rec import read_new_users
-        labels, lists = read_new_users(src)
-        d, f = os.path.split(path)
-        idx, val, al = self.recommend_new_users(lists, steps=getattr(self.params, "fold_steps", 30),
-                                                negatives=getattr(self.params, "fold_negatives", 4),
-                                                seed=getattr(self.params, "init_seed", 0))
-        with open(os.path.join(d, f.replace("recs-", "new-user-recs-", 1)), 'w') as out:
-            for r, label in enumerate(labels):
-                for q in range(idx.shape[1]):
-                    out.write(label + '\t' + str(idx[r, q]) + '\t' + str(val[r, q]) + '\t' + str(al[r, q, 0]) + '\t' +
-                              str(al[r, q, 1]) + '\t' + str(al[r, q, 2]) + '\n')
+    new_users_param, new_users_side = "af_new_users", 3
 
     def _store_recs(self, path):
         """recs-* / best-recs-* with the attentions; with params.af_explain = G > 0 also expl-* / best-expl-* next to them."""

@@ -1,0 +1,87 @@
+"""The one place where score rows become top-K lists and lists become rows of text: every recs-* / new-recs-* /
+new-user-recs-* file, single GPU or sharded, catalogue items or new ones, is ranked and written here.
+
+The contract is the reference's (Evaluator.py:225-239): mask the row, then take numpy_topk of it; numpy's unstable argsort
+decides the order of EQUAL scores.  The top-K kernel returns the list wherever it does not depend on that order and flags
+every other row (include/bprx.h, bprx_topk); a flagged row is redone by numpy_topk on the row the kernel has masked.
+Plain numpy + torch: no library call is made here, the caller brings the top-K entry as a callable.
+"""
+import numpy as np
+import torch
+
+
+def numpy_topk(row, k):
+    """The reference's list of one masked score row, best first (Evaluator.py:234)."""
+    return row.argsort()[-k:][::-1]
+
+
+def rows_per_block(user_block, width):
+    """Rows of `width` scores per block: user_block, cut so that one block's scores stay below 2^27 elements."""
+    return max(1, min(user_block, (1 << 27) // max(1, width)))
+
+
+def lists_to_csr(lists, device, dedup=False):
+    """Python lists of item ids per row -> (int64 ptr [n + 1], int32 items) tensors on `device`.  dedup: a repeated id counts
+    once, the first time (the reference masks with set(training_list[user]), Evaluator.py:41).  `items` is never empty (one
+    zero when every list is: a kernel is handed a pointer it does not read); counts come from ptr[-1]."""
+    if dedup:
+        lists = [list(dict.fromkeys(l)) for l in lists]
+    lens = np.fromiter((len(l) for l in lists), dtype=np.int64, count=len(lists))
+    ptr = np.zeros(len(lists) + 1, np.int64)
+    np.cumsum(lens, out=ptr[1:])
+    items = np.fromiter((int(i) for l in lists for i in l), dtype=np.int64, count=int(ptr[-1])).astype(np.int32)
+    if items.size == 0:
+        items = np.zeros(1, np.int32)
+    return torch.as_tensor(ptr, device=device), torch.as_tensor(items, device=device)
+
+
+def rank_rows(topk, scores, k, side=None):
+    """The lists of a block of device score rows [n, width]: numpy ids int64 [n, kk], vals fp32 [n, kk], kk = min(k, width),
+    best first, and side_rows [n, kk, c] (None without `side`).  topk(scores, k) is the top-K entry: it masks IN `scores` and
+    returns the device (idx, val, flag).  Unflagged rows are the kernel's; a flagged row is downloaded (masked) and redone by
+    numpy_topk, its kernel output is not read.  side: a device tensor [n, width, c] gathered at the final ids (the
+    AttentiveFashion attentions).  One download of idx / val / flag (and of the gathered side) per call, one row per flagged row."""
+    width = int(scores.shape[1])
+    kk = min(k, width)
+    idx, val, flag = topk(scores, k)
+    side_rows = None
+    if side is not None:
+        pick = idx[:, :kk].long().clamp_(0, width - 1).unsqueeze(-1).expand(-1, -1, side.shape[2])
+        side_rows = torch.gather(side, 1, pick).cpu().numpy()
+    idx, val, flag = idx.cpu().numpy(), val.cpu().numpy(), flag.cpu().numpy()
+    ids, vals = idx[:, :kk].astype(np.int64), val[:, :kk].copy()
+    for r in np.nonzero(flag)[0]:                             # few: ties are rare in real-valued scores
+        row = scores[int(r)].cpu().numpy()
+        ids[r] = numpy_topk(row, k)
+        vals[r] = row[ids[r]]
+        if side is not None:
+            side_rows[r] = side[int(r)].cpu().numpy()[ids[r]]
+    return ids, vals, side_rows
+
+
+def rank_rows_host(scores, mask_lists, k):
+    """rank_rows on the host: row r of the numpy block `scores` gets -inf (IN `scores`) at mask_lists[r] (None: nothing is
+    masked) and is listed by numpy_topk.  Returns (ids int64 [n, kk], vals [n, kk])."""
+    n, width = scores.shape
+    ids = np.empty((n, len(range(width)[-k:])), np.int64)     # (the length of numpy_topk's slice)
+    for r in range(n):
+        row = scores[r]
+        if mask_lists is not None:
+            row[mask_lists[r]] = -np.inf
+        ids[r] = numpy_topk(row, k)
+    return ids, np.take_along_axis(scores, ids, axis=1)
+
+
+def write_ranked(out, labels, ids, vals, side=None):
+    """One row 'label\\tid\\tval[\\tside_0 ...]' per list entry, list by list, each field the str() of its numpy scalar (vals
+    and side stay float32: the text of a float depends on its type).  Returns (labels, items) of the rows written, one entry
+    per row, as a block_hook takes them."""
+    users, items = [], []
+    for r, label in enumerate(labels):
+        head = str(label) + '\t'
+        for q, item in enumerate(ids[r]):
+            tail = '' if side is None else ''.join('\t' + str(a) for a in side[r, q])
+            out.write(head + str(item) + '\t' + str(vals[r, q]) + tail + '\n')
+        users.extend([label] * len(ids[r]))
+        items.extend(int(v) for v in ids[r])
+    return users, items

@@ -29,6 +29,7 @@ import torch.distributed as dist
 
 from . import configs
 from .dist import all_gather_into, all_reduce
+from .ranking import rank_rows, rank_rows_host, write_ranked
 from .synth import glorot_uniform
 
 EVAL_MAX = 32                       # held-out items per user that the device evaluation kernels take (EVMAX, bprx_eval.hip)
@@ -299,12 +300,7 @@ class ShardedVBPR(_ShardedModel):
                 sc = self.predict_block(u0, u1)
                 if self.rank != 0:
                     continue
-                for r in range(sc.shape[0]):
-                    u, row = u0 + r, sc[r]
-                    row[self.data.training_list[u]] = -np.inf
-                    top_k_id = row.argsort()[-K:][::-1]
-                    for i, value in enumerate(top_k_id):
-                        out.write(str(u) + '\t' + str(value) + '\t' + str(row[top_k_id][i]) + '\n')
+                write_ranked(out, range(u0, u1), *rank_rows_host(sc, self.data.training_list[u0:u1], K))
         finally:
             if out is not None:
                 out.close()
@@ -420,27 +416,17 @@ class ShardedBPRMF(_ShardedModel):
         return out if self.rank == 0 else None
 
     def store_recommendation(self, path):
-        """Evaluator.py:225-239: every rank lists the top-k of ITS users (device top-K; rows that hinge on ties redone with numpy
-        exactly as the single-GPU evaluator does), rank 0 writes the ranks' lines in user order."""
+        """Evaluator.py:225-239: every rank lists the top-k of ITS users (ranking.rank_rows over the device top-K, exactly as the
+        single-GPU evaluator does), rank 0 writes the ranks' lines in user order."""
         self._gather_items()
-        K, nu, lines = self.params.top_k, self.u1 - self.u0, []
+        K, nu, lines = self.params.top_k, self.u1 - self.u0, io.StringIO()
         for b0 in range(0, max(nu, 0), 4096):
             b1 = min(nu, b0 + 4096)
-            sc = self.ev_eng.score_block(b0, b1)
-            idx, val, flag = self.ev_eng.topk(b0, b1, sc, self._csr["train"], K)
-            idx, val, flag = idx.cpu().numpy(), val.cpu().numpy(), flag.cpu().numpy()
-            for r in range(b1 - b0):
-                u = self.u0 + b0 + r
-                if flag[r]:
-                    row = sc[r].cpu().numpy()
-                    ids = row.argsort()[-K:][::-1]
-                    vals = row[ids]
-                else:
-                    kk = min(K, idx.shape[1], sc.shape[1])
-                    ids, vals = idx[r, :kk], val[r, :kk]
-                lines += [str(u) + '\t' + str(v) + '\t' + str(vals[q]) + '\n' for q, v in enumerate(ids)]
+            topk = lambda sc, k: self.ev_eng.topk(b0, b1, sc, self._csr["train"], k)
+            ids, vals, _ = rank_rows(topk, self.ev_eng.score_block(b0, b1), K)
+            write_ranked(lines, range(self.u0 + b0, self.u0 + b1), ids, vals)
         parts = [None] * self.world
-        dist.all_gather_object(parts, "".join(lines), group=self.group)
+        dist.all_gather_object(parts, lines.getvalue(), group=self.group)
         if self.rank == 0:
             with open(path, 'w') as f:
                 f.write("".join(parts))

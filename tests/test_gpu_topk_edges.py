@@ -137,3 +137,102 @@ def test_metrics_device_equal_host_with_32_and_33_held_out_items(most):
     assert set(got) == set(want) and len(want) == 10
     for k in want:
         assert got[k] == pytest.approx(want[k], abs=1e-12), k
+
+
+# ---- every device entry that lists a top-K against ranking.rank_rows_host of the same matrix ----------------------------------------
+def _params(rec, K):
+    return Namespace(dataset="toy", validation=True, batch_size=64, epochs=1, batch_eval=128, embed_k=4, embed_d=4, lr=0.05,
+                     reg=1e-3, top_k=K, verbose=-1, restore_epochs=1, rec=rec, best_metric="ndcg", optimizer="sgd", init_seed=5,
+                     dtype="fp32")
+
+
+def _lists_store_recommendation(tmp_path, data, sc, train, K):
+    ev = Evaluator(_ScoreModel(data, sc), data, K, user_block=16)
+    ev.store_recommendation(str(tmp_path / "recs.tsv"))
+    rows = [l.split("\t") for l in (tmp_path / "recs.tsv").read_text().splitlines()]
+    kk = min(K, I_E)
+    assert [int(r[0]) for r in rows] == [u for u in range(U_E) for _ in range(kk)]
+    ids = np.array([int(r[1]) for r in rows]).reshape(U_E, kk)
+    vals = np.array([np.float32(r[2]) for r in rows], np.float32).reshape(U_E, kk)      # (str of a float32 round-trips)
+    return ev.model.engine, ids, vals, train
+
+
+def _lists_new_users(tmp_path, data, sc, train, K):
+    from fashionvisualexpl_recommend_amd.models import BPRMF
+    m = BPRMF(data, _params("bprmf", K))
+    S = torch.as_tensor(sc, device="cuda")
+    m.evaluator.user_block = 16
+    m.fold_in_users = lambda histories, **fold: (torch.zeros((len(histories), 4), dtype=torch.float32, device="cuda"), None)
+    m.engine.score_rows_block = lambda Gu, Tu, r0, r1, out=None: S[r0:r1].clone()
+    ids, vals = m.recommend_new_users(train)                   # the histories are the matrix's train lists: masked
+    return m.engine, ids, vals, train
+
+
+def _lists_new_items(tmp_path, data, sc, train, K):
+    from fashionvisualexpl_recommend_amd import synth
+    from fashionvisualexpl_recommend_amd.models import VBPR
+    m = VBPR(data, _params("vbpr", K), features=synth.make_features(I_E, 32, seed=40))
+    S = torch.as_tensor(sc, device="cuda")
+    m.evaluator.user_block = 16
+    m.engine.score_new_block = lambda u0, u1, P, out=None: S[u0:u1].clone()
+    ids, vals = m.recommend_new(synth.make_features(I_E, 32, seed=41))       # 300 new items: the matrix's columns, nothing masked
+    return m.engine, ids, vals, None
+
+
+@pytest.mark.parametrize("K", [5, 400])
+@pytest.mark.parametrize("entry", [_lists_store_recommendation, _lists_new_users, _lists_new_items],
+                         ids=["store_recommendation", "recommend_new_users", "recommend_new"])
+def test_every_device_entry_lists_as_rank_rows_host(tmp_path, entry, K):
+    from fashionvisualexpl_recommend_amd.ranking import rank_rows_host
+    data, sc, train, _ = _eval_data(lambda u: 1)
+    eng, ids, vals, masks = entry(tmp_path, data, sc, train, K)
+    eng.sync_check()
+    eng.close()
+    wid, wval = rank_rows_host(sc.copy(), masks, K)
+    assert ids.shape == wid.shape == (U_E, min(K, I_E))
+    bits = lambda a: np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    assert np.array_equal(ids, wid)
+    assert np.array_equal(bits(vals), bits(wval))
+
+
+class _ExplainedScoreModel(_ScoreModel):
+    """_ScoreModel with the explain surfaces of VBPR (model.explain) and ACF (engine.acf_explain) stubbed: each records the
+    (users, items) it is called with and explains nothing."""
+
+    def __init__(self, data, scores):
+        super().__init__(data, scores)
+        self.calls = []
+        self.engine.acf_train = self.engine.acf_eval = None
+        self.engine.acf_explain = self._acf_explain
+
+    def explain(self, users, items, top):
+        self.calls.append((list(users), list(items)))
+        n = len(users)
+        return {"score": np.zeros(n, np.float32), "base": np.zeros(n, np.float32), "col": np.zeros((n, 0), np.int32),
+                "contrib": np.zeros((n, 0), np.float32)}
+
+    def _acf_explain(self, users, items, top=5, lists=None, csr=None, maps=False):
+        self.calls.append((list(users), list(items)))
+        n = len(users)
+        return {"score": torch.zeros(n), "base": torch.zeros(n), "pos": torch.full((n, 1), -1, dtype=torch.int32)}
+
+
+@pytest.mark.parametrize("K", [5, 400])
+@pytest.mark.parametrize("writer", ["store_recommendation_acf", "store_recommendation_features"])
+def test_explain_writers_receive_the_rec_files_pairs_block_by_block(tmp_path, writer, K):
+    data, sc, _, _ = _eval_data(lambda u: 1)
+    m = _ExplainedScoreModel(data, sc)
+    ev = Evaluator(m, data, K, user_block=16)
+    recs, expl, plain = tmp_path / "recs.tsv", tmp_path / "expl.tsv", tmp_path / "plain.tsv"
+    getattr(ev, writer)(str(recs), str(expl), 3)
+    ev.store_recommendation(str(plain))
+    m.engine.sync_check()
+    m.engine.close()
+    assert recs.read_bytes() == plain.read_bytes()             # the rec file does not know that it is explained
+    rows = [l.split("\t") for l in recs.read_text().splitlines()]
+    kk = min(K, I_E)
+    assert len(rows) == U_E * kk
+    assert [len(c[0]) for c in m.calls] == [16 * kk, 16 * kk, 8 * kk]          # one call per user block, the short last one included
+    assert all(type(x) is int for c in m.calls for x in c[0][:3] + c[1][:3])
+    assert [u for c in m.calls for u in c[0]] == [int(r[0]) for r in rows]
+    assert [i for c in m.calls for i in c[1]] == [int(r[1]) for r in rows]
