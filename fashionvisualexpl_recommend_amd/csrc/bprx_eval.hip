@@ -113,6 +113,74 @@ __global__ __launch_bounds__(256) void k_score_new_gemm(const float *__restrict_
   }
 }
 
+// ---- similar items (include/bprx.h): cosine of item vectors z = [Gi | P[0:d]] (either part may be absent) ----
+// One part of z: n rows of `w` floats, row stride ld (w == 0: the part is absent).
+struct SimPart {
+  const float *p;
+  int w, ld;
+};
+
+constexpr int RN_LANES = 16;   // lanes per row of k_sim_rnorm: 4 rows per wave, 16 per workgroup
+
+// rn[r] = 1 / sqrt(sum_x z_rx^2), 0 for a zero row.  16 lanes load 16 consecutive x of a row (one 64-byte segment) and square
+// them; every lane of the group then adds the 16 squares in ascending x (read by lane index), so the fp32 sum is the serial
+// ascending-x sum of the row: s = (..((z_0^2 + z_1^2) + z_2^2)..), each product and each sum rounded once (no fma).  Columns
+// past the width add +0.  No atomics; the loop bounds are the same for every lane (rows past n are clamped and not written).
+__global__ __launch_bounds__(256) void k_sim_rnorm(SimPart a, SimPart b, int n, float *__restrict__ rn) {
+  const int lane = threadIdx.x & 63, l = lane & (RN_LANES - 1), g0 = lane & ~(RN_LANES - 1);
+  const int64_t row = (int64_t)blockIdx.x * (256 / RN_LANES) + (threadIdx.x / RN_LANES);
+  const size_t rr = (size_t)(row < n ? row : n - 1);
+  float s = 0.f;
+#pragma unroll
+  for (int part = 0; part < 2; ++part) {
+    const SimPart z = part ? b : a;
+    for (int c0 = 0; c0 < z.w; c0 += RN_LANES) {
+      const int x = c0 + l;
+      const float v = x < z.w ? z.p[rr * z.ld + x] : 0.f;
+      const float sq = __fmul_rn(v, v);
+#pragma unroll
+      for (int j = 0; j < RN_LANES; ++j) s = __fadd_rn(s, __shfl(sq, g0 + j));
+    }
+  }
+  if (row < n && l == 0) rn[row] = s > 0.f ? 1.f / sqrtf(s) : 0.f;
+}
+
+// out[q - q0][j] = <z_q, z_j> (rn_q[q] rn_items[j]) for the queries q in [q0, q1) against every catalogue item j: the tiles, the
+// phases and the C/D map of k_score_gemm, one gemm_phase per part of z (any width >= 1: gemm_phase pads with zeros).  A holds
+// the query rows (the catalogue's own tables, or the caller's projected rows), B the catalogue.  Products are exact fp32 and the
+// sums k-ordered from +0, so <z_q, z_j> has the bits of <z_j, z_q>, and an element depends on its two rows and its two norms only.
+__global__ __launch_bounds__(256) void k_sim_gemm(SimPart a0, SimPart a1, SimPart b0, SimPart b1, int I, int q0, int q1,
+                                                  const float *__restrict__ rn_q, const float *__restrict__ rn_items,
+                                                  float *__restrict__ out) {
+  __shared__ float As[TM][GLD];
+  __shared__ float Bs[TN][GLD];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wr = w >> 1, wc = w & 1;
+  const int i0 = blockIdx.x * TN, qb = q0 + blockIdx.y * TM;
+  const int arows = min(TM, q1 - qb), brows = min(TN, I - i0);
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+  if (a0.w) gemm_phase(a0.p, a0.ld, qb, arows, b0.p, b0.ld, i0, brows, a0.w, As, Bs, acc, wr, wc, lane);
+  if (a1.w) gemm_phase(a1.p, a1.ld, qb, arows, b1.p, b1.ld, i0, brows, a1.w, As, Bs, acc, wr, wc, lane);
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+    const int ic = i0 + wc * 64 + b * 32 + (lane & 31);
+    if (ic >= I) continue;
+    const float rj = rn_items[ic];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int qr = qb + wr * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (qr < q1) out[(size_t)(qr - q0) * I + ic] = __fmul_rn(acc[a][b][r], __fmul_rn(rn_q[qr], rj));   // norms first: symmetric
+      }
+  }
+}
+
 constexpr int EVMAX = 32;   // held-out items per user handled on the device (the reference's split holds out 1)
 
 // One workgroup per user.  out[5] = hr, prec, rec, auc, ndcg (double); out[0] = -1 marks "no held-out items"
@@ -463,6 +531,63 @@ extern "C" int bprx_score_new_block(bprx_handle *h, int32_t u0, int32_t u1, cons
   dim3 grid((unsigned)((n + TN - 1) / TN), (unsigned)((u1 - u0 + TM - 1) / TM));
   hipLaunchKernelGGL(k_score_new_gemm, grid, dim3(256), 0, s, (const float *)h->t.Tu, P, (int)n, h->cfg.embed_d, h->PS, u0, u1, out);
   BPRX_LAUNCH_CHECK(h, "k_score_new_gemm");
+  return BPRX_OK;
+}
+
+// ---- similar items: bprx_sim_rnorm / bprx_sim_block (include/bprx.h) ----
+// The checks the two entries share, then the gate: the space, the query rows (the catalogue: nq == num_items; the caller's rows:
+// visual only), fp8 in a space that reads P, and plan_read's own (bound, handle kind).
+static int sim_enter(bprx_handle *h, const char *what, int32_t space, const float *Pq, int64_t nq, hipStream_t s) {
+  if (space != BPRX_SIM_LATENT && space != BPRX_SIM_VISUAL && space != BPRX_SIM_BOTH)
+    BPRX_FAIL(h, BPRX_E_INVALID, "%s: unknown space %d (BPRX_SIM_LATENT, _VISUAL or _BOTH)", what, space);
+  if (Pq && space != BPRX_SIM_VISUAL) BPRX_FAIL(h, BPRX_E_INVALID, "%s: rows from outside the catalogue live in the visual space only", what);
+  if (nq < 0 || nq >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "%s: nq = %lld out of range", what, (long long)nq);
+  if (!Pq && nq != h->cfg.num_items)
+    BPRX_FAIL(h, BPRX_E_INVALID, "%s: nq = %lld, the catalogue has %d items", what, (long long)nq, h->cfg.num_items);
+  const bool latent = space == BPRX_SIM_LATENT;
+  if (!latent && h->cfg.model == BPRX_MODEL_VBPR && h->cfg.feat_dtype == BPRX_F_FP8)
+    BPRX_FAIL(h, BPRX_E_INVALID, "%s: the visual space of an fp8 handle is not supported (its projections carry the rounding of the "
+                                 "fp8 codes): use BPRX_SIM_LATENT, or fp32 / bf16 features", what);
+  return bprx_enter(h, what, NEED_BOUND | NEED_ROWS | (latent ? 0 : NEED_P_ALL), latent ? KIND_PLAIN : KIND_VBPR, s);
+}
+
+// the parts of z for the catalogue (Pq == nullptr) or the caller's rows: [Gi over k | P over d], absent parts have width 0
+static void sim_parts(const bprx_handle *h, int32_t space, const float *Pq, SimPart &g, SimPart &p) {
+  g = {h->t.Gi, space != BPRX_SIM_VISUAL && !Pq ? h->cfg.embed_k : 0, h->cfg.embed_k};
+  p = {Pq ? Pq : h->P, space != BPRX_SIM_LATENT ? h->cfg.embed_d : 0, h->PS};
+}
+
+extern "C" int bprx_sim_rnorm(bprx_handle *h, int32_t space, const float *Pq, int64_t nq, float *rn, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (!rn) BPRX_FAIL(h, BPRX_E_INVALID, "sim_rnorm: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = sim_enter(h, "sim_rnorm", space, Pq, nq, s);
+  if (rc || nq == 0) return rc;
+  SimPart g, p;
+  sim_parts(h, space, Pq, g, p);
+  constexpr int rows = 256 / RN_LANES;
+  hipLaunchKernelGGL(k_sim_rnorm, dim3((unsigned)((nq + rows - 1) / rows)), dim3(256), 0, s, g, p, (int)nq, rn);
+  BPRX_LAUNCH_CHECK(h, "k_sim_rnorm");
+  return BPRX_OK;
+}
+
+extern "C" int bprx_sim_block(bprx_handle *h, int32_t space, const float *Pq, int64_t nq, int64_t q0, int64_t q1, const float *rn_q,
+                              const float *rn_items, float *out, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (!rn_q || !rn_items || !out) BPRX_FAIL(h, BPRX_E_INVALID, "sim_block: null pointer");
+  if (q0 < 0 || q0 > q1 || q1 > nq || q1 - q0 > (int64_t)65535 * TM)
+    BPRX_FAIL(h, BPRX_E_INVALID, "sim_block: bad query range [%lld,%lld) of %lld", (long long)q0, (long long)q1, (long long)nq);
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = sim_enter(h, "sim_block", space, Pq, nq, s);
+  if (rc || q0 == q1) return rc;
+  SimPart ag, ap, bg, bp;
+  sim_parts(h, space, Pq, ag, ap);
+  sim_parts(h, space, nullptr, bg, bp);
+  bg.w = ag.w;                                               // (the caller's rows have no Gi part)
+  const int I = h->cfg.num_items;
+  dim3 grid((unsigned)((I + TN - 1) / TN), (unsigned)((q1 - q0 + TM - 1) / TM));
+  hipLaunchKernelGGL(k_sim_gemm, grid, dim3(256), 0, s, ag, ap, bg, bp, I, (int)q0, (int)q1, rn_q, rn_items, out);
+  BPRX_LAUNCH_CHECK(h, "k_sim_gemm");
   return BPRX_OK;
 }
 

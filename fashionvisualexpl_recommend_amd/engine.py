@@ -607,6 +607,31 @@ class Engine:
         _ffi.check(self.h, self.lib.bprx_topk_lists(self.h, nrows, p(scores), p(ptr), p(items), K, p(idx), p(val), p(flag), _stream()))
         return idx, val, flag
 
+    # ---- similar items (include/bprx.h: the cosine of two item vectors, z = Gi | f E | both) --------------------------------------
+    def sim_rnorm(self, space, Pq=None):
+        """bprx_sim_rnorm: fp32 [I], 1 / |z_i| of every catalogue item in `space` ('latent', 'visual', 'both' or BPRX_SIM_*; 0 for a
+        zero row); with Pq = project_rows(F): fp32 [n] of those rows (visual only)."""
+        n = self.I if Pq is None else int(Pq.shape[0])
+        rn = torch.empty(n, dtype=torch.float32, device=self.device)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _ffi.check(self.h, self.lib.bprx_sim_rnorm(self.h, _ffi.SIM_SPACE.get(space, space), p(Pq), n, p(rn), _stream()))
+        return rn
+
+    def sim_block(self, space, q0, q1, rn_items, Pq=None, rn_q=None, out=None):
+        """bprx_sim_block: fp32 [q1 - q0, I], the cosine of the catalogue items q0 .. q1-1 (Pq: of rows q0 .. q1-1 of Pq, with
+        rn_q = sim_rnorm(space, Pq)) with every catalogue item; the item itself is not masked.  rn_items = sim_rnorm(space)."""
+        if rn_q is None:
+            if Pq is not None:
+                raise ValueError("sim_block: rows from outside the catalogue come with their norms (rn_q = sim_rnorm(space, Pq))")
+            rn_q = rn_items
+        nq = self.I if Pq is None else int(Pq.shape[0])
+        if out is None:
+            out = torch.empty((max(q1 - q0, 0), self.I), dtype=torch.float32, device=self.device)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _ffi.check(self.h, self.lib.bprx_sim_block(self.h, _ffi.SIM_SPACE.get(space, space), p(Pq), nq, int(q0), int(q1), p(rn_q),
+                                                   p(rn_items), p(out), _stream()))
+        return out
+
     def _hyper(self):
         return self._lr_reg
 

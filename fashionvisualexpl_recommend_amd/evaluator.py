@@ -241,6 +241,20 @@ class Evaluator:
                             break
                         ex.write(head + str(s) + '\t' + str(e["col"][p, s]) + '\t' + str(e["contrib"][p, s]) + '\n')
 
+    def store_similar_items(self, path="", space=None):
+        """Every catalogue item's nearest neighbours by cosine in `space` (model.similar_items: None = the model's own space, the
+        item itself excluded) as rows 'i\tj\tcosine', item by item, best first, formatted as store_recommendation formats."""
+        ids, vals = self.model.similar_items(None, None, space)
+        with open(path, 'w') as out:
+            write_ranked(out, range(ids.shape[0]), ids, vals)
+
+    def store_similar_new(self, path="", features=None):
+        """VBPR / GradFashion: the catalogue neighbours of every row of `features` (raw rows of items outside the catalogue, as
+        model.prepare_new_items takes them) in the visual space as rows 'j_new\ti\tcosine', row by row, best first."""
+        ids, vals = self.model.similar_to_new(features)
+        with open(path, 'w') as out:
+            write_ranked(out, range(ids.shape[0]), ids, vals)
+
     def store_recommendation_grads(self, path="", path_expl=None, top=5):
         """Evaluator.py:261-275 (GradFashion): for every user the items training_list[u] + validation_list[u] + test_list[u],
         in that order, one row 'u\\ti\\tcolour\\tedges' each (get_explanations.py:19-21 reads USER_ID, ITEM_ID, COLOR, EDGES).

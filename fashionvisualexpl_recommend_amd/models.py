@@ -105,6 +105,8 @@ class BPRMF(RecommenderModel):
         self.reg = params.reg
         self.optimizer_name = getattr(params, "optimizer", "adam_tf23")
         self.evaluator = Evaluator(self, data, params.top_k)                       # BPRMF.py:40
+        self.similar_k = int(getattr(params, "similar_items", 0) or 0)             # neighbours per item in sim-*; 0: none
+        self.similar_space = getattr(params, "similar_space", None) or self.sim_space
         self.directory_parameters = f'batch_{params.batch_size}-K_{params.embed_k}-lr_{params.lr}-reg_{params.reg}'
         self._build(init or {})
 
@@ -257,6 +259,7 @@ class BPRMF(RecommenderModel):
         print('Training end...')
         self._store_recs(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
         self._store_new_user_recs(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
+        self._store_similar(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
         with open(os.path.join(rdir, f'results-metrics-{self.directory_parameters}') + '.pkl', 'wb') as f:
             pickle.dump(results, f)                                             # utils/write.py:14-22
         print("Store Best Model at Epoch {0}".format(best_epoch))
@@ -267,6 +270,7 @@ class BPRMF(RecommenderModel):
             self.load_state_dict(best_state)
         self._store_recs(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
         self._store_new_user_recs(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
+        self._store_similar(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
         self.load_state_dict(last_state)
         print('End Store Best Model!')
         print('Best Values for Each Metric:\nHR\tPrec\tRec\tAUC\tnDCG\n{}\t{}\t{}\t{}\t{}\n'.format(
@@ -332,6 +336,41 @@ class BPRMF(RecommenderModel):
                                        seed=getattr(self.params, "init_seed", 0))
         with open(os.path.join(d, f.replace("recs-", "new-user-recs-", 1)), 'w') as out:
             write_ranked(out, labels, *res)
+
+    # ---- similar items: the cosine of two items in the model's item space (include/bprx.h, bprx_sim_*) -------------------------
+    sim_space = "latent"                                         # the space similar_items walks by default
+
+    def similar_items(self, items=None, k=None, space=None):
+        """The k (default: params.similar_items, else top_k) catalogue items most like each item of `items` (None: the whole
+        catalogue, in id order) by cosine in `space` ('latent': Gi; 'visual': f E; 'both': [Gi | f E]; None: the model's own,
+        latent for BPRMF, visual for VBPR / GradFashion): numpy ids int64 [n, kk] and vals fp32 [n, kk], kk = min(k, I - 1), best
+        first, the item itself excluded.  The catalogue is walked in blocks of item rows (Engine.sim_block), every block listed by
+        ranking.rank_rows with Engine.topk_lists and lists in which every row names itself; an explicit id list ranks the blocks
+        that hold its ids and keeps those rows."""
+        eng, I = self.engine, self.num_items
+        k = (self.similar_k or self.evaluator.k) if k is None else int(k)
+        space = self.similar_space if space is None else space
+        want = np.arange(I, dtype=np.int64) if items is None else np.asarray(items, dtype=np.int64).reshape(-1)
+        if want.size and (want.min() < 0 or want.max() >= I):
+            raise ValueError("similar_items: item ids lie in [0, %d)" % I)
+        kk = min(k, I - 1)
+        blk = rows_per_block(self.evaluator.user_block, I)
+        rn = eng.sim_rnorm(space)
+        ids, vals = np.zeros((want.size, kk), np.int64), np.zeros((want.size, kk), np.float32)
+        for b0 in sorted({int(q) // blk * blk for q in want}):
+            b1 = min(I, b0 + blk)
+            own = eng.csr([[q] for q in range(b0, b1)])
+            bi, bv, _ = rank_rows(lambda s, kq: eng.topk_lists(s, own, kq), eng.sim_block(space, b0, b1, rn), k)
+            rows = np.nonzero((want >= b0) & (want < b1))[0]
+            ids[rows], vals[rows] = bi[want[rows] - b0, :kk], bv[want[rows] - b0, :kk]      # (k >= I: the masked self is last)
+        return ids, vals
+
+    def _store_similar(self, path):
+        """params.similar_items = K > 0: sim-* next to the recs-* file at `path`, rows 'i\tj\tcosine', item by item, best first."""
+        if self.similar_k <= 0:
+            return
+        d, f = os.path.split(path)
+        self.evaluator.store_similar_items(os.path.join(d, f.replace("recs-", "sim-", 1)), self.similar_space)
 
 
 def _stack_blocks(parts, kk, c=0):
@@ -483,6 +522,32 @@ class VBPR(BPRMF):
         users = np.repeat(np.arange(u0, u1), kk)
         ex = eng.feat_explain_new(F, users, idx_all.reshape(-1), explain, self.feat_cols) if users.size else None
         return idx_all, val_all, ({} if ex is None else {nm: v.cpu().numpy() for nm, v in ex.items() if nm != "visual"})
+
+    # ---- similar items (BPRMF.similar_items): the visual space is the model's own, and rows from outside the catalogue have one ----
+    sim_space = "visual"
+
+    def similar_to_new(self, features, k=None):
+        """The k (default: params.similar_items, else top_k) catalogue items most like each row of `features` (raw rows of items
+        outside the catalogue, or a table from prepare_new_items) by cosine in the visual space: numpy ids int64 [n, kk] and vals
+        fp32 [n, kk], kk = min(k, I), best first.  Engine.project_rows puts the rows on the catalogue's scale; sim_rnorm and
+        sim_block give the cosines, ranking.rank_rows with Engine.topk_rows the lists (nothing is masked)."""
+        eng, I = self.engine, self.num_items
+        k = (self.similar_k or self.evaluator.k) if k is None else int(k)
+        P = eng.project_rows(self._as_new_table(features))
+        n = int(P.shape[0])
+        rn, rq = eng.sim_rnorm("visual"), eng.sim_rnorm("visual", P)
+        blk = rows_per_block(self.evaluator.user_block, I)
+        parts = [rank_rows(eng.topk_rows, eng.sim_block("visual", b0, min(n, b0 + blk), rn, P, rq), k) for b0 in range(0, n, blk)]
+        return _stack_blocks(parts, min(k, I))
+
+    def _store_similar(self, path):
+        """sim-* as every model writes it; with params.new_items also new-sim-*, rows 'j_new\ti\tcosine' (always the visual space)."""
+        super()._store_similar(path)
+        feats = self._load_new_items() if self.similar_k > 0 else None
+        if feats is None:
+            return
+        d, f = os.path.split(path)
+        self.evaluator.store_similar_new(os.path.join(d, f.replace("recs-", "new-sim-", 1)), feats)
 
     def _load_new_items(self):
         paths = list(getattr(self.params, "new_items", None) or [])

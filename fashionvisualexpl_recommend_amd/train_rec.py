@@ -6,6 +6,8 @@ Same flag names and defaults for every flag BPRMF/VBPR consume; new flags: --opt
 reachable there); here they take two ints `h 1`, and so does AttentiveFashion's --attention_layers.  --dropout is the rate of the
 three encoders' Dropout layers (the reference's constant 0.5).
 --af_new_users PATH (attentive_fashion only) fits rows for users the model was not trained on and writes new-user-recs-* files.
+--similar_items K (bprmf, vbpr, grad_fashion) writes sim-* / best-sim-* files with every item's K nearest items by cosine in the
+space of --similar_space (latent: Gi; visual: f E; both), and with --new_items new-sim-* / best-new-sim-* (the visual space).
 Run as `python -m fashionvisualexpl_recommend_amd.train_rec --rec bprmf --dataset <name> ...`.
 """
 import argparse
@@ -74,6 +76,14 @@ def parse_args(argv=None):
                              "item side, the encoders and the attention frozen and dropout off, and new-user-recs-* / "
                              "best-new-user-recs-* files (label, item, score, alpha_colour, alpha_edges, alpha_class) are written "
                              "next to recs-* / best-recs-*")
+    parser.add_argument('--similar_items', type=int, default=0, metavar='K',
+                        help="bprmf, vbpr, grad_fashion: also write sim-* / best-sim-* files next to recs-* / best-recs-* with every "
+                             "catalogue item's K (1..1024) nearest items by cosine in the model's item space, rows `i j cosine`, "
+                             "the item itself excluded; with --new_items also new-sim-* / best-new-sim-*, the catalogue neighbours "
+                             "of every new item, rows `j_new i cosine`, always in the visual space; 0 = off")
+    parser.add_argument('--similar_space', default=None, choices=['latent', 'visual', 'both'],
+                        help="--similar_items: latent = Gi, visual = f E (vbpr, grad_fashion; fp32 or bf16 features), both = "
+                             "[Gi | f E]; default: latent for bprmf, visual for vbpr and grad_fashion")
     parser.add_argument('--fold_steps', type=int, default=30, help='--new_users / --af_new_users: optimiser steps per new user')
     parser.add_argument('--fold_negatives', type=int, default=4,
                         help='--new_users / --af_new_users: sampled negatives per history item')
@@ -128,6 +138,18 @@ def parse_args(argv=None):
         parser.error("--af_new_users needs --rec attentive_fashion (got --rec %s)" % args.rec)
     if args.fold_steps < 1 or args.fold_negatives < 1:
         parser.error("--fold_steps and --fold_negatives take values >= 1 (got %s, %s)" % (args.fold_steps, args.fold_negatives))
+    if not 0 <= args.similar_items <= 1024:
+        parser.error("--similar_items takes 0 (off) .. 1024 (got %s)" % args.similar_items)
+    asked = args.similar_items != 0 or args.similar_space is not None
+    if args.similar_space is None:                            # the model's own space
+        args.similar_space = {'bprmf': 'latent', 'vbpr': 'visual', 'grad_fashion': 'visual'}.get(args.rec)
+    if asked:
+        if args.rec not in ('bprmf', 'vbpr', 'grad_fashion'):
+            parser.error("--similar_items / --similar_space need --rec bprmf, vbpr or grad_fashion (got --rec %s)" % args.rec)
+        if args.similar_space != 'latent' and args.rec == 'bprmf':
+            parser.error("--similar_space %s needs --rec vbpr or grad_fashion (bprmf has the latent space only)" % args.similar_space)
+        if args.similar_space != 'latent' and args.dtype == 'fp8':
+            parser.error("--similar_space %s runs with --dtype fp32 or bf16 (got fp8): use --similar_space latent" % args.similar_space)
     if not 0.0 <= args.dropout < 1.0:
         parser.error("--dropout takes a rate in [0, 1) (got %s)" % args.dropout)
     return args
@@ -169,6 +191,8 @@ def train(argv=None):
         raise NotImplementedError('--new_users runs on one GPU (the sharded drivers write no new-user-recs-* files): use --world_size 1')
     if args.af_new_users is not None and int(args.world_size) > 1:
         raise NotImplementedError('--af_new_users runs on one GPU (no multi-GPU form): use --world_size 1')
+    if args.similar_items != 0 and int(args.world_size) > 1:
+        raise NotImplementedError('--similar_items runs on one GPU (the sharded drivers write no sim-* files): use --world_size 1')
     if args.new_items is not None and args.dtype == 'fp8':
         raise ValueError('--new_items runs with --dtype fp32 or bf16 (an fp8 table is scaled for the training max-abs: a new row '
                          'may saturate)')

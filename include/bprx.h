@@ -305,6 +305,37 @@ BPRX_API int bprx_score_rows_block(bprx_handle *h, const float *Gu_rows, const f
 BPRX_API int bprx_topk_lists(bprx_handle *h, int64_t nrows, float *scores, const int64_t *list_ptr, const int32_t *list_items,
                              int32_t K, int32_t *idx, float *val, int32_t *flag, void *stream);
 
+/* ---- BPRMF, VBPR and GradFashion: similar items, the cosine of two items in the model's item space --------------------------
+   "Which items are like this one": the item vector z_i by space,
+       BPRX_SIM_LATENT  z_i = Gi_i                      (k numbers)      a BPRMF or VBPR handle, plain or factored, any feat_dtype
+       BPRX_SIM_VISUAL  z_i = P[i, 0:d] = f_i E         (not the Bp column; a factored handle: E_eff)
+       BPRX_SIM_BOTH    z_i = [Gi_i | P[i, 0:d]]        (the item side of x_ui)
+                                                        VISUAL / BOTH: a VBPR handle, plain or factored, fp32 or bf16 features
+       rn_i = 1 / sqrt(sum_x z_ix^2)   the fp32 sum taken in ascending x, each square and each sum rounded once; rn_i = 0 for sum 0
+       s(q, j) = <z_q, z_j> (rn_q rn_j)                 the two norms are multiplied first: the factor is symmetric
+   <z_q, z_j> is the fp32 MFMA GEMM of bprx_score_block (exact fp32 products, sums in x order, Gi before P): s(q, j) has the bits
+   of s(j, q), two items with bit-equal z have bit-equal rows, a zero row has similarity 0.0 to everything (never NaN), and a
+   row's bits depend on its own z, the catalogue and the norms only -- not on q0, q1, nq or the tile it lands in.  The entry of
+   an item with itself is NOT masked: rank a block with bprx_topk_lists and lists in which row r names item q0 + r, rows from
+   outside the catalogue with bprx_topk_rows.
+   Errors: BPRX_E_INVALID for a NULL handle or pointer, an unknown space, an ACF or AttentiveFashion handle, a BPRMF handle in
+   VISUAL / BOTH, an fp8 handle in VISUAL / BOTH, a bad range, Pq != NULL with another space than VISUAL, Pq == NULL with
+   nq != num_items; BPRX_E_STATE for unbound tables; q0 == q1: BPRX_OK, nothing is written.  After any error the handle stays
+   usable.  State: like bprx_score_block both calls first settle a pending dense update, bring lazy adam_tf23 rows up to date and
+   (VISUAL / BOTH) make P current; apart from that they write their outputs only and allocate nothing. */
+#define BPRX_SIM_LATENT 0
+#define BPRX_SIM_VISUAL 1
+#define BPRX_SIM_BOTH 2
+/* Pq == NULL: rn fp32 [num_items] of the catalogue, nq must equal num_items.  Pq != NULL: rn fp32 [nq] of the nq rows of
+   bprx_project_rows' output Pq [nq, PS] (items outside the catalogue, on the catalogue's scale); space must be BPRX_SIM_VISUAL. */
+BPRX_API int bprx_sim_rnorm(bprx_handle *h, int32_t space, const float *Pq, int64_t nq, float *rn, void *stream);
+/* out fp32 [(q1-q0), num_items]: out[r][j] = s(q0 + r, j).  Pq == NULL: the queries are the catalogue items q0 .. q1-1
+   (nq == num_items; rn_q is indexed by item id and may equal rn_items).  Pq != NULL: the queries are rows q0 .. q1-1 of Pq, rn_q
+   fp32 [nq] their norms, visual space only.  rn_items: bprx_sim_rnorm of the catalogue in the same space.
+   0 <= q0 <= q1 <= nq < 2^31, q1 - q0 <= 65535 * 128. */
+BPRX_API int bprx_sim_block(bprx_handle *h, int32_t space, const float *Pq, int64_t nq, int64_t q0, int64_t q1, const float *rn_q,
+                            const float *rn_items, float *out, void *stream);
+
 /* ---- ACF (ACF.py:20-270) on a BPRMF handle ------------------------------------------------------------------------------
    Attentive Collaborative Filtering over per-item feature maps f_l [M, C] (M = H*W spatial components).  For user u with
    history P(u) (ACF.py:135-181):
