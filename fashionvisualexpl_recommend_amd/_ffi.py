@@ -82,6 +82,7 @@ class Tables(C.Structure):
 
 
 DEFER_ENTRIES = ("bprx_settle", "bprx_dense_pending", "bprx_set_loss_lag")    # the deferred dense update (include/bprx.h)
+QUEUE_ENTRIES = ("bprx_index_pass_queue",)                                   # the samplers' owner queues: an introspection getter
 
 _lib = None
 
@@ -183,6 +184,7 @@ def lib():
         "bprx_epoch_slots": (C.c_int, [vp, i32, vp, i64, vp]),
         "bprx_sample_epoch": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, C.c_uint64, u32, i64, i64, vp, vp, vp, vp]),
         "bprx_index_pass_kind": (C.c_int, [vp]),
+        "bprx_index_pass_queue": (C.c_int, [vp]),
         "bprx_proj_mask_kind": (C.c_int, [vp]),
         "bprx_adam_rows": (C.c_int, [vp, vp, vp, vp, i64, C.c_float, C.c_float, C.c_float, C.c_float, vp]),
         "bprx_step_lr": (C.c_int, [vp, vp]),
@@ -197,7 +199,7 @@ def lib():
         "bprx_set_loss_lag": (C.c_int, [vp, C.c_int]),
     }
     for name, (res, args) in sig.items():
-        if name in DEFER_ENTRIES and not hasattr(L, name):
+        if name in DEFER_ENTRIES + QUEUE_ENTRIES and not hasattr(L, name):
             continue                # an older build named by BPRX_LIB (A/B runs): it never defers, the engine skips these calls
         fn = getattr(L, name)       # AttributeError here == header/library mismatch: fail loudly
         fn.restype, fn.argtypes = res, args
@@ -215,7 +217,7 @@ EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error",
            "bprx_scatter_add", "bprx_route_reset", "bprx_route_plan", "bprx_route_gather", "bprx_route_unpack", "bprx_route_gather_checked",
            "bprx_route_unpack_checked", "bprx_route_pack",
            "bprx_route_scatter_add", "bprx_score_block", "bprx_eval_users", "bprx_eval_pos", "bprx_eval_counts", "bprx_eval_finish", "bprx_topk", "bprx_sync_check", "bprx_probe_stream_read", "bprx_probe_stream_read_nt", "bprx_probe_row_gather", "bprx_profile_enable",
-           "bprx_profile_read", "bprx_sample_philox", "bprx_epoch_prepare", "bprx_epoch_slots", "bprx_sample_epoch", "bprx_sample_philox_h", "bprx_sample_epoch_h", "bprx_index_pass_kind", "bprx_proj_mask_kind", "bprx_adam_rows", "bprx_step_lr", "bprx_user_msg_floats", "bprx_pack_user_msg",
+           "bprx_profile_read", "bprx_sample_philox", "bprx_epoch_prepare", "bprx_epoch_slots", "bprx_sample_epoch", "bprx_sample_philox_h", "bprx_sample_epoch_h", "bprx_index_pass_kind", "bprx_index_pass_queue", "bprx_proj_mask_kind", "bprx_adam_rows", "bprx_step_lr", "bprx_user_msg_floats", "bprx_pack_user_msg",
            "bprx_apply_user_msgs", "bprx_sampler_create",
            "bprx_sampler_destroy", "bprx_sampler_count", "bprx_sampler_ref_stream", "bprx_settle", "bprx_dense_pending", "bprx_set_loss_lag"]
 

@@ -171,7 +171,20 @@ extern "C" int bprx_create(const bprx_config *cfg, bprx_handle **out) {
       A.zeros((int2 **)&h->seg_ent, (size_t)h->seg_ent_cap);
       A.zeros(&h->uslot_of, U); A.zeros(&h->ulist, MB);
       A.zeros(&h->uold, MB * (k + d));
-      if (h->idx8_shift) { A.zeros(&h->own8, (size_t)2 * MB); A.zeros(&h->loc8, (size_t)2 * MB * (h->idx8_shift > 8 ? 2 : 1)); }
+      // BPRX_INDEX_QUEUE: the samplers also leave their occurrences binned by owner and the owners of k_index_seg read their
+      // own records instead of scanning the planes (DESIGN §4 "Owner queues"; byte locals only: up to 65 536 items).  0: the scan.
+      // The queues live behind the owner plane, in its allocation: records, then ranges.
+      h->index_queue = env_int("BPRX_INDEX_QUEUE", 1) != 0;
+      const size_t nreg = (h->index_queue && h->idx8_shift == 8) ? (size_t)ixq_regions((int64_t)MB) : 0;
+      const size_t plane = ((size_t)2 * MB + 15) / 16 * 16;
+      if (h->idx8_shift) {
+        A.zeros(&h->own8, plane + nreg * (IXQ_REC + IXQ_BINS) * sizeof(uint32_t));
+        A.zeros(&h->loc8, (size_t)2 * MB * (h->idx8_shift > 8 ? 2 : 1));
+      }
+      if (nreg && h->own8) {
+        h->qrec = reinterpret_cast<uint32_t *>(h->own8 + plane);
+        h->qrange = h->qrec + nreg * IXQ_REC;
+      }
     }
   }
   // Touched-item list (sparse batches): when the batch touches few of the items, both projections run over the batch's
@@ -439,6 +452,7 @@ static void commit_plan(bprx_handle *h, const StepPlan &p) {
   h->adam_t = p.adam_t;
   if (p.B == 0) return;
   h->idx8_n = 0;                                           // the byte planes are consumed, whatever this step does with them
+  h->idxq_n = 0; h->idxq_trip = 0;                         // ... and the owner queues with them
   h->proj_fresh = false;
   h->W_dirty = p.leaves_w_dirty;
   if (p.item_mode) h->seg_slot ^= 1;                       // (k_index_seg clears the other cursor triple for the next such step)
@@ -684,6 +698,7 @@ extern "C" int bprx_step_lr(const bprx_handle *h, float *lr_t) {
 }
 
 extern "C" int bprx_index_pass_kind(const bprx_handle *h) { return h ? h->step.idx_kind : 0; }
+extern "C" int bprx_index_pass_queue(const bprx_handle *h) { return h && h->step.idxq ? 1 : 0; }
 extern "C" int bprx_proj_mask_kind(const bprx_handle *h) {
   if (!h || !h->step.mask) return 0;
   const bool fwd = bprx_proj_fwd_takes_mask(*h), bwd = bprx_proj_bwd_takes_mask(*h);

@@ -71,6 +71,28 @@ constexpr int ADAM_HIST = 8192;   // lazy adam_tf23: steps of lr_t the device ri
 constexpr int IX_RMAX = 8192;     // k_index_seg: items an owner workgroup can own (LDS counters)
 constexpr int IX_LPAD = 4;        // chunk-list slots of an owner beyond one per item (hot items' extra chunks; more: overflow list)
 
+// ---- the samplers' owner queues (DESIGN §4 "Owner queues") ----
+// Every 256-thread sampler workgroup leaves its up to 512 item occurrences as ONE region of 4-byte records, sorted by owner
+// (id >> 8: a counting sort in LDS), and for every owner the [lo, hi) slots it holds in that region: an owner workgroup of
+// k_index_seg then reads its own records only, not the whole batch.
+//   record        (occ << 8) | (id & 255), occ in [0, 2B): b for the positive of triplet b, B + b for its negative (seg_rank's index)
+//   records       [regions][IXQ_REC]: slot s of region r at r * IXQ_REC + s
+//   ranges        [IXQ_BINS][stride]: owner w's range in region r at w * stride + r (an owner reads consecutive words), lo | hi << 16
+// A batch filled by several sampler calls numbers its regions on: stride = ixq_regions(max_batch) holds a batch of two calls.
+constexpr int IXQ_WG = 256;                  // triplets per sampler workgroup = per region
+constexpr int IXQ_REC = 2 * IXQ_WG;          // records of a region
+constexpr int IXQ_BINS = 256;                // owners (the planes' owner byte at shift 8)
+constexpr int64_t IXQ_MAX_OCC = 1 << 24;     // occ has 24 bits: 2B <= 2^24
+__host__ __device__ inline uint32_t ixq_pack(uint32_t occ, uint32_t id) { return (occ << 8) | (id & 255u); }
+__host__ __device__ inline uint32_t ixq_occ(uint32_t rec) { return rec >> 8; }
+__host__ __device__ inline uint32_t ixq_local(uint32_t rec) { return rec & 255u; }
+__host__ __device__ inline uint32_t ixq_range(uint32_t lo, uint32_t hi) { return lo | (hi << 16); }
+__host__ __device__ inline uint32_t ixq_lo(uint32_t range) { return range & 0xffffu; }
+__host__ __device__ inline uint32_t ixq_hi(uint32_t range) { return range >> 16; }
+__host__ __device__ inline int64_t ixq_regions(int64_t max_batch) { return max_batch / IXQ_WG + 2; }
+__host__ __device__ inline size_t ixq_rec_at(int region, int slot) { return (size_t)region * IXQ_REC + (size_t)slot; }
+__host__ __device__ inline size_t ixq_range_at(int owner, int region, int stride) { return (size_t)owner * (size_t)stride + (size_t)region; }
+
 // What ONE BPRMF / VBPR training step does: every decision about its form, made once by plan_step (below the handle) from the
 // configuration, the create-time policies and the state carried from step to step.  bprx_step_begin_sparse commits it to
 // bprx_handle::step; bprx_step_begin_dense, bprx_step_end and every launcher read it and decide nothing themselves.
@@ -94,6 +116,8 @@ struct StepPlan {
   bool index_first;               // the index pass runs before the forward projection (list, mask), otherwise after it
   bool row_count;                 // atomic staging / list mode: the index pass is k_row_count (neither: no index pass)
   bool idx8;                      // the index pass scans the sampler's byte planes of this very batch
+  bool idxq;                      // ... its owners read the sampler's owner queues of this very batch instead (bprx_index_pass_queue)
+  int idxq_regions;               // ... which hold this many regions
   int idx_kind;                   // bprx_index_pass_kind: of this step if it is a segment-mode step, else of the last one
   bool project, fwd;              // VBPR, no bprx_step_project before: [E|Bp]^T images are made; P is projected (not current)
   int fast, fastU, fastI;         // sgd: rows used by exactly one triplet are updated in place; per side (off for exported rows)
@@ -199,6 +223,9 @@ struct bprx_handle {
   // filled so far (-1: invalid): written by the samplers; consumed (idx8_n = 0) by commit_plan, whatever the step does with them.
   const int32_t *idx8_pos, *idx8_neg;
   int64_t idx8_B, idx8_n;
+  // the owner queues of the same batch (same tags): regions filled so far (-1: a call of this batch left none) and the triplets
+  // they hold; written and consumed with the planes
+  int64_t idxq_n, idxq_trip;
 
   int32_t *errflag;               // device-side deferred error (index out of range)
   // VBPR projection state
@@ -244,6 +271,13 @@ struct bprx_handle {
   bool idx8_ready(bool item_mode, const int32_t *pos, const int32_t *neg, int64_t B) const {
     return item_mode && own8 && B > 0 && idx8_n == B && idx8_B == B && idx8_pos == pos && idx8_neg == neg && B % 16 == 0;
   }
+  uint32_t *qrec, *qrange;        // the samplers' owner queues: records [ixq_regions(max_batch)][IXQ_REC], ranges [IXQ_BINS][the same];
+                                  //    not allocations of their own: they lie behind the owner plane in own8's buffer
+  int index_queue;                // env BPRX_INDEX_QUEUE, read at create: 1 (default) the owners of k_index_seg read the queues, 0 they scan the planes
+  // the samplers fill queues for a batch of B on this handle at all (byte locals, occ in 24 bits)
+  bool idxq_feeds(int64_t B) const { return index_queue && qrec && qrange && idx8_shift == 8 && 2 * B <= IXQ_MAX_OCC; }
+  // the planes of this very batch are ready (idx8_ready) and every sampler call that filled them left its regions too
+  bool idxq_ready(bool idx8, int64_t B) const { return idx8 && idxq_feeds(B) && idxq_n > 0 && idxq_trip == B; }
   int32_t *hot_done;              // [I] finished chunks of a hot item (k_item_seg), all-zero between steps
   void *seg_ent;                  // [seg_ent_cap] 8-byte entries {user or user slot | role << 31, g_b}: the owners' regions (twice
                                   //     the expected occupancy each) + 2 * max_batch for the owners that overflow theirs
@@ -454,6 +488,9 @@ inline StepPlan plan_step(const bprx_handle &h, const int32_t *user, const int32
   p.row_count = !p.item_mode && (h.fast_rows || p.list_mode);
   // byte planes of this very batch, left by bprx_sample_*_h
   p.idx8 = h.idx8_ready(p.item_mode, pos, neg, B);
+  // ... and its owner queues: the owners read their own records instead of scanning the planes (BPRX_INDEX_QUEUE, shift 8, 2B <= 2^24)
+  p.idxq = h.idxq_ready(p.idx8, B);
+  p.idxq_regions = p.idxq ? (int)h.idxq_n : 0;
   if (p.list_mode) {
     p.list_bound = 2 * B < I ? 2 * B : I;
     p.list_cur = h.ilist_n + h.list_slot; p.list_next = h.ilist_n + (h.list_slot ^ 1);
@@ -510,6 +547,43 @@ inline StepPlan plan_step(const bprx_handle &h, const int32_t *user, const int32
     p.apply = lazy ? APPLY_ADAM_LAZY : APPLY_ADAM_SWEEP;  // lazy: touched rows only, everything else is replayed later
   }
   return p;
+}
+
+// ---- what a sampler call leaves for the handle's next step (bprx_sample_*_h) ----
+// This call fills triplets [batch_offset, batch_offset + B) of a batch of batch_size.  Moves the handle's tags (host fields only,
+// no HIP call) and says where the call's planes and regions go.  The call with batch_offset 0 begins the batch; a later call
+// that does not continue it drops the planes, one whose regions do not fit (more calls than the stride allows for) drops the
+// queues alone.
+struct SamplerFeed {
+  bool planes, queues;
+  long long pl_i, pl_j;           // plane positions, and the `occ` of a record, of the call's first positive / negative
+  int sh;                         // idx8_shift
+  int q0, qstride;                // first region of this call, regions per owner in qrange
+};
+inline SamplerFeed sampler_feed(bprx_handle *h, const int32_t *pos, const int32_t *neg, int64_t B, int64_t batch_offset,
+                                int64_t batch_size) {
+  SamplerFeed f = {};
+  f.sh = 8;
+  if (!h || !h->own8 || batch_size <= 0 || batch_size > h->cfg.max_batch || batch_offset < 0 || batch_offset + B > batch_size) return f;
+  if (batch_offset == 0) {
+    h->idx8_pos = pos; h->idx8_neg = neg; h->idx8_B = batch_size; h->idx8_n = 0;
+    h->idxq_n = 0; h->idxq_trip = 0;
+  } else if (h->idx8_n < 0 || h->idx8_B != batch_size || pos != h->idx8_pos + batch_offset || neg != h->idx8_neg + batch_offset) {
+    h->idx8_n = -1;                                        // not a continuation of the batch begun at offset 0: no planes
+    h->idxq_n = -1;
+    return f;
+  }
+  h->idx8_n += B;
+  f.planes = true;
+  f.pl_i = batch_offset; f.pl_j = batch_size + batch_offset; f.sh = h->idx8_shift;
+  const int64_t nreg = (B + IXQ_WG - 1) / IXQ_WG, cap = ixq_regions(h->cfg.max_batch);
+  if (h->idxq_n >= 0 && h->idxq_trip == batch_offset && h->idxq_feeds(batch_size) && h->idxq_n + nreg <= cap) {
+    f.queues = true;
+    f.q0 = (int)h->idxq_n; f.qstride = (int)cap;
+    h->idxq_n += nreg; h->idxq_trip += B;
+  } else
+    h->idxq_n = -1;
+  return f;
 }
 
 // ---- how a read is planned ----

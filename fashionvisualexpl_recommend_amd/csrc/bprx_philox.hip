@@ -46,41 +46,84 @@ __device__ __forceinline__ void put_planes(uint8_t *__restrict__ own8, uint8_t *
   }
 }
 
+// The owner queues (bprx_internal.h): a counting sort of the workgroup's up to 512 occurrences by owner (id >> 8).  EVERY thread
+// of the workgroup comes here (barriers); `live`: it holds a triplet.  hist is all-zero on entry (cleared at the kernel's start,
+// behind a barrier).  The returning LDS add is the rank inside the bin; the exclusive scan over the 256 bins gives the bins'
+// first slots; thread t stores bin t's [lo, hi) where owner t finds it.  No global atomic, no capacity: the region holds what
+// the workgroup drew, whatever the item distribution.
+struct QueueArgs {
+  uint32_t *rec, *range;          // nullptr: no queues
+  int q0, stride;                 // region of workgroup 0 of this launch, regions per owner in `range`
+};
+__device__ __forceinline__ void put_queues(const QueueArgs &q, int *hist, int *wtot, bool live, int32_t ii, int32_t jj,
+                                           long long occ_i, long long occ_j) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int bi = (ii >> 8) & (IXQ_BINS - 1), bj = (jj >> 8) & (IXQ_BINS - 1);       // (the owner byte of the planes)
+  int ri = 0, rj = 0;
+  if (live) { ri = atomicAdd(&hist[bi], 1); rj = atomicAdd(&hist[bj], 1); }
+  __syncthreads();
+  const int c = hist[tid];                                                          // IXQ_BINS == blockDim.x: one bin per thread
+  int inc = c;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += v;
+  }
+  if (lane == 63) wtot[wv] = inc;
+  __syncthreads();
+  int lo = inc - c;
+  for (int x = 0; x < wv; ++x) lo += wtot[x];
+  hist[tid] = lo;                                                       // (my bin alone: nobody else reads it before the next barrier)
+  const int region = q.q0 + (int)blockIdx.x;
+  q.range[ixq_range_at(tid, region, q.stride)] = ixq_range((uint32_t)lo, (uint32_t)(lo + c));
+  __syncthreads();
+  if (live) {
+    q.rec[ixq_rec_at(region, hist[bi] + ri)] = ixq_pack((uint32_t)occ_i, (uint32_t)ii);
+    q.rec[ixq_rec_at(region, hist[bj] + rj)] = ixq_pack((uint32_t)occ_j, (uint32_t)jj);
+  }
+}
+
 __global__ __launch_bounds__(256) void k_sample_philox(const int64_t *__restrict__ indptr, const int32_t *__restrict__ items,
                                                        const int32_t *__restrict__ pos_user, unsigned long long N, uint32_t I,
                                                        uint32_t k0, uint32_t k1, unsigned long long first, long long B,
                                                        int32_t *__restrict__ u, int32_t *__restrict__ i, int32_t *__restrict__ j,
                                                        uint8_t *__restrict__ own8, uint8_t *__restrict__ loc8, long long pl_i,
-                                                       long long pl_j, int sh) {
+                                                       long long pl_j, int sh, QueueArgs qa) {
+  __shared__ int q_hist[IXQ_BINS], q_wtot[4];
   const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (b >= B) return;
-  const unsigned long long n = first + (unsigned long long)b;
-  uint32_t r[4];
-  philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), 0u, 0u, k0, k1, r);
-  const unsigned long long x = ((unsigned long long)r[1] << 32) | r[0];
-  const unsigned long long p = __umul64hi(x, N);
-  const int32_t uu = pos_user[p];
-  const long long lo0 = indptr[uu], len = indptr[uu + 1] - lo0;
-  const int32_t *lst = items + lo0;
-  int32_t jj = 0;
-  bool hit = true;
-  for (uint32_t a = 0; a < 1024u && hit; ++a) {
-    if (a) philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), a, 0u, k0, k1, r);
-    jj = (int32_t)__umulhi(r[2], I);
-    long long lo = 0, hi = len;
-    while (lo < hi) {
-      const long long mid = (lo + hi) >> 1;
-      if (lst[mid] < jj) lo = mid + 1; else hi = mid;
+  const bool live = b < B;
+  if (!qa.rec && !live) return;
+  if (qa.rec) { q_hist[threadIdx.x] = 0; __syncthreads(); }   // (threads without a triplet stay for put_queues' barriers)
+  int32_t ii = 0, jj = 0;
+  if (live) {
+    const unsigned long long n = first + (unsigned long long)b;
+    uint32_t r[4];
+    philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), 0u, 0u, k0, k1, r);
+    const unsigned long long x = ((unsigned long long)r[1] << 32) | r[0];
+    const unsigned long long p = __umul64hi(x, N);
+    const int32_t uu = pos_user[p];
+    const long long lo0 = indptr[uu], len = indptr[uu + 1] - lo0;
+    const int32_t *lst = items + lo0;
+    bool hit = true;
+    for (uint32_t a = 0; a < 1024u && hit; ++a) {
+      if (a) philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), a, 0u, k0, k1, r);
+      jj = (int32_t)__umulhi(r[2], I);
+      long long lo = 0, hi = len;
+      while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (lst[mid] < jj) lo = mid + 1; else hi = mid;
+      }
+      hit = lo < len && lst[lo] == jj;
     }
-    hit = lo < len && lst[lo] == jj;
+    if (hit) {
+      philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), 1024u, 0u, k0, k1, r);
+      jj = nth_non_positive(lst, len, I, r[2], jj);
+    }
+    ii = items[p];
+    u[b] = uu; i[b] = ii; j[b] = jj;
+    if (own8) put_planes(own8, loc8, pl_i + b, pl_j + b, ii, jj, sh);   // byte planes of the item ids for the handle's index pass
   }
-  if (hit) {
-    philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), 1024u, 0u, k0, k1, r);
-    jj = nth_non_positive(lst, len, I, r[2], jj);
-  }
-  const int32_t ii = items[p];
-  u[b] = uu; i[b] = ii; j[b] = jj;
-  if (own8) put_planes(own8, loc8, pl_i + b, pl_j + b, ii, jj, sh);   // byte planes of the item ids for the handle's index pass
+  if (qa.rec) put_queues(qa, q_hist, q_wtot, live, ii, jj, pl_i + b, pl_j + b);   // ... and its owners' queues
 }
 
 // Epoch-walk mode (the reference's order, dataset.py:93-107, as a stateless stream): within epoch e the users come in the
@@ -94,40 +137,46 @@ __global__ __launch_bounds__(256) void k_sample_epoch(const int64_t *__restrict_
                                                       long long first, long long B, int32_t *__restrict__ u,
                                                       int32_t *__restrict__ i, int32_t *__restrict__ j,
                                                       uint8_t *__restrict__ own8, uint8_t *__restrict__ loc8, long long pl_i,
-                                                      long long pl_j, int sh) {
+                                                      long long pl_j, int sh, QueueArgs qa) {
+  __shared__ int q_hist[IXQ_BINS], q_wtot[4];
   const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (b >= B) return;
-  const long long n = first + b;
-  int lo = 0, hi = U;                                   // largest a with epoch_ptr[a] <= n (and a non-empty list)
-  if (pos_slot) lo = pos_slot[n];                       // precomputed once per epoch
-  else
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (epoch_ptr[mid] <= n) lo = mid; else hi = mid;
+  const bool live = b < B;
+  if (!qa.rec && !live) return;
+  if (qa.rec) { q_hist[threadIdx.x] = 0; __syncthreads(); }   // (threads without a triplet stay for put_queues' barriers)
+  int32_t ii = 0, jj = 0;
+  if (live) {
+    const long long n = first + b;
+    int lo = 0, hi = U;                                   // largest a with epoch_ptr[a] <= n (and a non-empty list)
+    if (pos_slot) lo = pos_slot[n];                       // precomputed once per epoch
+    else
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (epoch_ptr[mid] <= n) lo = mid; else hi = mid;
+      }
+    const int32_t uu = perm[lo];
+    const long long l0 = indptr[uu], len = indptr[uu + 1] - l0;
+    const int32_t *lst = items + l0;
+    uint32_t r[4];
+    bool hit = true;
+    for (uint32_t a = 0; a < 1024u && hit; ++a) {
+      philox4x32_10((uint32_t)n, (uint32_t)((unsigned long long)n >> 32), a, epoch, k0, k1, r);
+      jj = (int32_t)__umulhi(r[2], I);
+      long long l = 0, h = len;
+      while (l < h) {
+        const long long mid = (l + h) >> 1;
+        if (lst[mid] < jj) l = mid + 1; else h = mid;
+      }
+      hit = l < len && lst[l] == jj;
     }
-  const int32_t uu = perm[lo];
-  const long long l0 = indptr[uu], len = indptr[uu + 1] - l0;
-  const int32_t *lst = items + l0;
-  uint32_t r[4];
-  int32_t jj = 0;
-  bool hit = true;
-  for (uint32_t a = 0; a < 1024u && hit; ++a) {
-    philox4x32_10((uint32_t)n, (uint32_t)((unsigned long long)n >> 32), a, epoch, k0, k1, r);
-    jj = (int32_t)__umulhi(r[2], I);
-    long long l = 0, h = len;
-    while (l < h) {
-      const long long mid = (l + h) >> 1;
-      if (lst[mid] < jj) l = mid + 1; else h = mid;
+    if (hit) {
+      philox4x32_10((uint32_t)n, (uint32_t)((unsigned long long)n >> 32), 1024u, epoch, k0, k1, r);
+      jj = nth_non_positive(lst, len, I, r[2], jj);
     }
-    hit = l < len && lst[l] == jj;
+    ii = lst[n - epoch_ptr[lo]];
+    u[b] = uu; i[b] = ii; j[b] = jj;
+    if (own8) put_planes(own8, loc8, pl_i + b, pl_j + b, ii, jj, sh);
   }
-  if (hit) {
-    philox4x32_10((uint32_t)n, (uint32_t)((unsigned long long)n >> 32), 1024u, epoch, k0, k1, r);
-    jj = nth_non_positive(lst, len, I, r[2], jj);
-  }
-  const int32_t ii = lst[n - epoch_ptr[lo]];
-  u[b] = uu; i[b] = ii; j[b] = jj;
-  if (own8) put_planes(own8, loc8, pl_i + b, pl_j + b, ii, jj, sh);
+  if (qa.rec) put_queues(qa, q_hist, q_wtot, live, ii, jj, pl_i + b, pl_j + b);
 }
 
 // The user order of an epoch: a keyed permutation of [0, U) evaluated POINTWISE -- slot a of epoch `epoch` holds user
@@ -206,16 +255,13 @@ extern "C" int bprx_epoch_slots(const int64_t *epoch_ptr, int32_t num_users, int
 // triplets [batch_offset, batch_offset + B) of a batch of batch_size (an epoch crossing fills a batch in two calls); the planes
 // are valid for the step that is called with exactly these buffers and B = batch_size, and are consumed by it.
 static void plane_args(bprx_handle *h, const int32_t *pos, const int32_t *neg, int64_t B, int64_t batch_offset, int64_t batch_size,
-                       uint8_t **own8, uint8_t **loc8, long long *pl_i, long long *pl_j, int *sh) {
-  *own8 = nullptr; *loc8 = nullptr; *pl_i = 0; *pl_j = 0; *sh = 8;
-  if (!h || !h->own8 || batch_size <= 0 || batch_size > h->cfg.max_batch || batch_offset < 0 || batch_offset + B > batch_size) return;
-  if (batch_offset == 0) { h->idx8_pos = pos; h->idx8_neg = neg; h->idx8_B = batch_size; h->idx8_n = 0; }
-  else if (h->idx8_n < 0 || h->idx8_B != batch_size || pos != h->idx8_pos + batch_offset || neg != h->idx8_neg + batch_offset) {
-    h->idx8_n = -1;                                        // not a continuation of the batch begun at offset 0: no planes
-    return;
-  }
-  h->idx8_n += B;
-  *own8 = h->own8; *loc8 = h->loc8; *pl_i = batch_offset; *pl_j = batch_size + batch_offset; *sh = h->idx8_shift;
+                       uint8_t **own8, uint8_t **loc8, long long *pl_i, long long *pl_j, int *sh, QueueArgs *qa) {
+  const SamplerFeed f = sampler_feed(h, pos, neg, B, batch_offset, batch_size);      // (moves the handle's tags: bprx_internal.h)
+  *own8 = f.planes ? h->own8 : nullptr; *loc8 = f.planes ? h->loc8 : nullptr;
+  *pl_i = f.pl_i; *pl_j = f.pl_j; *sh = f.sh;
+  // the owner queues of the same occurrences (shift 8, 2 * batch_size <= 2^24, BPRX_INDEX_QUEUE): a later call of the batch
+  // numbers its regions on behind this one's
+  *qa = QueueArgs{f.queues ? h->qrec : nullptr, f.queues ? h->qrange : nullptr, f.q0, f.qstride};
 }
 
 extern "C" int bprx_sample_epoch_h(bprx_handle *h, const int64_t *indptr, const int32_t *items_sorted, const int32_t *perm,
@@ -229,10 +275,11 @@ extern "C" int bprx_sample_epoch_h(bprx_handle *h, const int64_t *indptr, const 
   uint8_t *own8, *loc8;
   long long pl_i, pl_j;
   int sh;
-  plane_args(h, pos, neg, B, batch_offset, batch_size, &own8, &loc8, &pl_i, &pl_j, &sh);
+  QueueArgs qa;
+  plane_args(h, pos, neg, B, batch_offset, batch_size, &own8, &loc8, &pl_i, &pl_j, &sh, &qa);
   hipLaunchKernelGGL(k_sample_epoch, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, indptr,
                      items_sorted, perm, epoch_ptr, pos_slot, num_users, (uint32_t)num_items, (uint32_t)seed, (uint32_t)(seed >> 32),
-                     epoch, (long long)first, (long long)B, user, pos, neg, own8, loc8, pl_i, pl_j, sh);
+                     epoch, (long long)first, (long long)B, user, pos, neg, own8, loc8, pl_i, pl_j, sh, qa);
   return hipGetLastError() == hipSuccess ? BPRX_OK : BPRX_E_HIP;
 }
 
@@ -253,10 +300,11 @@ extern "C" int bprx_sample_philox_h(bprx_handle *h, const int64_t *indptr, const
   uint8_t *own8, *loc8;
   long long pl_i, pl_j;
   int sh;
-  plane_args(h, pos, neg, B, batch_offset, batch_size, &own8, &loc8, &pl_i, &pl_j, &sh);
+  QueueArgs qa;
+  plane_args(h, pos, neg, B, batch_offset, batch_size, &own8, &loc8, &pl_i, &pl_j, &sh, &qa);
   hipLaunchKernelGGL(k_sample_philox, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, indptr,
                      items_sorted, pos_user, (unsigned long long)num_pos, (uint32_t)num_items, (uint32_t)seed,
-                     (uint32_t)(seed >> 32), (unsigned long long)first, (long long)B, user, pos, neg, own8, loc8, pl_i, pl_j, sh);
+                     (uint32_t)(seed >> 32), (unsigned long long)first, (long long)B, user, pos, neg, own8, loc8, pl_i, pl_j, sh, qa);
   return hipGetLastError() == hipSuccess ? BPRX_OK : BPRX_E_HIP;
 }
 

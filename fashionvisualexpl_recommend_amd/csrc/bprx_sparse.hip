@@ -1056,6 +1056,10 @@ struct IndexSegArgs {
   // R == 256 and B % 16 == 0: owner w scans own8 for bytes equal to w, sixteen values per 16-byte load.
   const uint8_t *own8, *loc8;
   int wide;                       // loc8 holds 16-bit locals (R = 2^shift > 256 items per owner: num_items > 65 536)
+  // the samplers' owner queues of the batch (bprx_internal.h: ixq_*) or nullptr: R == 256, owner w reads its [lo, hi) of every
+  // one of the qn regions (its ranges: qn consecutive words at w * qstride) and nothing else
+  const uint32_t *qrec, *qrange;
+  int qn, qstride;
   // the LAST step's dense update, deferred into this launch (StepPlan::carry_dense): ndense workgroups behind the owners
   int ndense;
   DenseArgs dn;
@@ -1136,7 +1140,32 @@ __global__ __launch_bounds__(IX_T) void k_index_seg(IndexSegArgs a) {
     const unsigned mn = min(min(x0, x1), min(x2, x3));
     if (in && mn <= Wm) { one(v.x, occ); one(v.y, occ + 1); one(v.z, occ + 2); one(v.w, occ + 3); }
   };
-  if (a.own8 && a.wide) {
+  if (a.qrec) {
+    // The sampler left my occurrences in my slots [lo, hi) of every region: nothing to scan.  Four lanes per region, each takes
+    // every fourth record of the range, four loads in flight (a hot owner holds a large part of every region).  Ranges, occ and
+    // local are clamped like every index read from memory: a stale word cannot cause a wild load or store.
+    const uint32_t *myr = a.qrange + ixq_range_at(w, 0, a.qstride);
+    const unsigned otop = (unsigned)(2 * a.B - 1), ltop = (unsigned)Rw - 1u;
+    const unsigned q = (unsigned)tid & 3u;
+    for (int r = tid >> 2; r < a.qn; r += IX_T / 4) {
+      const uint32_t rg = myr[r];
+      unsigned qhi = ixq_hi(rg), qlo = ixq_lo(rg);
+      qhi = qhi < (unsigned)IXQ_REC ? qhi : (unsigned)IXQ_REC;
+      qlo = qlo < qhi ? qlo : qhi;
+      const uint32_t *rec = a.qrec + ixq_rec_at(r, 0);
+      for (unsigned x = qlo + q; x < qhi; x += 16) {
+        uint32_t v[4];
+#pragma unroll
+        for (unsigned y = 0; y < 4; ++y) v[y] = rec[x + 4 * y < qhi ? x + 4 * y : qhi - 1];
+#pragma unroll
+        for (unsigned y = 0; y < 4; ++y)
+          if (x + 4 * y < qhi) {
+            const unsigned oc = ixq_occ(v[y]), l = ixq_local(v[y]);
+            a.seg_rank[oc < otop ? oc : otop] = atomicAdd(&cnt[l < ltop ? l : ltop], 1);
+          }
+      }
+    }
+  } else if (a.own8 && a.wide) {
     // as below with 16-bit locals (two 16-byte loads of the local plane per load of the owner plane; four loads in flight)
     const uint4 *o4 = reinterpret_cast<const uint4 *>(a.own8), *l4 = reinterpret_cast<const uint4 *>(a.loc8);
     const int n16 = (int)((2 * a.B) >> 4);
@@ -2121,6 +2150,11 @@ int bprx_launch_index_pass(bprx_handle *h, const StepPlan &p, hipStream_t s) {
     x.R = p.ix_R; x.nown = p.ix_nown;                                            // (one owner workgroup per CU: plan_step)
     x.own8 = x.loc8 = nullptr; x.wide = 0;
     if (p.idx8) { x.own8 = h->own8; x.loc8 = h->loc8; x.wide = h->idx8_shift > 8; }   // the sampler left byte planes of this batch
+    x.qrec = x.qrange = nullptr; x.qn = 0; x.qstride = 0;
+    if (p.idxq) {                                         // ... and its owners' queues: they read those instead
+      x.qrec = h->qrec; x.qrange = h->qrange;
+      x.qn = p.idxq_regions; x.qstride = (int)ixq_regions(h->cfg.max_batch);
+    }
     x.seg_rank = h->seg_rank; x.seg_cnt = h->seg_cnt; x.seg_ptr = h->seg_ptr;
     x.Ce = (int)(2 * ((2 * B + x.nown - 1) / x.nown) + 64);
     x.Lc = x.R + IX_LPAD;

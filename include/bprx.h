@@ -789,7 +789,9 @@ BPRX_API int bprx_sample_epoch(const int64_t *indptr, const int32_t *items_sorte
    workgroups each read the whole batch).  batch_offset / batch_size: this call fills triplets [batch_offset, batch_offset + B)
    of a batch of batch_size, whose arrays start at user - batch_offset, pos - batch_offset, neg - batch_offset (an epoch
    crossing fills a batch in two calls; the call with batch_offset 0 comes first).  The caller must not change pos / neg between
-   the sampler and the step; any other step on the handle simply ignores (and drops) the planes.  Results are identical. */
+   the sampler and the step; any other step on the handle simply ignores (and drops) the planes.  Results are identical.
+   Up to 65 536 items (and 2 * batch_size <= 2^24) each call also leaves its item occurrences sorted by owner in queues the handle
+   owns (4 B per occurrence; a later call of the batch continues behind the earlier ones): bprx_index_pass_queue below. */
 BPRX_API int bprx_sample_philox_h(bprx_handle *h, const int64_t *indptr, const int32_t *items_sorted, const int32_t *pos_user,
                                   int64_t num_pos, int32_t num_items, uint64_t seed, uint64_t first, int64_t B, int32_t *user,
                                   int32_t *pos, int32_t *neg, int64_t batch_offset, int64_t batch_size, void *stream);
@@ -800,6 +802,12 @@ BPRX_API int bprx_sample_epoch_h(bprx_handle *h, const int64_t *indptr, const in
 /* What the index pass of the handle's last step read: 0 = no segment-mode step yet, 1 = the int32 index arrays,
    2 = the sampler's byte planes.  (Introspection for tests and benchmarks.) */
 BPRX_API int bprx_index_pass_kind(const bprx_handle *h);
+/* Whether the owner workgroups of that index pass read the sampler's owner queues (1) or scanned the planes / the index arrays
+   (0).  Up to 65 536 items and 2 * batch_size <= 2^24 the samplers above also leave every 256 triplets' item occurrences sorted
+   by owner (id >> 8), so that an owner reads its own records instead of the whole batch; bprx_index_pass_kind is 2 either way.
+   BPRX_INDEX_QUEUE=0 (read by bprx_create) keeps the plane scan.  Results are identical up to the order in which equal items'
+   occurrences are ranked, as between two runs of the scan.  (Introspection for tests and benchmarks.) */
+BPRX_API int bprx_index_pass_queue(const bprx_handle *h);
 /* Whether the projections of the handle's last step left out the feature rows of the items its batch did not touch:
    0 = both streamed every row (list mode, a step after bprx_step_project or bprx_score_block, fp32 features, fp8 features or
    more than nine column tiles unless BPRX_PROJ_MASK=2, BPRX_PROJ_MASK=0, no step yet), 1 = both passes masked, 2 = the forward pass alone (a split of the backward pass too long for its row bits),
