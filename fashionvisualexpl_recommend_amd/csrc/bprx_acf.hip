@@ -26,6 +26,9 @@
 //   k_acf_colsum    column sums of the user rows (dbc0, dbi0, dW1c, dW1i); k_acf_reduce sums partials in ascending order
 //   k_acf_proj_bwd_*  [dWci | dWix] = F^T dZ over the rows (l, m) of the listed items: MFMA GEMM, K split over the workgroups
 //   k_acf_clear     dZ / dGP rows of the listed items back to zero
+// Users the model was not trained on (bprx_acf_fold_in, bprx_acf_profile_rows, bprx_acf_score_rows_block):
+//   k_acf_fold      one workgroup per new user, the step loop inside: the forward walk, the user's pairs, a backward walk that
+//                   recomputes both levels and keeps only d / dg, the update of the caller's row; no atomics
 #include <climits>
 
 #include "bprx_internal.h"
@@ -69,6 +72,9 @@ struct AcfState {
   float *xt;                          // [xt_cap] item-level logits t_l by CSR position of the call's histories
   float *xu;                          // int64 xt_cap, then [U][2 + h]: the item softmax's max and denominator, uc
   int64_t xt_cap;
+  // bprx_acf_score_rows_block, allocated at its first call with more rows than gp holds and regrown on demand
+  float *prow;                        // [prow_cap][k] g' of the call's rows
+  int64_t prow_cap;
 };
 
 // ---- projection operand --------------------------------------------------------------------------------------------
@@ -291,6 +297,51 @@ struct AcfUserArgs {
   int U, I, k, M, hc, ha, NP;
 };
 
+#define ACF_JR 4                      // column slots per lane: h, a <= ACF_MAX_NP = 4 * 64
+
+// Both attention levels of one history entry for the row whose (uc, ui) are in LDS, shared by k_acf_user,
+// k_acf_user_bwd and k_acf_fold: leaves e^(s_m - max) in beta[M] (the calling wave's), 1 / their sum in inv, the lane's item-level relu inputs in
+// prej, and returns t_l.
+__device__ __forceinline__ float acf_entry_fwd(const AcfUserArgs &A, int l, const float *uc, const float *ui, const float *w1c,
+                                               const float *w1i, float bc1, float bi1, float *beta, int lane, float &inv,
+                                               float (&prej)[ACF_JR]) {
+  const int M = A.M, hc = A.hc, ha = A.ha, NP = A.NP;
+  const float *Zl = A.Z + (int64_t)l * M * NP;
+  float lmax = -INFINITY;
+  for (int m = lane; m < M; m += 64) {
+    const float *z = Zl + (int64_t)m * NP;
+    float s = 0.f;
+    for (int j = 0; j < hc; ++j) s = fmaf(w1c[j], fmaxf(uc[j] + z[j], 0.f), s);
+    s += bc1;
+    beta[m] = s;
+    lmax = fmaxf(lmax, s);
+  }
+  lmax = wave_max(lmax);
+  wave_sync();
+  float lsum = 0.f;
+  for (int m = lane; m < M; m += 64) {
+    const float e = expf(beta[m] - lmax);
+    beta[m] = e;
+    lsum += e;
+  }
+  lsum = wave_sum(lsum);
+  wave_sync();
+  inv = 1.0f / lsum;
+  float tp = 0.f;
+#pragma unroll
+  for (int i = 0; i < ACF_JR; ++i) {
+    const int j = lane + 64 * i;
+    prej[i] = 0.f;
+    if (j < ha) {
+      float xz = 0.f;
+      for (int m = 0; m < M; ++m) xz = fmaf(beta[m], Zl[(int64_t)m * NP + hc + j], xz);
+      prej[i] = ui[j] + A.GP[(int64_t)l * ha + j] + xz * inv;
+      tp = fmaf(w1i[j], fmaxf(prej[i], 0.f), tp);
+    }
+  }
+  return wave_sum(tp) + bi1;
+}
+
 // One workgroup (4 waves) per position b.  Wave w walks history entries w, w+4, ...; for each item l:
 //   s_m = w1c.relu(uc + Z_lm[:h]) + bc1 (lane per m), beta = softmax_m(s), xz = sum_m beta_m Z_lm[h:] (lane per column),
 //   t = w1i.relu(ui + GP_l + xz) + bi1; the wave keeps a running max / denominator / sum of e^(t - max) Pi_l.
@@ -341,34 +392,8 @@ __global__ __launch_bounds__(256) void k_acf_user(AcfUserArgs A, const int32_t *
   float mx = -INFINITY, den = 0.f;
   for (int64_t p = beg + w; p < end; p += 4) {
     const int l = clamp_index(A.items[p], A.I, A.errflag, 5);
-    const float *Zl = A.Z + (int64_t)l * M * NP;
-    float lmax = -INFINITY;
-    for (int m = lane; m < M; m += 64) {
-      const float *z = Zl + (int64_t)m * NP;
-      float s = 0.f;
-      for (int j = 0; j < hc; ++j) s = fmaf(w1c[j], fmaxf(uc[j] + z[j], 0.f), s);
-      s += bc1;
-      beta[m] = s;
-      lmax = fmaxf(lmax, s);
-    }
-    lmax = wave_max(lmax);
-    wave_sync();
-    float lsum = 0.f;
-    for (int m = lane; m < M; m += 64) {
-      const float e = expf(beta[m] - lmax);
-      beta[m] = e;
-      lsum += e;
-    }
-    lsum = wave_sum(lsum);
-    wave_sync();
-    const float inv = 1.0f / lsum;
-    float tp = 0.f;
-    for (int j = lane; j < ha; j += 64) {
-      float xz = 0.f;
-      for (int m = 0; m < M; ++m) xz = fmaf(beta[m], Zl[(int64_t)m * NP + hc + j], xz);
-      tp = fmaf(w1i[j], fmaxf(ui[j] + A.GP[(int64_t)l * ha + j] + xz * inv, 0.f), tp);
-    }
-    const float t = wave_sum(tp) + bi1;
+    float inv, prej[ACF_JR];
+    const float t = acf_entry_fwd(A, l, uc, ui, w1c, w1i, bc1, bi1, beta, lane, inv, prej);
     const float nmx = fmaxf(mx, t);
     const float sc = expf(mx - nmx), e = expf(t - nmx);        // (mx = -inf at the first item: sc = 0)
     den = den * sc + e;
@@ -745,8 +770,6 @@ struct AcfBwdArgs {
   float *dZ, *dGP, *dPi, *dGu, *UV;
 };
 
-#define ACF_JR 4                      // column slots per lane: h, a <= ACF_MAX_NP = 4 * 64
-
 // One workgroup (4 waves) per distinct user, at the user's first position b.  Wave w walks history entries w, w+4, ... and
 // recomputes beta_l, pre_l and t_l as k_acf_user does; alpha_l = e^(t_l - max) / den comes from the forward's aux row, and
 // sum_l alpha_l Pi_l . q from its stored attention part.  Per entry: dt, dpre (dGP_l, dPi_l by atomics), dbeta, ds, then a pass
@@ -806,39 +829,8 @@ __global__ __launch_bounds__(256) void k_acf_user_bwd(AcfUserArgs A, AcfBwdArgs 
     for (int64_t p = beg + w; p < end; p += 4) {
       const int l = clamp_index(A.items[p], A.I, A.errflag, 5);
       const float *Zl = A.Z + (int64_t)l * M * NP;
-      float lmax = -INFINITY;
-      for (int m = lane; m < M; m += 64) {                   // component scores, as k_acf_user
-        const float *z = Zl + (int64_t)m * NP;
-        float s = 0.f;
-        for (int j = 0; j < hc; ++j) s = fmaf(w1c[j], fmaxf(uc[j] + z[j], 0.f), s);
-        s += bc1;
-        beta[m] = s;
-        lmax = fmaxf(lmax, s);
-      }
-      lmax = wave_max(lmax);
-      wave_sync();
-      float lsum = 0.f;
-      for (int m = lane; m < M; m += 64) {
-        const float e = expf(beta[m] - lmax);
-        beta[m] = e;
-        lsum += e;
-      }
-      lsum = wave_sum(lsum);
-      wave_sync();
-      const float inv = 1.0f / lsum;
-      float prej[ACF_JR], tp = 0.f;
-#pragma unroll
-      for (int i = 0; i < ACF_JR; ++i) {
-        const int j = lane + 64 * i;
-        prej[i] = 0.f;
-        if (j < ha) {
-          float xz = 0.f;
-          for (int m = 0; m < M; ++m) xz = fmaf(beta[m], Zl[(int64_t)m * NP + hc + j], xz);
-          prej[i] = ui[j] + A.GP[(int64_t)l * ha + j] + xz * inv;
-          tp = fmaf(w1i[j], fmaxf(prej[i], 0.f), tp);
-        }
-      }
-      const float t = wave_sum(tp) + bi1;
+      float inv, prej[ACF_JR];
+      const float t = acf_entry_fwd(A, l, uc, ui, w1c, w1i, bc1, bi1, beta, lane, inv, prej);
       const float alpha = expf(t - gm) / D;
       const float *pl = A.Pi + (int64_t)l * k;
       float r = 0.f;
@@ -932,6 +924,267 @@ __global__ __launch_bounds__(256) void k_acf_user_bwd(AcfUserArgs A, AcfBwdArgs 
     for (int j = 0; j < hc; ++j) s = fmaf(A.wcu[(int64_t)c * hc + j], fin[j], s);
     for (int j = 0; j < ha; ++j) s = fmaf(A.wiu[(int64_t)c * ha + j], fin[hc + j], s);
     G.dGu[(int64_t)u * k + c] += s;
+  }
+}
+
+// ---- users the model was not trained on (bprx_acf_fold_in) ------------------------------------------------------------
+struct AcfFold {
+  AcfUserArgs A;                      // Gu is not read (the rows are the caller's); ptr / items: the call's histories, by ROW
+  const float *Gi;
+  const int64_t *pptr;                // [n + 1] pairs of row r: [pptr[r], pptr[r + 1])
+  const int32_t *pos, *neg;
+  int steps, adam;
+  float lr, reg, b1, b2, eps;
+  float *Gu, *loss;                   // [n, k] in / out; [n] or nullptr
+  int cache;                          // floats of LDS behind the fixed part (0: every pair is gathered every step)
+};
+constexpr int ACF_FOLD_EPL = ACF_MAX_K / 64;    // elements of a row per lane
+constexpr int ACF_FOLD_EPT = ACF_MAX_K / 256;   // ... per thread
+
+// One workgroup (4 waves) per new user r, resident across the steps (include/bprx.h, bprx_acf_fold_in).  Per step:
+//   uc / ui from g; the forward walk of k_acf_user (wave w: entries w, w + 4, ...; online softmax per wave, merged) -> the item
+//   softmax's max gm and denominator D, ap = sum_l alpha_l Pi_l;
+//   the pairs (wave w: pairs w, w + 4, ...; D_p = Gi_i - Gi_j a lane-strided register row, from the cache area for the first nc
+//   pairs after the first step): x_p = (g + ap).D_p, the wave's compensated sum of -s_p D_p and its loss terms; the four waves'
+//   sums are added as (0 + 1) + (2 + 3) -> q;
+//   the backward walk of k_acf_user_bwd over the entries, recomputing both levels, keeping only what reaches g: per-lane column
+//   sums of dpre_l and da_lm in entry order, merged over the waves as (0 + 1) + (2 + 3);
+//   grad = q + Wcu sum da + Wiu sum dpre + 2 reg n_r g, thread c owns g_c and its Adam slots.
+// Nothing depends on another workgroup, on the cache size or on the grid; no atomics (but the error flag).
+// LDS (floats): ls[4] (double) | g[k] ap[k] q[k] uc[h] ui[a] w1c[h] w1i[a] | per wave: beta[M] dbeta[M] dpre[a] acc[k] |
+//               red[4][h + a] fin[h + a] wmx[4] wden[4] rb[4] | cache[nc][k]
+__global__ __launch_bounds__(256) void k_acf_fold(AcfFold F) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const AcfUserArgs &A = F.A;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int64_t r = blockIdx.x;
+  const int64_t p0 = F.pptr[r], np64 = F.pptr[r + 1] - p0;
+  if (np64 <= 0) {                                           // no pairs: the row stays, the loss is 0 (the whole workgroup leaves)
+    if (tid == 0 && F.loss) F.loss[r] = 0.f;
+    return;
+  }
+  const int np = np64 > INT32_MAX ? INT32_MAX : (int)np64;
+  const int k = A.k, M = A.M, hc = A.hc, ha = A.ha, NP = A.NP, W = hc + ha;
+  double *lsd = (double *)sm;
+  float *g = sm + 8, *ap = g + k, *qs = ap + k, *uc = qs + k, *ui = uc + hc, *w1c = ui + ha, *w1i = w1c + hc;
+  float *wbase = w1i + ha;
+  const size_t wstride = 2 * (size_t)M + ha + k;
+  float *beta = wbase + (size_t)w * wstride, *dbeta = beta + M, *dpre = dbeta + M, *acc = dpre + ha;
+  float *red = wbase + 4 * wstride, *fin = red + 4 * (size_t)W, *wmx = fin + W, *wden = wmx + 4, *rb = wden + 4;
+  float *cache = rb + 4;
+  const int fit = F.cache / k, nc = np < fit ? np : fit;
+  const int32_t *pos = F.pos + p0, *neg = F.neg + p0;
+  const int64_t beg = A.ptr[r], end = A.ptr[r + 1];
+  float gw[ACF_FOLD_EPT], am[ACF_FOLD_EPT], av[ACF_FOLD_EPT];
+#pragma unroll
+  for (int e = 0; e < ACF_FOLD_EPT; ++e) {
+    const int c = tid + 256 * e;
+    gw[e] = c < k ? F.Gu[r * k + c] : 0.f;
+    am[e] = 0.f; av[e] = 0.f;
+    if (c < k) g[c] = gw[e];
+  }
+  for (int j = tid; j < hc; j += 256) w1c[j] = A.w1c[j];
+  for (int j = tid; j < ha; j += 256) w1i[j] = A.w1i[j];
+  __syncthreads();
+  const float bc1 = A.bc1[0], bi1 = A.bi1[0];
+  const float r2n = 2.f * F.reg * (float)np, rn = F.reg * (float)np;
+  for (int t = 1; t <= F.steps; ++t) {
+    const bool last = t == F.steps && F.loss != nullptr;
+    for (int j = tid; j < W; j += 256) {                       // W_0_u^T g + b_0 of both levels, as k_acf_user
+      float s = 0.f;
+      if (j < hc) {
+        for (int c = 0; c < k; ++c) s = fmaf(g[c], A.wcu[(int64_t)c * hc + j], s);
+        uc[j] = s + A.bc0[j];
+      } else {
+        const int jj = j - hc;
+        for (int c = 0; c < k; ++c) s = fmaf(g[c], A.wiu[(int64_t)c * ha + jj], s);
+        ui[jj] = s + A.bi0[jj];
+      }
+    }
+    for (int c = lane; c < k; c += 64) acc[c] = 0.f;
+    __syncthreads();
+    // ---- forward over the history ----
+    float prej[ACF_JR], inv;
+    float mx = -INFINITY, den = 0.f;
+    for (int64_t p = beg + w; p < end; p += 4) {
+      const int l = clamp_index(A.items[p], A.I, A.errflag, 5);
+      const float tl = acf_entry_fwd(A, l, uc, ui, w1c, w1i, bc1, bi1, beta, lane, inv, prej);
+      const float nmx = fmaxf(mx, tl);
+      const float sc = expf(mx - nmx), e = expf(tl - nmx);     // (mx = -inf at the first entry: sc = 0)
+      den = den * sc + e;
+      const float *pl = A.Pi + (int64_t)l * k;
+      for (int c = lane; c < k; c += 64) acc[c] = acc[c] * sc + e * pl[c];
+      mx = nmx;
+      wave_sync();                                             // beta is rewritten by the next entry
+    }
+    if (lane == 0) { wmx[w] = mx; wden[w] = den; }
+    __syncthreads();
+    float gm = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) gm = fmaxf(gm, wmx[q]);
+    float f[4], D = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      f[q] = wden[q] > 0.f ? expf(wmx[q] - gm) : 0.f;
+      D += wden[q] * f[q];
+    }
+    for (int c = tid; c < k; c += 256) {
+      float s = 0.f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (f[q] != 0.f) s += wbase[(size_t)q * wstride + 2 * M + ha + c] * f[q];
+      ap[c] = D > 0.f ? s / D : 0.f;                           // sum_l alpha_l Pi_l
+    }
+    __syncthreads();
+    // ---- the pairs ----
+    {
+      float qa[ACF_FOLD_EPL], qc[ACF_FOLD_EPL], gp[ACF_FOLD_EPL];      // -s_p D_p summed (Kahan) over this wave's pairs; g'
+      double ls = 0.0;
+#pragma unroll
+      for (int e = 0; e < ACF_FOLD_EPL; ++e) {
+        const int c = lane + 64 * e;
+        qa[e] = 0.f; qc[e] = 0.f;
+        gp[e] = c < k ? g[c] + ap[c] : 0.f;
+      }
+      for (int p = w; p < np; p += 4) {
+        float d[ACF_FOLD_EPL], x = 0.f;
+        if (p < nc && t > 1) {                                 // (a lane reads back what it wrote itself)
+#pragma unroll
+          for (int e = 0; e < ACF_FOLD_EPL; ++e) {
+            const int c = lane + 64 * e;
+            d[e] = c < k ? cache[(size_t)p * k + c] : 0.f;
+          }
+        } else {
+          const int i = clamp_index(pos[p], A.I, A.errflag, 2), j = clamp_index(neg[p], A.I, A.errflag, 2);
+          const float *gi = F.Gi + (int64_t)i * k, *gj = F.Gi + (int64_t)j * k;
+#pragma unroll
+          for (int e = 0; e < ACF_FOLD_EPL; ++e) {
+            const int c = lane + 64 * e;
+            d[e] = c < k ? gi[c] - gj[c] : 0.f;
+            if (p < nc && c < k) cache[(size_t)p * k + c] = d[e];
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < ACF_FOLD_EPL; ++e) x = fmaf(gp[e], d[e], x);
+        const float diff = wave_sum(x);
+        const bool inr = (diff >= -80.0f) && (diff <= 1e8f);             // tf.clip_by_value gradient mask
+        const float z = -fminf(fmaxf(diff, -80.0f), 1e8f);
+        ls += (double)(z > 0.f ? z + log1pf(expf(-z)) : log1pf(expf(z)));
+        const float gd = inr ? -1.0f / (1.0f + expf(diff)) : 0.f;        // -s_p
+#pragma unroll
+        for (int e = 0; e < ACF_FOLD_EPL; ++e) {               // compensated: thousands of pairs pushing one way must not round
+          const float y = gd * d[e] - qc[e];                   // every add at the ulp of the whole sum
+          const float ts = qa[e] + y;
+          qc[e] = (ts - qa[e]) - y;
+          qa[e] = ts;
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < ACF_FOLD_EPL; ++e) {
+        const int c = lane + 64 * e;
+        if (c < k) acc[c] = qa[e];
+      }
+      if (lane == 0) lsd[w] = ls;
+    }
+    __syncthreads();
+    for (int c = tid; c < k; c += 256)
+      qs[c] = (wbase[2 * M + ha + c] + wbase[wstride + 2 * M + ha + c]) +
+              (wbase[2 * wstride + 2 * M + ha + c] + wbase[3 * wstride + 2 * M + ha + c]);
+    __syncthreads();
+    // ---- backward over the history ----
+    {
+      float pr = 0.f;
+      for (int c = tid; c < k; c += 256) pr = fmaf(ap[c], qs[c], pr);
+      pr = wave_sum(pr);
+      if (lane == 0) rb[w] = pr;
+    }
+    __syncthreads();
+    const float rbar = (rb[0] + rb[1]) + (rb[2] + rb[3]);      // sum_l alpha_l Pi_l . q
+    float duc_r[ACF_JR], dui_r[ACF_JR];
+#pragma unroll
+    for (int i = 0; i < ACF_JR; ++i) duc_r[i] = dui_r[i] = 0.f;
+    if (D > 0.f) {
+      for (int64_t p = beg + w; p < end; p += 4) {
+        const int l = clamp_index(A.items[p], A.I, A.errflag, 5);
+        const float *Zl = A.Z + (int64_t)l * M * NP;
+        const float tl = acf_entry_fwd(A, l, uc, ui, w1c, w1i, bc1, bi1, beta, lane, inv, prej);
+        const float alpha = expf(tl - gm) / D;
+        const float *pl = A.Pi + (int64_t)l * k;
+        float rr = 0.f;
+        for (int c = lane; c < k; c += 64) rr = fmaf(pl[c], qs[c], rr);
+        rr = wave_sum(rr);
+        const float dt = alpha * (rr - rbar);
+#pragma unroll
+        for (int i = 0; i < ACF_JR; ++i) {
+          const int j = lane + 64 * i;
+          if (j < ha) {
+            const float dp = prej[i] > 0.f ? dt * w1i[j] : 0.f;
+            dpre[j] = dp;
+            dui_r[i] += dp;
+          }
+        }
+        wave_sync();
+        float bsum = 0.f;
+        for (int m = lane; m < M; m += 64) {                   // dbeta_lm = Z_lm[h:] . dpre_l
+          const float *z = Zl + (int64_t)m * NP + hc;
+          float d = 0.f;
+          for (int j = 0; j < ha; ++j) d = fmaf(z[j], dpre[j], d);
+          const float bn = beta[m] * inv;
+          beta[m] = bn;
+          bsum = fmaf(bn, d, bsum);
+          dbeta[m] = d;
+        }
+        bsum = wave_sum(bsum);
+        for (int m = lane; m < M; m += 64) dbeta[m] = beta[m] * (dbeta[m] - bsum);      // ds_lm (the lane's own entries)
+        wave_sync();
+        for (int m = 0; m < M; ++m) {                           // a lane per column: sum_m da_lm
+          const float ds = dbeta[m];
+          const float *z = Zl + (int64_t)m * NP;
+#pragma unroll
+          for (int i = 0; i < ACF_JR; ++i) {
+            const int j = lane + 64 * i;
+            if (j < hc && uc[j] + z[j] > 0.f) duc_r[i] += ds * w1c[j];
+          }
+        }
+        wave_sync();                                             // beta / dbeta / dpre are rewritten by the next entry
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < ACF_JR; ++i) {
+      const int j = lane + 64 * i;
+      if (j < hc) red[(size_t)w * W + j] = duc_r[i];
+      if (j < ha) red[(size_t)w * W + hc + j] = dui_r[i];
+    }
+    __syncthreads();
+    for (int e = tid; e < W; e += 256) fin[e] = (red[e] + red[(size_t)W + e]) + (red[2 * (size_t)W + e] + red[3 * (size_t)W + e]);
+    if (last && w == 0) {                                      // loss_T, before the last update
+      float s = 0.f;
+      for (int c = lane; c < k; c += 64) s = fmaf(g[c], g[c], s);
+      s = wave_sum(s);
+      if (lane == 0) F.loss[r] = (float)(((lsd[0] + lsd[1]) + (lsd[2] + lsd[3])) + (double)(rn * s));
+    }
+    __syncthreads();
+    const float tt = (float)t;
+    const float lr_t = F.adam ? F.lr * sqrtf(1.0f - powf(F.b2, tt)) / (1.0f - powf(F.b1, tt)) : F.lr;
+#pragma unroll
+    for (int e = 0; e < ACF_FOLD_EPT; ++e) {
+      const int c = tid + 256 * e;
+      if (c < k) {
+        float s = qs[c];
+        for (int j = 0; j < hc; ++j) s = fmaf(A.wcu[(int64_t)c * hc + j], fin[j], s);
+        for (int j = 0; j < ha; ++j) s = fmaf(A.wiu[(int64_t)c * ha + j], fin[hc + j], s);
+        const float gr = s + r2n * gw[e];
+        if (F.adam) adam_elem(gw[e], am[e], av[e], gr, F.b1, F.b2, lr_t, F.eps);
+        else gw[e] = gw[e] - lr_t * gr;
+        g[c] = gw[e];
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int e = 0; e < ACF_FOLD_EPT; ++e) {
+    const int c = tid + 256 * e;
+    if (c < k) F.Gu[r * k + c] = gw[e];
   }
 }
 
@@ -1292,11 +1545,12 @@ static size_t acf_user_lds(const AcfState *S) {
   return sizeof(float) * ((size_t)S->k + 2 * (S->hc + S->ha) + 4 * (size_t)(S->M + S->k) + 8);
 }
 
+// Gu_rows: the user rows (nullptr: the handle's own Gu); with users == nullptr position b is row b of that table and of the CSR
 static int acf_users(bprx_handle *h, const int32_t *users, int64_t n, const int32_t *uslot, const int64_t *ptr,
-                     const int32_t *items, float *out, hipStream_t s, float *aux = nullptr) {
+                     const int32_t *items, float *out, hipStream_t s, float *aux = nullptr, const float *Gu_rows = nullptr) {
   AcfState *S = h->acf;
   AcfUserArgs A;
-  A.Gu = h->t.Gu; A.Pi = S->a.Pi; A.Z = S->Z; A.GP = S->GP;
+  A.Gu = Gu_rows ? Gu_rows : h->t.Gu; A.Pi = S->a.Pi; A.Z = S->Z; A.GP = S->GP;
   A.wcu = S->a.w[BPRX_ACF_C_WU]; A.bc0 = S->a.w[BPRX_ACF_C_B0]; A.w1c = S->a.w[BPRX_ACF_C_W1]; A.bc1 = S->a.w[BPRX_ACF_C_B1];
   A.wiu = S->a.w[BPRX_ACF_I_WU]; A.bi0 = S->a.w[BPRX_ACF_I_B0]; A.w1i = S->a.w[BPRX_ACF_I_W1]; A.bi1 = S->a.w[BPRX_ACF_I_B1];
   A.ptr = ptr; A.items = items; A.errflag = h->errflag;
@@ -1606,6 +1860,97 @@ extern "C" int bprx_acf_profiles(bprx_handle *h, const int32_t *users, int64_t n
   int rc;
   if ((rc = acf_prepare(h, users, n, nullptr, hist_ptr, hist_items, s))) return rc;
   return acf_users(h, users, n, nullptr, hist_ptr, hist_items, out, s);
+}
+
+// ---- caller-owned rows: users folded in by bprx_acf_fold_in (include/bprx.h) -------------------------------------------------
+static int acf_rows_args(bprx_handle *h, const char *what, int64_t n) {
+  if (n < 0 || n >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "%s: n = %lld out of range", what, (long long)n);
+  return BPRX_OK;
+}
+
+extern "C" int bprx_acf_profile_rows(bprx_handle *h, const float *Gu_rows, int64_t n, const int64_t *hist_ptr,
+                                     const int32_t *hist_items, float *out, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  int rc;
+  if ((rc = acf_rows_args(h, "acf_profile_rows", n))) return rc;
+  if (!hist_ptr || (n && (!Gu_rows || !hist_items || !out))) BPRX_FAIL(h, BPRX_E_INVALID, "acf_profile_rows: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  rc = bprx_enter(h, "acf_profile_rows", NEED_BOUND, KIND_ACF, s);
+  if (rc || n == 0) return rc;
+  if ((rc = acf_prepare(h, nullptr, n, nullptr, hist_ptr, hist_items, s))) return rc;
+  return acf_users(h, nullptr, n, nullptr, hist_ptr, hist_items, out, s, nullptr, Gu_rows);
+}
+
+int bprx_acf_row_profiles(bprx_handle *h, const float *Gu_rows, int64_t r0, int64_t r1, const int64_t *hist_ptr,
+                          const int32_t *hist_items, float **gp, hipStream_t s) {
+  AcfState *S = h->acf;
+  const int64_t n = r1 - r0;
+  float *ws = S->gp;
+  if (n > h->cfg.max_batch) {
+    if (n > S->prow_cap) {
+      BPRX_HIP(h, hipStreamSynchronize(s));                    // (an earlier call's score kernel on this stream may still read the old buffer)
+      S->prow_cap = 0;
+      if (S->mem.regrow(&S->prow, (size_t)n * S->k) != hipSuccess)
+        BPRX_FAIL(h, BPRX_E_NOMEM, "acf_score_rows_block: workspace allocation failed (%zu MB)", ((size_t)n * S->k * 4) >> 20);
+      S->prow_cap = n;
+    }
+    ws = S->prow;
+  }
+  int rc;
+  if ((rc = acf_prepare(h, nullptr, n, nullptr, hist_ptr + r0, hist_items, s))) return rc;
+  if ((rc = acf_users(h, nullptr, n, nullptr, hist_ptr + r0, hist_items, ws, s, nullptr, Gu_rows + r0 * S->k))) return rc;
+  *gp = ws;
+  return BPRX_OK;
+}
+
+// LDS of a k_acf_fold workgroup: what the walk needs, and behind it the cached pair differences.  Where the fixed part leaves
+// room the total is 40 KB, the budget of bprx_fold_in and bprx_af_fold_in.  The kernel's 162 VGPRs let three workgroups share a CU,
+// so up to 53 KB would cost no occupancy; the cache is not what binds (all 80 pairs of a user against 60: BPRX_FOLD_CACHE=0 costs
+// 2.6 % at the measured shape), and a larger budget has not been measured.
+constexpr size_t ACF_FOLD_LDS = 40 * 1024;
+static size_t acf_fold_fixed(const AcfState *S) {
+  const size_t hw = (size_t)S->hc + S->ha;
+  return sizeof(float) * (20 + 3 * (size_t)S->k + 7 * hw + 4 * (2 * (size_t)S->M + S->ha + S->k));
+}
+
+extern "C" int bprx_acf_fold_in(bprx_handle *h, const int64_t *hist_ptr, const int32_t *hist_items, const int64_t *pair_ptr,
+                                const int32_t *pos, const int32_t *neg, int64_t n, int32_t steps, float lr, float reg,
+                                int32_t optimizer, float *Gu_rows, float *loss, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  int rc;
+  if ((rc = acf_rows_args(h, "acf_fold_in", n))) return rc;
+  if (steps < 1) BPRX_FAIL(h, BPRX_E_INVALID, "acf_fold_in: steps = %d < 1", steps);
+  if (optimizer != BPRX_OPT_SGD && optimizer != BPRX_OPT_ADAM_TF23) BPRX_FAIL(h, BPRX_E_INVALID, "acf_fold_in: optimizer %d", optimizer);
+  if (!hist_ptr || !pair_ptr || !Gu_rows) BPRX_FAIL(h, BPRX_E_INVALID, "acf_fold_in: null pointer");
+  if (n && (!hist_items || !pos || !neg)) BPRX_FAIL(h, BPRX_E_INVALID, "acf_fold_in: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  rc = bprx_enter(h, "acf_fold_in", NEED_BOUND, KIND_ACF, s);
+  if (rc) return rc;
+  AcfState *S = h->acf;
+  const size_t fixed = acf_fold_fixed(S);
+  if (fixed > 65536)
+    BPRX_FAIL(h, BPRX_E_INVALID, "acf_fold_in: M = %d, embed_k = %d, h = %d, a = %d need %zu bytes of LDS, more than a workgroup has",
+              S->M, S->k, S->hc, S->ha, fixed);
+  if (n == 0) return BPRX_OK;
+  if ((rc = acf_prepare(h, nullptr, n, nullptr, hist_ptr, hist_items, s))) return rc;   // Z / GP of the distinct history items
+  const bprx_config &c = h->cfg;
+  AcfFold F;
+  AcfUserArgs &A = F.A;
+  A.Gu = nullptr; A.Pi = S->a.Pi; A.Z = S->Z; A.GP = S->GP;
+  A.wcu = S->a.w[BPRX_ACF_C_WU]; A.bc0 = S->a.w[BPRX_ACF_C_B0]; A.w1c = S->a.w[BPRX_ACF_C_W1]; A.bc1 = S->a.w[BPRX_ACF_C_B1];
+  A.wiu = S->a.w[BPRX_ACF_I_WU]; A.bi0 = S->a.w[BPRX_ACF_I_B0]; A.w1i = S->a.w[BPRX_ACF_I_W1]; A.bi1 = S->a.w[BPRX_ACF_I_B1];
+  A.ptr = hist_ptr; A.items = hist_items; A.errflag = h->errflag;
+  A.U = c.num_users; A.I = c.num_items; A.k = S->k; A.M = S->M; A.hc = S->hc; A.ha = S->ha; A.NP = S->NP;
+  F.Gi = h->t.Gi; F.pptr = pair_ptr; F.pos = pos; F.neg = neg;
+  F.steps = steps; F.adam = optimizer == BPRX_OPT_ADAM_TF23;
+  F.lr = lr; F.reg = reg; F.b1 = c.beta1; F.b2 = c.beta2; F.eps = c.epsilon;
+  F.Gu = Gu_rows; F.loss = loss;
+  const size_t total = fixed > ACF_FOLD_LDS ? fixed : ACF_FOLD_LDS;
+  F.cache = h->fold_cache ? (int)((total - fixed) / sizeof(float)) : 0;
+  BprxProfScope ps(h, BPRX_PHASE_TRIPLET, s);
+  hipLaunchKernelGGL(k_acf_fold, dim3((unsigned)n), dim3(256), fixed + (size_t)F.cache * sizeof(float), s, F);
+  BPRX_LAUNCH_CHECK(h, "k_acf_fold");
+  return BPRX_OK;
 }
 
 // Workspace of the full-gradient mode, allocated at the first switch to it (a detached handle never pays for it)

@@ -674,6 +674,22 @@ extern "C" int bprx_score_rows_block(bprx_handle *h, const float *Gu_rows, const
   return score_rows(h, (int32_t)r0, (int32_t)r1, out, s, {Gu_rows, Tu_rows});
 }
 
+// bprx_score_block of an ACF handle for caller-owned rows (users folded in by bprx_acf_fold_in): g' of the rows with the caller's
+// histories, then the same scoring kernels
+extern "C" int bprx_acf_score_rows_block(bprx_handle *h, const float *Gu_rows, int64_t n_rows, const int64_t *hist_ptr,
+                                         const int32_t *hist_items, int64_t r0, int64_t r1, float *out, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (n_rows < 0 || n_rows >= ((int64_t)1 << 31) || r0 < 0 || r1 > n_rows || r0 > r1)
+    BPRX_FAIL(h, BPRX_E_INVALID, "acf_score_rows_block: bad row range [%lld,%lld) of %lld", (long long)r0, (long long)r1, (long long)n_rows);
+  if (r0 != r1 && (!Gu_rows || !hist_ptr || !hist_items || !out)) BPRX_FAIL(h, BPRX_E_INVALID, "acf_score_rows_block: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  int rc = bprx_enter(h, "acf_score_rows_block", NEED_BOUND, KIND_ACF, s);
+  if (rc || r0 == r1) return rc;
+  float *gp = nullptr;
+  if ((rc = bprx_acf_row_profiles(h, Gu_rows, r0, r1, hist_ptr, hist_items, &gp, s))) return rc;
+  return score_rows(h, 0, (int32_t)(r1 - r0), out, s, {gp, h->t.Tu});
+}
+
 // ---- items outside the catalogue (include/bprx.h): bprx_project_rows here, bprx_score_new_block / bprx_topk_rows in
 // bprx_eval.hip, bprx_feat_explain_new in bprx_explain.hip ----
 extern "C" int32_t bprx_proj_stride(const bprx_handle *h) {

@@ -407,6 +407,9 @@ int bprx_acf_step(bprx_handle *h, const int32_t *u, const int32_t *i, const int3
 int bprx_acf_score_pairs(bprx_handle *h, const int32_t *u, const int32_t *i, int64_t B, float *x, hipStream_t s);
 int bprx_acf_eval_profiles(bprx_handle *h, hipStream_t s);   // g'_u of every user (evaluation histories) into acf_eval_gu()
 float *bprx_acf_eval_gu(bprx_handle *h);
+// g'_r of rows [r0, r1) of a caller's table with the histories of a CSR indexed by row: *gp = where they are, [(r1 - r0), k]
+int bprx_acf_row_profiles(bprx_handle *h, const float *Gu_rows, int64_t r0, int64_t r1, const int64_t *hist_ptr,
+                          const int32_t *hist_items, float **gp, hipStream_t s);
 void bprx_acf_invalidate(bprx_handle *h);                    // bound tables written from outside
 void bprx_acf_free(bprx_handle *h);
 // AttentiveFashion (bprx_attentive.hip): what bprx_step / bprx_score_pairs / bprx_score_block do on a handle bound with bprx_bind_attentive
@@ -595,8 +598,8 @@ enum : unsigned {
   NEED_P_ALL = 8,                 // VBPR: P holds the projection of every item (makes the image current on the way)
 };
 constexpr const char *BPRX_NOT_BOUND = "%s: tables not bound (call bprx_bind_tables first)";   // (also the step path's message)
-enum { KIND_ANY = 0, KIND_PLAIN, KIND_VBPR, KIND_VBPR_NO_FP8, KIND_FACTORED, KIND_AF };   // PLAIN: BPRMF / VBPR, not ACF / AttentiveFashion;
-                                                                                            // AF: bound with bprx_bind_attentive
+enum { KIND_ANY = 0, KIND_PLAIN, KIND_VBPR, KIND_VBPR_NO_FP8, KIND_FACTORED, KIND_AF, KIND_ACF };   // PLAIN: BPRMF / VBPR, not ACF /
+                                                   // AttentiveFashion; AF: bound with bprx_bind_attentive; ACF: with bprx_bind_acf
 struct ReadPlan {
   int error;                      // 0, or BPRX_E_STATE (not bound) / BPRX_E_INVALID (a handle of the wrong kind): nothing is launched
   const char *why;                // ... and its message, a format with one %s for the name of the entry
@@ -618,6 +621,7 @@ inline ReadPlan plan_read(const bprx_handle &h, unsigned need, int kind) {
                                 "were scaled for and would saturate): fp32 or bf16");
   if (kind == KIND_FACTORED && !h.factored) return fail(BPRX_E_INVALID, "%s: the handle is not bound with bprx_bind_factored");
   if (kind == KIND_AF && !h.af) return fail(BPRX_E_INVALID, "%s: the handle is not bound with bprx_bind_attentive");
+  if (kind == KIND_ACF && !h.acf) return fail(BPRX_E_INVALID, "%s: the handle is not bound with bprx_bind_acf");
   p.settle = h.pend.on;
   p.sync = (need & NEED_ROWS) && plain && h.adam_lazy && h.adam_synced < h.adam_t;
   p.project = (need & NEED_P_ALL) && plain && vb && !h.p_valid;

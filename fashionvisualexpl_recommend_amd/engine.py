@@ -335,6 +335,56 @@ class Engine:
                                                      _stream()))
         return out
 
+    def _acf_rows(self, what, Gu_rows, lists, csr):
+        """(hist_ptr, hist_items, n) of a caller-owned table Gu_rows [n, k] and its histories by row."""
+        ptr, items = csr if csr is not None else self.csr(lists)
+        n = int(ptr.numel()) - 1
+        if not (Gu_rows.is_cuda and Gu_rows.dtype == torch.float32 and Gu_rows.is_contiguous() and tuple(Gu_rows.shape) == (n, self.k)):
+            raise ValueError("%s: Gu_rows must be a contiguous fp32 device tensor [%d, %d]" % (what, n, self.k))
+        return ptr, items, n
+
+    def acf_fold_in(self, pair_ptr, pos, neg, steps, Gu_rows, lists=None, csr=None, lr=None, reg=None, optimizer=None,
+                    want_loss=True):
+        """bprx_acf_fold_in: `steps` optimiser steps on each row of Gu_rows [n, k] (a contiguous fp32 device tensor, updated IN
+        PLACE) over the pairs (pos[p], neg[p]), p in [pair_ptr[r], pair_ptr[r + 1]), of row r, through both attention levels over
+        the row's history (`lists` per row, or a prebuilt `csr`), everything but the row frozen.  pair_ptr: int64 [n + 1].
+        lr / reg / optimizer default to the engine's.  Returns loss fp32 [n] (loss_steps, before the last update) or None."""
+        hp, hi, n = self._acf_rows("acf_fold_in", Gu_rows, lists, csr)
+        ptr = torch.as_tensor(pair_ptr, dtype=torch.int64).to(self.device).contiguous()
+        if int(ptr.numel()) - 1 != n:
+            raise ValueError("acf_fold_in: pair_ptr for %d rows, histories for %d" % (int(ptr.numel()) - 1, n))
+        p_, n_ = as_index(pos, self.device), as_index(neg, self.device)
+        if p_.numel() != n_.numel():
+            raise ValueError("acf_fold_in: %d positives for %d negatives" % (p_.numel(), n_.numel()))
+        lr = self._hyper()[0] if lr is None else float(lr)
+        reg = self._hyper()[1] if reg is None else float(reg)
+        opt = _ffi.OPTIMIZER[self.optimizer if optimizer is None else optimizer]
+        loss = torch.empty(max(n, 0), dtype=torch.float32, device=self.device) if want_loss else None
+        if p_.numel() == 0:                                  # (nobody has a pair: the library still wants the pointers)
+            p_ = n_ = torch.zeros(1, dtype=torch.int32, device=self.device)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _ffi.check(self.h, self.lib.bprx_acf_fold_in(self.h, p(hp), p(hi), p(ptr), p(p_), p(n_), n, int(steps), lr, reg, opt,
+                                                     p(Gu_rows), p(loss), _stream()))
+        return loss
+
+    def acf_profile_rows(self, Gu_rows, lists=None, csr=None):
+        """bprx_acf_profile_rows: g'_r [n, k] of the rows of a caller-owned table with the histories `lists` (per row, or a
+        prebuilt `csr`)."""
+        hp, hi, n = self._acf_rows("acf_profile_rows", Gu_rows, lists, csr)
+        out = torch.empty((n, self.k), dtype=torch.float32, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        _ffi.check(self.h, self.lib.bprx_acf_profile_rows(self.h, p(Gu_rows), n, p(hp), p(hi), p(out), _stream()))
+        return out
+
+    def acf_score_rows_block(self, Gu_rows, r0, r1, lists=None, csr=None):
+        """bprx_acf_score_rows_block: score_block for rows [r0, r1) of a caller-owned user table with the histories `lists` (per
+        row of the whole table, or a prebuilt `csr`): scores [r1 - r0, I]."""
+        hp, hi, n = self._acf_rows("acf_score_rows_block", Gu_rows, lists, csr)
+        x = torch.empty((max(r1 - r0, 0), self.I), dtype=torch.float32, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        _ffi.check(self.h, self.lib.bprx_acf_score_rows_block(self.h, p(Gu_rows), n, p(hp), p(hi), int(r0), int(r1), p(x), _stream()))
+        return x
+
     def bind_attentive(self, Gu, Gi, Bi, edges, color, cls, weights, dropout=0.5, seed=0, slots=None):
         """AttentiveFashion (bprx_bind_attentive) on a BPRMF engine: edges uint8 [I, 224, 224], color fp32 [I, Dc] (each row already
         divided by its own max-abs), cls fp32 [I, Dk], weights = the thirteen tensors keyed by _ffi.AF_WEIGHTS (shapes of

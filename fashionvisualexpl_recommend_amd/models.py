@@ -296,8 +296,12 @@ class BPRMF(RecommenderModel):
                     optimizer=self.optimizer_name if optimizer is None else optimizer, want_loss=False)
         return Gu, Tu
 
+    def _fold_rows(self, histories, **fold):
+        """What recommend_new_users hands to _score_fold_rows: the fitted rows (a model whose scores need more says so here)."""
+        return self.fold_in_users(histories, **fold)
+
     def _score_fold_rows(self, rows, r0, r1):
-        """(scores [r1 - r0, I], side [r1 - r0, I, c] or None) of rows [r0, r1) of what fold_in_users returned."""
+        """(scores [r1 - r0, I], side [r1 - r0, I, c] or None) of rows [r0, r1) of what _fold_rows returned."""
         return self.engine.score_rows_block(rows[0], rows[1], r0, r1), None
 
     def recommend_new_users(self, histories, k=None, **fold):
@@ -309,7 +313,7 @@ class BPRMF(RecommenderModel):
         eng = self.engine
         n, I = len(histories), self.num_items
         k = self.evaluator.k if k is None else int(k)
-        rows = self.fold_in_users(histories, **fold)
+        rows = self._fold_rows(histories, **fold)
         blk = rows_per_block(self.evaluator.user_block, I)
         parts = []
         for b0 in range(0, n, blk):
@@ -902,6 +906,32 @@ class ACF(BPRMF):
         """explain() for one user and several items."""
         items = [int(i) for i in np.asarray(items).reshape(-1)]
         return self.explain([int(u)] * len(items), items, top, lists, maps)
+
+    # ---- users the model was not trained on: the full derivative of the user's own loss, everything but the row frozen ----------
+    def fold_in_users(self, histories, steps=30, negatives=4, lr=None, reg=None, optimizer=None, seed=0, init=None):
+        """Rows for users who arrive after training with a history of catalogue items each: Gu_new [n, k] (device), fitted by
+        Engine.acf_fold_in over the pairs of draw_fold_pairs(histories, num_items, negatives, seed) with the same histories as the
+        attention histories.  lr / reg / optimizer: None = the run's.  init: None = zero rows (at g = 0 the gradient is q plus the
+        attention terms, not zero: a zero start is live), or the rows to start from.  steps = 0 returns the start rows without a
+        kernel call: scored with the history they give the history-only profile g' = g + sum_l alpha_l Pi_l."""
+        eng = self.engine
+        Gu = fold_start_rows(init, len(histories), eng.k, eng.device)
+        if int(steps) == 0:
+            return Gu
+        ptr, pos, neg = draw_fold_pairs(histories, self.num_items, negatives, seed)
+        eng.acf_fold_in(ptr, pos, neg, steps, Gu, lists=histories, lr=self.learning_rate if lr is None else lr,
+                        reg=self.reg if reg is None else reg, optimizer=self.optimizer_name if optimizer is None else optimizer,
+                        want_loss=False)
+        return Gu
+
+    def _fold_rows(self, histories, **fold):
+        """The fitted rows and the CSR of their attention histories: ACF scores a row together with its history."""
+        return self.fold_in_users(histories, **fold), self.engine.csr(histories)
+
+    def _score_fold_rows(self, rows, r0, r1):
+        return self.engine.acf_score_rows_block(rows[0], r0, r1, csr=rows[1]), None
+
+    new_users_param, new_users_side = "acf_new_users", 0
 
     def _store_recs(self, path):
         """recs-* / best-recs-* as every model writes them; with params.acf_explain = L > 0 also expl-* / best-expl-* next to them."""

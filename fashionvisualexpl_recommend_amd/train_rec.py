@@ -6,6 +6,7 @@ Same flag names and defaults for every flag BPRMF/VBPR consume; new flags: --opt
 reachable there); here they take two ints `h 1`, and so does AttentiveFashion's --attention_layers.  --dropout is the rate of the
 three encoders' Dropout layers (the reference's constant 0.5).
 --af_new_users PATH (attentive_fashion only) fits rows for users the model was not trained on and writes new-user-recs-* files.
+--acf_new_users PATH (acf only) does the same for ACF: each row is fitted through both attention levels over the user's history.
 --similar_items K (bprmf, vbpr, grad_fashion) writes sim-* / best-sim-* files with every item's K nearest items by cosine in the
 space of --similar_space (latent: Gi; visual: f E; both), and with --new_items new-sim-* / best-new-sim-* (the visual space).
 Run as `python -m fashionvisualexpl_recommend_amd.train_rec --rec bprmf --dataset <name> ...`.
@@ -76,6 +77,11 @@ def parse_args(argv=None):
                              "item side, the encoders and the attention frozen and dropout off, and new-user-recs-* / "
                              "best-new-user-recs-* files (label, item, score, alpha_colour, alpha_edges, alpha_class) are written "
                              "next to recs-* / best-recs-*")
+    parser.add_argument('--acf_new_users', default=None, metavar='PATH',
+                        help="acf: a TSV in the format of --new_users.  Each new user's row of Gu is fitted by the full derivative "
+                             "of the user's own loss through both attention levels over the user's history, everything else "
+                             "frozen, and new-user-recs-* / best-new-user-recs-* files (label, item, score) are written next to "
+                             "recs-* / best-recs-*")
     parser.add_argument('--similar_items', type=int, default=0, metavar='K',
                         help="bprmf, vbpr, grad_fashion: also write sim-* / best-sim-* files next to recs-* / best-recs-* with every "
                              "catalogue item's K (1..1024) nearest items by cosine in the model's item space, rows `i j cosine`, "
@@ -84,9 +90,9 @@ def parse_args(argv=None):
     parser.add_argument('--similar_space', default=None, choices=['latent', 'visual', 'both'],
                         help="--similar_items: latent = Gi, visual = f E (vbpr, grad_fashion; fp32 or bf16 features), both = "
                              "[Gi | f E]; default: latent for bprmf, visual for vbpr and grad_fashion")
-    parser.add_argument('--fold_steps', type=int, default=30, help='--new_users / --af_new_users: optimiser steps per new user')
+    parser.add_argument('--fold_steps', type=int, default=30, help='--new_users / --af_new_users / --acf_new_users: optimiser steps per new user')
     parser.add_argument('--fold_negatives', type=int, default=4,
-                        help='--new_users / --af_new_users: sampled negatives per history item')
+                        help='--new_users / --af_new_users / --acf_new_users: sampled negatives per history item')
     # not in the reference
     parser.add_argument('--dropout', type=float, default=0.5,
                         help="attentive_fashion: rate of the encoders' Dropout layers (AttentiveFashion.py:53,62,70: 0.5)")
@@ -136,6 +142,8 @@ def parse_args(argv=None):
         parser.error("--new_users needs --rec bprmf, vbpr or grad_fashion (got --rec %s)" % args.rec)
     if args.af_new_users is not None and args.rec != 'attentive_fashion':
         parser.error("--af_new_users needs --rec attentive_fashion (got --rec %s)" % args.rec)
+    if args.acf_new_users is not None and args.rec != 'acf':
+        parser.error("--acf_new_users needs --rec acf (got --rec %s)" % args.rec)
     if args.fold_steps < 1 or args.fold_negatives < 1:
         parser.error("--fold_steps and --fold_negatives take values >= 1 (got %s, %s)" % (args.fold_steps, args.fold_negatives))
     if not 0 <= args.similar_items <= 1024:

@@ -151,6 +151,7 @@ BPRX_API int bprx_sync_adam(bprx_handle *h, void *stream);
      bprx_score_block                                                 any                 yes           yes   via P  yes (VBPR)
      bprx_score_rows_block, bprx_fold_in                              BPRMF / VBPR        yes           yes   via P  yes
      bprx_af_fold_in, bprx_af_score_rows_block                        AttentiveFashion    yes           -     -      -
+     bprx_acf_fold_in, bprx_acf_profile_rows, bprx_acf_score_rows_block   ACF             yes           -     -      -
      bprx_step_project                                                any                 yes           -     yes    yes
      bprx_score_pairs                                                 any                 yes           yes   unless P is current  -
      bprx_project_rows, bprx_score_new_block, bprx_feat_explain_new   VBPR, not fp8       yes           yes   yes    -
@@ -424,6 +425,60 @@ BPRX_API int bprx_acf_explain(bprx_handle *h, const int32_t *user, const int32_t
 enum { BPRX_ACF_GRAD_DETACHED = 0, BPRX_ACF_GRAD_FULL = 1 };
 BPRX_API int bprx_acf_set_gradient(bprx_handle *h, int mode);
 BPRX_API int bprx_acf_get_gradient(bprx_handle *h);
+/* Users the model was not trained on.  For ACF the user representation is made from the history, g' = g + sum_l alpha_l Pi_l with
+   both attention levels looking at g, so a new user is its history plus the k numbers g.  The reference's own tape detaches g'
+   (ACF.py:203-208): its train step gives Gu nothing but 2 reg g_u, and a fold-in "by the reference's step" would only shrink the
+   start row.  DEFINITION: the fold-in therefore differentiates the loss of the user's pairs with respect to g with NOTHING
+   detached and everything but g frozen -- the BPRX_ACF_GRAD_FULL derivative restricted to the user's row, whatever gradient mode
+   the handle is in (the mode is neither read nor changed, the FULL-mode workspace is neither needed nor allocated).  New user r
+   has history entries l in [hist_ptr[r], hist_ptr[r+1]) (a CSR indexed by ROW; every position is an entry, a repeated item is
+   several entries, as in bprx_acf_explain) and pairs (i_p, j_p), p in [pair_ptr[r], pair_ptr[r+1]), n_r of them; g starts at
+   Gu_rows[r]; for t = 1 .. steps:
+       s_lm = W1c.relu(Wcu^T g + Wci^T f_lm + bc0) + bc1        beta_l = softmax_m(s_l)
+       t_l  = W1i.relu(Wiu^T g + Wiv^T Gi_l + Wip^T Pi_l + Wix^T sum_m beta_lm f_lm + bi0) + bi1        alpha = softmax_l(t)
+       g'   = g + sum_l alpha_l Pi_l                 (g' = g for an empty history)
+       x_p  = g'.(Gi_i - Gi_j)    d_p = clip(x_p, -80, 1e8)    s_p = sigmoid(-d_p) inside the clip range (inclusive bounds), 0 outside
+       loss_t = sum_p softplus(-d_p) + reg n_r |g|^2
+       q    = sum_p -s_p (Gi_i - Gi_j)
+       dt_l = alpha_l (Pi_l.q - (sum_l' alpha_l' Pi_l').q)        dpre_l = dt_l W1i * [pre_l > 0]
+       dbeta_lm = Z_lm[h:].dpre_l     ds_lm = beta_lm (dbeta_lm - sum_m' beta_lm' dbeta_lm')     da_lm = ds_lm W1c * [a_lm > 0]
+       grad = q + Wiu sum_l dpre_l + Wcu sum_l sum_m da_lm + 2 reg n_r g
+       BPRX_OPT_SGD: g <- g - lr grad       BPRX_OPT_ADAM_TF23: the sparse-variable rule of the Gu rows, slots starting at zero,
+                                            lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t); beta1, beta2, epsilon are the handle's
+   The regularisers that do not depend on g are left out of `loss`.  For steps = 1 and sgd, started from a trained user's row with
+   that user's training history, the row moves as a BPRX_ACF_GRAD_FULL bprx_step on the batch of the user's pairs moves Gu_u.
+   bprx_acf_fold_in: hist_ptr / pair_ptr int64 [n+1], hist_items / pos / neg int32 (device); Gu_rows fp32 [n, k] in / out; loss
+   fp32 [n] or NULL: loss_steps, evaluated before the last update.  A user without pairs keeps its row bit for bit and has loss 0,
+   whatever its history; a user with pairs and an empty history is bprx_fold_in's BPRMF problem with Bi = 0.  lr, reg, optimizer
+   are the call's.  The call first makes Z / GP of the distinct history items current (the preparation every ACF call runs over
+   the items it reads, so a bprx_step between two folds is seen by the second); apart from that it writes its outputs only and
+   allocates nothing.  fp32 throughout, no float atomics, every sum in one fixed order: two calls return the same bits, and a
+   user's result depends on its own history, pairs, start row and the tables only -- not on n, on its position, or on
+   BPRX_FOLD_CACHE (1, the default: the first Gi_i - Gi_j rows of a user that fit are kept in LDS across the steps; 0: every step
+   gathers every pair's rows again; read by bprx_create).  Any history length and any n_r.  LDS of a workgroup:
+       4 (20 + 7 k + 8 M + 7 h + 11 a) bytes  <= 64 KB  (BPRX_E_INVALID otherwise; M = 196, k = 128, h = a = 64: 14.2 KB)
+   and behind it the cached pair rows, k floats each, up to a total of 40 KB.  Item ids out of range, in the histories and in the
+   pairs, are clamped and reported by bprx_sync_check (BPRX_E_RANGE).  With bf16 features Z is made, as in every ACF call, from
+   [Wci | Wix] held as two bf16 halves (16 mantissa bits): the fit sees those two tensors at that precision.
+   BPRX_E_INVALID for a NULL handle, a handle that is not bound with bprx_bind_acf, a NULL pointer, n < 0, steps < 1, an unknown
+   optimizer, a shape beyond the LDS bound; BPRX_E_STATE for an unbound handle; n == 0: BPRX_OK. */
+BPRX_API int bprx_acf_fold_in(bprx_handle *h, const int64_t *hist_ptr, const int32_t *hist_items, const int64_t *pair_ptr,
+                              const int32_t *pos, const int32_t *neg, int64_t n, int32_t steps, float lr, float reg,
+                              int32_t optimizer, float *Gu_rows, float *loss, void *stream);
+/* bprx_acf_profiles for caller-owned rows: out fp32 [n, k] = g'_r of row r of Gu_rows [n, k] with the history
+   [hist_ptr[r], hist_ptr[r+1]) of a CSR indexed by ROW.  The same kernel: a slice of the handle's own Gu with the matching slice
+   of the training CSR gives the bits of bprx_acf_profiles.  0 <= n < 2^31; errors as for bprx_acf_fold_in. */
+BPRX_API int bprx_acf_profile_rows(bprx_handle *h, const float *Gu_rows, int64_t n, const int64_t *hist_ptr,
+                                   const int32_t *hist_items, float *out, void *stream);
+/* bprx_score_block of an ACF handle for caller-owned rows: out fp32 [(r1-r0), num_items] = g'_r . Gi_i for rows [r0, r1) of
+   Gu_rows [n_rows, k] with the histories of a CSR [n_rows + 1] indexed by row, through the scoring kernel of bprx_score_block: the
+   handle's own rows with the evaluation histories give its bits.  0 <= r0 <= r1 <= n_rows < 2^31; errors as for
+   bprx_acf_fold_in.  A block of more rows than max_batch keeps its profiles in one workspace allocated at the first such call
+   and regrown when a block is larger (BPRX_E_NOMEM); smaller blocks allocate nothing.  A call that regrows it first waits for the
+   work queued on `stream` (an earlier block's scores may still read the old buffer): issue such blocks on one stream, and not
+   under stream capture. */
+BPRX_API int bprx_acf_score_rows_block(bprx_handle *h, const float *Gu_rows, int64_t n_rows, const int64_t *hist_ptr,
+                                       const int32_t *hist_items, int64_t r0, int64_t r1, float *out, void *stream);
 
 /* ---- AttentiveFashion (AttentiveFashion.py:20-371) on a BPRMF handle ----------------------------------------------------
    Per item i three inputs: an edge image (uint8 [224, 224]; the model sees pixel / 255), a colour histogram [Dc] and a class
