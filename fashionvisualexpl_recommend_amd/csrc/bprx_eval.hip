@@ -114,12 +114,7 @@ __global__ __launch_bounds__(256) void k_score_new_gemm(const float *__restrict_
 }
 
 // ---- similar items (include/bprx.h): cosine of item vectors z = [Gi | P[0:d]] (either part may be absent) ----
-// One part of z: n rows of `w` floats, row stride ld (w == 0: the part is absent).
-struct SimPart {
-  const float *p;
-  int w, ld;
-};
-
+// (SimPart, one part of z: bprx_internal.h)
 constexpr int RN_LANES = 16;   // lanes per row of k_sim_rnorm: 4 rows per wave, 16 per workgroup
 
 // rn[r] = 1 / sqrt(sum_x z_rx^2), 0 for a zero row.  16 lanes load 16 consecutive x of a row (one 64-byte segment) and square
@@ -537,7 +532,7 @@ extern "C" int bprx_score_new_block(bprx_handle *h, int32_t u0, int32_t u1, cons
 // ---- similar items: bprx_sim_rnorm / bprx_sim_block (include/bprx.h) ----
 // The checks the two entries share, then the gate: the space, the query rows (the catalogue: nq == num_items; the caller's rows:
 // visual only), fp8 in a space that reads P, and plan_read's own (bound, handle kind).
-static int sim_enter(bprx_handle *h, const char *what, int32_t space, const float *Pq, int64_t nq, hipStream_t s) {
+int bprx_sim_enter(bprx_handle *h, const char *what, int32_t space, const float *Pq, int64_t nq, hipStream_t s) {
   if (space != BPRX_SIM_LATENT && space != BPRX_SIM_VISUAL && space != BPRX_SIM_BOTH)
     BPRX_FAIL(h, BPRX_E_INVALID, "%s: unknown space %d (BPRX_SIM_LATENT, _VISUAL or _BOTH)", what, space);
   if (Pq && space != BPRX_SIM_VISUAL) BPRX_FAIL(h, BPRX_E_INVALID, "%s: rows from outside the catalogue live in the visual space only", what);
@@ -552,7 +547,7 @@ static int sim_enter(bprx_handle *h, const char *what, int32_t space, const floa
 }
 
 // the parts of z for the catalogue (Pq == nullptr) or the caller's rows: [Gi over k | P over d], absent parts have width 0
-static void sim_parts(const bprx_handle *h, int32_t space, const float *Pq, SimPart &g, SimPart &p) {
+void bprx_sim_parts(const bprx_handle *h, int32_t space, const float *Pq, SimPart &g, SimPart &p) {
   g = {h->t.Gi, space != BPRX_SIM_VISUAL && !Pq ? h->cfg.embed_k : 0, h->cfg.embed_k};
   p = {Pq ? Pq : h->P, space != BPRX_SIM_LATENT ? h->cfg.embed_d : 0, h->PS};
 }
@@ -561,10 +556,10 @@ extern "C" int bprx_sim_rnorm(bprx_handle *h, int32_t space, const float *Pq, in
   if (!h) return BPRX_E_INVALID;
   if (!rn) BPRX_FAIL(h, BPRX_E_INVALID, "sim_rnorm: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  const int rc = sim_enter(h, "sim_rnorm", space, Pq, nq, s);
+  const int rc = bprx_sim_enter(h, "sim_rnorm", space, Pq, nq, s);
   if (rc || nq == 0) return rc;
   SimPart g, p;
-  sim_parts(h, space, Pq, g, p);
+  bprx_sim_parts(h, space, Pq, g, p);
   constexpr int rows = 256 / RN_LANES;
   hipLaunchKernelGGL(k_sim_rnorm, dim3((unsigned)((nq + rows - 1) / rows)), dim3(256), 0, s, g, p, (int)nq, rn);
   BPRX_LAUNCH_CHECK(h, "k_sim_rnorm");
@@ -578,11 +573,11 @@ extern "C" int bprx_sim_block(bprx_handle *h, int32_t space, const float *Pq, in
   if (q0 < 0 || q0 > q1 || q1 > nq || q1 - q0 > (int64_t)65535 * TM)
     BPRX_FAIL(h, BPRX_E_INVALID, "sim_block: bad query range [%lld,%lld) of %lld", (long long)q0, (long long)q1, (long long)nq);
   hipStream_t s = (hipStream_t)stream;
-  const int rc = sim_enter(h, "sim_block", space, Pq, nq, s);
+  const int rc = bprx_sim_enter(h, "sim_block", space, Pq, nq, s);
   if (rc || q0 == q1) return rc;
   SimPart ag, ap, bg, bp;
-  sim_parts(h, space, Pq, ag, ap);
-  sim_parts(h, space, nullptr, bg, bp);
+  bprx_sim_parts(h, space, Pq, ag, ap);
+  bprx_sim_parts(h, space, nullptr, bg, bp);
   bg.w = ag.w;                                               // (the caller's rows have no Gi part)
   const int I = h->cfg.num_items;
   dim3 grid((unsigned)((I + TN - 1) / TN), (unsigned)((q1 - q0 + TM - 1) / TM));

@@ -419,6 +419,16 @@ int bprx_af_pairs(bprx_handle *h, const int32_t *u, const int32_t *i, int64_t n,
 int bprx_af_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, float *alpha, hipStream_t s, const float *Gu_rows = nullptr);
 void bprx_af_invalidate(bprx_handle *h);
 void bprx_af_free(bprx_handle *h);
+// The item space of bprx_sim_* and bprx_diversify (bprx_eval.hip).  One part of z: n rows of `w` floats, row stride ld (w == 0:
+// the part is absent); z = [g | p].
+struct SimPart {
+  const float *p;
+  int w, ld;
+};
+// the checks every entry of an item space shares (space, query rows, fp8, handle kind), then the read gate
+int bprx_sim_enter(bprx_handle *h, const char *what, int32_t space, const float *Pq, int64_t nq, hipStream_t s);
+// the parts of z for the catalogue (Pq == nullptr) or the caller's projected rows
+void bprx_sim_parts(const bprx_handle *h, int32_t space, const float *Pq, SimPart &g, SimPart &p);
 
 // ---- host helpers ----
 // Adam's bias-corrected step size at optimizer.iterations = it

@@ -682,6 +682,26 @@ class Engine:
                                                    p(rn_items), p(out), _stream()))
         return out
 
+    def diversify(self, space, rn, pool_idx, pool_val, k, theta):
+        """bprx_diversify: greedy MMR over the pools (pool_idx int32, pool_val fp32: contiguous device tensors [n, N], best first,
+        as the top-K entries return them) in `space`, rn = sim_rnorm(space): (idx int32 [n, k], val fp32 [n, k] the picks' pool
+        scores, pen fp32 [n, k] each pick's largest cosine with the picks above it, ild fp32 [n] the lists' intra-list
+        diversity).  theta in [0, 1]: 0 keeps the pool's order, 1 ranks by dissimilarity alone.  Slots past the candidates of
+        a pool hold -1 / 0 / 0."""
+        n, N = (int(x) for x in pool_idx.shape)
+        if tuple(pool_val.shape) != (n, N) or pool_idx.dtype != torch.int32 or pool_val.dtype != torch.float32:
+            raise ValueError("diversify: pool_idx int32 [n, N] and pool_val fp32 [n, N]")
+        if not (pool_idx.is_contiguous() and pool_val.is_contiguous()):
+            raise ValueError("diversify: the pools must be contiguous")
+        k = int(k)
+        idx = torch.empty((n, max(k, 0)), dtype=torch.int32, device=self.device)
+        val, pen = (torch.empty((n, max(k, 0)), dtype=torch.float32, device=self.device) for _ in range(2))
+        ild = torch.empty(n, dtype=torch.float32, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        _ffi.check(self.h, self.lib.bprx_diversify(self.h, _ffi.SIM_SPACE.get(space, space), p(rn), n, N, p(pool_idx), p(pool_val), k,
+                                                   float(theta), p(idx), p(val), p(pen), p(ild), _stream()))
+        return idx, val, pen, ild
+
     def _hyper(self):
         return self._lr_reg
 

@@ -18,7 +18,7 @@ from time import time
 
 import numpy as np
 
-from .ranking import lists_to_csr, rank_rows, rank_rows_host, rows_per_block, write_ranked
+from .ranking import lists_to_csr, rank_rows, rank_rows_host, rows_per_block, write_diverse, write_ranked
 
 
 def _eval_block(scores, u0, train, evl, K):
@@ -247,6 +247,16 @@ class Evaluator:
         ids, vals = self.model.similar_items(None, None, space)
         with open(path, 'w') as out:
             write_ranked(out, range(ids.shape[0]), ids, vals)
+
+    def store_recommendation_diverse(self, path="", path_ild="", k=None, pool=None, theta=None, space=None):
+        """BPRMF / VBPR / GradFashion: every user's diversified list (model.recommend_diverse: greedy MMR over the user's top-`pool`,
+        None = the run's --diversify / --diversify_pool / --similar_space) as rows 'u\ti\tscore\tredundancy' in `path`, in list
+        order (redundancy = the pick's largest cosine with the picks above it), and one row 'u\tild' per user in `path_ild` (1 -
+        the mean pairwise cosine of the list), formatted as store_recommendation formats.  Device only: force_host or
+        top_k > 1024 raise ValueError (there is no host MMR)."""
+        ids, vals, pen, ild = self.model.recommend_diverse(None, k, pool, theta, space)
+        with open(path, 'w') as out, open(path_ild, 'w') as out_ild:
+            write_diverse(out, out_ild, range(ids.shape[0]), ids, vals, pen, ild)
 
     def store_similar_new(self, path="", features=None):
         """VBPR / GradFashion: the catalogue neighbours of every row of `features` (raw rows of items outside the catalogue, as

@@ -19,7 +19,7 @@ import torch
 from . import configs
 from .engine import Engine, as_index
 from .evaluator import Evaluator
-from .ranking import rank_rows, rows_per_block, write_ranked
+from .ranking import diversify_rows, div_paths, rank_rows, rows_per_block, write_diverse, write_ranked
 from .synth import glorot_uniform
 
 
@@ -107,6 +107,8 @@ class BPRMF(RecommenderModel):
         self.evaluator = Evaluator(self, data, params.top_k)                       # BPRMF.py:40
         self.similar_k = int(getattr(params, "similar_items", 0) or 0)             # neighbours per item in sim-*; 0: none
         self.similar_space = getattr(params, "similar_space", None) or self.sim_space
+        self.diversify_theta = float(getattr(params, "diversify", 0.0) or 0.0)     # theta of the div-* files; 0: none
+        self.diversify_pool = int(getattr(params, "diversify_pool", 100) or 100)   # candidates per list the MMR step picks from
         self.directory_parameters = f'batch_{params.batch_size}-K_{params.embed_k}-lr_{params.lr}-reg_{params.reg}'
         self._build(init or {})
 
@@ -260,6 +262,7 @@ class BPRMF(RecommenderModel):
         self._store_recs(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
         self._store_new_user_recs(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
         self._store_similar(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
+        self._store_diverse(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
         with open(os.path.join(rdir, f'results-metrics-{self.directory_parameters}') + '.pkl', 'wb') as f:
             pickle.dump(results, f)                                             # utils/write.py:14-22
         print("Store Best Model at Epoch {0}".format(best_epoch))
@@ -271,6 +274,7 @@ class BPRMF(RecommenderModel):
         self._store_recs(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
         self._store_new_user_recs(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
         self._store_similar(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
+        self._store_diverse(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
         self.load_state_dict(last_state)
         print('End Store Best Model!')
         print('Best Values for Each Metric:\nHR\tPrec\tRec\tAUC\tnDCG\n{}\t{}\t{}\t{}\t{}\n'.format(
@@ -304,22 +308,39 @@ class BPRMF(RecommenderModel):
         """(scores [r1 - r0, I], side [r1 - r0, I, c] or None) of rows [r0, r1) of what _fold_rows returned."""
         return self.engine.score_rows_block(rows[0], rows[1], r0, r1), None
 
-    def recommend_new_users(self, histories, k=None, **fold):
+    def recommend_new_users(self, histories, k=None, diversify=None, **fold):
         """The k (default top_k) best catalogue items of every new user, their own histories masked: numpy idx int [n, kk] and
         val [n, kk], kk = min(k, I), best first; a model whose scores come with attentions (AttentiveFashion) also returns alpha
         [n, kk, 3] (colour, edges, class).  The rows are fitted by fold_in_users(histories, **fold), scored in row blocks and
         listed by ranking.rank_rows: on the device, rows whose list depends on the order of equal scores redone with numpy on the
-        GPU's (masked) row."""
+        GPU's (masked) row.
+        diversify: None, or theta (a float in [0, 1]), or a dict with any of theta / pool / space as recommend_diverse takes
+        them: the lists are then picked by greedy MMR from each row's top-`pool` and (ids, vals, pen, ild) is returned, as by
+        recommend_diverse (BPRMF, VBPR, GradFashion)."""
+        div = None
+        if diversify is not None:
+            opts = dict(diversify) if isinstance(diversify, dict) else {"theta": diversify}
+            kk, pool, theta, space = self._diverse_args(k, opts.get("pool"), opts.get("theta"), opts.get("space"))
         eng = self.engine
         n, I = len(histories), self.num_items
         k = self.evaluator.k if k is None else int(k)
         rows = self._fold_rows(histories, **fold)
+        if diversify is not None:
+            rn = eng.sim_rnorm(space)
+            div = lambda pi, pv, kq: eng.diversify(space, rn, pi, pv, kq, theta)
         blk = rows_per_block(self.evaluator.user_block, I)
         parts = []
         for b0 in range(0, n, blk):
             b1 = min(n, b0 + blk)
             sc, side = self._score_fold_rows(rows, b0, b1)
-            parts.append(rank_rows(lambda s, kq: eng.topk_lists(s, eng.csr(histories[b0:b1]), kq), sc, k, side))
+            topk = lambda s, kq: eng.topk_lists(s, eng.csr(histories[b0:b1]), kq)
+            if div is None:
+                parts.append(rank_rows(topk, sc, k, side))
+            else:
+                pi, pv, _ = rank_rows(topk, sc, pool)
+                parts.append(diversify_rows(div, pi, pv, kk, eng.device))
+        if div is not None:
+            return _stack_diverse(parts, kk)
         return _stack_blocks(parts, min(k, I), self.new_users_side)
 
     new_users_param = "new_users"                                # the params entry that names the new users' file
@@ -338,8 +359,16 @@ class BPRMF(RecommenderModel):
         res = self.recommend_new_users(lists, steps=getattr(self.params, "fold_steps", 30),
                                        negatives=getattr(self.params, "fold_negatives", 4),
                                        seed=getattr(self.params, "init_seed", 0))
-        with open(os.path.join(d, f.replace("recs-", "new-user-recs-", 1)), 'w') as out:
+        new_path = os.path.join(d, f.replace("recs-", "new-user-recs-", 1))
+        with open(new_path, 'w') as out:
             write_ranked(out, labels, *res)
+        if self.diversify_theta > 0:                             # div-new-user-recs-* / div-new-user-ild-*: the same fitted rows
+            res = self.recommend_new_users(lists, diversify={}, steps=getattr(self.params, "fold_steps", 30),
+                                           negatives=getattr(self.params, "fold_negatives", 4),
+                                           seed=getattr(self.params, "init_seed", 0))
+            p_recs, p_ild = div_paths(new_path)
+            with open(p_recs, 'w') as out, open(p_ild, 'w') as out_ild:
+                write_diverse(out, out_ild, labels, *res)
 
     # ---- similar items: the cosine of two items in the model's item space (include/bprx.h, bprx_sim_*) -------------------------
     sim_space = "latent"                                         # the space similar_items walks by default
@@ -375,6 +404,68 @@ class BPRMF(RecommenderModel):
             return
         d, f = os.path.split(path)
         self.evaluator.store_similar_items(os.path.join(d, f.replace("recs-", "sim-", 1)), self.similar_space)
+
+    # ---- diversified lists: greedy MMR over each list's top-N pool in the model's item space (include/bprx.h, bprx_diversify) --
+    diverse = True                                               # False: the model has no item space (ACF, AttentiveFashion)
+
+    def _diverse_args(self, k, pool, theta, space):
+        """(kk, N, theta, space) of a diversified ranking, checked: k (None: top_k) and pool (None: params.diversify_pool, 100)
+        cut to the catalogue, theta (None: params.diversify, 0.5 where that is off), space (None: similar_items' own)."""
+        if not self.diverse:
+            raise NotImplementedError("%s has no item space: diversified lists come from BPRMF, VBPR and GradFashion"
+                                      % type(self).__name__)
+        k = self.evaluator.k if k is None else int(k)
+        if getattr(self.evaluator, "force_host", False) or k > 1024:
+            raise ValueError("--diversify ranks on the device only (no force_host, top_k <= 1024): there is no host MMR")
+        pool = self.diversify_pool if pool is None else int(pool)
+        theta = (self.diversify_theta or 0.5) if theta is None else float(theta)
+        if not 0.0 <= theta <= 1.0:
+            raise ValueError("diversify: theta lies in [0, 1] (got %s)" % theta)
+        if not 1 <= k <= pool <= 1024:
+            raise ValueError("diversify: need 1 <= k <= pool <= 1024 (got k = %d, pool = %d)" % (k, pool))
+        I = self.num_items
+        return min(k, I), min(pool, I), theta, self.similar_space if space is None else space
+
+    def recommend_diverse(self, users=None, k=None, pool=None, theta=None, space=None):
+        """The k (default top_k) items of every user of `users` (None: all, in id order) picked by greedy Maximal Marginal Relevance
+        from the user's top-`pool` (default params.diversify_pool, 100; training items masked): each pick maximises
+        (1 - theta) rel - theta max-cosine-with-the-picks-above, cosines in `space` (None: the model's own, as similar_items).
+        Returns numpy ids int64 [n, kk], vals fp32 [n, kk] (the model's scores), pen fp32 [n, kk] (each pick's redundancy: its
+        largest cosine with the picks above it) and ild fp32 [n] (1 - the mean pairwise cosine of the list), kk = min(k, I);
+        slots past a user's unmasked items hold -1 / 0 / 0.  The pools are ranking.rank_rows' lists (Engine.topk, K = pool), the
+        picks Engine.diversify's through ranking.diversify_rows; an explicit user list ranks the blocks that hold its users."""
+        kk, N, theta, space = self._diverse_args(k, pool, theta, space)
+        eng, ev = self.engine, self.evaluator
+        U = self.num_users
+        want = np.arange(U, dtype=np.int64) if users is None else np.asarray(users, dtype=np.int64).reshape(-1)
+        if want.size and (want.min() < 0 or want.max() >= U):
+            raise ValueError("recommend_diverse: user ids lie in [0, %d)" % U)
+        ev._metrics_device_csr()
+        rn = eng.sim_rnorm(space)
+        div = lambda pi, pv, kq: eng.diversify(space, rn, pi, pv, kq, theta)
+        blk = ev.user_block
+        out = _stack_diverse([], kk, want.size)
+        for b0 in sorted({int(q) // blk * blk for q in want}):
+            b1 = min(U, b0 + blk)
+            pi, pv, _ = rank_rows(ev._topk(b0, b1), eng.score_block(b0, b1), N)
+            res = diversify_rows(div, pi, pv, kk, eng.device)
+            rows = np.nonzero((want >= b0) & (want < b1))[0]
+            for o, r in zip(out, res):
+                o[rows] = r[want[rows] - b0]
+        return out
+
+    def _store_diverse(self, path):
+        """params.diversify = theta > 0: div-recs-* (rows 'u\ti\tscore\tredundancy', in list order) and div-ild-* (rows 'u\tild')
+        next to the recs-* file at `path`."""
+        if self.diversify_theta <= 0:
+            return
+        self.evaluator.store_recommendation_diverse(*div_paths(path))
+
+
+def _stack_diverse(parts, kk, n=0):
+    """The per-block (ids, vals, pen, ild) of ranking.diversify_rows as whole arrays (no parts: n zero rows)."""
+    parts = [(np.zeros((n, kk), np.int64), np.zeros((n, kk), np.float32), np.zeros((n, kk), np.float32), np.zeros(n, np.float32))] + parts
+    return tuple(np.concatenate(p) for p in zip(*parts))
 
 
 def _stack_blocks(parts, kk, c=0):
@@ -932,6 +1023,7 @@ class ACF(BPRMF):
         return self.engine.acf_score_rows_block(rows[0], r0, r1, csr=rows[1]), None
 
     new_users_param, new_users_side = "acf_new_users", 0
+    diverse = False
 
     def _store_recs(self, path):
         """recs-* / best-recs-* as every model writes them; with params.acf_explain = L > 0 also expl-* / best-expl-* next to them."""
@@ -1109,6 +1201,7 @@ class AttentiveFashion(BPRMF):
         return self.engine.af_score_rows_block(rows, r0, r1)
 
     new_users_param, new_users_side = "af_new_users", 3
+    diverse = False
 
     def _store_recs(self, path):
         """recs-* / best-recs-* with the attentions; with params.af_explain = G > 0 also expl-* / best-expl-* next to them."""

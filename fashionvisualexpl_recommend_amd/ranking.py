@@ -1,10 +1,11 @@
 """The one place where score rows become top-K lists and lists become rows of text: every recs-* / new-recs-* /
-new-user-recs-* file, single GPU or sharded, catalogue items or new ones, is ranked and written here.
+new-user-recs-* / div-* file, single GPU or sharded, catalogue items or new ones, is ranked and written here.
 
 The contract is the reference's (Evaluator.py:225-239): mask the row, then take numpy_topk of it; numpy's unstable argsort
 decides the order of EQUAL scores.  The top-K kernel returns the list wherever it does not depend on that order and flags
 every other row (include/bprx.h, bprx_topk); a flagged row is redone by numpy_topk on the row the kernel has masked.
-Plain numpy + torch: no library call is made here, the caller brings the top-K entry as a callable.
+Plain numpy + torch: no library call is made here, the caller brings the top-K entry (and the MMR entry of diversify_rows) as a
+callable.
 """
 import numpy as np
 import torch
@@ -59,6 +60,22 @@ def rank_rows(topk, scores, k, side=None):
     return ids, vals, side_rows
 
 
+def diversify_rows(diversify, ids, vals, k, device):
+    """The diversified lists of a block of pools: `ids` int64 [n, N] / `vals` fp32 [n, N] are what rank_rows returned for a pool
+    of N (flagged rows already redone by numpy there; a masked entry keeps its -inf and is no candidate).  They are uploaded
+    once, diversify(pool_idx int32, pool_val, kk) is the MMR entry (Engine.diversify with its space, norms and theta bound) and
+    returns the device (idx, val, pen, ild).  Returns numpy ids int64 [n, kk], vals fp32 [n, kk], pen fp32 [n, kk] and ild fp32
+    [n], kk = min(k, N); slots past a pool's candidates hold -1 / 0 / 0."""
+    n, N = ids.shape
+    kk = min(int(k), N)
+    if n == 0 or kk == 0:
+        return np.zeros((n, kk), np.int64), np.zeros((n, kk), np.float32), np.zeros((n, kk), np.float32), np.zeros(n, np.float32)
+    pool_idx = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32), device=device)
+    pool_val = torch.as_tensor(np.ascontiguousarray(vals, dtype=np.float32), device=device)
+    idx, val, pen, ild = diversify(pool_idx, pool_val, kk)
+    return idx.cpu().numpy().astype(np.int64), val.cpu().numpy(), pen.cpu().numpy(), ild.cpu().numpy()
+
+
 def rank_rows_host(scores, mask_lists, k):
     """rank_rows on the host: row r of the numpy block `scores` gets -inf (IN `scores`) at mask_lists[r] (None: nothing is
     masked) and is listed by numpy_topk.  Returns (ids int64 [n, kk], vals [n, kk])."""
@@ -85,3 +102,25 @@ def write_ranked(out, labels, ids, vals, side=None):
         users.extend([label] * len(ids[r]))
         items.extend(int(v) for v in ids[r])
     return users, items
+
+
+def div_paths(path):
+    """(div-recs-*, div-ild-*) next to the recs-* / best-recs-* / new-user-recs-* / best-new-user-recs-* file at `path`: 'div-'
+    goes in front of the file's own 'recs-' / 'new-user-recs-' part, the ild file has 'ild-' where that part is."""
+    d, sep, f = path.rpartition('/')
+    for part in ("new-user-recs-", "recs-"):
+        if part in f:
+            return d + sep + f.replace(part, "div-" + part, 1), d + sep + f.replace(part, "div-" + part.replace("recs-", "ild-"), 1)
+    raise ValueError("div_paths: %r is no recs-* path" % path)
+
+
+def write_diverse(out, out_ild, labels, ids, vals, pen, ild):
+    """One row 'label\tid\tval\tredundancy' per pick, list by list in selection order (empty slots, id < 0, are left out), into
+    `out`; one row 'label\tild' per list into `out_ild`.  Fields are formatted as write_ranked formats them."""
+    for r, label in enumerate(labels):
+        head = str(label) + '\t'
+        for q, item in enumerate(ids[r]):
+            if item < 0:
+                break
+            out.write(head + str(item) + '\t' + str(vals[r, q]) + '\t' + str(pen[r, q]) + '\n')
+        out_ild.write(head + str(ild[r]) + '\n')

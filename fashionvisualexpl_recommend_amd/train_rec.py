@@ -9,6 +9,8 @@ three encoders' Dropout layers (the reference's constant 0.5).
 --acf_new_users PATH (acf only) does the same for ACF: each row is fitted through both attention levels over the user's history.
 --similar_items K (bprmf, vbpr, grad_fashion) writes sim-* / best-sim-* files with every item's K nearest items by cosine in the
 space of --similar_space (latent: Gi; visual: f E; both), and with --new_items new-sim-* / best-new-sim-* (the visual space).
+--diversify THETA (bprmf, vbpr, grad_fashion) writes div-recs-* / div-ild-* files next to recs-*: every user's top_k picked by
+greedy Maximal Marginal Relevance from the user's top --diversify_pool, cosines in the space of --similar_space.
 Run as `python -m fashionvisualexpl_recommend_amd.train_rec --rec bprmf --dataset <name> ...`.
 """
 import argparse
@@ -90,6 +92,15 @@ def parse_args(argv=None):
     parser.add_argument('--similar_space', default=None, choices=['latent', 'visual', 'both'],
                         help="--similar_items: latent = Gi, visual = f E (vbpr, grad_fashion; fp32 or bf16 features), both = "
                              "[Gi | f E]; default: latent for bprmf, visual for vbpr and grad_fashion")
+    parser.add_argument('--diversify', type=float, default=0.0, metavar='THETA',
+                        help="bprmf, vbpr, grad_fashion: also write div-recs-* / best-div-recs-* files next to recs-* / best-recs-* "
+                             "with every user's top_k picked by greedy Maximal Marginal Relevance from the user's top "
+                             "--diversify_pool: each pick maximises (1 - THETA) relevance - THETA (largest cosine with the picks "
+                             "above it), cosines in the space of --similar_space; rows `u i score redundancy` in list order, and "
+                             "div-ild-* / best-div-ild-* with one row `u ild` per user (1 - mean pairwise cosine of the list); "
+                             "with --new_users also div-new-user-recs-* / div-new-user-ild-*.  THETA in [0, 1]; 0 = off")
+    parser.add_argument('--diversify_pool', type=int, default=100, metavar='N',
+                        help="--diversify: candidates per user the lists are picked from, top_k <= N <= 1024")
     parser.add_argument('--fold_steps', type=int, default=30, help='--new_users / --af_new_users / --acf_new_users: optimiser steps per new user')
     parser.add_argument('--fold_negatives', type=int, default=4,
                         help='--new_users / --af_new_users / --acf_new_users: sampled negatives per history item')
@@ -148,12 +159,16 @@ def parse_args(argv=None):
         parser.error("--fold_steps and --fold_negatives take values >= 1 (got %s, %s)" % (args.fold_steps, args.fold_negatives))
     if not 0 <= args.similar_items <= 1024:
         parser.error("--similar_items takes 0 (off) .. 1024 (got %s)" % args.similar_items)
-    asked = args.similar_items != 0 or args.similar_space is not None
+    if not 0.0 <= args.diversify <= 1.0:                      # (NaN fails both comparisons)
+        parser.error("--diversify takes theta in [0, 1], 0 = off (got %s)" % args.diversify)
+    if args.diversify > 0 and not args.top_k <= args.diversify_pool <= 1024:
+        parser.error("--diversify_pool takes top_k (%d) .. 1024 (got %s)" % (args.top_k, args.diversify_pool))
+    asked = args.similar_items != 0 or args.similar_space is not None or args.diversify > 0
     if args.similar_space is None:                            # the model's own space
         args.similar_space = {'bprmf': 'latent', 'vbpr': 'visual', 'grad_fashion': 'visual'}.get(args.rec)
     if asked:
         if args.rec not in ('bprmf', 'vbpr', 'grad_fashion'):
-            parser.error("--similar_items / --similar_space need --rec bprmf, vbpr or grad_fashion (got --rec %s)" % args.rec)
+            parser.error("--similar_items / --similar_space / --diversify need --rec bprmf, vbpr or grad_fashion (got --rec %s)" % args.rec)
         if args.similar_space != 'latent' and args.rec == 'bprmf':
             parser.error("--similar_space %s needs --rec vbpr or grad_fashion (bprmf has the latent space only)" % args.similar_space)
         if args.similar_space != 'latent' and args.dtype == 'fp8':
@@ -201,6 +216,8 @@ def train(argv=None):
         raise NotImplementedError('--af_new_users runs on one GPU (no multi-GPU form): use --world_size 1')
     if args.similar_items != 0 and int(args.world_size) > 1:
         raise NotImplementedError('--similar_items runs on one GPU (the sharded drivers write no sim-* files): use --world_size 1')
+    if args.diversify > 0 and int(args.world_size) > 1:
+        raise NotImplementedError('--diversify runs on one GPU (the sharded drivers write no div-* files): use --world_size 1')
     if args.new_items is not None and args.dtype == 'fp8':
         raise ValueError('--new_items runs with --dtype fp32 or bf16 (an fp8 table is scaled for the training max-abs: a new row '
                          'may saturate)')

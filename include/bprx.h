@@ -157,6 +157,7 @@ BPRX_API int bprx_sync_adam(bprx_handle *h, void *stream);
      bprx_project_rows, bprx_score_new_block, bprx_feat_explain_new   VBPR, not fp8       yes           yes   yes    -
      bprx_feat_explain                                                VBPR                yes           yes   -      -
      bprx_explain_pairs                                               GradFashion         yes           yes   -      -
+     bprx_sim_rnorm, bprx_sim_block, bprx_diversify                   BPRMF / VBPR        yes           yes   via P  VISUAL / BOTH
      bprx_sync_adam                                                   any                 yes           yes   -      -
      bprx_topk_rows                                                   VBPR, not fp8       yes           -     -      -
      bprx_apply_user_msgs                                             any                 yes           -     -      -
@@ -336,6 +337,41 @@ BPRX_API int bprx_sim_rnorm(bprx_handle *h, int32_t space, const float *Pq, int6
    0 <= q0 <= q1 <= nq < 2^31, q1 - q0 <= 65535 * 128. */
 BPRX_API int bprx_sim_block(bprx_handle *h, int32_t space, const float *Pq, int64_t nq, int64_t q0, int64_t q1, const float *rn_q,
                             const float *rn_items, float *out, void *stream);
+
+/* ---- BPRMF, VBPR and GradFashion: diversified lists, greedy Maximal Marginal Relevance over a top-N pool -------------------
+   "K of the N best that are good and unlike the picks above them".  One list has the pool (id_c, v_c), c = 0 .. N-1, best first,
+   as bprx_topk / bprx_topk_lists / bprx_topk_rows return it with K = N.  A slot with id_c < 0 or v_c == -inf is no candidate;
+   M = the number of candidates.  z_i and rn_i are those of bprx_sim_rnorm / bprx_sim_block for `space` (same handle rules).
+       rel_c     = (v_c - v_min) / (v_max - v_min) over the candidates, 0 when v_max == v_min: relevance on [0, 1] per list
+                   (scores have no fixed scale, cosines do); the two differences and the quotient are each rounded once
+       cos(c, s) = <z_c, z_s> (rn_c rn_s)   fp32: <z_c, z_s> is the serial chain a = fma(z_cx, z_sx, a) from +0 in ascending x, Gi
+                   before P (one rounding per term); the two norms are multiplied first, then the sum by their product.  A
+                   function of the two rows and their norms alone, with the bits of cos(s, c).  (bprx_sim_block's MFMA sum
+                   rounds products and sums separately: close, not bit-equal.)
+       pen_c     = max over the items s selected so far of cos(c, s); 0 before the first pick (a candidate's first cosine
+                   replaces that 0, also a negative one)
+       obj_c     = (1 - theta) rel_c - theta pen_c    1 - theta, both products and the difference are each rounded once (four
+                   roundings, nothing fused)
+   At each of min(K, M) steps the unselected candidate with the largest obj_c is selected; values compare as floats (-0 == +0),
+   equal values go to the lower pool position.  theta = 0 returns the pool's first min(K, M) candidates unchanged.
+   Outputs per list r: idx int32 [K] the picks' pool ids in selection order, val fp32 [K] their pool scores (bits unchanged), pen
+   fp32 [K] each pick's pen at the moment it was picked (its redundancy; 0 for the first), slots past min(K, M) hold -1 / 0.0f /
+   0.0f.  ild fp32 [n] (may be NULL): the intra-list diversity 1 - (sum of cos over the pairs of the list) / (T (T - 1) / 2), T =
+   min(K, M), 0 for T < 2.  The sum runs in selection order: a_t = ((cos(s_t, s_0) + cos(s_t, s_1)) + ..) + cos(s_t, s_t-1) from
+   +0 (the pick's running sum), total = ((a_0 + a_1) + ..) + a_T-1 from +0; one rounded quotient, one rounded difference.
+   A list's outputs depend on its own pool, the rows of its candidates and their norms only: not on n, its position in the call,
+   the other lists, the call, or on whether the kernel kept the rows in LDS or re-read them from memory.
+   rn_items: bprx_sim_rnorm of the catalogue in the same space.  pool_idx int32 [n, N], pool_val fp32 [n, N].
+   1 <= K <= N <= 1024, 0 <= n < 2^31 (n == 0: BPRX_OK, nothing is written), 0 <= theta <= 1.
+   Errors: BPRX_E_INVALID for a NULL handle or pointer (ild excepted; with n == 0 only rn_items is looked at), an unknown space, an ACF or AttentiveFashion handle, a
+   BPRMF handle in VISUAL / BOTH, an fp8 handle in VISUAL / BOTH, K / N / n out of range, theta outside [0, 1] or NaN;
+   BPRX_E_STATE for unbound tables.  A candidate id >= num_items is clamped (its row is item num_items - 1, the returned id is
+   the pool's) and reported by bprx_sync_check (BPRX_E_RANGE).  After any error the handle stays usable.
+   State: like bprx_sim_block the call first settles a pending dense update, brings lazy adam_tf23 rows up to date and (VISUAL /
+   BOTH) makes P current; apart from that it writes its outputs only and allocates nothing. */
+BPRX_API int bprx_diversify(bprx_handle *h, int32_t space, const float *rn_items, int64_t n, int32_t N, const int32_t *pool_idx,
+                            const float *pool_val, int32_t K, float theta, int32_t *idx, float *val, float *pen, float *ild,
+                            void *stream);
 
 /* ---- ACF (ACF.py:20-270) on a BPRMF handle ------------------------------------------------------------------------------
    Attentive Collaborative Filtering over per-item feature maps f_l [M, C] (M = H*W spatial components).  For user u with
