@@ -23,22 +23,6 @@ struct DivArgs {
   int32_t *errflag;
 };
 
-// larger float <-> larger key; -0.0 and +0.0 share one key ("values compare as floats")
-__device__ __forceinline__ uint32_t dv_key(float x) {
-  uint32_t u = __float_as_uint(x);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ unsigned long long dv_wave_max(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long w = __shfl_xor(v, o, 64);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-
 // One workgroup per list.  Thread t holds pool positions t, t + 256, t + 512, t + 768: their relevance term, running penalty and
 // running cosine sum stay in registers for the whole list.  A round = one argmax over (objective descending, position ascending)
 // -- a 64-bit key per thread, wave shuffles, four keys through LDS, ONE barrier (the key slots alternate between rounds) -- and

@@ -702,6 +702,31 @@ class Engine:
                                                    float(theta), p(idx), p(val), p(pen), p(ild), _stream()))
         return idx, val, pen, ild
 
+    def because(self, space, rn, list_idx, hist_csr, top, Pq=None, rn_q=None):
+        """bprx_because: for every entry of the lists (list_idx: contiguous int32 device tensor [n, K], catalogue ids, or rows of
+        Pq = project_rows(F) with rn_q = sim_rnorm('visual', Pq); a slot < 0 is empty) the `top` (1..32) nearest items of the
+        list's history by cosine in `space`, rn = sim_rnorm(space).  hist_csr = (int64 ptr [n + 1], int32 items) on the device,
+        list r's history.  Returns device (item int32 [n, K, top], cos fp32 [n, K, top], cnt int32 [n, K]): the history's ids by
+        descending cosine (ties: the earlier entry), -1 / 0 past the candidates, and the number of candidates (the history
+        without the explained item itself)."""
+        if list_idx.dim() != 2 or list_idx.dtype != torch.int32 or not list_idx.is_contiguous():
+            raise ValueError("because: list_idx is a contiguous int32 tensor [n, K]")
+        if Pq is not None and rn_q is None:
+            raise ValueError("because: rows from outside the catalogue come with their norms (rn_q = sim_rnorm('visual', Pq))")
+        n, K = (int(x) for x in list_idx.shape)
+        ptr, items = hist_csr
+        if ptr.dtype != torch.int64 or items.dtype != torch.int32 or int(ptr.numel()) != n + 1:
+            raise ValueError("because: hist_csr is (int64 ptr [n + 1], int32 items), one history per list")
+        top = int(top)
+        item = torch.empty((n, K, max(top, 0)), dtype=torch.int32, device=self.device)
+        cos = torch.empty((n, K, max(top, 0)), dtype=torch.float32, device=self.device)
+        cnt = torch.empty((n, K), dtype=torch.int32, device=self.device)
+        nq = self.I if Pq is None else int(Pq.shape[0])
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _ffi.check(self.h, self.lib.bprx_because(self.h, _ffi.SIM_SPACE.get(space, space), p(Pq), nq, p(rn_q), p(rn), n, K,
+                                                 p(list_idx), p(ptr), p(items), top, p(item), p(cos), p(cnt), _stream()))
+        return item, cos, cnt
+
     def _hyper(self):
         return self._lr_reg
 

@@ -18,7 +18,7 @@ from time import time
 
 import numpy as np
 
-from .ranking import lists_to_csr, rank_rows, rank_rows_host, rows_per_block, write_diverse, write_ranked
+from .ranking import lists_to_csr, rank_rows, rank_rows_host, rows_per_block, write_because, write_diverse, write_ranked
 
 
 def _eval_block(scores, u0, train, evl, K):
@@ -257,6 +257,50 @@ class Evaluator:
         ids, vals, pen, ild = self.model.recommend_diverse(None, k, pool, theta, space)
         with open(path, 'w') as out, open(path_ild, 'w') as out_ild:
             write_diverse(out, out_ild, range(ids.shape[0]), ids, vals, pen, ild)
+
+    def store_recommendation_because(self, path="", top=5, space=None):
+        """BPRMF / VBPR / GradFashion: for every (u, i) of every user's top-k list (the lists store_recommendation writes, ranked
+        again the same way) the `top` items of the user's training list nearest to i by cosine in `space` (None: the model's own)
+        as rows 'u\\ti\\tscore\\trank\\thist_item\\tcosine' in `path` (ranking.write_because).  One bprx_because call per user block
+        with the training CSR the lists were masked with.  Device only: force_host or top_k > 1024 raise ValueError."""
+        import torch
+        m = self.model
+        top, space = m._because_args(top, space)
+        eng = m.engine
+        self._metrics_device_csr()
+        ptr, items = self._csr["train"]
+        rn = eng.sim_rnorm(space)
+        U = m.data.num_users
+        with open(path, 'w') as out:
+            for u0 in range(0, U, self.user_block):
+                u1 = min(U, u0 + self.user_block)
+                ids, vals, _ = rank_rows(self._topk(u0, u1), eng.score_block(u0, u1), self.k)
+                idx = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32), device=eng.device)
+                hist, cos, _ = eng.because(space, rn, idx, (ptr[u0:u1 + 1], items), top)
+                write_because(out, range(u0, u1), ids, vals, hist.cpu().numpy(), cos.cpu().numpy())
+
+    def store_because_new(self, path="", features=None, top=5):
+        """VBPR / GradFashion: store_recommendation_because for the pairs of store_recommendation_new (every user's top-k NEW
+        items, j = the row of `features`): the user's training items nearest to the new item in the visual space."""
+        import torch
+        m = self.model
+        top, _ = m._because_args(top, "visual")
+        eng = m.engine
+        self._metrics_device_csr()
+        ptr, items = self._csr["train"]
+        F = m.prepare_new_items(features)
+        P = eng.project_rows(F)
+        rn, rq = eng.sim_rnorm("visual"), eng.sim_rnorm("visual", P)
+        U = m.data.num_users
+        with open(path, 'w') as out:
+            for u0 in range(0, U, self.user_block):
+                u1 = min(U, u0 + self.user_block)
+                ids, vals = m.recommend_new(F, self.k, u0, u1)[:2]
+                if not ids.size:
+                    continue
+                idx = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32), device=eng.device)
+                hist, cos, _ = eng.because("visual", rn, idx, (ptr[u0:u1 + 1], items), top, P, rq)
+                write_because(out, range(u0, u1), ids, vals, hist.cpu().numpy(), cos.cpu().numpy())
 
     def store_similar_new(self, path="", features=None):
         """VBPR / GradFashion: the catalogue neighbours of every row of `features` (raw rows of items outside the catalogue, as

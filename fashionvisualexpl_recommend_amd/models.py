@@ -19,7 +19,8 @@ import torch
 from . import configs
 from .engine import Engine, as_index
 from .evaluator import Evaluator
-from .ranking import diversify_rows, div_paths, rank_rows, rows_per_block, write_diverse, write_ranked
+from .ranking import (because_paths, because_rows, diversify_rows, div_paths, rank_rows, rows_per_block, write_because, write_diverse,
+                      write_ranked)
 from .synth import glorot_uniform
 
 
@@ -109,6 +110,7 @@ class BPRMF(RecommenderModel):
         self.similar_space = getattr(params, "similar_space", None) or self.sim_space
         self.diversify_theta = float(getattr(params, "diversify", 0.0) or 0.0)     # theta of the div-* files; 0: none
         self.diversify_pool = int(getattr(params, "diversify_pool", 100) or 100)   # candidates per list the MMR step picks from
+        self.because_top = int(getattr(params, "because", 0) or 0)                 # owned items per pair in because-*; 0: none
         self.directory_parameters = f'batch_{params.batch_size}-K_{params.embed_k}-lr_{params.lr}-reg_{params.reg}'
         self._build(init or {})
 
@@ -263,6 +265,7 @@ class BPRMF(RecommenderModel):
         self._store_new_user_recs(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
         self._store_similar(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
         self._store_diverse(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
+        self._store_because(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
         with open(os.path.join(rdir, f'results-metrics-{self.directory_parameters}') + '.pkl', 'wb') as f:
             pickle.dump(results, f)                                             # utils/write.py:14-22
         print("Store Best Model at Epoch {0}".format(best_epoch))
@@ -275,6 +278,7 @@ class BPRMF(RecommenderModel):
         self._store_new_user_recs(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
         self._store_similar(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
         self._store_diverse(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
+        self._store_because(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
         self.load_state_dict(last_state)
         print('End Store Best Model!')
         print('Best Values for Each Metric:\nHR\tPrec\tRec\tAUC\tnDCG\n{}\t{}\t{}\t{}\t{}\n'.format(
@@ -362,6 +366,12 @@ class BPRMF(RecommenderModel):
         new_path = os.path.join(d, f.replace("recs-", "new-user-recs-", 1))
         with open(new_path, 'w') as out:
             write_ranked(out, labels, *res)
+        if self.because_top > 0:                                 # because-new-user-recs-*: each label's own history, deduplicated
+            ids, vals = res[0], res[1]
+            hist, cos, _ = self.because(np.repeat(np.arange(len(labels)), ids.shape[1]), ids.reshape(-1), self.because_top,
+                                        lists=[list(dict.fromkeys(l)) for l in lists])
+            with open(because_paths(new_path), 'w') as out:
+                write_because(out, labels, ids, vals, hist.reshape(ids.shape + (-1,)), cos.reshape(ids.shape + (-1,)))
         if self.diversify_theta > 0:                             # div-new-user-recs-* / div-new-user-ild-*: the same fitted rows
             res = self.recommend_new_users(lists, diversify={}, steps=getattr(self.params, "fold_steps", 30),
                                            negatives=getattr(self.params, "fold_negatives", 4),
@@ -460,6 +470,58 @@ class BPRMF(RecommenderModel):
         if self.diversify_theta <= 0:
             return
         self.evaluator.store_recommendation_diverse(*div_paths(path))
+
+
+    # ---- "because you own X": the nearest owned items of a recommended one (include/bprx.h, bprx_because) ----------------------
+    def _because_args(self, top, space):
+        """(top, space) of a because-call, checked: 1 <= top <= 32, space None: similar_items' own."""
+        if not self.diverse:
+            raise NotImplementedError("%s has no item space: its explanations by the user's history come from %s"
+                                      % (type(self).__name__, self.because_instead))
+        if getattr(self.evaluator, "force_host", False) or self.evaluator.k > 1024:
+            raise ValueError("--because runs on the device only (no force_host, top_k <= 1024): there is no host form")
+        top = int(top)
+        if not 1 <= top <= 32:
+            raise ValueError("because: top lies in [1, 32] (got %d)" % top)
+        return top, self.similar_space if space is None else space
+
+    because_instead = "--feat_explain"                           # (what a model without an item space names instead)
+
+    def because(self, users, items, top=5, space=None, lists=None):
+        """For every pair (users[p], items[p]) the `top` items of the user's history that are nearest to the item by cosine in
+        `space` (None: the model's own, as similar_items): numpy hist int64 [n, top] (catalogue ids, nearest first, -1 past the
+        candidates), cos fp32 [n, top] and count int64 [n] (the history's entries without the item itself).  lists: the
+        histories, indexed by user (default: the training lists, a repeated item counted once).  Pairs may come in any order:
+        runs of equal users share one list of the call (ranking.because_rows, Engine.because)."""
+        top, space = self._because_args(top, space)
+        eng = self.engine
+        dedup = lists is None
+        if lists is None:
+            lists = _Padded(self.data.training_list, self.num_users)
+        u = np.asarray(users, dtype=np.int64).reshape(-1)
+        if u.size and (u.min() < 0 or u.max() >= len(lists)):
+            raise ValueError("because: user ids lie in [0, %d)" % len(lists))
+        rn = eng.sim_rnorm(space)
+        return because_rows(lambda li, csr: eng.because(space, rn, li, csr, top), u, items, lists, top, eng.device, dedup)
+
+    def _store_because(self, path):
+        """params.because = L > 0: because-* next to the recs-* file at `path`, rows 'u\ti\tscore\trank\thist_item\tcosine' for
+        every (u, i) of every user's top-k list."""
+        if self.because_top <= 0:
+            return
+        self.evaluator.store_recommendation_because(because_paths(path), self.because_top, self.similar_space)
+
+
+class _Padded:
+    """lists[u] for u < n: the list, [] past the end of a shorter table."""
+    def __init__(self, lists, n):
+        self.lists, self.n = lists, n
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, u):
+        return self.lists[u] if u < len(self.lists) else []
 
 
 def _stack_diverse(parts, kk, n=0):
@@ -634,6 +696,31 @@ class VBPR(BPRMF):
         blk = rows_per_block(self.evaluator.user_block, I)
         parts = [rank_rows(eng.topk_rows, eng.sim_block("visual", b0, min(n, b0 + blk), rn, P, rq), k) for b0 in range(0, n, blk)]
         return _stack_blocks(parts, min(k, I))
+
+    def because_new(self, features, users, rows, top=5):
+        """BPRMF.because for items outside the catalogue: for every pair (users[p], rows[p] of `features`: raw rows, or a table
+        from prepare_new_items) the `top` items of the user's training list nearest to the new item in the visual space."""
+        top, _ = self._because_args(top, "visual")
+        eng = self.engine
+        P = eng.project_rows(self._as_new_table(features))
+        r = np.asarray(rows, dtype=np.int64).reshape(-1)
+        u = np.asarray(users, dtype=np.int64).reshape(-1)
+        if r.size and (r.min() < 0 or r.max() >= int(P.shape[0])):
+            raise ValueError("because_new: rows lie in [0, %d)" % int(P.shape[0]))
+        if u.size and (u.min() < 0 or u.max() >= self.num_users):
+            raise ValueError("because_new: user ids lie in [0, %d)" % self.num_users)
+        rn, rq = eng.sim_rnorm("visual"), eng.sim_rnorm("visual", P)
+        return because_rows(lambda li, csr: eng.because("visual", rn, li, csr, top, P, rq), u, r,
+                            _Padded(self.data.training_list, self.num_users), top, eng.device, True)
+
+    def _store_because(self, path):
+        """because-* as every model writes it; with params.new_items also because-new-recs-* for the pairs of new-recs-*."""
+        super()._store_because(path)
+        feats = self._load_new_items() if self.because_top > 0 else None
+        if feats is None:
+            return
+        d, f = os.path.split(path)
+        self.evaluator.store_because_new(because_paths(os.path.join(d, f.replace("recs-", "new-recs-", 1))), feats, self.because_top)
 
     def _store_similar(self, path):
         """sim-* as every model writes it; with params.new_items also new-sim-*, rows 'j_new\ti\tcosine' (always the visual space)."""
@@ -1024,6 +1111,7 @@ class ACF(BPRMF):
 
     new_users_param, new_users_side = "acf_new_users", 0
     diverse = False
+    because_instead = "--acf_explain"
 
     def _store_recs(self, path):
         """recs-* / best-recs-* as every model writes them; with params.acf_explain = L > 0 also expl-* / best-expl-* next to them."""
@@ -1202,6 +1290,7 @@ class AttentiveFashion(BPRMF):
 
     new_users_param, new_users_side = "af_new_users", 3
     diverse = False
+    because_instead = "--af_explain"
 
     def _store_recs(self, path):
         """recs-* / best-recs-* with the attentions; with params.af_explain = G > 0 also expl-* / best-expl-* next to them."""

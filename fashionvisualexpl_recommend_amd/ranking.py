@@ -1,5 +1,5 @@
 """The one place where score rows become top-K lists and lists become rows of text: every recs-* / new-recs-* /
-new-user-recs-* / div-* file, single GPU or sharded, catalogue items or new ones, is ranked and written here.
+new-user-recs-* / div-* / because-* file, single GPU or sharded, catalogue items or new ones, is ranked and written here.
 
 The contract is the reference's (Evaluator.py:225-239): mask the row, then take numpy_topk of it; numpy's unstable argsort
 decides the order of EQUAL scores.  The top-K kernel returns the list wherever it does not depend on that order and flags
@@ -76,6 +76,35 @@ def diversify_rows(diversify, ids, vals, k, device):
     return idx.cpu().numpy().astype(np.int64), val.cpu().numpy(), pen.cpu().numpy(), ild.cpu().numpy()
 
 
+BECAUSE_MAX_LIST = 1024                                       # slots of one list in bprx_because
+
+
+def because_rows(because, users, items, lists, top, device, dedup=False):
+    """The nearest owned items of arbitrary (user, item) pairs: runs of equal users become the lists of one call, padded with -1
+    and split at BECAUSE_MAX_LIST entries, the history of a list is lists[user] (dedup: a repeated id counts once, the first time).
+    because(list_idx int32 [n, K], (ptr, items)) is the entry (Engine.because with its space, norms and top bound) and returns
+    the device (item [n, K, L], cos [n, K, L], cnt [n, K]), L = top.  Returns numpy hist int64 [pairs, L], cos fp32 [pairs, L]
+    and count int64 [pairs], pair by pair; without pairs the entry is not called."""
+    users, items = np.asarray(users, dtype=np.int64).reshape(-1), np.asarray(items, dtype=np.int64).reshape(-1)
+    if users.size != items.size:
+        raise ValueError("because: %d users for %d items" % (users.size, items.size))
+    if users.size == 0:
+        return np.zeros((0, int(top)), np.int64), np.zeros((0, int(top)), np.float32), np.zeros(0, np.int64)
+    run = np.cumsum(np.r_[True, users[1:] != users[:-1]]) - 1              # the run of every pair
+    first = np.flatnonzero(np.r_[True, run[1:] != run[:-1]])               # where each run starts
+    within = np.arange(users.size) - first[run]
+    chunk = within // BECAUSE_MAX_LIST
+    new = np.r_[True, (run[1:] != run[:-1]) | (chunk[1:] != chunk[:-1])]
+    li, off = np.cumsum(new) - 1, within % BECAUSE_MAX_LIST                # list and slot of every pair
+    heads = np.flatnonzero(new)
+    list_idx = np.full((heads.size, int(off.max()) + 1), -1, np.int32)
+    list_idx[li, off] = items
+    csr = lists_to_csr([lists[int(u)] for u in users[heads]], device, dedup)
+    item, cos, cnt = because(torch.as_tensor(list_idx, device=device), csr)
+    item, cos, cnt = item.cpu().numpy(), cos.cpu().numpy(), cnt.cpu().numpy()
+    return item[li, off].astype(np.int64), cos[li, off], cnt[li, off].astype(np.int64)
+
+
 def rank_rows_host(scores, mask_lists, k):
     """rank_rows on the host: row r of the numpy block `scores` gets -inf (IN `scores`) at mask_lists[r] (None: nothing is
     masked) and is listed by numpy_topk.  Returns (ids int64 [n, kk], vals [n, kk])."""
@@ -124,3 +153,33 @@ def write_diverse(out, out_ild, labels, ids, vals, pen, ild):
                 break
             out.write(head + str(item) + '\t' + str(vals[r, q]) + '\t' + str(pen[r, q]) + '\n')
         out_ild.write(head + str(ild[r]) + '\n')
+
+
+def because_paths(path):
+    """The because-* file next to the list file at `path`: 'because-' takes the place of the 'recs-' of recs-* / best-recs-* and
+    goes in front of the 'new-user-recs-' / 'new-recs-' of the other list files (best-new-recs-2-x -> best-because-new-recs-2-x)."""
+    d, sep, f = path.rpartition('/')
+    for part in ("new-user-recs-", "new-recs-"):
+        if part in f:
+            return d + sep + f.replace(part, "because-" + part, 1)
+    if "recs-" in f and "div-" not in f:
+        return d + sep + f.replace("recs-", "because-", 1)
+    raise ValueError("because_paths: %r is no recs-* path" % path)
+
+
+def write_because(out, labels, ids, vals, hist, cos):
+    """One row 'label\tid\tval\trank\thist_item\tcosine' per owned item that explains a list entry, rank 0 (the nearest) first,
+    for every entry of every list in write_ranked's order: ids / vals [n, kk] as write_ranked takes them, hist int / cos fp32
+    [n, kk, L] with -1 past an entry's candidates.  An entry without a candidate gets one row with rank -1, hist_item -1 and
+    cosine 0.0, so that the file names every pair of the list file.  Fields are formatted as write_ranked formats them."""
+    for r, label in enumerate(labels):
+        head = str(label) + '\t'
+        for q, item in enumerate(ids[r]):
+            pair = head + str(item) + '\t' + str(vals[r, q]) + '\t'
+            if hist.shape[2] == 0 or hist[r, q, 0] < 0:
+                out.write(pair + '-1\t-1\t0.0\n')
+                continue
+            for s in range(hist.shape[2]):
+                if hist[r, q, s] < 0:
+                    break
+                out.write(pair + str(s) + '\t' + str(hist[r, q, s]) + '\t' + str(cos[r, q, s]) + '\n')

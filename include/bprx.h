@@ -157,7 +157,7 @@ BPRX_API int bprx_sync_adam(bprx_handle *h, void *stream);
      bprx_project_rows, bprx_score_new_block, bprx_feat_explain_new   VBPR, not fp8       yes           yes   yes    -
      bprx_feat_explain                                                VBPR                yes           yes   -      -
      bprx_explain_pairs                                               GradFashion         yes           yes   -      -
-     bprx_sim_rnorm, bprx_sim_block, bprx_diversify                   BPRMF / VBPR        yes           yes   via P  VISUAL / BOTH
+     bprx_sim_*, bprx_diversify, bprx_because                         BPRMF / VBPR        yes           yes   via P  VISUAL / BOTH
      bprx_sync_adam                                                   any                 yes           yes   -      -
      bprx_topk_rows                                                   VBPR, not fp8       yes           -     -      -
      bprx_apply_user_msgs                                             any                 yes           -     -      -
@@ -372,6 +372,36 @@ BPRX_API int bprx_sim_block(bprx_handle *h, int32_t space, const float *Pq, int6
 BPRX_API int bprx_diversify(bprx_handle *h, int32_t space, const float *rn_items, int64_t n, int32_t N, const int32_t *pool_idx,
                             const float *pool_val, int32_t K, float theta, int32_t *idx, float *val, float *pen, float *ild,
                             void *stream);
+
+/* ---- BPRMF, VBPR and GradFashion: "because you own X", the nearest owned items of every entry of a list ---------------------
+   For each entry of each of n lists of K slots, the L items of that list's history that are nearest to it by cosine in the
+   model's item space.  space, z_i, rn_i and the handle rules are those of bprx_sim_block.
+   The explained items: Pq == NULL: list_idx[r, q] is a catalogue item (nq == num_items; rn_q is indexed by item id, may equal
+   rn_items, NULL: rn_items).  Pq != NULL (visual space only): list_idx[r, q] is a row of Pq [nq, PS] = bprx_project_rows'
+   output, rn_q fp32 [nq] = bprx_sim_rnorm of those rows.  A slot < 0 is empty.
+   The history of list r is hist_items[hist_ptr[r] .. hist_ptr[r+1]) (hist_ptr int64 [n + 1], catalogue ids); an entry is
+   identified by its position in it (fewer than 2^31 entries per list; an id may repeat, each position is an entry of its own).
+   With Pq == NULL an entry whose id equals the explained item is no candidate (as --similar_items excludes the item itself).
+   M = the number of candidates.
+       cos(q, l) = <z_q, z_l> (rn_q rn_l)   exactly bprx_diversify's: <z_q, z_l> is the serial chain a = fma(z_qx, z_lx, a) from +0
+                   in ascending x, Gi before P; the two norms are multiplied first, then the sum by their product.  It has the
+                   bits of cos(l, q) and of the pen bprx_diversify reports for the same two rows.
+   out_item int32 / out_cos fp32 [n, K, L]: slots s < min(L, M) of (r, q) hold the candidates' ids (as the history gives them)
+   and cosines by descending cosine; values compare as floats (-0 == +0), equal values go to the lower history position.  Slots
+   past min(L, M), and every slot of an empty list slot, hold -1 / 0.0f.  out_cnt int32 [n, K] (may be NULL): M, 0 for an empty
+   slot.  The outputs of (r, q) depend on that item's row, the history's rows and the norms only: not on K, n, the other slots,
+   or on how the kernel chunks a list or tiles a history.
+   1 <= L <= 32, 1 <= K <= 1024, 0 <= n < 2^31 (n == 0: BPRX_OK, nothing is written), any history length.
+   Errors: BPRX_E_INVALID for a NULL handle or pointer (out_cnt excepted; rn_q may be NULL with Pq == NULL; with n == 0 only the
+   norms are looked at), K / L / n out of range, every space / handle / Pq / nq combination bprx_sim_block rejects, and an item
+   space too wide for two rows in a workgroup's LDS (more than about 8000 numbers); BPRX_E_STATE for unbound tables.  An id >=
+   num_items (a list entry >= nq) is clamped (the returned id is the history's) and reported by bprx_sync_check (BPRX_E_RANGE).
+   After any error the handle stays usable.
+   State: like bprx_sim_block the call first settles a pending dense update, brings lazy adam_tf23 rows up to date and (VISUAL /
+   BOTH) makes P current; apart from that it writes its outputs only and allocates nothing. */
+BPRX_API int bprx_because(bprx_handle *h, int32_t space, const float *Pq, int64_t nq, const float *rn_q, const float *rn_items,
+                          int64_t n, int32_t K, const int32_t *list_idx, const int64_t *hist_ptr, const int32_t *hist_items,
+                          int32_t L, int32_t *out_item, float *out_cos, int32_t *out_cnt, void *stream);
 
 /* ---- ACF (ACF.py:20-270) on a BPRMF handle ------------------------------------------------------------------------------
    Attentive Collaborative Filtering over per-item feature maps f_l [M, C] (M = H*W spatial components).  For user u with
