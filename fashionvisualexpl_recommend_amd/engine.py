@@ -17,7 +17,13 @@ FACTORED_PARAM_NAMES = ("Gu", "Gi", "Bi", "Tu", "Ec", "Ee", "E", "Bp")     # Gra
 
 
 def _ptr(t):
+    """NULL for None or an empty tensor, else the tensor's address."""
     return None if (t is None or t.numel() == 0) else C.c_void_p(t.data_ptr())
+
+
+def _addr(t):
+    """NULL for None, else the tensor's address: an empty tensor still reaches the library's own argument checks."""
+    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _stream():
@@ -328,20 +334,47 @@ class Engine:
                "peak": g(*shape), "beta_peak": f(*shape)}
         if maps:
             out["beta"] = f(n, max(top, 0), int(self.acf_F.shape[1]) if getattr(self, "acf", False) else 1)
-        p = lambda t: C.c_void_p(t.data_ptr())      # (an empty tensor still has to reach the library's argument checks)
-        _ffi.check(self.h, self.lib.bprx_acf_explain(self.h, p(u), p(i), n, p(ptr), p(hist), top, p(out["score"]), p(out["base"]),
-                                                     p(out["pos"]), p(out["hist_item"]), p(out["alpha"]), p(out["contrib"]),
-                                                     p(out["peak"]), p(out["beta_peak"]), p(out["beta"]) if maps else None,
-                                                     _stream()))
+        _ffi.check(self.h, self.lib.bprx_acf_explain(self.h, _addr(u), _addr(i), n, _addr(ptr), _addr(hist), top,
+                                                     *(_addr(out[name]) for name in ("score", "base", "pos", "hist_item", "alpha",
+                                                                                     "contrib", "peak", "beta_peak")),
+                                                     _addr(out["beta"]) if maps else None, _stream()))
         return out
 
     def _acf_rows(self, what, Gu_rows, lists, csr):
         """(hist_ptr, hist_items, n) of a caller-owned table Gu_rows [n, k] and its histories by row."""
         ptr, items = csr if csr is not None else self.csr(lists)
         n = int(ptr.numel()) - 1
-        if not (Gu_rows.is_cuda and Gu_rows.dtype == torch.float32 and Gu_rows.is_contiguous() and tuple(Gu_rows.shape) == (n, self.k)):
-            raise ValueError("%s: Gu_rows must be a contiguous fp32 device tensor [%d, %d]" % (what, n, self.k))
+        self._check_rows(what, n, ("Gu_rows", Gu_rows, self.k))
         return ptr, items, n
+
+    def _check_rows(self, what, n, *rows):
+        """Each (name, tensor, width) of `rows` is a caller-owned row table [n, width] the library may write: ValueError unless it
+        is a contiguous fp32 device tensor of that shape (None: the model has no such table)."""
+        for name, t, w in rows:
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n, w)):
+                raise ValueError("%s: %s must be a contiguous fp32 device tensor [%d, %d]" % (what, name, n, w))
+
+    def _fold_in(self, what, entry, lead, pair_ptr, pos, neg, steps, rows, lr, reg, optimizer, want_loss, hist_rows=None):
+        """The body of fold_in / acf_fold_in / af_fold_in (`what`, for the messages): entry(h, *lead, pair_ptr, pos, neg, n, steps,
+        lr, reg, optimizer, *row tables, loss, stream) after the checks they share.  rows: the (name, tensor, width) row tables as
+        _check_rows takes them; hist_rows: the rows the histories behind `lead` were given for."""
+        ptr = torch.as_tensor(pair_ptr, dtype=torch.int64).to(self.device).contiguous()
+        n = int(ptr.numel()) - 1
+        if hist_rows is not None and n != hist_rows:
+            raise ValueError("%s: pair_ptr for %d rows, histories for %d" % (what, n, hist_rows))
+        p_, n_ = as_index(pos, self.device), as_index(neg, self.device)
+        if p_.numel() != n_.numel():
+            raise ValueError("%s: %d positives for %d negatives" % (what, p_.numel(), n_.numel()))
+        self._check_rows(what, n, *rows)
+        lr = self._hyper()[0] if lr is None else float(lr)
+        reg = self._hyper()[1] if reg is None else float(reg)
+        opt = _ffi.OPTIMIZER[self.optimizer if optimizer is None else optimizer]
+        loss = torch.empty(max(n, 0), dtype=torch.float32, device=self.device) if want_loss else None
+        if p_.numel() == 0:                                  # (nobody has a pair: the library still wants the pointers)
+            p_ = n_ = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _ffi.check(self.h, entry(self.h, *lead, _addr(ptr), _addr(p_), _addr(n_), n, int(steps), lr, reg, opt,
+                                 *(_addr(t) for _, t, _ in rows), _addr(loss), _stream()))
+        return loss
 
     def acf_fold_in(self, pair_ptr, pos, neg, steps, Gu_rows, lists=None, csr=None, lr=None, reg=None, optimizer=None,
                     want_loss=True):
@@ -350,30 +383,15 @@ class Engine:
         the row's history (`lists` per row, or a prebuilt `csr`), everything but the row frozen.  pair_ptr: int64 [n + 1].
         lr / reg / optimizer default to the engine's.  Returns loss fp32 [n] (loss_steps, before the last update) or None."""
         hp, hi, n = self._acf_rows("acf_fold_in", Gu_rows, lists, csr)
-        ptr = torch.as_tensor(pair_ptr, dtype=torch.int64).to(self.device).contiguous()
-        if int(ptr.numel()) - 1 != n:
-            raise ValueError("acf_fold_in: pair_ptr for %d rows, histories for %d" % (int(ptr.numel()) - 1, n))
-        p_, n_ = as_index(pos, self.device), as_index(neg, self.device)
-        if p_.numel() != n_.numel():
-            raise ValueError("acf_fold_in: %d positives for %d negatives" % (p_.numel(), n_.numel()))
-        lr = self._hyper()[0] if lr is None else float(lr)
-        reg = self._hyper()[1] if reg is None else float(reg)
-        opt = _ffi.OPTIMIZER[self.optimizer if optimizer is None else optimizer]
-        loss = torch.empty(max(n, 0), dtype=torch.float32, device=self.device) if want_loss else None
-        if p_.numel() == 0:                                  # (nobody has a pair: the library still wants the pointers)
-            p_ = n_ = torch.zeros(1, dtype=torch.int32, device=self.device)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _ffi.check(self.h, self.lib.bprx_acf_fold_in(self.h, p(hp), p(hi), p(ptr), p(p_), p(n_), n, int(steps), lr, reg, opt,
-                                                     p(Gu_rows), p(loss), _stream()))
-        return loss
+        return self._fold_in("acf_fold_in", self.lib.bprx_acf_fold_in, (_addr(hp), _addr(hi)), pair_ptr, pos, neg, steps,
+                             (("Gu_rows", Gu_rows, self.k),), lr, reg, optimizer, want_loss, hist_rows=n)
 
     def acf_profile_rows(self, Gu_rows, lists=None, csr=None):
         """bprx_acf_profile_rows: g'_r [n, k] of the rows of a caller-owned table with the histories `lists` (per row, or a
         prebuilt `csr`)."""
         hp, hi, n = self._acf_rows("acf_profile_rows", Gu_rows, lists, csr)
         out = torch.empty((n, self.k), dtype=torch.float32, device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        _ffi.check(self.h, self.lib.bprx_acf_profile_rows(self.h, p(Gu_rows), n, p(hp), p(hi), p(out), _stream()))
+        _ffi.check(self.h, self.lib.bprx_acf_profile_rows(self.h, _addr(Gu_rows), n, _addr(hp), _addr(hi), _addr(out), _stream()))
         return out
 
     def acf_score_rows_block(self, Gu_rows, r0, r1, lists=None, csr=None):
@@ -381,8 +399,8 @@ class Engine:
         row of the whole table, or a prebuilt `csr`): scores [r1 - r0, I]."""
         hp, hi, n = self._acf_rows("acf_score_rows_block", Gu_rows, lists, csr)
         x = torch.empty((max(r1 - r0, 0), self.I), dtype=torch.float32, device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        _ffi.check(self.h, self.lib.bprx_acf_score_rows_block(self.h, p(Gu_rows), n, p(hp), p(hi), int(r0), int(r1), p(x), _stream()))
+        _ffi.check(self.h, self.lib.bprx_acf_score_rows_block(self.h, _addr(Gu_rows), n, _addr(hp), _addr(hi), int(r0), int(r1),
+                                                              _addr(x), _stream()))
         return x
 
     def bind_attentive(self, Gu, Gi, Bi, edges, color, cls, weights, dropout=0.5, seed=0, slots=None):
@@ -457,12 +475,12 @@ class Engine:
                "peak_val": f(n)}
         if maps:
             out["map"] = f(n, G2)
-        p = lambda t, r0: C.c_void_p(t.data_ptr() + r0 * t.stride(0) * t.element_size() if t.numel() else t.data_ptr())
+        at = lambda t, r0: C.c_void_p(t.data_ptr() + r0 * t.stride(0) * t.element_size() if t.numel() else t.data_ptr())
         for r0 in range(0, max(n, 1), self.max_batch):          # (an empty call still reaches the library's argument checks)
             m = min(self.max_batch, n - r0)
-            _ffi.check(self.h, self.lib.bprx_af_explain(self.h, p(u, r0), p(i, r0), m, G, p(out["score"], r0), p(out["alpha"], r0),
-                                                        p(out["parts"], r0), p(out["map"], r0) if maps else None,
-                                                        p(out["peak_cell"], r0), p(out["peak_val"], r0), _stream()))
+            _ffi.check(self.h, self.lib.bprx_af_explain(self.h, at(u, r0), at(i, r0), m, G, at(out["score"], r0), at(out["alpha"], r0),
+                                                        at(out["parts"], r0), at(out["map"], r0) if maps else None,
+                                                        at(out["peak_cell"], r0), at(out["peak_val"], r0), _stream()))
         return out
 
     def af_score_block(self, u0, u1):
@@ -477,32 +495,16 @@ class Engine:
         PLACE) over the pairs (pos[p], neg[p]), p in [pair_ptr[r], pair_ptr[r + 1]), of row r, the item side, the encoders and the
         attention tensors frozen and dropout off.  pair_ptr: int64 [n + 1].  lr / reg / optimizer default to the engine's.
         Returns loss fp32 [n] (loss_steps, before the last update) or None."""
-        ptr = torch.as_tensor(pair_ptr, dtype=torch.int64).to(self.device).contiguous()
-        n = int(ptr.numel()) - 1
-        p_, n_ = as_index(pos, self.device), as_index(neg, self.device)
-        if p_.numel() != n_.numel():
-            raise ValueError("af_fold_in: %d positives for %d negatives" % (p_.numel(), n_.numel()))
-        if not (Gu_rows.is_cuda and Gu_rows.dtype == torch.float32 and Gu_rows.is_contiguous() and tuple(Gu_rows.shape) == (n, self.k)):
-            raise ValueError("af_fold_in: Gu_rows must be a contiguous fp32 device tensor [%d, %d]" % (n, self.k))
-        lr = self._hyper()[0] if lr is None else float(lr)
-        reg = self._hyper()[1] if reg is None else float(reg)
-        opt = _ffi.OPTIMIZER[self.optimizer if optimizer is None else optimizer]
-        loss = torch.empty(max(n, 0), dtype=torch.float32, device=self.device) if want_loss else None
-        if p_.numel() == 0:                                  # (nobody has a pair: the library still wants the pointers)
-            p_ = n_ = torch.zeros(1, dtype=torch.int32, device=self.device)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _ffi.check(self.h, self.lib.bprx_af_fold_in(self.h, p(ptr), p(p_), p(n_), n, int(steps), lr, reg, opt, p(Gu_rows), p(loss),
-                                                    _stream()))
-        return loss
+        return self._fold_in("af_fold_in", self.lib.bprx_af_fold_in, (), pair_ptr, pos, neg, steps, (("Gu_rows", Gu_rows, self.k),),
+                             lr, reg, optimizer, want_loss)
 
     def af_score_rows_block(self, Gu_rows, r0, r1, want_alpha=True):
         """bprx_af_score_rows_block: af_score_block for rows [r0, r1) of a caller-owned user table: scores [r1 - r0, I] and
         attentions [r1 - r0, I, 3] (None with want_alpha=False)."""
         x = torch.empty((r1 - r0, self.I), dtype=torch.float32, device=self.device)
         al = torch.empty((r1 - r0, self.I, 3), dtype=torch.float32, device=self.device) if want_alpha else None
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _ffi.check(self.h, self.lib.bprx_af_score_rows_block(self.h, p(Gu_rows), int(Gu_rows.shape[0]), int(r0), int(r1), p(x), p(al),
-                                                             _stream()))
+        _ffi.check(self.h, self.lib.bprx_af_score_rows_block(self.h, _addr(Gu_rows), int(Gu_rows.shape[0]), int(r0), int(r1),
+                                                             _addr(x), _addr(al), _stream()))
         return x, al
 
     def af_dropout_mask(self, step, n_rows):
@@ -544,10 +546,9 @@ class Engine:
         if maps:
             out["map"] = f(n, max(ncols, 0))
         F = self._t.get("F")
-        p = lambda t: C.c_void_p(t.data_ptr())      # (an empty tensor still has to reach the library's argument checks)
-        _ffi.check(self.h, self.lib.bprx_feat_explain(self.h, None if F is None else p(F), p(u), p(i), n, ncols, top, p(out["score"]),
-                                                      p(out["base"]), p(out["visual"]), p(out["col"]), p(out["contrib"]),
-                                                      p(out["map"]) if maps else None, _stream()))
+        _ffi.check(self.h, self.lib.bprx_feat_explain(self.h, _addr(F), _addr(u), _addr(i), n, ncols, top,
+                                                      _addr(out["score"]), _addr(out["base"]), _addr(out["visual"]), _addr(out["col"]),
+                                                      _addr(out["contrib"]), _addr(out["map"]) if maps else None, _stream()))
         return out
 
     # ---- items outside the catalogue (include/bprx.h: x_uj = Tu_u.(f_j E) + f_j.Bp, no Gi / Bi term) --------------------------
@@ -568,8 +569,7 @@ class Engine:
         Ft = self._new_table(F)
         n = int(Ft.shape[0])
         P = torch.empty((n, self.proj_stride()), dtype=torch.float32, device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        _ffi.check(self.h, self.lib.bprx_project_rows(self.h, p(Ft), n, p(P), _stream()))
+        _ffi.check(self.h, self.lib.bprx_project_rows(self.h, _addr(Ft), n, _addr(P), _stream()))
         return P
 
     def score_new_block(self, u0, u1, P, out=None):
@@ -577,8 +577,7 @@ class Engine:
         n = int(P.shape[0])
         if out is None:
             out = torch.empty((u1 - u0, n), dtype=torch.float32, device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        _ffi.check(self.h, self.lib.bprx_score_new_block(self.h, int(u0), int(u1), p(P), n, p(out), _stream()))
+        _ffi.check(self.h, self.lib.bprx_score_new_block(self.h, int(u0), int(u1), _addr(P), n, _addr(out), _stream()))
         return out
 
     def topk_rows(self, scores, K):
@@ -587,8 +586,7 @@ class Engine:
         nrows, width = (int(x) for x in scores.shape)
         K = int(K)
         idx, val, flag = self._topk_out(nrows, K)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        _ffi.check(self.h, self.lib.bprx_topk_rows(self.h, nrows, width, p(scores), K, p(idx), p(val), p(flag), _stream()))
+        _ffi.check(self.h, self.lib.bprx_topk_rows(self.h, nrows, width, _addr(scores), K, _addr(idx), _addr(val), _addr(flag), _stream()))
         return idx, val, flag
 
     def feat_explain_new(self, F, user, row, top=5, ncols=None, maps=False):
@@ -605,10 +603,9 @@ class Engine:
         out["visual"] = out["score"]
         if maps:
             out["map"] = f(n, max(ncols, 0))
-        p = lambda t: C.c_void_p(t.data_ptr())
-        _ffi.check(self.h, self.lib.bprx_feat_explain_new(self.h, p(Ft), int(Ft.shape[0]), p(u), p(r), n, ncols, top, p(out["score"]),
-                                                          p(out["col"]), p(out["contrib"]), p(out["map"]) if maps else None,
-                                                          _stream()))
+        _ffi.check(self.h, self.lib.bprx_feat_explain_new(self.h, _addr(Ft), int(Ft.shape[0]), _addr(u), _addr(r), n, ncols, top,
+                                                          _addr(out["score"]), _addr(out["col"]), _addr(out["contrib"]),
+                                                          _addr(out["map"]) if maps else None, _stream()))
         return out
 
     # ---- users outside the training set (include/bprx.h: the reference's step on one user's pairs, the item side frozen) -------
@@ -617,34 +614,15 @@ class Engine:
         updated IN PLACE; Tu_rows is None iff d == 0) over the pairs (pos[p], neg[p]), p in [pair_ptr[r], pair_ptr[r + 1]), of row
         r.  pair_ptr: int64 [n + 1].  lr / reg / optimizer default to the engine's.  Returns loss fp32 [n] (loss_steps, before the
         last update) or None."""
-        ptr = torch.as_tensor(pair_ptr, dtype=torch.int64).to(self.device).contiguous()
-        n = int(ptr.numel()) - 1
-        p_, n_ = as_index(pos, self.device), as_index(neg, self.device)
-        if p_.numel() != n_.numel():
-            raise ValueError("fold_in: %d positives for %d negatives" % (p_.numel(), n_.numel()))
-        for name, t, w in (("Gu_rows", Gu_rows, self.k), ("Tu_rows", Tu_rows, self.d)):
-            if t is None:
-                continue
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n, w)):
-                raise ValueError("fold_in: %s must be a contiguous fp32 device tensor [%d, %d]" % (name, n, w))
-        lr = self._hyper()[0] if lr is None else float(lr)
-        reg = self._hyper()[1] if reg is None else float(reg)
-        opt = _ffi.OPTIMIZER[self.optimizer if optimizer is None else optimizer]
-        loss = torch.empty(max(n, 0), dtype=torch.float32, device=self.device) if want_loss else None
-        if p_.numel() == 0:                                  # (nobody has a pair: the library still wants the pointers)
-            p_ = n_ = torch.zeros(1, dtype=torch.int32, device=self.device)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _ffi.check(self.h, self.lib.bprx_fold_in(self.h, p(ptr), p(p_), p(n_), n,
-                                                 int(steps), lr, reg, opt, p(Gu_rows), p(Tu_rows), p(loss), _stream()))
-        return loss
+        return self._fold_in("fold_in", self.lib.bprx_fold_in, (), pair_ptr, pos, neg, steps,
+                             (("Gu_rows", Gu_rows, self.k), ("Tu_rows", Tu_rows, self.d)), lr, reg, optimizer, want_loss)
 
     def score_rows_block(self, Gu_rows, Tu_rows, r0, r1, out=None):
         """bprx_score_rows_block: score_block for rows [r0, r1) of caller-owned user tables: fp32 [r1 - r0, I]."""
         if out is None:
             out = torch.empty((r1 - r0, self.I), dtype=torch.float32, device=self.device)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _ffi.check(self.h, self.lib.bprx_score_rows_block(self.h, p(Gu_rows), p(Tu_rows), int(Gu_rows.shape[0]), int(r0), int(r1),
-                                                          p(out), _stream()))
+        _ffi.check(self.h, self.lib.bprx_score_rows_block(self.h, _addr(Gu_rows), _addr(Tu_rows), int(Gu_rows.shape[0]), int(r0), int(r1),
+                                                          _addr(out), _stream()))
         return out
 
     def topk_lists(self, scores, lists_csr, K):
@@ -653,8 +631,8 @@ class Engine:
         nrows, K = int(scores.shape[0]), int(K)
         idx, val, flag = self._topk_out(nrows, K)
         ptr, items = lists_csr
-        p = lambda t: C.c_void_p(t.data_ptr())
-        _ffi.check(self.h, self.lib.bprx_topk_lists(self.h, nrows, p(scores), p(ptr), p(items), K, p(idx), p(val), p(flag), _stream()))
+        _ffi.check(self.h, self.lib.bprx_topk_lists(self.h, nrows, _addr(scores), _addr(ptr), _addr(items), K, _addr(idx), _addr(val),
+                                                    _addr(flag), _stream()))
         return idx, val, flag
 
     # ---- similar items (include/bprx.h: the cosine of two item vectors, z = Gi | f E | both) --------------------------------------
@@ -663,8 +641,7 @@ class Engine:
         zero row); with Pq = project_rows(F): fp32 [n] of those rows (visual only)."""
         n = self.I if Pq is None else int(Pq.shape[0])
         rn = torch.empty(n, dtype=torch.float32, device=self.device)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _ffi.check(self.h, self.lib.bprx_sim_rnorm(self.h, _ffi.SIM_SPACE.get(space, space), p(Pq), n, p(rn), _stream()))
+        _ffi.check(self.h, self.lib.bprx_sim_rnorm(self.h, _ffi.SIM_SPACE.get(space, space), _addr(Pq), n, _addr(rn), _stream()))
         return rn
 
     def sim_block(self, space, q0, q1, rn_items, Pq=None, rn_q=None, out=None):
@@ -677,9 +654,8 @@ class Engine:
         nq = self.I if Pq is None else int(Pq.shape[0])
         if out is None:
             out = torch.empty((max(q1 - q0, 0), self.I), dtype=torch.float32, device=self.device)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _ffi.check(self.h, self.lib.bprx_sim_block(self.h, _ffi.SIM_SPACE.get(space, space), p(Pq), nq, int(q0), int(q1), p(rn_q),
-                                                   p(rn_items), p(out), _stream()))
+        _ffi.check(self.h, self.lib.bprx_sim_block(self.h, _ffi.SIM_SPACE.get(space, space), _addr(Pq), nq, int(q0), int(q1), _addr(rn_q),
+                                                   _addr(rn_items), _addr(out), _stream()))
         return out
 
     def diversify(self, space, rn, pool_idx, pool_val, k, theta):
@@ -697,9 +673,9 @@ class Engine:
         idx = torch.empty((n, max(k, 0)), dtype=torch.int32, device=self.device)
         val, pen = (torch.empty((n, max(k, 0)), dtype=torch.float32, device=self.device) for _ in range(2))
         ild = torch.empty(n, dtype=torch.float32, device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        _ffi.check(self.h, self.lib.bprx_diversify(self.h, _ffi.SIM_SPACE.get(space, space), p(rn), n, N, p(pool_idx), p(pool_val), k,
-                                                   float(theta), p(idx), p(val), p(pen), p(ild), _stream()))
+        _ffi.check(self.h, self.lib.bprx_diversify(self.h, _ffi.SIM_SPACE.get(space, space), _addr(rn), n, N, _addr(pool_idx),
+                                                   _addr(pool_val), k, float(theta), _addr(idx), _addr(val), _addr(pen), _addr(ild),
+                                                   _stream()))
         return idx, val, pen, ild
 
     def because(self, space, rn, list_idx, hist_csr, top, Pq=None, rn_q=None):
@@ -722,9 +698,9 @@ class Engine:
         cos = torch.empty((n, K, max(top, 0)), dtype=torch.float32, device=self.device)
         cnt = torch.empty((n, K), dtype=torch.int32, device=self.device)
         nq = self.I if Pq is None else int(Pq.shape[0])
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _ffi.check(self.h, self.lib.bprx_because(self.h, _ffi.SIM_SPACE.get(space, space), p(Pq), nq, p(rn_q), p(rn), n, K,
-                                                 p(list_idx), p(ptr), p(items), top, p(item), p(cos), p(cnt), _stream()))
+        _ffi.check(self.h, self.lib.bprx_because(self.h, _ffi.SIM_SPACE.get(space, space), _addr(Pq), nq, _addr(rn_q), _addr(rn), n, K,
+                                                 _addr(list_idx), _addr(ptr), _addr(items), top, _addr(item), _addr(cos), _addr(cnt),
+                                                 _stream()))
         return item, cos, cnt
 
     def _hyper(self):

@@ -18,7 +18,7 @@ from time import time
 
 import numpy as np
 
-from .ranking import lists_to_csr, rank_rows, rank_rows_host, rows_per_block, write_because, write_diverse, write_ranked
+from .ranking import blocks, lists_to_csr, rank_rows, rank_rows_host, write_because, write_diverse, write_feature_rows, write_ranked
 
 
 def _eval_block(scores, u0, train, evl, K):
@@ -75,11 +75,9 @@ class Evaluator:
         self.model = model
         self.user_block = user_block
 
-    def _score_blocks(self):
-        U = self.model.data.num_users
-        for u0 in range(0, U, self.user_block):
-            u1 = min(U, u0 + self.user_block)
-            yield u0, self.model.predict_block(u0, u1)
+    def _user_blocks(self, width=None):
+        """ranking.blocks over the model's users, user_block at a time (width: cut for rows of that many scores)."""
+        return blocks(self.model.data.num_users, self.user_block, width)
 
     # ---- device path (libbprx bprx_score_block + bprx_eval_users): used whenever the model runs on the engine ----
     def _device_csr(self, lists, device, dedup=False):
@@ -89,10 +87,8 @@ class Evaluator:
         import torch
         eng = self.model.engine
         self._metrics_device_csr()
-        U = self.model.data.num_users
         rows = {"test": [], "val": []}
-        for u0 in range(0, U, self.user_block):
-            u1 = min(U, u0 + self.user_block)
+        for u0, u1 in self._user_blocks():
             sc = eng.score_block(u0, u1)
             for key in ("test", "val"):
                 if self._csr[key] is not None:
@@ -117,7 +113,8 @@ class Evaluator:
                 return m
         res_t, res_v = [], []
         val = bool(self.data.validation_list)
-        for u0, sc in self._score_blocks():
+        for u0, u1 in self._user_blocks():
+            sc = self.model.predict_block(u0, u1)
             res_t += _eval_block(sc, u0, self.data.training_list, self.data.test_list, self.k)
             if val:
                 res_v += _eval_block(sc, u0, self.data.training_list, self.data.validation_list, self.k)
@@ -157,9 +154,7 @@ class Evaluator:
         per user block with the (u, item) of the rows just written, in their order."""
         eng = self.model.engine
         self._metrics_device_csr()
-        U = self.model.data.num_users
-        for u0 in range(0, U, self.user_block):
-            u1 = min(U, u0 + self.user_block)
+        for u0, u1 in self._user_blocks():
             ids, vals, _ = rank_rows(self._topk(u0, u1), eng.score_block(u0, u1), self.k)
             self._write_block(out, range(u0, u1), ids, vals, None, block_hook)
 
@@ -194,28 +189,17 @@ class Evaluator:
         if getattr(self.model, "engine", None) is not None and not getattr(self, "force_host", False) and self.k <= 1024:
             self._store_recommendation_device(out, block_hook)
             return
-        for u0, sc in self._score_blocks():
-            u1 = u0 + sc.shape[0]
-            ids, vals = rank_rows_host(sc, self.data.training_list[u0:u1], self.k)
+        for u0, u1 in self._user_blocks():
+            ids, vals = rank_rows_host(self.model.predict_block(u0, u1), self.data.training_list[u0:u1], self.k)
             self._write_block(out, range(u0, u1), ids, vals, None, block_hook)
-
-    def _write_feature_rows(self, ex, users, items, top):
-        """The expl-* rows of VBPR and GradFashion for the pairs (users, items), one bprx_feat_explain call:
-        'u\\ti\\tscore\\tbase\\trank\\tcolumn\\tcontribution', rank 0 (the largest F_ic w_uc) first, one row per rank below
-        min(top, feature columns); score = base + the sum of all the pair's contributions."""
-        e = self.model.explain(users, items, top)
-        for r, (u, i) in enumerate(zip(users, items)):
-            head = str(u) + '\t' + str(i) + '\t' + str(e["score"][r]) + '\t' + str(e["base"][r]) + '\t'
-            for s in range(e["col"].shape[1]):
-                if e["col"][r, s] < 0:
-                    break
-                ex.write(head + str(s) + '\t' + str(e["col"][r, s]) + '\t' + str(e["contrib"][r, s]) + '\n')
 
     def store_recommendation_features(self, path_recs="", path_expl="", top=5):
         """VBPR: `path_recs` exactly as store_recommendation writes it (the same device or host path), and for every row written
-        there the rows of _write_feature_rows in `path_expl`, one call per user block."""
+        there the rows of ranking.write_feature_rows in `path_expl` (rank below min(top, feature columns); score = base + the sum
+        of all the pair's contributions), one bprx_feat_explain call per user block."""
         with open(path_recs, 'w') as out, open(path_expl, 'w') as ex:
-            self._store_recommendation_rows(out, lambda users, items: self._write_feature_rows(ex, users, items, top))
+            self._store_recommendation_rows(out, lambda users, items: write_feature_rows(ex, users, items,
+                                                                                         self.model.explain(users, items, top)))
 
     def store_recommendation_new(self, path="", features=None, path_expl=None, top=0):
         """VBPR / GradFashion: the top-k NEW items of every user (model.recommend_new: the visual score, nothing masked) as rows
@@ -224,22 +208,13 @@ class Evaluator:
         the same pairs in the same order, rank 0 first, one row per rank below min(top, feature columns); there is no base."""
         m = self.model
         F = m.prepare_new_items(features)
-        U = m.data.num_users
         with open(path, 'w') as out, (open(path_expl, 'w') if path_expl and top > 0 else contextlib.nullcontext()) as ex:
-            for u0 in range(0, U, self.user_block):
-                u1 = min(U, u0 + self.user_block)
+            for u0, u1 in self._user_blocks():
                 res = m.recommend_new(F, self.k, u0, u1, explain=top if ex is not None else 0)
                 idx, val = res[0], res[1]
                 write_ranked(out, range(u0, u1), idx, val)
-                if ex is None or not idx.size:
-                    continue
-                e, kk = res[2], idx.shape[1]
-                for p in range(e["col"].shape[0]):
-                    head = str(u0 + p // kk) + '\t' + str(idx[p // kk, p % kk]) + '\t' + str(e["score"][p]) + '\t'
-                    for s in range(e["col"].shape[1]):
-                        if e["col"][p, s] < 0:
-                            break
-                        ex.write(head + str(s) + '\t' + str(e["col"][p, s]) + '\t' + str(e["contrib"][p, s]) + '\n')
+                if ex is not None and idx.size:
+                    write_feature_rows(ex, np.repeat(np.arange(u0, u1), idx.shape[1]), idx.reshape(-1), res[2])
 
     def store_similar_items(self, path="", space=None):
         """Every catalogue item's nearest neighbours by cosine in `space` (model.similar_items: None = the model's own space, the
@@ -263,43 +238,36 @@ class Evaluator:
         again the same way) the `top` items of the user's training list nearest to i by cosine in `space` (None: the model's own)
         as rows 'u\\ti\\tscore\\trank\\thist_item\\tcosine' in `path` (ranking.write_because).  One bprx_because call per user block
         with the training CSR the lists were masked with.  Device only: force_host or top_k > 1024 raise ValueError."""
-        import torch
-        m = self.model
-        top, space = m._because_args(top, space)
-        eng = m.engine
+        top, space = self.model._because_args(top, space)
+        eng = self.model.engine
         self._metrics_device_csr()
-        ptr, items = self._csr["train"]
-        rn = eng.sim_rnorm(space)
-        U = m.data.num_users
-        with open(path, 'w') as out:
-            for u0 in range(0, U, self.user_block):
-                u1 = min(U, u0 + self.user_block)
-                ids, vals, _ = rank_rows(self._topk(u0, u1), eng.score_block(u0, u1), self.k)
-                idx = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32), device=eng.device)
-                hist, cos, _ = eng.because(space, rn, idx, (ptr[u0:u1 + 1], items), top)
-                write_because(out, range(u0, u1), ids, vals, hist.cpu().numpy(), cos.cpu().numpy())
+        lists = lambda u0, u1: rank_rows(self._topk(u0, u1), eng.score_block(u0, u1), self.k)[:2]
+        self._store_because(path, lists, top, space, eng.sim_rnorm(space))
 
     def store_because_new(self, path="", features=None, top=5):
         """VBPR / GradFashion: store_recommendation_because for the pairs of store_recommendation_new (every user's top-k NEW
         items, j = the row of `features`): the user's training items nearest to the new item in the visual space."""
-        import torch
         m = self.model
         top, _ = m._because_args(top, "visual")
-        eng = m.engine
         self._metrics_device_csr()
-        ptr, items = self._csr["train"]
         F = m.prepare_new_items(features)
-        P = eng.project_rows(F)
-        rn, rq = eng.sim_rnorm("visual"), eng.sim_rnorm("visual", P)
-        U = m.data.num_users
+        P = m.engine.project_rows(F)
+        lists = lambda u0, u1: m.recommend_new(F, self.k, u0, u1)[:2]
+        self._store_because(path, lists, top, "visual", m.engine.sim_rnorm("visual"), P, m.engine.sim_rnorm("visual", P))
+
+    def _store_because(self, path, lists, top, space, rn, Pq=None, rn_q=None):
+        """The because-* file of the lists (ids, vals) = lists(u0, u1) of every user block: one bprx_because call per block (none
+        for a block without a list entry) with the training CSR, rn / Pq / rn_q as Engine.because takes them."""
+        import torch
+        eng = self.model.engine
+        ptr, items = self._csr["train"]
         with open(path, 'w') as out:
-            for u0 in range(0, U, self.user_block):
-                u1 = min(U, u0 + self.user_block)
-                ids, vals = m.recommend_new(F, self.k, u0, u1)[:2]
+            for u0, u1 in self._user_blocks():
+                ids, vals = lists(u0, u1)
                 if not ids.size:
                     continue
                 idx = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32), device=eng.device)
-                hist, cos, _ = eng.because("visual", rn, idx, (ptr[u0:u1 + 1], items), top, P, rq)
+                hist, cos, _ = eng.because(space, rn, idx, (ptr[u0:u1 + 1], items), top, Pq, rn_q)
                 write_because(out, range(u0, u1), ids, vals, hist.cpu().numpy(), cos.cpu().numpy())
 
     def store_similar_new(self, path="", features=None):
@@ -313,12 +281,10 @@ class Evaluator:
         """Evaluator.py:261-275 (GradFashion): for every user the items training_list[u] + validation_list[u] + test_list[u],
         in that order, one row 'u\\ti\\tcolour\\tedges' each (get_explanations.py:19-21 reads USER_ID, ITEM_ID, COLOR, EDGES).
         The attributions come from the device, one bprx_explain_pairs call per block of users.  path_expl: also the rows of
-        _write_feature_rows for the same pairs in the same order, one bprx_feat_explain call per block."""
+        ranking.write_feature_rows for the same pairs in the same order, one bprx_feat_explain call per block."""
         lists = (self.data.training_list, self.data.validation_list, self.data.test_list)
-        U = self.data.num_users
         with open(path, 'w') as out, (open(path_expl, 'w') if path_expl else contextlib.nullcontext()) as ex:
-            for u0 in range(0, U, self.user_block):
-                u1 = min(U, u0 + self.user_block)
+            for u0, u1 in blocks(self.data.num_users, self.user_block):
                 users, items = [], []
                 for u in range(u0, u1):
                     pos_items_u = [i for l in lists for i in (l[u] if u < len(l) else [])]
@@ -330,7 +296,7 @@ class Evaluator:
                 for r, (u, i) in enumerate(zip(users, items)):
                     out.write(str(u) + '\t' + str(i) + '\t' + str(g[r, 0]) + '\t' + str(g[r, 1]) + '\n')
                 if ex is not None:
-                    self._write_feature_rows(ex, users, items, top)
+                    write_feature_rows(ex, users, items, self.model.explain(users, items, top))
 
     def store_recommendation_attention(self, path=""):
         """Evaluator.py:241-259 (AttentiveFashion): the top-k rows 'u\\titem\\tscore\\talpha_colour\\talpha_edges\\talpha_class'.
@@ -345,10 +311,7 @@ class Evaluator:
         just written, in their order."""
         eng = self.model.engine
         self._metrics_device_csr()
-        U, I = self.model.data.num_users, self.model.data.num_items
-        blk = rows_per_block(self.user_block, I)
-        for u0 in range(0, U, blk):
-            u1 = min(U, u0 + blk)
+        for u0, u1 in self._user_blocks(width=self.model.data.num_items):
             sc, al = eng.af_score_block(u0, u1)
             ids, vals, att = rank_rows(self._topk(u0, u1), sc, self.k, side=al)
             self._write_block(out, range(u0, u1), ids, vals, att, block_hook)

@@ -19,8 +19,8 @@ import torch
 from . import configs
 from .engine import Engine, as_index
 from .evaluator import Evaluator
-from .ranking import (because_paths, because_rows, diversify_rows, div_paths, rank_rows, rows_per_block, write_because, write_diverse,
-                      write_ranked)
+from .ranking import (because_paths, because_rows, blocks, diverse_zeros, diversify_rows, div_paths, rank_rows, ranked_zeros,
+                      run_file, wanted_blocks, write_because, write_diverse, write_ranked)
 from .synth import glorot_uniform
 
 
@@ -139,11 +139,15 @@ class BPRMF(RecommenderModel):
         elems = kw["num_users"] * (kw["embed_k"] + kw.get("embed_d", 0)) + kw["num_items"] * (kw["embed_k"] + 1)
         return "lazy" if chain_us < elems * 24.0 / 4e6 else "sweep"
 
+    def _new_engine(self, min_batch=4096):
+        """self.engine for the tables _init_tables has just made (the kwargs and the Adam form are read off them), not yet bound."""
+        self.engine = Engine(optimizer=self.optimizer_name, lr=self.learning_rate, reg=self.reg,
+                             max_batch=max(self.batch_size, min_batch), adam_form=self._adam_form(), **self._engine_kwargs())
+        return self.engine
+
     def _build(self, init):
         t, _ = self._init_tables(init)
-        self.engine = Engine(optimizer=self.optimizer_name, lr=self.learning_rate, reg=self.reg,
-                             max_batch=max(self.batch_size, 4096), adam_form=self._adam_form(), **self._engine_kwargs())
-        self.engine.bind(**t)
+        self._new_engine().bind(**t)
         self._alias()
 
     def _alias(self):
@@ -152,9 +156,13 @@ class BPRMF(RecommenderModel):
         raw alias of the tensor would show rows that have not been replayed yet."""
 
     # ---- BPRMF.py:55-76 ------------------------------------------------------------------------------------------
+    def _pairs(self, inputs):
+        """(u, i) of call()'s inputs = (user, item, ...): int64 device tensors, as the tables are indexed."""
+        dev = self.engine.device
+        return as_index(inputs[0], dev).long(), as_index(inputs[1], dev).long()
+
     def call(self, inputs, training=None, mask=None):
-        user, item = inputs
-        u, i = as_index(user, self.engine.device).long(), as_index(item, self.engine.device).long()
+        u, i = self._pairs(inputs)
         xui = self.engine.score_pairs(u, i)
         return xui, self.Bi[i], self.Gu[u], self.Gi[i]
 
@@ -261,11 +269,7 @@ class BPRMF(RecommenderModel):
             # loss_buf is still alive, and steps asked for their loss afterwards (train_step) get it at once again
             self.engine.set_loss_lag(False)
         print('Training end...')
-        self._store_recs(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
-        self._store_new_user_recs(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
-        self._store_similar(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
-        self._store_diverse(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
-        self._store_because(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
+        self._store_run_files(os.path.join(rdir, f'recs-{it - 1}-{self.directory_parameters}.tsv'))
         with open(os.path.join(rdir, f'results-metrics-{self.directory_parameters}') + '.pkl', 'wb') as f:
             pickle.dump(results, f)                                             # utils/write.py:14-22
         print("Store Best Model at Epoch {0}".format(best_epoch))
@@ -274,17 +278,23 @@ class BPRMF(RecommenderModel):
         if best_state is not None:
             torch.save(best_state, os.path.join(wdir, f'best-weights-{best_epoch}-{self.directory_parameters}.pt'))
             self.load_state_dict(best_state)
-        self._store_recs(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
-        self._store_new_user_recs(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
-        self._store_similar(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
-        self._store_diverse(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
-        self._store_because(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
+        self._store_run_files(os.path.join(rdir, f'best-recs-{best_epoch}-{self.directory_parameters}.tsv'))
         self.load_state_dict(last_state)
         print('End Store Best Model!')
         print('Best Values for Each Metric:\nHR\tPrec\tRec\tAUC\tnDCG\n{}\t{}\t{}\t{}\t{}\n'.format(
             max_metrics['hr'], max_metrics['p'], max_metrics['r'], max_metrics['auc'], max_metrics['ndcg']))
         self.results = results
         return results
+
+    def _store_run_files(self, path):
+        """Every file of ranking.RUN_FILES the run's flags ask for, next to (and with) the recs-* / best-recs-* file at `path`, from
+        the tables the model holds now.  ValueError for a path that is neither."""
+        run_file(path, "recs")
+        self._store_recs(path)
+        self._store_new_user_recs(path)
+        self._store_similar(path)
+        self._store_diverse(path)
+        self._store_because(path)
 
     def _store_recs(self, path):
         """What train() leaves at the recs-* / best-recs-* paths: the top-K lists (BPRMF.py:167-187)."""
@@ -321,31 +331,40 @@ class BPRMF(RecommenderModel):
         diversify: None, or theta (a float in [0, 1]), or a dict with any of theta / pool / space as recommend_diverse takes
         them: the lists are then picked by greedy MMR from each row's top-`pool` and (ids, vals, pen, ild) is returned, as by
         recommend_diverse (BPRMF, VBPR, GradFashion)."""
-        div = None
-        if diversify is not None:
-            opts = dict(diversify) if isinstance(diversify, dict) else {"theta": diversify}
-            kk, pool, theta, space = self._diverse_args(k, opts.get("pool"), opts.get("theta"), opts.get("space"))
+        div = self._fold_diverse_args(k, diversify)              # (checked before anything is fitted)
+        return self._rank_fold_rows(self._fold_rows(histories, **fold), histories, k, div)
+
+    def _fold_diverse_args(self, k, diversify):
+        """recommend_new_users' `diversify` as _diverse_args returns it, checked; None for None."""
+        if diversify is None:
+            return None
+        opts = dict(diversify) if isinstance(diversify, dict) else {"theta": diversify}
+        return self._diverse_args(k, opts.get("pool"), opts.get("theta"), opts.get("space"))
+
+    def _rank_fold_rows(self, rows, histories, k=None, div=None):
+        """What recommend_new_users returns for the fitted rows of _fold_rows(histories): the plain lists, or with div (from
+        _fold_diverse_args) the diversified ones.  The rows are only read: one fit serves both."""
         eng = self.engine
         n, I = len(histories), self.num_items
         k = self.evaluator.k if k is None else int(k)
-        rows = self._fold_rows(histories, **fold)
-        if diversify is not None:
+        if div is None:
+            out = ranked_zeros(n, min(k, I), self.new_users_side)
+        else:
+            kk, pool, theta, space = div
             rn = eng.sim_rnorm(space)
-            div = lambda pi, pv, kq: eng.diversify(space, rn, pi, pv, kq, theta)
-        blk = rows_per_block(self.evaluator.user_block, I)
-        parts = []
-        for b0 in range(0, n, blk):
-            b1 = min(n, b0 + blk)
+            mmr = lambda pi, pv, kq: eng.diversify(space, rn, pi, pv, kq, theta)
+            out = diverse_zeros(n, kk)
+        for b0, b1 in blocks(n, self.evaluator.user_block, I):
             sc, side = self._score_fold_rows(rows, b0, b1)
             topk = lambda s, kq: eng.topk_lists(s, eng.csr(histories[b0:b1]), kq)
             if div is None:
-                parts.append(rank_rows(topk, sc, k, side))
+                res = rank_rows(topk, sc, k, side)
             else:
                 pi, pv, _ = rank_rows(topk, sc, pool)
-                parts.append(diversify_rows(div, pi, pv, kk, eng.device))
-        if div is not None:
-            return _stack_diverse(parts, kk)
-        return _stack_blocks(parts, min(k, I), self.new_users_side)
+                res = diversify_rows(mmr, pi, pv, kk, eng.device)
+            for o, r in zip(out, res):
+                o[b0:b1] = r
+        return out
 
     new_users_param = "new_users"                                # the params entry that names the new users' file
     new_users_side = 0                                           # columns of the side _score_fold_rows returns; 0: none
@@ -359,11 +378,10 @@ class BPRMF(RecommenderModel):
             return
         from .train_rec import read_new_users
         labels, lists = read_new_users(src)
-        d, f = os.path.split(path)
-        res = self.recommend_new_users(lists, steps=getattr(self.params, "fold_steps", 30),
-                                       negatives=getattr(self.params, "fold_negatives", 4),
-                                       seed=getattr(self.params, "init_seed", 0))
-        new_path = os.path.join(d, f.replace("recs-", "new-user-recs-", 1))
+        rows = self._fold_rows(lists, steps=getattr(self.params, "fold_steps", 30), negatives=getattr(self.params, "fold_negatives", 4),
+                               seed=getattr(self.params, "init_seed", 0))
+        res = self._rank_fold_rows(rows, lists)
+        new_path = run_file(path, "new-user-recs")
         with open(new_path, 'w') as out:
             write_ranked(out, labels, *res)
         if self.because_top > 0:                                 # because-new-user-recs-*: each label's own history, deduplicated
@@ -373,12 +391,9 @@ class BPRMF(RecommenderModel):
             with open(because_paths(new_path), 'w') as out:
                 write_because(out, labels, ids, vals, hist.reshape(ids.shape + (-1,)), cos.reshape(ids.shape + (-1,)))
         if self.diversify_theta > 0:                             # div-new-user-recs-* / div-new-user-ild-*: the same fitted rows
-            res = self.recommend_new_users(lists, diversify={}, steps=getattr(self.params, "fold_steps", 30),
-                                           negatives=getattr(self.params, "fold_negatives", 4),
-                                           seed=getattr(self.params, "init_seed", 0))
             p_recs, p_ild = div_paths(new_path)
             with open(p_recs, 'w') as out, open(p_ild, 'w') as out_ild:
-                write_diverse(out, out_ild, labels, *res)
+                write_diverse(out, out_ild, labels, *self._rank_fold_rows(rows, lists, div=self._fold_diverse_args(None, {})))
 
     # ---- similar items: the cosine of two items in the model's item space (include/bprx.h, bprx_sim_*) -------------------------
     sim_space = "latent"                                         # the space similar_items walks by default
@@ -397,23 +412,19 @@ class BPRMF(RecommenderModel):
         if want.size and (want.min() < 0 or want.max() >= I):
             raise ValueError("similar_items: item ids lie in [0, %d)" % I)
         kk = min(k, I - 1)
-        blk = rows_per_block(self.evaluator.user_block, I)
         rn = eng.sim_rnorm(space)
-        ids, vals = np.zeros((want.size, kk), np.int64), np.zeros((want.size, kk), np.float32)
-        for b0 in sorted({int(q) // blk * blk for q in want}):
-            b1 = min(I, b0 + blk)
+        ids, vals = ranked_zeros(want.size, kk)
+        for b0, b1, rows, local in wanted_blocks(want, I, self.evaluator.user_block, I):
             own = eng.csr([[q] for q in range(b0, b1)])
             bi, bv, _ = rank_rows(lambda s, kq: eng.topk_lists(s, own, kq), eng.sim_block(space, b0, b1, rn), k)
-            rows = np.nonzero((want >= b0) & (want < b1))[0]
-            ids[rows], vals[rows] = bi[want[rows] - b0, :kk], bv[want[rows] - b0, :kk]      # (k >= I: the masked self is last)
+            ids[rows], vals[rows] = bi[local, :kk], bv[local, :kk]                          # (k >= I: the masked self is last)
         return ids, vals
 
     def _store_similar(self, path):
         """params.similar_items = K > 0: sim-* next to the recs-* file at `path`, rows 'i\tj\tcosine', item by item, best first."""
         if self.similar_k <= 0:
             return
-        d, f = os.path.split(path)
-        self.evaluator.store_similar_items(os.path.join(d, f.replace("recs-", "sim-", 1)), self.similar_space)
+        self.evaluator.store_similar_items(run_file(path, "sim"), self.similar_space)
 
     # ---- diversified lists: greedy MMR over each list's top-N pool in the model's item space (include/bprx.h, bprx_diversify) --
     diverse = True                                               # False: the model has no item space (ACF, AttentiveFashion)
@@ -453,15 +464,12 @@ class BPRMF(RecommenderModel):
         ev._metrics_device_csr()
         rn = eng.sim_rnorm(space)
         div = lambda pi, pv, kq: eng.diversify(space, rn, pi, pv, kq, theta)
-        blk = ev.user_block
-        out = _stack_diverse([], kk, want.size)
-        for b0 in sorted({int(q) // blk * blk for q in want}):
-            b1 = min(U, b0 + blk)
+        out = diverse_zeros(want.size, kk)
+        for b0, b1, rows, local in wanted_blocks(want, U, ev.user_block):
             pi, pv, _ = rank_rows(ev._topk(b0, b1), eng.score_block(b0, b1), N)
             res = diversify_rows(div, pi, pv, kk, eng.device)
-            rows = np.nonzero((want >= b0) & (want < b1))[0]
             for o, r in zip(out, res):
-                o[rows] = r[want[rows] - b0]
+                o[rows] = r[local]
         return out
 
     def _store_diverse(self, path):
@@ -524,19 +532,6 @@ class _Padded:
         return self.lists[u] if u < len(self.lists) else []
 
 
-def _stack_diverse(parts, kk, n=0):
-    """The per-block (ids, vals, pen, ild) of ranking.diversify_rows as whole arrays (no parts: n zero rows)."""
-    parts = [(np.zeros((n, kk), np.int64), np.zeros((n, kk), np.float32), np.zeros((n, kk), np.float32), np.zeros(n, np.float32))] + parts
-    return tuple(np.concatenate(p) for p in zip(*parts))
-
-
-def _stack_blocks(parts, kk, c=0):
-    """The per-block (ids, vals, side) of ranking.rank_rows as whole arrays: (ids int64 [n, kk], vals fp32 [n, kk]) and, for
-    blocks with a side of c > 0 columns, side fp32 [n, kk, c]."""
-    parts = [(np.zeros((0, kk), np.int64), np.zeros((0, kk), np.float32), np.zeros((0, kk, c), np.float32))] + parts
-    return tuple(np.concatenate(p) for p in list(zip(*parts))[:3 if c else 2])
-
-
 def _table_property(name):
     return property(lambda self: self.engine.t[name], doc="bound tensor %s (current: lazy adam_tf23 rows are replayed first)" % name)
 
@@ -589,8 +584,7 @@ class VBPR(BPRMF):
                     feat_dtype=getattr(self.params, "dtype", "fp32"))
 
     def call(self, inputs, training=None, mask=None):                           # VBPR.py:59-86
-        user, item = inputs
-        u, i = as_index(user, self.engine.device).long(), as_index(item, self.engine.device).long()
+        u, i = self._pairs(inputs)
         xui = self.engine.score_pairs(u, i)
         return xui, self.Gu[u], self.Gi[i], self.F[i], self.Tu[u], self.Bi[i]
 
@@ -614,11 +608,10 @@ class VBPR(BPRMF):
     def _store_recs(self, path):
         """recs-* / best-recs-* as every model writes them; with params.feat_explain = L > 0 also expl-* / best-expl-* next to them;
         with params.new_items also new-recs-* (and new-expl-*) for the items of those files."""
-        d, f = os.path.split(path)
         if self.feat_explain <= 0:
             super()._store_recs(path)
         else:
-            self.evaluator.store_recommendation_features(path, os.path.join(d, f.replace("recs-", "expl-", 1)), self.feat_explain)
+            self.evaluator.store_recommendation_features(path, run_file(path, "expl"), self.feat_explain)
         self._store_new_recs(path)
 
     # ---- items the model was not trained on: x_uj = Tu_u.(f_j E) + f_j.Bp, no Gi_j / Bi_j term (include/bprx.h) ---------------
@@ -671,9 +664,9 @@ class VBPR(BPRMF):
         u1 = self.num_users if u1 is None else u1
         P = eng.project_rows(F)
         kk = min(k, n)
-        blk = rows_per_block(self.evaluator.user_block, n)
-        parts = [rank_rows(eng.topk_rows, eng.score_new_block(b0, min(u1, b0 + blk), P), k) for b0 in range(u0, u1, blk)]
-        idx_all, val_all = _stack_blocks(parts, kk)
+        idx_all, val_all = ranked_zeros(max(u1 - u0, 0), kk)
+        for b0, b1 in blocks(u1 - u0, self.evaluator.user_block, n):
+            idx_all[b0:b1], val_all[b0:b1], _ = rank_rows(eng.topk_rows, eng.score_new_block(u0 + b0, u0 + b1, P), k)
         if explain <= 0:
             return idx_all, val_all
         users = np.repeat(np.arange(u0, u1), kk)
@@ -693,9 +686,10 @@ class VBPR(BPRMF):
         P = eng.project_rows(self._as_new_table(features))
         n = int(P.shape[0])
         rn, rq = eng.sim_rnorm("visual"), eng.sim_rnorm("visual", P)
-        blk = rows_per_block(self.evaluator.user_block, I)
-        parts = [rank_rows(eng.topk_rows, eng.sim_block("visual", b0, min(n, b0 + blk), rn, P, rq), k) for b0 in range(0, n, blk)]
-        return _stack_blocks(parts, min(k, I))
+        ids, vals = ranked_zeros(n, min(k, I))
+        for b0, b1 in blocks(n, self.evaluator.user_block, I):
+            ids[b0:b1], vals[b0:b1], _ = rank_rows(eng.topk_rows, eng.sim_block("visual", b0, b1, rn, P, rq), k)
+        return ids, vals
 
     def because_new(self, features, users, rows, top=5):
         """BPRMF.because for items outside the catalogue: for every pair (users[p], rows[p] of `features`: raw rows, or a table
@@ -719,8 +713,7 @@ class VBPR(BPRMF):
         feats = self._load_new_items() if self.because_top > 0 else None
         if feats is None:
             return
-        d, f = os.path.split(path)
-        self.evaluator.store_because_new(because_paths(os.path.join(d, f.replace("recs-", "new-recs-", 1))), feats, self.because_top)
+        self.evaluator.store_because_new(run_file(path, "because-new-recs"), feats, self.because_top)
 
     def _store_similar(self, path):
         """sim-* as every model writes it; with params.new_items also new-sim-*, rows 'j_new\ti\tcosine' (always the visual space)."""
@@ -728,8 +721,7 @@ class VBPR(BPRMF):
         feats = self._load_new_items() if self.similar_k > 0 else None
         if feats is None:
             return
-        d, f = os.path.split(path)
-        self.evaluator.store_similar_new(os.path.join(d, f.replace("recs-", "new-sim-", 1)), feats)
+        self.evaluator.store_similar_new(run_file(path, "new-sim"), feats)
 
     def _load_new_items(self):
         paths = list(getattr(self.params, "new_items", None) or [])
@@ -740,10 +732,8 @@ class VBPR(BPRMF):
         feats = self._load_new_items()
         if feats is None:
             return
-        d, f = os.path.split(path)
-        new = f.replace("recs-", "new-recs-", 1)
-        expl = os.path.join(d, new.replace("recs-", "expl-", 1)) if self.feat_explain > 0 else None
-        self.evaluator.store_recommendation_new(os.path.join(d, new), feats, expl, self.feat_explain)
+        expl = run_file(path, "new-expl") if self.feat_explain > 0 else None
+        self.evaluator.store_recommendation_new(run_file(path, "new-recs"), feats, expl, self.feat_explain)
 
 
 class GradFashion(VBPR):
@@ -811,9 +801,7 @@ class GradFashion(VBPR):
 
     def _build(self, init):
         t, _ = self._init_tables(init)
-        self.engine = Engine(optimizer=self.optimizer_name, lr=self.learning_rate, reg=self.reg,
-                             max_batch=max(self.batch_size, 4096), adam_form=self._adam_form(), **self._engine_kwargs())
-        self.engine.bind_factored(t["Gu"], t["Gi"], t["Bi"], t["Tu"], t["F"], t["Ec"], t["Ee"], t["E"], t["Bp"],
+        self._new_engine().bind_factored(t["Gu"], t["Gi"], t["Bi"], t["Tu"], t["F"], t["Ec"], t["Ee"], t["E"], t["Bp"],
                                   self.dim_color_features, self.dim_edge_features, neg_bias_reg=1.0)
 
     # ---- the reference's attribute surface ---------------------------------------------------------------------------
@@ -839,8 +827,7 @@ class GradFashion(VBPR):
     def call(self, inputs, training=True, mask=None):
         """xui from the engine (bprx_score_pairs); the other outputs are the reference's gathered rows (theta_i = F_i E_eff:
         the projected rows, recomputed here for inspection only -- the training step never calls this)."""
-        user, item = inputs
-        u, i = as_index(user, self.engine.device).long(), as_index(item, self.engine.device).long()
+        u, i = self._pairs(inputs)
         xui = self.engine.score_pairs(u, i)
         t = self.engine.t
         Dc, De = self.dim_color_features, self.dim_edge_features
@@ -868,8 +855,7 @@ class GradFashion(VBPR):
         """GradFashion.py:236-240, 252-258: the reference writes the top-K list to the recs path and then OVERWRITES the same
         path with the explanation rows (get_explanations.py:19-21 reads them from there); only the final content is written.
         With params.feat_explain = L > 0 also expl-* / best-expl-* next to it: the L strongest feature columns of the same pairs."""
-        d, f = os.path.split(path)
-        expl = os.path.join(d, f.replace("recs-", "expl-", 1)) if self.feat_explain > 0 else None
+        expl = run_file(path, "expl") if self.feat_explain > 0 else None
         self.evaluator.store_recommendation_grads(path=path, path_expl=expl, top=self.feat_explain)
         self._store_new_recs(path)
 
@@ -1028,10 +1014,8 @@ class ACF(BPRMF):
 
     def _build(self, init):
         t, _ = self._init_tables(init)
-        self.engine = Engine(optimizer=self.optimizer_name, lr=self.learning_rate, reg=self.reg,
-                             max_batch=max(self.batch_size, 4096), adam_form=self._adam_form(), **self._engine_kwargs())
         kw = {"gradient": "full"} if self.acf_gradient == "full" else {}
-        self.engine.bind_acf(t["Gu"], t["Gi"], t["Bi"], self.acf_features, t["Pi"], {n: t[n] for n in _ACF_W},
+        self._new_engine().bind_acf(t["Gu"], t["Gi"], t["Bi"], self.acf_features, t["Pi"], {n: t[n] for n in _ACF_W},
                              self.data.training_list, self.eval_lists(), **kw)
 
     # ---- snapshots: the gradient mode is part of a full-mode snapshot; one without the key is detached --------------------
@@ -1066,8 +1050,7 @@ class ACF(BPRMF):
 
     # ---- ACF.py:183-212 ----------------------------------------------------------------------------------------------------
     def call(self, inputs, training=None, mask=None):
-        user, item = inputs
-        u, i = as_index(user, self.engine.device).long(), as_index(item, self.engine.device).long()
+        u, i = self._pairs(inputs)
         xui = self.engine.score_pairs(u, i)
         return xui, self.Gu[u], self.Gi[i], self.Pi[i]
 
@@ -1117,10 +1100,7 @@ class ACF(BPRMF):
         """recs-* / best-recs-* as every model writes them; with params.acf_explain = L > 0 also expl-* / best-expl-* next to them."""
         if self.acf_explain <= 0:
             return super()._store_recs(path)
-        d, f = os.path.split(path)
-        if not (f.startswith("recs-") or f.startswith("best-recs-")):
-            raise ValueError("ACF: %s is neither a recs-* nor a best-recs-* path" % path)
-        self.evaluator.store_recommendation_acf(path, os.path.join(d, f.replace("recs-", "expl-", 1)), self.acf_explain)
+        self.evaluator.store_recommendation_acf(path, run_file(path, "expl"), self.acf_explain)
 
 
 AF_EXPLAIN_GRIDS = (0, 1, 2, 4, 7, 8, 14, 16)      # --af_explain: the divisors of 112 whose expl-* rows stay readable
@@ -1212,9 +1192,7 @@ class AttentiveFashion(BPRMF):
 
     def _build(self, init):
         t, _ = self._init_tables(init)
-        self.engine = Engine(optimizer=self.optimizer_name, lr=self.learning_rate, reg=self.reg,
-                             max_batch=max(self.batch_size, 1024), adam_form=self._adam_form(), **self._engine_kwargs())
-        self.engine.bind_attentive(t["Gu"], t["Gi"], t["Bi"], self.edges, self.color, self.classes, {n: t[n] for n in _AF_W},
+        self._new_engine(min_batch=1024).bind_attentive(t["Gu"], t["Gi"], t["Bi"], self.edges, self.color, self.classes, {n: t[n] for n in _AF_W},
                                    dropout=self.dropout, seed=getattr(self.params, "init_seed", 0))
 
     # ---- the reference's attribute surface ---------------------------------------------------------------------------
@@ -1228,8 +1206,7 @@ class AttentiveFashion(BPRMF):
 
     # ---- AttentiveFashion.py:168-209 (dropout off, as a call outside train_step) -------------------------------------------------
     def call(self, inputs, training=None, mask=None):
-        user, item = inputs[0], inputs[1]
-        u, i = as_index(user, self.engine.device).long(), as_index(item, self.engine.device).long()
+        u, i = self._pairs(inputs)
         xui, alpha = self.engine.af_attention_pairs(u, i)
         c = self.engine.af_encode(i)
         return xui, self.Gu[u], self.Gi[i], c[0], c[1], c[2], alpha
@@ -1242,8 +1219,8 @@ class AttentiveFashion(BPRMF):
         (the reference re-encodes every item for every user, and fails when num_items % batch_eval == 0); `step` / `next_image` are
         accepted for the reference's signature and ignored."""
         xs, als = [], []
-        for u0 in range(0, self.num_users, user_block):
-            x, al = self.engine.af_score_block(u0, min(self.num_users, u0 + user_block))
+        for u0, u1 in blocks(self.num_users, user_block):
+            x, al = self.engine.af_score_block(u0, u1)
             xs.append(x.cpu().numpy()); als.append(al.cpu().numpy())
         return np.concatenate(xs), np.concatenate(als)
 
@@ -1296,10 +1273,7 @@ class AttentiveFashion(BPRMF):
         """recs-* / best-recs-* with the attentions; with params.af_explain = G > 0 also expl-* / best-expl-* next to them."""
         if self.af_explain <= 0:
             return self.evaluator.store_recommendation_attention(path=path)
-        d, f = os.path.split(path)
-        if not (f.startswith("recs-") or f.startswith("best-recs-")):
-            raise ValueError("AttentiveFashion: %s is neither a recs-* nor a best-recs-* path" % path)
-        self.evaluator.store_recommendation_attention_explain(path, os.path.join(d, f.replace("recs-", "expl-", 1)), self.af_explain)
+        self.evaluator.store_recommendation_attention_explain(path, run_file(path, "expl"), self.af_explain)
 
 
 from ._ffi import ACF_WEIGHTS as _ACF_W     # noqa: E402

@@ -1,5 +1,6 @@
 """The one place where score rows become top-K lists and lists become rows of text: every recs-* / new-recs-* /
-new-user-recs-* / div-* / because-* file, single GPU or sharded, catalogue items or new ones, is ranked and written here.
+new-user-recs-* / div-* / because-* file, single GPU or sharded, catalogue items or new ones, is ranked and written here, block
+by block (blocks, wanted_blocks), and gets its name here (RUN_FILES, run_file).
 
 The contract is the reference's (Evaluator.py:225-239): mask the row, then take numpy_topk of it; numpy's unstable argsort
 decides the order of EQUAL scores.  The top-K kernel returns the list wherever it does not depend on that order and flags
@@ -19,6 +20,24 @@ def numpy_topk(row, k):
 def rows_per_block(user_block, width):
     """Rows of `width` scores per block: user_block, cut so that one block's scores stay below 2^27 elements."""
     return max(1, min(user_block, (1 << 27) // max(1, width)))
+
+
+def blocks(n, block, width=None):
+    """(b0, b1) of the rows [0, n), `block` rows at a time, the last block the shorter one; with `width` (scores per row) the block
+    is cut by rows_per_block."""
+    step = block if width is None else rows_per_block(block, width)
+    for b0 in range(0, n, step):
+        yield b0, min(n, b0 + step)
+
+
+def wanted_blocks(want, n, block, width=None):
+    """The blocks of blocks(n, block, width) that hold an id of `want` (int64 array, any order, repeats allowed), ascending, each
+    as (b0, b1, rows, local): want[rows] are the ids in [b0, b1), rows ascending (the caller's order), local = want[rows] - b0."""
+    step = block if width is None else rows_per_block(block, width)
+    for b0 in sorted({int(q) // step * step for q in want}):
+        b1 = min(n, b0 + step)
+        rows = np.nonzero((want >= b0) & (want < b1))[0]
+        yield b0, b1, rows, want[rows] - b0
 
 
 def lists_to_csr(lists, device, dedup=False):
@@ -60,6 +79,17 @@ def rank_rows(topk, scores, k, side=None):
     return ids, vals, side_rows
 
 
+def ranked_zeros(n, kk, c=0):
+    """(ids int64 [n, kk], vals fp32 [n, kk]) and, with c > 0 side columns, side fp32 [n, kk, c] of zeros: what rank_rows' blocks are
+    put into."""
+    return (np.zeros((n, kk), np.int64), np.zeros((n, kk), np.float32)) + ((np.zeros((n, kk, c), np.float32),) if c else ())
+
+
+def diverse_zeros(n, kk):
+    """(ids int64 [n, kk], vals fp32 [n, kk], pen fp32 [n, kk], ild fp32 [n]) of zeros: what diversify_rows' blocks are put into."""
+    return np.zeros((n, kk), np.int64), np.zeros((n, kk), np.float32), np.zeros((n, kk), np.float32), np.zeros(n, np.float32)
+
+
 def diversify_rows(diversify, ids, vals, k, device):
     """The diversified lists of a block of pools: `ids` int64 [n, N] / `vals` fp32 [n, N] are what rank_rows returned for a pool
     of N (flagged rows already redone by numpy there; a masked entry keeps its -inf and is no candidate).  They are uploaded
@@ -69,7 +99,7 @@ def diversify_rows(diversify, ids, vals, k, device):
     n, N = ids.shape
     kk = min(int(k), N)
     if n == 0 or kk == 0:
-        return np.zeros((n, kk), np.int64), np.zeros((n, kk), np.float32), np.zeros((n, kk), np.float32), np.zeros(n, np.float32)
+        return diverse_zeros(n, kk)
     pool_idx = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32), device=device)
     pool_val = torch.as_tensor(np.ascontiguousarray(vals, dtype=np.float32), device=device)
     idx, val, pen, ild = diversify(pool_idx, pool_val, kk)
@@ -133,14 +163,62 @@ def write_ranked(out, labels, ids, vals, side=None):
     return users, items
 
 
+def write_feature_rows(out, users, items, e):
+    """The expl-* rows of VBPR and GradFashion for the pairs (users, items): 'u\\ti\\tscore\\tbase\\trank\\tcolumn\\tcontribution',
+    rank 0 (the largest F_ic w_uc) first, one row per rank the pair has.  e: the numpy dict of Engine.feat_explain, or of
+    feat_explain_new, which has no base: new items get no base column.  Fields are formatted as write_ranked formats them."""
+    for r, (u, i) in enumerate(zip(users, items)):
+        head = str(u) + '\t' + str(i) + '\t' + str(e["score"][r]) + '\t' + (str(e["base"][r]) + '\t' if "base" in e else '')
+        for s in range(e["col"].shape[1]):
+            if e["col"][r, s] < 0:
+                break
+            out.write(head + str(s) + '\t' + str(e["col"][r, s]) + '\t' + str(e["contrib"][r, s]) + '\n')
+
+
+# Every file a run can write next to its recs-<epoch>-<params>.tsv: the file is named [best-]<kind>-<epoch>-<params>.tsv.  The value
+# is the list file whose pairs (or users) the file is about; None: the file stands for itself.
+RUN_FILES = {"recs": None, "expl": "recs",
+             "new-recs": None, "new-expl": "new-recs",
+             "new-user-recs": None,
+             "sim": None, "new-sim": None,
+             "div-recs": "recs", "div-ild": "recs", "div-new-user-recs": "new-user-recs", "div-new-user-ild": "new-user-recs",
+             "because": "recs", "because-new-recs": "new-recs", "because-new-user-recs": "new-user-recs"}
+
+
+def _split_run_file(path):
+    """(directory and 'best-' if any, kind, '-<epoch>-<params>.tsv') of a run file's path; the kind is None for any other name."""
+    d, sep, f = path.rpartition('/')
+    best = "best-" if f.startswith("best-") else ""
+    for kind in sorted(RUN_FILES, key=len, reverse=True):     # ('because-new-recs' before 'because')
+        if f.startswith(best + kind + "-"):
+            return d + sep + best, kind, f[len(best) + len(kind):]
+    return d + sep + best, None, f
+
+
+def run_file(path, kind):
+    """The file of `kind` (a key of RUN_FILES) next to the recs-* / best-recs-* file at `path`; 'best-' stays in front.  ValueError
+    for a path whose file name starts with neither."""
+    head, base, tail = _split_run_file(path)
+    if base != "recs":
+        raise ValueError("%r is neither a recs-* nor a best-recs-* path" % path)
+    if kind not in RUN_FILES:
+        raise ValueError("run_file: %r is none of %s" % (kind, ", ".join(RUN_FILES)))
+    return head + kind + tail
+
+
+def _about(path, family, what):
+    """The files of RUN_FILES that are about the list file at `path` and whose kind starts with `family`, in the table's order."""
+    head, base, tail = _split_run_file(path)
+    out = tuple(head + kind + tail for kind, of in RUN_FILES.items() if base is not None and of == base and kind.startswith(family))
+    if not out:
+        raise ValueError("%s: %r is no recs-* path" % (what, path))
+    return out
+
+
 def div_paths(path):
     """(div-recs-*, div-ild-*) next to the recs-* / best-recs-* / new-user-recs-* / best-new-user-recs-* file at `path`: 'div-'
     goes in front of the file's own 'recs-' / 'new-user-recs-' part, the ild file has 'ild-' where that part is."""
-    d, sep, f = path.rpartition('/')
-    for part in ("new-user-recs-", "recs-"):
-        if part in f:
-            return d + sep + f.replace(part, "div-" + part, 1), d + sep + f.replace(part, "div-" + part.replace("recs-", "ild-"), 1)
-    raise ValueError("div_paths: %r is no recs-* path" % path)
+    return _about(path, "div-", "div_paths")
 
 
 def write_diverse(out, out_ild, labels, ids, vals, pen, ild):
@@ -158,13 +236,7 @@ def write_diverse(out, out_ild, labels, ids, vals, pen, ild):
 def because_paths(path):
     """The because-* file next to the list file at `path`: 'because-' takes the place of the 'recs-' of recs-* / best-recs-* and
     goes in front of the 'new-user-recs-' / 'new-recs-' of the other list files (best-new-recs-2-x -> best-because-new-recs-2-x)."""
-    d, sep, f = path.rpartition('/')
-    for part in ("new-user-recs-", "new-recs-"):
-        if part in f:
-            return d + sep + f.replace(part, "because-" + part, 1)
-    if "recs-" in f and "div-" not in f:
-        return d + sep + f.replace("recs-", "because-", 1)
-    raise ValueError("because_paths: %r is no recs-* path" % path)
+    return _about(path, "because", "because_paths")[0]
 
 
 def write_because(out, labels, ids, vals, hist, cos):
