@@ -20,8 +20,10 @@ class GradFashionRef:
     """tables: Gu [U,k], Gi [I,k], Bi [I], Tu [U,d], Fc [I,Dc], Fe [I,De], Ec [Dc,ec], Ee [De,ee], E [ec+ee,d], Bp [ec+ee]
     (numpy or torch; Bp may be [ec+ee, 1] as in the reference)."""
 
-    def __init__(self, tables, reg):
-        f = lambda x: torch.as_tensor(np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x), dtype=torch.float64).clone()
+    def __init__(self, tables, reg, dtype=torch.float64):
+        """`dtype=torch.float32` runs the same restatement in float32: its deviation from float64 is one sample of float32 rounding."""
+        self.dtype = dtype
+        f = lambda x: torch.as_tensor(np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x), dtype=torch.float64).to(dtype).clone()
         self.p = {n: f(tables[n]) for n in PARAMS}
         self.p["Bp"] = self.p["Bp"].reshape(-1, 1)
         self.Fc, self.Fe = f(tables["Fc"]), f(tables["Fe"])
@@ -32,7 +34,7 @@ class GradFashionRef:
 
     def load(self, t, step):
         """Continue from an engine's state (`Engine.t` names: Ec, Ee, E, Bp and m_ / v_ slots) at Adam step `step`."""
-        f = lambda x: x.detach().to("cpu", torch.float64).clone()
+        f = lambda x: x.detach().to("cpu", self.dtype).clone()
         for n in PARAMS:
             self.p[n] = f(t[n]).reshape(self.p[n].shape)
             if ("m_" + n) in t:
