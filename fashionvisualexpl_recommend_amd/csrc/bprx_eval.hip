@@ -113,6 +113,43 @@ __global__ __launch_bounds__(256) void k_score_new_gemm(const float *__restrict_
   }
 }
 
+// bprx_audience_block: k_score_gemm (g.Gi != nullptr) / k_score_new_gemm (g.Gi == nullptr: g.P holds the caller's rows) with the
+// operand roles swapped: out[q - q0][u] for the item rows q in [q0, q1) against every user.  A holds the item rows (Gi, then P),
+// B the user rows (Gu, then Tu); same tiles, same phase order, same C/D map, so an output row is an item, its bias Bi_q + P_q[d]
+// is constant along it and the 32 lanes of a half-wave write 32 consecutive users.  Products are exact fp32 and the sums k-ordered
+// from +0: for even k and d the element has the bits of the user-major kernels' out[u][q]; any k, d >= 1 (gemm_phase pads with
+// zeros).  An element depends on its item row and its user row only.
+__global__ __launch_bounds__(256) void k_audience_gemm(GemmArgs g, int q0, int q1, float *__restrict__ out) {
+  __shared__ float As[TM][GLD];
+  __shared__ float Bs[TN][GLD];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wr = w >> 1, wc = w & 1;
+  const int ub = blockIdx.x * TN, qb = q0 + blockIdx.y * TM;
+  const int arows = min(TM, q1 - qb), brows = min(TN, g.U - ub);
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+  if (g.Gi) gemm_phase(g.Gi, g.k, qb, arows, g.Gu, g.k, ub, brows, g.k, As, Bs, acc, wr, wc, lane);
+  if (g.d) gemm_phase(g.P, g.PS, qb, arows, g.Tu, g.d, ub, brows, g.d, As, Bs, acc, wr, wc, lane);
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int qr = qb + wr * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+      if (qr >= q1) continue;
+      const float pb = g.d ? g.P[(size_t)qr * g.PS + g.d] : 0.f;
+      const float bias = g.Gi ? g.Bi[qr] + pb : pb;            // as k_score_gemm / k_score_new_gemm form it
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int uc = ub + wc * 64 + b * 32 + (lane & 31);
+        if (uc < g.U) out[(size_t)(qr - q0) * g.U + uc] = acc[a][b][r] + bias;
+      }
+    }
+}
+
 // ---- similar items (include/bprx.h): cosine of item vectors z = [Gi | P[0:d]] (either part may be absent) ----
 // (SimPart, one part of z: bprx_internal.h)
 constexpr int RN_LANES = 16;   // lanes per row of k_sim_rnorm: 4 rows per wave, 16 per workgroup
@@ -511,6 +548,41 @@ extern "C" int bprx_topk_lists(bprx_handle *h, int64_t nrows, float *scores, con
   if (nrows < 0 || nrows >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "topk_lists: nrows = %lld out of range", (long long)nrows);
   return topk_launch(h, "topk_lists", "k_topk<lists>", nrows && (!scores || !list_ptr || !list_items || !idx || !val || !flag), 0,
                      KIND_ANY, nrows, scores, 0, h->cfg.num_items, list_ptr, list_items, K, idx, val, flag, stream);
+}
+
+// bprx_topk_rows with bprx_topk_lists' per-row mask lists: rows of the caller's width (an audience block: num_users wide)
+extern "C" int bprx_topk_rows_masked(bprx_handle *h, int64_t nrows, int32_t width, float *scores, const int64_t *list_ptr,
+                                     const int32_t *list_items, int32_t K, int32_t *idx, float *val, int32_t *flag, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (nrows < 0 || nrows >= ((int64_t)1 << 31))
+    BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows_masked: nrows = %lld out of range", (long long)nrows);
+  if (width < 1) BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows_masked: width = %d < 1", width);
+  return topk_launch(h, "topk_rows_masked", "k_topk<rows_masked>", nrows && (!scores || !list_ptr || !list_items || !idx || !val || !flag),
+                     0, KIND_ANY, nrows, scores, 0, width, list_ptr, list_items, K, idx, val, flag, stream);
+}
+
+// ---- audience: the item-major score block (include/bprx.h) ----
+extern "C" int bprx_audience_block(bprx_handle *h, const float *Pq, int64_t nq, int64_t q0, int64_t q1, float *out, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (!out) BPRX_FAIL(h, BPRX_E_INVALID, "audience_block: null pointer");
+  if (nq < 0 || nq >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "audience_block: nq = %lld out of range", (long long)nq);
+  if (!Pq && nq != h->cfg.num_items)
+    BPRX_FAIL(h, BPRX_E_INVALID, "audience_block: nq = %lld, the catalogue has %d items", (long long)nq, h->cfg.num_items);
+  if (q0 < 0 || q0 > q1 || q1 > nq || q1 - q0 > (int64_t)65535 * TM)
+    BPRX_FAIL(h, BPRX_E_INVALID, "audience_block: bad item range [%lld,%lld) of %lld", (long long)q0, (long long)q1, (long long)nq);
+  hipStream_t s = (hipStream_t)stream;
+  // the catalogue: what bprx_score_block needs; the caller's rows: what bprx_score_new_block needs (NEED_ET: the image Pq was
+  // made from stays the current one)
+  const int rc = Pq ? bprx_enter(h, "audience_block", NEED_BOUND | NEED_ROWS | NEED_ET, KIND_VBPR_NO_FP8, s)
+                    : bprx_enter(h, "audience_block", NEED_BOUND | NEED_ROWS | NEED_P_ALL, KIND_PLAIN, s);
+  if (rc || q0 == q1) return rc;
+  GemmArgs g;
+  g.Gu = h->t.Gu; g.Gi = Pq ? nullptr : h->t.Gi; g.Bi = h->t.Bi; g.Tu = h->t.Tu; g.P = Pq ? Pq : h->P;
+  g.U = h->cfg.num_users; g.I = (int)nq; g.k = h->cfg.embed_k; g.d = h->cfg.embed_d; g.PS = h->PS;
+  dim3 grid((unsigned)((g.U + TN - 1) / TN), (unsigned)((q1 - q0 + TM - 1) / TM));
+  hipLaunchKernelGGL(k_audience_gemm, grid, dim3(256), 0, s, g, (int)q0, (int)q1, out);
+  BPRX_LAUNCH_CHECK(h, "k_audience_gemm");
+  return BPRX_OK;
 }
 
 extern "C" int bprx_score_new_block(bprx_handle *h, int32_t u0, int32_t u1, const float *P, int64_t n, float *out, void *stream) {

@@ -658,6 +658,28 @@ class Engine:
                                                    _addr(rn_items), _addr(out), _stream()))
         return out
 
+    # ---- audiences (include/bprx.h: the score block item-major, one row per item against every user) -----------------------------
+    def audience_block(self, q0, q1, P=None, out=None):
+        """bprx_audience_block: fp32 [q1 - q0, U], the scores of the catalogue items q0 .. q1-1 (P = project_rows(F): of rows
+        q0 .. q1-1 of P, the visual score of items outside the catalogue) for every user: score_block / score_new_block
+        item-major, bit for bit where k and d are even."""
+        nq = self.I if P is None else int(P.shape[0])
+        if out is None:
+            out = torch.empty((max(q1 - q0, 0), self.U), dtype=torch.float32, device=self.device)
+        _ffi.check(self.h, self.lib.bprx_audience_block(self.h, _addr(P), nq, int(q0), int(q1), _addr(out), _stream()))
+        return out
+
+    def topk_rows_masked(self, scores, lists_csr, K):
+        """bprx_topk_rows_masked: topk_rows for the rows of a contiguous fp32 [nrows, width] device tensor, row r masking (IN
+        `scores`) the ids of list r of lists_csr = (int64 ptr [nrows + 1], int32 ids): (idx int32 [nrows, K], val, flag)."""
+        nrows, width = (int(x) for x in scores.shape)
+        K = int(K)
+        idx, val, flag = self._topk_out(nrows, K)
+        ptr, items = lists_csr
+        _ffi.check(self.h, self.lib.bprx_topk_rows_masked(self.h, nrows, width, _addr(scores), _addr(ptr), _addr(items), K, _addr(idx),
+                                                          _addr(val), _addr(flag), _stream()))
+        return idx, val, flag
+
     def diversify(self, space, rn, pool_idx, pool_val, k, theta):
         """bprx_diversify: greedy MMR over the pools (pool_idx int32, pool_val fp32: contiguous device tensors [n, N], best first,
         as the top-K entries return them) in `space`, rn = sim_rnorm(space): (idx int32 [n, k], val fp32 [n, k] the picks' pool

@@ -18,7 +18,8 @@ from time import time
 
 import numpy as np
 
-from .ranking import blocks, lists_to_csr, rank_rows, rank_rows_host, write_because, write_diverse, write_feature_rows, write_ranked
+from .ranking import (blocks, lists_to_csr, rank_rows, rank_rows_host, write_because, write_diverse, write_feature_rows, write_item_lists,
+                      write_ranked)
 
 
 def _eval_block(scores, u0, train, evl, K):
@@ -276,6 +277,23 @@ class Evaluator:
         ids, vals = self.model.similar_to_new(features)
         with open(path, 'w') as out:
             write_ranked(out, range(ids.shape[0]), ids, vals)
+
+    def store_audience(self, path="", items=None):
+        """BPRMF / VBPR / GradFashion: the audience of every item of `items` (None: the whole catalogue; model.audience: the
+        params' K users with the highest score, the item's owners excluded) as rows 'i\tu\tscore', item by item, best first,
+        formatted as store_recommendation formats; an item with fewer non-owners than K has that many rows."""
+        ids, vals = self.model.audience(items)
+        labels = range(ids.shape[0]) if items is None else [int(i) for i in np.asarray(items).reshape(-1)]
+        with open(path, 'w') as out:
+            write_item_lists(out, labels, ids, vals)
+
+    def store_audience_new(self, path="", features=None):
+        """VBPR / GradFashion: the audience of every row of `features` (raw rows of items outside the catalogue, as
+        model.prepare_new_items takes them; model.audience_new: the visual score, nothing masked) as rows 'j\tu\tscore', j = the
+        row of `features`, row by row, best first."""
+        ids, vals = self.model.audience_new(features)
+        with open(path, 'w') as out:
+            write_item_lists(out, range(ids.shape[0]), ids, vals)
 
     def store_recommendation_grads(self, path="", path_expl=None, top=5):
         """Evaluator.py:261-275 (GradFashion): for every user the items training_list[u] + validation_list[u] + test_list[u],

@@ -19,8 +19,8 @@ import torch
 from . import configs
 from .engine import Engine, as_index
 from .evaluator import Evaluator
-from .ranking import (because_paths, because_rows, blocks, diverse_zeros, diversify_rows, div_paths, rank_rows, ranked_zeros,
-                      run_file, wanted_blocks, write_because, write_diverse, write_ranked)
+from .ranking import (because_paths, because_rows, blocks, diverse_zeros, diversify_rows, div_paths, item_file, owners_of, rank_rows,
+                      ranked_zeros, run_file, wanted_blocks, write_because, write_diverse, write_ranked)
 from .synth import glorot_uniform
 
 
@@ -111,6 +111,7 @@ class BPRMF(RecommenderModel):
         self.diversify_theta = float(getattr(params, "diversify", 0.0) or 0.0)     # theta of the div-* files; 0: none
         self.diversify_pool = int(getattr(params, "diversify_pool", 100) or 100)   # candidates per list the MMR step picks from
         self.because_top = int(getattr(params, "because", 0) or 0)                 # owned items per pair in because-*; 0: none
+        self.audience_k = int(getattr(params, "audience", 0) or 0)                 # users per item in audience-*; 0: none
         self.directory_parameters = f'batch_{params.batch_size}-K_{params.embed_k}-lr_{params.lr}-reg_{params.reg}'
         self._build(init or {})
 
@@ -295,6 +296,7 @@ class BPRMF(RecommenderModel):
         self._store_similar(path)
         self._store_diverse(path)
         self._store_because(path)
+        self._store_audience(path)
 
     def _store_recs(self, path):
         """What train() leaves at the recs-* / best-recs-* paths: the top-K lists (BPRMF.py:167-187)."""
@@ -425,6 +427,46 @@ class BPRMF(RecommenderModel):
         if self.similar_k <= 0:
             return
         self.evaluator.store_similar_items(run_file(path, "sim"), self.similar_space)
+
+    # ---- audiences: the top-K users of an item, the score block item-major (include/bprx.h, bprx_audience_block) ----------------
+    def _owners(self):
+        """ranking.owners_of the training lists: per item the users store_recommendation masks it for (made once)."""
+        if getattr(self, "_owners_of", None) is None:
+            self._owners_of = owners_of(self.data.training_list[:self.num_users], self.num_items)
+        return self._owners_of
+
+    def audience(self, items=None, k=None):
+        """The k (default: params.audience, else top_k) users with the highest score for each item of `items` (None: the whole
+        catalogue, in id order), the item's owners (the users whose training list names it) excluded: numpy ids int64 [n, kk] and
+        vals fp32 [n, kk], kk = min(k, U), best first; an item with fewer than kk non-owners has -1 / -inf in the slots past them.
+        The scores are predict_all's, item-major (Engine.audience_block); the catalogue is walked in blocks of item rows, every
+        block listed by ranking.rank_rows with Engine.topk_rows_masked and the block's owner lists; an explicit id list ranks the
+        blocks that hold its ids and keeps those rows."""
+        eng, I, U = self.engine, self.num_items, self.num_users
+        k = (self.audience_k or self.evaluator.k) if k is None else int(k)
+        want = np.arange(I, dtype=np.int64) if items is None else np.asarray(items, dtype=np.int64).reshape(-1)
+        if want.size and (want.min() < 0 or want.max() >= I):
+            raise ValueError("audience: item ids lie in [0, %d)" % I)
+        ids, vals = ranked_zeros(want.size, min(k, U))
+        owners = self._owners() if want.size else None
+        for b0, b1, rows, local in wanted_blocks(want, I, self.evaluator.user_block, U):
+            own = eng.csr(owners[b0:b1])
+            bi, bv, _ = rank_rows(lambda s, kq: eng.topk_rows_masked(s, own, kq), eng.audience_block(b0, b1), k)
+            ids[rows], vals[rows] = bi[local], bv[local]
+        ids[vals == -np.inf] = -1                                # (a masked entry reached the list: the row came through numpy)
+        return ids, vals
+
+    def _store_audience(self, path):
+        """params.audience = K > 0: audience-* next to the recs-* file at `path`, rows 'i\tu\tscore', item by item (the ids of
+        params.audience_items, else the whole catalogue), best first."""
+        if self.audience_k <= 0:
+            return
+        src = getattr(self.params, "audience_items", None)
+        items = None
+        if src:
+            from .train_rec import read_audience_items
+            items = read_audience_items(src, self.num_items)
+        self.evaluator.store_audience(item_file(path, "audience"), items)
 
     # ---- diversified lists: greedy MMR over each list's top-N pool in the model's item space (include/bprx.h, bprx_diversify) --
     diverse = True                                               # False: the model has no item space (ACF, AttentiveFashion)
@@ -690,6 +732,28 @@ class VBPR(BPRMF):
         for b0, b1 in blocks(n, self.evaluator.user_block, I):
             ids[b0:b1], vals[b0:b1], _ = rank_rows(eng.topk_rows, eng.sim_block("visual", b0, b1, rn, P, rq), k)
         return ids, vals
+
+    def audience_new(self, features, k=None):
+        """BPRMF.audience for items outside the catalogue: the k (default: params.audience, else top_k) users with the highest
+        visual score for each row of `features` (raw rows, or a table from prepare_new_items): numpy ids int64 [n, kk] and vals
+        fp32 [n, kk], kk = min(k, U), best first.  Engine.project_rows, audience_block on those rows and ranking.rank_rows with
+        Engine.topk_rows: a new item has no owners, nothing is masked."""
+        eng, U = self.engine, self.num_users
+        k = (self.audience_k or self.evaluator.k) if k is None else int(k)
+        P = eng.project_rows(self._as_new_table(features))
+        n = int(P.shape[0])
+        ids, vals = ranked_zeros(n, min(k, U))
+        for b0, b1 in blocks(n, self.evaluator.user_block, U):
+            ids[b0:b1], vals[b0:b1], _ = rank_rows(eng.topk_rows, eng.audience_block(b0, b1, P), k)
+        return ids, vals
+
+    def _store_audience(self, path):
+        """audience-* as every model writes it; with params.new_items also new-audience-*, rows 'j_new\tu\tscore'."""
+        super()._store_audience(path)
+        feats = self._load_new_items() if self.audience_k > 0 else None
+        if feats is None:
+            return
+        self.evaluator.store_audience_new(item_file(path, "new-audience"), feats)
 
     def because_new(self, features, users, rows, top=5):
         """BPRMF.because for items outside the catalogue: for every pair (users[p], rows[p] of `features`: raw rows, or a table

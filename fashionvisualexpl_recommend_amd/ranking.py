@@ -1,6 +1,7 @@
 """The one place where score rows become top-K lists and lists become rows of text: every recs-* / new-recs-* /
 new-user-recs-* / div-* / because-* file, single GPU or sharded, catalogue items or new ones, is ranked and written here, block
-by block (blocks, wanted_blocks), and gets its name here (RUN_FILES, run_file).
+by block (blocks, wanted_blocks), and gets its name here (RUN_FILES, run_file).  So are the item-side lists, audience-* /
+new-audience-* (owners_of: the transposed mask; ITEM_FILES, item_file: their names).
 
 The contract is the reference's (Evaluator.py:225-239): mask the row, then take numpy_topk of it; numpy's unstable argsort
 decides the order of EQUAL scores.  The top-K kernel returns the list wherever it does not depend on that order and flags
@@ -53,6 +54,21 @@ def lists_to_csr(lists, device, dedup=False):
     if items.size == 0:
         items = np.zeros(1, np.int32)
     return torch.as_tensor(ptr, device=device), torch.as_tensor(items, device=device)
+
+
+def owners_of(training_list, num_items):
+    """For each item of [0, num_items) its owners: the users whose training list names it, each once, ascending (int64 arrays, one
+    per item).  The transpose of what store_recommendation masks (set(training_list[user])): an id outside the catalogue has no
+    row here, as it has no column there."""
+    if num_items <= 0:
+        return []
+    lens = np.fromiter((len(l) for l in training_list), dtype=np.int64, count=len(training_list))
+    users = np.repeat(np.arange(len(training_list), dtype=np.int64), lens)
+    items = np.fromiter((int(i) for l in training_list for i in l), dtype=np.int64, count=int(lens.sum()))
+    keep = (items >= 0) & (items < num_items)
+    pairs = np.unique(items[keep] * max(1, len(training_list)) + users[keep])     # by item, then by user, each pair once
+    it, us = pairs // max(1, len(training_list)), pairs % max(1, len(training_list))
+    return np.split(us, np.searchsorted(it, np.arange(1, num_items)))
 
 
 def rank_rows(topk, scores, k, side=None):
@@ -163,6 +179,14 @@ def write_ranked(out, labels, ids, vals, side=None):
     return users, items
 
 
+def write_item_lists(out, labels, ids, vals):
+    """write_ranked for lists that may end in empty slots (id < 0: an item with fewer non-owners than the list is long): the
+    rows 'label\\tid\\tval' of every list up to its first empty slot, formatted as write_ranked formats them."""
+    for r, label in enumerate(labels):
+        n = int((ids[r] >= 0).sum())
+        write_ranked(out, [label], ids[r:r + 1, :n], vals[r:r + 1, :n])
+
+
 def write_feature_rows(out, users, items, e):
     """The expl-* rows of VBPR and GradFashion for the pairs (users, items): 'u\\ti\\tscore\\tbase\\trank\\tcolumn\\tcontribution',
     rank 0 (the largest F_ic w_uc) first, one row per rank the pair has.  e: the numpy dict of Engine.feat_explain, or of
@@ -203,6 +227,22 @@ def run_file(path, kind):
         raise ValueError("%r is neither a recs-* nor a best-recs-* path" % path)
     if kind not in RUN_FILES:
         raise ValueError("run_file: %r is none of %s" % (kind, ", ".join(RUN_FILES)))
+    return head + kind + tail
+
+
+# The files of a run whose lists have one block per ITEM (rows 'item user score'), named like the files of RUN_FILES:
+# [best-]<kind>-<epoch>-<params>.tsv next to the recs-* / best-recs-* file.  A table of its own: RUN_FILES holds the user-side files.
+ITEM_FILES = {"audience": None, "new-audience": None}
+
+
+def item_file(path, kind):
+    """run_file for the kinds of ITEM_FILES: the file of `kind` next to the recs-* / best-recs-* file at `path`, 'best-' stays in
+    front; ValueError for a path whose file name starts with neither, and for a kind that is none of ITEM_FILES."""
+    head, base, tail = _split_run_file(path)
+    if base != "recs":
+        raise ValueError("%r is neither a recs-* nor a best-recs-* path" % path)
+    if kind not in ITEM_FILES:
+        raise ValueError("item_file: %r is none of %s" % (kind, ", ".join(ITEM_FILES)))
     return head + kind + tail
 
 

@@ -14,6 +14,9 @@ greedy Maximal Marginal Relevance from the user's top --diversify_pool, cosines 
 --because L (bprmf, vbpr, grad_fashion) writes because-* / best-because-* files next to recs-*: for every recommended (u, i) the L
 items of u's training list nearest to i by cosine in the space of --similar_space ("because it is like the X you own"), and with
 --new_users / --new_items because-new-user-recs-* / because-new-recs-*.
+--audience K (bprmf, vbpr, grad_fashion) writes audience-* / best-audience-* files next to recs-*: for every catalogue item (or
+the ids of --audience_items) the K users that score it highest, its owners excluded, and with --new_items new-audience-* /
+best-new-audience-* (the visual score of items the model was not trained on).
 Run as `python -m fashionvisualexpl_recommend_amd.train_rec --rec bprmf --dataset <name> ...`.
 """
 import argparse
@@ -111,6 +114,15 @@ def parse_args(argv=None):
                              "without an owned item to compare with: one row with rank -1); with --new_users also "
                              "because-new-user-recs-* (the history is the file's), with --new_items also because-new-recs-* "
                              "(always the visual space); 0 = off")
+    parser.add_argument('--audience', type=int, default=0, metavar='K',
+                        help="bprmf, vbpr, grad_fashion: also write audience-* / best-audience-* files next to recs-* / best-recs-* "
+                             "with the K (1..1024) users that score every catalogue item highest, the item's owners (the users "
+                             "whose training list names it) excluded, rows `i u score`, item by item, best first; with --new_items "
+                             "also new-audience-* / best-new-audience-*, the audience of every new item by the visual score, rows "
+                             "`j_new u score`; 0 = off")
+    parser.add_argument('--audience_items', default=None, metavar='PATH',
+                        help="--audience: a text file with one catalogue item id per line, the items whose audience is written "
+                             "(default: the whole catalogue)")
     parser.add_argument('--fold_steps', type=int, default=30, help='--new_users / --af_new_users / --acf_new_users: optimiser steps per new user')
     parser.add_argument('--fold_negatives', type=int, default=4,
                         help='--new_users / --af_new_users / --acf_new_users: sampled negatives per history item')
@@ -186,9 +198,51 @@ def parse_args(argv=None):
             parser.error("--similar_space %s needs --rec vbpr or grad_fashion (bprmf has the latent space only)" % args.similar_space)
         if args.similar_space != 'latent' and args.dtype == 'fp8':
             parser.error("--similar_space %s runs with --dtype fp32 or bf16 (got fp8): use --similar_space latent" % args.similar_space)
+    if not 0 <= args.audience <= 1024:
+        parser.error("--audience takes 0 (off) .. 1024 (got %s)" % args.audience)
+    if args.audience != 0 and args.rec not in ('bprmf', 'vbpr', 'grad_fashion'):
+        parser.error("--audience needs --rec bprmf, vbpr or grad_fashion (got --rec %s)" % args.rec)
+    if args.audience_items is not None:
+        if args.audience == 0:
+            parser.error("--audience_items needs --audience K")
+        try:
+            read_audience_items(args.audience_items)
+        except (OSError, ValueError) as e:
+            parser.error("--audience_items: %s" % e)
     if not 0.0 <= args.dropout < 1.0:
         parser.error("--dropout takes a rate in [0, 1) (got %s)" % args.dropout)
     return args
+
+
+def read_audience_items(path, num_items=None):
+    """The --audience_items file: one catalogue item id per line -> the ids in file order (repeats kept).  Empty lines are
+    skipped; a line that is no integer, a negative id and (with num_items) an id outside the catalogue raise ValueError with the
+    line's number."""
+    ids = []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            try:
+                i = int(line.strip())
+            except ValueError:
+                raise ValueError("%s:%d: the item %r is not an integer" % (path, ln, line.strip())) from None
+            if i < 0 or (num_items is not None and i >= num_items):
+                raise ValueError("%s:%d: the audience item %d is outside the catalogue%s" % (
+                    path, ln, i, "" if num_items is None else " [0, %d)" % num_items))
+            ids.append(i)
+    return ids
+
+
+def check_audience_items(args, num_items):
+    """--audience_items against the loaded catalogue: an id outside it ends the run as a rejected argument does (parse_args knows
+    no catalogue; it has rejected everything else)."""
+    if getattr(args, "audience_items", None) is None:
+        return
+    try:
+        read_audience_items(args.audience_items, num_items)
+    except ValueError as e:
+        argparse.ArgumentParser(description="Run train of the Recommender Model.").error("--audience_items: %s" % e)
 
 
 def read_new_users(path):
@@ -233,6 +287,8 @@ def train(argv=None):
         raise NotImplementedError('--diversify runs on one GPU (the sharded drivers write no div-* files): use --world_size 1')
     if args.because != 0 and int(args.world_size) > 1:
         raise NotImplementedError('--because runs on one GPU (the sharded drivers write no because-* files): use --world_size 1')
+    if args.audience != 0 and int(args.world_size) > 1:
+        raise NotImplementedError('--audience runs on one GPU (the sharded drivers write no audience-* files): use --world_size 1')
     if args.because != 0 and args.top_k > 1024:
         raise ValueError('--because runs on the device only (top_k <= 1024): there is no host form')
     if args.new_items is not None and args.dtype == 'fp8':
@@ -267,6 +323,7 @@ def train(argv=None):
         print('--------------------------------------------------------------------')
         print('ITERATION %d/%d WITH REGULARIZATION: %f' % (it + 1, len(list(args.list_of_regs)), current_reg))
         data = DataLoader(params=args)
+        check_audience_items(args, data.num_items)
         print("Training {0} on {1}".format(args.rec, args.dataset))
         print("Parameters:")
         args.reg = current_reg                                                                  # train_rec.py:69

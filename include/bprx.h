@@ -150,6 +150,8 @@ BPRX_API int bprx_sync_adam(bprx_handle *h, void *stream);
      entries                                                          handle              tables bound  rows  image  P of all items
      bprx_score_block                                                 any                 yes           yes   via P  yes (VBPR)
      bprx_score_rows_block, bprx_fold_in                              BPRMF / VBPR        yes           yes   via P  yes
+     bprx_audience_block, Pq == NULL                                  BPRMF / VBPR        yes           yes   via P  yes
+     bprx_audience_block, Pq != NULL                                  VBPR, not fp8       yes           yes   yes    -
      bprx_af_fold_in, bprx_af_score_rows_block                        AttentiveFashion    yes           -     -      -
      bprx_acf_fold_in, bprx_acf_profile_rows, bprx_acf_score_rows_block   ACF             yes           -     -      -
      bprx_step_project                                                any                 yes           -     yes    yes
@@ -162,7 +164,7 @@ BPRX_API int bprx_sync_adam(bprx_handle *h, void *stream);
      bprx_topk_rows                                                   VBPR, not fp8       yes           -     -      -
      bprx_apply_user_msgs                                             any                 yes           -     -      -
      bprx_sum_dense_parts                                             VBPR                -             -     -      -
-     bprx_topk, bprx_topk_lists, bprx_eval_*, bprx_tables_dirty, bprx_set_adam_step, bprx_clear_*_grad, bprx_sync_check,
+     bprx_topk, bprx_topk_lists, bprx_topk_rows_masked, bprx_eval_*, bprx_tables_dirty, bprx_set_adam_step, bprx_clear_*_grad, bprx_sync_check,
      bprx_pack_user_msg, the bind calls                               any                 -             -     -      -
    Not behind the gate: bprx_step and bprx_step_begin[_sparse] (a step may carry the update), the samplers, the profile calls, bprx_last_error, bprx_set_hyper,
    bprx_set_loss_lag, the getters, bprx_settle and bprx_dense_pending. */
@@ -337,6 +339,38 @@ BPRX_API int bprx_sim_rnorm(bprx_handle *h, int32_t space, const float *Pq, int6
    0 <= q0 <= q1 <= nq < 2^31, q1 - q0 <= 65535 * 128. */
 BPRX_API int bprx_sim_block(bprx_handle *h, int32_t space, const float *Pq, int64_t nq, int64_t q0, int64_t q1, const float *rn_q,
                             const float *rn_items, float *out, void *stream);
+
+/* ---- BPRMF, VBPR and GradFashion: audiences, the score block item-major ---------------------------------------------------
+   "Who should see this item": the scores of a range of items against EVERY user, one output row per item, so that a top-K over
+   a row is the item's audience.  The user-major blocks of bprx_score_block / bprx_score_new_block cannot be transposed
+   afterwards (the U x I matrix is never resident); this is their kernel with the operand roles swapped.
+   out fp32 [(q1-q0), num_users] (row stride num_users), q = q0 + r:
+       Pq == NULL  the catalogue, nq must equal num_items:
+                   out[r][u] = Bi_q + Gu_u.Gi_q (+ Tu_u.P_q[0:d] + P_q[d])     bprx_score_block's score
+       Pq != NULL  rows of bprx_project_rows' output Pq [nq, PS], items outside the catalogue:
+                   out[r][u] = Tu_u.Pq_q[0:d] + Pq_q[d]                        bprx_score_new_block's score
+   The fp32 MFMA GEMM of bprx_score_block with A = the item rows, B = the user rows: exact fp32 products, sums in x order from
+   +0, Gi before P, then acc + (Bi_q + P_q[d]).  Contract: for EVEN embed_k and embed_d, out[r][u] has the bits of
+   bprx_score_block's out[u][q] (Pq: of bprx_score_new_block's out[u][q]).  For an odd embed_k or embed_d bprx_score_block
+   runs its non-MFMA kernel, whose summation order differs; this entry stays on the MFMA path (K padded with zeros) and is
+   then close to it, not bit-equal (bprx_score_new_block is always on the MFMA path: bit-equal for any d).  A row's bits
+   depend on its item row and the user tables only: not on q0, q1, nq or the tile it lands in.
+   Handles: a bound BPRMF or VBPR handle, plain or factored; the catalogue form takes every feature dtype bprx_score_block takes,
+   the Pq form a VBPR handle with fp32 or bf16 features (the rule of bprx_score_new_block).
+   0 <= q0 <= q1 <= nq < 2^31, q1 - q0 <= 65535 * 128.  BPRX_E_INVALID for a NULL handle or pointer (Pq excepted), an ACF or
+   AttentiveFashion handle, Pq with a BPRMF or an fp8 handle, Pq == NULL with nq != num_items, a bad range; BPRX_E_STATE for
+   unbound tables; q0 == q1: BPRX_OK, nothing is written.  After any error the handle stays usable.
+   State: the catalogue form enters like bprx_score_block (settles a pending dense update, brings lazy adam_tf23 rows up to
+   date, makes P current), the Pq form like bprx_score_new_block (rows, the [E|Bp]^T image); apart from that the call writes its
+   output only and allocates nothing: a training run with these calls between its steps ends bit-identical to one without. */
+BPRX_API int bprx_audience_block(bprx_handle *h, const float *Pq, int64_t nq, int64_t q0, int64_t q1, float *out, void *stream);
+/* bprx_topk_rows with bprx_topk_lists' per-row mask lists: nrows rows of explicit `width` (row stride width; an audience block:
+   width = num_users), row r gets -inf IN `scores` at list_items[list_ptr[r] .. list_ptr[r+1]) (list_ptr int64 [nrows+1], device;
+   an id outside [0, width) is ignored, a repeated id is harmless).  Selection, order and flag rules, K (1..1024) and outputs as
+   bprx_topk; a row with fewer than min(K, width) unmasked entries is flagged.  1 <= width < 2^31, 0 <= nrows < 2^31.  Any handle,
+   bound or not (as bprx_topk_lists). */
+BPRX_API int bprx_topk_rows_masked(bprx_handle *h, int64_t nrows, int32_t width, float *scores, const int64_t *list_ptr,
+                                   const int32_t *list_items, int32_t K, int32_t *idx, float *val, int32_t *flag, void *stream);
 
 /* ---- BPRMF, VBPR and GradFashion: diversified lists, greedy Maximal Marginal Relevance over a top-N pool -------------------
    "K of the N best that are good and unlike the picks above them".  One list has the pool (id_c, v_c), c = 0 .. N-1, best first,
