@@ -601,6 +601,58 @@ extern "C" int bprx_score_new_block(bprx_handle *h, int32_t u0, int32_t u1, cons
   return BPRX_OK;
 }
 
+// ---- warm items: the full score of caller-owned item rows (include/bprx.h: bprx_score_warm_block / bprx_audience_warm_block) ----
+// The checks the two entries share, then the gate: the rows are scored against Gu / Tu only (no catalogue projection is read); Pn
+// was made by bprx_project_rows, so the handles are its handles plus BPRMF (d == 0, no Pn).
+static int warm_enter(bprx_handle *h, const char *what, const float *Gi_rows, const float *Bi_rows, const float *Pn, int64_t n,
+                      bool empty, const float *out, hipStream_t s) {
+  if (n < 0 || n >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "%s: n = %lld out of range", what, (long long)n);
+  if (!empty && (!Gi_rows || !Bi_rows || !out || (h->cfg.embed_d > 0) != (Pn != nullptr)))
+    BPRX_FAIL(h, BPRX_E_INVALID, "%s: null pointer", what);
+  if (h->cfg.model == BPRX_MODEL_VBPR && h->cfg.feat_dtype == BPRX_F_FP8)
+    BPRX_FAIL(h, BPRX_E_INVALID, "%s: fp8 features are not supported for new items (a new row may exceed the max-abs the codes "
+                                 "were scaled for and would saturate): fp32 or bf16", what);
+  return bprx_enter(h, what, NEED_BOUND | NEED_ROWS | NEED_ET, KIND_PLAIN, s);
+}
+
+static GemmArgs warm_args(const bprx_handle *h, const float *Gi_rows, const float *Bi_rows, const float *Pn, int64_t n) {
+  GemmArgs g;
+  g.Gu = h->t.Gu; g.Gi = Gi_rows; g.Bi = Bi_rows; g.Tu = h->t.Tu; g.P = Pn;
+  g.U = h->cfg.num_users; g.I = (int)n; g.k = h->cfg.embed_k; g.d = h->cfg.embed_d; g.PS = h->PS;
+  return g;
+}
+
+extern "C" int bprx_score_warm_block(bprx_handle *h, int32_t u0, int32_t u1, const float *Gi_rows, const float *Bi_rows, const float *Pn,
+                                     int64_t n, float *out, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (u0 < 0 || u1 > h->cfg.num_users || u0 > u1) BPRX_FAIL(h, BPRX_E_INVALID, "score_warm_block: bad user range [%d,%d)", u0, u1);
+  const bool empty = n == 0 || u0 == u1;
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = warm_enter(h, "score_warm_block", Gi_rows, Bi_rows, Pn, n, empty, out, s);
+  if (rc || empty) return rc;
+  if (h->cfg.embed_k % 2 || h->cfg.embed_d % 2)              // an odd width: the non-MFMA kernel, as bprx_score_block
+    return bprx_launch_score_block(h, u0, u1, out, s, {h->t.Gu, h->t.Tu}, {Gi_rows, Bi_rows, Pn, (int)n});
+  dim3 grid((unsigned)((n + TN - 1) / TN), (unsigned)((u1 - u0 + TM - 1) / TM));
+  hipLaunchKernelGGL(k_score_gemm, grid, dim3(256), 0, s, warm_args(h, Gi_rows, Bi_rows, Pn, n), u0, u1, out);
+  BPRX_LAUNCH_CHECK(h, "k_score_gemm");
+  return BPRX_OK;
+}
+
+extern "C" int bprx_audience_warm_block(bprx_handle *h, const float *Gi_rows, const float *Bi_rows, const float *Pn, int64_t n,
+                                        int64_t q0, int64_t q1, float *out, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (q0 < 0 || q0 > q1 || q1 > n || q1 - q0 > (int64_t)65535 * TM)
+    BPRX_FAIL(h, BPRX_E_INVALID, "audience_warm_block: bad item range [%lld,%lld) of %lld", (long long)q0, (long long)q1, (long long)n);
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = warm_enter(h, "audience_warm_block", Gi_rows, Bi_rows, Pn, n, q0 == q1, out, s);
+  if (rc || q0 == q1) return rc;
+  const GemmArgs g = warm_args(h, Gi_rows, Bi_rows, Pn, n);
+  dim3 grid((unsigned)((g.U + TN - 1) / TN), (unsigned)((q1 - q0 + TM - 1) / TM));
+  hipLaunchKernelGGL(k_audience_gemm, grid, dim3(256), 0, s, g, (int)q0, (int)q1, out);
+  BPRX_LAUNCH_CHECK(h, "k_audience_gemm");
+  return BPRX_OK;
+}
+
 // ---- similar items: bprx_sim_rnorm / bprx_sim_block (include/bprx.h) ----
 // The checks the two entries share, then the gate: the space, the query rows (the catalogue: nq == num_items; the caller's rows:
 // visual only), fp8 in a space that reads P, and plan_read's own (bound, handle kind).

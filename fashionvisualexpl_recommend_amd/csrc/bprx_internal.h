@@ -378,7 +378,9 @@ int bprx_launch_loss_reduce(bprx_handle *h, int64_t B, float *loss_out, hipStrea
 int bprx_launch_loss_reduce_at(bprx_handle *h, int64_t B, int nsq, float reg, float *loss_out, hipStream_t s);   // a lagging loss
 // the user side of a block score: rows [u0, u1) of these tables (the handle's own Gu / Tu, or a caller's)
 struct UserRows { const float *Gu, *Tu; };
-int bprx_launch_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s, UserRows rows);
+// the item side: the catalogue (Gi == nullptr), or n caller-owned rows Gi [n, k] / Bi [n] / P [n, PS] (bprx_score_warm_block)
+struct ItemRows { const float *Gi, *Bi, *P; int n; };
+int bprx_launch_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s, UserRows rows, ItemRows items = {});
 int bprx_launch_score_gemm(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s, UserRows rows);
 // projection part (bprx_proj.hip)
 int bprx_launch_tile_F(bprx_handle *h);

@@ -2407,9 +2407,10 @@ int bprx_launch_loss_reduce(bprx_handle *h, int64_t B, float *loss_out, hipStrea
   return bprx_launch_loss_reduce_at(h, B, h->cfg.model == BPRX_MODEL_VBPR ? h->dense_blocks : 0, h->cfg.reg, loss_out, s);
 }
 
-int bprx_launch_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s, UserRows rows) {
+int bprx_launch_score_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, hipStream_t s, UserRows rows, ItemRows items) {
   SparseArgs a = make_args(h, h->P, h->step);
   a.Gu = rows.Gu; a.Tu = rows.Tu;
+  if (items.Gi) { a.Gi = items.Gi; a.Bi = items.Bi; a.P = items.P; a.I = items.n; }
   dim3 grid((a.I + 63) / 64, (u1 - u0 + 3) / 4);
   hipLaunchKernelGGL(k_score_block, grid, dim3(256), 0, s, a, u0, u1, out);
   BPRX_LAUNCH_CHECK(h, "k_score_block");

@@ -669,6 +669,64 @@ class Engine:
         _ffi.check(self.h, self.lib.bprx_audience_block(self.h, _addr(P), nq, int(q0), int(q1), _addr(out), _stream()))
         return out
 
+    # ---- warm items (include/bprx.h: Gi / Bi rows for new items with first buyers, everything else frozen) ----------------------
+    def _warm_rows(self, what, Gi_rows, Bi_rows, Pn):
+        """n of the caller-owned item rows Gi_rows [n, k] / Bi_rows [n] / Pn [n, proj_stride()] (None iff d == 0), checked."""
+        n = int(Bi_rows.shape[0]) if Bi_rows is not None and Bi_rows.dim() == 1 else -1
+        if n < 0 or not (Bi_rows.is_cuda and Bi_rows.dtype == torch.float32 and Bi_rows.is_contiguous()):
+            raise ValueError("%s: Bi_rows must be a contiguous fp32 device tensor [n]" % what)
+        if (self.d > 0) != (Pn is not None):
+            raise ValueError("%s: Pn = project_rows(F) is needed iff the model has a visual part (d = %d)" % (what, self.d))
+        self._check_rows(what, n, ("Gi_rows", Gi_rows, self.k), ("Pn", Pn, self.proj_stride() if self.d else 0))
+        if Gi_rows is None:
+            raise ValueError("%s: Gi_rows is None" % what)
+        return n
+
+    def fold_in_items(self, pair_ptr, user, other, role, steps, Gi_rows, Bi_rows, Pn=None, lr=None, reg=None, optimizer=None,
+                      want_loss=True):
+        """bprx_fold_in_items: `steps` optimiser steps on each row of Gi_rows [n, k] / Bi_rows [n] (contiguous fp32 device tensors,
+        updated IN PLACE) over the pairs (user[p], other[p], role[p]), p in [pair_ptr[r], pair_ptr[r + 1]), of new item r: role 0
+        the new item is the positive against the catalogue item other[p], role 1 the negative.  Pn = project_rows(F) of the new
+        items (None iff d == 0).  pair_ptr: int64 [n + 1].  lr / reg / optimizer default to the engine's.  Plain sgd sums the
+        batch loss and oscillates once lr * 0.25 * pairs * (1 + |Gu|^2) passes 2: few pairs or a small lr; Adam does not care.
+        Returns loss fp32 [n] (loss_steps, before the last update) or None."""
+        n = self._warm_rows("fold_in_items", Gi_rows, Bi_rows, Pn)
+        ptr = torch.as_tensor(pair_ptr, dtype=torch.int64).to(self.device).contiguous()
+        if int(ptr.numel()) - 1 != n:
+            raise ValueError("fold_in_items: pair_ptr for %d items, rows for %d" % (int(ptr.numel()) - 1, n))
+        u_, o_, r_ = (as_index(x, self.device) for x in (user, other, role))
+        if not u_.numel() == o_.numel() == r_.numel():
+            raise ValueError("fold_in_items: %d users, %d items, %d roles" % (u_.numel(), o_.numel(), r_.numel()))
+        lr = self._hyper()[0] if lr is None else float(lr)
+        reg = self._hyper()[1] if reg is None else float(reg)
+        opt = _ffi.OPTIMIZER[self.optimizer if optimizer is None else optimizer]
+        loss = torch.empty(n, dtype=torch.float32, device=self.device) if want_loss else None
+        if u_.numel() == 0:                                  # (no item has a pair: the library still wants the pointers)
+            u_ = o_ = r_ = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _ffi.check(self.h, self.lib.bprx_fold_in_items(self.h, _addr(ptr), _addr(u_), _addr(o_), _addr(r_), n, _addr(Pn), int(steps),
+                                                       lr, reg, opt, _addr(Gi_rows), _addr(Bi_rows), _addr(loss), _stream()))
+        return loss
+
+    def score_warm_block(self, u0, u1, Gi_rows, Bi_rows, Pn=None, out=None):
+        """bprx_score_warm_block: fp32 [u1 - u0, n], out[u][j] = Bi_j + Gu_u.Gi_j + Tu_u.Pn[j, :d] + Pn[j, d] for caller-owned item
+        rows (fold_in_items' result; Pn None iff d == 0): score_block's kernels, given these rows."""
+        n = self._warm_rows("score_warm_block", Gi_rows, Bi_rows, Pn)
+        if out is None:
+            out = torch.empty((max(u1 - u0, 0), n), dtype=torch.float32, device=self.device)
+        _ffi.check(self.h, self.lib.bprx_score_warm_block(self.h, int(u0), int(u1), _addr(Gi_rows), _addr(Bi_rows), _addr(Pn), n,
+                                                          _addr(out), _stream()))
+        return out
+
+    def audience_warm_block(self, Gi_rows, Bi_rows, Pn, q0, q1, out=None):
+        """bprx_audience_warm_block: fp32 [q1 - q0, U], score_warm_block item-major for rows q0 .. q1-1 (bit for bit where k and d
+        are even)."""
+        n = self._warm_rows("audience_warm_block", Gi_rows, Bi_rows, Pn)
+        if out is None:
+            out = torch.empty((max(q1 - q0, 0), self.U), dtype=torch.float32, device=self.device)
+        _ffi.check(self.h, self.lib.bprx_audience_warm_block(self.h, _addr(Gi_rows), _addr(Bi_rows), _addr(Pn), n, int(q0), int(q1),
+                                                             _addr(out), _stream()))
+        return out
+
     def topk_rows_masked(self, scores, lists_csr, K):
         """bprx_topk_rows_masked: topk_rows for the rows of a contiguous fp32 [nrows, width] device tensor, row r masking (IN
         `scores`) the ids of list r of lists_csr = (int64 ptr [nrows + 1], int32 ids): (idx int32 [nrows, K], val, flag)."""

@@ -295,6 +295,32 @@ class Evaluator:
         with open(path, 'w') as out:
             write_item_lists(out, range(ids.shape[0]), ids, vals)
 
+    def store_recommendation_warm(self, path="", buyers=None, features=None, rows=None, **fold):
+        """BPRMF / VBPR / GradFashion: the top-k WARM items of every user (model.recommend_warm: new items whose Gi / Bi rows are
+        fitted from buyers[j], the users who bought item j; the ones a user bought are masked) as rows 'u\tj\tscore', j = the row
+        of `buyers` (and of `features`, raw rows as model.prepare_new_items takes them), best first, formatted as
+        store_recommendation formats them.  rows: what model.fold_in_items returned for these buyers (None: fitted here with
+        **fold).  Returns the rows, so that store_audience_warm can read the same fit."""
+        m = self.model
+        if rows is None:
+            rows = m.fold_in_items(buyers, features, **fold)
+        ids, vals = m._rank_warm_recs(rows, buyers)
+        with open(path, 'w') as out:
+            write_item_lists(out, range(ids.shape[0]), ids, vals)
+        return rows
+
+    def store_audience_warm(self, path="", buyers=None, features=None, rows=None, **fold):
+        """BPRMF / VBPR / GradFashion: the audience of every warm item (model.audience_warm: the params' K users with the highest
+        score, the item's buyers masked) as rows 'j\tu\tscore', item by item, best first.  rows / **fold as
+        store_recommendation_warm takes them."""
+        m = self.model
+        if rows is None:
+            rows = m.fold_in_items(buyers, features, **fold)
+        ids, vals = m._rank_warm_audience(rows, buyers)
+        with open(path, 'w') as out:
+            write_item_lists(out, range(ids.shape[0]), ids, vals)
+        return rows
+
     def store_recommendation_grads(self, path="", path_expl=None, top=5):
         """Evaluator.py:261-275 (GradFashion): for every user the items training_list[u] + validation_list[u] + test_list[u],
         in that order, one row 'u\\ti\\tcolour\\tedges' each (get_explanations.py:19-21 reads USER_ID, ITEM_ID, COLOR, EDGES).

@@ -20,7 +20,7 @@ from . import configs
 from .engine import Engine, as_index
 from .evaluator import Evaluator
 from .ranking import (because_paths, because_rows, blocks, diverse_zeros, diversify_rows, div_paths, item_file, owners_of, rank_rows,
-                      ranked_zeros, run_file, wanted_blocks, write_because, write_diverse, write_ranked)
+                      ranked_zeros, run_file, wanted_blocks, warm_file, write_because, write_diverse, write_ranked)
 from .synth import glorot_uniform
 
 
@@ -68,6 +68,70 @@ def draw_fold_pairs(histories, num_items, negatives, seed):
         ptr[r + 1] = ptr[r] + need
     cat = lambda parts: (np.concatenate(parts) if parts else np.zeros(0, np.int64)).astype(np.int32)
     return ptr, cat(pos), cat(neg)
+
+
+def draw_item_fold_pairs(buyers, training_list, num_items, negatives, seed):
+    """The pairs of items the model was not trained on, from their first buyers (buyers[r]: the catalogue users who bought new
+    item r), drawn on the host with numpy.random.default_rng(seed).  Items are taken in order, each item's buyers deduplicated in
+    first-appearance order.
+      role 0  the new item is the positive: for each buyer u `negatives` pairs (u, o, 0), o uniform over the catalogue items
+              outside training_list[u] (by rejection); a buyer whose list covers the catalogue gives none;
+      role 1  the new item is the negative, as often as it was the positive (what training does to an item of average
+              popularity; with role 0 alone nothing but the regulariser holds the item's bias down): as many pairs (u', o', 1)
+              as the item got in role 0, u' uniform over the users that are not buyers of this item and have a non-empty
+              training list (by rejection), o' uniform from training_list[u']; no such user: none.
+    Returns (pair_ptr int64 [n + 1], user int32, other int32, role int32), each item's role-0 pairs first; a buyer outside
+    [0, len(training_list)) or a listed item outside [0, num_items) raises ValueError."""
+    I, U, negatives = int(num_items), len(training_list), int(negatives)
+    if negatives < 1:
+        raise ValueError("draw_item_fold_pairs: negatives = %d < 1" % negatives)
+    lens = np.fromiter((len(l) for l in training_list), dtype=np.int64, count=U)
+    tptr = np.zeros(U + 1, np.int64)
+    np.cumsum(lens, out=tptr[1:])
+    flat = np.fromiter((int(i) for l in training_list for i in l), dtype=np.int64, count=int(tptr[-1]))
+    if flat.size and (flat.min() < 0 or flat.max() >= I):
+        raise ValueError("draw_item_fold_pairs: a training list has an item outside [0, %d)" % I)
+    rng = np.random.default_rng(seed)
+    ptr = np.zeros(len(buyers) + 1, np.int64)
+    users, others, roles = [], [], []
+    owned, is_buyer = np.zeros(I, bool), np.zeros(U, bool)
+
+    def rejected(high, need, bad):
+        """`need` uniform draws from [0, high) outside the mask `bad`"""
+        out, filled = np.empty(need, np.int64), 0
+        while filled < need:
+            c = rng.integers(0, high, size=need - filled)
+            c = c[~bad[c]]
+            out[filled:filled + c.size] = c
+            filled += c.size
+        return out
+
+    for r, who in enumerate(buyers):
+        b = np.asarray(list(dict.fromkeys(int(u) for u in who)), dtype=np.int64)
+        if b.size and (b.min() < 0 or b.max() >= U):
+            raise ValueError("draw_item_fold_pairs: item %d has a buyer outside [0, %d)" % (r, U))
+        n0 = 0
+        for u in b:
+            mine = flat[tptr[u]:tptr[u + 1]]
+            owned[mine] = True
+            if int(owned.sum()) < I:
+                users.append(np.full(negatives, u, np.int64))
+                others.append(rejected(I, negatives, owned))
+                roles.append(np.zeros(negatives, np.int64))
+                n0 += negatives
+            owned[mine] = False
+        is_buyer[b] = True
+        out_of_play = is_buyer | (lens == 0)
+        n1 = n0 if not out_of_play.all() else 0
+        if n1:
+            up = rejected(U, n1, out_of_play)
+            users.append(up)
+            others.append(flat[tptr[up] + rng.integers(0, lens[up])])
+            roles.append(np.ones(n1, np.int64))
+        is_buyer[b] = False
+        ptr[r + 1] = ptr[r] + n0 + n1
+    cat = lambda parts: (np.concatenate(parts) if parts else np.zeros(0, np.int64)).astype(np.int32)
+    return ptr, cat(users), cat(others), cat(roles)
 
 
 def fold_start_rows(x, n, w, device):
@@ -297,6 +361,7 @@ class BPRMF(RecommenderModel):
         self._store_diverse(path)
         self._store_because(path)
         self._store_audience(path)
+        self._store_warm(path)
 
     def _store_recs(self, path):
         """What train() leaves at the recs-* / best-recs-* paths: the top-K lists (BPRMF.py:167-187)."""
@@ -467,6 +532,93 @@ class BPRMF(RecommenderModel):
             from .train_rec import read_audience_items
             items = read_audience_items(src, self.num_items)
         self.evaluator.store_audience(item_file(path, "audience"), items)
+
+    # ---- warm items: Gi / Bi rows for new items from their first buyers, everything else frozen (include/bprx.h) ------------------
+    def _warm_projections(self, features, n):
+        """Pn of the n new items as Engine.fold_in_items takes it: None for a model without a visual part, which takes no features."""
+        if features is not None:
+            raise ValueError("%s: a model without a visual part takes no features" % type(self).__name__)
+        return None
+
+    def fold_in_items(self, buyers, features=None, steps=30, negatives=4, lr=None, reg=None, optimizer=None, seed=0, init=None):
+        """Rows for items that arrive after training, from their first buyers (buyers[r]: the catalogue users who bought new item
+        r): (Gi_new [n, k], Bi_new [n], P_new [n, proj_stride] or None) device tensors, fitted by Engine.fold_in_items over the
+        pairs of draw_item_fold_pairs(buyers, training_list, num_items, negatives, seed).  VBPR / GradFashion need `features` (raw
+        rows, or a table from prepare_new_items), one row per item.  lr / reg / optimizer: None = the run's.  init: None = zero
+        rows, or (Gi rows, Bi rows) to start from.  An item without buyers keeps its start rows: from zeros it scores exactly as
+        score_new_items scores it.  With plain sgd the step size must shrink with the number of pairs (the batch loss is summed:
+        lr * 0.25 * pairs * (1 + |Gu|^2) < 2); Adam, the default, does not care.  For first buyers, not for refitting
+        bestsellers."""
+        eng = self.engine
+        n = len(buyers)
+        P = self._warm_projections(features, n)
+        ptr, user, other, role = draw_item_fold_pairs(buyers, self.data.training_list[:self.num_users], self.num_items, negatives, seed)
+        g0, b0 = (None, None) if init is None else init
+        Gi, Bi = fold_start_rows(g0, n, eng.k, eng.device), fold_start_rows(b0, n, 1, eng.device).reshape(n)
+        eng.fold_in_items(ptr, user, other, role, steps, Gi, Bi, P, lr=self.learning_rate if lr is None else lr,
+                          reg=self.reg if reg is None else reg, optimizer=self.optimizer_name if optimizer is None else optimizer,
+                          want_loss=False)
+        return Gi, Bi, P
+
+    def recommend_warm(self, buyers, features=None, k=None, **fold):
+        """The k (default top_k) best warm items of every user, the ones the user bought masked: numpy ids int64 [U, kk] (rows of
+        `buyers`) and vals fp32 [U, kk], kk = min(k, n), best first, -1 / -inf past a user's unmasked items.  The rows are fitted
+        by fold_in_items(buyers, features, **fold), scored by Engine.score_warm_block and listed by ranking.rank_rows with
+        Engine.topk_rows_masked."""
+        return self._rank_warm_recs(self.fold_in_items(buyers, features, **fold), buyers, k)
+
+    def audience_warm(self, buyers, features=None, k=None, **fold):
+        """The k (default: params.audience, else top_k) users with the highest score for every warm item, its buyers masked: numpy
+        ids int64 [n, kk] and vals fp32 [n, kk], kk = min(k, U), best first, -1 / -inf past an item's non-buyers.  Fitted as
+        recommend_warm fits, scored item-major by Engine.audience_warm_block."""
+        return self._rank_warm_audience(self.fold_in_items(buyers, features, **fold), buyers, k)
+
+    def _rank_warm_recs(self, rows, buyers, k=None):
+        """recommend_warm's lists for the fitted rows of fold_in_items(buyers): the rows are only read, one fit serves both lists."""
+        eng, U, n = self.engine, self.num_users, len(buyers)
+        k = self.evaluator.k if k is None else int(k)
+        ids, vals = ranked_zeros(U, min(k, n))
+        if n == 0:
+            return ids, vals
+        bought = owners_of(buyers, U)                            # per user the warm items that user bought
+        for b0, b1 in blocks(U, self.evaluator.user_block, n):
+            own = eng.csr(bought[b0:b1])
+            ids[b0:b1], vals[b0:b1], _ = rank_rows(lambda s, kq: eng.topk_rows_masked(s, own, kq),
+                                                   eng.score_warm_block(b0, b1, *rows), k)
+        ids[vals == -np.inf] = -1
+        return ids, vals
+
+    def _rank_warm_audience(self, rows, buyers, k=None):
+        """audience_warm's lists for the fitted rows of fold_in_items(buyers)."""
+        eng, U, n = self.engine, self.num_users, len(buyers)
+        k = (self.audience_k or self.evaluator.k) if k is None else int(k)
+        ids, vals = ranked_zeros(n, min(k, U))
+        for b0, b1 in blocks(n, self.evaluator.user_block, U):
+            own = eng.csr([list(dict.fromkeys(int(u) for u in who)) for who in buyers[b0:b1]])
+            ids[b0:b1], vals[b0:b1], _ = rank_rows(lambda s, kq: eng.topk_rows_masked(s, own, kq),
+                                                   eng.audience_warm_block(*rows, b0, b1), k)
+        ids[vals == -np.inf] = -1
+        return ids, vals
+
+    def _store_warm(self, path):
+        """params.warm_items: warm-recs-* (rows 'u\tj\tscore') and, with params.audience = K > 0, warm-audience-* (rows
+        'j\tu\tscore') next to the recs-* file at `path`, j = the row of the file (VBPR / GradFashion: of the new_items table); one
+        fit serves both."""
+        src = getattr(self.params, "warm_items", None)
+        if not src:
+            return
+        from .train_rec import read_warm_items
+        feats = self._load_new_items()
+        buyers = read_warm_items(src, None if feats is None else len(feats[0] if isinstance(feats, tuple) else feats))
+        fold = dict(steps=getattr(self.params, "fold_steps", 30), negatives=getattr(self.params, "fold_negatives", 4),
+                    seed=getattr(self.params, "init_seed", 0))
+        rows = self.evaluator.store_recommendation_warm(warm_file(path, "warm-recs"), buyers, feats, **fold)
+        if self.audience_k > 0:
+            self.evaluator.store_audience_warm(warm_file(path, "warm-audience"), buyers, rows=rows)
+
+    def _load_new_items(self):
+        """The tables of params.new_items; a model without a visual part has none."""
+        return None
 
     # ---- diversified lists: greedy MMR over each list's top-N pool in the model's item space (include/bprx.h, bprx_diversify) --
     diverse = True                                               # False: the model has no item space (ACF, AttentiveFashion)
@@ -746,6 +898,15 @@ class VBPR(BPRMF):
         for b0, b1 in blocks(n, self.evaluator.user_block, U):
             ids[b0:b1], vals[b0:b1], _ = rank_rows(eng.topk_rows, eng.audience_block(b0, b1, P), k)
         return ids, vals
+
+    def _warm_projections(self, features, n):
+        """Pn [n, proj_stride] of the new items' features (raw rows, or a table from prepare_new_items), one row per item."""
+        if features is None:
+            raise ValueError("%s: warm items need their features (raw rows, or a table from prepare_new_items)" % type(self).__name__)
+        P = self.engine.project_rows(self._as_new_table(features))
+        if int(P.shape[0]) != n:
+            raise ValueError("%s: %d feature rows for %d warm items" % (type(self).__name__, int(P.shape[0]), n))
+        return P
 
     def _store_audience(self, path):
         """audience-* as every model writes it; with params.new_items also new-audience-*, rows 'j_new\tu\tscore'."""

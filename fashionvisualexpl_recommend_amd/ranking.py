@@ -246,6 +246,22 @@ def item_file(path, kind):
     return head + kind + tail
 
 
+# The files of a run about WARM items (new items whose Gi / Bi rows were fitted from their first buyers): warm-recs-* has one block
+# per user (rows 'user row score'), warm-audience-* one per warm item (rows 'row user score'), named like the files above.
+WARM_FILES = {"warm-recs": None, "warm-audience": None}
+
+
+def warm_file(path, kind):
+    """run_file for the kinds of WARM_FILES: the file of `kind` next to the recs-* / best-recs-* file at `path`, 'best-' stays in
+    front; ValueError for a path whose file name starts with neither, and for a kind that is none of WARM_FILES."""
+    head, base, tail = _split_run_file(path)
+    if base != "recs":
+        raise ValueError("%r is neither a recs-* nor a best-recs-* path" % path)
+    if kind not in WARM_FILES:
+        raise ValueError("warm_file: %r is none of %s" % (kind, ", ".join(WARM_FILES)))
+    return head + kind + tail
+
+
 def _about(path, family, what):
     """The files of RUN_FILES that are about the list file at `path` and whose kind starts with `family`, in the table's order."""
     head, base, tail = _split_run_file(path)

@@ -17,6 +17,8 @@ items of u's training list nearest to i by cosine in the space of --similar_spac
 --audience K (bprmf, vbpr, grad_fashion) writes audience-* / best-audience-* files next to recs-*: for every catalogue item (or
 the ids of --audience_items) the K users that score it highest, its owners excluded, and with --new_items new-audience-* /
 best-new-audience-* (the visual score of items the model was not trained on).
+--warm_items PATH (bprmf, vbpr, grad_fashion) fits Gi / Bi rows for new items from their first buyers (rows `row<TAB>user`; vbpr and
+grad_fashion: rows of the --new_items table) and writes warm-recs-* / best-warm-recs-* files, with --audience K also warm-audience-*.
 Run as `python -m fashionvisualexpl_recommend_amd.train_rec --rec bprmf --dataset <name> ...`.
 """
 import argparse
@@ -123,9 +125,19 @@ def parse_args(argv=None):
     parser.add_argument('--audience_items', default=None, metavar='PATH',
                         help="--audience: a text file with one catalogue item id per line, the items whose audience is written "
                              "(default: the whole catalogue)")
-    parser.add_argument('--fold_steps', type=int, default=30, help='--new_users / --af_new_users / --acf_new_users: optimiser steps per new user')
+    parser.add_argument('--warm_items', default=None, metavar='PATH',
+                        help="bprmf, vbpr, grad_fashion: a TSV of `row<TAB>user` rows, the first buyers (catalogue users) of items the "
+                             "model was not trained on; vbpr, grad_fashion: `row` is a row of the --new_items table (required), bprmf: "
+                             "the file defines max row + 1 items.  Each item's Gi / Bi row is fitted with everything else frozen "
+                             "(the item as the positive against sampled negatives of its buyers, and as often as the negative of "
+                             "other users' items) and warm-recs-* / best-warm-recs-* files (u, row, score: every user's top_k warm "
+                             "items, bought ones excluded) are written next to recs-* / best-recs-*; with --audience K also "
+                             "warm-audience-* / best-warm-audience-* (row, u, score).  A row without buyers keeps zero Gi / Bi and "
+                             "scores as in new-recs-*")
+    parser.add_argument('--fold_steps', type=int, default=30,
+                        help='--new_users / --af_new_users / --acf_new_users / --warm_items: optimiser steps per new user or item')
     parser.add_argument('--fold_negatives', type=int, default=4,
-                        help='--new_users / --af_new_users / --acf_new_users: sampled negatives per history item')
+                        help='--new_users / --af_new_users / --acf_new_users: sampled negatives per history item; --warm_items: per buyer')
     # not in the reference
     parser.add_argument('--dropout', type=float, default=0.5,
                         help="attentive_fashion: rate of the encoders' Dropout layers (AttentiveFashion.py:53,62,70: 0.5)")
@@ -177,6 +189,15 @@ def parse_args(argv=None):
         parser.error("--af_new_users needs --rec attentive_fashion (got --rec %s)" % args.rec)
     if args.acf_new_users is not None and args.rec != 'acf':
         parser.error("--acf_new_users needs --rec acf (got --rec %s)" % args.rec)
+    if args.warm_items is not None:
+        if args.rec not in ('bprmf', 'vbpr', 'grad_fashion'):
+            parser.error("--warm_items needs --rec bprmf, vbpr or grad_fashion (got --rec %s)" % args.rec)
+        if args.rec != 'bprmf' and args.new_items is None:
+            parser.error("--warm_items needs --new_items with --rec %s (the rows of the file are rows of that table)" % args.rec)
+        try:
+            read_warm_items(args.warm_items)
+        except (OSError, ValueError) as e:
+            parser.error("--warm_items: %s" % e)
     if args.fold_steps < 1 or args.fold_negatives < 1:
         parser.error("--fold_steps and --fold_negatives take values >= 1 (got %s, %s)" % (args.fold_steps, args.fold_negatives))
     if not 0 <= args.similar_items <= 1024:
@@ -245,6 +266,35 @@ def check_audience_items(args, num_items):
         argparse.ArgumentParser(description="Run train of the Recommender Model.").error("--audience_items: %s" % e)
 
 
+def read_warm_items(path, num_rows=None):
+    """The --warm_items file: rows `row<TAB>user` -> one list of buyers per new item, buyers[row] in file order (repeats kept).
+    num_rows: the rows of the --new_items table the file refers to (None: the file defines max row + 1 items); rows without a
+    line have no buyers.  Empty lines are skipped; a line that is not two integers, a negative row or user and a row past the
+    table raise ValueError with the line's number."""
+    pairs = []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip():
+                continue
+            parts = line.split("\t")
+            try:
+                if len(parts) != 2:
+                    raise ValueError
+                row, user = int(parts[0]), int(parts[1])
+            except ValueError:
+                raise ValueError("%s:%d: expected `row<TAB>user`, two integers, got %r" % (path, ln, line)) from None
+            if row < 0 or user < 0:
+                raise ValueError("%s:%d: row and user are not negative, got %r" % (path, ln, line))
+            if num_rows is not None and row >= num_rows:
+                raise ValueError("%s:%d: row %d is past the table of %d new items" % (path, ln, row, num_rows))
+            pairs.append((row, user))
+    buyers = [[] for _ in range(max((r for r, _ in pairs), default=-1) + 1 if num_rows is None else num_rows)]
+    for row, user in pairs:
+        buyers[row].append(user)
+    return buyers
+
+
 def read_new_users(path):
     """The --new_users file: rows `label<TAB>item` -> (labels in first-appearance order, one item list per label, in file order).
     Empty lines are skipped; anything else that is not a label and an integer item raises ValueError with its line number."""
@@ -289,6 +339,11 @@ def train(argv=None):
         raise NotImplementedError('--because runs on one GPU (the sharded drivers write no because-* files): use --world_size 1')
     if args.audience != 0 and int(args.world_size) > 1:
         raise NotImplementedError('--audience runs on one GPU (the sharded drivers write no audience-* files): use --world_size 1')
+    if args.warm_items is not None and int(args.world_size) > 1:
+        raise NotImplementedError('--warm_items runs on one GPU (the sharded drivers write no warm-* files): use --world_size 1')
+    if args.warm_items is not None and args.new_items is not None:                  # a row past the table: before anything is trained
+        import numpy as np
+        read_warm_items(args.warm_items, int(np.load(args.new_items[0], mmap_mode='r').shape[0]))
     if args.because != 0 and args.top_k > 1024:
         raise ValueError('--because runs on the device only (top_k <= 1024): there is no host form')
     if args.new_items is not None and args.dtype == 'fp8':
@@ -324,6 +379,8 @@ def train(argv=None):
         print('ITERATION %d/%d WITH REGULARIZATION: %f' % (it + 1, len(list(args.list_of_regs)), current_reg))
         data = DataLoader(params=args)
         check_audience_items(args, data.num_items)
+        if args.warm_items is not None and any(u >= data.num_users for who in read_warm_items(args.warm_items) for u in who):
+            raise ValueError('--warm_items: a buyer is outside the %d users of the dataset' % data.num_users)
         print("Training {0} on {1}".format(args.rec, args.dataset))
         print("Parameters:")
         args.reg = current_reg                                                                  # train_rec.py:69

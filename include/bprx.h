@@ -372,6 +372,55 @@ BPRX_API int bprx_audience_block(bprx_handle *h, const float *Pq, int64_t nq, in
 BPRX_API int bprx_topk_rows_masked(bprx_handle *h, int64_t nrows, int32_t width, float *scores, const int64_t *list_ptr,
                                    const int32_t *list_items, int32_t K, int32_t *idx, float *val, int32_t *flag, void *stream);
 
+/* ---- BPRMF, VBPR and GradFashion: warm items, new items with first buyers --------------------------------------------------
+   The twin of bprx_fold_in on the item side.  An item outside the catalogue is scored by its picture alone
+   (bprx_score_new_block); once it has buyers, its Gi_r and Bi_r can be fitted with every user-side and catalogue parameter
+   frozen.  New item r owns w = [Gi_r (k) | Bi_r (1)] and, for VBPR, its projection row Pn_r (bprx_project_rows).  Its pairs
+   p in [pair_ptr[r], pair_ptr[r+1]) are triples (u_p, o_p, role_p): a catalogue user, a catalogue item and the role the new item
+   plays against it: role 0, the new item is the positive (the reference's triplet (u, r, o)), s_p = +1; role 1, the negative
+   (the triplet (u, o, r)), s_p = -1.  With n_r pairs, n_pos of them in role 0 and n_neg in role 1:
+       a_p = [Gu_u | 1]
+       v_p = Tu_u.(Pn_r[0:d] - P_o[0:d]) + (Pn_r[d] - P_o[d]) - Bi_o - Gu_u.Gi_o          (d = 0: -Bi_o - Gu_u.Gi_o)
+       D_p = s_p a_p                 dc_p = s_p v_p                 (formed once: nothing in them moves)
+       rv  = [n_r, ..., n_r | n_pos + c_neg n_neg]                  c_neg: 0.1 (VBPR.py:125, BPRMF.py:111: the bias of a negative
+                                                                    is regularised by reg / 10); a factored handle: its neg_bias_reg
+       w starts at the caller's row; for t = 1 .. steps:
+         x_p = w.D_p + dc_p          s = sigmoid(-clip(x_p, -80, 1e8))                    (inclusive bounds, no gradient outside)
+         g = sum_p (-s D_p) + 2 reg rv o w                                                (summed in pair order)
+         loss_t = sum_p softplus(-clip(x_p)) + reg sum(rv o w o w)
+         BPRX_OPT_SGD: w <- w - lr g;  BPRX_OPT_ADAM_TF23: the sparse-variable rule, slots from zero, lr_t as for bprx_fold_in
+   i.e. one train_step of the reference on a batch in which the new item occurs once per triplet, in either role: for steps = 1,
+   started from a catalogue item's own Gi / Bi / P row, the row moves as bprx_step on that batch moves it.  Both roles matter: with
+   the new item only ever the positive nothing but the regulariser holds Bi_r down.
+   Plain sgd sums the batch loss: the curvature along the bias is up to 0.25 n_r, and the iteration oscillates once
+   lr 0.25 n_r (1 + |Gu|^2) passes 2 (lr = 0.02 with 200 pairs already does).  Adam, the reference's optimiser, does not care.  The
+   call is for first buyers, not for refitting bestsellers.
+   bprx_fold_in_items: pair_ptr int64 [n+1], user / other / role int32 (device); Pn fp32 [n, PS] from bprx_project_rows (NULL iff
+   d == 0); Gi_rows fp32 [n, k] and Bi_rows fp32 [n] in / out; loss fp32 [n] or NULL: loss_steps, before the last update.  An item
+   without pairs keeps its rows and has loss 0.  lr, reg, optimizer are the call's.
+   Handles: a bound BPRMF or VBPR handle, plain or factored, fp32 or bf16 features.  BPRX_E_INVALID for a NULL handle, an ACF or
+   AttentiveFashion handle, an fp8 handle, a NULL pointer, n < 0, steps < 1, an unknown optimizer, k + 1 > 1024, k + d > 1024;
+   BPRX_E_STATE for an unbound handle; n == 0: BPRX_OK.  User and item ids out of range and a role other than 0 or 1 are clamped
+   and reported by bprx_sync_check (BPRX_E_RANGE).  The call enters like bprx_fold_in (settles a pending dense update, brings lazy
+   adam_tf23 rows up to date, makes P current); apart from that it writes its outputs only and allocates nothing.  No atomics: an
+   item's result depends on its own pairs, its start row and the tables only -- not on n, on its position, or on BPRX_FOLD_CACHE
+   (0: every step forms D_p and dc_p again instead of keeping them in LDS where an item's pairs fit). */
+BPRX_API int bprx_fold_in_items(bprx_handle *h, const int64_t *pair_ptr, const int32_t *user, const int32_t *other, const int32_t *role,
+                                int64_t n, const float *Pn, int32_t steps, float lr, float reg, int32_t optimizer, float *Gi_rows,
+                                float *Bi_rows, float *loss, void *stream);
+/* The full score of n caller-owned item rows: out fp32 [(u1-u0), n], out[u][j] = Bi_j + Gu_u.Gi_j + Tu_u.Pn_j[0:d] + Pn_j[d]
+   (Gi_rows [n, k], Bi_rows [n], Pn [n, PS] or NULL iff d == 0).  bprx_score_block's kernels given the caller's rows (the non-MFMA
+   one for an odd k or d): a slice of the catalogue's own Gi / Bi / P gives the bits of those columns of bprx_score_block, zero
+   Gi / Bi rows give the bits of bprx_score_new_block for even k, d.  0 <= u0 <= u1 <= num_users, 0 <= n < 2^31.  Handles and errors as
+   for bprx_fold_in_items; the call brings lazy adam_tf23 rows and the [E|Bp]^T image up to date and writes its output only. */
+BPRX_API int bprx_score_warm_block(bprx_handle *h, int32_t u0, int32_t u1, const float *Gi_rows, const float *Bi_rows, const float *Pn,
+                                   int64_t n, float *out, void *stream);
+/* The same item-major: out fp32 [(q1-q0), num_users], out[r][u] = the score above of row q0 + r: bprx_audience_block's kernel
+   given the caller's rows (always the MFMA path; bit for bit bprx_score_warm_block's out[u][q] for even k and d).
+   0 <= q0 <= q1 <= n < 2^31, q1 - q0 <= 65535 * 128. */
+BPRX_API int bprx_audience_warm_block(bprx_handle *h, const float *Gi_rows, const float *Bi_rows, const float *Pn, int64_t n, int64_t q0,
+                                      int64_t q1, float *out, void *stream);
+
 /* ---- BPRMF, VBPR and GradFashion: diversified lists, greedy Maximal Marginal Relevance over a top-N pool -------------------
    "K of the N best that are good and unlike the picks above them".  One list has the pool (id_c, v_c), c = 0 .. N-1, best first,
    as bprx_topk / bprx_topk_lists / bprx_topk_rows return it with K = N.  A slot with id_c < 0 or v_c == -inf is no candidate;
