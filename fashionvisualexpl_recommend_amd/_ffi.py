@@ -143,6 +143,10 @@ def lib():
         "bprx_af_score_block": (C.c_int, [vp, C.c_int32, C.c_int32, vp, vp, vp]),
         "bprx_af_fold_in": (C.c_int, [vp, vp, vp, vp, i64, i32, f32, f32, i32, vp, vp, vp]),
         "bprx_af_score_rows_block": (C.c_int, [vp, vp, i64, i64, i64, vp, vp, vp]),
+        "bprx_af_encode_new": (C.c_int, [vp, vp, vp, vp, i64, vp, vp]),
+        "bprx_af_fold_in_items": (C.c_int, [vp, vp, vp, vp, vp, i64, vp, i32, f32, f32, i32, vp, vp, vp, vp]),
+        "bprx_af_score_warm_block": (C.c_int, [vp, C.c_int32, C.c_int32, vp, vp, i64, vp, vp, vp]),
+        "bprx_af_audience_block": (C.c_int, [vp, vp, vp, i64, i64, i64, vp, vp, vp]),
         "bprx_af_dropout_mask": (C.c_int, [vp, i64, i64, vp, vp]),
         "bprx_af_get_step": (i64, [vp]),
         "bprx_af_set_step": (C.c_int, [vp, i64]),
@@ -220,7 +224,8 @@ def lib():
 
 
 EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error", "bprx_live_device_allocs", "bprx_bind_tables", "bprx_bind_factored", "bprx_explain_pairs", "bprx_feat_explain", "bprx_proj_stride", "bprx_project_rows", "bprx_score_new_block", "bprx_topk_rows", "bprx_feat_explain_new", "bprx_fold_in", "bprx_score_rows_block", "bprx_topk_lists", "bprx_sim_rnorm", "bprx_sim_block", "bprx_audience_block", "bprx_topk_rows_masked", "bprx_fold_in_items", "bprx_score_warm_block", "bprx_audience_warm_block", "bprx_diversify", "bprx_because", "bprx_bind_acf", "bprx_acf_profiles", "bprx_acf_explain", "bprx_acf_set_gradient", "bprx_acf_get_gradient", "bprx_acf_fold_in", "bprx_acf_profile_rows", "bprx_acf_score_rows_block", "bprx_bind_attentive", "bprx_af_encode", "bprx_af_attention_pairs", "bprx_af_explain",
-           "bprx_af_score_block", "bprx_af_fold_in", "bprx_af_score_rows_block", "bprx_af_dropout_mask", "bprx_af_get_step", "bprx_af_set_step", "bprx_set_hyper", "bprx_tables_dirty",
+           "bprx_af_score_block", "bprx_af_fold_in", "bprx_af_score_rows_block", "bprx_af_encode_new", "bprx_af_fold_in_items",
+           "bprx_af_score_warm_block", "bprx_af_audience_block", "bprx_af_dropout_mask", "bprx_af_get_step", "bprx_af_set_step", "bprx_set_hyper", "bprx_tables_dirty",
            "bprx_set_adam_step", "bprx_get_adam_step", "bprx_adam_is_lazy", "bprx_sync_adam", "bprx_score_pairs", "bprx_step", "bprx_step_begin",
            "bprx_step_begin_sparse", "bprx_step_begin_dense", "bprx_sum_dense_parts",
            "bprx_dense_grad", "bprx_step_end", "bprx_step_project", "bprx_user_grad", "bprx_clear_user_grad", "bprx_item_grad", "bprx_clear_item_grad",

@@ -21,6 +21,9 @@
 //                     user's diag(g_u) W_1 staged in LDS, relu . W_2, 3-way softmax and the score in the epilogue
 //   k_af_fold         bprx_af_fold_in: one workgroup per new user, one wave per pair: attention forward + backward for the user's
 //                     row only, the item side and the encodings frozen, the row's optimiser steps in registers
+//   k_af_item_pairs   bprx_af_fold_in_items: one wave per pair of a new item, two attention forwards -> the pair's (D_p, dc_p) of
+//                     the linear fit in Gi_r (the step loop is k_af_fold_items, bprx_foldin.hip)
+//   k_af_block<., TR> bprx_af_audience_block: the same block for an item window, stored item-major
 #include <climits>
 
 #include "bprx_internal.h"
@@ -799,9 +802,11 @@ __global__ __launch_bounds__(256) void k_af_update(AfDense T, int adam, float lr
 // LDS: Ws[KP][HP] = g_u[c] W_1[c][j] (zero padded), b1s[HP], w2s[HP], gus[KP].  The MFMA runs transposed,
 // hidden^T [HP, 32 items] = Ws^T . C_l^T, so that a lane holds 16 hidden units per tile of ONE item (column = lane & 31): the
 // relu . W_2 sum stays in the lane, one exchange between the lane halves finishes it.  Lane half hb takes k in [hb KP/2, (hb+1) KP/2).
-template <int NJ>
+// Call [3, I, k] and A.Gi [I, k] are the item rows: the catalogue's, or a caller's (bprx_af_score_warm_block).  TR (bprx_af_audience_block):
+// the same arithmetic per (u, item) for the items [q0, q1) only, stored item-major, out[(item - q0) * ldo + u] with ldo = num_users.
+template <int NJ, bool TR>
 __global__ __launch_bounds__(256) void k_af_block(AfAtt A, const float *__restrict__ Call, int I, int u0, int KP,
-                                                  float *__restrict__ out, float *__restrict__ alpha) {
+                                                  float *__restrict__ out, float *__restrict__ alpha, int q0, int q1, int64_t ldo) {
   constexpr int HP = 32 * NJ;
   extern __shared__ float sm[];
   float *Ws = sm, *b1s = Ws + (size_t)KP * HP, *w2s = b1s + HP, *gus = w2s + HP;
@@ -817,10 +822,11 @@ __global__ __launch_bounds__(256) void k_af_block(AfAtt A, const float *__restri
   __syncthreads();
   const float b2 = A.b2[0];
   const bool vec = (k % 8) == 0;                 // KP == k: float4 rows
-  const int64_t tiles = ((int64_t)I + 127) / 128;
+  const int64_t first = TR ? q0 : 0, end = TR ? q1 : I;
+  const int64_t tiles = (end - first + 127) / 128;
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const int64_t item = tile * 128 + w * 32 + it;
-    const bool ok = item < I;
+    const int64_t item = first + tile * 128 + w * 32 + it;
+    const bool ok = item < end;
     const int64_t irow = ok ? item : 0;
     const float *gi = A.Gi + irow * k + hb * KH;
     float a[3], t[3];
@@ -867,7 +873,7 @@ __global__ __launch_bounds__(256) void k_af_block(AfAtt A, const float *__restri
     float al[3];
     af_softmax3(a, al);
     if (ok && hb == 0) {
-      const int64_t o = ub * I + item;
+      const int64_t o = TR ? (item - first) * ldo + u : ub * I + item;
       out[o] = al[0] * t[0] + al[1] * t[1] + al[2] * t[2];
       if (alpha) { alpha[o * 3] = al[0]; alpha[o * 3 + 1] = al[1]; alpha[o * 3 + 2] = al[2]; }
     }
@@ -1058,6 +1064,79 @@ __global__ __launch_bounds__(256) void k_af_fold(AfFold F) {
   }
 }
 
+// ---- items the model was not trained on, once they have first buyers (bprx_af_fold_in_items) ----------------------------------
+// alpha is computed from g_u and the encodings only, so x_ur = Gi_r . m(u, r) is linear in the new item's row: with everything
+// else frozen a pair is the (D_p, dc_p) of bprx_fold_in_items' linear-logistic fit, formed ONCE here, one wave per pair; the step
+// loop (k_af_fold_items, bprx_foldin.hip) reads them from `work` [pairs, KW] = [D_p (k) | dc_p | zeros].
+// LDS of a wave (8k floats): g_u | the new item's three encoding rows | the other item's three rows from Call | Gi_o.
+struct AfItemPairs {
+  AfAtt A;                        // C = Call [3, I, k]; Gu, Gi the bound tables
+  const float *Cn;                // [3, n, k] encodings of the new items
+  int U, I;
+  int64_t n;
+  const int64_t *ptr;             // [n + 1]
+  const int32_t *user, *other, *role;
+  float *work;
+  int KW;
+  int32_t *errflag;
+};
+
+// D_p and dc_p of one pair from the wave's LDS rows; the one place a pair is formed (contraction off: the same roundings wherever
+// it is inlined).  sgn = +1 (role 0) or -1 (role 1): a sign flip of either output, exact.
+__device__ __forceinline__ void af_item_pair(const AfAtt &A, const float *gu, const float *cr, const float *co, const float *gio, float sgn,
+                                             int lane, float *__restrict__ row, int KW) {
+#pragma clang fp contract(off)
+  const int k = A.k;
+  float a[3], alr[3], alo[3];
+  af_att_fwd(A, gu, cr, lane, a, nullptr, 0, 0);
+  af_softmax3(a, alr);
+  af_att_fwd(A, gu, co, lane, a, nullptr, 0, 0);
+  af_softmax3(a, alo);
+  float t[3] = {0.f, 0.f, 0.f};
+  for (int c = lane; c < k; c += 64) {
+    const float wf = alr[0] * cr[c] + alr[1] * cr[k + c] + alr[2] * cr[2 * k + c];      // (the wf form of k_af_pairs)
+    row[c] = sgn * (gu[c] * wf);
+    const float pg = gu[c] * gio[c];
+#pragma unroll
+    for (int l = 0; l < 3; ++l) t[l] = fmaf(co[l * k + c], pg, t[l]);                    // (the epilogue form of k_af_block)
+  }
+#pragma unroll
+  for (int l = 0; l < 3; ++l) t[l] = wave_sum(t[l]);
+  const float xo = alo[0] * t[0] + alo[1] * t[1] + alo[2] * t[2];
+  for (int c = k + lane; c < KW; c += 64) row[c] = c == k ? -sgn * xo : 0.f;
+}
+
+// Waves walk the pairs with the grid's stride (the number of pairs is ptr[n], on the device); a pair finds its item by a search of ptr
+__global__ __launch_bounds__(256) void k_af_item_pairs(AfItemPairs X) {
+  extern __shared__ float sm[];
+  const AfAtt &A = X.A;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, k = A.k;
+  float *gu = sm + (size_t)w * 8 * k, *cr = gu + k, *co = cr + 3 * k, *gio = co + 3 * k;
+  const int64_t P = X.ptr[X.n];
+  for (int64_t p = (int64_t)blockIdx.x * 4 + w; p < P; p += (int64_t)gridDim.x * 4) {      // (wave-uniform)
+    int64_t lo = 0, hi = X.n;                                // the item r with ptr[r] <= p < ptr[r + 1]: the last r with ptr[r] <= p
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (X.ptr[mid] <= p) lo = mid; else hi = mid;
+    }
+    const int64_t r = lo;
+    const int u = clamp_index(X.user[p], X.U, X.errflag, 1), o = clamp_index(X.other[p], X.I, X.errflag, 2);
+    const int role = clamp_index(X.role[p], 2, X.errflag, 2);
+    wave_sync();                                             // the previous pair's reads of this area are done
+    for (int c = lane; c < k; c += 64) {
+      gu[c] = A.Gu[(int64_t)u * k + c];
+      gio[c] = A.Gi[(int64_t)o * k + c];
+#pragma unroll
+      for (int l = 0; l < 3; ++l) {
+        cr[l * k + c] = X.Cn[((int64_t)l * X.n + r) * k + c];
+        co[l * k + c] = A.C[((int64_t)l * A.ldr + o) * k + c];
+      }
+    }
+    wave_sync();
+    af_item_pair(A, gu, cr, co, gio, role ? -1.f : 1.f, lane, X.work + p * X.KW, X.KW);
+  }
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------
 static AfDrop af_drop(const AfState *S, int64_t step, bool training) {
   AfDrop d;
@@ -1085,25 +1164,30 @@ static int af_gemm(bprx_handle *h, hipStream_t s, bool ta, bool tb, const float 
   return BPRX_OK;
 }
 
-// The three encodings of rows 0..n (items S->rowitem[r]) into Cout [3, ldr, k].  dedupe: conv only on the owner rows (islot)
-static int af_encode_rows(bprx_handle *h, int64_t n, bool dedupe, const AfDrop &d, float *Cout, int64_t ldr, hipStream_t s) {
+// The per-item inputs the encoders read, indexed by S->rowitem: the bound tables, or a chunk of a caller's (bprx_af_encode_new)
+struct AfInputs { const uint8_t *edges; const float *color, *cls; };
+static AfInputs af_bound_inputs(const AfState *S) { return AfInputs{S->a.edges, S->a.color, S->a.cls}; }
+
+// The three encodings of rows 0..n (items S->rowitem[r] of `in`) into Cout [3, ldr, k].  dedupe: conv only on the owner rows (islot)
+static int af_encode_rows(bprx_handle *h, const AfInputs &in, int64_t n, bool dedupe, const AfDrop &d, float *Cout, int64_t ldr,
+                          hipStream_t s) {
   AfState *S = h->af;
   const int k = S->k;
   const int32_t *islot = dedupe ? S->islot : nullptr;
   int rc;
   {
     BprxProfScope ps(h, BPRX_PHASE_PROJ_FWD, s);
-    hipLaunchKernelGGL(k_af_conv<AF_CONV_FWD>, dim3((unsigned)n), dim3(256), 0, s, S->a.edges, S->a.w[BPRX_AF_EDG_CW], S->a.w[BPRX_AF_EDG_CB],
+    hipLaunchKernelGGL(k_af_conv<AF_CONV_FWD>, dim3((unsigned)n), dim3(256), 0, s, in.edges, S->a.w[BPRX_AF_EDG_CW], S->a.w[BPRX_AF_EDG_CB],
                        S->rowitem, islot, n, S->pool, (const float *)nullptr, (float *)nullptr);
     BPRX_LAUNCH_CHECK(h, "k_af_conv<fwd>");
   }
   hipLaunchKernelGGL(k_af_pooldrop, dim3(bprx_blocks(n * (AF_CH / 4), 256)), dim3(256), 0, s, S->pool, S->rowitem, islot, n, d, S->PD);
   BPRX_LAUNCH_CHECK(h, "k_af_pooldrop");
-  if ((rc = af_gemm(h, s, false, false, S->a.color, S->Dc, S->rowitem, S->a.w[BPRX_AF_COL_W1], AF_HID, S->Hc, AF_HID, (int)n, AF_HID,
+  if ((rc = af_gemm(h, s, false, false, in.color, S->Dc, S->rowitem, S->a.w[BPRX_AF_COL_W1], AF_HID, S->Hc, AF_HID, (int)n, AF_HID,
                     S->Dc, 1, S->a.w[BPRX_AF_COL_B1], 0, &d))) return rc;
   if ((rc = af_gemm(h, s, false, false, S->Hc, AF_HID, nullptr, S->a.w[BPRX_AF_COL_W2], k, Cout, k, (int)n, k, AF_HID))) return rc;
   if ((rc = af_gemm(h, s, false, false, S->PD, AF_CH, nullptr, S->a.w[BPRX_AF_EDG_W2], k, Cout + ldr * k, k, (int)n, k, AF_CH))) return rc;
-  if ((rc = af_gemm(h, s, false, false, S->a.cls, S->Dk, S->rowitem, S->a.w[BPRX_AF_CLS_W1], AF_HID, S->Hk, AF_HID, (int)n, AF_HID,
+  if ((rc = af_gemm(h, s, false, false, in.cls, S->Dk, S->rowitem, S->a.w[BPRX_AF_CLS_W1], AF_HID, S->Hk, AF_HID, (int)n, AF_HID,
                     S->Dk, 1, S->a.w[BPRX_AF_CLS_B1], 2, &d))) return rc;
   return af_gemm(h, s, false, false, S->Hk, AF_HID, nullptr, S->a.w[BPRX_AF_CLS_W2], k, Cout + 2 * ldr * k, k, (int)n, k, AF_HID);
 }
@@ -1147,7 +1231,7 @@ static int af_step_body(bprx_handle *h, const int32_t *user, const int32_t *pos,
   hipLaunchKernelGGL(k_af_claim, dim3(bprx_blocks(R, 256)), dim3(256), 0, s, pos, neg, B, R, user, B, I, U, S->rowitem, S->rowuser,
                      S->islot, S->uslot, h->errflag);
   BPRX_LAUNCH_CHECK(h, "k_af_claim");
-  if ((rc = af_encode_rows(h, R, true, d, S->C, S->R, s))) return rc;
+  if ((rc = af_encode_rows(h, af_bound_inputs(S), R, true, d, S->C, S->R, s))) return rc;
   {
     BprxProfScope ps(h, BPRX_PHASE_TRIPLET, s);
     AfTrip T;
@@ -1239,7 +1323,7 @@ int bprx_af_pairs(bprx_handle *h, const int32_t *user, const int32_t *item, int6
                      S->rowitem, S->rowuser, (int32_t *)nullptr, (int32_t *)nullptr, h->errflag);
   BPRX_LAUNCH_CHECK(h, "k_af_claim");
   const AfDrop d = af_drop(S, 0, false);
-  if ((rc = af_encode_rows(h, n, false, d, S->C, S->R, s))) return rc;
+  if ((rc = af_encode_rows(h, af_bound_inputs(S), n, false, d, S->C, S->R, s))) return rc;
   hipLaunchKernelGGL(k_af_pairs, dim3(bprx_blocks(n, 4)), dim3(256), 16 * sizeof(float) * (size_t)S->k, s, af_att(h, S->C, S->R), S->rowuser,
                      S->rowitem, n, x, alpha);
   BPRX_LAUNCH_CHECK(h, "k_af_pairs");
@@ -1256,7 +1340,7 @@ static int af_explain_body(bprx_handle *h, const int32_t *user, const int32_t *i
   BPRX_LAUNCH_CHECK(h, "k_af_claim");
   // x and alpha: the kernels of bprx_af_attention_pairs; the conv runs on the owner rows only and gives the same bits per item
   const AfDrop d = af_drop(S, 0, false);
-  if ((rc = af_encode_rows(h, n, true, d, S->C, S->R, s))) return rc;
+  if ((rc = af_encode_rows(h, af_bound_inputs(S), n, true, d, S->C, S->R, s))) return rc;
   hipLaunchKernelGGL(k_af_pairs, dim3(bprx_blocks(n, 4)), dim3(256), 16 * sizeof(float) * (size_t)S->k, s, af_att(h, S->C, S->R), S->rowuser,
                      S->rowitem, n, x, alpha);
   BPRX_LAUNCH_CHECK(h, "k_af_pairs");
@@ -1299,7 +1383,7 @@ static int af_encode_many(bprx_handle *h, const int32_t *items, int64_t n, float
       hipLaunchKernelGGL(k_af_iota, dim3(bprx_blocks(m, 256)), dim3(256), 0, s, S->rowitem, m, (int32_t)r0);
     BPRX_LAUNCH_CHECK(h, "k_af_claim");
     int rc;
-    if ((rc = af_encode_rows(h, m, false, d, S->C, S->R, s))) return rc;
+    if ((rc = af_encode_rows(h, af_bound_inputs(S), m, false, d, S->C, S->R, s))) return rc;
     for (int l = 0; l < 3; ++l)
       BPRX_HIP(h, hipMemcpyAsync(out + ((int64_t)l * ld + r0) * S->k, S->C + (int64_t)l * S->R * S->k, m * kb, hipMemcpyDeviceToDevice, s));
   }
@@ -1316,29 +1400,41 @@ static int af_call_current(bprx_handle *h, hipStream_t s) {
   return rc;
 }
 
+// k_af_block for the users [u0, u1) of A.Gu against the I item rows (Call, A.Gi): user-major out [(u1 - u0), I], or with tr the
+// items [q0, q1) item-major, out [(q1 - q0), ldo] (u0 = 0: the column of a user is its id)
+static int af_block_run(bprx_handle *h, const AfAtt &A, const float *Call, int I, int32_t u0, int32_t u1, float *out, float *alpha,
+                        hipStream_t s, bool tr = false, int q0 = 0, int q1 = 0, int64_t ldo = 0) {
+  AfState *S = h->af;
+  const int KP = (S->k + 7) / 8 * 8, NJ = (S->h + 31) / 32;
+  const size_t lds = sizeof(float) * ((size_t)KP * 32 * NJ + 64 * NJ + KP);
+  const int64_t tiles = tr ? ((int64_t)q1 - q0 + 127) / 128 : ((int64_t)I + 127) / 128;
+  for (int32_t c0 = u0; c0 < u1; c0 += 32768) {              // gridDim.y holds the users: at most 65 535 per launch
+    const int32_t c1 = u1 - c0 < 32768 ? u1 : c0 + 32768;
+    const dim3 grid((unsigned)(tiles < 16 ? tiles : 16), (unsigned)(c1 - c0));
+    float *o = tr ? out : out + (int64_t)(c0 - u0) * I, *al = !alpha || tr ? alpha : alpha + (int64_t)(c0 - u0) * I * 3;
+#define AF_BLOCK(NJ_)                                                                                                         \
+  if (tr) hipLaunchKernelGGL((k_af_block<NJ_, true>), grid, dim3(256), lds, s, A, Call, I, c0, KP, o, al, q0, q1, ldo);      \
+  else hipLaunchKernelGGL((k_af_block<NJ_, false>), grid, dim3(256), lds, s, A, Call, I, c0, KP, o, al, 0, 0, (int64_t)0);
+    switch (NJ) {
+      case 1: AF_BLOCK(1) break;
+      case 2: AF_BLOCK(2) break;
+      case 3: AF_BLOCK(3) break;
+      default: AF_BLOCK(4) break;
+    }
+#undef AF_BLOCK
+    BPRX_LAUNCH_CHECK(h, "k_af_block");
+  }
+  return BPRX_OK;
+}
+
 int bprx_af_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, float *alpha, hipStream_t s, const float *Gu_rows) {
   AfState *S = h->af;
   const int I = h->cfg.num_items;
   int rc;
   if ((rc = af_call_current(h, s))) return rc;
-  const int KP = (S->k + 7) / 8 * 8, NJ = (S->h + 31) / 32;
-  const size_t lds = sizeof(float) * ((size_t)KP * 32 * NJ + 64 * NJ + KP);
-  const int64_t tiles = ((int64_t)I + 127) / 128;
   AfAtt A = af_att(h, S->Call, I);
   if (Gu_rows) A.Gu = Gu_rows;
-  for (int32_t c0 = u0; c0 < u1; c0 += 32768) {              // gridDim.y holds the users: at most 65 535 per launch
-    const int32_t c1 = u1 - c0 < 32768 ? u1 : c0 + 32768;
-    const dim3 grid((unsigned)(tiles < 16 ? tiles : 16), (unsigned)(c1 - c0));
-    float *o = out + (int64_t)(c0 - u0) * I, *al = alpha ? alpha + (int64_t)(c0 - u0) * I * 3 : nullptr;
-    switch (NJ) {
-      case 1: hipLaunchKernelGGL(k_af_block<1>, grid, dim3(256), lds, s, A, S->Call, I, c0, KP, o, al); break;
-      case 2: hipLaunchKernelGGL(k_af_block<2>, grid, dim3(256), lds, s, A, S->Call, I, c0, KP, o, al); break;
-      case 3: hipLaunchKernelGGL(k_af_block<3>, grid, dim3(256), lds, s, A, S->Call, I, c0, KP, o, al); break;
-      default: hipLaunchKernelGGL(k_af_block<4>, grid, dim3(256), lds, s, A, S->Call, I, c0, KP, o, al); break;
-    }
-    BPRX_LAUNCH_CHECK(h, "k_af_block");
-  }
-  return BPRX_OK;
+  return af_block_run(h, A, S->Call, I, u0, u1, out, alpha, s);
 }
 
 void bprx_af_invalidate(bprx_handle *h) {
@@ -1545,6 +1641,104 @@ extern "C" int bprx_af_fold_in(bprx_handle *h, const int64_t *pair_ptr, const in
   hipLaunchKernelGGL(k_af_fold, dim3((unsigned)n), dim3(64 * NW), lds, s, F);
   BPRX_LAUNCH_CHECK(h, "k_af_fold");
   return BPRX_OK;
+}
+
+// ---- new items: encodings of caller-owned inputs, the warm fit, and the blocks for caller-owned item rows (include/bprx.h) ----
+extern "C" int bprx_af_encode_new(bprx_handle *h, const uint8_t *edges, const float *color, const float *cls, int64_t n, float *out,
+                                  void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (n < 0 || n >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "af_encode_new: n = %lld out of range", (long long)n);
+  if (n && (!edges || !color || !cls || !out)) BPRX_FAIL(h, BPRX_E_INVALID, "af_encode_new: null pointer");
+  if ((uintptr_t)edges & 15) BPRX_FAIL(h, BPRX_E_INVALID, "af_encode_new: edges must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc0 = bprx_enter(h, "af_encode_new", NEED_BOUND, KIND_AF, s);
+  if (rc0 || n == 0) return rc0;
+  AfState *S = h->af;
+  const AfDrop d = af_drop(S, 0, false);
+  const size_t kb = (size_t)S->k * sizeof(float);
+  for (int64_t r0 = 0; r0 < n; r0 += S->R) {                 // the chunks of bprx_af_encode: row r of a chunk reads row r of its inputs
+    const int64_t m = n - r0 < S->R ? n - r0 : S->R;
+    hipLaunchKernelGGL(k_af_iota, dim3(bprx_blocks(m, 256)), dim3(256), 0, s, S->rowitem, m, (int32_t)0);
+    BPRX_LAUNCH_CHECK(h, "k_af_iota");
+    const AfInputs in = {edges + r0 * (int64_t)(AF_IMG * AF_IMG), color + r0 * S->Dc, cls + r0 * S->Dk};
+    int rc;
+    if ((rc = af_encode_rows(h, in, m, false, d, S->C, S->R, s))) return rc;
+    for (int l = 0; l < 3; ++l)
+      BPRX_HIP(h, hipMemcpyAsync(out + ((int64_t)l * n + r0) * S->k, S->C + (int64_t)l * S->R * S->k, m * kb, hipMemcpyDeviceToDevice, s));
+  }
+  return BPRX_OK;
+}
+
+// float4 rows in k_af_block where k is a multiple of 8: the caller's item rows must then start on 16 bytes, as the bound tables do
+static bool af_rows_aligned(const AfState *S, const float *C_rows, const float *Gi_rows) {
+  return (S->k % 8) != 0 || ((((uintptr_t)C_rows | (uintptr_t)Gi_rows) & 15) == 0);
+}
+
+constexpr unsigned AF_ITEM_PAIR_GRID = 2048;                  // workgroups of k_af_item_pairs: four waves each, walking the pairs
+
+extern "C" int bprx_af_fold_in_items(bprx_handle *h, const int64_t *pair_ptr, const int32_t *user, const int32_t *other, const int32_t *role,
+                                     int64_t n, const float *C_rows, int32_t steps, float lr, float reg, int32_t optimizer, float *Gi_rows,
+                                     float *loss, float *work, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (n < 0 || n >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in_items: n = %lld out of range", (long long)n);
+  if (steps < 1) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in_items: steps = %d < 1", steps);
+  if (optimizer != BPRX_OPT_SGD && optimizer != BPRX_OPT_ADAM_TF23) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in_items: optimizer %d", optimizer);
+  if (!pair_ptr) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in_items: null pointer");
+  if (n && (!user || !other || !role || !Gi_rows || !C_rows || !work)) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in_items: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  int rc = bprx_enter(h, "af_fold_in_items", NEED_BOUND, KIND_AF, s);
+  if (rc || n == 0) return rc;
+  if ((rc = af_call_current(h, s))) return rc;               // the encodings the scores are computed from
+  AfState *S = h->af;
+  const bprx_config &c = h->cfg;
+  AfItemPairs X;
+  X.A = af_att(h, S->Call, c.num_items);
+  X.Cn = C_rows; X.U = c.num_users; X.I = c.num_items; X.n = n;
+  X.ptr = pair_ptr; X.user = user; X.other = other; X.role = role;
+  X.work = work; X.KW = (S->k + 1 + 3) / 4 * 4; X.errflag = h->errflag;
+  // 8k floats per wave: 60 KB at k = 480, the widest shape bprx_bind_attentive accepts (k <= 512 fits 64 KB)
+  hipLaunchKernelGGL(k_af_item_pairs, dim3(AF_ITEM_PAIR_GRID), dim3(256), 32 * sizeof(float) * (size_t)S->k, s, X);
+  BPRX_LAUNCH_CHECK(h, "k_af_item_pairs");
+  return bprx_launch_af_fold_items(h, pair_ptr, n, work, X.KW, S->k, steps, optimizer == BPRX_OPT_ADAM_TF23, lr, reg, Gi_rows, loss, s);
+}
+
+extern "C" int bprx_af_score_warm_block(bprx_handle *h, int32_t u0, int32_t u1, const float *C_rows, const float *Gi_rows, int64_t n,
+                                        float *scores, float *alpha, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (u0 < 0 || u1 > h->cfg.num_users || u0 > u1) BPRX_FAIL(h, BPRX_E_INVALID, "af_score_warm_block: bad user range [%d,%d)", u0, u1);
+  if (n < 0 || n >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "af_score_warm_block: n = %lld out of range", (long long)n);
+  const bool work = n != 0 && u0 != u1;
+  if (work && (!C_rows || !Gi_rows || !scores)) BPRX_FAIL(h, BPRX_E_INVALID, "af_score_warm_block: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = bprx_enter(h, "af_score_warm_block", NEED_BOUND, KIND_AF, s);
+  if (rc || !work) return rc;
+  if (!af_rows_aligned(h->af, C_rows, Gi_rows)) BPRX_FAIL(h, BPRX_E_INVALID, "af_score_warm_block: C_rows and Gi_rows must be 16-byte aligned");
+  AfAtt A = af_att(h, C_rows, n);
+  A.Gi = Gi_rows;
+  return af_block_run(h, A, C_rows, (int)n, u0, u1, scores, alpha, s);
+}
+
+extern "C" int bprx_af_audience_block(bprx_handle *h, const float *C_rows, const float *Gi_rows, int64_t n, int64_t q0, int64_t q1,
+                                      float *scores, float *alpha, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if ((C_rows == nullptr) != (Gi_rows == nullptr)) BPRX_FAIL(h, BPRX_E_INVALID, "af_audience_block: C_rows and Gi_rows are both NULL (the catalogue) or both given");
+  if (n < 0 || n >= ((int64_t)1 << 31) || (!C_rows && n != h->cfg.num_items))
+    BPRX_FAIL(h, BPRX_E_INVALID, "af_audience_block: n = %lld (the catalogue form takes n = num_items)", (long long)n);
+  if (q0 < 0 || q1 > n || q0 > q1) BPRX_FAIL(h, BPRX_E_INVALID, "af_audience_block: bad item range [%lld,%lld) of %lld", (long long)q0, (long long)q1, (long long)n);
+  if (q0 != q1 && !scores) BPRX_FAIL(h, BPRX_E_INVALID, "af_audience_block: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  int rc = bprx_enter(h, "af_audience_block", NEED_BOUND, KIND_AF, s);
+  if (rc || q0 == q1) return rc;
+  AfState *S = h->af;
+  const int U = h->cfg.num_users;
+  if (!C_rows) {
+    if ((rc = af_call_current(h, s))) return rc;
+    return af_block_run(h, af_att(h, S->Call, n), S->Call, (int)n, 0, U, scores, alpha, s, true, (int)q0, (int)q1, U);
+  }
+  if (!af_rows_aligned(S, C_rows, Gi_rows)) BPRX_FAIL(h, BPRX_E_INVALID, "af_audience_block: C_rows and Gi_rows must be 16-byte aligned");
+  AfAtt A = af_att(h, C_rows, n);
+  A.Gi = Gi_rows;
+  return af_block_run(h, A, C_rows, (int)n, 0, U, scores, alpha, s, true, (int)q0, (int)q1, U);
 }
 
 extern "C" int bprx_af_dropout_mask(bprx_handle *h, int64_t step, int64_t n_rows, uint8_t *out, void *stream) {

@@ -1,5 +1,5 @@
 // bprx_foldin.hip -- users the model was not trained on (include/bprx.h: bprx_fold_in), and items with first buyers
-// (bprx_fold_in_items: k_fold_items, further down, with its own notes).
+// (bprx_fold_in_items: k_fold_items, further down, with its own notes; bprx_af_fold_in_items' step loop k_af_fold_items after it).
 //   k_fold_in   n independent small optimisations: the reference's train_step (BPRMF.py:87-125 / VBPR.py:99-144) on a batch made
 //               of ONE user's pairs with every item-side parameter frozen, `steps` times, for each of n caller-owned user rows.
 //
@@ -407,7 +407,139 @@ __global__ __launch_bounds__(64 * FOLD_WAVES) void k_fold_items(FoldItemArgs a) 
   }
 }
 
+// ---- AttentiveFashion items with first buyers (include/bprx.h: bprx_af_fold_in_items) ----
+//   k_af_fold_items   the step loop of k_fold_items for rows that are already formed: k_af_item_pairs (bprx_attentive.hip) has
+//                     written [D_p (k) | dc_p | zeros] of every pair to work [pairs, KW].  New item r owns w = Gi_r (k numbers, no
+//                     bias: the model scores no Bi), rv = n_r for every element.  One wave per item, four per workgroup, the same
+//                     LDS share, groups and fold_group as above: the first pairs that fit are read from work once, the others
+//                     every step (work of a call sits in L2 / the Infinity Cache); both forms hand fold_group the same words.
+struct AfFoldItemArgs {
+  const float *work;                    // [ptr[n], KW]
+  int k, KW;
+  const int64_t *ptr;                   // [n + 1] pairs of item r: [ptr[r], ptr[r + 1])
+  int n, steps, adam;
+  float lr, reg, b1, b2, eps;
+  float *Gi_rows, *loss;                // [n, k] in / out; [n] or nullptr
+  int share;                            // floats of LDS per wave (0: every step reads work)
+};
+
+template <int EPL>
+__global__ __launch_bounds__(64 * FOLD_WAVES) void k_af_fold_items(AfFoldItemArgs a) {
+  constexpr int NP = EPL <= 4 ? 4 : 2;                       // pairs per group, as k_fold_in
+  extern __shared__ __attribute__((aligned(16))) float fold_lds[];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int r = blockIdx.x * FOLD_WAVES + wv;
+  if (r >= a.n) return;                                      // (no workgroup barrier anywhere below)
+  const int64_t p0 = a.ptr[r];
+  const int64_t np64 = a.ptr[r + 1] - p0;
+  if (np64 <= 0) {                                           // no pairs: the row stays, the loss is 0
+    if (lane == 0 && a.loss) a.loss[r] = 0.f;
+    return;
+  }
+  const int np = np64 > INT32_MAX ? INT32_MAX : (int)np64;
+  float w[EPL], m[EPL], v[EPL];
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) {
+    const int col = lane + 64 * e;
+    w[e] = col < a.k ? a.Gi_rows[(size_t)r * a.k + col] : 0.f;
+    m[e] = 0.f; v[e] = 0.f;
+  }
+  const float *rows = a.work + (size_t)p0 * a.KW;
+  float *dls = fold_lds + (size_t)wv * a.share;              // [nc][EPL][64] D, then [nc] dc
+  const int fit = a.share / (64 * EPL + 1);
+  const int nc = np <= fit ? np : fit / NP * NP;
+  float *dcs = dls + (size_t)nc * (64 * EPL);
+
+  // D (elements lane, lane + 64, ... : zero past k) and dc of pair p
+  auto read_pair = [&](int p, float (&dl)[EPL], float &dc) {
+    const float *row = rows + (size_t)p * a.KW;
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+      const int col = lane + 64 * e;
+      dl[e] = col < a.k ? row[col] : 0.f;
+    }
+    dc = row[a.k];
+  };
+
+  for (int p = 0; p < nc; ++p) {
+    float dl[EPL], dc;
+    read_pair(p, dl, dc);
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) dls[((size_t)p * EPL + e) * 64 + lane] = dl[e];
+    if (lane == 0) dcs[p] = dc;
+  }
+  if (nc) wave_sync();                                       // dc: written by lane 0, read by every lane
+
+  const float r2 = 2.f * a.reg * (float)np, r1 = a.reg * (float)np;
+  for (int t = 1; t <= a.steps; ++t) {
+#pragma clang fp contract(off)
+    const bool last = t == a.steps && a.loss != nullptr;
+    float acc[EPL];
+    double lsum = 0.0;
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
+    for (int q0 = 0; q0 < nc; q0 += NP) {
+      const int cnt = min(NP, nc - q0);
+      float dl[NP][EPL], dc[NP];
+#pragma unroll
+      for (int q = 0; q < NP; ++q) {
+        const int src = min(q0 + q, nc - 1);
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) dl[q][e] = dls[((size_t)src * EPL + e) * 64 + lane];
+        dc[q] = dcs[src];
+      }
+      fold_group<EPL, NP>(w, dl, dc, cnt, acc, lsum, last);
+    }
+    for (int q0 = nc; q0 < np; q0 += NP) {                   // (nc is a multiple of NP here: the same groups as from LDS)
+      const int cnt = min(NP, np - q0);
+      float dl[NP][EPL], dc[NP];
+#pragma unroll
+      for (int q = 0; q < NP; ++q) read_pair(min(q0 + q, np - 1), dl[q], dc[q]);   // (a group's tail reads its last pair again)
+      fold_group<EPL, NP>(w, dl, dc, cnt, acc, lsum, last);
+    }
+    if (last) {                                              // loss_T, before the last update, as train_step returns it
+      float s = 0.f;
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) s += r1 * (w[e] * w[e]);
+      s = wave_sum(s);
+      if (lane == 0) a.loss[r] = (float)(lsum + (double)s);
+    }
+    if (a.adam) {
+      const float tt = (float)t;
+      const float lr_t = a.lr * sqrtf(1.0f - powf(a.b2, tt)) / (1.0f - powf(a.b1, tt));
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) adam_elem(w[e], m[e], v[e], acc[e] + r2 * w[e], a.b1, a.b2, lr_t, a.eps);
+    } else {
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) w[e] = w[e] - a.lr * (acc[e] + r2 * w[e]);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) {
+    const int col = lane + 64 * e;
+    if (col < a.k) a.Gi_rows[(size_t)r * a.k + col] = w[e];
+  }
+}
+
 }  // namespace
+
+int bprx_launch_af_fold_items(bprx_handle *h, const int64_t *pair_ptr, int64_t n, const float *work, int KW, int k, int steps, bool adam,
+                              float lr, float reg, float *Gi_rows, float *loss, hipStream_t s) {
+  const bprx_config &c = h->cfg;
+  AfFoldItemArgs a;
+  a.work = work; a.k = k; a.KW = KW; a.ptr = pair_ptr;
+  a.n = (int)n; a.steps = steps; a.adam = adam ? 1 : 0;
+  a.lr = lr; a.reg = reg; a.b1 = c.beta1; a.b2 = c.beta2; a.eps = c.epsilon;
+  a.Gi_rows = Gi_rows; a.loss = loss;
+  a.share = h->fold_cache ? FOLD_ITEM_SHARE : 0;
+  const unsigned grid = (unsigned)((n + FOLD_WAVES - 1) / FOLD_WAVES);
+  const size_t lds = (size_t)a.share * FOLD_WAVES * sizeof(float);
+#define CALL(N) hipLaunchKernelGGL(k_af_fold_items<N>, dim3(grid), dim3(64 * FOLD_WAVES), lds, s, a)
+  EPL_SWITCH((k + 63) / 64, CALL)
+#undef CALL
+  BPRX_LAUNCH_CHECK(h, "k_af_fold_items");
+  return BPRX_OK;
+}
 
 extern "C" int bprx_fold_in(bprx_handle *h, const int64_t *pair_ptr, const int32_t *pos, const int32_t *neg, int64_t n,
                             int32_t steps, float lr, float reg, int32_t optimizer, float *Gu_rows, float *Tu_rows, float *loss,

@@ -421,6 +421,10 @@ int bprx_af_pairs(bprx_handle *h, const int32_t *u, const int32_t *i, int64_t n,
 int bprx_af_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, float *alpha, hipStream_t s, const float *Gu_rows = nullptr);
 void bprx_af_invalidate(bprx_handle *h);
 void bprx_af_free(bprx_handle *h);
+// The step loop of bprx_af_fold_in_items (k_af_fold_items, bprx_foldin.hip, next to the fold_group it shares with k_fold_items):
+// work [pair_ptr[n], KW] holds [D_p (k) | dc_p | zeros] of every pair, Gi_rows [n, k] in / out, loss [n] or nullptr
+int bprx_launch_af_fold_items(bprx_handle *h, const int64_t *pair_ptr, int64_t n, const float *work, int KW, int k, int steps, bool adam,
+                              float lr, float reg, float *Gi_rows, float *loss, hipStream_t s);
 // The item space of bprx_sim_* and bprx_diversify (bprx_eval.hip).  One part of z: n rows of `w` floats, row stride ld (w == 0:
 // the part is absent); z = [g | p].
 struct SimPart {

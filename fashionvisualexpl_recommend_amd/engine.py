@@ -507,6 +507,87 @@ class Engine:
                                                              _addr(x), _addr(al), _stream()))
         return x, al
 
+    # ---- AttentiveFashion: new items with first buyers (include/bprx.h, bprx_af_fold_in_items) ---------------------------------
+    def af_encode_new(self, edges, color, cls):
+        """bprx_af_encode_new: the three dropout-off encodings [3, n, k] of caller-owned inputs: edges uint8 [n, 224, 224], color
+        fp32 [n, Dc] (each row already divided by its own max-abs), cls fp32 [n, Dk] (tensors or arrays; copied to the device)."""
+        Dc, Dk = int(self.af_inputs[1].shape[1]), int(self.af_inputs[2].shape[1])
+        prep = lambda x, dt: torch.as_tensor(x).to(device=self.device, dtype=dt).contiguous()
+        Ed, Xc, Xk = prep(edges, torch.uint8), prep(color, torch.float32), prep(cls, torch.float32)
+        n = int(Ed.shape[0]) if Ed.dim() == 3 else -1
+        if n < 0 or tuple(Ed.shape) != (n, 224, 224) or tuple(Xc.shape) != (n, Dc) or tuple(Xk.shape) != (n, Dk):
+            raise ValueError("af_encode_new: edges [n, 224, 224], color [n, %d], cls [n, %d] expected, got %s, %s, %s"
+                             % (Dc, Dk, tuple(Ed.shape), tuple(Xc.shape), tuple(Xk.shape)))
+        out = torch.empty((3, n, self.k), dtype=torch.float32, device=self.device)
+        _ffi.check(self.h, self.lib.bprx_af_encode_new(self.h, _addr(Ed), _addr(Xc), _addr(Xk), n, _addr(out), _stream()))
+        return out
+
+    def af_work_stride(self):
+        """KW: floats per pair of af_fold_in_items' work rows, k + 1 rounded up to a multiple of 4."""
+        return (self.k + 1 + 3) // 4 * 4
+
+    def _af_item_rows(self, what, C_rows, Gi_rows):
+        """n of the caller-owned item rows C_rows [3, n, k] / Gi_rows [n, k], checked."""
+        ok = lambda t, nd: t is not None and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == nd
+        if not ok(Gi_rows, 2) or not ok(C_rows, 3) or tuple(C_rows.shape) != (3, int(Gi_rows.shape[0]), self.k) \
+                or int(Gi_rows.shape[1]) != self.k:
+            raise ValueError("%s: C_rows [3, n, %d] and Gi_rows [n, %d] must be contiguous fp32 device tensors" % (what, self.k, self.k))
+        return int(Gi_rows.shape[0])
+
+    def af_fold_in_items(self, pair_ptr, user, other, role, steps, C_rows, Gi_rows, lr=None, reg=None, optimizer=None,
+                         want_loss=True, want_work=False):
+        """bprx_af_fold_in_items: `steps` optimiser steps on each row of Gi_rows [n, k] (a contiguous fp32 device tensor, updated
+        IN PLACE) over the pairs (user[p], other[p], role[p]), p in [pair_ptr[r], pair_ptr[r + 1]), of new item r with the
+        encodings C_rows [3, n, k] (af_encode_new): role 0 the new item is the positive against the catalogue item other[p], role 1
+        the negative.  Everything else is frozen, dropout off.  pair_ptr: int64 [n + 1].  lr / reg / optimizer default to the
+        engine's.  The work rows [pairs, af_work_stride()] = [D_p | dc_p | zeros] are allocated here.  Returns loss fp32 [n]
+        (loss_steps, before the last update) or None; with want_work=True (loss, work)."""
+        n = self._af_item_rows("af_fold_in_items", C_rows, Gi_rows)
+        ptr_host = torch.as_tensor(pair_ptr, dtype=torch.int64).cpu()
+        if int(ptr_host.numel()) - 1 != n:
+            raise ValueError("af_fold_in_items: pair_ptr for %d items, rows for %d" % (int(ptr_host.numel()) - 1, n))
+        ptr = ptr_host.to(self.device).contiguous()
+        u_, o_, r_ = (as_index(x, self.device) for x in (user, other, role))
+        if not u_.numel() == o_.numel() == r_.numel():
+            raise ValueError("af_fold_in_items: %d users, %d items, %d roles" % (u_.numel(), o_.numel(), r_.numel()))
+        pairs = int(ptr_host[-1]) if n >= 0 and ptr_host.numel() else 0
+        if pairs != u_.numel():
+            raise ValueError("af_fold_in_items: pair_ptr ends at %d, %d pairs given" % (pairs, u_.numel()))
+        lr = self._hyper()[0] if lr is None else float(lr)
+        reg = self._hyper()[1] if reg is None else float(reg)
+        opt = _ffi.OPTIMIZER[self.optimizer if optimizer is None else optimizer]
+        loss = torch.empty(n, dtype=torch.float32, device=self.device) if want_loss else None
+        work = torch.empty((max(pairs, 1), self.af_work_stride()), dtype=torch.float32, device=self.device)
+        if u_.numel() == 0:                                  # (no item has a pair: the library still wants the pointers)
+            u_ = o_ = r_ = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _ffi.check(self.h, self.lib.bprx_af_fold_in_items(self.h, _addr(ptr), _addr(u_), _addr(o_), _addr(r_), n, _addr(C_rows),
+                                                          int(steps), lr, reg, opt, _addr(Gi_rows), _addr(loss), _addr(work),
+                                                          _stream()))
+        return (loss, work[:pairs]) if want_work else loss
+
+    def af_score_warm_block(self, u0, u1, C_rows, Gi_rows, want_alpha=True):
+        """bprx_af_score_warm_block: af_score_block for caller-owned item rows: scores [u1 - u0, n] and attentions [u1 - u0, n, 3]
+        (None with want_alpha=False)."""
+        n = self._af_item_rows("af_score_warm_block", C_rows, Gi_rows)
+        x = torch.empty((max(u1 - u0, 0), n), dtype=torch.float32, device=self.device)
+        al = torch.empty((max(u1 - u0, 0), n, 3), dtype=torch.float32, device=self.device) if want_alpha else None
+        _ffi.check(self.h, self.lib.bprx_af_score_warm_block(self.h, int(u0), int(u1), _addr(C_rows), _addr(Gi_rows), n, _addr(x),
+                                                             _addr(al), _stream()))
+        return x, al
+
+    def af_audience_block(self, q0, q1, C_rows=None, Gi_rows=None, want_alpha=True):
+        """bprx_af_audience_block: the same scores item-major for the rows [q0, q1) of the caller's item rows (both None: of the
+        catalogue): scores [q1 - q0, U] and attentions [q1 - q0, U, 3] (None with want_alpha=False)."""
+        if C_rows is None and Gi_rows is None:
+            n = self.I
+        else:
+            n = self._af_item_rows("af_audience_block", C_rows, Gi_rows)
+        x = torch.empty((max(q1 - q0, 0), self.U), dtype=torch.float32, device=self.device)
+        al = torch.empty((max(q1 - q0, 0), self.U, 3), dtype=torch.float32, device=self.device) if want_alpha else None
+        _ffi.check(self.h, self.lib.bprx_af_audience_block(self.h, _addr(C_rows), _addr(Gi_rows), n, int(q0), int(q1), _addr(x),
+                                                           _addr(al), _stream()))
+        return x, al
+
     def af_dropout_mask(self, step, n_rows):
         """The keep masks of step index `step` for n_rows = 2B sample rows (bprx_af_dropout_mask): three uint8 device tensors
         [n_rows, 256], [n_rows, 64], [n_rows, 256] (colour hidden units, pooled edge channels, class hidden units)."""

@@ -279,13 +279,13 @@ class Evaluator:
             write_ranked(out, range(ids.shape[0]), ids, vals)
 
     def store_audience(self, path="", items=None):
-        """BPRMF / VBPR / GradFashion: the audience of every item of `items` (None: the whole catalogue; model.audience: the
+        """BPRMF / VBPR / GradFashion / AttentiveFashion (rows with the attentions): the audience of every item of `items` (None: the whole catalogue; model.audience: the
         params' K users with the highest score, the item's owners excluded) as rows 'i\tu\tscore', item by item, best first,
         formatted as store_recommendation formats; an item with fewer non-owners than K has that many rows."""
-        ids, vals = self.model.audience(items)
-        labels = range(ids.shape[0]) if items is None else [int(i) for i in np.asarray(items).reshape(-1)]
+        res = self.model.audience(items)                     # (ids, vals) and, AttentiveFashion, the attentions
+        labels = range(res[0].shape[0]) if items is None else [int(i) for i in np.asarray(items).reshape(-1)]
         with open(path, 'w') as out:
-            write_item_lists(out, labels, ids, vals)
+            write_item_lists(out, labels, *res)
 
     def store_audience_new(self, path="", features=None):
         """VBPR / GradFashion: the audience of every row of `features` (raw rows of items outside the catalogue, as
@@ -296,7 +296,7 @@ class Evaluator:
             write_item_lists(out, range(ids.shape[0]), ids, vals)
 
     def store_recommendation_warm(self, path="", buyers=None, features=None, rows=None, **fold):
-        """BPRMF / VBPR / GradFashion: the top-k WARM items of every user (model.recommend_warm: new items whose Gi / Bi rows are
+        """BPRMF / VBPR / GradFashion / AttentiveFashion (whose rows end in the three attentions): the top-k WARM items of every user (model.recommend_warm: new items whose Gi / Bi rows are
         fitted from buyers[j], the users who bought item j; the ones a user bought are masked) as rows 'u\tj\tscore', j = the row
         of `buyers` (and of `features`, raw rows as model.prepare_new_items takes them), best first, formatted as
         store_recommendation formats them.  rows: what model.fold_in_items returned for these buyers (None: fitted here with
@@ -304,21 +304,21 @@ class Evaluator:
         m = self.model
         if rows is None:
             rows = m.fold_in_items(buyers, features, **fold)
-        ids, vals = m._rank_warm_recs(rows, buyers)
+        res = m._rank_warm_recs(rows, buyers)                # (ids, vals) and, AttentiveFashion, the attentions
         with open(path, 'w') as out:
-            write_item_lists(out, range(ids.shape[0]), ids, vals)
+            write_item_lists(out, range(res[0].shape[0]), *res)
         return rows
 
     def store_audience_warm(self, path="", buyers=None, features=None, rows=None, **fold):
-        """BPRMF / VBPR / GradFashion: the audience of every warm item (model.audience_warm: the params' K users with the highest
+        """BPRMF / VBPR / GradFashion / AttentiveFashion (rows with the attentions): the audience of every warm item (model.audience_warm: the params' K users with the highest
         score, the item's buyers masked) as rows 'j\tu\tscore', item by item, best first.  rows / **fold as
         store_recommendation_warm takes them."""
         m = self.model
         if rows is None:
             rows = m.fold_in_items(buyers, features, **fold)
-        ids, vals = m._rank_warm_audience(rows, buyers)
+        res = m._rank_warm_audience(rows, buyers)
         with open(path, 'w') as out:
-            write_item_lists(out, range(ids.shape[0]), ids, vals)
+            write_item_lists(out, range(res[0].shape[0]), *res)
         return rows
 
     def store_recommendation_grads(self, path="", path_expl=None, top=5):

@@ -600,11 +600,14 @@ class BPRMF(RecommenderModel):
         ids[vals == -np.inf] = -1
         return ids, vals
 
+    warm_param = "warm_items"                                    # the params entry that names the first buyers' file
+
     def _store_warm(self, path):
-        """params.warm_items: warm-recs-* (rows 'u\tj\tscore') and, with params.audience = K > 0, warm-audience-* (rows
-        'j\tu\tscore') next to the recs-* file at `path`, j = the row of the file (VBPR / GradFashion: of the new_items table); one
+        """params.warm_items (AttentiveFashion: params.af_warm_items): warm-recs-* (rows 'u\tj\tscore') and, with params.audience
+        (af_audience) = K > 0, warm-audience-* (rows 'j\tu\tscore') next to the recs-* file at `path`, j = the row of the file
+        (VBPR / GradFashion / AttentiveFashion: of the new items' table; AttentiveFashion adds the three attentions to a row); one
         fit serves both."""
-        src = getattr(self.params, "warm_items", None)
+        src = getattr(self.params, self.warm_param, None)
         if not src:
             return
         from .train_rec import read_warm_items
@@ -1362,6 +1365,11 @@ def load_attentive_inputs(dataset, num_items):
     return edges, torch.from_numpy(color), torch.from_numpy(classes)
 
 
+class AfNewItems(tuple):
+    """What AttentiveFashion.prepare_new_items returns: (edges uint8 [n, 224, 224], colour fp32 [n, Dc] normalised, classes fp32
+    [n, Dk]) CPU tensors, marked as prepared."""
+
+
 class AttentiveFashion(BPRMF):
     """AttentiveFashion.py:20-371: x_ui = sum_k g_u * (sum_l alpha_l c_l) * g_i with the encodings c_l of the item's colour
     histogram, edge image and class vector and a three-way attention over them, trained on the engine's AttentiveFashion path
@@ -1385,6 +1393,7 @@ class AttentiveFashion(BPRMF):
                              % (", ".join(str(g) for g in AF_EXPLAIN_GRIDS[1:]), self.af_explain))
         self._inputs = inputs
         super().__init__(data, params, init)
+        self.audience_k = int(getattr(params, "af_audience", 0) or 0)             # users per item in audience-* / warm-audience-*
         self.directory_parameters = f'batch_{params.batch_size}' \
                                     f'-K_{params.embed_k}' \
                                     f'-lr_{params.lr}' \
@@ -1493,6 +1502,124 @@ class AttentiveFashion(BPRMF):
     new_users_param, new_users_side = "af_new_users", 3
     diverse = False
     because_instead = "--af_explain"
+
+    # ---- items the model was not trained on, once they have first buyers: x_ur is linear in Gi_r (include/bprx.h) ----------------
+    warm_param = "af_warm_items"
+
+    def prepare_new_items(self, edges, color, classes):
+        """The inputs of n new items as the encoders take them, an AfNewItems of CPU tensors: edges uint8 [n, 224, 224] as they
+        are, colour fp32 [n, Dc] with every raw histogram divided by its OWN max-abs (an all-zero row is rejected: the rule of
+        load_attentive_inputs), classes fp32 [n, Dk].  ValueError for shapes that do not match the bound Dc and Dk."""
+        Dc, Dk = int(self.color.shape[1]), int(self.classes.shape[1])
+        ed, col, cl = np.asarray(edges), np.asarray(color), np.asarray(classes)
+        if ed.dtype != np.uint8 or ed.ndim != 3 or ed.shape[1:] != (224, 224):
+            raise ValueError("new items: edges must be uint8 [n, 224, 224], got %s %s" % (ed.dtype, ed.shape))
+        n = ed.shape[0]
+        if col.shape != (n, Dc) or cl.shape != (n, Dk):
+            raise ValueError("new items: colour must be [%d, %d] and classes [%d, %d], got %s and %s" % (n, Dc, n, Dk, col.shape, cl.shape))
+        mx = np.max(np.abs(col), axis=1) if n else np.zeros(0)
+        if not np.all(mx > 0):
+            raise ValueError("new items: the colour histogram of row %d is all zero: its max-abs normalisation divides by zero"
+                             % int(np.flatnonzero(~(mx > 0))[0]))
+        return AfNewItems((torch.from_numpy(np.ascontiguousarray(ed)), torch.from_numpy((col / mx[:, None]).astype(np.float32)),
+                           torch.from_numpy(np.ascontiguousarray(cl, dtype=np.float32))))
+
+    def fold_in_items(self, buyers, features=None, steps=30, negatives=4, lr=None, reg=None, optimizer=None, seed=0, init=None):
+        """Rows for items that arrive after training, from their first buyers (buyers[r]: the catalogue users who bought new item
+        r): (Gi_new [n, k], C_new [3, n, k]) device tensors.  features: (edges, colour, classes) raw, as prepare_new_items takes
+        them, or what it returned.  C_new = Engine.af_encode_new of them; Gi_new is fitted by Engine.af_fold_in_items over the
+        pairs of draw_item_fold_pairs(buyers, training_list, num_items, negatives, seed), everything else frozen, dropout off.
+        lr / reg / optimizer: None = the run's.  init: None = zero rows, or the Gi rows to start from.  An item without buyers
+        keeps its start row: from zeros it scores 0.0 for everyone.  With plain sgd the step size must shrink with the number of
+        pairs (the batch loss is summed); Adam, the default, does not care."""
+        eng = self.engine
+        n = len(buyers)
+        if features is None:
+            raise ValueError("AttentiveFashion: fold_in_items needs the new items' (edges, colour, classes)")
+        feats = features if isinstance(features, AfNewItems) else self.prepare_new_items(*features)
+        if len(feats[0]) != n:
+            raise ValueError("AttentiveFashion: %d buyer lists for %d new items" % (n, len(feats[0])))
+        ptr, user, other, role = draw_item_fold_pairs(buyers, self.data.training_list[:self.num_users], self.num_items, negatives, seed)
+        Gi = fold_start_rows(init, n, eng.k, eng.device)
+        if n == 0:
+            return Gi, torch.zeros((3, 0, eng.k), dtype=torch.float32, device=eng.device)
+        C = eng.af_encode_new(*feats)
+        eng.af_fold_in_items(ptr, user, other, role, steps, C, Gi, lr=self.learning_rate if lr is None else lr,
+                             reg=self.reg if reg is None else reg, optimizer=self.optimizer_name if optimizer is None else optimizer,
+                             want_loss=False)
+        return Gi, C
+
+    def recommend_warm(self, buyers, features=None, k=None, **fold):
+        """The k (default top_k) best warm items of every user, the ones the user bought masked: numpy ids int64 [U, kk] (rows of
+        `buyers`), vals fp32 [U, kk] and alpha fp32 [U, kk, 3] (colour, edges, class), kk = min(k, n), best first, -1 / -inf past a
+        user's unmasked items.  Fitted by fold_in_items(buyers, features, **fold), scored by Engine.af_score_warm_block."""
+        return self._rank_warm_recs(self.fold_in_items(buyers, features, **fold), buyers, k)
+
+    def audience_warm(self, buyers, features=None, k=None, **fold):
+        """The k (default: params.af_audience, else top_k) users with the highest score for every warm item, its buyers masked:
+        numpy ids int64 [n, kk], vals fp32 [n, kk] and alpha fp32 [n, kk, 3], kk = min(k, U), best first, -1 / -inf past an item's
+        non-buyers.  Fitted as recommend_warm fits, scored item-major by Engine.af_audience_block."""
+        return self._rank_warm_audience(self.fold_in_items(buyers, features, **fold), buyers, k)
+
+    def _rank_warm_recs(self, rows, buyers, k=None):
+        eng, U, n = self.engine, self.num_users, len(buyers)
+        Gi, Cn = rows
+        k = self.evaluator.k if k is None else int(k)
+        ids, vals, att = ranked_zeros(U, min(k, n), 3)
+        if n == 0:
+            return ids, vals, att
+        bought = owners_of(buyers, U)                            # per user the warm items that user bought
+        for b0, b1 in blocks(U, self.evaluator.user_block, n):
+            own = eng.csr(bought[b0:b1])
+            sc, al = eng.af_score_warm_block(b0, b1, Cn, Gi)
+            ids[b0:b1], vals[b0:b1], att[b0:b1] = rank_rows(lambda s, kq: eng.topk_rows_masked(s, own, kq), sc, k, side=al)
+        ids[vals == -np.inf] = -1
+        return ids, vals, att
+
+    def _rank_warm_audience(self, rows, buyers, k=None):
+        eng, U, n = self.engine, self.num_users, len(buyers)
+        Gi, Cn = rows
+        k = (self.audience_k or self.evaluator.k) if k is None else int(k)
+        ids, vals, att = ranked_zeros(n, min(k, U), 3)
+        for b0, b1 in blocks(n, self.evaluator.user_block, U):
+            own = eng.csr([list(dict.fromkeys(int(u) for u in who)) for who in buyers[b0:b1]])
+            sc, al = eng.af_audience_block(b0, b1, Cn, Gi)
+            ids[b0:b1], vals[b0:b1], att[b0:b1] = rank_rows(lambda s, kq: eng.topk_rows_masked(s, own, kq), sc, k, side=al)
+        ids[vals == -np.inf] = -1
+        return ids, vals, att
+
+    def audience(self, items=None, k=None):
+        """The k (default: params.af_audience, else top_k) users with the highest score for each item of `items` (None: the whole
+        catalogue, in id order), the item's owners excluded: numpy ids int64 [n, kk], vals fp32 [n, kk] and alpha fp32 [n, kk, 3],
+        kk = min(k, U), best first, -1 / -inf past an item's non-owners.  The scores are af_score_block's, item-major
+        (Engine.af_audience_block)."""
+        eng, I, U = self.engine, self.num_items, self.num_users
+        k = (self.audience_k or self.evaluator.k) if k is None else int(k)
+        want = np.arange(I, dtype=np.int64) if items is None else np.asarray(items, dtype=np.int64).reshape(-1)
+        if want.size and (want.min() < 0 or want.max() >= I):
+            raise ValueError("audience: item ids lie in [0, %d)" % I)
+        ids, vals, att = ranked_zeros(want.size, min(k, U), 3)
+        owners = self._owners() if want.size else None
+        for b0, b1, rows, local in wanted_blocks(want, I, self.evaluator.user_block, U):
+            own = eng.csr(owners[b0:b1])
+            sc, al = eng.af_audience_block(b0, b1)
+            bi, bv, ba = rank_rows(lambda s, kq: eng.topk_rows_masked(s, own, kq), sc, k, side=al)
+            ids[rows], vals[rows], att[rows] = bi[local], bv[local], ba[local]
+        ids[vals == -np.inf] = -1
+        return ids, vals, att
+
+    def _store_audience(self, path):
+        """params.af_audience = K > 0: audience-* next to the recs-* file at `path`, rows 'i\tu\tscore\talpha_colour\talpha_edges\t
+        alpha_class', item by item over the whole catalogue, best first."""
+        if self.audience_k > 0:
+            self.evaluator.store_audience(item_file(path, "audience"), None)
+
+    def _load_new_items(self):
+        """The tables of params.af_new_items (edges, colour, classes), prepared; None without the flag."""
+        src = getattr(self.params, "af_new_items", None)
+        if not src:
+            return None
+        return self.prepare_new_items(*(np.load(p) for p in src))
 
     def _store_recs(self, path):
         """recs-* / best-recs-* with the attentions; with params.af_explain = G > 0 also expl-* / best-expl-* next to them."""

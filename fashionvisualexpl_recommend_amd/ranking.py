@@ -179,12 +179,12 @@ def write_ranked(out, labels, ids, vals, side=None):
     return users, items
 
 
-def write_item_lists(out, labels, ids, vals):
+def write_item_lists(out, labels, ids, vals, side=None):
     """write_ranked for lists that may end in empty slots (id < 0: an item with fewer non-owners than the list is long): the
-    rows 'label\\tid\\tval' of every list up to its first empty slot, formatted as write_ranked formats them."""
+    rows 'label\\tid\\tval[\\tside_0 ...]' of every list up to its first empty slot, formatted as write_ranked formats them."""
     for r, label in enumerate(labels):
         n = int((ids[r] >= 0).sum())
-        write_ranked(out, [label], ids[r:r + 1, :n], vals[r:r + 1, :n])
+        write_ranked(out, [label], ids[r:r + 1, :n], vals[r:r + 1, :n], None if side is None else side[r:r + 1, :n])
 
 
 def write_feature_rows(out, users, items, e):

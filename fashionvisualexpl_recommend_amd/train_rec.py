@@ -17,6 +17,9 @@ items of u's training list nearest to i by cosine in the space of --similar_spac
 --audience K (bprmf, vbpr, grad_fashion) writes audience-* / best-audience-* files next to recs-*: for every catalogue item (or
 the ids of --audience_items) the K users that score it highest, its owners excluded, and with --new_items new-audience-* /
 best-new-audience-* (the visual score of items the model was not trained on).
+--af_new_items EDGES COLOUR CLASSES, --af_warm_items PATH and --af_audience K (attentive_fashion only) are the warm-item and
+audience products of AttentiveFashion: Gi rows for new items from their first buyers (warm-recs-*, warm-audience-*) and
+audience-* for the catalogue, each row with its three attentions.
 --warm_items PATH (bprmf, vbpr, grad_fashion) fits Gi / Bi rows for new items from their first buyers (rows `row<TAB>user`; vbpr and
 grad_fashion: rows of the --new_items table) and writes warm-recs-* / best-warm-recs-* files, with --audience K also warm-audience-*.
 Run as `python -m fashionvisualexpl_recommend_amd.train_rec --rec bprmf --dataset <name> ...`.
@@ -134,10 +137,30 @@ def parse_args(argv=None):
                              "items, bought ones excluded) are written next to recs-* / best-recs-*; with --audience K also "
                              "warm-audience-* / best-warm-audience-* (row, u, score).  A row without buyers keeps zero Gi / Bi and "
                              "scores as in new-recs-*")
+    parser.add_argument('--af_new_items', nargs=3, default=None, metavar=('EDGES.npy', 'COLOUR.npy', 'CLASSES.npy'),
+                        help="attentive_fashion: the inputs of n items the model was not trained on: edge images uint8 [n, 224, 224], "
+                             "raw colour histograms [n, Dc] (each divided by its own max-abs, as the catalogue's are; an all-zero "
+                             "histogram is rejected) and class vectors [n, Dk]; read by --af_warm_items")
+    parser.add_argument('--af_warm_items', default=None, metavar='PATH',
+                        help="attentive_fashion: a TSV of `row<TAB>user` rows in the format of --warm_items, the first buyers "
+                             "(catalogue users) of the rows of the --af_new_items tables (required).  The score is linear in an "
+                             "item's Gi row, so each new item's row is fitted with everything else frozen and dropout off (the item "
+                             "as the positive against sampled negatives of its buyers, and as often as the negative of other "
+                             "users' items) and warm-recs-* / best-warm-recs-* files (u, row, score, alpha_colour, alpha_edges, "
+                             "alpha_class: every user's top_k warm items, bought ones excluded) are written next to recs-* / "
+                             "best-recs-*; with --af_audience K also warm-audience-* / best-warm-audience-* (row, u, score, alpha...; "
+                             "the item's buyers excluded).  A row without buyers keeps a zero Gi row and scores 0.0 for everyone")
+    parser.add_argument('--af_audience', type=int, default=0, metavar='K',
+                        help="attentive_fashion: also write audience-* / best-audience-* files next to recs-* / best-recs-* with the K "
+                             "(1..1024) users that score every catalogue item highest, the item's owners excluded, rows `i u score "
+                             "alpha_colour alpha_edges alpha_class`, item by item, best first; with --af_warm_items also "
+                             "warm-audience-* / best-warm-audience-*; 0 = off")
     parser.add_argument('--fold_steps', type=int, default=30,
-                        help='--new_users / --af_new_users / --acf_new_users / --warm_items: optimiser steps per new user or item')
+                        help='--new_users / --af_new_users / --acf_new_users / --warm_items / --af_warm_items: optimiser steps per new '
+                             'user or item')
     parser.add_argument('--fold_negatives', type=int, default=4,
-                        help='--new_users / --af_new_users / --acf_new_users: sampled negatives per history item; --warm_items: per buyer')
+                        help='--new_users / --af_new_users / --acf_new_users: sampled negatives per history item; --warm_items / '
+                             '--af_warm_items: per buyer')
     # not in the reference
     parser.add_argument('--dropout', type=float, default=0.5,
                         help="attentive_fashion: rate of the encoders' Dropout layers (AttentiveFashion.py:53,62,70: 0.5)")
@@ -198,6 +221,21 @@ def parse_args(argv=None):
             read_warm_items(args.warm_items)
         except (OSError, ValueError) as e:
             parser.error("--warm_items: %s" % e)
+    if args.af_new_items is not None and args.rec != 'attentive_fashion':
+        parser.error("--af_new_items needs --rec attentive_fashion (got --rec %s)" % args.rec)
+    if args.af_warm_items is not None:
+        if args.rec != 'attentive_fashion':
+            parser.error("--af_warm_items needs --rec attentive_fashion (got --rec %s)" % args.rec)
+        if args.af_new_items is None:
+            parser.error("--af_warm_items needs --af_new_items (the rows of the file are rows of those tables)")
+        try:
+            read_warm_items(args.af_warm_items)
+        except (OSError, ValueError) as e:
+            parser.error("--af_warm_items: %s" % e)
+    if not 0 <= args.af_audience <= 1024:
+        parser.error("--af_audience takes 0 (off) .. 1024 (got %s)" % args.af_audience)
+    if args.af_audience != 0 and args.rec != 'attentive_fashion':
+        parser.error("--af_audience needs --rec attentive_fashion (got --rec %s)" % args.rec)
     if args.fold_steps < 1 or args.fold_negatives < 1:
         parser.error("--fold_steps and --fold_negatives take values >= 1 (got %s, %s)" % (args.fold_steps, args.fold_negatives))
     if not 0 <= args.similar_items <= 1024:
@@ -295,6 +333,27 @@ def read_warm_items(path, num_rows=None):
     return buyers
 
 
+def read_af_new_items(paths):
+    """The --af_new_items tables (edges, colour, classes .npy) -> the three arrays, checked: edges uint8 [n, 224, 224], colour and
+    classes real-valued [n, D] with the same n, no colour histogram all zero (its max-abs normalisation would divide by zero).
+    ValueError names the file; the widths are checked against the model's Dc, Dk by AttentiveFashion.prepare_new_items."""
+    import numpy as np
+    if len(paths) != 3:
+        raise ValueError("three paths (edges, colour, classes), got %d" % len(paths))
+    ed, col, cl = (np.load(p, mmap_mode='r') for p in paths)
+    if ed.dtype != np.uint8 or ed.ndim != 3 or ed.shape[1:] != (224, 224):
+        raise ValueError("%s: edges must be uint8 [n, 224, 224], got %s %s" % (paths[0], ed.dtype, ed.shape))
+    n = ed.shape[0]
+    for p, a, what in ((paths[1], col, "colour"), (paths[2], cl, "classes")):
+        if a.ndim != 2 or a.shape[0] != n or a.shape[1] < 1 or a.dtype.kind not in "fiu":
+            raise ValueError("%s: %s must be a real-valued [%d, D] table, got %s %s" % (p, what, n, a.dtype, a.shape))
+    mx = np.max(np.abs(np.asarray(col)), axis=1) if n else np.zeros(0)
+    if not np.all(mx > 0):
+        raise ValueError("%s: the colour histogram of row %d is all zero: its max-abs normalisation divides by zero"
+                         % (paths[1], int(np.flatnonzero(~(mx > 0))[0])))
+    return np.asarray(ed), np.asarray(col), np.asarray(cl)
+
+
 def read_new_users(path):
     """The --new_users file: rows `label<TAB>item` -> (labels in first-appearance order, one item list per label, in file order).
     Empty lines are skipped; anything else that is not a label and an integer item raises ValueError with its line number."""
@@ -344,6 +403,13 @@ def train(argv=None):
     if args.warm_items is not None and args.new_items is not None:                  # a row past the table: before anything is trained
         import numpy as np
         read_warm_items(args.warm_items, int(np.load(args.new_items[0], mmap_mode='r').shape[0]))
+    for flag in ("af_new_items", "af_warm_items", "af_audience"):
+        if getattr(args, flag) and int(args.world_size) > 1:
+            raise NotImplementedError('--%s runs on one GPU (no multi-GPU form): use --world_size 1' % flag)
+    if args.af_new_items is not None:                                               # before anything is loaded or trained
+        n_new = int(read_af_new_items(args.af_new_items)[0].shape[0])
+        if args.af_warm_items is not None:
+            read_warm_items(args.af_warm_items, n_new)
     if args.because != 0 and args.top_k > 1024:
         raise ValueError('--because runs on the device only (top_k <= 1024): there is no host form')
     if args.new_items is not None and args.dtype == 'fp8':
@@ -381,6 +447,8 @@ def train(argv=None):
         check_audience_items(args, data.num_items)
         if args.warm_items is not None and any(u >= data.num_users for who in read_warm_items(args.warm_items) for u in who):
             raise ValueError('--warm_items: a buyer is outside the %d users of the dataset' % data.num_users)
+        if args.af_warm_items is not None and any(u >= data.num_users for who in read_warm_items(args.af_warm_items) for u in who):
+            raise ValueError('--af_warm_items: a buyer is outside the %d users of the dataset' % data.num_users)
         print("Training {0} on {1}".format(args.rec, args.dataset))
         print("Parameters:")
         args.reg = current_reg                                                                  # train_rec.py:69

@@ -153,6 +153,7 @@ BPRX_API int bprx_sync_adam(bprx_handle *h, void *stream);
      bprx_audience_block, Pq == NULL                                  BPRMF / VBPR        yes           yes   via P  yes
      bprx_audience_block, Pq != NULL                                  VBPR, not fp8       yes           yes   yes    -
      bprx_af_fold_in, bprx_af_score_rows_block                        AttentiveFashion    yes           -     -      -
+     bprx_af_encode_new, bprx_af_fold_in_items, bprx_af_score_warm_block, bprx_af_audience_block   AttentiveFashion   yes   -   -   -
      bprx_acf_fold_in, bprx_acf_profile_rows, bprx_acf_score_rows_block   ACF             yes           -     -      -
      bprx_step_project                                                any                 yes           -     yes    yes
      bprx_score_pairs                                                 any                 yes           yes   unless P is current  -
@@ -737,6 +738,65 @@ BPRX_API int bprx_af_fold_in(bprx_handle *h, const int64_t *pair_ptr, const int3
    bprx_af_score_block.  0 <= r0 <= r1 <= n_rows < 2^31; errors as for bprx_af_fold_in. */
 BPRX_API int bprx_af_score_rows_block(bprx_handle *h, const float *Gu_rows, int64_t n_rows, int64_t r0, int64_t r1, float *scores,
                                       float *alpha, void *stream);
+/* Items the model was not trained on, once they have first buyers.  An item without a Gi row scores 0 for everybody, and for
+   AttentiveFashion nothing but Gi_i is missing: the encoders give c_l(i) from the item's own inputs.  alpha is computed from g_u
+   and the encodings only (AttentiveFashion.py:146-166), Gi_i does not enter it, so the score is LINEAR in the new item's row:
+       x_ur = Gi_r . m(u, r)       m(u, r) = g_u o sum_l alpha_l(u, r) c_l(r)
+   and fitting the row with everything else frozen and dropout off is the linear-logistic problem of bprx_fold_in_items.
+
+   bprx_af_encode_new: the three dropout-off encodings of n caller-owned inputs (device): edges uint8 [n, 224, 224] (16-byte
+   aligned), color fp32 [n, Dc] (each row already divided by its own max-abs), cls fp32 [n, Dk] -> out fp32 [3, n, k].  The kernels
+   and workspaces of bprx_af_encode, in chunks of 2 * max_batch rows: fed copies of catalogue items' own inputs it returns the bits
+   of bprx_af_encode.  Allocates nothing.  Any 0 <= n < 2^31.
+
+   bprx_af_fold_in_items: pair p of new item r, p in [pair_ptr[r], pair_ptr[r+1]), n_r of them, is (u_p, o_p, role_p) as for
+   bprx_fold_in_items; s_p = +1 for role 0 (r is the positive against the catalogue item o_p), -1 for role 1.  C_rows fp32
+   [3, n, k]: the encodings of the new items (bprx_af_encode_new).
+       alpha^r = softmax_l( relu((g_u o c_l(r)) W_1 + b_1).W_2 + b_2 )
+       m_p     = g_u o (alpha^r_0 c_0(r) + alpha^r_1 c_1(r) + alpha^r_2 c_2(r))
+       x_o     = sum_l alpha_l(u, o) t_l,   t_l = sum_k c_lk(o) (g_uk Gi_ok)          (the catalogue item's score)
+       D_p     = s_p m_p          dc_p = -s_p x_o                                     (formed once: nothing in them moves)
+       w starts at Gi_rows[r]; for t = 1 .. steps:
+         x_p = w.D_p + dc_p          s = sigmoid(-x_p) inside [-80, 1e8] (inclusive bounds), 0 outside
+         g = sum_p (-s D_p) + 2 reg n_r w                                             (summed in pair order)
+         loss_t = sum_p softplus(-clip(x_p)) + reg n_r |w|^2
+         BPRX_OPT_SGD: w <- w - lr g;  BPRX_OPT_ADAM_TF23: the sparse-variable rule, slots from zero, lr_t as for bprx_fold_in
+   The model scores no Bi: there is no bias and no reg / 10 rule.  The constant regularisers of the reference's loss (g_u, the
+   encoder outputs, the attention tensors) are left out of `loss`.  For steps = 1 and sgd, started from a catalogue item's own row
+   and encodings on a handle bound with dropout = 0, the row moves as bprx_step moves it on the batch that has the item once per
+   triplet, in either role.  Role 1 is a sign flip of role 0: D_p and dc_p of (u, o, 1) are the bit negations of those of (u, o, 0).
+   pair_ptr int64 [n+1], user / other / role int32 (device); Gi_rows fp32 [n, k] in / out; loss fp32 [n] or NULL: loss_steps,
+   before the last update.  An item without pairs keeps its row and has loss 0.  lr, reg, optimizer are the call's.
+   work: caller-owned, fp32, at least pair_ptr[n] * KW floats, KW = (k + 1) rounded up to a multiple of 4.  After the call row p
+   holds [D_p (k) | dc_p | zeros].
+   The call first makes the catalogue encodings current, as bprx_af_fold_in does; apart from that it writes its outputs (Gi_rows,
+   loss, work) only and allocates nothing.  No float atomics, every sum in one fixed order: two calls return the same bits, and an
+   item's result depends on its own pairs, its start row, its encodings and the tables only -- not on n, on its position, or on
+   BPRX_FOLD_CACHE (0: every step reads every pair from work again instead of keeping the first pairs of an item in LDS).  Any
+   n_r, every shape bprx_bind_attentive accepts, independent of max_batch.
+
+   bprx_af_score_warm_block: k_af_block given the caller's item rows: scores fp32 [(u1-u0), n] and alpha fp32 [(u1-u0), n, 3]
+   (NULL: scores only) of the users [u0, u1) against C_rows [3, n, k] / Gi_rows [n, k] (16-byte aligned where k is a multiple of
+   8).  Rows sliced out of bprx_af_encode and Gi give the bits of those columns of bprx_af_score_block.
+
+   bprx_af_audience_block: the same score item-major for the rows [q0, q1): scores fp32 [(q1-q0), num_users], alpha fp32
+   [(q1-q0), num_users, 3] (NULL: scores only); out[r][u] has the bits of bprx_af_score_warm_block's out[u][q0 + r].  C_rows and
+   Gi_rows both NULL: the items are the catalogue (n must equal num_items; the encodings are made current first) and out[r][u]
+   has the bits of bprx_af_score_block's out[u][q0 + r].  0 <= q0 <= q1 <= n.
+
+   All four: BPRX_E_INVALID for a NULL handle, a handle that is not bound with bprx_bind_attentive, a NULL pointer, a bad range,
+   steps < 1, an unknown optimizer; BPRX_E_STATE for an unbound handle; n == 0 or an empty range: BPRX_OK, nothing is written.
+   User and item ids and roles out of range are clamped and reported once by bprx_sync_check (BPRX_E_RANGE); after any error the
+   handle stays usable. */
+BPRX_API int bprx_af_encode_new(bprx_handle *h, const uint8_t *edges, const float *color, const float *cls, int64_t n, float *out,
+                                void *stream);
+BPRX_API int bprx_af_fold_in_items(bprx_handle *h, const int64_t *pair_ptr, const int32_t *user, const int32_t *other,
+                                   const int32_t *role, int64_t n, const float *C_rows, int32_t steps, float lr, float reg,
+                                   int32_t optimizer, float *Gi_rows, float *loss, float *work, void *stream);
+BPRX_API int bprx_af_score_warm_block(bprx_handle *h, int32_t u0, int32_t u1, const float *C_rows, const float *Gi_rows, int64_t n,
+                                      float *scores, float *alpha, void *stream);
+BPRX_API int bprx_af_audience_block(bprx_handle *h, const float *C_rows, const float *Gi_rows, int64_t n, int64_t q0, int64_t q1,
+                                    float *scores, float *alpha, void *stream);
 /* The keep-mask bytes (1 = kept) of step index `step` for a batch of n_rows / 2 triplets: out uint8
    [n_rows * 256 | n_rows * 64 | n_rows * 256] (colour hidden units, pooled edge channels, class hidden units). */
 BPRX_API int bprx_af_dropout_mask(bprx_handle *h, int64_t step, int64_t n_rows, uint8_t *out, void *stream);
