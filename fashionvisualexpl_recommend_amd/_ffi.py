@@ -83,6 +83,7 @@ class Tables(C.Structure):
 
 DEFER_ENTRIES = ("bprx_settle", "bprx_dense_pending", "bprx_set_loss_lag")    # the deferred dense update (include/bprx.h)
 QUEUE_ENTRIES = ("bprx_index_pass_queue",)                                   # the samplers' owner queues: an introspection getter
+PROBE_ENTRIES = ("bprx_probe_stream_read_nt_shape", "bprx_item_proj")        # the in-flight sweep's probe (scripts/nt_inflight_sweep.py); a test getter
 
 _lib = None
 
@@ -184,8 +185,10 @@ def lib():
         "bprx_eval_counts": (C.c_int, [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
         "bprx_eval_finish": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
         "bprx_sync_check": (C.c_int, [vp, vp]),
+        "bprx_item_proj": (C.c_int, [vp, C.POINTER(vp), C.POINTER(i64)]),
         "bprx_probe_stream_read": (i64, [vp, i64, vp, vp]),
         "bprx_probe_stream_read_nt": (i64, [vp, i64, vp, vp]),
+        "bprx_probe_stream_read_nt_shape": (i64, [vp, i64, i32, i32, i32, vp, vp]),
         "bprx_probe_row_gather": (i64, [vp, i64, i32, vp, i64, i32, vp, vp]),
         "bprx_profile_enable": (C.c_int, [vp, C.c_int]),
         "bprx_profile_read": (C.c_int, [vp, vp, vp]),
@@ -213,7 +216,7 @@ def lib():
         "bprx_set_loss_lag": (C.c_int, [vp, C.c_int]),
     }
     for name, (res, args) in sig.items():
-        if name in DEFER_ENTRIES + QUEUE_ENTRIES and not hasattr(L, name):
+        if name in DEFER_ENTRIES + QUEUE_ENTRIES + PROBE_ENTRIES and not hasattr(L, name):
             continue                # an older build named by BPRX_LIB (A/B runs): it never defers, the engine skips these calls
         fn = getattr(L, name)       # AttributeError here == header/library mismatch: fail loudly
         fn.restype, fn.argtypes = res, args
@@ -228,10 +231,10 @@ EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error",
            "bprx_af_score_warm_block", "bprx_af_audience_block", "bprx_af_dropout_mask", "bprx_af_get_step", "bprx_af_set_step", "bprx_set_hyper", "bprx_tables_dirty",
            "bprx_set_adam_step", "bprx_get_adam_step", "bprx_adam_is_lazy", "bprx_sync_adam", "bprx_score_pairs", "bprx_step", "bprx_step_begin",
            "bprx_step_begin_sparse", "bprx_step_begin_dense", "bprx_sum_dense_parts",
-           "bprx_dense_grad", "bprx_step_end", "bprx_step_project", "bprx_user_grad", "bprx_clear_user_grad", "bprx_item_grad", "bprx_clear_item_grad",
+           "bprx_dense_grad", "bprx_item_proj", "bprx_step_end", "bprx_step_project", "bprx_user_grad", "bprx_clear_user_grad", "bprx_item_grad", "bprx_clear_item_grad",
            "bprx_scatter_add", "bprx_route_reset", "bprx_route_plan", "bprx_route_gather", "bprx_route_unpack", "bprx_route_gather_checked",
            "bprx_route_unpack_checked", "bprx_route_pack",
-           "bprx_route_scatter_add", "bprx_score_block", "bprx_eval_users", "bprx_eval_pos", "bprx_eval_counts", "bprx_eval_finish", "bprx_topk", "bprx_sync_check", "bprx_probe_stream_read", "bprx_probe_stream_read_nt", "bprx_probe_row_gather", "bprx_profile_enable",
+           "bprx_route_scatter_add", "bprx_score_block", "bprx_eval_users", "bprx_eval_pos", "bprx_eval_counts", "bprx_eval_finish", "bprx_topk", "bprx_sync_check", "bprx_probe_stream_read", "bprx_probe_stream_read_nt", "bprx_probe_stream_read_nt_shape", "bprx_probe_row_gather", "bprx_profile_enable",
            "bprx_profile_read", "bprx_sample_philox", "bprx_epoch_prepare", "bprx_epoch_slots", "bprx_sample_epoch", "bprx_sample_philox_h", "bprx_sample_epoch_h", "bprx_index_pass_kind", "bprx_index_pass_queue", "bprx_proj_mask_kind", "bprx_adam_rows", "bprx_step_lr", "bprx_user_msg_floats", "bprx_pack_user_msg",
            "bprx_apply_user_msgs", "bprx_sampler_create",
            "bprx_sampler_destroy", "bprx_sampler_count", "bprx_sampler_ref_stream", "bprx_settle", "bprx_dense_pending", "bprx_set_loss_lag"]

@@ -594,6 +594,13 @@ extern "C" int bprx_dense_grad(bprx_handle *h, float **ptr, int64_t *count) {
   return BPRX_OK;
 }
 
+extern "C" int bprx_item_proj(bprx_handle *h, float **ptr, int64_t *count) {
+  if (!h || !ptr || !count) return BPRX_E_INVALID;
+  *ptr = h->P;
+  *count = h->cfg.model == BPRX_MODEL_VBPR ? (int64_t)h->cfg.num_items * h->PS : 0;
+  return BPRX_OK;
+}
+
 // may_defer: the caller is bprx_step -- the dense update may be left to the next step's index pass (StepPlan::defer_ok)
 static int step_end(bprx_handle *h, float *loss_out, void *stream, bool may_defer) {
   if (!h) return BPRX_E_INVALID;

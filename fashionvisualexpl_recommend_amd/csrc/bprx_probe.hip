@@ -22,6 +22,23 @@ __global__ __launch_bounds__(1024) void k_probe_stream(const u32x4_t *__restrict
   if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x9e3779b9u && threadIdx.x == 0) sink[blockIdx.x] = acc;
 }
 
+// The same stream with the bytes in flight as arguments: `nt` loads, U 16-byte loads per lane outstanding, any workgroup
+// count and size (scripts/nt_inflight_sweep.py: what the hardware gives per byte in flight per CU).
+template <int U>
+__global__ __launch_bounds__(1024) void k_probe_stream_shape(const u32x4_t *__restrict__ p, size_t per_wg, u32x4_t *__restrict__ sink) {
+  const u32x4_t *base = p + (size_t)blockIdx.x * per_wg;
+  const size_t nthr = blockDim.x;
+  u32x4_t acc = {0, 0, 0, 0};
+  for (size_t i = threadIdx.x; i + (size_t)(U - 1) * nthr < per_wg; i += (size_t)U * nthr) {
+    u32x4_t v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = __builtin_nontemporal_load(base + i + (size_t)u * nthr);
+#pragma unroll
+    for (int u = 0; u < U; ++u) acc ^= v[u];
+  }
+  if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x9e3779b9u && threadIdx.x == 0) sink[blockIdx.x] = acc;
+}
+
 // Random-row probe: one lane group per listed row, 16 B per lane (the access shape of k_triplet_grad / k_item_seg: a
 // 256..1024-byte table row picked by an index); mode 0 reads the row, mode 1 reads it and writes it back in place
 // (the exclusive-row sgd update).  `idx` holds n row numbers (distinct when mode = 1).
@@ -69,6 +86,24 @@ static int64_t probe_stream(const void *buf, int64_t bytes, void *sink, void *st
   else hipLaunchKernelGGL(k_probe_stream<false>, dim3(512), dim3(1024), 0, (hipStream_t)stream, (const u32x4_t *)buf, per_wg, (u32x4_t *)sink);
   if (hipGetLastError() != hipSuccess) return BPRX_E_HIP;
   return (int64_t)(per_wg * 16 * 512);                    // bytes actually read
+}
+
+extern "C" int64_t bprx_probe_stream_read_nt_shape(const void *buf, int64_t bytes, int32_t workgroups, int32_t threads,
+                                                   int32_t loads_in_flight, void *sink, void *stream) {
+  if (!buf || !sink || bytes <= 0 || workgroups < 1 || workgroups > 512 || threads < 64 || threads > 1024 || threads % 64)
+    return BPRX_E_INVALID;                                  // (sink holds one 16-byte slot per workgroup: 8 KiB)
+  const int U = loads_in_flight;
+  if (U != 1 && U != 2 && U != 3 && U != 4 && U != 6 && U != 8 && U != 12 && U != 16) return BPRX_E_INVALID;
+  const size_t trip = (size_t)U * (size_t)threads;          // 16-byte elements per workgroup and loop trip
+  const size_t per_wg = (size_t)bytes / 16 / (size_t)workgroups / trip * trip;   // whole trips only
+  if (per_wg == 0) return BPRX_E_INVALID;
+  const dim3 g((unsigned)workgroups), b((unsigned)threads);
+  hipStream_t s = (hipStream_t)stream;
+#define SHAPE_GO(U_) case U_: hipLaunchKernelGGL(k_probe_stream_shape<U_>, g, b, 0, s, (const u32x4_t *)buf, per_wg, (u32x4_t *)sink); break;
+  switch (U) { SHAPE_GO(1) SHAPE_GO(2) SHAPE_GO(3) SHAPE_GO(4) SHAPE_GO(6) SHAPE_GO(8) SHAPE_GO(12) SHAPE_GO(16) }
+#undef SHAPE_GO
+  if (hipGetLastError() != hipSuccess) return BPRX_E_HIP;
+  return (int64_t)(per_wg * 16 * (size_t)workgroups);      // bytes actually read
 }
 
 extern "C" int64_t bprx_probe_stream_read(const void *buf, int64_t bytes, void *sink, void *stream) {

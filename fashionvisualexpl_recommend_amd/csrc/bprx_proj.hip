@@ -784,15 +784,16 @@ __device__ __forceinline__ void v10_body(const uint16_t *const (&asrc)[2], const
   {                                                                                                                   \
     int ce_ = (c_) + cshift;                                                                                          \
     if (ce_ >= nch) ce_ -= nch;                                                                                       \
-    _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) _Pragma("unroll") for (int x = 0; x < 4; ++x) {                 \
-      if constexpr (MASK) AR[mt][x] = ld_buf16<NTL>(ars[mt], voff[mt][x], (uint32_t)ce_ << 13);  /* loop-invariant offsets */ \
-      else AR[mt][x] = ld_stream16<NTL>(asrc[mt] + ((size_t)ce_ << 12) + x * 512 + lane * 8);                        \
-    }                                                                                                                 \
+    /* B FIRST: vmcnt retires in issue order, so V10_PARK's wait for the B pieces must not stand behind the A loads */ \
     const uint16_t *bc_ = Et + (size_t)ce_ * et_chunk;                                                                \
     _Pragma("unroll") for (int x = 0; x < NBR; ++x) {                                                                 \
       int pc = tid + x * bdim;                                                                                        \
       pc = pc < NPIECE ? pc : NPIECE - 1;                                                                             \
       bst[x] = *reinterpret_cast<const i32x4_t *>(bc_ + pc * 8);                                                      \
+    }                                                                                                                 \
+    _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) _Pragma("unroll") for (int x = 0; x < 4; ++x) {                 \
+      if constexpr (MASK) AR[mt][x] = ld_buf16<NTL>(ars[mt], voff[mt][x], (uint32_t)ce_ << 13);  /* loop-invariant offsets */ \
+      else AR[mt][x] = ld_stream16<NTL>(asrc[mt] + ((size_t)ce_ << 12) + x * 512 + lane * 8);                        \
     }                                                                                                                 \
   }
 #define V10_PARK(buf_)                                                                                                \
@@ -837,8 +838,11 @@ __device__ __forceinline__ void v10_body(const uint16_t *const (&asrc)[2], const
     V10_PARK(0)
     __syncthreads();
   }
-  // (A two chunks ahead -- three register sets in rotation, 128 KB per CU in flight -- was measured SLOWER: 85.0 vs 80.2 us
-  //  on C2, 129.5 vs 115.8 us (v8) on the c4 shard; removed)
+  // Outstanding loads per wave at the loop's two waits (NBR pieces of B and 4*MT pieces of A per chunk; vmcnt retires in issue
+  // order, which is why a chunk's B pieces are requested BEFORE its A pieces; measurements and history: DESIGN.md 6.4):
+  //                                             MT = 1          MT = 2
+  //   before V10_COMPUTE(c)   vmcnt <=          NBR + 4         NBR + 8      B(c+1) and A(c+1) stay outstanding
+  //   before the barrier      vmcnt <=          4               8            A(c+1) stays in flight across it
 #undef V10_ISSUE
 #undef V10_PARK
 #undef V10_COMPUTE
@@ -917,8 +921,9 @@ __global__ __launch_bounds__(512) void k_proj_fwd_bf16_v10(const uint16_t *__res
 //   * the [E|Bp]^T chunk (NT*2 KB per 128 k) is staged through LDS, shared by the four waves, from the image EtS that
 //     k_cast_Et8 writes in exactly the LDS order ((chunk, column tile, half, lane) x 16 B): the global -> LDS copy is a
 //     straight contiguous copy and every fragment read is a conflict-free 1-KB ds_read_b128;
-//   * two-stage pipeline, one barrier per chunk: chunk c+1's feature fragments and B pieces are requested before chunk
-//     c's MFMAs (scheduling fences keep hipcc from sinking them), the B pieces are parked in the other LDS buffer after.
+//   * two-stage pipeline, one barrier per chunk: chunk c+1's B pieces and then its feature fragments are requested before chunk
+//     c's MFMAs (scheduling fences keep hipcc from sinking them), the B pieces are parked in the other LDS buffer after -- B
+//     FIRST: vmcnt retires in issue order, so the park's wait leaves the 2*MT feature loads in flight across the barrier.
 // Balanced share of the row tiles per workgroup as in v8; the body is instantiated for 1 and 2 row tiles and picked per wave.
 //   * (round 3) WHOLE-LINE feature loads: a 16-row tile x 128-k chunk is 16 aligned 128-B lines of the tiled F (rows 256 B
 //     apart); a load instruction takes 8 of them whole (lane l: row 8x + l/8, 16-B piece l%8) instead of half of all 16 (the
@@ -959,15 +964,16 @@ __device__ __forceinline__ void f8s_body(const unsigned char *const (&arow)[2][2
     int ce_ = (c_) + cshift;                                                                                          \
     if (ce_ >= nch) ce_ -= nch;                                                                                       \
     const size_t ao_ = (size_t)(ce_ >> 1) * 8192 + (size_t)(ce_ & 1) * 128;                                           \
-    _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) {                                                               \
-      AR[mt].lo = ld_stream16<NTL>(arow[mt][0] + ao_);                                                                \
-      AR[mt].hi = ld_stream16<NTL>(arow[mt][1] + ao_);                                                                \
-    }                                                                                                                 \
+    /* B first, as in v10_body: F8S_PARK's wait then leaves the feature loads in flight across the barrier */         \
     const unsigned char *bc_ = EtS + (size_t)ce_ * BCH;                                                               \
     _Pragma("unroll") for (int x = 0; x < NBP; ++x) {                                                                 \
       int pc = tid + x * 512;                                                                                         \
       pc = pc < NPIECE ? pc : NPIECE - 1;                                                                             \
       bst[x] = *reinterpret_cast<const i32x4_t *>(bc_ + pc * 16);                                                     \
+    }                                                                                                                 \
+    _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) {                                                               \
+      AR[mt].lo = ld_stream16<NTL>(arow[mt][0] + ao_);                                                                \
+      AR[mt].hi = ld_stream16<NTL>(arow[mt][1] + ao_);                                                                \
     }                                                                                                                 \
   }
 #define F8S_PARK(buf_)                                                                                                \

@@ -938,6 +938,12 @@ class Engine:
             self._dense_view = _DevView(p.value, n.value, self.device).tensor
         return self._dense_view
 
+    def item_proj(self):
+        """fp32 view [I, PS] of the handle-owned item projections (bprx_item_proj: what the last forward projection wrote)."""
+        p, n = C.c_void_p(), C.c_int64()
+        _ffi.check(self.h, self.lib.bprx_item_proj(self.h, C.byref(p), C.byref(n)))
+        return None if n.value == 0 else _DevView(p.value, n.value, self.device).tensor.view(self.I, n.value // self.I)
+
     def step_project(self):
         _ffi.check(self.h, self.lib.bprx_step_project(self.h, _stream()))
 

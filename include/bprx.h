@@ -820,6 +820,11 @@ BPRX_API int bprx_step(bprx_handle *h, const int32_t *user, const int32_t *pos, 
 BPRX_API int bprx_step_begin(bprx_handle *h, const int32_t *user, const int32_t *pos, const int32_t *neg, int64_t B,
                     void *stream);
 BPRX_API int bprx_dense_grad(bprx_handle *h, float **ptr, int64_t *count);
+/* The handle-owned item projections P = F.[E|Bp]: [num_items, bprx_proj_stride] fp32, column d the visual bias (0 floats for
+   BPRMF).  Read-only introspection for tests: between bprx_step_begin_sparse and bprx_step_end the rows hold what the step's
+   forward projection wrote (a masked segment-mode step: zeros in the rows of items its batch does not touch); at other
+   times the rows may be stale. */
+BPRX_API int bprx_item_proj(bprx_handle *h, float **ptr, int64_t *count);
 BPRX_API int bprx_step_end(bprx_handle *h, float *loss_out, void *stream);
 /* _begin itself in two halves (bprx_step_begin == _begin_sparse + _begin_dense), so that a collective on the user-side
    gradients overlaps the backward projection:
@@ -987,6 +992,12 @@ BPRX_API int bprx_topk(bprx_handle *h, int32_t u0, int32_t u1, float *scores, co
 BPRX_API int64_t bprx_probe_stream_read(const void *buf, int64_t bytes, void *sink, void *stream);
 /* ... with `nt` (streaming, no-retain) loads, the policy of the bf16 feature passes */
 BPRX_API int64_t bprx_probe_stream_read_nt(const void *buf, int64_t bytes, void *sink, void *stream);
+/* ... with `nt` loads and the launch shape as arguments: `workgroups` (1..512) of `threads` (a multiple of 64, 64..1024), each
+   lane keeping `loads_in_flight` (1, 2, 3, 4, 6, 8, 12 or 16) 16-byte loads outstanding -- workgroups * threads *
+   loads_in_flight * 16 bytes in flight on the device (scripts/nt_inflight_sweep.py).  buf[0, bytes) must hold at least one
+   loop trip of every workgroup; the launch reads whole trips only.  Returns the bytes read, or a negative BPRX_E_* code. */
+BPRX_API int64_t bprx_probe_stream_read_nt_shape(const void *buf, int64_t bytes, int32_t workgroups, int32_t threads,
+                                                 int32_t loads_in_flight, void *sink, void *stream);
 /* Measurement helper: n lane groups each move one row of table[num_rows][row_floats] (fp32, row_floats a multiple of 4)
    picked by idx[] -- mode 0: read; mode 1: read and write back in place (idx distinct).  The access shape of the sparse
    kernels (a table row per index): the rate quoted beside their gather/scatter roofline.  Returns the bytes moved. */
