@@ -1918,9 +1918,7 @@ extern "C" int bprx_acf_fold_in(bprx_handle *h, const int64_t *hist_ptr, const i
                                 int32_t optimizer, float *Gu_rows, float *loss, void *stream) {
   if (!h) return BPRX_E_INVALID;
   int rc;
-  if ((rc = acf_rows_args(h, "acf_fold_in", n))) return rc;
-  if (steps < 1) BPRX_FAIL(h, BPRX_E_INVALID, "acf_fold_in: steps = %d < 1", steps);
-  if (optimizer != BPRX_OPT_SGD && optimizer != BPRX_OPT_ADAM_TF23) BPRX_FAIL(h, BPRX_E_INVALID, "acf_fold_in: optimizer %d", optimizer);
+  if ((rc = fold_check_args(h, "acf_fold_in", n, steps, optimizer))) return rc;
   if (!hist_ptr || !pair_ptr || !Gu_rows) BPRX_FAIL(h, BPRX_E_INVALID, "acf_fold_in: null pointer");
   if (n && (!hist_items || !pos || !neg)) BPRX_FAIL(h, BPRX_E_INVALID, "acf_fold_in: null pointer");
   hipStream_t s = (hipStream_t)stream;

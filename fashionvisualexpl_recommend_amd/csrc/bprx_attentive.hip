@@ -22,7 +22,7 @@
 //   k_af_fold         bprx_af_fold_in: one workgroup per new user, one wave per pair: attention forward + backward for the user's
 //                     row only, the item side and the encodings frozen, the row's optimiser steps in registers
 //   k_af_item_pairs   bprx_af_fold_in_items: one wave per pair of a new item, two attention forwards -> the pair's (D_p, dc_p) of
-//                     the linear fit in Gi_r (the step loop is k_af_fold_items, bprx_foldin.hip)
+//                     the linear fit in Gi_r (the step loop is k_fold_fit over AfItemRow, bprx_foldin.hip)
 //   k_af_block<., TR> bprx_af_audience_block: the same block for an item window, stored item-major
 #include <climits>
 
@@ -1067,7 +1067,7 @@ __global__ __launch_bounds__(256) void k_af_fold(AfFold F) {
 // ---- items the model was not trained on, once they have first buyers (bprx_af_fold_in_items) ----------------------------------
 // alpha is computed from g_u and the encodings only, so x_ur = Gi_r . m(u, r) is linear in the new item's row: with everything
 // else frozen a pair is the (D_p, dc_p) of bprx_fold_in_items' linear-logistic fit, formed ONCE here, one wave per pair; the step
-// loop (k_af_fold_items, bprx_foldin.hip) reads them from `work` [pairs, KW] = [D_p (k) | dc_p | zeros].
+// loop (k_fold_fit over AfItemRow, bprx_foldin.hip) reads them from `work` [pairs, KW] = [D_p (k) | dc_p | zeros].
 // LDS of a wave (8k floats): g_u | the new item's three encoding rows | the other item's three rows from Call | Gi_o.
 struct AfItemPairs {
   AfAtt A;                        // C = Call [3, I, k]; Gu, Gi the bound tables
@@ -1612,13 +1612,12 @@ constexpr size_t AF_FOLD_LDS = 40 * 1024;
 extern "C" int bprx_af_fold_in(bprx_handle *h, const int64_t *pair_ptr, const int32_t *pos, const int32_t *neg, int64_t n, int32_t steps,
                                float lr, float reg, int32_t optimizer, float *Gu_rows, float *loss, void *stream) {
   if (!h) return BPRX_E_INVALID;
-  if (n < 0 || n >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in: n = %lld out of range", (long long)n);
-  if (steps < 1) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in: steps = %d < 1", steps);
-  if (optimizer != BPRX_OPT_SGD && optimizer != BPRX_OPT_ADAM_TF23) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in: optimizer %d", optimizer);
+  int rc = fold_check_args(h, "af_fold_in", n, steps, optimizer);
+  if (rc) return rc;
   if (!pair_ptr || !Gu_rows) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in: null pointer");
   if (n && (!pos || !neg)) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  int rc = bprx_enter(h, "af_fold_in", NEED_BOUND, KIND_AF, s);
+  rc = bprx_enter(h, "af_fold_in", NEED_BOUND, KIND_AF, s);
   if (rc || n == 0) return rc;
   if ((rc = af_call_current(h, s))) return rc;               // the encodings the scores are computed from
   AfState *S = h->af;
@@ -1680,13 +1679,12 @@ extern "C" int bprx_af_fold_in_items(bprx_handle *h, const int64_t *pair_ptr, co
                                      int64_t n, const float *C_rows, int32_t steps, float lr, float reg, int32_t optimizer, float *Gi_rows,
                                      float *loss, float *work, void *stream) {
   if (!h) return BPRX_E_INVALID;
-  if (n < 0 || n >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in_items: n = %lld out of range", (long long)n);
-  if (steps < 1) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in_items: steps = %d < 1", steps);
-  if (optimizer != BPRX_OPT_SGD && optimizer != BPRX_OPT_ADAM_TF23) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in_items: optimizer %d", optimizer);
+  int rc = fold_check_args(h, "af_fold_in_items", n, steps, optimizer);
+  if (rc) return rc;
   if (!pair_ptr) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in_items: null pointer");
   if (n && (!user || !other || !role || !Gi_rows || !C_rows || !work)) BPRX_FAIL(h, BPRX_E_INVALID, "af_fold_in_items: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  int rc = bprx_enter(h, "af_fold_in_items", NEED_BOUND, KIND_AF, s);
+  rc = bprx_enter(h, "af_fold_in_items", NEED_BOUND, KIND_AF, s);
   if (rc || n == 0) return rc;
   if ((rc = af_call_current(h, s))) return rc;               // the encodings the scores are computed from
   AfState *S = h->af;

@@ -349,6 +349,14 @@ struct BprxProfScope {
     if (e__ != hipSuccess) BPRX_FAIL(h, BPRX_E_HIP, "launch %s: %s", name, hipGetErrorString(e__)); \
   } while (0)
 
+// The argument checks every fold-in entry point shares (`what`: the entry's name in the messages).
+static inline int fold_check_args(bprx_handle *h, const char *what, int64_t n, int32_t steps, int32_t optimizer) {
+  if (n < 0 || n >= ((int64_t)1 << 31)) BPRX_FAIL(h, BPRX_E_INVALID, "%s: n = %lld out of range", what, (long long)n);
+  if (steps < 1) BPRX_FAIL(h, BPRX_E_INVALID, "%s: steps = %d < 1", what, steps);
+  if (optimizer != BPRX_OPT_SGD && optimizer != BPRX_OPT_ADAM_TF23) BPRX_FAIL(h, BPRX_E_INVALID, "%s: optimizer %d", what, optimizer);
+  return BPRX_OK;
+}
+
 // ---- launchers implemented in the kernel translation units ----
 // sparse part (bprx_sparse.hip)
 int bprx_launch_score(bprx_handle *h, const int32_t *u, const int32_t *i, int64_t B, const float *Prow,
@@ -421,7 +429,7 @@ int bprx_af_pairs(bprx_handle *h, const int32_t *u, const int32_t *i, int64_t n,
 int bprx_af_block(bprx_handle *h, int32_t u0, int32_t u1, float *out, float *alpha, hipStream_t s, const float *Gu_rows = nullptr);
 void bprx_af_invalidate(bprx_handle *h);
 void bprx_af_free(bprx_handle *h);
-// The step loop of bprx_af_fold_in_items (k_af_fold_items, bprx_foldin.hip, next to the fold_group it shares with k_fold_items):
+// The step loop of bprx_af_fold_in_items (k_fold_fit over AfItemRow, bprx_foldin.hip):
 // work [pair_ptr[n], KW] holds [D_p (k) | dc_p | zeros] of every pair, Gi_rows [n, k] in / out, loss [n] or nullptr
 int bprx_launch_af_fold_items(bprx_handle *h, const int64_t *pair_ptr, int64_t n, const float *work, int KW, int k, int steps, bool adam,
                               float lr, float reg, float *Gi_rows, float *loss, hipStream_t s);

@@ -376,6 +376,24 @@ class Engine:
                                  *(_addr(t) for _, t, _ in rows), _addr(loss), _stream()))
         return loss
 
+    def _fold_in_items(self, what, pair_ptr, user, other, role, n, lr, reg, optimizer, want_loss, call):
+        """The body of fold_in_items / af_fold_in_items (`what`, for the messages) for n checked item rows: (loss, what
+        call(ptr, user, other, role: addresses, pairs given, lr, reg, optimizer: resolved, loss: fp32 [n] or None) returned)."""
+        ptr = torch.as_tensor(pair_ptr, dtype=torch.int64).to(self.device).contiguous()
+        if int(ptr.numel()) - 1 != n:
+            raise ValueError("%s: pair_ptr for %d items, rows for %d" % (what, int(ptr.numel()) - 1, n))
+        u_, o_, r_ = (as_index(x, self.device) for x in (user, other, role))
+        if not u_.numel() == o_.numel() == r_.numel():
+            raise ValueError("%s: %d users, %d items, %d roles" % (what, u_.numel(), o_.numel(), r_.numel()))
+        pairs = int(u_.numel())
+        lr = self._hyper()[0] if lr is None else float(lr)
+        reg = self._hyper()[1] if reg is None else float(reg)
+        opt = _ffi.OPTIMIZER[self.optimizer if optimizer is None else optimizer]
+        loss = torch.empty(n, dtype=torch.float32, device=self.device) if want_loss else None
+        if pairs == 0:                                       # (no item has a pair: the library still wants the pointers)
+            u_ = o_ = r_ = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return loss, call(_addr(ptr), _addr(u_), _addr(o_), _addr(r_), pairs, lr, reg, opt, loss)
+
     def acf_fold_in(self, pair_ptr, pos, neg, steps, Gu_rows, lists=None, csr=None, lr=None, reg=None, optimizer=None,
                     want_loss=True):
         """bprx_acf_fold_in: `steps` optimiser steps on each row of Gu_rows [n, k] (a contiguous fp32 device tensor, updated IN
@@ -544,26 +562,18 @@ class Engine:
         (loss_steps, before the last update) or None; with want_work=True (loss, work)."""
         n = self._af_item_rows("af_fold_in_items", C_rows, Gi_rows)
         ptr_host = torch.as_tensor(pair_ptr, dtype=torch.int64).cpu()
-        if int(ptr_host.numel()) - 1 != n:
-            raise ValueError("af_fold_in_items: pair_ptr for %d items, rows for %d" % (int(ptr_host.numel()) - 1, n))
-        ptr = ptr_host.to(self.device).contiguous()
-        u_, o_, r_ = (as_index(x, self.device) for x in (user, other, role))
-        if not u_.numel() == o_.numel() == r_.numel():
-            raise ValueError("af_fold_in_items: %d users, %d items, %d roles" % (u_.numel(), o_.numel(), r_.numel()))
-        pairs = int(ptr_host[-1]) if n >= 0 and ptr_host.numel() else 0
-        if pairs != u_.numel():
-            raise ValueError("af_fold_in_items: pair_ptr ends at %d, %d pairs given" % (pairs, u_.numel()))
-        lr = self._hyper()[0] if lr is None else float(lr)
-        reg = self._hyper()[1] if reg is None else float(reg)
-        opt = _ffi.OPTIMIZER[self.optimizer if optimizer is None else optimizer]
-        loss = torch.empty(n, dtype=torch.float32, device=self.device) if want_loss else None
-        work = torch.empty((max(pairs, 1), self.af_work_stride()), dtype=torch.float32, device=self.device)
-        if u_.numel() == 0:                                  # (no item has a pair: the library still wants the pointers)
-            u_ = o_ = r_ = torch.zeros(1, dtype=torch.int32, device=self.device)
-        _ffi.check(self.h, self.lib.bprx_af_fold_in_items(self.h, _addr(ptr), _addr(u_), _addr(o_), _addr(r_), n, _addr(C_rows),
-                                                          int(steps), lr, reg, opt, _addr(Gi_rows), _addr(loss), _addr(work),
-                                                          _stream()))
-        return (loss, work[:pairs]) if want_work else loss
+
+        def call(ptr, u_, o_, r_, given, lr, reg, opt, loss):
+            pairs = int(ptr_host[-1])
+            if pairs != given:
+                raise ValueError("af_fold_in_items: pair_ptr ends at %d, %d pairs given" % (pairs, given))
+            work = torch.empty((max(pairs, 1), self.af_work_stride()), dtype=torch.float32, device=self.device)
+            _ffi.check(self.h, self.lib.bprx_af_fold_in_items(self.h, ptr, u_, o_, r_, n, _addr(C_rows), int(steps), lr, reg, opt,
+                                                              _addr(Gi_rows), _addr(loss), _addr(work), _stream()))
+            return work[:pairs]
+
+        loss, work = self._fold_in_items("af_fold_in_items", ptr_host, user, other, role, n, lr, reg, optimizer, want_loss, call)
+        return (loss, work) if want_work else loss
 
     def af_score_warm_block(self, u0, u1, C_rows, Gi_rows, want_alpha=True):
         """bprx_af_score_warm_block: af_score_block for caller-owned item rows: scores [u1 - u0, n] and attentions [u1 - u0, n, 3]
@@ -772,21 +782,9 @@ class Engine:
         batch loss and oscillates once lr * 0.25 * pairs * (1 + |Gu|^2) passes 2: few pairs or a small lr; Adam does not care.
         Returns loss fp32 [n] (loss_steps, before the last update) or None."""
         n = self._warm_rows("fold_in_items", Gi_rows, Bi_rows, Pn)
-        ptr = torch.as_tensor(pair_ptr, dtype=torch.int64).to(self.device).contiguous()
-        if int(ptr.numel()) - 1 != n:
-            raise ValueError("fold_in_items: pair_ptr for %d items, rows for %d" % (int(ptr.numel()) - 1, n))
-        u_, o_, r_ = (as_index(x, self.device) for x in (user, other, role))
-        if not u_.numel() == o_.numel() == r_.numel():
-            raise ValueError("fold_in_items: %d users, %d items, %d roles" % (u_.numel(), o_.numel(), r_.numel()))
-        lr = self._hyper()[0] if lr is None else float(lr)
-        reg = self._hyper()[1] if reg is None else float(reg)
-        opt = _ffi.OPTIMIZER[self.optimizer if optimizer is None else optimizer]
-        loss = torch.empty(n, dtype=torch.float32, device=self.device) if want_loss else None
-        if u_.numel() == 0:                                  # (no item has a pair: the library still wants the pointers)
-            u_ = o_ = r_ = torch.zeros(1, dtype=torch.int32, device=self.device)
-        _ffi.check(self.h, self.lib.bprx_fold_in_items(self.h, _addr(ptr), _addr(u_), _addr(o_), _addr(r_), n, _addr(Pn), int(steps),
-                                                       lr, reg, opt, _addr(Gi_rows), _addr(Bi_rows), _addr(loss), _stream()))
-        return loss
+        call = lambda ptr, u_, o_, r_, _, lr, reg, opt, loss: _ffi.check(self.h, self.lib.bprx_fold_in_items(
+            self.h, ptr, u_, o_, r_, n, _addr(Pn), int(steps), lr, reg, opt, _addr(Gi_rows), _addr(Bi_rows), _addr(loss), _stream()))
+        return self._fold_in_items("fold_in_items", pair_ptr, user, other, role, n, lr, reg, optimizer, want_loss, call)[0]
 
     def score_warm_block(self, u0, u1, Gi_rows, Bi_rows, Pn=None, out=None):
         """bprx_score_warm_block: fp32 [u1 - u0, n], out[u][j] = Bi_j + Gu_u.Gi_j + Tu_u.Pn[j, :d] + Pn[j, d] for caller-owned item

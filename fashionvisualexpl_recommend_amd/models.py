@@ -501,25 +501,41 @@ class BPRMF(RecommenderModel):
         return self._owners_of
 
     def audience(self, items=None, k=None):
-        """The k (default: params.audience, else top_k) users with the highest score for each item of `items` (None: the whole
-        catalogue, in id order), the item's owners (the users whose training list names it) excluded: numpy ids int64 [n, kk] and
-        vals fp32 [n, kk], kk = min(k, U), best first; an item with fewer than kk non-owners has -1 / -inf in the slots past them.
-        The scores are predict_all's, item-major (Engine.audience_block); the catalogue is walked in blocks of item rows, every
-        block listed by ranking.rank_rows with Engine.topk_rows_masked and the block's owner lists; an explicit id list ranks the
-        blocks that hold its ids and keeps those rows."""
+        """The k (default: params.audience (AttentiveFashion: af_audience), else top_k) users with the highest score for each item
+        of `items` (None: the whole catalogue, in id order), the item's owners (the users whose training list names it) excluded:
+        numpy ids int64 [n, kk] and vals fp32 [n, kk], kk = min(k, U), best first; AttentiveFashion adds alpha fp32 [n, kk, 3]
+        (colour, edges, class); an item with fewer than kk non-owners has -1 / -inf in the slots past them.  The scores are
+        predict_all's, item-major (Engine.audience_block; AttentiveFashion: af_score_block's, Engine.af_audience_block); the
+        catalogue is walked in blocks of item rows, every block listed by ranking.rank_rows with Engine.topk_rows_masked and the
+        block's owner lists; an explicit id list ranks the blocks that hold its ids and keeps those rows."""
         eng, I, U = self.engine, self.num_items, self.num_users
         k = (self.audience_k or self.evaluator.k) if k is None else int(k)
         want = np.arange(I, dtype=np.int64) if items is None else np.asarray(items, dtype=np.int64).reshape(-1)
         if want.size and (want.min() < 0 or want.max() >= I):
             raise ValueError("audience: item ids lie in [0, %d)" % I)
-        ids, vals = ranked_zeros(want.size, min(k, U))
+        out = ranked_zeros(want.size, min(k, U), self.warm_side)
         owners = self._owners() if want.size else None
         for b0, b1, rows, local in wanted_blocks(want, I, self.evaluator.user_block, U):
             own = eng.csr(owners[b0:b1])
-            bi, bv, _ = rank_rows(lambda s, kq: eng.topk_rows_masked(s, own, kq), eng.audience_block(b0, b1), k)
-            ids[rows], vals[rows] = bi[local], bv[local]
-        ids[vals == -np.inf] = -1                                # (a masked entry reached the list: the row came through numpy)
-        return ids, vals
+            sc, side = self._audience_block(b0, b1)
+            for o, res in zip(out, rank_rows(lambda s, kq: eng.topk_rows_masked(s, own, kq), sc, k, side)):
+                o[rows] = res[local]
+        out[0][out[1] == -np.inf] = -1                           # (a masked entry reached the list: the row came through numpy)
+        return out
+
+    warm_side = 0                                                # columns of the side the three block hooks below return; 0: none
+
+    def _audience_block(self, b0, b1):
+        """(scores [b1 - b0, U], side [b1 - b0, U, c] or None) of the catalogue items [b0, b1), item-major."""
+        return self.engine.audience_block(b0, b1), None
+
+    def _score_warm_block(self, rows, b0, b1):
+        """(scores [b1 - b0, n], side or None) of the users [b0, b1) for the warm rows fold_in_items returned."""
+        return self.engine.score_warm_block(b0, b1, *rows), None
+
+    def _audience_warm_block(self, rows, b0, b1):
+        """(scores [b1 - b0, U], side or None) of the warm rows [b0, b1) of what fold_in_items returned, item-major."""
+        return self.engine.audience_warm_block(*rows, b0, b1), None
 
     def _store_audience(self, path):
         """params.audience = K > 0: audience-* next to the recs-* file at `path`, rows 'i\tu\tscore', item by item (the ids of
@@ -562,43 +578,47 @@ class BPRMF(RecommenderModel):
 
     def recommend_warm(self, buyers, features=None, k=None, **fold):
         """The k (default top_k) best warm items of every user, the ones the user bought masked: numpy ids int64 [U, kk] (rows of
-        `buyers`) and vals fp32 [U, kk], kk = min(k, n), best first, -1 / -inf past a user's unmasked items.  The rows are fitted
-        by fold_in_items(buyers, features, **fold), scored by Engine.score_warm_block and listed by ranking.rank_rows with
+        `buyers`) and vals fp32 [U, kk] (AttentiveFashion: and alpha fp32 [U, kk, 3], colour, edges, class), kk = min(k, n), best
+        first, -1 / -inf past a user's unmasked items.  The rows are fitted by fold_in_items(buyers, features, **fold), scored by
+        Engine.score_warm_block (AttentiveFashion: Engine.af_score_warm_block) and listed by ranking.rank_rows with
         Engine.topk_rows_masked."""
         return self._rank_warm_recs(self.fold_in_items(buyers, features, **fold), buyers, k)
 
     def audience_warm(self, buyers, features=None, k=None, **fold):
-        """The k (default: params.audience, else top_k) users with the highest score for every warm item, its buyers masked: numpy
-        ids int64 [n, kk] and vals fp32 [n, kk], kk = min(k, U), best first, -1 / -inf past an item's non-buyers.  Fitted as
-        recommend_warm fits, scored item-major by Engine.audience_warm_block."""
+        """The k (default: params.audience (AttentiveFashion: af_audience), else top_k) users with the highest score for every
+        warm item, its buyers masked: numpy ids int64 [n, kk] and vals fp32 [n, kk] (AttentiveFashion: and alpha fp32 [n, kk, 3]),
+        kk = min(k, U), best first, -1 / -inf past an item's non-buyers.  Fitted as recommend_warm fits, scored item-major by
+        Engine.audience_warm_block (AttentiveFashion: Engine.af_audience_block)."""
         return self._rank_warm_audience(self.fold_in_items(buyers, features, **fold), buyers, k)
 
     def _rank_warm_recs(self, rows, buyers, k=None):
         """recommend_warm's lists for the fitted rows of fold_in_items(buyers): the rows are only read, one fit serves both lists."""
         eng, U, n = self.engine, self.num_users, len(buyers)
         k = self.evaluator.k if k is None else int(k)
-        ids, vals = ranked_zeros(U, min(k, n))
+        out = ranked_zeros(U, min(k, n), self.warm_side)
         if n == 0:
-            return ids, vals
+            return out
         bought = owners_of(buyers, U)                            # per user the warm items that user bought
         for b0, b1 in blocks(U, self.evaluator.user_block, n):
             own = eng.csr(bought[b0:b1])
-            ids[b0:b1], vals[b0:b1], _ = rank_rows(lambda s, kq: eng.topk_rows_masked(s, own, kq),
-                                                   eng.score_warm_block(b0, b1, *rows), k)
-        ids[vals == -np.inf] = -1
-        return ids, vals
+            sc, side = self._score_warm_block(rows, b0, b1)
+            for o, res in zip(out, rank_rows(lambda s, kq: eng.topk_rows_masked(s, own, kq), sc, k, side)):
+                o[b0:b1] = res
+        out[0][out[1] == -np.inf] = -1
+        return out
 
     def _rank_warm_audience(self, rows, buyers, k=None):
         """audience_warm's lists for the fitted rows of fold_in_items(buyers)."""
         eng, U, n = self.engine, self.num_users, len(buyers)
         k = (self.audience_k or self.evaluator.k) if k is None else int(k)
-        ids, vals = ranked_zeros(n, min(k, U))
+        out = ranked_zeros(n, min(k, U), self.warm_side)
         for b0, b1 in blocks(n, self.evaluator.user_block, U):
             own = eng.csr([list(dict.fromkeys(int(u) for u in who)) for who in buyers[b0:b1]])
-            ids[b0:b1], vals[b0:b1], _ = rank_rows(lambda s, kq: eng.topk_rows_masked(s, own, kq),
-                                                   eng.audience_warm_block(*rows, b0, b1), k)
-        ids[vals == -np.inf] = -1
-        return ids, vals
+            sc, side = self._audience_warm_block(rows, b0, b1)
+            for o, res in zip(out, rank_rows(lambda s, kq: eng.topk_rows_masked(s, own, kq), sc, k, side)):
+                o[b0:b1] = res
+        out[0][out[1] == -np.inf] = -1
+        return out
 
     warm_param = "warm_items"                                    # the params entry that names the first buyers' file
 
@@ -1549,64 +1569,16 @@ class AttentiveFashion(BPRMF):
                              want_loss=False)
         return Gi, C
 
-    def recommend_warm(self, buyers, features=None, k=None, **fold):
-        """The k (default top_k) best warm items of every user, the ones the user bought masked: numpy ids int64 [U, kk] (rows of
-        `buyers`), vals fp32 [U, kk] and alpha fp32 [U, kk, 3] (colour, edges, class), kk = min(k, n), best first, -1 / -inf past a
-        user's unmasked items.  Fitted by fold_in_items(buyers, features, **fold), scored by Engine.af_score_warm_block."""
-        return self._rank_warm_recs(self.fold_in_items(buyers, features, **fold), buyers, k)
+    warm_side = 3                                                # (Gi_new, C_new) rows; every block comes with its attentions
 
-    def audience_warm(self, buyers, features=None, k=None, **fold):
-        """The k (default: params.af_audience, else top_k) users with the highest score for every warm item, its buyers masked:
-        numpy ids int64 [n, kk], vals fp32 [n, kk] and alpha fp32 [n, kk, 3], kk = min(k, U), best first, -1 / -inf past an item's
-        non-buyers.  Fitted as recommend_warm fits, scored item-major by Engine.af_audience_block."""
-        return self._rank_warm_audience(self.fold_in_items(buyers, features, **fold), buyers, k)
+    def _score_warm_block(self, rows, b0, b1):
+        return self.engine.af_score_warm_block(b0, b1, rows[1], rows[0])
 
-    def _rank_warm_recs(self, rows, buyers, k=None):
-        eng, U, n = self.engine, self.num_users, len(buyers)
-        Gi, Cn = rows
-        k = self.evaluator.k if k is None else int(k)
-        ids, vals, att = ranked_zeros(U, min(k, n), 3)
-        if n == 0:
-            return ids, vals, att
-        bought = owners_of(buyers, U)                            # per user the warm items that user bought
-        for b0, b1 in blocks(U, self.evaluator.user_block, n):
-            own = eng.csr(bought[b0:b1])
-            sc, al = eng.af_score_warm_block(b0, b1, Cn, Gi)
-            ids[b0:b1], vals[b0:b1], att[b0:b1] = rank_rows(lambda s, kq: eng.topk_rows_masked(s, own, kq), sc, k, side=al)
-        ids[vals == -np.inf] = -1
-        return ids, vals, att
+    def _audience_warm_block(self, rows, b0, b1):
+        return self.engine.af_audience_block(b0, b1, rows[1], rows[0])
 
-    def _rank_warm_audience(self, rows, buyers, k=None):
-        eng, U, n = self.engine, self.num_users, len(buyers)
-        Gi, Cn = rows
-        k = (self.audience_k or self.evaluator.k) if k is None else int(k)
-        ids, vals, att = ranked_zeros(n, min(k, U), 3)
-        for b0, b1 in blocks(n, self.evaluator.user_block, U):
-            own = eng.csr([list(dict.fromkeys(int(u) for u in who)) for who in buyers[b0:b1]])
-            sc, al = eng.af_audience_block(b0, b1, Cn, Gi)
-            ids[b0:b1], vals[b0:b1], att[b0:b1] = rank_rows(lambda s, kq: eng.topk_rows_masked(s, own, kq), sc, k, side=al)
-        ids[vals == -np.inf] = -1
-        return ids, vals, att
-
-    def audience(self, items=None, k=None):
-        """The k (default: params.af_audience, else top_k) users with the highest score for each item of `items` (None: the whole
-        catalogue, in id order), the item's owners excluded: numpy ids int64 [n, kk], vals fp32 [n, kk] and alpha fp32 [n, kk, 3],
-        kk = min(k, U), best first, -1 / -inf past an item's non-owners.  The scores are af_score_block's, item-major
-        (Engine.af_audience_block)."""
-        eng, I, U = self.engine, self.num_items, self.num_users
-        k = (self.audience_k or self.evaluator.k) if k is None else int(k)
-        want = np.arange(I, dtype=np.int64) if items is None else np.asarray(items, dtype=np.int64).reshape(-1)
-        if want.size and (want.min() < 0 or want.max() >= I):
-            raise ValueError("audience: item ids lie in [0, %d)" % I)
-        ids, vals, att = ranked_zeros(want.size, min(k, U), 3)
-        owners = self._owners() if want.size else None
-        for b0, b1, rows, local in wanted_blocks(want, I, self.evaluator.user_block, U):
-            own = eng.csr(owners[b0:b1])
-            sc, al = eng.af_audience_block(b0, b1)
-            bi, bv, ba = rank_rows(lambda s, kq: eng.topk_rows_masked(s, own, kq), sc, k, side=al)
-            ids[rows], vals[rows], att[rows] = bi[local], bv[local], ba[local]
-        ids[vals == -np.inf] = -1
-        return ids, vals, att
+    def _audience_block(self, b0, b1):
+        return self.engine.af_audience_block(b0, b1)
 
     def _store_audience(self, path):
         """params.af_audience = K > 0: audience-* next to the recs-* file at `path`, rows 'i\tu\tscore\talpha_colour\talpha_edges\t
