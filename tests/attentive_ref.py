@@ -29,11 +29,18 @@ class AttentiveRef:
         self.slots, self.t = {}, 0
 
     # ---- encoders (AttentiveFashion.py:50-72) -------------------------------------------------------------------------
-    def pooled(self, p, items):
+    def pooled_rows(self, p, items):
+        """the literal form: every row's image through conv / relu / max-pool / mean (25.7 MB of float64 activation per row)"""
         x = (self.edges[items].to(self.dt) / 255.0).unsqueeze(1)                     # dataset.py:172 (/ np.float32(255))
         w = p["edges.conv"].reshape(5, 5, 64).permute(2, 0, 1).unsqueeze(1)          # [64, 1, 5, 5]
         y = torch.relu(Fn.conv2d(x, w, p["edges.conv_b"], padding=2))
         return Fn.max_pool2d(y, 2).mean((2, 3))
+
+    def pooled(self, p, items):
+        """the same function, the DISTINCT items pooled once and their rows gathered (tests/test_af_step_cases_cpu.py holds the
+        two forms equal)"""
+        uniq, inverse = torch.unique(torch.as_tensor(np.asarray(items)).long().reshape(-1), return_inverse=True)
+        return self.pooled_rows(p, uniq)[inverse]
 
     def encode(self, p, items, masks=None):
         items = torch.as_tensor(np.asarray(items)).long()

@@ -355,7 +355,14 @@ def test_errors_leave_the_handle_usable_and_no_allocation_behind():
     torch.cuda.synchronize()
     assert (oi == -777).all() and (oc == PATTERN).all() and (on == -777).all()      # no rejected call wrote anything
     usable()
-    assert call(e.h, c=None) == 0 and call(e.h, q=rn) == 0 and call(e.h, LL=32) == 0    # cnt may be NULL; rn_q may be given; L = 32
+    assert call(e.h, c=None) == 0 and call(e.h, q=rn) == 0                          # cnt may be NULL; rn_q may be given
+    # L = 32 writes n * K * 32 entries: outputs of its own size (oi / oc hold n * K * L and were written past their end here once,
+    # which faulted or not with where the allocator had put them)
+    wi = torch.full((n * K * 32 + GUARD,), -777, dtype=torch.int32, device="cuda")
+    wc = torch.full((n * K * 32 + GUARD,), PATTERN, dtype=torch.float32, device="cuda")
+    assert call(e.h, LL=32, a=wi, b=wc) == 0
+    torch.cuda.synchronize()
+    assert (wi[n * K * 32:] == -777).all() and (wc[n * K * 32:] == PATTERN).all() and not (wi[:n * K * 32] == -777).any()
     assert call(e.h, space=1, Pq=P, nq=4, q=rq, r=rv, l=torch.zeros_like(li)) == 0
     # handles of the wrong kind, fp8 in a space that reads P, unbound tables
     for eng, spaces, code in ((m, ("visual", "both"), _ffi.E_INVALID), (f8, ("visual", "both"), _ffi.E_INVALID),
