@@ -207,6 +207,9 @@ def lib():
         "bprx_step_lr": (C.c_int, [vp, vp]),
         "bprx_sample_philox_h": (C.c_int, [vp, vp, vp, vp, i64, i32, C.c_uint64, C.c_uint64, i64, vp, vp, vp, i64, i64, vp]),
         "bprx_sample_epoch_h": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, C.c_uint64, u32, i64, i64, vp, vp, vp, i64, i64, vp]),
+        "bprx_sample_philox_hard": (C.c_int, [vp, vp, vp, vp, i64, i32, C.c_uint64, C.c_uint64, i64, vp, vp, vp, i64, i64, vp, i32, vp, vp, vp]),
+        "bprx_sample_epoch_hard": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, C.c_uint64, u32, i64, i64, vp, vp, vp, i64, i64, vp, i32, vp, vp, vp]),
+        "bprx_hard_snapshot": (C.c_int, [vp, vp, vp]),
         "bprx_sampler_create": (C.c_int, [vp, vp, i32, i32, C.POINTER(vp)]),
         "bprx_sampler_destroy": (C.c_int, [vp]),
         "bprx_sampler_count": (i64, [vp, i32, i32]),
@@ -237,7 +240,8 @@ EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error",
            "bprx_route_scatter_add", "bprx_score_block", "bprx_eval_users", "bprx_eval_pos", "bprx_eval_counts", "bprx_eval_finish", "bprx_topk", "bprx_sync_check", "bprx_probe_stream_read", "bprx_probe_stream_read_nt", "bprx_probe_stream_read_nt_shape", "bprx_probe_row_gather", "bprx_profile_enable",
            "bprx_profile_read", "bprx_sample_philox", "bprx_epoch_prepare", "bprx_epoch_slots", "bprx_sample_epoch", "bprx_sample_philox_h", "bprx_sample_epoch_h", "bprx_index_pass_kind", "bprx_index_pass_queue", "bprx_proj_mask_kind", "bprx_adam_rows", "bprx_step_lr", "bprx_user_msg_floats", "bprx_pack_user_msg",
            "bprx_apply_user_msgs", "bprx_sampler_create",
-           "bprx_sampler_destroy", "bprx_sampler_count", "bprx_sampler_ref_stream", "bprx_settle", "bprx_dense_pending", "bprx_set_loss_lag"]
+           "bprx_sampler_destroy", "bprx_sampler_count", "bprx_sampler_ref_stream", "bprx_settle", "bprx_dense_pending", "bprx_set_loss_lag",
+           "bprx_sample_philox_hard", "bprx_sample_epoch_hard", "bprx_hard_snapshot"]
 
 
 def check(handle, rc):

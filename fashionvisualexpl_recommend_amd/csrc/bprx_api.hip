@@ -549,6 +549,19 @@ extern "C" int bprx_step_project(bprx_handle *h, void *stream) {
   return rc;
 }
 
+// The hard samplers' snapshot (bprx_philox.hip): Ps = F.[E|Bp] of every item from the tables as they are now, straight into the
+// caller's buffer.  Not NEED_P_ALL plus a copy of h->P: that would mark P current (p_valid) and so change the plan of the next
+// step (no masked projection, no catch-up beside it), and it would cost a second pass over I * PS floats.
+extern "C" int bprx_hard_snapshot(bprx_handle *h, float *Ps, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  const bool vb = h->cfg.model == BPRX_MODEL_VBPR && !h->acf && !h->af;
+  if (vb && h->bound && !Ps) BPRX_FAIL(h, BPRX_E_INVALID, "hard_snapshot: a VBPR handle needs a buffer [num_items, proj_stride]");
+  const int rc = bprx_enter(h, "hard_snapshot", NEED_BOUND | (vb ? NEED_ET : 0), KIND_PLAIN, s);
+  if (rc || !vb) return rc;
+  return bprx_launch_proj_fwd(h, nullptr, h->cfg.num_items, nullptr, 0, Ps, s);
+}
+
 extern "C" int bprx_user_grad(bprx_handle *h, float **dGu, float **dTu) {
   if (!h || !dGu || !dTu) return BPRX_E_INVALID;
   *dGu = h->dGu;

@@ -34,6 +34,32 @@ __device__ __forceinline__ int32_t nth_non_positive(const int32_t *__restrict__ 
   return x < I ? (int32_t)x : last;                       // (ids outside [0, I) in the list)
 }
 
+// The negative of stream position n, shared by the uniform and the hard kernels: the rejection draw over attempts a = 0, 1, ..
+// with the third counter word base + a, the nth_non_positive fallback at base + 1024.  base = 0 is the uniform samplers' stream;
+// candidate c of a hard sampler draws with base = c * 2048 (no word of one candidate is a word of another, nor the permutation's
+// 0xFFFFFFFE).  HAVE0: r already holds the block of attempt 0 (k_sample_philox draws the positive from the same block).
+template <bool HAVE0>
+__device__ __forceinline__ int32_t draw_negative(const int32_t *__restrict__ lst, long long len, uint32_t I, unsigned long long n,
+                                                 uint32_t base, uint32_t w3, uint32_t k0, uint32_t k1, uint32_t (&r)[4]) {
+  int32_t jj = 0;
+  bool hit = true;
+  for (uint32_t a = 0; a < 1024u && hit; ++a) {
+    if (!HAVE0 || a) philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), base + a, w3, k0, k1, r);
+    jj = (int32_t)__umulhi(r[2], I);
+    long long lo = 0, hi = len;
+    while (lo < hi) {
+      const long long mid = (lo + hi) >> 1;
+      if (lst[mid] < jj) lo = mid + 1; else hi = mid;
+    }
+    hit = lo < len && lst[lo] == jj;
+  }
+  if (hit) {
+    philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), base + 1024u, w3, k0, k1, r);
+    jj = nth_non_positive(lst, len, I, r[2], jj);
+  }
+  return jj;
+}
+
 // the owner plane (id >> sh: one byte) and the local plane (id & (2^sh - 1): a byte at sh == 8, else 16 bits) of a triplet's items
 __device__ __forceinline__ void put_planes(uint8_t *__restrict__ own8, uint8_t *__restrict__ loc8, long long pi, long long pj,
                                            int32_t ii, int32_t jj, int sh) {
@@ -55,6 +81,9 @@ struct QueueArgs {
   uint32_t *rec, *range;          // nullptr: no queues
   int q0, stride;                 // region of workgroup 0 of this launch, regions per owner in `range`
 };
+// WIDE (k_sample_hard): the workgroup has more than IXQ_BINS threads; hist has one entry per thread (those beyond the bins stay
+// zero), wtot one per wave, and only the first IXQ_BINS threads hold a triplet or store a range.
+template <bool WIDE = false>
 __device__ __forceinline__ void put_queues(const QueueArgs &q, int *hist, int *wtot, bool live, int32_t ii, int32_t jj,
                                            long long occ_i, long long occ_j) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -75,7 +104,7 @@ __device__ __forceinline__ void put_queues(const QueueArgs &q, int *hist, int *w
   for (int x = 0; x < wv; ++x) lo += wtot[x];
   hist[tid] = lo;                                                       // (my bin alone: nobody else reads it before the next barrier)
   const int region = q.q0 + (int)blockIdx.x;
-  q.range[ixq_range_at(tid, region, q.stride)] = ixq_range((uint32_t)lo, (uint32_t)(lo + c));
+  if (!WIDE || tid < IXQ_BINS) q.range[ixq_range_at(tid, region, q.stride)] = ixq_range((uint32_t)lo, (uint32_t)(lo + c));
   __syncthreads();
   if (live) {
     q.rec[ixq_rec_at(region, hist[bi] + ri)] = ixq_pack((uint32_t)occ_i, (uint32_t)ii);
@@ -104,21 +133,7 @@ __global__ __launch_bounds__(256) void k_sample_philox(const int64_t *__restrict
     const int32_t uu = pos_user[p];
     const long long lo0 = indptr[uu], len = indptr[uu + 1] - lo0;
     const int32_t *lst = items + lo0;
-    bool hit = true;
-    for (uint32_t a = 0; a < 1024u && hit; ++a) {
-      if (a) philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), a, 0u, k0, k1, r);
-      jj = (int32_t)__umulhi(r[2], I);
-      long long lo = 0, hi = len;
-      while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (lst[mid] < jj) lo = mid + 1; else hi = mid;
-      }
-      hit = lo < len && lst[lo] == jj;
-    }
-    if (hit) {
-      philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), 1024u, 0u, k0, k1, r);
-      jj = nth_non_positive(lst, len, I, r[2], jj);
-    }
+    jj = draw_negative<true>(lst, len, I, n, 0u, 0u, k0, k1, r);
     ii = items[p];
     u[b] = uu; i[b] = ii; j[b] = jj;
     if (own8) put_planes(own8, loc8, pl_i + b, pl_j + b, ii, jj, sh);   // byte planes of the item ids for the handle's index pass
@@ -157,26 +172,172 @@ __global__ __launch_bounds__(256) void k_sample_epoch(const int64_t *__restrict_
     const long long l0 = indptr[uu], len = indptr[uu + 1] - l0;
     const int32_t *lst = items + l0;
     uint32_t r[4];
-    bool hit = true;
-    for (uint32_t a = 0; a < 1024u && hit; ++a) {
-      philox4x32_10((uint32_t)n, (uint32_t)((unsigned long long)n >> 32), a, epoch, k0, k1, r);
-      jj = (int32_t)__umulhi(r[2], I);
-      long long l = 0, h = len;
-      while (l < h) {
-        const long long mid = (l + h) >> 1;
-        if (lst[mid] < jj) l = mid + 1; else h = mid;
-      }
-      hit = l < len && lst[l] == jj;
-    }
-    if (hit) {
-      philox4x32_10((uint32_t)n, (uint32_t)((unsigned long long)n >> 32), 1024u, epoch, k0, k1, r);
-      jj = nth_non_positive(lst, len, I, r[2], jj);
-    }
+    jj = draw_negative<false>(lst, len, I, (unsigned long long)n, 0u, epoch, k0, k1, r);
     ii = lst[n - epoch_ptr[lo]];
     u[b] = uu; i[b] = ii; j[b] = jj;
     if (own8) put_planes(own8, loc8, pl_i + b, pl_j + b, ii, jj, sh);
   }
   if (qa.rec) put_queues(qa, q_hist, q_wtot, live, ii, jj, pl_i + b, pl_j + b);
+}
+
+// ---- hard negatives (DESIGN §9 "Hard negatives"): the best-scored of C candidates ----
+// The hard forms of the two kernels above.  The user and the positive of stream position n are the uniform stream's; candidate c
+// (0 <= c < C <= 16) of the position is draw_negative with base = c * 2048 (candidate 0 is the uniform negative), and the triplet's
+// negative is the candidate with the largest
+//   s_c = Gu_u.Gi_j + Bi_j (+ Tu_u.Ps_j[:d] + Ps_j[d]: VBPR, Ps = the caller's snapshot of the item projections),
+// ties to the smallest c, a NaN never ahead of a number.  The tables are read AS STORED (no lazy-Adam catch-up).  One workgroup =
+// 256 triplets (a region of put_queues) and 1 024 threads -- sixteen waves on a CU whose batch of 65 536 gives it one workgroup: the
+// draws and the row reads are chains of dependent loads, and four waves hide none of them -- in three phases:
+//   1  four threads per triplet (t, t + 256, ..) look its user up and draw every fourth candidate each into LDS;
+//   2  a group of 16 lanes per triplet, 4 triplets per group: a lane keeps its slice of the user's row in registers and reads the
+//      same slice of up to eight candidate rows before the first use (float4 slices where k / d are multiples of 4 and the tables
+//      16-byte aligned, single floats otherwise), sums in the group by shuffles, picks;
+//   3  thread t < 256 writes (u, i, j) and the planes and queue records of the chosen negative, exactly as the uniform kernels do.
+constexpr int HARD_MAX_C = 16;
+constexpr int HARD_T = 1024;                        // threads of a workgroup
+
+struct StreamArgs {
+  const int64_t *indptr;
+  const int32_t *items, *pos_user;                  // pos_user: the Philox stream
+  const int32_t *perm, *pos_slot;                   // the epoch walk
+  const int64_t *epoch_ptr;
+  unsigned long long N, first;
+  int U;                                            // users of the epoch walk
+  uint32_t I, k0, k1, w3;                           // w3: 0, or the epoch
+};
+struct HardArgs {
+  const float *Gu, *Gi, *Bi, *Tu, *Ps;              // Tu == nullptr: BPRMF
+  int k, d, PS, C, U;                               // U, and StreamArgs::I: rows of the handle's tables (row reads are clamped to them)
+  int vec_k, vec_d;                                 // float4 slices of the k / d part
+  int32_t *cand_out;                                // [B, C] optional: what was drawn ...
+  float *score_out;                                 // [B, C] optional: ... and what was compared
+};
+
+__device__ __forceinline__ float dot_slice(float a, float b) { return a * b; }
+__device__ __forceinline__ float dot_slice(const float4 &a, const float4 &b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+
+// acc[c] += <urow, rows[cand[c]]> over n slices of type T, slice q of every row by lane q % 16 of the group; the rows of eight
+// candidates are in flight before the first multiply.  cand: the triplet's column of the LDS candidate table (stride 256).
+template <typename T>
+__device__ __forceinline__ void hard_dots(const T *__restrict__ urow, const T *__restrict__ rows, size_t stride, int n, const int *cand,
+                                          int C, int l16, float (&acc)[HARD_MAX_C]) {
+  for (int q = l16; q < n; q += 16) {
+    const T g = urow[q];
+#pragma unroll
+    for (int h = 0; h < HARD_MAX_C; h += 8) {
+      if (h < C) {
+        T v[8];
+#pragma unroll
+        for (int x = 0; x < 8; ++x)
+          if (h + x < C) v[x] = rows[(size_t)cand[(h + x) * 256] * stride + q];
+#pragma unroll
+        for (int x = 0; x < 8; ++x)
+          if (h + x < C) acc[h + x] += dot_slice(g, v[x]);
+      }
+    }
+  }
+}
+
+template <bool EPOCH>
+__global__ __launch_bounds__(HARD_T) void k_sample_hard(StreamArgs sa, HardArgs ha, long long B, int32_t *__restrict__ u,
+                                                        int32_t *__restrict__ i, int32_t *__restrict__ j, uint8_t *__restrict__ own8,
+                                                        uint8_t *__restrict__ loc8, long long pl_i, long long pl_j, int sh, QueueArgs qa) {
+  __shared__ int q_hist[HARD_T], q_wtot[HARD_T / 64];
+  __shared__ int s_cand[HARD_MAX_C * 256], s_user[256], s_neg[256];
+  const int tid = threadIdx.x, trip = tid & 255, part = tid >> 8;
+  const long long b0 = (long long)blockIdx.x * 256, b = b0 + trip;
+  const bool live = tid < 256 && b < B;
+  q_hist[tid] = 0;
+  int32_t uu = 0, ii = 0;
+  if (b < B) {                                            // phase 1
+    const unsigned long long n = sa.first + (unsigned long long)b;
+    uint32_t r[4];
+    const int32_t *lst;
+    long long len;
+    if (EPOCH) {
+      int lo = 0, hi = sa.U;
+      if (sa.pos_slot) lo = sa.pos_slot[n];
+      else
+        while (hi - lo > 1) {
+          const int mid = (lo + hi) >> 1;
+          if (sa.epoch_ptr[mid] <= (long long)n) lo = mid; else hi = mid;
+        }
+      uu = sa.perm[lo];
+      const long long l0 = sa.indptr[uu];
+      len = sa.indptr[uu + 1] - l0;
+      lst = sa.items + l0;
+      ii = lst[(long long)n - sa.epoch_ptr[lo]];
+    } else {
+      philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), 0u, 0u, sa.k0, sa.k1, r);
+      const unsigned long long p = __umul64hi(((unsigned long long)r[1] << 32) | r[0], sa.N);
+      uu = sa.pos_user[p];
+      const long long l0 = sa.indptr[uu];
+      len = sa.indptr[uu + 1] - l0;
+      lst = sa.items + l0;
+      ii = sa.items[p];
+    }
+    for (int c = part; c < ha.C; c += HARD_T / 256) {
+      const int32_t jc = draw_negative<false>(lst, len, sa.I, n, (uint32_t)c * 2048u, sa.w3, sa.k0, sa.k1, r);
+      s_cand[c * 256 + trip] = jc;
+      if (ha.cand_out) ha.cand_out[b * ha.C + c] = jc;
+    }
+    if (part == 0) s_user[trip] = uu;
+  }
+  __syncthreads();
+  {                                                       // phase 2
+    const int grp = tid >> 4, l16 = tid & 15;
+    const int C = ha.C;
+    for (int t = grp; t < 256 && b0 + t < B; t += HARD_T / 16) {
+      const int *cand = s_cand + t;
+      const size_t ur = (size_t)min(max(s_user[t], 0), ha.U - 1);
+      float acc[HARD_MAX_C];
+#pragma unroll
+      for (int c = 0; c < HARD_MAX_C; ++c) acc[c] = 0.f;
+      if (ha.vec_k)
+        hard_dots(reinterpret_cast<const float4 *>(ha.Gu + ur * ha.k), reinterpret_cast<const float4 *>(ha.Gi), (size_t)(ha.k >> 2),
+                  ha.k >> 2, cand, C, l16, acc);
+      else
+        hard_dots(ha.Gu + ur * ha.k, ha.Gi, (size_t)ha.k, ha.k, cand, C, l16, acc);
+      if (ha.Tu) {
+        if (ha.vec_d)
+          hard_dots(reinterpret_cast<const float4 *>(ha.Tu + ur * ha.d), reinterpret_cast<const float4 *>(ha.Ps), (size_t)(ha.PS >> 2),
+                    ha.d >> 2, cand, C, l16, acc);
+        else
+          hard_dots(ha.Tu + ur * ha.d, ha.Ps, (size_t)ha.PS, ha.d, cand, C, l16, acc);
+      }
+#pragma unroll
+      for (int c = 0; c < HARD_MAX_C; ++c)
+        if (c < C) {
+          if (l16 == 0) {                                 // the biases ride on one lane of the group
+            const size_t jc = (size_t)cand[c * 256];
+            acc[c] += ha.Bi[jc];
+            if (ha.Tu) acc[c] += ha.Ps[jc * ha.PS + ha.d];
+          }
+#pragma unroll
+          for (int o = 8; o; o >>= 1) acc[c] += __shfl_xor(acc[c], o, 16);
+        }
+      // largest wins, ties to the smallest c; a NaN only ever stays when nothing but NaNs follow
+      int best = 0;
+      float sb = acc[0];
+#pragma unroll
+      for (int c = 1; c < HARD_MAX_C; ++c)
+        if (c < C && (acc[c] > sb || (sb != sb && acc[c] == acc[c]))) { best = c; sb = acc[c]; }
+      if (l16 == 0) s_neg[t] = cand[best * 256];
+      if (ha.score_out) {
+#pragma unroll
+        for (int c = 0; c < HARD_MAX_C; ++c)
+          if (c < C && l16 == (c & 15)) ha.score_out[(b0 + t) * C + c] = acc[c];
+      }
+    }
+  }
+  __syncthreads();
+  int32_t jj = 0;
+  if (live) {                                             // phase 3
+    jj = s_neg[tid];
+    u[b] = uu; i[b] = ii; j[b] = jj;
+    if (own8) put_planes(own8, loc8, pl_i + b, pl_j + b, ii, jj, sh);
+  }
+  if (qa.rec) put_queues<true>(qa, q_hist, q_wtot, live, ii, jj, pl_i + b, pl_j + b);
 }
 
 // The user order of an epoch: a keyed permutation of [0, U) evaluated POINTWISE -- slot a of epoch `epoch` holds user
@@ -313,4 +474,79 @@ extern "C" int bprx_sample_philox(const int64_t *indptr, const int32_t *items_so
                                   int32_t *user, int32_t *pos, int32_t *neg, void *stream) {
   return bprx_sample_philox_h(nullptr, indptr, items_sorted, pos_user, num_pos, num_items, seed, first, B, user, pos, neg, 0, 0,
                               stream);
+}
+
+// ---- the hard samplers: bprx_sample_philox_hard / bprx_sample_epoch_hard (include/bprx.h) ----
+// Like the samplers above they stay outside the gate: nothing they read is written by a pending dense update, and a lazy-Adam
+// catch-up of every row per batch would undo the lazy replay -- the rows are scored as stored.
+static int hard_args(bprx_handle *h, const char *what, int32_t num_items, int32_t candidates, const float *Ps, int32_t *cand_out,
+                     float *score_out, HardArgs *ha) {
+  if (!h) return BPRX_E_INVALID;
+  const ReadPlan rp = plan_read(*h, NEED_BOUND, KIND_PLAIN);
+  if (rp.error) BPRX_FAIL(h, rp.error, rp.why, what);
+  if (h->cfg.flags & (BPRX_FLAG_EXPORT_USER_GRAD | BPRX_FLAG_EXPORT_ITEM_GRAD))
+    BPRX_FAIL(h, BPRX_E_INVALID, "%s: the handle's rows are staged by a multi-GPU driver, not the whole tables", what);
+  if (candidates < 1 || candidates > HARD_MAX_C)
+    BPRX_FAIL(h, BPRX_E_INVALID, "%s: candidates = %d outside [1, %d]", what, candidates, HARD_MAX_C);
+  if (num_items != h->cfg.num_items)
+    BPRX_FAIL(h, BPRX_E_INVALID, "%s: num_items = %d, the handle has %lld", what, num_items, (long long)h->cfg.num_items);
+  const bool vb = h->cfg.model == BPRX_MODEL_VBPR;
+  if (vb && !Ps) BPRX_FAIL(h, BPRX_E_INVALID, "%s: a VBPR handle needs the snapshot Ps (bprx_hard_snapshot)", what);
+  const int k = h->cfg.embed_k, d = vb ? h->cfg.embed_d : 0;
+  auto al16 = [](const void *p) { return ((uintptr_t)p & 15u) == 0; };
+  *ha = HardArgs{h->t.Gu, h->t.Gi, h->t.Bi, vb ? h->t.Tu : nullptr, vb ? Ps : nullptr, k, d, vb ? h->PS : 0, candidates,
+                 (int)h->cfg.num_users, k % 4 == 0 && al16(h->t.Gu) && al16(h->t.Gi), vb && d % 4 == 0 && al16(h->t.Tu) && al16(Ps),
+                 cand_out, score_out};
+  return BPRX_OK;
+}
+
+extern "C" int bprx_sample_philox_hard(bprx_handle *h, const int64_t *indptr, const int32_t *items_sorted, const int32_t *pos_user,
+                                       int64_t num_pos, int32_t num_items, uint64_t seed, uint64_t first, int64_t B, int32_t *user,
+                                       int32_t *pos, int32_t *neg, int64_t batch_offset, int64_t batch_size, void *stream,
+                                       int32_t candidates, const float *Ps, int32_t *cand_out, float *score_out) {
+  if (!h) return BPRX_E_INVALID;
+  if (!indptr || !items_sorted || !pos_user || !user || !pos || !neg || num_pos <= 0 || num_items <= 0 || B < 0)
+    BPRX_FAIL(h, BPRX_E_INVALID, "sample_philox_hard: null pointer or bad size");
+  HardArgs ha;
+  { const int rc = hard_args(h, "sample_philox_hard", num_items, candidates, Ps, cand_out, score_out, &ha); if (rc) return rc; }
+  if (B == 0) return BPRX_OK;
+  uint8_t *own8, *loc8;
+  long long pl_i, pl_j;
+  int sh;
+  QueueArgs qa;
+  plane_args(h, pos, neg, B, batch_offset, batch_size, &own8, &loc8, &pl_i, &pl_j, &sh, &qa);
+  StreamArgs sa = {};
+  sa.indptr = indptr; sa.items = items_sorted; sa.pos_user = pos_user;
+  sa.N = (unsigned long long)num_pos; sa.first = (unsigned long long)first;
+  sa.I = (uint32_t)num_items; sa.k0 = (uint32_t)seed; sa.k1 = (uint32_t)(seed >> 32); sa.w3 = 0u;
+  hipLaunchKernelGGL(k_sample_hard<false>, dim3((unsigned)((B + 255) / 256)), dim3(HARD_T), 0, (hipStream_t)stream, sa, ha, (long long)B,
+                     user, pos, neg, own8, loc8, pl_i, pl_j, sh, qa);
+  BPRX_LAUNCH_CHECK(h, "k_sample_hard<philox>");
+  return BPRX_OK;
+}
+
+extern "C" int bprx_sample_epoch_hard(bprx_handle *h, const int64_t *indptr, const int32_t *items_sorted, const int32_t *perm,
+                                      const int64_t *epoch_ptr, const int32_t *pos_slot, int32_t num_users, int32_t num_items,
+                                      uint64_t seed, uint32_t epoch, int64_t first, int64_t B, int32_t *user, int32_t *pos, int32_t *neg,
+                                      int64_t batch_offset, int64_t batch_size, void *stream, int32_t candidates, const float *Ps,
+                                      int32_t *cand_out, float *score_out) {
+  if (!h) return BPRX_E_INVALID;
+  if (!indptr || !items_sorted || !perm || !epoch_ptr || !user || !pos || !neg || num_users <= 0 || num_items <= 0 || B < 0 || first < 0)
+    BPRX_FAIL(h, BPRX_E_INVALID, "sample_epoch_hard: null pointer or bad size");
+  HardArgs ha;
+  { const int rc = hard_args(h, "sample_epoch_hard", num_items, candidates, Ps, cand_out, score_out, &ha); if (rc) return rc; }
+  if (B == 0) return BPRX_OK;
+  uint8_t *own8, *loc8;
+  long long pl_i, pl_j;
+  int sh;
+  QueueArgs qa;
+  plane_args(h, pos, neg, B, batch_offset, batch_size, &own8, &loc8, &pl_i, &pl_j, &sh, &qa);
+  StreamArgs sa = {};
+  sa.indptr = indptr; sa.items = items_sorted; sa.perm = perm; sa.epoch_ptr = epoch_ptr; sa.pos_slot = pos_slot;
+  sa.U = num_users; sa.first = (unsigned long long)first;
+  sa.I = (uint32_t)num_items; sa.k0 = (uint32_t)seed; sa.k1 = (uint32_t)(seed >> 32); sa.w3 = epoch;
+  hipLaunchKernelGGL(k_sample_hard<true>, dim3((unsigned)((B + 255) / 256)), dim3(HARD_T), 0, (hipStream_t)stream, sa, ha, (long long)B,
+                     user, pos, neg, own8, loc8, pl_i, pl_j, sh, qa);
+  BPRX_LAUNCH_CHECK(h, "k_sample_hard<epoch>");
+  return BPRX_OK;
 }

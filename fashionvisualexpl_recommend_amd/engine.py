@@ -1132,11 +1132,60 @@ class PhiloxSampler:
         self._handle = engine.h if engine is not None else None
         return self
 
-    def sample(self, B, first=None, out=None):
-        """B triplets starting at stream position `first` (default: continue).  Returns int32 device tensors."""
+    # ---- hard negatives (include/bprx.h bprx_sample_*_hard; DESIGN §9 "Hard negatives") ----
+    def hard(self, engine, candidates):
+        """Every negative becomes the best-scored of `candidates` (1..16) draws under the engine's model as stored (BPRMF, VBPR,
+        GradFashion); the user and the positive stay the uniform stream's, candidates == 1 is the uniform stream.  Implies
+        feeds(engine).  Returns self."""
+        self.feeds(engine)
+        self._engine, self._hard, self.snapshot, self._snapped = engine, int(candidates), None, False
+        return self
+
+    def refresh(self):
+        """bprx_hard_snapshot: the item projections the candidates are scored with (VBPR: `snapshot`, fp32 [I, proj_stride], a
+        tensor this sampler owns) are made again from the tables as they are now.  BPRMF has none; the call is then a check."""
+        eng = self._engine
+        if eng.d and self.snapshot is None:
+            self.snapshot = torch.zeros((eng.I, eng.proj_stride()), dtype=torch.float32, device=self.device)
+        _ffi.check(eng.h, self.lib.bprx_hard_snapshot(eng.h, _ptr(self.snapshot), _stream()))
+        self._snapped = True
+
+    def _hard_args(self, B, want_candidates):
+        """(candidates, Ps, cand, score) of one hard sample of B triplets; the first one takes the snapshot."""
+        if not self._snapped:
+            self.refresh()
+        C_ = self._hard
+        cand = torch.empty((B, C_), dtype=torch.int32, device=self.device) if want_candidates else None
+        score = torch.empty((B, C_), dtype=torch.float32, device=self.device) if want_candidates else None
+        return C_, self.snapshot, cand, score
+
+    @property
+    def position(self):
+        """The stream position of the next sample()."""
+        return self.next
+
+    def seek(self, position):
+        """Continue at stream position `position`; nothing is drawn."""
+        self.next = int(position)
+
+    def skip(self, B):
+        """Advance the stream by B triplets without drawing them (a resumed run's fast-forward)."""
+        self.seek(self.position + int(B))
+
+    def sample(self, B, first=None, out=None, want_candidates=False):
+        """B triplets starting at stream position `first` (default: continue).  Returns int32 device tensors (u, i, j); a hard
+        sampler asked for want_candidates returns (u, i, j, cand int32 [B, C], score fp32 [B, C]): what it drew and compared."""
         if first is None:
             first, self.next = self.next, self.next + B
         u, i, j = out if out is not None else tuple(torch.empty(B, dtype=torch.int32, device=self.device) for _ in range(3))
+        if getattr(self, "_hard", 0):
+            C_, ps, cand, score = self._hard_args(B, want_candidates)
+            _ffi.check(self._handle, self.lib.bprx_sample_philox_hard(
+                self._handle, _ptr(self.indptr), _ptr(self.items), _ptr(self.pos_user), self.num_pos, self.num_items, self.seed,
+                first, B, _ptr(u), _ptr(i), _ptr(j), 0, B, _stream(), C_, _ptr(ps), _ptr(cand), _ptr(score)))
+            return (u, i, j, cand, score) if want_candidates else (u, i, j)
+        if want_candidates:
+            raise ValueError("want_candidates needs a hard sampler: call hard(engine, candidates) first")
         rc = self.lib.bprx_sample_philox_h(getattr(self, "_handle", None), _ptr(self.indptr), _ptr(self.items), _ptr(self.pos_user),
                                            self.num_pos, self.num_items, self.seed, first, B, _ptr(u), _ptr(i), _ptr(j), 0, B,
                                            _stream())
@@ -1182,26 +1231,50 @@ class EpochWalkSampler(PhiloxSampler):
         self.epoch, self.pos_in_epoch = epoch, 0
         self._next = self._prepare(epoch + 1)
 
-    def sample(self, B, first=None, out=None):
+    @property
+    def position(self):
+        """The stream position of the next sample(): epoch * interactions + position inside the epoch."""
+        return 0 if getattr(self, "perm", None) is None else self.epoch * self.num_pos + self.pos_in_epoch
+
+    def seek(self, position):
+        """Continue at stream position `position`; nothing is drawn (the epoch it lies in is prepared if it is another one)."""
+        epoch, pos = divmod(int(position), self.num_pos)
+        if getattr(self, "perm", None) is None or epoch != self.epoch:
+            self._start_epoch(epoch)
+        self.pos_in_epoch = pos
+
+    def sample(self, B, first=None, out=None, want_candidates=False):
         if first is not None:
             raise ValueError("the epoch walk is a sequential stream")
         if getattr(self, "perm", None) is None:
             self._start_epoch(0)
         u, i, j = out if out is not None else tuple(torch.empty(B, dtype=torch.int32, device=self.device) for _ in range(3))
+        hard = getattr(self, "_hard", 0)
+        if want_candidates and not hard:
+            raise ValueError("want_candidates needs a hard sampler: call hard(engine, candidates) first")
+        if hard:
+            C_, ps, cand, score = self._hard_args(B, want_candidates)
         done = 0
         while done < B:
             n = min(B - done, self.num_pos - self.pos_in_epoch)
-            rc = self.lib.bprx_sample_epoch_h(getattr(self, "_handle", None), _ptr(self.indptr), _ptr(self.items), _ptr(self.perm),
-                                              _ptr(self.epoch_ptr), _ptr(self.pos_slot), self.indptr.numel() - 1, self.num_items,
-                                              self.seed, self.epoch, self.pos_in_epoch, n, _ptr(u[done:]), _ptr(i[done:]),
-                                              _ptr(j[done:]), done, B, _stream())
-            if rc < 0:
-                raise _ffi.BprxError(rc, "bprx_sample_epoch failed")
+            if hard:
+                _ffi.check(self._handle, self.lib.bprx_sample_epoch_hard(
+                    self._handle, _ptr(self.indptr), _ptr(self.items), _ptr(self.perm), _ptr(self.epoch_ptr), _ptr(self.pos_slot),
+                    self.indptr.numel() - 1, self.num_items, self.seed, self.epoch, self.pos_in_epoch, n, _ptr(u[done:]),
+                    _ptr(i[done:]), _ptr(j[done:]), done, B, _stream(), C_, _ptr(ps),
+                    _ptr(cand[done:]) if want_candidates else None, _ptr(score[done:]) if want_candidates else None))
+            else:
+                rc = self.lib.bprx_sample_epoch_h(getattr(self, "_handle", None), _ptr(self.indptr), _ptr(self.items), _ptr(self.perm),
+                                                  _ptr(self.epoch_ptr), _ptr(self.pos_slot), self.indptr.numel() - 1, self.num_items,
+                                                  self.seed, self.epoch, self.pos_in_epoch, n, _ptr(u[done:]), _ptr(i[done:]),
+                                                  _ptr(j[done:]), done, B, _stream())
+                if rc < 0:
+                    raise _ffi.BprxError(rc, "bprx_sample_epoch failed")
             done += n
             self.pos_in_epoch += n
             if self.pos_in_epoch >= self.num_pos:
                 self._start_epoch(self.epoch + 1)
-        return u, i, j
+        return (u, i, j, cand, score) if (hard and want_candidates) else (u, i, j)
 
 
 class HostSampler:

@@ -176,8 +176,25 @@ class BPRMF(RecommenderModel):
         self.diversify_pool = int(getattr(params, "diversify_pool", 100) or 100)   # candidates per list the MMR step picks from
         self.because_top = int(getattr(params, "because", 0) or 0)                 # owned items per pair in because-*; 0: none
         self.audience_k = int(getattr(params, "audience", 0) or 0)                 # users per item in audience-*; 0: none
-        self.directory_parameters = f'batch_{params.batch_size}-K_{params.embed_k}-lr_{params.lr}-reg_{params.reg}'
+        # hard negatives (--hard_negatives C): every negative is the best-scored of C sampled candidates; 0: the uniform draw
+        self.hard_negatives = int(getattr(params, "hard_negatives", 0) or 0)
+        self.hard_refresh = int(getattr(params, "hard_refresh", 0) or 0)           # steps between snapshots inside an epoch; 0: none
+        if self.hard_negatives and not (2 <= self.hard_negatives <= 16 and self.hard_models):
+            raise ValueError("%s: hard_negatives is 0 (off) or 2 .. 16 with BPRMF, VBPR or GradFashion (got %r)"
+                             % (type(self).__name__, self.hard_negatives))
+        if self.hard_negatives and getattr(params, "sampler", "ref_stream") != "philox":
+            raise ValueError("%s: hard_negatives needs the philox sampler" % type(self).__name__)
+        if self.hard_refresh < 0 or (self.hard_refresh and not self.hard_negatives):
+            raise ValueError("%s: hard_refresh is >= 0 and needs hard_negatives (got %r)" % (type(self).__name__, self.hard_refresh))
+        self.directory_parameters = f'batch_{params.batch_size}-K_{params.embed_k}-lr_{params.lr}-reg_{params.reg}' \
+                                    + self._hard_suffix()
         self._build(init or {})
+
+    hard_models = True                                           # ACF / AttentiveFashion: False (their scores are not the kernel's)
+
+    def _hard_suffix(self):
+        """What a run with hard negatives adds to directory_parameters (uniform runs keep the reference's file names)."""
+        return f'-hard_{self.hard_negatives}' if self.hard_negatives else ''
 
     # ---- parameters (BPRMF.py:48-52) ---------------------------------------------------------------------------
     def _init_tables(self, init):
@@ -281,7 +298,20 @@ class BPRMF(RecommenderModel):
             from .engine import EpochWalkSampler
             smp = EpochWalkSampler(self.data.training_list, self.num_items, device=self.engine.device,
                                    seed=getattr(self.params, "init_seed", 0)).feeds(self.engine)
-            next_batch = (smp.sample(self.params.batch_size) for _ in range(steps_total))
+            if self.hard_negatives:
+                # --hard_negatives C: the snapshot the candidates are scored with is taken again at the start of every epoch of
+                # this loop, and with --hard_refresh N every N steps counted from there (the step is read off the stream's
+                # position when the first batch is asked for: a resumed run has skipped to its own by then)
+                smp.hard(self.engine, self.hard_negatives)
+
+                def hard_batches(B=self.params.batch_size, spe=max(1, steps_total // max(1, self.params.epochs))):
+                    for s in range(smp.position // B, steps_total):
+                        if s % spe == 0 or (self.hard_refresh and (s % spe) % self.hard_refresh == 0):
+                            smp.refresh()
+                        yield smp.sample(B)
+                next_batch = hard_batches()
+            else:
+                next_batch = (smp.sample(self.params.batch_size) for _ in range(steps_total))
         else:
             next_batch = self.data.next_triple_batch(self.engine.device)
         steps = 0
@@ -296,8 +326,11 @@ class BPRMF(RecommenderModel):
         if resume:
             path = self.weights_path(self.restore_epochs)
             self.load_state_dict(torch.load(path, map_location=self.engine.device, weights_only=True))
-            for _ in range(self.restore_epochs * steps_per_epoch):
-                next(next_batch)
+            if self.hard_negatives:                               # nothing is drawn: the stream position moves (the skipped
+                smp.skip(self.restore_epochs * steps_per_epoch * self.params.batch_size)   # batches would be scored by THIS model)
+            else:
+                for _ in range(self.restore_epochs * steps_per_epoch):
+                    next(next_batch)
             it = self.restore_epochs + 1
             print('Restored epoch {0} from {1}'.format(self.restore_epochs, path))
         start_ep = time()
@@ -770,7 +803,7 @@ class VBPR(BPRMF):
             raise ValueError("%s: feat_explain is 0 (off) .. 32 (got %r)" % (type(self).__name__, self.feat_explain))
         super().__init__(data, params, init)
         self.directory_parameters = f'batch_{params.batch_size}-D_{params.embed_d}-K_{params.embed_k}' \
-                                    f'-lr_{params.lr}-reg_{params.reg}'      # VBPR.py:35-39
+                                    f'-lr_{params.lr}-reg_{params.reg}' + self._hard_suffix()      # VBPR.py:35-39
 
     def process_cnn_visual_features(self):
         """visual_loader_mixin.py:22-31: np.load, divide by the GLOBAL max-abs, D = shape[1]."""
@@ -1000,7 +1033,7 @@ class GradFashion(VBPR):
         self.embed_edges = params.embed_edges
         super().__init__(data, params, init, features)
         self.directory_parameters = f'batch_{params.batch_size}-D_{params.embed_d}-K_{params.embed_k}' \
-                                    f'-lr_{params.lr}-reg_{params.reg}'      # GradFashion.py:48-52
+                                    f'-lr_{params.lr}-reg_{params.reg}' + self._hard_suffix()      # GradFashion.py:48-52
 
     # ---- visual_loader_mixin.py:51-54, 60-69: np.load, each table divided by its OWN global max-abs -------------------
     def process_edge_visual_features(self):
@@ -1179,6 +1212,7 @@ class ACF(BPRMF):
     predict_all, train_step, train.  `features`: optional [I, M, C] (or [I, H, W, C]) array used instead of the per-item .npy
     files (not normalised, like the files)."""
     model_kind = "acf"
+    hard_models = False
 
     def __init__(self, data, params, init=None, features=None):
         self.layers_component = [int(x) for x in getattr(params, "layers_component", [64, 1])]
@@ -1398,6 +1432,7 @@ class AttentiveFashion(BPRMF):
     train, predict_all_batch.  `inputs`: optional (edges uint8 [I, 224, 224], colour [I, Dc] already normalised, classes [I, Dk]) used
     instead of the per-item files."""
     model_kind = "attentive_fashion"
+    hard_models = False
 
     def __init__(self, data, params, init=None, inputs=None):
         self.attention_layers = [int(x) for x in getattr(params, "attention_layers", [64, 1])]

@@ -175,6 +175,13 @@ def parse_args(argv=None):
     parser.add_argument('--sampler', default='ref_stream', choices=['ref_stream', 'philox'],
                         help="ref_stream: the reference's MT19937 index stream (single GPU); philox: device epoch walk "
                              "(always used with --world_size > 1: negatives stay GPU-local)")
+    parser.add_argument('--hard_negatives', type=int, default=0,
+                        help="C in 2..16: every negative is the best-scored of C sampled candidates under the current model "
+                             "(dynamic negative sampling; bprmf, vbpr, grad_fashion with --sampler philox on one GPU); 0 = off. "
+                             "File names then end in -hard_C")
+    parser.add_argument('--hard_refresh', type=int, default=0,
+                        help="with --hard_negatives: take the snapshot of the item projections the candidates are scored with "
+                             "again every N steps inside an epoch (it is always taken at an epoch's start); 0 = only there")
     parser.add_argument('--dense_reduce', default='gather', choices=['gather', 'allreduce'],
                         help='multi-GPU VBPR: how the gradient of E / beta-prime is summed over the ranks (dist.py)')
     parser.add_argument('--dist_backend', default='nccl', choices=['nccl', 'gloo'], help='nccl == RCCL on ROCm')
@@ -268,6 +275,18 @@ def parse_args(argv=None):
             read_audience_items(args.audience_items)
         except (OSError, ValueError) as e:
             parser.error("--audience_items: %s" % e)
+    if args.hard_negatives != 0 and not 2 <= args.hard_negatives <= 16:
+        parser.error("--hard_negatives takes 0 (off) or 2 .. 16 (got %s)" % args.hard_negatives)
+    if args.hard_negatives != 0 and args.sampler != 'philox':
+        parser.error("--hard_negatives needs --sampler philox (got --sampler %s)" % args.sampler)
+    if args.hard_negatives != 0 and args.rec not in ('bprmf', 'vbpr', 'grad_fashion'):
+        parser.error("--hard_negatives needs --rec bprmf, vbpr or grad_fashion (got --rec %s)" % args.rec)
+    if args.hard_negatives != 0 and int(args.world_size) != 1:
+        parser.error("--hard_negatives runs on one GPU (got --world_size %s)" % args.world_size)
+    if args.hard_refresh < 0:
+        parser.error("--hard_refresh takes N >= 0 (got %s)" % args.hard_refresh)
+    if args.hard_refresh != 0 and args.hard_negatives == 0:
+        parser.error("--hard_refresh needs --hard_negatives C")
     if not 0.0 <= args.dropout < 1.0:
         parser.error("--dropout takes a rate in [0, 1) (got %s)" % args.dropout)
     return args

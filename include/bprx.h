@@ -1074,6 +1074,40 @@ BPRX_API int bprx_sample_epoch_h(bprx_handle *h, const int64_t *indptr, const in
                                  const int64_t *epoch_ptr, const int32_t *pos_slot, int32_t num_users, int32_t num_items,
                                  uint64_t seed, uint32_t epoch, int64_t first, int64_t B, int32_t *user, int32_t *pos, int32_t *neg,
                                  int64_t batch_offset, int64_t batch_size, void *stream);
+/* Hard negatives (dynamic negative sampling): the hard forms of the two samplers above.  The user and the positive of a stream
+   position are the uniform stream's.  Candidate c (0 <= c < candidates <= 16) of position n is the uniform samplers' rejection
+   draw with the third counter word c * 2048 + a instead of a (attempts a = 0, 1, .., the 1024 fallback included): candidate 0 is
+   the uniform negative, every candidate is uniform over the user's non-positives, candidates may repeat.  The negative is the
+   candidate with the largest
+     s_c = Gu_u.Gi_j + Bi_j                                  (BPRMF)
+     s_c = Gu_u.Gi_j + Bi_j + Tu_u.Ps_j[:d] + Ps_j[d]        (VBPR, plain or factored)
+   in fp32 (the summation order is the kernel's); ties go to the smallest c, a NaN never wins against a number.  candidates == 1
+   reproduces bprx_sample_*_h bit for bit.  Planes and queues of the chosen negatives are left for the handle's next step as above.
+   h is required: a bound BPRMF or VBPR handle whose tables are whole (not a multi-GPU staging handle) and whose num_items is the
+   sampler's.  The rows of Gu / Gi / Bi / Tu are read AS STORED: the call runs no lazy adam_tf23 catch-up, so rows the batches have
+   not touched lately lag by their pending momentum steps.  It runs on `stream` behind the previous step.
+   Ps (VBPR: required; BPRMF: ignored): fp32 [num_items, bprx_proj_stride] device memory of the caller, filled by
+   bprx_hard_snapshot; between two refreshes it lags E / Bp.  Both lags steer the choice only: the step computes its gradient
+   from current values.
+   cand_out (int32 [B, candidates]) / score_out (fp32 [B, candidates]), both optional: what was drawn and what was compared.
+   BPRX_E_INVALID for a NULL handle or pointer, an ACF or AttentiveFashion handle, candidates outside 1..16, a VBPR handle without
+   Ps, another num_items; BPRX_E_STATE for an unbound handle.  After any error the handle stays usable. */
+BPRX_API int bprx_sample_philox_hard(bprx_handle *h, const int64_t *indptr, const int32_t *items_sorted, const int32_t *pos_user,
+                                     int64_t num_pos, int32_t num_items, uint64_t seed, uint64_t first, int64_t B, int32_t *user,
+                                     int32_t *pos, int32_t *neg, int64_t batch_offset, int64_t batch_size, void *stream,
+                                     int32_t candidates, const float *Ps, int32_t *cand_out, float *score_out);
+BPRX_API int bprx_sample_epoch_hard(bprx_handle *h, const int64_t *indptr, const int32_t *items_sorted, const int32_t *perm,
+                                    const int64_t *epoch_ptr, const int32_t *pos_slot, int32_t num_users, int32_t num_items,
+                                    uint64_t seed, uint32_t epoch, int64_t first, int64_t B, int32_t *user, int32_t *pos,
+                                    int32_t *neg, int64_t batch_offset, int64_t batch_size, void *stream, int32_t candidates,
+                                    const float *Ps, int32_t *cand_out, float *score_out);
+/* Fills Ps = F.[E|Bp] of every item from the bound tables as they are now (fp32, bf16 or fp8 features, plain or factored): the
+   forward projection written straight into the caller's buffer.  Like every gated call it first settles a deferred dense update
+   and makes the [E|Bp]^T image current.  It is not the handle's own P and leaves the plan of the next step alone.  BPRMF: BPRX_OK,
+   nothing is touched (Ps may be NULL).  BPRX_E_INVALID for a NULL handle, a VBPR handle with Ps == NULL, an ACF or AttentiveFashion
+   handle; BPRX_E_STATE for an unbound handle. */
+BPRX_API int bprx_hard_snapshot(bprx_handle *h, float *Ps, void *stream);
+
 /* What the index pass of the handle's last step read: 0 = no segment-mode step yet, 1 = the int32 index arrays,
    2 = the sampler's byte planes.  (Introspection for tests and benchmarks.) */
 BPRX_API int bprx_index_pass_kind(const bprx_handle *h);
