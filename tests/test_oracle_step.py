@@ -144,7 +144,8 @@ def test_quant_bf16_rounds_operands_only():
 def test_e4m3_rounding_matches_torch_cpu_cast():
     """The oracle's (and, bit for bit, the device's) OCP e4m3fn rounding against torch's CPU float8_e4m3fn cast:
     identical inside the finite range (normals, subnormals, ties, signed zero); beyond 464 torch yields NaN where the
-    quantiser saturates at 448 (the scale 448/max|x| never produces such inputs)."""
+    quantiser saturates at 448 (the scale 448/max|x| never produces such inputs).  The device's half of the claim:
+    tests/test_gpu_fp8_codes.py::test_cast_and_maximum, on every boundary between two codes."""
     import torch
     from oracle import oracle as orc
     rs = np.random.RandomState(0)
