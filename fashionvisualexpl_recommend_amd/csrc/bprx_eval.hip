@@ -505,6 +505,298 @@ __global__ __launch_bounds__(256) void k_topk(float *__restrict__ S, int u0, int
   if (tid == 0) flag_out[blockIdx.x] = s_bad;
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// bprx_topk_classes (include/bprx.h): the K best entries of every CLASS of a score row.  The row's I elements fall into C
+// independent selections, read through the class CSR (s[class_items[p]]: the ids ascend inside a class, so the addresses move
+// forward through the L2-resident row).  A list has a total order of its own -- (score descending as floats, item ascending),
+// at the selection boundary too -- so nothing is flagged; entries that are -inf in the (masked) row are on no list.
+//   k_mask_rows      row r gets -inf at the ids of list row0 + r: a launch of its own in front, so a row's mask is complete before
+//                    any class of the row is read
+//   k_topk_classes   one workgroup per (row, tile of TKC_TILE = 4 consecutive classes); by class size n:
+//                      n <= TKC_WAVE_MAX   one wave sorts the whole class in its quarter of the candidate buffer (wave w takes
+//                                          class 4g + w; the bitonic stages of the four waves run in step, to the largest of them)
+//                      larger              the workgroup: k_topk's radix select over the gathered keys, STOPPED after the first
+//                                          histogram pass at which the elements at or above the selected bin fit the candidate
+//                                          buffer (for real-valued scores the first: the K-th best shares its sign and exponent
+//                                          byte with a few per cent of a class); those are collected and sorted whole, which
+//                                          settles every tie by the sort's own order.  Only when four passes leave more than
+//                                          TOPK_MAX such elements (that many EQUAL scores) the select ends as k_topk's does: one
+//                                          collection pass, and a second select over the item ids of exactly the tied elements.
+//                    Classes are skewed: a tile of small classes costs one workgroup, not four.  The histogram's bin is picked
+//                    by a wave scan, not a serial walk.  Split point and pass counts: DESIGN 9.
+// No float arithmetic, no float atomics, no scratch; LDS 9.3 KB per workgroup.
+// ------------------------------------------------------------------------------------------------------------
+#ifndef BPRX_TKC_WAVE_MAX
+#define BPRX_TKC_WAVE_MAX 256
+#endif
+constexpr int TKC_TILE = 4, TKC_WAVE_MAX = BPRX_TKC_WAVE_MAX;
+static_assert(TKC_WAVE_MAX * TKC_TILE <= TOPK_MAX && (TKC_WAVE_MAX & (TKC_WAVE_MAX - 1)) == 0, "a wave's quarter of the buffer");
+constexpr uint32_t KEY_NINF = 0x007fffffu;                 // f2key(-inf): a candidate's key is larger
+constexpr int PAD_ITEM = 0x7fffffff;                       // (key 0, PAD_ITEM): sorts behind every candidate
+
+struct TkcShared {
+  int hist[256];
+  uint32_t prefix, mask;
+  int remaining, kc, ngt, neq, cand;                       // cand: the elements at or above the selected bin, so far
+  uint32_t ckey[TOPK_MAX];
+  int cidx[TOPK_MAX];
+};
+
+// Workgroup b of a launch of `total` workgroups, laid out by tkc_grid: a launch takes fewer than 2^32 threads along x, and nrows * C
+// may reach 2^31, so the count is folded into (x, y); the workgroups past `total` in the last row of the grid leave at once.
+constexpr int64_t TKC_GRID_X = (int64_t)1 << 22;
+__device__ __forceinline__ int64_t tkc_block() { return (int64_t)blockIdx.y * gridDim.x + blockIdx.x; }
+
+__global__ __launch_bounds__(256) void k_mask_rows(float *__restrict__ S, int64_t nrows, int64_t row0, int width,
+                                                   const int64_t *__restrict__ ptr, const int32_t *__restrict__ items) {
+  const int64_t row = tkc_block();
+  if (row >= nrows) return;
+  float *s = S + (size_t)row * width;
+  const int64_t t0 = ptr[row0 + row], t1 = ptr[row0 + row + 1];
+  for (int64_t q = t0 + threadIdx.x; q < t1; q += 256) {
+    const int it = items[q];
+    if ((unsigned)it < (unsigned)width) s[it] = -INFINITY;
+  }
+}
+
+// The sort key of class entry `it`, false for an entry that is on no list (an id outside the row: reported; a score of -inf).
+// TIE: only the entries whose score key is kth take part, and their key is the item id, smaller id = larger key.
+template <bool TIE>
+__device__ __forceinline__ bool tkc_elem(const float *__restrict__ s, int width, int it, uint32_t kth, uint32_t &key,
+                                         int32_t *__restrict__ errflag) {
+  if ((unsigned)it >= (unsigned)width) { *errflag = 5; return false; }   // reported by bprx_sync_check, never dereferenced
+  const uint32_t k = f2key(s[it]);
+  if (TIE) { key = ~(uint32_t)it; return k == kth; }
+  key = k;
+  return k > KEY_NINF;
+}
+
+// Wave 0, after a histogram pass: the bin (from the largest down) in which the `remaining`-th largest key lies, by a wave scan
+// over 4 bins per lane.  first_k > 0 (the first pass of a selection over all candidates): remaining = kc = min(first_k, number of
+// candidates) first.
+__device__ __forceinline__ void tkc_pick(TkcShared &sh, int pass, int first_k) {
+  const int lane = threadIdx.x;
+  int c[4], local = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { c[j] = sh.hist[255 - (4 * lane + j)]; local += c[j]; }
+  int incl = local;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int t = __shfl_up(incl, off);
+    if (lane >= off) incl += t;
+  }
+  const int total = __shfl(incl, 63);
+  int rem = sh.remaining;
+  if (first_k > 0) {
+    rem = first_k < total ? first_k : total;
+    if (lane == 0) { sh.kc = rem; sh.remaining = rem; }
+  }
+  if (rem <= 0 || rem > total) return;                       // (nothing wanted; rem > total cannot happen: prefix stays)
+  const int excl = incl - local;
+  if (excl < rem && rem <= incl) {                           // exactly one lane
+    int r = rem - excl, b = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (c[j] >= r) { b = 255 - (4 * lane + j); break; }
+      r -= c[j];
+    }
+    sh.remaining = r;                                        // still wanted among the elements whose byte == b
+    sh.cand = (first_k > 0 ? rem : sh.kc) - r + sh.hist[b];  // all kc - r above the bin are on the list, the bin's may be
+    sh.prefix |= (uint32_t)b << (8 * pass);
+    sh.mask |= 255u << (8 * pass);
+  }
+}
+
+// k_topk's radix select over the keys of tkc_elem<TIE>: afterwards sh.prefix is the key of the wanted-th largest and sh.remaining
+// how many of the elements equal to it are wanted.  The caller has set prefix = mask = 0 (and remaining, unless first_k > 0).
+template <bool TIE>
+__device__ void tkc_select(TkcShared &sh, const float *__restrict__ s, int width, const int32_t *__restrict__ items, int n,
+                           int first_k, uint32_t kth, int32_t *__restrict__ errflag) {
+  const int tid = threadIdx.x;
+  for (int pass = 3; pass >= 0; --pass) {
+    sh.hist[tid] = 0;
+    __syncthreads();
+    const uint32_t prefix = sh.prefix, mask = sh.mask;
+    for (int q = tid; q < n; q += 256) {
+      uint32_t key;
+      if (tkc_elem<TIE>(s, width, items[q], kth, key, errflag) && (key & mask) == prefix)
+        atomicAdd(&sh.hist[(key >> (8 * pass)) & 255], 1);
+    }
+    __syncthreads();
+    if (tid < 64) tkc_pick(sh, pass, pass == 3 ? first_k : 0);
+    __syncthreads();
+    if (pass == 3 && first_k > 0 && sh.kc == 0) return;      // no candidate (the same for every thread)
+    if (!TIE && sh.cand <= TOPK_MAX) return;                 // what is left fits the buffer: the caller sorts it
+  }
+}
+
+// The elements above the selected key go to slots base .. base + ngt_cap - 1, the first want_eq that equal it (in arrival order)
+// behind them (tkc_select ran all four passes); sh.ngt / sh.neq count what was seen.  Slots hold the SCORE key (TIE: score_kth for all) and the item.
+template <bool TIE>
+__device__ void tkc_collect(TkcShared &sh, const float *__restrict__ s, int width, const int32_t *__restrict__ items, int n,
+                            uint32_t score_kth, uint32_t kth, int base, int ngt_cap, int want_eq, int32_t *__restrict__ errflag) {
+  for (int q = threadIdx.x; q < n; q += 256) {
+    const int it = items[q];
+    uint32_t key;
+    if (!tkc_elem<TIE>(s, width, it, score_kth, key, errflag)) continue;
+    if (key > kth) {
+      const int p = atomicAdd(&sh.ngt, 1);
+      if (p < ngt_cap) { sh.ckey[base + p] = TIE ? score_kth : key; sh.cidx[base + p] = it; }
+    } else if (key == kth) {
+      const int e = atomicAdd(&sh.neq, 1);
+      if (e < want_eq) { sh.ckey[base + ngt_cap + e] = TIE ? score_kth : key; sh.cidx[base + ngt_cap + e] = it; }
+    }
+  }
+}
+
+// Bitonic sort of n2 (a power of two) slots by (key descending, item ascending), `nt` threads of which this one is `t`; every thread
+// of the workgroup calls it with the same n2 (each stage ends in a barrier).
+__device__ __forceinline__ void tkc_sort(uint32_t *ckey, int *cidx, int n2, int t, int nt) {
+  for (int size = 2; size <= n2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int q = t; q < n2; q += nt) {
+        const int partner = q ^ stride;
+        if (partner > q) {
+          const bool desc = (q & size) == 0;
+          const uint32_t ka = ckey[q], kb = ckey[partner];
+          const int ia = cidx[q], ib = cidx[partner];
+          const bool a_better = ka > kb || (ka == kb && ia < ib);
+          if (a_better != desc) { ckey[q] = kb; ckey[partner] = ka; cidx[q] = ib; cidx[partner] = ia; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// Slots [0, n2) of a buffer <- the candidates of a whole class, padded; returns how many of this thread's entries are candidates.
+__device__ __forceinline__ int tkc_load(uint32_t *ckey, int *cidx, const float *__restrict__ s, int width,
+                                        const int32_t *__restrict__ items, int n, int n2, int t, int nt, int32_t *__restrict__ errflag) {
+  int m = 0;
+  for (int q = t; q < n2; q += nt) {
+    uint32_t key = 0u;
+    int it = PAD_ITEM;
+    if (q < n) {
+      it = items[q];
+      if (tkc_elem<false>(s, width, it, 0u, key, errflag)) ++m;
+      else { key = 0u; it = PAD_ITEM; }
+    }
+    ckey[q] = key; cidx[q] = it;
+  }
+  return m;
+}
+
+__device__ __forceinline__ void tkc_write(const int *cidx, const float *__restrict__ s, int width, int kc, int K, int t, int nt,
+                                          int32_t *__restrict__ idx, float *__restrict__ val, int32_t *__restrict__ cnt) {
+  for (int q = t; q < K; q += nt) {
+    const int it = q < kc ? cidx[q] : -1;
+    const bool on = (unsigned)it < (unsigned)width;          // (every candidate's id lies in the row)
+    idx[q] = on ? it : -1;
+    val[q] = on ? s[it] : 0.f;                               // read from the row: the sign of a zero is kept
+  }
+  if (t == 0) *cnt = kc;
+}
+
+__device__ __forceinline__ int tkc_pow2(int n) {
+  int n2 = 1;
+  while (n2 < n) n2 <<= 1;
+  return n2;
+}
+
+__global__ __launch_bounds__(256) void k_topk_classes(const float *__restrict__ S, int width, const int64_t *__restrict__ cptr,
+                                                      const int32_t *__restrict__ citems, int C, int tiles, int64_t total, int K,
+                                                      int32_t *__restrict__ idx_out, float *__restrict__ val_out,
+                                                      int32_t *__restrict__ cnt_out, int32_t *__restrict__ errflag) {
+  __shared__ TkcShared sh;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int64_t blk = tkc_block();
+  if (blk >= total) return;                                  // (the whole workgroup: no barrier is left waiting)
+  const int64_t row = blk / tiles;
+  const int c0 = (int)(blk % tiles) * TKC_TILE;
+  const float *s = S + (size_t)row * width;
+  // (start, length) of class c; length -1: no such class.  A class holds at most `width` items.
+  auto class_of = [&](int c, int64_t &p) -> int {
+    if (c >= C) { p = 0; return -1; }
+    p = cptr[c];
+    const int64_t len = cptr[c + 1] - p;
+    return len < 0 ? 0 : len > 0x7fffffff ? 0x7fffffff : (int)len;
+  };
+  int wave_n2 = 0;                                           // the bitonic width of the tile's wave-sorted classes
+#pragma unroll
+  for (int j = 0; j < TKC_TILE; ++j) {
+    int64_t p;
+    const int nj = class_of(c0 + j, p);
+    if (nj >= 0 && nj <= TKC_WAVE_MAX) wave_n2 = max(wave_n2, tkc_pow2(nj));
+  }
+  // ---- classes of at most TKC_WAVE_MAX items: wave w sorts class c0 + w whole ----
+  if (wave_n2 > 0) {
+    int64_t pw;
+    const int nw = class_of(c0 + w, pw);
+    const bool mine = nw >= 0 && nw <= TKC_WAVE_MAX;
+    uint32_t *ck = sh.ckey + w * TKC_WAVE_MAX;
+    int *ci = sh.cidx + w * TKC_WAVE_MAX;
+    int m = tkc_load(ck, ci, s, width, citems + pw, mine ? nw : 0, wave_n2, lane, 64, errflag);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m += __shfl_xor(m, off);
+    __syncthreads();
+    tkc_sort(ck, ci, wave_n2, lane, 64);
+    if (mine) {
+      const size_t o = ((size_t)row * C + (c0 + w)) * K;
+      tkc_write(ci, s, width, m < K ? m : K, K, lane, 64, idx_out + o, val_out + o, cnt_out + (size_t)row * C + (c0 + w));
+    }
+  }
+  // ---- larger classes: the whole workgroup, one class after the other ----
+#pragma unroll 1
+  for (int j = 0; j < TKC_TILE; ++j) {
+    int64_t pj;
+    const int nj = class_of(c0 + j, pj);
+    if (nj <= TKC_WAVE_MAX) continue;                        // (the same for every thread)
+    const int32_t *items = citems + pj;
+    const size_t o = ((size_t)row * C + (c0 + j)) * K;
+    int32_t *cnt = cnt_out + (size_t)row * C + (c0 + j);
+    __syncthreads();                                         // the buffer is free again
+    if (tid == 0) { sh.prefix = 0; sh.mask = 0; sh.remaining = 0; sh.kc = 0; sh.ngt = 0; sh.neq = 0; sh.cand = 0x7fffffff; }
+    tkc_select<false>(sh, s, width, items, nj, K, 0u, errflag);          // (its first barrier publishes the line above)
+    const int kc = sh.kc;
+    if (kc > 0 && sh.cand <= TOPK_MAX) {                     // everything at or above the selected bin, sorted whole
+      const uint32_t prefix = sh.prefix, mask = sh.mask;
+      for (int q = tid; q < nj; q += 256) {
+        const int it = items[q];
+        uint32_t key;
+        if (tkc_elem<false>(s, width, it, 0u, key, errflag) && (key & mask) >= prefix) {
+          const int p = atomicAdd(&sh.ngt, 1);
+          if (p < TOPK_MAX) { sh.ckey[p] = key; sh.cidx[p] = it; }
+        }
+      }
+      __syncthreads();
+      const int got = sh.ngt < TOPK_MAX ? sh.ngt : TOPK_MAX; // (== sh.cand >= kc)
+      const int n2 = tkc_pow2(got);
+      for (int q = got + tid; q < n2; q += 256) { sh.ckey[q] = 0u; sh.cidx[q] = PAD_ITEM; }
+      __syncthreads();
+      tkc_sort(sh.ckey, sh.cidx, n2, tid, 256);
+    } else if (kc > 0) {
+      const uint32_t kth = sh.prefix;                        // key of the kc-th largest score; want_eq of the elements equal to
+      const int want_eq = sh.remaining;                      // it belong to the list, all kc - want_eq larger ones do
+      tkc_collect<false>(sh, s, width, items, nj, 0u, kth, 0, kc - want_eq, want_eq, errflag);
+      __syncthreads();
+      if (sh.neq > want_eq) {                                // a tie straddles the boundary: the want_eq smallest ids of it
+        __syncthreads();
+        if (tid == 0) { sh.prefix = 0; sh.mask = 0; sh.remaining = want_eq; sh.ngt = 0; sh.neq = 0; }
+        tkc_select<true>(sh, s, width, items, nj, 0, kth, errflag);
+        const uint32_t id_kth = sh.prefix;
+        const int want_id = sh.remaining;
+        tkc_collect<true>(sh, s, width, items, nj, kth, id_kth, kc - want_eq, want_eq - want_id, want_id, errflag);
+        __syncthreads();
+      }
+      const int n2 = tkc_pow2(kc);
+      for (int q = kc + tid; q < n2; q += 256) { sh.ckey[q] = 0u; sh.cidx[q] = PAD_ITEM; }
+      __syncthreads();
+      tkc_sort(sh.ckey, sh.cidx, n2, tid, 256);
+    }
+    tkc_write(sh.cidx, s, width, kc, K, tid, 256, idx_out + o, val_out + o, cnt);
+  }
+}
+
 }  // namespace
 
 // The shared tail of the three top-K entries, after each one's own argument checks: the K range, then `null` (the entry found a
@@ -559,6 +851,38 @@ extern "C" int bprx_topk_rows_masked(bprx_handle *h, int64_t nrows, int32_t widt
   if (width < 1) BPRX_FAIL(h, BPRX_E_INVALID, "topk_rows_masked: width = %d < 1", width);
   return topk_launch(h, "topk_rows_masked", "k_topk<rows_masked>", nrows && (!scores || !list_ptr || !list_items || !idx || !val || !flag),
                      0, KIND_ANY, nrows, scores, 0, width, list_ptr, list_items, K, idx, val, flag, stream);
+}
+
+// ---- category shelves: the K best entries of every class of a row (include/bprx.h; k_mask_rows, k_topk_classes) ----
+extern "C" int bprx_topk_classes(bprx_handle *h, int64_t nrows, int32_t width, float *scores, int64_t row0, const int64_t *list_ptr,
+                                 const int32_t *list_items, const int64_t *class_ptr, const int32_t *class_items, int32_t C, int32_t K,
+                                 int32_t *idx, float *val, int32_t *cnt, void *stream) {
+  if (!h) return BPRX_E_INVALID;
+  if (K <= 0 || K > TOPK_MAX) BPRX_FAIL(h, BPRX_E_INVALID, "topk_classes: K=%d outside [1, %d]", K, TOPK_MAX);
+  if (C < 1) BPRX_FAIL(h, BPRX_E_INVALID, "topk_classes: C = %d < 1", C);
+  if (width < 1) BPRX_FAIL(h, BPRX_E_INVALID, "topk_classes: width = %d < 1", width);
+  if (nrows < 0 || row0 < 0) BPRX_FAIL(h, BPRX_E_INVALID, "topk_classes: nrows = %lld, row0 = %lld: neither is negative", (long long)nrows, (long long)row0);
+  if (nrows >= ((int64_t)1 << 31) || nrows * C > (((int64_t)1 << 31) - 1) / K)
+    BPRX_FAIL(h, BPRX_E_INVALID, "topk_classes: nrows * C * K = %lld * %d * %d does not stay below 2^31", (long long)nrows, C, K);
+  if (nrows && (!scores || !class_ptr || !class_items || !idx || !val || !cnt || (list_ptr && !list_items)))
+    BPRX_FAIL(h, BPRX_E_INVALID, "topk_classes: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = bprx_enter(h, "topk_classes", 0, KIND_ANY, s);
+  if (rc || nrows == 0) return rc;
+  auto grid = [](int64_t total) {                            // tkc_block's layout: x up to 2^22 workgroups, y the rest (at most 2^9)
+    const int64_t x = total < TKC_GRID_X ? total : TKC_GRID_X;
+    return dim3((unsigned)x, (unsigned)((total + x - 1) / x));
+  };
+  if (list_ptr) {                                            // a launch of its own: every class of a row reads the finished mask
+    hipLaunchKernelGGL(k_mask_rows, grid(nrows), dim3(256), 0, s, scores, nrows, row0, width, list_ptr, list_items);
+    BPRX_LAUNCH_CHECK(h, "k_mask_rows");
+  }
+  const int tiles = (C + TKC_TILE - 1) / TKC_TILE;
+  const int64_t total = nrows * tiles;                       // < 2^31: nrows * C is
+  hipLaunchKernelGGL(k_topk_classes, grid(total), dim3(256), 0, s, (const float *)scores, width, class_ptr, class_items, C, tiles,
+                     total, K, idx, val, cnt, h->errflag);
+  BPRX_LAUNCH_CHECK(h, "k_topk_classes");
+  return BPRX_OK;
 }
 
 // ---- audience: the item-major score block (include/bprx.h) ----

@@ -817,6 +817,23 @@ class Engine:
                                                           _addr(val), _addr(flag), _stream()))
         return idx, val, flag
 
+    def topk_classes(self, scores, lists_csr, class_csr, K, row0=0):
+        """bprx_topk_classes: the K best entries of every class of every row of a contiguous fp32 [nrows, width] device tensor.  Row
+        r masks (IN `scores`) the ids of list row0 + r of lists_csr = (int64 ptr, int32 ids), None: nothing is masked; class_csr =
+        (int64 ptr [C + 1], int32 items, C) as ranking.class_csr makes it.  Returns (idx int32 [nrows, C, K], val fp32 [nrows, C, K],
+        cnt int32 [nrows, C]): per class best first, equal scores by ascending item, -1 / 0.0 past cnt; masked items are on no list."""
+        nrows, width = (int(x) for x in scores.shape)
+        K = int(K)
+        ptr, items = (None, None) if lists_csr is None else lists_csr
+        cptr, citems, C = class_csr
+        C = int(C)
+        idx = torch.empty((nrows, max(C, 0), max(K, 0)), dtype=torch.int32, device=self.device)
+        val = torch.empty((nrows, max(C, 0), max(K, 0)), dtype=torch.float32, device=self.device)
+        cnt = torch.empty((nrows, max(C, 0)), dtype=torch.int32, device=self.device)
+        _ffi.check(self.h, self.lib.bprx_topk_classes(self.h, nrows, width, _addr(scores), int(row0), _addr(ptr), _addr(items),
+                                                      _addr(cptr), _addr(citems), C, K, _addr(idx), _addr(val), _addr(cnt), _stream()))
+        return idx, val, cnt
+
     def diversify(self, space, rn, pool_idx, pool_val, k, theta):
         """bprx_diversify: greedy MMR over the pools (pool_idx int32, pool_val fp32: contiguous device tensors [n, N], best first,
         as the top-K entries return them) in `space`, rn = sim_rnorm(space): (idx int32 [n, k], val fp32 [n, k] the picks' pool

@@ -18,8 +18,8 @@ from time import time
 
 import numpy as np
 
-from .ranking import (blocks, lists_to_csr, rank_rows, rank_rows_host, write_because, write_diverse, write_feature_rows, write_item_lists,
-                      write_ranked)
+from .ranking import (blocks, lists_to_csr, rank_rows, rank_rows_host, write_because, write_capped, write_diverse, write_feature_rows,
+                      write_item_lists, write_ranked, write_shelves)
 
 
 def _eval_block(scores, u0, train, evl, K):
@@ -233,6 +233,23 @@ class Evaluator:
         ids, vals, pen, ild = self.model.recommend_diverse(None, k, pool, theta, space)
         with open(path, 'w') as out, open(path_ild, 'w') as out_ild:
             write_diverse(out, out_ild, range(ids.shape[0]), ids, vals, pen, ild)
+
+    def store_recommendation_shelves(self, path="", k=None, count=0):
+        """BPRMF / VBPR / GradFashion: every user's shelves (model.recommend_by_class: the k best items of every item class, None =
+        the run's --shelves; training items masked) as rows 'u\tclass\ti\tscore' in `path`: user by user, the user's classes
+        ordered by their best entry's score (count > 0: only the first `count` of them), each shelf best first, formatted as
+        store_recommendation formats.  Device only: force_host raises ValueError (there is no host form)."""
+        ids, vals, cnt = self.model.recommend_by_class(None, k)
+        with open(path, 'w') as out:
+            write_shelves(out, range(ids.shape[0]), ids, vals, cnt, int(count))
+
+    def store_recommendation_capped(self, path="", cap=None):
+        """BPRMF / VBPR / GradFashion: every user's quota list (model.recommend_capped: the top_k with at most `cap` items of any one
+        class, None = the run's --class_cap) as rows 'u\ti\tscore\tclass' in `path`, best first.  Device only: force_host raises
+        ValueError."""
+        ids, vals, cls = self.model.recommend_capped(None, None, cap)
+        with open(path, 'w') as out:
+            write_capped(out, range(ids.shape[0]), ids, vals, cls)
 
     def store_recommendation_because(self, path="", top=5, space=None):
         """BPRMF / VBPR / GradFashion: for every (u, i) of every user's top-k list (the lists store_recommendation writes, ranked

@@ -19,8 +19,9 @@ import torch
 from . import configs
 from .engine import Engine, as_index
 from .evaluator import Evaluator
-from .ranking import (because_paths, because_rows, blocks, diverse_zeros, diversify_rows, div_paths, item_file, owners_of, rank_rows,
-                      ranked_zeros, run_file, wanted_blocks, warm_file, write_because, write_diverse, write_ranked)
+from .ranking import (because_paths, because_rows, blocks, cap_rows, class_csr, class_rows_per_block, diverse_zeros, diversify_rows,
+                      div_paths, item_file, owners_of, rank_class_rows, rank_rows, ranked_zeros, run_file, shelf_file, wanted_blocks,
+                      warm_file, write_because, write_capped, write_diverse, write_ranked, write_shelves)
 from .synth import glorot_uniform
 
 
@@ -176,6 +177,9 @@ class BPRMF(RecommenderModel):
         self.diversify_pool = int(getattr(params, "diversify_pool", 100) or 100)   # candidates per list the MMR step picks from
         self.because_top = int(getattr(params, "because", 0) or 0)                 # owned items per pair in because-*; 0: none
         self.audience_k = int(getattr(params, "audience", 0) or 0)                 # users per item in audience-*; 0: none
+        self.shelves_k = int(getattr(params, "shelves", 0) or 0)                   # entries per class in shelf-*; 0: none
+        self.shelf_count = int(getattr(params, "shelf_count", 0) or 0)             # shelves per user in shelf-*; 0: all
+        self.class_cap = int(getattr(params, "class_cap", 0) or 0)                 # items per class in cap-*; 0: none
         # hard negatives (--hard_negatives C): every negative is the best-scored of C sampled candidates; 0: the uniform draw
         self.hard_negatives = int(getattr(params, "hard_negatives", 0) or 0)
         self.hard_refresh = int(getattr(params, "hard_refresh", 0) or 0)           # steps between snapshots inside an epoch; 0: none
@@ -395,6 +399,7 @@ class BPRMF(RecommenderModel):
         self._store_because(path)
         self._store_audience(path)
         self._store_warm(path)
+        self._store_shelves(path)
 
     def _store_recs(self, path):
         """What train() leaves at the recs-* / best-recs-* paths: the top-K lists (BPRMF.py:167-187)."""
@@ -422,7 +427,7 @@ class BPRMF(RecommenderModel):
         """(scores [r1 - r0, I], side [r1 - r0, I, c] or None) of rows [r0, r1) of what _fold_rows returned."""
         return self.engine.score_rows_block(rows[0], rows[1], r0, r1), None
 
-    def recommend_new_users(self, histories, k=None, diversify=None, **fold):
+    def recommend_new_users(self, histories, k=None, diversify=None, by_class=None, class_cap=None, classes=None, **fold):
         """The k (default top_k) best catalogue items of every new user, their own histories masked: numpy idx int [n, kk] and
         val [n, kk], kk = min(k, I), best first; a model whose scores come with attentions (AttentiveFashion) also returns alpha
         [n, kk, 3] (colour, edges, class).  The rows are fitted by fold_in_users(histories, **fold), scored in row blocks and
@@ -430,8 +435,18 @@ class BPRMF(RecommenderModel):
         GPU's (masked) row.
         diversify: None, or theta (a float in [0, 1]), or a dict with any of theta / pool / space as recommend_diverse takes
         them: the lists are then picked by greedy MMR from each row's top-`pool` and (ids, vals, pen, ild) is returned, as by
-        recommend_diverse (BPRMF, VBPR, GradFashion)."""
+        recommend_diverse (BPRMF, VBPR, GradFashion).
+        by_class = K: the new users' shelves instead, (ids [n, C, kk], vals, cnt) as recommend_by_class returns them; class_cap = M:
+        their quota lists, (ids [n, kk], vals, cls) as recommend_capped returns them; classes as recommend_by_class takes them."""
+        if sum(x is not None for x in (diversify, by_class, class_cap)) > 1:
+            raise ValueError("recommend_new_users: one of diversify, by_class and class_cap")
         div = self._fold_diverse_args(k, diversify)              # (checked before anything is fitted)
+        if by_class is not None or class_cap is not None:
+            self._class_args(by_class if by_class is not None else 1, class_cap)
+            ccsr = self._class_csr(classes)
+            rows = self._fold_rows(histories, **fold)
+            return self._rank_fold_classes(rows, histories, ccsr, by_class) if by_class is not None \
+                else self._cap_fold_rows(rows, histories, ccsr, k, class_cap)
         return self._rank_fold_rows(self._fold_rows(histories, **fold), histories, k, div)
 
     def _fold_diverse_args(self, k, diversify):
@@ -494,6 +509,113 @@ class BPRMF(RecommenderModel):
             p_recs, p_ild = div_paths(new_path)
             with open(p_recs, 'w') as out, open(p_ild, 'w') as out_ild:
                 write_diverse(out, out_ild, labels, *self._rank_fold_rows(rows, lists, div=self._fold_diverse_args(None, {})))
+        if self.shelves_k > 0:                                   # shelf-new-user-recs-*: the same fitted rows
+            with open(shelf_file(path, "shelf-new-user-recs"), 'w') as out:
+                write_shelves(out, labels, *self._rank_fold_classes(rows, lists, self._class_csr(), self.shelves_k), self.shelf_count)
+        if self.class_cap > 0:                                   # cap-new-user-recs-*
+            with open(shelf_file(path, "cap-new-user-recs"), 'w') as out:
+                write_capped(out, labels, *self._cap_fold_rows(rows, lists, self._class_csr(), None, self.class_cap))
+
+    # ---- category shelves and quota lists: per-class top-K over the score rows (include/bprx.h, bprx_topk_classes) ---------------
+    def _class_args(self, k, cap):
+        """recommend_by_class' / recommend_capped's checks: a model on the engine's plain score block, the device path, K and cap."""
+        if not self.diverse:
+            raise NotImplementedError("%s: category lists come from BPRMF, VBPR and GradFashion" % type(self).__name__)
+        if getattr(self.evaluator, "force_host", False):
+            raise ValueError("category lists are ranked on the device only (no force_host): there is no host form")
+        if not 1 <= int(k) <= 1024:
+            raise ValueError("category lists: K lies in [1, 1024] (got %d)" % int(k))
+        if cap is not None and int(cap) < 1:
+            raise ValueError("category lists: the cap per class is >= 1 (got %d)" % int(cap))
+
+    def item_classes(self):
+        """The run's class table, an int64 array [num_items] with -1 for an item without a class: params.item_classes is such an
+        array, the path of a TSV of `item<TAB>class` rows (train_rec.read_item_classes) or the literal 'dataset' (the argmax of every
+        item's one-hot class vector, train_rec.dataset_item_classes).  Read once."""
+        if getattr(self, "_item_classes", None) is None:
+            src = getattr(self.params, "item_classes", None)
+            if src is None:
+                raise ValueError("%s: no class table (params.item_classes, --item_classes)" % type(self).__name__)
+            if isinstance(src, str):
+                from .train_rec import dataset_item_classes, read_item_classes
+                src = dataset_item_classes(self.params.dataset, self.num_items) if src == "dataset" \
+                    else read_item_classes(src, self.num_items)
+            self._item_classes = np.asarray(src, dtype=np.int64).reshape(-1)
+        return self._item_classes
+
+    def _class_csr(self, classes=None):
+        """ranking.class_csr of `classes` (an int array [num_items], -1 = no class); None: of the run's table, made once."""
+        if classes is not None:
+            return class_csr(np.asarray(classes), self.num_items, self.engine.device)
+        if getattr(self, "_class_csr_dev", None) is None:
+            self._class_csr_dev = class_csr(self.item_classes(), self.num_items, self.engine.device)
+        return self._class_csr_dev
+
+    def _class_blocks(self, want, n, C, K):
+        """ranking.wanted_blocks over n score rows of the catalogue's width, cut so that one call's outputs stay below 2^27 too."""
+        return wanted_blocks(want, n, class_rows_per_block(self.evaluator.user_block, self.num_items, C, K))
+
+    def recommend_by_class(self, users=None, k=None, classes=None):
+        """The shelves of every user of `users` (None: all, in id order): the k (default: params.shelves, else top_k) best items of
+        every class, the training items masked: numpy ids int64 [n, C, kk], vals fp32 [n, C, kk] and cnt int64 [n, C], kk = min(k,
+        I); list (u, c) holds cnt[u, c] entries best first, equal scores by ascending item, then -1 / 0.0.  classes: an int array
+        [num_items], the class of every item, -1 = none (None: the run's table, item_classes()); C = the largest class id + 1.  The
+        scores are predict_all's (Engine.score_block), ranked by Engine.topk_classes through ranking.rank_class_rows; the user's
+        order of the shelves is ranking.shelf_order(vals, cnt)."""
+        k = (self.shelves_k or self.evaluator.k) if k is None else int(k)
+        self._class_args(k, None)
+        return self._rank_user_classes(users, self._class_csr(classes), k)
+
+    def recommend_capped(self, users=None, k=None, cap=None, classes=None):
+        """The quota lists of every user of `users` (None: all, in id order): the user's top-k (default top_k) with at most `cap`
+        (default: params.class_cap) items of any one class, the training items masked and items without a class left out: numpy ids
+        int64 [n, k], vals fp32 [n, k] and cls int64 [n, k], best first (equal scores by ascending item), -1 / 0.0 / -1 past a
+        user's entries.  Exact: the k best of the union of every class's first min(cap, k) entries (ranking.cap_rows)."""
+        k = self.evaluator.k if k is None else int(k)
+        cap = (self.class_cap or k) if cap is None else int(cap)
+        self._class_args(k, cap)
+        ids, vals, cnt = self._rank_user_classes(users, self._class_csr(classes), min(cap, k))
+        return cap_rows(ids, vals, cnt, k, cap)
+
+    def _rank_user_classes(self, users, ccsr, K):
+        """recommend_by_class' lists for the class table ccsr: user blocks of Engine.score_block, the training CSR as the mask."""
+        eng, ev, U = self.engine, self.evaluator, self.num_users
+        want = np.arange(U, dtype=np.int64) if users is None else np.asarray(users, dtype=np.int64).reshape(-1)
+        if want.size and (want.min() < 0 or want.max() >= U):
+            raise ValueError("category lists: user ids lie in [0, %d)" % U)
+        ev._metrics_device_csr()
+        C, kk = ccsr[2], min(K, self.num_items)
+        out = np.full((want.size, C, kk), -1, np.int64), np.zeros((want.size, C, kk), np.float32), np.zeros((want.size, C), np.int64)
+        for b0, b1, rows, local in self._class_blocks(want, U, C, kk):
+            res = rank_class_rows(lambda s, kq: eng.topk_classes(s, ev._csr["train"], ccsr, kq, row0=b0), eng.score_block(b0, b1), K)
+            for o, r in zip(out, res):
+                o[rows] = r[local]
+        return out
+
+    def _rank_fold_classes(self, rows, histories, ccsr, K):
+        """recommend_by_class' lists for the fitted rows of _fold_rows(histories), each row's own history masked."""
+        eng, n = self.engine, len(histories)
+        C, kk = ccsr[2], min(int(K), self.num_items)
+        out = np.full((n, C, kk), -1, np.int64), np.zeros((n, C, kk), np.float32), np.zeros((n, C), np.int64)
+        for b0, b1, _, _ in self._class_blocks(np.arange(n, dtype=np.int64), n, C, kk):
+            sc, _ = self._score_fold_rows(rows, b0, b1)
+            res = rank_class_rows(lambda s, kq: eng.topk_classes(s, eng.csr(histories[b0:b1]), ccsr, kq), sc, K)
+            for o, r in zip(out, res):
+                o[b0:b1] = r
+        return out
+
+    def _cap_fold_rows(self, rows, histories, ccsr, k, cap):
+        """recommend_capped's lists for the fitted rows of _fold_rows(histories)."""
+        k = self.evaluator.k if k is None else int(k)
+        return cap_rows(*self._rank_fold_classes(rows, histories, ccsr, min(int(cap), k)), k, int(cap))
+
+    def _store_shelves(self, path):
+        """params.shelves = K > 0: shelf-recs-* (rows 'u\tclass\ti\tscore': per user the first params.shelf_count shelves, 0 = all,
+        in the user's order) and params.class_cap = M > 0: cap-recs-* (rows 'u\ti\tscore\tclass') next to the recs-* file at `path`."""
+        if self.shelves_k > 0:
+            self.evaluator.store_recommendation_shelves(shelf_file(path, "shelf-recs"), self.shelves_k, self.shelf_count)
+        if self.class_cap > 0:
+            self.evaluator.store_recommendation_capped(shelf_file(path, "cap-recs"), self.class_cap)
 
     # ---- similar items: the cosine of two items in the model's item space (include/bprx.h, bprx_sim_*) -------------------------
     sim_space = "latent"                                         # the space similar_items walks by default

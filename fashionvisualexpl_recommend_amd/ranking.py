@@ -6,6 +6,8 @@ new-audience-* (owners_of: the transposed mask; ITEM_FILES, item_file: their nam
 The contract is the reference's (Evaluator.py:225-239): mask the row, then take numpy_topk of it; numpy's unstable argsort
 decides the order of EQUAL scores.  The top-K kernel returns the list wherever it does not depend on that order and flags
 every other row (include/bprx.h, bprx_topk); a flagged row is redone by numpy_topk on the row the kernel has masked.
+The category lists (shelf-* / cap-*: class_csr, rank_class_rows, shelf_order, cap_rows; SHELF_FILES, shelf_file) have a total
+order of their own (score descending, item ascending: include/bprx.h, bprx_topk_classes), so nothing is flagged or redone there.
 Plain numpy + torch: no library call is made here, the caller brings the top-K entry (and the MMR entry of diversify_rows) as a
 callable.
 """
@@ -120,6 +122,98 @@ def diversify_rows(diversify, ids, vals, k, device):
     pool_val = torch.as_tensor(np.ascontiguousarray(vals, dtype=np.float32), device=device)
     idx, val, pen, ild = diversify(pool_idx, pool_val, kk)
     return idx.cpu().numpy().astype(np.int64), val.cpu().numpy(), pen.cpu().numpy(), ild.cpu().numpy()
+
+
+# ---- category shelves and quota lists: the per-class lists of bprx_topk_classes ------------------------------------------------
+def class_csr(item_class, num_items, device):
+    """The class table of a catalogue as bprx_topk_classes takes it: item_class is an int array [num_items], the class of every
+    item, -1 = no class (the item is on no list) -> (int64 ptr [C + 1], int32 items, C) with ptr / items tensors on `device`, C =
+    the largest class id + 1 (at least 1; a class id nobody has is an empty class), the items of a class ascending.  `items` is
+    never empty (one zero when every item is classless: a kernel is handed a pointer it does not read)."""
+    cls = np.asarray(item_class).reshape(-1)
+    if cls.size != num_items or cls.dtype.kind not in "iu":
+        raise ValueError("class_csr: one integer class per item, [%d] (got %s %s)" % (num_items, cls.dtype, cls.shape))
+    cls = cls.astype(np.int64)
+    if cls.size and cls.min() < -1:
+        raise ValueError("class_csr: a class id is >= 0, or -1 for no class (got %d)" % cls.min())
+    C = max(1, int(cls.max()) + 1 if cls.size else 1)
+    have = np.flatnonzero(cls >= 0)
+    items = have[np.argsort(cls[have], kind="stable")].astype(np.int32)            # by class, ascending item inside a class
+    ptr = np.zeros(C + 1, np.int64)
+    np.cumsum(np.bincount(cls[have], minlength=C), out=ptr[1:])
+    if items.size == 0:
+        items = np.zeros(1, np.int32)
+    return torch.as_tensor(ptr, device=device), torch.as_tensor(items, device=device), C
+
+
+def class_rows_per_block(user_block, width, C, K):
+    """rows_per_block, cut further so that one call's outputs (rows x C x K elements) stay below 2^27 as well; never below one row."""
+    return max(1, min(rows_per_block(user_block, width), ((1 << 27) - 1) // max(1, int(C) * int(K))))
+
+
+def rank_class_rows(topk_classes, scores, k):
+    """The per-class lists of a block of device score rows [n, width]: numpy ids int64 [n, C, kk], vals fp32 [n, C, kk] and cnt
+    int64 [n, C], kk = min(k, width); list (r, c) holds cnt[r, c] entries, best first, equal scores by ascending item, then -1 /
+    0.0.  topk_classes(scores, kk) is the entry (Engine.topk_classes with its mask lists and class table): it masks IN `scores`
+    and returns the device (idx, val, cnt).  One download per call; no row is redone (the order is total)."""
+    kk = min(int(k), int(scores.shape[1]))
+    idx, val, cnt = topk_classes(scores, kk)
+    return idx.cpu().numpy().astype(np.int64), val.cpu().numpy(), cnt.cpu().numpy().astype(np.int64)
+
+
+def shelf_order(vals, cnt):
+    """Per row the classes with a non-empty list, the row's shelves in the row's order: by the score of the list's first entry,
+    descending (compared as floats: +0.0 == -0.0), equal scores by ascending class id.  vals [n, C, kk] / cnt [n, C] as
+    rank_class_rows returns them -> a list of n int64 arrays."""
+    out = []
+    for r in range(cnt.shape[0]):
+        cls = np.flatnonzero(cnt[r] > 0)
+        out.append(cls[np.lexsort((cls, -(vals[r, cls, 0] + np.float32(0.0))))].astype(np.int64))
+    return out
+
+
+def cap_rows(ids, vals, cnt, k, cap):
+    """The quota lists of rank_class_rows' lists (ranked with K >= min(cap, k)): per row the first k of the union of every class's
+    first min(cap, k) entries by (score descending as floats, item ascending) -- the top-k with at most `cap` items of any class,
+    exactly.  Returns numpy ids int64 [n, k], vals fp32 [n, k] and cls int64 [n, k] (the class of each entry); -1 / 0.0 / -1 past
+    a row's entries."""
+    n, C, kk = ids.shape
+    k, m = int(k), min(int(cap), int(k), kk)
+    on = np.arange(m)[None, None, :] < np.minimum(cnt, m)[:, :, None]
+    it = np.where(on, ids[:, :, :m], np.iinfo(np.int64).max).reshape(n, C * m)
+    sc = np.where(on, vals[:, :, :m], np.float32(-np.inf)).reshape(n, C * m)
+    cl = np.broadcast_to(np.arange(C, dtype=np.int64)[None, :, None], (n, C, m)).reshape(n, C * m)
+    o = np.argsort(it, axis=1, kind="stable")                 # by item, then (stable) by score: equal scores stay item-ascending
+    it, sc, cl = (np.take_along_axis(a, o, axis=1) for a in (it, sc, cl))
+    o = np.argsort(-(sc + np.float32(0.0)), axis=1, kind="stable")[:, :k]
+    it, sc, cl = (np.take_along_axis(a, o, axis=1) for a in (it, sc, cl))
+    out_i, out_v, out_c = np.full((n, k), -1, np.int64), np.zeros((n, k), np.float32), np.full((n, k), -1, np.int64)
+    have = np.minimum(k, on.reshape(n, -1).sum(axis=1))
+    keep = np.arange(it.shape[1])[None, :] < have[:, None]
+    out_i[:, :it.shape[1]][keep], out_v[:, :it.shape[1]][keep], out_c[:, :it.shape[1]][keep] = it[keep], sc[keep], cl[keep]
+    return out_i, out_v, out_c
+
+
+def write_shelves(out, labels, ids, vals, cnt, count=0):
+    """One row 'label\tclass\titem\tscore' per shelf entry: label by label, the label's shelves in shelf_order (count > 0: only the
+    first `count` of them), each shelf best first.  Fields are formatted as write_ranked formats them."""
+    order = shelf_order(vals, cnt)
+    for r, label in enumerate(labels):
+        head = str(label) + '\t'
+        for c in (order[r][:count] if count > 0 else order[r]):
+            for q in range(int(cnt[r, c])):
+                out.write(head + str(c) + '\t' + str(ids[r, c, q]) + '\t' + str(vals[r, c, q]) + '\n')
+
+
+def write_capped(out, labels, ids, vals, cls):
+    """One row 'label\titem\tscore\tclass' per entry of cap_rows' lists, list by list up to its first empty slot, formatted as
+    write_ranked formats them."""
+    for r, label in enumerate(labels):
+        head = str(label) + '\t'
+        for q, item in enumerate(ids[r]):
+            if item < 0:
+                break
+            out.write(head + str(item) + '\t' + str(vals[r, q]) + '\t' + str(cls[r, q]) + '\n')
 
 
 BECAUSE_MAX_LIST = 1024                                       # slots of one list in bprx_because
@@ -259,6 +353,22 @@ def warm_file(path, kind):
         raise ValueError("%r is neither a recs-* nor a best-recs-* path" % path)
     if kind not in WARM_FILES:
         raise ValueError("warm_file: %r is none of %s" % (kind, ", ".join(WARM_FILES)))
+    return head + kind + tail
+
+
+# The files of a run whose lists know the items' CLASSES (--item_classes): shelf-* has one block per user and class (rows 'user class
+# item score'), cap-* the top-k with a per-class cap (rows 'user item score class'), named like the files above.
+SHELF_FILES = {"shelf-recs": None, "cap-recs": None, "shelf-new-user-recs": None, "cap-new-user-recs": None}
+
+
+def shelf_file(path, kind):
+    """run_file for the kinds of SHELF_FILES: the file of `kind` next to the recs-* / best-recs-* file at `path`, 'best-' stays in
+    front; ValueError for a path whose file name starts with neither, and for a kind that is none of SHELF_FILES."""
+    head, base, tail = _split_run_file(path)
+    if base != "recs":
+        raise ValueError("%r is neither a recs-* nor a best-recs-* path" % path)
+    if kind not in SHELF_FILES:
+        raise ValueError("shelf_file: %r is none of %s" % (kind, ", ".join(SHELF_FILES)))
     return head + kind + tail
 
 

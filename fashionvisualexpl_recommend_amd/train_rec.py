@@ -20,6 +20,9 @@ best-new-audience-* (the visual score of items the model was not trained on).
 --af_new_items EDGES COLOUR CLASSES, --af_warm_items PATH and --af_audience K (attentive_fashion only) are the warm-item and
 audience products of AttentiveFashion: Gi rows for new items from their first buyers (warm-recs-*, warm-audience-*) and
 audience-* for the catalogue, each row with its three attentions.
+--item_classes PATH with --shelves K / --class_cap M (bprmf, vbpr, grad_fashion) writes shelf-recs-* (every user's K best items of
+every item class, the classes in the user's order) and cap-recs-* (the top_k with at most M items of any class) next to recs-*, and
+with --new_users shelf-new-user-recs-* / cap-new-user-recs-*.
 --warm_items PATH (bprmf, vbpr, grad_fashion) fits Gi / Bi rows for new items from their first buyers (rows `row<TAB>user`; vbpr and
 grad_fashion: rows of the --new_items table) and writes warm-recs-* / best-warm-recs-* files, with --audience K also warm-audience-*.
 Run as `python -m fashionvisualexpl_recommend_amd.train_rec --rec bprmf --dataset <name> ...`.
@@ -137,6 +140,21 @@ def parse_args(argv=None):
                              "items, bought ones excluded) are written next to recs-* / best-recs-*; with --audience K also "
                              "warm-audience-* / best-warm-audience-* (row, u, score).  A row without buyers keeps zero Gi / Bi and "
                              "scores as in new-recs-*")
+    parser.add_argument('--item_classes', default=None, metavar='PATH',
+                        help="bprmf, vbpr, grad_fashion: the class (category) of every catalogue item, a TSV of `item<TAB>class` rows "
+                             "with non-negative integer class ids, every item exactly once; or the literal `dataset`: the argmax of "
+                             "every item's original/features/one_hot_encodings/{i}.npy.  Read by --shelves and --class_cap")
+    parser.add_argument('--shelves', type=int, default=0, metavar='K',
+                        help="bprmf, vbpr, grad_fashion: also write shelf-recs-* / best-shelf-recs-* files next to recs-* / "
+                             "best-recs-*: every user's K (1..1024) best items of every class of --item_classes, training items "
+                             "excluded, rows `u class i score`, the user's classes ordered by their best item's score, each shelf "
+                             "best first; with --new_users also shelf-new-user-recs-*; 0 = off")
+    parser.add_argument('--shelf_count', type=int, default=0, metavar='S',
+                        help="--shelves: only every user's first S shelves; 0 = all")
+    parser.add_argument('--class_cap', type=int, default=0, metavar='M',
+                        help="bprmf, vbpr, grad_fashion: also write cap-recs-* / best-cap-recs-* files next to recs-* / best-recs-*: "
+                             "every user's top_k with at most M items of any one class of --item_classes, rows `u i score class`, "
+                             "best first; with --new_users also cap-new-user-recs-*; 0 = off")
     parser.add_argument('--af_new_items', nargs=3, default=None, metavar=('EDGES.npy', 'COLOUR.npy', 'CLASSES.npy'),
                         help="attentive_fashion: the inputs of n items the model was not trained on: edge images uint8 [n, 224, 224], "
                              "raw colour histograms [n, Dc] (each divided by its own max-abs, as the catalogue's are; an all-zero "
@@ -275,6 +293,24 @@ def parse_args(argv=None):
             read_audience_items(args.audience_items)
         except (OSError, ValueError) as e:
             parser.error("--audience_items: %s" % e)
+    if not 0 <= args.shelves <= 1024:
+        parser.error("--shelves takes 0 (off) .. 1024 (got %s)" % args.shelves)
+    if args.shelf_count < 0:
+        parser.error("--shelf_count takes S >= 0, 0 = all (got %s)" % args.shelf_count)
+    if args.shelf_count != 0 and args.shelves == 0:
+        parser.error("--shelf_count needs --shelves K")
+    if args.class_cap < 0:
+        parser.error("--class_cap takes M >= 1, 0 = off (got %s)" % args.class_cap)
+    if args.shelves != 0 or args.class_cap != 0 or args.item_classes is not None:
+        if args.rec not in ('bprmf', 'vbpr', 'grad_fashion'):
+            parser.error("--item_classes / --shelves / --class_cap need --rec bprmf, vbpr or grad_fashion (got --rec %s)" % args.rec)
+        if args.item_classes is None:
+            parser.error("--shelves / --class_cap need --item_classes PATH (or --item_classes dataset)")
+        if args.item_classes != 'dataset':
+            try:
+                read_item_classes(args.item_classes)
+            except (OSError, ValueError) as e:
+                parser.error("--item_classes: %s" % e)
     if args.hard_negatives != 0 and not 2 <= args.hard_negatives <= 16:
         parser.error("--hard_negatives takes 0 (off) or 2 .. 16 (got %s)" % args.hard_negatives)
     if args.hard_negatives != 0 and args.sampler != 'philox':
@@ -321,6 +357,67 @@ def check_audience_items(args, num_items):
         read_audience_items(args.audience_items, num_items)
     except ValueError as e:
         argparse.ArgumentParser(description="Run train of the Recommender Model.").error("--audience_items: %s" % e)
+
+
+def read_item_classes(path, num_items=None):
+    """The --item_classes file: rows `item<TAB>class`, two non-negative integers -> the class of every item, an int64 array indexed
+    by item ([num_items]; without num_items: [largest item + 1], -1 where the file has no line).  Empty lines are skipped; a line
+    that is not two non-negative integers, a repeated item and (with num_items) an item outside the catalogue raise ValueError with
+    the line's number; with num_items an item without a line raises ValueError naming the item."""
+    import numpy as np
+    seen = {}
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip():
+                continue
+            parts = line.split("\t")
+            try:
+                if len(parts) != 2:
+                    raise ValueError
+                item, cls = int(parts[0]), int(parts[1])
+            except ValueError:
+                raise ValueError("%s:%d: expected `item<TAB>class`, two integers, got %r" % (path, ln, line)) from None
+            if item < 0 or cls < 0:
+                raise ValueError("%s:%d: item and class are not negative, got %r" % (path, ln, line))
+            if num_items is not None and item >= num_items:
+                raise ValueError("%s:%d: the item %d is outside the catalogue [0, %d)" % (path, ln, item, num_items))
+            if item in seen:
+                raise ValueError("%s:%d: the item %d has a class already (line %d)" % (path, ln, item, seen[item][0]))
+            seen[item] = (ln, cls)
+    out = np.full(max(seen, default=-1) + 1 if num_items is None else num_items, -1, np.int64)
+    for item, (_, cls) in seen.items():
+        out[item] = cls
+    if num_items is not None and (out < 0).any():
+        raise ValueError("%s: the item %d has no class (every catalogue item appears exactly once)" % (path, int(np.flatnonzero(out < 0)[0])))
+    return out
+
+
+def dataset_item_classes(dataset, num_items):
+    """--item_classes dataset: the argmax of every item's one-hot class vector original/features/one_hot_encodings/{i}.npy (the
+    table AttentiveFashion reads whole) -> int64 [num_items].  A missing file raises ValueError naming it."""
+    import numpy as np
+    d = configs.class_features_path_dir(dataset)
+    out = np.empty(num_items, np.int64)
+    for i in range(num_items):
+        f = d + "%d.npy" % i
+        if not os.path.exists(f):
+            raise ValueError("--item_classes dataset: the class vector %s is missing" % f)
+        out[i] = int(np.argmax(np.asarray(np.load(f)).reshape(-1)))
+    return out
+
+
+def check_item_classes(args, num_items):
+    """--item_classes against the loaded catalogue, before anything is trained: an item outside it or without a class (or a missing
+    class vector of the dataset) ends the run as a rejected argument does.  Returns the table, int64 [num_items] (None without the
+    flag; an array that is there already is returned as it is), so that it is read once per run."""
+    src = getattr(args, "item_classes", None)
+    if src is None or not isinstance(src, str):
+        return src
+    try:
+        return dataset_item_classes(args.dataset, num_items) if src == 'dataset' else read_item_classes(src, num_items)
+    except (OSError, ValueError) as e:
+        argparse.ArgumentParser(description="Run train of the Recommender Model.").error("--item_classes: %s" % e)
 
 
 def read_warm_items(path, num_rows=None):
@@ -419,6 +516,11 @@ def train(argv=None):
         raise NotImplementedError('--audience runs on one GPU (the sharded drivers write no audience-* files): use --world_size 1')
     if args.warm_items is not None and int(args.world_size) > 1:
         raise NotImplementedError('--warm_items runs on one GPU (the sharded drivers write no warm-* files): use --world_size 1')
+    if (args.shelves != 0 or args.class_cap != 0) and int(args.world_size) > 1:
+        raise NotImplementedError('--shelves / --class_cap run on one GPU (the sharded drivers write no shelf-* / cap-* files): use '
+                                  '--world_size 1')
+    if args.class_cap != 0 and min(args.class_cap, args.top_k) > 1024:
+        raise ValueError('--class_cap ranks on the device only (min(class_cap, top_k) <= 1024): there is no host form')
     if args.warm_items is not None and args.new_items is not None:                  # a row past the table: before anything is trained
         import numpy as np
         read_warm_items(args.warm_items, int(np.load(args.new_items[0], mmap_mode='r').shape[0]))
@@ -464,6 +566,7 @@ def train(argv=None):
         print('ITERATION %d/%d WITH REGULARIZATION: %f' % (it + 1, len(list(args.list_of_regs)), current_reg))
         data = DataLoader(params=args)
         check_audience_items(args, data.num_items)
+        class_table = check_item_classes(args, data.num_items)
         if args.warm_items is not None and any(u >= data.num_users for who in read_warm_items(args.warm_items) for u in who):
             raise ValueError('--warm_items: a buyer is outside the %d users of the dataset' % data.num_users)
         if args.af_warm_items is not None and any(u >= data.num_users for who in read_warm_items(args.af_warm_items) for u in who):
@@ -474,6 +577,7 @@ def train(argv=None):
         for arg in vars(args):
             print("\t- " + str(arg) + " = " + str(getattr(args, arg)))
         print("\n")
+        args.item_classes = class_table                            # (the table itself from here on: the model does not read it again)
         if world > 1 and args.rec == 'vbpr' and args.shard == 'item':
             from .sharded import ShardedVBPR
             model = ShardedVBPR(data, args)

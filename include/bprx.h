@@ -165,7 +165,7 @@ BPRX_API int bprx_sync_adam(bprx_handle *h, void *stream);
      bprx_topk_rows                                                   VBPR, not fp8       yes           -     -      -
      bprx_apply_user_msgs                                             any                 yes           -     -      -
      bprx_sum_dense_parts                                             VBPR                -             -     -      -
-     bprx_topk, bprx_topk_lists, bprx_topk_rows_masked, bprx_eval_*, bprx_tables_dirty, bprx_set_adam_step, bprx_clear_*_grad, bprx_sync_check,
+     bprx_topk, bprx_topk_lists, bprx_topk_rows_masked, bprx_topk_classes, bprx_eval_*, bprx_tables_dirty, bprx_set_adam_step, bprx_clear_*_grad, bprx_sync_check,
      bprx_pack_user_msg, the bind calls                               any                 -             -     -      -
    Not behind the gate: bprx_step and bprx_step_begin[_sparse] (a step may carry the update), the samplers, the profile calls, bprx_last_error, bprx_set_hyper,
    bprx_set_loss_lag, the getters, bprx_settle and bprx_dense_pending. */
@@ -372,6 +372,32 @@ BPRX_API int bprx_audience_block(bprx_handle *h, const float *Pq, int64_t nq, in
    bound or not (as bprx_topk_lists). */
 BPRX_API int bprx_topk_rows_masked(bprx_handle *h, int64_t nrows, int32_t width, float *scores, const int64_t *list_ptr,
                                    const int32_t *list_items, int32_t K, int32_t *idx, float *val, int32_t *flag, void *stream);
+
+/* ---- category shelves: the K best entries of every CLASS of a score row (a segmented top-K) --------------------------------
+   "Dresses for you, shoes for you": every list surface above is blind to item category; this one call over a block of score rows
+   returns, per row, one list per class, and the quota list (the top-k with at most M items of any class) is the k best of the union
+   of every class's first min(M, k) entries.  Model-agnostic: it ranks a score block and touches no table or slot.
+   scores fp32 [nrows, width] (row stride width, device).  Mask: row r gets -inf IN `scores` at list_items[list_ptr[row0 + r] ..
+   list_ptr[row0 + r + 1]) (list_ptr int64, device; an id outside [0, width) is ignored, a repeated id is harmless; list_ptr ==
+   NULL masks nothing and list_items is not read); afterwards the row holds -inf at the masked ids and is otherwise bit-unchanged.
+   Classes: class_ptr int64 [C + 1], class_items int32 [class_ptr[C]] (device): the items of class c in ascending order, every item
+   in at most one class; an item in no class is on no list, an empty class is allowed.  A class_items entry outside [0, width) is
+   skipped and reported by bprx_sync_check (BPRX_E_RANGE); it is never dereferenced.
+   Outputs idx int32 [nrows, C, K], val fp32 [nrows, C, K], cnt int32 [nrows, C]:
+       cnt[r][c] = min(K, number of items of class c whose score in the masked row is > -inf)    (a masked item is on no shelf)
+       slots past cnt hold -1 / 0.0f.
+   Order: a total order of this surface's own, so there is NO flag and no host redo: score descending compared as floats (+0.0 ==
+   -0.0), equal scores by ascending item id -- at the selection boundary too: when more items equal the K-th score than there are
+   slots left, the smallest ids are taken.  val is read from the row: val[r][c][q] has the bits of scores[r][idx[r][c][q]] (the sign
+   of a zero is kept).  NaN scores are outside the contract.  List (r, c) depends on row r's scores at the items of class c and on
+   row r's mask only: not on nrows, on the row's position, on the other classes or on their numbering.
+   1 <= K <= 1024, C >= 1, width >= 1, nrows >= 0, row0 >= 0, nrows * C * K < 2^31, else BPRX_E_INVALID; a NULL pointer with rows
+   to list: BPRX_E_INVALID; nrows == 0: BPRX_OK, nothing is launched.  Every accepted shape launches (the workgroup counts, up
+   to 2^31, are folded into two grid dimensions).  Any handle, bound or not (as bprx_topk_lists); the call
+   allocates nothing and after an error the handle stays usable. */
+BPRX_API int bprx_topk_classes(bprx_handle *h, int64_t nrows, int32_t width, float *scores, int64_t row0, const int64_t *list_ptr,
+                               const int32_t *list_items, const int64_t *class_ptr, const int32_t *class_items, int32_t C,
+                               int32_t K, int32_t *idx, float *val, int32_t *cnt, void *stream);
 
 /* ---- BPRMF, VBPR and GradFashion: warm items, new items with first buyers --------------------------------------------------
    The twin of bprx_fold_in on the item side.  An item outside the catalogue is scored by its picture alone
