@@ -619,7 +619,7 @@ __global__ __launch_bounds__(NW * 64) void k_proj_bwd_bf16_v3(const uint16_t *__
         i32x4_t v_;                                                                                                      \
         if constexpr (MASK) {                                                                                            \
           const uint32_t br_ = (uint32_t)(((t0 - tbeg) >> 5) + blk / CBK);            /* block row within the split */   \
-          const uint32_t on_ = (tmask[br_] >> ((pp & 511) >> 4)) & 1u;                                                   \
+          const uint32_t on_ = (mword[ST] >> ((pp & 511) >> 4)) & 1u;                                                    \
           v_ = ld_buf16<!F8>(frs, on_ ? (uint32_t)((m0q >> 7) + blk % CBK) * 8192u + (uint32_t)(pp & 511) * 16u : BUF_OOB, \
                              br_ * (uint32_t)(Deq >> 7) * 8192u);                                                        \
         } else {                                                                                                         \
@@ -684,6 +684,18 @@ __global__ __launch_bounds__(NW * 64) void k_proj_bwd_bf16_v3(const uint16_t *__
       if (idx < BTV * WCH) *reinterpret_cast<uint4 *>(&Ws[tr * WSB + ((tr & 8) << 4) + ch * 16]) = v;                    \
     }                                                                                                                    \
   }
+  // MASK: a tile's row-bit word (BTV == 32: one per tile), read from LDS ahead of the tile's loads.  The prologue reads its PD
+  // words first, behind ONE wait, and then issues tile by tile: with a read and a wait in front of every tile's loads the
+  // prologue's loads come out as F0 F0 F1 F1 W0 W1 F2 F2 W2, W0 has four younger loads where the loop has two, and the
+  // loop's counted waits in front of the tile stores are shortened to match on every trip.
+  static_assert(!MASK || BTV == 32, "one mask word per tile");
+  uint32_t mword[MASK ? PD : 1];
+#define BWD3_MASKW(ST, TILE)                                                                                             \
+  if constexpr (MASK) {                                                                                                  \
+    int tile_ = (TILE);                                                                                                  \
+    tile_ = tile_ < ntiles ? tile_ : ntiles - 1;                                                                         \
+    mword[ST] = tmask[descend ? (ntiles - 1 - tile_) : tile_];                                                           \
+  }
   if (ntiles == 0) {                                  // empty split: zero slab
     float *slab0 = part + ((size_t)by * D + m0) * PS;
     for (int e = threadIdx.x; e < MC * PS; e += NTH) slab0[e] = 0.f;
@@ -700,13 +712,19 @@ __global__ __launch_bounds__(NW * 64) void k_proj_bwd_bf16_v3(const uint16_t *__
     }
   }
 #pragma unroll
-  for (int st = 0; st < PD; ++st) BWD3_ISSUE(st, st)
+  for (int st = 0; st < PD; ++st) BWD3_MASKW(st, st)
+#pragma unroll
+  for (int st = 0; st < PD; ++st) {
+    BWD3_ISSUE(st, st)
+    if constexpr (MASK) __builtin_amdgcn_sched_barrier(0);           // tile by tile (F, F, W), as the loop issues them
+  }
   for (int tile0 = 0; tile0 < ntiles; tile0 += PD) {
 #pragma unroll
    for (int st = 0; st < PD; ++st) {                 // tiles past the end are all-zero: computed, harmless
     if (DB == 1) __syncthreads();                     // (DB == 2: the image of tile t+1 was last read for tile t-1, and every
     BWD3_COMMIT(st, tile0 + st)                       //  wave has passed tile t's barrier since.  Committing tile t+1 BEHIND tile
     __syncthreads();                                  //  t's barrier, in one block with tile t's MFMAs, measured 2-4 % slower.)
+    BWD3_MASKW(st, tile0 + st + PD)
     BWD3_ISSUE(st, tile0 + st + PD)
     const unsigned char *const Fs = Fs0 + (DB == 2 ? ((tile0 + st) & 1) * IMG : 0), *const Ws = Ws0 + (DB == 2 ? ((tile0 + st) & 1) * IMG : 0);
 #pragma unroll
@@ -736,6 +754,7 @@ __global__ __launch_bounds__(NW * 64) void k_proj_bwd_bf16_v3(const uint16_t *__
   }
 #undef BWD3_ISSUE
 #undef BWD3_COMMIT
+#undef BWD3_MASKW
   float *slab = part + ((size_t)by * D + m0) * PS;
 #pragma unroll
   for (int mt = 0; mt < MTW; ++mt)

@@ -1364,15 +1364,17 @@ __global__ __launch_bounds__(TS_T) void k_triplet_seg(SparseArgs a, SegUser su, 
   const int u = clamp_index(u_raw, a.U, a.errflag, 1);
   const int i = clamp_index(i_raw, a.I, a.errflag, 2), j = clamp_index(j_raw, a.I, a.errflag, 3);
   const int k = a.k, d = a.d, kd = k + d;
-  // everything that depends on the indices alone is requested together with the rows
+  // everything that depends on the indices alone is requested together with the rows, in straight-line code: a load under
+  // a branch of its own (`if (mode == 0) slot = uslot_of[u]`) is waited for at the end of that branch, in front of the rows
   const float bi = a.Bi[i], bj = a.Bi[j];
   int spI = a.seg_rank[b] + a.seg_ptr[i], spJ = a.seg_rank[B + b] + a.seg_ptr[j];
   {
     const unsigned top = (unsigned)a.seg_cap - 1u;          // (never beyond the allocation, whatever the index state holds)
     spI = (int)((unsigned)spI < top ? (unsigned)spI : top); spJ = (int)((unsigned)spJ < top ? (unsigned)spJ : top);
   }
-  int slot = 0, ucnt = 0;
-  if (su.mode == 0) { slot = su.uslot_of[u]; ucnt = a.cntU[u]; }    // (the user's occurrences in the batch: final since k_index_seg)
+  const int32_t *const slot_of = su.mode == 0 ? su.uslot_of : a.cntU;      // mode 1: any valid address, the values are unused
+  const int slot_ld = slot_of[u], ucnt_ld = a.cntU[u];             // (the user's occurrences in the batch: final since k_index_seg)
+  const int slot = su.mode == 0 ? slot_ld : 0, ucnt = su.mode == 0 ? ucnt_ld : 0;
   const int c4 = lane * 4;
   const bool hk = c4 < k, hd = c4 < d;
   const int ck = hk ? c4 : 0, cd = hd ? c4 : 0;
@@ -1547,13 +1549,17 @@ __global__ __launch_bounds__(IS_T) void k_item_seg(SparseArgs a, float *__restri
     nl = nl < a.seg_lead_cap - a.seg_lead_over ? nl : a.seg_lead_cap - a.seg_lead_over;
     if (e0 - a.seg_lead_over >= nl) return;
   }
-  const int4 job = a.seg_lead[e0];
+  // The job record is ONE 16-byte load: all four fields are made live here, in front of the early exit (with only .z
+  // read before it, the load is split and the .x / .y half is requested behind the branch -- a second round trip).
+  int4 job = a.seg_lead[e0];
+  asm volatile("" : "+v"(job.x), "+v"(job.y), "+v"(job.z), "+v"(job.w));
   if (job.z <= 0) return;
   const int item = clamp_quiet(job.x, a.I);
   const int n = job.w;
   int e_first = job.y, ns = job.z;
-  if (e_first < 0 || ns < 0 || e_first + ns > a.seg_cap) ns = 0;    // (never beyond the allocation)
+  if (e_first < 0 || ns < 0 || e_first + ns > a.seg_cap) { ns = 0; e_first = 0; }   // (never beyond the allocation)
   const int2 *ent = a.seg_ent + e_first;
+  const int e_last = ns > 0 ? ns - 1 : 0;                            // entries are read clamped to the chunk
   const int k = a.k, d = a.d;
   const int c4 = lane * 4;
   const bool hk = c4 < k, hd = c4 < d;
@@ -1572,8 +1578,11 @@ __global__ __launch_bounds__(IS_T) void k_item_seg(SparseArgs a, float *__restri
   const size_t og = (size_t)item * k + c4, ow = (size_t)item * a.PS;
   float4 q = ld4(Gi + (size_t)item * k + ck);
   const float pb = Bi[item];
-  for (; e + 2 <= ns; e += 2) {                                       // two entries in flight
-    const int2 r0 = ent[e], r1 = ent[e + 1];
+  // The entries run one pair ahead of the rows: the next pair (and the odd last entry) is requested before the rows in
+  // front of it are consumed, so a further pair costs one round trip -- its rows -- not two.
+  int2 r0 = ent[0], r1 = ent[1 < e_last ? 1 : e_last];
+  for (; e + 2 <= ns; e += 2) {                                       // two entries' rows in flight
+    const int2 n0 = ent[e + 2 < e_last ? e + 2 : e_last], n1 = ent[e + 3 < e_last ? e + 3 : e_last];
     const int u0 = r0.x & 0x7fffffff, u1 = r1.x & 0x7fffffff;
     const float4 p0 = ld4(UG + (size_t)u0 * gs + ck), p1 = ld4(UG + (size_t)u1 * gs + ck);
     const float4 t0 = ld4(UT + (size_t)u0 * ds + cd), t1 = ld4(UT + (size_t)u1 * ds + cd);
@@ -1584,9 +1593,13 @@ __global__ __launch_bounds__(IS_T) void k_item_seg(SparseArgs a, float *__restri
     const float g0 = s0 * mk, g1 = s1 * mk, h0 = s0 * md, h1 = s1 * md;
     ag.x += g0 * p0.x + g1 * p1.x; ag.y += g0 * p0.y + g1 * p1.y; ag.z += g0 * p0.z + g1 * p1.z; ag.w += g0 * p0.w + g1 * p1.w;
     at.x += h0 * t0.x + h1 * t1.x; at.y += h0 * t0.y + h1 * t1.y; at.z += h0 * t0.z + h1 * t1.z; at.w += h0 * t0.w + h1 * t1.w;
+    // (a second use of the loaded values: without one, the loop-carried loads are folded into one load of a loop-carried
+    // address at the top of the NEXT trip -- the entry is then requested where it is needed, a round trip in front of its rows)
+    asm volatile("" ::"v"(n0.x), "v"(n0.y), "v"(n1.x), "v"(n1.y));
+    r0 = n0; r1 = n1;
   }
-  if (e < ns) {
-    const int2 r0 = ent[e];
+  asm volatile("" ::"v"(r1.x), "v"(r1.y));   // (live on the path around the loop too: the first ent[1] stays beside ent[0], in front of the branch)
+  if (e < ns) {                                                     // the odd last entry: r0 holds it already
     const int u0 = r0.x & 0x7fffffff;
     const float4 p0 = ld4(UG + (size_t)u0 * gs + ck);
     const float4 t0 = ld4(UT + (size_t)u0 * ds + cd);
