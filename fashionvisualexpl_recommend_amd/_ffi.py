@@ -125,6 +125,8 @@ def lib():
         "bprx_audience_block": (C.c_int, [vp, vp, i64, i64, i64, vp, vp]),
         "bprx_topk_rows_masked": (C.c_int, [vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
         "bprx_topk_classes": (C.c_int, [vp, i64, i32, vp, i64, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+        "bprx_style_assign": (C.c_int, [vp, i32, vp, i64, i64, i64, vp, vp, i32, vp, vp, vp, vp]),
+        "bprx_style_update": (C.c_int, [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
         "bprx_fold_in_items": (C.c_int, [vp, vp, vp, vp, vp, i64, vp, i32, f32, f32, i32, vp, vp, vp, vp]),
         "bprx_score_warm_block": (C.c_int, [vp, i32, i32, vp, vp, vp, i64, vp, vp]),
         "bprx_audience_warm_block": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, vp, vp]),
@@ -242,7 +244,8 @@ EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error",
            "bprx_profile_read", "bprx_sample_philox", "bprx_epoch_prepare", "bprx_epoch_slots", "bprx_sample_epoch", "bprx_sample_philox_h", "bprx_sample_epoch_h", "bprx_index_pass_kind", "bprx_index_pass_queue", "bprx_proj_mask_kind", "bprx_adam_rows", "bprx_step_lr", "bprx_user_msg_floats", "bprx_pack_user_msg",
            "bprx_apply_user_msgs", "bprx_sampler_create",
            "bprx_sampler_destroy", "bprx_sampler_count", "bprx_sampler_ref_stream", "bprx_settle", "bprx_dense_pending", "bprx_set_loss_lag",
-           "bprx_sample_philox_hard", "bprx_sample_epoch_hard", "bprx_hard_snapshot", "bprx_topk_classes"]
+           "bprx_sample_philox_hard", "bprx_sample_epoch_hard", "bprx_hard_snapshot", "bprx_topk_classes",
+           "bprx_style_assign", "bprx_style_update"]
 
 
 def check(handle, rc):

@@ -444,6 +444,46 @@ int bprx_sim_enter(bprx_handle *h, const char *what, int32_t space, const float 
 // the parts of z for the catalogue (Pq == nullptr) or the caller's projected rows
 void bprx_sim_parts(const bprx_handle *h, int32_t space, const float *Pq, SimPart &g, SimPart &p);
 
+// ---- the fp32 MFMA GEMM tile of the block scores (bprx_eval.hip) and of bprx_style_assign (bprx_styles.hip) ----
+namespace bprx_gemm {
+
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+constexpr int TM = 128, TN = 128, GKC = 16, GLD = GKC + 1;   // 17-float LDS rows: conflict-free column reads
+
+// one K phase: acc += A[rows, 0:K] . B[cols, 0:K]^T   (A row stride lda, B row stride ldb)
+__device__ __forceinline__ void gemm_phase(const float *__restrict__ A, int lda, int arow0, int arows,
+                                           const float *__restrict__ Bm, int ldb, int brow0, int brows, int K,
+                                           float (*As)[GLD], float (*Bs)[GLD], f32x16 (&acc)[2][2], int wr, int wc, int lane) {
+  const int t = threadIdx.x;
+  for (int k0 = 0; k0 < K; k0 += GKC) {
+    __syncthreads();
+    // 128 rows x 16 floats per operand: thread t -> row t/2, 8 floats at (t%2)*8
+    {
+      const int r = t >> 1, c0 = (t & 1) * 8;
+#pragma unroll
+      for (int x = 0; x < 8; ++x) {
+        const int kk = k0 + c0 + x;
+        As[r][c0 + x] = (r < arows && kk < K) ? A[(size_t)(arow0 + r) * lda + kk] : 0.f;
+        Bs[r][c0 + x] = (r < brows && kk < K) ? Bm[(size_t)(brow0 + r) * ldb + kk] : 0.f;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < GKC; kk += 2) {
+      const int kq = kk + (lane >> 5), rr = lane & 31;
+      const float a0 = As[wr * 64 + rr][kq], a1 = As[wr * 64 + 32 + rr][kq];
+      const float b0 = Bs[wc * 64 + rr][kq], b1 = Bs[wc * 64 + 32 + rr][kq];
+      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+    }
+  }
+}
+
+}  // namespace bprx_gemm
+
 // ---- host helpers ----
 // Adam's bias-corrected step size at optimizer.iterations = it
 static inline float bprx_adam_lr_at(const bprx_config &c, int64_t it) {

@@ -749,6 +749,51 @@ class Engine:
                                                    _addr(rn_items), _addr(out), _stream()))
         return out
 
+    # ---- style clusters (include/bprx.h: spherical k-means of the item space, bprx_style_assign / bprx_style_update) ---------------
+    def _style_width(self, space):
+        """The numbers of an item vector in `space`: k, d or k + d."""
+        sp = _ffi.SIM_SPACE.get(space, space)
+        return {0: self.k, 1: self.d, 2: self.k + self.d}.get(sp, 0)
+
+    def _style_table(self, what, space, cent):
+        """S of the centroid table `cent`, a contiguous fp32 device tensor [S, w] (w = the width of `space`), checked."""
+        w = self._style_width(space)
+        if not (isinstance(cent, torch.Tensor) and cent.is_cuda and cent.dtype == torch.float32 and cent.is_contiguous()
+                and cent.dim() == 2 and (w == 0 or int(cent.shape[1]) == w)):
+            raise ValueError("%s: the centroids are a contiguous fp32 device tensor [S, %d]" % (what, w))
+        return int(cent.shape[0])
+
+    def style_assign(self, space, cent, q0, q1, rn_items, Pq=None, rn_q=None, want_second=True):
+        """bprx_style_assign: (style int32 [q1 - q0], cos fp32 [q1 - q0], second fp32 [q1 - q0]) of the catalogue items q0 .. q1-1
+        (Pq = project_rows(F): of rows q0 .. q1-1 of Pq, with rn_q = sim_rnorm(space, Pq), visual only) against the centroid rows
+        of `cent` (fp32 [S, w], unit or zero rows): the nearest centroid by cosine (ties: the smallest index; -1 for a zero row),
+        that cosine, and the largest cosine with another centroid (-inf for S == 1; None with want_second=False)."""
+        if rn_q is None:
+            if Pq is not None:
+                raise ValueError("style_assign: rows from outside the catalogue come with their norms (rn_q = sim_rnorm(space, Pq))")
+            rn_q = rn_items
+        S = self._style_table("style_assign", space, cent)
+        nq = self.I if Pq is None else int(Pq.shape[0])
+        n = max(int(q1) - int(q0), 0)
+        buf = lambda dtype: torch.empty(max(n, 1), dtype=dtype, device=self.device)        # (an empty range still hands pointers over)
+        style, cos, second = buf(torch.int32), buf(torch.float32), buf(torch.float32) if want_second else None
+        _ffi.check(self.h, self.lib.bprx_style_assign(self.h, _ffi.SIM_SPACE.get(space, space), _addr(Pq), nq, int(q0), int(q1),
+                                                      _addr(rn_q), _addr(cent), S, _addr(style), _addr(cos), _addr(second), _stream()))
+        return style[:n], cos[:n], None if second is None else second[:n]
+
+    def style_update(self, space, rn_items, member_csr, cent_prev):
+        """bprx_style_update: (cent fp32 [S, w], mass fp32 [S]) for the clusters of member_csr = (int64 ptr [S + 1], int32 items, S)
+        as ranking.class_csr makes it: every cluster's fp64 sum of its members' unit rows, normalised; an empty cluster (or one
+        whose rows cancel) keeps its row of cent_prev and has mass 0.  rn_items = sim_rnorm(space)."""
+        ptr, items, S = member_csr
+        if self._style_table("style_update", space, cent_prev) != int(S):
+            raise ValueError("style_update: %d clusters, %d centroid rows" % (int(S), int(cent_prev.shape[0])))
+        cent = torch.empty_like(cent_prev)
+        mass = torch.empty(int(S), dtype=torch.float32, device=self.device)
+        _ffi.check(self.h, self.lib.bprx_style_update(self.h, _ffi.SIM_SPACE.get(space, space), _addr(rn_items), _addr(ptr), _addr(items),
+                                                      int(S), _addr(cent_prev), _addr(cent), _addr(mass), _stream()))
+        return cent, mass
+
     # ---- audiences (include/bprx.h: the score block item-major, one row per item against every user) -----------------------------
     def audience_block(self, q0, q1, P=None, out=None):
         """bprx_audience_block: fp32 [q1 - q0, U], the scores of the catalogue items q0 .. q1-1 (P = project_rows(F): of rows

@@ -19,7 +19,8 @@ from time import time
 import numpy as np
 
 from .ranking import (blocks, lists_to_csr, rank_rows, rank_rows_host, write_because, write_capped, write_diverse, write_feature_rows,
-                      write_item_lists, write_ranked, write_shelves)
+                      write_item_lists, write_ranked, write_shelves, style_file, user_style_rows, write_style_items, write_styles,
+                      write_user_styles)
 
 
 def _eval_block(scores, u0, train, evl, K):
@@ -250,6 +251,27 @@ class Evaluator:
         ids, vals, cls = self.model.recommend_capped(None, None, cap)
         with open(path, 'w') as out:
             write_capped(out, range(ids.shape[0]), ids, vals, cls)
+
+    def store_styles(self, path="", style=None, cos=None, top=None):
+        """BPRMF / VBPR / GradFashion: the style files next to the recs-* / best-recs-* file at `path` for the assignment (style int
+        [I], cos fp32 [I]) of model.item_styles (None: clustered now with the run's --styles / --style_iters / --similar_space):
+        styles-* (rows 'i\tstyle\tcosine', every item in id order, -1 for a zero row), style-items-* (rows 'style\tsize\trank\ti\t
+        cosine': every style's `top`, None = --style_top, members nearest its centroid, best first, equal cosines by ascending
+        item; model.style_members) and user-styles-* (rows 'u\tstyle\towned\tshare': the styles of every user's training list by
+        descending count, then ascending style; share = owned / list length), formatted as store_recommendation formats."""
+        if style is None:
+            style, cos = self.model.item_styles()[:2]
+        with open(style_file(path, "styles"), 'w') as out:
+            write_styles(out, style, cos)
+        with open(style_file(path, "style-items"), 'w') as out:
+            write_style_items(out, *self.model.style_members(style, cos, top))
+        with open(style_file(path, "user-styles"), 'w') as out:
+            write_user_styles(out, range(self.data.num_users), user_style_rows(self.data.training_list, style))
+
+    def store_styles_new(self, path="", style=None, cos=None):
+        """VBPR / GradFashion: new-styles-*, rows 'j_new\tstyle\tcosine' for the rows of the --new_items table (model.styles_of_new)."""
+        with open(path, 'w') as out:
+            write_styles(out, style, cos)
 
     def store_recommendation_because(self, path="", top=5, space=None):
         """BPRMF / VBPR / GradFashion: for every (u, i) of every user's top-k list (the lists store_recommendation writes, ranked

@@ -20,8 +20,8 @@ from . import configs
 from .engine import Engine, as_index
 from .evaluator import Evaluator
 from .ranking import (because_paths, because_rows, blocks, cap_rows, class_csr, class_rows_per_block, diverse_zeros, diversify_rows,
-                      div_paths, item_file, owners_of, rank_class_rows, rank_rows, ranked_zeros, run_file, shelf_file, wanted_blocks,
-                      warm_file, write_because, write_capped, write_diverse, write_ranked, write_shelves)
+                      div_paths, item_file, owners_of, rank_class_rows, rank_rows, ranked_zeros, run_file, shelf_file, style_file,
+                      wanted_blocks, warm_file, write_because, write_capped, write_diverse, write_ranked, write_shelves)
 from .synth import glorot_uniform
 
 
@@ -180,6 +180,9 @@ class BPRMF(RecommenderModel):
         self.shelves_k = int(getattr(params, "shelves", 0) or 0)                   # entries per class in shelf-*; 0: none
         self.shelf_count = int(getattr(params, "shelf_count", 0) or 0)             # shelves per user in shelf-*; 0: all
         self.class_cap = int(getattr(params, "class_cap", 0) or 0)                 # items per class in cap-*; 0: none
+        self.styles_S = int(getattr(params, "styles", 0) or 0)                     # clusters of the styles-* files; 0: none
+        self.style_iters = int(getattr(params, "style_iters", 20) or 20)           # Lloyd iterations at the most
+        self.style_top = int(getattr(params, "style_top", 10) or 10)               # members per style in style-items-*
         # hard negatives (--hard_negatives C): every negative is the best-scored of C sampled candidates; 0: the uniform draw
         self.hard_negatives = int(getattr(params, "hard_negatives", 0) or 0)
         self.hard_refresh = int(getattr(params, "hard_refresh", 0) or 0)           # steps between snapshots inside an epoch; 0: none
@@ -392,14 +395,19 @@ class BPRMF(RecommenderModel):
         """Every file of ranking.RUN_FILES the run's flags ask for, next to (and with) the recs-* / best-recs-* file at `path`, from
         the tables the model holds now.  ValueError for a path that is neither."""
         run_file(path, "recs")
-        self._store_recs(path)
-        self._store_new_user_recs(path)
-        self._store_similar(path)
-        self._store_diverse(path)
-        self._store_because(path)
-        self._store_audience(path)
-        self._store_warm(path)
-        self._store_shelves(path)
+        self._styles_open, self._styles_now = True, None         # one style table per store call, from the tables held now
+        try:
+            self._store_recs(path)
+            self._store_new_user_recs(path)
+            self._store_similar(path)
+            self._store_diverse(path)
+            self._store_because(path)
+            self._store_audience(path)
+            self._store_warm(path)
+            self._store_styles(path)
+            self._store_shelves(path)
+        finally:
+            self._styles_open, self._styles_now = False, None
 
     def _store_recs(self, path):
         """What train() leaves at the recs-* / best-recs-* paths: the top-K lists (BPRMF.py:167-187)."""
@@ -536,6 +544,8 @@ class BPRMF(RecommenderModel):
             src = getattr(self.params, "item_classes", None)
             if src is None:
                 raise ValueError("%s: no class table (params.item_classes, --item_classes)" % type(self).__name__)
+            if isinstance(src, str) and src == "styles":         # never cached: the best model's styles are not the last epoch's
+                return self._run_styles()[0]
             if isinstance(src, str):
                 from .train_rec import dataset_item_classes, read_item_classes
                 src = dataset_item_classes(self.params.dataset, self.num_items) if src == "dataset" \
@@ -547,6 +557,8 @@ class BPRMF(RecommenderModel):
         """ranking.class_csr of `classes` (an int array [num_items], -1 = no class); None: of the run's table, made once."""
         if classes is not None:
             return class_csr(np.asarray(classes), self.num_items, self.engine.device)
+        if isinstance(getattr(self.params, "item_classes", None), str) and self.params.item_classes == "styles":
+            return class_csr(self.item_classes(), self.num_items, self.engine.device, classes=self.styles_S or None)
         if getattr(self, "_class_csr_dev", None) is None:
             self._class_csr_dev = class_csr(self.item_classes(), self.num_items, self.engine.device)
         return self._class_csr_dev
@@ -616,6 +628,118 @@ class BPRMF(RecommenderModel):
             self.evaluator.store_recommendation_shelves(shelf_file(path, "shelf-recs"), self.shelves_k, self.shelf_count)
         if self.class_cap > 0:
             self.evaluator.store_recommendation_capped(shelf_file(path, "cap-recs"), self.class_cap)
+
+    # ---- style clusters: spherical k-means of the item space (include/bprx.h, bprx_style_assign / bprx_style_update) -------------
+    STYLE_BLOCK = 1 << 16                                        # catalogue rows per bprx_style_assign call
+
+    def _style_args(self, S, space):
+        """(S, space) of a clustering, checked: S (None: params.styles) in [1, 1024], space (None: similar_items' own)."""
+        if not self.diverse:
+            raise NotImplementedError("%s has no item space: styles come from BPRMF, VBPR and GradFashion" % type(self).__name__)
+        S = self.styles_S if S is None else int(S)
+        if not 1 <= S <= 1024:
+            raise ValueError("styles: S lies in [1, 1024] (got %d)" % S)
+        return S, self.similar_space if space is None else space
+
+    def _style_assign_all(self, space, cent, rn):
+        """(style int32 [I], cos fp32 [I]) device tensors: Engine.style_assign over the whole catalogue, block by block."""
+        I = self.num_items
+        parts = [self.engine.style_assign(space, cent, b0, min(b0 + self.STYLE_BLOCK, I), rn, want_second=False)
+                 for b0 in range(0, I, self.STYLE_BLOCK)]
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+    def _seed_centroids(self, space, rn, seeds):
+        """fp32 [S, w] on the device: the unit rows of the items `seeds`, each made by Engine.style_update as the centroid of the
+        cluster that holds that one item (so a seed's row is what a one-member cluster gets in the loop)."""
+        eng, seeds = self.engine, np.asarray(seeds, dtype=np.int64).reshape(-1)
+        if seeds.size and (seeds.min() < 0 or seeds.max() >= self.num_items):
+            raise ValueError("styles: seed ids lie in [0, %d)" % self.num_items)
+        S = int(seeds.size)
+        csr = (torch.arange(S + 1, dtype=torch.int64, device=eng.device), torch.as_tensor(seeds.astype(np.int32), device=eng.device), S)
+        zeros = torch.zeros((S, eng._style_width(space)), dtype=torch.float32, device=eng.device)
+        return eng.style_update(space, rn, csr, zeros)[0]
+
+    def style_seeds(self, S, space=None):
+        """S deterministic farthest-first seeds, an int64 array of item ids: the first is the smallest id with a non-zero norm, each
+        next one the item with a non-zero norm whose largest cosine to the seeds so far is smallest, equal values by the smallest
+        id (a seed is not taken twice).  One S = 1 Engine.style_assign per round: S I w multiply-adds in all.  ValueError for fewer
+        than S items with a non-zero norm."""
+        S, space = self._style_args(S, space)
+        eng, I = self.engine, self.num_items
+        rn = eng.sim_rnorm(space)
+        live = rn > 0
+        if int(live.sum()) < S:
+            raise ValueError("style_seeds: %d items with a non-zero norm, %d seeds asked" % (int(live.sum()), S))
+        inf = torch.full((I,), float("inf"), dtype=torch.float32, device=eng.device)
+        far = torch.where(live, torch.full_like(inf, -float("inf")), inf)       # the largest cosine to a seed; +inf: not a candidate
+        seeds = [int(torch.nonzero(live)[0])]
+        while len(seeds) < S:
+            far[seeds[-1]] = float("inf")
+            _, cos, _ = eng.style_assign(space, self._seed_centroids(space, rn, seeds[-1:]), 0, I, rn, want_second=False)
+            far = torch.maximum(far, cos)                        # (+inf stays +inf)
+            seeds.append(int(torch.nonzero(far == far.min())[0]))               # the smallest id among the equal minima
+        return np.asarray(seeds, dtype=np.int64)
+
+    def item_styles(self, S=None, iters=None, space=None, seeds=None):
+        """Spherical k-means of the catalogue in `space` (None: similar_items' own) with S (None: params.styles) clusters: Lloyd's
+        loop from the unit rows of `seeds` (None: style_seeds(S, space)).  The catalogue is assigned once; then every iteration
+        builds ranking.class_csr of the assignment, runs Engine.style_update and assigns the whole catalogue again in blocks,
+        until no assignment changes or `iters` (None: params.style_iters, 20) iterations have run.  Returns numpy arrays: style
+        int64 [I] (-1 for a zero row), cos fp32 [I] (to the item's centroid), cent fp32 [S, w] and objective float64 [iterations
+        run], objective[t] = sum_s mass[s] / (items with a style) after iteration t's update: it never decreases.  style and
+        cos are those of the returned centroids."""
+        S, space = self._style_args(S, space)
+        iters = self.style_iters if iters is None else int(iters)
+        if iters < 0:
+            raise ValueError("styles: iters >= 0 (got %d)" % iters)
+        eng, I = self.engine, self.num_items
+        seeds = self.style_seeds(S, space) if seeds is None else np.asarray(seeds, dtype=np.int64).reshape(-1)
+        if seeds.size != S:
+            raise ValueError("styles: %d seeds for %d styles" % (seeds.size, S))
+        rn = eng.sim_rnorm(space)
+        cent = self._seed_centroids(space, rn, seeds)
+        style, cos = self._style_assign_all(space, cent, rn)
+        objective = []
+        for _ in range(iters):
+            st = style.cpu().numpy()
+            cent, mass = eng.style_update(space, rn, class_csr(st, I, eng.device, classes=S), cent)
+            objective.append(float(mass.double().sum()) / max(1, int((st >= 0).sum())))
+            new_style, cos = self._style_assign_all(space, cent, rn)
+            same = bool(torch.equal(new_style, style))
+            style = new_style
+            if same:
+                break
+        eng.sync_check()
+        return style.cpu().numpy().astype(np.int64), cos.cpu().numpy(), cent.cpu().numpy(), np.asarray(objective, dtype=np.float64)
+
+    def _run_styles(self):
+        """(style, cos, cent, objective) of the run's flags from the tables the model holds now; inside a store call (see
+        _store_run_files) computed once and shared by every file of the call."""
+        if getattr(self, "_styles_now", None) is not None:
+            return self._styles_now
+        res = self.item_styles()
+        if getattr(self, "_styles_open", False):
+            self._styles_now = res
+        return res
+
+    def style_members(self, style, cos, top=None, S=None):
+        """Every style's `top` (None: params.style_top) members nearest its centroid: (sizes int64 [S], ids int64 [S, R], vals fp32
+        [S, R], cnt int64 [S]), R = min(top, I), best first, equal cosines by ascending item, -1 / 0.0 past cnt: Engine.topk_classes
+        over the one-row score block `cos` with the styles as the classes (S: their number, None: params.styles)."""
+        top = self.style_top if top is None else int(top)
+        self._class_args(top, None)
+        S, eng = int(S) if S is not None else (self.styles_S or max(1, int(np.max(style)) + 1)), self.engine
+        ccsr = class_csr(np.asarray(style), self.num_items, eng.device, classes=S)
+        row = torch.as_tensor(np.ascontiguousarray(cos, dtype=np.float32), device=eng.device).reshape(1, -1)
+        ids, vals, cnt = rank_class_rows(lambda sc, kq: eng.topk_classes(sc, None, ccsr, kq), row, top)
+        return np.bincount(np.asarray(style)[np.asarray(style) >= 0], minlength=S).astype(np.int64), ids[0], vals[0], cnt[0]
+
+    def _store_styles(self, path):
+        """params.styles = S > 0: styles-*, style-items-* and user-styles-* next to the recs-* file at `path`."""
+        if self.styles_S <= 0:
+            return
+        style, cos = self._run_styles()[:2]
+        self.evaluator.store_styles(path, style, cos)
 
     # ---- similar items: the cosine of two items in the model's item space (include/bprx.h, bprx_sim_*) -------------------------
     sim_space = "latent"                                         # the space similar_items walks by default
@@ -1062,6 +1186,32 @@ class VBPR(BPRMF):
         for b0, b1 in blocks(n, self.evaluator.user_block, I):
             ids[b0:b1], vals[b0:b1], _ = rank_rows(eng.topk_rows, eng.sim_block("visual", b0, b1, rn, P, rq), k)
         return ids, vals
+
+    def styles_of_new(self, features, cent):
+        """The style of every row of `features` (raw rows of items outside the catalogue, or a table from prepare_new_items) among
+        the centroids `cent` (fp32 [S, d], of item_styles in the visual space): numpy style int64 [n] (-1 for a zero projection)
+        and cos fp32 [n].  Engine.project_rows puts the rows on the catalogue's scale, Engine.style_assign's Pq form assigns."""
+        eng = self.engine
+        P = eng.project_rows(self._as_new_table(features))
+        n = int(P.shape[0])
+        if n == 0:
+            return np.zeros(0, np.int64), np.zeros(0, np.float32)
+        rq = eng.sim_rnorm("visual", P)
+        ct = torch.as_tensor(np.ascontiguousarray(cent, dtype=np.float32), device=eng.device)
+        style, cos, _ = eng.style_assign("visual", ct, 0, n, rq, P, rq, want_second=False)
+        return style.cpu().numpy().astype(np.int64), cos.cpu().numpy()
+
+    def _store_styles(self, path):
+        """styles-* as every model writes them; with params.new_items also new-styles-*, rows 'j_new\tstyle\tcosine' (the visual
+        space)."""
+        super()._store_styles(path)
+        feats = self._load_new_items() if self.styles_S > 0 else None
+        if feats is None:
+            return
+        if self.similar_space != "visual":
+            raise ValueError("new-styles-* needs the visual space (similar_space = %r)" % self.similar_space)
+        style, cos = self.styles_of_new(feats, self._run_styles()[2])
+        self.evaluator.store_styles_new(style_file(path, "new-styles"), style, cos)
 
     def audience_new(self, features, k=None):
         """BPRMF.audience for items outside the catalogue: the k (default: params.audience, else top_k) users with the highest

@@ -125,11 +125,12 @@ def diversify_rows(diversify, ids, vals, k, device):
 
 
 # ---- category shelves and quota lists: the per-class lists of bprx_topk_classes ------------------------------------------------
-def class_csr(item_class, num_items, device):
+def class_csr(item_class, num_items, device, classes=None):
     """The class table of a catalogue as bprx_topk_classes takes it: item_class is an int array [num_items], the class of every
     item, -1 = no class (the item is on no list) -> (int64 ptr [C + 1], int32 items, C) with ptr / items tensors on `device`, C =
     the largest class id + 1 (at least 1; a class id nobody has is an empty class), the items of a class ascending.  `items` is
-    never empty (one zero when every item is classless: a kernel is handed a pointer it does not read)."""
+    never empty (one zero when every item is classless: a kernel is handed a pointer it does not read).  classes = S: exactly S
+    classes (the clusters of bprx_style_update, whose last ones may be empty); a class id >= S is a ValueError."""
     cls = np.asarray(item_class).reshape(-1)
     if cls.size != num_items or cls.dtype.kind not in "iu":
         raise ValueError("class_csr: one integer class per item, [%d] (got %s %s)" % (num_items, cls.dtype, cls.shape))
@@ -137,6 +138,10 @@ def class_csr(item_class, num_items, device):
     if cls.size and cls.min() < -1:
         raise ValueError("class_csr: a class id is >= 0, or -1 for no class (got %d)" % cls.min())
     C = max(1, int(cls.max()) + 1 if cls.size else 1)
+    if classes is not None:
+        if C > int(classes):
+            raise ValueError("class_csr: class id %d with %d classes" % (C - 1, int(classes)))
+        C = int(classes)
     have = np.flatnonzero(cls >= 0)
     items = have[np.argsort(cls[have], kind="stable")].astype(np.int32)            # by class, ascending item inside a class
     ptr = np.zeros(C + 1, np.int64)
@@ -370,6 +375,63 @@ def shelf_file(path, kind):
     if kind not in SHELF_FILES:
         raise ValueError("shelf_file: %r is none of %s" % (kind, ", ".join(SHELF_FILES)))
     return head + kind + tail
+
+
+# The files of a run about the STYLES of the item space (--styles: spherical k-means, models.item_styles): styles-* has one row per
+# catalogue item (rows 'item style cosine'), style-items-* every style's members nearest its centroid (rows 'style size rank item
+# cosine'), user-styles-* every user's style profile (rows 'user style owned share'), new-styles-* the style of every new item
+# (rows 'row style cosine'), named like the files above.
+STYLE_FILES = {"styles": None, "style-items": None, "user-styles": None, "new-styles": None}
+
+
+def style_file(path, kind):
+    """run_file for the kinds of STYLE_FILES: the file of `kind` next to the recs-* / best-recs-* file at `path`, 'best-' stays in
+    front; ValueError for a path whose file name starts with neither, and for a kind that is none of STYLE_FILES."""
+    head, base, tail = _split_run_file(path)
+    if base != "recs":
+        raise ValueError("%r is neither a recs-* nor a best-recs-* path" % path)
+    if kind not in STYLE_FILES:
+        raise ValueError("style_file: %r is none of %s" % (kind, ", ".join(STYLE_FILES)))
+    return head + kind + tail
+
+
+def write_styles(out, style, cos):
+    """One row 'item\tstyle\tcosine' per row of `style` (int) / `cos` (fp32), in order; a zero row has style -1.  Fields are
+    formatted as write_ranked formats them."""
+    for i in range(len(style)):
+        out.write(str(i) + '\t' + str(style[i]) + '\t' + str(cos[i]) + '\n')
+
+
+def write_style_items(out, sizes, ids, vals, cnt):
+    """One row 'style\tsize\trank\titem\tcosine' per entry of every style's list, style by style, rank 0 first: ids [S, R] /
+    vals [S, R] / cnt [S] are the one score row's lists of rank_class_rows (best first, equal cosines by ascending item), sizes
+    [S] the styles' member counts.  An empty style has no rows."""
+    for s in range(len(sizes)):
+        head = str(s) + '\t' + str(sizes[s]) + '\t'
+        for q in range(int(cnt[s])):
+            out.write(head + str(q) + '\t' + str(ids[s, q]) + '\t' + str(vals[s, q]) + '\n')
+
+
+def user_style_rows(lists, style):
+    """The style profile of every list of item ids: per list the (style, owned) pairs of the styles its items have, by descending
+    count, equal counts by ascending style, and the list's length (repeats and items without a style count towards the length;
+    items without a style are in no pair).  style: int array [num_items], -1 = none."""
+    style = np.asarray(style, dtype=np.int64)
+    out = []
+    for l in lists:
+        own = style[np.asarray(l, dtype=np.int64)] if len(l) else np.zeros(0, np.int64)
+        st, n = np.unique(own[own >= 0], return_counts=True)
+        o = np.lexsort((st, -n))
+        out.append((st[o], n[o], len(l)))
+    return out
+
+
+def write_user_styles(out, labels, rows):
+    """One row 'label\tstyle\towned\tshare' per pair of user_style_rows, label by label; share = owned / list length as float32."""
+    for label, (st, n, total) in zip(labels, rows):
+        head = str(label) + '\t'
+        for s, c in zip(st, n):
+            out.write(head + str(s) + '\t' + str(c) + '\t' + str(np.float32(c) / np.float32(total)) + '\n')
 
 
 def _about(path, family, what):

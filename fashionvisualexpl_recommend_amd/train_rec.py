@@ -23,6 +23,9 @@ audience-* for the catalogue, each row with its three attentions.
 --item_classes PATH with --shelves K / --class_cap M (bprmf, vbpr, grad_fashion) writes shelf-recs-* (every user's K best items of
 every item class, the classes in the user's order) and cap-recs-* (the top_k with at most M items of any class) next to recs-*, and
 with --new_users shelf-new-user-recs-* / cap-new-user-recs-*.
+--styles S [--style_iters T] [--style_top R] (bprmf, vbpr, grad_fashion) clusters the item space of --similar_space into S styles
+(spherical k-means) and writes styles-*, style-items-* and user-styles-* next to recs-*, with --new_items also new-styles-*;
+--item_classes styles makes the styles the classes of --shelves / --class_cap.
 --warm_items PATH (bprmf, vbpr, grad_fashion) fits Gi / Bi rows for new items from their first buyers (rows `row<TAB>user`; vbpr and
 grad_fashion: rows of the --new_items table) and writes warm-recs-* / best-warm-recs-* files, with --audience K also warm-audience-*.
 Run as `python -m fashionvisualexpl_recommend_amd.train_rec --rec bprmf --dataset <name> ...`.
@@ -143,7 +146,8 @@ def parse_args(argv=None):
     parser.add_argument('--item_classes', default=None, metavar='PATH',
                         help="bprmf, vbpr, grad_fashion: the class (category) of every catalogue item, a TSV of `item<TAB>class` rows "
                              "with non-negative integer class ids, every item exactly once; or the literal `dataset`: the argmax of "
-                             "every item's original/features/one_hot_encodings/{i}.npy.  Read by --shelves and --class_cap")
+                             "every item's original/features/one_hot_encodings/{i}.npy.  Read by --shelves and --class_cap; "
+                             "or the literal `styles`: the clusters of --styles, made from the model that writes the files")
     parser.add_argument('--shelves', type=int, default=0, metavar='K',
                         help="bprmf, vbpr, grad_fashion: also write shelf-recs-* / best-shelf-recs-* files next to recs-* / "
                              "best-recs-*: every user's K (1..1024) best items of every class of --item_classes, training items "
@@ -155,6 +159,17 @@ def parse_args(argv=None):
                         help="bprmf, vbpr, grad_fashion: also write cap-recs-* / best-cap-recs-* files next to recs-* / best-recs-*: "
                              "every user's top_k with at most M items of any one class of --item_classes, rows `u i score class`, "
                              "best first; with --new_users also cap-new-user-recs-*; 0 = off")
+    parser.add_argument('--styles', type=int, default=0, metavar='S',
+                        help="bprmf, vbpr, grad_fashion: cluster the item space of --similar_space into S (2..1024) styles by "
+                             "spherical k-means and write styles-* (rows `i style cosine`, every item, -1 for a zero row), "
+                             "style-items-* (rows `style size rank i cosine`, every style's --style_top members nearest its "
+                             "centroid) and user-styles-* (rows `u style owned share`, the styles of every user's training list) "
+                             "next to recs-* / best-recs-*; with --new_items also new-styles-* (rows `j_new style cosine`, visual "
+                             "space); `--item_classes styles` makes the styles the classes of --shelves / --class_cap; 0 = off")
+    parser.add_argument('--style_iters', type=int, default=20, metavar='T',
+                        help="--styles: Lloyd iterations at the most (the loop stops when no item changes its style)")
+    parser.add_argument('--style_top', type=int, default=10, metavar='R',
+                        help="--styles: members per style in style-items-* (1..1024)")
     parser.add_argument('--af_new_items', nargs=3, default=None, metavar=('EDGES.npy', 'COLOUR.npy', 'CLASSES.npy'),
                         help="attentive_fashion: the inputs of n items the model was not trained on: edge images uint8 [n, 224, 224], "
                              "raw colour histograms [n, Dc] (each divided by its own max-abs, as the catalogue's are; an all-zero "
@@ -271,17 +286,30 @@ def parse_args(argv=None):
         parser.error("--diversify_pool takes top_k (%d) .. 1024 (got %s)" % (args.top_k, args.diversify_pool))
     if not 0 <= args.because <= 32:
         parser.error("--because takes 0 (off) .. 32 (got %s)" % args.because)
-    asked = args.similar_items != 0 or args.similar_space is not None or args.diversify > 0 or args.because != 0
+    if args.styles != 0 and not 2 <= args.styles <= 1024:
+        parser.error("--styles takes 0 (off) or 2 .. 1024 (got %s)" % args.styles)
+    if args.style_iters < 1:
+        parser.error("--style_iters takes T >= 1 (got %s)" % args.style_iters)
+    if not 1 <= args.style_top <= 1024:
+        parser.error("--style_top takes 1 .. 1024 (got %s)" % args.style_top)
+    if args.styles == 0 and (args.style_iters != 20 or args.style_top != 10):
+        parser.error("--style_iters / --style_top need --styles S")
+    if args.item_classes == 'styles' and args.styles == 0:
+        parser.error("--item_classes styles needs --styles S")
+    asked = args.similar_items != 0 or args.similar_space is not None or args.diversify > 0 or args.because != 0 or args.styles != 0
     if args.similar_space is None:                            # the model's own space
         args.similar_space = {'bprmf': 'latent', 'vbpr': 'visual', 'grad_fashion': 'visual'}.get(args.rec)
     if asked:
         if args.rec not in ('bprmf', 'vbpr', 'grad_fashion'):
-            parser.error("--similar_items / --similar_space / --diversify / --because need --rec bprmf, vbpr or grad_fashion (got "
-                         "--rec %s)" % args.rec)
+            parser.error("--similar_items / --similar_space / --diversify / --because / --styles need --rec bprmf, vbpr or "
+                         "grad_fashion (got --rec %s)" % args.rec)
         if args.similar_space != 'latent' and args.rec == 'bprmf':
             parser.error("--similar_space %s needs --rec vbpr or grad_fashion (bprmf has the latent space only)" % args.similar_space)
         if args.similar_space != 'latent' and args.dtype == 'fp8':
             parser.error("--similar_space %s runs with --dtype fp32 or bf16 (got fp8): use --similar_space latent" % args.similar_space)
+    if args.styles != 0 and args.new_items is not None and args.similar_space != 'visual':
+        parser.error("--styles with --new_items writes new-styles-* in the visual space: --similar_space %s does not go with "
+                     "--new_items here" % args.similar_space)
     if not 0 <= args.audience <= 1024:
         parser.error("--audience takes 0 (off) .. 1024 (got %s)" % args.audience)
     if args.audience != 0 and args.rec not in ('bprmf', 'vbpr', 'grad_fashion'):
@@ -306,7 +334,7 @@ def parse_args(argv=None):
             parser.error("--item_classes / --shelves / --class_cap need --rec bprmf, vbpr or grad_fashion (got --rec %s)" % args.rec)
         if args.item_classes is None:
             parser.error("--shelves / --class_cap need --item_classes PATH (or --item_classes dataset)")
-        if args.item_classes != 'dataset':
+        if args.item_classes not in ('dataset', 'styles'):
             try:
                 read_item_classes(args.item_classes)
             except (OSError, ValueError) as e:
@@ -412,7 +440,7 @@ def check_item_classes(args, num_items):
     class vector of the dataset) ends the run as a rejected argument does.  Returns the table, int64 [num_items] (None without the
     flag; an array that is there already is returned as it is), so that it is read once per run."""
     src = getattr(args, "item_classes", None)
-    if src is None or not isinstance(src, str):
+    if src is None or not isinstance(src, str) or src == 'styles':     # (the styles are made by the model that stores)
         return src
     try:
         return dataset_item_classes(args.dataset, num_items) if src == 'dataset' else read_item_classes(src, num_items)
@@ -519,6 +547,8 @@ def train(argv=None):
     if (args.shelves != 0 or args.class_cap != 0) and int(args.world_size) > 1:
         raise NotImplementedError('--shelves / --class_cap run on one GPU (the sharded drivers write no shelf-* / cap-* files): use '
                                   '--world_size 1')
+    if args.styles != 0 and int(args.world_size) > 1:
+        raise NotImplementedError('--styles runs on one GPU (the sharded drivers write no styles-* files): use --world_size 1')
     if args.class_cap != 0 and min(args.class_cap, args.top_k) > 1024:
         raise ValueError('--class_cap ranks on the device only (min(class_cap, top_k) <= 1024): there is no host form')
     if args.warm_items is not None and args.new_items is not None:                  # a row past the table: before anything is trained

@@ -160,7 +160,7 @@ BPRX_API int bprx_sync_adam(bprx_handle *h, void *stream);
      bprx_project_rows, bprx_score_new_block, bprx_feat_explain_new   VBPR, not fp8       yes           yes   yes    -
      bprx_feat_explain                                                VBPR                yes           yes   -      -
      bprx_explain_pairs                                               GradFashion         yes           yes   -      -
-     bprx_sim_*, bprx_diversify, bprx_because                         BPRMF / VBPR        yes           yes   via P  VISUAL / BOTH
+     bprx_sim_*, bprx_style_*, bprx_diversify, bprx_because           BPRMF / VBPR        yes           yes   via P  VISUAL / BOTH
      bprx_sync_adam                                                   any                 yes           yes   -      -
      bprx_topk_rows                                                   VBPR, not fp8       yes           -     -      -
      bprx_apply_user_msgs                                             any                 yes           -     -      -
@@ -398,6 +398,47 @@ BPRX_API int bprx_topk_rows_masked(bprx_handle *h, int64_t nrows, int32_t width,
 BPRX_API int bprx_topk_classes(bprx_handle *h, int64_t nrows, int32_t width, float *scores, int64_t row0, const int64_t *list_ptr,
                                const int32_t *list_items, const int64_t *class_ptr, const int32_t *class_items, int32_t C,
                                int32_t K, int32_t *idx, float *val, int32_t *cnt, void *stream);
+
+/* ---- BPRMF, VBPR and GradFashion: style clusters, spherical k-means of the item space -----------------------------------------
+   "Which styles has the model found, which style is this dress": Lloyd's loop over the unit vectors z_i rn_i of bprx_sim_* (space,
+   z_i, rn_i and the handle rules are those of bprx_sim_block) is these two calls in turn; the caller keeps the S centroids, fp32
+   [S, w] row-major on the device, w = k (LATENT), d (VISUAL) or k + d (BOTH, the Gi part before the P part), 1 <= S <= 1024.
+   bprx_style_assign, for the query rows q in [q0, q1) and centroid rows that are unit vectors or zero rows:
+       c(q, s)         = <z_q, cent_s> rn_q     the fp32 MFMA GEMM of bprx_sim_block (exact fp32 products, sums in x order from
+                                                +0, Gi before P) against the centroids; the norm is multiplied last
+       style[q - q0]   = the s with the largest c(q, s), int32; cos[q - q0] = that maximum
+       second[q - q0]  = the largest c(q, s) over s != style, -inf for S == 1 (second may be NULL: style and cos keep their bits)
+   Ties go to the smallest s: (value, index) pairs are compared, inside a wave's reduction and across centroid tiles alike.  A
+   query with rn_q == 0 gets style -1, cos 0.0, second 0.0; a zero centroid scores 0.0 against everything; NaN is outside the
+   contract.  One workgroup owns 128 query rows and walks the centroids in tiles of 128 with the running result in registers:
+   nothing of size rows x S is written.  A row's three outputs depend on that row, its norm and the centroid table only: not on
+   q0, q1, nq, the tile the row lands in, or where a centroid sits inside its tile.  Pq == NULL: the catalogue, nq == num_items,
+   rn_q indexed by item id; Pq != NULL: rows of bprx_project_rows' output, rn_q their norms, VISUAL only (as bprx_sim_block).
+   bprx_style_update, for the clusters given as a CSR (member_ptr int64 [S + 1], member_items int32, ascending within a cluster,
+   device: the layout of a class table), with rn_items = bprx_sim_rnorm of the catalogue:
+       sum_s      = sum over i in members(s) of fl32(z_ix rn_i)     accumulated in fp64
+       cent_out_s = sum_s / |sum_s|, mass[s] = |sum_s|              formed in fp64, each rounded once to fp32; 0 <= mass[s] <= size
+   The fp64 order is fixed by the cluster's own member list: the list is cut at multiples of 16, a piece is added up in list order
+   from +0, and the pieces are added to the sum in ascending order; |sum|^2 adds the squares of the columns l, l + 64, .. in
+   ascending order for l < 64 and folds the 64 sums in an xor tree.  No float atomics.  An empty cluster, or one whose |sum|^2 is
+   exactly 0 in fp64 (a row and its negation), copies cent_prev_s and reports mass 0 (cent_out may be cent_prev).  A member id
+   outside [0, num_items) is skipped and reported by bprx_sync_check (BPRX_E_RANGE); it is never dereferenced.  The bits of
+   cluster s depend on its member list and those members' rows and norms only: not on S, the other clusters, its number or the
+   launch; two calls give equal bits.  The objective of a run is sum_s mass[s] / (number of assigned items).
+   Errors: BPRX_E_INVALID for a NULL handle or pointer (second excepted), S outside [1, 1024], an unknown space, an ACF or
+   AttentiveFashion handle, a BPRMF handle in VISUAL / BOTH, an fp8 handle in VISUAL / BOTH, a bad range, Pq != NULL with another
+   space than VISUAL, Pq == NULL with nq != num_items, bprx_style_update in a space wider than 4096 numbers; BPRX_E_STATE for
+   unbound tables; q0 == q1: BPRX_OK, nothing is written.  After any error the handle stays usable.  State: like bprx_sim_block
+   both calls first settle a pending dense update, bring lazy adam_tf23 rows up to date and (VISUAL / BOTH) make P current; apart
+   from that they write their outputs only and allocate nothing: a training run with these calls between its steps ends
+   bit-identical to one without. */
+#define BPRX_STYLES_MAX 1024
+BPRX_API int bprx_style_assign(bprx_handle *h, int32_t space, const float *Pq, int64_t nq, int64_t q0, int64_t q1, const float *rn_q,
+                               const float *cent, int32_t S, int32_t *style, float *cos, float *second /* may be NULL */,
+                               void *stream);
+BPRX_API int bprx_style_update(bprx_handle *h, int32_t space, const float *rn_items, const int64_t *member_ptr,
+                               const int32_t *member_items, int32_t S, const float *cent_prev, float *cent_out, float *mass,
+                               void *stream);
 
 /* ---- BPRMF, VBPR and GradFashion: warm items, new items with first buyers --------------------------------------------------
    The twin of bprx_fold_in on the item side.  An item outside the catalogue is scored by its picture alone
