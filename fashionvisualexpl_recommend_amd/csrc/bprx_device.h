@@ -1,5 +1,5 @@
 // bprx_device.h -- device functions every kernel file of libbprx.so may use (included by bprx_internal.h): the wave and
-// workgroup reductions, the index clamps, bf16 rounding, Philox, and the ONE definition of each optimizer rule.
+// workgroup reductions, the index clamps, the item side of a user's pairs (fold_row), bf16 rounding, Philox, and the ONE definition of each optimizer rule.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -67,6 +67,21 @@ __device__ __forceinline__ int clamp_index(int v, int n, int32_t *errflag, int c
 }
 // the same value without the flag: for kernels that run after one that has already raised it
 __device__ __forceinline__ int clamp_quiet(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
+
+// ---- the item side of a fitted user row (bprx_fold_in, bprx_influence) -------------------------------------------------------
+// elements lane, lane + 64, ... of z_it = [Gi_it | P_it[0:d]] (zero past k + d) and c_it = Bi_it + P_it[d] (BPRMF: Bi_it).  a: any
+// argument struct with Gi [I, k], Bi [I], P [I, PS] (unread when d == 0), k, d, PS.
+template <int EPL, class Args>
+__device__ __forceinline__ void fold_row(const Args &a, int it, int lane, float (&z)[EPL], float &c) {
+  const float *g = a.Gi + (size_t)it * a.k;
+  const size_t pb = (size_t)it * a.PS;
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) {
+    const int col = lane + 64 * e;
+    z[e] = col < a.k ? g[col] : (col < a.k + a.d ? a.P[pb + (col - a.k)] : 0.f);
+  }
+  c = a.d ? a.Bi[it] + a.P[pb + a.d] : a.Bi[it];
+}
 
 // bf16 code of x, round-to-nearest-even; x is finite
 __device__ __forceinline__ uint32_t bf16_rne(float x) {

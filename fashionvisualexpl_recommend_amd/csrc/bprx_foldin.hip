@@ -97,19 +97,6 @@ struct RowPlace {
   }
 };
 
-// elements lane, lane + 64, ... of z_it = [Gi_it | P_it[0:d]] (zero past k + d) and c_it
-template <int EPL>
-__device__ __forceinline__ void fold_row(const FoldArgs &a, int it, int lane, float (&z)[EPL], float &c) {
-  const float *g = a.Gi + (size_t)it * a.k;
-  const size_t pb = (size_t)it * a.PS;
-#pragma unroll
-  for (int e = 0; e < EPL; ++e) {
-    const int col = lane + 64 * e;
-    z[e] = col < a.k ? g[col] : (col < a.k + a.d ? a.P[pb + (col - a.k)] : 0.f);
-  }
-  c = a.d ? a.Bi[it] + a.P[pb + a.d] : a.Bi[it];
-}
-
 // D_p (elements lane, lane + 64, ... of s [Gu_u | 1], zero past k + 1) and dc_p = s v_p of one pair of an item; pn: the item's row
 // of Pn.  dc_p costs a (k + d)-wide dot over four gathered rows (Gu_u, Gi_o, Tu_u, P_o) and Pn_r: the k part is formed from the
 // registers that hold a_p, the d part in a strided loop (Pn_r: one row per wave, L1-resident).  Contraction off: the same

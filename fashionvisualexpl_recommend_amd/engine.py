@@ -924,6 +924,43 @@ class Engine:
                                                  _stream()))
         return item, cos, cnt
 
+    def influence(self, Gu_rows, Tu_rows, pair_ptr, pos, neg, per_entry, list_idx, top, reg=None, damp=1.0, maps=False):
+        """bprx_influence: for every entry of the lists (list_idx: contiguous int32 device tensor [n, K] of catalogue ids, a slot
+        < 0 is empty) the `top` (1..32) history entries of row r the entry's score rests on most, on the fold-in objective of the
+        row [Gu_rows_r | Tu_rows_r] (contiguous fp32 device tensors [n, k] / [n, d], Tu_rows None iff d == 0) over its pairs
+        (pos[p], neg[p]), p in [pair_ptr[r], pair_ptr[r + 1]); `per_entry` consecutive pairs are one history entry.  reg defaults
+        to the engine's.  Returns the device dict item int32 [n, K, top] (the entries' ids by descending influence, -1 past
+        them), infl fp32 [n, K, top], total fp32 [n, K] (sum of |influence| over all entries), cnt int32 [n, K] (entries),
+        flag int32 [n] (1: the row's factorisation failed, its slots are empty) and, with maps, full fp32 [n, K, M] (every
+        entry's influence, M the longest row's entries; 0 past a row's own)."""
+        if list_idx.dim() != 2 or list_idx.dtype != torch.int32 or not list_idx.is_contiguous():
+            raise ValueError("influence: list_idx is a contiguous int32 tensor [n, K]")
+        n, K = (int(x) for x in list_idx.shape)
+        if pair_ptr.dtype != torch.int64 or pos.dtype != torch.int32 or neg.dtype != torch.int32 or int(pair_ptr.numel()) != n + 1:
+            raise ValueError("influence: pair_ptr is int64 [n + 1], pos / neg are int32, one row per list")
+        for name, rows, width in (("Gu_rows", Gu_rows, self.k), ("Tu_rows", Tu_rows, self.d)):
+            if (rows is None) != (width == 0):
+                raise ValueError("influence: %s is None exactly when its width is 0" % name)
+            if rows is not None and (rows.dtype != torch.float32 or not rows.is_contiguous() or tuple(rows.shape) != (n, width)):
+                raise ValueError("influence: %s is a contiguous fp32 tensor [%d, %d]" % (name, n, width))
+        top, per_entry = int(top), int(per_entry)
+        reg = self._hyper()[1] if reg is None else float(reg)
+        out = {"item": torch.empty((n, K, max(top, 0)), dtype=torch.int32, device=self.device),
+               "infl": torch.empty((n, K, max(top, 0)), dtype=torch.float32, device=self.device),
+               "total": torch.empty((n, K), dtype=torch.float32, device=self.device),
+               "cnt": torch.empty((n, K), dtype=torch.int32, device=self.device),
+               "flag": torch.empty(n, dtype=torch.int32, device=self.device)}
+        stride = 1
+        if maps:
+            m = (pair_ptr[1:] - pair_ptr[:-1]).max().item() if n else 0
+            stride = max(1, -(-int(m) // max(per_entry, 1)))
+            out["full"] = torch.zeros((n, K, stride), dtype=torch.float32, device=self.device)
+        _ffi.check(self.h, self.lib.bprx_influence(self.h, _addr(Gu_rows), _addr(Tu_rows), n, _addr(pair_ptr), _addr(pos), _addr(neg),
+                                                   per_entry, reg, float(damp), K, _addr(list_idx), top, _addr(out["item"]),
+                                                   _addr(out["infl"]), _addr(out["total"]), _addr(out["cnt"]),
+                                                   _addr(out["full"]) if maps else None, stride, _addr(out["flag"]), _stream()))
+        return out
+
     def _hyper(self):
         return self._lr_reg
 

@@ -18,7 +18,7 @@ from time import time
 
 import numpy as np
 
-from .ranking import (blocks, lists_to_csr, rank_rows, rank_rows_host, write_because, write_capped, write_diverse, write_feature_rows,
+from .ranking import (blocks, lists_to_csr, rank_rows, rank_rows_host, write_because, write_influence, write_capped, write_diverse, write_feature_rows,
                       write_item_lists, write_ranked, write_shelves, style_file, user_style_rows, write_style_items, write_styles,
                       write_user_styles)
 
@@ -309,6 +309,36 @@ class Evaluator:
                 idx = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32), device=eng.device)
                 hist, cos, _ = eng.because(space, rn, idx, (ptr[u0:u1 + 1], items), top, Pq, rn_q)
                 write_because(out, range(u0, u1), ids, vals, hist.cpu().numpy(), cos.cpu().numpy())
+
+    def store_recommendation_influence(self, path="", top=5, damp=1.0):
+        """BPRMF / VBPR / GradFashion: for every (u, i) of every user's top-k list (the lists store_recommendation writes, ranked
+        again the same way) the `top` entries of u's training list the score rests on most (bprx_influence on the user's own row)
+        as rows 'u\\ti\\tscore\\trank\\thist_item\\tinfluence\\tshare' in `path` (ranking.write_influence).  The pairs of ALL
+        users are drawn once, before blocking, by draw_fold_pairs(training lists, num_items, --fold_negatives, --init_seed): a
+        user's rows do not depend on the block size.  One bprx_influence call per user block.  Device only: force_host or top_k >
+        1024 raise ValueError."""
+        import torch
+        from .models import draw_fold_pairs
+        m = self.model
+        top = m._influence_args(top)
+        eng = m.engine
+        self._metrics_device_csr()
+        U = m.data.num_users
+        train = self.data.training_list
+        negatives = int(getattr(m.params, "fold_negatives", 4))
+        ptr, pos, neg = draw_fold_pairs(list(train[:U]) + [[] for _ in range(U - len(train))], m.data.num_items, negatives,
+                                        getattr(m.params, "init_seed", 0))
+        ptr, pos, neg = (torch.as_tensor(a, device=eng.device) for a in (ptr, pos, neg))
+        Gu, Tu = eng.t["Gu"], (eng.t["Tu"] if eng.d else None)
+        with open(path, 'w') as out:
+            for u0, u1 in self._user_blocks():
+                ids, vals = rank_rows(self._topk(u0, u1), eng.score_block(u0, u1), self.k)[:2]
+                if not ids.size:
+                    continue
+                idx = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32), device=eng.device)
+                e = eng.influence(Gu[u0:u1], None if Tu is None else Tu[u0:u1], ptr[u0:u1 + 1], pos, neg, negatives, idx, top,
+                                  reg=m.reg, damp=damp)
+                write_influence(out, range(u0, u1), ids, vals, e["item"].cpu().numpy(), e["infl"].cpu().numpy(), e["total"].cpu().numpy())
 
     def store_similar_new(self, path="", features=None):
         """VBPR / GradFashion: the catalogue neighbours of every row of `features` (raw rows of items outside the catalogue, as

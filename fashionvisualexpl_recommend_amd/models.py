@@ -20,8 +20,9 @@ from . import configs
 from .engine import Engine, as_index
 from .evaluator import Evaluator
 from .ranking import (because_paths, because_rows, blocks, cap_rows, class_csr, class_rows_per_block, diverse_zeros, diversify_rows,
-                      div_paths, item_file, owners_of, rank_class_rows, rank_rows, ranked_zeros, run_file, shelf_file, style_file,
-                      wanted_blocks, warm_file, write_because, write_capped, write_diverse, write_ranked, write_shelves)
+                      div_paths, influence_file, influence_rows, item_file, owners_of, rank_class_rows, rank_rows, ranked_zeros,
+                      run_file, shelf_file, style_file, wanted_blocks, warm_file, write_because, write_capped, write_diverse,
+                      write_influence, write_ranked, write_shelves)
 from .synth import glorot_uniform
 
 
@@ -176,6 +177,8 @@ class BPRMF(RecommenderModel):
         self.diversify_theta = float(getattr(params, "diversify", 0.0) or 0.0)     # theta of the div-* files; 0: none
         self.diversify_pool = int(getattr(params, "diversify_pool", 100) or 100)   # candidates per list the MMR step picks from
         self.because_top = int(getattr(params, "because", 0) or 0)                 # owned items per pair in because-*; 0: none
+        self.influence_top = int(getattr(params, "influence", 0) or 0)             # history entries per pair in influence-*; 0: none
+        self.influence_damp = float(getattr(params, "influence_damp", 1.0))        # the relative damping of bprx_influence
         self.audience_k = int(getattr(params, "audience", 0) or 0)                 # users per item in audience-*; 0: none
         self.shelves_k = int(getattr(params, "shelves", 0) or 0)                   # entries per class in shelf-*; 0: none
         self.shelf_count = int(getattr(params, "shelf_count", 0) or 0)             # shelves per user in shelf-*; 0: all
@@ -402,6 +405,7 @@ class BPRMF(RecommenderModel):
             self._store_similar(path)
             self._store_diverse(path)
             self._store_because(path)
+            self._store_influence(path)
             self._store_audience(path)
             self._store_warm(path)
             self._store_styles(path)
@@ -513,6 +517,16 @@ class BPRMF(RecommenderModel):
                                         lists=[list(dict.fromkeys(l)) for l in lists])
             with open(because_paths(new_path), 'w') as out:
                 write_because(out, labels, ids, vals, hist.reshape(ids.shape + (-1,)), cos.reshape(ids.shape + (-1,)))
+        if self.influence_top > 0:                               # influence-new-user-recs-*: the fitted rows and the pairs that fitted them
+            top = self._influence_args(self.influence_top)
+            ids, vals = res[0], res[1]
+            negatives = getattr(self.params, "fold_negatives", 4)
+            ptr, pos, neg = draw_fold_pairs(lists, self.num_items, negatives, getattr(self.params, "init_seed", 0))
+            dev = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=self.engine.device)
+            e = self.engine.influence(rows[0], rows[1], dev(ptr, np.int64), dev(pos, np.int32), dev(neg, np.int32), negatives,
+                                      dev(ids, np.int32), top, reg=self.reg, damp=self.influence_damp)
+            with open(influence_file(path, "influence-new-user-recs"), 'w') as out:
+                write_influence(out, labels, ids, vals, e["item"].cpu().numpy(), e["infl"].cpu().numpy(), e["total"].cpu().numpy())
         if self.diversify_theta > 0:                             # div-new-user-recs-* / div-new-user-ild-*: the same fitted rows
             p_recs, p_ild = div_paths(new_path)
             with open(p_recs, 'w') as out, open(p_ild, 'w') as out_ild:
@@ -1014,6 +1028,61 @@ class BPRMF(RecommenderModel):
         if self.because_top <= 0:
             return
         self.evaluator.store_recommendation_because(because_paths(path), self.because_top, self.similar_space)
+
+
+    # ---- influence: the history entries a score rests on, on the user's own fold-in objective (include/bprx.h, bprx_influence) --
+    def _influence_args(self, top):
+        """`top` of an influence call, checked: a model whose user row alone makes the score, the device path, 1 <= top <= 32."""
+        if not self.diverse:
+            raise NotImplementedError("%s: the score is not linear in the user's row; its explanations by the user's history come "
+                                      "from %s" % (type(self).__name__, self.because_instead))
+        if getattr(self.evaluator, "force_host", False) or self.evaluator.k > 1024:
+            raise ValueError("--influence runs on the device only (no force_host, top_k <= 1024): there is no host form")
+        top = int(top)
+        if not 1 <= top <= 32:
+            raise ValueError("influence: top lies in [1, 32] (got %d)" % top)
+        return top
+
+    def influence(self, users, items, top=5, negatives=None, seed=None, reg=None, damp=1.0, lists=None, rows=None, maps=False):
+        """For every pair (users[p], items[p]) the `top` entries of the user's history the item's score rests on most: how far
+        x_ui would fall, to first order, had the user not bought the entry (one damped Newton step on the user's fold-in
+        objective with the entry's pairs left out; include/bprx.h, bprx_influence).  Returns numpy hist int64 [n, top] (catalogue
+        ids by descending influence, -1 past the history's entries), infl fp32 [n, top], total fp32 [n] (sum of |influence| over
+        all entries) and count int64 [n] (entries; 0 for a user without pairs or a row whose factorisation failed); with maps also
+        fp32 [n, M], every entry's influence in history order (M: the longest history of the call, 0 past a user's own).
+        lists: the histories, indexed by user (default: the training lists; a repeated item is an entry each time).  rows: None =
+        the model's own rows of those users, or device (Gu rows, Tu rows or None) indexed like lists: folded-in users.  The
+        objective's pairs are draw_fold_pairs(the histories of the call's users in order, num_items, negatives, seed); negatives /
+        seed / reg: None = the run's --fold_negatives / --init_seed / reg.  Pairs may come in any order: runs of equal users
+        share one list of the call (ranking.influence_rows, Engine.influence)."""
+        top = self._influence_args(top)
+        eng = self.engine
+        negatives = int(getattr(self.params, "fold_negatives", 4) if negatives is None else negatives)
+        seed = getattr(self.params, "init_seed", 0) if seed is None else seed
+        reg = self.reg if reg is None else reg
+        if lists is None:
+            lists = _Padded(self.data.training_list, self.num_users)
+        u = np.asarray(users, dtype=np.int64).reshape(-1)
+        if u.size and (u.min() < 0 or u.max() >= len(lists)):
+            raise ValueError("influence: user ids lie in [0, %d)" % len(lists))
+        Gu, Tu = (eng.t["Gu"], eng.t["Tu"] if eng.d else None) if rows is None else rows
+        if int(Gu.shape[0]) < len(lists):
+            raise ValueError("influence: %d rows for %d histories" % (int(Gu.shape[0]), len(lists)))
+
+        def take(ids):
+            ix = torch.as_tensor(ids, dtype=torch.int64, device=eng.device)
+            return Gu.index_select(0, ix).contiguous(), (Tu.index_select(0, ix).contiguous() if Tu is not None else None)
+
+        return influence_rows(lambda g, t, ptr, pos, neg, li: eng.influence(g, t, ptr, pos, neg, negatives, li, top, reg=reg, damp=damp,
+                                                                            maps=maps),
+                              u, items, lists, top, eng.device, lambda h: draw_fold_pairs(h, self.num_items, negatives, seed), take, maps)
+
+    def _store_influence(self, path):
+        """params.influence = L > 0: influence-* next to the recs-* file at `path`, rows 'u\ti\tscore\trank\thist_item\tinfluence\t
+        share' for every (u, i) of every user's top-k list."""
+        if self.influence_top <= 0:
+            return
+        self.evaluator.store_recommendation_influence(influence_file(path, "influence"), self.influence_top, self.influence_damp)
 
 
 class _Padded:

@@ -250,6 +250,44 @@ def because_rows(because, users, items, lists, top, device, dedup=False):
     return item[li, off].astype(np.int64), cos[li, off], cnt[li, off].astype(np.int64)
 
 
+def influence_rows(influence, users, items, lists, top, device, draw, rows, maps=False):
+    """The influence of the history entries of arbitrary (user, item) pairs: runs of equal users become the lists of one call,
+    padded with -1 and split at BECAUSE_MAX_LIST entries, as because_rows forms them.  The pairs of the call are draw(the
+    histories lists[user] of the runs, in order) = (pair_ptr, pos, neg) (models.draw_fold_pairs: one draw per run; the lists a
+    long run is split into share the run's pairs), rows(user ids int64) the device (Gu rows, Tu rows or None) of those users.
+    influence(Gu, Tu, ptr, pos, neg, list_idx int32 [n, K]) is the entry (Engine.influence with its per_entry, top, reg, damp and
+    maps) and returns the device dict.  Returns numpy hist int64 [pairs, L], infl fp32 [pairs, L], total fp32 [pairs] and count
+    int64 [pairs], pair by pair, and with maps the per-entry influences fp32 [pairs, M] (M: the longest history of the call in
+    entries, 0 past a pair's own); without pairs the entry is not called."""
+    users, items = np.asarray(users, dtype=np.int64).reshape(-1), np.asarray(items, dtype=np.int64).reshape(-1)
+    if users.size != items.size:
+        raise ValueError("influence: %d users for %d items" % (users.size, items.size))
+    top = int(top)
+    if users.size == 0:
+        out = (np.zeros((0, top), np.int64), np.zeros((0, top), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int64))
+        return out + (np.zeros((0, 0), np.float32),) if maps else out
+    run = np.cumsum(np.r_[True, users[1:] != users[:-1]]) - 1              # the run of every pair
+    first = np.flatnonzero(np.r_[True, run[1:] != run[:-1]])               # where each run starts
+    within = np.arange(users.size) - first[run]
+    chunk = within // BECAUSE_MAX_LIST
+    new = np.r_[True, (run[1:] != run[:-1]) | (chunk[1:] != chunk[:-1])]
+    li, off = np.cumsum(new) - 1, within % BECAUSE_MAX_LIST                # list and slot of every pair
+    heads = np.flatnonzero(new)
+    list_idx = np.full((heads.size, int(off.max()) + 1), -1, np.int32)
+    list_idx[li, off] = items
+    ptr, pos, neg = draw([lists[int(u)] for u in users[first]])
+    of = run[heads]                                                         # the run of every list
+    if heads.size != first.size:                                            # a run split into lists: each gets the run's pairs
+        take = np.concatenate([np.arange(ptr[r], ptr[r + 1]) for r in of] + [np.zeros(0, np.int64)]).astype(np.int64)
+        ptr, pos, neg = np.concatenate([[0], np.cumsum(ptr[of + 1] - ptr[of])]).astype(np.int64), pos[take], neg[take]
+    Gu, Tu = rows(users[heads])
+    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=device)
+    res = influence(Gu, Tu, dev(ptr), dev(pos), dev(neg), dev(list_idx))
+    host = {n: v.cpu().numpy() for n, v in res.items()}
+    out = (host["item"][li, off].astype(np.int64), host["infl"][li, off], host["total"][li, off], host["cnt"][li, off].astype(np.int64))
+    return out + (host["full"][li, off],) if maps else out
+
+
 def rank_rows_host(scores, mask_lists, k):
     """rank_rows on the host: row r of the numpy block `scores` gets -inf (IN `scores`) at mask_lists[r] (None: nothing is
     masked) and is listed by numpy_topk.  Returns (ids int64 [n, kk], vals [n, kk])."""
@@ -393,6 +431,46 @@ def style_file(path, kind):
     if kind not in STYLE_FILES:
         raise ValueError("style_file: %r is none of %s" % (kind, ", ".join(STYLE_FILES)))
     return head + kind + tail
+
+
+# The files of a run about INFLUENCE (--influence L: the history entries a pick's score rests on, on the user's own fold-in
+# objective; include/bprx.h, bprx_influence): influence-* is about the pairs of recs-*, influence-new-user-recs-* about those of
+# new-user-recs-* (rows 'label item score rank hist_item influence share'), named like the files above.
+INFLUENCE_FILES = {"influence": None, "influence-new-user-recs": None}
+
+
+def influence_file(path, kind):
+    """run_file for the kinds of INFLUENCE_FILES: the file of `kind` next to the recs-* / best-recs-* file at `path`, 'best-' stays
+    in front; ValueError for a path whose file name starts with neither, and for a kind that is none of INFLUENCE_FILES."""
+    head, base, tail = _split_run_file(path)
+    if base != "recs":
+        raise ValueError("%r is neither a recs-* nor a best-recs-* path" % path)
+    if kind not in INFLUENCE_FILES:
+        raise ValueError("influence_file: %r is none of %s" % (kind, ", ".join(INFLUENCE_FILES)))
+    return head + kind + tail
+
+
+def write_influence(out, labels, ids, vals, hist, infl, total):
+    """One row 'label\tid\tval\trank\thist_item\tinfluence\tshare' per history entry that explains a list entry, rank 0 (the
+    largest influence) first, for every entry of every list in write_ranked's order: ids / vals [n, kk] as write_ranked takes
+    them, hist int / infl fp32 [n, kk, L] with -1 past an entry's candidates, total fp32 [n, kk] the sum of |influence| over ALL
+    of the user's entries; share = influence / total in float32, 0.0 where total is 0.  An entry without a candidate (a user
+    without pairs, or a row whose factorisation failed) gets one row with rank -1, hist_item -1, influence 0.0 and share 0.0, so
+    that the file names every pair of the list file.  Fields are formatted as write_ranked formats them."""
+    for r, label in enumerate(labels):
+        head = str(label) + '\t'
+        for q, item in enumerate(ids[r]):
+            pair = head + str(item) + '\t' + str(vals[r, q]) + '\t'
+            if hist.shape[2] == 0 or hist[r, q, 0] < 0:
+                out.write(pair + '-1\t-1\t0.0\t0.0\n')
+                continue
+            tot = np.float32(total[r, q])
+            for s in range(hist.shape[2]):
+                if hist[r, q, s] < 0:
+                    break
+                v = np.float32(infl[r, q, s])
+                share = v / tot if tot != 0 else np.float32(0.0)
+                out.write(pair + str(s) + '\t' + str(hist[r, q, s]) + '\t' + str(v) + '\t' + str(share) + '\n')
 
 
 def write_styles(out, style, cos):

@@ -14,6 +14,9 @@ greedy Maximal Marginal Relevance from the user's top --diversify_pool, cosines 
 --because L (bprmf, vbpr, grad_fashion) writes because-* / best-because-* files next to recs-*: for every recommended (u, i) the L
 items of u's training list nearest to i by cosine in the space of --similar_space ("because it is like the X you own"), and with
 --new_users / --new_items because-new-user-recs-* / because-new-recs-*.
+--influence L (bprmf, vbpr, grad_fashion) writes influence-* / best-influence-* files next to recs-*: for every recommended (u, i) the
+L entries of u's training list the score rests on most, by influence on u's own fold-in objective (include/bprx.h, bprx_influence),
+and with --new_users influence-new-user-recs-*.
 --audience K (bprmf, vbpr, grad_fashion) writes audience-* / best-audience-* files next to recs-*: for every catalogue item (or
 the ids of --audience_items) the K users that score it highest, its owners excluded, and with --new_items new-audience-* /
 best-new-audience-* (the visual score of items the model was not trained on).
@@ -125,6 +128,17 @@ def parse_args(argv=None):
                              "without an owned item to compare with: one row with rank -1); with --new_users also "
                              "because-new-user-recs-* (the history is the file's), with --new_items also because-new-recs-* "
                              "(always the visual space); 0 = off")
+    parser.add_argument('--influence', type=int, default=0, metavar='L',
+                        help="bprmf, vbpr, grad_fashion: also write influence-* / best-influence-* files next to recs-* / best-recs-*: "
+                             "for every (u, i) of every user's top_k list the L (1..32) entries of u's training list the score rests "
+                             "on most -- how far it would fall, to first order, had u not bought the entry (one damped Newton step on "
+                             "u's own fold-in objective over --fold_negatives sampled negatives per entry, seed --init_seed) -- rows "
+                             "`u i score rank hist_item influence share`, rank 0 first, share = influence / sum of |influence| over "
+                             "all of u's entries (a pair without entries: one row with rank -1); with --new_users also "
+                             "influence-new-user-recs-* (the fitted rows and the pairs that fitted them); 0 = off")
+    parser.add_argument('--influence_damp', type=float, default=1.0, metavar='DAMP',
+                        help="--influence: the ridge added to the Hessian A of u's objective is 2 reg pairs + DAMP trace(A) / (k + d); "
+                             "DAMP > 0 bounds its condition number by (k + d) / DAMP + 1; 0 needs --reg > 0")
     parser.add_argument('--audience', type=int, default=0, metavar='K',
                         help="bprmf, vbpr, grad_fashion: also write audience-* / best-audience-* files next to recs-* / best-recs-* "
                              "with the K (1..1024) users that score every catalogue item highest, the item's owners (the users "
@@ -286,6 +300,14 @@ def parse_args(argv=None):
         parser.error("--diversify_pool takes top_k (%d) .. 1024 (got %s)" % (args.top_k, args.diversify_pool))
     if not 0 <= args.because <= 32:
         parser.error("--because takes 0 (off) .. 32 (got %s)" % args.because)
+    if not 0 <= args.influence <= 32:
+        parser.error("--influence takes 0 (off) .. 32 (got %s)" % args.influence)
+    if not (args.influence_damp >= 0 and args.influence_damp < float("inf")):
+        parser.error("--influence_damp takes a finite value >= 0 (got %s)" % args.influence_damp)
+    if args.influence != 0 and args.rec not in ('bprmf', 'vbpr', 'grad_fashion'):
+        parser.error("--influence needs --rec bprmf, vbpr or grad_fashion (got --rec %s)" % args.rec)
+    if args.influence != 0 and args.influence_damp == 0 and not args.reg > 0:
+        parser.error("--influence_damp 0 needs --reg > 0: without either the Hessian of a user's objective may be singular")
     if args.styles != 0 and not 2 <= args.styles <= 1024:
         parser.error("--styles takes 0 (off) or 2 .. 1024 (got %s)" % args.styles)
     if args.style_iters < 1:
@@ -540,6 +562,10 @@ def train(argv=None):
         raise NotImplementedError('--diversify runs on one GPU (the sharded drivers write no div-* files): use --world_size 1')
     if args.because != 0 and int(args.world_size) > 1:
         raise NotImplementedError('--because runs on one GPU (the sharded drivers write no because-* files): use --world_size 1')
+    if args.influence != 0 and int(args.world_size) > 1:
+        raise NotImplementedError('--influence runs on one GPU (the sharded drivers write no influence-* files): use --world_size 1')
+    if args.influence != 0 and args.top_k > 1024:
+        raise ValueError('--influence runs on the device only (top_k <= 1024): there is no host form')
     if args.audience != 0 and int(args.world_size) > 1:
         raise NotImplementedError('--audience runs on one GPU (the sharded drivers write no audience-* files): use --world_size 1')
     if args.warm_items is not None and int(args.world_size) > 1:

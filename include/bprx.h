@@ -554,6 +554,47 @@ BPRX_API int bprx_because(bprx_handle *h, int32_t space, const float *Pq, int64_
                           int64_t n, int32_t K, const int32_t *list_idx, const int64_t *hist_ptr, const int32_t *hist_items,
                           int32_t L, int32_t *out_item, float *out_cos, int32_t *out_cnt, void *stream);
 
+/* ---- BPRMF, VBPR and GradFashion: influence, the owned items a pick's score rests on -----------------------------------------
+   "How far would this pick's score fall had the user not bought X": the training-point influence (Koh & Liang 2017; for latent
+   factor models Cheng et al., KDD 2019) of every history entry on the scores of a list, taken on the user's own objective, the
+   per-user convex problem of bprx_fold_in with every item-side parameter frozen.  For row r: w = [Gu_rows_r | Tu_rows_r] (k + d
+   numbers), its m_r pairs (pos[p], neg[p]), p in [pair_ptr[r], pair_ptr[r+1]); `per_entry` consecutive pairs form one history
+   entry, a short last group is an entry of its own: M_r = ceil(m_r / per_entry) entries, entry e owns the row's pairs
+   [e per_entry, (e+1) per_entry) and is named by pos of its first pair.  z_i, c_i, D_p, dc_p, x_p and the clip as above:
+       s_p = sigmoid(-x_p)   c_p = s_p (1 - s_p)           (x_p outside [-80, 1e8]: s_p = c_p = 0)
+       A = sum_p c_p D_p D_p^T                              (n x n, n = k + d)
+       lambda = 2 reg m_r + damp trace(A) / n               (the objective's own ridge + a Levenberg-Marquardt term relative to A)
+       g_e = sum_{p in entry e} s_p D_p
+       infl(q, e) = z_q^T (A + lambda I)^-1 g_e             total(q) = sum_e |infl(q, e)|
+   infl(q, e) is the first-order fall of x_rq when entry e's pairs leave the row's objective and the row is refitted by one damped
+   Newton step: positive = the purchase holds the pick up.  With damp > 0 the condition number of A + lambda I is at most
+   n / damp + 1, which keeps the fp32 Cholesky factorisation safe (and defined for reg == 0, where A alone may be singular).
+   list_idx int32 [n, K]: catalogue ids, a slot < 0 is empty.  Outputs:
+     out_item int32 / out_infl fp32 [n, K, L]  the min(L, M_r) entries of largest influence by descending value (values compare
+                as floats, equal values go to the lower entry position; every entry is a candidate, one whose id equals q too);
+                the id is the entry's own; -1 / 0.0f past them and in every slot of an empty list slot
+     out_total fp32 [n, K]; out_cnt int32 [n, K] (may be NULL): M_r, 0 for an empty slot
+     out_full (may be NULL): out_full[(r K + q) full_stride + e] = infl(q, e) for e < M_r (the caller makes full_stride >= M_r;
+                an entry past it is not written), nothing else is written
+     out_flag int32 [n] (may be NULL): 1 where the factorisation met a pivot that is not positive and finite; all of that row's
+                slots are then empty (cnt 0, total 0, out_full untouched, never a NaN); 0 otherwise.  A row without pairs has
+                empty slots and flag 0.
+   No atomics: the outputs of (r, q) depend on the row, its pairs, the tables and q only -- not on n, K, the row's position, the
+   other slots, or on how the kernel tiles pairs or chunks a list.
+   Handles and state as bprx_fold_in: a bound BPRMF or VBPR handle, plain or factored, any feature dtype (the call reads P, never
+   F); it first settles a pending dense update, brings lazy adam_tf23 rows up to date and makes P current, then writes its outputs
+   only and allocates nothing.
+   Errors: BPRX_E_INVALID for a NULL handle or required pointer (Tu_rows NULL iff d == 0), an ACF or AttentiveFashion handle,
+   n < 0 or >= 2^31, K outside [1, 1024], L outside [1, 32], per_entry < 1, reg or damp negative or not finite or both zero,
+   out_full with full_stride < 1, k + d > BPRX_INFLUENCE_MAX_WIDTH (one workgroup keeps A's triangle in half a CU's LDS);
+   BPRX_E_STATE for an unbound handle; n == 0: BPRX_OK, nothing is written.  Item ids out of range are clamped and reported by
+   bprx_sync_check (BPRX_E_RANGE).  After any error the handle stays usable. */
+#define BPRX_INFLUENCE_MAX_WIDTH 160
+BPRX_API int bprx_influence(bprx_handle *h, const float *Gu_rows, const float *Tu_rows, int64_t n, const int64_t *pair_ptr,
+                            const int32_t *pos, const int32_t *neg, int32_t per_entry, float reg, float damp, int32_t K,
+                            const int32_t *list_idx, int32_t L, int32_t *out_item, float *out_infl, float *out_total,
+                            int32_t *out_cnt, float *out_full, int64_t full_stride, int32_t *out_flag, void *stream);
+
 /* ---- ACF (ACF.py:20-270) on a BPRMF handle ------------------------------------------------------------------------------
    Attentive Collaborative Filtering over per-item feature maps f_l [M, C] (M = H*W spatial components).  For user u with
    history P(u) (ACF.py:135-181):
