@@ -132,6 +132,7 @@ def lib():
         "bprx_audience_warm_block": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, vp, vp]),
         "bprx_diversify": (C.c_int, [vp, i32, vp, i64, i32, vp, vp, i32, f32, vp, vp, vp, vp, vp]),
         "bprx_because": (C.c_int, [vp, i32, vp, i64, vp, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
+        "bprx_calibrate": (C.c_int, [vp, i64, i32, vp, vp, i64, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp]),
         "bprx_influence": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, i32, f32, f32, i32, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp]),
         "bprx_bind_acf": (C.c_int, [vp, C.POINTER(Tables), C.POINTER(Acf)]),
         "bprx_acf_profiles": (C.c_int, [vp, vp, i64, vp, vp, vp, vp]),
@@ -246,7 +247,7 @@ EXPORTS = ["bprx_abi_version", "bprx_create", "bprx_destroy", "bprx_last_error",
            "bprx_apply_user_msgs", "bprx_sampler_create",
            "bprx_sampler_destroy", "bprx_sampler_count", "bprx_sampler_ref_stream", "bprx_settle", "bprx_dense_pending", "bprx_set_loss_lag",
            "bprx_sample_philox_hard", "bprx_sample_epoch_hard", "bprx_hard_snapshot", "bprx_topk_classes",
-           "bprx_style_assign", "bprx_style_update", "bprx_influence"]
+           "bprx_style_assign", "bprx_style_update", "bprx_influence", "bprx_calibrate"]
 
 
 def check(handle, rc):

@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libbprx.so")
-SOURCES = ["bprx_api.hip", "bprx_sparse.hip", "bprx_proj.hip", "bprx_philox.hip", "bprx_eval.hip", "bprx_probe.hip", "bprx_route.hip", "bprx_factored.hip", "bprx_explain.hip", "bprx_foldin.hip", "bprx_acf.hip", "bprx_attentive.hip", "bprx_diversify.hip", "bprx_because.hip", "bprx_styles.hip", "bprx_influence.hip", "bprx_sampler.cpp"]
+SOURCES = ["bprx_api.hip", "bprx_sparse.hip", "bprx_proj.hip", "bprx_philox.hip", "bprx_eval.hip", "bprx_probe.hip", "bprx_route.hip", "bprx_factored.hip", "bprx_explain.hip", "bprx_foldin.hip", "bprx_acf.hip", "bprx_attentive.hip", "bprx_diversify.hip", "bprx_because.hip", "bprx_styles.hip", "bprx_influence.hip", "bprx_calibrate.hip", "bprx_sampler.cpp"]
 
 
 def _hipcc():

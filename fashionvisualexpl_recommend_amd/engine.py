@@ -899,6 +899,34 @@ class Engine:
                                                    _stream()))
         return idx, val, pen, ild
 
+    def calibrate(self, pool_idx, pool_val, hist_csr, item_class, C, k, lam, alpha=0.01, row0=0):
+        """bprx_calibrate: greedy KL re-rank of the pools (pool_idx int32, pool_val fp32: contiguous device tensors [n, N], best
+        first, as the top-K entries return them) toward the class mix of each list's history.  hist_csr = (int64 ptr, int32 items)
+        on the device, list r's history is list row0 + r of it (None: every history is empty); item_class: a contiguous int32
+        device tensor [width], -1 = no class, otherwise in [0, C).  lam in [0, 1]: 0 keeps the pool's order, 1 ranks by the KL
+        gain alone; alpha in (0, 1) smooths the list's class shares.  Returns the device (idx int32 [n, k], val fp32 [n, k] the
+        picks' pool scores, cls int32 [n, k] their classes, gain fp32 [n, k] the KL term each pick removed, kl fp32 [n, 2] the
+        KL(p || q~) of the pool's first k candidates and of the calibrated list).  Slots past the candidates of a pool hold -1 / 0 /
+        -1 / 0."""
+        n, N = (int(x) for x in pool_idx.shape)
+        if tuple(pool_val.shape) != (n, N) or pool_idx.dtype != torch.int32 or pool_val.dtype != torch.float32:
+            raise ValueError("calibrate: pool_idx int32 [n, N] and pool_val fp32 [n, N]")
+        if not (pool_idx.is_contiguous() and pool_val.is_contiguous()):
+            raise ValueError("calibrate: the pools must be contiguous")
+        if item_class.dim() != 1 or item_class.dtype != torch.int32 or not item_class.is_contiguous():
+            raise ValueError("calibrate: item_class is a contiguous int32 tensor [width]")
+        ptr, items = (None, None) if hist_csr is None else hist_csr
+        if ptr is not None and (ptr.dtype != torch.int64 or items.dtype != torch.int32):
+            raise ValueError("calibrate: hist_csr = (int64 ptr, int32 items)")
+        k = int(k)
+        idx, cls = (torch.empty((n, max(k, 0)), dtype=torch.int32, device=self.device) for _ in range(2))
+        val, gain = (torch.empty((n, max(k, 0)), dtype=torch.float32, device=self.device) for _ in range(2))
+        kl = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        _ffi.check(self.h, self.lib.bprx_calibrate(self.h, n, N, _addr(pool_idx), _addr(pool_val), int(row0), _addr(ptr), _addr(items),
+                                                   _addr(item_class), int(item_class.shape[0]), int(C), k, float(lam), float(alpha),
+                                                   _addr(idx), _addr(val), _addr(cls), _addr(gain), _addr(kl), _stream()))
+        return idx, val, cls, gain, kl
+
     def because(self, space, rn, list_idx, hist_csr, top, Pq=None, rn_q=None):
         """bprx_because: for every entry of the lists (list_idx: contiguous int32 device tensor [n, K], catalogue ids, or rows of
         Pq = project_rows(F) with rn_q = sim_rnorm('visual', Pq); a slot < 0 is empty) the `top` (1..32) nearest items of the

@@ -20,7 +20,7 @@ import numpy as np
 
 from .ranking import (blocks, lists_to_csr, rank_rows, rank_rows_host, write_because, write_influence, write_capped, write_diverse, write_feature_rows,
                       write_item_lists, write_ranked, write_shelves, style_file, user_style_rows, write_style_items, write_styles,
-                      write_user_styles)
+                      write_user_styles, hist_classed, write_calibrated)
 
 
 def _eval_block(scores, u0, train, evl, K):
@@ -234,6 +234,19 @@ class Evaluator:
         ids, vals, pen, ild = self.model.recommend_diverse(None, k, pool, theta, space)
         with open(path, 'w') as out, open(path_ild, 'w') as out_ild:
             write_diverse(out, out_ild, range(ids.shape[0]), ids, vals, pen, ild)
+
+    def store_recommendation_calibrated(self, path="", path_kl="", k=None, pool=None, lam=None, alpha=None):
+        """BPRMF / VBPR / GradFashion: every user's calibrated list (model.recommend_calibrated: greedy KL re-rank of the user's
+        top-`pool` toward the class mix of the user's training items, None = the run's --calibrate / --calibrate_pool /
+        --calibrate_alpha) as rows 'u\ti\tscore\tclass\tgain' in `path`, in list order (gain = the KL term the pick removed at its
+        step), and one row 'u\tkl_plain\tkl_calibrated\thist_classed' per user in `path_kl` (KL(p || q~) of the plain top_k and of
+        the calibrated list; the user's training items that have a class), formatted as store_recommendation formats.  Device
+        only: force_host or top_k > 1024 raise ValueError (there is no host form)."""
+        ids, vals, cls, gain, kl = self.model.recommend_calibrated(None, k, pool, lam, alpha)
+        U = ids.shape[0]
+        lists = list(self.data.training_list[:U]) + [[] for _ in range(U - len(self.data.training_list))]
+        with open(path, 'w') as out, open(path_kl, 'w') as out_kl:
+            write_calibrated(out, out_kl, range(U), ids, vals, cls, gain, kl, hist_classed(lists, self.model.item_classes()))
 
     def store_recommendation_shelves(self, path="", k=None, count=0):
         """BPRMF / VBPR / GradFashion: every user's shelves (model.recommend_by_class: the k best items of every item class, None =

@@ -19,10 +19,11 @@ import torch
 from . import configs
 from .engine import Engine, as_index
 from .evaluator import Evaluator
-from .ranking import (because_paths, because_rows, blocks, cap_rows, class_csr, class_rows_per_block, diverse_zeros, diversify_rows,
-                      div_paths, influence_file, influence_rows, item_file, owners_of, rank_class_rows, rank_rows, ranked_zeros,
-                      run_file, shelf_file, style_file, wanted_blocks, warm_file, write_because, write_capped, write_diverse,
-                      write_influence, write_ranked, write_shelves)
+from .ranking import (because_paths, because_rows, blocks, cal_paths, calibrate_rows, calibrated_zeros, cap_rows, class_csr,
+                      class_rows_per_block, diverse_zeros, diversify_rows, div_paths, hist_classed, influence_file, influence_rows,
+                      item_file, owners_of, rank_class_rows, rank_rows, ranked_zeros, run_file, shelf_file, style_file, wanted_blocks,
+                      warm_file, write_because, write_calibrated, write_capped, write_diverse, write_influence, write_ranked,
+                      write_shelves)
 from .synth import glorot_uniform
 
 
@@ -183,6 +184,9 @@ class BPRMF(RecommenderModel):
         self.shelves_k = int(getattr(params, "shelves", 0) or 0)                   # entries per class in shelf-*; 0: none
         self.shelf_count = int(getattr(params, "shelf_count", 0) or 0)             # shelves per user in shelf-*; 0: all
         self.class_cap = int(getattr(params, "class_cap", 0) or 0)                 # items per class in cap-*; 0: none
+        self.calibrate_lambda = float(getattr(params, "calibrate", 0.0) or 0.0)    # lambda of the cal-* files; 0: none
+        self.calibrate_pool = int(getattr(params, "calibrate_pool", 100) or 100)   # candidates per list the KL step picks from
+        self.calibrate_alpha = float(getattr(params, "calibrate_alpha", 0.01) or 0.01)   # the smoothing of the list's class shares
         self.styles_S = int(getattr(params, "styles", 0) or 0)                     # clusters of the styles-* files; 0: none
         self.style_iters = int(getattr(params, "style_iters", 20) or 20)           # Lloyd iterations at the most
         self.style_top = int(getattr(params, "style_top", 10) or 10)               # members per style in style-items-*
@@ -404,6 +408,7 @@ class BPRMF(RecommenderModel):
             self._store_new_user_recs(path)
             self._store_similar(path)
             self._store_diverse(path)
+            self._store_calibrated(path)
             self._store_because(path)
             self._store_influence(path)
             self._store_audience(path)
@@ -439,7 +444,8 @@ class BPRMF(RecommenderModel):
         """(scores [r1 - r0, I], side [r1 - r0, I, c] or None) of rows [r0, r1) of what _fold_rows returned."""
         return self.engine.score_rows_block(rows[0], rows[1], r0, r1), None
 
-    def recommend_new_users(self, histories, k=None, diversify=None, by_class=None, class_cap=None, classes=None, **fold):
+    def recommend_new_users(self, histories, k=None, diversify=None, by_class=None, class_cap=None, classes=None, calibrate=None,
+                            **fold):
         """The k (default top_k) best catalogue items of every new user, their own histories masked: numpy idx int [n, kk] and
         val [n, kk], kk = min(k, I), best first; a model whose scores come with attentions (AttentiveFashion) also returns alpha
         [n, kk, 3] (colour, edges, class).  The rows are fitted by fold_in_users(histories, **fold), scored in row blocks and
@@ -449,10 +455,16 @@ class BPRMF(RecommenderModel):
         them: the lists are then picked by greedy MMR from each row's top-`pool` and (ids, vals, pen, ild) is returned, as by
         recommend_diverse (BPRMF, VBPR, GradFashion).
         by_class = K: the new users' shelves instead, (ids [n, C, kk], vals, cnt) as recommend_by_class returns them; class_cap = M:
-        their quota lists, (ids [n, kk], vals, cls) as recommend_capped returns them; classes as recommend_by_class takes them."""
-        if sum(x is not None for x in (diversify, by_class, class_cap)) > 1:
-            raise ValueError("recommend_new_users: one of diversify, by_class and class_cap")
+        their quota lists, (ids [n, kk], vals, cls) as recommend_capped returns them; classes as recommend_by_class takes them.
+        calibrate: None, or lambda (a float in [0, 1]), or a dict with any of lam / pool / alpha as recommend_calibrated takes
+        them: the lists are then re-ranked toward the class mix of each history (a repeated item counted once) and (ids, vals, cls,
+        gain, kl) is returned, as by recommend_calibrated."""
+        if sum(x is not None for x in (diversify, by_class, class_cap, calibrate)) > 1:
+            raise ValueError("recommend_new_users: one of diversify, by_class, class_cap and calibrate")
         div = self._fold_diverse_args(k, diversify)              # (checked before anything is fitted)
+        if calibrate is not None:
+            cal = self._fold_calibrate_args(k, calibrate, classes)
+            return self._rank_fold_rows(self._fold_rows(histories, **fold), histories, k, cal=cal)
         if by_class is not None or class_cap is not None:
             self._class_args(by_class if by_class is not None else 1, class_cap)
             ccsr = self._class_csr(classes)
@@ -468,13 +480,18 @@ class BPRMF(RecommenderModel):
         opts = dict(diversify) if isinstance(diversify, dict) else {"theta": diversify}
         return self._diverse_args(k, opts.get("pool"), opts.get("theta"), opts.get("space"))
 
-    def _rank_fold_rows(self, rows, histories, k=None, div=None):
-        """What recommend_new_users returns for the fitted rows of _fold_rows(histories): the plain lists, or with div (from
-        _fold_diverse_args) the diversified ones.  The rows are only read: one fit serves both."""
+    def _rank_fold_rows(self, rows, histories, k=None, div=None, cal=None):
+        """What recommend_new_users returns for the fitted rows of _fold_rows(histories): the plain lists, with div (from
+        _fold_diverse_args) the diversified ones, with cal (from _fold_calibrate_args) the calibrated ones.  The rows are only
+        read: one fit serves all."""
         eng = self.engine
         n, I = len(histories), self.num_items
         k = self.evaluator.k if k is None else int(k)
-        if div is None:
+        if cal is not None:
+            kk, pool, lam, alpha, (table, C) = cal
+            once = [list(dict.fromkeys(l)) for l in histories]   # a repeated item counts once
+            out = calibrated_zeros(n, kk)
+        elif div is None:
             out = ranked_zeros(n, min(k, I), self.new_users_side)
         else:
             kk, pool, theta, space = div
@@ -484,7 +501,11 @@ class BPRMF(RecommenderModel):
         for b0, b1 in blocks(n, self.evaluator.user_block, I):
             sc, side = self._score_fold_rows(rows, b0, b1)
             topk = lambda s, kq: eng.topk_lists(s, eng.csr(histories[b0:b1]), kq)
-            if div is None:
+            if cal is not None:
+                pi, pv, _ = rank_rows(topk, sc, pool)
+                hist = eng.csr(once[b0:b1])
+                res = calibrate_rows(lambda qi, qv, kq: eng.calibrate(qi, qv, hist, table, C, kq, lam, alpha), pi, pv, kk, eng.device)
+            elif div is None:
                 res = rank_rows(topk, sc, k, side)
             else:
                 pi, pv, _ = rank_rows(topk, sc, pool)
@@ -531,6 +552,12 @@ class BPRMF(RecommenderModel):
             p_recs, p_ild = div_paths(new_path)
             with open(p_recs, 'w') as out, open(p_ild, 'w') as out_ild:
                 write_diverse(out, out_ild, labels, *self._rank_fold_rows(rows, lists, div=self._fold_diverse_args(None, {})))
+        if self.calibrate_lambda > 0:                            # cal-new-user-recs-* / cal-new-user-kl-*: the same fitted rows
+            p_recs, p_kl = cal_paths(new_path)
+            cal = self._fold_calibrate_args(None, {}, None)
+            with open(p_recs, 'w') as out, open(p_kl, 'w') as out_kl:
+                write_calibrated(out, out_kl, labels, *self._rank_fold_rows(rows, lists, cal=cal),
+                                 hist_classed(lists, cal[4][0].cpu().numpy()))
         if self.shelves_k > 0:                                   # shelf-new-user-recs-*: the same fitted rows
             with open(shelf_file(path, "shelf-new-user-recs"), 'w') as out:
                 write_shelves(out, labels, *self._rank_fold_classes(rows, lists, self._class_csr(), self.shelves_k), self.shelf_count)
@@ -988,6 +1015,83 @@ class BPRMF(RecommenderModel):
         if self.diversify_theta <= 0:
             return
         self.evaluator.store_recommendation_diverse(*div_paths(path))
+
+    # ---- calibrated lists: greedy KL re-rank of each list's top-N pool toward the user's class mix (include/bprx.h, bprx_calibrate) --
+    CALIBRATE_CLASSES_MAX = 1024                                 # classes bprx_calibrate takes (BPRX_STYLES_MAX)
+
+    def _calibrate_args(self, k, pool, lam, alpha, classes=None):
+        """(kk, N, lambda, alpha, (class table int32 [I] on the device, C)) of a calibrated ranking, checked: k (None: top_k) and pool
+        (None: params.calibrate_pool, 100) cut to the catalogue, lam (None: params.calibrate, 0.5 where that is off), alpha (None:
+        params.calibrate_alpha, 0.01), classes (None: the run's table, item_classes(); with --item_classes styles the styles)."""
+        if not self.diverse:
+            raise NotImplementedError("%s: calibrated lists come from BPRMF, VBPR and GradFashion" % type(self).__name__)
+        k = self.evaluator.k if k is None else int(k)
+        if getattr(self.evaluator, "force_host", False) or k > 1024:
+            raise ValueError("--calibrate ranks on the device only (no force_host, top_k <= 1024): there is no host form")
+        pool = self.calibrate_pool if pool is None else int(pool)
+        lam = (self.calibrate_lambda or 0.5) if lam is None else float(lam)
+        alpha = self.calibrate_alpha if alpha is None else float(alpha)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError("calibrate: lambda lies in [0, 1] (got %s)" % lam)
+        if not 0.0 < alpha < 1.0:
+            raise ValueError("calibrate: alpha lies in (0, 1) (got %s)" % alpha)
+        if not 1 <= k <= pool <= 1024:
+            raise ValueError("calibrate: need 1 <= k <= pool <= 1024 (got k = %d, pool = %d)" % (k, pool))
+        I = self.num_items
+        return min(k, I), min(pool, I), lam, alpha, self._class_table(classes)
+
+    def _class_table(self, classes=None):
+        """(int32 device tensor [num_items], C) of `classes` (an int array [num_items], -1 = no class; None: the run's table): what
+        bprx_calibrate reads.  C = the largest class id + 1, at least 1 (the styles: params.styles); more than 1024 is a ValueError."""
+        styles = classes is None and isinstance(getattr(self.params, "item_classes", None), str) and self.params.item_classes == "styles"
+        cls = np.asarray(self.item_classes() if classes is None else classes).reshape(-1)
+        if cls.size != self.num_items or cls.dtype.kind not in "iu":
+            raise ValueError("calibrate: one integer class per item, [%d] (got %s %s)" % (self.num_items, cls.dtype, cls.shape))
+        if cls.size and cls.min() < -1:
+            raise ValueError("calibrate: a class id is >= 0, or -1 for no class (got %d)" % cls.min())
+        C = max(1, int(cls.max()) + 1 if cls.size else 1)
+        if styles and self.styles_S:
+            C = max(C, self.styles_S)
+        if C > self.CALIBRATE_CLASSES_MAX:
+            raise ValueError("calibrate: %d classes, the limit is %d" % (C, self.CALIBRATE_CLASSES_MAX))
+        return torch.as_tensor(np.ascontiguousarray(cls, dtype=np.int32), device=self.engine.device), C
+
+    def _fold_calibrate_args(self, k, calibrate, classes):
+        """recommend_new_users' `calibrate` as _calibrate_args returns it, checked."""
+        opts = dict(calibrate) if isinstance(calibrate, dict) else {"lam": calibrate}
+        return self._calibrate_args(k, opts.get("pool"), opts.get("lam"), opts.get("alpha"), classes)
+
+    def recommend_calibrated(self, users=None, k=None, pool=None, lam=None, alpha=None, classes=None):
+        """The k (default top_k) items of every user of `users` (None: all, in id order) picked from the user's top-`pool` (default
+        params.calibrate_pool, 100; training items masked) so that the list's class mix follows the mix of the user's training
+        items (Steck 2018): each pick maximises (1 - lam) rel - lam (the change of KL(p || q~) the pick makes), q~ = (1 - alpha) q
+        + alpha p.  classes: an int array [num_items], -1 = none (None: the run's table, item_classes()).  Returns numpy ids int64
+        [n, kk], vals fp32 [n, kk] (the model's scores), cls int64 [n, kk] (the picks' classes), gain fp32 [n, kk] (the KL each
+        pick removed at its step) and kl fp32 [n, 2] (KL(p || q~) of the plain top-kk and of the calibrated list), kk = min(k, I);
+        slots past a user's unmasked items hold -1 / 0 / -1 / 0.  The pools are ranking.rank_rows' lists (Engine.topk, K = pool),
+        the picks Engine.calibrate's through ranking.calibrate_rows, the histories the training CSR."""
+        kk, N, lam, alpha, (table, C) = self._calibrate_args(k, pool, lam, alpha, classes)
+        eng, ev = self.engine, self.evaluator
+        U = self.num_users
+        want = np.arange(U, dtype=np.int64) if users is None else np.asarray(users, dtype=np.int64).reshape(-1)
+        if want.size and (want.min() < 0 or want.max() >= U):
+            raise ValueError("recommend_calibrated: user ids lie in [0, %d)" % U)
+        ev._metrics_device_csr()
+        out = calibrated_zeros(want.size, kk)
+        for b0, b1, rows, local in wanted_blocks(want, U, ev.user_block):
+            pi, pv, _ = rank_rows(ev._topk(b0, b1), eng.score_block(b0, b1), N)
+            cal = lambda qi, qv, kq: eng.calibrate(qi, qv, ev._csr["train"], table, C, kq, lam, alpha, row0=b0)
+            res = calibrate_rows(cal, pi, pv, kk, eng.device)
+            for o, r in zip(out, res):
+                o[rows] = r[local]
+        return out
+
+    def _store_calibrated(self, path):
+        """params.calibrate = lambda > 0: cal-recs-* (rows 'u\ti\tscore\tclass\tgain', in list order) and cal-kl-* (rows
+        'u\tkl_plain\tkl_calibrated\thist_classed') next to the recs-* file at `path`."""
+        if self.calibrate_lambda <= 0:
+            return
+        self.evaluator.store_recommendation_calibrated(*cal_paths(path))
 
 
     # ---- "because you own X": the nearest owned items of a recommended one (include/bprx.h, bprx_because) ----------------------

@@ -512,10 +512,12 @@ def write_user_styles(out, labels, rows):
             out.write(head + str(s) + '\t' + str(c) + '\t' + str(np.float32(c) / np.float32(total)) + '\n')
 
 
-def _about(path, family, what):
-    """The files of RUN_FILES that are about the list file at `path` and whose kind starts with `family`, in the table's order."""
+def _about(path, family, what, table=None):
+    """The files of `table` (None: RUN_FILES) that are about the list file at `path` and whose kind starts with `family`, in the
+    table's order."""
     head, base, tail = _split_run_file(path)
-    out = tuple(head + kind + tail for kind, of in RUN_FILES.items() if base is not None and of == base and kind.startswith(family))
+    table = RUN_FILES if table is None else table
+    out = tuple(head + kind + tail for kind, of in table.items() if base is not None and of == base and kind.startswith(family))
     if not out:
         raise ValueError("%s: %r is no recs-* path" % (what, path))
     return out
@@ -537,6 +539,67 @@ def write_diverse(out, out_ild, labels, ids, vals, pen, ild):
                 break
             out.write(head + str(item) + '\t' + str(vals[r, q]) + '\t' + str(pen[r, q]) + '\n')
         out_ild.write(head + str(ild[r]) + '\n')
+
+
+# The files of a run whose lists are CALIBRATED (--calibrate: greedy KL re-rank toward the class mix of the user's history;
+# include/bprx.h, bprx_calibrate): cal-recs-* has the lists (rows 'label item score class gain'), cal-kl-* one row per list (rows
+# 'label kl_plain kl_calibrated hist_classed'); the value is the list file the file is about, as in RUN_FILES.
+CAL_FILES = {"cal-recs": "recs", "cal-kl": "recs", "cal-new-user-recs": "new-user-recs", "cal-new-user-kl": "new-user-recs"}
+
+
+def cal_paths(path):
+    """(cal-recs-*, cal-kl-*) next to the recs-* / best-recs-* / new-user-recs-* / best-new-user-recs-* file at `path`: 'cal-'
+    goes in front of the file's own 'recs-' / 'new-user-recs-' part, the kl file has 'kl-' where that part's 'recs-' is."""
+    return _about(path, "cal-", "cal_paths", CAL_FILES)
+
+
+def calibrated_zeros(n, kk):
+    """(ids int64 [n, kk], vals fp32 [n, kk], cls int64 [n, kk], gain fp32 [n, kk], kl fp32 [n, 2]) of zeros: what calibrate_rows'
+    blocks are put into."""
+    return (np.zeros((n, kk), np.int64), np.zeros((n, kk), np.float32), np.zeros((n, kk), np.int64), np.zeros((n, kk), np.float32),
+            np.zeros((n, 2), np.float32))
+
+
+def calibrate_rows(calibrate, ids, vals, k, device):
+    """The calibrated lists of a block of pools, the twin of diversify_rows: `ids` int64 [n, N] / `vals` fp32 [n, N] are what
+    rank_rows returned for a pool of N (a masked entry keeps its -inf and is no candidate).  They are uploaded once,
+    calibrate(pool_idx int32, pool_val, kk) is the entry (Engine.calibrate with its histories, class table, lambda and alpha bound)
+    and returns the device (idx, val, cls, gain, kl).  Returns numpy ids int64 [n, kk], vals fp32 [n, kk], cls int64 [n, kk], gain
+    fp32 [n, kk] and kl fp32 [n, 2], kk = min(k, N); slots past a pool's candidates hold -1 / 0 / -1 / 0."""
+    n, N = ids.shape
+    kk = min(int(k), N)
+    if n == 0 or kk == 0:
+        return calibrated_zeros(n, kk)
+    pool_idx = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32), device=device)
+    pool_val = torch.as_tensor(np.ascontiguousarray(vals, dtype=np.float32), device=device)
+    idx, val, cls, gain, kl = calibrate(pool_idx, pool_val, kk)
+    return (idx.cpu().numpy().astype(np.int64), val.cpu().numpy(), cls.cpu().numpy().astype(np.int64), gain.cpu().numpy(),
+            kl.cpu().numpy())
+
+
+def hist_classed(lists, item_class):
+    """H of bprx_calibrate for every list of item ids as a run hands it over, every id once (the training CSR and the new users'
+    histories are deduplicated): the number of its distinct ids that lie in the class table and have a class, int64 [len(lists)]."""
+    item_class = np.asarray(item_class, dtype=np.int64)
+    out = np.zeros(len(lists), np.int64)
+    for r, l in enumerate(lists):
+        it = np.unique(np.asarray(l, dtype=np.int64).reshape(-1))
+        it = it[(it >= 0) & (it < item_class.size)]
+        out[r] = int((item_class[it] >= 0).sum())
+    return out
+
+
+def write_calibrated(out, out_kl, labels, ids, vals, cls, gain, kl, hist_classed):
+    """One row 'label\tid\tval\tclass\tgain' per pick, list by list in selection order (empty slots, id < 0, are left out), into
+    `out`; one row 'label\tkl_plain\tkl_calibrated\thist_classed' per list into `out_kl`.  Fields are formatted as write_ranked
+    formats them."""
+    for r, label in enumerate(labels):
+        head = str(label) + '\t'
+        for q, item in enumerate(ids[r]):
+            if item < 0:
+                break
+            out.write(head + str(item) + '\t' + str(vals[r, q]) + '\t' + str(cls[r, q]) + '\t' + str(gain[r, q]) + '\n')
+        out_kl.write(head + str(kl[r, 0]) + '\t' + str(kl[r, 1]) + '\t' + str(hist_classed[r]) + '\n')
 
 
 def because_paths(path):

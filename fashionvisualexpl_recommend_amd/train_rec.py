@@ -29,6 +29,9 @@ with --new_users shelf-new-user-recs-* / cap-new-user-recs-*.
 --styles S [--style_iters T] [--style_top R] (bprmf, vbpr, grad_fashion) clusters the item space of --similar_space into S styles
 (spherical k-means) and writes styles-*, style-items-* and user-styles-* next to recs-*, with --new_items also new-styles-*;
 --item_classes styles makes the styles the classes of --shelves / --class_cap.
+--calibrate LAMBDA with --item_classes (bprmf, vbpr, grad_fashion) writes cal-recs-* / cal-kl-* files next to recs-*: every user's
+top_k picked from the user's top --calibrate_pool so that the list's class mix follows the mix of the user's training items
+(greedy KL re-rank, include/bprx.h, bprx_calibrate), and with --new_users cal-new-user-recs-* / cal-new-user-kl-*.
 --warm_items PATH (bprmf, vbpr, grad_fashion) fits Gi / Bi rows for new items from their first buyers (rows `row<TAB>user`; vbpr and
 grad_fashion: rows of the --new_items table) and writes warm-recs-* / best-warm-recs-* files, with --audience K also warm-audience-*.
 Run as `python -m fashionvisualexpl_recommend_amd.train_rec --rec bprmf --dataset <name> ...`.
@@ -37,6 +40,8 @@ import argparse
 import os
 
 from . import configs
+
+CALIBRATE_CLASSES_MAX = 1024                                  # classes --calibrate takes (bprx_calibrate's limit)
 
 _last_model = None
 
@@ -121,6 +126,18 @@ def parse_args(argv=None):
                              "with --new_users also div-new-user-recs-* / div-new-user-ild-*.  THETA in [0, 1]; 0 = off")
     parser.add_argument('--diversify_pool', type=int, default=100, metavar='N',
                         help="--diversify: candidates per user the lists are picked from, top_k <= N <= 1024")
+    parser.add_argument('--calibrate', type=float, default=0.0, metavar='LAMBDA',
+                        help="bprmf, vbpr, grad_fashion, with --item_classes: also write cal-recs-* / best-cal-recs-* files next to "
+                             "recs-* / best-recs-* with every user's top_k picked from the user's top --calibrate_pool so that the "
+                             "list's class mix follows the mix of the user's training items (Steck 2018): each pick maximises "
+                             "(1 - LAMBDA) relevance - LAMBDA (the change of KL(history mix || list mix) it makes); rows `u i score "
+                             "class gain` in list order, and cal-kl-* / best-cal-kl-* with one row `u kl_plain kl_calibrated "
+                             "hist_classed` per user; with --new_users also cal-new-user-recs-* / cal-new-user-kl-*.  LAMBDA in "
+                             "[0, 1]; 0 = off")
+    parser.add_argument('--calibrate_pool', type=int, default=100, metavar='N',
+                        help="--calibrate: candidates per user the lists are picked from, top_k <= N <= 1024")
+    parser.add_argument('--calibrate_alpha', type=float, default=0.01, metavar='ALPHA',
+                        help="--calibrate: the list's class mix is smoothed to (1 - ALPHA) list + ALPHA history; in (0, 1)")
     parser.add_argument('--because', type=int, default=0, metavar='L',
                         help="bprmf, vbpr, grad_fashion: also write because-* / best-because-* files next to recs-* / best-recs-*: "
                              "for every (u, i) of every user's top_k list the L (1..32) items of u's training list nearest to i by "
@@ -351,6 +368,16 @@ def parse_args(argv=None):
         parser.error("--shelf_count needs --shelves K")
     if args.class_cap < 0:
         parser.error("--class_cap takes M >= 1, 0 = off (got %s)" % args.class_cap)
+    if not 0.0 <= args.calibrate <= 1.0:                      # (NaN fails both comparisons)
+        parser.error("--calibrate takes lambda in [0, 1], 0 = off (got %s)" % args.calibrate)
+    if args.calibrate > 0 and not args.top_k <= args.calibrate_pool <= 1024:
+        parser.error("--calibrate_pool takes top_k (%d) .. 1024 (got %s)" % (args.top_k, args.calibrate_pool))
+    if not 0.0 < args.calibrate_alpha < 1.0:
+        parser.error("--calibrate_alpha takes alpha in (0, 1) (got %s)" % args.calibrate_alpha)
+    if args.calibrate > 0 and args.rec not in ('bprmf', 'vbpr', 'grad_fashion'):
+        parser.error("--calibrate needs --rec bprmf, vbpr or grad_fashion (got --rec %s)" % args.rec)
+    if args.calibrate > 0 and args.item_classes is None:
+        parser.error("--calibrate needs --item_classes PATH (or --item_classes dataset / styles)")
     if args.shelves != 0 or args.class_cap != 0 or args.item_classes is not None:
         if args.rec not in ('bprmf', 'vbpr', 'grad_fashion'):
             parser.error("--item_classes / --shelves / --class_cap need --rec bprmf, vbpr or grad_fashion (got --rec %s)" % args.rec)
@@ -358,9 +385,12 @@ def parse_args(argv=None):
             parser.error("--shelves / --class_cap need --item_classes PATH (or --item_classes dataset)")
         if args.item_classes not in ('dataset', 'styles'):
             try:
-                read_item_classes(args.item_classes)
+                table = read_item_classes(args.item_classes)
             except (OSError, ValueError) as e:
                 parser.error("--item_classes: %s" % e)
+            if args.calibrate > 0 and table.size and int(table.max()) + 1 > CALIBRATE_CLASSES_MAX:
+                parser.error("--calibrate takes at most %d classes (--item_classes has %d)"
+                             % (CALIBRATE_CLASSES_MAX, int(table.max()) + 1))
     if args.hard_negatives != 0 and not 2 <= args.hard_negatives <= 16:
         parser.error("--hard_negatives takes 0 (off) or 2 .. 16 (got %s)" % args.hard_negatives)
     if args.hard_negatives != 0 and args.sampler != 'philox':
@@ -560,6 +590,10 @@ def train(argv=None):
         raise NotImplementedError('--similar_items runs on one GPU (the sharded drivers write no sim-* files): use --world_size 1')
     if args.diversify > 0 and int(args.world_size) > 1:
         raise NotImplementedError('--diversify runs on one GPU (the sharded drivers write no div-* files): use --world_size 1')
+    if args.calibrate > 0 and int(args.world_size) > 1:
+        raise NotImplementedError('--calibrate runs on one GPU (the sharded drivers write no cal-* files): use --world_size 1')
+    if args.calibrate > 0 and args.top_k > 1024:
+        raise ValueError('--calibrate ranks on the device only (top_k <= 1024): there is no host form')
     if args.because != 0 and int(args.world_size) > 1:
         raise NotImplementedError('--because runs on one GPU (the sharded drivers write no because-* files): use --world_size 1')
     if args.influence != 0 and int(args.world_size) > 1:
@@ -623,6 +657,9 @@ def train(argv=None):
         data = DataLoader(params=args)
         check_audience_items(args, data.num_items)
         class_table = check_item_classes(args, data.num_items)
+        if args.calibrate > 0 and not isinstance(class_table, str) and int(class_table.max()) + 1 > CALIBRATE_CLASSES_MAX:
+            raise ValueError('--calibrate takes at most %d classes (--item_classes has %d)'
+                             % (CALIBRATE_CLASSES_MAX, int(class_table.max()) + 1))
         if args.warm_items is not None and any(u >= data.num_users for who in read_warm_items(args.warm_items) for u in who):
             raise ValueError('--warm_items: a buyer is outside the %d users of the dataset' % data.num_users)
         if args.af_warm_items is not None and any(u >= data.num_users for who in read_warm_items(args.af_warm_items) for u in who):

@@ -168,7 +168,8 @@ BPRX_API int bprx_sync_adam(bprx_handle *h, void *stream);
      bprx_topk, bprx_topk_lists, bprx_topk_rows_masked, bprx_topk_classes, bprx_eval_*, bprx_tables_dirty, bprx_set_adam_step, bprx_clear_*_grad, bprx_sync_check,
      bprx_pack_user_msg, the bind calls                               any                 -             -     -      -
    Not behind the gate: bprx_step and bprx_step_begin[_sparse] (a step may carry the update), the samplers, the profile calls, bprx_last_error, bprx_set_hyper,
-   bprx_set_loss_lag, the getters, bprx_settle and bprx_dense_pending. */
+   bprx_set_loss_lag, the getters, bprx_settle and bprx_dense_pending; bprx_calibrate (it reads pools, histories and a class table of
+   the caller's, no state of the handle). */
 BPRX_API int bprx_settle(bprx_handle *h, void *stream);
 BPRX_API int bprx_dense_pending(const bprx_handle *h);
 BPRX_API int bprx_set_loss_lag(bprx_handle *h, int on);
@@ -523,6 +524,42 @@ BPRX_API int bprx_audience_warm_block(bprx_handle *h, const float *Gi_rows, cons
 BPRX_API int bprx_diversify(bprx_handle *h, int32_t space, const float *rn_items, int64_t n, int32_t N, const int32_t *pool_idx,
                             const float *pool_val, int32_t K, float theta, int32_t *idx, float *val, float *pen, float *ild,
                             void *stream);
+
+/* ---- calibrated lists: greedy KL re-rank of a top-N pool toward the class mix of the user's own history --------------------------
+   Calibration (Steck, "Calibrated Recommendations", RecSys 2018) with one-hot classes: each of n lists is picked greedily from its
+   pool so that (1 - lambda) relevance - lambda KL(p || q~) grows the most, p the class shares of the user's history, q the class
+   shares of the list so far and q~ = (1 - alpha) q + alpha p.
+   The pool of list r: pool_idx int32 [n, N] / pool_val fp32 [n, N] in pool order (bprx_topk's output with K = N); an entry with
+   pool_idx < 0 or pool_val == -inf is no candidate, M = the number of candidates.  The class table: item_class int32 [width]
+   (device), -1 = no class, otherwise in [0, C).  The history of list r: hist_items[hist_ptr[row0 + r] .. hist_ptr[row0 + r + 1])
+   (hist_ptr int64, device; hist_ptr == NULL: every history is empty and hist_items is not read).
+       cnt_c     = the number of history entries of class c (an id outside [0, width) or a classless item is not counted; a repeated
+                   id counts every time); H = sum of cnt_c, p_c = cnt_c / H
+       rel_c     = (v_c - v_min) / (v_max - v_min) over the candidates, 0 for a flat pool: bprx_diversify's
+       den_g(m)  = (1 - alpha) m / L + alpha p_g                                  with t picks made, n_g of them of class g, L = t + 1
+       delta_g   = p_g log(den_g(n_g) / den_g(n_g + 1))                           <= 0; 0 when p_g = 0 or the candidate has no class
+       obj_c     = (1 - lambda) rel_c - lambda delta_class(c)
+   (the terms of the KL that do not depend on the candidate cancel out of the arg-max: one number per class and step.)  Every
+   operation is rounded once in fp32, nothing is fused, log is logf.  At each of T = min(K, M) steps the unselected candidate with
+   the largest obj_c is selected; values compare as floats (-0 == +0), equal values go to the lower pool position.  lambda = 0
+   returns the pool's first T candidates unchanged; with H = 0 every delta is 0 and the same holds.
+   Outputs per list r: idx int32 [K] the picks' pool ids in selection order, val fp32 [K] their pool scores (bits unchanged), cls
+   int32 [K] their classes (-1: none), gain fp32 [K] -delta of the pick at its step (>= 0); slots past T hold -1 / 0.0f / -1 /
+   0.0f.  kl fp32 [n, 2] (may be NULL): kl[r][0] = KL(p || q~) of the pool's first T candidates (the plain list), kl[r][1] of the
+   calibrated list, KL = sum over the classes with p_c > 0 of p_c log(p_c / den_c(n_c)) at L = T, summed in an order that depends
+   on C only (no float atomics); both are 0.0 when H = 0 or T = 0.  Without kl the other outputs have the same bits.
+   A list's outputs depend on its own pool, its history and the class table only: not on n, its position in the call or row0.
+   1 <= K <= N <= 1024, 1 <= C <= 1024, 0 <= lambda <= 1, 0 < alpha < 1, width >= 1, 0 <= n < 2^31, row0 >= 0; a value out of range
+   or NaN, or a NULL pointer with n > 0 (kl and hist_ptr excepted; hist_items with hist_ptr): BPRX_E_INVALID, the message starts
+   with "calibrate".  n == 0: BPRX_OK, nothing is launched.  A candidate's id >= width, or an item_class value outside [-1, C) at a
+   candidate or a history entry, is treated as classless, never used as an index, and reported by bprx_sync_check (BPRX_E_RANGE);
+   the returned id is the pool's own.
+   The call reads no model table: any handle, bound or not, of any model.  It is not behind the gate: it settles nothing, changes
+   no state and allocates nothing; after an error the handle stays usable. */
+BPRX_API int bprx_calibrate(bprx_handle *h, int64_t n, int32_t N, const int32_t *pool_idx, const float *pool_val, int64_t row0,
+                            const int64_t *hist_ptr, const int32_t *hist_items, const int32_t *item_class, int32_t width, int32_t C,
+                            int32_t K, float lambda, float alpha, int32_t *idx, float *val, int32_t *cls, float *gain,
+                            float *kl /* may be NULL */, void *stream);
 
 /* ---- BPRMF, VBPR and GradFashion: "because you own X", the nearest owned items of every entry of a list ---------------------
    For each entry of each of n lists of K slots, the L items of that list's history that are nearest to it by cosine in the
